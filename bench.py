@@ -17,13 +17,18 @@ process, before this process touches torch or the GPU) and relays rank 0's JSON 
 torch.distributed.run it is one of the ranks.  `--single-process` drives the N GPUs from ONE process
 instead (cafe_create_sharded: a host thread and stream per device, ncclCommInitAll).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (fp64 MFMA, from HIP
-events the library records around every K2 launch in the timed region) and, at N = 1, `cpu_baseline`
-(the CPU restatement of the reference algorithm timed on this host's cores on a bounded sample),
-`parity_sample` (the CPU-pruned families against the GPU's values for the same families, and the
-reference-algorithm matrices against the GPU's), `one_column_per_family` (the same call without the
-subtree-level column sharing: the data-independent figure) and `other_configs` (BASELINE configs 2, 3
-on the mammals fixture and config 5's shape).
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+A plain run sets up, warms up, times --steps steps and prints the line; at N = 1 it carries
+`roofline` (fp64 MFMA, from HIP events the library records around every K2 launch in the timed
+region).  `--full` adds what takes runs of its own:
+at N > 1 (and --emulate-shard) the roofline from one more, profiled, step behind the timed region, and
+at N = 1 `cpu_baseline` (the CPU restatement of the reference algorithm timed on this host's cores on a
+bounded sample), `parity_sample` (the CPU-pruned families against the GPU's values for the same
+families, and the reference-algorithm matrices against the GPU's), `one_column_per_family` (the same
+call without the subtree-level column sharing: the data-independent figure), `every_k_tile`,
+`one_op_per_launch` and `other_configs` (BASELINE configs 2, 3 on the mammals fixture and config 5's
+shape).  `--dump-outputs DIR` writes what the last timed step returned (-lnL and the per-family
+results) as .npy files, so that two builds can be compared value for value on the same seeded inputs.
 """
 import argparse
 import json
@@ -39,21 +44,26 @@ if ROOT not in sys.path:
 
 FP64_MFMA_PEAK_TFLOPS = 78.6      # AMD MI355X datasheet: FP64 matrix = FP64 vector = 78.6 TFLOP/s
 PARITY_TOL = 1e-10                # per-family values against the CPU restatement (BASELINE asks 1e-6 on -lnL)
+DUMP_BYTES = 64 << 20             # --dump-outputs: at most this much in all
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (scorer calls)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline and parity sample, the variants of the headline call, "
+                    "other configs (N = 1) and the per-launch roofline of a rank (N > 1, --emulate-shard); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write -lnL and the per-family results of the last timed step "
+                    "(of the families rank 0 holds) to DIR/<name>.npy, float64")
     ap.add_argument("--families", type=int, default=50000)
     ap.add_argument("--taxa", type=int, default=100)
     ap.add_argument("--max-count", type=int, default=600)
     ap.add_argument("--categories", type=int, default=8)
     ap.add_argument("--lam", type=float, default=0.002)
     ap.add_argument("--alpha", type=float, default=2.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip one_column_per_family and other_configs (N = 1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and the parity samples")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip one_column_per_family and other_configs (N = 1 only)")
     ap.add_argument("--single-process", action="store_true", help="N > 1: one process drives all GPUs (cafe_create_sharded)")
     ap.add_argument("--emulate-shard", default="", help="R/W: rehearsal on one GPU of what rank R of W would run (no collective)")
     ap.add_argument("--force-comm", action="store_true", help="diagnostic, under a launcher with ONE rank: take the N > 1 path (process group, "
@@ -61,7 +71,7 @@ def parse():
     ap.add_argument("--shard-times", default="", help="with --emulate-shard: ms per shard measured under the default plan (comma list; "
                     "several steps separated by ';': each measured under the plan the steps before it give): use the plan rebalanced by "
                     "them, as the ranks of an N > 1 run do after their first calls")
-    ap.add_argument("--rebalance-steps", type=int, default=1, help="N > 1: steps of measured rebalancing during set-up (a second step measured no better: the residual 2 % is run-to-run noise)")
+    ap.add_argument("--rebalance-steps", type=int, default=1, help="N > 1: steps of measured rebalancing during set-up (a second step measured no better: the residual 2 %% is run-to-run noise)")
     ap.add_argument("--no-rebalance", dest="rebalance", action="store_false", help="N > 1: keep the predicted shard plan.  Default: one step "
                     "of measured rebalancing during set-up (every rank times a few calls of its predicted shard, the plan is corrected by the "
                     "gathered times)")
@@ -73,7 +83,10 @@ def parse():
     ap.add_argument("--cpu-matrices", type=int, default=3, help="matrices built by the O(N^3) reference algorithm in the CPU sample")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU sample (0 = the host CPU share)")
     ap.add_argument("--cpu-families", type=int, default=256, help="families pruned in the CPU sample (SURVEY 8d: 256)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(args):
@@ -173,6 +186,27 @@ def timed_calls(fn, reps):
     for _ in range(reps):
         v = fn()
     return (time.perf_counter() - t0) / reps, v
+
+
+def dump_outputs(path, value, owner, K):
+    """--dump-outputs: what the last timed step returned to its caller -- -lnL, and the per-family results of the families
+    `owner` holds (cafe_family_results of that very call) -- as float64 .npy files.  Above DUMP_BYTES the per-family arrays
+    keep a fixed, seeded sample of the families, listed in family_index.npy."""
+    import numpy as np
+    out = {"neg_lnl": np.array([value], dtype=np.float64)}
+    if value != float("inf"):                         # a rejected call (+inf) leaves no per-family results
+        fam = {k: np.asarray(v, dtype=np.float64) for k, v in owner.family_results(K if K > 1 else 0).items()}
+        F = len(fam["family_lnl"])
+        row = sum(a.nbytes for a in fam.values()) // F
+        budget = DUMP_BYTES - (1 << 20)               # (headers and neg_lnl)
+        if F * row > budget:
+            sel = np.sort(np.random.default_rng(20251004).choice(F, budget // (row + 8), replace=False))
+            fam = {k: a[sel] for k, a in fam.items()}
+            fam["family_index"] = sel.astype(np.float64)
+        out.update(fam)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def other_configs(args):
@@ -425,16 +459,20 @@ def main():
             account()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, value, sharded if sharded is not None else ctx, K)
+    profiled = live_events or args.full               # the profiled step of a rank is a run of its own: --full only
     n_prof = args.steps
-    if not live_events:
+    if not live_events and profiled:
         ctx.set_profiling(True)
         step()
         account()
         n_prof = 1
         fence()
-    # what the K2 launches of a step really executed (the same every step: same parameters); counted once, outside the timing
-    flops_executed = ctx.executed_flops() * n_prof
-    flops_tile_ranges = ctx.tile_range_flops() * n_prof
+    if profiled:
+        # what the K2 launches of a step really executed (the same every step: same parameters); counted once, outside the timing
+        flops_executed = ctx.executed_flops() * n_prof
+        flops_tile_ranges = ctx.tile_range_flops() * n_prof
     if dist_on:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if native_comm else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -443,17 +481,6 @@ def main():
     rc = 0
     if rank == 0:
         st = ctx.stats()
-        achieved = flops_executed / (ms_gemm * 1e-3) / 1e12 if ms_gemm > 0 else 0.0
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tpath):                     # PMC passes of this same workload (profiles/)
-            try:
-                t = json.load(open(tpath))
-                if t.get("workload") == {"families": args.families, "taxa": args.taxa, "max_count": args.max_count,
-                                         "categories": args.categories, "gpus": n_gpus}:
-                    traffic = t.get("prune_gemm_hbm_bytes_per_launch")
-            except Exception:
-                traffic = None
         out = {
             "metric": "gene-family likelihoods/sec per optimizer_scorer call",
             "value": F * args.steps / elapsed, "unit": "families/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
@@ -467,31 +494,43 @@ def main():
                                          "issued by torch.distributed (cafe_comm_attach failed)" if native_comm else "on the host (gloo rehearsal)",
                                          "one process, a host thread per GPU" if sharded is not None else "one process per GPU")},
             "neg_lnl": value,
-            "roofline": {"bound": "mfma", "achieved": achieved, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / FP64_MFMA_PEAK_TFLOPS, "traffic": traffic,
-                         "kernel": "prune_gemm_kernel", "launches_per_step": launches // max(1, n_prof),
-                         "measured": "HIP events on every K2 dispatch of the timed steps" if live_events
-                                     else "HIP events on every K2 dispatch of one step behind the timed region (rank 0's shard)",
-                         "avg_launch_ms": ms_gemm / max(1, launches), "flops_per_launch": flops_executed / max(1, launches),
-                         # flops_per_launch = the flops of the MFMAs the launches ISSUE: columns = distinct subtree patterns, K
-                         # tiles = those inside a row tile's non-zero extent, each 16-row block of the tile over its own extent
-                         # only (DESIGN.md sections 2, 3).  Then: every block over its tile's whole K range (the count rounds 2
-                         # and 3a quoted `frac` on: the kernel issued those MFMAs then), every K tile of the distinct columns,
-                         # one column per family at every node (SURVEY 8d's per-family figure):
-                         "flops_per_launch_whole_tile_ranges": flops_tile_ranges / max(1, launches),
-                         "frac_over_whole_tile_ranges": flops_tile_ranges / (ms_gemm * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS if ms_gemm > 0 else None,
-                         "flops_per_launch_all_k_tiles": flops / max(1, launches),
-                         "flops_per_launch_one_column_per_family": flops_fam / max(1, launches)},
-            "phases_ms_per_step": {"bd_matrix_build": ms_mat / n_prof, "prune_total": ms_prune / n_prof,
-                                   "prune_gemm": ms_gemm / n_prof},
-            "n_matrices": st["n_matrices"],
         }
-        if n_gpus > 1:
-            out["roofline"]["note"] = "rank 0's shard"
+        if profiled:
+            achieved = flops_executed / (ms_gemm * 1e-3) / 1e12 if ms_gemm > 0 else 0.0
+            traffic = None
+            tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(tpath):                 # PMC passes of this same workload (profiles/)
+                try:
+                    t = json.load(open(tpath))
+                    if t.get("workload") == {"families": args.families, "taxa": args.taxa, "max_count": args.max_count,
+                                             "categories": args.categories, "gpus": n_gpus}:
+                        traffic = t.get("prune_gemm_hbm_bytes_per_launch")
+                except Exception:
+                    traffic = None
+            out["roofline"] = {"bound": "mfma", "achieved": achieved, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                               "frac": achieved / FP64_MFMA_PEAK_TFLOPS, "traffic": traffic,
+                               "kernel": "prune_gemm_kernel", "launches_per_step": launches // max(1, n_prof),
+                               "measured": "HIP events on every K2 dispatch of the timed steps" if live_events
+                                           else "HIP events on every K2 dispatch of one step behind the timed region (rank 0's shard)",
+                               "avg_launch_ms": ms_gemm / max(1, launches), "flops_per_launch": flops_executed / max(1, launches),
+                               # flops_per_launch = the flops of the MFMAs the launches ISSUE: columns = distinct subtree patterns, K
+                               # tiles = those inside a row tile's non-zero extent, each 16-row block of the tile over its own extent
+                               # only (DESIGN.md sections 2, 3).  Then: every block over its tile's whole K range (the count rounds 2
+                               # and 3a quoted `frac` on: the kernel issued those MFMAs then), every K tile of the distinct columns,
+                               # one column per family at every node (SURVEY 8d's per-family figure):
+                               "flops_per_launch_whole_tile_ranges": flops_tile_ranges / max(1, launches),
+                               "frac_over_whole_tile_ranges": flops_tile_ranges / (ms_gemm * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS if ms_gemm > 0 else None,
+                               "flops_per_launch_all_k_tiles": flops / max(1, launches),
+                               "flops_per_launch_one_column_per_family": flops_fam / max(1, launches)}
+            out["phases_ms_per_step"] = {"bd_matrix_build": ms_mat / n_prof, "prune_total": ms_prune / n_prof,
+                                         "prune_gemm": ms_gemm / n_prof}
+            if n_gpus > 1:
+                out["roofline"]["note"] = "rank 0's shard"
+        out["n_matrices"] = st["n_matrices"]
         if dist_on or n_gpus > 1 or args.emulate_shard:
             out["config"]["shard_plan"] = plan_note or "predicted device time (cafe_shard_plan)"
         if not dist_on and sharded is None and not args.emulate_shard:
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 res = ctx.family_results(K if K > 1 else 0)
                 res["matrix"] = ctx.matrix
                 out["cpu_baseline"], out["parity_sample"] = cpu_baseline(pb, pr, args, st["n_matrices"], res)
@@ -500,7 +539,7 @@ def main():
                     print("bench.py: PARITY FAILURE at full size: %r" % out["parity_sample"], file=sys.stderr)
                     rc = 3
             ctx.close()
-            if not args.no_extras:
+            if args.full and not args.no_extras:
                 # the same call with one column per family at every node (no subtree-level sharing): data-independent
                 plain = capi.Context(pb, max_categories=max(1, K), device=device, subtree_dedup=False)
                 plain.set_profiling(True)
