@@ -134,7 +134,10 @@ typedef struct cafe_stats {
     double gemm_flops_dense;         /* = gemm_flops */
 } cafe_stats;
 
-/* NULL on failure; err (optional, errlen bytes) receives the reason. */
+/* NULL on failure; err (optional, errlen bytes) receives the reason.
+ * Supported sizes: matrix order N = max(max_family_size, max_root_family_size) + 1 <= 2048.  Under the reference's size
+ * rules (user_data.cpp:45-46) that is a largest family count of at most 1637 (N = 2047); 1638 gives N = 2049, which
+ * cafe_create rejects with CAFE_ERR_ARGUMENT ("matrix order ... exceeds 2048").  The reference has no such limit. */
 cafe_ctx* cafe_create(const cafe_problem* problem, char* err, size_t errlen);
 void      cafe_destroy(cafe_ctx* ctx);
 const char* cafe_last_error(const cafe_ctx* ctx);

@@ -14,7 +14,7 @@ bad = 0
 for case in range(n_cases):
     n_taxa = int(rng.choice([4, 7, 16, 33, 60]))
     n_fam = int(rng.choice([130, 700, 2500, 6000]))
-    max_count = int(rng.choice([230, 300, 420, 600]))
+    max_count = int(rng.choice([230, 300, 420, 600, 900, 1300]))   # (900, 1300: matrix orders 1126, 1626 -- K1 at 20 and 28 columns per lane)
     n_dev = int(rng.choice([0, 0, 3]))
     two = bool(rng.integers(0, 2)) and n_taxa >= 16
     K = int(rng.choice([1, 2, 4, 8]))
