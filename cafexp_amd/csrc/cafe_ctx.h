@@ -86,6 +86,7 @@ struct cafe_ctx {
     std::vector<int> parent, lam_idx, leaf_taxon;
     std::vector<double> blen;
     std::vector<std::vector<int>> children;
+    std::vector<std::vector<int>> inner, leaves;    // [n_nodes] interior / leaf children of a node, in child order
     int64_t F_all = 0, F_uniq = 0, Fp = 0;
     std::vector<int64_t> ref_of;            // family -> unique column
     std::vector<double> weights;
@@ -114,6 +115,7 @@ struct cafe_ctx {
     std::vector<char> edge_identity;         // [n_nodes] interior child whose columns are its parent's, in order
     std::vector<int32_t*> d_edge_map;        // [n_nodes] interior child: its column for every column of the parent
     std::vector<int32_t*> d_leaf_cnt;        // [n_nodes] interior parent: [its leaf children][its columns] observed counts
+    std::vector<std::vector<int32_t>> h_edge_map, h_leaf_cnt;    // host copies (empty: none) until cafe_create uploads them
     std::vector<int> leaf_rank;              // [n_nodes] leaf: its row in the parent's d_leaf_cnt table
     int n_panels = 0, root_panel = -1;
 
@@ -249,6 +251,20 @@ void set_err(cafe_ctx* c, const char* fmt, ...);
             return CAFE_ERR_DEVICE;                                                         \
         }                                                                                   \
     } while (0)
+
+// Columns of node v's panel (or of its factor) in a chunk `cols` wide: its distinct subtree patterns when the schedule
+// de-duplicates subtrees, else the chunk's
+inline int64_t panel_cols(bool dedup, const cafe_ctx* c, int v, int64_t cols) { return dedup ? c->pat_cols[v] : cols; }
+inline int64_t panel_cols(const cafe_ctx* c, int v, int64_t cols) { return panel_cols(c->subtree_dedup, c, v, cols); }
+
+// Host planner of cafe_create (cafe_schedule.hip): no HIP call, no environment; in the order cafe_create runs them
+void plan_patterns(cafe_ctx* c, const cafe_problem* p, const std::vector<int64_t>& uniq);
+// commits the chosen schedule (ops, panels, chunk width, subtree_dedup, grouped); returns the arena's size in doubles
+size_t plan_schedule(cafe_ctx* c, bool dedup, bool try_grouped, size_t budget, int64_t desc_cols);
+std::vector<int> plan_extent_levels(cafe_ctx* c, bool matrix_extents);
+size_t plan_leaf_transposes(cafe_ctx* c, double lt_min, size_t free_bytes, std::vector<int>& lt_of_pair);
+void group_launches(cafe_ctx* c);
+void dump_schedule(const cafe_ctx* c);
 
 bool lambdas_valid(const cafe_ctx* c, const double* lam);
 // One slot per distinct quantized (lambda * multiplier, t) and layout (matrix_cache.h:42-61), parameters uploaded on

@@ -1,4 +1,4 @@
-// Host side of the C ABI (include/cafe_mi355x.h): context, schedule, per-call enqueue.
+// Host side of the C ABI (include/cafe_mi355x.h): context, per-call enqueue (the schedule's planner: cafe_schedule.hip).
 //
 // What of the reference this replaces, per scorer call:
 //   base_model::infer_family_likelihoods   src/base_model.cpp:53-112
@@ -43,250 +43,6 @@ void set_err(cafe_ctx* c, const char* fmt, ...) {
 
 namespace {
 
-// Sethi-Ullman style need: panels live while evaluating node v (leaves need none).
-int panel_need(const cafe_ctx* c, int v, std::vector<int>& need) {
-    std::vector<int> kid;
-    for (int u : c->children[v])
-        if (c->leaf_taxon[u] < 0) kid.push_back(panel_need(c, u, need));
-    std::sort(kid.begin(), kid.end(), std::greater<int>());
-    int n = (int)kid.size() + 1;
-    for (size_t i = 0; i < kid.size(); ++i) n = std::max(n, (int)i + kid[i]);
-    need[v] = n;
-    return n;
-}
-
-struct PanelAlloc {
-    bool reuse = true;          // false: every panel gets an id of its own (grouped schedule; the arena is planned afterwards)
-    std::vector<int> free_list;
-    int high = 0;
-    int get() {
-        if (reuse && !free_list.empty()) { int p = free_list.back(); free_list.pop_back(); return p; }
-        return high++;
-    }
-    void put(int p) { if (reuse) free_list.push_back(p); }
-};
-
-int emit_node(cafe_ctx* c, int v, const std::vector<int>& need, PanelAlloc& pa) {
-    std::vector<int> inner, leaves;
-    for (int u : c->children[v]) (c->leaf_taxon[u] < 0 ? inner : leaves).push_back(u);
-    std::vector<int> order = inner;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return need[x] > need[y]; });
-    std::map<int, int> panel_of;
-    for (size_t idx = 0; idx < order.size(); ++idx) panel_of[order[idx]] = emit_node(c, order[idx], need, pa);
-    const int dst = pa.get();
-    bool init = false;
-    // A parent with interior children folds (up to kMaxLeafPerOp of) its leaf children into the epilogue of
-    // the first GEMM; a parent with leaf children only (a cherry) is a pure gather.  Extra leaves gather-multiply.
-    // (one leaf, without an error model or with a 3-tap one: the specialised epilogues of prune_gemm.hip)
-    // A child with fewer distinct columns than its parent (subtree-level de-duplication) first gets its factor
-    // P . L over ITS columns in a scratch panel, which a combine pass spreads over the parent's columns.
-    const bool first_direct = !inner.empty() && (!c->subtree_dedup || c->edge_identity[inner[0]]);
-    size_t fused = (!first_direct || leaves.empty() || (c->n_dev != 0 && c->n_dev != 3)) ? 0 : 1;
-    std::vector<std::pair<int, int>> factors;             // (child, scratch panel) waiting to be assembled
-    auto is_direct = [&](int u) { return !c->subtree_dedup || c->edge_identity[u]; };
-    if (inner.size() == 2 && leaves.empty() && is_direct(inner[0]) != is_direct(inner[1])) {
-        // one child shares the parent's columns, the other has fewer: the smaller one's factor GEMM runs first over ITS
-        // columns, the other's GEMM then writes the parent's panel and multiplies the gathered factor in (the product
-        // of two numbers: the same bits whichever child comes first)
-        const int big = is_direct(inner[0]) ? inner[0] : inner[1], small = big == inner[0] ? inner[1] : inner[0];
-        const int scratch = pa.get();
-        Op f{};
-        f.type = 1; f.parent = v; f.src_panel = panel_of[small]; f.child = small; f.to_root = (v == c->root);
-        f.dst_panel = scratch; f.mode = 0; f.to_factor = true;
-        c->ops.push_back(f);
-        Op g{};
-        g.type = 1; g.parent = v; g.src_panel = panel_of[big]; g.child = big; g.to_root = (v == c->root);
-        g.dst_panel = dst; g.mode = 0; g.has_gath = true; g.gath_child = small; g.gath_panel = scratch;
-        c->ops.push_back(g);
-        pa.put(scratch);
-        for (int u : inner) pa.put(panel_of[u]);
-        return dst;
-    }
-    for (size_t gi = 0; gi < inner.size(); ++gi) {   // child order of the reference (probability.cpp:205 walks _descendants in order)
-        const int u = inner[gi];
-        const bool direct = is_direct(u);
-        Op op{};
-        op.type = 1;
-        op.parent = v;
-        op.src_panel = panel_of[u];
-        op.child = u;
-        op.to_root = (v == c->root);
-        if (direct) {
-            op.dst_panel = dst;
-            op.mode = init ? 1 : 0;
-            if (gi == 0) {
-                op.n_leaf = (int)fused;
-                for (size_t l = 0; l < fused; ++l) op.leaf_node[l] = leaves[l];
-            }
-            c->ops.push_back(op);
-            init = true;
-        } else {
-            const int scratch = pa.get();
-            op.dst_panel = scratch;
-            op.mode = 0;
-            op.to_factor = true;
-            c->ops.push_back(op);
-            factors.emplace_back(u, scratch);
-        }
-    }
-    // assemble the parent's panel: up to two factor panels and two leaf children per pass, written once
-    size_t li = fused, fi = 0;
-    while (li < leaves.size() || fi < factors.size()) {
-        Op op{};
-        op.type = 0;
-        op.parent = v;
-        op.dst_panel = dst;
-        op.to_root = (v == c->root);
-        const size_t max_leaf = factors.empty() ? (size_t)kMaxLeafPerOp : 2;     // the fast kernel takes two of each
-        op.n_leaf = (int)std::min<size_t>(max_leaf, leaves.size() - li);
-        for (int l = 0; l < op.n_leaf; ++l) op.leaf_node[l] = leaves[li + l];
-        li += op.n_leaf;
-        op.n_src = (int)std::min<size_t>(2, factors.size() - fi);
-        for (int j = 0; j < op.n_src; ++j) { op.src_child[j] = factors[fi + j].first; op.src_panels[j] = factors[fi + j].second; }
-        fi += op.n_src;
-        op.mode = init ? 1 : 0;
-        c->ops.push_back(op);
-        init = true;
-    }
-    for (auto& fs : factors) pa.put(fs.second);
-    for (int u : inner) pa.put(panel_of[u]);
-    return dst;
-}
-
-// Subtree-level de-duplication (host side, once): the distinct patterns of leaf counts under every interior node, the
-// column of each child for every column of its parent, and the leaf children's counts per parent column.  Columns are
-// numbered by first occurrence in (distinct-)family order, so the root's columns are the distinct families themselves
-// and a child with as many patterns as its parent has them in the same order (an identity map: no combine pass).
-int compute_patterns(cafe_ctx* c, const cafe_problem* p, const std::vector<int64_t>& uniq) {
-    const int n = c->n_nodes, T = c->n_taxa;
-    const int64_t F = c->F_uniq;
-    c->pat_cols.assign(n, 0);
-    c->edge_identity.assign(n, 0);
-    c->d_edge_map.assign(n, nullptr);
-    c->d_leaf_cnt.assign(n, nullptr);
-    c->leaf_rank.assign(n, 0);
-    // ---- 1. every interior node's own patterns, children first.  Patterns are numbered in the order of the node's
-    // HEAVY child's pattern numbers (the interior child with the most patterns; ties and cherries: first occurrence in
-    // family order), so that along the heavy path a parent's columns map to non-decreasing child columns: the
-    // gathers of the assemble passes and of K2's gathered-factor epilogue then read the big factor panel in order.
-    std::vector<std::vector<int32_t>> pid(n);            // [interior node][distinct family] own pattern index
-    std::vector<std::vector<int64_t>> rep(n);            // [interior node][own pattern] first distinct family showing it
-    for (int v = 0; v < n; ++v) {
-        if (c->leaf_taxon[v] >= 0) continue;
-        std::vector<int> inner, leaves;
-        for (int u : c->children[v]) (c->leaf_taxon[u] < 0 ? inner : leaves).push_back(u);
-        const size_t kw = inner.size() + leaves.size();
-        pid[v].resize(F);
-        if (v == c->root) {                              // the root keeps one column per family of the context (K4 reads them
-            rep[v].resize(F);                            // by family index), also when identical families were kept apart
-            for (int64_t f = 0; f < F; ++f) { pid[v][f] = (int32_t)f; rep[v][f] = f; }
-            continue;
-        }
-        std::unordered_map<std::string, int32_t> seen;
-        seen.reserve((size_t)F * 2);
-        std::vector<int64_t> first;                      // raw pattern (first-occurrence number) -> first family
-        std::vector<int32_t> key(kw);
-        for (int64_t f = 0; f < F; ++f) {
-            size_t k = 0;
-            for (int u : inner) key[k++] = pid[u][f];
-            for (int u : leaves) key[k++] = p->counts[uniq[f] * T + c->leaf_taxon[u]];
-            std::string ks(reinterpret_cast<const char*>(key.data()), sizeof(int32_t) * kw);
-            auto it = seen.find(ks);
-            if (it == seen.end()) {
-                it = seen.emplace(std::move(ks), (int32_t)first.size()).first;
-                first.push_back(f);
-            }
-            pid[v][f] = it->second;
-        }
-        int heavy = -1;
-        for (int u : inner) if (heavy < 0 || rep[u].size() > rep[heavy].size()) heavy = u;
-        const size_t U = first.size();
-        std::vector<int32_t> order(U), renum(U);
-        for (size_t i = 0; i < U; ++i) order[i] = (int32_t)i;
-        // largest leaf count under v, per pattern: the primary key (columns of similar size share a 128-column tile, whose
-        // all-zero rows K2 skips); within equal sizes the heavy child's numbering
-        std::vector<int32_t> big(U, 0), small(U, 0x7fffffff);
-        {
-            std::vector<int> under;                       // taxa under v
-            std::vector<int> stack(1, v);
-            while (!stack.empty()) {
-                const int w = stack.back(); stack.pop_back();
-                if (c->leaf_taxon[w] >= 0) under.push_back(c->leaf_taxon[w]);
-                for (int u : c->children[w]) stack.push_back(u);
-            }
-            for (size_t i = 0; i < U; ++i)
-                for (int t : under) {
-                    const int32_t x = p->counts[uniq[first[i]] * T + t];
-                    big[i] = std::max(big[i], x);
-                    small[i] = std::min(small[i], x);
-                }
-        }
-        // (the lower end of a column's non-zero rows follows its largest count, the upper end its smallest)
-        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
-            if (big[x] != big[y]) return big[x] < big[y];
-            if (small[x] != small[y]) return small[x] < small[y];
-            return heavy >= 0 && pid[heavy][first[x]] < pid[heavy][first[y]];
-        });
-        rep[v].resize(U);
-        for (size_t i = 0; i < U; ++i) { renum[order[i]] = (int32_t)i; rep[v][i] = first[order[i]]; }
-        for (int64_t f = 0; f < F; ++f) pid[v][f] = renum[pid[v][f]];
-    }
-    // ---- 2. column space of every interior node, parents first: its own patterns, or its parent's columns, which makes
-    // the edge direct (the GEMM's epilogue writes the parent's panel).  A GEMM column costs about 0.12 us, a column of an
-    // assemble pass 0.024 us (one factor + leaf) to 0.036 us (two factors) at the bench shape, so:
-    //  * all interior children inherit when together they add < 15 % GEMM columns (store / multiply epilogues, one leaf
-    //    sibling fused);
-    //  * of two interior children (no leaf sibling) the larger one inherits alone when it adds < 12 % (an assemble pass
-    //    saved is worth about that many GEMM columns): the smaller one keeps its own columns and its factor is gathered
-    //    in the larger one's epilogue -- no assemble pass either.
-    std::vector<int> space(n, -1);
-    space[c->root] = c->root;
-    for (int v = n - 1; v >= 0; --v) {
-        if (c->leaf_taxon[v] >= 0) continue;
-        std::vector<int> inner;
-        int n_leaves = 0;
-        for (int u : c->children[v]) { if (c->leaf_taxon[u] < 0) inner.push_back(u); else ++n_leaves; }
-        const double Uv = (double)rep[space[v]].size();
-        double extra = 0;
-        for (int u : inner) extra += 1.0 - (double)rep[u].size() / Uv;
-        static const double thr_all = std::getenv("CAFE_INHERIT_ALL") ? std::atof(std::getenv("CAFE_INHERIT_ALL")) : 0.15;
-        static const double thr_big = std::getenv("CAFE_INHERIT_BIG") ? std::atof(std::getenv("CAFE_INHERIT_BIG")) : 0.12;
-        const bool inherit = !inner.empty() && n_leaves <= 1 && extra < thr_all;
-        for (int u : inner) space[u] = inherit ? space[v] : u;
-        if (!inherit && inner.size() == 2 && n_leaves == 0) {
-            const int big = rep[inner[0]].size() >= rep[inner[1]].size() ? inner[0] : inner[1];
-            if (1.0 - (double)rep[big].size() / Uv < thr_big) space[big] = space[v];
-        }
-    }
-    // ---- 3. tables
-    for (int v = 0; v < n; ++v) {
-        if (c->leaf_taxon[v] >= 0) continue;
-        std::vector<int> inner, leaves;
-        for (int u : c->children[v]) (c->leaf_taxon[u] < 0 ? inner : leaves).push_back(u);
-        const std::vector<int64_t>& cols = rep[space[v]];                // representative family of every column of v's panel
-        const int64_t U = (int64_t)cols.size(), Up = round_up64(U, kBN);
-        c->pat_cols[v] = Up;
-        for (size_t l = 0; l < leaves.size(); ++l) c->leaf_rank[leaves[l]] = (int)l;
-        if (!leaves.empty()) {
-            std::vector<int32_t> tab(leaves.size() * (size_t)Up, 0);
-            for (size_t l = 0; l < leaves.size(); ++l)
-                for (int64_t u2 = 0; u2 < U; ++u2) tab[l * Up + u2] = p->counts[uniq[cols[u2]] * T + c->leaf_taxon[leaves[l]]];
-            HIP_TRY(c, hipMalloc(&c->d_leaf_cnt[v], tab.size() * sizeof(int32_t)));
-            HIP_TRY(c, hipMemcpy(c->d_leaf_cnt[v], tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        for (int u : inner) {
-            if (space[u] == space[v]) { c->edge_identity[u] = 1; continue; }      // the child's columns ARE the parent's
-            std::vector<int32_t> map((size_t)Up, 0);
-            bool same = (int64_t)rep[u].size() == U;     // as many own patterns as the parent has columns, in the same order?
-            for (int64_t u2 = 0; u2 < U; ++u2) { map[u2] = pid[u][cols[u2]]; same = same && map[u2] == (int32_t)u2; }
-            if (same) { c->edge_identity[u] = 1; continue; }
-            HIP_TRY(c, hipMalloc(&c->d_edge_map[u], map.size() * sizeof(int32_t)));
-            HIP_TRY(c, hipMemcpy(c->d_edge_map[u], map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-    }
-    return CAFE_OK;
-}
-
 // matrix_cache_key (matrix_cache.h:42-61)
 inline void quantize(double lambda, double t, long* lq, long* tq) {
     *lq = long(lambda * 1000000000);
@@ -300,22 +56,14 @@ void free_device(cafe_ctx* c) {
     comm_release(c);
     for (auto& g : c->graphs) if (g.second.exec) hipGraphExecDestroy(g.second.exec);
     hipFree(c->d_counts); hipFree(c->d_weights); hipFree(c->pool.base); hipFree(c->kpool.base); hipFree(c->kpool.ext); hipFree(c->pool.ext); hipFree(c->d_params); hipFree(c->d_panels);
-    hipFree(c->d_ext_nodes);
-    for (auto ptr : c->d_colext) hipFree(ptr);
-    for (auto ptr : c->d_tileext) hipFree(ptr);
-    hipFree(c->d_fam_out); hipFree(c->d_fam_lik); hipFree(c->d_cat_out); hipFree(c->d_failed);
+    hipFree(c->d_ext_nodes); hipFree(c->d_fam_out); hipFree(c->d_fam_lik); hipFree(c->d_cat_out); hipFree(c->d_failed);
+    for (auto* ptrs : {&c->d_colext, &c->d_tileext, &c->d_edge_map, &c->d_leaf_cnt}) for (auto ptr : *ptrs) hipFree(ptr);
     hipFree(c->d_scratch); hipFree(c->d_result); hipFree(c->d_stamps);
-    for (auto ptr : c->d_edge_map) hipFree(ptr);
-    for (auto ptr : c->d_leaf_cnt) hipFree(ptr);
-    if (c->h_stage) hipHostFree(c->h_stage);
-    if (c->h_result) hipHostFree(c->h_result);
-    if (c->h_ext) hipHostFree(c->h_ext);
+    for (void* h : {(void*)c->h_stage, (void*)c->h_result, (void*)c->h_ext, (void*)c->h_gemm_stage, (void*)c->h_plan_desc}) if (h) hipHostFree(h);
     auto free_desc = [](DescSet& d) { hipFree(d.d_gemm_ops); hipFree(d.d_plan_desc); hipFree(d.d_plan); d = DescSet(); };
     free_desc(c->desc);
     for (auto& g : c->graphs) free_desc(g.second.desc);
     hipFree(c->d_gather_ops); hipFree(c->d_lt); hipFree(c->d_lt_pairs);
-    if (c->h_gemm_stage) hipHostFree(c->h_gemm_stage);
-    if (c->h_plan_desc) hipHostFree(c->h_plan_desc);
     if (c->ev_upload) hipEventDestroy(c->ev_upload);
     for (auto& e : c->ev) if (e) hipEventDestroy(e);
     for (auto& e : c->gemm_ev) hipEventDestroy(e);
@@ -323,16 +71,39 @@ void free_device(cafe_ctx* c) {
     if (c->stream) hipStreamDestroy(c->stream);
 }
 
-int create_impl(cafe_ctx* c, const cafe_problem* p) {
+// Environment switches read at cafe_create, all diagnostics: none of them changes a result bit.  Those of the call path go
+// into the context; those of cafe_create itself come back.
+struct Switches { bool no_groups, no_kskip, no_leaf_t, gemm_stamps, dump_schedule; double lt_min; int kb; };
+
+Switches read_switches(cafe_ctx* c) {
+    Switches sw{};
+    const char* e;
+    sw.no_groups = std::getenv("CAFE_NO_GROUPS");            // one op per launch from the slot pool instead of level-batched launches
+    sw.no_kskip = std::getenv("CAFE_NO_KSKIP");              // no matrix or panel extents: every K tile of every launch
+    sw.no_leaf_t = std::getenv("CAFE_NO_LEAF_T");            // no transposed leaf matrices for the assemble passes
+    sw.lt_min = (e = std::getenv("CAFE_LEAF_T_MIN")) ? atof(e) : 6.0;   // a leaf branch gets one when its passes write >= lt_min N columns
+    sw.kb = (e = std::getenv("CAFE_KB")) ? (std::atoi(e) == 16 ? 16 : 8) : 0;   // depth of K2's K tiles, 8 or 16
+    sw.gemm_stamps = std::getenv("CAFE_GEMM_STAMPS");        // per-workgroup block timeline of a K2 launch (cafe_debug_stamps)
+    sw.dump_schedule = std::getenv("CAFE_DUMP_SCHEDULE");    // the launch list with its column counts, on stderr
+    if ((e = std::getenv("CAFE_GEMM_STAMPS_LAUNCH"))) c->stamps_launch = std::atol(e);   // stamps of that K2 launch only
+    c->no_asm_skip = std::getenv("CAFE_NO_ASM_SKIP") != nullptr;   // the assemble passes write every row
+    if ((e = std::getenv("CAFE_FORCE_TILE")) && std::atoi(e) >= 2 && std::atoi(e) <= 9) c->force_mi = std::atoi(e);   // like cafe_debug_force_tile
+    if ((e = std::getenv("CAFE_PLAN_FIXED"))) c->plan_fixed = std::max(0, atoi(e));   // the tile planner's cost of a tile beyond its K loop
+    if ((e = std::getenv("CAFE_PLAN_BIAS"))) c->plan_bias = std::min(50, std::max(0, atoi(e)));   // first-dispatched workgroup of a CU, percent
+    int v[4];                                                // a K tile's cost to the 1st .. 4th / 1st .. 3rd dispatched workgroup of a CU, percent
+    if ((e = std::getenv("CAFE_PLAN_BIAS4")) && std::sscanf(e, "%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3]) == 4 && v[0] > 0 && v[1] > 0 && v[2] > 0 && v[3] > 0)
+        std::copy(v, v + 4, c->plan_bias4);
+    if ((e = std::getenv("CAFE_PLAN_BIAS3")) && std::sscanf(e, "%d,%d,%d", &v[0], &v[1], &v[2]) == 3 && v[0] > 0 && v[1] > 0 && v[2] > 0)
+        std::copy(v, v + 3, c->plan_bias3);
+    return sw;
+}
+
+// The tree and the family table: range checks, every node's interior and leaf children, family de-duplication
+// (build_reference_list, base_model.cpp:27-51) and the column order.  uniq: the first family of every column.
+int load_problem(cafe_ctx* c, const cafe_problem* p, std::vector<int64_t>& uniq) {
     const bool device_counts = p && (p->flags & kFlagDeviceCounts);      // internal: the caller fills d_counts on the device
-    if (!p || p->n_nodes < 3 || !p->parent || !p->branch_length || !p->leaf_taxon || (!p->counts && !device_counts)) {
-        set_err(c, "cafe_create: missing tree or family arrays");
-        return CAFE_ERR_ARGUMENT;
-    }
-    if (p->n_families < 1 || p->n_taxa < 2 || p->max_family_size < 1 || p->max_root_family_size < 1) {
-        set_err(c, "cafe_create: empty family table or non-positive max sizes");
-        return CAFE_ERR_ARGUMENT;
-    }
+    if (!p || p->n_nodes < 3 || !p->parent || !p->branch_length || !p->leaf_taxon || (!p->counts && !device_counts)) { set_err(c, "cafe_create: missing tree or family arrays"); return CAFE_ERR_ARGUMENT; }
+    if (p->n_families < 1 || p->n_taxa < 2 || p->max_family_size < 1 || p->max_root_family_size < 1) { set_err(c, "cafe_create: empty family table or non-positive max sizes"); return CAFE_ERR_ARGUMENT; }
     c->n_nodes = p->n_nodes; c->n_taxa = p->n_taxa; c->M = p->max_family_size; c->R = p->max_root_family_size;
     c->N = std::max(c->M, c->R) + 1;                                   // base_model.cpp:77
     c->n_lambdas = std::max(1, p->n_lambdas); c->single_lambda = p->single_lambda;
@@ -343,33 +114,31 @@ int create_impl(cafe_ctx* c, const cafe_problem* p) {
     c->leaf_taxon.assign(p->leaf_taxon, p->leaf_taxon + p->n_nodes);
     if (p->lambda_index) c->lam_idx.assign(p->lambda_index, p->lambda_index + p->n_nodes);
     else c->lam_idx.assign(p->n_nodes, 0);
-    c->children.assign(p->n_nodes, {});
+    c->children.assign(p->n_nodes, {}); c->inner.assign(p->n_nodes, {}); c->leaves.assign(p->n_nodes, {});
     for (int v = 0; v < p->n_nodes; ++v) {
         int par = c->parent[v];
         if (par < 0) {
             if (c->root >= 0) { set_err(c, "cafe_create: more than one root"); return CAFE_ERR_ARGUMENT; }
             c->root = v;
         } else if (par >= p->n_nodes || par <= v) {
-            set_err(c, "cafe_create: node %d: parent %d must come after its children", v, par);
-            return CAFE_ERR_ARGUMENT;
+            set_err(c, "cafe_create: node %d: parent %d must come after its children", v, par); return CAFE_ERR_ARGUMENT;
         } else {
             c->children[par].push_back(v);
+            (c->leaf_taxon[v] < 0 ? c->inner[par] : c->leaves[par]).push_back(v);
         }
         if (c->lam_idx[v] < 0 || c->lam_idx[v] >= c->n_lambdas) { set_err(c, "cafe_create: lambda index out of range at node %d", v); return CAFE_ERR_ARGUMENT; }
     }
     if (c->root < 0) { set_err(c, "cafe_create: no root"); return CAFE_ERR_ARGUMENT; }
     for (int v = 0; v < p->n_nodes; ++v) {
         bool leaf = c->children[v].empty();
-        if (leaf != (c->leaf_taxon[v] >= 0) || (leaf && c->leaf_taxon[v] >= c->n_taxa)) {
-            set_err(c, "cafe_create: leaf_taxon inconsistent with the tree at node %d", v);
-            return CAFE_ERR_ARGUMENT;
-        }
+        if (leaf != (c->leaf_taxon[v] >= 0) || (leaf && c->leaf_taxon[v] >= c->n_taxa)) { set_err(c, "cafe_create: leaf_taxon inconsistent with the tree at node %d", v); return CAFE_ERR_ARGUMENT; }
     }
     if (c->children[c->root].empty()) { set_err(c, "cafe_create: the root is a leaf"); return CAFE_ERR_ARGUMENT; }
     if (c->N > bd_matrix_max_order()) { set_err(c, "cafe_create: matrix order %d exceeds %d", c->N, bd_matrix_max_order()); return CAFE_ERR_ARGUMENT; }
 
     // families: range check + de-duplication (build_reference_list, base_model.cpp:27-51)
     c->F_all = p->n_families;
+    c->workspace_limit = p->workspace_limit;
     const int T = c->n_taxa;
     for (int64_t i = 0; !device_counts && i < c->F_all * T; ++i)
         if (p->counts[i] < 0 || p->counts[i] > c->M) {
@@ -377,7 +146,6 @@ int create_impl(cafe_ctx* c, const cafe_problem* p) {
             return CAFE_ERR_ARGUMENT;
         }
     c->ref_of.resize(c->F_all);
-    std::vector<int64_t> uniq;                 // first occurrence of each distinct row
     if ((p->flags & CAFE_FLAG_NO_DEDUP) || device_counts) {
         uniq.resize(c->F_all);
         for (int64_t f = 0; f < c->F_all; ++f) { uniq[f] = f; c->ref_of[f] = f; }
@@ -417,67 +185,43 @@ int create_impl(cafe_ctx* c, const cafe_problem* p) {
         c->weights.swap(nw);
         for (int64_t f = 0; f < c->F_all; ++f) c->ref_of[f] = inv[c->ref_of[f]];
     }
+    return CAFE_OK;
+}
 
-    // device
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_err(c, "cafe_create: no HIP device available (this library has no CPU path)"); return CAFE_ERR_DEVICE; }
-    if (c->device < 0 || c->device >= ndev) { set_err(c, "cafe_create: device %d out of range (%d devices)", c->device, ndev); return CAFE_ERR_DEVICE; }
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->device_ready = true;
-    HIP_TRY(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+template <class T>
+int upload(cafe_ctx* c, T** d, const std::vector<T>& h) {
+    HIP_TRY(c, hipMalloc(d, sizeof(T) * std::max<size_t>(1, h.size())));
+    HIP_TRY(c, hipMemcpy(*d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+    return CAFE_OK;
+}
 
-    // counts, taxon-major, padded families replicate an all-zero family
-    {
-        std::vector<int32_t> tm((size_t)T * c->Fp, 0);
-        for (int64_t u = 0; !device_counts && u < c->F_uniq; ++u)
-            for (int t = 0; t < T; ++t) tm[(size_t)t * c->Fp + u] = p->counts[uniq[u] * T + t];
-        HIP_TRY(c, hipMalloc(&c->d_counts, tm.size() * sizeof(int32_t)));
-        HIP_TRY(c, hipMemcpy(c->d_counts, tm.data(), tm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        std::vector<double> w(c->Fp, 0.0);
-        std::copy(c->weights.begin(), c->weights.end(), w.begin());
-        HIP_TRY(c, hipMalloc(&c->d_weights, w.size() * sizeof(double)));
-        HIP_TRY(c, hipMemcpy(c->d_weights, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-
-    // subtree-level de-duplication tables (the schedule depends on them)
-    c->subtree_dedup = !device_counts && !(p->flags & CAFE_FLAG_NO_SUBTREE_DEDUP);
-    if (c->subtree_dedup) { const int rc = compute_patterns(c, p, uniq); if (rc != CAFE_OK) return rc; }
-    std::vector<int> need(c->n_nodes, 0);
-    panel_need(c, c->root, need);
-
-    // matrix pools: one slot per (distinct quantized branch length, lambda index) pair and category, per layout.
-    // Leaf branches use row-major matrices (K3 gathers a column), interior branches k-major ones (K2's A).
+// matrix pools: one slot per (distinct quantized branch length, lambda index) pair and category, per layout.
+// Leaf branches use row-major matrices (K3 gathers a column), interior branches k-major ones (K2's A).
+void plan_pools(cafe_ctx* c, int kb) {
     c->pair_of.assign(c->n_nodes, -1);
-    {
-        std::map<std::pair<long, int>, int> seen[2], any;
-        for (int v = 0; v < c->n_nodes; ++v) {
-            if (v == c->root) continue;
-            const int layout = c->leaf_taxon[v] >= 0 ? 0 : 1;
-            long lq, tq;
-            quantize(0.0, c->blen[v], &lq, &tq);
-            const auto key = std::make_pair(tq, c->lam_idx[v]);
-            auto it = seen[layout].find(key);
-            if (it == seen[layout].end()) {
-                it = seen[layout].emplace(key, (int)c->pair_tq[layout].size()).first;
-                c->pair_tq[layout].push_back(tq);
-                c->pair_lam[layout].push_back(c->lam_idx[v]);
-            }
-            c->pair_of[v] = it->second;
-            any.emplace(key, 0);
+    std::map<std::pair<long, int>, int> seen[2], any;
+    for (int v = 0; v < c->n_nodes; ++v) {
+        if (v == c->root) continue;
+        const int layout = c->leaf_taxon[v] >= 0 ? 0 : 1;
+        long lq, tq;
+        quantize(0.0, c->blen[v], &lq, &tq);
+        const auto key = std::make_pair(tq, c->lam_idx[v]);
+        auto it = seen[layout].find(key);
+        if (it == seen[layout].end()) {
+            it = seen[layout].emplace(key, (int)c->pair_tq[layout].size()).first;
+            c->pair_tq[layout].push_back(tq);
+            c->pair_lam[layout].push_back(c->lam_idx[v]);
         }
-        c->n_pairs[0] = (int)c->pair_tq[0].size();
-        c->n_pairs[1] = (int)c->pair_tq[1].size();
-        c->n_distinct_pairs = (int)any.size();
+        c->pair_of[v] = it->second;
+        any.emplace(key, 0);
     }
+    c->n_pairs[0] = (int)c->pair_tq[0].size(); c->n_pairs[1] = (int)c->pair_tq[1].size();
+    c->n_distinct_pairs = (int)any.size();
     c->kc = round_up(c->M + 1, kBK);
-    c->pool.n = c->N;
-    c->pool.ld = round_up(c->N, 16);
-    c->pool.stride = (int64_t)c->N * c->pool.ld;
+    c->pool.n = c->N; c->pool.ld = round_up(c->N, 16); c->pool.stride = (int64_t)c->N * c->pool.ld;
+    c->pool.ext_blocks = c->N;               // row-major: one entry per column x of a leaf branch's matrix
     c->max_slots = c->n_pairs[0] * c->Kmax;
-    c->kpool.n = c->N;
-    c->kpool.rows = c->kc;
-    c->kpool.k_valid = c->M + 1;
-    c->kpool.kmajor = 1;
+    c->kpool.n = c->N; c->kpool.rows = c->kc; c->kpool.k_valid = c->M + 1; c->kpool.kmajor = 1;
     c->kpool.ld = round_up(c->N - 1, 16) + round_up(kMaxBM, 16) + 16;     // a row tile may start at any valid row
     c->kpool.stride = (int64_t)c->kc * c->kpool.ld;
     c->kpool.ext_blocks = (c->N - 1 + 15) / 16;
@@ -488,6 +232,38 @@ int create_impl(cafe_ctx* c, const cafe_problem* p) {
         const int layout = c->leaf_taxon[v] >= 0 ? 0 : 1;
         for (int k = 0; k < c->Kmax; ++k) c->slot_of[(size_t)v * c->Kmax + k] = k * c->n_pairs[layout] + c->pair_of[v];
     }
+    // small matrices (a K2 launch is one round of tiles and lasts as long as one tile): 16-deep K tiles, half as many DMA
+    // round trips per tile; otherwise 8-deep ones, four workgroups per CU
+    c->kb = kb ? kb : (c->N < 256 ? 16 : 8);
+    // likelihood panels: rows padded so that every panel can be a GEMM B operand (kc rows) or the root (R rows)
+    // a factor GEMM stores transposed, [column][16 - out_off + panel row] (prune_gemm.hip): factor_ld rows per column, and a
+    // panel slot must be able to hold a factor of as many columns
+    c->factor_ld = round_up(std::max(c->M + 1, c->R) + 16, 16);
+    c->rows_pad = std::max(std::max(c->kc, round_up(c->R, kBK)), c->factor_ld);
+}
+
+// The family table on the device (counts taxon-major, padded families replicate an all-zero family) and the subtree
+// pattern tables when plan_patterns built them (the host copies are released)
+int upload_families(cafe_ctx* c, const cafe_problem* p, const std::vector<int64_t>& uniq) {
+    const int T = c->n_taxa;
+    std::vector<int32_t> tm((size_t)T * c->Fp, 0);
+    for (int64_t u = 0; !(p->flags & kFlagDeviceCounts) && u < c->F_uniq; ++u)
+        for (int t = 0; t < T; ++t) tm[(size_t)t * c->Fp + u] = p->counts[uniq[u] * T + t];
+    std::vector<double> w(c->Fp, 0.0);
+    std::copy(c->weights.begin(), c->weights.end(), w.begin());
+    if (int rc = upload(c, &c->d_counts, tm)) return rc;
+    if (int rc = upload(c, &c->d_weights, w)) return rc;
+    c->d_leaf_cnt.assign(c->h_leaf_cnt.size(), nullptr); c->d_edge_map.assign(c->h_edge_map.size(), nullptr);
+    for (size_t v = 0; v < c->h_leaf_cnt.size(); ++v) {
+        if (!c->h_leaf_cnt[v].empty()) if (int rc = upload(c, &c->d_leaf_cnt[v], c->h_leaf_cnt[v])) return rc;
+        for (int u : c->inner[v]) if (!c->h_edge_map[u].empty()) if (int rc = upload(c, &c->d_edge_map[u], c->h_edge_map[u])) return rc;
+    }
+    c->h_leaf_cnt.clear(); c->h_edge_map.clear();
+    return CAFE_OK;
+}
+
+// What lives as long as the context beside the family table: the matrix pools, the per-call parameter block, the outputs
+int alloc_resident(cafe_ctx* c, bool kskip, bool gemm_stamps) {
     const size_t pool_bytes = (size_t)std::max(1, c->max_slots) * c->pool.stride * sizeof(double);
     const size_t kpool_bytes = (size_t)std::max(1, c->max_kslots) * c->kpool.stride * sizeof(double);
     if (hipMalloc(&c->pool.base, pool_bytes) != hipSuccess || hipMalloc(&c->kpool.base, kpool_bytes) != hipSuccess) {
@@ -498,64 +274,42 @@ int create_impl(cafe_ctx* c, const cafe_problem* p) {
     // padding columns / rows of both layouts are never written by K1 and must read as 0
     HIP_TRY(c, hipMemset(c->pool.base, 0, pool_bytes));
     HIP_TRY(c, hipMemset(c->kpool.base, 0, kpool_bytes));
-    // non-zero extents of the k-major matrices (K1 writes them, K2 skips the K tiles outside them)
-    HIP_TRY(c, hipMalloc(&c->kpool.ext, sizeof(int32_t) * 2 * (size_t)std::max(1, c->max_kslots) * c->kpool.ext_blocks));
-    HIP_TRY(c, hipMemset(c->kpool.ext, 0, sizeof(int32_t) * 2 * (size_t)std::max(1, c->max_kslots) * c->kpool.ext_blocks));
-    c->pool.ext_blocks = c->N;               // row-major: one entry per column x of a leaf branch's matrix
-    HIP_TRY(c, hipMalloc(&c->pool.ext, sizeof(int32_t) * 2 * (size_t)std::max(1, c->max_slots) * c->pool.ext_blocks));
-    HIP_TRY(c, hipMemset(c->pool.ext, 0, sizeof(int32_t) * 2 * (size_t)std::max(1, c->max_slots) * c->pool.ext_blocks));
-    // diagnostic CAFE_NO_KSKIP: every K tile of every launch.  Small matrices (mammals: N = 141, 9 K tiles): a row tile spans
-    // most of the band anyway, and the extent kernels and lookups cost more than the few K tiles they would save (measured:
-    // 0.34 -> 0.38 ms per call with them) -- no extents below N = 256 unless CAFE_FORCE_KSKIP asks for them
-    if (std::getenv("CAFE_NO_KSKIP") || (c->N < 256 && !std::getenv("CAFE_FORCE_KSKIP"))) {
-        (void)hipFree(c->kpool.ext); c->kpool.ext = nullptr;
-        (void)hipFree(c->pool.ext); c->pool.ext = nullptr;
-    }
-    if (c->kpool.ext && c->N >= 256)         // (small matrices: one row tile spans most of the band anyway, and a copy per call is not free)
+    // non-zero extents of the matrices (K1 writes them, K2 skips the K tiles outside them), and the host copy of the
+    // k-major ones that picks K2's tile heights
+    if (kskip) {
+        HIP_TRY(c, hipMalloc(&c->kpool.ext, sizeof(int32_t) * 2 * (size_t)std::max(1, c->max_kslots) * c->kpool.ext_blocks));
+        HIP_TRY(c, hipMemset(c->kpool.ext, 0, sizeof(int32_t) * 2 * (size_t)std::max(1, c->max_kslots) * c->kpool.ext_blocks));
+        HIP_TRY(c, hipMalloc(&c->pool.ext, sizeof(int32_t) * 2 * (size_t)std::max(1, c->max_slots) * c->pool.ext_blocks));
+        HIP_TRY(c, hipMemset(c->pool.ext, 0, sizeof(int32_t) * 2 * (size_t)std::max(1, c->max_slots) * c->pool.ext_blocks));
         HIP_TRY(c, hipHostMalloc(&c->h_ext, sizeof(int32_t) * 2 * (size_t)std::max(1, c->max_kslots) * c->kpool.ext_blocks, hipHostMallocDefault));
-    c->stats.matrix_bytes = (int64_t)(pool_bytes + kpool_bytes);
-
-    // per-call parameter block (layout: cafe_ctx.h), device + pinned mirror
-    {
-        size_t off = sizeof(SlotParam) * (size_t)(c->max_slots + c->max_kslots);
-        off = (off + 63) / 64 * 64;
-        const size_t off_prior = off; off += sizeof(double) * c->R;
-        const size_t off_logprior = off; off += sizeof(double) * c->R;
-        const size_t off_cat = off; off += sizeof(double) * c->Kmax;
-        const size_t off_err = off; off += sizeof(double) * (size_t)(c->M + 1) * std::max(1, c->n_dev);
-        c->params_bytes = off;
-        HIP_TRY(c, hipMalloc(&c->d_params, c->params_bytes));
-        HIP_TRY(c, hipMemset(c->d_params, 0, c->params_bytes));
-        c->d_slots = reinterpret_cast<SlotParam*>(c->d_params);
-        c->d_prior = reinterpret_cast<double*>(c->d_params + off_prior);
-        c->d_logprior = reinterpret_cast<double*>(c->d_params + off_logprior);
-        c->d_catprobs = reinterpret_cast<double*>(c->d_params + off_cat);
-        c->d_err = c->n_dev > 0 ? reinterpret_cast<double*>(c->d_params + off_err) : nullptr;
-        c->stage_bytes = c->params_bytes;
-        HIP_TRY(c, hipHostMalloc(&c->h_stage, c->stage_bytes, hipHostMallocDefault));
-        std::memset(c->h_stage, 0, c->stage_bytes);
     }
+    c->stats.matrix_bytes = (int64_t)(pool_bytes + kpool_bytes);
+    // per-call parameter block (layout: cafe_ctx.h), device + pinned mirror
+    size_t off = sizeof(SlotParam) * (size_t)(c->max_slots + c->max_kslots);
+    off = (off + 63) / 64 * 64;
+    const size_t off_prior = off; off += sizeof(double) * c->R;
+    const size_t off_logprior = off; off += sizeof(double) * c->R;
+    const size_t off_cat = off; off += sizeof(double) * c->Kmax;
+    const size_t off_err = off; off += sizeof(double) * (size_t)(c->M + 1) * std::max(1, c->n_dev);
+    c->params_bytes = off;
+    HIP_TRY(c, hipMalloc(&c->d_params, c->params_bytes));
+    HIP_TRY(c, hipMemset(c->d_params, 0, c->params_bytes));
+    c->d_slots = reinterpret_cast<SlotParam*>(c->d_params);
+    c->d_prior = reinterpret_cast<double*>(c->d_params + off_prior);
+    c->d_logprior = reinterpret_cast<double*>(c->d_params + off_logprior);
+    c->d_catprobs = reinterpret_cast<double*>(c->d_params + off_cat);
+    c->d_err = c->n_dev > 0 ? reinterpret_cast<double*>(c->d_params + off_err) : nullptr;
+    c->stage_bytes = c->params_bytes;
+    HIP_TRY(c, hipHostMalloc(&c->h_stage, c->stage_bytes, hipHostMallocDefault));
+    std::memset(c->h_stage, 0, c->stage_bytes);
     HIP_TRY(c, hipHostMalloc(&c->h_result, 4 * sizeof(double), hipHostMallocDefault));
     c->h_poison = c->h_result + 2;                       // what a failing rank of a communicator feeds the all-reduce
-    c->h_poison[0] = 0.0;
-    c->h_poison[1] = std::numeric_limits<double>::quiet_NaN();
+    c->h_poison[0] = 0.0; c->h_poison[1] = std::numeric_limits<double>::quiet_NaN();
     HIP_TRY(c, hipEventCreateWithFlags(&c->ev_upload, hipEventDisableTiming));
     for (auto& e : c->ev) HIP_TRY(c, hipEventCreate(&e));
-    {
-        hipDeviceProp_t prop;
-        HIP_TRY(c, hipGetDeviceProperties(&prop, c->device));
-        c->n_cu = prop.multiProcessorCount;
-        const char* sl = std::getenv("CAFE_GEMM_STAMPS_LAUNCH");       // diagnostics: read once, never on the call path
-        c->stamps_launch = sl ? std::atol(sl) : -1;
-        if (std::getenv("CAFE_USE_GRAPH")) c->use_graph = 1;
-        // small matrices (a K2 launch is one round of tiles and lasts as long as one tile): 16-deep K tiles, half as many DMA
-        // round trips per tile; otherwise 8-deep ones, four workgroups per CU
-        c->kb = c->N < 256 ? 16 : 8;
-        if (const char* e = std::getenv("CAFE_KB")) c->kb = std::atoi(e) == 16 ? 16 : 8;
-        const char* fm = std::getenv("CAFE_FORCE_TILE");             // diagnostic, like cafe_debug_force_tile
-        if (fm && std::atoi(fm) >= 2 && std::atoi(fm) <= 9) c->force_mi = std::atoi(fm);
-    }
-
+    hipDeviceProp_t prop;
+    HIP_TRY(c, hipGetDeviceProperties(&prop, c->device));
+    c->n_cu = prop.multiProcessorCount;
     // outputs
     HIP_TRY(c, hipMalloc(&c->d_fam_out, sizeof(double) * c->Fp));
     HIP_TRY(c, hipMalloc(&c->d_fam_lik, sizeof(double) * c->Fp));
@@ -565,305 +319,59 @@ int create_impl(cafe_ctx* c, const cafe_problem* p) {
     HIP_TRY(c, hipMalloc(&c->d_scratch, sizeof(double) * (2 * c->n_scratch + 1)));      // partials + the ticket counter of the final sum
     HIP_TRY(c, hipMemset(c->d_scratch, 0, sizeof(double) * (2 * c->n_scratch + 1)));
     HIP_TRY(c, hipMalloc(&c->d_result, sizeof(double) * 2));
-    if (std::getenv("CAFE_GEMM_STAMPS")) {
+    if (gemm_stamps) {
         c->stamps_words = (size_t)6 * 8 * ((c->Fp / kBN + 8) * 16) * c->Kmax;
         HIP_TRY(c, hipMalloc(&c->d_stamps, c->stamps_words * sizeof(unsigned long long)));
         HIP_TRY(c, hipMemset(c->d_stamps, 0, c->stamps_words * sizeof(unsigned long long)));
     }
+    return CAFE_OK;
+}
 
-    // likelihood panels: rows padded so that every panel can be a GEMM B operand (kc rows) or the root (R rows)
-    // a factor GEMM stores transposed, [column][16 - out_off + panel row] (prune_gemm.hip): factor_ld rows per column, and a
-    // panel slot must be able to hold a factor of as many columns
-    c->factor_ld = round_up(std::max(c->M + 1, c->R) + 16, 16);
-    c->rows_pad = std::max(std::max(c->kc, round_up(c->R, kBK)), c->factor_ld);
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
-    c->workspace_limit = p->workspace_limit;
-    const size_t budget = p->workspace_limit ? p->workspace_limit : (size_t)(free_b * 0.80);
-    // K2 addresses a panel category through a 32-bit buffer descriptor: rows_pad * cols * 8 bytes must stay below 4 GB
-    const int64_t desc_cols = (int64_t)(0xFFFFFFF0ll / ((int64_t)c->rows_pad * 8)) / kBN * kBN;
+// a leaf child's row in the counts its parent's ops read (the parent's pattern table, or the family table)
+int cnt_row(const cafe_ctx* c, int leaf) { return c->subtree_dedup ? c->leaf_rank[leaf] : c->leaf_taxon[leaf]; }
 
-    // ---- the schedule.  Preferred (the table fits one column chunk with a place of its own for every panel): GROUPED --
-    // the ops are levelled by their dependencies into steps, a step's ops of one kernel variant share a launch, and the
-    // arena is planned from the panels' lifetimes.  Otherwise: one op per launch in post-order with the Sethi-Ullman slot
-    // pool (few live panels), in as many column chunks as the workspace asks for.
-    auto cols_of = [&](int v) -> int64_t { return c->subtree_dedup ? c->pat_cols[v] : c->Fp; };
-    size_t panel_doubles = 0;
-    c->grouped = !std::getenv("CAFE_NO_GROUPS");
-    if (c->grouped) {
-        PanelAlloc pa;
-        pa.reuse = false;
-        c->ops.clear();
-        c->root_panel = emit_node(c, c->root, need, pa);
-        c->panels.assign(pa.high, Panel());
-        // what each panel is: the transposed factor of a child (its own columns) or a node's panel
-        for (const Op& op : c->ops) {
-            Panel& P = c->panels[op.dst_panel];
-            P.factor = op.type == 1 && op.to_factor;
-            P.cols = P.factor ? cols_of(op.child) : cols_of(op.parent);
-            P.kstride = P.cols * (P.factor ? c->factor_ld : c->rows_pad);
-        }
-        // steps: an op runs one step after the last op it depends on -- the writers of what it reads (its children's panels,
-        // gathered factors, and its own destination when it multiplies)
-        {
-            std::vector<int> last_writer(c->panels.size(), -1);
-            int n_steps = 0;
-            for (size_t i = 0; i < c->ops.size(); ++i) {
-                Op& op = c->ops[i];
-                int st = 0;
-                auto dep = [&](int panel) { if (last_writer[panel] >= 0) st = std::max(st, c->ops[last_writer[panel]].step + 1); };
-                if (op.type == 1) { dep(op.src_panel); if (op.has_gath) dep(op.gath_panel); }
-                for (int j = 0; j < op.n_src; ++j) dep(op.src_panels[j]);
-                dep(op.dst_panel);                           // (a store is the first writer: no-op; a multiply follows the store)
-                op.step = st;
-                last_writer[op.dst_panel] = (int)i;
-                n_steps = std::max(n_steps, st + 1);
-            }
-            for (Panel& P : c->panels) { P.first_step = 0x7fffffff; P.last_step = -1; }
-            for (const Op& op : c->ops) {
-                auto use = [&](int panel) { Panel& P = c->panels[panel]; P.first_step = std::min(P.first_step, op.step); P.last_step = std::max(P.last_step, op.step); };
-                use(op.dst_panel);
-                if (op.type == 1) { use(op.src_panel); if (op.has_gath) use(op.gath_panel); }
-                for (int j = 0; j < op.n_src; ++j) use(op.src_panels[j]);
-            }
-            c->panels[c->root_panel].last_step = n_steps;    // K4 and cafe_get_root_likelihoods read it after the last step
-            // arena: first fit over the steps; a panel's place is free again after the step that reads it last
-            std::vector<std::pair<int64_t, int64_t>> holes;  // (offset, length) sorted by offset
-            int64_t top = 0;
-            std::vector<std::vector<int>> born(n_steps + 1), dies(n_steps + 1);
-            for (size_t i = 0; i < c->panels.size(); ++i) { born[c->panels[i].first_step].push_back((int)i); dies[c->panels[i].last_step].push_back((int)i); }
-            for (int st = 0; st <= n_steps; ++st) {
-                std::sort(born[st].begin(), born[st].end(), [&](int x, int y) { return c->panels[x].kstride > c->panels[y].kstride; });
-                for (int id : born[st]) {
-                    Panel& P = c->panels[id];
-                    const int64_t len = round_up64(P.kstride * c->Kmax, 64);          // 512-byte granules
-                    bool placed = false;
-                    for (size_t h = 0; h < holes.size() && !placed; ++h)
-                        if (holes[h].second >= len) {
-                            P.offset = holes[h].first;
-                            holes[h].first += len; holes[h].second -= len;
-                            if (holes[h].second == 0) holes.erase(holes.begin() + h);
-                            placed = true;
-                        }
-                    if (!placed) {
-                        if (!holes.empty() && holes.back().first + holes.back().second == top) {     // grow the hole at the top
-                            P.offset = holes.back().first;
-                            top = P.offset + len;
-                            holes.pop_back();
-                        } else {
-                            P.offset = top;
-                            top += len;
-                        }
-                    }
-                }
-                for (int id : dies[st]) {
-                    const Panel& P = c->panels[id];
-                    const int64_t len = round_up64(P.kstride * c->Kmax, 64);
-                    auto it = std::lower_bound(holes.begin(), holes.end(), std::make_pair(P.offset, (int64_t)0));
-                    it = holes.insert(it, std::make_pair(P.offset, len));
-                    if (it + 1 != holes.end() && it->first + it->second == (it + 1)->first) { it->second += (it + 1)->second; holes.erase(it + 1); }
-                    if (it != holes.begin() && (it - 1)->first + (it - 1)->second == it->first) { (it - 1)->second += it->second; holes.erase(it); }
-                }
-            }
-            panel_doubles = (size_t)top;
-        }
-        int64_t widest = 0;
-        for (const Panel& P : c->panels) widest = std::max(widest, P.cols);
-        // (a place of its own for every panel takes several times the slot pool: not when that is more than half the workspace)
-        if (panel_doubles * sizeof(double) + 65536 > budget / 2 || widest > desc_cols) c->grouped = false;
-    }
-    if (c->grouped) {
-        c->chunk_cols = c->Fp;
-        c->n_panels = (int)c->panels.size();
-        c->panel_kstride = (int64_t)c->rows_pad * c->Fp;     // (the root panel's, what K4 reads)
-        c->panel_stride = 0;
-    } else {
-        PanelAlloc pa;
-        c->ops.clear();
-        c->root_panel = emit_node(c, c->root, need, pa);
-        c->n_panels = pa.high;
-        size_t per_col = (size_t)c->n_panels * c->Kmax * c->rows_pad * sizeof(double);
-        int64_t cols = std::min<int64_t>((int64_t)(budget / per_col) / kBN * kBN, desc_cols);
-        if (c->subtree_dedup && cols < c->Fp) {
-            // several column chunks: the per-node column maps address whole panels, so this case keeps one column per
-            // family in every panel (the schedule without combine passes needs no more panels than the one with them)
-            c->subtree_dedup = false;
-            c->ops.clear();
-            PanelAlloc pb;
-            c->root_panel = emit_node(c, c->root, need, pb);
-            c->n_panels = pb.high;
-            per_col = (size_t)c->n_panels * c->Kmax * c->rows_pad * sizeof(double);
-            cols = std::min<int64_t>((int64_t)(budget / per_col) / kBN * kBN, desc_cols);
-        }
-        if (cols < kBN) { set_err(c, "cafe_create: %zu bytes of workspace cannot hold %d panels of one 128-family tile", budget, c->n_panels); return CAFE_ERR_MEMORY; }
-        c->chunk_cols = std::min<int64_t>(cols, c->Fp);
-        c->panel_kstride = (int64_t)c->rows_pad * c->chunk_cols;
-        c->panel_stride = c->panel_kstride * c->Kmax;
-        c->panels.assign(c->n_panels, Panel());
-        for (int i = 0; i < c->n_panels; ++i) {              // slots as wide as the widest panel; a node uses a prefix with its own leading dimension
-            c->panels[i].cols = c->chunk_cols;
-            c->panels[i].offset = (int64_t)i * c->panel_stride;
-            c->panels[i].kstride = c->panel_kstride;
-        }
-        for (size_t i = 0; i < c->ops.size(); ++i) c->ops[i].step = (int)i;
-        panel_doubles = (size_t)c->n_panels * c->panel_stride;
-    }
+// The arena of the likelihood panels, and the zero extents of the planned nodes' panels with their descriptors
+int alloc_panels(cafe_ctx* c, size_t panel_doubles, const std::vector<int>& ext_order) {
     // (+64 KB: the assemble pass reads whole 64-row tiles of a transposed factor, up to a tile past its last column)
     const size_t panel_bytes = panel_doubles * sizeof(double) + 65536;
-    if (hipMalloc(&c->d_panels, panel_bytes) != hipSuccess) {
-        set_err(c, "cafe_create: cannot allocate %.2f GB of likelihood panels", panel_bytes / 1e9);
-        return CAFE_ERR_MEMORY;
-    }
+    if (hipMalloc(&c->d_panels, panel_bytes) != hipSuccess) { set_err(c, "cafe_create: cannot allocate %.2f GB of likelihood panels", panel_bytes / 1e9); return CAFE_ERR_MEMORY; }
     // rows beyond what the first writer of a panel covers must not hold NaN bit patterns
     HIP_TRY(c, hipMemset(c->d_panels, 0, panel_bytes));
-    c->stats.panel_bytes = (int64_t)panel_bytes;
-    c->stats.n_unique_families = c->F_uniq;
-    c->stats.n_chunks = (c->Fp + c->chunk_cols - 1) / c->chunk_cols;
-
-    // zero extents of the panels: descriptors of the interior non-root nodes, children before parents, level by level
-    c->d_colext.assign(c->n_nodes, nullptr);
-    c->d_tileext.assign(c->n_nodes, nullptr);
-    // (one column per family at every node -- CAFE_FLAG_NO_SUBTREE_DEDUP, device-written counts -- works the same way as long
-    // as the families fit one column chunk: every edge is the identity and the counts are the family table itself)
-    c->panel_extents = (c->subtree_dedup || c->stats.n_chunks == 1) && c->kpool.ext && c->pool.ext && !std::getenv("CAFE_NO_PANEL_EXTENTS");
-    c->no_asm_skip = std::getenv("CAFE_NO_ASM_SKIP") != nullptr;
+    c->stats.panel_bytes = (int64_t)panel_bytes; c->stats.n_unique_families = c->F_uniq;
+    c->d_colext.assign(c->n_nodes, nullptr); c->d_tileext.assign(c->n_nodes, nullptr);
+    for (int v : ext_order) {
+        const int64_t cols = panel_cols(c, v, c->Fp);
+        HIP_TRY(c, hipMalloc(&c->d_colext[v], sizeof(int32_t) * 2 * (size_t)c->Kmax * cols));
+        HIP_TRY(c, hipMalloc(&c->d_tileext[v], sizeof(int32_t) * 2 * (size_t)c->Kmax * (cols / kBN)));
+    }
     if (c->panel_extents) {
-        std::vector<int> level(c->n_nodes, -1);
-        int max_level = -1;
-        for (int v = 0; v < c->n_nodes && c->panel_extents; ++v) {
-            if (c->leaf_taxon[v] >= 0 || v == c->root) continue;
-            int lv = 0, n_leaf = 0, n_inner = 0;
-            for (int u : c->children[v]) {
-                if (c->leaf_taxon[u] >= 0) ++n_leaf; else { ++n_inner; lv = std::max(lv, level[u] + 1); }
+        std::vector<ExtNode> nodes;
+        for (int v : ext_order) {
+            ExtNode nd{};
+            nd.cols = (int32_t)panel_cols(c, v, c->Fp);
+            nd.colext = c->d_colext[v]; nd.tileext = c->d_tileext[v];
+            nd.cnt = c->subtree_dedup ? c->d_leaf_cnt[v] : c->d_counts; nd.cnt_ld = nd.cols;
+            for (int u : c->leaves[v]) { nd.leaf_pair[nd.n_leaf] = c->pair_of[u]; nd.leaf_row[nd.n_leaf++] = cnt_row(c, u); }
+            for (int u : c->inner[v]) {
+                nd.inner_pair[nd.n_inner] = c->pair_of[u];
+                nd.inner_cols[nd.n_inner] = (int32_t)panel_cols(c, u, c->Fp);
+                nd.inner_map[nd.n_inner] = c->subtree_dedup ? c->d_edge_map[u] : nullptr;    // (nullptr for an identity edge)
+                nd.inner_colext[nd.n_inner++] = c->d_colext[u];
             }
-            if (n_leaf > kMaxExtChildren || n_inner > kMaxExtChildren) c->panel_extents = false;   // (a wide polytomy: no extents)
-            level[v] = lv;
-            max_level = std::max(max_level, lv);
+            nodes.push_back(nd);
         }
-        if (c->panel_extents) {
-            std::vector<ExtNode> nodes;
-            for (int lv = 0; lv <= max_level; ++lv) {
-                cafe_ctx::ExtLevel L{(int)nodes.size(), 0, 0};
-                for (int v = 0; v < c->n_nodes; ++v) {
-                    if (level[v] != lv) continue;
-                    ExtNode nd{};
-                    nd.cols = (int32_t)(c->subtree_dedup ? c->pat_cols[v] : c->Fp);
-                    HIP_TRY(c, hipMalloc(&c->d_colext[v], sizeof(int32_t) * 2 * (size_t)c->Kmax * nd.cols));
-                    HIP_TRY(c, hipMalloc(&c->d_tileext[v], sizeof(int32_t) * 2 * (size_t)c->Kmax * (nd.cols / kBN)));
-                    nd.colext = c->d_colext[v];
-                    nd.tileext = c->d_tileext[v];
-                    nd.cnt = c->subtree_dedup ? c->d_leaf_cnt[v] : c->d_counts;
-                    nd.cnt_ld = c->subtree_dedup ? c->pat_cols[v] : c->Fp;
-                    for (int u : c->children[v]) {
-                        if (c->leaf_taxon[u] >= 0) {
-                            nd.leaf_pair[nd.n_leaf] = c->pair_of[u];
-                            nd.leaf_row[nd.n_leaf] = c->subtree_dedup ? c->leaf_rank[u] : c->leaf_taxon[u];
-                            ++nd.n_leaf;
-                        } else {
-                            nd.inner_pair[nd.n_inner] = c->pair_of[u];
-                            nd.inner_cols[nd.n_inner] = (int32_t)(c->subtree_dedup ? c->pat_cols[u] : c->Fp);
-                            nd.inner_map[nd.n_inner] = (!c->subtree_dedup || c->edge_identity[u]) ? nullptr : c->d_edge_map[u];
-                            nd.inner_colext[nd.n_inner] = c->d_colext[u];
-                            ++nd.n_inner;
-                        }
-                    }
-                    L.max_col_tiles = std::max(L.max_col_tiles, nd.cols / kBN);
-                    nodes.push_back(nd);
-                    ++L.count;
-                }
-                if (L.count) c->ext_levels.push_back(L);
-            }
-            HIP_TRY(c, hipMalloc(&c->d_ext_nodes, sizeof(ExtNode) * std::max<size_t>(1, nodes.size())));
-            HIP_TRY(c, hipMemcpy(c->d_ext_nodes, nodes.data(), sizeof(ExtNode) * nodes.size(), hipMemcpyHostToDevice));
-        }
+        return upload(c, &c->d_ext_nodes, nodes);
     }
+    return CAFE_OK;
+}
 
-
-    // ---- launches: the ops of a step that share a kernel variant go out together
-    if (const char* e = std::getenv("CAFE_PLAN_FIXED")) c->plan_fixed = std::max(0, atoi(e));
-    if (const char* e = std::getenv("CAFE_PLAN_BIAS")) c->plan_bias = std::min(50, std::max(0, atoi(e)));
-    if (const char* e = std::getenv("CAFE_PLAN_BIAS4")) {
-        int v[4];
-        if (std::sscanf(e, "%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3]) == 4 && v[0] > 0 && v[1] > 0 && v[2] > 0 && v[3] > 0)
-            for (int i = 0; i < 4; ++i) c->plan_bias4[i] = v[i];
-    }
-    if (const char* e = std::getenv("CAFE_PLAN_BIAS3")) {
-        int a = 100, b = 100, d = 100;
-        if (std::sscanf(e, "%d,%d,%d", &a, &b, &d) == 3 && a > 0 && b > 0 && d > 0) { c->plan_bias3[0] = a; c->plan_bias3[1] = b; c->plan_bias3[2] = d; }
-    }
-    // Leaf branches whose matrix an assemble pass multiplies with a factor get a transposed copy (leaf_transpose_kernel, every
-    // call): the pass then reads the leaf's column as lines, like the factor's, instead of 8 bytes per matrix row (4.0 -> 6 TB/s).
-    // A copy costs 16 N^2 bytes per category and call whatever the number of columns, so a branch gets one only when the
-    // passes that read it write enough columns: >= lt_min N.  Bench table: 31 branches, 139.5 -> 137.9 ms per call; its 1/8
-    // shards copy 2 to 6 branches and take what they took (20.1 / 20.2 ms; with all 30 copied: +0.3 to +0.6 ms).
-    std::vector<int> lt_of_pair(std::max(1, c->n_pairs[0]), -1);
-    if (!std::getenv("CAFE_NO_LEAF_T")) {
-        double lt_min = 6.0;
-        if (const char* e = std::getenv("CAFE_LEAF_T_MIN")) lt_min = atof(e);
-        std::vector<int64_t> served(lt_of_pair.size(), 0);
-        auto eligible = [](const Op& op) { return op.type == 0 && op.n_src >= 1 && op.n_src <= 2 && op.n_leaf >= 1 && op.n_leaf <= 2; };
-        for (const Op& op : c->ops)
-            if (eligible(op))
-                for (int l = 0; l < op.n_leaf; ++l) served[c->pair_of[op.leaf_node[l]]] += cols_of(op.parent) * std::max<int64_t>(1, c->stats.n_chunks);
-        for (size_t pr = 0; pr < served.size(); ++pr)
-            if (served[pr] > 0 && (double)served[pr] >= lt_min * c->N) { lt_of_pair[pr] = (int)c->lt_pairs.size(); c->lt_pairs.push_back((int)pr); }
-        const size_t lt_bytes = sizeof(double) * ((size_t)c->lt_pairs.size() * c->Kmax * (size_t)(c->M + 1) * c->factor_ld + 2 * kBN);
-        size_t free_now = 0, total_now = 0;
-        HIP_TRY(c, hipMemGetInfo(&free_now, &total_now));
-        const bool fits = !c->lt_pairs.empty() && (size_t)c->lt_pairs.size() * c->Kmax <= 65535u && lt_bytes <= free_now / 4 &&
-                          (!c->workspace_limit || lt_bytes <= c->workspace_limit / 8);
-        if (fits) {
-            HIP_TRY(c, hipMalloc(&c->d_lt, lt_bytes));
-            HIP_TRY(c, hipMemset(c->d_lt, 0, lt_bytes));
-            HIP_TRY(c, hipMalloc(&c->d_lt_pairs, sizeof(int32_t) * c->lt_pairs.size()));
-            HIP_TRY(c, hipMemcpy(c->d_lt_pairs, c->lt_pairs.data(), sizeof(int32_t) * c->lt_pairs.size(), hipMemcpyHostToDevice));
-            for (Op& op : c->ops) {
-                if (!eligible(op)) continue;
-                op.leaf_t = true;
-                for (int l = 0; l < op.n_leaf; ++l) op.leaf_t = op.leaf_t && lt_of_pair[c->pair_of[op.leaf_node[l]]] >= 0;
-            }
-        } else {
-            c->lt_pairs.clear();
-        }
-    }
-    {
-        std::vector<size_t> idx(c->ops.size());
-        for (size_t i = 0; i < idx.size(); ++i) idx[i] = i;
-        auto key = [&](const Op& o) -> int {                 // launch order inside a step: factor GEMMs, the other GEMMs, then K3
-            if (o.type == 1) return o.to_factor ? 0 : 1 + (o.has_gath ? 2 : (o.n_leaf ? 1 : 0)) * 2 + o.mode;
-            return 16 + o.n_src * 32 + o.n_leaf * 2 + o.mode + (o.leaf_t ? 1024 : 0);
-        };
-        std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) {
-            const Op &a = c->ops[x], &b = c->ops[y];
-            if (a.step != b.step) return a.step < b.step;
-            if (a.to_root != b.to_root) return b.to_root;
-            return key(a) < key(b);
-        });
-        for (size_t i : idx) {
-            Op& o = c->ops[i];
-            const bool fresh = c->groups.empty() || c->groups.back().step != o.step || c->groups.back().type != o.type ||
-                               key(c->ops[c->groups.back().ops[0]]) != key(o) || c->groups.back().to_root != o.to_root ||
-                               (int)c->groups.back().ops.size() >= (o.type == 1 ? kMaxGroupOps : 512);
-            if (fresh) {
-                Group g;
-                g.type = o.type; g.step = o.step; g.to_root = o.to_root;
-                g.first_desc = o.type == 1 ? c->n_gemm_ops : c->n_gather_ops;
-                if (o.type == 1) g.variant = GemmVariant{o.mode, o.has_gath ? 2 : (o.n_leaf ? 1 : 0), o.to_factor ? 1 : 0};
-                c->groups.push_back(g);
-                c->n_gemm_groups += o.type == 1;
-            }
-            o.desc = o.type == 1 ? c->n_gemm_ops++ : c->n_gather_ops++;
-            c->groups.back().ops.push_back((int)i);
-        }
-    }
-    // static descriptors (n_row_tiles of a K2 op follows the tile height, chosen per call)
-    c->h_gemm_ops.assign(std::max(1, c->n_gemm_ops), GemmOp{});
-    c->h_gather_ops.assign(std::max(1, c->n_gather_ops), GatherArgs{});
+// Static descriptors (n_row_tiles of a K2 op follows the tile height, chosen per call) and the per-call launch state
+int build_descriptors(cafe_ctx* c, const std::vector<int>& lt_of_pair) {
+    c->h_gemm_ops.assign(std::max(1, c->n_gemm_ops), GemmOp{}); c->h_gather_ops.assign(std::max(1, c->n_gather_ops), GatherArgs{});
     const int64_t lt_kstride = (int64_t)(c->M + 1) * c->factor_ld;
     for (const Op& op : c->ops) {
         const int32_t* cnt_base = c->subtree_dedup ? c->d_leaf_cnt[op.parent] : c->d_counts;
-        const int64_t cnt_ld = c->subtree_dedup ? c->pat_cols[op.parent] : c->Fp;
-        auto cnt_row = [&](int leaf) { return c->subtree_dedup ? c->leaf_rank[leaf] : c->leaf_taxon[leaf]; };
+        const int64_t cnt_ld = panel_cols(c, op.parent, c->Fp);
         const Panel& D = c->panels[op.dst_panel];
         if (op.type == 1) {
             GemmOp& g = c->h_gemm_ops[op.desc];
@@ -871,43 +379,36 @@ int create_impl(cafe_ctx* c, const cafe_problem* p) {
             for (int k = 0; k < c->Kmax; ++k) g.slot[k] = c->slot_of[(size_t)op.child * c->Kmax + k];
             g.src = c->d_panels + S.offset; g.src_kstride = S.kstride;
             g.dst = c->d_panels + D.offset; g.dst_kstride = D.kstride;
-            g.ld = (int32_t)cols_of(op.child);               // the GEMM runs over the child's columns (= the parent's when direct)
+            g.ld = (int32_t)panel_cols(c, op.child, c->Fp);               // the GEMM runs over the child's columns (= the parent's when direct)
             g.n_col_tiles = g.ld / kBN;
             g.rows = op.to_root ? c->R : c->M;               // parent sizes 1..rows
-            g.out_off = op.to_root ? 0 : 1;
-            g.dst_ldt = op.to_factor ? c->factor_ld : 0;
-            g.n_leaf = op.n_leaf;
+            g.out_off = op.to_root ? 0 : 1; g.dst_ldt = op.to_factor ? c->factor_ld : 0; g.n_leaf = op.n_leaf;
             if (op.n_leaf) {
-                g.taxon = cnt_row(op.leaf_node[0]);
+                g.taxon = cnt_row(c, op.leaf_node[0]);
                 for (int k = 0; k < c->Kmax; ++k) g.leaf_slot[k] = c->slot_of[(size_t)op.leaf_node[0] * c->Kmax + k];
             }
             g.counts = cnt_base; g.counts_ld = cnt_ld;
             if (op.has_gath) {
                 const Panel& G = c->panels[op.gath_panel];
                 g.gath_src = c->d_panels + G.offset; g.gath_kstride = G.kstride;
-                g.gath_ld = c->factor_ld;
-                g.gath_map = c->d_edge_map[op.gath_child];
+                g.gath_ld = c->factor_ld; g.gath_map = c->d_edge_map[op.gath_child];
             }
             g.bext = c->panel_extents ? c->d_tileext[op.child] : nullptr;
         } else {
             GatherArgs& g = c->h_gather_ops[op.desc];
             g.n_leaf = op.n_leaf;
             for (int l = 0; l < op.n_leaf; ++l) {
-                g.taxon[l] = cnt_row(op.leaf_node[l]);
+                g.taxon[l] = cnt_row(c, op.leaf_node[l]);
                 for (int k = 0; k < c->Kmax; ++k) g.slot[l][k] = c->slot_of[(size_t)op.leaf_node[l] * c->Kmax + k];
             }
             g.counts = cnt_base; g.counts_ld = cnt_ld;
-            g.dst = c->d_panels + D.offset; g.panel_kstride = D.kstride; g.ld = (int32_t)cols_of(op.parent);
-            g.row_off = op.to_root ? 1 : 0;
-            g.rows = op.to_root ? c->R : c->M + 1;
-            g.rows_store = op.to_root ? c->R : c->kc;
-            g.mode = op.mode;
-            g.n_src = op.n_src;
+            g.dst = c->d_panels + D.offset; g.panel_kstride = D.kstride; g.ld = (int32_t)panel_cols(c, op.parent, c->Fp);
+            g.row_off = op.to_root ? 1 : 0; g.rows = op.to_root ? c->R : c->M + 1; g.rows_store = op.to_root ? c->R : c->kc;
+            g.mode = op.mode; g.n_src = op.n_src;
             for (int j = 0; j < op.n_src; ++j) {
                 const Panel& S = c->panels[op.src_panels[j]];
                 g.src[j] = c->d_panels + S.offset; g.kstride_src[j] = S.kstride;
-                g.ld_src[j] = c->factor_ld;
-                g.map[j] = c->d_edge_map[op.src_child[j]];
+                g.ld_src[j] = c->factor_ld; g.map[j] = c->d_edge_map[op.src_child[j]];
             }
             // (the root's vector is read whole by the reduction and has no extent record)
             g.tileext = c->panel_extents && !op.to_root && !c->no_asm_skip ? c->d_tileext[op.parent] : nullptr;
@@ -917,58 +418,64 @@ int create_impl(cafe_ctx* c, const cafe_problem* p) {
                     g.lt[l] = c->d_lt + (int64_t)lt_of_pair[c->pair_of[op.leaf_node[l]]] * c->Kmax * lt_kstride;
         }
     }
-    HIP_TRY(c, hipMalloc(&c->d_gather_ops, sizeof(GatherArgs) * c->h_gather_ops.size()));
-    HIP_TRY(c, hipMemcpy(c->d_gather_ops, c->h_gather_ops.data(), sizeof(GatherArgs) * c->h_gather_ops.size(), hipMemcpyHostToDevice));
+    if (int rc = upload(c, &c->d_gather_ops, c->h_gather_ops)) return rc;
     HIP_TRY(c, hipHostMalloc(&c->h_gemm_stage, sizeof(GemmOp) * c->h_gemm_ops.size(), hipHostMallocDefault));
-    // tile lists of the K2 launches: room for the tallest list any tile height can ask for
-    // (the planner is one 64-lane wave per XCD, a lane per workgroup: MI355X has 32 CUs x 2 workgroups per XCD)
-    {
-        size_t entries = 0;
-        for (const Group& g : c->groups) {
-            if (g.type != 1) continue;
-            size_t worst = 0;
-            for (int mi = 2; mi <= 9; ++mi) {
-                int64_t tiles = 0;
-                for (int oi : g.ops) {
-                    const Op& op = c->ops[oi];
-                    const int rows = op.to_root ? c->R : c->M;
-                    const int64_t gc = c->subtree_dedup ? c->pat_cols[op.child] : c->chunk_cols;
-                    tiles += prune_gemm_tiles_xcd0(c->Kmax, (int)(gc / kBN), (rows + 16 * mi - 1) / (16 * mi));
-                }
-                worst = std::max(worst, (size_t)8 * (size_t)(tiles + kPlanLanes * (1 + kPlanSlack)));   // >= 8 * nlb * (ceil(tiles / nlb) + slack), any K <= Kmax
-            }
-            entries += worst;
+    HIP_TRY(c, hipHostMalloc(&c->h_plan_desc, sizeof(PlanLaunch) * std::max(1, c->n_gemm_groups), hipHostMallocDefault));
+    c->gemm_ev.resize((size_t)2 * c->n_gemm_groups * c->stats.n_chunks);
+    for (auto& e : c->gemm_ev) HIP_TRY(c, hipEventCreate(&e));
+    return CAFE_OK;
+}
+
+int create_impl(cafe_ctx* c, const cafe_problem* p) {
+    const Switches sw = read_switches(c);
+    std::vector<int64_t> uniq;
+    int rc = load_problem(c, p, uniq);
+    if (rc != CAFE_OK) return rc;
+    const bool device_counts = p->flags & kFlagDeviceCounts;      // internal: the caller fills d_counts on the device
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_err(c, "cafe_create: no HIP device available (this library has no CPU path)"); return CAFE_ERR_DEVICE; }
+    if (c->device < 0 || c->device >= ndev) { set_err(c, "cafe_create: device %d out of range (%d devices)", c->device, ndev); return CAFE_ERR_DEVICE; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->device_ready = true;
+    HIP_TRY(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+
+    // subtree-level de-duplication tables (the schedule depends on them)
+    const bool dedup = !device_counts && !(p->flags & CAFE_FLAG_NO_SUBTREE_DEDUP);
+    if (dedup) plan_patterns(c, p, uniq);
+    if ((rc = upload_families(c, p, uniq)) != CAFE_OK) return rc;
+    plan_pools(c, sw.kb);
+    // Extents (K2 skips the K tiles outside a matrix's non-zero band).  Small matrices (mammals: N = 141, 9 K tiles): a row
+    // tile spans most of the band anyway, and the extent kernels and lookups cost more than the few K tiles they would save
+    // (measured: 0.34 -> 0.38 ms per call with them) -- no extents below N = 256
+    const bool kskip = !sw.no_kskip && c->N >= 256;
+    if ((rc = alloc_resident(c, kskip, sw.gemm_stamps)) != CAFE_OK) return rc;
+
+    // the schedule, for a panel budget of what is free now (or the given workspace)
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+    const size_t budget = p->workspace_limit ? p->workspace_limit : (size_t)(free_b * 0.80);
+    // K2 addresses a panel category through a 32-bit buffer descriptor: rows_pad * cols * 8 bytes must stay below 4 GB
+    const int64_t desc_cols = (int64_t)(0xFFFFFFF0ll / ((int64_t)c->rows_pad * 8)) / kBN * kBN;
+    const size_t panel_doubles = plan_schedule(c, dedup, !sw.no_groups, budget, desc_cols);
+    if (c->chunk_cols < kBN) { set_err(c, "cafe_create: %zu bytes of workspace cannot hold %d panels of one 128-family tile", budget, c->n_panels); return CAFE_ERR_MEMORY; }
+    const std::vector<int> ext_order = plan_extent_levels(c, kskip);
+    if ((rc = alloc_panels(c, panel_doubles, ext_order)) != CAFE_OK) return rc;
+
+    // transposed leaf copies, if they fit what is free after the panels
+    std::vector<int> lt_of_pair;
+    if (!sw.no_leaf_t) {
+        size_t free_now = 0, total_now = 0;
+        HIP_TRY(c, hipMemGetInfo(&free_now, &total_now));
+        if (const size_t lt_bytes = plan_leaf_transposes(c, sw.lt_min, free_now, lt_of_pair)) {
+            HIP_TRY(c, hipMalloc(&c->d_lt, lt_bytes));
+            HIP_TRY(c, hipMemset(c->d_lt, 0, lt_bytes));
+            if ((rc = upload(c, &c->d_lt_pairs, c->lt_pairs)) != CAFE_OK) return rc;
         }
-        c->plan_entries = entries;
-        HIP_TRY(c, hipHostMalloc(&c->h_plan_desc, sizeof(PlanLaunch) * std::max(1, c->n_gemm_groups), hipHostMallocDefault));
     }
 
-    if (std::getenv("CAFE_DUMP_SCHEDULE")) {             // diagnostic: the launch list with its column counts
-        std::fprintf(stderr, "cafe schedule: %s, %zu ops in %zu launches, %d panels, %.2f GB\n", c->grouped ? "grouped" : "one op per launch", c->ops.size(),
-                     c->groups.size(), c->n_panels, c->stats.panel_bytes / 1e9);
-        for (const Group& g : c->groups) {
-            std::fprintf(stderr, "cafe schedule: step %d %s x%zu\n", g.step, g.type == 1 ? "K2" : "K3", g.ops.size());
-            for (int oi : g.ops) {
-                const Op& op = c->ops[oi];
-                const int64_t pc = c->subtree_dedup ? c->pat_cols[op.parent] : c->chunk_cols;
-                if (op.type == 1)
-                    std::fprintf(stderr, "cafe schedule:   gemm child %d -> parent %d cols %lld %s%s%s leaf %d\n", op.child, op.parent,
-                                 (long long)(c->subtree_dedup ? c->pat_cols[op.child] : c->chunk_cols), op.to_factor ? "factor(transposed)" : (op.mode ? "multiply" : "store"),
-                                 op.has_gath ? " +gathered-factor" : "", op.to_root ? " root" : "", op.n_leaf);
-                else
-                    std::fprintf(stderr, "cafe schedule:   %s parent %d cols %lld factors %d leaves %d %s\n", op.n_src ? "assemble" : "leaf-gather", op.parent,
-                                 (long long)pc, op.n_src, op.n_leaf, op.mode ? "multiply" : "store");
-            }
-        }
-    }
-    int n_gemm = c->n_gemm_groups;
-    for (auto& op : c->ops) {
-        c->stats.n_gather_epilogues += op.type == 1 && op.has_gath;
-        c->stats.n_assemble_passes += op.type == 0 && op.n_src > 0;
-        c->stats.n_leaf_passes += op.type == 0 && op.n_src == 0;
-    }
-    c->gemm_ev.resize((size_t)2 * n_gemm * c->stats.n_chunks);
-    for (auto& e : c->gemm_ev) HIP_TRY(c, hipEventCreate(&e));
+    group_launches(c);
+    if ((rc = build_descriptors(c, lt_of_pair)) != CAFE_OK) return rc;
+    if (sw.dump_schedule) dump_schedule(c);
     HIP_TRY(c, hipDeviceSynchronize());
     return CAFE_OK;
 }
@@ -1067,7 +574,7 @@ int pick_tile_height(const cafe_ctx* c, const int32_t* ext, const Group& g, int 
         for (int oi : g.ops) {
             const Op& op = c->ops[oi];
             const int rows = op.to_root ? c->R : c->M;
-            const int n_col_tiles = (int)((c->subtree_dedup ? c->pat_cols[op.child] : chunk_cols) / kBN);
+            const int n_col_tiles = (int)(panel_cols(c, op.child, chunk_cols) / kBN);
             const int row_tiles = (rows + 16 * mi - 1) / (16 * mi);
             for (int k = 0; k < K; ++k) {
                 const int32_t* e = ext + (size_t)c->slot_of[(size_t)op.child * c->Kmax + k] * nb * 2;
@@ -1115,7 +622,7 @@ int prepare_descriptors(cafe_ctx* c, DescSet& ds, int K, int64_t cols, const std
             for (int h = 2; h <= 9; ++h)
                 for (int oi : g.ops) {
                     const Op& op = c->ops[oi];
-                    const int64_t gc = c->subtree_dedup ? c->pat_cols[op.child] : cols;
+                    const int64_t gc = panel_cols(c, op.child, cols);
                     tiles_by_mi[h] += (int64_t)(((op.to_root ? c->R : c->M) + 16 * h - 1) / (16 * h)) * (gc / kBN) * K;
                 }
             mi = prune_gemm_pick_mi(tiles_by_mi, c->n_cu, c->kb);
@@ -1125,7 +632,7 @@ int prepare_descriptors(cafe_ctx* c, DescSet& ds, int K, int64_t cols, const std
             const Op& op = c->ops[oi];
             GemmOp& d = ops[op.desc];
             d.n_row_tiles = (d.rows + 16 * mi - 1) / (16 * mi);
-            const int64_t gc = c->subtree_dedup ? c->pat_cols[op.child] : cols;
+            const int64_t gc = panel_cols(c, op.child, cols);
             tiles0 += prune_gemm_tiles_xcd0(K, (int)(gc / kBN), d.n_row_tiles);
         }
         const int blocks = prune_gemm_blocks(tiles0, c->n_cu, mi, c->kb), nlb = blocks / 8;
@@ -1283,7 +790,7 @@ int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool 
             c->gemm_launches_info.push_back({(int)g_index, K, a.mi, cols});
             for (int oi : g.ops) {
                 const Op& op = c->ops[oi];
-                const double gc = (double)(c->subtree_dedup ? c->pat_cols[op.child] : cols);
+                const double gc = (double)panel_cols(c, op.child, cols);
                 const int rows = op.to_root ? c->R : c->M;
                 c->stats.gemm_flops_dense += 2.0 * rows * (c->M + 1) * gc * K;
                 c->stats.gemm_flops += 2.0 * rows * (c->M + 1) * gc * K;      // (cafe_executed_flops counts what the tiles really ran)
@@ -1435,7 +942,7 @@ double count_executed_flops(cafe_ctx* c, std::vector<double>* per_launch = nullp
         for (int oi : c->groups[L.group].ops) {
             const Op& op = c->ops[oi];
             const int rows = op.to_root ? c->R : c->M;
-            const int64_t cols = c->subtree_dedup ? c->pat_cols[op.child] : L.cols;
+            const int64_t cols = panel_cols(c, op.child, L.cols);
             const int n_ct = (int)(cols / kBN);
             const bool have_b = c->kpool.ext && c->panel_extents && c->d_tileext[op.child];
             if (have_b) {
@@ -1775,7 +1282,7 @@ int cafe_get_extents(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* mat
     }
     if (n_tiles) *n_tiles = 0;
     if (panel_ext && !leaf && ctx->panel_extents && ctx->d_tileext[node]) {
-        const int nt = (int)((ctx->subtree_dedup ? ctx->pat_cols[node] : ctx->Fp) / kBN);
+        const int nt = (int)(panel_cols(ctx, node, ctx->Fp) / kBN);
         if (panel_ext_len < (size_t)2 * nt) { set_err(ctx, "cafe_get_extents: panel_ext too small"); return CAFE_ERR_ARGUMENT; }
         HIP_TRY(ctx, hipMemcpy(panel_ext, ctx->d_tileext[node] + (size_t)category * nt * 2, sizeof(int32_t) * 2 * nt, hipMemcpyDeviceToHost));
         if (n_tiles) *n_tiles = nt;
@@ -1797,7 +1304,7 @@ int cafe_debug_column_extents(cafe_ctx* ctx, int32_t node, int32_t category, int
         set_err(ctx, "cafe_debug_column_extents: no extents for this node");
         return CAFE_ERR_ARGUMENT;
     }
-    const int64_t cols = ctx->subtree_dedup ? ctx->pat_cols[node] : ctx->Fp;
+    const int64_t cols = panel_cols(ctx, node, ctx->Fp);
     if (n_cols) *n_cols = cols;
     if (out_len < (size_t)2 * cols) { set_err(ctx, "cafe_debug_column_extents: out too small"); return CAFE_ERR_ARGUMENT; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1937,7 +1444,7 @@ int cafe_debug_launch_flops(cafe_ctx* ctx, double* executed, double* all_k_tiles
             all_k_tiles[i] = 0;
             for (int oi : ctx->groups[L.group].ops) {
                 const Op& op = ctx->ops[oi];
-                all_k_tiles[i] += 2.0 * (op.to_root ? ctx->R : ctx->M) * (ctx->M + 1) * (double)(ctx->subtree_dedup ? ctx->pat_cols[op.child] : L.cols) * L.K;
+                all_k_tiles[i] += 2.0 * (op.to_root ? ctx->R : ctx->M) * (ctx->M + 1) * (double)panel_cols(ctx, op.child, L.cols) * L.K;
             }
         }
         if (tile_height) tile_height[i] = L.mi;

@@ -281,7 +281,7 @@ int cafe_matrix_size(const cafe_ctx* ctx);
  * 0 (default): no events. */
 int cafe_set_profiling(cafe_ctx* ctx, int on);
 /* 1: capture the call's fixed launch sequence once per (model, K) in a hipGraph and replay it (not while profiling);
- * 0 (default; environment CAFE_USE_GRAPH at cafe_create turns it on): enqueue launch by launch.  Same kernels, same
+ * 0 (default): enqueue launch by launch.  Same kernels, same
  * arguments, same bits; which is faster depends on the runtime. */
 int cafe_set_graphs(cafe_ctx* ctx, int on);
 /* diagnostic: K2's row tile is 16*mi rows, mi = 2..9, normally chosen per launch; mi forces one, 0 restores the choice */
