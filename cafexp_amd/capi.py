@@ -62,6 +62,16 @@ class CafeStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CafeSimProblem(C.Structure):
+    _fields_ = [
+        ("n_nodes", C.c_int32), ("parent", _i32p), ("branch_length", _f64p), ("lambda_index", _i32p), ("leaf_taxon", _i32p),
+        ("n_taxa", C.c_int32), ("n_lambdas", C.c_int32), ("lambdas", _f64p), ("max_family_size", C.c_int32),
+        ("n_families", C.c_int64), ("root_size", _i32p), ("chunk_size", C.c_int32), ("chunk_multiplier", _f64p),
+        ("n_deviations", C.c_int32), ("error_model", _f64p), ("error_model_max_size", C.c_int32), ("device", C.c_int32),
+        ("workspace_limit", C.c_size_t),
+    ]
+
+
 EXPORTS = [
     "cafe_abi_version", "cafe_create", "cafe_destroy", "cafe_last_error", "cafe_score", "cafe_score_partial",
     "cafe_finish_partial", "cafe_family_results", "cafe_get_matrix", "cafe_get_root_likelihoods", "cafe_get_stats",
@@ -70,7 +80,7 @@ EXPORTS = [
     "cafe_comm_unique_id", "cafe_comm_attach", "cafe_comm_detach", "cafe_shard_plan", "cafe_shard_plan_scaled", "cafe_create_sharded",
     "cafe_sharded_destroy", "cafe_sharded_last_error", "cafe_sharded_score", "cafe_sharded_family_results",
     "cafe_sharded_size", "cafe_sharded_context", "cafe_set_graphs", "cafe_executed_flops", "cafe_debug_tile_range_flops", "cafe_get_extents", "cafe_debug_launch_flops", "cafe_debug_launch_ms", "cafe_debug_plan_check",
-    "cafe_debug_fail_next", "cafe_debug_column_extents", "cafe_debug_leaf_transposes",
+    "cafe_debug_fail_next", "cafe_debug_column_extents", "cafe_debug_leaf_transposes", "cafe_simulate",
 ]
 CAFE_COMM_ID_BYTES = 128
 
@@ -170,6 +180,8 @@ def load():
     L.cafe_sharded_context.argtypes = [C.c_void_p, C.c_int32]
     L.cafe_debug_fail_next.restype = C.c_int
     L.cafe_debug_fail_next.argtypes = [C.c_void_p, C.c_int]
+    L.cafe_simulate.restype = C.c_int
+    L.cafe_simulate.argtypes = [C.POINTER(CafeSimProblem), C.c_uint64, _i32p, _i32p, C.c_char_p, C.c_size_t]
     _lib = L
     return L
 
@@ -577,6 +589,60 @@ def build_matrices(n: int, lambdas, ts, device: int = 0, layout: int = 0) -> np.
     if rc:
         raise CafeError("cafe_build_matrices failed with code %d" % rc)
     return out
+
+
+def simulate(pb: Problem, lambdas, max_family_size: int, root_size, seed: int, chunk_size: int = 50, chunk_multiplier=None,
+             error_model=None, error_model_max_size: int = 0, device: int = 0, workspace_limit: int = 0, node_sizes: bool = True):
+    """cafe_simulate: gene families simulated down pb's tree (its parent / branch_length / lambda_index / leaf_taxon; its
+    families are not read) from root_size[F], every child size drawn from the order-S transition matrices of the chunk's
+    lambdas * chunk_multiplier[f // chunk_size].  error_model: [S][n_deviations] table of get_probs(c), with
+    error_model_max_size = error_model::get_max_family_size().  Returns (leaf_counts int32 [F][n_taxa], node_sizes int32
+    [F][n_nodes] or None)."""
+    keep = []
+
+    def k(a, dt):
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a
+    lam = k(np.atleast_1d(lambdas), np.float64)
+    roots = k(root_size, np.int32).reshape(-1)
+    F = len(roots)
+    cp = CafeSimProblem()
+    cp.n_nodes = pb.n_nodes
+    cp.parent = _p(k(pb.parent, np.int32), _i32p)
+    cp.branch_length = _p(k(pb.branch_length, np.float64), _f64p)
+    cp.lambda_index = _p(k(pb.lambda_index, np.int32), _i32p)
+    cp.leaf_taxon = _p(k(pb.leaf_taxon, np.int32), _i32p)
+    cp.n_taxa = pb.n_taxa
+    cp.n_lambdas = len(lam)
+    cp.lambdas = _p(lam, _f64p)
+    cp.max_family_size = max_family_size
+    cp.n_families = F
+    cp.root_size = _p(roots, _i32p)
+    cp.chunk_size = chunk_size
+    if chunk_multiplier is not None:
+        cm = k(chunk_multiplier, np.float64).reshape(-1)
+        n_chunks = (F + chunk_size - 1) // chunk_size if chunk_size > 0 else min(F, 1)
+        if len(cm) < n_chunks:
+            raise CafeError("chunk_multiplier needs %d entries" % n_chunks)
+        cp.chunk_multiplier = _p(cm, _f64p)
+    if error_model is not None:
+        em = k(error_model, np.float64)
+        if em.ndim != 2 or em.shape[0] < max_family_size:
+            raise CafeError("error_model needs [S][n_deviations] entries")
+        em = k(em[:max_family_size], np.float64)
+        cp.n_deviations = em.shape[1]
+        cp.error_model = _p(em, _f64p)
+        cp.error_model_max_size = error_model_max_size
+    cp.device = device
+    cp.workspace_limit = workspace_limit
+    leaf = np.empty((F, pb.n_taxa), dtype=np.int32)
+    nodes = np.empty((F, pb.n_nodes), dtype=np.int32) if node_sizes else None
+    err = C.create_string_buffer(512)
+    rc = load().cafe_simulate(C.byref(cp), seed, _p(leaf, _i32p), _p(nodes, _i32p), err, 512)
+    if rc:
+        raise CafeError("code %d: %s" % (rc, err.value.decode()))
+    return leaf, nodes
 
 
 def probe_fp64_mfma(device: int = 0) -> float:

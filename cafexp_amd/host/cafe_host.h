@@ -154,11 +154,18 @@ public:
 };
 
 // ---------------------------------------------------------------- root priors
+extern std::mt19937 randomizer_engine;                     // the reference's global engine (main.cpp:3)
+
 class root_distribution {                                  // src/root_distribution.{h,cpp}
     std::vector<int> _v;
 public:
     void vectorize(const std::map<int, int>& rootdist);
     void vectorize_uniform(int max) { _v.assign(max, 1); }
+    void vectorize_increasing(int max);                    // 0, 1, .., max-1
+    int max() const;
+    bool empty() const { return _v.empty(); }
+    int select_randomly(std::mt19937& engine = randomizer_engine) const;     // a uniformly chosen entry
+    void pare(size_t new_size, std::mt19937& engine = randomizer_engine);    // shuffle, keep new_size, sort (if size >= new_size)
     void vector(const std::vector<int>& v) { _v = v; }
     size_t size() const { return _v.size(); }
     int at(size_t i) const;
@@ -506,6 +513,27 @@ double pvalue(double v, const std::vector<double>& conddist);                   
 std::vector<double> compute_pvalues(const clade* p_tree, const std::vector<gene_family>& families, const lambda* p_lambda,
                                     int number_of_simulations, int max_family_size, int max_root_family_size, int device = 0,
                                     pvalue_work* keep = nullptr);                                     // probability.cpp:418
+
+// ---------------------------------------------------------------- simulation (the reference's -s; src/simulator.cpp)
+const size_t LAMBDA_PERTURBATION_STEP_SIZE = 50;                    // families per simulation lambda (configure.ac default)
+struct simulation {
+    std::vector<const clade*> order;       // reverse level order: the writers' columns
+    size_t n_families = 0;
+    int max_family_size = 0;               // S: 100, or 2 * the root distribution's maximum
+    std::vector<int32_t> sizes;            // [family][index in order]
+    std::vector<double> multipliers;       // the gamma model's multiplier per chunk (empty for the base model)
+};
+// simulate_processes draw for draw on randomizer_engine; gamma_alpha > 0: the gamma model (one Gamma(alpha, 1/alpha)
+// multiplier per chunk).  rootdist empty: nsims families with root sizes 0..99; else the vectorized distribution, pared to
+// nsims when 0 < nsims <= its size.  Matrices from cafe_build_matrices on `device`.
+simulation simulate_families(const clade* p_tree, const lambda* p_lambda, const error_model* p_error_model, const std::map<int, int>& rootdist,
+                             int nsims, double gamma_alpha, int device);
+// the same families' distribution from cafe_simulate: root sizes and multipliers from an engine seeded by `seed`
+simulation simulate_families_device(const clade* p_tree, const lambda* p_lambda, const error_model* p_error_model, const std::map<int, int>& rootdist,
+                                    int nsims, double gamma_alpha, int device, uint64_t seed, size_t workspace_limit = 0);
+double average_multiplier(const simulation& sim);                   // write_average_multiplier's value (NaN without draws)
+// simulator::print_simulations (simulator.cpp:150-186): leaves only, or every node (interior ones by order index)
+void print_simulations(std::ostream& ost, bool include_internal_nodes, const simulation& sim);
 
 // ---------------------------------------------------------------- Nelder-Mead driver (src/optimizer.cpp)
 struct optimizer_result {

@@ -2,6 +2,9 @@
 // [-e] [-p] [-f] [-z]` (src/cafexp.cpp:175, src/execute.cpp:42-150) that ends in scorer calls.
 // With a fixed lambda it evaluates one infer_family_likelihoods call; without, it runs the
 // Nelder-Mead search on the GPU scorer.  Output: one JSON object on stdout.
+#include <sys/stat.h>
+
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -20,7 +23,12 @@ static void usage() {
         "                  [-e [ERRMODEL]] [-p [POISSON_LAMBDA]] [-f ROOTDIST] [-z] [-s SEED] [-I MAXITER] [-d DEVICE | --gpus N] [--reps N] [--family-out FILE] [-o OUTDIR] [--limit N]\n"
         "                  [--pvalues NSIM [--pvalues-device] [--pvalues-out FILE] [--pvalues-cond FILE:K]] [--sizes M,R]\n"
         "                  [--reconstruct [-P PVALUE]]   (with -o: the reports of reconstruction::write_results)\n"
-        "  --gpus N: the scorer calls shard the families over devices 0..N-1 (one host thread per GPU, one RCCL all-reduce per call)\n");
+        "  --gpus N: the scorer calls shard the families over devices 0..N-1 (one host thread per GPU, one RCCL all-reduce per call)\n"
+        "simulation (the reference's -s; -s here is the SEED): cafexp_hip -t TREE (-l LAMBDA | -m L1,L2,.. -y LAMBDA_TREE) --simulate [N]\n"
+        "                  [-k K] [-a ALPHA] [-e ERRMODEL] [-f ROOTDIST] [-s SEED] [-o OUTDIR] [--simulate-device [--workspace BYTES]] [-d DEVICE]\n"
+        "  writes OUTDIR (default results)/simulation.txt and simulation_truth.txt; N families (root sizes 0..99), or the\n"
+        "  -f distribution pared to N.  --simulate-device: the draws on the GPU (same distribution, another sample).\n"
+        "  The gamma model (-k > 1 or -a > 0) needs -a > 0: the reference would draw from Gamma(-1, -1) instead.\n");
 }
 
 static std::string slurp_first_line(const std::string& path) {
@@ -37,9 +45,85 @@ static void print_num(const char* key, double v, bool comma = true) {
     else std::printf("\"%s\": %.17g%s", key, v, comma ? ", " : "");
 }
 
+// simulator::simulate (simulator.cpp:113-147) with the checks of input_parameters::check_input (io.cpp:55-98)
+static int simulate_main(const std::string& tree_path, const std::string& fam_path, const std::string& rootdist_path,
+                         const std::string& lambda_tree_path, const std::string& multi, const std::string& err_path, bool use_err,
+                         double fixed_lambda, double fixed_alpha, int k, int nsims, bool on_device, uint64_t seed, int device,
+                         size_t workspace, std::string out_dir) {
+    try {
+        if (!multi.empty() && lambda_tree_path.empty()) throw std::runtime_error("Multiple lambda values (-m) specified with no lambda tree (-y)");
+        if (!fam_path.empty() && !rootdist_path.empty()) throw std::runtime_error("Options -i and -f are mutually exclusive.");
+        if (fixed_lambda <= 0.0 && multi.empty()) throw std::runtime_error("Cannot simulate without initial lambda values");
+        const bool gamma = fixed_alpha > 0 || k > 1;                 // build_models (core.cpp:26)
+        if (gamma && !(fixed_alpha > 0)) throw std::runtime_error("Cannot simulate gamma clusters without an alpha value");
+        if (use_err && err_path.empty()) throw std::runtime_error("Simulation needs an error model file (-e FILE)");
+        user_data d;
+        d.p_tree.reset(parse_newick(slurp_first_line(tree_path), false));
+        if (!err_path.empty()) {
+            std::ifstream f(err_path);
+            if (!f.is_open()) throw std::runtime_error("Failed to open " + err_path + ". Exiting...");
+            d.p_error_model.reset(new error_model);
+            read_error_model_file(f, d.p_error_model.get());
+        }
+        if (!lambda_tree_path.empty()) {
+            d.p_lambda_tree.reset(parse_newick(slurp_first_line(lambda_tree_path), true));
+            d.p_tree->validate_lambda_tree(d.p_lambda_tree.get());
+        }
+        if (fixed_lambda > 0) d.p_lambda.reset(new single_lambda(fixed_lambda));
+        if (!multi.empty()) {
+            std::vector<double> v;
+            std::stringstream ss(multi);
+            std::string tok;
+            while (std::getline(ss, tok, ',')) v.push_back(std::stod(tok));
+            d.p_lambda.reset(new multiple_lambda(d.p_lambda_tree->get_lambda_index_map(), v));
+        }
+        if (!rootdist_path.empty()) {
+            std::ifstream f(rootdist_path);
+            if (!f.is_open()) throw std::runtime_error("Failed to open file '" + rootdist_path + "'");
+            read_rootdist(f, d.rootdist);
+        }
+        const double alpha = gamma ? fixed_alpha : 0.0;
+        auto t0 = std::chrono::steady_clock::now();
+        simulation sim = on_device
+            ? simulate_families_device(d.p_tree.get(), d.p_lambda.get(), d.p_error_model.get(), d.rootdist, nsims, alpha, device, seed, workspace)
+            : simulate_families(d.p_tree.get(), d.p_lambda.get(), d.p_error_model.get(), d.rootdist, nsims, alpha, device);
+        const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (out_dir.empty()) out_dir = "results";                   // filename() (core.h:196)
+        if (::mkdir(out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("Failed to create directory " + out_dir);
+        auto t1 = std::chrono::steady_clock::now();
+        {
+            std::ofstream leaves(out_dir + "/simulation.txt");
+            print_simulations(leaves, false, sim);
+            std::ofstream truth(out_dir + "/simulation_truth.txt");
+            print_simulations(truth, true, sim);
+            if (!leaves || !truth) throw std::runtime_error("Failed to write the simulations to " + out_dir);
+        }
+        const double write_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+        const double avg = average_multiplier(sim);
+        if (fixed_lambda > 0) std::cout << "Average multiplier for simulated values: " << avg << std::endl;     // simulator.cpp:141-144
+        std::printf("{\"model\": \"%s\", \"mode\": \"%s\", \"n_families\": %zu, \"max_family_size\": %d, \"seconds\": %.6f, \"write_seconds\": %.6f, ",
+                    gamma ? "Gamma" : "Base", on_device ? "device" : "host", sim.n_families, sim.max_family_size, seconds, write_s);
+        print_num("average_multiplier", avg, false);
+        if (!sim.multipliers.empty() && sim.multipliers.size() <= 1000) {     // one per chunk of 50 families
+            std::printf(", \"multipliers\": [");
+            for (size_t i = 0; i < sim.multipliers.size(); ++i) std::printf("%s%.17g", i ? ", " : "", sim.multipliers[i]);
+            std::printf("]");
+        }
+        std::printf("}\n");
+    } catch (const std::exception& e) {
+        std::fflush(stdout);
+        std::fprintf(stderr, "cafexp_hip: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     std::string tree_path, fam_path, lambda_tree_path, multi, err_path, rootdist_path, family_out, out_dir;
     std::string pvalues_out, pvalues_cond;
+    int simulate_n = -1;                                         // -1: estimation; >= 0: simulation (0 = no count given)
+    bool simulate_on_device = false;
+    size_t sim_workspace = 0;
     int pvalue_sims = 0, force_m = -1, force_r = -1;
     bool do_reconstruct = false, pvalues_on_device = false;
     double test_pvalue = 0.05;                                   // input_parameters::pvalue default (io.h)
@@ -83,7 +167,16 @@ int main(int argc, char** argv) {
         else if (a == "--pvalues") pvalue_sims = std::stoi(next());
         else if (a == "--pvalues-out") pvalues_out = next();
         else if (a == "--pvalues-cond") pvalues_cond = next();
+        else if (a == "--simulate") { std::string v = optional(); simulate_n = v.empty() ? 0 : std::stoi(v); }
+        else if (a == "--simulate-device") simulate_on_device = true;
+        else if (a == "--workspace") sim_workspace = std::stoull(next());
         else { usage(); return 2; }
+    }
+    if (simulate_n >= 0) {
+        if (tree_path.empty()) { usage(); return 2; }
+        if (have_seed) randomizer_engine.seed(seed);
+        return simulate_main(tree_path, fam_path, rootdist_path, lambda_tree_path, multi, err_path, use_err, fixed_lambda, fixed_alpha, k,
+                             simulate_n, simulate_on_device, have_seed ? seed : randomizer_engine(), device, sim_workspace, out_dir);
     }
     if (tree_path.empty() || fam_path.empty()) { usage(); return 2; }
     if (have_seed) randomizer_engine.seed(seed);

@@ -224,6 +224,42 @@ int cafe_root_max(cafe_ctx* ctx, const cafe_params* params, double* out);
  * params->lambdas is the only field read; 1 <= n_simulations <= 2048. */
 int cafe_pvalues(cafe_ctx* ctx, const cafe_params* params, int32_t n_simulations, uint64_t seed, double* pvalues);
 
+/* Gene-family simulation (the reference's -s: simulator::simulate_processes, src/simulator.cpp:62-103, with
+ * set_weighted_random_family_size / adjust_for_error_model, src/probability.cpp:320-377).  Families are simulated down
+ * the tree from the given root sizes: every child size is drawn from row `parent size` of the branch's transition matrix
+ * (order S = max_family_size, quantized key (lambda * multiplier, t) as matrix_cache_key), restricted to sizes 0..S-1; a
+ * parent of size 0 gives 0; an all-zero row (saturated or degenerate branch) gives 0.  Family f belongs to chunk
+ * f / chunk_size, whose lambdas are lambdas[i] * chunk_multiplier[chunk] (LAMBDA_PERTURBATION_STEP_SIZE; gamma_core.cpp:88).
+ * With an error model, a leaf of size c draws u and becomes c-1 if u < probs[0], c+1 if u > 1 - probs[2]
+ * (probs = error_model[c * n_deviations ..]); c >= error_model_max_size fails with CAFE_ERR_ARGUMENT and the reference's
+ * message.  The draws come from Philox4x32-10 keyed by `seed` with counter (family, node, stream): the result depends on
+ * the arguments only -- not on workspace_limit, batching or device -- and is a different sample than the reference's
+ * engine would give (cafexp_amd/host/simulator.cpp follows the reference draw for draw).
+ * Chunks whose quantized keys agree share their matrices; the chunks are processed in batches whose matrices and
+ * buffers fit workspace_limit bytes (0 = automatic; a batch always holds at least one chunk's matrices). */
+typedef struct cafe_sim_problem {
+    int32_t n_nodes;                 /* tree nodes; any order with children before parents; exactly one root */
+    const int32_t* parent;           /* [n_nodes] parent index, -1 for the root */
+    const double*  branch_length;    /* [n_nodes]; the root's entry is ignored */
+    const int32_t* lambda_index;     /* [n_nodes] 0-based lambda of the branch above the node; NULL = all 0 */
+    const int32_t* leaf_taxon;       /* [n_nodes] column of leaf_counts for a leaf, -1 for interior nodes */
+    int32_t  n_taxa;
+    int32_t  n_lambdas;
+    const double* lambdas;           /* [n_lambdas]: one lambda > 0, or several >= 0 (lambda.h:58, lambda.cpp:59) */
+    int32_t  max_family_size;        /* S, 2..2048: sizes 0..S-1 (100 without -f, 2 * max root size with -f) */
+    int64_t  n_families;
+    const int32_t* root_size;        /* [n_families], each 0..S-1 */
+    int32_t  chunk_size;             /* families per lambda multiplier (50 in the reference); 0 = one chunk */
+    const double* chunk_multiplier;  /* [ceil(n_families / chunk_size)] >= 0, or NULL = all 1 */
+    int32_t  n_deviations;           /* >= 3 with an error model (only probs[0] and probs[2] are read) */
+    const double* error_model;       /* [S][n_deviations] error_model::get_probs(c), or NULL */
+    int32_t  error_model_max_size;   /* error_model::get_max_family_size(): leaf sizes >= it fail */
+    int32_t  device;                 /* HIP device ordinal */
+    size_t   workspace_limit;        /* bytes of device memory a batch may take; 0 = automatic */
+} cafe_sim_problem;
+/* leaf_counts[n_families][n_taxa] and node_sizes[n_families][n_nodes] (host memory; either may be NULL, not both). */
+int cafe_simulate(const cafe_sim_problem* problem, uint64_t seed, int32_t* leaf_counts, int32_t* node_sizes, char* err, size_t errlen);
+
 /* Ancestral reconstruction.  Pupko's joint reconstruction as reconstruct_gene_family runs it
  * (gene_family_reconstructor.cpp:13-165; base_model.cpp:145, gamma_core.cpp:301): for every category k (one for
  * the base model; lambda * multipliers[k] for the gamma model) and family f, the reconstructed size of every node
