@@ -23,6 +23,7 @@ CAFE_FLAG_NO_SUBTREE_DEDUP = 2
 CAFE_MODEL_BASE, CAFE_MODEL_GAMMA = 0, 1
 
 _i32p = C.POINTER(C.c_int32)
+_i64p = C.POINTER(C.c_int64)
 _f64p = C.POINTER(C.c_double)
 _f32p = C.POINTER(C.c_float)
 
@@ -81,6 +82,7 @@ EXPORTS = [
     "cafe_sharded_destroy", "cafe_sharded_last_error", "cafe_sharded_score", "cafe_sharded_family_results",
     "cafe_sharded_size", "cafe_sharded_context", "cafe_set_graphs", "cafe_executed_flops", "cafe_debug_tile_range_flops", "cafe_get_extents", "cafe_debug_launch_flops", "cafe_debug_launch_ms", "cafe_debug_plan_check",
     "cafe_debug_fail_next", "cafe_debug_column_extents", "cafe_debug_leaf_transposes", "cafe_simulate",
+    "cafe_score_per_family",
 ]
 CAFE_COMM_ID_BYTES = 128
 
@@ -128,6 +130,8 @@ def load():
     L.cafe_get_root_likelihoods.argtypes = [C.c_void_p, C.c_int64, C.c_int32, _f64p, C.c_size_t]
     L.cafe_root_max.restype = C.c_int
     L.cafe_root_max.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p]
+    L.cafe_score_per_family.restype = C.c_int
+    L.cafe_score_per_family.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p]
     L.cafe_pvalues.restype = C.c_int
     L.cafe_pvalues.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.c_uint64, _f64p]
     L.cafe_reconstruct.restype = C.c_int
@@ -349,6 +353,19 @@ class Context:
             fo.family_likelihood = _p(res["family_likelihood"], _f64p)
         self._check(self._lib.cafe_family_results(self._h, C.byref(fo)))
         return res
+
+    def score_per_family(self, pr: Params, family, lambdas) -> np.ndarray:
+        """cafe_score_per_family: lnL of every listed family under ITS OWN lambdas (lambdas[n][n_lambdas]; a 1-d array is
+        one lambda per family).  -inf where score() would return +inf for that vector.  pr gives the prior and the error
+        model; pr.lambdas is not read.  Base model only."""
+        fam = np.ascontiguousarray(family, dtype=np.int64).reshape(-1)
+        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(len(fam), -1)
+        if lam.shape[1] != self.problem.n_lambdas:
+            raise ValueError("lambdas must be [%d][%d]" % (len(fam), self.problem.n_lambdas))
+        cp, keep = self._params(pr)
+        out = np.empty(len(fam))
+        self._check(self._lib.cafe_score_per_family(self._h, C.byref(cp), len(fam), _p(fam, _i64p), _p(lam, _f64p), _p(out, _f64p)))
+        return out
 
     def root_max(self, lambdas) -> np.ndarray:
         """max_j L_root[j] per family under the plain lambdas (p-value path, probability.cpp:313, :399)."""

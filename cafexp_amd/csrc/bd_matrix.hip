@@ -32,6 +32,7 @@
 // pi(n) = 1/n, so P[s][c] = (s/c) P[c][s] for s,c >= 1; Pt's row c is P's row c scaled by s/c
 // (one extra rounding), Pt's row 0 is P[s][0] = a^s, and P's row 0 (e_0) is never stored: K2
 // copies that row (prune_gemm.hip).
+#include "bd_row.h"
 #include "cafe_kernels.h"
 
 // diagnostic: -D'CAFE_EXPERIMENT_K1_STORE_IF=&& n < 0' builds K1 without its global stores (the matrices are wrong): what is
@@ -53,16 +54,6 @@ struct InvTable {
 };
 __constant__ InvTable kInvR = InvTable();
 
-// DPP move of a double (two 32-bit halves); lanes without a source read 0
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ double dpp_move(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-constexpr int kDppRowShr1 = 0x111, kDppRowShr2 = 0x112, kDppRowShr4 = 0x114, kDppRowShr8 = 0x118;
-constexpr int kDppWaveShr1 = 0x138, kDppRowBcast15 = 0x142, kDppRowBcast31 = 0x143;
-
 template <int E, bool KMAJOR>
 __device__ __forceinline__ void bd_matrix_build_one(const MatrixPool& pool, const SlotParam sp, int slot) {
     const int lane = threadIdx.x;
@@ -76,17 +67,8 @@ __device__ __forceinline__ void bd_matrix_build_one(const MatrixPool& pool, cons
     const int j0 = lane * E;                          // where they are stored
     const double a = sp.alpha, q = sp.oma2;
 
-    double apow[E];                      // a^(i+1)
-    apow[0] = a;
-#pragma unroll
-    for (int i = 1; i < E; ++i) apow[i] = apow[i - 1] * a;
-    double ratio[4];                     // (a^E)^(2^d): the in-row scan steps
-    ratio[0] = apow[E - 1];
-#pragma unroll
-    for (int d = 1; d < 4; ++d) ratio[d] = ratio[d - 1] * ratio[d - 1];
-    // what a lane of rows 1, 3 (rows 2, 3) adds of the total that lane 15 of the row before (lane 31) holds
-    const double w15 = pow(apow[E - 1], (double)((lane & 15) + 1));
-    const double w31 = lane >= 32 ? pow(apow[E - 1], (double)(lane - 31)) : 0.0;
+    BdRowConsts<E> rc;                   // the powers of a the row step needs (bd_row.h)
+    rc.init(a, q, lane);
 
     // Columns past the matrix (c0 + i >= n: the tail of the last lanes) must be stored as zeros.  Up to E = 16 they ARE zeros: the
     // lane multiplies h by a per-element (1-a)^2 that is 0 there, so p stays exactly 0 (a p + 0 h) and nothing is masked per
@@ -205,27 +187,7 @@ __device__ __forceinline__ void bd_matrix_build_one(const MatrixPool& pool, cons
             store_row(r, z);
             continue;
         }
-        double left = dpp_move<kDppWaveShr1>(p[E - 1]);
-        if (lane == 0) left = KMAJOR ? p0 : 0.0;
-        double h[E];
-        h[0] = left;
-#pragma unroll
-        for (int i = 1; i < E; ++i) h[i] = fma(a, h[i - 1], p[i - 1]);
-        double S = h[E - 1];             // inclusive scan of the lane totals with ratio a^E
-        S = fma(ratio[0], dpp_move<kDppRowShr1>(S), S);          // lanes without a source add ratio * 0
-        S = fma(ratio[1], dpp_move<kDppRowShr2>(S), S);
-        S = fma(ratio[2], dpp_move<kDppRowShr4>(S), S);
-        S = fma(ratio[3], dpp_move<kDppRowShr8>(S), S);
-        S = fma(w15, dpp_move<kDppRowBcast15, 0xa>(S), S);       // rows 1 and 3 take the total of rows 0 and 2
-        S = fma(w31, dpp_move<kDppRowBcast31, 0xc>(S), S);       // rows 2 and 3 take the total of rows 0..1
-        const double carry = dpp_move<kDppWaveShr1>(S);          // lane 0: 0
-#pragma unroll
-        for (int i = 0; i < E; ++i) {
-            double hh = fma(apow[i], carry, h[i]);
-            double v = fma(a, p[i], (QM ? qm[i] : q) * hh);
-            v = v < 1.0 ? v : 1.0;
-            p[i] = v > 0.0 ? v : 0.0;
-        }
+        bd_row_step<E, QM>(rc, qm, KMAJOR ? p0 : 0.0, lane, p);
         p0 *= a;
         if (KMAJOR) {
             const double inv_r = kInvR.v[r];               // = 1.0 / (double)r, bit for bit

@@ -173,6 +173,10 @@ struct cafe_ctx {
     // altogether is caught by the deadline below (the waiting ranks abort their communicator and return CAFE_ERR_DEVICE).
     double comm_timeout_s = 120.0;           // CAFE_COMM_TIMEOUT_S at cafe_comm_attach / cafe_create_sharded; <= 0: wait for ever
     double* h_poison = nullptr;              // pinned {0, NaN}
+    // cafe_score_per_family (family_lambda.hip): its workspace, kept between calls and grown on demand
+    void* pf_dev = nullptr;
+    size_t pf_dev_bytes = 0;
+    int64_t pf_max_batch = 0;                // CAFE_PER_FAMILY_BATCH: at most that many families per batch (diagnostic; 0 = what fits)
     int debug_fail_in = 0;                   // cafe_debug_fail_next: the n-th next enqueue fails behind its K1 launch
 
     // last call
@@ -280,6 +284,8 @@ int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_simulations, uint
 cafe_ctx* create_child_for_device_counts(const cafe_ctx* parent, int64_t n_families);
 void destroy_child(cafe_ctx* c);
 int enqueue_rootmax(cafe_ctx* c, const double* lambdas, hipStream_t s);
+// one scorer evaluation per listed family, each under its own lambdas (family_lambda.hip)
+int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_t* family, const double* lambdas, double* family_lnl);
 // multi-GPU (cafe_sharded.hip)
 int comm_allreduce_pair(cafe_ctx* c, double* d_pair, hipStream_t s);
 void comm_release(cafe_ctx* c);

@@ -63,7 +63,7 @@ void free_device(cafe_ctx* c) {
     auto free_desc = [](DescSet& d) { hipFree(d.d_gemm_ops); hipFree(d.d_plan_desc); hipFree(d.d_plan); d = DescSet(); };
     free_desc(c->desc);
     for (auto& g : c->graphs) free_desc(g.second.desc);
-    hipFree(c->d_gather_ops); hipFree(c->d_lt); hipFree(c->d_lt_pairs);
+    hipFree(c->d_gather_ops); hipFree(c->d_lt); hipFree(c->d_lt_pairs); hipFree(c->pf_dev);
     if (c->ev_upload) hipEventDestroy(c->ev_upload);
     for (auto& e : c->ev) if (e) hipEventDestroy(e);
     for (auto& e : c->gemm_ev) hipEventDestroy(e);
@@ -86,6 +86,7 @@ Switches read_switches(cafe_ctx* c) {
     sw.gemm_stamps = std::getenv("CAFE_GEMM_STAMPS");        // per-workgroup block timeline of a K2 launch (cafe_debug_stamps)
     sw.dump_schedule = std::getenv("CAFE_DUMP_SCHEDULE");    // the launch list with its column counts, on stderr
     if ((e = std::getenv("CAFE_GEMM_STAMPS_LAUNCH"))) c->stamps_launch = std::atol(e);   // stamps of that K2 launch only
+    if ((e = std::getenv("CAFE_PER_FAMILY_BATCH"))) c->pf_max_batch = std::max(0L, std::atol(e));   // cafe_score_per_family: families per batch
     c->no_asm_skip = std::getenv("CAFE_NO_ASM_SKIP") != nullptr;   // the assemble passes write every row
     if ((e = std::getenv("CAFE_FORCE_TILE")) && std::atoi(e) >= 2 && std::atoi(e) <= 9) c->force_mi = std::atoi(e);   // like cafe_debug_force_tile
     if ((e = std::getenv("CAFE_PLAN_FIXED"))) c->plan_fixed = std::max(0, atoi(e));   // the tile planner's cost of a tile beyond its K loop

@@ -17,6 +17,7 @@
 #include <cstdint>
 #include <functional>
 #include <iosfwd>
+#include <deque>
 #include <map>
 #include <memory>
 #include <random>
@@ -251,7 +252,8 @@ public:
 // Flattens (tree in `order` = children before parents, lambda structure, counts[n_families][leaves of `order`]) into a
 // cafe_problem and creates the device context; throws std::runtime_error on failure.
 cafe_ctx* create_device_context(const lambda* lam, const std::vector<const clade*>& order, const int32_t* counts, int64_t n_families,
-                                 int max_family_size, int max_root_family_size, int max_categories, int n_deviations, int device);
+                                 int max_family_size, int max_root_family_size, int max_categories, int n_deviations, int device,
+                                 size_t workspace_limit = 0);
 
 // The two models whose infer_family_likelihoods runs on the GPU through the C ABI.
 class hip_model_base : public model {
@@ -260,6 +262,7 @@ protected:
     int _ctx_categories = 0;
     int _ctx_lambda_sig = -1;                                        // lambda kind/count the context was built for
     int _device = 0;
+    size_t _workspace_limit = 0;
     // several GPUs: the scorer calls go to a cafe_sharded (family shards, one host thread per device, one RCCL
     // all-reduce per call); what runs once after the search (reconstruction, p-values) stays on the first device
     std::vector<int> _devices;
@@ -282,6 +285,7 @@ public:
     using model::model;
     ~hip_model_base() override;
     void set_device(int d) { _device = d; }
+    void set_workspace_limit(size_t bytes) { _workspace_limit = bytes; }     // cafe_problem::workspace_limit of the contexts made from now on
     void set_devices(const std::vector<int>& d) { _devices = d; if (!d.empty()) _device = d[0]; }
     // compute_pvalues with the Monte-Carlo simulation on the device too (cafe_pvalues): statistical agreement with the
     // reference's procedure, not draw for draw
@@ -299,6 +303,10 @@ public:
     void write_family_likelihoods(std::ostream& ost) override;
     inference_optimizer_scorer* get_lambda_optimizer(user_data& data) override;
     reconstruction* reconstruct_ancestral_states(const std::vector<gene_family>& families, root_equilibrium_distribution* p_prior) override;   // base_model.cpp:145
+    // Scorer values (-lnL, +inf for a rejected vector or NaN) of the listed families of the model's table, each under its own
+    // lambdas[i * count .. ): one cafe_score_per_family call.  The model's lambda gives the structure (count, lambda tree) only.
+    std::vector<double> per_family_scores(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist,
+                                          const std::vector<int64_t>& family, const std::vector<double>& lambdas);
 };
 class hip_gamma_model : public hip_model_base {
     std::vector<double> _lambda_multipliers, _gamma_cat_probs;
@@ -542,6 +550,46 @@ struct optimizer_result {
     int num_iterations = 0;
     int num_scorer_calls = 0;
 };
+// One Nelder-Mead search as a state machine (the moves and stop rules of optimizer::optimize, which drives one of these):
+// trial() is the point whose score is needed next, feed() takes it.  A caller with many independent searches can gather
+// their trials, score them together and feed each its own (lambda_per_family.cpp).
+struct nm_settings {
+    int max_iterations = 300;
+    double tolx = 1e-6, tolf = 1e-6;
+    int similarity_window = 12;
+    double similarity_precision = 1e-3;
+    double delta = 0.05;                         // the first simplex: vertex i is x0 with coordinate i-1 times (1 + delta)
+};
+class nm_search {
+public:
+    struct vertex { std::vector<double> x; double f = 0; };
+    nm_search(const nm_settings& s, const std::vector<double>& x0);      // the first trial is x0 itself
+    bool done() const { return _phase == DONE; }
+    const std::vector<double>& trial() const { return _trial == kTrialReflected ? _xr : _trial == kTrialOther ? _xt : _simplex[_trial].x; }
+    void feed(double score);
+    const std::vector<double>& best() const { return _simplex[0].x; }
+    double best_score() const { return _simplex[0].f; }
+    int iterations() const { return _it; }
+    int calls() const { return _calls; }
+private:
+    enum phase { INIT, REFLECT, EXPAND, CONTRACT_IN, CONTRACT_OUT, SHRINK, DONE };
+    nm_settings _s;
+    std::vector<double> _x0;
+    int _n;
+    std::vector<vertex> _simplex;
+    std::vector<double> _mean, _xr, _xt;
+    std::deque<double> _recent;
+    static constexpr int kTrialReflected = -1, kTrialOther = -2;
+    int _trial = 0;                              // the vertex whose point is the trial, or one of the two above
+    phase _phase = INIT;
+    int _i = 0, _it = 0, _calls = 0;
+    double _fr = 0;
+    void begin_iteration();
+    void end_iteration();
+    void accept(const std::vector<double>& x, double f);
+    void start_shrink();
+};
+
 class optimizer {
     optimizer_scorer* _scorer;
 public:
@@ -553,5 +601,24 @@ public:
     std::vector<double> get_initial_guesses(int& calls);          // <= 100 retries while +inf (optimizer.cpp:345)
     optimizer_result optimize();
 };
+
+// ---------------------------------------------------------------- lambda per family (-b; src/execute.cpp:104-128)
+// estimator::estimate_lambda_per_family as ONE lock-step search: every distinct family runs its own Nelder-Mead
+// (nm_search: the reference's moves and stop rules), and per round the next trial of every unfinished family goes to the
+// device in one cafe_score_per_family call.  Starts are lambda_optimizer::initial_guesses draws from randomizer_engine,
+// one sequence per distinct family in order of first appearance, redrawn (<= 100 times) while the score is infinite.
+// A finished search is begun again from its best point (inward first simplex, high-precision stop rule) while the last one
+// still gained (lambda_per_family.cpp).
+// M, R and the prior are the whole table's, as in the reference (set_families only swaps the family list).
+struct per_family_result {
+    std::vector<std::vector<double>> lambdas;    // per family, table order
+    size_t distinct_families = 0;
+    int rounds = 0;                              // device calls
+    long evaluations = 0;                        // (family, lambda vector) pairs scored
+    long restarts = 0;                           // searches begun again from a family's best point
+};
+per_family_result estimate_lambda_per_family(hip_base_model& mdl, user_data& data, int max_iterations);
+// what the reference prints when no start has a finite score (execute.cpp:192-206)
+void initialization_failure_advice(std::ostream& ost, const std::vector<gene_family>& families);
 
 }  // namespace cafe

@@ -22,18 +22,20 @@ hip_model_base::~hip_model_base() {
 // devices: nullptr / 0 -> one context on `device` (returned through *ctx); else a sharded scorer over the listed devices
 static void create_device_objects(const lambda* lam, const std::vector<const clade*>& order, const int32_t* counts, int64_t n_families,
                                   int max_family_size, int max_root_family_size, int max_categories, int n_deviations, int device,
-                                  const std::vector<int>* devices, cafe_ctx** ctx, cafe_sharded** sharded);
+                                  const std::vector<int>* devices, cafe_ctx** ctx, cafe_sharded** sharded, size_t workspace_limit = 0);
 
 cafe_ctx* create_device_context(const lambda* lam, const std::vector<const clade*>& order, const int32_t* counts, int64_t n_families,
-                                 int max_family_size, int max_root_family_size, int max_categories, int n_deviations, int device) {
+                                 int max_family_size, int max_root_family_size, int max_categories, int n_deviations, int device,
+                                 size_t workspace_limit) {
     cafe_ctx* ctx = nullptr;
-    create_device_objects(lam, order, counts, n_families, max_family_size, max_root_family_size, max_categories, n_deviations, device, nullptr, &ctx, nullptr);
+    create_device_objects(lam, order, counts, n_families, max_family_size, max_root_family_size, max_categories, n_deviations, device, nullptr, &ctx, nullptr,
+                          workspace_limit);
     return ctx;
 }
 
 static void create_device_objects(const lambda* lam, const std::vector<const clade*>& order, const int32_t* counts, int64_t n_families,
                                   int max_family_size, int max_root_family_size, int max_categories, int n_deviations, int device,
-                                  const std::vector<int>* devices, cafe_ctx** out_ctx, cafe_sharded** out_sharded) {
+                                  const std::vector<int>* devices, cafe_ctx** out_ctx, cafe_sharded** out_sharded, size_t workspace_limit) {
     const int n = (int)order.size();
     std::map<const clade*, int> index;
     for (int i = 0; i < n; ++i) index[order[i]] = i;
@@ -54,7 +56,7 @@ static void create_device_objects(const lambda* lam, const std::vector<const cla
     pb.max_family_size = max_family_size; pb.max_root_family_size = max_root_family_size;
     pb.n_lambdas = lam->count(); pb.single_lambda = ml ? 0 : 1; pb.max_categories = max_categories;
     pb.n_deviations = n_deviations;
-    pb.device = device; pb.flags = 0; pb.workspace_limit = 0;
+    pb.device = device; pb.flags = 0; pb.workspace_limit = workspace_limit;
     char err[512];
     if (devices && !devices->empty() && out_sharded) {
         std::vector<int32_t> dev(devices->begin(), devices->end());
@@ -87,7 +89,7 @@ void hip_model_base::ensure_context(int max_categories) {
         throw std::runtime_error("hip model: a tree and a non-empty family list are required");
     const std::vector<int32_t> counts = flatten_counts(_p_tree, *_p_gene_families, _order);
     _ctx = create_device_context(_p_lambda, _order, counts.data(), (int64_t)_p_gene_families->size(), _max_family_size, _max_root_family_size,
-                                 max_categories, _p_error_model ? (int)_p_error_model->n_deviations() : 0, _device);
+                                 max_categories, _p_error_model ? (int)_p_error_model->n_deviations() : 0, _device, _workspace_limit);
     _ctx_categories = max_categories;
 }
 
@@ -167,6 +169,22 @@ double hip_base_model::infer_family_likelihoods(root_equilibrium_distribution* p
             results[i].posterior_probability = lnl[i];
         }
     return score;
+}
+
+std::vector<double> hip_base_model::per_family_scores(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist,
+                                                      const std::vector<int64_t>& family, const std::vector<double>& lambdas) {
+    ensure_context(1);
+    std::vector<float> prior_f;
+    std::vector<double> err, unused;
+    gather_call_inputs(prior, rootdist, prior_f, err, unused);
+    cafe_params pr{};
+    pr.model = CAFE_MODEL_BASE; pr.n_categories = 1; pr.prior = prior_f.data();
+    pr.error_model = err.empty() ? nullptr : err.data();
+    std::vector<double> out(family.size());
+    if (cafe_score_per_family(_ctx, &pr, (int64_t)family.size(), family.data(), lambdas.data(), out.data()) != CAFE_OK)
+        throw std::runtime_error(std::string("cafe_score_per_family: ") + cafe_last_error(_ctx));
+    for (double& v : out) v = std::isnan(v) ? std::numeric_limits<double>::infinity() : -v;      // optimizer_scorer.cpp:30
+    return out;
 }
 
 void hip_base_model::write_family_likelihoods(std::ostream& ost) {

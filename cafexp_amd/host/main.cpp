@@ -24,6 +24,8 @@ static void usage() {
         "                  [--pvalues NSIM [--pvalues-device] [--pvalues-out FILE] [--pvalues-cond FILE:K]] [--sizes M,R]\n"
         "                  [--reconstruct [-P PVALUE]]   (with -o: the reports of reconstruction::write_results)\n"
         "  --gpus N: the scorer calls shard the families over devices 0..N-1 (one host thread per GPU, one RCCL all-reduce per call)\n"
+        "lambda per family (the reference's -b): cafexp_hip -t TREE -i FAMILIES -b [-y LAMBDA_TREE] [-e ERRMODEL] [-p [L]] [-z] [-s SEED] [-I MAXITER]\n"
+        "                  [--workspace BYTES] [-o OUTDIR]   writes OUTDIR (default results)/Base_lambda_per_family.txt, one line per family\n"
         "simulation (the reference's -s; -s here is the SEED): cafexp_hip -t TREE (-l LAMBDA | -m L1,L2,.. -y LAMBDA_TREE) --simulate [N]\n"
         "                  [-k K] [-a ALPHA] [-e ERRMODEL] [-f ROOTDIST] [-s SEED] [-o OUTDIR] [--simulate-device [--workspace BYTES]] [-d DEVICE]\n"
         "  writes OUTDIR (default results)/simulation.txt and simulation_truth.txt; N families (root sizes 0..99), or the\n"
@@ -131,6 +133,7 @@ int main(int argc, char** argv) {
     double fixed_lambda = 0, fixed_alpha = -1, poisson = 0;
     int k = 1, device = 0, max_iter = 300, reps = 1, n_gpus = 1;
     bool use_err = false, use_poisson = false, keep_all = false;
+    bool per_family = false, gpus_given = false, alpha_given = false;      // -b: one lambda (vector) per family
     unsigned seed = 0;
     bool have_seed = false;
     for (int i = 1; i < argc; ++i) {
@@ -143,7 +146,8 @@ int main(int argc, char** argv) {
         else if (a == "-m") multi = next();
         else if (a == "-y") lambda_tree_path = next();
         else if (a == "-k") k = std::stoi(next());
-        else if (a == "-a") fixed_alpha = std::stod(next());
+        else if (a == "-a") { fixed_alpha = std::stod(next()); alpha_given = true; }
+        else if (a == "-b") per_family = true;
         else if (a == "-e") { use_err = true; err_path = optional(); }
         else if (a == "-p") { use_poisson = true; std::string v = optional(); poisson = v.empty() ? 0 : std::stod(v); }
         else if (a == "-f") rootdist_path = next();
@@ -151,7 +155,7 @@ int main(int argc, char** argv) {
         else if (a == "-s") { seed = (unsigned)std::stoul(next()); have_seed = true; }
         else if (a == "-I") max_iter = std::stoi(next());
         else if (a == "-d") device = std::stoi(next());
-        else if (a == "--gpus") n_gpus = std::stoi(next());
+        else if (a == "--gpus") { n_gpus = std::stoi(next()); gpus_given = true; }
         else if (a == "--reps") reps = std::stoi(next());
         else if (a == "--family-out") family_out = next();
         else if (a == "-o") out_dir = next();
@@ -179,6 +183,17 @@ int main(int argc, char** argv) {
                              simulate_n, simulate_on_device, have_seed ? seed : randomizer_engine(), device, sim_workspace, out_dir);
     }
     if (tree_path.empty() || fam_path.empty()) { usage(); return 2; }
+    if (per_family) {                                            // what -b cannot be combined with: refused before anything is read or written
+        const char* why = nullptr;
+        if (k > 1 || alpha_given) why = "-b estimates one lambda per family under the base model; -k > 1 and -a are not supported with it";
+        else if (use_err && err_path.empty()) why = "-b with -e needs an error model file: estimating epsilon per family is not supported";
+        else if (gpus_given) why = "-b runs on one GPU: --gpus is not supported with it";
+        if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
+        if (fixed_lambda > 0 || !multi.empty()) {                // execute.cpp:116 clears the lambda before every family's search
+            std::fprintf(stderr, "cafexp_hip: -b estimates every lambda; -l / -m are ignored\n");
+            fixed_lambda = 0; multi.clear();
+        }
+    }
     if (have_seed) randomizer_engine.seed(seed);
     try {
         user_data d;
@@ -240,6 +255,31 @@ int main(int argc, char** argv) {
             mdl.reset(new hip_base_model(start_lambda, d.p_tree.get(), &d.gene_families, d.max_family_size, d.max_root_family_size, em));
         }
         mdl->set_device(device);
+        if (per_family) {                                        // estimator::estimate_lambda_per_family (execute.cpp:104-128, :136-141)
+            hip_base_model* base = static_cast<hip_base_model*>(mdl.get());      // -k / -a were refused above
+            base->set_workspace_limit(sim_workspace);
+            const auto t0 = std::chrono::steady_clock::now();
+            const per_family_result res = estimate_lambda_per_family(*base, d, max_iter);
+            const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            if (out_dir.empty()) out_dir = "results";
+            if (::mkdir(out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("Failed to create directory " + out_dir);
+            {
+                std::ofstream f(out_dir + "/" + mdl->name() + "_lambda_per_family.txt");
+                std::unique_ptr<lambda> shape(d.p_lambda_tree ? (lambda*)new multiple_lambda(d.p_lambda_tree->get_lambda_index_map(), res.lambdas.empty() ? std::vector<double>() : res.lambdas[0])
+                                                              : (lambda*)new single_lambda(0.0));
+                for (size_t i = 0; i < d.gene_families.size(); ++i) {
+                    shape->update(res.lambdas[i].data());
+                    f << d.gene_families[i].id() << '\t' << shape->to_string() << "\n";
+                }
+                if (!f) throw std::runtime_error("Failed to write " + out_dir + "/" + mdl->name() + "_lambda_per_family.txt");
+            }
+            std::printf("{\"model\": \"%s\", \"mode\": \"lambda_per_family\", \"families\": %zu, \"distinct_families\": %zu, \"rounds\": %d, \"evaluations\": %ld, \"restarts\": %ld, "
+                        "\"max_family_size\": %d, \"max_root_family_size\": %d, ", mdl->name().c_str(), d.gene_families.size(), res.distinct_families, res.rounds,
+                        res.evaluations, res.restarts, d.max_family_size, d.max_root_family_size);
+            if (auto pd = dynamic_cast<poisson_distribution*>(d.p_prior.get())) print_num("poisson_lambda", pd->poisson_lambda());
+            std::printf("\"seconds\": %.3f}\n", seconds);
+            return 0;
+        }
         if (n_gpus > 1) {
             std::vector<int> devs(n_gpus);
             for (int g = 0; g < n_gpus; ++g) devs[g] = g;

@@ -24,80 +24,137 @@ std::vector<double> optimizer::get_initial_guesses(int& calls) {
     return initial;
 }
 
-optimizer_result optimizer::optimize() {
-    const double rho = 1, chi = 2, psi = 0.5, sigma = 0.5, delta = 0.05, zero_delta = 0.00025;
-    optimizer_result res;
-    std::vector<double> x0 = get_initial_guesses(res.num_scorer_calls);
-    const int n = (int)x0.size();
-    struct vertex { std::vector<double> x; double f; };
-    std::vector<vertex> simplex(n + 1);
-    auto eval = [&](const std::vector<double>& x) { ++res.num_scorer_calls; return _scorer->calculate_score(x.data()); };
-    auto by_score = [](const vertex& a, const vertex& b) { return a.f < b.f; };
+// ---- the moves, as a state machine: trial() is the point whose score the search needs next, feed() takes that score.
+// The scalar optimizer below and the lock-step search over many families (lambda_per_family.cpp) both drive it.
+namespace {
+const double rho = 1, chi = 2, psi = 0.5, sigma = 0.5, zero_delta = 0.00025;
+bool by_score(const nm_search::vertex& a, const nm_search::vertex& b) { return a.f < b.f; }
+}  // namespace
 
-    for (int i = 0; i <= n; ++i) {                                   // __fminsearch_min_init
-        simplex[i].x = x0;
-        if (i > 0) {
-            const int j = i - 1;
-            const bool widen = i > 1 && std::isinf(simplex[i - 1].f);
-            simplex[i].x[j] = x0[j] ? (1 + (widen ? delta * 100 : delta)) * x0[j] : zero_delta;
+nm_search::nm_search(const nm_settings& s, const std::vector<double>& x0) : _s(s), _x0(x0), _n((int)x0.size()), _simplex(x0.size() + 1), _mean(x0.size()), _xr(x0.size()), _xt(x0.size()) {
+    _phase = INIT;                                                   // __fminsearch_min_init
+    _i = 0;
+    _simplex[0].x = _x0;
+    _trial = 0;
+}
+
+void nm_search::accept(const std::vector<double>& x, double f) {
+    _simplex[_n].x = x;
+    _simplex[_n].f = f;
+    end_iteration();
+}
+
+void nm_search::end_iteration() {
+    std::sort(_simplex.begin(), _simplex.end(), by_score);
+    ++_it;
+    begin_iteration();
+}
+
+void nm_search::begin_iteration() {
+    const int n = _n;
+    if (_it >= _s.max_iterations) { _phase = DONE; return; }
+    double dx = 0, df = 0;                                           // threshold_achieved: checkV && checkF
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) dx = std::max(dx, std::fabs(_simplex[i + 1].x[j] - _simplex[i].x[j]));
+    for (int i = 1; i <= n; ++i) df = std::max(df, std::fabs(_simplex[i].f - _simplex[0].f));
+    if (dx <= _s.tolx && df <= _s.tolf) { _phase = DONE; return; }
+    if (_s.similarity_window > 0) {
+        _recent.push_back(_simplex[0].f);
+        if ((int)_recent.size() > _s.similarity_window) _recent.pop_front();
+        if ((int)_recent.size() == _s.similarity_window) {
+            const auto mm = std::minmax_element(_recent.begin(), _recent.end());
+            if (*mm.second - *mm.first < _s.similarity_precision) { _phase = DONE; return; }
         }
-        simplex[i].f = eval(simplex[i].x);
     }
-    std::sort(simplex.begin(), simplex.end(), by_score);
+    for (int j = 0; j < n; ++j) {
+        _mean[j] = 0;
+        for (int i = 0; i < n; ++i) _mean[j] += _simplex[i].x[j];
+        _mean[j] /= n;
+    }
+    const vertex& worst = _simplex[n];
+    for (int j = 0; j < n; ++j) _xr[j] = _mean[j] + rho * (_mean[j] - worst.x[j]);
+    _phase = REFLECT;
+    _trial = kTrialReflected;
+}
 
-    std::deque<double> recent;
-    std::vector<double> mean(n), xr(n), xt(n);
-    int it = 0;
-    for (; it < max_iterations; ++it) {
-        double dx = 0, df = 0;                                       // threshold_achieved: checkV && checkF
-        for (int i = 0; i < n; ++i)
-            for (int j = 0; j < n; ++j) dx = std::max(dx, std::fabs(simplex[i + 1].x[j] - simplex[i].x[j]));
-        for (int i = 1; i <= n; ++i) df = std::max(df, std::fabs(simplex[i].f - simplex[0].f));
-        if (dx <= tolx && df <= tolf) break;
-        if (similarity_window > 0) {
-            recent.push_back(simplex[0].f);
-            if ((int)recent.size() > similarity_window) recent.pop_front();
-            if ((int)recent.size() == similarity_window) {
-                const auto mm = std::minmax_element(recent.begin(), recent.end());
-                if (*mm.second - *mm.first < similarity_precision) break;
-            }
-        }
-        for (int j = 0; j < n; ++j) {
-            mean[j] = 0;
-            for (int i = 0; i < n; ++i) mean[j] += simplex[i].x[j];
-            mean[j] /= n;
-        }
-        vertex& worst = simplex[n];
-        for (int j = 0; j < n; ++j) xr[j] = mean[j] + rho * (mean[j] - worst.x[j]);
-        const double fr = eval(xr);
-        bool shrink = false;
-        if (fr < simplex[0].f) {
-            for (int j = 0; j < n; ++j) xt[j] = mean[j] + chi * (xr[j] - mean[j]);
-            const double fe = eval(xt);
-            if (fe < fr) { worst.x = xt; worst.f = fe; } else { worst.x = xr; worst.f = fr; }
-        } else if (fr >= worst.f) {
-            if (fr > worst.f) {
-                for (int j = 0; j < n; ++j) xt[j] = mean[j] + psi * (mean[j] - worst.x[j]);     // contract inside
-                const double fc = eval(xt);
-                if (fc < worst.f) { worst.x = xt; worst.f = fc; } else shrink = true;
-            } else {
-                for (int j = 0; j < n; ++j) xt[j] = mean[j] + psi * (xr[j] - mean[j]);          // contract outside
-                const double fc = eval(xt);
-                if (fc <= fr) { worst.x = xt; worst.f = fc; } else shrink = true;
-            }
+void nm_search::start_shrink() {
+    _phase = SHRINK;
+    _i = 1;
+    for (int j = 0; j < _n; ++j) _simplex[1].x[j] = _simplex[0].x[j] + sigma * (_simplex[1].x[j] - _simplex[0].x[j]);
+    _trial = 1;
+}
+
+void nm_search::feed(double f) {
+    const int n = _n;
+    ++_calls;
+    vertex& worst = _simplex[n];
+    switch (_phase) {
+    case INIT:
+        _simplex[_i].f = f;
+        if (++_i <= n) {
+            const int i = _i, j = i - 1;
+            const bool widen = i > 1 && std::isinf(_simplex[i - 1].f);
+            _simplex[i].x = _x0;
+            _simplex[i].x[j] = _x0[j] ? (1 + (widen ? _s.delta * 100 : _s.delta)) * _x0[j] : zero_delta;
+            _trial = i;
         } else {
-            worst.x = xr; worst.f = fr;
+            std::sort(_simplex.begin(), _simplex.end(), by_score);
+            begin_iteration();
         }
-        if (shrink)
-            for (int i = 1; i <= n; ++i) {
-                for (int j = 0; j < n; ++j) simplex[i].x[j] = simplex[0].x[j] + sigma * (simplex[i].x[j] - simplex[0].x[j]);
-                simplex[i].f = eval(simplex[i].x);
+        break;
+    case REFLECT:
+        _fr = f;
+        if (_fr < _simplex[0].f) {
+            for (int j = 0; j < n; ++j) _xt[j] = _mean[j] + chi * (_xr[j] - _mean[j]);
+            _phase = EXPAND; _trial = kTrialOther;
+        } else if (_fr >= worst.f) {
+            if (_fr > worst.f) {
+                for (int j = 0; j < n; ++j) _xt[j] = _mean[j] + psi * (_mean[j] - worst.x[j]);     // contract inside
+                _phase = CONTRACT_IN;
+            } else {
+                for (int j = 0; j < n; ++j) _xt[j] = _mean[j] + psi * (_xr[j] - _mean[j]);         // contract outside
+                _phase = CONTRACT_OUT;
             }
-        std::sort(simplex.begin(), simplex.end(), by_score);
+            _trial = kTrialOther;
+        } else {
+            accept(_xr, _fr);
+        }
+        break;
+    case EXPAND:
+        if (f < _fr) accept(_xt, f); else accept(_xr, _fr);
+        break;
+    case CONTRACT_IN:
+        if (f < worst.f) accept(_xt, f); else start_shrink();
+        break;
+    case CONTRACT_OUT:
+        if (f <= _fr) accept(_xt, f); else start_shrink();
+        break;
+    case SHRINK:
+        _simplex[_i].f = f;
+        if (++_i <= n) {
+            for (int j = 0; j < n; ++j) _simplex[_i].x[j] = _simplex[0].x[j] + sigma * (_simplex[_i].x[j] - _simplex[0].x[j]);
+            _trial = _i;
+        } else {
+            end_iteration();
+        }
+        break;
+    case DONE:
+        break;
     }
-    res.values = simplex[0].x;
-    res.score = simplex[0].f;
-    res.num_iterations = it;
+}
+
+optimizer_result optimizer::optimize() {
+    optimizer_result res;
+    const std::vector<double> x0 = get_initial_guesses(res.num_scorer_calls);
+    nm_settings s;
+    s.max_iterations = max_iterations; s.tolx = tolx; s.tolf = tolf;
+    s.similarity_window = similarity_window; s.similarity_precision = similarity_precision;
+    nm_search search(s, x0);
+    while (!search.done()) search.feed(_scorer->calculate_score(search.trial().data()));
+    res.values = search.best();
+    res.score = search.best_score();
+    res.num_iterations = search.iterations();
+    res.num_scorer_calls += search.calls();
     return res;
 }
 

@@ -260,6 +260,19 @@ typedef struct cafe_sim_problem {
 /* leaf_counts[n_families][n_taxa] and node_sizes[n_families][n_nodes] (host memory; either may be NULL, not both). */
 int cafe_simulate(const cafe_sim_problem* problem, uint64_t seed, int32_t* leaf_counts, int32_t* node_sizes, char* err, size_t errlen);
 
+/* model::infer_family_likelihoods for ONE family at a time, each with its own lambdas (estimate_lambda_per_family,
+ * execute.cpp:104-128).  family[n] indexes the context's families (caller's order, duplicates allowed);
+ * lambdas[n][n_lambdas].  family_lnl[n] receives what cafe_score's family_lnl[family[i]] would be with
+ * params->lambdas = lambdas[i]: -inf where cafe_score would return +inf for that vector (invalid lambda, zero
+ * likelihood), NaN passed through.  Base model only (CAFE_MODEL_GAMMA: CAFE_ERR_ARGUMENT; a context with a communicator
+ * attached: CAFE_ERR_STATE); params->prior and params->error_model are read, params->lambdas is not.  No matrix is built
+ * in memory: one wave per (family, branch) runs the row recurrence and consumes every row in a dot product
+ * (family_lambda.hip).  The list is processed in batches that fit the problem's workspace_limit (0 = automatic); a value
+ * depends on the family's counts and lambdas only, never on the list or the batches.  cafe_family_results is not
+ * meaningful after this call. */
+int cafe_score_per_family(cafe_ctx* ctx, const cafe_params* params, int64_t n, const int64_t* family,
+                          const double* lambdas, double* family_lnl);
+
 /* Ancestral reconstruction.  Pupko's joint reconstruction as reconstruct_gene_family runs it
  * (gene_family_reconstructor.cpp:13-165; base_model.cpp:145, gamma_core.cpp:301): for every category k (one for
  * the base model; lambda * multipliers[k] for the gamma model) and family f, the reconstructed size of every node
