@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -255,6 +256,23 @@ void set_err(cafe_ctx* c, const char* fmt, ...);
             return CAFE_ERR_DEVICE;                                                         \
         }                                                                                   \
     } while (0)
+
+// A device allocation freed when it goes out of scope
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+// Workspace of a call that cuts its work into batches: the caller's limit, else half of the free memory (counting the
+// held_bytes of a workspace the caller keeps and will reuse), at most 8 GiB
+inline hipError_t workspace_budget(size_t limit, size_t held_bytes, size_t* budget) {
+    *budget = limit;
+    if (limit) return hipSuccess;
+    size_t free_b = 0, total_b = 0;
+    const hipError_t e = hipMemGetInfo(&free_b, &total_b);
+    *budget = std::min<size_t>((free_b + held_bytes) / 2, (size_t)8 << 30);
+    return e;
+}
 
 // Columns of node v's panel (or of its factor) in a chunk `cols` wide: its distinct subtree patterns when the schedule
 // de-duplicates subtrees, else the chunk's

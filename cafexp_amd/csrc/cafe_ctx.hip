@@ -43,12 +43,6 @@ void set_err(cafe_ctx* c, const char* fmt, ...) {
 
 namespace {
 
-// matrix_cache_key (matrix_cache.h:42-61)
-inline void quantize(double lambda, double t, long* lq, long* tq) {
-    *lq = long(lambda * 1000000000);
-    *tq = long(t * 1000);
-}
-
 void free_device(cafe_ctx* c) {
     if (!c->device_ready) return;            // nothing was created on a device (argument / device errors)
     hipSetDevice(c->device);
@@ -204,8 +198,7 @@ void plan_pools(cafe_ctx* c, int kb) {
     for (int v = 0; v < c->n_nodes; ++v) {
         if (v == c->root) continue;
         const int layout = c->leaf_taxon[v] >= 0 ? 0 : 1;
-        long lq, tq;
-        quantize(0.0, c->blen[v], &lq, &tq);
+        const long tq = quantize_time(c->blen[v]);
         const auto key = std::make_pair(tq, c->lam_idx[v]);
         auto it = seen[layout].find(key);
         if (it == seen[layout].end()) {
@@ -219,7 +212,7 @@ void plan_pools(cafe_ctx* c, int kb) {
     c->n_pairs[0] = (int)c->pair_tq[0].size(); c->n_pairs[1] = (int)c->pair_tq[1].size();
     c->n_distinct_pairs = (int)any.size();
     c->kc = round_up(c->M + 1, kBK);
-    c->pool.n = c->N; c->pool.ld = round_up(c->N, 16); c->pool.stride = (int64_t)c->N * c->pool.ld;
+    c->pool = row_major_pool(c->N);
     c->pool.ext_blocks = c->N;               // row-major: one entry per column x of a leaf branch's matrix
     c->max_slots = c->n_pairs[0] * c->Kmax;
     c->kpool.n = c->N; c->kpool.rows = c->kc; c->kpool.k_valid = c->M + 1; c->kpool.kmajor = 1;
@@ -500,16 +493,7 @@ void fill_slots(cafe_ctx* c, const double* lambdas, const double* multipliers, i
         for (int k = 0; k < K; ++k) {
             const double mult = multipliers ? multipliers[k] : 1.0;
             for (int p = 0; p < P; ++p) {
-                const long lq = long(lambdas[c->pair_lam[layout][p]] * mult * 1000000000);     // matrix_cache.h:47
-                const double lambda_q = double(lq) / 1000000000.0, t_q = double(c->pair_tq[layout][p]) / 1000.0;
-                const double alpha = lambda_q * t_q / (1 + lambda_q * t_q);
-                const double coeff = 1 - 2 * alpha;
-                SlotParam sp;
-                sp.alpha = alpha;
-                sp.oma2 = (1 - alpha) * (1 - alpha);
-                sp.zero = !(coeff > 0 && coeff != 1);       // saturated (coeff < 0) or degenerate: rows s>=1 are 0
-                sp.pad = 0;
-                h[layout][k * P + p] = sp;
+                h[layout][k * P + p] = slot_param(quantize_lambda(lambdas[c->pair_lam[layout][p]] * mult), c->pair_tq[layout][p]);
             }
         }
     }
@@ -1521,23 +1505,13 @@ int cafe_build_matrices(int32_t device, int32_t n, int32_t count, const double* 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CAFE_ERR_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return CAFE_ERR_DEVICE;
-    MatrixPool pool{};
-    pool.n = n;
-    if (layout == 0) {
-        pool.ld = round_up(n, 16); pool.stride = (int64_t)n * pool.ld; pool.kmajor = 0; pool.rows = n; pool.k_valid = n;
-    } else {
+    MatrixPool pool = row_major_pool(n);
+    if (layout != 0) {
         pool.rows = round_up(n, kBK); pool.k_valid = n; pool.kmajor = 1;
         pool.ld = round_up(n - 1, 16) + 16; pool.stride = (int64_t)pool.rows * pool.ld;
     }
     std::vector<SlotParam> sp(count);
-    for (int i = 0; i < count; ++i) {
-        long lq, tq;
-        quantize(lambdas[i], ts[i], &lq, &tq);
-        const double lambda_q = double(lq) / 1000000000.0, t_q = double(tq) / 1000.0;
-        const double alpha = lambda_q * t_q / (1 + lambda_q * t_q);
-        const double coeff = 1 - 2 * alpha;
-        sp[i].alpha = alpha; sp[i].oma2 = (1 - alpha) * (1 - alpha); sp[i].zero = !(coeff > 0 && coeff != 1); sp[i].pad = 0;
-    }
+    for (int i = 0; i < count; ++i) sp[i] = slot_param(quantize_lambda(lambdas[i]), quantize_time(ts[i]));
     SlotParam* d_sp = nullptr;
     int rc = CAFE_OK;
     const size_t bytes = sizeof(double) * pool.stride * count;

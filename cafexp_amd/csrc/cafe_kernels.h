@@ -52,6 +52,29 @@ struct MatrixPool {
     int32_t ext_blocks;
 };
 
+// The reference keeps a matrix under the key (long(lambda * 1e9), long(t * 1000)) (matrix_cache_key, matrix_cache.h:42-61)
+// and builds it from the DE-QUANTIZED key (precalculate_matrices, matrix_cache.cpp:148-153).  Every entry point builds
+// its slot parameters through these three, so that they agree with the reference, and with each other, to the bit.
+// A lambda * 1e9 beyond a long is the caller's to reject or to treat (family_lambda.hip).
+inline long quantize_lambda(double lambda) { return long(lambda * 1000000000); }
+inline long quantize_time(double t) { return long(t * 1000); }
+inline SlotParam slot_param(long lq, long tq) {
+    const double lambda_q = double(lq) / 1000000000.0, t_q = double(tq) / 1000.0;
+    const double alpha = lambda_q * t_q / (1 + lambda_q * t_q), coeff = 1 - 2 * alpha;
+    SlotParam sp;
+    sp.alpha = alpha;
+    sp.oma2 = (1 - alpha) * (1 - alpha);
+    sp.zero = !(coeff > 0 && coeff != 1);       // saturated (coeff < 0) or degenerate: rows s >= 1 are 0
+    sp.pad = 0;
+    return sp;
+}
+// A row-major pool of matrices of order n, not yet placed (base null, no extents)
+inline MatrixPool row_major_pool(int n) {
+    MatrixPool p{};
+    p.n = n; p.ld = (n + 15) / 16 * 16; p.stride = (int64_t)n * p.ld; p.rows = n; p.k_valid = n; p.kmajor = 0;
+    return p;
+}
+
 // Likelihood panels: [category][row][family], family fastest, so that a node's panel is the
 // GEMM's B operand with the family axis as its N dimension.
 //

@@ -183,21 +183,15 @@ hipError_t launch_family_lambda(const FamLamArgs& a, int n, int64_t batch, int n
 
 inline size_t align_up(size_t v) { return (v + 255) / 256 * 256; }
 
-// The branch above node u under one family's lambdas: the de-quantized key of matrix_cache.cpp:148-149, as fill_slots
+// The branch above node u under one family's lambdas
 SlotParam branch_param(const cafe_ctx* c, int u, const double* lam) {
     const double l = lam[c->lam_idx[u]];
-    SlotParam sp{};
     if (!(l * 1000000000 < 9.0e18)) {                  // beyond a long: saturated on any branch (lambdas are >= 0 and not NaN here)
+        SlotParam sp{};
         sp.alpha = 1.0; sp.oma2 = 0.0; sp.zero = 1;
         return sp;
     }
-    const long lq = long(l * 1000000000), tq = long(c->blen[u] * 1000);     // matrix_cache.h:47
-    const double lambda_q = double(lq) / 1000000000.0, t_q = double(tq) / 1000.0;
-    const double alpha = lambda_q * t_q / (1 + lambda_q * t_q), coeff = 1 - 2 * alpha;
-    sp.alpha = alpha;
-    sp.oma2 = (1 - alpha) * (1 - alpha);
-    sp.zero = !(coeff > 0 && coeff != 1);
-    return sp;
+    return slot_param(quantize_lambda(l), quantize_time(c->blen[u]));
 }
 
 }  // namespace
@@ -264,12 +258,8 @@ int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const i
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t static_bytes = align_up(sizeof(int32_t) * tables.size()) + align_up(sizeof(double) * reals.size());
     const size_t family_bytes = sizeof(double) * (size_t)nn * ld + sizeof(SlotParam) * (size_t)nn + sizeof(int64_t) + sizeof(double);
-    size_t budget = c->workspace_limit;
-    if (budget == 0) {
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
-        budget = std::min<size_t>((free_b + c->pf_dev_bytes) / 2, (size_t)8 << 30);
-    }
+    size_t budget = 0;
+    HIP_TRY(c, workspace_budget(c->workspace_limit, c->pf_dev_bytes, &budget));
     int64_t batch = std::max<int64_t>(1, std::min<int64_t>(na, budget > static_bytes + 1024 ? (int64_t)((budget - static_bytes - 1024) / family_bytes) : 1));
     if (c->pf_max_batch > 0) batch = std::min(batch, c->pf_max_batch);
     const size_t o_reals = align_up(sizeof(int32_t) * tables.size()), o_col = o_reals + align_up(sizeof(double) * reals.size()),

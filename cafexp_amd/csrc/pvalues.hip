@@ -11,7 +11,8 @@
 // come from a counter-based generator (Philox4x32-10 keyed by the seed, counter = (family, node)), so the simulated
 // families are a DIFFERENT sample of the same distribution: p-values agree with the reference statistically (Monte
 // Carlo error ~ sqrt(p(1-p)/n)), not draw for draw.
-//   row_cdf       prefix sums of every branch's row-major matrix rows over c = 0..M-1 (inverse-CDF sampling)
+//   row_cdf       prefix sums of every branch's row-major matrix rows over c = 0..M-1 (inverse-CDF sampling; tree_sampler.h,
+//                 shared with simulate.hip like the generator and the draw)
 //   simulate      one thread per simulated family, nodes parents first; sizes in a [node][family] scratch, leaves
 //                 written straight into the child context's taxon-major count table
 //   (prune)       cafe_ctx.hip's root-maximum schedule on the child context and on the observed families
@@ -23,36 +24,11 @@
 #include <vector>
 
 #include "cafe_ctx.h"
-#include "philox.h"
+#include "tree_sampler.h"
 
 namespace cafe {
 
 namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
-// inclusive prefix sums along c of rows 1..n-1 of `count` row-major matrices; one wave per row
-__global__ __launch_bounds__(64) void row_cdf_kernel(double* __restrict__ base, int64_t stride, int ld, int n, int m_cols) {
-    const int row = blockIdx.x + 1, slot = blockIdx.y, lane = threadIdx.x;
-    double* r = base + (int64_t)slot * stride + (int64_t)row * ld;
-    double carry = 0.0;
-    for (int c0 = 0; c0 < m_cols; c0 += 64) {
-        const int c = c0 + lane;
-        double v = c < m_cols ? r[c] : 0.0;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const double up = __shfl_up(v, d);
-            if (lane >= d) v += up;
-        }
-        v += carry;
-        if (c < m_cols) r[c] = v;
-        carry = __shfl(v, 63);
-    }
-    (void)n;
-}
 
 struct SimArgs {
     const double* cdf;          // [slot][N][ld] row-major prefix sums
@@ -83,20 +59,7 @@ __global__ __launch_bounds__(256) void simulate_kernel(const SimArgs a) {
             size = 0;
             if (ps > 0) {                                   // an extinct lineage stays extinct, no draw (:328)
                 const double* row = a.cdf + (int64_t)a.slot[v] * a.stride + (int64_t)ps * a.ld;
-                uint32_t r[4];
-                philox4x32_10((uint32_t)f, (uint32_t)(f >> 32), (uint32_t)v, 0u, a.k0, a.k1, r);
-                const double u = ((double)(((uint64_t)r[0] << 21) ^ (r[1] >> 11)) + 0.5) * (1.0 / 9007199254740992.0);   // (0,1)
-                // A saturated / degenerate branch has an all-zero row (matrix_cache.cpp:153): target = 0 and the search
-                // returns size 0.  The reference draws from std::discrete_distribution over all-zero weights there
-                // (probability.cpp:333-344, after a uniform draw it then discards) -- outside that distribution's
-                // precondition (sum of weights > 0); libstdc++ returns index 0, so does this path, by construction.
-                const double target = u * row[a.M - 1];     // sizes 0..M-1 carry the weights (:338-341)
-                int lo = 0, hi = a.M - 1;                   // first c with cdf[c] >= target
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (row[mid] >= target) hi = mid; else lo = mid + 1;
-                }
-                size = lo;
+                size = draw_child_size(row, a.M, uniform01(f, v, 0u, a.k0, a.k1));
             }
         }
         a.sizes[(int64_t)v * a.ld_f + f] = size;
@@ -164,8 +127,7 @@ int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t see
     { const int rc = enqueue_rootmax(c, pr->lambdas, s); if (rc != CAFE_OK) return rc; }
 
     // ---- row-major matrix + CDF of EVERY branch (the scorer keeps interior branches k-major only)
-    MatrixPool sp{};
-    sp.n = N; sp.ld = round_up(N, 16); sp.stride = (int64_t)N * sp.ld; sp.kmajor = 0; sp.rows = N; sp.k_valid = N;
+    MatrixPool sp = row_major_pool(N);
     std::map<std::pair<long, long>, int> key_slot;
     std::vector<SlotParam> slots;
     std::vector<int32_t> h_slot(n, 0), h_parent(n), h_leaf(n), h_order;
@@ -173,14 +135,11 @@ int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t see
         h_parent[v] = c->parent[v];
         h_leaf[v] = c->leaf_taxon[v];
         if (v == c->root) continue;
-        const long lq = long(pr->lambdas[c->lam_idx[v]] * 1000000000), tq = long(c->blen[v] * 1000);     // matrix_cache.h:47-50
+        const long lq = quantize_lambda(pr->lambdas[c->lam_idx[v]]), tq = quantize_time(c->blen[v]);
         auto it = key_slot.find({tq, lq});
         if (it == key_slot.end()) {
-            const double lambda_q = double(lq) / 1000000000.0, t_q = double(tq) / 1000.0;
-            const double alpha = lambda_q * t_q / (1 + lambda_q * t_q), coeff = 1 - 2 * alpha;
-            SlotParam p0; p0.alpha = alpha; p0.oma2 = (1 - alpha) * (1 - alpha); p0.zero = !(coeff > 0 && coeff != 1); p0.pad = 0;
             it = key_slot.emplace(std::make_pair(tq, lq), (int)slots.size()).first;
-            slots.push_back(p0);
+            slots.push_back(slot_param(lq, tq));
         }
         h_slot[v] = it->second;
     }
@@ -203,9 +162,7 @@ int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t see
     HIP_TRY(c, hipMemcpyAsync(meta + 2 * n, h_slot.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(meta + 3 * n, h_leaf.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
     HIP_TRY(c, launch_bd_matrix_build(sp, static_cast<const SlotParam*>(d_sp.p), (int)slots.size(), s));
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(row_cdf_kernel, dim3(N - 1, (unsigned)slots.size()), dim3(64), 0, s, sp.base, sp.stride, sp.ld, N, M);
-    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, launch_row_cdf(sp.base, sp.stride, sp.ld, (int)slots.size(), N, M, s));
     HIP_TRY(c, hipStreamSynchronize(s));                            // the host vectors above go out of use
 
     // ---- simulate into a child context over the same tree, prune, keep the root maxima

@@ -261,11 +261,6 @@ __global__ __launch_bounds__(256) void viterbi_kernel(const int32_t* __restrict_
     out[idx] = result;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 // (The reference's "Zero matrix found" throw, gene_family_reconstructor.cpp:87, cannot fire: matrix::is_zero tests the

@@ -7,7 +7,8 @@
 //               buffers fit the workspace; within a batch, chunks whose quantized lambdas agree share one block of
 //               matrices (the base model: one block for the whole batch)
 //   K1          launch_bd_matrix_build, row-major, order S, one slot per (block, distinct (lambda index, t_q) pair)
-//   row_cdf     inclusive prefix sums of rows 1..S-1 over columns 0..S-1 (the reference's weights, :338-341)
+//   row_cdf     inclusive prefix sums of rows 1..S-1 over columns 0..S-1 (the reference's weights, :338-341); this pass, the
+//               generator and the draw are tree_sampler.h's, shared with pvalues.hip
 //   sample      one thread per family, nodes parents first, inverse-CDF draws by binary search; sizes node-major in a
 //               scratch table so that a parent's size is one coalesced load
 //   transpose   the scratch to family-major leaf counts / node sizes through LDS, so that both writes coalesce
@@ -25,32 +26,13 @@
 #include <vector>
 
 #include "cafe_ctx.h"
-#include "philox.h"
+#include "tree_sampler.h"
 
 namespace cafe {
 
 namespace {
 
 constexpr int kTile = 64;                       // families x columns per transpose tile
-
-// inclusive prefix sums along c = 0..S-1 of rows 1..S-1 of every matrix of the pool; one wave per row (x: matrix, y: row)
-__global__ __launch_bounds__(64) void sim_row_cdf_kernel(double* __restrict__ base, int64_t stride, int ld, int S) {
-    const int row = blockIdx.y + 1, lane = threadIdx.x;
-    double* r = base + (int64_t)blockIdx.x * stride + (int64_t)row * ld;
-    double carry = 0.0;
-    for (int c0 = 0; c0 < S; c0 += 64) {
-        const int c = c0 + lane;
-        double v = c < S ? r[c] : 0.0;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const double up = __shfl_up(v, d);
-            if (lane >= d) v += up;
-        }
-        v += carry;
-        if (c < S) r[c] = v;
-        carry = __shfl(v, 63);
-    }
-}
 
 struct SampleArgs {
     const double* cdf;              // [slot][S][ld] row prefix sums
@@ -70,12 +52,6 @@ struct SampleArgs {
     uint32_t k0, k1;
 };
 
-__device__ inline double uniform01(int64_t f, int v, uint32_t stream, uint32_t k0, uint32_t k1) {
-    uint32_t r[4];
-    philox4x32_10((uint32_t)f, (uint32_t)((uint64_t)f >> 32), (uint32_t)v, stream, k0, k1, r);
-    return ((double)(((uint64_t)r[0] << 21) ^ (r[1] >> 11)) + 0.5) * (1.0 / 9007199254740992.0);     // (0,1)
-}
-
 __global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) {
     const int64_t fl = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (fl >= a.fb) return;
@@ -92,15 +68,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const SampleArgs a) {
             size = 0;
             if (ps > 0) {                               // an extinct lineage stays extinct, no draw (:328)
                 const double* row = a.cdf + (slot_base + a.pair_of[v]) * a.stride + (int64_t)ps * a.ld;
-                // an all-zero row (saturated / degenerate branch, matrix_cache.cpp:153) has target 0 and gives size 0:
-                // what libstdc++'s discrete_distribution returns for all-zero weights (see pvalues.hip)
-                const double target = uniform01(f, v, 0u, a.k0, a.k1) * row[a.S - 1];
-                int lo = 0, hi = a.S - 1;               // first c with cdf[c] >= target
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (row[mid] >= target) hi = mid; else lo = mid + 1;
-                }
-                size = lo;
+                size = draw_child_size(row, a.S, uniform01(f, v, 0u, a.k0, a.k1));
             }
             if (a.err && a.is_leaf[v]) {                // adjust_for_error_model (:354-377)
                 if (size >= a.err_max) {
@@ -135,11 +103,6 @@ __global__ __launch_bounds__(256) void transpose_kernel(const int32_t* __restric
     }
 }
 
-struct DevMem {
-    void* p = nullptr;
-    ~DevMem() { if (p) (void)hipFree(p); }
-};
-
 struct StreamGuard {
     hipStream_t s = nullptr;
     ~StreamGuard() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
@@ -166,7 +129,7 @@ void put_err(char* err, size_t errlen, const char* fmt, ...) {
 // vectors build the same matrices.
 std::vector<long> chunk_key(const cafe_sim_problem* p, double m) {
     std::vector<long> k((size_t)p->n_lambdas);
-    for (int i = 0; i < p->n_lambdas; ++i) k[i] = long(p->lambdas[i] * m * 1000000000);
+    for (int i = 0; i < p->n_lambdas; ++i) k[i] = quantize_lambda(p->lambdas[i] * m);
     return k;
 }
 
@@ -232,7 +195,7 @@ int simulate_impl(const cafe_sim_problem* p, uint64_t seed, int32_t* leaf_counts
     for (int v = 0; v < n; ++v) {
         if (v == root) continue;
         const int li = p->lambda_index ? p->lambda_index[v] : 0;
-        const long tq = long(p->branch_length[v] * 1000);
+        const long tq = quantize_time(p->branch_length[v]);
         auto it = pair_id.find({li, tq});
         if (it == pair_id.end()) {
             it = pair_id.emplace(std::make_pair(li, tq), (int)pair_lam.size()).first;
@@ -246,26 +209,21 @@ int simulate_impl(const cafe_sim_problem* p, uint64_t seed, int32_t* leaf_counts
     std::vector<int32_t> all_nodes(n);
     for (int v = 0; v < n; ++v) all_nodes[v] = v;
 
-    MatrixPool pool{};
-    pool.n = S; pool.ld = round_up(S, 16); pool.stride = (int64_t)S * pool.ld; pool.kmajor = 0; pool.rows = S; pool.k_valid = S;
+    MatrixPool pool = row_major_pool(S);
     const size_t block_bytes = sizeof(double) * (size_t)pool.stride * n_pairs + sizeof(SlotParam) * n_pairs + sizeof(int32_t);
     const size_t family_bytes = sizeof(int32_t) * ((size_t)n + (leaf_counts ? T : 0) + (node_sizes ? n : 0));
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || p->device < 0 || p->device >= ndev) { put_err(err, errlen, "cafe_simulate: no HIP device %d", p->device); return CAFE_ERR_DEVICE; }
     SIM_TRY(hipSetDevice(p->device));
-    size_t budget = p->workspace_limit;
-    if (budget == 0) {
-        size_t free_b = 0, total_b = 0;
-        SIM_TRY(hipMemGetInfo(&free_b, &total_b));
-        budget = std::min<size_t>(free_b / 2, (size_t)8 << 30);
-    }
+    size_t budget = 0;
+    SIM_TRY(workspace_budget(p->workspace_limit, 0, &budget));
     // a batch holds <= max_blocks matrix blocks and <= max_fams families (at least one block and one tile of families)
     const int64_t max_blocks = std::max<int64_t>(1, (int64_t)(budget / 2 / block_bytes));
     const int64_t max_fams = std::max<int64_t>(kTile, (int64_t)(budget / 2 / family_bytes) / kTile * kTile);
 
     // ---------------------------------------------------------------- device buffers sized for the largest batch
-    DevMem d_pool, d_slots, d_meta, d_root, d_err, d_flag, d_sizes, d_leaf, d_node, d_cblock;
+    DevBuf d_pool, d_slots, d_meta, d_root, d_err, d_flag, d_sizes, d_leaf, d_node, d_cblock;
     StreamGuard sg;
     SIM_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
     hipStream_t s = sg.s;
@@ -342,21 +300,14 @@ int simulate_impl(const cafe_sim_problem* p, uint64_t seed, int32_t* leaf_counts
         const int64_t fb = f1 - f0;
         slots.assign((size_t)blocks.size() * n_pairs, SlotParam{});
         for (size_t b = 0; b < blocks.size(); ++b)
-            for (int q = 0; q < n_pairs; ++q) {                        // the de-quantized key, as matrix_cache.cpp:148-149
-                const double lambda_q = double(blocks[b][pair_lam[q]]) / 1000000000.0, t_q = double(pair_tq[q]) / 1000.0;
-                const double alpha = lambda_q * t_q / (1 + lambda_q * t_q), coeff = 1 - 2 * alpha;
-                SlotParam& sp = slots[b * n_pairs + q];
-                sp.alpha = alpha; sp.oma2 = (1 - alpha) * (1 - alpha); sp.zero = !(coeff > 0 && coeff != 1); sp.pad = 0;
-            }
+            for (int q = 0; q < n_pairs; ++q) slots[b * n_pairs + q] = slot_param(blocks[b][pair_lam[q]], pair_tq[q]);
         const int n_slots = (int)slots.size();
         pool.base = static_cast<double*>(d_pool.p);
         SIM_TRY(hipMemcpyAsync(d_slots.p, slots.data(), sizeof(SlotParam) * n_slots, hipMemcpyHostToDevice, s));
         SIM_TRY(hipMemcpyAsync(d_cblock.p, cblock.data(), sizeof(int32_t) * cblock.size(), hipMemcpyHostToDevice, s));
         // K1 stores every row of every slot (a saturated one too): no clearing pass; columns >= S are never read
         SIM_TRY(launch_bd_matrix_build(pool, static_cast<const SlotParam*>(d_slots.p), n_slots, s));
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(sim_row_cdf_kernel, dim3(n_slots, S - 1), dim3(64), 0, s, pool.base, pool.stride, pool.ld, S);
-        SIM_TRY(hipGetLastError());
+        SIM_TRY(launch_row_cdf(pool.base, pool.stride, pool.ld, n_slots, S, S, s));
         a.cdf = pool.base; a.f0 = f0; a.fb = fb; a.chunk0 = c0;
         hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((fb + 255) / 256)), dim3(256), 0, s, a);
         SIM_TRY(hipGetLastError());
