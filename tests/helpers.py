@@ -65,6 +65,15 @@ def case_from_args(args, oracle):
     return pb, pr, alpha
 
 
+def _explicit_problem(newick, rows, M, R):
+    """rows: one {species: count} dict per family.  M and R are given: pb.matrix_size == max(M, R) + 1."""
+    tree = P.parse_newick(newick)
+    species = sorted(rows[0])
+    table = np.array([[r[s] for s in species] for r in rows], dtype=np.int32)
+    return P.build_problem(tree, species, ["f%d" % i for i in range(len(rows))], table, root_filter=False,
+                           max_family_size=M, max_root_family_size=R)
+
+
 def rel_err(a, b):
     if np.isinf(a) or np.isinf(b):
         return 0.0 if a == b else np.inf

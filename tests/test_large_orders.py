@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 from cafexp_amd import problem as P, synth
-from helpers import case_from_args, rel_err
+from helpers import _explicit_problem, case_from_args, rel_err
 from test_large_order_golden import check_matrix
 
 pytestmark = pytest.mark.gpu
@@ -103,14 +103,6 @@ def test_order_above_the_limit_is_an_argument_error(capi):
 
 
 # ------------------------------------------------------------------ K1, two-pool launch (the scorer's)
-def _explicit_problem(newick, rows, M, R):
-    tree = P.parse_newick(newick)
-    species = sorted(rows[0])
-    table = np.array([[r[s] for s in species] for r in rows], dtype=np.int32)
-    return P.build_problem(tree, species, ["f%d" % i for i in range(len(rows))], table, root_filter=False,
-                           max_family_size=M, max_root_family_size=R)
-
-
 FAMS = [{"A": 3, "B": 5, "C": 2}, {"A": 300, "B": 280, "C": 310}, {"A": 0, "B": 1, "C": 1}, {"A": 40, "B": 44, "C": 39}]
 
 
