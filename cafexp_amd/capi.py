@@ -49,6 +49,11 @@ class CafeFamilyOut(C.Structure):
     _fields_ = [("family_lnl", _f64p), ("category_likelihood", _f64p), ("family_likelihood", _f64p), ("failed", _i32p)]
 
 
+class CafeMarginalOut(C.Structure):
+    _fields_ = [("mean", _f64p), ("mode", _i32p), ("lo", _i32p), ("hi", _i32p), ("p_increase", _f64p), ("p_decrease", _f64p),
+                ("log_evidence", _f64p), ("failed", _i32p)]
+
+
 class CafeStats(C.Structure):
     _fields_ = [
         ("ms_total", C.c_double), ("ms_matrices", C.c_double), ("ms_prune", C.c_double), ("ms_gemm", C.c_double),
@@ -82,7 +87,7 @@ EXPORTS = [
     "cafe_sharded_destroy", "cafe_sharded_last_error", "cafe_sharded_score", "cafe_sharded_family_results",
     "cafe_sharded_size", "cafe_sharded_context", "cafe_set_graphs", "cafe_executed_flops", "cafe_debug_tile_range_flops", "cafe_get_extents", "cafe_debug_launch_flops", "cafe_debug_launch_ms", "cafe_debug_plan_check",
     "cafe_debug_fail_next", "cafe_debug_column_extents", "cafe_debug_leaf_transposes", "cafe_simulate",
-    "cafe_score_per_family",
+    "cafe_score_per_family", "cafe_marginal_reconstruct", "cafe_debug_marginal_gemm",
 ]
 CAFE_COMM_ID_BYTES = 128
 
@@ -132,6 +137,10 @@ def load():
     L.cafe_root_max.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p]
     L.cafe_score_per_family.restype = C.c_int
     L.cafe_score_per_family.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p]
+    L.cafe_marginal_reconstruct.restype = C.c_int
+    L.cafe_marginal_reconstruct.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_double, C.POINTER(CafeMarginalOut)]
+    L.cafe_debug_marginal_gemm.restype = C.c_int
+    L.cafe_debug_marginal_gemm.argtypes = [C.c_void_p, _f64p, _f64p]
     L.cafe_pvalues.restype = C.c_int
     L.cafe_pvalues.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.c_uint64, _f64p]
     L.cafe_reconstruct.restype = C.c_int
@@ -366,6 +375,27 @@ class Context:
         out = np.empty(len(fam))
         self._check(self._lib.cafe_score_per_family(self._h, C.byref(cp), len(fam), _p(fam, _i64p), _p(lam, _f64p), _p(out, _f64p)))
         return out
+
+    def marginal_reconstruct(self, pr: Params, level: float = 0.95, alpha: float = 1.0) -> dict:
+        """cafe_marginal_reconstruct: posterior size of every node under the scorer's model with pr's lambdas, categories,
+        prior and error model.  Returns numpy arrays: mean, mode, lo, hi, p_increase, p_decrease [n_families][n_nodes],
+        log_evidence and failed [n_families]; lo..hi is the equal-tailed interval at `level`."""
+        cp, keep = self._params(pr, alpha)
+        F, n = self.n_families, self.n_nodes
+        res = {"mean": np.empty((F, n)), "mode": np.empty((F, n), dtype=np.int32), "lo": np.empty((F, n), dtype=np.int32),
+               "hi": np.empty((F, n), dtype=np.int32), "p_increase": np.empty((F, n)), "p_decrease": np.empty((F, n)),
+               "log_evidence": np.empty(F), "failed": np.empty(F, dtype=np.int32)}
+        mo = CafeMarginalOut()
+        for name, _ in CafeMarginalOut._fields_:
+            setattr(mo, name, _p(res[name], _i32p if res[name].dtype == np.int32 else _f64p))
+        self._check(self._lib.cafe_marginal_reconstruct(self._h, C.byref(cp), float(level), C.byref(mo)))
+        return res
+
+    def marginal_gemm_stats(self):
+        """(summed HIP-event ms of the GEMM launches of the last marginal_reconstruct -- 0 unless profiling was on --, their flops)"""
+        ms, fl = C.c_double(), C.c_double()
+        self._check(self._lib.cafe_debug_marginal_gemm(self._h, C.byref(ms), C.byref(fl)))
+        return ms.value, fl.value
 
     def root_max(self, lambdas) -> np.ndarray:
         """max_j L_root[j] per family under the plain lambdas (p-value path, probability.cpp:313, :399)."""

@@ -178,6 +178,7 @@ struct cafe_ctx {
     void* pf_dev = nullptr;
     size_t pf_dev_bytes = 0;
     int64_t pf_max_batch = 0;                // CAFE_PER_FAMILY_BATCH: at most that many families per batch (diagnostic; 0 = what fits)
+    double marginal_gemm_ms = 0, marginal_gemm_flops = 0;   // cafe_marginal_reconstruct: its GEMM launches (ms: while profiling)
     int debug_fail_in = 0;                   // cafe_debug_fail_next: the n-th next enqueue fails behind its K1 launch
 
     // last call
@@ -295,6 +296,8 @@ int prepare_matrices(cafe_ctx* c, const double* lambdas, const double* multiplie
 // Pupko reconstruction and Viterbi branch probabilities (reconstruct.hip)
 int reconstruct_impl(cafe_ctx* c, const cafe_params* pr, const float* root_prior, int32_t* states);
 int branch_probabilities_impl(cafe_ctx* c, const cafe_params* pr, const int32_t* sizes, double* out);
+// Marginal reconstruction: posterior sizes, intervals and branch change probabilities (marginal.hip)
+int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_marginal_out* out);
 // Device-side p-values (pvalues.hip) and what it needs from cafe_ctx.hip: a context over the same tree whose family
 // counts are written on the device, and the root-maximum prune of a context's families (-> d_fam_out, on stream s)
 constexpr int32_t kFlagDeviceCounts = 0x40000000;        // internal cafe_problem flag

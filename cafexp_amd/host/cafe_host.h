@@ -255,6 +255,19 @@ cafe_ctx* create_device_context(const lambda* lam, const std::vector<const clade
                                  int max_family_size, int max_root_family_size, int max_categories, int n_deviations, int device,
                                  size_t workspace_limit = 0);
 
+// cafe_marginal_reconstruct's outputs, [family][index in the caller's node order] (log_evidence, failed: [family])
+struct marginal_result {
+    double level = 0.95;
+    size_t n_nodes = 0;
+    std::vector<double> mean, p_increase, p_decrease, log_evidence;
+    std::vector<int32_t> mode, lo, hi, failed;
+    size_t failed_count() const { size_t k = 0; for (int32_t f : failed) k += f != 0; return k; }
+};
+// <Model>_posterior_sizes.tab (mean:mode:lo-hi) and <Model>_posterior_change.tab (p_decrease:p_increase, "-" at the root):
+// header row, family order and node naming of <Model>_count.tab
+void write_marginal_reports(const marginal_result& res, const std::string& model_identifier, const std::string& dir,
+                            const std::vector<const clade*>& order, const std::vector<gene_family>& families);
+
 // The two models whose infer_family_likelihoods runs on the GPU through the C ABI.
 class hip_model_base : public model {
 protected:
@@ -290,6 +303,15 @@ public:
     // compute_pvalues with the Monte-Carlo simulation on the device too (cafe_pvalues): statistical agreement with the
     // reference's procedure, not draw for draw
     std::vector<double> device_pvalues(int number_of_simulations, uint64_t seed);
+    // Marginal reconstruction under the model's own likelihood (cafe_marginal_reconstruct): posterior mean, mode and
+    // equal-tailed interval at `level` of every node's size, and the posterior probability that the branch above it
+    // expanded / contracted -- with the model's lambda, prior, error model and (gamma) categories; columns in `order`
+    marginal_result marginal_reconstruction(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, double level,
+                                            const std::vector<const clade*>& order);
+protected:
+    // gamma model: multipliers, category probabilities and alpha of the mixture; the base model leaves them empty
+    virtual void category_parameters(std::vector<double>&, std::vector<double>&, double&) const {}
+public:
     // compute_viterbi_sum (gene_family_reconstructor.cpp:361) for every family x node of `order` under the model's
     // plain lambda: [family][order index], NaN where the reference returns an invalid branch_probability
     std::vector<double> branch_probability_table(const reconstruction& rec, const std::vector<gene_family>& families,
@@ -321,6 +343,9 @@ public:
     double get_alpha() const { return _alpha; }
     std::vector<double> get_lambda_multipliers() const { return _lambda_multipliers; }
     bool can_infer() const;                                          // gamma_core.cpp:123
+    void category_parameters(std::vector<double>& multipliers, std::vector<double>& probs, double& alpha) const override {
+        multipliers = _lambda_multipliers; probs = _gamma_cat_probs; alpha = _alpha;
+    }
     double infer_family_likelihoods(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const lambda* p_lambda) override;
     std::string name() const override { return "Gamma"; }
     void write_family_likelihoods(std::ostream& ost) override;

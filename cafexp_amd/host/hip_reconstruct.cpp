@@ -5,6 +5,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <fstream>
 
 #include "../../include/cafe_mi355x.h"
 
@@ -59,6 +61,76 @@ std::vector<double> hip_model_base::branch_probability_table(const reconstructio
     for (size_t f = 0; f < F; ++f)
         for (size_t i = 0; i < order.size(); ++i) out[f * order.size() + i] = flat[f * n + pos.at(order[i])];
     return out;
+}
+
+marginal_result hip_model_base::marginal_reconstruction(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, double level,
+                                                        const std::vector<const clade*>& order) {
+    std::vector<double> mult, probs;
+    double alpha = 0;
+    category_parameters(mult, probs, alpha);
+    const int K = mult.empty() ? 1 : (int)mult.size();
+    ensure_context(K);
+    std::vector<float> prior_f;
+    std::vector<double> err, lambdas;
+    gather_call_inputs(prior, rootdist, prior_f, err, lambdas);
+    cafe_params pr{};
+    pr.model = mult.empty() ? CAFE_MODEL_BASE : CAFE_MODEL_GAMMA;
+    pr.lambdas = lambdas.data(); pr.n_categories = K;
+    pr.multipliers = mult.empty() ? nullptr : mult.data();
+    pr.cat_probs = probs.empty() ? nullptr : probs.data();
+    pr.alpha = alpha; pr.prior = prior_f.data(); pr.error_model = err.empty() ? nullptr : err.data();
+    const size_t n = _order.size(), F = _p_gene_families->size();
+    std::vector<double> mean(F * n), pi(F * n), pd(F * n);
+    std::vector<int32_t> mode(F * n), lo(F * n), hi(F * n);
+    marginal_result res;
+    res.level = level; res.n_nodes = order.size();
+    res.log_evidence.resize(F); res.failed.resize(F);
+    cafe_marginal_out out{};
+    out.mean = mean.data(); out.mode = mode.data(); out.lo = lo.data(); out.hi = hi.data(); out.p_increase = pi.data(); out.p_decrease = pd.data();
+    out.log_evidence = res.log_evidence.data(); out.failed = res.failed.data();
+    if (cafe_marginal_reconstruct(_ctx, &pr, level, &out) != CAFE_OK)
+        throw std::runtime_error(std::string("cafe_marginal_reconstruct: ") + cafe_last_error(_ctx));
+    std::map<const clade*, size_t> pos;
+    for (size_t v = 0; v < n; ++v) pos[_order[v]] = v;
+    const size_t m = order.size();
+    res.mean.resize(F * m); res.p_increase.resize(F * m); res.p_decrease.resize(F * m);
+    res.mode.resize(F * m); res.lo.resize(F * m); res.hi.resize(F * m);
+    for (size_t f = 0; f < F; ++f)
+        for (size_t i = 0; i < m; ++i) {
+            const size_t src = f * n + pos.at(order[i]), dst = f * m + i;
+            res.mean[dst] = mean[src]; res.mode[dst] = mode[src]; res.lo[dst] = lo[src]; res.hi[dst] = hi[src];
+            res.p_increase[dst] = pi[src]; res.p_decrease[dst] = pd[src];
+        }
+    return res;
+}
+
+void write_marginal_reports(const marginal_result& res, const std::string& model_identifier, const std::string& dir,
+                            const std::vector<const clade*>& order, const std::vector<gene_family>& families) {
+    const std::string prefix = (dir.empty() ? std::string("results") : dir) + "/" + model_identifier;
+    std::ofstream sizes(prefix + "_posterior_sizes.tab"), change(prefix + "_posterior_change.tab");
+    for (std::ofstream* f : {&sizes, &change}) {
+        *f << "FamilyID";
+        for (auto c : order) *f << "\t" << clade_index_or_name(c, order);
+        *f << std::endl;
+    }
+    char buf[128];
+    const size_t m = order.size();
+    for (size_t i = 0; i < families.size(); ++i) {
+        sizes << families[i].id();
+        change << families[i].id();
+        for (size_t v = 0; v < m; ++v) {
+            const size_t at = i * m + v;
+            std::snprintf(buf, sizeof buf, "\t%.6g:%d:%d-%d", res.mean[at], res.mode[at], res.lo[at], res.hi[at]);
+            sizes << buf;
+            if (order[v]->is_root()) change << "\t-";
+            else {
+                std::snprintf(buf, sizeof buf, "\t%.6g:%.6g", res.p_decrease[at], res.p_increase[at]);
+                change << buf;
+            }
+        }
+        sizes << std::endl;
+        change << std::endl;
+    }
 }
 
 reconstruction* hip_base_model::reconstruct_ancestral_states(const std::vector<gene_family>& families, root_equilibrium_distribution* p_prior) {

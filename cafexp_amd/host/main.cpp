@@ -23,6 +23,9 @@ static void usage() {
         "                  [-e [ERRMODEL]] [-p [POISSON_LAMBDA]] [-f ROOTDIST] [-z] [-s SEED] [-I MAXITER] [-d DEVICE | --gpus N] [--reps N] [--family-out FILE] [-o OUTDIR] [--limit N]\n"
         "                  [--pvalues NSIM [--pvalues-device] [--pvalues-out FILE] [--pvalues-cond FILE:K]] [--sizes M,R]\n"
         "                  [--reconstruct [-P PVALUE]]   (with -o: the reports of reconstruction::write_results)\n"
+        "                  [--reconstruct-marginal [LEVEL]]   posterior size of every node under the fitted model: mean, mode, equal-tailed\n"
+        "                  interval at LEVEL (default 0.95), probability that each branch contracted / expanded; with -o:\n"
+        "                  <Model>_posterior_sizes.tab (mean:mode:lo-hi) and <Model>_posterior_change.tab (p_decrease:p_increase); one GPU\n"
         "  --gpus N: the scorer calls shard the families over devices 0..N-1 (one host thread per GPU, one RCCL all-reduce per call)\n"
         "lambda per family (the reference's -b): cafexp_hip -t TREE -i FAMILIES -b [-y LAMBDA_TREE] [-e ERRMODEL] [-p [L]] [-z] [-s SEED] [-I MAXITER]\n"
         "                  [--workspace BYTES] [-o OUTDIR]   writes OUTDIR (default results)/Base_lambda_per_family.txt, one line per family\n"
@@ -128,6 +131,8 @@ int main(int argc, char** argv) {
     size_t sim_workspace = 0;
     int pvalue_sims = 0, force_m = -1, force_r = -1;
     bool do_reconstruct = false, pvalues_on_device = false;
+    bool do_marginal = false;                                    // --reconstruct-marginal [LEVEL]
+    double marginal_level = 0.95;
     double test_pvalue = 0.05;                                   // input_parameters::pvalue default (io.h)
     long limit = -1;
     double fixed_lambda = 0, fixed_alpha = -1, poisson = 0;
@@ -166,6 +171,7 @@ int main(int argc, char** argv) {
             force_m = std::stoi(v.substr(0, comma)); force_r = std::stoi(v.substr(comma + 1));
         }
         else if (a == "--reconstruct") do_reconstruct = true;
+        else if (a == "--reconstruct-marginal") { do_marginal = true; std::string v = optional(); if (!v.empty()) marginal_level = std::stod(v); }
         else if (a == "-P") test_pvalue = std::stod(next());
         else if (a == "--pvalues-device") pvalues_on_device = true;
         else if (a == "--pvalues") pvalue_sims = std::stoi(next());
@@ -183,6 +189,13 @@ int main(int argc, char** argv) {
                              simulate_n, simulate_on_device, have_seed ? seed : randomizer_engine(), device, sim_workspace, out_dir);
     }
     if (tree_path.empty() || fam_path.empty()) { usage(); return 2; }
+    if (do_marginal) {
+        const char* why = nullptr;
+        if (gpus_given) why = "--reconstruct-marginal runs on one GPU: --gpus is not supported with it";
+        else if (per_family) why = "--reconstruct-marginal needs one fitted model: -b is not supported with it";
+        else if (!(marginal_level > 0 && marginal_level < 1)) why = "--reconstruct-marginal: LEVEL must lie in (0, 1)";
+        if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
+    }
     if (per_family) {                                            // what -b cannot be combined with: refused before anything is read or written
         const char* why = nullptr;
         if (k > 1 || alpha_given) why = "-b estimates one lambda per family under the base model; -k > 1 and -a are not supported with it";
@@ -370,6 +383,18 @@ int main(int argc, char** argv) {
             for (const auto& gf : d.gene_families) n_with_probs += probs.contains(gf);
             if (!out_dir.empty()) rec->write_results(mdl->name(), out_dir, d.p_tree.get(), d.gene_families, pvalues, test_pvalue, probs);
         }
+        // marginal reconstruction with the model's final parameters and prior: independent of --reconstruct
+        double marginal_s = 0;
+        size_t marginal_failed = 0;
+        if (do_marginal) {
+            auto t0 = std::chrono::steady_clock::now();
+            cladevector order;
+            d.p_tree->apply_reverse_level_order([&order](const clade* c) { order.push_back(c); });
+            const marginal_result mr = mdl->marginal_reconstruction(d.p_prior.get(), d.rootdist, marginal_level, order);
+            marginal_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            marginal_failed = mr.failed_count();
+            if (!out_dir.empty()) write_marginal_reports(mr, mdl->name(), out_dir, order, d.gene_families);
+        }
         std::printf("{\"model\": \"%s\", ", mdl->name().c_str());
         print_num("neg_lnl", score);
         std::printf("\"n_families\": %zu, \"max_family_size\": %d, \"max_root_family_size\": %d, \"seconds_per_call\": %.6f, ",
@@ -398,6 +423,8 @@ int main(int argc, char** argv) {
         }
         if (do_reconstruct)
             std::printf(", \"reconstruct\": {\"seconds\": %.3f, \"families_with_branch_probabilities\": %zu}", reconstruct_s, n_with_probs);
+        if (do_marginal)
+            std::printf(", \"marginal\": {\"seconds\": %.3f, \"level\": %.17g, \"failed\": %zu}", marginal_s, marginal_level, marginal_failed);
         std::printf("}\n");
     } catch (const std::exception& e) {
         std::fprintf(stderr, "cafexp_hip: %s\n", e.what());

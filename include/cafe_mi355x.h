@@ -286,6 +286,36 @@ int cafe_reconstruct(cafe_ctx* ctx, const cafe_params* params, const float* root
  * reference returns "invalid" (the root; parent size == child size). */
 int cafe_branch_probabilities(cafe_ctx* ctx, const cafe_params* params, const int32_t* sizes, double* out);
 
+/* Marginal ancestral reconstruction under the SCORER's model (inference_prune with the call's lambdas, categories, prior
+ * and error model -- not cafe_reconstruct's joint variant): an up pass and a down pass of sum-products give, for every
+ * family f and node v, the posterior distribution of the node's size.  With the gamma model the categories are mixed with
+ * weights cat_probs[k] before anything is summarised.  Outputs, [n_families][n_nodes] in the problem's orders unless noted
+ * (host pointers, any may be NULL):
+ *   mean, mode (first arg max), lo / hi: the equal-tailed interval on the discrete CDF at `level` in (0, 1),
+ *     lo = min{j : CDF(j) >= (1 - level) / 2}, hi = min{j : CDF(j) >= 1 - (1 - level) / 2};
+ *   p_increase / p_decrease = P(X_v > X_parent | data) / P(X_v < X_parent | data) for the branch above v; NaN at the root;
+ *   a leaf's row is its observed count, or with an error model the posterior over the model's taps;
+ *   log_evidence[n_families] = log Z, Z = sum_k p_k sum_s prior[s-1] B_root[s]; failed[n_families] = 1 where Z is 0 or not
+ *     finite: that family's doubles are NaN and its integers -1 (the call still returns CAFE_OK).
+ * Reads model, lambdas, n_categories, multipliers, cat_probs, prior and error_model of params.  CAFE_ERR_ARGUMENT for a level
+ * outside (0, 1), invalid lambdas or a bad K; CAFE_ERR_STATE on a context with a communicator attached.  The columns are
+ * processed in batches that fit the problem's workspace_limit (0 = automatic); a value never depends on the batches.
+ * cafe_family_results is not meaningful after this call; a later cafe_score is unaffected. */
+typedef struct cafe_marginal_out {
+    double*  mean;
+    int32_t* mode;
+    int32_t* lo;
+    int32_t* hi;
+    double*  p_increase;
+    double*  p_decrease;
+    double*  log_evidence;
+    int32_t* failed;
+} cafe_marginal_out;
+int cafe_marginal_reconstruct(cafe_ctx* ctx, const cafe_params* params, double level, const cafe_marginal_out* out);
+/* measurement: flops of the GEMM launches of the last cafe_marginal_reconstruct and, when it ran with profiling on
+ * (cafe_set_profiling), their summed HIP-event time in milliseconds (else 0) */
+int cafe_debug_marginal_gemm(cafe_ctx* ctx, double* ms, double* flops);
+
 /* Introspection for parity tests: the transition matrix the last call built for the branch above
  * `node` in category k (N x N row-major, N = max(M,R)+1: matrix_cache::get_matrix; for an interior
  * branch the columns c > M, which the prune never reads, are not materialised and come back 0), and the root
