@@ -77,9 +77,18 @@ def _summary(post, z, level, first_size=0):
     return out
 
 
-def updown_family(pb, pr, mats, f, level):
+MUTANTS = ("split_takes_the_diagonal", "root_range_stops_short", "prior_indexed_at_s")
+
+
+def updown_family(pb, pr, mats, f, level, detail=False, mutant=None):
     """One family.  Returns a dict: per node arrays mean / mode / lo / hi / p_increase / p_decrease (+ the *_gap tie
-    measures), log_evidence, failed, and root_inside[k] = B_root[1..R] (inference_prune's return)."""
+    measures), log_evidence, failed, and root_inside[k] = B_root[1..R] (inference_prune's return).
+
+    detail: also Z, post[v] (the un-normalised posterior of node v over sizes 0..max(M, R), categories mixed) and
+    row0[v] = (G_v[0], sum_i G_v[i]) with G_v[0] = O[p][0] prod F_sib[0], p the parent of v (categories mixed).
+    mutant: one of MUTANTS -- a deliberately WRONG pass, for tests that ask whether their inputs can tell:
+    the branch split takes i <= j for i < j; the root takes sizes 1..R-1; the prior is read at s, not s - 1."""
+    assert mutant is None or mutant in MUTANTS, mutant
     n, M, R = pb.n_nodes, pb.max_family_size, pb.max_root_family_size
     ch, root = children_of(pb), root_of(pb)
     K = len(mats)
@@ -88,6 +97,7 @@ def updown_family(pb, pr, mats, f, level):
     post = [np.zeros(max(M, R) + 1) for _ in range(n)]
     inc, dec = np.zeros(n), np.zeros(n)
     root_inside = []
+    row0 = np.zeros((n, 2))
     Z = 0.0
     for k in range(K):
         P = mats[k]
@@ -105,6 +115,11 @@ def updown_family(pb, pr, mats, f, level):
         O = [None] * n
         o = np.zeros(R + 1)
         o[1:] = prior[:R]
+        if mutant == "root_range_stops_short":
+            o[R] = 0.0
+        elif mutant == "prior_indexed_at_s":
+            o[1:R] = prior[1:R]
+            o[R] = 0.0
         O[root] = o
         root_inside.append(B[root][1:R + 1].copy())
         Z += probs[k] * float((O[root] * B[root]).sum())
@@ -120,13 +135,17 @@ def updown_family(pb, pr, mats, f, level):
                         G = G * F[w]
                 Pv = P[v][:top + 1, :M + 1]
                 O[v] = G @ Pv
+                row0[v] += probs[k] * np.array([G[0], G.sum()])
                 post[v][:M + 1] += probs[k] * O[v] * B[v]
                 joint = G[:, None] * Pv * B[v][None, :]      # [parent size i][size j]
                 i = np.arange(top + 1)[:, None]
                 j = np.arange(M + 1)[None, :]
-                inc[v] += probs[k] * float(joint[i < j].sum())
+                inc[v] += probs[k] * float(joint[(i <= j) if mutant == "split_takes_the_diagonal" else (i < j)].sum())
                 dec[v] += probs[k] * float(joint[i > j].sum())
-    return _finish(pb, pr, f, level, post, inc, dec, Z, root_inside)
+    res = _finish(pb, pr, f, level, post, inc, dec, Z, root_inside)
+    if detail:
+        res.update(Z=Z, post=post, row0=row0)
+    return res
 
 
 def _finish(pb, pr, f, level, post, inc, dec, Z, root_inside):
@@ -212,14 +231,19 @@ def brute_force_family(pb, pr, mats, f, level):
 KEYS = ("mean", "mode", "lo", "hi", "p_increase", "p_decrease", "mode_gap", "lo_gap", "hi_gap")
 
 
-def updown(pb, pr, mats, level, families=None):
-    """All (or the listed) families -> arrays shaped like Context.marginal_reconstruct's, plus the tie measures."""
+def updown(pb, pr, mats, level, families=None, detail=False, mutant=None):
+    """All (or the listed) families -> arrays shaped like Context.marginal_reconstruct's, plus the tie measures (and with
+    detail: Z [family], post [family][node][size], row0 [family][node][2], see updown_family)."""
     fams = range(pb.n_families) if families is None else families
-    rows = [updown_family(pb, pr, mats, f, level) for f in fams]
+    rows = [updown_family(pb, pr, mats, f, level, detail=detail, mutant=mutant) for f in fams]
     out = {k: np.stack([r[k] for r in rows]) for k in KEYS}
     out["log_evidence"] = np.array([r["log_evidence"] for r in rows])
     out["failed"] = np.array([r["failed"] for r in rows], dtype=np.int32)
     out["root_inside"] = [r["root_inside"] for r in rows]
+    if detail:
+        out["Z"] = np.array([r["Z"] for r in rows])
+        out["post"] = np.array([r["post"] for r in rows])
+        out["row0"] = np.array([r["row0"] for r in rows])
     return out
 
 
