@@ -1,4 +1,6 @@
-// Internal: the context behind the C ABI handle, shared by cafe_ctx.hip (scorer path) and reconstruct.hip.
+// Internal: the context behind the C ABI handle and what the translation units of the library share.  cafe_create.hip builds
+// it, cafe_score.hip is the scorer's call path, cafe_debug.hip reads it back; reconstruct.hip, marginal.hip, pvalues.hip and
+// family_lambda.hip are the calls beside the scorer (their common frame: cafe_call.h), cafe_sharded.hip the multi-GPU layer.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -289,7 +291,16 @@ size_t plan_leaf_transposes(cafe_ctx* c, double lt_min, size_t free_bytes, std::
 void group_launches(cafe_ctx* c);
 void dump_schedule(const cafe_ctx* c);
 
+// cafe_create.hip
+int create_impl(cafe_ctx* c, const cafe_problem* p);     // everything cafe_create does to a fresh context
+void free_device(cafe_ctx* c);                            // releases what create_impl made, however far it got
+// cafe_score.hip
 bool lambdas_valid(const cafe_ctx* c, const double* lam);
+// one scorer call enqueued on `s`, {sum lnL, rejects} -> d_out; rootmax: max_j L_root[j] per family instead (-> d_fam_out)
+int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bool rootmax = false);
+void collect_stats(cafe_ctx* c);                          // the profiling events of the last call into c->stats
+// cafe_debug.hip: flops the K2 launches of the last call executed, from the extents it published (< 0: read-back failed)
+double count_executed_flops(cafe_ctx* c, std::vector<double>* per_launch = nullptr, bool per_block = true);
 // One slot per distinct quantized (lambda * multiplier, t) and layout (matrix_cache.h:42-61), parameters uploaded on
 // `s`, K1 launched: afterwards slot_of[node * Kmax + k] names the matrix of every branch and category.
 int prepare_matrices(cafe_ctx* c, const double* lambdas, const double* multipliers, int K, hipStream_t s);
@@ -298,8 +309,8 @@ int reconstruct_impl(cafe_ctx* c, const cafe_params* pr, const float* root_prior
 int branch_probabilities_impl(cafe_ctx* c, const cafe_params* pr, const int32_t* sizes, double* out);
 // Marginal reconstruction: posterior sizes, intervals and branch change probabilities (marginal.hip)
 int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_marginal_out* out);
-// Device-side p-values (pvalues.hip) and what it needs from cafe_ctx.hip: a context over the same tree whose family
-// counts are written on the device, and the root-maximum prune of a context's families (-> d_fam_out, on stream s)
+// Device-side p-values (pvalues.hip) and what it needs from cafe_create.hip and cafe_score.hip: a context over the same tree
+// whose family counts are written on the device, and the root-maximum prune of a context's families (-> d_fam_out, on stream s)
 constexpr int32_t kFlagDeviceCounts = 0x40000000;        // internal cafe_problem flag
 int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_simulations, uint64_t seed, double* pvalues);
 cafe_ctx* create_child_for_device_counts(const cafe_ctx* parent, int64_t n_families);

@@ -1,4 +1,4 @@
-// Host planner of cafe_create (cafe_ctx.hip): subtree patterns, schedule emission, step levelling, panel arena, extent
+// Host planner of cafe_create (cafe_create.hip): subtree patterns, schedule emission, step levelling, panel arena, extent
 // levels, leaf-transpose choice, launch grouping.  Nothing here calls HIP or reads the environment: every function reads
 // its inputs from its arguments and the context's host fields and writes host fields only.
 #include <algorithm>

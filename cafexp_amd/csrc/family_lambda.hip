@@ -33,7 +33,7 @@
 #include <vector>
 
 #include "bd_row.h"
-#include "cafe_ctx.h"
+#include "cafe_call.h"
 
 namespace cafe {
 
@@ -311,9 +311,7 @@ int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const i
             a.nodes = d_tables + o_level + level_off[lv];
             HIP_TRY(c, launch_family_lambda(a, c->N, nb, level_off[lv + 1] - level_off[lv], s));
         }
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(family_root_kernel, dim3((unsigned)nb), dim3(64), 0, s, ra);
-        HIP_TRY(c, hipGetLastError());
+        CAFE_LAUNCH(c, family_root_kernel, dim3((unsigned)nb), dim3(64), 0, s, ra);
         HIP_TRY(c, hipMemcpyAsync(res.data(), base + o_out, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));            // the host tables of this batch go out of use
         for (int64_t b = 0; b < nb; ++b) family_lnl[active[b0 + b]] = res[b];
@@ -324,13 +322,7 @@ int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const i
 }  // namespace cafe
 
 int cafe_score_per_family(cafe_ctx* ctx, const cafe_params* params, int64_t n, const int64_t* family, const double* lambdas, double* family_lnl) {
-    if (!ctx) return CAFE_ERR_ARGUMENT;
-    try {
-        const int rc = cafe::score_per_family_impl(ctx, params, n, family, lambdas, family_lnl);
-        if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
-        return rc;
-    } catch (const std::exception& e) {
-        cafe::set_err(ctx, "cafe_score_per_family: %s", e.what());
-        return CAFE_ERR_MEMORY;
-    }
+    const int rc = cafe::guarded(ctx, "cafe_score_per_family", [&] { return cafe::score_per_family_impl(ctx, params, n, family, lambdas, family_lnl); });
+    if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
+    return rc;
 }

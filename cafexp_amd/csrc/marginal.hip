@@ -17,7 +17,7 @@
 #include <limits>
 #include <vector>
 
-#include "cafe_ctx.h"
+#include "cafe_call.h"
 
 namespace cafe {
 
@@ -341,15 +341,6 @@ __global__ __launch_bounds__(256) void marginal_leaf_summary_kernel(const double
     out.hi[f] = hi < 0 ? last : hi;
 }
 
-template <int MODE>
-void launch_gemm(const GemmParams& g, bool mul, hipStream_t s) {
-    dim3 grid((unsigned)(g.ld / kNT), (unsigned)((g.nr + kMT - 1) / kMT));
-    if constexpr (MODE == kUp) {
-        if (mul) { hipLaunchKernelGGL((marginal_gemm_kernel<kUp, true>), grid, dim3(256), 0, s, g); return; }
-    }
-    hipLaunchKernelGGL((marginal_gemm_kernel<MODE, false>), grid, dim3(256), 0, s, g);
-}
-
 // HIP-event brackets of the GEMM launches (cafe_set_profiling): summed after the call
 struct GemmTimer {
     bool on = false;
@@ -373,6 +364,20 @@ struct GemmTimer {
     }
 };
 
+// One GEMM launch between the timer's marks; share: the part of its K tiles that runs
+template <int MODE>
+int launch_gemm(cafe_ctx* c, const GemmParams& g, bool mul, hipStream_t s, GemmTimer& timer, double share = 1.0) {
+    dim3 grid((unsigned)(g.ld / kNT), (unsigned)((g.nr + kMT - 1) / kMT));
+    timer.mark(s);
+    if constexpr (MODE == kUp) {
+        if (mul) CAFE_LAUNCH(c, (marginal_gemm_kernel<kUp, true>), grid, dim3(256), 0, s, g);
+    }
+    if (MODE != kUp || !mul) CAFE_LAUNCH(c, (marginal_gemm_kernel<MODE, false>), grid, dim3(256), 0, s, g);
+    timer.mark(s);
+    timer.flops += share * 2.0 * g.nr * g.nk * (double)g.ld;
+    return CAFE_OK;
+}
+
 }  // namespace
 
 int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_marginal_out* out) {
@@ -387,15 +392,8 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
     }
     if (!lambdas_valid(c, pr->lambdas)) { set_err(c, "cafe_marginal_reconstruct: invalid lambda"); return CAFE_ERR_ARGUMENT; }
     if (pr->error_model && c->n_dev < 1) { set_err(c, "cafe_marginal_reconstruct: the context was created without an error model"); return CAFE_ERR_ARGUMENT; }
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    if (c->upload_pending) { HIP_TRY(c, hipEventSynchronize(c->ev_upload)); c->upload_pending = false; }
-    c->have_results = false;
-    c->last_stream = s;
-    c->K_last = K;
-    { const int rc = prepare_matrices(c, pr->lambdas, gamma ? pr->multipliers : nullptr, K, s); if (rc != CAFE_OK) return rc; }
-    HIP_TRY(c, hipEventRecord(c->ev_upload, s));
-    c->upload_pending = true;
+    hipStream_t s = nullptr;
+    if (const int rc = begin_matrix_call(c, pr->lambdas, gamma ? pr->multipliers : nullptr, K, &s)) return rc;
 
     const int M = c->M, R = c->R, n = c->n_nodes, rows = c->N;      // a panel holds sizes 0..max(M, R)
     const bool has_err = pr->error_model != nullptr;
@@ -408,11 +406,9 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
     // sums, Z and the summaries
     const size_t dbl_per_col = (size_t)4 * nI * rows + 2 * (size_t)rows + (size_t)nL * (n_tap + 2) + 2 * (size_t)nI + 1 + 3 * (size_t)n;
     const size_t per_col = dbl_per_col * sizeof(double) + (size_t)3 * n * sizeof(int32_t);
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
-    const size_t budget = c->workspace_limit ? c->workspace_limit : (size_t)(free_b * 0.8);
-    const int64_t cols = std::min<int64_t>(c->Fp, (int64_t)(budget / per_col) / kBN * kBN);
-    if (cols < kBN) { set_err(c, "cafe_marginal_reconstruct: not enough device memory for the panels of %d interior nodes", nI); return CAFE_ERR_MEMORY; }
+    int64_t cols = 0;
+    if (const int rc = column_chunk(c, per_col, "cafe_marginal_reconstruct: not enough device memory for the panels of " + std::to_string(nI) + " interior nodes", &cols))
+        return rc;
     DevBuf wd, wi, dprior, derr;
     if (hipMalloc(&wd.p, dbl_per_col * cols * sizeof(double)) != hipSuccess || hipMalloc(&wi.p, (size_t)3 * n * cols * sizeof(int32_t)) != hipSuccess ||
         hipMalloc(&dprior.p, sizeof(double) * R) != hipSuccess ||
@@ -471,17 +467,15 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
                     const int w = mult[i];
                     if (c->leaf_taxon[w] >= 0) {
                         if (p.n_leaf == kMaxProd) break;
-                        p.P[p.n_leaf] = c->pool.base + (int64_t)c->slot_of[(size_t)w * c->Kmax + k] * c->pool.stride;
-                        p.cnt[p.n_leaf] = c->d_counts + (int64_t)c->leaf_taxon[w] * c->Fp + f0;
+                        p.P[p.n_leaf] = leaf_matrix(c, w, k);
+                        p.cnt[p.n_leaf] = leaf_counts(c, w, f0);
                         ++p.n_leaf;
                     } else {
                         if (p.n_pan == kMaxProd) break;
                         p.pan[p.n_pan++] = panel(d_F, w);
                     }
                 }
-                (void)hipGetLastError();
-                hipLaunchKernelGGL(marginal_product_kernel, dim3(gb, (unsigned)((nrows + 15) / 16)), dim3(256), 0, s, p);
-                HIP_TRY(c, hipGetLastError());
+                CAFE_LAUNCH(c, marginal_product_kernel, dim3(gb, (unsigned)((nrows + 15) / 16)), dim3(256), 0, s, p);
                 started = true;
             }
             return CAFE_OK;
@@ -504,23 +498,16 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
                 for (int v : c->children[p]) {
                     if (c->leaf_taxon[v] >= 0) continue;
                     GemmParams g{};
-                    g.Pt = c->kpool.base + (int64_t)c->slot_of[(size_t)v * c->Kmax + k] * c->kpool.stride;
+                    g.Pt = interior_matrix(c, v, k);
                     g.ldp = c->kpool.ld; g.X = panel(d_B, v); g.ld = ld; g.nr = np; g.nk = M + 1;
                     g.out1 = panel(d_F, v); g.out2 = panel(d_B, p);
-                    (void)hipGetLastError();
-                    timer.mark(s);
-                    launch_gemm<kUp>(g, started, s);
-                    timer.mark(s);
-                    HIP_TRY(c, hipGetLastError());
-                    timer.flops += 2.0 * g.nr * g.nk * (double)ld;
+                    if (const int rc = launch_gemm<kUp>(c, g, started, s, timer)) return rc;
                     started = true;
                 }
             }
             // ---- root, then parents before children
-            (void)hipGetLastError();
-            hipLaunchKernelGGL(marginal_root_kernel, dim3(gb, (unsigned)((R + 1 + 15) / 16)), dim3(256), 0, s, panel(d_B, c->root), d_prior, R, ld,
-                               panel(d_O, c->root), panel(d_A, c->root), pk, first);
-            HIP_TRY(c, hipGetLastError());
+            CAFE_LAUNCH(c, marginal_root_kernel, dim3(gb, (unsigned)((R + 1 + 15) / 16)), dim3(256), 0, s, panel(d_B, c->root), d_prior, R, ld, panel(d_O, c->root),
+                        panel(d_A, c->root), pk, first);
             for (int p = n - 1; p >= 0; --p) {
                 if (c->leaf_taxon[p] >= 0) continue;
                 const int np = p == c->root ? R : M;
@@ -528,55 +515,39 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
                     std::vector<int> sib;
                     for (int w : c->children[p]) if (w != v) sib.push_back(w);
                     { const int rc = product(panel(d_O, p), d_G, np + 1, sib, k); if (rc != CAFE_OK) return rc; }
-                    const int slot = c->slot_of[(size_t)v * c->Kmax + k];
                     if (c->leaf_taxon[v] >= 0) {
-                        (void)hipGetLastError();
-                        hipLaunchKernelGGL(marginal_leaf_kernel, dim3(gb), dim3(256), 0, s, d_G, np + 1, ld, c->pool.base + (int64_t)slot * c->pool.stride,
-                                           c->pool.ld, c->d_counts + (int64_t)c->leaf_taxon[v] * c->Fp + f0, d_err, n_dev, M,
-                                           d_leaf + (int64_t)lidx[v] * (n_tap + 2) * cols, pk, first);
-                        HIP_TRY(c, hipGetLastError());
+                        CAFE_LAUNCH(c, marginal_leaf_kernel, dim3(gb), dim3(256), 0, s, d_G, np + 1, ld, leaf_matrix(c, v, k), c->pool.ld, leaf_counts(c, v, f0), d_err,
+                                    n_dev, M, d_leaf + (int64_t)lidx[v] * (n_tap + 2) * cols, pk, first);
                         continue;
                     }
                     GemmParams g{};
-                    g.Pt = c->kpool.base + (int64_t)slot * c->kpool.stride;
+                    g.Pt = interior_matrix(c, v, k);
                     g.ldp = c->kpool.ld; g.X = d_G; g.ld = ld; g.nr = M + 1; g.nk = np;
                     g.out1 = panel(d_O, v); g.out2 = panel(d_A, v); g.Bv = panel(d_B, v); g.pk = pk; g.first = first;
-                    (void)hipGetLastError();
-                    timer.mark(s);
-                    launch_gemm<kDown>(g, false, s);
-                    timer.mark(s);
-                    HIP_TRY(c, hipGetLastError());
-                    timer.flops += 2.0 * g.nr * g.nk * (double)ld;
+                    if (const int rc = launch_gemm<kDown>(c, g, false, s, timer)) return rc;
                     for (int m = 1; m <= 2; ++m) {           // the branch split: i < j, then i > j
                         g.mask = m; g.out1 = d_D; g.out2 = nullptr;
-                        timer.mark(s);
-                        launch_gemm<kSplit>(g, false, s);
-                        timer.mark(s);
-                        HIP_TRY(c, hipGetLastError());
-                        timer.flops += 1.0 * g.nr * g.nk * (double)ld;       // about half of the K tiles run
-                        hipLaunchKernelGGL(marginal_colsum_kernel, dim3(gb), dim3(256), 0, s, d_D, M + 1, ld, d_br + ((int64_t)2 * bidx[v] + (m - 1)) * cols, pk, first);
-                        HIP_TRY(c, hipGetLastError());
+                        if (const int rc = launch_gemm<kSplit>(c, g, false, s, timer, 0.5)) return rc;      // about half of the K tiles run
+                        CAFE_LAUNCH(c, marginal_colsum_kernel, dim3(gb), dim3(256), 0, s, d_D, M + 1, ld, d_br + ((int64_t)2 * bidx[v] + (m - 1)) * cols, pk, first);
                     }
                 }
             }
         }
         // ---- summaries: the root first (it makes Z)
-        (void)hipGetLastError();
         for (int pass = 0; pass < 2; ++pass)
             for (int v = 0; v < n; ++v) {
                 if ((v == c->root) != (pass == 0)) continue;
                 SummaryOut so{d_mean + (int64_t)v * cols, d_mode + (int64_t)v * cols, d_lo + (int64_t)v * cols, d_hi + (int64_t)v * cols,
                               d_pinc + (int64_t)v * cols, d_pdec + (int64_t)v * cols};
                 if (c->leaf_taxon[v] >= 0) {
-                    hipLaunchKernelGGL(marginal_leaf_summary_kernel, dim3(gb), dim3(256), 0, s, d_leaf + (int64_t)lidx[v] * (n_tap + 2) * cols,
-                                       c->d_counts + (int64_t)c->leaf_taxon[v] * c->Fp + f0, n_dev, has_err ? 1 : 0, M, ld, d_Z, level, so);
+                    CAFE_LAUNCH(c, marginal_leaf_summary_kernel, dim3(gb), dim3(256), 0, s, d_leaf + (int64_t)lidx[v] * (n_tap + 2) * cols, leaf_counts(c, v, f0), n_dev,
+                                has_err ? 1 : 0, M, ld, d_Z, level, so);
                 } else {
                     const bool is_root = v == c->root;
                     const double* bi = is_root ? nullptr : d_br + (int64_t)2 * bidx[v] * cols;
-                    hipLaunchKernelGGL(marginal_summary_kernel, dim3(gb), dim3(256), 0, s, panel(d_A, v), is_root ? R : M, ld, d_Z, is_root ? 1 : 0, level, bi,
-                                       bi ? bi + cols : nullptr, so);
+                    CAFE_LAUNCH(c, marginal_summary_kernel, dim3(gb), dim3(256), 0, s, panel(d_A, v), is_root ? R : M, ld, d_Z, is_root ? 1 : 0, level, bi,
+                                bi ? bi + cols : nullptr, so);
                 }
-                HIP_TRY(c, hipGetLastError());
             }
         HIP_TRY(c, hipMemcpyAsync(h_mean.data(), d_mean, sizeof(double) * (size_t)n * cols, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(h_pinc.data(), d_pinc, sizeof(double) * (size_t)n * cols, hipMemcpyDeviceToHost, s));
@@ -586,11 +557,7 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
         HIP_TRY(c, hipMemcpyAsync(h_hi.data(), d_hi, sizeof(int32_t) * (size_t)n * cols, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(h_Z.data(), d_Z, sizeof(double) * (size_t)ld, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
-        // unique column -> every family that shares it
-        for (int64_t f = 0; f < c->F_all; ++f) {
-            const int64_t u = c->ref_of[f];
-            if (u < f0 || u >= f0 + ld) continue;
-            const int64_t col = u - f0;
+        for_each_family_of_chunk(c, f0, ld, [&](int64_t f, int64_t col) {
             const double z = h_Z[col];
             const bool bad = !(z > 0.0) || !std::isfinite(z);
             if (out->log_evidence) out->log_evidence[f] = bad ? nan : std::log(z);
@@ -604,7 +571,7 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
                 if (out->p_increase) out->p_increase[dst] = h_pinc[src];
                 if (out->p_decrease) out->p_decrease[dst] = h_pdec[src];
             }
-        }
+        });
     }
     c->upload_pending = false;
     // the matrices of this call stay readable (cafe_get_matrix); per-family scorer results are not meaningful
@@ -621,13 +588,7 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
 extern "C" {
 
 int cafe_marginal_reconstruct(cafe_ctx* ctx, const cafe_params* params, double level, const cafe_marginal_out* out) {
-    if (!ctx) return CAFE_ERR_ARGUMENT;
-    try {
-        return cafe::marginal_impl(ctx, params, level, out);
-    } catch (const std::exception& e) {
-        cafe::set_err(ctx, "cafe_marginal_reconstruct: %s", e.what());
-        return CAFE_ERR_MEMORY;
-    }
+    return cafe::guarded(ctx, "cafe_marginal_reconstruct", [&] { return cafe::marginal_impl(ctx, params, level, out); });
 }
 
 int cafe_debug_marginal_gemm(cafe_ctx* ctx, double* ms, double* flops) {

@@ -15,7 +15,7 @@
 //                 shared with simulate.hip like the generator and the draw)
 //   simulate      one thread per simulated family, nodes parents first; sizes in a [node][family] scratch, leaves
 //                 written straight into the child context's taxon-major count table
-//   (prune)       cafe_ctx.hip's root-maximum schedule on the child context and on the observed families
+//   (prune)       cafe_score.hip's root-maximum schedule on the child context and on the observed families
 //   sort_rows     bitonic sort of each root size's n values in LDS
 //   tree_pvalue   per observed family: max over root sizes of the upper_bound position
 #include <algorithm>
@@ -23,7 +23,7 @@
 #include <map>
 #include <vector>
 
-#include "cafe_ctx.h"
+#include "cafe_call.h"
 #include "tree_sampler.h"
 
 namespace cafe {
@@ -179,29 +179,29 @@ int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t see
     a.order = meta; a.parent = meta + n; a.slot = meta + 2 * n; a.leaf_taxon = meta + 3 * n;
     a.sizes = static_cast<int32_t*>(d_sizes.p); a.counts = child->d_counts; a.counts_ld = child->Fp; a.ld_f = Fs; a.n_families = Fs;
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(simulate_kernel, dim3((unsigned)((Fs + 255) / 256)), dim3(256), 0, s, a);
-    HIP_TRY(c, hipGetLastError());
+    CAFE_LAUNCH(c, simulate_kernel, dim3((unsigned)((Fs + 255) / 256)), dim3(256), 0, s, a);
     HIP_TRY(c, hipStreamSynchronize(s));                            // the child context runs on its own stream
     { const int rc = enqueue_rootmax(child, pr->lambdas, child->stream); if (rc != CAFE_OK) { set_err(c, "cafe_pvalues: %s", child->err.c_str()); return rc; } }
     HIP_TRY(c, hipMemcpyAsync(d_cond.p, child->d_fam_out, sizeof(double) * Fs, hipMemcpyDeviceToDevice, child->stream));
     int P2 = 1;
     while (P2 < n_sim) P2 <<= 1;
-    hipLaunchKernelGGL(sort_rows_kernel, dim3(R), dim3(256), sizeof(double) * P2, child->stream, static_cast<double*>(d_cond.p), n_sim);
-    HIP_TRY(c, hipGetLastError());
+    CAFE_LAUNCH(c, sort_rows_kernel, dim3(R), dim3(256), sizeof(double) * P2, child->stream, static_cast<double*>(d_cond.p), n_sim);
     HIP_TRY(c, hipStreamSynchronize(child->stream));
     child->upload_pending = false;
 
     // ---- p-value of every (distinct) observed family, spread to the families that share a column
-    hipLaunchKernelGGL(tree_pvalue_kernel, dim3((unsigned)((c->F_uniq + 255) / 256)), dim3(256), 0, s, c->d_fam_out, c->F_uniq,
-                       static_cast<const double*>(d_cond.p), R, n_sim, static_cast<double*>(d_pv.p));
-    HIP_TRY(c, hipGetLastError());
+    CAFE_LAUNCH(c, tree_pvalue_kernel, dim3((unsigned)((c->F_uniq + 255) / 256)), dim3(256), 0, s, c->d_fam_out, c->F_uniq, static_cast<const double*>(d_cond.p), R,
+                n_sim, static_cast<double*>(d_pv.p));
     std::vector<double> tmp((size_t)c->F_uniq);
     HIP_TRY(c, hipMemcpyAsync(tmp.data(), d_pv.p, sizeof(double) * c->F_uniq, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     c->upload_pending = false;
-    for (int64_t f = 0; f < c->F_all; ++f) pvalues[f] = tmp[c->ref_of[f]];
+    spread_unique(c, tmp.data(), pvalues);
     return CAFE_OK;
 }
 
 }  // namespace cafe
+
+extern "C" int cafe_pvalues(cafe_ctx* ctx, const cafe_params* params, int32_t n_simulations, uint64_t seed, double* pvalues) {
+    return cafe::guarded(ctx, "cafe_pvalues", [&] { return cafe::pvalues_impl(ctx, params, n_simulations, seed, pvalues); });
+}

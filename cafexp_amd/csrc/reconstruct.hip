@@ -24,7 +24,7 @@
 #include <memory>
 #include <vector>
 
-#include "cafe_ctx.h"
+#include "cafe_call.h"
 
 namespace cafe {
 
@@ -273,15 +273,8 @@ int reconstruct_impl(cafe_ctx* c, const cafe_params* pr, const float* root_prior
     const int K = gamma ? pr->n_categories : 1;
     if (gamma && (K < 1 || K > c->Kmax || !pr->multipliers)) { set_err(c, "cafe_reconstruct: gamma model needs 1..%d categories with multipliers", c->Kmax); return CAFE_ERR_ARGUMENT; }
     if (!lambdas_valid(c, pr->lambdas)) { set_err(c, "cafe_reconstruct: invalid lambda"); return CAFE_ERR_ARGUMENT; }
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    if (c->upload_pending) { HIP_TRY(c, hipEventSynchronize(c->ev_upload)); c->upload_pending = false; }
-    c->have_results = false;
-    c->last_stream = s;
-    c->K_last = K;
-    { const int rc = prepare_matrices(c, pr->lambdas, gamma ? pr->multipliers : nullptr, K, s); if (rc != CAFE_OK) return rc; }
-    HIP_TRY(c, hipEventRecord(c->ev_upload, s));
-    c->upload_pending = true;
+    hipStream_t s = nullptr;
+    if (const int rc = begin_matrix_call(c, pr->lambdas, gamma ? pr->multipliers : nullptr, K, &s)) return rc;
 
     const int M = c->M, jmax = std::min(c->M, c->R), n = c->n_nodes;
     std::vector<int> interior, bidx(n, -1);
@@ -290,13 +283,10 @@ int reconstruct_impl(cafe_ctx* c, const cafe_params* pr, const float* root_prior
     const int rows = round_up(M + 1, 4);                    // K5 walks the child sizes in groups of four
 
     // workspace: one product panel per interior node + the state table, sized to the free memory
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
     // (panels, the state table both ways round, the row-group flags: one int per 64 columns and 16 rows)
     const size_t per_col = (size_t)nI * rows * sizeof(double) + (size_t)2 * n * sizeof(int32_t) + (size_t)nI * ((M + 15) / 16) * sizeof(int32_t) / 64 + 1;
-    const size_t budget = c->workspace_limit ? c->workspace_limit : (size_t)(free_b * 0.8);
-    int64_t cols = std::min<int64_t>(c->Fp, (int64_t)(budget / per_col) / kBN * kBN);
-    if (cols < kBN) { set_err(c, "cafe_reconstruct: not enough device memory for %d product panels", nI); return CAFE_ERR_MEMORY; }
+    int64_t cols = 0;
+    if (const int rc = column_chunk(c, per_col, "cafe_reconstruct: not enough device memory for " + std::to_string(nI) + " product panels", &cols)) return rc;
     const int n_groups = (M + 15) / 16;                     // row groups of a panel (flags, see recon_leaf_kernel)
     const int64_t n_tiles = cols / 64;
     DevBuf panels, st, prior, flg;
@@ -334,56 +324,39 @@ int reconstruct_impl(cafe_ctx* c, const cafe_params* pr, const float* root_prior
                 double* dst = d_B + (int64_t)bidx[par] * pstride;
                 const bool mul = started[par];
                 started[par] = 1;
-                const int slot = c->slot_of[(size_t)v * c->Kmax + k];
-                (void)hipGetLastError();
+                int32_t* dfl = d_flags + (int64_t)bidx[par] * n_tiles * n_groups;
                 if (c->leaf_taxon[v] >= 0) {
-                    const double* P = c->pool.base + (int64_t)slot * c->pool.stride;
-                    const int32_t* cnt = c->d_counts + (int64_t)c->leaf_taxon[v] * c->Fp + f0;
                     dim3 grid((unsigned)((ld + 255) / 256), (unsigned)n_groups);
-                    int32_t* dfl = d_flags + (int64_t)bidx[par] * n_tiles * n_groups;
-                    if (mul) hipLaunchKernelGGL(recon_leaf_kernel<true>, grid, dim3(256), 0, s, P, c->pool.ld, cnt, dst, ld, M, dfl, n_groups);
-                    else hipLaunchKernelGGL(recon_leaf_kernel<false>, grid, dim3(256), 0, s, P, c->pool.ld, cnt, dst, ld, M, dfl, n_groups);
+                    CAFE_LAUNCH(c, mul ? recon_leaf_kernel<true> : recon_leaf_kernel<false>, grid, dim3(256), 0, s, leaf_matrix(c, v, k), c->pool.ld,
+                                leaf_counts(c, v, f0), dst, ld, M, dfl, n_groups);
                 } else {
-                    const double* Pt = c->kpool.base + (int64_t)slot * c->kpool.stride;
                     const double* B = d_B + (int64_t)bidx[v] * pstride;
                     const int n_ct = (int)(ld / 64), n_rg = (M + kRowsPerBlock - 1) / kRowsPerBlock;
                     dim3 grid((unsigned)(8 * ((n_ct + 7) / 8) * n_rg));
-                    const int32_t* ext = c->kpool.ext ? c->kpool.ext + (size_t)slot * c->kpool.ext_blocks * 2 : nullptr;
                     const int32_t* bfl = use_flags ? d_flags + (int64_t)bidx[v] * n_tiles * n_groups : nullptr;
-                    int32_t* dfl = d_flags + (int64_t)bidx[par] * n_tiles * n_groups;
-                    if (mul) hipLaunchKernelGGL(maxprod_kernel<true>, grid, dim3(256), 0, s, Pt, c->kpool.ld, B, dst, ld, M, c->kpool.rows, ext, bfl, dfl, n_groups);
-                    else hipLaunchKernelGGL(maxprod_kernel<false>, grid, dim3(256), 0, s, Pt, c->kpool.ld, B, dst, ld, M, c->kpool.rows, ext, bfl, dfl, n_groups);
+                    CAFE_LAUNCH(c, mul ? maxprod_kernel<true> : maxprod_kernel<false>, grid, dim3(256), 0, s, interior_matrix(c, v, k), c->kpool.ld, B, dst, ld,
+                                M, c->kpool.rows, interior_extents(c, v, k), bfl, dfl, n_groups);
                 }
-                HIP_TRY(c, hipGetLastError());
             }
             // ---- root choice, then parents before children
             const unsigned gb = (unsigned)((ld + 255) / 256);
-            hipLaunchKernelGGL(root_select_kernel, dim3(gb), dim3(256), 0, s, d_B + (int64_t)bidx[c->root] * pstride, ld,
-                               static_cast<const double*>(prior.p), jmax, d_state + (int64_t)c->root * cols);
-            HIP_TRY(c, hipGetLastError());
+            CAFE_LAUNCH(c, root_select_kernel, dim3(gb), dim3(256), 0, s, d_B + (int64_t)bidx[c->root] * pstride, ld, static_cast<const double*>(prior.p), jmax,
+                        d_state + (int64_t)c->root * cols);
             for (int v = n - 1; v >= 0; --v) {
                 if (v == c->root) continue;
                 if (c->leaf_taxon[v] >= 0) {
-                    HIP_TRY(c, hipMemcpyAsync(d_state + (int64_t)v * cols, c->d_counts + (int64_t)c->leaf_taxon[v] * c->Fp + f0, sizeof(int32_t) * ld,
-                                              hipMemcpyDeviceToDevice, s));
+                    HIP_TRY(c, hipMemcpyAsync(d_state + (int64_t)v * cols, leaf_counts(c, v, f0), sizeof(int32_t) * ld, hipMemcpyDeviceToDevice, s));
                     continue;
                 }
-                const int slot = c->slot_of[(size_t)v * c->Kmax + k];
-                hipLaunchKernelGGL(backtrack_kernel, dim3((unsigned)(ld / 64)), dim3(256), 0, s, c->kpool.base + (int64_t)slot * c->kpool.stride, c->kpool.ld,
-                                   d_B + (int64_t)bidx[v] * pstride, ld, M, d_state + (int64_t)c->parent[v] * cols, d_state + (int64_t)v * cols,
-                                   c->kpool.ext ? c->kpool.ext + (size_t)slot * c->kpool.ext_blocks * 2 : nullptr);
-                HIP_TRY(c, hipGetLastError());
+                CAFE_LAUNCH(c, backtrack_kernel, dim3((unsigned)(ld / 64)), dim3(256), 0, s, interior_matrix(c, v, k), c->kpool.ld, d_B + (int64_t)bidx[v] * pstride,
+                            ld, M, d_state + (int64_t)c->parent[v] * cols, d_state + (int64_t)v * cols, interior_extents(c, v, k));
             }
-            hipLaunchKernelGGL(state_transpose_kernel, dim3(gb, (unsigned)((n + 15) / 16)), dim3(256), 0, s, d_state, n, cols, ld, d_state_t);
-            HIP_TRY(c, hipGetLastError());
+            CAFE_LAUNCH(c, state_transpose_kernel, dim3(gb, (unsigned)((n + 15) / 16)), dim3(256), 0, s, d_state, n, cols, ld, d_state_t);
             HIP_TRY(c, hipMemcpyAsync(h_state.get(), d_state_t, sizeof(int32_t) * (size_t)n * ld, hipMemcpyDeviceToHost, s));
             HIP_TRY(c, hipStreamSynchronize(s));
-            // unique column -> every family that shares it
-            for (int64_t f = 0; f < c->F_all; ++f) {
-                const int64_t u = c->ref_of[f];
-                if (u < f0 || u >= f0 + ld) continue;
-                std::memcpy(states + ((int64_t)k * c->F_all + f) * n, h_state.get() + (size_t)(u - f0) * n, sizeof(int32_t) * n);
-            }
+            for_each_family_of_chunk(c, f0, ld, [&](int64_t f, int64_t col) {
+                std::memcpy(states + ((int64_t)k * c->F_all + f) * n, h_state.get() + (size_t)col * n, sizeof(int32_t) * n);
+            });
         }
     c->upload_pending = false;
     return CAFE_OK;
@@ -396,15 +369,8 @@ int branch_probabilities_impl(cafe_ctx* c, const cafe_params* pr, const int32_t*
     const int64_t F = c->F_all;
     for (int64_t i = 0; i < F * n; ++i)
         if (sizes[i] < 0 || sizes[i] > c->M) { set_err(c, "cafe_branch_probabilities: size outside [0, %d] for family %lld", c->M, (long long)(i / n)); return CAFE_ERR_ARGUMENT; }
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    if (c->upload_pending) { HIP_TRY(c, hipEventSynchronize(c->ev_upload)); c->upload_pending = false; }
-    c->have_results = false;
-    c->last_stream = s;
-    c->K_last = 1;
-    { const int rc = prepare_matrices(c, pr->lambdas, nullptr, 1, s); if (rc != CAFE_OK) return rc; }     // the plain lambda (execute.cpp:158)
-    HIP_TRY(c, hipEventRecord(c->ev_upload, s));
-    c->upload_pending = true;
+    hipStream_t s = nullptr;
+    if (const int rc = begin_matrix_call(c, pr->lambdas, nullptr, 1, &s)) return rc;                      // the plain lambda (execute.cpp:158)
     std::vector<int32_t> h_parent(n), h_leaf(n), h_slot(n, 0);
     for (int v = 0; v < n; ++v) {
         h_parent[v] = c->parent[v];
@@ -423,10 +389,8 @@ int branch_probabilities_impl(cafe_ctx* c, const cafe_params* pr, const int32_t*
     HIP_TRY(c, hipMemcpyAsync(meta, h_parent.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(meta + n, h_leaf.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(meta + 2 * n, h_slot.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(viterbi_kernel, dim3((unsigned)((F * n + 255) / 256)), dim3(256), 0, s, static_cast<const int32_t*>(d_sizes.p), F, n, meta, meta + n,
-                       meta + 2 * n, c->pool, c->kpool, c->M, static_cast<double*>(d_out.p));
-    HIP_TRY(c, hipGetLastError());
+    CAFE_LAUNCH(c, viterbi_kernel, dim3((unsigned)((F * n + 255) / 256)), dim3(256), 0, s, static_cast<const int32_t*>(d_sizes.p), F, n, meta, meta + n, meta + 2 * n,
+                c->pool, c->kpool, c->M, static_cast<double*>(d_out.p));
     HIP_TRY(c, hipMemcpyAsync(out, d_out.p, sizeof(double) * F * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     c->upload_pending = false;
@@ -434,3 +398,11 @@ int branch_probabilities_impl(cafe_ctx* c, const cafe_params* pr, const int32_t*
 }
 
 }  // namespace cafe
+
+extern "C" int cafe_reconstruct(cafe_ctx* ctx, const cafe_params* params, const float* root_prior, int32_t* states) {
+    return cafe::guarded(ctx, "cafe_reconstruct", [&] { return cafe::reconstruct_impl(ctx, params, root_prior, states); });
+}
+
+extern "C" int cafe_branch_probabilities(cafe_ctx* ctx, const cafe_params* params, const int32_t* sizes, double* out) {
+    return cafe::guarded(ctx, "cafe_branch_probabilities", [&] { return cafe::branch_probabilities_impl(ctx, params, sizes, out); });
+}

@@ -355,7 +355,7 @@ def shard_families(n_families: int, world_size: int, rank: int) -> Tuple[int, in
 
 def shard_families_by_pattern_cost(pb: "Problem", world_size: int) -> List[np.ndarray]:
     """Family indices of every rank for the multi-GPU path when the device shares likelihood columns between families
-    that agree on a whole subtree (csrc/cafe_ctx.hip, compute_patterns): a shard's work is the number of DISTINCT
+    that agree on a whole subtree (csrc/cafe_schedule.hip, plan_patterns): a shard's work is the number of DISTINCT
     leaf-count patterns under every interior node, not its number of families.  Families are ordered by total size and
     then lexicographically, so that look-alikes land on the same rank; a family's cost is the number of interior nodes at
     which it is the first of its shard-order neighbours to show its pattern, and the ranks get consecutive runs of equal
