@@ -88,6 +88,7 @@ EXPORTS = [
     "cafe_sharded_size", "cafe_sharded_context", "cafe_set_graphs", "cafe_executed_flops", "cafe_debug_tile_range_flops", "cafe_get_extents", "cafe_debug_launch_flops", "cafe_debug_launch_ms", "cafe_debug_plan_check",
     "cafe_debug_fail_next", "cafe_debug_column_extents", "cafe_debug_leaf_transposes", "cafe_simulate",
     "cafe_score_per_family", "cafe_marginal_reconstruct", "cafe_debug_marginal_gemm",
+    "cafe_set_death_rates", "cafe_bd_rates", "cafe_build_matrices_lm",
 ]
 CAFE_COMM_ID_BYTES = 128
 
@@ -153,6 +154,12 @@ def load():
     L.cafe_matrix_size.argtypes = [C.c_void_p]
     L.cafe_build_matrices.restype = C.c_int
     L.cafe_build_matrices.argtypes = [C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, C.c_int32, _f64p]
+    L.cafe_build_matrices_lm.restype = C.c_int
+    L.cafe_build_matrices_lm.argtypes = [C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, C.c_int32, _f64p]
+    L.cafe_set_death_rates.restype = C.c_int
+    L.cafe_set_death_rates.argtypes = [C.c_void_p, _f64p]
+    L.cafe_bd_rates.restype = C.c_int
+    L.cafe_bd_rates.argtypes = [C.c_double, C.c_double, C.c_double, _f64p]
     L.cafe_probe_fp64_mfma.restype = C.c_int
     L.cafe_probe_fp64_mfma.argtypes = [C.c_int32, _f64p]
     L.cafe_debug_stamps.restype = C.c_int
@@ -553,6 +560,18 @@ class Context:
         """Test hook: the n-th next call of this context fails with CAFE_ERR_DEVICE in the middle of its enqueue."""
         self._check(self._lib.cafe_debug_fail_next(self._h, n))
 
+    def set_death_rates(self, mus):
+        """cafe_set_death_rates: from now on every call of this context scores the birth-death process with birth rate
+        lambdas[i] and death rate mus[i] (one per lambda index); None restores lambda = mu."""
+        if mus is None:
+            self._check(self._lib.cafe_set_death_rates(self._h, None))
+            return
+        mu = np.ascontiguousarray(np.atleast_1d(mus), dtype=np.float64)
+        pb = getattr(self, "problem", None)                  # (a shard borrowed from a Sharded object does not know its problem)
+        if pb is not None and mu.shape != (pb.n_lambdas,):
+            raise ValueError("mus must have %d entries" % pb.n_lambdas)
+        self._check(self._lib.cafe_set_death_rates(self._h, _p(mu, _f64p)))
+
     def set_graphs(self, on: bool):
         """False: enqueue every call launch by launch instead of replaying its captured hipGraph."""
         self._check(self._lib.cafe_set_graphs(self._h, 1 if on else 0))
@@ -635,6 +654,29 @@ def build_matrices(n: int, lambdas, ts, device: int = 0, layout: int = 0) -> np.
     rc = load().cafe_build_matrices(device, n, len(lam), _p(lam, _f64p), _p(t, _f64p), layout, _p(out, _f64p))
     if rc:
         raise CafeError("cafe_build_matrices failed with code %d" % rc)
+    return out
+
+
+def bd_rates(lam: float, mu: float, t: float):
+    """cafe_bd_rates: (alpha, beta, zero) of the quantized key (lambda, mu, t).  Host code: needs no GPU."""
+    out = np.empty(3)
+    rc = load().cafe_bd_rates(float(lam), float(mu), float(t), _p(out, _f64p))
+    if rc:
+        raise CafeError("cafe_bd_rates failed with code %d" % rc)
+    return float(out[0]), float(out[1]), bool(out[2])
+
+
+def build_matrices_lm(n: int, lambdas, mus, ts, device: int = 0, layout: int = 0) -> np.ndarray:
+    """cafe_build_matrices_lm: the two-rate kernel's matrices for (lambdas[i], mus[i], ts[i]), always P[s][c] row-major."""
+    lam = np.ascontiguousarray(lambdas, dtype=np.float64)
+    mu = np.ascontiguousarray(mus, dtype=np.float64)
+    t = np.ascontiguousarray(ts, dtype=np.float64)
+    if not (lam.shape == mu.shape == t.shape):
+        raise ValueError("lambdas, mus and ts must have the same length")
+    out = np.empty((len(lam), n, n))
+    rc = load().cafe_build_matrices_lm(device, n, len(lam), _p(lam, _f64p), _p(mu, _f64p), _p(t, _f64p), layout, _p(out, _f64p))
+    if rc:
+        raise CafeError("cafe_build_matrices_lm failed with code %d" % rc)
     return out
 
 

@@ -33,6 +33,7 @@ void free_device(cafe_ctx* c) {
     auto free_desc = [](DescSet& d) { hipFree(d.d_gemm_ops); hipFree(d.d_plan_desc); hipFree(d.d_plan); d = DescSet(); };
     free_desc(c->desc);
     for (auto& g : c->graphs) free_desc(g.second.desc);
+    hipFree(c->d_slots_lm); if (c->h_slots_lm) hipHostFree(c->h_slots_lm);
     hipFree(c->d_gather_ops); hipFree(c->d_lt); hipFree(c->d_lt_pairs); hipFree(c->pf_dev);
     if (c->ev_upload) hipEventDestroy(c->ev_upload);
     for (auto& e : c->ev) if (e) hipEventDestroy(e);

@@ -144,6 +144,12 @@ struct cafe_ctx {
     char* d_params = nullptr;
     size_t params_bytes = 0;
     cafe::SlotParam* d_slots = nullptr;                   // [max_slots] row-major, then [max_kslots] k-major
+    // cafe_set_death_rates: while `mus` is not empty every call builds its matrices with the two-rate kernel
+    // (bd_matrix_lm.hip) from slot parameters of their own -- device array and pinned mirror, [max_slots] row-major then
+    // [max_kslots] k-major, allocated by the first call of the setter
+    std::vector<double> mus;                 // [n_lambdas] death rate per lambda index; empty: lambda = mu
+    cafe::SlotParamLM* d_slots_lm = nullptr;
+    cafe::SlotParamLM* h_slots_lm = nullptr;
     double* d_panels = nullptr;
     int64_t panel_stride = 0;               // doubles per panel
     int64_t panel_kstride = 0;              // doubles per category inside a panel
@@ -296,6 +302,13 @@ int create_impl(cafe_ctx* c, const cafe_problem* p);     // everything cafe_crea
 void free_device(cafe_ctx* c);                            // releases what create_impl made, however far it got
 // cafe_score.hip
 bool lambdas_valid(const cafe_ctx* c, const double* lam);
+bool rates_valid(const cafe_ctx* c, const double* lam);  // lambdas_valid, and no death rate of the context (cafe_set_death_rates) negative
+int set_death_rates_impl(cafe_ctx* c, const double* mus);     // cafe_set_death_rates: [n_lambdas] or nullptr (lambda = mu again)
+// the (lambda, mu) of lambda index i under multiplier `mult` as the matrix key quantizes them; mu = lambda without death rates
+inline void quantized_rates(const cafe_ctx* c, const double* lambdas, int i, double mult, long* lq, long* mq) {
+    *lq = quantize_lambda(lambdas[i] * mult);
+    *mq = c->mus.empty() ? *lq : quantize_lambda(c->mus[i] * mult);
+}
 // one scorer call enqueued on `s`, {sum lnL, rejects} -> d_out; rootmax: max_j L_root[j] per family instead (-> d_fam_out)
 int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bool rootmax = false);
 void collect_stats(cafe_ctx* c);                          // the profiling events of the last call into c->stats

@@ -329,7 +329,8 @@ int cafe_get_root_likelihoods(cafe_ctx* ctx, int64_t family, int32_t category, d
     return CAFE_OK;
 }
 
-int cafe_build_matrices(int32_t device, int32_t n, int32_t count, const double* lambdas, const double* ts, int32_t layout, double* out) {
+// cafe_build_matrices (mus == nullptr: K1) and cafe_build_matrices_lm (the two-rate kernel)
+static int build_matrices(int32_t device, int32_t n, int32_t count, const double* lambdas, const double* mus, const double* ts, int32_t layout, double* out) {
     if (n < 2 || count < 1 || !lambdas || !ts || !out || n > bd_matrix_max_order()) return CAFE_ERR_ARGUMENT;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CAFE_ERR_DEVICE;
@@ -339,16 +340,24 @@ int cafe_build_matrices(int32_t device, int32_t n, int32_t count, const double* 
         pool.rows = round_up(n, kBK); pool.k_valid = n; pool.kmajor = 1;
         pool.ld = round_up(n - 1, 16) + 16; pool.stride = (int64_t)pool.rows * pool.ld;
     }
-    std::vector<SlotParam> sp(count);
-    for (int i = 0; i < count; ++i) sp[i] = slot_param(quantize_lambda(lambdas[i]), quantize_time(ts[i]));
-    SlotParam* d_sp = nullptr;
+    std::vector<SlotParam> sp(mus ? 0 : count);
+    std::vector<SlotParamLM> sp_lm(mus ? count : 0);
+    for (int i = 0; i < count; ++i) {
+        if (mus) sp_lm[i] = slot_param_lm(quantize_lambda(lambdas[i]), quantize_lambda(mus[i]), quantize_time(ts[i]));
+        else sp[i] = slot_param(quantize_lambda(lambdas[i]), quantize_time(ts[i]));
+    }
+    const size_t sp_bytes = mus ? sizeof(SlotParamLM) * count : sizeof(SlotParam) * count;
+    const void* h_sp = mus ? (const void*)sp_lm.data() : (const void*)sp.data();
+    void* d_sp = nullptr;
     int rc = CAFE_OK;
     const size_t bytes = sizeof(double) * pool.stride * count;
     if (hipMalloc(&pool.base, bytes) != hipSuccess) return CAFE_ERR_MEMORY;
-    if (hipMalloc(&d_sp, sizeof(SlotParam) * count) != hipSuccess) { (void)hipFree(pool.base); return CAFE_ERR_MEMORY; }
+    if (hipMalloc(&d_sp, sp_bytes) != hipSuccess) { (void)hipFree(pool.base); return CAFE_ERR_MEMORY; }
     if (hipMemset(pool.base, 0, bytes) != hipSuccess) rc = CAFE_ERR_DEVICE;
-    if (rc == CAFE_OK && hipMemcpy(d_sp, sp.data(), sizeof(SlotParam) * count, hipMemcpyHostToDevice) != hipSuccess) rc = CAFE_ERR_DEVICE;
-    if (rc == CAFE_OK && launch_bd_matrix_build(pool, d_sp, count, nullptr) != hipSuccess) rc = CAFE_ERR_DEVICE;
+    if (rc == CAFE_OK && hipMemcpy(d_sp, h_sp, sp_bytes, hipMemcpyHostToDevice) != hipSuccess) rc = CAFE_ERR_DEVICE;
+    if (rc == CAFE_OK && (mus ? launch_bd_lm_build(pool, static_cast<const SlotParamLM*>(d_sp), count, nullptr)
+                              : launch_bd_matrix_build(pool, static_cast<const SlotParam*>(d_sp), count, nullptr)) != hipSuccess)
+        rc = CAFE_ERR_DEVICE;
     if (rc == CAFE_OK && hipDeviceSynchronize() != hipSuccess) rc = CAFE_ERR_DEVICE;
     std::vector<double> tmp;
     for (int i = 0; i < count && rc == CAFE_OK; ++i) {
@@ -372,6 +381,15 @@ int cafe_build_matrices(int32_t device, int32_t n, int32_t count, const double* 
     (void)hipFree(pool.base);
     (void)hipFree(d_sp);
     return rc;
+}
+
+int cafe_build_matrices(int32_t device, int32_t n, int32_t count, const double* lambdas, const double* ts, int32_t layout, double* out) {
+    return build_matrices(device, n, count, lambdas, nullptr, ts, layout, out);
+}
+
+int cafe_build_matrices_lm(int32_t device, int32_t n, int32_t count, const double* lambdas, const double* mus, const double* ts, int32_t layout, double* out) {
+    if (!mus) return CAFE_ERR_ARGUMENT;
+    return build_matrices(device, n, count, lambdas, mus, ts, layout, out);
 }
 
 int cafe_probe_fp64_mfma(int32_t device, double* tflops) {

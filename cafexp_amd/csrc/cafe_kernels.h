@@ -68,6 +68,55 @@ inline SlotParam slot_param(long lq, long tq) {
     sp.pad = 0;
     return sp;
 }
+// Separate birth and death rates (bd_matrix_lm.hip).  The single-lineage law of the linear birth-death process is
+// p1(0) = alpha, p1(k) = (1-alpha)(1-beta) beta^(k-1),
+//     alpha = mu (E-1) / (lambda E - mu),   beta = lambda (E-1) / (lambda E - mu),   E = exp((lambda - mu) t).
+// Evaluated as w = -expm1(-|lambda-mu| t), D = |lambda-mu| + min(lambda, mu) w, alpha = mu w / D, beta = lambda w / D: every
+// term is non-negative, nothing overflows however large |lambda-mu| t is, and both tend to lambda t / (1 + lambda t) as
+// mu -> lambda.  Equal rates take that formula itself, so that alpha has slot_param's bits.  Mathematically alpha, beta < 1;
+// a quotient that rounds up to 1 is put back to the largest double below it.  Plain doubles in, no quantization.
+struct BdRates { double alpha, beta, coeff; };
+inline BdRates bd_rates(double lambda, double mu, double t) {
+    BdRates r;
+    if (lambda == mu) {
+        r.alpha = r.beta = lambda * t / (1 + lambda * t);
+        r.coeff = 1 - 2 * r.alpha;
+        return r;
+    }
+    const double d = lambda > mu ? lambda - mu : mu - lambda, lo = lambda > mu ? mu : lambda;
+    const double w = -expm1(-d * t), D = d + lo * w;
+    r.alpha = mu * w / D;
+    r.beta = lambda * w / D;
+    const double below_one = 1.0 - 0x1p-53;
+    if (!(r.alpha < 1.0)) r.alpha = below_one;
+    if (!(r.beta < 1.0)) r.beta = below_one;
+    r.coeff = 1 - r.alpha - r.beta;
+    return r;
+}
+// Per transition matrix of the two-rate kernel: q = (1-alpha)(1-beta).  zero carries the reference's saturation rule
+// (matrix_cache.cpp:153, probability.cpp:154) over to coeff = 1 - alpha - beta: a convention that keeps the model continuous
+// at mu = lambda (the recurrence itself is well defined wherever alpha, beta < 1).  A 32-byte struct of its own: SlotParam,
+// and with it the code of the lambda = mu kernels, stays what it is.
+struct SlotParamLM {
+    double alpha;
+    double beta;
+    double q;
+    int32_t zero;
+    int32_t pad;
+};
+inline SlotParamLM slot_param_lm(long lq, long mq, long tq) {
+    const BdRates r = bd_rates(double(lq) / 1000000000.0, double(mq) / 1000000000.0, double(tq) / 1000.0);
+    SlotParamLM sp;
+    sp.alpha = r.alpha;
+    sp.beta = r.beta;
+    sp.q = (1 - r.alpha) * (1 - r.beta);
+    sp.zero = !(r.coeff > 0 && r.coeff != 1);
+    sp.pad = 0;
+    return sp;
+}
+hipError_t launch_bd_lm_build(const MatrixPool& pool, const SlotParamLM* d_slots, int n_slots, hipStream_t stream);
+hipError_t launch_bd_lm_build_both(const MatrixPool& pool, const MatrixPool& kpool, const SlotParamLM* d_slots, const SlotParamLM* d_kslots,
+                                   int n_slots, int n_kslots, hipStream_t stream);
 // A row-major pool of matrices of order n, not yet placed (base null, no extents)
 inline MatrixPool row_major_pool(int n) {
     MatrixPool p{};

@@ -42,6 +42,31 @@ bool lambdas_valid(const cafe_ctx* c, const double* lam) {
     return true;
 }
 
+// ... and the death rates of the context, when it has any: no rate may be negative (one lambda: that lambda > 0 as above)
+bool rates_valid(const cafe_ctx* c, const double* lam) {
+    if (!lambdas_valid(c, lam)) return false;
+    for (const double mu : c->mus) if (!(mu >= 0)) return false;
+    return true;
+}
+
+int set_death_rates_impl(cafe_ctx* c, const double* mus) {
+    if (!mus) { c->mus.clear(); return CAFE_OK; }
+    // (each buffer on its own pointer: a setter that failed half way allocates only what is still missing)
+    const size_t nb = sizeof(SlotParamLM) * (size_t)std::max(1, c->max_slots + c->max_kslots);
+    if (!c->h_slots_lm) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipHostMalloc(&c->h_slots_lm, nb, hipHostMallocDefault));
+        std::memset(c->h_slots_lm, 0, nb);
+    }
+    if (!c->d_slots_lm) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipMalloc(&c->d_slots_lm, nb));
+        HIP_TRY(c, hipMemset(c->d_slots_lm, 0, nb));
+    }
+    c->mus.assign(mus, mus + c->n_lambdas);
+    return CAFE_OK;
+}
+
 // The pinned stage (and the other pinned mirrors) may be rewritten once the last call's uploads from it have landed
 int wait_for_stage(cafe_ctx* c) {
     if (c->upload_pending) { HIP_TRY(c, hipEventSynchronize(c->ev_upload)); c->upload_pending = false; }
@@ -61,9 +86,37 @@ void fill_slots(cafe_ctx* c, const double* lambdas, const double* multipliers, i
             }
         }
     }
+    if (!c->mus.empty()) {                   // death rates set: the two-rate kernel's parameters, same slots (the multiplier scales both rates)
+        SlotParamLM* hl[2] = {c->h_slots_lm, c->h_slots_lm + c->max_slots};
+        for (int layout = 0; layout < 2; ++layout) {
+            const int P = c->n_pairs[layout];
+            for (int k = 0; k < K; ++k)
+                for (int p = 0; p < P; ++p) {
+                    long lq, mq;
+                    quantized_rates(c, lambdas, c->pair_lam[layout][p], multipliers ? multipliers[k] : 1.0, &lq, &mq);
+                    hl[layout][k * P + p] = slot_param_lm(lq, mq, c->pair_tq[layout][p]);
+                }
+        }
+    }
     c->n_slots_last = K * c->n_pairs[0];
     c->n_kslots_last = K * c->n_pairs[1];
     c->stats.n_matrices = (int64_t)K * c->n_distinct_pairs;
+}
+
+// K1 of a call whose slot parameters fill_slots left in the pinned mirrors: the lambda = mu kernels, or with death rates set
+// their two-rate twins behind an upload of their own parameters
+int upload_lm_slots(cafe_ctx* c, hipStream_t s) {
+    if (c->mus.empty()) return CAFE_OK;
+    const size_t n = (size_t)(c->max_slots + c->max_kslots);         // (the buffers hold max(1, n): a context without slots uploads nothing)
+    if (n) HIP_TRY(c, hipMemcpyAsync(c->d_slots_lm, c->h_slots_lm, sizeof(SlotParamLM) * n, hipMemcpyHostToDevice, s));
+    return CAFE_OK;
+}
+int launch_call_matrices(cafe_ctx* c, hipStream_t s) {
+    if (c->mus.empty())
+        HIP_TRY(c, launch_bd_matrix_build_both(c->pool, c->kpool, c->d_slots, c->d_slots + c->max_slots, c->n_slots_last, c->n_kslots_last, s));
+    else
+        HIP_TRY(c, launch_bd_lm_build_both(c->pool, c->kpool, c->d_slots_lm, c->d_slots_lm + c->max_slots, c->n_slots_last, c->n_kslots_last, s));
+    return CAFE_OK;
 }
 
 // For the callers outside the scorer path (begin_matrix_call, cafe_call.h): slot parameters uploaded on `s`, K1 launched.  Afterwards
@@ -73,17 +126,17 @@ int prepare_matrices(cafe_ctx* c, const double* lambdas, const double* multiplie
     fill_slots(c, lambdas, multipliers, K);
     const size_t nb = sizeof(SlotParam) * (size_t)(c->max_slots + c->max_kslots);
     HIP_TRY(c, hipMemcpyAsync(c->d_params, c->h_stage, nb, hipMemcpyHostToDevice, s));
+    if (const int rc = upload_lm_slots(c, s)) return rc;
     HIP_TRY(c, hipEventRecord(c->ev_upload, s));
     c->upload_pending = true;
-    HIP_TRY(c, launch_bd_matrix_build_both(c->pool, c->kpool, c->d_slots, c->d_slots + c->max_slots, c->n_slots_last, c->n_kslots_last, s));
-    return CAFE_OK;
+    return launch_call_matrices(c, s);
 }
 
 namespace {
 
 // Host-only rejections; true => the call's value is +inf without touching the device.
 bool rejected(const cafe_ctx* c, const cafe_params* pr, int K) {
-    if (!lambdas_valid(c, pr->lambdas)) return true;                           // base_model.cpp:56 / gamma_core.cpp:125
+    if (!rates_valid(c, pr->lambdas)) return true;                             // base_model.cpp:56 / gamma_core.cpp:125
     if (pr->model != CAFE_MODEL_GAMMA) return false;
     if (pr->alpha < 0) return true;                                            // gamma_core.cpp:128
     // gamma_core.cpp:131-139: longest branch x largest multiplier x largest lambda saturated?
@@ -97,8 +150,9 @@ bool rejected(const cafe_ctx* c, const cafe_params* pr, int K) {
     double lm = *std::max_element(pr->multipliers, pr->multipliers + K);
     double ll = *std::max_element(pr->lambdas, pr->lambdas + c->n_lambdas);
     double lambda = lm * ll;
-    double alpha = lambda * longest / (1 + lambda * longest);                  // matrix_cache.cpp:115
-    return (1 - 2 * alpha) < 0;
+    // matrix_cache.cpp:115; with death rates: coeff = 1 - alpha - beta of that branch under the largest of either rate
+    const double mu = c->mus.empty() ? lambda : lm * *std::max_element(c->mus.begin(), c->mus.end());
+    return bd_rates(lambda, mu, longest).coeff < 0;
 }
 
 // Row-tile height of one K2 launch (a group of ops) from the (previous call's) non-zero extents of its matrices: a tile runs
@@ -249,8 +303,9 @@ int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool 
         c->panels_dirty = false;
     }
     HIP_TRY(c, hipMemcpyAsync(c->d_params, c->h_stage, c->params_bytes, hipMemcpyHostToDevice, s));
+    if (const int rc = upload_lm_slots(c, s)) return rc;
     if (events) HIP_TRY(c, hipEventRecord(c->ev[0], s));
-    HIP_TRY(c, launch_bd_matrix_build_both(c->pool, c->kpool, c->d_slots, c->d_slots + c->max_slots, c->n_slots_last, c->n_kslots_last, s));
+    if (const int rc = launch_call_matrices(c, s)) return rc;
     if (events) HIP_TRY(c, hipEventRecord(c->ev[1], s));
     if (c->debug_fail_in > 0 && --c->debug_fail_in == 0) {                     // test hook: a device error in the middle of a call
         set_err(c, "injected failure (cafe_debug_fail_next)");
@@ -393,7 +448,7 @@ int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bo
     c->model_last = rootmax ? CAFE_MODEL_BASE : pr->model;
     c->rootmax_last = rootmax;
 
-    c->last_rejected = rootmax ? !lambdas_valid(c, pr->lambdas) : rejected(c, pr, K);
+    c->last_rejected = rootmax ? !rates_valid(c, pr->lambdas) : rejected(c, pr, K);
     if (c->last_rejected) {
         double* hr = reinterpret_cast<double*>(c->h_stage);
         hr[0] = 0.0; hr[1] = 1.0;
@@ -426,7 +481,8 @@ int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bo
         const int rc = record_call(c, c->desc, K, gamma, rootmax, use_err, d_out, s, c->profile != 0, false);
         if (rc != CAFE_OK) return rc;
     } else {
-        const int key = (rootmax ? 2 : (gamma ? 1 : 0)) + 4 * K;
+        // (a graph holds the K1 kernels of the mode it was captured in: one per mode)
+        const int key = (rootmax ? 2 : (gamma ? 1 : 0)) + 4 * K + (c->mus.empty() ? 0 : 4 * (kMaxCategories + 1));
         cafe_ctx::CallGraph& cg = c->graphs[key];
         auto drop = [&]() { hipFree(cg.desc.d_gemm_ops); hipFree(cg.desc.d_plan_desc); hipFree(cg.desc.d_plan); c->graphs.erase(key); };
         if (!cg.exec) {
@@ -600,7 +656,7 @@ int cafe_root_max(cafe_ctx* ctx, const cafe_params* params, double* out) {
     ctx->upload_pending = false;
     collect_stats(ctx);
     if (ctx->last_rejected) {            // an invalid lambda has no matrices: the reference would throw (matrix_cache.cpp:90)
-        set_err(ctx, "cafe_root_max: invalid lambda");
+        set_err(ctx, "cafe_root_max: invalid lambda or death rate");
         return CAFE_ERR_ARGUMENT;
     }
     std::vector<double> tmp((size_t)ctx->F_uniq);
@@ -612,6 +668,17 @@ int cafe_root_max(cafe_ctx* ctx, const cafe_params* params, double* out) {
 int cafe_set_profiling(cafe_ctx* ctx, int on) {
     if (!ctx) return CAFE_ERR_ARGUMENT;
     ctx->profile = on ? 1 : 0;
+    return CAFE_OK;
+}
+
+int cafe_set_death_rates(cafe_ctx* ctx, const double* mus) {
+    return guarded(ctx, "cafe_set_death_rates", [&] { return set_death_rates_impl(ctx, mus); });
+}
+
+int cafe_bd_rates(double lambda, double mu, double t, double out[3]) {
+    if (!out) return CAFE_ERR_ARGUMENT;
+    const SlotParamLM sp = slot_param_lm(quantize_lambda(lambda), quantize_lambda(mu), quantize_time(t));
+    out[0] = sp.alpha; out[1] = sp.beta; out[2] = sp.zero;
     return CAFE_OK;
 }
 

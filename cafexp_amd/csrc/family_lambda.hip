@@ -200,6 +200,7 @@ int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const i
     if (!pr || !pr->prior) { set_err(c, "cafe_score_per_family: params with a prior are required"); return CAFE_ERR_ARGUMENT; }
     if (pr->model != CAFE_MODEL_BASE) { set_err(c, "cafe_score_per_family: base model only"); return CAFE_ERR_ARGUMENT; }
     if (c->comm) { set_err(c, "cafe_score_per_family: not valid on a context with a communicator attached"); return CAFE_ERR_STATE; }
+    if (!c->mus.empty()) { set_err(c, "cafe_score_per_family: not valid while death rates are set (cafe_set_death_rates)"); return CAFE_ERR_STATE; }
     if (n < 0 || (n > 0 && (!family || !lambdas || !family_lnl))) { set_err(c, "cafe_score_per_family: family, lambdas and family_lnl are required"); return CAFE_ERR_ARGUMENT; }
     if ((c->n_dev > 0) != (pr->error_model != nullptr)) {
         set_err(c, "cafe_score_per_family: error model %s but the problem was created with n_deviations=%d", pr->error_model ? "given" : "missing", c->n_dev);

@@ -390,7 +390,7 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
         set_err(c, "cafe_marginal_reconstruct: gamma model needs 1..%d categories with multipliers and cat_probs", c->Kmax);
         return CAFE_ERR_ARGUMENT;
     }
-    if (!lambdas_valid(c, pr->lambdas)) { set_err(c, "cafe_marginal_reconstruct: invalid lambda"); return CAFE_ERR_ARGUMENT; }
+    if (!rates_valid(c, pr->lambdas)) { set_err(c, "cafe_marginal_reconstruct: invalid lambda or death rate"); return CAFE_ERR_ARGUMENT; }
     if (pr->error_model && c->n_dev < 1) { set_err(c, "cafe_marginal_reconstruct: the context was created without an error model"); return CAFE_ERR_ARGUMENT; }
     hipStream_t s = nullptr;
     if (const int rc = begin_matrix_call(c, pr->lambdas, gamma ? pr->multipliers : nullptr, K, &s)) return rc;

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <map>
+#include <tuple>
 #include <vector>
 
 #include "cafe_call.h"
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(256) void tree_pvalue_kernel(const double* __restri
 int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t seed, double* pvalues) {
     if (!pr || !pr->lambdas || !pvalues) { set_err(c, "cafe_pvalues: lambdas and pvalues are required"); return CAFE_ERR_ARGUMENT; }
     if (n_sim < 1 || n_sim > 2048) { set_err(c, "cafe_pvalues: 1..2048 simulations per root size"); return CAFE_ERR_ARGUMENT; }
-    if (!lambdas_valid(c, pr->lambdas)) { set_err(c, "cafe_pvalues: invalid lambda"); return CAFE_ERR_ARGUMENT; }
+    if (!rates_valid(c, pr->lambdas)) { set_err(c, "cafe_pvalues: invalid lambda or death rate"); return CAFE_ERR_ARGUMENT; }
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int n = c->n_nodes, N = c->N, M = c->M, R = c->R;
@@ -128,25 +129,32 @@ int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t see
 
     // ---- row-major matrix + CDF of EVERY branch (the scorer keeps interior branches k-major only)
     MatrixPool sp = row_major_pool(N);
-    std::map<std::pair<long, long>, int> key_slot;
+    // (with death rates set, cafe_set_death_rates: the two-rate parameters, built by the two-rate kernel; one or the other is filled)
+    const bool lm = !c->mus.empty();
+    std::map<std::tuple<long, long, long>, int> key_slot;
     std::vector<SlotParam> slots;
+    std::vector<SlotParamLM> slots_lm;
     std::vector<int32_t> h_slot(n, 0), h_parent(n), h_leaf(n), h_order;
     for (int v = 0; v < n; ++v) {
         h_parent[v] = c->parent[v];
         h_leaf[v] = c->leaf_taxon[v];
         if (v == c->root) continue;
-        const long lq = quantize_lambda(pr->lambdas[c->lam_idx[v]]), tq = quantize_time(c->blen[v]);
-        auto it = key_slot.find({tq, lq});
+        long lq, mq;
+        quantized_rates(c, pr->lambdas, c->lam_idx[v], 1.0, &lq, &mq);
+        const long tq = quantize_time(c->blen[v]);
+        auto it = key_slot.find({tq, lq, mq});
         if (it == key_slot.end()) {
-            it = key_slot.emplace(std::make_pair(tq, lq), (int)slots.size()).first;
-            slots.push_back(slot_param(lq, tq));
+            it = key_slot.emplace(std::make_tuple(tq, lq, mq), (int)key_slot.size()).first;
+            if (lm) slots_lm.push_back(slot_param_lm(lq, mq, tq)); else slots.push_back(slot_param(lq, tq));
         }
         h_slot[v] = it->second;
     }
     for (int v = n - 1; v >= 0; --v) h_order.push_back(v);          // parents have larger indices: descending = parents first
     DevBuf d_pool, d_sp, d_meta, d_sizes, d_cond, d_pv;
-    const size_t pool_bytes = sizeof(double) * (size_t)sp.stride * slots.size();
-    if (hipMalloc(&d_pool.p, pool_bytes) != hipSuccess || hipMalloc(&d_sp.p, sizeof(SlotParam) * slots.size()) != hipSuccess ||
+    const size_t n_slots = key_slot.size();
+    const size_t sp_bytes = lm ? sizeof(SlotParamLM) * n_slots : sizeof(SlotParam) * n_slots;
+    const size_t pool_bytes = sizeof(double) * (size_t)sp.stride * n_slots;
+    if (hipMalloc(&d_pool.p, pool_bytes) != hipSuccess || hipMalloc(&d_sp.p, sp_bytes) != hipSuccess ||
         hipMalloc(&d_meta.p, sizeof(int32_t) * 4 * n) != hipSuccess || hipMalloc(&d_cond.p, sizeof(double) * Fs) != hipSuccess ||
         hipMalloc(&d_pv.p, sizeof(double) * c->F_uniq) != hipSuccess) {
         (void)hipGetLastError();
@@ -155,20 +163,22 @@ int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t see
     }
     sp.base = static_cast<double*>(d_pool.p);
     HIP_TRY(c, hipMemsetAsync(d_pool.p, 0, pool_bytes, s));
-    HIP_TRY(c, hipMemcpyAsync(d_sp.p, slots.data(), sizeof(SlotParam) * slots.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d_sp.p, lm ? (const void*)slots_lm.data() : (const void*)slots.data(), sp_bytes, hipMemcpyHostToDevice, s));
     int32_t* meta = static_cast<int32_t*>(d_meta.p);
     HIP_TRY(c, hipMemcpyAsync(meta, h_order.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(meta + n, h_parent.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(meta + 2 * n, h_slot.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(meta + 3 * n, h_leaf.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, launch_bd_matrix_build(sp, static_cast<const SlotParam*>(d_sp.p), (int)slots.size(), s));
-    HIP_TRY(c, launch_row_cdf(sp.base, sp.stride, sp.ld, (int)slots.size(), N, M, s));
+    if (lm) HIP_TRY(c, launch_bd_lm_build(sp, static_cast<const SlotParamLM*>(d_sp.p), (int)n_slots, s));
+    else HIP_TRY(c, launch_bd_matrix_build(sp, static_cast<const SlotParam*>(d_sp.p), (int)n_slots, s));
+    HIP_TRY(c, launch_row_cdf(sp.base, sp.stride, sp.ld, (int)n_slots, N, M, s));
     HIP_TRY(c, hipStreamSynchronize(s));                            // the host vectors above go out of use
 
     // ---- simulate into a child context over the same tree, prune, keep the root maxima
     cafe_ctx* child = create_child_for_device_counts(c, Fs);
     if (!child) { set_err(c, "cafe_pvalues: cannot create the context of %lld simulated families", (long long)Fs); return CAFE_ERR_MEMORY; }
     struct ChildGuard { cafe_ctx* p; ~ChildGuard() { destroy_child(p); } } guard{child};
+    if (lm) { const int rc = set_death_rates_impl(child, c->mus.data()); if (rc != CAFE_OK) { set_err(c, "cafe_pvalues: %s", child->err.c_str()); return rc; } }
     if (hipMalloc(&d_sizes.p, sizeof(int32_t) * (size_t)n * Fs) != hipSuccess) {
         (void)hipGetLastError();
         set_err(c, "cafe_pvalues: cannot allocate the simulation scratch");

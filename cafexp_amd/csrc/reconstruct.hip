@@ -272,7 +272,7 @@ int reconstruct_impl(cafe_ctx* c, const cafe_params* pr, const float* root_prior
     const bool gamma = pr->model == CAFE_MODEL_GAMMA;
     const int K = gamma ? pr->n_categories : 1;
     if (gamma && (K < 1 || K > c->Kmax || !pr->multipliers)) { set_err(c, "cafe_reconstruct: gamma model needs 1..%d categories with multipliers", c->Kmax); return CAFE_ERR_ARGUMENT; }
-    if (!lambdas_valid(c, pr->lambdas)) { set_err(c, "cafe_reconstruct: invalid lambda"); return CAFE_ERR_ARGUMENT; }
+    if (!rates_valid(c, pr->lambdas)) { set_err(c, "cafe_reconstruct: invalid lambda or death rate"); return CAFE_ERR_ARGUMENT; }
     hipStream_t s = nullptr;
     if (const int rc = begin_matrix_call(c, pr->lambdas, gamma ? pr->multipliers : nullptr, K, &s)) return rc;
 
@@ -364,7 +364,7 @@ int reconstruct_impl(cafe_ctx* c, const cafe_params* pr, const float* root_prior
 
 int branch_probabilities_impl(cafe_ctx* c, const cafe_params* pr, const int32_t* sizes, double* out) {
     if (!pr || !pr->lambdas || !sizes || !out) { set_err(c, "cafe_branch_probabilities: lambdas, sizes and out are required"); return CAFE_ERR_ARGUMENT; }
-    if (!lambdas_valid(c, pr->lambdas)) { set_err(c, "cafe_branch_probabilities: invalid lambda"); return CAFE_ERR_ARGUMENT; }
+    if (!rates_valid(c, pr->lambdas)) { set_err(c, "cafe_branch_probabilities: invalid lambda or death rate"); return CAFE_ERR_ARGUMENT; }
     const int n = c->n_nodes;
     const int64_t F = c->F_all;
     for (int64_t i = 0; i < F * n; ++i)

@@ -230,7 +230,12 @@ protected:
     error_model* _p_error_model;
     std::vector<family_info_stash> results;
     event_monitor _monitor;
+    // Separate birth and death rates: one mu per lambda (index order); empty = the reference's model, lambda = mu
+    std::vector<double> _death_rates;
 public:
+    void set_death_rates(const std::vector<double>& mus) { _death_rates = mus; }
+    const std::vector<double>& death_rates() const { return _death_rates; }
+    std::string death_rates_to_string() const;                       // formatted like lambda::to_string
     model(lambda* l, const clade* tree, const std::vector<gene_family>* fams, int max_family_size, int max_root_family_size, error_model* em)
         : _p_lambda(l), _p_tree(tree), _p_gene_families(fams), _max_family_size(max_family_size), _max_root_family_size(max_root_family_size), _p_error_model(em) {}
     virtual ~model() {}
@@ -282,6 +287,8 @@ protected:
     cafe_sharded* _sharded = nullptr;
     int _sharded_categories = 0, _sharded_lambda_sig = -1;
     std::vector<const clade*> _order;                                // post-order used to flatten
+    // (both leave the model's death rates set on what they return -- cafe_set_death_rates, NULL without any -- so every
+    // call on _ctx / _sharded runs under the model's current pair)
     void ensure_context(int max_categories);                         // single-device context (_ctx)
     void ensure_scorer(int max_categories);                          // what infer_family_likelihoods calls: _sharded or _ctx
     int score_call(const cafe_params* pr, double* score);
@@ -517,6 +524,21 @@ public:
     void report_precalculation() override;
     void finalize(double* results) override;
 };
+// Death rates searched with whatever `inner` searches: the vector is inner's followed by one mu per lambda ([lambda..., mu...]
+// for the base model).  mu starts at the lambda guess (the nested model's point); a negative mu scores +inf like a negative
+// lambda (the library's rule, cafe_set_death_rates).  `inner` must lead with the lambdas (every scorer above but gamma_optimizer).
+class lambda_mu_optimizer : public inference_optimizer_scorer {
+    std::unique_ptr<inference_optimizer_scorer> _inner;
+    size_t _n_inner = 0;
+    void apply(const double* values) { _p_model->set_death_rates(std::vector<double>(values + _n_inner, values + _n_inner + _p_lambda->count())); }
+public:
+    lambda_mu_optimizer(inference_optimizer_scorer* inner, lambda* l, model* m, root_equilibrium_distribution* d, const std::map<int, int>& rootdist)
+        : inference_optimizer_scorer(l, m, d, rootdist), _inner(inner) {}
+    std::vector<double> initial_guesses() override;
+    void prepare_calculation(const double* values) override { _inner->prepare_calculation(values); apply(values); }
+    void report_precalculation() override;
+    void finalize(double* results) override { _inner->finalize(results); apply(results); }
+};
 
 // ---------------------------------------------------------------- inputs (src/io.cpp, src/user_data.cpp)
 struct user_data {
@@ -545,7 +567,8 @@ struct pvalue_work {
 double pvalue(double v, const std::vector<double>& conddist);                                        // probability.cpp:379
 std::vector<double> compute_pvalues(const clade* p_tree, const std::vector<gene_family>& families, const lambda* p_lambda,
                                     int number_of_simulations, int max_family_size, int max_root_family_size, int device = 0,
-                                    pvalue_work* keep = nullptr);                                     // probability.cpp:418
+                                    pvalue_work* keep = nullptr,                                      // probability.cpp:418
+                                    const std::vector<double>* death_rates = nullptr);               // one mu per lambda: both prunes and the draws under the pair
 
 // ---------------------------------------------------------------- simulation (the reference's -s; src/simulator.cpp)
 const size_t LAMBDA_PERTURBATION_STEP_SIZE = 50;                    // families per simulation lambda (configure.ac default)

@@ -80,9 +80,16 @@ static std::vector<int32_t> flatten_counts(const clade* tree, const std::vector<
     return counts;
 }
 
+// the model's death rates on a context (none: lambda = mu)
+static void apply_death_rates(cafe_ctx* ctx, const std::vector<double>& mus, int n_lambdas) {
+    if (!mus.empty() && (int)mus.size() != n_lambdas) throw std::runtime_error("hip model: one death rate per lambda is required");
+    if (cafe_set_death_rates(ctx, mus.empty() ? nullptr : mus.data()) != CAFE_OK)
+        throw std::runtime_error(std::string("cafe_set_death_rates: ") + cafe_last_error(ctx));
+}
+
 void hip_model_base::ensure_context(int max_categories) {
     const int sig = _p_lambda->count() * 2 + (dynamic_cast<const multiple_lambda*>(_p_lambda) ? 1 : 0);
-    if (_ctx && max_categories <= _ctx_categories && sig == _ctx_lambda_sig) return;
+    if (_ctx && max_categories <= _ctx_categories && sig == _ctx_lambda_sig) { apply_death_rates(_ctx, _death_rates, _p_lambda->count()); return; }
     _ctx_lambda_sig = sig;
     if (_ctx) { cafe_destroy(_ctx); _ctx = nullptr; }
     if (!_p_tree || !_p_gene_families || _p_gene_families->empty())
@@ -91,6 +98,7 @@ void hip_model_base::ensure_context(int max_categories) {
     _ctx = create_device_context(_p_lambda, _order, counts.data(), (int64_t)_p_gene_families->size(), _max_family_size, _max_root_family_size,
                                  max_categories, _p_error_model ? (int)_p_error_model->n_deviations() : 0, _device, _workspace_limit);
     _ctx_categories = max_categories;
+    apply_death_rates(_ctx, _death_rates, _p_lambda->count());
 }
 
 void hip_model_base::ensure_scorer(int max_categories) {
@@ -99,7 +107,8 @@ void hip_model_base::ensure_scorer(int max_categories) {
     if (_devices.size() <= 1 && std::getenv("CAFE_FORCE_SHARDED")) { if (_devices.empty()) _devices.push_back(_device); }
     else if (_devices.size() <= 1) { ensure_context(max_categories); return; }
     const int sig = _p_lambda->count() * 2 + (dynamic_cast<const multiple_lambda*>(_p_lambda) ? 1 : 0);
-    if (_sharded && max_categories <= _sharded_categories && sig == _sharded_lambda_sig) return;
+    auto apply_to_shards = [this] { for (int32_t r = 0; r < cafe_sharded_size(_sharded); ++r) apply_death_rates(cafe_sharded_context(_sharded, r), _death_rates, _p_lambda->count()); };
+    if (_sharded && max_categories <= _sharded_categories && sig == _sharded_lambda_sig) { apply_to_shards(); return; }
     _sharded_lambda_sig = sig;
     if (_sharded) { cafe_sharded_destroy(_sharded); _sharded = nullptr; }
     if (!_p_tree || !_p_gene_families || _p_gene_families->empty())
@@ -108,6 +117,7 @@ void hip_model_base::ensure_scorer(int max_categories) {
     create_device_objects(_p_lambda, _order, counts.data(), (int64_t)_p_gene_families->size(), _max_family_size, _max_root_family_size, max_categories,
                           _p_error_model ? (int)_p_error_model->n_deviations() : 0, _device, &_devices, nullptr, &_sharded);
     _sharded_categories = max_categories;
+    apply_to_shards();
 }
 
 int hip_model_base::score_call(const cafe_params* pr, double* score) {

@@ -20,6 +20,8 @@ using namespace cafe;
 static void usage() {
     std::fprintf(stderr,
         "usage: cafexp_hip -t TREE -i FAMILIES [-l LAMBDA | -m L1,L2,.. -y LAMBDA_TREE | -y LAMBDA_TREE] [-k K] [-a ALPHA]\n"
+        "                  [--mu M1[,M2,..] | --estimate-mu]   separate death rates, one per lambda: fixed, or searched together with lambda\n"
+        "                  (start mu = lambda); every call after the search runs under the pair, <Model>_results.txt gains a Mu: line\n"
         "                  [-e [ERRMODEL]] [-p [POISSON_LAMBDA]] [-f ROOTDIST] [-z] [-s SEED] [-I MAXITER] [-d DEVICE | --gpus N] [--reps N] [--family-out FILE] [-o OUTDIR] [--limit N]\n"
         "                  [--pvalues NSIM [--pvalues-device] [--pvalues-out FILE] [--pvalues-cond FILE:K]] [--sizes M,R]\n"
         "                  [--reconstruct [-P PVALUE]]   (with -o: the reports of reconstruction::write_results)\n"
@@ -139,6 +141,8 @@ int main(int argc, char** argv) {
     int k = 1, device = 0, max_iter = 300, reps = 1, n_gpus = 1;
     bool use_err = false, use_poisson = false, keep_all = false;
     bool per_family = false, gpus_given = false, alpha_given = false;      // -b: one lambda (vector) per family
+    std::string mu_list;                                         // --mu: fixed death rates, one per lambda
+    bool estimate_mu = false;                                    // --estimate-mu: death rates searched with the lambdas
     unsigned seed = 0;
     bool have_seed = false;
     for (int i = 1; i < argc; ++i) {
@@ -153,6 +157,8 @@ int main(int argc, char** argv) {
         else if (a == "-k") k = std::stoi(next());
         else if (a == "-a") { fixed_alpha = std::stod(next()); alpha_given = true; }
         else if (a == "-b") per_family = true;
+        else if (a == "--mu") mu_list = next();
+        else if (a == "--estimate-mu") estimate_mu = true;
         else if (a == "-e") { use_err = true; err_path = optional(); }
         else if (a == "-p") { use_poisson = true; std::string v = optional(); poisson = v.empty() ? 0 : std::stod(v); }
         else if (a == "-f") rootdist_path = next();
@@ -189,6 +195,13 @@ int main(int argc, char** argv) {
                              simulate_n, simulate_on_device, have_seed ? seed : randomizer_engine(), device, sim_workspace, out_dir);
     }
     if (tree_path.empty() || fam_path.empty()) { usage(); return 2; }
+    if (estimate_mu || !mu_list.empty()) {
+        const char* why = nullptr;
+        if (estimate_mu && !mu_list.empty()) why = "--mu fixes the death rates and --estimate-mu searches them: give one of the two";
+        else if (per_family) why = "-b runs the lambda = mu kernel: --mu / --estimate-mu are not supported with it";
+        else if (estimate_mu && (fixed_lambda > 0 || !multi.empty())) why = "--estimate-mu searches lambda and mu together: -l / -m are not supported with it";
+        if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
+    }
     if (do_marginal) {
         const char* why = nullptr;
         if (gpus_given) why = "--reconstruct-marginal runs on one GPU: --gpus is not supported with it";
@@ -268,6 +281,20 @@ int main(int argc, char** argv) {
             mdl.reset(new hip_base_model(start_lambda, d.p_tree.get(), &d.gene_families, d.max_family_size, d.max_root_family_size, em));
         }
         mdl->set_device(device);
+        if (!mu_list.empty()) {                                  // fixed death rates: one per lambda of the -y tree (one without)
+            std::vector<double> mus;
+            std::stringstream ss(mu_list);
+            std::string tok;
+            while (std::getline(ss, tok, ',')) mus.push_back(std::stod(tok));
+            size_t n_lambdas = 1;
+            if (d.p_lambda_tree) {
+                std::set<int> uniq;
+                d.p_lambda_tree->apply_prefix_order([&](const clade* c) { uniq.insert(c->get_lambda_index()); });
+                n_lambdas = uniq.size();
+            }
+            if (mus.size() != n_lambdas) throw std::runtime_error("--mu needs one death rate per lambda (" + std::to_string(n_lambdas) + ")");
+            mdl->set_death_rates(mus);
+        }
         if (per_family) {                                        // estimator::estimate_lambda_per_family (execute.cpp:104-128, :136-141)
             hip_base_model* base = static_cast<hip_base_model*>(mdl.get());      // -k / -a were refused above
             base->set_workspace_limit(sim_workspace);
@@ -300,6 +327,8 @@ int main(int argc, char** argv) {
         }
 
         std::unique_ptr<inference_optimizer_scorer> scorer(mdl->get_lambda_optimizer(d));
+        if (estimate_mu)                                         // lambda is searched (-l / -m were refused), so the scorer leads with the lambdas
+            scorer.reset(new lambda_mu_optimizer(scorer.release(), mdl->get_lambda(), mdl.get(), d.p_prior.get(), d.rootdist));
         std::unique_ptr<lambda> owned_lambda;
         optimizer_result opt;
         double search_s = 0;
@@ -348,7 +377,7 @@ int main(int argc, char** argv) {
                 pvalues = mdl->device_pvalues(pvalue_sims, have_seed ? seed : 1u);
             else
                 pvalues = compute_pvalues(d.p_tree.get(), d.gene_families, mdl->get_lambda(), pvalue_sims, d.max_family_size, d.max_root_family_size,
-                                          device, &work);
+                                          device, &work, &mdl->death_rates());
             pvalue_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             if (!pvalues_out.empty()) {
                 std::ofstream f(pvalues_out);
@@ -403,6 +432,11 @@ int main(int argc, char** argv) {
         auto lv = mdl->get_lambda()->values();
         for (size_t i = 0; i < lv.size(); ++i) std::printf("%s%.17g", i ? ", " : "", lv[i]);
         std::printf("]");
+        if (!mdl->death_rates().empty()) {
+            std::printf(", \"mu\": [");
+            for (size_t i = 0; i < mdl->death_rates().size(); ++i) std::printf("%s%.17g", i ? ", " : "", mdl->death_rates()[i]);
+            std::printf("]");
+        }
         if (auto g = dynamic_cast<hip_gamma_model*>(mdl.get())) {
             std::printf(", "); print_num("alpha", g->get_alpha(), false);
             std::printf(", \"multipliers\": [");

@@ -41,7 +41,12 @@ bool is_saturated(double branch_length, double lambda) {          // matrix_cach
 }  // namespace
 
 std::vector<double> compute_pvalues(const clade* p_tree, const std::vector<gene_family>& families, const lambda* p_lambda,
-                                    int number_of_simulations, int max_family_size, int max_root_family_size, int device, pvalue_work* keep) {
+                                    int number_of_simulations, int max_family_size, int max_root_family_size, int device, pvalue_work* keep,
+                                    const std::vector<double>* death_rates) {
+    const double* mus = death_rates && !death_rates->empty() ? death_rates->data() : nullptr;
+    auto with_death_rates = [mus](cafe_ctx* ctx) {
+        if (mus && cafe_set_death_rates(ctx, mus) != CAFE_OK) throw std::runtime_error(std::string("cafe_set_death_rates: ") + cafe_last_error(ctx));
+    };
     const std::vector<const clade*> order = p_tree->post_order();
     const int n = (int)order.size();
     std::map<const clade*, int> index;
@@ -58,6 +63,7 @@ std::vector<double> compute_pvalues(const clade* p_tree, const std::vector<gene_
         for (int t = 0; t < T; ++t) counts[(size_t)f * T + t] = families[f].get_species_size(leaves[t]->get_taxon_name());
     ctx_holder obs;
     obs.ctx = create_device_context(p_lambda, order, counts.data(), F, max_family_size, max_root_family_size, 1, 0, device);
+    with_death_rates(obs.ctx);
     const std::vector<double> observed = root_max(obs.ctx, p_lambda, (size_t)F);
 
     // ---- the matrices those prunes used, row-major on the host, for the draws
@@ -88,7 +94,14 @@ std::vector<double> compute_pvalues(const clade* p_tree, const std::vector<gene_
                 int csize = 0;
                 if (parent_family_size > 0) {
                     const double lam = p_lambda->get_value_for_clade(c), t = c->get_branch_length();
-                    if (is_saturated(t, lam)) {                 // the reference draws and then overwrites the value (:333-337)
+                    bool saturated = is_saturated(t, lam);
+                    if (mus) {                                   // the same rule on coeff = 1 - alpha - beta of the pair (cafe_bd_rates)
+                        const multiple_lambda* ml = dynamic_cast<const multiple_lambda*>(p_lambda);
+                        double r[3];
+                        cafe_bd_rates(lam, mus[ml ? ml->index_of(c) : 0], t, r);
+                        saturated = (1 - r[0] - r[1]) < 0;
+                    }
+                    if (saturated) {                 // the reference draws and then overwrites the value (:333-337)
                         std::uniform_int_distribution<int> distribution(0, max_family_size - 1);
                         csize = distribution(randomizer_engine);
                     }
@@ -109,6 +122,7 @@ std::vector<double> compute_pvalues(const clade* p_tree, const std::vector<gene_
     {
         ctx_holder sim;
         sim.ctx = create_device_context(p_lambda, order, sim_counts.data(), (int64_t)R * nsim, max_family_size, max_root_family_size, 1, 0, device);
+        with_death_rates(sim.ctx);
         const std::vector<double> lik = root_max(sim.ctx, p_lambda, (size_t)R * nsim);
         for (int i = 0; i < R; ++i) {
             cond[i].assign(lik.begin() + (size_t)i * nsim, lik.begin() + (size_t)(i + 1) * nsim);

@@ -88,6 +88,18 @@ void gamma_lambda_optimizer::finalize(double* results) {
     _gamma_optimizer.finalize(results + _p_lambda->count());
 }
 
+std::vector<double> lambda_mu_optimizer::initial_guesses() {
+    std::vector<double> values = _inner->initial_guesses();
+    _n_inner = values.size();
+    values.insert(values.end(), values.begin(), values.begin() + _p_lambda->count());
+    return values;
+}
+
+void lambda_mu_optimizer::report_precalculation() {
+    _inner->report_precalculation();
+    std::cout << "Mu: " << _p_model->death_rates_to_string() << std::endl;
+}
+
 // ---------------------------------------------------------------- empirical Poisson prior (src/poisson.cpp)
 static double poisspdf(int x, double lambda) { return std::exp(x * std::log(lambda) - std::lgamma(x + 1) - lambda); }
 

@@ -273,6 +273,32 @@ int cafe_simulate(const cafe_sim_problem* problem, uint64_t seed, int32_t* leaf_
 int cafe_score_per_family(cafe_ctx* ctx, const cafe_params* params, int64_t n, const int64_t* family,
                           const double* lambdas, double* family_lnl);
 
+/* Separate birth and death rates.  The reference fits the critical process lambda = mu only; with death rates set a context
+ * scores the linear birth-death process with birth rate lambdas[i] and death rate mus[i] per lineage on the branches of
+ * lambda index i.  mus[n_lambdas] is copied; NULL restores lambda = mu (and the kernels that run then).  While death rates
+ * are set every call that builds transition matrices uses them: cafe_score, cafe_score_partial, cafe_root_max,
+ * cafe_reconstruct, cafe_branch_probabilities, cafe_marginal_reconstruct, cafe_pvalues (its own order-S matrices and its
+ * simulated families' prune included) and with them cafe_get_matrix / cafe_get_extents.  Gamma multipliers scale both rates.
+ * Validity follows the context's rule for lambdas -- one lambda: lambda > 0 and mu >= 0; several: none negative -- and an
+ * invalid mu makes a call's value +inf (or its error) exactly as an invalid lambda does; the gamma model's host rejection
+ * (gamma_core.cpp:131-139) reads coeff = 1 - alpha - beta of the longest branch under the largest of either rate.  With
+ * mus[i] == lambdas[i] every result is bit for bit the unset call's.
+ * cafe_score_per_family returns CAFE_ERR_STATE while death rates are set (its kernel is the lambda = mu row step), and
+ * cafe_simulate, which takes no context, is untouched: it simulates lambda = mu.  Sharded use needs no entry of its own: call
+ * the setter on every cafe_sharded_context(s, r) (or on every rank's context) before the collective call. */
+int cafe_set_death_rates(cafe_ctx* ctx, const double* mus);
+/* What a transition matrix is built from, for the key (lambda, mu, t): lambda and mu quantized like lambda, t like the branch
+ * length (matrix_cache_key, matrix_cache.h:42-61).  out[0] = alpha = P(a lineage is extinct after t), out[1] = beta, the ratio
+ * of the geometric tail p1(k) = (1-alpha)(1-beta) beta^(k-1),
+ *     alpha = mu (E-1) / (lambda E - mu),   beta = lambda (E-1) / (lambda E - mu),   E = exp((lambda - mu) t),
+ * evaluated through expm1 and exp(-|lambda-mu| t) so that both are finite and below 1 for every valid key and tend to
+ * lambda t / (1 + lambda t) as mu -> lambda; equal quantized rates give exactly the bits the lambda = mu kernels use.
+ * out[2] = 1 when the matrix is built with rows s >= 1 all zero: !(coeff > 0 && coeff != 1), coeff = 1 - alpha - beta.  That
+ * is the reference's saturation rule (matrix_cache.cpp:153, probability.cpp:154) carried over so that the model is continuous
+ * at mu = lambda and lambda = mu = 0 stays degenerate -- a convention: the recurrence itself is defined wherever alpha and
+ * beta are below 1.  Pure host code, no device needed. */
+int cafe_bd_rates(double lambda, double mu, double t, double out[3]);
+
 /* Ancestral reconstruction.  Pupko's joint reconstruction as reconstruct_gene_family runs it
  * (gene_family_reconstructor.cpp:13-165; base_model.cpp:145, gamma_core.cpp:301): for every category k (one for
  * the base model; lambda * multipliers[k] for the gamma model) and family f, the reconstructed size of every node
@@ -377,6 +403,9 @@ int cafe_debug_stamps(cafe_ctx* ctx, unsigned long long* out, size_t words);
  * device layout leaf branches use; layout 1: the k-major layout of interior branches (built through the
  * reversibility relation, see bd_matrix.hip), converted back on the host. */
 int cafe_build_matrices(int32_t device, int32_t n, int32_t count, const double* lambdas, const double* ts, int32_t layout, double* out);
+/* the same under separate birth and death rates (lambdas[i], mus[i], ts[i]): the two-rate kernel (bd_matrix_lm.hip) */
+int cafe_build_matrices_lm(int32_t device, int32_t n, int32_t count, const double* lambdas, const double* mus, const double* ts,
+                           int32_t layout, double* out);
 /* back-to-back v_mfma_f64_16x16x4_f64 issue-rate probe: returns achieved TFLOP/s on `device`. */
 int cafe_probe_fp64_mfma(int32_t device, double* tflops);
 

@@ -1,0 +1,57 @@
+"""The two-rate K1 (bd_matrix_lm.hip: separate birth and death rates) keeps every row of its recurrence in registers exactly as
+K1 does, with one more constant live.  The rule tests/test_k1_resources.py pins for bd_matrix.hip, on the new file: cross-compile
+for gfx950 (CPU only), read the compiler's resource remarks -- every width 2 .. 32 in both layouts and in the two-pool launch is
+there, and none uses scratch memory or spills a vector register.  No kernel of the file carries K1's name (that test counts
+them by it)."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "cafexp_amd", "csrc")
+HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+WIDTHS = [2, 4, 6, 8, 10, 12, 14, 16, 20, 24, 28, 32]
+
+
+def _flags():
+    with open(os.path.join(CSRC, "Makefile")) as f:
+        line = next(ln for ln in f if ln.startswith("FLAGS"))
+    return line.split(":=", 1)[1].replace("$(ARCH)", "gfx950").split()
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_every_two_rate_k1_instantiation_runs_without_scratch(tmp_path):
+    r = subprocess.run([HIPCC] + _flags() + ["-Rpass-analysis=kernel-resource-usage", "-c", "bd_matrix_lm.hip", "-o", str(tmp_path / "k1lm.o")],
+                       cwd=CSRC, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    kernels, name = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            kernels[name] = {}
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/lane\])?: (\d+)", line)
+        if m and name:
+            kernels[name][m.group(1).strip()] = int(m.group(2))
+    assert not [k for k in kernels if "bd_matrix_build" in k], sorted(kernels)
+    k1 = {k: v for k, v in kernels.items() if "bd_lm_" in k}
+    for E in WIDTHS:
+        assert "_ZN4cafe17bd_lm_both_kernelILi%dEEEv" % E in "|".join(k1), E
+        for km in (0, 1):
+            assert "_ZN4cafe12bd_lm_kernelILi%dELb%dEEEv" % (E, km) in "|".join(k1), (E, km)
+    assert len(k1) == 3 * len(WIDTHS), sorted(k1)
+    for k, res in k1.items():
+        assert res["ScratchSize"] == 0, (k, res)
+        assert res["VGPRs Spill"] == 0, (k, res)
+
+
+def test_makefile_builds_and_checks_the_two_rate_kernel():
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    src = next(ln for ln in mk.splitlines() if ln.startswith("SRC"))
+    assert "bd_matrix_lm.hip" in src.split()
+    check = mk[mk.index("\ncheck:"):]
+    assert "-c bd_matrix_lm.hip" in check
