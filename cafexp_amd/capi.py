@@ -88,7 +88,7 @@ EXPORTS = [
     "cafe_sharded_size", "cafe_sharded_context", "cafe_set_graphs", "cafe_executed_flops", "cafe_debug_tile_range_flops", "cafe_get_extents", "cafe_debug_launch_flops", "cafe_debug_launch_ms", "cafe_debug_plan_check",
     "cafe_debug_fail_next", "cafe_debug_column_extents", "cafe_debug_leaf_transposes", "cafe_simulate",
     "cafe_score_per_family", "cafe_marginal_reconstruct", "cafe_debug_marginal_gemm",
-    "cafe_set_death_rates", "cafe_bd_rates", "cafe_build_matrices_lm",
+    "cafe_set_death_rates", "cafe_bd_rates", "cafe_build_matrices_lm", "cafe_score_per_family_lm", "cafe_simulate_lm",
 ]
 CAFE_COMM_ID_BYTES = 128
 
@@ -138,6 +138,8 @@ def load():
     L.cafe_root_max.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p]
     L.cafe_score_per_family.restype = C.c_int
     L.cafe_score_per_family.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p]
+    L.cafe_score_per_family_lm.restype = C.c_int
+    L.cafe_score_per_family_lm.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p, _f64p]
     L.cafe_marginal_reconstruct.restype = C.c_int
     L.cafe_marginal_reconstruct.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_double, C.POINTER(CafeMarginalOut)]
     L.cafe_debug_marginal_gemm.restype = C.c_int
@@ -202,6 +204,8 @@ def load():
     L.cafe_debug_fail_next.argtypes = [C.c_void_p, C.c_int]
     L.cafe_simulate.restype = C.c_int
     L.cafe_simulate.argtypes = [C.POINTER(CafeSimProblem), C.c_uint64, _i32p, _i32p, C.c_char_p, C.c_size_t]
+    L.cafe_simulate_lm.restype = C.c_int
+    L.cafe_simulate_lm.argtypes = [C.POINTER(CafeSimProblem), _f64p, C.c_uint64, _i32p, _i32p, C.c_char_p, C.c_size_t]
     _lib = L
     return L
 
@@ -381,6 +385,21 @@ class Context:
         cp, keep = self._params(pr)
         out = np.empty(len(fam))
         self._check(self._lib.cafe_score_per_family(self._h, C.byref(cp), len(fam), _p(fam, _i64p), _p(lam, _f64p), _p(out, _f64p)))
+        return out
+
+    def score_per_family_lm(self, pr: Params, family, lambdas, mus) -> np.ndarray:
+        """cafe_score_per_family_lm: lnL of every listed family under ITS OWN birth and death rates (lambdas and mus
+        [n][n_lambdas]; 1-d arrays are one rate per family).  The context's death rates are not read.  Otherwise
+        score_per_family."""
+        fam = np.ascontiguousarray(family, dtype=np.int64).reshape(-1)
+        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(len(fam), -1)
+        mu = np.ascontiguousarray(mus, dtype=np.float64).reshape(len(fam), -1)
+        if lam.shape[1] != self.problem.n_lambdas or mu.shape != lam.shape:
+            raise ValueError("lambdas and mus must be [%d][%d]" % (len(fam), self.problem.n_lambdas))
+        cp, keep = self._params(pr)
+        out = np.empty(len(fam))
+        self._check(self._lib.cafe_score_per_family_lm(self._h, C.byref(cp), len(fam), _p(fam, _i64p), _p(lam, _f64p), _p(mu, _f64p),
+                                                       _p(out, _f64p)))
         return out
 
     def marginal_reconstruct(self, pr: Params, level: float = 0.95, alpha: float = 1.0) -> dict:
@@ -680,13 +699,10 @@ def build_matrices_lm(n: int, lambdas, mus, ts, device: int = 0, layout: int = 0
     return out
 
 
-def simulate(pb: Problem, lambdas, max_family_size: int, root_size, seed: int, chunk_size: int = 50, chunk_multiplier=None,
-             error_model=None, error_model_max_size: int = 0, device: int = 0, workspace_limit: int = 0, node_sizes: bool = True):
-    """cafe_simulate: gene families simulated down pb's tree (its parent / branch_length / lambda_index / leaf_taxon; its
-    families are not read) from root_size[F], every child size drawn from the order-S transition matrices of the chunk's
-    lambdas * chunk_multiplier[f // chunk_size].  error_model: [S][n_deviations] table of get_probs(c), with
-    error_model_max_size = error_model::get_max_family_size().  Returns (leaf_counts int32 [F][n_taxa], node_sizes int32
-    [F][n_nodes] or None)."""
+def _simulate(call, pb: Problem, lambdas, max_family_size: int, root_size, seed: int, chunk_size: int = 50, chunk_multiplier=None,
+              error_model=None, error_model_max_size: int = 0, device: int = 0, workspace_limit: int = 0, node_sizes: bool = True):
+    """What simulate and simulate_lm share: the cafe_sim_problem block and the outputs.  call(problem, seed, leaf, nodes, err,
+    errlen) is the C entry, with whatever else it takes already bound."""
     keep = []
 
     def k(a, dt):
@@ -728,10 +744,32 @@ def simulate(pb: Problem, lambdas, max_family_size: int, root_size, seed: int, c
     leaf = np.empty((F, pb.n_taxa), dtype=np.int32)
     nodes = np.empty((F, pb.n_nodes), dtype=np.int32) if node_sizes else None
     err = C.create_string_buffer(512)
-    rc = load().cafe_simulate(C.byref(cp), seed, _p(leaf, _i32p), _p(nodes, _i32p), err, 512)
+    rc = call(C.byref(cp), seed, _p(leaf, _i32p), _p(nodes, _i32p), err, 512)
     if rc:
         raise CafeError("code %d: %s" % (rc, err.value.decode()))
     return leaf, nodes
+
+
+def simulate(pb: Problem, lambdas, max_family_size: int, root_size, seed: int, chunk_size: int = 50, chunk_multiplier=None,
+             error_model=None, error_model_max_size: int = 0, device: int = 0, workspace_limit: int = 0, node_sizes: bool = True):
+    """cafe_simulate: gene families simulated down pb's tree (its parent / branch_length / lambda_index / leaf_taxon; its
+    families are not read) from root_size[F], every child size drawn from the order-S transition matrices of the chunk's
+    lambdas * chunk_multiplier[f // chunk_size].  error_model: [S][n_deviations] table of get_probs(c), with
+    error_model_max_size = error_model::get_max_family_size().  Returns (leaf_counts int32 [F][n_taxa], node_sizes int32
+    [F][n_nodes] or None)."""
+    return _simulate(load().cafe_simulate, pb, lambdas, max_family_size, root_size, seed, chunk_size, chunk_multiplier, error_model,
+                     error_model_max_size, device, workspace_limit, node_sizes)
+
+
+def simulate_lm(pb: Problem, lambdas, mus, max_family_size: int, root_size, seed: int, **kwargs):
+    """cafe_simulate_lm: simulate() under separate birth and death rates, mus[n_lambdas] beside lambdas (a chunk multiplier
+    scales both).  mus=None passes NULL, which is cafe_simulate.  Keyword arguments and the result are simulate()'s."""
+    mu = None
+    if mus is not None:
+        mu = np.ascontiguousarray(np.atleast_1d(mus), dtype=np.float64)
+        if mu.shape != np.atleast_1d(lambdas).shape:
+            raise CafeError("mus needs one entry per lambda")
+    return _simulate(lambda cp, *rest: load().cafe_simulate_lm(cp, _p(mu, _f64p), *rest), pb, lambdas, max_family_size, root_size, seed, **kwargs)
 
 
 def probe_fp64_mfma(device: int = 0) -> float:

@@ -331,6 +331,9 @@ void destroy_child(cafe_ctx* c);
 int enqueue_rootmax(cafe_ctx* c, const double* lambdas, hipStream_t s);
 // one scorer evaluation per listed family, each under its own lambdas (family_lambda.hip)
 int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_t* family, const double* lambdas, double* family_lnl);
+// ... each under its own (lambdas, mus): the same frame with the two-rate kernel (family_lambda_lm.hip)
+int score_per_family_lm_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_t* family, const double* lambdas, const double* mus,
+                             double* family_lnl);
 // multi-GPU (cafe_sharded.hip)
 int comm_allreduce_pair(cafe_ctx* c, double* d_pair, hipStream_t s);
 void comm_release(cafe_ctx* c);

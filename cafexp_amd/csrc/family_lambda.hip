@@ -34,13 +34,14 @@
 
 #include "bd_row.h"
 #include "cafe_call.h"
+#include "family_lambda_lm.h"
 
 namespace cafe {
 
 namespace {
 
-constexpr int kPartRows = 16;        // rows whose lane partials are parked before they are summed
-constexpr int kPartLd = 65;          // doubles per parked row: 64 lanes + 1, so that the transposed read spreads over the banks
+// kPartRows, kPartLd: family_lambda_lm.h, shared with the two-rate twin of this kernel (family_lambda_lm.hip).  That kernel
+// MIRRORS the one below -- slot type, rc.init and the row step apart -- so a fix to one is a fix to both.
 
 struct FamLamArgs {
     const int32_t* nodes;            // the nodes of this level: one unit of work per branch above them
@@ -193,22 +194,54 @@ SlotParam branch_param(const cafe_ctx* c, int u, const double* lam) {
     }
     return slot_param(quantize_lambda(l), quantize_time(c->blen[u]));
 }
+// ... and under its (lambdas, mus): either rate beyond a long saturates the branch
+SlotParamLM branch_param_lm(const cafe_ctx* c, int u, const double* lam, const double* mus) {
+    const double l = lam[c->lam_idx[u]], m = mus[c->lam_idx[u]];
+    if (!(l * 1000000000 < 9.0e18) || !(m * 1000000000 < 9.0e18)) {
+        SlotParamLM sp{};
+        sp.alpha = 1.0; sp.beta = 1.0; sp.q = 0.0; sp.zero = 1;
+        return sp;
+    }
+    return slot_param_lm(quantize_lambda(l), quantize_lambda(m), quantize_time(c->blen[u]));
+}
 
-}  // namespace
+// What the two entries differ in: the slot type and argument block of their branch kernel, its launcher, and how a family's
+// rates become a branch's slot.  mus is null for the lambda = mu entry.
+struct EqualRates {
+    using Slot = SlotParam;
+    using Args = FamLamArgs;
+    static constexpr const char* entry = "cafe_score_per_family";
+    static constexpr bool reads_context_rates = true;  // lambda = mu is what it computes: refused while the context has death rates
+    static Slot slot(const cafe_ctx* c, int u, const double* lam, const double*) { return branch_param(c, u, lam); }
+    static hipError_t launch(const Args& a, int n, int64_t batch, int n_level_nodes, hipStream_t s) { return launch_family_lambda(a, n, batch, n_level_nodes, s); }
+};
+struct TwoRates {
+    using Slot = SlotParamLM;
+    using Args = FamLamArgsLM;
+    static constexpr const char* entry = "cafe_score_per_family_lm";
+    static constexpr bool reads_context_rates = false;
+    static Slot slot(const cafe_ctx* c, int u, const double* lam, const double* mus) { return branch_param_lm(c, u, lam, mus); }
+    static hipError_t launch(const Args& a, int n, int64_t batch, int n_level_nodes, hipStream_t s) { return launch_family_lambda_lm(a, n, batch, n_level_nodes, s); }
+};
 
-int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_t* family, const double* lambdas, double* family_lnl) {
-    if (!pr || !pr->prior) { set_err(c, "cafe_score_per_family: params with a prior are required"); return CAFE_ERR_ARGUMENT; }
-    if (pr->model != CAFE_MODEL_BASE) { set_err(c, "cafe_score_per_family: base model only"); return CAFE_ERR_ARGUMENT; }
-    if (c->comm) { set_err(c, "cafe_score_per_family: not valid on a context with a communicator attached"); return CAFE_ERR_STATE; }
-    if (!c->mus.empty()) { set_err(c, "cafe_score_per_family: not valid while death rates are set (cafe_set_death_rates)"); return CAFE_ERR_STATE; }
-    if (n < 0 || (n > 0 && (!family || !lambdas || !family_lnl))) { set_err(c, "cafe_score_per_family: family, lambdas and family_lnl are required"); return CAFE_ERR_ARGUMENT; }
+// The host frame of both entries: argument checks, what the host decides alone, levels and tables, the batches under the
+// workspace limit, one launch per level and the root kernel.  mus[n][n_lambdas] belongs to Kind = TwoRates only.
+template <class Kind>
+int per_family_frame(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_t* family, const double* lambdas, const double* mus, double* family_lnl) {
+    using Slot = typename Kind::Slot;
+    const char* const who = Kind::entry;
+    if (!pr || !pr->prior) { set_err(c, "%s: params with a prior are required", who); return CAFE_ERR_ARGUMENT; }
+    if (pr->model != CAFE_MODEL_BASE) { set_err(c, "%s: base model only", who); return CAFE_ERR_ARGUMENT; }
+    if (c->comm) { set_err(c, "%s: not valid on a context with a communicator attached", who); return CAFE_ERR_STATE; }
+    if (Kind::reads_context_rates && !c->mus.empty()) { set_err(c, "%s: not valid while death rates are set (cafe_set_death_rates)", who); return CAFE_ERR_STATE; }
+    if (n < 0 || (n > 0 && (!family || !lambdas || !family_lnl))) { set_err(c, "%s: family, lambdas and family_lnl are required", who); return CAFE_ERR_ARGUMENT; }
     if ((c->n_dev > 0) != (pr->error_model != nullptr)) {
-        set_err(c, "cafe_score_per_family: error model %s but the problem was created with n_deviations=%d", pr->error_model ? "given" : "missing", c->n_dev);
+        set_err(c, "%s: error model %s but the problem was created with n_deviations=%d", who, pr->error_model ? "given" : "missing", c->n_dev);
         return CAFE_ERR_ARGUMENT;
     }
-    if (!c->device_ready || !c->d_counts) { set_err(c, "cafe_score_per_family: the context holds no family table"); return CAFE_ERR_STATE; }
+    if (!c->device_ready || !c->d_counts) { set_err(c, "%s: the context holds no family table", who); return CAFE_ERR_STATE; }
     for (int64_t i = 0; i < n; ++i)
-        if (family[i] < 0 || family[i] >= c->F_all) { set_err(c, "cafe_score_per_family: family index %lld outside 0..%lld", (long long)family[i], (long long)c->F_all - 1); return CAFE_ERR_ARGUMENT; }
+        if (family[i] < 0 || family[i] >= c->F_all) { set_err(c, "%s: family index %lld outside 0..%lld", who, (long long)family[i], (long long)c->F_all - 1); return CAFE_ERR_ARGUMENT; }
     if (n == 0) return CAFE_OK;
     const int nn = c->n_nodes, L = c->n_lambdas, ld = round_up(c->N, 2);
 
@@ -217,9 +250,10 @@ int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const i
     active.reserve((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         const double* lam = lambdas + i * L;
-        bool nan = false;
+        bool nan = false, valid = lambdas_valid(c, lam);
         for (int k = 0; k < L; ++k) nan = nan || std::isnan(lam[k]);
-        if (!lambdas_valid(c, lam)) family_lnl[i] = -std::numeric_limits<double>::infinity();
+        for (int k = 0; mus && k < L; ++k) valid = valid && mus[i * L + k] >= 0;      // rates_valid's rule for a death rate
+        if (!valid) family_lnl[i] = -std::numeric_limits<double>::infinity();
         else if (nan) family_lnl[i] = std::numeric_limits<double>::quiet_NaN();
         else active.push_back(i);
     }
@@ -258,20 +292,20 @@ int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const i
     // ---- the batch: as many listed families as the workspace holds
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t static_bytes = align_up(sizeof(int32_t) * tables.size()) + align_up(sizeof(double) * reals.size());
-    const size_t family_bytes = sizeof(double) * (size_t)nn * ld + sizeof(SlotParam) * (size_t)nn + sizeof(int64_t) + sizeof(double);
+    const size_t family_bytes = sizeof(double) * (size_t)nn * ld + sizeof(Slot) * (size_t)nn + sizeof(int64_t) + sizeof(double);
     size_t budget = 0;
     HIP_TRY(c, workspace_budget(c->workspace_limit, c->pf_dev_bytes, &budget));
     int64_t batch = std::max<int64_t>(1, std::min<int64_t>(na, budget > static_bytes + 1024 ? (int64_t)((budget - static_bytes - 1024) / family_bytes) : 1));
     if (c->pf_max_batch > 0) batch = std::min(batch, c->pf_max_batch);
     const size_t o_reals = align_up(sizeof(int32_t) * tables.size()), o_col = o_reals + align_up(sizeof(double) * reals.size()),
                  o_out = o_col + align_up(sizeof(int64_t) * batch), o_slots = o_out + align_up(sizeof(double) * batch),
-                 o_fac = o_slots + align_up(sizeof(SlotParam) * (size_t)batch * nn), need = o_fac + sizeof(double) * (size_t)batch * nn * ld;
+                 o_fac = o_slots + align_up(sizeof(Slot) * (size_t)batch * nn), need = o_fac + sizeof(double) * (size_t)batch * nn * ld;
     if (need > c->pf_dev_bytes) {
         if (c->pf_dev) { HIP_TRY(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->pf_dev); c->pf_dev = nullptr; c->pf_dev_bytes = 0; }
         if (hipMalloc(&c->pf_dev, need) != hipSuccess) {
             (void)hipGetLastError();
             c->pf_dev = nullptr;
-            set_err(c, "cafe_score_per_family: cannot allocate a workspace of %zu bytes (%lld families per batch)", need, (long long)batch);
+            set_err(c, "%s: cannot allocate a workspace of %zu bytes (%lld families per batch)", who, need, (long long)batch);
             return CAFE_ERR_MEMORY;
         }
         c->pf_dev_bytes = need;
@@ -283,9 +317,9 @@ int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const i
     HIP_TRY(c, hipMemcpyAsync(base, tables.data(), sizeof(int32_t) * tables.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(base + o_reals, reals.data(), sizeof(double) * reals.size(), hipMemcpyHostToDevice, s));
 
-    FamLamArgs a{};
+    typename Kind::Args a{};
     a.child_off = d_tables; a.child_idx = d_tables + o_child_idx; a.taxon = d_tables + o_taxon; a.n_rows = d_tables + o_rows;
-    a.slots = reinterpret_cast<const SlotParam*>(base + o_slots);
+    a.slots = reinterpret_cast<const Slot*>(base + o_slots);
     a.col = reinterpret_cast<const int64_t*>(base + o_col);
     a.counts = c->d_counts; a.counts_ld = c->Fp;
     a.err = c->n_dev > 0 ? d_reals + c->R : nullptr;
@@ -296,7 +330,7 @@ int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const i
     ra.R = c->R; ra.ld = ld; ra.n_nodes = nn; ra.log_prior = d_reals; ra.factors = a.factors;
     ra.out = reinterpret_cast<double*>(base + o_out);
 
-    std::vector<SlotParam> slots((size_t)batch * nn);
+    std::vector<Slot> slots((size_t)batch * nn);
     std::vector<int64_t> col((size_t)batch);
     std::vector<double> res((size_t)batch);
     for (int64_t b0 = 0; b0 < na; b0 += batch) {
@@ -304,13 +338,13 @@ int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const i
         for (int64_t b = 0; b < nb; ++b) {
             const int64_t i = active[b0 + b];
             col[b] = c->ref_of[family[i]];
-            for (int u = 0; u < nn; ++u) slots[(size_t)b * nn + u] = u == c->root ? SlotParam{} : branch_param(c, u, lambdas + i * L);
+            for (int u = 0; u < nn; ++u) slots[(size_t)b * nn + u] = u == c->root ? Slot{} : Kind::slot(c, u, lambdas + i * L, mus ? mus + i * L : nullptr);
         }
-        HIP_TRY(c, hipMemcpyAsync(base + o_slots, slots.data(), sizeof(SlotParam) * (size_t)nb * nn, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(base + o_slots, slots.data(), sizeof(Slot) * (size_t)nb * nn, hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(base + o_col, col.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, s));
         for (int lv = 0; lv < n_levels; ++lv) {
             a.nodes = d_tables + o_level + level_off[lv];
-            HIP_TRY(c, launch_family_lambda(a, c->N, nb, level_off[lv + 1] - level_off[lv], s));
+            HIP_TRY(c, Kind::launch(a, c->N, nb, level_off[lv + 1] - level_off[lv], s));
         }
         CAFE_LAUNCH(c, family_root_kernel, dim3((unsigned)nb), dim3(64), 0, s, ra);
         HIP_TRY(c, hipMemcpyAsync(res.data(), base + o_out, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
@@ -320,10 +354,28 @@ int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const i
     return CAFE_OK;
 }
 
+}  // namespace
+
+int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_t* family, const double* lambdas, double* family_lnl) {
+    return per_family_frame<EqualRates>(c, pr, n, family, lambdas, nullptr, family_lnl);
+}
+int score_per_family_lm_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_t* family, const double* lambdas, const double* mus,
+                             double* family_lnl) {
+    if (n > 0 && !mus) { set_err(c, "cafe_score_per_family_lm: mus are required"); return CAFE_ERR_ARGUMENT; }
+    return per_family_frame<TwoRates>(c, pr, n, family, lambdas, mus, family_lnl);
+}
+
 }  // namespace cafe
 
 int cafe_score_per_family(cafe_ctx* ctx, const cafe_params* params, int64_t n, const int64_t* family, const double* lambdas, double* family_lnl) {
     const int rc = cafe::guarded(ctx, "cafe_score_per_family", [&] { return cafe::score_per_family_impl(ctx, params, n, family, lambdas, family_lnl); });
+    if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
+    return rc;
+}
+
+int cafe_score_per_family_lm(cafe_ctx* ctx, const cafe_params* params, int64_t n, const int64_t* family, const double* lambdas, const double* mus,
+                             double* family_lnl) {
+    const int rc = cafe::guarded(ctx, "cafe_score_per_family_lm", [&] { return cafe::score_per_family_lm_impl(ctx, params, n, family, lambdas, mus, family_lnl); });
     if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
     return rc;
 }

@@ -6,7 +6,9 @@
 //   batches     the chunks (chunk_size families sharing one lambda multiplier) are cut into batches whose matrices and
 //               buffers fit the workspace; within a batch, chunks whose quantized lambdas agree share one block of
 //               matrices (the base model: one block for the whole batch)
-//   K1          launch_bd_matrix_build, row-major, order S, one slot per (block, distinct (lambda index, t_q) pair)
+//   K1          launch_bd_matrix_build, row-major, order S, one slot per (block, distinct (lambda index, t_q) pair);
+//               cafe_simulate_lm with death rates: launch_bd_lm_build from slot_param_lm, the multiplier scaling both rates, and
+//               chunks share a block when both quantized vectors agree.  Everything behind the matrices is the same code
 //   row_cdf     inclusive prefix sums of rows 1..S-1 over columns 0..S-1 (the reference's weights, :338-341); this pass, the
 //               generator and the draw are tree_sampler.h's, shared with pvalues.hip
 //   sample      one thread per family, nodes parents first, inverse-CDF draws by binary search; sizes node-major in a
@@ -120,69 +122,81 @@ void put_err(char* err, size_t errlen, const char* fmt, ...) {
     do {                                                                                                         \
         hipError_t e_ = (expr);                                                                                  \
         if (e_ != hipSuccess) {                                                                                  \
-            put_err(err, errlen, "cafe_simulate: %s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+            put_err(err, errlen, "%s: %s failed: %s (%s:%d)", who, #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
             return CAFE_ERR_DEVICE;                                                                              \
         }                                                                                                        \
     } while (0)
 
 // The quantized lambda of every lambda index under multiplier m (matrix_cache_key, matrix_cache.h:47): chunks with equal
 // vectors build the same matrices.
-std::vector<long> chunk_key(const cafe_sim_problem* p, double m) {
-    std::vector<long> k((size_t)p->n_lambdas);
-    for (int i = 0; i < p->n_lambdas; ++i) k[i] = quantize_lambda(p->lambdas[i] * m);
+// With death rates the key is [lambdas..., mus...].
+std::vector<long> chunk_key(const cafe_sim_problem* p, const double* mus, double m) {
+    const int L = p->n_lambdas;
+    std::vector<long> k((size_t)L * (mus ? 2 : 1));
+    for (int i = 0; i < L; ++i) k[i] = quantize_lambda(p->lambdas[i] * m);
+    for (int i = 0; mus && i < L; ++i) k[L + i] = quantize_lambda(mus[i] * m);
     return k;
 }
 
-int simulate_impl(const cafe_sim_problem* p, uint64_t seed, int32_t* leaf_counts, int32_t* node_sizes, char* err, size_t errlen) {
+// mus == nullptr: cafe_simulate (lambda = mu, K1)
+int simulate_impl(const cafe_sim_problem* p, const double* mus, uint64_t seed, int32_t* leaf_counts, int32_t* node_sizes, char* err, size_t errlen) {
+    const char* const who = mus ? "cafe_simulate_lm" : "cafe_simulate";      // the entry the messages name
     // ---------------------------------------------------------------- arguments
-    if (!p) { put_err(err, errlen, "cafe_simulate: problem is NULL"); return CAFE_ERR_ARGUMENT; }
+    if (!p) { put_err(err, errlen, "%s: problem is NULL", who); return CAFE_ERR_ARGUMENT; }
     const int n = p->n_nodes, S = p->max_family_size, T = p->n_taxa, L = p->n_lambdas;
     const int64_t F = p->n_families;
-    if (n < 2 || !p->parent || !p->branch_length || !p->leaf_taxon || T < 1) { put_err(err, errlen, "cafe_simulate: a tree of >= 2 nodes with parent, branch_length and leaf_taxon is required"); return CAFE_ERR_ARGUMENT; }
-    if (S < 2 || S > bd_matrix_max_order()) { put_err(err, errlen, "cafe_simulate: matrix order %d outside 2..%d", S, bd_matrix_max_order()); return CAFE_ERR_ARGUMENT; }
-    if (F < 0 || (F > 0 && !p->root_size)) { put_err(err, errlen, "cafe_simulate: root_size[n_families] is required"); return CAFE_ERR_ARGUMENT; }
-    if (!leaf_counts && !node_sizes) { put_err(err, errlen, "cafe_simulate: no output"); return CAFE_ERR_ARGUMENT; }
-    if (L < 1 || !p->lambdas) { put_err(err, errlen, "cafe_simulate: lambdas are required"); return CAFE_ERR_ARGUMENT; }
+    if (n < 2 || !p->parent || !p->branch_length || !p->leaf_taxon || T < 1) { put_err(err, errlen, "%s: a tree of >= 2 nodes with parent, branch_length and leaf_taxon is required", who); return CAFE_ERR_ARGUMENT; }
+    if (S < 2 || S > bd_matrix_max_order()) { put_err(err, errlen, "%s: matrix order %d outside 2..%d", who, S, bd_matrix_max_order()); return CAFE_ERR_ARGUMENT; }
+    if (F < 0 || (F > 0 && !p->root_size)) { put_err(err, errlen, "%s: root_size[n_families] is required", who); return CAFE_ERR_ARGUMENT; }
+    if (!leaf_counts && !node_sizes) { put_err(err, errlen, "%s: no output", who); return CAFE_ERR_ARGUMENT; }
+    if (L < 1 || !p->lambdas) { put_err(err, errlen, "%s: lambdas are required", who); return CAFE_ERR_ARGUMENT; }
     for (int i = 0; i < L; ++i) {
         const double l = p->lambdas[i];
-        if (!std::isfinite(l) || l < 0 || (L == 1 && !(l > 0)) || l * 1000000000 > 1e18) { put_err(err, errlen, "cafe_simulate: invalid lambda %g", l); return CAFE_ERR_ARGUMENT; }
+        if (!std::isfinite(l) || l < 0 || (L == 1 && !(l > 0)) || l * 1000000000 > 1e18) { put_err(err, errlen, "%s: invalid lambda %g", who, l); return CAFE_ERR_ARGUMENT; }
     }
-    if (p->chunk_size < 0) { put_err(err, errlen, "cafe_simulate: chunk_size < 0"); return CAFE_ERR_ARGUMENT; }
+    for (int i = 0; mus && i < L; ++i) {
+        const double mu = mus[i];
+        if (!std::isfinite(mu) || mu < 0 || mu * 1000000000 > 1e18) { put_err(err, errlen, "%s: invalid mu %g", who, mu); return CAFE_ERR_ARGUMENT; }
+    }
+    if (p->chunk_size < 0) { put_err(err, errlen, "%s: chunk_size < 0", who); return CAFE_ERR_ARGUMENT; }
     const int64_t chunk = p->chunk_size > 0 ? p->chunk_size : std::max<int64_t>(F, 1);
     const int64_t n_chunks = (F + chunk - 1) / chunk;
     double max_lambda = 0;
     for (int i = 0; i < L; ++i) max_lambda = std::max(max_lambda, p->lambdas[i]);
+    double max_mu = 0;
+    for (int i = 0; mus && i < L; ++i) max_mu = std::max(max_mu, mus[i]);
     if (p->chunk_multiplier)
         for (int64_t c = 0; c < n_chunks; ++c) {
             const double m = p->chunk_multiplier[c];
-            if (!std::isfinite(m) || m < 0 || max_lambda * m * 1000000000 > 1e18) { put_err(err, errlen, "cafe_simulate: invalid lambda multiplier %g of chunk %lld", m, (long long)c); return CAFE_ERR_ARGUMENT; }
+            if (!std::isfinite(m) || m < 0 || max_lambda * m * 1000000000 > 1e18) { put_err(err, errlen, "%s: invalid lambda multiplier %g of chunk %lld", who, m, (long long)c); return CAFE_ERR_ARGUMENT; }
+            if (max_mu * m * 1000000000 > 1e18) { put_err(err, errlen, "%s: mu %g times multiplier %g of chunk %lld is out of range", who, max_mu, m, (long long)c); return CAFE_ERR_ARGUMENT; }
         }
-    if (p->error_model && (p->n_deviations < 3 || p->error_model_max_size < 0)) { put_err(err, errlen, "cafe_simulate: an error model needs >= 3 deviations"); return CAFE_ERR_ARGUMENT; }
+    if (p->error_model && (p->n_deviations < 3 || p->error_model_max_size < 0)) { put_err(err, errlen, "%s: an error model needs >= 3 deviations", who); return CAFE_ERR_ARGUMENT; }
     int root = -1;
     std::vector<int32_t> n_children(n, 0);
     for (int v = 0; v < n; ++v) {
         const int par = p->parent[v];
-        if (par < 0) { if (root >= 0) { put_err(err, errlen, "cafe_simulate: more than one root"); return CAFE_ERR_ARGUMENT; } root = v; continue; }
-        if (par <= v || par >= n) { put_err(err, errlen, "cafe_simulate: node %d: parents must come after their children", v); return CAFE_ERR_ARGUMENT; }
+        if (par < 0) { if (root >= 0) { put_err(err, errlen, "%s: more than one root", who); return CAFE_ERR_ARGUMENT; } root = v; continue; }
+        if (par <= v || par >= n) { put_err(err, errlen, "%s: node %d: parents must come after their children", who, v); return CAFE_ERR_ARGUMENT; }
         ++n_children[par];
         const double t = p->branch_length[v];
-        if (!std::isfinite(t) || t < 0 || t > 1e15) { put_err(err, errlen, "cafe_simulate: invalid branch length %g", t); return CAFE_ERR_ARGUMENT; }
-        if (p->lambda_index && (p->lambda_index[v] < 0 || p->lambda_index[v] >= L)) { put_err(err, errlen, "cafe_simulate: lambda index out of range"); return CAFE_ERR_ARGUMENT; }
+        if (!std::isfinite(t) || t < 0 || t > 1e15) { put_err(err, errlen, "%s: invalid branch length %g", who, t); return CAFE_ERR_ARGUMENT; }
+        if (p->lambda_index && (p->lambda_index[v] < 0 || p->lambda_index[v] >= L)) { put_err(err, errlen, "%s: lambda index out of range", who); return CAFE_ERR_ARGUMENT; }
     }
-    if (root < 0) { put_err(err, errlen, "cafe_simulate: no root"); return CAFE_ERR_ARGUMENT; }
+    if (root < 0) { put_err(err, errlen, "%s: no root", who); return CAFE_ERR_ARGUMENT; }
     std::vector<int32_t> taxon_node(T, -1), is_leaf(n, 0);
     for (int v = 0; v < n; ++v) {
         const int tx = p->leaf_taxon[v];
         if ((n_children[v] == 0) != (tx >= 0) || tx >= T || (tx >= 0 && taxon_node[tx] >= 0)) {
-            put_err(err, errlen, "cafe_simulate: leaf_taxon must name a distinct taxon for every leaf and -1 for interior nodes");
+            put_err(err, errlen, "%s: leaf_taxon must name a distinct taxon for every leaf and -1 for interior nodes", who);
             return CAFE_ERR_ARGUMENT;
         }
         if (tx >= 0) { taxon_node[tx] = v; is_leaf[v] = 1; }
     }
-    for (int t = 0; t < T; ++t) if (taxon_node[t] < 0) { put_err(err, errlen, "cafe_simulate: taxon %d has no leaf", t); return CAFE_ERR_ARGUMENT; }
+    for (int t = 0; t < T; ++t) if (taxon_node[t] < 0) { put_err(err, errlen, "%s: taxon %d has no leaf", who, t); return CAFE_ERR_ARGUMENT; }
     for (int64_t f = 0; f < F; ++f)
         if (p->root_size[f] < 0 || p->root_size[f] >= S) {
-            put_err(err, errlen, "cafe_simulate: root size %d of family %lld outside 0..%d", p->root_size[f], (long long)f, S - 1);
+            put_err(err, errlen, "%s: root size %d of family %lld outside 0..%d", who, p->root_size[f], (long long)f, S - 1);
             return CAFE_ERR_ARGUMENT;
         }
     if (F == 0) return CAFE_OK;
@@ -210,11 +224,12 @@ int simulate_impl(const cafe_sim_problem* p, uint64_t seed, int32_t* leaf_counts
     for (int v = 0; v < n; ++v) all_nodes[v] = v;
 
     MatrixPool pool = row_major_pool(S);
-    const size_t block_bytes = sizeof(double) * (size_t)pool.stride * n_pairs + sizeof(SlotParam) * n_pairs + sizeof(int32_t);
+    const size_t slot_bytes = mus ? sizeof(SlotParamLM) : sizeof(SlotParam);
+    const size_t block_bytes = sizeof(double) * (size_t)pool.stride * n_pairs + slot_bytes * n_pairs + sizeof(int32_t);
     const size_t family_bytes = sizeof(int32_t) * ((size_t)n + (leaf_counts ? T : 0) + (node_sizes ? n : 0));
 
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || p->device < 0 || p->device >= ndev) { put_err(err, errlen, "cafe_simulate: no HIP device %d", p->device); return CAFE_ERR_DEVICE; }
+    if (hipGetDeviceCount(&ndev) != hipSuccess || p->device < 0 || p->device >= ndev) { put_err(err, errlen, "%s: no HIP device %d", who, p->device); return CAFE_ERR_DEVICE; }
     SIM_TRY(hipSetDevice(p->device));
     size_t budget = 0;
     SIM_TRY(workspace_budget(p->workspace_limit, 0, &budget));
@@ -234,7 +249,7 @@ int simulate_impl(const cafe_sim_problem* p, uint64_t seed, int32_t* leaf_counts
     const size_t meta_len = (size_t)5 * n + T;
     const bool ok =
         hipMalloc(&d_pool.p, sizeof(double) * (size_t)pool.stride * n_pairs * blocks_max) == hipSuccess &&
-        hipMalloc(&d_slots.p, sizeof(SlotParam) * (size_t)n_pairs * blocks_max) == hipSuccess &&
+        hipMalloc(&d_slots.p, slot_bytes * (size_t)n_pairs * blocks_max) == hipSuccess &&
         hipMalloc(&d_meta.p, sizeof(int32_t) * meta_len) == hipSuccess &&
         hipMalloc(&d_root.p, sizeof(int32_t) * (size_t)F) == hipSuccess &&
         (!em_len || hipMalloc(&d_err.p, sizeof(double) * em_len) == hipSuccess) &&
@@ -245,7 +260,7 @@ int simulate_impl(const cafe_sim_problem* p, uint64_t seed, int32_t* leaf_counts
         hipMalloc(&d_cblock.p, sizeof(int32_t) * (size_t)chunks_max) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        put_err(err, errlen, "cafe_simulate: cannot allocate the workspace (%lld families, %lld matrix blocks per batch)", (long long)fb_max, (long long)blocks_max);
+        put_err(err, errlen, "%s: cannot allocate the workspace (%lld families, %lld matrix blocks per batch)", who, (long long)fb_max, (long long)blocks_max);
         return CAFE_ERR_MEMORY;
     }
     int32_t* meta = static_cast<int32_t*>(d_meta.p);                   // order, parent, pair_of, is_leaf, nodes, taxon_node
@@ -276,6 +291,7 @@ int simulate_impl(const cafe_sim_problem* p, uint64_t seed, int32_t* leaf_counts
 
     // ---------------------------------------------------------------- batches
     std::vector<SlotParam> slots;
+    std::vector<SlotParamLM> slots_lm;
     std::vector<int32_t> cblock;
     for (int64_t f0 = 0; f0 < F;) {
         int64_t f1 = std::min(F, f0 + fb_max);
@@ -288,7 +304,7 @@ int simulate_impl(const cafe_sim_problem* p, uint64_t seed, int32_t* leaf_counts
             const double m = p->chunk_multiplier ? p->chunk_multiplier[c] : 1.0;
             if (!cblock.empty() && m == prev_m) { cblock.push_back(cblock.back()); continue; }
             prev_m = m;
-            std::vector<long> key = chunk_key(p, m);
+            std::vector<long> key = chunk_key(p, mus, m);
             auto it = block_of.find(key);
             if (it == block_of.end()) {
                 if ((int64_t)blocks.size() == blocks_max) { f1 = c * chunk; break; }     // the batch ends before this chunk
@@ -298,15 +314,23 @@ int simulate_impl(const cafe_sim_problem* p, uint64_t seed, int32_t* leaf_counts
             cblock.push_back(it->second);
         }
         const int64_t fb = f1 - f0;
-        slots.assign((size_t)blocks.size() * n_pairs, SlotParam{});
-        for (size_t b = 0; b < blocks.size(); ++b)
-            for (int q = 0; q < n_pairs; ++q) slots[b * n_pairs + q] = slot_param(blocks[b][pair_lam[q]], pair_tq[q]);
-        const int n_slots = (int)slots.size();
+        const int n_slots = (int)blocks.size() * n_pairs;
         pool.base = static_cast<double*>(d_pool.p);
-        SIM_TRY(hipMemcpyAsync(d_slots.p, slots.data(), sizeof(SlotParam) * n_slots, hipMemcpyHostToDevice, s));
+        // K1 (or its two-rate twin) stores every row of every slot (a saturated one too): no clearing pass; columns >= S are never read
+        if (mus) {
+            slots_lm.assign((size_t)n_slots, SlotParamLM{});
+            for (size_t b = 0; b < blocks.size(); ++b)
+                for (int q = 0; q < n_pairs; ++q) slots_lm[b * n_pairs + q] = slot_param_lm(blocks[b][pair_lam[q]], blocks[b][L + pair_lam[q]], pair_tq[q]);
+            SIM_TRY(hipMemcpyAsync(d_slots.p, slots_lm.data(), sizeof(SlotParamLM) * n_slots, hipMemcpyHostToDevice, s));
+            SIM_TRY(launch_bd_lm_build(pool, static_cast<const SlotParamLM*>(d_slots.p), n_slots, s));
+        } else {
+            slots.assign((size_t)n_slots, SlotParam{});
+            for (size_t b = 0; b < blocks.size(); ++b)
+                for (int q = 0; q < n_pairs; ++q) slots[b * n_pairs + q] = slot_param(blocks[b][pair_lam[q]], pair_tq[q]);
+            SIM_TRY(hipMemcpyAsync(d_slots.p, slots.data(), sizeof(SlotParam) * n_slots, hipMemcpyHostToDevice, s));
+            SIM_TRY(launch_bd_matrix_build(pool, static_cast<const SlotParam*>(d_slots.p), n_slots, s));
+        }
         SIM_TRY(hipMemcpyAsync(d_cblock.p, cblock.data(), sizeof(int32_t) * cblock.size(), hipMemcpyHostToDevice, s));
-        // K1 stores every row of every slot (a saturated one too): no clearing pass; columns >= S are never read
-        SIM_TRY(launch_bd_matrix_build(pool, static_cast<const SlotParam*>(d_slots.p), n_slots, s));
         SIM_TRY(launch_row_cdf(pool.base, pool.stride, pool.ld, n_slots, S, S, s));
         a.cdf = pool.base; a.f0 = f0; a.fb = fb; a.chunk0 = c0;
         hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((fb + 255) / 256)), dim3(256), 0, s, a);
@@ -341,12 +365,17 @@ int simulate_impl(const cafe_sim_problem* p, uint64_t seed, int32_t* leaf_counts
 
 }  // namespace cafe
 
-int cafe_simulate(const cafe_sim_problem* problem, uint64_t seed, int32_t* leaf_counts, int32_t* node_sizes, char* err, size_t errlen) {
+int cafe_simulate_lm(const cafe_sim_problem* problem, const double* mus, uint64_t seed, int32_t* leaf_counts, int32_t* node_sizes, char* err,
+                     size_t errlen) {
     if (err && errlen) err[0] = 0;
     try {
-        return cafe::simulate_impl(problem, seed, leaf_counts, node_sizes, err, errlen);
+        return cafe::simulate_impl(problem, mus, seed, leaf_counts, node_sizes, err, errlen);
     } catch (const std::exception& e) {
-        cafe::put_err(err, errlen, "cafe_simulate: %s", e.what());
+        cafe::put_err(err, errlen, "%s: %s", mus ? "cafe_simulate_lm" : "cafe_simulate", e.what());
         return CAFE_ERR_MEMORY;
     }
+}
+
+int cafe_simulate(const cafe_sim_problem* problem, uint64_t seed, int32_t* leaf_counts, int32_t* node_sizes, char* err, size_t errlen) {
+    return cafe_simulate_lm(problem, nullptr, seed, leaf_counts, node_sizes, err, errlen);
 }

@@ -334,8 +334,11 @@ public:
     reconstruction* reconstruct_ancestral_states(const std::vector<gene_family>& families, root_equilibrium_distribution* p_prior) override;   // base_model.cpp:145
     // Scorer values (-lnL, +inf for a rejected vector or NaN) of the listed families of the model's table, each under its own
     // lambdas[i * count .. ): one cafe_score_per_family call.  The model's lambda gives the structure (count, lambda tree) only.
+    // mus (laid out like lambdas): each family under its own (lambdas, mus), one cafe_score_per_family_lm call; the model's own
+    // death rates are not read.
     std::vector<double> per_family_scores(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist,
-                                          const std::vector<int64_t>& family, const std::vector<double>& lambdas);
+                                          const std::vector<int64_t>& family, const std::vector<double>& lambdas,
+                                          const std::vector<double>* mus = nullptr);
 };
 class hip_gamma_model : public hip_model_base {
     std::vector<double> _lambda_multipliers, _gamma_cat_probs;
@@ -581,12 +584,15 @@ struct simulation {
 };
 // simulate_processes draw for draw on randomizer_engine; gamma_alpha > 0: the gamma model (one Gamma(alpha, 1/alpha)
 // multiplier per chunk).  rootdist empty: nsims families with root sizes 0..99; else the vectorized distribution, pared to
-// nsims when 0 < nsims <= its size.  Matrices from cafe_build_matrices on `device`.
+// nsims when 0 < nsims <= its size.  Matrices from cafe_build_matrices on `device`.  death_rates (one mu per lambda, or
+// null / empty: lambda = mu): the same draws on the rows of cafe_build_matrices_lm; a chunk's multiplier scales both rates.
 simulation simulate_families(const clade* p_tree, const lambda* p_lambda, const error_model* p_error_model, const std::map<int, int>& rootdist,
-                             int nsims, double gamma_alpha, int device);
-// the same families' distribution from cafe_simulate: root sizes and multipliers from an engine seeded by `seed`
+                             int nsims, double gamma_alpha, int device, const std::vector<double>* death_rates = nullptr);
+// the same families' distribution from cafe_simulate (cafe_simulate_lm with death rates): root sizes and multipliers from an
+// engine seeded by `seed`
 simulation simulate_families_device(const clade* p_tree, const lambda* p_lambda, const error_model* p_error_model, const std::map<int, int>& rootdist,
-                                    int nsims, double gamma_alpha, int device, uint64_t seed, size_t workspace_limit = 0);
+                                    int nsims, double gamma_alpha, int device, uint64_t seed, size_t workspace_limit = 0,
+                                    const std::vector<double>* death_rates = nullptr);
 double average_multiplier(const simulation& sim);                   // write_average_multiplier's value (NaN without draws)
 // simulator::print_simulations (simulator.cpp:150-186): leaves only, or every node (interior ones by order index)
 void print_simulations(std::ostream& ost, bool include_internal_nodes, const simulation& sim);
@@ -658,14 +664,23 @@ public:
 // A finished search is begun again from its best point (inward first simplex, high-precision stop rule) while the last one
 // still gained (lambda_per_family.cpp).
 // M, R and the prior are the whole table's, as in the reference (set_families only swaps the family list).
+// Separate death rates per family (--family-mu): FIXED searches every family's lambdas with mu held at the given rates (one
+// per lambda); ESTIMATE searches [lambdas..., mus...] per family from the family's lambda-only optimum, every mu starting at
+// its lambda, so that the result is never worse than plain -b's (lambda_per_family.cpp).  Either scores through
+// cafe_score_per_family_lm.
+struct per_family_mu {
+    enum { NONE, FIXED, ESTIMATE } mode = NONE;
+    std::vector<double> fixed;                   // FIXED: one per lambda
+};
 struct per_family_result {
     std::vector<std::vector<double>> lambdas;    // per family, table order
+    std::vector<std::vector<double>> mus;        // per family with per_family_mu (empty without)
     size_t distinct_families = 0;
     int rounds = 0;                              // device calls
     long evaluations = 0;                        // (family, lambda vector) pairs scored
     long restarts = 0;                           // searches begun again from a family's best point
 };
-per_family_result estimate_lambda_per_family(hip_base_model& mdl, user_data& data, int max_iterations);
+per_family_result estimate_lambda_per_family(hip_base_model& mdl, user_data& data, int max_iterations, const per_family_mu& family_mu = per_family_mu());
 // what the reference prints when no start has a finite score (execute.cpp:192-206)
 void initialization_failure_advice(std::ostream& ost, const std::vector<gene_family>& families);
 

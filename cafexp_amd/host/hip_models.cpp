@@ -182,7 +182,8 @@ double hip_base_model::infer_family_likelihoods(root_equilibrium_distribution* p
 }
 
 std::vector<double> hip_base_model::per_family_scores(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist,
-                                                      const std::vector<int64_t>& family, const std::vector<double>& lambdas) {
+                                                      const std::vector<int64_t>& family, const std::vector<double>& lambdas,
+                                                      const std::vector<double>* mus) {
     ensure_context(1);
     std::vector<float> prior_f;
     std::vector<double> err, unused;
@@ -191,7 +192,11 @@ std::vector<double> hip_base_model::per_family_scores(root_equilibrium_distribut
     pr.model = CAFE_MODEL_BASE; pr.n_categories = 1; pr.prior = prior_f.data();
     pr.error_model = err.empty() ? nullptr : err.data();
     std::vector<double> out(family.size());
-    if (cafe_score_per_family(_ctx, &pr, (int64_t)family.size(), family.data(), lambdas.data(), out.data()) != CAFE_OK)
+    if (mus) {
+        if (mus->size() != lambdas.size()) throw std::runtime_error("per_family_scores: one mu per lambda is required");
+        if (cafe_score_per_family_lm(_ctx, &pr, (int64_t)family.size(), family.data(), lambdas.data(), mus->data(), out.data()) != CAFE_OK)
+            throw std::runtime_error(std::string("cafe_score_per_family_lm: ") + cafe_last_error(_ctx));
+    } else if (cafe_score_per_family(_ctx, &pr, (int64_t)family.size(), family.data(), lambdas.data(), out.data()) != CAFE_OK)
         throw std::runtime_error(std::string("cafe_score_per_family: ") + cafe_last_error(_ctx));
     for (double& v : out) v = std::isnan(v) ? std::numeric_limits<double>::infinity() : -v;      // optimizer_scorer.cpp:30
     return out;

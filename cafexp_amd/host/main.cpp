@@ -31,10 +31,13 @@ static void usage() {
         "  --gpus N: the scorer calls shard the families over devices 0..N-1 (one host thread per GPU, one RCCL all-reduce per call)\n"
         "lambda per family (the reference's -b): cafexp_hip -t TREE -i FAMILIES -b [-y LAMBDA_TREE] [-e ERRMODEL] [-p [L]] [-z] [-s SEED] [-I MAXITER]\n"
         "                  [--workspace BYTES] [-o OUTDIR]   writes OUTDIR (default results)/Base_lambda_per_family.txt, one line per family\n"
+        "                  [--family-mu M1[,M2,..] | --family-mu estimate]   separate death rates per family (only with -b): fixed at the given\n"
+        "                  rates, one per lambda, or searched with each family's lambdas (start mu = lambda); also writes Base_mu_per_family.txt\n"
         "simulation (the reference's -s; -s here is the SEED): cafexp_hip -t TREE (-l LAMBDA | -m L1,L2,.. -y LAMBDA_TREE) --simulate [N]\n"
         "                  [-k K] [-a ALPHA] [-e ERRMODEL] [-f ROOTDIST] [-s SEED] [-o OUTDIR] [--simulate-device [--workspace BYTES]] [-d DEVICE]\n"
         "  writes OUTDIR (default results)/simulation.txt and simulation_truth.txt; N families (root sizes 0..99), or the\n"
         "  -f distribution pared to N.  --simulate-device: the draws on the GPU (same distribution, another sample).\n"
+        "  --mu M1[,M2,..]: simulate under separate death rates, one per lambda (a gamma multiplier scales both rates).\n"
         "  The gamma model (-k > 1 or -a > 0) needs -a > 0: the reference would draw from Gamma(-1, -1) instead.\n");
 }
 
@@ -52,11 +55,20 @@ static void print_num(const char* key, double v, bool comma = true) {
     else std::printf("\"%s\": %.17g%s", key, v, comma ? ", " : "");
 }
 
+// "V1,V2,.." -> rates
+static std::vector<double> parse_rates(const std::string& list) {
+    std::vector<double> v;
+    std::stringstream ss(list);
+    std::string tok;
+    while (std::getline(ss, tok, ',')) v.push_back(std::stod(tok));
+    return v;
+}
+
 // simulator::simulate (simulator.cpp:113-147) with the checks of input_parameters::check_input (io.cpp:55-98)
 static int simulate_main(const std::string& tree_path, const std::string& fam_path, const std::string& rootdist_path,
                          const std::string& lambda_tree_path, const std::string& multi, const std::string& err_path, bool use_err,
                          double fixed_lambda, double fixed_alpha, int k, int nsims, bool on_device, uint64_t seed, int device,
-                         size_t workspace, std::string out_dir) {
+                         size_t workspace, std::string out_dir, const std::string& mu_list) {
     try {
         if (!multi.empty() && lambda_tree_path.empty()) throw std::runtime_error("Multiple lambda values (-m) specified with no lambda tree (-y)");
         if (!fam_path.empty() && !rootdist_path.empty()) throw std::runtime_error("Options -i and -f are mutually exclusive.");
@@ -90,10 +102,11 @@ static int simulate_main(const std::string& tree_path, const std::string& fam_pa
             read_rootdist(f, d.rootdist);
         }
         const double alpha = gamma ? fixed_alpha : 0.0;
+        const std::vector<double> mus = parse_rates(mu_list);       // one per lambda (checked by the simulator); empty: lambda = mu
         auto t0 = std::chrono::steady_clock::now();
         simulation sim = on_device
-            ? simulate_families_device(d.p_tree.get(), d.p_lambda.get(), d.p_error_model.get(), d.rootdist, nsims, alpha, device, seed, workspace)
-            : simulate_families(d.p_tree.get(), d.p_lambda.get(), d.p_error_model.get(), d.rootdist, nsims, alpha, device);
+            ? simulate_families_device(d.p_tree.get(), d.p_lambda.get(), d.p_error_model.get(), d.rootdist, nsims, alpha, device, seed, workspace, &mus)
+            : simulate_families(d.p_tree.get(), d.p_lambda.get(), d.p_error_model.get(), d.rootdist, nsims, alpha, device, &mus);
         const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (out_dir.empty()) out_dir = "results";                   // filename() (core.h:196)
         if (::mkdir(out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("Failed to create directory " + out_dir);
@@ -111,6 +124,11 @@ static int simulate_main(const std::string& tree_path, const std::string& fam_pa
         std::printf("{\"model\": \"%s\", \"mode\": \"%s\", \"n_families\": %zu, \"max_family_size\": %d, \"seconds\": %.6f, \"write_seconds\": %.6f, ",
                     gamma ? "Gamma" : "Base", on_device ? "device" : "host", sim.n_families, sim.max_family_size, seconds, write_s);
         print_num("average_multiplier", avg, false);
+        if (!mus.empty()) {
+            std::printf(", \"mu\": [");
+            for (size_t i = 0; i < mus.size(); ++i) std::printf("%s%.17g", i ? ", " : "", mus[i]);
+            std::printf("]");
+        }
         if (!sim.multipliers.empty() && sim.multipliers.size() <= 1000) {     // one per chunk of 50 families
             std::printf(", \"multipliers\": [");
             for (size_t i = 0; i < sim.multipliers.size(); ++i) std::printf("%s%.17g", i ? ", " : "", sim.multipliers[i]);
@@ -143,6 +161,7 @@ int main(int argc, char** argv) {
     bool per_family = false, gpus_given = false, alpha_given = false;      // -b: one lambda (vector) per family
     std::string mu_list;                                         // --mu: fixed death rates, one per lambda
     bool estimate_mu = false;                                    // --estimate-mu: death rates searched with the lambdas
+    std::string family_mu;                                       // --family-mu (with -b): rates, or "estimate"
     unsigned seed = 0;
     bool have_seed = false;
     for (int i = 1; i < argc; ++i) {
@@ -159,6 +178,7 @@ int main(int argc, char** argv) {
         else if (a == "-b") per_family = true;
         else if (a == "--mu") mu_list = next();
         else if (a == "--estimate-mu") estimate_mu = true;
+        else if (a == "--family-mu") family_mu = next();
         else if (a == "-e") { use_err = true; err_path = optional(); }
         else if (a == "-p") { use_poisson = true; std::string v = optional(); poisson = v.empty() ? 0 : std::stod(v); }
         else if (a == "-f") rootdist_path = next();
@@ -190,9 +210,11 @@ int main(int argc, char** argv) {
     }
     if (simulate_n >= 0) {
         if (tree_path.empty()) { usage(); return 2; }
+        if (estimate_mu) { std::fprintf(stderr, "cafexp_hip: --simulate draws under given rates: --estimate-mu is not supported with it (give --mu)\n"); return 1; }
+        if (!family_mu.empty()) { std::fprintf(stderr, "cafexp_hip: --family-mu sets the death rates of -b: it is not supported without -b\n"); return 1; }
         if (have_seed) randomizer_engine.seed(seed);
         return simulate_main(tree_path, fam_path, rootdist_path, lambda_tree_path, multi, err_path, use_err, fixed_lambda, fixed_alpha, k,
-                             simulate_n, simulate_on_device, have_seed ? seed : randomizer_engine(), device, sim_workspace, out_dir);
+                             simulate_n, simulate_on_device, have_seed ? seed : randomizer_engine(), device, sim_workspace, out_dir, mu_list);
     }
     if (tree_path.empty() || fam_path.empty()) { usage(); return 2; }
     if (estimate_mu || !mu_list.empty()) {
@@ -201,6 +223,10 @@ int main(int argc, char** argv) {
         else if (per_family) why = "-b runs the lambda = mu kernel: --mu / --estimate-mu are not supported with it";
         else if (estimate_mu && (fixed_lambda > 0 || !multi.empty())) why = "--estimate-mu searches lambda and mu together: -l / -m are not supported with it";
         if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
+    }
+    if (!family_mu.empty() && !per_family) {
+        std::fprintf(stderr, "cafexp_hip: --family-mu sets the death rates of -b: it is not supported without -b\n");
+        return 1;
     }
     if (do_marginal) {
         const char* why = nullptr;
@@ -282,10 +308,7 @@ int main(int argc, char** argv) {
         }
         mdl->set_device(device);
         if (!mu_list.empty()) {                                  // fixed death rates: one per lambda of the -y tree (one without)
-            std::vector<double> mus;
-            std::stringstream ss(mu_list);
-            std::string tok;
-            while (std::getline(ss, tok, ',')) mus.push_back(std::stod(tok));
+            const std::vector<double> mus = parse_rates(mu_list);
             size_t n_lambdas = 1;
             if (d.p_lambda_tree) {
                 std::set<int> uniq;
@@ -299,7 +322,10 @@ int main(int argc, char** argv) {
             hip_base_model* base = static_cast<hip_base_model*>(mdl.get());      // -k / -a were refused above
             base->set_workspace_limit(sim_workspace);
             const auto t0 = std::chrono::steady_clock::now();
-            const per_family_result res = estimate_lambda_per_family(*base, d, max_iter);
+            per_family_mu fmu;
+            if (family_mu == "estimate") fmu.mode = per_family_mu::ESTIMATE;
+            else if (!family_mu.empty()) { fmu.mode = per_family_mu::FIXED; fmu.fixed = parse_rates(family_mu); }
+            const per_family_result res = estimate_lambda_per_family(*base, d, max_iter, fmu);
             const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             if (out_dir.empty()) out_dir = "results";
             if (::mkdir(out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("Failed to create directory " + out_dir);
@@ -312,11 +338,20 @@ int main(int argc, char** argv) {
                     f << d.gene_families[i].id() << '\t' << shape->to_string() << "\n";
                 }
                 if (!f) throw std::runtime_error("Failed to write " + out_dir + "/" + mdl->name() + "_lambda_per_family.txt");
+                if (fmu.mode != per_family_mu::NONE) {           // the death rates, in the same shape and format
+                    std::ofstream g(out_dir + "/" + mdl->name() + "_mu_per_family.txt");
+                    for (size_t i = 0; i < d.gene_families.size(); ++i) {
+                        shape->update(res.mus[i].data());
+                        g << d.gene_families[i].id() << '\t' << shape->to_string() << "\n";
+                    }
+                    if (!g) throw std::runtime_error("Failed to write " + out_dir + "/" + mdl->name() + "_mu_per_family.txt");
+                }
             }
             std::printf("{\"model\": \"%s\", \"mode\": \"lambda_per_family\", \"families\": %zu, \"distinct_families\": %zu, \"rounds\": %d, \"evaluations\": %ld, \"restarts\": %ld, "
                         "\"max_family_size\": %d, \"max_root_family_size\": %d, ", mdl->name().c_str(), d.gene_families.size(), res.distinct_families, res.rounds,
                         res.evaluations, res.restarts, d.max_family_size, d.max_root_family_size);
             if (auto pd = dynamic_cast<poisson_distribution*>(d.p_prior.get())) print_num("poisson_lambda", pd->poisson_lambda());
+            if (fmu.mode != per_family_mu::NONE) std::printf("\"family_mu\": \"%s\", ", fmu.mode == per_family_mu::FIXED ? "fixed" : "estimate");
             std::printf("\"seconds\": %.3f}\n", seconds);
             return 0;
         }

@@ -5,10 +5,13 @@
 // LAMBDA_PERTURBATION_STEP_SIZE families the simulation lambda (a gamma draw for the gamma model), per family the root
 // size, then the prefix traversal with the same libstdc++ distribution objects (the uniform_int draw a saturated branch
 // throws away, the discrete_distribution over the S weights of row `parent size`, the error model's uniform at leaves).
-// The rows come from cafe_build_matrices (order S, row-major): no transition probability is computed on the host.
+// The rows come from cafe_build_matrices (order S, row-major): no transition probability is computed on the host.  With death
+// rates (one mu per lambda; a chunk's multiplier scales both rates) they come from cafe_build_matrices_lm, and the draw a
+// saturated branch throws away follows the library's rule for the pair (cafe_bd_rates).
 //
 // simulate_families_device draws only the root sizes and the chunk multipliers on the host (an engine seeded by the
-// seed, the same distributions) and hands the families to cafe_simulate: the same distribution, a different sample.
+// seed, the same distributions) and hands the families to cafe_simulate (cafe_simulate_lm with death rates): the same
+// distribution, a different sample.
 #include "cafe_host.h"
 
 #include <algorithm>
@@ -17,6 +20,7 @@
 #include <iostream>
 #include <numeric>
 #include <ostream>
+#include <tuple>
 
 #include "../../include/cafe_mi355x.h"
 
@@ -102,15 +106,24 @@ flat_tree flatten(const std::vector<const clade*>& order, const lambda* p_lambda
     return t;
 }
 
-void check_lambda(const lambda* p_lambda) {
+void check_lambda(const lambda* p_lambda, const std::vector<double>* death_rates) {
     if (!p_lambda) throw std::runtime_error("Cannot simulate without initial lambda values");     // io.cpp:66-69
+    if (death_rates && !death_rates->empty() && (int)death_rates->size() != p_lambda->count())
+        throw std::runtime_error("--mu needs one death rate per lambda (" + std::to_string(p_lambda->count()) + ")");
+}
+
+// the death rate of the branch above c: the mu of its lambda's index
+double mu_for_clade(const lambda* p_lambda, const std::vector<double>& mus, const clade* c) {
+    const multiple_lambda* ml = dynamic_cast<const multiple_lambda*>(p_lambda);
+    return mus[ml ? ml->index_of(c) : 0];
 }
 
 }  // namespace
 
 simulation simulate_families(const clade* p_tree, const lambda* p_lambda, const error_model* p_error_model, const std::map<int, int>& rootdist,
-                             int nsims, double gamma_alpha, int device) {
-    check_lambda(p_lambda);
+                             int nsims, double gamma_alpha, int device, const std::vector<double>* death_rates) {
+    check_lambda(p_lambda, death_rates);
+    const bool two_rates = death_rates && !death_rates->empty();
     simulation sim;
     p_tree->apply_reverse_level_order([&](const clade* c) { sim.order.push_back(c); });
     const int n = (int)sim.order.size();
@@ -129,31 +142,43 @@ simulation simulate_families(const clade* p_tree, const lambda* p_lambda, const 
     // (branch, parent size) -- they keep no state between draws, so one object serves every draw of its row
     std::vector<std::vector<double>> matrix(n);
     std::vector<std::map<int, std::discrete_distribution<int>>> dist(n);
-    std::vector<double> chunk_lambda(n, -1.0);
+    std::vector<double> chunk_lambda(n, -1.0), chunk_mu(n, -1.0);
+    std::vector<char> chunk_saturated(n, 0);
     const size_t step = LAMBDA_PERTURBATION_STEP_SIZE;
     for (size_t i = 0; i < sim.n_families; i += step) {
         const double m = chunk_multiplier(gamma_alpha, randomizer_engine);
         if (gamma_alpha > 0) sim.multipliers.push_back(m);
         std::unique_ptr<lambda> sim_lambda(p_lambda->multiply(m));
         // the rows of this chunk's matrices; branches whose (lambda, t) did not change keep theirs
-        std::map<std::pair<long, long>, std::vector<int>> need;
+        std::map<std::tuple<long, long, long>, std::vector<int>> need;
         for (int v = 0; v < n; ++v) {
             if (v == root) continue;
             const double lam = sim_lambda->get_value_for_clade(sim.order[v]);
-            if (lam == chunk_lambda[v]) continue;
+            const double mu = two_rates ? mu_for_clade(p_lambda, *death_rates, sim.order[v]) * m : lam;
+            if (lam == chunk_lambda[v] && mu == chunk_mu[v]) continue;
             chunk_lambda[v] = lam;
+            chunk_mu[v] = mu;
             dist[v].clear();
             const double t = sim.order[v]->get_branch_length();
-            need[{long(lam * 1000000000), long(t * 1000)}].push_back(v);
+            if (two_rates) {
+                double r[3];
+                cafe_bd_rates(lam, mu, t, r);
+                chunk_saturated[v] = 1 - r[0] - r[1] < 0;
+            } else {
+                chunk_saturated[v] = saturated(t, lam);
+            }
+            need[{long(lam * 1000000000), long(mu * 1000000000), long(t * 1000)}].push_back(v);
         }
         if (!need.empty()) {
-            std::vector<double> lams, ts, out((size_t)need.size() * S * S);
+            std::vector<double> lams, mus, ts, out((size_t)need.size() * S * S);
             for (const auto& kv : need) {
                 lams.push_back(chunk_lambda[kv.second[0]]);
+                mus.push_back(chunk_mu[kv.second[0]]);
                 ts.push_back(sim.order[kv.second[0]]->get_branch_length());
             }
-            const int rc = cafe_build_matrices(device, S, (int)need.size(), lams.data(), ts.data(), 0, out.data());
-            if (rc != CAFE_OK) throw std::runtime_error("cafe_build_matrices failed with code " + std::to_string(rc));
+            const int rc = two_rates ? cafe_build_matrices_lm(device, S, (int)need.size(), lams.data(), mus.data(), ts.data(), 0, out.data())
+                                     : cafe_build_matrices(device, S, (int)need.size(), lams.data(), ts.data(), 0, out.data());
+            if (rc != CAFE_OK) throw std::runtime_error(std::string(two_rates ? "cafe_build_matrices_lm" : "cafe_build_matrices") + " failed with code " + std::to_string(rc));
             size_t k = 0;
             for (const auto& kv : need) {
                 for (int v : kv.second) matrix[v].assign(out.begin() + k * S * S, out.begin() + (k + 1) * S * S);
@@ -170,7 +195,7 @@ simulation simulate_families(const clade* p_tree, const lambda* p_lambda, const 
                 const int parent_family_size = sizes[index.at(c->get_parent())];
                 int csize = 0;
                 if (parent_family_size > 0) {
-                    if (saturated(c->get_branch_length(), chunk_lambda[v])) {     // drawn, then overwritten (:333-337)
+                    if (chunk_saturated[v]) {                               // drawn, then overwritten (:333-337)
                         std::uniform_int_distribution<int> distribution(0, S - 1);
                         csize = distribution(randomizer_engine);
                     }
@@ -197,8 +222,9 @@ simulation simulate_families(const clade* p_tree, const lambda* p_lambda, const 
 }
 
 simulation simulate_families_device(const clade* p_tree, const lambda* p_lambda, const error_model* p_error_model, const std::map<int, int>& rootdist,
-                                    int nsims, double gamma_alpha, int device, uint64_t seed, size_t workspace_limit) {
-    check_lambda(p_lambda);
+                                    int nsims, double gamma_alpha, int device, uint64_t seed, size_t workspace_limit,
+                                    const std::vector<double>* death_rates) {
+    check_lambda(p_lambda, death_rates);
     simulation sim;
     p_tree->apply_reverse_level_order([&](const clade* c) { sim.order.push_back(c); });
     const int n = (int)sim.order.size();
@@ -239,7 +265,8 @@ simulation simulate_families_device(const clade* p_tree, const lambda* p_lambda,
     }
     pb.device = device; pb.workspace_limit = workspace_limit;
     char err[512];
-    const int rc = cafe_simulate(&pb, seed, nullptr, sim.sizes.data(), err, sizeof err);
+    const double* mus = death_rates && !death_rates->empty() ? death_rates->data() : nullptr;      // NULL: exactly cafe_simulate
+    const int rc = cafe_simulate_lm(&pb, mus, seed, nullptr, sim.sizes.data(), err, sizeof err);
     if (rc != CAFE_OK) throw std::runtime_error(err);
     return sim;
 }

@@ -259,6 +259,15 @@ typedef struct cafe_sim_problem {
 } cafe_sim_problem;
 /* leaf_counts[n_families][n_taxa] and node_sizes[n_families][n_nodes] (host memory; either may be NULL, not both). */
 int cafe_simulate(const cafe_sim_problem* problem, uint64_t seed, int32_t* leaf_counts, int32_t* node_sizes, char* err, size_t errlen);
+/* The same under separate birth and death rates: mus[n_lambdas], the death rate of the branches of lambda index i (birth rate
+ * problem->lambdas[i]); NULL is exactly cafe_simulate.  With mus the order-S matrices of every block are built by the two-rate
+ * kernel (bd_matrix_lm.hip) from the key (lambda * multiplier, mu * multiplier, t) -- a chunk multiplier scales both rates, as
+ * gamma multipliers do everywhere else -- and chunks share their matrices when both quantized vectors agree.  The row sums, the
+ * sampler, the Philox counters, the error-model step and the batching are cafe_simulate's.  Every mu must be finite, >= 0 and
+ * mu * multiplier * 1e9 within the bound lambda has: CAFE_ERR_ARGUMENT with a message that names mu otherwise.  With
+ * mus[i] == lambdas[i] the output is cafe_simulate's for the same seed. */
+int cafe_simulate_lm(const cafe_sim_problem* problem, const double* mus, uint64_t seed, int32_t* leaf_counts, int32_t* node_sizes,
+                     char* err, size_t errlen);
 
 /* model::infer_family_likelihoods for ONE family at a time, each with its own lambdas (estimate_lambda_per_family,
  * execute.cpp:104-128).  family[n] indexes the context's families (caller's order, duplicates allowed);
@@ -272,6 +281,19 @@ int cafe_simulate(const cafe_sim_problem* problem, uint64_t seed, int32_t* leaf_
  * meaningful after this call. */
 int cafe_score_per_family(cafe_ctx* ctx, const cafe_params* params, int64_t n, const int64_t* family,
                           const double* lambdas, double* family_lnl);
+/* The same with separate birth and death rates PER FAMILY: lambdas[n][n_lambdas] and mus[n][n_lambdas], entry i scores
+ * family[i] under its own pair.  Everything else is cafe_score_per_family's: base model only, params->prior and
+ * params->error_model are read, the list is processed in batches that fit workspace_limit, a value depends on the family's
+ * counts and its rates only, CAFE_ERR_STATE with a communicator attached.  The context's own death rates
+ * (cafe_set_death_rates) are NOT read: the call is valid, and gives the same values, whether or not they are set.
+ * Validity per entry is the context's rule as cafe_set_death_rates applies it -- one lambda: lambda > 0; several: no lambda
+ * negative; every mu must satisfy mu >= 0 (so a NaN mu is invalid, as it is in the setter's calls) -- and an invalid entry gives
+ * -inf; a NaN lambda that passes the rule gives NaN.  Either rate * 1e9 beyond a long gives the saturated branch (rows >= 1
+ * zero), as a lambda beyond it does in cafe_score_per_family.  The branch kernel is the two-rate twin of that entry's
+ * (family_lambda_lm.hip: the row step of bd_matrix_lm.hip on the key (lambda, mu, t), quantized like cafe_bd_rates); with
+ * mus[i] == lambdas[i] every value is bit for bit what cafe_score_per_family returns for that vector. */
+int cafe_score_per_family_lm(cafe_ctx* ctx, const cafe_params* params, int64_t n, const int64_t* family,
+                             const double* lambdas, const double* mus, double* family_lnl);
 
 /* Separate birth and death rates.  The reference fits the critical process lambda = mu only; with death rates set a context
  * scores the linear birth-death process with birth rate lambdas[i] and death rate mus[i] per lineage on the branches of
@@ -283,9 +305,10 @@ int cafe_score_per_family(cafe_ctx* ctx, const cafe_params* params, int64_t n, c
  * invalid mu makes a call's value +inf (or its error) exactly as an invalid lambda does; the gamma model's host rejection
  * (gamma_core.cpp:131-139) reads coeff = 1 - alpha - beta of the longest branch under the largest of either rate.  With
  * mus[i] == lambdas[i] every result is bit for bit the unset call's.
- * cafe_score_per_family returns CAFE_ERR_STATE while death rates are set (its kernel is the lambda = mu row step), and
- * cafe_simulate, which takes no context, is untouched: it simulates lambda = mu.  Sharded use needs no entry of its own: call
- * the setter on every cafe_sharded_context(s, r) (or on every rank's context) before the collective call. */
+ * cafe_score_per_family returns CAFE_ERR_STATE while death rates are set (its kernel is the lambda = mu row step):
+ * cafe_score_per_family_lm takes the death rates per family and does not read the context's.  cafe_simulate, which takes no
+ * context, simulates lambda = mu; cafe_simulate_lm takes the death rates as an argument.  Sharded use needs no entry of its own:
+ * call the setter on every cafe_sharded_context(s, r) (or on every rank's context) before the collective call. */
 int cafe_set_death_rates(cafe_ctx* ctx, const double* mus);
 /* What a transition matrix is built from, for the key (lambda, mu, t): lambda and mu quantized like lambda, t like the branch
  * length (matrix_cache_key, matrix_cache.h:42-61).  out[0] = alpha = P(a lineage is extinct after t), out[1] = beta, the ratio
