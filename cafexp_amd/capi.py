@@ -54,6 +54,11 @@ class CafeMarginalOut(C.Structure):
                 ("log_evidence", _f64p), ("failed", _i32p)]
 
 
+class CafeHistoryOut(C.Structure):
+    _fields_ = [("sizes", _i32p), ("category", _i32p), ("n_increase", _i64p), ("n_decrease", _i64p), ("net_change", _i64p),
+                ("log_evidence", _f64p), ("failed", _i32p)]
+
+
 class CafeStats(C.Structure):
     _fields_ = [
         ("ms_total", C.c_double), ("ms_matrices", C.c_double), ("ms_prune", C.c_double), ("ms_gemm", C.c_double),
@@ -87,7 +92,7 @@ EXPORTS = [
     "cafe_sharded_destroy", "cafe_sharded_last_error", "cafe_sharded_score", "cafe_sharded_family_results",
     "cafe_sharded_size", "cafe_sharded_context", "cafe_set_graphs", "cafe_executed_flops", "cafe_debug_tile_range_flops", "cafe_get_extents", "cafe_debug_launch_flops", "cafe_debug_launch_ms", "cafe_debug_plan_check",
     "cafe_debug_fail_next", "cafe_debug_column_extents", "cafe_debug_leaf_transposes", "cafe_simulate",
-    "cafe_score_per_family", "cafe_marginal_reconstruct", "cafe_debug_marginal_gemm",
+    "cafe_score_per_family", "cafe_marginal_reconstruct", "cafe_debug_marginal_gemm", "cafe_sample_histories", "cafe_debug_history_batches",
     "cafe_set_death_rates", "cafe_bd_rates", "cafe_build_matrices_lm", "cafe_score_per_family_lm", "cafe_simulate_lm",
 ]
 CAFE_COMM_ID_BYTES = 128
@@ -142,6 +147,8 @@ def load():
     L.cafe_score_per_family_lm.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p, _f64p]
     L.cafe_marginal_reconstruct.restype = C.c_int
     L.cafe_marginal_reconstruct.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_double, C.POINTER(CafeMarginalOut)]
+    L.cafe_sample_histories.restype = C.c_int
+    L.cafe_sample_histories.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.c_uint64, C.POINTER(CafeHistoryOut)]
     L.cafe_debug_marginal_gemm.restype = C.c_int
     L.cafe_debug_marginal_gemm.argtypes = [C.c_void_p, _f64p, _f64p]
     L.cafe_pvalues.restype = C.c_int
@@ -253,7 +260,7 @@ def _c_params(pr: Params, alpha: float = 1.0):
     if pr.multipliers is not None:
         cp.n_categories = len(pr.multipliers)
         cp.multipliers = _p(k(pr.multipliers, np.float64), _f64p)
-        cp.cat_probs = _p(k(pr.cat_probs, np.float64), _f64p)
+        cp.cat_probs = _p(k(pr.cat_probs, np.float64), _f64p) if pr.cat_probs is not None else None
     else:
         cp.n_categories = 1
     cp.alpha = alpha
@@ -416,6 +423,36 @@ class Context:
             setattr(mo, name, _p(res[name], _i32p if res[name].dtype == np.int32 else _f64p))
         self._check(self._lib.cafe_marginal_reconstruct(self._h, C.byref(cp), float(level), C.byref(mo)))
         return res
+
+    def sample_histories(self, pr: Params, n_draws: int, seed: int, alpha: float = 1.0, sizes: bool = True) -> dict:
+        """cafe_sample_histories: n_draws ancestral histories of every family from the posterior of marginal_reconstruct's
+        model.  Returns numpy arrays: sizes int32 [n_draws][n_families][n_nodes] (left out with sizes=False: then only
+        the counts leave the device), category int32 [n_draws][n_families], n_increase / n_decrease / net_change int64
+        [n_draws][n_nodes], log_evidence and failed [n_families]."""
+        cp, keep = self._params(pr, alpha)
+        D, F, n = int(n_draws), self.n_families, self.n_nodes
+        rows = D
+        if not 1 <= D <= 65536:
+            rows = 0                                             # the library rejects the call; nothing to allocate for it
+        res = {"category": np.empty((rows, F), dtype=np.int32), "n_increase": np.empty((rows, n), dtype=np.int64),
+               "n_decrease": np.empty((rows, n), dtype=np.int64), "net_change": np.empty((rows, n), dtype=np.int64),
+               "log_evidence": np.empty(F), "failed": np.empty(F, dtype=np.int32)}
+        if sizes:
+            res["sizes"] = np.empty((rows, F, n), dtype=np.int32)
+        ho = CafeHistoryOut()
+        for name, t in CafeHistoryOut._fields_:
+            if name in res:
+                setattr(ho, name, _p(res[name], t))
+        self._check(self._lib.cafe_sample_histories(self._h, C.byref(cp), D, int(seed), C.byref(ho)))
+        return res
+
+    def history_batches(self):
+        """(column batches, draw passes per batch) of the last sample_histories under the workspace budget"""
+        self._lib.cafe_debug_history_batches.restype = C.c_int
+        self._lib.cafe_debug_history_batches.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        nb, npass = C.c_int32(), C.c_int32()
+        self._check(self._lib.cafe_debug_history_batches(self._h, C.byref(nb), C.byref(npass)))
+        return nb.value, npass.value
 
     def marginal_gemm_stats(self):
         """(summed HIP-event ms of the GEMM launches of the last marginal_reconstruct -- 0 unless profiling was on --, their flops)"""

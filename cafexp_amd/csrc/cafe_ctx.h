@@ -1,6 +1,6 @@
 // Internal: the context behind the C ABI handle and what the translation units of the library share.  cafe_create.hip builds
-// it, cafe_score.hip is the scorer's call path, cafe_debug.hip reads it back; reconstruct.hip, marginal.hip, pvalues.hip and
-// family_lambda.hip are the calls beside the scorer (their common frame: cafe_call.h), cafe_sharded.hip the multi-GPU layer.
+// it, cafe_score.hip is the scorer's call path, cafe_debug.hip reads it back; reconstruct.hip, marginal.hip, history.hip,
+// pvalues.hip and family_lambda.hip are the calls beside the scorer (their common frame: cafe_call.h), cafe_sharded.hip the multi-GPU layer.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -187,7 +187,8 @@ struct cafe_ctx {
     size_t pf_dev_bytes = 0;
     int64_t pf_max_batch = 0;                // CAFE_PER_FAMILY_BATCH: at most that many families per batch (diagnostic; 0 = what fits)
     double marginal_gemm_ms = 0, marginal_gemm_flops = 0;   // cafe_marginal_reconstruct: its GEMM launches (ms: while profiling)
-    int debug_fail_in = 0;                   // cafe_debug_fail_next: the n-th next enqueue fails behind its K1 launch
+    int history_batches = 0, history_passes = 0;            // cafe_sample_histories: column batches, draw passes per batch of the last call
+    int debug_fail_in = 0;                  // cafe_debug_fail_next: the n-th next enqueue fails behind its K1 launch
 
     // last call
     std::vector<int> slot_of;               // [node*Kmax + k]
@@ -322,6 +323,8 @@ int reconstruct_impl(cafe_ctx* c, const cafe_params* pr, const float* root_prior
 int branch_probabilities_impl(cafe_ctx* c, const cafe_params* pr, const int32_t* sizes, double* out);
 // Marginal reconstruction: posterior sizes, intervals and branch change probabilities (marginal.hip)
 int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_marginal_out* out);
+// Ancestral histories drawn from the posterior of the same model (history.hip)
+int history_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_draws, uint64_t seed, const cafe_history_out* out);
 // Device-side p-values (pvalues.hip) and what it needs from cafe_create.hip and cafe_score.hip: a context over the same tree
 // whose family counts are written on the device, and the root-maximum prune of a context's families (-> d_fam_out, on stream s)
 constexpr int32_t kFlagDeviceCounts = 0x40000000;        // internal cafe_problem flag

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "cafe_call.h"
+#include "marginal_up.h"
 
 namespace cafe {
 
@@ -341,29 +342,6 @@ __global__ __launch_bounds__(256) void marginal_leaf_summary_kernel(const double
     out.hi[f] = hi < 0 ? last : hi;
 }
 
-// HIP-event brackets of the GEMM launches (cafe_set_profiling): summed after the call
-struct GemmTimer {
-    bool on = false;
-    std::vector<hipEvent_t> ev;
-    double flops = 0.0;
-    ~GemmTimer() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    void mark(hipStream_t s) {
-        if (!on) return;
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) { on = false; return; }
-        ev.push_back(e);
-        (void)hipEventRecord(e, s);
-    }
-    double total_ms() const {
-        double t = 0.0;
-        for (size_t i = 0; i + 1 < ev.size(); i += 2) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) t += ms;
-        }
-        return t;
-    }
-};
-
 // One GEMM launch between the timer's marks; share: the part of its K tiles that runs
 template <int MODE>
 int launch_gemm(cafe_ctx* c, const GemmParams& g, bool mul, hipStream_t s, GemmTimer& timer, double share = 1.0) {
@@ -379,6 +357,61 @@ int launch_gemm(cafe_ctx* c, const GemmParams& g, bool mul, hipStream_t s, GemmT
 }
 
 }  // namespace
+
+// dst = (src0) * the factors of `mult` (interior: stored F panels, leaves: gathered), rows 0..nrows-1
+int marginal_product(cafe_ctx* c, const UpPanels& w, const double* src0, double* dst, int nrows, const std::vector<int>& mult, int k, int64_t f0, int64_t ld,
+                     hipStream_t s) {
+    const unsigned gb = (unsigned)((ld + 255) / 256);
+    size_t i = 0;
+    bool started = false;
+    while (i < mult.size() || !started) {
+        ProdParams p{};
+        p.src0 = started ? dst : src0;
+        p.dst = dst; p.ld = ld; p.rows = nrows; p.ldp = c->pool.ld; p.err = w.err; p.n_dev = w.n_dev; p.M = c->M;
+        for (; i < mult.size(); ++i) {
+            const int m = mult[i];
+            if (c->leaf_taxon[m] >= 0) {
+                if (p.n_leaf == kMaxProd) break;
+                p.P[p.n_leaf] = leaf_matrix(c, m, k);
+                p.cnt[p.n_leaf] = leaf_counts(c, m, f0);
+                ++p.n_leaf;
+            } else {
+                if (p.n_pan == kMaxProd) break;
+                p.pan[p.n_pan++] = w.panel(w.F, m);
+            }
+        }
+        CAFE_LAUNCH(c, marginal_product_kernel, dim3(gb, (unsigned)((nrows + 15) / 16)), dim3(256), 0, s, p);
+        started = true;
+    }
+    return CAFE_OK;
+}
+
+// The up pass of category k over the columns f0 .. f0 + ld: children before parents (node order of the problem)
+int marginal_up_pass(cafe_ctx* c, const UpPanels& w, int k, int64_t f0, int64_t ld, hipStream_t s, GemmTimer& timer) {
+    const int M = c->M, R = c->R, n = c->n_nodes;
+    for (int p = 0; p < n; ++p) {
+        if (c->leaf_taxon[p] >= 0) continue;
+        const int np = p == c->root ? R : M;          // parent sizes 1..np
+        std::vector<int> leaves;
+        for (int v : c->children[p]) if (c->leaf_taxon[v] >= 0) leaves.push_back(v);
+        bool started = false;
+        if (!leaves.empty()) {
+            const int rc = marginal_product(c, w, nullptr, w.panel(w.B, p), np + 1, leaves, k, f0, ld, s);
+            if (rc != CAFE_OK) return rc;
+            started = true;
+        }
+        for (int v : c->children[p]) {
+            if (c->leaf_taxon[v] >= 0) continue;
+            GemmParams g{};
+            g.Pt = interior_matrix(c, v, k);
+            g.ldp = c->kpool.ld; g.X = w.panel(w.B, v); g.ld = ld; g.nr = np; g.nk = M + 1;
+            g.out1 = w.panel(w.F, v); g.out2 = w.panel(w.B, p);
+            if (const int rc = launch_gemm<kUp>(c, g, started, s, timer)) return rc;
+            started = true;
+        }
+    }
+    return CAFE_OK;
+}
 
 int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_marginal_out* out) {
     if (c->comm) { set_err(c, "cafe_marginal_reconstruct: not valid on a context with a communicator attached"); return CAFE_ERR_STATE; }
@@ -398,7 +431,10 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
     const int M = c->M, R = c->R, n = c->n_nodes, rows = c->N;      // a panel holds sizes 0..max(M, R)
     const bool has_err = pr->error_model != nullptr;
     const int n_dev = has_err ? c->n_dev : 1, n_tap = n_dev;
-    std::vector<int> bidx(n, -1), lidx(n, -1);
+    UpPanels up;
+    std::vector<int>& bidx = up.bidx;
+    std::vector<int> lidx(n, -1);
+    bidx.assign(n, -1);
     int nI = 0, nL = 0;
     for (int v = 0; v < n; ++v) { if (c->leaf_taxon[v] < 0) bidx[v] = nI++; else lidx[v] = nL++; }
 
@@ -444,6 +480,7 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
     }
     const double* d_prior = static_cast<const double*>(dprior.p);
     const double* d_err = has_err ? static_cast<const double*>(derr.p) : nullptr;
+    up.B = d_B; up.F = d_F; up.pstride = pstride; up.err = d_err; up.n_dev = n_dev;
 
     GemmTimer timer;
     timer.on = c->profile != 0;
@@ -455,56 +492,14 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
         const int64_t ld = std::min<int64_t>(cols, c->Fp - f0);
         const unsigned gb = (unsigned)((ld + 255) / 256);
         auto panel = [&](double* arena, int v) { return arena + (int64_t)bidx[v] * pstride; };
-        // dst = (src0) * the factors of `mult` (interior: stored F panels, leaves: gathered), rows 0..nrows-1
-        auto product = [&](const double* src0, double* dst, int nrows, const std::vector<int>& mult, int k) -> int {
-            size_t i = 0;
-            bool started = false;
-            while (i < mult.size() || !started) {
-                ProdParams p{};
-                p.src0 = started ? dst : src0;
-                p.dst = dst; p.ld = ld; p.rows = nrows; p.ldp = c->pool.ld; p.err = d_err; p.n_dev = n_dev; p.M = M;
-                for (; i < mult.size(); ++i) {
-                    const int w = mult[i];
-                    if (c->leaf_taxon[w] >= 0) {
-                        if (p.n_leaf == kMaxProd) break;
-                        p.P[p.n_leaf] = leaf_matrix(c, w, k);
-                        p.cnt[p.n_leaf] = leaf_counts(c, w, f0);
-                        ++p.n_leaf;
-                    } else {
-                        if (p.n_pan == kMaxProd) break;
-                        p.pan[p.n_pan++] = panel(d_F, w);
-                    }
-                }
-                CAFE_LAUNCH(c, marginal_product_kernel, dim3(gb, (unsigned)((nrows + 15) / 16)), dim3(256), 0, s, p);
-                started = true;
-            }
-            return CAFE_OK;
+        auto product = [&](const double* src0, double* dst, int nrows, const std::vector<int>& mult, int k) {
+            return marginal_product(c, up, src0, dst, nrows, mult, k, f0, ld, s);
         };
         for (int k = 0; k < K; ++k) {
             const double pk = gamma ? pr->cat_probs[k] : 1.0;
             const int first = k == 0;
-            // ---- up: children before parents (node order of the problem)
-            for (int p = 0; p < n; ++p) {
-                if (c->leaf_taxon[p] >= 0) continue;
-                const int np = p == c->root ? R : M;          // parent sizes 1..np
-                std::vector<int> leaves;
-                for (int w : c->children[p]) if (c->leaf_taxon[w] >= 0) leaves.push_back(w);
-                bool started = false;
-                if (!leaves.empty()) {
-                    const int rc = product(nullptr, panel(d_B, p), np + 1, leaves, k);
-                    if (rc != CAFE_OK) return rc;
-                    started = true;
-                }
-                for (int v : c->children[p]) {
-                    if (c->leaf_taxon[v] >= 0) continue;
-                    GemmParams g{};
-                    g.Pt = interior_matrix(c, v, k);
-                    g.ldp = c->kpool.ld; g.X = panel(d_B, v); g.ld = ld; g.nr = np; g.nk = M + 1;
-                    g.out1 = panel(d_F, v); g.out2 = panel(d_B, p);
-                    if (const int rc = launch_gemm<kUp>(c, g, started, s, timer)) return rc;
-                    started = true;
-                }
-            }
+            // ---- up: children before parents (marginal_up_pass, shared with cafe_sample_histories)
+            if (const int rc = marginal_up_pass(c, up, k, f0, ld, s, timer)) return rc;
             // ---- root, then parents before children
             CAFE_LAUNCH(c, marginal_root_kernel, dim3(gb, (unsigned)((R + 1 + 15) / 16)), dim3(256), 0, s, panel(d_B, c->root), d_prior, R, ld, panel(d_O, c->root),
                         panel(d_A, c->root), pk, first);

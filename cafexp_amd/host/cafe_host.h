@@ -273,6 +273,20 @@ struct marginal_result {
 void write_marginal_reports(const marginal_result& res, const std::string& model_identifier, const std::string& dir,
                             const std::vector<const clade*>& order, const std::vector<gene_family>& families);
 
+// cafe_sample_histories' counts, [draw][index in the caller's node order] (failed: [family])
+struct history_result {
+    size_t n_draws = 0, n_nodes = 0;
+    uint64_t seed = 0;
+    std::vector<int64_t> n_increase, n_decrease, net_change;
+    std::vector<int32_t> failed;
+    size_t failed_count() const { size_t k = 0; for (int32_t f : failed) k += f != 0; return k; }
+};
+// <Model>_sampled_change.tab: one row per node of `order`; for the number of families that expanded / contracted on the
+// branch above it and the net change in genes, the mean across the draws and the equal-tailed interval at `level` on the
+// draws' empirical CDF (the marginal reports' rule: lo = the least value whose CDF reaches (1 - level) / 2, hi likewise)
+void write_history_reports(const history_result& res, double level, const std::string& model_identifier, const std::string& dir,
+                           const std::vector<const clade*>& order);
+
 // The two models whose infer_family_likelihoods runs on the GPU through the C ABI.
 class hip_model_base : public model {
 protected:
@@ -315,6 +329,10 @@ public:
     // expanded / contracted -- with the model's lambda, prior, error model and (gamma) categories; columns in `order`
     marginal_result marginal_reconstruction(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, double level,
                                             const std::vector<const clade*>& order);
+    // Whole ancestral histories drawn from the same posterior (cafe_sample_histories), counted per draw on the device:
+    // how many families expanded / contracted on every branch and the net change, rows in `order`
+    history_result sample_histories(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, int n_draws, uint64_t seed,
+                                    const std::vector<const clade*>& order);
 protected:
     // gamma model: multipliers, category probabilities and alpha of the mixture; the base model leaves them empty
     virtual void category_parameters(std::vector<double>&, std::vector<double>&, double&) const {}

@@ -133,6 +133,67 @@ void write_marginal_reports(const marginal_result& res, const std::string& model
     }
 }
 
+history_result hip_model_base::sample_histories(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, int n_draws, uint64_t seed,
+                                                const std::vector<const clade*>& order) {
+    std::vector<double> mult, probs;
+    double alpha = 0;
+    category_parameters(mult, probs, alpha);
+    const int K = mult.empty() ? 1 : (int)mult.size();
+    ensure_context(K);
+    std::vector<float> prior_f;
+    std::vector<double> err, lambdas;
+    gather_call_inputs(prior, rootdist, prior_f, err, lambdas);
+    cafe_params pr{};
+    pr.model = mult.empty() ? CAFE_MODEL_BASE : CAFE_MODEL_GAMMA;
+    pr.lambdas = lambdas.data(); pr.n_categories = K;
+    pr.multipliers = mult.empty() ? nullptr : mult.data();
+    pr.cat_probs = probs.empty() ? nullptr : probs.data();
+    pr.alpha = alpha; pr.prior = prior_f.data(); pr.error_model = err.empty() ? nullptr : err.data();
+    if (n_draws < 1) throw std::runtime_error("cafe_sample_histories: the number of draws must be positive");
+    const size_t n = _order.size(), D = (size_t)n_draws;
+    std::vector<int64_t> inc(D * n), dec(D * n), net(D * n);
+    history_result res;
+    res.n_draws = D; res.n_nodes = order.size(); res.seed = seed;
+    res.failed.resize(_p_gene_families->size());
+    cafe_history_out out{};
+    out.n_increase = inc.data(); out.n_decrease = dec.data(); out.net_change = net.data(); out.failed = res.failed.data();
+    if (cafe_sample_histories(_ctx, &pr, n_draws, seed, &out) != CAFE_OK)
+        throw std::runtime_error(std::string("cafe_sample_histories: ") + cafe_last_error(_ctx));
+    std::map<const clade*, size_t> pos;
+    for (size_t v = 0; v < n; ++v) pos[_order[v]] = v;
+    const size_t m = order.size();
+    res.n_increase.resize(D * m); res.n_decrease.resize(D * m); res.net_change.resize(D * m);
+    for (size_t d = 0; d < D; ++d)
+        for (size_t i = 0; i < m; ++i) {
+            const size_t src = d * n + pos.at(order[i]), dst = d * m + i;
+            res.n_increase[dst] = inc[src]; res.n_decrease[dst] = dec[src]; res.net_change[dst] = net[src];
+        }
+    return res;
+}
+
+void write_history_reports(const history_result& res, double level, const std::string& model_identifier, const std::string& dir,
+                           const std::vector<const clade*>& order) {
+    const std::string prefix = (dir.empty() ? std::string("results") : dir) + "/" + model_identifier;
+    std::ofstream f(prefix + "_sampled_change.tab");
+    f << "#Node\tn_increase\tn_decrease\tnet_change\t(mean:lo-hi over " << res.n_draws << " draws, level " << level << ", seed " << res.seed << ")" << std::endl;
+    char buf[160];
+    const size_t m = order.size(), D = res.n_draws;
+    std::vector<int64_t> col(D);
+    for (size_t v = 0; v < m; ++v) {
+        f << clade_index_or_name(order[v], order);
+        for (const std::vector<int64_t>* a : {&res.n_increase, &res.n_decrease, &res.net_change}) {
+            double sum = 0;
+            for (size_t d = 0; d < D; ++d) { col[d] = (*a)[d * m + v]; sum += (double)col[d]; }
+            std::sort(col.begin(), col.end());
+            // the least value whose empirical CDF (rank / D) reaches the threshold
+            auto at = [&](double thr) { size_t r = 0; while (r + 1 < D && (double)(r + 1) / (double)D < thr) ++r; return col[r]; };
+            std::snprintf(buf, sizeof buf, "\t%.6g:%lld-%lld", sum / (double)D, (long long)at(0.5 * (1.0 - level)), (long long)at(1.0 - 0.5 * (1.0 - level)));
+            f << buf;
+        }
+        f << std::endl;
+    }
+}
+
 reconstruction* hip_base_model::reconstruct_ancestral_states(const std::vector<gene_family>& families, root_equilibrium_distribution* p_prior) {
     const std::vector<int32_t> states = device_reconstruct(families, p_prior, nullptr);
     auto result = new base_model_reconstruction();

@@ -28,6 +28,10 @@ static void usage() {
         "                  [--reconstruct-marginal [LEVEL]]   posterior size of every node under the fitted model: mean, mode, equal-tailed\n"
         "                  interval at LEVEL (default 0.95), probability that each branch contracted / expanded; with -o:\n"
         "                  <Model>_posterior_sizes.tab (mean:mode:lo-hi) and <Model>_posterior_change.tab (p_decrease:p_increase); one GPU\n"
+        "                  [--sample-histories N [--sample-seed S]]   N whole ancestral histories per family drawn from the posterior of the\n"
+        "                  fitted model (seed S, else -s, else 1); with -o: <Model>_sampled_change.tab, per node the mean and the equal-tailed\n"
+        "                  interval (LEVEL of --reconstruct-marginal, default 0.95) across the draws of how many families expanded /\n"
+        "                  contracted on its branch and of the net change in genes; one GPU\n"
         "  --gpus N: the scorer calls shard the families over devices 0..N-1 (one host thread per GPU, one RCCL all-reduce per call)\n"
         "lambda per family (the reference's -b): cafexp_hip -t TREE -i FAMILIES -b [-y LAMBDA_TREE] [-e ERRMODEL] [-p [L]] [-z] [-s SEED] [-I MAXITER]\n"
         "                  [--workspace BYTES] [-o OUTDIR]   writes OUTDIR (default results)/Base_lambda_per_family.txt, one line per family\n"
@@ -153,6 +157,9 @@ int main(int argc, char** argv) {
     bool do_reconstruct = false, pvalues_on_device = false;
     bool do_marginal = false;                                    // --reconstruct-marginal [LEVEL]
     double marginal_level = 0.95;
+    int history_draws = 0;                                       // --sample-histories N
+    bool do_histories = false, have_history_seed = false;
+    uint64_t history_seed = 1;                                   // --sample-seed S; else -s; else this
     double test_pvalue = 0.05;                                   // input_parameters::pvalue default (io.h)
     long limit = -1;
     double fixed_lambda = 0, fixed_alpha = -1, poisson = 0;
@@ -198,6 +205,8 @@ int main(int argc, char** argv) {
         }
         else if (a == "--reconstruct") do_reconstruct = true;
         else if (a == "--reconstruct-marginal") { do_marginal = true; std::string v = optional(); if (!v.empty()) marginal_level = std::stod(v); }
+        else if (a == "--sample-histories") { do_histories = true; history_draws = std::stoi(next()); }
+        else if (a == "--sample-seed") { history_seed = std::stoull(next()); have_history_seed = true; }
         else if (a == "-P") test_pvalue = std::stod(next());
         else if (a == "--pvalues-device") pvalues_on_device = true;
         else if (a == "--pvalues") pvalue_sims = std::stoi(next());
@@ -234,6 +243,15 @@ int main(int argc, char** argv) {
         else if (per_family) why = "--reconstruct-marginal needs one fitted model: -b is not supported with it";
         else if (!(marginal_level > 0 && marginal_level < 1)) why = "--reconstruct-marginal: LEVEL must lie in (0, 1)";
         if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
+    }
+    if (do_histories) {
+        const char* why = nullptr;
+        if (gpus_given) why = "--sample-histories runs on one GPU: --gpus is not supported with it";
+        else if (per_family) why = "--sample-histories needs one fitted model: -b is not supported with it";
+        else if (history_draws < 1 || history_draws > 65536) why = "--sample-histories: N must lie in 1..65536";
+        else if (!(marginal_level > 0 && marginal_level < 1)) why = "--sample-histories: LEVEL must lie in (0, 1)";
+        if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
+        if (!have_history_seed && have_seed) history_seed = seed;
     }
     if (per_family) {                                            // what -b cannot be combined with: refused before anything is read or written
         const char* why = nullptr;
@@ -459,6 +477,18 @@ int main(int argc, char** argv) {
             marginal_failed = mr.failed_count();
             if (!out_dir.empty()) write_marginal_reports(mr, mdl->name(), out_dir, order, d.gene_families);
         }
+        // histories drawn from the same posterior, counted per draw: independent of the two reconstructions
+        double history_s = 0;
+        size_t history_failed = 0;
+        if (do_histories) {
+            auto t0 = std::chrono::steady_clock::now();
+            cladevector order;
+            d.p_tree->apply_reverse_level_order([&order](const clade* c) { order.push_back(c); });
+            const history_result hr = mdl->sample_histories(d.p_prior.get(), d.rootdist, history_draws, history_seed, order);
+            history_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            history_failed = hr.failed_count();
+            if (!out_dir.empty()) write_history_reports(hr, marginal_level, mdl->name(), out_dir, order);
+        }
         std::printf("{\"model\": \"%s\", ", mdl->name().c_str());
         print_num("neg_lnl", score);
         std::printf("\"n_families\": %zu, \"max_family_size\": %d, \"max_root_family_size\": %d, \"seconds_per_call\": %.6f, ",
@@ -494,6 +524,8 @@ int main(int argc, char** argv) {
             std::printf(", \"reconstruct\": {\"seconds\": %.3f, \"families_with_branch_probabilities\": %zu}", reconstruct_s, n_with_probs);
         if (do_marginal)
             std::printf(", \"marginal\": {\"seconds\": %.3f, \"level\": %.17g, \"failed\": %zu}", marginal_s, marginal_level, marginal_failed);
+        if (do_histories)
+            std::printf(", \"histories\": {\"seconds\": %.3f, \"draws\": %d, \"failed\": %zu}", history_s, history_draws, history_failed);
         std::printf("}\n");
     } catch (const std::exception& e) {
         std::fprintf(stderr, "cafexp_hip: %s\n", e.what());

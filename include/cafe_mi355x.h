@@ -365,6 +365,42 @@ int cafe_marginal_reconstruct(cafe_ctx* ctx, const cafe_params* params, double l
  * (cafe_set_profiling), their summed HIP-event time in milliseconds (else 0) */
 int cafe_debug_marginal_gemm(cafe_ctx* ctx, double* ms, double* flops);
 
+/* Ancestral histories drawn from the posterior of the model of cafe_marginal_reconstruct (the scorer's: leaf vectors with
+ * the error model's taps, interior sizes 0..M, root sizes 1..R under the float prior, gamma categories): n_draws whole
+ * assignments of a size to every node of every family, for statements about several nodes or families at once.  With B the
+ * up-pass vector of a node, P its branch's matrix and u(f, v, s) the Philox uniform of (family f, node v, stream s) keyed
+ * by `seed`, draw d of family f takes
+ *   the category: the first k over cat_probs[k] Z_k, Z_k = sum_s prior[s-1] B_root^k[s], with u(f, root, 2d+1) (0: base model);
+ *   the root: the first s in 1..R over prior[s-1] B_root^k[s], with u(f, root, 2d);
+ *   a node v whose parent drew i: the first j in 0..M over P_v^k[i][j] B_v^k[j], with u(f, v, 2d) (a parent at 0 gives 0);
+ *   a leaf: its observed count, or with an error model the first tap c over err[x][t] P_v^k[i][c], with u(f, v, 2d);
+ * "first" = the first index whose inclusive prefix sum is >= u * (sum of all weights); an all-zero range gives its first
+ * index.  f is the family's index in the problem's table: identical families draw different histories.  The result is a
+ * function of the arguments only (not of workspace_limit, batches or the device).  Outputs (host pointers, any may be NULL):
+ *   sizes [n_draws][n_families][n_nodes] and category [n_draws][n_families] in the problem's orders;
+ *   n_increase / n_decrease [n_draws][n_nodes]: the families of a draw with X_v > / < X_parent(v); net_change: the sum over
+ *     the families of X_v - X_parent(v); 0 at the root.  They are counted on the device: with sizes = NULL nothing of size
+ *     n_draws * n_families * n_nodes is moved;
+ *   log_evidence, failed [n_families] as cafe_marginal_reconstruct: a failed family (Z = 0 or not finite) has sizes and
+ *     category -1 and adds nothing to the counts.
+ * Reads model, lambdas, n_categories, multipliers, cat_probs, prior and error_model of params; the context's death rates
+ * apply.  CAFE_ERR_ARGUMENT for invalid rates, a bad K or n_draws outside 1..65536; CAFE_ERR_STATE on a context with a
+ * communicator attached.  cafe_family_results is not meaningful after this call; a later cafe_score is unaffected. */
+typedef struct cafe_history_out {
+    int32_t* sizes;
+    int32_t* category;
+    int64_t* n_increase;
+    int64_t* n_decrease;
+    int64_t* net_change;
+    double*  log_evidence;
+    int32_t* failed;
+} cafe_history_out;
+int cafe_sample_histories(cafe_ctx* ctx, const cafe_params* params, int32_t n_draws, uint64_t seed,
+                          const cafe_history_out* out);
+/* diagnostics: how the last cafe_sample_histories cut its work under the workspace budget -- the column batches of the
+ * unique families and the passes over the draws that each batch took */
+int cafe_debug_history_batches(cafe_ctx* ctx, int32_t* column_batches, int32_t* draw_passes);
+
 /* Introspection for parity tests: the transition matrix the last call built for the branch above
  * `node` in category k (N x N row-major, N = max(M,R)+1: matrix_cache::get_matrix; for an interior
  * branch the columns c > M, which the prune never reads, are not materialised and come back 0), and the root
