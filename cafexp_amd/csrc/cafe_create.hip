@@ -55,7 +55,7 @@ Switches read_switches(cafe_ctx* c) {
     sw.no_kskip = std::getenv("CAFE_NO_KSKIP");              // no matrix or panel extents: every K tile of every launch
     sw.no_leaf_t = std::getenv("CAFE_NO_LEAF_T");            // no transposed leaf matrices for the assemble passes
     sw.lt_min = (e = std::getenv("CAFE_LEAF_T_MIN")) ? atof(e) : 6.0;   // a leaf branch gets one when its passes write >= lt_min N columns
-    sw.kb = (e = std::getenv("CAFE_KB")) ? (std::atoi(e) == 16 ? 16 : 8) : 0;   // depth of K2's K tiles, 8 or 16
+    sw.kb = (e = std::getenv("CAFE_KB")) ? (std::atoi(e) == 16 ? 16 : std::atoi(e) == 12 ? 12 : 8) : 0;   // depth of K2's K tiles: 8, 12 or 16
     sw.gemm_stamps = std::getenv("CAFE_GEMM_STAMPS");        // per-workgroup block timeline of a K2 launch (cafe_debug_stamps)
     sw.dump_schedule = std::getenv("CAFE_DUMP_SCHEDULE");    // the launch list with its column counts, on stderr
     if ((e = std::getenv("CAFE_GEMM_STAMPS_LAUNCH"))) c->stamps_launch = std::atol(e);   // stamps of that K2 launch only
@@ -206,8 +206,9 @@ void plan_pools(cafe_ctx* c, int kb) {
         for (int k = 0; k < c->Kmax; ++k) c->slot_of[(size_t)v * c->Kmax + k] = k * c->n_pairs[layout] + c->pair_of[v];
     }
     // small matrices (a K2 launch is one round of tiles and lasts as long as one tile): 16-deep K tiles, half as many DMA
-    // round trips per tile; otherwise 8-deep ones, four workgroups per CU
-    c->kb = kb ? kb : (c->N < 256 ? 16 : 8);
+    // round trips per tile; otherwise 12-deep ones: still four workgroups per CU, a third fewer barriers per MFMA than 8-deep
+    // ones (config 4: 130.4 against 133.6 ms per call)
+    c->kb = kb ? kb : (c->N < 256 ? 16 : 12);
     // likelihood panels: rows padded so that every panel can be a GEMM B operand (kc rows) or the root (R rows)
     // a factor GEMM stores transposed, [column][16 - out_off + panel row] (prune_gemm.hip): factor_ld rows per column, and a
     // panel slot must be able to hold a factor of as many columns

@@ -14,8 +14,9 @@ namespace cafe {
 // Flops the K2 launches of the last (profiled) call EXECUTED: a (row tile, column tile) pair runs only the K tiles inside
 // matrix extent x panel extent, so read the extents this call published and count, per launch, what its tiles ran.  Reads
 // the extents back (a few synchronous copies, milliseconds of host work): for measurement, once, not per call.
-// per_block: count a row block only over the K tiles inside its own extent (what the kernel issues); false: every block over
-// its tile's whole K range (the count of rounds 2 and 3a, kept for comparison)
+// per_block: count a row block only over the k-steps (4 deep) inside its own extent and the panel's (what the kernel issues,
+// prune_gemm.hip block_ranges); false: every block over its tile's whole K range (the count of rounds 2 and 3a, kept for
+// comparison).  Both count the valid k and rows only (a ragged last k-step counts its k <= M, a ragged last block its rows).
 double count_executed_flops(cafe_ctx* c, std::vector<double>* per_launch, bool per_block) {
     if (c->gemm_launches_info.empty()) return c->stats.gemm_flops;
     const int kBK = c->kb;
@@ -49,22 +50,27 @@ double count_executed_flops(cafe_ctx* c, std::vector<double>* per_launch, bool p
                         for (int b = row0 / 16; b < row0 / 16 + mi && b < nb; ++b) { alo = std::min(alo, e[2 * b]); ahi = std::max(ahi, e[2 * b + 1]); }
                     }
                     for (int ct = 0; ct < (have_b ? n_ct : 1); ++ct) {
-                        int lo = alo, hi = ahi;
-                        if (have_b) { lo = std::max(lo, bext[((size_t)k * n_ct + ct) * 2]); hi = std::min(hi, bext[((size_t)k * n_ct + ct) * 2 + 1]); }
+                        int lo = alo, hi = ahi, plo = 0, phi = c->M;
+                        if (have_b) {
+                            plo = bext[((size_t)k * n_ct + ct) * 2]; phi = std::min(c->M, bext[((size_t)k * n_ct + ct) * 2 + 1]);
+                            lo = std::max(lo, plo); hi = std::min(hi, phi);
+                            if (bext[((size_t)k * n_ct + ct) * 2 + 1] < plo) { plo = 0; phi = 0; }      // an empty panel extent: row 0 (extents.hip)
+                        }
                         if (hi < lo) { lo = 0; hi = 0; }
                         hi = std::min(hi, c->M);
-                        // the tile runs K tiles lo/kb .. hi/kb; its row block b issues MFMAs only in those inside ITS OWN extent
-                        // (prune_gemm.hip, block_ranges); the last K tile of the matrix is ragged
+                        // the tile runs K tiles lo/kb .. hi/kb; its row block b issues MFMAs only in the k-steps that meet ITS OWN
+                        // extent cut by the panel's (prune_gemm.hip, block_ranges); the last k-step of the matrix is ragged
                         const int t_lo = lo / kBK, t_hi = hi / kBK;
                         for (int b = row0 / 16; b < row0 / 16 + mi && b * 16 < rows; ++b) {
-                            int b_lo = t_lo, b_hi = t_hi;
+                            int kk;
                             if (e && per_block) {
-                                if (b >= nb || e[2 * b + 1] < e[2 * b]) continue;
-                                b_lo = std::max(t_lo, e[2 * b] / kBK);
-                                b_hi = std::min(t_hi, e[2 * b + 1] / kBK);
+                                if (b >= nb) continue;
+                                const int s_lo = std::max(e[2 * b], plo), s_hi = std::min(e[2 * b + 1], phi);
+                                if (s_hi < s_lo) continue;
+                                kk = std::min((s_hi / 4 - s_lo / 4 + 1) * 4, c->M + 1 - s_lo / 4 * 4);
+                            } else {
+                                kk = std::min((t_hi - t_lo + 1) * kBK, c->M + 1 - t_lo * kBK);
                             }
-                            if (b_hi < b_lo) continue;
-                            const int kk = std::min((b_hi - b_lo + 1) * kBK, c->M + 1 - b_lo * kBK);
                             executed += 2.0 * std::min(16, rows - b * 16) * (double)kk * (have_b ? (double)kBN : (double)cols);
                         }
                     }

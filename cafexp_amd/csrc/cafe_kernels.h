@@ -18,8 +18,11 @@ constexpr int kMaxLeafPerOp = 4;     // leaf children folded by one gather launc
 // GEMM tiling (fp64 MFMA 16x16x4): block tile (16*MI) x 128, K step 16, 4 waves side by side in N
 constexpr int kBN = 128;
 constexpr int kBK = 16;          // largest depth of a K tile (panel / matrix row counts are rounded to it); a context runs K2 with 16-deep
-                                 // K tiles (small matrices: a launch is one round of tiles, fewer DMA round trips per tile) or 8-deep ones
-                                 // (half the LDS per stage: four workgroups per CU) -- GemmArgs::kb
+                                 // K tiles (small matrices: a launch is one round of tiles, fewer DMA round trips per tile), 8-deep ones
+                                 // (half the LDS per stage: four workgroups per CU) or 12-deep ones (still four: 39 936 bytes each, a
+                                 // third fewer barriers per MFMA) -- GemmArgs::kb.  A 12-deep last K tile may stage rows past the
+                                 // rounded count: the buffer descriptors end at the matrix / the panel category, the DMA reads zeros or
+                                 // the neighbour's rows there, and no MFMA uses them (only k-steps with a valid k run)
 constexpr int kMaxBM = 144;          // largest row tile (MI = 9)
 
 // Per transition matrix: a = lambda_q t_q / (1 + lambda_q t_q) of the de-quantized key
@@ -168,7 +171,7 @@ struct GemmArgs {
     const GemmOp* ops;              // the group's descriptors (device memory)
     int32_t n_ops;
     int32_t k_valid;                // contraction extent M+1
-    int32_t kb;                     // depth of a K tile: 8 or 16
+    int32_t kb;                     // depth of a K tile: 8, 12 or 16
     int32_t mi;                     // row tile = 16*mi, the same for every op of the launch
     int32_t n_categories;
     int32_t uniform_ld;             // > 0 (several column chunks, one column per family): columns of every panel in this chunk;
@@ -209,10 +212,10 @@ struct PlanLaunch {
 constexpr int kPlanSlack = 2;       // spare list entries per workgroup (the planner's last rounds are dealt as one batch)
 // max_rounds: the longest PlanLaunch::rounds of the launches (the planner's grid depth)
 hipError_t launch_tile_plan(const PlanLaunch* d_launches, int n_launches, int max_rounds, hipStream_t stream);
-// Workgroups of K2 resident on a CU.  Row tiles of up to 80 rows: four with 8-deep K tiles (26 KB of LDS each, 128 vector
-// registers), three with 16-deep ones (52 KB with an unpadded B tile, <= 168 registers); the taller ones: two (<= 250
+// Workgroups of K2 resident on a CU.  Row tiles of up to 80 rows: four with 8- and 12-deep K tiles (26 / 39 KB of LDS each: four
+// times 39 936 bytes, allocated in 1 280-byte granules, are exactly a CU's 160 KB; 128 vector registers), three with 16-deep ones (52 KB with an unpadded B tile, <= 168 registers); the taller ones: two (<= 250
 // registers).
-constexpr int prune_gemm_wg_per_cu(int mi, int kb) { return mi <= 5 ? (kb <= 8 ? 4 : 3) : 2; }
+constexpr int prune_gemm_wg_per_cu(int mi, int kb) { return mi <= 5 ? (kb <= 12 ? 4 : 3) : 2; }
 constexpr int kPlanLanes = 128;     // workgroups of an XCD the tile planner can deal to (32 CUs x 3 = 96 on MI355X)
 // workgroups of a K2 launch (a multiple of 8) whose busiest XCD owns `tiles_xcd0` tiles: as many as are resident, fewer when there are fewer tiles
 int prune_gemm_blocks(int64_t tiles_xcd0, int n_cu, int mi, int kb);

@@ -29,7 +29,8 @@
 //    MFMA stream is therefore written to need almost no VALU: uniform bases in SGPRs + one 32-bit
 //    per-lane offset, compile-time specialised epilogues, no per-element branches;
 //  * the accumulator array must only be indexed by compile-time constants, or it is demoted to
-//    scratch memory (5x slower).  `make check` fails the build if a K2 instantiation uses scratch.
+//    scratch memory (5x slower).  `make check` fails the build if a K2 instantiation spills more than 8 vector registers
+//    or uses more than 64 bytes of scratch.
 #include <algorithm>
 #include <type_traits>
 
@@ -55,8 +56,8 @@
 // matrix tiles (A), the child panel's K tiles (B, LDS-DMA both) and the stores of the output panel (C).  Measured at config 4
 // (one process per build, K2 per call): everything 0 117.4-117.8 ms; B loads nt 122.3; A loads nt
 // 128.1 (both streams live on their L2 hits); C stores nt 117.0-117.5; C stores nt + sc1 116.9; C stores sc1 117.7.  The
-// output panel is written once and read again a launch later from HBM whatever the policy, so the variants with 8-deep
-// K tiles (matrix orders >= 256, where a panel is far larger than the L2s) store it non-temporal and leave the L2s to A and
+// output panel is written once and read again a launch later from HBM whatever the policy, so the variants with 8- and
+// 12-deep K tiles (matrix orders >= 256, where a panel is far larger than the L2s) store it non-temporal and leave the L2s to A and
 // B; the small-order variants keep the default (their whole panel fits the L2s and the next launch reads it from there).
 #ifndef CAFE_K2_A_LOAD_AUX
 #define CAFE_K2_A_LOAD_AUX 0
@@ -65,10 +66,10 @@
 #define CAFE_K2_B_LOAD_AUX 0
 #endif
 #ifndef CAFE_K2_MUL_LOAD_AUX
-#define CAFE_K2_MUL_LOAD_AUX (KB == 8 ? 2 : 0)   // the parent panel's old values in multiply mode: read once, then overwritten (116.62 -> 116.40 ms, three alternating runs)
+#define CAFE_K2_MUL_LOAD_AUX (KB <= 12 ? 2 : 0)   // the parent panel's old values in multiply mode: read once, then overwritten (116.62 -> 116.40 ms, three alternating runs)
 #endif
 #ifndef CAFE_K2_C_STORE_AUX
-#define CAFE_K2_C_STORE_AUX (KB == 8 ? 2 : 0)
+#define CAFE_K2_C_STORE_AUX (KB <= 12 ? 2 : 0)
 #endif
 
 namespace cafe {
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(256, prune_gemm_wg_per_cu(MI, KB)) void prune_gemm_
     unsigned long long st0 = 0, ep_ticks = 0, n_done = 0, loop_ticks = 0, kt_done = 0, t_tile = 0;
     if (a.stamps) st0 = __builtin_amdgcn_s_memrealtime();
 
-    // ---- persistent tile loop.  The grid is 2 workgroups per CU; a workgroup walks a fixed list of output
+    // ---- persistent tile loop.  The grid is 2 to 4 workgroups per CU (prune_gemm_wg_per_cu); a workgroup walks a fixed list of output
     // tiles so that the first K tile of the next output tile is already being fetched while the current one
     // is finished and stored: no per-tile launch gap or cold prologue.  XCD-aware order (speed only): blocks
     // b and b+8 share an XCD under round-robin dispatch, so XCD x owns the (category, column tile) pairs
@@ -132,7 +133,9 @@ __global__ __launch_bounds__(256, prune_gemm_wg_per_cu(MI, KB)) void prune_gemm_
     constexpr bool A_CONTIG = (SA == BM);
     constexpr int NS = KB / 4;                    // k-steps of a K tile = DMA "quarters" of a stage (4 k-rows each, one per wave)
     constexpr int SLOTS = 4 * NS;
-    constexpr int NP = KB * BM / 128, PER = (NP + SLOTS - 1) / SLOTS;     // 1 KB pieces of the contiguous [KB][BM] A image
+    // 1 KB pieces of the contiguous [KB][BM] A image.  Where the image is no whole number of them (12-deep tiles: 7.5 at 80 rows)
+    // the last piece starts half a piece early and overlaps its neighbour: the same bytes, written twice.
+    constexpr int IMG = KB * BM, NP = (IMG + 127) / 128, PER = (NP + SLOTS - 1) / SLOTS;
     unsigned a_voff[NS][PER > 0 ? PER : 1];      // bytes
     int a_dst[NS][PER > 0 ? PER : 1];
     if (A_CONTIG) {
@@ -140,17 +143,17 @@ __global__ __launch_bounds__(256, prune_gemm_wg_per_cu(MI, KB)) void prune_gemm_
         for (int q = 0; q < NS; ++q)
 #pragma unroll
             for (int j = 0; j < PER; ++j) {
-                int piece = q * 4 + wave + SLOTS * j;          // scalar
-                while (piece >= NP) piece -= NP;               // (scalar; at most twice: NP >= 6)
-                // element e = 128*piece + 2*lane of the [16][BM] image -> (k-row, column).  128*piece splits on
-                // the scalar unit; adding 2*lane (<= 126 < 2*BM as BM >= 64) wraps at most twice
-                const int r0s = (piece * 128) / BM, c0s = (piece * 128) % BM;
+                const int piece = std::min(q * 4 + wave + SLOTS * j, NP - 1);     // scalar (slots >= NP move nothing: stage_quarter)
+                const int e0 = std::min(piece * 128, IMG - 128);
+                // element e = e0 + 2*lane of the [KB][BM] image -> (k-row, column).  e0 splits on the scalar unit; adding
+                // 2*lane (<= 126 < 2*BM as BM >= 64) wraps at most twice
+                const int r0s = e0 / BM, c0s = e0 % BM;
                 int c = c0s + lane * 2, r = r0s;
                 if (c >= BM) { c -= BM; r += 1; }
                 if (c >= BM) { c -= BM; r += 1; }
                 if (BM < 64 && c >= BM) { c -= BM; r += 1; }        // (48-row tiles: 126 < 3 * 48)
                 a_voff[q][j] = (unsigned)((r * lda + c) * 8);
-                a_dst[q][j] = piece * 128;
+                a_dst[q][j] = e0;
             }
     }
     const unsigned lane16 = (unsigned)(lane * 16);
@@ -202,8 +205,8 @@ __global__ __launch_bounds__(256, prune_gemm_wg_per_cu(MI, KB)) void prune_gemm_
     };
     // LDS-DMA fill of K tile k0 of output tile x into stage `buf`, quarter q (16 slots = 4 quarters x 4 waves).
     // B: k-row `slot` is one 1 KB piece.  A: with SA == BM the [16][BM] image is contiguous, 2*MI pieces of 1 KB
-    // laid end to end (a piece may span two k-rows); slot s moves pieces s, s+16, ... and wraps, re-writing an
-    // identical piece rather than branching.  With a padded row (even MI) each k-row is moved on its own with
+    // laid end to end (a piece may span two k-rows); slot s moves pieces s, s + SLOTS, ...; a wave whose slot lies past the
+    // last piece moves nothing (a scalar branch).  With a padded row (even MI) each k-row is moved on its own with
     // the tail lanes masked off.  buffer_load ... lds: descriptor + scalar offset + fixed lane offset, no VALU.
     auto stage_quarter = [&](const Tile& x, int k0, int buf, int q) {
         double* As = lds + buf * STAGE;
@@ -213,7 +216,8 @@ __global__ __launch_bounds__(256, prune_gemm_wg_per_cu(MI, KB)) void prune_gemm_
             const int soff = (k0 * lda + CAFE_EXPERIMENT_A_ROW(x.row0)) * 8;
 #pragma unroll
             for (int j = 0; j < PER; ++j)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(x.rsA, (lptr_t)(As + a_dst[q][j]), 16, a_voff[q][j], soff, 0, CAFE_K2_A_LOAD_AUX);
+                if (q * 4 + SLOTS * j + 3 < NP || q * 4 + wave + SLOTS * j < NP)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(x.rsA, (lptr_t)(As + a_dst[q][j]), 16, a_voff[q][j], soff, 0, CAFE_K2_A_LOAD_AUX);
         } else {
             constexpr int nl = BM >= 128 ? 64 : BM / 2;
             if (nl == 64 || lane < nl)
@@ -222,12 +226,15 @@ __global__ __launch_bounds__(256, prune_gemm_wg_per_cu(MI, KB)) void prune_gemm_
         __builtin_amdgcn_raw_ptr_buffer_load_lds(x.rsB, (lptr_t)(Bs + krow * kBStride), 16, lane16, ((k0 + krow) * x.ldb + CAFE_EXPERIMENT_B_COLUMN(x.col0)) * 8, 0, CAFE_K2_B_LOAD_AUX);
     };
 
-    // Which of the tile's MI row blocks take part in K tile kt of its range: block i only inside ITS OWN matrix extent (the tile's
-    // range is the hull of them, cut by the panel's extent).  The band of a transition matrix moves down by 16 rows per block, so
-    // the first K tiles of a range meet only the upper blocks and the last ones only the lower blocks -- a tenth of the MFMAs of
-    // a config-4 call multiply a zero block of A; leaving them out changes no accumulator bit.  All scalar.
+    // Which of the tile's MI row blocks take part in k-step ks (4 deep, counted from the first one of the tile's range): block i
+    // only where k lies inside ITS OWN matrix extent and inside the panel's extent (the tile's range is the hull of those, in
+    // whole K tiles).  The band of a transition matrix moves down by 16 rows per block, so the first k-steps of a range meet
+    // only the upper blocks and the last ones only the lower blocks -- a tenth of the MFMAs of a config-4 call multiply a zero
+    // block of A; leaving them out changes no accumulator bit.  The same rule at every depth of a K tile, so the MFMAs issued
+    // do not depend on it; and no MFMA reads a panel row outside the panel's extent rounded to k-steps -- rows the assemble pass
+    // may have left unwritten (it writes the extent rounded to 16 rows, which 12-deep K tiles overhang).  All scalar.
     typedef const __attribute__((address_space(4))) int32_t* ext_cptr_t;
-    struct Blocks { int lo[MI], hi[MI]; };                  // K tiles relative to the tile's first one; lo > hi: never
+    struct Blocks { int lo[MI], hi[MI]; };                  // k-steps relative to the tile's first one; lo > hi: never
     auto block_ranges = [&](const Tile& x) -> Blocks {
         Blocks b;
         if (!a.pool.ext) {
@@ -235,21 +242,28 @@ __global__ __launch_bounds__(256, prune_gemm_wg_per_cu(MI, KB)) void prune_gemm_
             for (int i = 0; i < MI; ++i) { b.lo[i] = 0; b.hi[i] = 0x7fff; }
             return b;
         }
+        int plo = 0, phi = a.k_valid - 1;
+        if (x.o->bext) {                                    // the panel's extent, as the planner read it (empty: row 0, extents.hip)
+            const ext_cptr_t be = (ext_cptr_t)(unsigned long long)(x.o->bext + ((int64_t)x.cat * (x.ldb / kBN) + x.col0 / kBN) * 2);
+            plo = be[0];
+            phi = min(be[1], phi);
+            if (be[1] < be[0]) { plo = 0; phi = 0; }
+        }
         const ext_cptr_t e = (ext_cptr_t)(unsigned long long)(a.pool.ext + ((int64_t)x.o->slot[x.cat] * a.pool.ext_blocks + x.row_tile * MI) * 2);
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             int lo = 1, hi = 0;
-            if (x.row_tile * MI + i < a.pool.ext_blocks) { lo = e[2 * i]; hi = e[2 * i + 1]; }
+            if (x.row_tile * MI + i < a.pool.ext_blocks) { lo = max(e[2 * i], plo); hi = min(e[2 * i + 1], phi); }
             const bool some = hi >= lo;
-            b.lo[i] = some ? lo / KB - x.kt0 : 1;
-            b.hi[i] = some ? hi / KB - x.kt0 : 0;
+            b.lo[i] = some ? lo / 4 - x.kt0 * NS : 1;
+            b.hi[i] = some ? hi / 4 - x.kt0 * NS : 0;
         }
         return b;
     };
-    auto active = [&](const Blocks& b, int kt) -> unsigned {
+    auto active = [&](const Blocks& b, int ks) -> unsigned {
         unsigned m = 0;
 #pragma unroll
-        for (int i = 0; i < MI; ++i) m |= (unsigned)(kt >= b.lo[i] && kt <= b.hi[i]) << i;
+        for (int i = 0; i < MI; ++i) m |= (unsigned)(ks >= b.lo[i] && ks <= b.hi[i]) << i;
         return m;
     };
 
@@ -301,15 +315,20 @@ __global__ __launch_bounds__(256, prune_gemm_wg_per_cu(MI, KB)) void prune_gemm_
         const Blocks blk = block_ranges(cur);
         const int nkt = cur.nkt, kbase = cur.kt0 * KB;     // this tile's K tiles: kbase, kbase + 16, ...
         const int steps_last = cur.kt0 + nkt == n_k ? last_steps : NS;  // only the matrix's last K tile is ragged
-        for (int kt = 0; kt + 1 < nkt; ++kt) {
+        // One pipelined K tile.  P: which of the two B fragment pairs its first step finds loaded -- the pairs alternate per
+        // k-step, so with an odd number of steps per K tile (12-deep) the K tiles alternate between the two copies of this body.
+        auto k_tile = [&](auto parity, int kt) __attribute__((always_inline)) {
+            constexpr int P = decltype(parity)::value;
             const int buf = g & 1;
             const double* base = lds + buf * STAGE;
             const double* nbase = lds + (buf ^ 1) * STAGE;
             const int k1 = kbase + (kt + 1) * KB;          // K tile being staged into the other stage
             const bool next_full = kt + 2 < nkt;            // K tile kt+1 is another pipelined one (not this tile's last)
-            const unsigned on = active(blk, kt);
 #pragma unroll
             for (int s4 = 0; s4 < NS; ++s4) {
+                // (a plain comparison per block and k-step: one mask per K tile with a short cut where every block is live, and
+                // A fragment reads left out for the blocks dead in the coming k-step, both measured slower: DESIGN.md section 3)
+                const unsigned on = active(blk, kt * NS + s4);
                 if (s4 < NS - 1) {
                     if (s4 == 0 && kt == 0) {               // K tile 1 of this output tile: no earlier barrier to carry it
 #pragma unroll
@@ -333,16 +352,16 @@ __global__ __launch_bounds__(256, prune_gemm_wg_per_cu(MI, KB)) void prune_gemm_
                 const bool pre = s4 < NS - 1 || next_full;  // uniform
                 const double* src = s4 < NS - 1 ? base : nbase;
                 const int ns = (s4 + 1) % NS;
-                if (pre) read_b(src, ns, bfr[(s4 + 1) & 1]);
+                if (pre) read_b(src, ns, bfr[(s4 + 1 + P) & 1]);
 #pragma unroll
                 for (int i = 0; i < MI; ++i) {
                     if (on & (1u << i)) {
                         if (TRANS) {                        // operands swapped: the accumulators hold C^T
-                            acc[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(bfr[s4 & 1][0], af[i], acc[i][0], 0, 0, 0);
-                            acc[i][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(bfr[s4 & 1][1], af[i], acc[i][1], 0, 0, 0);
+                            acc[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(bfr[(s4 + P) & 1][0], af[i], acc[i][0], 0, 0, 0);
+                            acc[i][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(bfr[(s4 + P) & 1][1], af[i], acc[i][1], 0, 0, 0);
                         } else {
-                            acc[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bfr[s4 & 1][0], acc[i][0], 0, 0, 0);
-                            acc[i][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bfr[s4 & 1][1], acc[i][1], 0, 0, 0);
+                            acc[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bfr[(s4 + P) & 1][0], acc[i][0], 0, 0, 0);
+                            acc[i][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bfr[(s4 + P) & 1][1], acc[i][1], 0, 0, 0);
                         }
                     }
                     if (pre) af[i] = src[a_off + ns * 4 * SA + i * 16];
@@ -350,8 +369,13 @@ __global__ __launch_bounds__(256, prune_gemm_wg_per_cu(MI, KB)) void prune_gemm_
                 }
             }
             ++g;
+        };
+        // (one after the other in ONE loop body: as the two arms of a branch the register allocator demotes the accumulators)
+        for (int kt = 0; kt + 1 < nkt; kt += 1 + NS % 2) {
+            k_tile(std::integral_constant<int, 0>{}, kt);
+            if (NS % 2 && kt + 2 < nkt) k_tile(std::integral_constant<int, NS % 2>{}, kt + 1);
         }
-        {   // last K tile: last_steps of its four steps hold valid k; plain read -> MFMA steps.  The next output tile's
+        {   // last K tile: steps_last of its k-steps hold valid k; plain read -> MFMA steps.  The next output tile's
             // first K tile is in flight (it went out at the barrier of the K tile before, or goes out here if this is the only one).
             const int buf = g & 1;
             const double* base = lds + buf * STAGE;
@@ -360,10 +384,10 @@ __global__ __launch_bounds__(256, prune_gemm_wg_per_cu(MI, KB)) void prune_gemm_
 #pragma unroll
                 for (int q = 0; q < NS; ++q) stage_quarter(nxt, nk0, buf ^ 1, q);
             }
-            const unsigned on = active(blk, nkt - 1);
 #pragma unroll
             for (int s4 = 0; s4 < NS; ++s4) {
                 if (s4 < steps_last) {
+                    const unsigned on = active(blk, (nkt - 1) * NS + s4);
 #pragma unroll
                     for (int i = 0; i < MI; ++i) af[i] = base[a_off + s4 * 4 * SA + i * 16];
                     read_b(base, s4, bfr[0]);
@@ -571,8 +595,8 @@ int prune_gemm_pick_mi(int64_t tiles_by_mi[10], int n_cu, int kb) {
     return best;
 }
 
-// Persistent grid: as many workgroups per CU as are resident (the register/LDS budget admits three at up to 80-row tiles, two
-// above), a multiple of 8 so that every XCD gets the same number.  XCD x (blocks x, x+8, ...) owns the (category, column
+// Persistent grid: as many workgroups per CU as are resident (prune_gemm_wg_per_cu: the register/LDS budget admits four or three
+// at up to 80-row tiles, two above), a multiple of 8 so that every XCD gets the same number.  XCD x (blocks x, x+8, ...) owns the (category, column
 // tile) pairs x, x+8, ... of every op of the launch and its blocks share those pairs' row tiles: a small launch gets as
 // many blocks per XCD as the busiest XCD (XCD 0) has tiles.
 int prune_gemm_blocks(int64_t tiles_xcd0, int n_cu, int mi, int kb) {
@@ -617,8 +641,8 @@ hipError_t launch_prune_gemm(const GemmArgs& a, GemmVariant v, int blocks, hipSt
     if (v.trans && (v.leaf || v.mode)) return hipErrorInvalidValue;
     dim3 grid(blocks, 1, 1);
     (void)hipGetLastError();
-    if (a.kb != 8 && a.kb != 16) return hipErrorInvalidValue;
-#define CAFE_MI_CASE(M) case M: if (a.kb == 8) launch_mi<8, M>(a, v, grid, stream, ev0, ev1); else launch_mi<16, M>(a, v, grid, stream, ev0, ev1); break;
+    if (a.kb != 8 && a.kb != 12 && a.kb != 16) return hipErrorInvalidValue;
+#define CAFE_MI_CASE(M) case M: if (a.kb == 8) launch_mi<8, M>(a, v, grid, stream, ev0, ev1); else if (a.kb == 12) launch_mi<12, M>(a, v, grid, stream, ev0, ev1); else launch_mi<16, M>(a, v, grid, stream, ev0, ev1); break;
     switch (a.mi) {
         CAFE_MI_CASE(2) CAFE_MI_CASE(3) CAFE_MI_CASE(4) CAFE_MI_CASE(5) CAFE_MI_CASE(6) CAFE_MI_CASE(7) CAFE_MI_CASE(8) CAFE_MI_CASE(9)
         default: return hipErrorInvalidValue;
