@@ -144,8 +144,8 @@ struct cafe_ctx {
     char* d_params = nullptr;
     size_t params_bytes = 0;
     cafe::SlotParam* d_slots = nullptr;                   // [max_slots] row-major, then [max_kslots] k-major
-    // cafe_set_death_rates: while `mus` is not empty every call builds its matrices with the two-rate kernel
-    // (bd_matrix_lm.hip) from slot parameters of their own -- device array and pinned mirror, [max_slots] row-major then
+    // cafe_set_death_rates: while `mus` is not empty every call builds its matrices with K1's two-rate
+    // instantiation (bd_matrix_lm.hip) from slot parameters of their own -- device array and pinned mirror, [max_slots] row-major then
     // [max_kslots] k-major, allocated by the first call of the setter
     std::vector<double> mus;                 // [n_lambdas] death rate per lambda index; empty: lambda = mu
     cafe::SlotParamLM* d_slots_lm = nullptr;
@@ -334,7 +334,7 @@ void destroy_child(cafe_ctx* c);
 int enqueue_rootmax(cafe_ctx* c, const double* lambdas, hipStream_t s);
 // one scorer evaluation per listed family, each under its own lambdas (family_lambda.hip)
 int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_t* family, const double* lambdas, double* family_lnl);
-// ... each under its own (lambdas, mus): the same frame with the two-rate kernel (family_lambda_lm.hip)
+// ... each under its own (lambdas, mus): the same frame with the kernel's two-rate instantiation (family_lambda_lm.hip)
 int score_per_family_lm_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_t* family, const double* lambdas, const double* mus,
                              double* family_lnl);
 // multi-GPU (cafe_sharded.hip)

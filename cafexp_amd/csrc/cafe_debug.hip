@@ -361,7 +361,7 @@ static int build_matrices(int32_t device, int32_t n, int32_t count, const double
     if (hipMalloc(&d_sp, sp_bytes) != hipSuccess) { (void)hipFree(pool.base); return CAFE_ERR_MEMORY; }
     if (hipMemset(pool.base, 0, bytes) != hipSuccess) rc = CAFE_ERR_DEVICE;
     if (rc == CAFE_OK && hipMemcpy(d_sp, h_sp, sp_bytes, hipMemcpyHostToDevice) != hipSuccess) rc = CAFE_ERR_DEVICE;
-    if (rc == CAFE_OK && (mus ? launch_bd_lm_build(pool, static_cast<const SlotParamLM*>(d_sp), count, nullptr)
+    if (rc == CAFE_OK && (mus ? launch_bd_matrix_build(pool, static_cast<const SlotParamLM*>(d_sp), count, nullptr)
                               : launch_bd_matrix_build(pool, static_cast<const SlotParam*>(d_sp), count, nullptr)) != hipSuccess)
         rc = CAFE_ERR_DEVICE;
     if (rc == CAFE_OK && hipDeviceSynchronize() != hipSuccess) rc = CAFE_ERR_DEVICE;

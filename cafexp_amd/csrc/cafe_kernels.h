@@ -10,6 +10,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
+
 namespace cafe {
 
 constexpr int kMaxCategories = 32;   // CAFE_MAX_CATEGORIES
@@ -29,6 +32,7 @@ constexpr int kMaxBM = 144;          // largest row tile (MI = 9)
 // (matrix_cache.cpp:148-149), oma2 = (1-a)^2; zero = saturated (matrix_cache.cpp:153) or
 // !(coeff > 0 && coeff != 1) (probability.cpp:154): rows s >= 1 stay 0.
 struct SlotParam {
+    static constexpr bool two_rates = false;
     double alpha;
     double oma2;
     int32_t zero;
@@ -71,7 +75,7 @@ inline SlotParam slot_param(long lq, long tq) {
     sp.pad = 0;
     return sp;
 }
-// Separate birth and death rates (bd_matrix_lm.hip).  The single-lineage law of the linear birth-death process is
+// Separate birth and death rates (bd_row.h).  The single-lineage law of the linear birth-death process is
 // p1(0) = alpha, p1(k) = (1-alpha)(1-beta) beta^(k-1),
 //     alpha = mu (E-1) / (lambda E - mu),   beta = lambda (E-1) / (lambda E - mu),   E = exp((lambda - mu) t).
 // Evaluated as w = -expm1(-|lambda-mu| t), D = |lambda-mu| + min(lambda, mu) w, alpha = mu w / D, beta = lambda w / D: every
@@ -98,9 +102,11 @@ inline BdRates bd_rates(double lambda, double mu, double t) {
 }
 // Per transition matrix of the two-rate kernel: q = (1-alpha)(1-beta).  zero carries the reference's saturation rule
 // (matrix_cache.cpp:153, probability.cpp:154) over to coeff = 1 - alpha - beta: a convention that keeps the model continuous
-// at mu = lambda (the recurrence itself is well defined wherever alpha, beta < 1).  A 32-byte struct of its own: SlotParam,
-// and with it the code of the lambda = mu kernels, stays what it is.
+// at mu = lambda (the recurrence itself is well defined wherever alpha, beta < 1).  A 32-byte struct next to the 24-byte
+// SlotParam: K1 and the per-family kernel are one body each, instantiated on the slot type (bd_matrix_build.h,
+// family_lambda_kernel.h), and the lambda = mu instantiation loads and keeps live no second ratio.
 struct SlotParamLM {
+    static constexpr bool two_rates = true;
     double alpha;
     double beta;
     double q;
@@ -117,9 +123,12 @@ inline SlotParamLM slot_param_lm(long lq, long mq, long tq) {
     sp.pad = 0;
     return sp;
 }
-hipError_t launch_bd_lm_build(const MatrixPool& pool, const SlotParamLM* d_slots, int n_slots, hipStream_t stream);
-hipError_t launch_bd_lm_build_both(const MatrixPool& pool, const MatrixPool& kpool, const SlotParamLM* d_slots, const SlotParamLM* d_kslots,
-                                   int n_slots, int n_kslots, hipStream_t stream);
+// What the kernels that are one body for both slot types ask of a slot besides alpha and zero: the ratio of p1's geometric
+// tail and q = (1-alpha)(1-tail)
+__host__ __device__ inline double slot_tail(const SlotParam& sp) { return sp.alpha; }
+__host__ __device__ inline double slot_q(const SlotParam& sp) { return sp.oma2; }
+__host__ __device__ inline double slot_tail(const SlotParamLM& sp) { return sp.beta; }
+__host__ __device__ inline double slot_q(const SlotParamLM& sp) { return sp.q; }
 // A row-major pool of matrices of order n, not yet placed (base null, no extents)
 inline MatrixPool row_major_pool(int n) {
     MatrixPool p{};
@@ -316,9 +325,25 @@ struct ReduceArgs {
     int32_t* failed;                // [F]
 };
 
-hipError_t launch_bd_matrix_build(const MatrixPool& pool, const SlotParam* d_slots, int n_slots, hipStream_t stream);
-hipError_t launch_bd_matrix_build_both(const MatrixPool& pool, const MatrixPool& kpool, const SlotParam* d_slots, const SlotParam* d_kslots,
-                                       int n_slots, int n_kslots, hipStream_t stream);
+// K1, overloaded on the slot type: SlotParam (bd_matrix.hip) and SlotParamLM (bd_matrix_lm.hip) are the two instantiations
+template <class Slot>
+hipError_t launch_bd_matrix_build(const MatrixPool& pool, const Slot* d_slots, int n_slots, hipStream_t stream);
+template <class Slot>
+hipError_t launch_bd_matrix_build_both(const MatrixPool& pool, const MatrixPool& kpool, const Slot* d_slots, const Slot* d_kslots, int n_slots,
+                                       int n_kslots, hipStream_t stream);
+// The kernels that keep a row of the recurrence in registers (K1, the per-family kernel) exist per number E of columns a lane
+// owns: the smallest E of the list with cols <= 64 E.  Calls f(std::integral_constant<int, E>) and returns its result;
+// hipErrorInvalidValue past 64 * 32 = bd_matrix_max_order() columns.
+template <int... Es, class F>
+hipError_t for_lane_width(std::integer_sequence<int, Es...>, int cols, F&& f) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)(... || (cols <= 64 * Es ? (e = f(std::integral_constant<int, Es>{}), true) : false));
+    return e;
+}
+template <class F>
+hipError_t for_lane_width(int cols, F&& f) {
+    return for_lane_width(std::integer_sequence<int, 2, 4, 6, 8, 10, 12, 14, 16, 20, 24, 28, 32>{}, cols, f);
+}
 // One launch for a group of ops.  variant: what the epilogue of EVERY op of the group does (the host groups by it):
 //   mode (0 store, 1 multiply), leaf (0 none, 1 one leaf sibling, 2 gathered sibling factor), trans (factor GEMM, transposed store).
 // blocks: prune_gemm_blocks of the group; events: attached to the dispatch.

@@ -104,7 +104,7 @@ void fill_slots(cafe_ctx* c, const double* lambdas, const double* multipliers, i
 }
 
 // K1 of a call whose slot parameters fill_slots left in the pinned mirrors: the lambda = mu kernels, or with death rates set
-// their two-rate twins behind an upload of their own parameters
+// the two-rate instantiations behind an upload of their own parameters
 int upload_lm_slots(cafe_ctx* c, hipStream_t s) {
     if (c->mus.empty()) return CAFE_OK;
     const size_t n = (size_t)(c->max_slots + c->max_kslots);         // (the buffers hold max(1, n): a context without slots uploads nothing)
@@ -115,7 +115,7 @@ int launch_call_matrices(cafe_ctx* c, hipStream_t s) {
     if (c->mus.empty())
         HIP_TRY(c, launch_bd_matrix_build_both(c->pool, c->kpool, c->d_slots, c->d_slots + c->max_slots, c->n_slots_last, c->n_kslots_last, s));
     else
-        HIP_TRY(c, launch_bd_lm_build_both(c->pool, c->kpool, c->d_slots_lm, c->d_slots_lm + c->max_slots, c->n_slots_last, c->n_kslots_last, s));
+        HIP_TRY(c, launch_bd_matrix_build_both(c->pool, c->kpool, c->d_slots_lm, c->d_slots_lm + c->max_slots, c->n_slots_last, c->n_kslots_last, s));
     return CAFE_OK;
 }
 

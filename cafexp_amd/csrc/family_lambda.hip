@@ -32,101 +32,15 @@
 #include <limits>
 #include <vector>
 
-#include "bd_row.h"
 #include "cafe_call.h"
-#include "family_lambda_lm.h"
+#include "family_lambda_kernel.h"
 
 namespace cafe {
 
+// the branch kernel (family_lambda_kernel.h) for lambda = mu; family_lambda_lm.hip holds the two-rate instantiation
+template hipError_t launch_family_lambda<SlotParam>(const FamLamArgs<SlotParam>&, int, int64_t, int, hipStream_t);
+
 namespace {
-
-// kPartRows, kPartLd: family_lambda_lm.h, shared with the two-rate twin of this kernel (family_lambda_lm.hip).  That kernel
-// MIRRORS the one below -- slot type, rc.init and the row step apart -- so a fix to one is a fix to both.
-
-struct FamLamArgs {
-    const int32_t* nodes;            // the nodes of this level: one unit of work per branch above them
-    const int32_t* child_off;        // [n_nodes + 1] children of a node: child_idx[child_off[u] .. child_off[u + 1])
-    const int32_t* child_idx;
-    const int32_t* taxon;            // [n_nodes] row of `counts` for a leaf, -1 for interior nodes
-    const int32_t* n_rows;           // [n_nodes] factor rows s = 0..n_rows-1: M + 1, or R + 1 under the root
-    const SlotParam* slots;          // [batch][n_nodes] the branch's parameters under the family's lambdas
-    const int64_t* col;              // [batch] the family's column in `counts`
-    const int32_t* counts;           // [taxon][counts_ld]
-    int64_t counts_ld;
-    const double* err;               // [(M+1)][n_dev] or nullptr
-    int32_t n_dev, M, ld, n_nodes;
-    double* factors;                 // [batch][n_nodes][ld]
-};
-
-template <int E>
-__global__ __launch_bounds__(64) void family_lambda_kernel(const FamLamArgs a) {
-    __shared__ double part[kPartRows * kPartLd];
-    const int lane = threadIdx.x;
-    const int64_t b = blockIdx.x;
-    const int u = a.nodes[blockIdx.y];
-    const SlotParam sp = a.slots[b * a.n_nodes + u];
-    double* __restrict__ fac_b = a.factors + b * a.n_nodes * a.ld;
-    double* __restrict__ out = fac_b + (int64_t)u * a.ld;
-    const int c0 = lane * E;                           // owned columns c0 .. c0+E-1 of the current row
-    const int n_rows = a.n_rows[u];
-
-    double v[E];                                       // the child's likelihoods of sizes c0 .. c0+E-1 (0 past M)
-    const int tx = a.taxon[u];
-    if (tx >= 0) {                                     // probability.cpp:179-199
-        const int x = a.counts[(int64_t)tx * a.counts_ld + a.col[b]];
-        if (a.err) {
-            const int lo = x - (a.n_dev - 1) / 2;      // taps outside [0, M] are dropped
-#pragma unroll
-            for (int i = 0; i < E; ++i) {
-                const int c = c0 + i, t = c - lo;
-                v[i] = (t >= 0 && t < a.n_dev && c <= a.M) ? a.err[(int64_t)x * a.n_dev + t] : 0.0;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < E; ++i) v[i] = (c0 + i == x) ? 1.0 : 0.0;
-        }
-    } else {                                           // probability.cpp:211-218: the product of the children's factors
-#pragma unroll
-        for (int i = 0; i < E; ++i) v[i] = (c0 + i <= a.M) ? 1.0 : 0.0;
-        for (int k = a.child_off[u]; k < a.child_off[u + 1]; ++k) {
-            const double* __restrict__ f = fac_b + (int64_t)a.child_idx[k] * a.ld;
-#pragma unroll
-            for (int i = 0; i < E; ++i)
-                if (c0 + i <= a.M) v[i] *= f[c0 + i];
-        }
-    }
-
-    if (sp.zero) {                                     // saturated / degenerate: rows s >= 1 are 0, row 0 = e_0
-        for (int r = lane; r < n_rows; r += 64) out[r] = r == 0 ? v[0] : 0.0;
-        return;
-    }
-
-    BdRowConsts<E> rc;
-    rc.init(sp.alpha, sp.oma2, lane);
-    double p[E];                                       // P[row][c0 + i]; columns past the matrix hold values in [0,1] that meet v = 0
-#pragma unroll
-    for (int i = 0; i < E; ++i) p[i] = (c0 + i == 0) ? 1.0 : 0.0;
-
-    for (int r = 0; r < n_rows; ++r) {
-        if (r > 0) bd_row_step<E, false>(rc, nullptr, 0.0, lane, p);
-        double d = p[0] * v[0];
-#pragma unroll
-        for (int i = 1; i < E; ++i) d = fma(p[i], v[i], d);
-        part[(r & (kPartRows - 1)) * kPartLd + lane] = d;
-        if ((r & (kPartRows - 1)) == kPartRows - 1 || r == n_rows - 1) {
-            __syncthreads();                           // one wave per block: orders the LDS writes before the transposed reads
-            const int j = lane & 15, quarter = lane >> 4;
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) s += part[j * kPartLd + quarter * 16 + k];
-            s += __shfl_xor(s, 16);
-            s += __shfl_xor(s, 32);
-            const int row = (r & ~(kPartRows - 1)) + j;
-            if (lane < 16 && row <= r) out[row] = s;
-            __syncthreads();                           // the block is read before the next rows overwrite it
-        }
-    }
-}
 
 struct FamRootArgs {
     const int32_t* root_children;
@@ -156,32 +70,6 @@ __global__ __launch_bounds__(64) void family_root_kernel(const FamRootArgs a) {
     if (lane == 0) a.out[b] = best;
 }
 
-hipError_t launch_family_lambda(const FamLamArgs& a, int n, int64_t batch, int n_level_nodes, hipStream_t stream) {
-    if (batch <= 0 || n_level_nodes <= 0) return hipSuccess;
-    if (n > bd_matrix_max_order() || n > a.ld || batch > 0x7fffffff || n_level_nodes > 65535) return hipErrorInvalidValue;
-    dim3 grid((unsigned)batch, (unsigned)n_level_nodes), block(64);
-#define CAFE_FL_CASE(EV)                                                                     \
-    if (n <= 64 * EV) {                                                                      \
-        (void)hipGetLastError();                                                             \
-        hipLaunchKernelGGL((family_lambda_kernel<EV>), grid, block, 0, stream, a);           \
-        return hipGetLastError();                                                            \
-    }
-    CAFE_FL_CASE(2)
-    CAFE_FL_CASE(4)
-    CAFE_FL_CASE(6)
-    CAFE_FL_CASE(8)
-    CAFE_FL_CASE(10)
-    CAFE_FL_CASE(12)
-    CAFE_FL_CASE(14)
-    CAFE_FL_CASE(16)
-    CAFE_FL_CASE(20)
-    CAFE_FL_CASE(24)
-    CAFE_FL_CASE(28)
-    CAFE_FL_CASE(32)
-#undef CAFE_FL_CASE
-    return hipErrorInvalidValue;
-}
-
 inline size_t align_up(size_t v) { return (v + 255) / 256 * 256; }
 
 // The branch above node u under one family's lambdas
@@ -205,23 +93,19 @@ SlotParamLM branch_param_lm(const cafe_ctx* c, int u, const double* lam, const d
     return slot_param_lm(quantize_lambda(l), quantize_lambda(m), quantize_time(c->blen[u]));
 }
 
-// What the two entries differ in: the slot type and argument block of their branch kernel, its launcher, and how a family's
-// rates become a branch's slot.  mus is null for the lambda = mu entry.
+// What the two entries differ in: the slot type (the branch kernel's argument block and launcher follow from it) and how a
+// family's rates become a branch's slot.  mus is null for the lambda = mu entry.
 struct EqualRates {
     using Slot = SlotParam;
-    using Args = FamLamArgs;
     static constexpr const char* entry = "cafe_score_per_family";
     static constexpr bool reads_context_rates = true;  // lambda = mu is what it computes: refused while the context has death rates
     static Slot slot(const cafe_ctx* c, int u, const double* lam, const double*) { return branch_param(c, u, lam); }
-    static hipError_t launch(const Args& a, int n, int64_t batch, int n_level_nodes, hipStream_t s) { return launch_family_lambda(a, n, batch, n_level_nodes, s); }
 };
 struct TwoRates {
     using Slot = SlotParamLM;
-    using Args = FamLamArgsLM;
     static constexpr const char* entry = "cafe_score_per_family_lm";
     static constexpr bool reads_context_rates = false;
     static Slot slot(const cafe_ctx* c, int u, const double* lam, const double* mus) { return branch_param_lm(c, u, lam, mus); }
-    static hipError_t launch(const Args& a, int n, int64_t batch, int n_level_nodes, hipStream_t s) { return launch_family_lambda_lm(a, n, batch, n_level_nodes, s); }
 };
 
 // The host frame of both entries: argument checks, what the host decides alone, levels and tables, the batches under the
@@ -317,7 +201,7 @@ int per_family_frame(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_
     HIP_TRY(c, hipMemcpyAsync(base, tables.data(), sizeof(int32_t) * tables.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(base + o_reals, reals.data(), sizeof(double) * reals.size(), hipMemcpyHostToDevice, s));
 
-    typename Kind::Args a{};
+    FamLamArgs<Slot> a{};
     a.child_off = d_tables; a.child_idx = d_tables + o_child_idx; a.taxon = d_tables + o_taxon; a.n_rows = d_tables + o_rows;
     a.slots = reinterpret_cast<const Slot*>(base + o_slots);
     a.col = reinterpret_cast<const int64_t*>(base + o_col);
@@ -344,7 +228,7 @@ int per_family_frame(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_
         HIP_TRY(c, hipMemcpyAsync(base + o_col, col.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, s));
         for (int lv = 0; lv < n_levels; ++lv) {
             a.nodes = d_tables + o_level + level_off[lv];
-            HIP_TRY(c, Kind::launch(a, c->N, nb, level_off[lv + 1] - level_off[lv], s));
+            HIP_TRY(c, launch_family_lambda(a, c->N, nb, level_off[lv + 1] - level_off[lv], s));
         }
         CAFE_LAUNCH(c, family_root_kernel, dim3((unsigned)nb), dim3(64), 0, s, ra);
         HIP_TRY(c, hipMemcpyAsync(res.data(), base + o_out, sizeof(double) * nb, hipMemcpyDeviceToHost, s));

@@ -169,7 +169,7 @@ int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t see
     HIP_TRY(c, hipMemcpyAsync(meta + n, h_parent.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(meta + 2 * n, h_slot.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(meta + 3 * n, h_leaf.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-    if (lm) HIP_TRY(c, launch_bd_lm_build(sp, static_cast<const SlotParamLM*>(d_sp.p), (int)n_slots, s));
+    if (lm) HIP_TRY(c, launch_bd_matrix_build(sp, static_cast<const SlotParamLM*>(d_sp.p), (int)n_slots, s));
     else HIP_TRY(c, launch_bd_matrix_build(sp, static_cast<const SlotParam*>(d_sp.p), (int)n_slots, s));
     HIP_TRY(c, launch_row_cdf(sp.base, sp.stride, sp.ld, (int)n_slots, N, M, s));
     HIP_TRY(c, hipStreamSynchronize(s));                            // the host vectors above go out of use

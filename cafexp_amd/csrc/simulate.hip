@@ -7,7 +7,7 @@
 //               buffers fit the workspace; within a batch, chunks whose quantized lambdas agree share one block of
 //               matrices (the base model: one block for the whole batch)
 //   K1          launch_bd_matrix_build, row-major, order S, one slot per (block, distinct (lambda index, t_q) pair);
-//               cafe_simulate_lm with death rates: launch_bd_lm_build from slot_param_lm, the multiplier scaling both rates, and
+//               cafe_simulate_lm with death rates: the same launcher on slot_param_lm slots, the multiplier scaling both rates, and
 //               chunks share a block when both quantized vectors agree.  Everything behind the matrices is the same code
 //   row_cdf     inclusive prefix sums of rows 1..S-1 over columns 0..S-1 (the reference's weights, :338-341); this pass, the
 //               generator and the draw are tree_sampler.h's, shared with pvalues.hip
@@ -316,13 +316,13 @@ int simulate_impl(const cafe_sim_problem* p, const double* mus, uint64_t seed, i
         const int64_t fb = f1 - f0;
         const int n_slots = (int)blocks.size() * n_pairs;
         pool.base = static_cast<double*>(d_pool.p);
-        // K1 (or its two-rate twin) stores every row of every slot (a saturated one too): no clearing pass; columns >= S are never read
+        // K1 (either instantiation) stores every row of every slot (a saturated one too): no clearing pass; columns >= S are never read
         if (mus) {
             slots_lm.assign((size_t)n_slots, SlotParamLM{});
             for (size_t b = 0; b < blocks.size(); ++b)
                 for (int q = 0; q < n_pairs; ++q) slots_lm[b * n_pairs + q] = slot_param_lm(blocks[b][pair_lam[q]], blocks[b][L + pair_lam[q]], pair_tq[q]);
             SIM_TRY(hipMemcpyAsync(d_slots.p, slots_lm.data(), sizeof(SlotParamLM) * n_slots, hipMemcpyHostToDevice, s));
-            SIM_TRY(launch_bd_lm_build(pool, static_cast<const SlotParamLM*>(d_slots.p), n_slots, s));
+            SIM_TRY(launch_bd_matrix_build(pool, static_cast<const SlotParamLM*>(d_slots.p), n_slots, s));
         } else {
             slots.assign((size_t)n_slots, SlotParam{});
             for (size_t b = 0; b < blocks.size(); ++b)

@@ -261,7 +261,7 @@ typedef struct cafe_sim_problem {
 int cafe_simulate(const cafe_sim_problem* problem, uint64_t seed, int32_t* leaf_counts, int32_t* node_sizes, char* err, size_t errlen);
 /* The same under separate birth and death rates: mus[n_lambdas], the death rate of the branches of lambda index i (birth rate
  * problem->lambdas[i]); NULL is exactly cafe_simulate.  With mus the order-S matrices of every block are built by the two-rate
- * kernel (bd_matrix_lm.hip) from the key (lambda * multiplier, mu * multiplier, t) -- a chunk multiplier scales both rates, as
+ * instantiation of K1 (bd_matrix_lm.hip) from the key (lambda * multiplier, mu * multiplier, t) -- a chunk multiplier scales both rates, as
  * gamma multipliers do everywhere else -- and chunks share their matrices when both quantized vectors agree.  The row sums, the
  * sampler, the Philox counters, the error-model step and the batching are cafe_simulate's.  Every mu must be finite, >= 0 and
  * mu * multiplier * 1e9 within the bound lambda has: CAFE_ERR_ARGUMENT with a message that names mu otherwise.  With
@@ -289,8 +289,8 @@ int cafe_score_per_family(cafe_ctx* ctx, const cafe_params* params, int64_t n, c
  * Validity per entry is the context's rule as cafe_set_death_rates applies it -- one lambda: lambda > 0; several: no lambda
  * negative; every mu must satisfy mu >= 0 (so a NaN mu is invalid, as it is in the setter's calls) -- and an invalid entry gives
  * -inf; a NaN lambda that passes the rule gives NaN.  Either rate * 1e9 beyond a long gives the saturated branch (rows >= 1
- * zero), as a lambda beyond it does in cafe_score_per_family.  The branch kernel is the two-rate twin of that entry's
- * (family_lambda_lm.hip: the row step of bd_matrix_lm.hip on the key (lambda, mu, t), quantized like cafe_bd_rates); with
+ * zero), as a lambda beyond it does in cafe_score_per_family.  The branch kernel is that entry's, instantiated for two rates
+ * (family_lambda_kernel.h: the row step of bd_row.h on the key (lambda, mu, t), quantized like cafe_bd_rates); with
  * mus[i] == lambdas[i] every value is bit for bit what cafe_score_per_family returns for that vector. */
 int cafe_score_per_family_lm(cafe_ctx* ctx, const cafe_params* params, int64_t n, const int64_t* family,
                              const double* lambdas, const double* mus, double* family_lnl);
@@ -462,7 +462,7 @@ int cafe_debug_stamps(cafe_ctx* ctx, unsigned long long* out, size_t words);
  * device layout leaf branches use; layout 1: the k-major layout of interior branches (built through the
  * reversibility relation, see bd_matrix.hip), converted back on the host. */
 int cafe_build_matrices(int32_t device, int32_t n, int32_t count, const double* lambdas, const double* ts, int32_t layout, double* out);
-/* the same under separate birth and death rates (lambdas[i], mus[i], ts[i]): the two-rate kernel (bd_matrix_lm.hip) */
+/* the same under separate birth and death rates (lambdas[i], mus[i], ts[i]): K1's two-rate instantiation (bd_matrix_lm.hip) */
 int cafe_build_matrices_lm(int32_t device, int32_t n, int32_t count, const double* lambdas, const double* mus, const double* ts,
                            int32_t layout, double* out);
 /* back-to-back v_mfma_f64_16x16x4_f64 issue-rate probe: returns achieved TFLOP/s on `device`. */

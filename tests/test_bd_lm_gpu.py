@@ -1,4 +1,4 @@
-"""Separate birth and death rates on the GPU: the two-rate K1 against the numpy reference (tests/bd_lm_ref.py), bit identity with
+"""Separate birth and death rates on the GPU: K1's two-rate instantiation against the numpy reference (tests/bd_lm_ref.py), bit identity with
 the lambda = mu path when mu = lambda, and every call that builds matrices under cafe_set_death_rates against a numpy prune on the
 reference matrices.
 
@@ -63,6 +63,22 @@ def test_equal_rates_build_the_k1_matrices_bit_for_bit(capi):
             a = capi.build_matrices(n, [0.006335, 0.01], [68.7105, 30.0], layout=layout)
             b = capi.build_matrices_lm(n, [0.006335, 0.01], [0.006335, 0.01], [68.7105, 30.0], layout=layout)
             assert np.array_equal(a, b), (n, layout)
+
+
+# K1 is one body (bd_matrix_build.h) instantiated per slot type: with mu = lambda the two instantiations must give the same bits
+# at EVERY width E = 2 .. 32 columns per lane.  64 E_prev + 1 is the smallest order of a width in the row-major layout
+# (columns = n); 128 / 129 and 2048 are where the k-major layout (columns = n - 1) chooses differently, 2048 the maximum.
+EVERY_WIDTH = [2, 128, 129, 257, 385, 513, 641, 769, 897, 1025, 1281, 1537, 1793, 2048]
+
+
+@pytest.mark.parametrize("layout", [0, 1])
+@pytest.mark.parametrize("n", EVERY_WIDTH)
+def test_equal_rates_build_the_k1_matrices_at_every_width(capi, n, layout):
+    lam, t = [0.006335, 0.01, R.SATURATED[0]], [68.7105, 30.0, R.SATURATED[2]]
+    a = capi.build_matrices(n, lam, t, layout=layout)
+    b = capi.build_matrices_lm(n, lam, lam, t, layout=layout)
+    assert a[:2, 1:].any() and not a[2, 1:].any()          # two live keys, the third saturated at mu = lambda too
+    assert np.array_equal(a, b)
 
 
 # ------------------------------------------------------------------ the calls of a context (problem and numpy prune: bd_lm_ref.py)

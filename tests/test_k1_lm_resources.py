@@ -1,8 +1,8 @@
-"""The two-rate K1 (bd_matrix_lm.hip: separate birth and death rates) keeps every row of its recurrence in registers exactly as
-K1 does, with one more constant live.  The rule tests/test_k1_resources.py pins for bd_matrix.hip, on the new file: cross-compile
-for gfx950 (CPU only), read the compiler's resource remarks -- every width 2 .. 32 in both layouts and in the two-pool launch is
-there, and none uses scratch memory or spills a vector register.  No kernel of the file carries K1's name (that test counts
-them by it)."""
+"""The two-rate K1 (bd_matrix_lm.hip: the body of bd_matrix_build.h on SlotParamLM, separate birth and death rates) keeps every
+row of its recurrence in registers exactly as the lambda = mu instantiation does, with one more constant live.  The rule
+tests/test_k1_resources.py pins for bd_matrix.hip, on this file: cross-compile for gfx950 (CPU only), read the compiler's
+resource remarks -- every width 2 .. 32 in both layouts and in the two-pool launch is there, and none uses scratch memory or
+spills a vector register.  No kernel of the file is a lambda = mu instantiation (that test counts them by the slot type)."""
 import os
 import re
 import shutil
@@ -37,12 +37,12 @@ def test_every_two_rate_k1_instantiation_runs_without_scratch(tmp_path):
         m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/lane\])?: (\d+)", line)
         if m and name:
             kernels[name][m.group(1).strip()] = int(m.group(2))
-    assert not [k for k in kernels if "bd_matrix_build" in k], sorted(kernels)
-    k1 = {k: v for k, v in kernels.items() if "bd_lm_" in k}
+    assert not [k for k in kernels if "bd_matrix_build" in k and "SlotParamLM" not in k], sorted(kernels)
+    k1 = {k: v for k, v in kernels.items() if "bd_matrix_build" in k}
     for E in WIDTHS:
-        assert "_ZN4cafe17bd_lm_both_kernelILi%dEEEv" % E in "|".join(k1), E
+        assert "_ZN4cafe27bd_matrix_build_both_kernelINS_11SlotParamLMELi%dEEEv" % E in "|".join(k1), E
         for km in (0, 1):
-            assert "_ZN4cafe12bd_lm_kernelILi%dELb%dEEEv" % (E, km) in "|".join(k1), (E, km)
+            assert "_ZN4cafe22bd_matrix_build_kernelINS_11SlotParamLMELi%dELb%dEEEv" % (E, km) in "|".join(k1), (E, km)
     assert len(k1) == 3 * len(WIDTHS), sorted(k1)
     for k, res in k1.items():
         assert res["ScratchSize"] == 0, (k, res)

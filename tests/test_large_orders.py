@@ -31,7 +31,7 @@ ORDERS = [768, 769, 770, 896, 897, 898, 1024, 1025, 1026, 1280, 1281, 1536, 1537
 
 
 def k1_width(cols):
-    """E of bd_matrix.hip's CAFE_BD_CASE ladder for a launch over `cols` owned columns."""
+    """E of K1's width dispatch (for_lane_width) for a launch over `cols` owned columns."""
     return next(E for E in WIDTHS if cols <= 64 * E)
 
 

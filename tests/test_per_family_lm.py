@@ -1,11 +1,11 @@
-"""cafe_score_per_family_lm (family_lambda_lm.hip): the per-family kernel under separate birth and death rates, every family
-of a call under its own (lambdas, mus).
+"""cafe_score_per_family_lm (family_lambda_kernel.h on SlotParamLM, family_lambda_lm.hip): the per-family kernel under separate
+birth and death rates, every family of a call under its own (lambdas, mus).
 
 References: the scorer path of the same context under cafe_set_death_rates (tests/test_bd_lm_gpu.py pins it to a numpy prune),
 one call per distinct pair, and that numpy prune itself on the matrices of tests/bd_lm_ref.py.  Tolerance: the per-family one,
 test_lambda_per_family._close at REL = 1e-10, infinities matched exactly.  With mus == lambdas the values are compared with
-cafe_score_per_family's by ==: bd_row_step_lm with a == b is bd_row_step to the bit and slot_param_lm takes K1's formula at
-equal quantized rates."""
+cafe_score_per_family's by ==: the kernel is one body for both slot types, bd_row_step with a == b runs the equal-rate form's
+operands, and slot_param_lm takes K1's formula at equal quantized rates."""
 import dataclasses
 
 import numpy as np
@@ -184,10 +184,7 @@ def test_against_the_numpy_prune(capi, order, error):
     _close(got, scorer)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("error", [False, True])
-@pytest.mark.parametrize("n", [33, 641, 2048])
-def test_equal_rates_are_the_lambda_only_entry_bit_for_bit(capi, n, error):
+def _equal_rates_case(capi, n, error):
     M, Rr = sizes(n)
     rows = families(n)
     tree = P.parse_newick(TREE3)
@@ -211,6 +208,25 @@ def test_equal_rates_are_the_lambda_only_entry_bit_for_bit(capi, n, error):
     assert np.isfinite(plain).all()
     assert np.array_equal(twin, plain)
     assert not np.any(other == plain)                        # the second rate is read
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("error", [False, True])
+@pytest.mark.parametrize("n", [33, 641, 2048])
+def test_equal_rates_are_the_lambda_only_entry_bit_for_bit(capi, n, error):
+    _equal_rates_case(capi, n, error)
+
+
+# one order per instantiation of the kernel (the smallest that selects the width, and the maximum); the error model at the
+# first, a middle and the last
+EVERY_WIDTH = [128, 129, 257, 385, 513, 641, 769, 897, 1025, 1281, 1537, 1793, 2048]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,error", [(n, False) for n in EVERY_WIDTH] + [(n, True) for n in (128, 641, 2048)])
+def test_equal_rates_are_the_lambda_only_entry_at_every_width(capi, n, error):
+    assert sorted({width(m) for m in EVERY_WIDTH}) == WIDTHS
+    _equal_rates_case(capi, n, error)
 
 
 @pytest.mark.gpu

@@ -27,7 +27,7 @@ LAMBDAS = [0.0011, 0.002, 0.0051, 0.0034]
 
 
 def width(n):
-    """E of launch_family_lambda's CAFE_FL_CASE ladder at matrix order n."""
+    """E of launch_family_lambda's width dispatch (for_lane_width) at matrix order n."""
     return next(E for E in WIDTHS if n <= 64 * E)
 
 

@@ -1,4 +1,4 @@
-"""Scratch: the two-rate K1 (bd_matrix_lm.hip) next to K1 (bd_matrix.hip) -- sibling of tools/k1_time.py.  The HIP-event time
+"""Scratch: K1's two-rate instantiation (bd_matrix_lm.hip) next to the lambda = mu one (bd_matrix.hip) -- sibling of tools/k1_time.py.  The HIP-event time
 of the matrix build inside scorer calls (stats `ms_matrices`) and the whole call (`ms_total`) at the bench's matrix shape
 (order 751, K = 8: 1320 matrices), on one context in one process: without death rates (K1), with mu = lambda (the two-rate
 kernel on K1's own values) and with mu = 0.7 lambda."""

@@ -1,6 +1,6 @@
 """Scratch: K1 (bd_matrix_build) alone -- the HIP-event time of the matrix build inside scorer calls (stats `ms_matrices`) at
 the bench's matrix shape (order 751, 1320 matrices: independent of the number of families) and on the mammals fixture
-(order 141).  With a library built with -D'CAFE_EXPERIMENT_K1_STORE_IF=&& n < 0' (bd_matrix.hip) the same figure is the build
+(order 141).  With a library built with -D'CAFE_EXPERIMENT_K1_STORE_IF=&& n < 0' (bd_matrix_build.h) the same figure is the build
 without its global stores: how much of K1 is the latency chain of the row steps and how much the write of the pools."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
