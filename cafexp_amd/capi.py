@@ -21,6 +21,7 @@ CAFE_MAX_CATEGORIES = 32
 CAFE_FLAG_NO_DEDUP = 1
 CAFE_FLAG_NO_SUBTREE_DEDUP = 2
 CAFE_MODEL_BASE, CAFE_MODEL_GAMMA = 0, 1
+CAFE_ROOT_MAX, CAFE_ROOT_SUM = 0, 1
 
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -52,6 +53,10 @@ class CafeFamilyOut(C.Structure):
 class CafeMarginalOut(C.Structure):
     _fields_ = [("mean", _f64p), ("mode", _i32p), ("lo", _i32p), ("hi", _i32p), ("p_increase", _f64p), ("p_decrease", _f64p),
                 ("log_evidence", _f64p), ("failed", _i32p)]
+
+
+class CafeGradientOut(C.Structure):
+    _fields_ = [("family_lnl", _f64p), ("d_lambda", _f64p), ("d_mu", _f64p), ("d_multiplier", _f64p), ("failed", _i32p)]
 
 
 class CafeHistoryOut(C.Structure):
@@ -94,6 +99,7 @@ EXPORTS = [
     "cafe_debug_fail_next", "cafe_debug_column_extents", "cafe_debug_leaf_transposes", "cafe_simulate",
     "cafe_score_per_family", "cafe_marginal_reconstruct", "cafe_debug_marginal_gemm", "cafe_sample_histories", "cafe_debug_history_batches",
     "cafe_set_death_rates", "cafe_bd_rates", "cafe_build_matrices_lm", "cafe_score_per_family_lm", "cafe_simulate_lm",
+    "cafe_score_gradient", "cafe_bd_rates_grad",
 ]
 CAFE_COMM_ID_BYTES = 128
 
@@ -169,6 +175,10 @@ def load():
     L.cafe_set_death_rates.argtypes = [C.c_void_p, _f64p]
     L.cafe_bd_rates.restype = C.c_int
     L.cafe_bd_rates.argtypes = [C.c_double, C.c_double, C.c_double, _f64p]
+    L.cafe_score_gradient.restype = C.c_int
+    L.cafe_score_gradient.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.POINTER(CafeGradientOut)]
+    L.cafe_bd_rates_grad.restype = C.c_int
+    L.cafe_bd_rates_grad.argtypes = [C.c_double, C.c_double, C.c_double, _f64p]
     L.cafe_probe_fp64_mfma.restype = C.c_int
     L.cafe_probe_fp64_mfma.argtypes = [C.c_int32, _f64p]
     L.cafe_debug_stamps.restype = C.c_int
@@ -424,6 +434,27 @@ class Context:
         self._check(self._lib.cafe_marginal_reconstruct(self._h, C.byref(cp), float(level), C.byref(mo)))
         return res
 
+    def score_gradient(self, pr: Params, root_rule="max", alpha: float = 1.0, death_rates: Optional[bool] = None) -> dict:
+        """cafe_score_gradient: every family's log likelihood and its derivative in the rates at pr.  root_rule "max"
+        differentiates what score() returns per family, "sum" marginal_reconstruct's log_evidence.  Returns numpy arrays:
+        family_lnl and failed [n_families], d_lambda [n_families][n_lambdas] (along lambda = mu unless death rates are set),
+        d_mu of the same shape while death rates are set (death_rates: whether to ask for it; None asks the last
+        set_death_rates of this object), d_multiplier [n_families][K] with the gamma model."""
+        rule = {"max": CAFE_ROOT_MAX, "sum": CAFE_ROOT_SUM}.get(root_rule, root_rule)
+        cp, keep = self._params(pr, alpha)
+        F, nl = self.n_families, self.problem.n_lambdas
+        res = {"family_lnl": np.empty(F), "d_lambda": np.empty((F, nl)), "failed": np.empty(F, dtype=np.int32)}
+        if getattr(self, "_death_rates", False) if death_rates is None else death_rates:
+            res["d_mu"] = np.empty((F, nl))
+        if pr.multipliers is not None:
+            res["d_multiplier"] = np.empty((F, len(pr.multipliers)))
+        go = CafeGradientOut()
+        for name, t in CafeGradientOut._fields_:
+            if name in res:
+                setattr(go, name, _p(res[name], t))
+        self._check(self._lib.cafe_score_gradient(self._h, C.byref(cp), int(rule), C.byref(go)))
+        return res
+
     def sample_histories(self, pr: Params, n_draws: int, seed: int, alpha: float = 1.0, sizes: bool = True) -> dict:
         """cafe_sample_histories: n_draws ancestral histories of every family from the posterior of marginal_reconstruct's
         model.  Returns numpy arrays: sizes int32 [n_draws][n_families][n_nodes] (left out with sizes=False: then only
@@ -621,12 +652,14 @@ class Context:
         lambdas[i] and death rate mus[i] (one per lambda index); None restores lambda = mu."""
         if mus is None:
             self._check(self._lib.cafe_set_death_rates(self._h, None))
+            self._death_rates = False
             return
         mu = np.ascontiguousarray(np.atleast_1d(mus), dtype=np.float64)
         pb = getattr(self, "problem", None)                  # (a shard borrowed from a Sharded object does not know its problem)
         if pb is not None and mu.shape != (pb.n_lambdas,):
             raise ValueError("mus must have %d entries" % pb.n_lambdas)
         self._check(self._lib.cafe_set_death_rates(self._h, _p(mu, _f64p)))
+        self._death_rates = True
 
     def set_graphs(self, on: bool):
         """False: enqueue every call launch by launch instead of replaying its captured hipGraph."""
@@ -720,6 +753,16 @@ def bd_rates(lam: float, mu: float, t: float):
     if rc:
         raise CafeError("cafe_bd_rates failed with code %d" % rc)
     return float(out[0]), float(out[1]), bool(out[2])
+
+
+def bd_rates_grad(lam: float, mu: float, t: float):
+    """cafe_bd_rates_grad: (d alpha / d lambda, d alpha / d mu, d beta / d lambda, d beta / d mu) at the quantized key
+    (lambda, mu, t).  Host code: needs no GPU."""
+    out = np.empty(4)
+    rc = load().cafe_bd_rates_grad(float(lam), float(mu), float(t), _p(out, _f64p))
+    if rc:
+        raise CafeError("cafe_bd_rates_grad failed with code %d" % rc)
+    return tuple(float(x) for x in out)
 
 
 def build_matrices_lm(n: int, lambdas, mus, ts, device: int = 0, layout: int = 0) -> np.ndarray:

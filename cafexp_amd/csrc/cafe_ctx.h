@@ -1,5 +1,5 @@
 // Internal: the context behind the C ABI handle and what the translation units of the library share.  cafe_create.hip builds
-// it, cafe_score.hip is the scorer's call path, cafe_debug.hip reads it back; reconstruct.hip, marginal.hip, history.hip,
+// it, cafe_score.hip is the scorer's call path, cafe_debug.hip reads it back; reconstruct.hip, marginal.hip, gradient.hip, history.hip,
 // pvalues.hip and family_lambda.hip are the calls beside the scorer (their common frame: cafe_call.h), cafe_sharded.hip the multi-GPU layer.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -323,6 +323,9 @@ int reconstruct_impl(cafe_ctx* c, const cafe_params* pr, const float* root_prior
 int branch_probabilities_impl(cafe_ctx* c, const cafe_params* pr, const int32_t* sizes, double* out);
 // Marginal reconstruction: posterior sizes, intervals and branch change probabilities (marginal.hip)
 int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_marginal_out* out);
+// Per-family derivatives of log Z in the rates on the same two passes (gradient.hip)
+int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const cafe_gradient_out* out);
+void bd_rates_grad(double lambda, double mu, double t, double out[4]);     // plain doubles in, no quantization
 // Ancestral histories drawn from the posterior of the same model (history.hip)
 int history_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_draws, uint64_t seed, const cafe_history_out* out);
 // Device-side p-values (pvalues.hip) and what it needs from cafe_create.hip and cafe_score.hip: a context over the same tree

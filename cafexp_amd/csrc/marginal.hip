@@ -33,23 +33,6 @@ namespace {
 constexpr int kMT = 64, kNT = 128, kKT = 16;
 constexpr int kLdA = kMT + 16, kLdX = kNT + 16;
 
-enum { kUp = 0, kDown = 1, kSplit = 2 };
-
-struct GemmParams {
-    const double* Pt;       // k-major matrix of the branch above v
-    int ldp;
-    const double* X;        // up: B_v (rows = sizes of v); down / split: G_v (rows = sizes of v's parent)
-    int64_t ld;             // columns of every panel of the batch (a multiple of 128)
-    int nr;                 // output rows: up: parent sizes 1..nr; down / split: sizes 0..nr-1 of v
-    int nk;                 // contraction: up: sizes 0..nk-1 of v; down / split: parent sizes 1..nk
-    int mask;               // split: 1 keeps i < j (the branch expanded), 2 keeps i > j (it contracted)
-    double* out1;           // up: F_v;  down: O_v;  split: D
-    double* out2;           // up: B_parent (store or multiply);  down: the node's accumulation panel
-    const double* Bv;       // down / split: B_v
-    double pk;              // down: weight of the category
-    int first;              // down: first category (the accumulation panel is stored, not added to)
-};
-
 template <int MODE, bool MUL>
 __global__ __launch_bounds__(256) void marginal_gemm_kernel(const GemmParams a) {
     __shared__ __attribute__((aligned(16))) double As[kKT * kLdA];
@@ -342,9 +325,12 @@ __global__ __launch_bounds__(256) void marginal_leaf_summary_kernel(const double
     out.hi[f] = hi < 0 ? last : hi;
 }
 
-// One GEMM launch between the timer's marks; share: the part of its K tiles that runs
+}  // namespace
+
+// One GEMM launch between the timer's marks; share: the part of its K tiles that runs (declared in marginal_up.h, which
+// cafe_score_gradient shares it through)
 template <int MODE>
-int launch_gemm(cafe_ctx* c, const GemmParams& g, bool mul, hipStream_t s, GemmTimer& timer, double share = 1.0) {
+int launch_gemm(cafe_ctx* c, const GemmParams& g, bool mul, hipStream_t s, GemmTimer& timer, double share) {
     dim3 grid((unsigned)(g.ld / kNT), (unsigned)((g.nr + kMT - 1) / kMT));
     timer.mark(s);
     if constexpr (MODE == kUp) {
@@ -356,7 +342,9 @@ int launch_gemm(cafe_ctx* c, const GemmParams& g, bool mul, hipStream_t s, GemmT
     return CAFE_OK;
 }
 
-}  // namespace
+template int launch_gemm<kUp>(cafe_ctx*, const GemmParams&, bool, hipStream_t, GemmTimer&, double);
+template int launch_gemm<kDown>(cafe_ctx*, const GemmParams&, bool, hipStream_t, GemmTimer&, double);
+template int launch_gemm<kSplit>(cafe_ctx*, const GemmParams&, bool, hipStream_t, GemmTimer&, double);
 
 // dst = (src0) * the factors of `mult` (interior: stored F panels, leaves: gathered), rows 0..nrows-1
 int marginal_product(cafe_ctx* c, const UpPanels& w, const double* src0, double* dst, int nrows, const std::vector<int>& mult, int k, int64_t f0, int64_t ld,

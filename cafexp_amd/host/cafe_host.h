@@ -287,6 +287,31 @@ struct history_result {
 void write_history_reports(const history_result& res, double level, const std::string& model_identifier, const std::string& dir,
                            const std::vector<const clade*>& order);
 
+// cafe_score_gradient's outputs in the table's family order: the per-family scores of the model's likelihood
+struct gradient_result {
+    size_t n_lambdas = 0, n_categories = 0;                          // n_categories: 0 for the base model
+    std::vector<double> family_lnl, d_lambda, d_mu, d_multiplier;    // [family], [family][lambda] (d_mu: with death rates), [family][category]
+    std::vector<int32_t> failed;
+};
+// Standard errors from per-family scores (standard_errors.cpp): information = sum_f s_f s_f^T over the families with finite
+// scores, covariance = its inverse.  ok = false (every SE and correlation NaN) when the information matrix is singular or
+// too ill-conditioned to invert.
+struct standard_errors {
+    std::vector<std::string> names;
+    std::vector<double> estimate, se, correlation, total_score, information;     // correlation, information: [P][P]
+    size_t families_used = 0, families_left_out = 0;
+    bool ok = false;
+};
+// scores[family][parameter]
+standard_errors compute_standard_errors(const std::vector<std::string>& names, const std::vector<double>& estimates,
+                                        const std::vector<double>& scores, size_t n_families);
+// d multiplier_k / d alpha of the discrete gamma (get_gamma) by central differences with h = alpha / 100: the routine's
+// quantiles are good to about 1e-6, so a smaller step would differentiate its noise
+std::vector<double> multiplier_slopes(size_t n_categories, double alpha);
+// <Model>_standard_errors.txt: one line per parameter (name, estimate, SE, Wald 95 % interval), the correlation matrix, the
+// total score and what the errors are conditional on
+void write_standard_errors(const standard_errors& se, const std::string& model_identifier, const std::string& dir, const std::string& conditional_on);
+
 // The two models whose infer_family_likelihoods runs on the GPU through the C ABI.
 class hip_model_base : public model {
 protected:
@@ -329,6 +354,9 @@ public:
     // expanded / contracted -- with the model's lambda, prior, error model and (gamma) categories; columns in `order`
     marginal_result marginal_reconstruction(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, double level,
                                             const std::vector<const clade*>& order);
+    // Per-family scores of the model's likelihood at its current parameters (cafe_score_gradient; root_rule CAFE_ROOT_MAX is
+    // what infer_family_likelihoods sums)
+    gradient_result score_gradient(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, int root_rule);
     // Whole ancestral histories drawn from the same posterior (cafe_sample_histories), counted per draw on the device:
     // how many families expanded / contracted on every branch and the net change, rows in `order`
     history_result sample_histories(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, int n_draws, uint64_t seed,

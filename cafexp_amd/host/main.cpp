@@ -14,6 +14,7 @@
 #include <sstream>
 
 #include "cafe_host.h"
+#include "../../include/cafe_mi355x.h"
 
 using namespace cafe;
 
@@ -32,6 +33,9 @@ static void usage() {
         "                  fitted model (seed S, else -s, else 1); with -o: <Model>_sampled_change.tab, per node the mean and the equal-tailed\n"
         "                  interval (LEVEL of --reconstruct-marginal, default 0.95) across the draws of how many families expanded /\n"
         "                  contracted on its branch and of the net change in genes; one GPU\n"
+        "                  [--standard-errors]   after the search: the per-family scores at the optimum, the standard error of every\n"
+        "                  estimated lambda, mu (--estimate-mu) and alpha from their outer product, Wald 95 %% intervals, correlations and the\n"
+        "                  total score -> <Model>_standard_errors.txt in -o OUTDIR (default results); one GPU, not with -b or --simulate\n"
         "  --gpus N: the scorer calls shard the families over devices 0..N-1 (one host thread per GPU, one RCCL all-reduce per call)\n"
         "lambda per family (the reference's -b): cafexp_hip -t TREE -i FAMILIES -b [-y LAMBDA_TREE] [-e ERRMODEL] [-p [L]] [-z] [-s SEED] [-I MAXITER]\n"
         "                  [--workspace BYTES] [-o OUTDIR]   writes OUTDIR (default results)/Base_lambda_per_family.txt, one line per family\n"
@@ -169,6 +173,7 @@ int main(int argc, char** argv) {
     std::string mu_list;                                         // --mu: fixed death rates, one per lambda
     bool estimate_mu = false;                                    // --estimate-mu: death rates searched with the lambdas
     std::string family_mu;                                       // --family-mu (with -b): rates, or "estimate"
+    bool do_standard_errors = false;                             // --standard-errors
     unsigned seed = 0;
     bool have_seed = false;
     for (int i = 1; i < argc; ++i) {
@@ -186,6 +191,7 @@ int main(int argc, char** argv) {
         else if (a == "--mu") mu_list = next();
         else if (a == "--estimate-mu") estimate_mu = true;
         else if (a == "--family-mu") family_mu = next();
+        else if (a == "--standard-errors") do_standard_errors = true;
         else if (a == "-e") { use_err = true; err_path = optional(); }
         else if (a == "-p") { use_poisson = true; std::string v = optional(); poisson = v.empty() ? 0 : std::stod(v); }
         else if (a == "-f") rootdist_path = next();
@@ -221,6 +227,7 @@ int main(int argc, char** argv) {
         if (tree_path.empty()) { usage(); return 2; }
         if (estimate_mu) { std::fprintf(stderr, "cafexp_hip: --simulate draws under given rates: --estimate-mu is not supported with it (give --mu)\n"); return 1; }
         if (!family_mu.empty()) { std::fprintf(stderr, "cafexp_hip: --family-mu sets the death rates of -b: it is not supported without -b\n"); return 1; }
+        if (do_standard_errors) { std::fprintf(stderr, "cafexp_hip: --standard-errors belongs to a fitted model: --simulate is not supported with it\n"); return 1; }
         if (have_seed) randomizer_engine.seed(seed);
         return simulate_main(tree_path, fam_path, rootdist_path, lambda_tree_path, multi, err_path, use_err, fixed_lambda, fixed_alpha, k,
                              simulate_n, simulate_on_device, have_seed ? seed : randomizer_engine(), device, sim_workspace, out_dir, mu_list);
@@ -236,6 +243,12 @@ int main(int argc, char** argv) {
     if (!family_mu.empty() && !per_family) {
         std::fprintf(stderr, "cafexp_hip: --family-mu sets the death rates of -b: it is not supported without -b\n");
         return 1;
+    }
+    if (do_standard_errors) {
+        const char* why = nullptr;
+        if (gpus_given) why = "--standard-errors runs on one GPU: --gpus is not supported with it";
+        else if (per_family) why = "--standard-errors needs one fitted model: -b is not supported with it";
+        if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
     }
     if (do_marginal) {
         const char* why = nullptr;
@@ -489,6 +502,44 @@ int main(int argc, char** argv) {
             history_failed = hr.failed_count();
             if (!out_dir.empty()) write_history_reports(hr, marginal_level, mdl->name(), out_dir, order);
         }
+        // standard errors of what the search estimated, from the per-family scores of the searched objective at the optimum
+        standard_errors se;
+        std::vector<double> slopes;
+        if (do_standard_errors) {
+            auto g = dynamic_cast<hip_gamma_model*>(mdl.get());
+            const bool lambda_searched = scorer && !d.p_lambda, alpha_searched = scorer && g && !(fixed_alpha > 0);
+            const gradient_result gr = mdl->score_gradient(d.p_prior.get(), d.rootdist, CAFE_ROOT_MAX);
+            const std::vector<double> lv = mdl->get_lambda()->values();
+            const size_t nl = gr.n_lambdas, F = d.gene_families.size();
+            std::vector<std::string> names;
+            std::vector<double> est;
+            auto rate_name = [&](const char* what, size_t i) { return nl == 1 ? std::string(what) : what + std::to_string(i + 1); };
+            if (lambda_searched) for (size_t i = 0; i < nl; ++i) { names.push_back(rate_name("Lambda", i)); est.push_back(lv[i]); }
+            if (estimate_mu) for (size_t i = 0; i < nl; ++i) { names.push_back(rate_name("Mu", i)); est.push_back(mdl->death_rates()[i]); }
+            if (alpha_searched) { names.push_back("Alpha"); est.push_back(g->get_alpha()); slopes = multiplier_slopes(gr.n_categories, g->get_alpha()); }
+            if (names.empty()) throw std::runtime_error("--standard-errors: no parameter was estimated (lambda, mu and alpha are all fixed)");
+            const size_t P = names.size();
+            std::vector<double> scores(F * P);
+            for (size_t f = 0; f < F; ++f) {
+                size_t at = f * P;
+                if (lambda_searched) for (size_t i = 0; i < nl; ++i) scores[at++] = gr.d_lambda[f * nl + i];
+                if (estimate_mu) for (size_t i = 0; i < nl; ++i) scores[at++] = gr.d_mu[f * nl + i];
+                if (alpha_searched) {
+                    double s = 0;
+                    for (size_t c = 0; c < gr.n_categories; ++c) s += gr.d_multiplier[f * gr.n_categories + c] * slopes[c];
+                    scores[at++] = s;
+                }
+            }
+            se = compute_standard_errors(names, est, scores, F);
+            if (!se.ok) std::fprintf(stderr, "cafexp_hip: warning: the information matrix of the scores is singular or ill-conditioned: no standard errors\n");
+            std::string cond = em ? "the error model (epsilon is not differentiated)" : "the model as fitted";
+            if (!lambda_searched) cond += ", the fixed lambda";
+            if (!mdl->death_rates().empty() && !estimate_mu) cond += ", the fixed mu";
+            if (g && !alpha_searched) cond += ", the fixed alpha";
+            const std::string dir = out_dir.empty() ? "results" : out_dir;
+            if (::mkdir(dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("Failed to create directory " + dir);
+            write_standard_errors(se, mdl->name(), dir, cond);
+        }
         std::printf("{\"model\": \"%s\", ", mdl->name().c_str());
         print_num("neg_lnl", score);
         std::printf("\"n_families\": %zu, \"max_family_size\": %d, \"max_root_family_size\": %d, \"seconds_per_call\": %.6f, ",
@@ -526,6 +577,24 @@ int main(int argc, char** argv) {
             std::printf(", \"marginal\": {\"seconds\": %.3f, \"level\": %.17g, \"failed\": %zu}", marginal_s, marginal_level, marginal_failed);
         if (do_histories)
             std::printf(", \"histories\": {\"seconds\": %.3f, \"draws\": %d, \"failed\": %zu}", history_s, history_draws, history_failed);
+        if (do_standard_errors) {
+            auto list = [](const char* key, const std::vector<double>& v) {
+                std::printf("\"%s\": [", key);
+                for (size_t i = 0; i < v.size(); ++i) {
+                    if (std::isfinite(v[i])) std::printf("%s%.17g", i ? ", " : "", v[i]);
+                    else std::printf("%s\"nan\"", i ? ", " : "");
+                }
+                std::printf("]");
+            };
+            std::printf(", \"standard_errors\": {\"parameters\": [");
+            for (size_t i = 0; i < se.names.size(); ++i) std::printf("%s\"%s\"", i ? ", " : "", se.names[i].c_str());
+            std::printf("], ");
+            list("estimate", se.estimate); std::printf(", ");
+            list("se", se.se); std::printf(", ");
+            list("total_score", se.total_score); std::printf(", ");
+            if (!slopes.empty()) { list("dmultiplier_dalpha", slopes); std::printf(", "); }
+            std::printf("\"families\": %zu, \"left_out\": %zu}", se.families_used, se.families_left_out);
+        }
         std::printf("}\n");
     } catch (const std::exception& e) {
         std::fprintf(stderr, "cafexp_hip: %s\n", e.what());

@@ -401,6 +401,42 @@ int cafe_sample_histories(cafe_ctx* ctx, const cafe_params* params, int32_t n_dr
  * unique families and the passes over the draws that each batch took */
 int cafe_debug_history_batches(cafe_ctx* ctx, int32_t* column_batches, int32_t* draw_passes);
 
+/* Per-family score vectors: the derivative of every family's log likelihood in the rates, at the call's parameters.  The
+ * model, the passes and the GEMM are cafe_marginal_reconstruct's; the branch joint G_v P_v B_v that it forms is contracted
+ * with dP_v / d theta through a linear transform of B_v and one more GEMM per interior branch and free rate (no derivative
+ * matrix is built).  root_rule chooses what is differentiated:
+ *   CAFE_ROOT_MAX  what cafe_score returns per family -- base model: max_s(log L_s + log prior_s), first maximum; gamma model:
+ *                  log sum_k p_k max_s(L_s prior_s); the root weight of a category is the prior at its arg max, zero elsewhere;
+ *   CAFE_ROOT_SUM  cafe_marginal_reconstruct's log_evidence, Z = sum_k p_k sum_s prior[s-1] B_root[s].
+ * Outputs (host pointers, any may be NULL), rows in the problem's family order:
+ *   family_lnl[n_families] the differentiated value; failed[n_families] = 1 where Z is 0 or not finite: that family's doubles
+ *     are NaN (the call still returns CAFE_OK);
+ *   d_lambda[n_families][n_lambdas]: without death rates the derivative along lambda = mu (a non-NULL d_mu is then
+ *     CAFE_ERR_STATE); with death rates set d_lambda and d_mu[n_families][n_lambdas] are the two partials, and at mus == lambdas
+ *     their sum is the unset call's d_lambda to rounding;
+ *   d_multiplier[n_families][K], gamma model only (CAFE_ERR_ARGUMENT otherwise): the derivative in multipliers[k], which
+ *     scales both rates of category k; cat_probs are held fixed.
+ * The derivative is that of the smooth likelihood at the quantized keys the call builds its matrices from (cafe_bd_rates).  A
+ * branch whose key is marked zero (cafe_bd_rates out[2]) contributes 0.  The error model is read, not differentiated.
+ * CAFE_ERR_ARGUMENT for invalid rates, a bad K or root_rule; CAFE_ERR_STATE on a context with a communicator attached.  The
+ * columns are processed in batches that fit the problem's workspace_limit (0 = automatic); a value never depends on the
+ * batches, identical families get identical rows.  cafe_family_results is not meaningful after this call; a later cafe_score
+ * is unaffected; cafe_debug_marginal_gemm reports this call's GEMM launches. */
+enum { CAFE_ROOT_MAX = 0, CAFE_ROOT_SUM = 1 };
+typedef struct cafe_gradient_out {
+    double*  family_lnl;    /* [n_families] log Z_f under the chosen root rule */
+    double*  d_lambda;      /* [n_families][n_lambdas] */
+    double*  d_mu;          /* [n_families][n_lambdas]; only while death rates are set */
+    double*  d_multiplier;  /* [n_families][K]; gamma model only */
+    int32_t* failed;        /* [n_families] */
+} cafe_gradient_out;
+int cafe_score_gradient(cafe_ctx* ctx, const cafe_params* params, int32_t root_rule, const cafe_gradient_out* out);
+/* out = {d alpha / d lambda, d alpha / d mu, d beta / d lambda, d beta / d mu} of cafe_bd_rates' alpha and beta at the same
+ * quantized key.  Evaluated without a division by lambda - mu (expm1 away from it, a series where |lambda - mu| t is small), so
+ * finite and accurate as mu -> lambda; at equal quantized rates the four limits, whose sums out[0] + out[1] and out[2] + out[3]
+ * both equal t / (1 + lambda t)^2, the derivative of the lambda = mu kernels' alpha.  Pure host code, no device needed. */
+int cafe_bd_rates_grad(double lambda, double mu, double t, double out[4]);
+
 /* Introspection for parity tests: the transition matrix the last call built for the branch above
  * `node` in category k (N x N row-major, N = max(M,R)+1: matrix_cache::get_matrix; for an interior
  * branch the columns c > M, which the prune never reads, are not materialised and come back 0), and the root
