@@ -1,7 +1,7 @@
 // Per-family score vectors: the derivative of every family's log likelihood in the rates.
 //
 // The model, the panels and the two passes are cafe_marginal_reconstruct's (marginal.hip): B_v and F_v from the up pass
-// (marginal_up.h), O_v and G_v = O_parent prod_{siblings} F_w from the down pass, so that for the branch above v
+// (sum_product.h), O_v and G_v = O_parent prod_{siblings} F_w from the down pass, so that for the branch above v
 //     d Z / d theta = G_v^T (dP_v / d theta) B_v.
 // Row i of P is the i-fold convolution of the single-lineage law, generating function ((a + (1-a-b) z) / (1 - b z))^i with
 // a = alpha, b = beta of the branch (cafe_bd_rates).  With H the causal filter y[j] = x[j] + b y[j-1], S the shift by one and
@@ -18,11 +18,9 @@
 // Gamma model: the sums are kept per (category, rate index, rate) and combined on the host,
 //     d/d lambda_q = sum_k m_k d/d(lambda_q m_k),      d/d m_k = sum_q lambda_q d/d(lambda_q m_k) + mu_q d/d(mu_q m_k).
 #include <cmath>
-#include <limits>
 #include <vector>
 
-#include "cafe_call.h"
-#include "marginal_up.h"
+#include "sum_product.h"
 
 namespace cafe {
 
@@ -230,7 +228,7 @@ __global__ __launch_bounds__(256) void gradient_finish_kernel(const double* __re
     for (int k = 0; k < K; ++k) z += probs[k] * zk[(int64_t)k * stride + f];
     Z[f] = z;
     const double nan = __builtin_nan("");
-    const bool bad = !(z > 0.0) || z > 1.7976931348623157e308;
+    const bool bad = evidence_failed(z);
     lnl[f] = bad ? nan : (lbest ? lbest[f] : log(z));
     for (int j = 0; j < n_acc; ++j) {
         double* o = acc + (int64_t)j * stride + f;
@@ -270,31 +268,19 @@ BranchRates branch_rates(const cafe_ctx* c, const double* lambdas, int v, double
 }  // namespace
 
 int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const cafe_gradient_out* out) {
-    if (c->comm) { set_err(c, "cafe_score_gradient: not valid on a context with a communicator attached"); return CAFE_ERR_STATE; }
-    if (!pr || !pr->lambdas || !pr->prior || !out) { set_err(c, "cafe_score_gradient: lambdas, prior and out are required"); return CAFE_ERR_ARGUMENT; }
+    if (const int rc = check_call_args(c, "cafe_score_gradient", pr, out)) return rc;
     if (root_rule != CAFE_ROOT_MAX && root_rule != CAFE_ROOT_SUM) { set_err(c, "cafe_score_gradient: root_rule must be CAFE_ROOT_MAX or CAFE_ROOT_SUM"); return CAFE_ERR_ARGUMENT; }
-    const bool gamma = pr->model == CAFE_MODEL_GAMMA;
-    const int K = gamma ? pr->n_categories : 1;
-    if (gamma && (K < 1 || K > c->Kmax || !pr->multipliers || !pr->cat_probs)) {
-        set_err(c, "cafe_score_gradient: gamma model needs 1..%d categories with multipliers and cat_probs", c->Kmax);
-        return CAFE_ERR_ARGUMENT;
-    }
-    if (!gamma && out->d_multiplier) { set_err(c, "cafe_score_gradient: d_multiplier needs the gamma model"); return CAFE_ERR_ARGUMENT; }
-    if (!rates_valid(c, pr->lambdas)) { set_err(c, "cafe_score_gradient: invalid lambda or death rate"); return CAFE_ERR_ARGUMENT; }
-    if (pr->error_model && c->n_dev < 1) { set_err(c, "cafe_score_gradient: the context was created without an error model"); return CAFE_ERR_ARGUMENT; }
+    if (pr->model != CAFE_MODEL_GAMMA && out->d_multiplier) { set_err(c, "cafe_score_gradient: d_multiplier needs the gamma model"); return CAFE_ERR_ARGUMENT; }
+    if (const int rc = check_model_args(c, "cafe_score_gradient", pr)) return rc;
     if (out->d_mu && c->mus.empty()) { set_err(c, "cafe_score_gradient: d_mu needs death rates (cafe_set_death_rates)"); return CAFE_ERR_STATE; }
-    hipStream_t s = nullptr;
-    if (const int rc = begin_matrix_call(c, pr->lambdas, gamma ? pr->multipliers : nullptr, K, &s)) return rc;
-
-    const int M = c->M, R = c->R, n = c->n_nodes, rows = c->N, nl = c->n_lambdas;
+    PosteriorCall pc;
+    if (const int rc = open_posterior_call(c, pr, &pc)) return rc;
+    pc.timer.on = c->profile != 0;
+    hipStream_t s = pc.s;
+    UpPanels& up = pc.up;
+    const int M = c->M, R = c->R, rows = c->N, nl = c->n_lambdas, K = pc.K, nI = pc.nI;
     const int n_par = c->mus.empty() ? 1 : 2;
-    const bool has_err = pr->error_model != nullptr;
-    const int n_dev = has_err ? c->n_dev : 1;
-    const bool use_log = !gamma && root_rule == CAFE_ROOT_MAX;
-    UpPanels up;
-    up.bidx.assign(n, -1);
-    int nI = 0;
-    for (int v = 0; v < n; ++v) if (c->leaf_taxon[v] < 0) up.bidx[v] = nI++;
+    const bool gamma = pc.gamma, use_log = !gamma && root_rule == CAFE_ROOT_MAX;
     const int n_acc = K * nl * n_par;
 
     // workspace per column: B, F and O of every interior node; G, the scanned panel Bt, Ft and the panel that takes the down
@@ -307,9 +293,8 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
         return rc;
     const int ldp = c->pool.ld;
     const size_t leaf_mat = (size_t)(std::max(M, R) + 1) * ldp;
-    DevBuf wd, dsmall, dleaf;
-    const size_t n_small = (size_t)2 * R + K + (has_err ? (size_t)(M + 1) * n_dev : 0);
-    if (hipMalloc(&wd.p, dbl_per_col * cols * sizeof(double)) != hipSuccess || hipMalloc(&dsmall.p, sizeof(double) * n_small) != hipSuccess ||
+    DevBuf wd, dleaf;
+    if (hipMalloc(&wd.p, dbl_per_col * cols * sizeof(double)) != hipSuccess || alloc_constants(c, kWithPriorLogs, &pc) != hipSuccess ||
         hipMalloc(&dleaf.p, sizeof(double) * leaf_mat * n_par) != hipSuccess) {
         (void)hipGetLastError();
         set_err(c, "cafe_score_gradient: cannot allocate the workspace (%lld columns)", (long long)cols);
@@ -318,9 +303,7 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
     HIP_TRY(c, hipMemsetAsync(wd.p, 0, dbl_per_col * cols * sizeof(double), s));
     HIP_TRY(c, hipMemsetAsync(dleaf.p, 0, sizeof(double) * leaf_mat * n_par, s));
     const int64_t pstride = (int64_t)rows * cols;
-    double* d_B = static_cast<double*>(wd.p);
-    double* d_F = d_B + (int64_t)nI * pstride;
-    double* d_O = d_F + (int64_t)nI * pstride;
+    double* d_O = up.place(wd.p, nI, pstride);
     double* d_G = d_O + (int64_t)nI * pstride;
     double* d_Bt = d_G + pstride;
     double* d_Ft = d_Bt + pstride;
@@ -330,81 +313,59 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
     double* d_Z = d_acc + (int64_t)n_acc * cols;
     double* d_lnl = d_Z + cols;
     double* d_lbest = d_lnl + cols;
-    double* d_prior = static_cast<double*>(dsmall.p);
-    double* d_logprior = d_prior + R;
-    double* d_probs = d_logprior + R;
-    double* d_err = has_err ? d_probs + K : nullptr;
     double* d_dP[2] = {static_cast<double*>(dleaf.p), n_par > 1 ? static_cast<double*>(dleaf.p) + leaf_mat : nullptr};
-    {
-        std::vector<double> h(n_small);
-        for (int j = 0; j < R; ++j) { h[j] = (double)pr->prior[j]; h[R + j] = std::log(h[j]); }      // compute() returns a float
-        for (int k = 0; k < K; ++k) h[2 * R + k] = gamma ? pr->cat_probs[k] : 1.0;
-        if (has_err) std::copy(pr->error_model, pr->error_model + (size_t)(M + 1) * n_dev, h.begin() + 2 * R + K);
-        HIP_TRY(c, hipMemcpyAsync(dsmall.p, h.data(), sizeof(double) * n_small, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-    }
-    up.B = d_B; up.F = d_F; up.pstride = pstride; up.err = d_err; up.n_dev = n_dev;
+    if (const int rc = upload_constants(c, pr, &pc)) return rc;
 
-    GemmTimer timer;
-    timer.on = c->profile != 0;
     std::vector<double> h_acc((size_t)n_acc * cols), h_Z(cols), h_lnl(cols);
-    const double nan = std::numeric_limits<double>::quiet_NaN();
 
+    const std::vector<Branch> down = branches_down(c);
     for (int64_t f0 = 0; f0 < c->Fp; f0 += cols) {
         const int64_t ld = std::min<int64_t>(cols, c->Fp - f0);
         const unsigned gb = (unsigned)((ld + 255) / 256);
-        auto panel = [&](double* arena, int v) { return arena + (int64_t)up.bidx[v] * pstride; };
         HIP_TRY(c, hipMemsetAsync(d_acc, 0, sizeof(double) * (size_t)n_acc * cols, s));
         for (int k = 0; k < K; ++k) {
             const double pk = gamma ? pr->cat_probs[k] : 1.0, mult = gamma ? pr->multipliers[k] : 1.0;
             auto acc_of = [&](int v, int p) { return d_acc + (((int64_t)k * nl + c->lam_idx[v]) * n_par + p) * cols; };
-            if (const int rc = marginal_up_pass(c, up, k, f0, ld, s, timer)) return rc;
-            CAFE_LAUNCH(c, gradient_root_kernel, dim3(gb), dim3(256), 0, s, panel(d_B, c->root), d_prior, d_logprior, R, ld, panel(d_O, c->root),
+            if (const int rc = marginal_up_pass(c, up, k, f0, ld, s, pc.timer)) return rc;
+            CAFE_LAUNCH(c, gradient_root_kernel, dim3(gb), dim3(256), 0, s, up.panel(up.B, c->root), pc.prior, pc.logprior, R, ld, up.panel(d_O, c->root),
                         d_zk + (int64_t)k * cols, d_lbest, (int)root_rule, use_log ? 1 : 0);
             const double* filtered = nullptr;                // the leaf matrix whose derivative rows the scratch holds
-            for (int p = n - 1; p >= 0; --p) {               // parents before children
-                if (c->leaf_taxon[p] >= 0) continue;
-                const int np = p == c->root ? R : M;
-                for (int v : c->children[p]) {
-                    const bool leaf = c->leaf_taxon[v] >= 0;
-                    const BranchRates br = branch_rates(c, pr->lambdas, v, mult);
-                    if (leaf && br.zero) continue;           // a saturated branch adds nothing
-                    std::vector<int> sib;
-                    for (int w : c->children[p]) if (w != v) sib.push_back(w);
-                    if (const int rc = marginal_product(c, up, panel(d_O, p), d_G, np + 1, sib, k, f0, ld, s)) return rc;
-                    if (leaf) {
-                        const double* P = leaf_matrix(c, v, k);
-                        if (P != filtered) {
-                            FilterParams fp{};
-                            fp.P = P; fp.ldp = ldp; fp.np = std::max(M, R); fp.M = M; fp.n_par = n_par; fp.beta = br.beta;
-                            for (int q = 0; q < n_par; ++q) { fp.ca[q] = br.da[q]; fp.cb[q] = br.db[q] * (1 - br.alpha); fp.dP[q] = d_dP[q]; }
-                            if (n_par == 1) fp.dP[1] = d_dP[0];
-                            CAFE_LAUNCH(c, gradient_leaf_filter_kernel, dim3((unsigned)((fp.np + kFR - 1) / kFR)), dim3(256), 0, s, fp);
-                            filtered = P;
-                        }
-                        CAFE_LAUNCH(c, gradient_leaf_kernel, dim3(gb), dim3(256), 0, s, d_G, np, ld, d_dP[0], (const double*)d_dP[1], ldp,
-                                    leaf_counts(c, v, f0), (const double*)d_err, n_dev, M, pk, acc_of(v, 0), n_par > 1 ? acc_of(v, 1) : nullptr);
-                        continue;
+            for (const Branch& b : down) {
+                const int v = b.v, np = b.np;
+                const bool leaf = c->leaf_taxon[v] >= 0;
+                const BranchRates br = branch_rates(c, pr->lambdas, v, mult);
+                if (leaf && br.zero) continue;               // a saturated branch adds nothing
+                GemmParams g;
+                if (const int rc = down_branch(c, up, d_O, d_G, b, k, pk, f0, ld, s, &g)) return rc;
+                if (leaf) {
+                    const double* P = leaf_matrix(c, v, k);
+                    if (P != filtered) {
+                        FilterParams fp{};
+                        fp.P = P; fp.ldp = ldp; fp.np = std::max(M, R); fp.M = M; fp.n_par = n_par; fp.beta = br.beta;
+                        for (int q = 0; q < n_par; ++q) { fp.ca[q] = br.da[q]; fp.cb[q] = br.db[q] * (1 - br.alpha); fp.dP[q] = d_dP[q]; }
+                        if (n_par == 1) fp.dP[1] = d_dP[0];
+                        CAFE_LAUNCH(c, gradient_leaf_filter_kernel, dim3((unsigned)((fp.np + kFR - 1) / kFR)), dim3(256), 0, s, fp);
+                        filtered = P;
                     }
-                    GemmParams g{};
-                    g.Pt = interior_matrix(c, v, k);
-                    g.ldp = c->kpool.ld; g.X = d_G; g.ld = ld; g.nr = M + 1; g.nk = np;
-                    g.out1 = panel(d_O, v); g.out2 = d_S; g.Bv = panel(d_B, v); g.pk = pk; g.first = 1;
-                    if (const int rc = launch_gemm<kDown>(c, g, false, s, timer)) return rc;
-                    if (br.zero) continue;
-                    for (int q = 0; q < n_par; ++q) {
-                        CAFE_LAUNCH(c, gradient_scan_kernel, dim3(gb), dim3(256), 0, s, (const double*)panel(d_B, v), M, ld, br.beta, br.da[q],
-                                    br.db[q] * (1 - br.alpha), d_Bt);
-                        GemmParams u{};
-                        u.Pt = g.Pt; u.ldp = g.ldp; u.X = d_Bt; u.ld = ld; u.nr = np; u.nk = M + 1;
-                        u.out1 = d_Ft; u.out2 = d_Ft;        // a plain store, twice
-                        if (const int rc = launch_gemm<kUp>(c, u, false, s, timer)) return rc;
-                        CAFE_LAUNCH(c, gradient_dot_kernel, dim3(gb), dim3(256), 0, s, (const double*)d_G, (const double*)d_Ft, np, ld, pk, acc_of(v, q));
-                    }
+                    CAFE_LAUNCH(c, gradient_leaf_kernel, dim3(gb), dim3(256), 0, s, d_G, np, ld, d_dP[0], (const double*)d_dP[1], ldp,
+                                leaf_counts(c, v, f0), up.err, up.n_dev, M, pk, acc_of(v, 0), n_par > 1 ? acc_of(v, 1) : nullptr);
+                    continue;
+                }
+                g.out2 = d_S; g.first = 1;                   // the posterior product goes to a panel nobody reads
+                if (const int rc = launch_gemm<kDown>(c, g, false, s, pc.timer)) return rc;
+                if (br.zero) continue;
+                for (int q = 0; q < n_par; ++q) {
+                    CAFE_LAUNCH(c, gradient_scan_kernel, dim3(gb), dim3(256), 0, s, (const double*)up.panel(up.B, v), M, ld, br.beta, br.da[q],
+                                br.db[q] * (1 - br.alpha), d_Bt);
+                    GemmParams u{};
+                    u.Pt = g.Pt; u.ldp = g.ldp; u.X = d_Bt; u.ld = ld; u.nr = np; u.nk = M + 1;
+                    u.out1 = d_Ft; u.out2 = d_Ft;            // a plain store, twice
+                    if (const int rc = launch_gemm<kUp>(c, u, false, s, pc.timer)) return rc;
+                    CAFE_LAUNCH(c, gradient_dot_kernel, dim3(gb), dim3(256), 0, s, (const double*)d_G, (const double*)d_Ft, np, ld, pk, acc_of(v, q));
                 }
             }
         }
-        CAFE_LAUNCH(c, gradient_finish_kernel, dim3(gb), dim3(256), 0, s, (const double*)d_zk, (const double*)d_probs, K, ld, cols,
+        CAFE_LAUNCH(c, gradient_finish_kernel, dim3(gb), dim3(256), 0, s, (const double*)d_zk, pc.probs, K, ld, cols,
                     use_log ? (const double*)d_lbest : nullptr, d_acc, n_acc, d_Z, d_lnl);
         HIP_TRY(c, hipMemcpyAsync(h_acc.data(), d_acc, sizeof(double) * (size_t)n_acc * cols, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(h_Z.data(), d_Z, sizeof(double) * (size_t)ld, hipMemcpyDeviceToHost, s));
@@ -412,8 +373,8 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
         HIP_TRY(c, hipStreamSynchronize(s));
         for_each_family_of_chunk(c, f0, ld, [&](int64_t f, int64_t col) {
             const double z = h_Z[col];
-            const bool bad = !(z > 0.0) || !std::isfinite(z);
-            if (out->family_lnl) out->family_lnl[f] = bad ? nan : h_lnl[col];
+            const bool bad = evidence_failed(z);
+            if (out->family_lnl) out->family_lnl[f] = bad ? kNaN : h_lnl[col];
             if (out->failed) out->failed[f] = bad ? 1 : 0;
             auto a = [&](int k, int q, int p) { return h_acc[(((size_t)k * nl + q) * n_par + p) * cols + col]; };
             for (int q = 0; q < nl; ++q) {
@@ -423,8 +384,8 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
                     dl += m * a(k, q, 0);
                     if (n_par > 1) dm += m * a(k, q, 1);
                 }
-                if (out->d_lambda) out->d_lambda[f * nl + q] = bad ? nan : dl;
-                if (out->d_mu) out->d_mu[f * nl + q] = bad ? nan : dm;
+                if (out->d_lambda) out->d_lambda[f * nl + q] = bad ? kNaN : dl;
+                if (out->d_mu) out->d_mu[f * nl + q] = bad ? kNaN : dm;
             }
             if (out->d_multiplier)
                 for (int k = 0; k < K; ++k) {
@@ -433,17 +394,11 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
                         d += pr->lambdas[q] * a(k, q, 0);
                         if (n_par > 1) d += c->mus[q] * a(k, q, 1);
                     }
-                    out->d_multiplier[f * K + k] = bad ? nan : d;
+                    out->d_multiplier[f * K + k] = bad ? kNaN : d;
                 }
         });
     }
-    c->upload_pending = false;
-    // the matrices of this call stay readable (cafe_get_matrix); per-family scorer results are not meaningful
-    c->have_results = true;
-    c->rootmax_last = true;
-    c->last_rejected = false;
-    c->marginal_gemm_ms = timer.on ? timer.total_ms() : 0.0;
-    c->marginal_gemm_flops = timer.flops;
+    close_posterior_call(c, &pc.timer);
     return CAFE_OK;
 }
 

@@ -1,6 +1,6 @@
 // Ancestral histories drawn from the posterior (cafe_sample_histories): whole assignments of a size to
 // every node of a family's tree, drawn top-down from the conditionals that the up pass of the marginal reconstruction
-// (marginal_up.h; B, F and P as in marginal.hip's header comment) makes available:
+// (sum_product.h; B, F and P as in marginal.hip's header comment) makes available:
 //   category  k   ~ cat_probs[k] Z_k,              Z_k = sum_{s=1..R} prior[s-1] B_root^k[s]
 //   root      s   ~ prior[s-1] B_root^k[s],        s = 1..R
 //   interior  j   ~ P_v^k[i][j] B_v^k[j],          j = 0..M, i the size its parent drew (row 0 of P is e_0: j = 0)
@@ -16,12 +16,10 @@
 // eight steps are issued together, the prefix is summed in index order.  The total of an interior draw is the F_v[i] that
 // the up pass stored.
 #include <cmath>
-#include <limits>
 #include <string>
 #include <vector>
 
-#include "cafe_call.h"
-#include "marginal_up.h"
+#include "sum_product.h"
 #include "tree_sampler.h"
 
 namespace cafe {
@@ -40,8 +38,6 @@ struct Units {
     int32_t* cat;                        // [unit] category, -1: a failed family
     int32_t* sizes;                      // [node][unit]
 };
-
-__device__ inline bool bad_z(double z) { return !(z > 0.0) || z > 1.7976931348623157e308; }
 
 // Zk[k][f] = sum_s prior[s-1] B_root[s][f], summed in the order the root draw walks
 __global__ __launch_bounds__(256) void history_rootz_kernel(const double* __restrict__ B, const double* __restrict__ prior, int R, int64_t ld,
@@ -74,7 +70,7 @@ __global__ __launch_bounds__(256) void history_category_kernel(const Units un, c
     double z = 0.0;
     for (int k = 0; k < K; ++k) z += probs[k] * Zk[(int64_t)k * cols + col];
     int cat = -1;
-    if (!bad_z(z)) {
+    if (!evidence_failed(z)) {
         cat = 0;
         if (K > 1) {
             const double target = uniform01(un.family[fi], root, 2u * (uint32_t)d + 1u, un.k0, un.k1) * z;
@@ -254,28 +250,15 @@ __global__ __launch_bounds__(256) void history_transpose_kernel(const Units un, 
 }  // namespace
 
 int history_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_draws, uint64_t seed, const cafe_history_out* out) {
-    if (c->comm) { set_err(c, "cafe_sample_histories: not valid on a context with a communicator attached"); return CAFE_ERR_STATE; }
-    if (!pr || !pr->lambdas || !pr->prior || !out) { set_err(c, "cafe_sample_histories: lambdas, prior and out are required"); return CAFE_ERR_ARGUMENT; }
+    if (const int rc = check_call_args(c, "cafe_sample_histories", pr, out)) return rc;
     if (n_draws < 1 || n_draws > 65536) { set_err(c, "cafe_sample_histories: n_draws must lie in 1..65536"); return CAFE_ERR_ARGUMENT; }
-    const bool gamma = pr->model == CAFE_MODEL_GAMMA;
-    const int K = gamma ? pr->n_categories : 1;
-    if (gamma && (K < 1 || K > c->Kmax || !pr->multipliers || !pr->cat_probs)) {
-        set_err(c, "cafe_sample_histories: gamma model needs 1..%d categories with multipliers and cat_probs", c->Kmax);
-        return CAFE_ERR_ARGUMENT;
-    }
-    if (!rates_valid(c, pr->lambdas)) { set_err(c, "cafe_sample_histories: invalid lambda or death rate"); return CAFE_ERR_ARGUMENT; }
-    if (pr->error_model && c->n_dev < 1) { set_err(c, "cafe_sample_histories: the context was created without an error model"); return CAFE_ERR_ARGUMENT; }
-    hipStream_t s = nullptr;
-    if (const int rc = begin_matrix_call(c, pr->lambdas, gamma ? pr->multipliers : nullptr, K, &s)) return rc;
-
-    const int M = c->M, R = c->R, n = c->n_nodes, rows = c->N;
-    const bool has_err = pr->error_model != nullptr;
-    const int n_dev = has_err ? c->n_dev : 1;
+    if (const int rc = check_model_args(c, "cafe_sample_histories", pr)) return rc;
+    PosteriorCall pc;
+    if (const int rc = open_posterior_call(c, pr, &pc)) return rc;
+    hipStream_t s = pc.s;
+    UpPanels& up = pc.up;
+    const int M = c->M, R = c->R, n = c->n_nodes, rows = c->N, K = pc.K, nI = pc.nI, n_dev = pc.n_dev;
     const bool want_sizes = out->sizes != nullptr, want_counts = out->n_increase || out->n_decrease || out->net_change;
-    UpPanels up;
-    up.bidx.assign(n, -1);
-    int nI = 0;
-    for (int v = 0; v < n; ++v) if (c->leaf_taxon[v] < 0) up.bidx[v] = nI++;
 
     // What does not depend on the batches comes off the budget first: the three count arrays of all draws, the prior, the
     // category weights, the error model and the parents.  Of the rest three quarters hold B and F of every interior node
@@ -285,7 +268,7 @@ int history_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_draws, uint64_t s
     size_t budget = 0;
     if (const int rc = panel_budget(c, &budget)) return rc;
     const size_t count_len = (size_t)n_draws * n;
-    const size_t fixed = sizeof(unsigned long long) * 3 * count_len + sizeof(double) * ((size_t)R + K + (has_err ? (size_t)(M + 1) * n_dev : 0)) + sizeof(int32_t) * n;
+    const size_t fixed = sizeof(unsigned long long) * 3 * count_len + sizeof(double) * ((size_t)R + K + (pc.has_err ? (size_t)(M + 1) * n_dev : 0)) + sizeof(int32_t) * n;
     if (fixed >= budget) {
         set_err(c, "cafe_sample_histories: %zu bytes of workspace cannot hold the counts of %d draws", budget, (int)n_draws);
         return CAFE_ERR_MEMORY;
@@ -311,11 +294,9 @@ int history_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_draws, uint64_t s
     c->history_batches = (int)batch_fams.size();
     c->history_passes = (int)((n_draws + pass_draws - 1) / pass_draws);
 
-    DevBuf wd, wz, dprior, derr, dprobs, dfam, dcol, dcat, dsz, dtr, dcnt, dpar;
+    DevBuf wd, wz, dfam, dcol, dcat, dsz, dtr, dcnt, dpar;
     if (hipMalloc(&wd.p, (size_t)2 * nI * rows * cols * sizeof(double)) != hipSuccess || hipMalloc(&wz.p, (size_t)(K + 1) * cols * sizeof(double)) != hipSuccess ||
-        hipMalloc(&dprior.p, sizeof(double) * R) != hipSuccess || hipMalloc(&dprobs.p, sizeof(double) * K) != hipSuccess ||
-        (has_err && hipMalloc(&derr.p, sizeof(double) * (size_t)(M + 1) * n_dev) != hipSuccess) ||
-        hipMalloc(&dfam.p, sizeof(int64_t) * max_fams) != hipSuccess || hipMalloc(&dcol.p, sizeof(int32_t) * max_fams) != hipSuccess ||
+        alloc_constants(c, kNoPriorLogs, &pc) != hipSuccess || hipMalloc(&dfam.p, sizeof(int64_t) * max_fams) != hipSuccess || hipMalloc(&dcol.p, sizeof(int32_t) * max_fams) != hipSuccess ||
         hipMalloc(&dcat.p, sizeof(int32_t) * max_units) != hipSuccess || hipMalloc(&dsz.p, sizeof(int32_t) * (size_t)n * max_units) != hipSuccess ||
         (want_sizes && hipMalloc(&dtr.p, sizeof(int32_t) * (size_t)n * max_units) != hipSuccess) ||
         hipMalloc(&dcnt.p, sizeof(unsigned long long) * 3 * count_len) != hipSuccess || hipMalloc(&dpar.p, sizeof(int32_t) * n) != hipSuccess) {
@@ -326,35 +307,18 @@ int history_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_draws, uint64_t s
     HIP_TRY(c, hipMemsetAsync(wd.p, 0, (size_t)2 * nI * rows * cols * sizeof(double), s));
     HIP_TRY(c, hipMemsetAsync(dcnt.p, 0, sizeof(unsigned long long) * 3 * count_len, s));
     const int64_t pstride = (int64_t)rows * cols;
-    up.B = static_cast<double*>(wd.p);
-    up.F = up.B + (int64_t)nI * pstride;
-    up.pstride = pstride;
-    up.n_dev = n_dev;
+    up.place(wd.p, nI, pstride);
     double* d_Zk = static_cast<double*>(wz.p);               // [K][cols]
     double* d_Z = d_Zk + (int64_t)K * cols;
     unsigned long long* d_inc = static_cast<unsigned long long*>(dcnt.p);
     unsigned long long *d_dec = d_inc + count_len, *d_net = d_dec + count_len;
-    {
-        std::vector<double> hp(R), probs(K, 1.0);
-        for (int j = 0; j < R; ++j) hp[j] = (double)pr->prior[j];          // compute() returns a float
-        if (gamma) for (int k = 0; k < K; ++k) probs[k] = pr->cat_probs[k];
-        std::vector<int32_t> par(c->parent.begin(), c->parent.end());
-        HIP_TRY(c, hipMemcpyAsync(dprior.p, hp.data(), sizeof(double) * R, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(dprobs.p, probs.data(), sizeof(double) * K, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(dpar.p, par.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-        if (has_err) HIP_TRY(c, hipMemcpyAsync(derr.p, pr->error_model, sizeof(double) * (size_t)(M + 1) * n_dev, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-    }
-    const double* d_prior = static_cast<const double*>(dprior.p);
-    const double* d_probs = static_cast<const double*>(dprobs.p);
-    const double* d_err = has_err ? static_cast<const double*>(derr.p) : nullptr;
-    up.err = d_err;
+    const std::vector<int32_t> par(c->parent.begin(), c->parent.end());
+    HIP_TRY(c, hipMemcpyAsync(dpar.p, par.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+    if (const int rc = upload_constants(c, pr, &pc)) return rc;      // its synchronise covers the parents' copy
 
-    GemmTimer timer;                                         // off: the marginal call's measurement hook is not this call's
     std::vector<double> h_Z(cols);
     std::vector<int64_t> fams;
     std::vector<int32_t> fcols, h_cat, h_sizes;
-    const double nan = std::numeric_limits<double>::quiet_NaN();
     const int root = c->root;
 
     for (int64_t f0 = 0; f0 < c->Fp; f0 += cols) {
@@ -366,17 +330,17 @@ int history_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_draws, uint64_t s
         // ---- every Z_k; afterwards the panels hold category K - 1
         int held = -1;
         for (int k = 0; k < K; ++k) {
-            if (const int rc = marginal_up_pass(c, up, k, f0, ld, s, timer)) return rc;
+            if (const int rc = marginal_up_pass(c, up, k, f0, ld, s, pc.timer)) return rc;
             held = k;
-            CAFE_LAUNCH(c, history_rootz_kernel, dim3(gb), dim3(256), 0, s, up.panel(up.B, root), d_prior, R, ld, d_Zk + (int64_t)k * cols);
+            CAFE_LAUNCH(c, history_rootz_kernel, dim3(gb), dim3(256), 0, s, up.panel(up.B, root), pc.prior, R, ld, d_Zk + (int64_t)k * cols);
         }
-        CAFE_LAUNCH(c, history_z_kernel, dim3(gb), dim3(256), 0, s, d_Zk, d_probs, K, cols, ld, d_Z);
+        CAFE_LAUNCH(c, history_z_kernel, dim3(gb), dim3(256), 0, s, d_Zk, pc.probs, K, cols, ld, d_Z);
         HIP_TRY(c, hipMemcpyAsync(h_Z.data(), d_Z, sizeof(double) * (size_t)ld, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
         for (int64_t i = 0; i < nb; ++i) {
             const double z = h_Z[fcols[i]];
-            const bool bad = !(z > 0.0) || !std::isfinite(z);
-            if (out->log_evidence) out->log_evidence[fams[i]] = bad ? nan : std::log(z);
+            const bool bad = evidence_failed(z);
+            if (out->log_evidence) out->log_evidence[fams[i]] = bad ? kNaN : std::log(z);
             if (out->failed) out->failed[fams[i]] = bad ? 1 : 0;
         }
         if (nb == 0 || !(want_sizes || want_counts || out->category)) continue;
@@ -395,18 +359,18 @@ int history_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_draws, uint64_t s
             un.cat = static_cast<int32_t*>(dcat.p);
             un.sizes = static_cast<int32_t*>(dsz.p);
             const unsigned ub = (unsigned)((un.n_units + 255) / 256);
-            CAFE_LAUNCH(c, history_category_kernel, dim3(ub), dim3(256), 0, s, un, d_Zk, d_probs, K, cols, root);
+            CAFE_LAUNCH(c, history_category_kernel, dim3(ub), dim3(256), 0, s, un, d_Zk, pc.probs, K, cols, root);
             for (int k = K - 1; k >= 0; --k) {
                 if (k != held) {
-                    if (const int rc = marginal_up_pass(c, up, k, f0, ld, s, timer)) return rc;
+                    if (const int rc = marginal_up_pass(c, up, k, f0, ld, s, pc.timer)) return rc;
                     held = k;
                 }
-                CAFE_LAUNCH(c, history_root_kernel, dim3(ub), dim3(256), 0, s, un, k, up.panel(up.B, root), d_prior, R, ld, d_Zk + (int64_t)k * cols, root);
+                CAFE_LAUNCH(c, history_root_kernel, dim3(ub), dim3(256), 0, s, un, k, up.panel(up.B, root), pc.prior, R, ld, d_Zk + (int64_t)k * cols, root);
                 for (int v = n - 1; v >= 0; --v) {           // parents before children
                     if (v == root) continue;
                     const int p = c->parent[v];
                     if (c->leaf_taxon[v] >= 0)
-                        CAFE_LAUNCH(c, history_leaf_kernel, dim3(ub), dim3(256), 0, s, un, k, v, p, leaf_matrix(c, v, k), c->pool.ld, leaf_counts(c, v, f0), d_err,
+                        CAFE_LAUNCH(c, history_leaf_kernel, dim3(ub), dim3(256), 0, s, un, k, v, p, leaf_matrix(c, v, k), c->pool.ld, leaf_counts(c, v, f0), up.err,
                                     n_dev, M);
                     else
                         CAFE_LAUNCH(c, history_node_kernel, dim3(ub), dim3(256), 0, s, un, k, v, p, interior_matrix(c, v, k), c->kpool.ld, up.panel(up.B, v),
@@ -443,11 +407,7 @@ int history_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_draws, uint64_t s
             if (dst[a]) HIP_TRY(c, hipMemcpyAsync(dst[a], d_inc + a * count_len, sizeof(int64_t) * count_len, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
     }
-    c->upload_pending = false;
-    // the matrices of this call stay readable (cafe_get_matrix); per-family scorer results are not meaningful
-    c->have_results = true;
-    c->rootmax_last = true;
-    c->last_rejected = false;
+    close_posterior_call(c, nullptr);                        // no timer: cafe_debug_marginal_gemm keeps its figures
     return CAFE_OK;
 }
 

@@ -13,176 +13,13 @@
 // Gamma model: every category runs the same launches; the un-normalised posteriors are accumulated with weight cat_probs[k]
 // in one panel per interior node and summarised once (the base model is K = 1).
 #include <cmath>
-#include <cstring>
-#include <limits>
 #include <vector>
 
-#include "cafe_call.h"
-#include "marginal_up.h"
+#include "sum_product.h"
 
 namespace cafe {
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------------------------- GEMM
-// Block tile 64 rows x 128 families, K step 16; wave w owns the 32 families 32w.. over all 64 rows: 4 x 2 accumulator tiles
-// of v_mfma_f64_16x16x4_f64 (A fragment: row = lane & 15, k = lane >> 4; B fragment: k = lane >> 4, column = lane & 15;
-// D: row = (lane >> 4) + 4 * register, column = lane & 15).  Both tiles are staged in LDS k-major with a 16-double pad, so
-// that the four k rows a fragment load touches start 32 banks apart.  The next K step's global loads are in flight while
-// the current one is multiplied.  Every load is guarded by the matrix's extent: nothing depends on padding rows.
-constexpr int kMT = 64, kNT = 128, kKT = 16;
-constexpr int kLdA = kMT + 16, kLdX = kNT + 16;
-
-template <int MODE, bool MUL>
-__global__ __launch_bounds__(256) void marginal_gemm_kernel(const GemmParams a) {
-    __shared__ __attribute__((aligned(16))) double As[kKT * kLdA];
-    __shared__ __attribute__((aligned(16))) double Xs[kKT * kLdX];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l15 = lane & 15, l4 = lane >> 4;
-    const int r0 = blockIdx.y * kMT;
-    const int64_t c0 = (int64_t)blockIdx.x * kNT;
-    const int nr = a.nr, nk = a.nk, ldp = a.ldp;
-    const int64_t ld = a.ld;
-    // split: the K tiles strictly off the diagonal run whole (or not at all), the ones that meet it take the mask
-    int kbeg = 0, kend = nk;
-    if (MODE == kSplit) {
-        if (a.mask == 1) kend = min(nk, r0 + kMT - 1);       // i < j <= r0 + 63, i = k + 1
-        else kbeg = r0;                                      // i > j >= r0
-    }
-    typedef double d4 __attribute__((ext_vector_type(4)));
-    d4 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
-    double ra[4];
-    double2 rx[4];
-    const int xoff = MODE == kUp ? 0 : 1;
-    auto load = [&](int k0) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (MODE == kUp) {                               // A[r][k] = Pt[k][r]: 64 consecutive rows per k
-                const int r = r0 + lane, k = k0 + wave + 4 * u;
-                ra[u] = (r < nr && k < nk) ? a.Pt[(int64_t)k * ldp + r] : 0.0;
-            } else {                                         // A[r][k] = Pt[r][k]: 16 consecutive k per row
-                const int k = k0 + (tid & 15), r = r0 + (tid >> 4) + 16 * u;
-                bool ok = r < nr && k < nk;
-                if (MODE == kSplit) ok = ok && (a.mask == 1 ? k + 1 < r : k + 1 > r);
-                ra[u] = ok ? a.Pt[(int64_t)r * ldp + k] : 0.0;
-            }
-            const int k = k0 + wave + 4 * u;
-            rx[u] = k < nk ? *reinterpret_cast<const double2*>(a.X + (int64_t)(k + xoff) * ld + c0 + 2 * lane) : make_double2(0.0, 0.0);
-        }
-    };
-    if (kbeg < kend) load(kbeg);
-    for (int k0 = kbeg; k0 < kend; k0 += kKT) {
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (MODE == kUp) As[(wave + 4 * u) * kLdA + lane] = ra[u];
-            else As[(tid & 15) * kLdA + (tid >> 4) + 16 * u] = ra[u];
-            *reinterpret_cast<double2*>(&Xs[(wave + 4 * u) * kLdX + 2 * lane]) = rx[u];
-        }
-        __syncthreads();
-        if (k0 + kKT < kend) load(k0 + kKT);
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            double af[4], bf[2];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = As[(4 * s4 + l4) * kLdA + 16 * i + l15];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bf[j] = Xs[(4 * s4 + l4) * kLdX + 32 * wave + 16 * j + l15];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[j], acc[i][j], 0, 0, 0);
-        }
-    }
-    // ---- epilogue
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int r = r0 + 16 * i + l4 + 4 * q;
-                if (r >= nr) continue;
-                const int64_t c = c0 + 32 * wave + 16 * j + l15;
-                double v = acc[i][j][q];
-                if (MODE == kUp) {                           // parent size r + 1
-                    const int64_t o = (int64_t)(r + 1) * ld + c;
-                    a.out1[o] = v;
-                    a.out2[o] = MUL ? a.out2[o] * v : v;
-                } else if (MODE == kDown) {
-                    const int64_t o = (int64_t)r * ld + c;
-                    if (r == 0) v += a.X[c];                 // P[0][j] = delta(j, 0)
-                    a.out1[o] = v;
-                    const double t = a.pk * (v * a.Bv[o]);
-                    a.out2[o] = a.first ? t : a.out2[o] + t;
-                } else {
-                    const int64_t o = (int64_t)r * ld + c;
-                    a.out1[o] = v * a.Bv[o];
-                }
-            }
-    if (MODE == kUp && blockIdx.y == 0 && tid < kNT) {       // F[0] = B_v[0]
-        const int64_t c = c0 + tid;
-        const double v = a.X[c];
-        a.out1[c] = v;
-        a.out2[c] = MUL ? a.out2[c] * v : v;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------- small kernels
-// The scorer's leaf factor (leaf_reduce.hip): P[i][x], or with an error model sum_t err[x][t] P[i][x - half + t], taps
-// outside [0, M] dropped, in the scorer's tap order.
-__device__ inline double leaf_factor(const double* __restrict__ P, int ldp, int i, int x, const double* __restrict__ err, int n_dev, int M) {
-    const double* row = P + (int64_t)i * ldp;
-    if (err == nullptr) return row[x];
-    const int half = (n_dev - 1) / 2;
-    double fac = 0.0;
-    for (int t = 0; t < n_dev; ++t) {
-        const int c = x - half + t;
-        if (c < 0 || c > M) continue;
-        fac += row[c] * err[(int64_t)x * n_dev + t];
-    }
-    return fac;
-}
-
-// dst[i][f] = (src0 ? src0[i][f] : 1) * prod panels[i][f] * prod leaf factors(i, x_f), i = 0..rows-1.  The up pass forms the
-// product of a node's leaf children with it, the down pass G_v = O_parent * the siblings' factors.
-constexpr int kMaxProd = 6;
-struct ProdParams {
-    const double* src0;
-    double* dst;
-    int64_t ld;
-    int rows;
-    int n_pan, n_leaf;
-    const double* pan[kMaxProd];
-    const double* P[kMaxProd];          // row-major matrices of the leaf branches
-    const int32_t* cnt[kMaxProd];       // observed counts of the batch's columns
-    int ldp;
-    const double* err;
-    int n_dev, M;
-};
-__global__ __launch_bounds__(256) void marginal_product_kernel(const ProdParams a) {
-    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= a.ld) return;
-    int x[kMaxProd];
-#pragma unroll
-    for (int l = 0; l < kMaxProd; ++l) x[l] = l < a.n_leaf ? a.cnt[l][f] : 0;
-    const int i0 = blockIdx.y * 16, i1 = min(a.rows, i0 + 16);
-    for (int i = i0; i < i1; ++i) {
-        const int64_t o = (int64_t)i * a.ld + f;
-        double v = a.src0 ? a.src0[o] : 1.0;
-#pragma unroll
-        for (int p = 0; p < kMaxProd; ++p)
-            if (p < a.n_pan) v *= a.pan[p][o];
-#pragma unroll
-        for (int l = 0; l < kMaxProd; ++l)
-            if (l < a.n_leaf) v *= leaf_factor(a.P[l], a.ldp, i, x[l], a.err, a.n_dev, a.M);
-        a.dst[o] = v;
-    }
-}
 
 // root weighting: O_root[s] = prior[s-1], acc_root[s] (+)= p_k prior[s-1] B_root[s], s = 1..R; row 0 carries no mass
 __global__ __launch_bounds__(256) void marginal_root_kernel(const double* __restrict__ B, const double* __restrict__ prior, int R, int64_t ld,
@@ -264,7 +101,7 @@ __global__ __launch_bounds__(256) void marginal_summary_kernel(const double* __r
         z = Z[f];
     }
     const double nan = __builtin_nan("");
-    if (!(z > 0.0) || z > 1.7976931348623157e308) {          // Z = 0 or not finite: a failed family
+    if (evidence_failed(z)) {
         out.mean[f] = nan; out.mode[f] = -1; out.lo[f] = -1; out.hi[f] = -1; out.p_inc[f] = nan; out.p_dec[f] = nan;
         return;
     }
@@ -293,7 +130,7 @@ __global__ __launch_bounds__(256) void marginal_leaf_summary_kernel(const double
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (f >= ld) return;
     const double z = Z[f], nan = __builtin_nan("");
-    if (!(z > 0.0) || z > 1.7976931348623157e308) {
+    if (evidence_failed(z)) {
         out.mean[f] = nan; out.mode[f] = -1; out.lo[f] = -1; out.hi[f] = -1; out.p_inc[f] = nan; out.p_dec[f] = nan;
         return;
     }
@@ -327,104 +164,20 @@ __global__ __launch_bounds__(256) void marginal_leaf_summary_kernel(const double
 
 }  // namespace
 
-// One GEMM launch between the timer's marks; share: the part of its K tiles that runs (declared in marginal_up.h, which
-// cafe_score_gradient shares it through)
-template <int MODE>
-int launch_gemm(cafe_ctx* c, const GemmParams& g, bool mul, hipStream_t s, GemmTimer& timer, double share) {
-    dim3 grid((unsigned)(g.ld / kNT), (unsigned)((g.nr + kMT - 1) / kMT));
-    timer.mark(s);
-    if constexpr (MODE == kUp) {
-        if (mul) CAFE_LAUNCH(c, (marginal_gemm_kernel<kUp, true>), grid, dim3(256), 0, s, g);
-    }
-    if (MODE != kUp || !mul) CAFE_LAUNCH(c, (marginal_gemm_kernel<MODE, false>), grid, dim3(256), 0, s, g);
-    timer.mark(s);
-    timer.flops += share * 2.0 * g.nr * g.nk * (double)g.ld;
-    return CAFE_OK;
-}
-
-template int launch_gemm<kUp>(cafe_ctx*, const GemmParams&, bool, hipStream_t, GemmTimer&, double);
-template int launch_gemm<kDown>(cafe_ctx*, const GemmParams&, bool, hipStream_t, GemmTimer&, double);
-template int launch_gemm<kSplit>(cafe_ctx*, const GemmParams&, bool, hipStream_t, GemmTimer&, double);
-
-// dst = (src0) * the factors of `mult` (interior: stored F panels, leaves: gathered), rows 0..nrows-1
-int marginal_product(cafe_ctx* c, const UpPanels& w, const double* src0, double* dst, int nrows, const std::vector<int>& mult, int k, int64_t f0, int64_t ld,
-                     hipStream_t s) {
-    const unsigned gb = (unsigned)((ld + 255) / 256);
-    size_t i = 0;
-    bool started = false;
-    while (i < mult.size() || !started) {
-        ProdParams p{};
-        p.src0 = started ? dst : src0;
-        p.dst = dst; p.ld = ld; p.rows = nrows; p.ldp = c->pool.ld; p.err = w.err; p.n_dev = w.n_dev; p.M = c->M;
-        for (; i < mult.size(); ++i) {
-            const int m = mult[i];
-            if (c->leaf_taxon[m] >= 0) {
-                if (p.n_leaf == kMaxProd) break;
-                p.P[p.n_leaf] = leaf_matrix(c, m, k);
-                p.cnt[p.n_leaf] = leaf_counts(c, m, f0);
-                ++p.n_leaf;
-            } else {
-                if (p.n_pan == kMaxProd) break;
-                p.pan[p.n_pan++] = w.panel(w.F, m);
-            }
-        }
-        CAFE_LAUNCH(c, marginal_product_kernel, dim3(gb, (unsigned)((nrows + 15) / 16)), dim3(256), 0, s, p);
-        started = true;
-    }
-    return CAFE_OK;
-}
-
-// The up pass of category k over the columns f0 .. f0 + ld: children before parents (node order of the problem)
-int marginal_up_pass(cafe_ctx* c, const UpPanels& w, int k, int64_t f0, int64_t ld, hipStream_t s, GemmTimer& timer) {
-    const int M = c->M, R = c->R, n = c->n_nodes;
-    for (int p = 0; p < n; ++p) {
-        if (c->leaf_taxon[p] >= 0) continue;
-        const int np = p == c->root ? R : M;          // parent sizes 1..np
-        std::vector<int> leaves;
-        for (int v : c->children[p]) if (c->leaf_taxon[v] >= 0) leaves.push_back(v);
-        bool started = false;
-        if (!leaves.empty()) {
-            const int rc = marginal_product(c, w, nullptr, w.panel(w.B, p), np + 1, leaves, k, f0, ld, s);
-            if (rc != CAFE_OK) return rc;
-            started = true;
-        }
-        for (int v : c->children[p]) {
-            if (c->leaf_taxon[v] >= 0) continue;
-            GemmParams g{};
-            g.Pt = interior_matrix(c, v, k);
-            g.ldp = c->kpool.ld; g.X = w.panel(w.B, v); g.ld = ld; g.nr = np; g.nk = M + 1;
-            g.out1 = w.panel(w.F, v); g.out2 = w.panel(w.B, p);
-            if (const int rc = launch_gemm<kUp>(c, g, started, s, timer)) return rc;
-            started = true;
-        }
-    }
-    return CAFE_OK;
-}
-
 int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_marginal_out* out) {
-    if (c->comm) { set_err(c, "cafe_marginal_reconstruct: not valid on a context with a communicator attached"); return CAFE_ERR_STATE; }
-    if (!pr || !pr->lambdas || !pr->prior || !out) { set_err(c, "cafe_marginal_reconstruct: lambdas, prior and out are required"); return CAFE_ERR_ARGUMENT; }
+    if (const int rc = check_call_args(c, "cafe_marginal_reconstruct", pr, out)) return rc;
     if (!(level > 0.0 && level < 1.0)) { set_err(c, "cafe_marginal_reconstruct: level must lie in (0, 1)"); return CAFE_ERR_ARGUMENT; }
-    const bool gamma = pr->model == CAFE_MODEL_GAMMA;
-    const int K = gamma ? pr->n_categories : 1;
-    if (gamma && (K < 1 || K > c->Kmax || !pr->multipliers || !pr->cat_probs)) {
-        set_err(c, "cafe_marginal_reconstruct: gamma model needs 1..%d categories with multipliers and cat_probs", c->Kmax);
-        return CAFE_ERR_ARGUMENT;
-    }
-    if (!rates_valid(c, pr->lambdas)) { set_err(c, "cafe_marginal_reconstruct: invalid lambda or death rate"); return CAFE_ERR_ARGUMENT; }
-    if (pr->error_model && c->n_dev < 1) { set_err(c, "cafe_marginal_reconstruct: the context was created without an error model"); return CAFE_ERR_ARGUMENT; }
-    hipStream_t s = nullptr;
-    if (const int rc = begin_matrix_call(c, pr->lambdas, gamma ? pr->multipliers : nullptr, K, &s)) return rc;
-
+    if (const int rc = check_model_args(c, "cafe_marginal_reconstruct", pr)) return rc;
+    PosteriorCall pc;
+    if (const int rc = open_posterior_call(c, pr, &pc)) return rc;
+    pc.timer.on = c->profile != 0;
+    hipStream_t s = pc.s;
+    UpPanels& up = pc.up;
     const int M = c->M, R = c->R, n = c->n_nodes, rows = c->N;      // a panel holds sizes 0..max(M, R)
-    const bool has_err = pr->error_model != nullptr;
-    const int n_dev = has_err ? c->n_dev : 1, n_tap = n_dev;
-    UpPanels up;
-    std::vector<int>& bidx = up.bidx;
+    const int K = pc.K, nI = pc.nI, n_dev = pc.n_dev, n_tap = n_dev;
     std::vector<int> lidx(n, -1);
-    bidx.assign(n, -1);
-    int nI = 0, nL = 0;
-    for (int v = 0; v < n; ++v) { if (c->leaf_taxon[v] < 0) bidx[v] = nI++; else lidx[v] = nL++; }
+    int nL = 0;
+    for (int v = 0; v < n; ++v) if (c->leaf_taxon[v] >= 0) lidx[v] = nL++;
 
     // workspace per column: B, F, O and the accumulation panel of every interior node, G and D, the leaf sums, the branch
     // sums, Z and the summaries
@@ -433,20 +186,16 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
     int64_t cols = 0;
     if (const int rc = column_chunk(c, per_col, "cafe_marginal_reconstruct: not enough device memory for the panels of " + std::to_string(nI) + " interior nodes", &cols))
         return rc;
-    DevBuf wd, wi, dprior, derr;
+    DevBuf wd, wi;
     if (hipMalloc(&wd.p, dbl_per_col * cols * sizeof(double)) != hipSuccess || hipMalloc(&wi.p, (size_t)3 * n * cols * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc(&dprior.p, sizeof(double) * R) != hipSuccess ||
-        (has_err && hipMalloc(&derr.p, sizeof(double) * (size_t)(M + 1) * n_dev) != hipSuccess)) {
+        alloc_constants(c, kNoPriorLogs, &pc) != hipSuccess) {
         (void)hipGetLastError();
         set_err(c, "cafe_marginal_reconstruct: cannot allocate the workspace (%lld columns)", (long long)cols);
         return CAFE_ERR_MEMORY;
     }
     HIP_TRY(c, hipMemsetAsync(wd.p, 0, dbl_per_col * cols * sizeof(double), s));
     const int64_t pstride = (int64_t)rows * cols;
-    double* base = static_cast<double*>(wd.p);
-    double* d_B = base;
-    double* d_F = d_B + (int64_t)nI * pstride;
-    double* d_O = d_F + (int64_t)nI * pstride;
+    double* d_O = up.place(wd.p, nI, pstride);
     double* d_A = d_O + (int64_t)nI * pstride;
     double* d_G = d_A + (int64_t)nI * pstride;
     double* d_D = d_G + pstride;
@@ -459,60 +208,38 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
     int32_t* d_mode = static_cast<int32_t*>(wi.p);
     int32_t* d_lo = d_mode + (int64_t)n * cols;
     int32_t* d_hi = d_lo + (int64_t)n * cols;
-    {
-        std::vector<double> hp(R);
-        for (int j = 0; j < R; ++j) hp[j] = (double)pr->prior[j];          // compute() returns a float
-        HIP_TRY(c, hipMemcpyAsync(dprior.p, hp.data(), sizeof(double) * R, hipMemcpyHostToDevice, s));
-        if (has_err) HIP_TRY(c, hipMemcpyAsync(derr.p, pr->error_model, sizeof(double) * (size_t)(M + 1) * n_dev, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-    }
-    const double* d_prior = static_cast<const double*>(dprior.p);
-    const double* d_err = has_err ? static_cast<const double*>(derr.p) : nullptr;
-    up.B = d_B; up.F = d_F; up.pstride = pstride; up.err = d_err; up.n_dev = n_dev;
+    if (const int rc = upload_constants(c, pr, &pc)) return rc;
 
-    GemmTimer timer;
-    timer.on = c->profile != 0;
     std::vector<double> h_mean((size_t)n * cols), h_pinc((size_t)n * cols), h_pdec((size_t)n * cols), h_Z(cols);
     std::vector<int32_t> h_mode((size_t)n * cols), h_lo((size_t)n * cols), h_hi((size_t)n * cols);
-    const double nan = std::numeric_limits<double>::quiet_NaN();
 
+    const std::vector<Branch> down = branches_down(c);
     for (int64_t f0 = 0; f0 < c->Fp; f0 += cols) {
         const int64_t ld = std::min<int64_t>(cols, c->Fp - f0);
         const unsigned gb = (unsigned)((ld + 255) / 256);
-        auto panel = [&](double* arena, int v) { return arena + (int64_t)bidx[v] * pstride; };
-        auto product = [&](const double* src0, double* dst, int nrows, const std::vector<int>& mult, int k) {
-            return marginal_product(c, up, src0, dst, nrows, mult, k, f0, ld, s);
-        };
         for (int k = 0; k < K; ++k) {
-            const double pk = gamma ? pr->cat_probs[k] : 1.0;
+            const double pk = pc.gamma ? pr->cat_probs[k] : 1.0;
             const int first = k == 0;
-            // ---- up: children before parents (marginal_up_pass, shared with cafe_sample_histories)
-            if (const int rc = marginal_up_pass(c, up, k, f0, ld, s, timer)) return rc;
+            // ---- up: children before parents
+            if (const int rc = marginal_up_pass(c, up, k, f0, ld, s, pc.timer)) return rc;
             // ---- root, then parents before children
-            CAFE_LAUNCH(c, marginal_root_kernel, dim3(gb, (unsigned)((R + 1 + 15) / 16)), dim3(256), 0, s, panel(d_B, c->root), d_prior, R, ld, panel(d_O, c->root),
-                        panel(d_A, c->root), pk, first);
-            for (int p = n - 1; p >= 0; --p) {
-                if (c->leaf_taxon[p] >= 0) continue;
-                const int np = p == c->root ? R : M;
-                for (int v : c->children[p]) {
-                    std::vector<int> sib;
-                    for (int w : c->children[p]) if (w != v) sib.push_back(w);
-                    { const int rc = product(panel(d_O, p), d_G, np + 1, sib, k); if (rc != CAFE_OK) return rc; }
-                    if (c->leaf_taxon[v] >= 0) {
-                        CAFE_LAUNCH(c, marginal_leaf_kernel, dim3(gb), dim3(256), 0, s, d_G, np + 1, ld, leaf_matrix(c, v, k), c->pool.ld, leaf_counts(c, v, f0), d_err,
-                                    n_dev, M, d_leaf + (int64_t)lidx[v] * (n_tap + 2) * cols, pk, first);
-                        continue;
-                    }
-                    GemmParams g{};
-                    g.Pt = interior_matrix(c, v, k);
-                    g.ldp = c->kpool.ld; g.X = d_G; g.ld = ld; g.nr = M + 1; g.nk = np;
-                    g.out1 = panel(d_O, v); g.out2 = panel(d_A, v); g.Bv = panel(d_B, v); g.pk = pk; g.first = first;
-                    if (const int rc = launch_gemm<kDown>(c, g, false, s, timer)) return rc;
-                    for (int m = 1; m <= 2; ++m) {           // the branch split: i < j, then i > j
-                        g.mask = m; g.out1 = d_D; g.out2 = nullptr;
-                        if (const int rc = launch_gemm<kSplit>(c, g, false, s, timer, 0.5)) return rc;      // about half of the K tiles run
-                        CAFE_LAUNCH(c, marginal_colsum_kernel, dim3(gb), dim3(256), 0, s, d_D, M + 1, ld, d_br + ((int64_t)2 * bidx[v] + (m - 1)) * cols, pk, first);
-                    }
+            CAFE_LAUNCH(c, marginal_root_kernel, dim3(gb, (unsigned)((R + 1 + 15) / 16)), dim3(256), 0, s, up.panel(up.B, c->root), pc.prior, R, ld, up.panel(d_O, c->root),
+                        up.panel(d_A, c->root), pk, first);
+            for (const Branch& b : down) {
+                const int v = b.v, np = b.np;
+                GemmParams g;
+                if (const int rc = down_branch(c, up, d_O, d_G, b, k, pk, f0, ld, s, &g)) return rc;
+                if (c->leaf_taxon[v] >= 0) {
+                    CAFE_LAUNCH(c, marginal_leaf_kernel, dim3(gb), dim3(256), 0, s, d_G, np + 1, ld, leaf_matrix(c, v, k), c->pool.ld, leaf_counts(c, v, f0), up.err,
+                                n_dev, M, d_leaf + (int64_t)lidx[v] * (n_tap + 2) * cols, pk, first);
+                    continue;
+                }
+                g.out2 = up.panel(d_A, v); g.first = first;
+                if (const int rc = launch_gemm<kDown>(c, g, false, s, pc.timer)) return rc;
+                for (int m = 1; m <= 2; ++m) {               // the branch split: i < j, then i > j
+                    g.mask = m; g.out1 = d_D; g.out2 = nullptr;
+                    if (const int rc = launch_gemm<kSplit>(c, g, false, s, pc.timer, 0.5)) return rc;      // about half of the K tiles run
+                    CAFE_LAUNCH(c, marginal_colsum_kernel, dim3(gb), dim3(256), 0, s, d_D, M + 1, ld, d_br + ((int64_t)2 * up.bidx[v] + (m - 1)) * cols, pk, first);
                 }
             }
         }
@@ -524,11 +251,11 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
                               d_pinc + (int64_t)v * cols, d_pdec + (int64_t)v * cols};
                 if (c->leaf_taxon[v] >= 0) {
                     CAFE_LAUNCH(c, marginal_leaf_summary_kernel, dim3(gb), dim3(256), 0, s, d_leaf + (int64_t)lidx[v] * (n_tap + 2) * cols, leaf_counts(c, v, f0), n_dev,
-                                has_err ? 1 : 0, M, ld, d_Z, level, so);
+                                pc.has_err ? 1 : 0, M, ld, d_Z, level, so);
                 } else {
                     const bool is_root = v == c->root;
-                    const double* bi = is_root ? nullptr : d_br + (int64_t)2 * bidx[v] * cols;
-                    CAFE_LAUNCH(c, marginal_summary_kernel, dim3(gb), dim3(256), 0, s, panel(d_A, v), is_root ? R : M, ld, d_Z, is_root ? 1 : 0, level, bi,
+                    const double* bi = is_root ? nullptr : d_br + (int64_t)2 * up.bidx[v] * cols;
+                    CAFE_LAUNCH(c, marginal_summary_kernel, dim3(gb), dim3(256), 0, s, up.panel(d_A, v), is_root ? R : M, ld, d_Z, is_root ? 1 : 0, level, bi,
                                 bi ? bi + cols : nullptr, so);
                 }
             }
@@ -542,8 +269,8 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
         HIP_TRY(c, hipStreamSynchronize(s));
         for_each_family_of_chunk(c, f0, ld, [&](int64_t f, int64_t col) {
             const double z = h_Z[col];
-            const bool bad = !(z > 0.0) || !std::isfinite(z);
-            if (out->log_evidence) out->log_evidence[f] = bad ? nan : std::log(z);
+            const bool bad = evidence_failed(z);
+            if (out->log_evidence) out->log_evidence[f] = bad ? kNaN : std::log(z);
             if (out->failed) out->failed[f] = bad ? 1 : 0;
             for (int v = 0; v < n; ++v) {
                 const size_t src = (size_t)v * cols + col, dst = (size_t)f * n + v;
@@ -556,13 +283,7 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
             }
         });
     }
-    c->upload_pending = false;
-    // the matrices of this call stay readable (cafe_get_matrix); per-family scorer results are not meaningful
-    c->have_results = true;
-    c->rootmax_last = true;
-    c->last_rejected = false;
-    c->marginal_gemm_ms = timer.on ? timer.total_ms() : 0.0;
-    c->marginal_gemm_flops = timer.flops;
+    close_posterior_call(c, &pc.timer);
     return CAFE_OK;
 }
 

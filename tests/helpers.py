@@ -1,11 +1,43 @@
-"""Shared test plumbing: rebuild a (Problem, Params) pair from a golden fixture's argument record."""
+"""Shared test plumbing: rebuild a (Problem, Params) pair from a golden fixture's argument record; the compiler's resource
+remarks of one HIP file."""
+import functools
 import os
+import re
+import shutil
+import subprocess
 
 import numpy as np
+import pytest
 
 from cafexp_amd import problem as P
 
 DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "data")
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cafexp_amd", "csrc")
+HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+@functools.lru_cache(maxsize=None)
+def kernel_resources(hip_file):
+    """Cross-compiles cafexp_amd/csrc/<hip_file> for gfx950 with the Makefile's FLAGS (CPU only, device code only) and returns
+    the compiler's resource remarks as {mangled kernel name: {remark: value}} -- what `make check` reads.  Skips without hipcc."""
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not installed")
+    with open(os.path.join(CSRC, "Makefile")) as f:
+        flags = next(ln for ln in f if ln.startswith("FLAGS")).split(":=", 1)[1].replace("$(ARCH)", "gfx950").split()
+    r = subprocess.run([HIPCC] + flags + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", hip_file, "-o", os.devnull],
+                       cwd=CSRC, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stderr[-2000:]
+    kernels, name = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            kernels[name] = {}
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
+        if m and name:
+            kernels[name][m.group(1).strip()] = int(m.group(2))
+    return kernels
 
 
 def read(name):

@@ -4,39 +4,14 @@ tests/test_k1_resources.py pins for bd_matrix.hip, on this file: cross-compile f
 resource remarks -- every width 2 .. 32 in both layouts and in the two-pool launch is there, and none uses scratch memory or
 spills a vector register.  No kernel of the file is a lambda = mu instantiation (that test counts them by the slot type)."""
 import os
-import re
-import shutil
-import subprocess
 
-import pytest
+from helpers import CSRC, kernel_resources
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cafexp_amd", "csrc")
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 WIDTHS = [2, 4, 6, 8, 10, 12, 14, 16, 20, 24, 28, 32]
 
 
-def _flags():
-    with open(os.path.join(CSRC, "Makefile")) as f:
-        line = next(ln for ln in f if ln.startswith("FLAGS"))
-    return line.split(":=", 1)[1].replace("$(ARCH)", "gfx950").split()
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_every_two_rate_k1_instantiation_runs_without_scratch(tmp_path):
-    r = subprocess.run([HIPCC] + _flags() + ["-Rpass-analysis=kernel-resource-usage", "-c", "bd_matrix_lm.hip", "-o", str(tmp_path / "k1lm.o")],
-                       cwd=CSRC, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/lane\])?: (\d+)", line)
-        if m and name:
-            kernels[name][m.group(1).strip()] = int(m.group(2))
+def test_every_two_rate_k1_instantiation_runs_without_scratch():
+    kernels = kernel_resources("bd_matrix_lm.hip")
     assert not [k for k in kernels if "bd_matrix_build" in k and "SlotParamLM" not in k], sorted(kernels)
     k1 = {k: v for k, v in kernels.items() if "bd_matrix_build" in k}
     for E in WIDTHS:

@@ -2,40 +2,13 @@
 At E = 24 the kernel uses all 256 VGPRs and at E = 28 / 32 it also needs AGPRs, so a small change to the row step could push
 the widest variants to scratch memory without any value changing.  Cross-compile the kernel for gfx950 (CPU only) and read
 the compiler's resource remarks: no K1 instantiation may use scratch or spill vector registers."""
-import os
-import re
-import shutil
-import subprocess
+from helpers import kernel_resources
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cafexp_amd", "csrc")
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 WIDTHS = [2, 4, 6, 8, 10, 12, 14, 16, 20, 24, 28, 32]
 
 
-def _flags():
-    with open(os.path.join(CSRC, "Makefile")) as f:
-        line = next(ln for ln in f if ln.startswith("FLAGS"))
-    return line.split(":=", 1)[1].replace("$(ARCH)", "gfx950").split()
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_every_k1_instantiation_runs_without_scratch(tmp_path):
-    r = subprocess.run([HIPCC] + _flags() + ["-Rpass-analysis=kernel-resource-usage", "-c", "bd_matrix.hip", "-o", str(tmp_path / "k1.o")],
-                       cwd=CSRC, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/lane\])?: (\d+)", line)
-        if m and name:
-            kernels[name][m.group(1).strip()] = int(m.group(2))
+def test_every_k1_instantiation_runs_without_scratch():
+    kernels = kernel_resources("bd_matrix.hip")
     k1 = {k: v for k, v in kernels.items() if "bd_matrix_build" in k}
     # every width in both single-pool layouts (row-major, k-major) and in the scorer's two-pool launch
     for E in WIDTHS:

@@ -2,43 +2,18 @@
 memory the kernel is five times slower), and the variants with 12-deep K tiles and row tiles of up to 80 rows are built for
 FOUR workgroups per CU -- 128 VGPRs and, in 1 280-byte granules, a quarter of the CU's 160 KB of LDS each.  Cross-compile
 the kernel for gfx950 (CPU only) and read the compiler's resource remarks, as `make check` does."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cafexp_amd", "csrc")
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from helpers import kernel_resources
+
 MAX_SPILLED_VGPRS, MAX_SCRATCH_BYTES = 8, 64               # the limits of `make check`
 
 
-def _flags():
-    with open(os.path.join(CSRC, "Makefile")) as f:
-        line = next(ln for ln in f if ln.startswith("FLAGS"))
-    return line.split(":=", 1)[1].replace("$(ARCH)", "gfx950").split()
-
-
 @pytest.fixture(scope="module")
-def k2_kernels(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    out = tmp_path_factory.mktemp("k2") / "k2.o"
-    r = subprocess.run([HIPCC] + _flags() + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", "prune_gemm.hip", "-o", str(out)],
-                       cwd=CSRC, capture_output=True, text=True, timeout=1500)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and name:
-            kernels[name][m.group(1).strip()] = int(m.group(2))
+def k2_kernels():
+    kernels = kernel_resources("prune_gemm.hip")
     # _ZN4cafe17prune_gemm_kernelILi<KB>ELi<MI>ELb<MUL>ELi<LEAF>ELb<TRANS>EEEvNS_8GemmArgsE
     k2 = {}
     for k, v in kernels.items():
