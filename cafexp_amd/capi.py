@@ -59,6 +59,10 @@ class CafeGradientOut(C.Structure):
     _fields_ = [("family_lnl", _f64p), ("d_lambda", _f64p), ("d_mu", _f64p), ("d_multiplier", _f64p), ("failed", _i32p)]
 
 
+class CafeEventsOut(C.Structure):
+    _fields_ = [("gains", _f64p), ("losses", _f64p), ("log_evidence", _f64p), ("failed", _i32p)]
+
+
 class CafeHistoryOut(C.Structure):
     _fields_ = [("sizes", _i32p), ("category", _i32p), ("n_increase", _i64p), ("n_decrease", _i64p), ("net_change", _i64p),
                 ("log_evidence", _f64p), ("failed", _i32p)]
@@ -99,7 +103,7 @@ EXPORTS = [
     "cafe_debug_fail_next", "cafe_debug_column_extents", "cafe_debug_leaf_transposes", "cafe_simulate",
     "cafe_score_per_family", "cafe_marginal_reconstruct", "cafe_debug_marginal_gemm", "cafe_sample_histories", "cafe_debug_history_batches",
     "cafe_set_death_rates", "cafe_bd_rates", "cafe_build_matrices_lm", "cafe_score_per_family_lm", "cafe_simulate_lm",
-    "cafe_score_gradient", "cafe_bd_rates_grad",
+    "cafe_score_gradient", "cafe_bd_rates_grad", "cafe_expected_events", "cafe_bd_rates_events",
 ]
 CAFE_COMM_ID_BYTES = 128
 
@@ -179,6 +183,10 @@ def load():
     L.cafe_score_gradient.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.POINTER(CafeGradientOut)]
     L.cafe_bd_rates_grad.restype = C.c_int
     L.cafe_bd_rates_grad.argtypes = [C.c_double, C.c_double, C.c_double, _f64p]
+    L.cafe_expected_events.restype = C.c_int
+    L.cafe_expected_events.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.POINTER(CafeEventsOut)]
+    L.cafe_bd_rates_events.restype = C.c_int
+    L.cafe_bd_rates_events.argtypes = [C.c_double, C.c_double, C.c_double, _f64p]
     L.cafe_probe_fp64_mfma.restype = C.c_int
     L.cafe_probe_fp64_mfma.argtypes = [C.c_int32, _f64p]
     L.cafe_debug_stamps.restype = C.c_int
@@ -453,6 +461,19 @@ class Context:
             if name in res:
                 setattr(go, name, _p(res[name], t))
         self._check(self._lib.cafe_score_gradient(self._h, C.byref(cp), int(rule), C.byref(go)))
+        return res
+
+    def expected_events(self, pr: Params, alpha: float = 1.0) -> dict:
+        """cafe_expected_events: the expected number of births (gains) and of deaths (losses) on the branch above every node
+        given the leaf counts, under marginal_reconstruct's model.  Returns numpy arrays: gains and losses
+        [n_families][n_nodes] (NaN at the root), log_evidence and failed [n_families]."""
+        cp, keep = self._params(pr, alpha)
+        F, n = self.n_families, self.n_nodes
+        res = {"gains": np.empty((F, n)), "losses": np.empty((F, n)), "log_evidence": np.empty(F), "failed": np.empty(F, dtype=np.int32)}
+        eo = CafeEventsOut()
+        for name, t in CafeEventsOut._fields_:
+            setattr(eo, name, _p(res[name], t))
+        self._check(self._lib.cafe_expected_events(self._h, C.byref(cp), C.byref(eo)))
         return res
 
     def sample_histories(self, pr: Params, n_draws: int, seed: int, alpha: float = 1.0, sizes: bool = True) -> dict:
@@ -762,6 +783,16 @@ def bd_rates_grad(lam: float, mu: float, t: float):
     rc = load().cafe_bd_rates_grad(float(lam), float(mu), float(t), _p(out, _f64p))
     if rc:
         raise CafeError("cafe_bd_rates_grad failed with code %d" % rc)
+    return tuple(float(x) for x in out)
+
+
+def bd_rates_events(lam: float, mu: float, t: float):
+    """cafe_bd_rates_events: (da, db, dc) of the births tag, then (da, db, dc) of the deaths tag, at the quantized key
+    (lambda, mu, t).  Host code: needs no GPU."""
+    out = np.empty(6)
+    rc = load().cafe_bd_rates_events(float(lam), float(mu), float(t), _p(out, _f64p))
+    if rc:
+        raise CafeError("cafe_bd_rates_events failed with code %d" % rc)
     return tuple(float(x) for x in out)
 
 

@@ -267,6 +267,27 @@ BranchRates branch_rates(const cafe_ctx* c, const double* lambdas, int v, double
 
 }  // namespace
 
+// The kernels cafe_expected_events (events.hip) contracts the same branch joint with, behind host launches (sum_product.h)
+int launch_root_weights(cafe_ctx* c, hipStream_t s, const double* B, const double* prior, const double* logprior, int R, int64_t ld, double* O, double* zk,
+                        double* lbest, int rule, int use_log) {
+    CAFE_LAUNCH(c, gradient_root_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, s, B, prior, logprior, R, ld, O, zk, lbest, rule, use_log);
+    return CAFE_OK;
+}
+int launch_weighted_dot(cafe_ctx* c, hipStream_t s, const double* G, const double* Ft, int np, int64_t ld, double pk, double* acc) {
+    CAFE_LAUNCH(c, gradient_dot_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, s, G, Ft, np, ld, pk, acc);
+    return CAFE_OK;
+}
+int launch_leaf_sums(cafe_ctx* c, hipStream_t s, const double* G, int np, int64_t ld, const double* dP0, const double* dP1, int ldp, const int32_t* cnt,
+                     const double* err, int n_dev, int M, double pk, double* acc0, double* acc1) {
+    CAFE_LAUNCH(c, gradient_leaf_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, s, G, np, ld, dP0, dP1, ldp, cnt, err, n_dev, M, pk, acc0, acc1);
+    return CAFE_OK;
+}
+int launch_finish_sums(cafe_ctx* c, hipStream_t s, const double* zk, const double* probs, int K, int64_t ld, int64_t stride, const double* lbest, double* acc,
+                       int n_acc, double* Z, double* lnl) {
+    CAFE_LAUNCH(c, gradient_finish_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, s, zk, probs, K, ld, stride, lbest, acc, n_acc, Z, lnl);
+    return CAFE_OK;
+}
+
 int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const cafe_gradient_out* out) {
     if (const int rc = check_call_args(c, "cafe_score_gradient", pr, out)) return rc;
     if (root_rule != CAFE_ROOT_MAX && root_rule != CAFE_ROOT_SUM) { set_err(c, "cafe_score_gradient: root_rule must be CAFE_ROOT_MAX or CAFE_ROOT_SUM"); return CAFE_ERR_ARGUMENT; }

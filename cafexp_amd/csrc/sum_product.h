@@ -1,5 +1,5 @@
-// Internal: what cafe_marginal_reconstruct (marginal.hip), cafe_sample_histories (history.hip) and cafe_score_gradient
-// (gradient.hip) share.  The engine (sum_product.hip): the up pass of sum-products, F_v[i] = sum_j P_v[i][j] B_v[j], B_p[i] =
+// Internal: what cafe_marginal_reconstruct (marginal.hip), cafe_sample_histories (history.hip), cafe_score_gradient
+// (gradient.hip) and cafe_expected_events (events.hip) share.  The engine (sum_product.hip): the up pass of sum-products, F_v[i] = sum_j P_v[i][j] B_v[j], B_p[i] =
 // prod_{children} F_c[i], the leaves gathered with the error model's taps, its fp64 MFMA GEMM and product kernel, the down pass's
 // walk.  The frame, on top of cafe_call.h: argument checks, opening, constants, the test for a failed family, closing.
 #pragma once
@@ -86,7 +86,19 @@ std::vector<Branch> branches_down(const cafe_ctx* c);
 // out2 and first, which are the caller's (O: the arena of the O panels, G: one panel)
 int down_branch(cafe_ctx* c, const UpPanels& w, double* O, double* G, const Branch& b, int k, double pk, int64_t f0, int64_t ld, hipStream_t s, GemmParams* g);
 
-// ------------------------------------------------------------------------------------- the frame of the three calls
+// The kernels of gradient.hip that cafe_expected_events (events.hip) launches too, one block of 256 threads per 256 columns:
+// the root weight O_root and Z_k of a category (rule: CAFE_ROOT_MAX / CAFE_ROOT_SUM); acc[f] += pk sum_{i = 1..np} i G[i][f]
+// Ft[i-1][f]; a leaf branch's acc0 / acc1[f] += pk sum_taps err sum_i G[i][f] dP0 / dP1[i][tap] (dP1, acc1 may be nullptr);
+// Z = sum_k p_k Z_k, its logarithm (or lbest) and the n_acc sums of every column divided by it, NaN for a failed column
+int launch_root_weights(cafe_ctx* c, hipStream_t s, const double* B, const double* prior, const double* logprior, int R, int64_t ld, double* O, double* zk,
+                        double* lbest, int rule, int use_log);
+int launch_weighted_dot(cafe_ctx* c, hipStream_t s, const double* G, const double* Ft, int np, int64_t ld, double pk, double* acc);
+int launch_leaf_sums(cafe_ctx* c, hipStream_t s, const double* G, int np, int64_t ld, const double* dP0, const double* dP1, int ldp, const int32_t* cnt,
+                     const double* err, int n_dev, int M, double pk, double* acc0, double* acc1);
+int launch_finish_sums(cafe_ctx* c, hipStream_t s, const double* zk, const double* probs, int K, int64_t ld, int64_t stride, const double* lbest, double* acc,
+                       int n_acc, double* Z, double* lnl);
+
+// ------------------------------------------------------------------------------------- the frame of the posterior calls
 // A family whose evidence Z is zero, negative, NaN or infinite has failed: its doubles are kNaN
 __host__ __device__ inline bool evidence_failed(double z) { return !(z > 0.0) || z > DBL_MAX; }
 constexpr double kNaN = std::numeric_limits<double>::quiet_NaN();

@@ -1,5 +1,5 @@
 // The sum-product engine of the posterior calls -- cafe_marginal_reconstruct (marginal.hip), cafe_sample_histories
-// (history.hip) and cafe_score_gradient (gradient.hip) -- and the host frame they share (sum_product.h).
+// (history.hip), cafe_score_gradient (gradient.hip) and cafe_expected_events (events.hip) -- and the host frame they share (sum_product.h).
 // Panels, matrices and the two passes are described in marginal.hip's header comment.
 #include <cmath>
 

@@ -273,6 +273,19 @@ struct marginal_result {
 void write_marginal_reports(const marginal_result& res, const std::string& model_identifier, const std::string& dir,
                             const std::vector<const clade*>& order, const std::vector<gene_family>& families);
 
+// cafe_expected_events' outputs, [family][index in the caller's node order] (NaN at the root and for a failed family; failed: [family])
+struct events_result {
+    size_t n_nodes = 0;
+    std::vector<double> gains, losses;
+    std::vector<int32_t> failed;
+    size_t failed_count() const { size_t k = 0; for (int32_t f : failed) k += f != 0; return k; }
+};
+// <Model>_expected_events.tab (gains:losses per family and node, "-" at the root; header row, family order and node naming of
+// <Model>_posterior_change.tab) and <Model>_branch_events.tab: per branch the expected gains, losses, net change (gains - losses)
+// and turnover (gains + losses) summed in family order over the families that did not fail
+void write_events_reports(const events_result& res, const std::string& model_identifier, const std::string& dir,
+                          const std::vector<const clade*>& order, const std::vector<gene_family>& families);
+
 // cafe_sample_histories' counts, [draw][index in the caller's node order] (failed: [family])
 struct history_result {
     size_t n_draws = 0, n_nodes = 0;
@@ -357,6 +370,9 @@ public:
     // Per-family scores of the model's likelihood at its current parameters (cafe_score_gradient; root_rule CAFE_ROOT_MAX is
     // what infer_family_likelihoods sums)
     gradient_result score_gradient(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, int root_rule);
+    // Expected number of births and of deaths on the branch above every node given the leaf counts, under the same model
+    // (cafe_expected_events); columns in `order`
+    events_result expected_events(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<const clade*>& order);
     // Whole ancestral histories drawn from the same posterior (cafe_sample_histories), counted per draw on the device:
     // how many families expanded / contracted on every branch and the net change, rows in `order`
     history_result sample_histories(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, int n_draws, uint64_t seed,

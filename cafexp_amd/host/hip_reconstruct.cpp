@@ -133,6 +133,72 @@ void write_marginal_reports(const marginal_result& res, const std::string& model
     }
 }
 
+events_result hip_model_base::expected_events(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<const clade*>& order) {
+    std::vector<double> mult, probs;
+    double alpha = 0;
+    category_parameters(mult, probs, alpha);
+    const int K = mult.empty() ? 1 : (int)mult.size();
+    ensure_context(K);
+    std::vector<float> prior_f;
+    std::vector<double> err, lambdas;
+    gather_call_inputs(prior, rootdist, prior_f, err, lambdas);
+    cafe_params pr{};
+    pr.model = mult.empty() ? CAFE_MODEL_BASE : CAFE_MODEL_GAMMA;
+    pr.lambdas = lambdas.data(); pr.n_categories = K;
+    pr.multipliers = mult.empty() ? nullptr : mult.data();
+    pr.cat_probs = probs.empty() ? nullptr : probs.data();
+    pr.alpha = alpha; pr.prior = prior_f.data(); pr.error_model = err.empty() ? nullptr : err.data();
+    const size_t n = _order.size(), F = _p_gene_families->size(), m = order.size();
+    std::vector<double> gains(F * n), losses(F * n);
+    events_result res;
+    res.n_nodes = m;
+    res.failed.resize(F);
+    cafe_events_out out{};
+    out.gains = gains.data(); out.losses = losses.data(); out.failed = res.failed.data();
+    if (cafe_expected_events(_ctx, &pr, &out) != CAFE_OK)
+        throw std::runtime_error(std::string("cafe_expected_events: ") + cafe_last_error(_ctx));
+    std::map<const clade*, size_t> pos;
+    for (size_t v = 0; v < n; ++v) pos[_order[v]] = v;
+    res.gains.resize(F * m); res.losses.resize(F * m);
+    for (size_t f = 0; f < F; ++f)
+        for (size_t i = 0; i < m; ++i) {
+            const size_t src = f * n + pos.at(order[i]), dst = f * m + i;
+            res.gains[dst] = gains[src]; res.losses[dst] = losses[src];
+        }
+    return res;
+}
+
+void write_events_reports(const events_result& res, const std::string& model_identifier, const std::string& dir,
+                          const std::vector<const clade*>& order, const std::vector<gene_family>& families) {
+    const std::string prefix = (dir.empty() ? std::string("results") : dir) + "/" + model_identifier;
+    std::ofstream cells(prefix + "_expected_events.tab"), totals(prefix + "_branch_events.tab");
+    cells << "FamilyID";
+    for (auto c : order) cells << "\t" << clade_index_or_name(c, order);
+    cells << std::endl;
+    char buf[160];
+    const size_t m = order.size();
+    std::vector<double> g(m, 0.0), l(m, 0.0);
+    size_t used = 0;
+    for (size_t i = 0; i < families.size(); ++i) {
+        cells << families[i].id();
+        for (size_t v = 0; v < m; ++v) {
+            const size_t at = i * m + v;
+            if (order[v]->is_root()) { cells << "\t-"; continue; }
+            std::snprintf(buf, sizeof buf, "\t%.6g:%.6g", res.gains[at], res.losses[at]);
+            cells << buf;
+            if (!res.failed[i]) { g[v] += res.gains[at]; l[v] += res.losses[at]; }
+        }
+        cells << std::endl;
+        used += res.failed[i] == 0;
+    }
+    totals << "#Node\tgains\tlosses\tnet\tturnover\t(expected events summed over " << used << " families; " << families.size() - used << " failed)" << std::endl;
+    for (size_t v = 0; v < m; ++v) {
+        if (order[v]->is_root()) continue;
+        std::snprintf(buf, sizeof buf, "\t%.12g\t%.12g\t%.12g\t%.12g", g[v], l[v], g[v] - l[v], g[v] + l[v]);
+        totals << clade_index_or_name(order[v], order) << buf << std::endl;
+    }
+}
+
 history_result hip_model_base::sample_histories(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, int n_draws, uint64_t seed,
                                                 const std::vector<const clade*>& order) {
     std::vector<double> mult, probs;

@@ -33,6 +33,9 @@ static void usage() {
         "                  fitted model (seed S, else -s, else 1); with -o: <Model>_sampled_change.tab, per node the mean and the equal-tailed\n"
         "                  interval (LEVEL of --reconstruct-marginal, default 0.95) across the draws of how many families expanded /\n"
         "                  contracted on its branch and of the net change in genes; one GPU\n"
+        "                  [--expected-events]   after the search: the expected number of gene gains (births) and losses (deaths) on every\n"
+        "                  branch of every family given its counts, under the fitted model; with -o: <Model>_expected_events.tab (gains:losses\n"
+        "                  per family and node) and <Model>_branch_events.tab (per branch: gains, losses, net, turnover over the table); one GPU\n"
         "                  [--standard-errors]   after the search: the per-family scores at the optimum, the standard error of every\n"
         "                  estimated lambda, mu (--estimate-mu) and alpha from their outer product, Wald 95 %% intervals, correlations and the\n"
         "                  total score -> <Model>_standard_errors.txt in -o OUTDIR (default results); one GPU, not with -b or --simulate\n"
@@ -174,6 +177,7 @@ int main(int argc, char** argv) {
     bool estimate_mu = false;                                    // --estimate-mu: death rates searched with the lambdas
     std::string family_mu;                                       // --family-mu (with -b): rates, or "estimate"
     bool do_standard_errors = false;                             // --standard-errors
+    bool do_events = false;                                      // --expected-events
     unsigned seed = 0;
     bool have_seed = false;
     for (int i = 1; i < argc; ++i) {
@@ -192,6 +196,7 @@ int main(int argc, char** argv) {
         else if (a == "--estimate-mu") estimate_mu = true;
         else if (a == "--family-mu") family_mu = next();
         else if (a == "--standard-errors") do_standard_errors = true;
+        else if (a == "--expected-events") do_events = true;
         else if (a == "-e") { use_err = true; err_path = optional(); }
         else if (a == "-p") { use_poisson = true; std::string v = optional(); poisson = v.empty() ? 0 : std::stod(v); }
         else if (a == "-f") rootdist_path = next();
@@ -228,6 +233,7 @@ int main(int argc, char** argv) {
         if (estimate_mu) { std::fprintf(stderr, "cafexp_hip: --simulate draws under given rates: --estimate-mu is not supported with it (give --mu)\n"); return 1; }
         if (!family_mu.empty()) { std::fprintf(stderr, "cafexp_hip: --family-mu sets the death rates of -b: it is not supported without -b\n"); return 1; }
         if (do_standard_errors) { std::fprintf(stderr, "cafexp_hip: --standard-errors belongs to a fitted model: --simulate is not supported with it\n"); return 1; }
+        if (do_events) { std::fprintf(stderr, "cafexp_hip: --expected-events belongs to a fitted model: --simulate is not supported with it\n"); return 1; }
         if (have_seed) randomizer_engine.seed(seed);
         return simulate_main(tree_path, fam_path, rootdist_path, lambda_tree_path, multi, err_path, use_err, fixed_lambda, fixed_alpha, k,
                              simulate_n, simulate_on_device, have_seed ? seed : randomizer_engine(), device, sim_workspace, out_dir, mu_list);
@@ -255,6 +261,12 @@ int main(int argc, char** argv) {
         if (gpus_given) why = "--reconstruct-marginal runs on one GPU: --gpus is not supported with it";
         else if (per_family) why = "--reconstruct-marginal needs one fitted model: -b is not supported with it";
         else if (!(marginal_level > 0 && marginal_level < 1)) why = "--reconstruct-marginal: LEVEL must lie in (0, 1)";
+        if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
+    }
+    if (do_events) {
+        const char* why = nullptr;
+        if (gpus_given) why = "--expected-events runs on one GPU: --gpus is not supported with it";
+        else if (per_family) why = "--expected-events needs one fitted model: -b is not supported with it";
         if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
     }
     if (do_histories) {
@@ -502,6 +514,18 @@ int main(int argc, char** argv) {
             history_failed = hr.failed_count();
             if (!out_dir.empty()) write_history_reports(hr, marginal_level, mdl->name(), out_dir, order);
         }
+        // expected gains and losses per branch under the same model: what the node sizes of the reconstructions do not show
+        double events_s = 0;
+        size_t events_failed = 0;
+        if (do_events) {
+            auto t0 = std::chrono::steady_clock::now();
+            cladevector order;
+            d.p_tree->apply_reverse_level_order([&order](const clade* c) { order.push_back(c); });
+            const events_result er = mdl->expected_events(d.p_prior.get(), d.rootdist, order);
+            events_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            events_failed = er.failed_count();
+            if (!out_dir.empty()) write_events_reports(er, mdl->name(), out_dir, order, d.gene_families);
+        }
         // standard errors of what the search estimated, from the per-family scores of the searched objective at the optimum
         standard_errors se;
         std::vector<double> slopes;
@@ -577,6 +601,8 @@ int main(int argc, char** argv) {
             std::printf(", \"marginal\": {\"seconds\": %.3f, \"level\": %.17g, \"failed\": %zu}", marginal_s, marginal_level, marginal_failed);
         if (do_histories)
             std::printf(", \"histories\": {\"seconds\": %.3f, \"draws\": %d, \"failed\": %zu}", history_s, history_draws, history_failed);
+        if (do_events)
+            std::printf(", \"expected_events\": {\"seconds\": %.3f, \"failed\": %zu}", events_s, events_failed);
         if (do_standard_errors) {
             auto list = [](const char* key, const std::vector<double>& v) {
                 std::printf("\"%s\": [", key);

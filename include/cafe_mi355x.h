@@ -437,6 +437,37 @@ int cafe_score_gradient(cafe_ctx* ctx, const cafe_params* params, int32_t root_r
  * both equal t / (1 + lambda t)^2, the derivative of the lambda = mu kernels' alpha.  Pure host code, no device needed. */
 int cafe_bd_rates_grad(double lambda, double mu, double t, double out[4]);
 
+/* Expected gene gains and losses: the posterior expectation, given the leaf counts, of the number of births (gains) and of
+ * deaths (losses) on the branch above every node -- the turnover that node sizes do not show (a branch on which a family gained
+ * three genes and lost three has no net change).  The model is cafe_marginal_reconstruct's: the call's lambdas, categories,
+ * prior and error model, the context's death rates when set, the root weight of CAFE_ROOT_SUM; with the gamma model the
+ * categories mix with their posterior weights.  Tagging every birth with a factor r and every death with w keeps the
+ * single-lineage law linear-fractional, and the expected counts are the derivatives in r and w at 1 of the branch's matrix,
+ * contracted with the branch joint as cafe_score_gradient does: two scans of B_v in one pass, two GEMMs and two weighted dots
+ * per interior branch, no derivative matrix.  Outputs (host pointers, any may be NULL), rows in the
+ * problem's family order:
+ *   gains, losses [n_families][n_nodes]: NaN at the root; gains - losses is the posterior mean of X_v - X_parent(v).  The events
+ *     of a leaf branch are those leading to the true size behind the error model's taps;
+ *   log_evidence, failed [n_families] as cafe_marginal_reconstruct: a failed family's doubles are NaN (the call still returns
+ *     CAFE_OK).
+ * A branch whose key is marked zero (cafe_bd_rates out[2]) contributes 0.  CAFE_ERR_ARGUMENT for invalid rates or a bad K;
+ * CAFE_ERR_STATE on a context with a communicator attached.  The columns are processed in batches that fit the problem's
+ * workspace_limit (0 = automatic); a value never depends on the batches, identical families get identical rows.
+ * cafe_family_results is not meaningful after this call; a later cafe_score is unaffected; cafe_debug_marginal_gemm reports this
+ * call's GEMM launches. */
+typedef struct cafe_events_out {
+    double*  gains;        /* [n_families][n_nodes] E[births on the branch above v | data]; NaN at the root */
+    double*  losses;       /* [n_families][n_nodes] E[deaths on the branch above v | data]; NaN at the root */
+    double*  log_evidence; /* [n_families] */
+    int32_t* failed;       /* [n_families] */
+} cafe_events_out;
+int cafe_expected_events(cafe_ctx* ctx, const cafe_params* params, const cafe_events_out* out);
+/* out = {da, db, dc} of the births tag, then {da, db, dc} of the deaths tag, at r = w = 1 and the quantized key of cafe_bd_rates:
+ * the derivatives of the tagged law phi(z) = a + c z / (1 - b z), whose a and b are cafe_bd_rates' alpha and beta and whose
+ * c = (1 - alpha)(1 - beta) there.  All six are non-negative; evaluated without a division by lambda - mu (series where
+ * |lambda - mu| t is small), so finite and accurate as mu -> lambda and at mu = lambda.  Pure host code, no device needed. */
+int cafe_bd_rates_events(double lambda, double mu, double t, double out[6]);
+
 /* Introspection for parity tests: the transition matrix the last call built for the branch above
  * `node` in category k (N x N row-major, N = max(M,R)+1: matrix_cache::get_matrix; for an interior
  * branch the columns c > M, which the prune never reads, are not materialised and come back 0), and the root
