@@ -59,6 +59,11 @@ class CafeGradientOut(C.Structure):
     _fields_ = [("family_lnl", _f64p), ("d_lambda", _f64p), ("d_mu", _f64p), ("d_multiplier", _f64p), ("failed", _i32p)]
 
 
+class CafeBranchScoresOut(C.Structure):
+    _fields_ = [("rate", _f64p), ("birth", _f64p), ("death", _f64p), ("family_lnl", _f64p), ("d_lambda", _f64p), ("d_mu", _f64p),
+                ("d_multiplier", _f64p), ("failed", _i32p), ("total", _f64p), ("gram", _f64p), ("n_used", _i64p)]
+
+
 class CafeEventsOut(C.Structure):
     _fields_ = [("gains", _f64p), ("losses", _f64p), ("log_evidence", _f64p), ("failed", _i32p)]
 
@@ -104,6 +109,7 @@ EXPORTS = [
     "cafe_score_per_family", "cafe_marginal_reconstruct", "cafe_debug_marginal_gemm", "cafe_sample_histories", "cafe_debug_history_batches",
     "cafe_set_death_rates", "cafe_bd_rates", "cafe_build_matrices_lm", "cafe_score_per_family_lm", "cafe_simulate_lm",
     "cafe_score_gradient", "cafe_bd_rates_grad", "cafe_expected_events", "cafe_bd_rates_events",
+    "cafe_branch_scores", "cafe_branch_scores_dim", "cafe_weighted_gram", "cafe_debug_gram",
 ]
 CAFE_COMM_ID_BYTES = 128
 
@@ -187,6 +193,14 @@ def load():
     L.cafe_expected_events.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.POINTER(CafeEventsOut)]
     L.cafe_bd_rates_events.restype = C.c_int
     L.cafe_bd_rates_events.argtypes = [C.c_double, C.c_double, C.c_double, _f64p]
+    L.cafe_branch_scores.restype = C.c_int
+    L.cafe_branch_scores.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.POINTER(CafeBranchScoresOut)]
+    L.cafe_branch_scores_dim.restype = C.c_int
+    L.cafe_branch_scores_dim.argtypes = [C.c_void_p, C.POINTER(CafeParams), _i32p]
+    L.cafe_debug_gram.restype = C.c_int
+    L.cafe_debug_gram.argtypes = [C.c_void_p, _f64p, _f64p]
+    L.cafe_weighted_gram.restype = C.c_int
+    L.cafe_weighted_gram.argtypes = [C.c_int32, C.c_int32, C.c_int64, _f64p, _f64p, _f64p, _f64p]
     L.cafe_probe_fp64_mfma.restype = C.c_int
     L.cafe_probe_fp64_mfma.argtypes = [C.c_int32, _f64p]
     L.cafe_debug_stamps.restype = C.c_int
@@ -462,6 +476,54 @@ class Context:
                 setattr(go, name, _p(res[name], t))
         self._check(self._lib.cafe_score_gradient(self._h, C.byref(cp), int(rule), C.byref(go)))
         return res
+
+    def branch_scores_dim(self, pr: Params) -> int:
+        """cafe_branch_scores_dim: the length P of the score vector for pr's model and this context's death rates."""
+        cp, keep = self._params(pr)
+        out = C.c_int32()
+        self._check(self._lib.cafe_branch_scores_dim(self._h, C.byref(cp), C.byref(out)))
+        return out.value
+
+    def branch_scores(self, pr: Params, root_rule="max", alpha: float = 1.0, death_rates: Optional[bool] = None, per_family: bool = True,
+                      gram: bool = True) -> dict:
+        """cafe_branch_scores: score_gradient's derivative kept per branch, and the information of those scores.  Returns what
+        score_gradient returns and, with per_family, rate [n_families][n_nodes] (d lnL_f / d log of a factor on both rates of
+        the branch above the node; NaN at the root) and, while death rates are set, birth and death of the same shape (rate =
+        birth + death); with gram, total [P], gram [P][P] and n_used over the score vector (branch scores, then d_lambda, d_mu,
+        d_multiplier; P = branch_scores_dim)."""
+        rule = {"max": CAFE_ROOT_MAX, "sum": CAFE_ROOT_SUM}.get(root_rule, root_rule)
+        cp, keep = self._params(pr, alpha)
+        F, nl, n = self.n_families, self.problem.n_lambdas, self.n_nodes
+        two = getattr(self, "_death_rates", False) if death_rates is None else death_rates
+        res = {"family_lnl": np.empty(F), "d_lambda": np.empty((F, nl)), "failed": np.empty(F, dtype=np.int32)}
+        if two:
+            res["d_mu"] = np.empty((F, nl))
+        if pr.multipliers is not None:
+            res["d_multiplier"] = np.empty((F, len(pr.multipliers)))
+        if per_family:
+            res["rate"] = np.empty((F, n))
+            if two:
+                res["birth"], res["death"] = np.empty((F, n)), np.empty((F, n))
+        n_used = np.zeros(1, dtype=np.int64)
+        if gram:
+            P = self.branch_scores_dim(pr)
+            res["total"], res["gram"] = np.empty(P), np.empty((P, P))
+        bo = CafeBranchScoresOut()
+        for name, t in CafeBranchScoresOut._fields_:
+            if name in res:
+                setattr(bo, name, _p(res[name], t))
+        if gram:
+            bo.n_used = _p(n_used, _i64p)
+        self._check(self._lib.cafe_branch_scores(self._h, C.byref(cp), int(rule), C.byref(bo)))
+        if gram:
+            res["n_used"] = int(n_used[0])
+        return res
+
+    def gram_stats(self):
+        """(HIP-event ms of the Gram launches of the last branch_scores -- 0 unless profiling was on --, the flops of their MFMAs)"""
+        ms, fl = C.c_double(), C.c_double()
+        self._check(self._lib.cafe_debug_gram(self._h, C.byref(ms), C.byref(fl)))
+        return ms.value, fl.value
 
     def expected_events(self, pr: Params, alpha: float = 1.0) -> dict:
         """cafe_expected_events: the expected number of births (gains) and of deaths (losses) on the branch above every node
@@ -784,6 +846,20 @@ def bd_rates_grad(lam: float, mu: float, t: float):
     if rc:
         raise CafeError("cafe_bd_rates_grad failed with code %d" % rc)
     return tuple(float(x) for x in out)
+
+
+def weighted_gram(S, w, device: int = 0):
+    """cafe_weighted_gram: (S diag(w) S^T [p][p], S w [p]) of S [p][n] on the device's fp64 MFMA."""
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    p, n = S.shape
+    if w.shape != (n,):
+        raise ValueError("w must have one entry per column of S")
+    gram, total = np.empty((p, p)), np.empty(p)
+    rc = load().cafe_weighted_gram(int(device), p, n, _p(S, _f64p), _p(w, _f64p), _p(gram, _f64p), _p(total, _f64p))
+    if rc != 0:
+        raise CafeError("cafe_weighted_gram failed with code %d" % rc)
+    return gram, total
 
 
 def bd_rates_events(lam: float, mu: float, t: float):

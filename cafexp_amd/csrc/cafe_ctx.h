@@ -187,6 +187,7 @@ struct cafe_ctx {
     size_t pf_dev_bytes = 0;
     int64_t pf_max_batch = 0;                // CAFE_PER_FAMILY_BATCH: at most that many families per batch (diagnostic; 0 = what fits)
     double marginal_gemm_ms = 0, marginal_gemm_flops = 0;   // cafe_marginal_reconstruct: its GEMM launches (ms: while profiling)
+    double gram_ms = 0.0, gram_flops = 0.0;  // the Gram kernels of the last cafe_branch_scores (ms: profiling on)
     int history_batches = 0, history_passes = 0;            // cafe_sample_histories: column batches, draw passes per batch of the last call
     int debug_fail_in = 0;                  // cafe_debug_fail_next: the n-th next enqueue fails behind its K1 launch
 
@@ -323,8 +324,9 @@ int reconstruct_impl(cafe_ctx* c, const cafe_params* pr, const float* root_prior
 int branch_probabilities_impl(cafe_ctx* c, const cafe_params* pr, const int32_t* sizes, double* out);
 // Marginal reconstruction: posterior sizes, intervals and branch change probabilities (marginal.hip)
 int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_marginal_out* out);
-// Per-family derivatives of log Z in the rates on the same two passes (gradient.hip)
-int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const cafe_gradient_out* out);
+// Per-family derivatives of log Z in the rates on the same two passes (gradient.hip: gradient_walk, sum_product.h); the same
+// kept per branch, with their weighted Gram matrix (branch_scores.hip)
+int branch_scores_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const cafe_branch_scores_out* out);
 void bd_rates_grad(double lambda, double mu, double t, double out[4]);     // plain doubles in, no quantization
 // Ancestral histories drawn from the posterior of the same model (history.hip)
 int history_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_draws, uint64_t seed, const cafe_history_out* out);

@@ -133,15 +133,17 @@ __global__ __launch_bounds__(256) void gradient_scan_kernel(const double* __rest
     }
 }
 
-// acc[f] += pk sum_{i = 1..np} i G[i][f] Ft[i-1][f], in the order of i
+// acc[f] += pk sum_{i = 1..np} i G[i][f] Ft[i-1][f], in the order of i; the same sum times pk2 into acc2 when there is one
+// (cafe_branch_scores: the branch's own row)
 __global__ __launch_bounds__(256) void gradient_dot_kernel(const double* __restrict__ G, const double* __restrict__ Ft, int np, int64_t ld, double pk,
-                                                           double* __restrict__ acc) {
+                                                           double* __restrict__ acc, double pk2, double* __restrict__ acc2) {
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (f >= ld) return;
     double s = 0.0;
 #pragma unroll 8
     for (int i = 1; i <= np; ++i) s += (double)i * G[(int64_t)i * ld + f] * Ft[(int64_t)(i - 1) * ld + f];
     acc[f] += pk * s;
+    if (acc2) acc2[f] += pk2 * s;
 }
 
 // The derivative rows of a row-major leaf matrix: dP[p][i][c] = i (ca[p] y[c] - cb[p] z[c-1]) for i = 1..np, c = 0..M, with
@@ -190,11 +192,13 @@ __global__ __launch_bounds__(256) void gradient_leaf_filter_kernel(const FilterP
 }
 
 // A leaf branch: acc[p][f] += pk sum_t err[x][t] sum_{i = 1..np} G[i][f] dP[p][i][c_t], c_t the taps of the observed count x
-// inside [0, M] (c = x without an error model), in the scorer's tap order
+// inside [0, M] (c = x without an error model), in the scorer's tap order; the same two sums times bk[p] into row[p] when there
+// are any (cafe_branch_scores: the branch's own rows)
+struct LeafRows { double bk[2]; double* row[2]; };
 __global__ __launch_bounds__(256) void gradient_leaf_kernel(const double* __restrict__ G, int np, int64_t ld, const double* __restrict__ dP0,
                                                             const double* __restrict__ dP1, int ldp, const int32_t* __restrict__ cnt,
                                                             const double* __restrict__ err, int n_dev, int M, double pk, double* __restrict__ acc0,
-                                                            double* __restrict__ acc1) {
+                                                            double* __restrict__ acc1, const LeafRows rows) {
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (f >= ld) return;
     const int x = cnt[f];
@@ -215,6 +219,8 @@ __global__ __launch_bounds__(256) void gradient_leaf_kernel(const double* __rest
     }
     acc0[f] += pk * s0;
     if (dP1) acc1[f] += pk * s1;
+    if (rows.row[0]) rows.row[0][f] += rows.bk[0] * s0;
+    if (rows.row[1]) rows.row[1][f] += rows.bk[1] * s1;
 }
 
 // Z = sum_k p_k Z_k in the order of k; lnl = log Z (or the base model's maximum of logarithms); every sum of the column
@@ -274,12 +280,12 @@ int launch_root_weights(cafe_ctx* c, hipStream_t s, const double* B, const doubl
     return CAFE_OK;
 }
 int launch_weighted_dot(cafe_ctx* c, hipStream_t s, const double* G, const double* Ft, int np, int64_t ld, double pk, double* acc) {
-    CAFE_LAUNCH(c, gradient_dot_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, s, G, Ft, np, ld, pk, acc);
+    CAFE_LAUNCH(c, gradient_dot_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, s, G, Ft, np, ld, pk, acc, 0.0, (double*)nullptr);
     return CAFE_OK;
 }
 int launch_leaf_sums(cafe_ctx* c, hipStream_t s, const double* G, int np, int64_t ld, const double* dP0, const double* dP1, int ldp, const int32_t* cnt,
                      const double* err, int n_dev, int M, double pk, double* acc0, double* acc1) {
-    CAFE_LAUNCH(c, gradient_leaf_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, s, G, np, ld, dP0, dP1, ldp, cnt, err, n_dev, M, pk, acc0, acc1);
+    CAFE_LAUNCH(c, gradient_leaf_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, s, G, np, ld, dP0, dP1, ldp, cnt, err, n_dev, M, pk, acc0, acc1, LeafRows{});
     return CAFE_OK;
 }
 int launch_finish_sums(cafe_ctx* c, hipStream_t s, const double* zk, const double* probs, int K, int64_t ld, int64_t stride, const double* lbest, double* acc,
@@ -288,12 +294,16 @@ int launch_finish_sums(cafe_ctx* c, hipStream_t s, const double* zk, const doubl
     return CAFE_OK;
 }
 
-int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const cafe_gradient_out* out) {
-    if (const int rc = check_call_args(c, "cafe_score_gradient", pr, out)) return rc;
-    if (root_rule != CAFE_ROOT_MAX && root_rule != CAFE_ROOT_SUM) { set_err(c, "cafe_score_gradient: root_rule must be CAFE_ROOT_MAX or CAFE_ROOT_SUM"); return CAFE_ERR_ARGUMENT; }
-    if (pr->model != CAFE_MODEL_GAMMA && out->d_multiplier) { set_err(c, "cafe_score_gradient: d_multiplier needs the gamma model"); return CAFE_ERR_ARGUMENT; }
-    if (const int rc = check_model_args(c, "cafe_score_gradient", pr)) return rc;
-    if (out->d_mu && c->mus.empty()) { set_err(c, "cafe_score_gradient: d_mu needs death rates (cafe_set_death_rates)"); return CAFE_ERR_STATE; }
+// The walk of cafe_score_gradient.  cafe_branch_scores (branch_scores.hip) takes it too, with a score panel `sp`: every dot
+// and leaf sum then also goes, weighted p_k m_k lambda_q (or mu_q) -- the derivative in the logarithm of the branch's rate --
+// into the branch's own row of the panel, and the global scores of every column go to the panel's last rows.  What the
+// kernels add into the sums per lambda index, and in which order, does not depend on `sp`.
+int gradient_walk(cafe_ctx* c, const char* entry, const cafe_params* pr, int32_t root_rule, const cafe_gradient_out* out, ScorePanel* sp) {
+    if (const int rc = check_call_args(c, entry, pr, out)) return rc;
+    if (root_rule != CAFE_ROOT_MAX && root_rule != CAFE_ROOT_SUM) { set_err(c, "%s: root_rule must be CAFE_ROOT_MAX or CAFE_ROOT_SUM", entry); return CAFE_ERR_ARGUMENT; }
+    if (pr->model != CAFE_MODEL_GAMMA && out->d_multiplier) { set_err(c, "%s: d_multiplier needs the gamma model", entry); return CAFE_ERR_ARGUMENT; }
+    if (const int rc = check_model_args(c, entry, pr)) return rc;
+    if (out->d_mu && c->mus.empty()) { set_err(c, "%s: d_mu needs death rates (cafe_set_death_rates)", entry); return CAFE_ERR_STATE; }
     PosteriorCall pc;
     if (const int rc = open_posterior_call(c, pr, &pc)) return rc;
     pc.timer.on = c->profile != 0;
@@ -303,6 +313,8 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
     const int n_par = c->mus.empty() ? 1 : 2;
     const bool gamma = pc.gamma, use_log = !gamma && root_rule == CAFE_ROOT_MAX;
     const int n_acc = K * nl * n_par;
+    const int n_glob = nl * n_par + (gamma ? K : 0);         // d_lambda, d_mu, d_multiplier of a column
+    if (sp) if (const int rc = score_panel_open(c, entry, n_par, n_glob, sp)) return rc;      // before the batch is sized: it stays
 
     // workspace per column: B, F and O of every interior node; G, the scanned panel Bt, Ft and the panel that takes the down
     // GEMM's second output; Z_k, the sums, Z, lnl and the base model's maximum.  (The two derivative matrices of a leaf branch
@@ -310,7 +322,7 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
     const size_t dbl_per_col = (size_t)3 * nI * rows + 4 * (size_t)rows + K + n_acc + 3;
     int64_t cols = 0;
     if (const int rc = column_chunk(c, dbl_per_col * sizeof(double),
-                                    "cafe_score_gradient: not enough device memory for the panels of " + std::to_string(nI) + " interior nodes", &cols))
+                                    std::string(entry) + ": not enough device memory for the panels of " + std::to_string(nI) + " interior nodes", &cols))
         return rc;
     const int ldp = c->pool.ld;
     const size_t leaf_mat = (size_t)(std::max(M, R) + 1) * ldp;
@@ -318,7 +330,7 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
     if (hipMalloc(&wd.p, dbl_per_col * cols * sizeof(double)) != hipSuccess || alloc_constants(c, kWithPriorLogs, &pc) != hipSuccess ||
         hipMalloc(&dleaf.p, sizeof(double) * leaf_mat * n_par) != hipSuccess) {
         (void)hipGetLastError();
-        set_err(c, "cafe_score_gradient: cannot allocate the workspace (%lld columns)", (long long)cols);
+        set_err(c, "%s: cannot allocate the workspace (%lld columns)", entry, (long long)cols);
         return CAFE_ERR_MEMORY;
     }
     HIP_TRY(c, hipMemsetAsync(wd.p, 0, dbl_per_col * cols * sizeof(double), s));
@@ -337,7 +349,7 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
     double* d_dP[2] = {static_cast<double*>(dleaf.p), n_par > 1 ? static_cast<double*>(dleaf.p) + leaf_mat : nullptr};
     if (const int rc = upload_constants(c, pr, &pc)) return rc;
 
-    std::vector<double> h_acc((size_t)n_acc * cols), h_Z(cols), h_lnl(cols);
+    std::vector<double> h_acc((size_t)n_acc * cols), h_Z(cols), h_lnl(cols), h_glob((size_t)n_glob * cols);
 
     const std::vector<Branch> down = branches_down(c);
     for (int64_t f0 = 0; f0 < c->Fp; f0 += cols) {
@@ -347,6 +359,7 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
         for (int k = 0; k < K; ++k) {
             const double pk = gamma ? pr->cat_probs[k] : 1.0, mult = gamma ? pr->multipliers[k] : 1.0;
             auto acc_of = [&](int v, int p) { return d_acc + (((int64_t)k * nl + c->lam_idx[v]) * n_par + p) * cols; };
+            auto log_rate = [&](int v, int p) { return pk * (mult * (p == 0 ? pr->lambdas[c->lam_idx[v]] : c->mus[c->lam_idx[v]])); };
             if (const int rc = marginal_up_pass(c, up, k, f0, ld, s, pc.timer)) return rc;
             CAFE_LAUNCH(c, gradient_root_kernel, dim3(gb), dim3(256), 0, s, up.panel(up.B, c->root), pc.prior, pc.logprior, R, ld, up.panel(d_O, c->root),
                         d_zk + (int64_t)k * cols, d_lbest, (int)root_rule, use_log ? 1 : 0);
@@ -368,8 +381,10 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
                         CAFE_LAUNCH(c, gradient_leaf_filter_kernel, dim3((unsigned)((fp.np + kFR - 1) / kFR)), dim3(256), 0, s, fp);
                         filtered = P;
                     }
+                    LeafRows rows{};
+                    for (int q = 0; sp && q < n_par; ++q) { rows.bk[q] = log_rate(v, q); rows.row[q] = score_panel_row(sp, v, q, f0); }
                     CAFE_LAUNCH(c, gradient_leaf_kernel, dim3(gb), dim3(256), 0, s, d_G, np, ld, d_dP[0], (const double*)d_dP[1], ldp,
-                                leaf_counts(c, v, f0), up.err, up.n_dev, M, pk, acc_of(v, 0), n_par > 1 ? acc_of(v, 1) : nullptr);
+                                leaf_counts(c, v, f0), up.err, up.n_dev, M, pk, acc_of(v, 0), n_par > 1 ? acc_of(v, 1) : nullptr, rows);
                     continue;
                 }
                 g.out2 = d_S; g.first = 1;                   // the posterior product goes to a panel nobody reads
@@ -382,7 +397,8 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
                     u.Pt = g.Pt; u.ldp = g.ldp; u.X = d_Bt; u.ld = ld; u.nr = np; u.nk = M + 1;
                     u.out1 = d_Ft; u.out2 = d_Ft;            // a plain store, twice
                     if (const int rc = launch_gemm<kUp>(c, u, false, s, pc.timer)) return rc;
-                    CAFE_LAUNCH(c, gradient_dot_kernel, dim3(gb), dim3(256), 0, s, (const double*)d_G, (const double*)d_Ft, np, ld, pk, acc_of(v, q));
+                    CAFE_LAUNCH(c, gradient_dot_kernel, dim3(gb), dim3(256), 0, s, (const double*)d_G, (const double*)d_Ft, np, ld, pk, acc_of(v, q),
+                                sp ? log_rate(v, q) : 0.0, sp ? score_panel_row(sp, v, q, f0) : (double*)nullptr);
                 }
             }
         }
@@ -392,11 +408,8 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
         HIP_TRY(c, hipMemcpyAsync(h_Z.data(), d_Z, sizeof(double) * (size_t)ld, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(h_lnl.data(), d_lnl, sizeof(double) * (size_t)ld, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
-        for_each_family_of_chunk(c, f0, ld, [&](int64_t f, int64_t col) {
-            const double z = h_Z[col];
-            const bool bad = evidence_failed(z);
-            if (out->family_lnl) out->family_lnl[f] = bad ? kNaN : h_lnl[col];
-            if (out->failed) out->failed[f] = bad ? 1 : 0;
+        // the global scores of every column, then of every family that shares it
+        for (int64_t col = 0; col < ld; ++col) {
             auto a = [&](int k, int q, int p) { return h_acc[(((size_t)k * nl + q) * n_par + p) * cols + col]; };
             for (int q = 0; q < nl; ++q) {
                 double dl = 0.0, dm = 0.0;
@@ -405,20 +418,32 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
                     dl += m * a(k, q, 0);
                     if (n_par > 1) dm += m * a(k, q, 1);
                 }
-                if (out->d_lambda) out->d_lambda[f * nl + q] = bad ? kNaN : dl;
-                if (out->d_mu) out->d_mu[f * nl + q] = bad ? kNaN : dm;
+                h_glob[(size_t)q * cols + col] = dl;
+                if (n_par > 1) h_glob[(size_t)(nl + q) * cols + col] = dm;
+            }
+            for (int k = 0; gamma && k < K; ++k) {
+                double d = 0.0;
+                for (int q = 0; q < nl; ++q) {
+                    d += pr->lambdas[q] * a(k, q, 0);
+                    if (n_par > 1) d += c->mus[q] * a(k, q, 1);
+                }
+                h_glob[(size_t)(nl * n_par + k) * cols + col] = d;
+            }
+        }
+        for_each_family_of_chunk(c, f0, ld, [&](int64_t f, int64_t col) {
+            const bool bad = evidence_failed(h_Z[col]);
+            if (out->family_lnl) out->family_lnl[f] = bad ? kNaN : h_lnl[col];
+            if (out->failed) out->failed[f] = bad ? 1 : 0;
+            for (int q = 0; q < nl; ++q) {
+                if (out->d_lambda) out->d_lambda[f * nl + q] = bad ? kNaN : h_glob[(size_t)q * cols + col];
+                if (out->d_mu) out->d_mu[f * nl + q] = bad ? kNaN : h_glob[(size_t)(nl + q) * cols + col];
             }
             if (out->d_multiplier)
-                for (int k = 0; k < K; ++k) {
-                    double d = 0.0;
-                    for (int q = 0; q < nl; ++q) {
-                        d += pr->lambdas[q] * a(k, q, 0);
-                        if (n_par > 1) d += c->mus[q] * a(k, q, 1);
-                    }
-                    out->d_multiplier[f * K + k] = bad ? kNaN : d;
-                }
+                for (int k = 0; k < K; ++k) out->d_multiplier[f * K + k] = bad ? kNaN : h_glob[(size_t)(nl * n_par + k) * cols + col];
         });
+        if (sp) if (const int rc = score_panel_batch(c, s, sp, f0, ld, cols, d_Z, h_Z.data(), h_glob.data())) return rc;
     }
+    if (sp) if (const int rc = score_panel_close(c, s, sp)) return rc;
     close_posterior_call(c, &pc.timer);
     return CAFE_OK;
 }
@@ -428,7 +453,7 @@ int gradient_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, const c
 extern "C" {
 
 int cafe_score_gradient(cafe_ctx* ctx, const cafe_params* params, int32_t root_rule, const cafe_gradient_out* out) {
-    return cafe::guarded(ctx, "cafe_score_gradient", [&] { return cafe::gradient_impl(ctx, params, root_rule, out); });
+    return cafe::guarded(ctx, "cafe_score_gradient", [&] { return cafe::gradient_walk(ctx, "cafe_score_gradient", params, root_rule, out, nullptr); });
 }
 
 int cafe_bd_rates_grad(double lambda, double mu, double t, double out[4]) {

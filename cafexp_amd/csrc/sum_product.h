@@ -98,6 +98,27 @@ int launch_leaf_sums(cafe_ctx* c, hipStream_t s, const double* G, int np, int64_
 int launch_finish_sums(cafe_ctx* c, hipStream_t s, const double* zk, const double* probs, int K, int64_t ld, int64_t stride, const double* lbest, double* acc,
                        int n_acc, double* Z, double* lnl);
 
+// The score panel of cafe_branch_scores (branch_scores.hip): S [P][Fp], one row per entry of the score vector z, one column
+// per distinct family, kept on the device over all column batches.  Rows: the log-rate scores of the non-root nodes in node
+// order (births, then deaths, while death rates are set), then the n_glob global scores.  The walk adds into a branch's row
+// as it adds into the sums per lambda index; per batch the rows are divided by Z (a failed column: zeros), the global scores
+// come from the host, which has just formed them, and the per-family rows go out; after the last batch the Gram matrix.
+struct ScorePanel {
+    const cafe_branch_scores_out* out = nullptr;
+    int n_par = 1, n_branch = 0, n_glob = 0, P = 0;
+    int64_t Fp = 0;
+    std::vector<int> slot;              // [n_nodes] index among the non-root nodes, -1 at the root
+    std::vector<char> col_failed;       // [Fp]
+    DevBuf S;
+    double* base() const { return static_cast<double*>(S.p); }
+};
+int score_panel_open(cafe_ctx* c, const char* entry, int n_par, int n_glob, ScorePanel* sp);
+inline double* score_panel_row(const ScorePanel* sp, int v, int p, int64_t f0) { return sp->base() + ((int64_t)p * sp->n_branch + sp->slot[v]) * sp->Fp + f0; }
+int score_panel_batch(cafe_ctx* c, hipStream_t s, ScorePanel* sp, int64_t f0, int64_t ld, int64_t cols, const double* d_Z, const double* h_Z, const double* h_glob);
+int score_panel_close(cafe_ctx* c, hipStream_t s, ScorePanel* sp);
+// cafe_score_gradient's checks, passes and outputs under the error prefix `entry`; sp: nullptr, or the panel to fill
+int gradient_walk(cafe_ctx* c, const char* entry, const cafe_params* pr, int32_t root_rule, const cafe_gradient_out* out, ScorePanel* sp);
+
 // ------------------------------------------------------------------------------------- the frame of the posterior calls
 // A family whose evidence Z is zero, negative, NaN or infinite has failed: its doubles are kNaN
 __host__ __device__ inline bool evidence_failed(double z) { return !(z > 0.0) || z > DBL_MAX; }

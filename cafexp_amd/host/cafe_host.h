@@ -13,6 +13,7 @@
 // forward to cafe_score (HIP kernels), and fail loudly when the library or a GPU is missing.
 #pragma once
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <functional>
@@ -318,12 +319,55 @@ struct standard_errors {
 // scores[family][parameter]
 standard_errors compute_standard_errors(const std::vector<std::string>& names, const std::vector<double>& estimates,
                                         const std::vector<double>& scores, size_t n_families);
+// The inverse of a symmetric positive definite matrix [n][n] by Gauss-Jordan elimination with full pivoting on its correlation
+// form; false when a diagonal entry is not positive or a pivot falls below 1e-12 of the unit scale (standard_errors.cpp)
+bool invert_information(const std::vector<double>& A, size_t n, std::vector<double>& inv);
 // d multiplier_k / d alpha of the discrete gamma (get_gamma) by central differences with h = alpha / 100: the routine's
 // quantiles are good to about 1e-6, so a smaller step would differentiate its noise
 std::vector<double> multiplier_slopes(size_t n_categories, double alpha);
 // <Model>_standard_errors.txt: one line per parameter (name, estimate, SE, Wald 95 % interval), the correlation matrix, the
 // total score and what the errors are conditional on
 void write_standard_errors(const standard_errors& se, const std::string& model_identifier, const std::string& dir, const std::string& conditional_on);
+
+// cafe_branch_scores' total and Gram matrix over the score vector z (include/cafe_mi355x.h): n_par * n_branch branch scores
+// (n_par = 2 under death rates: births, then deaths), then d_lambda [n_lambdas], d_mu [n_lambdas] (n_par = 2), d_multiplier
+// [n_categories].  slot[i]: the index of the caller's node order[i] among the branch scores of one rate, -1 at the root.
+struct branch_scores_result {
+    size_t P = 0, n_branch = 0, n_par = 1, n_lambdas = 0, n_categories = 0;      // n_categories: 0 for the base model
+    std::vector<int> slot;
+    std::vector<double> total, gram;                                 // [P], [P][P]
+    size_t families_used = 0, families_failed = 0;
+    size_t global(size_t i) const { return n_par * n_branch + i; }   // z index of the i-th global score
+};
+// Rao's score test of a rate shift on every branch and clade (rate_shift_scan.cpp), from one cafe_branch_scores call at the
+// fitted optimum.  For a direction a in branch-score space, with theta the searched global parameters (as directions in z),
+//     U_a = a^T U - a^T G T (T^T G T)^-1 T^T U,   V_a = a^T G a - a^T G T (T^T G T)^-1 T^T G a,   T = U_a^2 / V_a,
+// p = erfc(sqrt(T / 2)), and exp(U_a / V_a) the one-step estimate of the rate multiplier.  Not testable (NaN):
+// V_a <= 1e-12 a^T G a.  holm: Holm's adjustment over the testable rows of the column.
+struct score_test {
+    bool testable = false;
+    double U = NAN, V = NAN, T = NAN, p = NAN, multiplier = NAN, holm = NAN;
+};
+struct rate_shift_row {
+    const clade* node = nullptr;
+    score_test branch, subtree;          // a = the joint-rate score of the branch / of every branch at and below the node
+    bool joint_testable = false;         // with death rates: the 2-df test on (birth, death) of the branch, p = exp(-T / 2)
+    double joint_T = NAN, joint_p = NAN;
+};
+struct rate_shift_scan {
+    std::vector<rate_shift_row> rows;    // the non-root nodes of the caller's order
+    bool two_rates = false;
+    int best = -1;                       // row with the smallest Holm-adjusted clade p, -1 when no clade is testable
+    size_t families_used = 0, families_failed = 0;
+    std::vector<std::string> profiled;   // names of the searched parameters
+};
+// theta: one direction [P] per searched parameter, named in `names`
+rate_shift_scan compute_rate_shift_scan(const branch_scores_result& bs, const std::vector<const clade*>& order,
+                                        const std::vector<std::vector<double>>& theta, const std::vector<std::string>& names);
+// <Model>_rate_shift_scan.tab: one row per non-root node (naming of <Model>_branch_events.tab)
+void write_rate_shift_scan(const rate_shift_scan& scan, const std::string& model_identifier, const std::string& dir, const std::vector<const clade*>& order);
+// <Model>_rate_shift_lambda_tree.txt: the tree in -y format, the clade of row `best` labelled 2 and the rest 1
+void write_rate_shift_lambda_tree(const rate_shift_scan& scan, const clade* tree, const std::string& model_identifier, const std::string& dir);
 
 // The two models whose infer_family_likelihoods runs on the GPU through the C ABI.
 class hip_model_base : public model {
@@ -370,6 +414,10 @@ public:
     // Per-family scores of the model's likelihood at its current parameters (cafe_score_gradient; root_rule CAFE_ROOT_MAX is
     // what infer_family_likelihoods sums)
     gradient_result score_gradient(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, int root_rule);
+    // The total and the Gram matrix of the per-family score vectors with the scores kept per branch (cafe_branch_scores);
+    // nothing per family crosses to the host.  slot in `order`
+    branch_scores_result branch_scores(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, int root_rule,
+                                       const std::vector<const clade*>& order);
     // Expected number of births and of deaths on the branch above every node given the leaf counts, under the same model
     // (cafe_expected_events); columns in `order`
     events_result expected_events(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<const clade*>& order);

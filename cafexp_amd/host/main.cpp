@@ -39,6 +39,10 @@ static void usage() {
         "                  [--standard-errors]   after the search: the per-family scores at the optimum, the standard error of every\n"
         "                  estimated lambda, mu (--estimate-mu) and alpha from their outer product, Wald 95 %% intervals, correlations and the\n"
         "                  total score -> <Model>_standard_errors.txt in -o OUTDIR (default results); one GPU, not with -b or --simulate\n"
+        "                  [--rate-shift-scan [-P PVALUE]]   after the search: one pass at the optimum keeps the score of every branch's rate\n"
+        "                  and their information; Rao score tests of a rate shift on every branch and in every clade (and, under death\n"
+        "                  rates, of birth and death jointly), Holm-adjusted -> <Model>_rate_shift_scan.tab in -o OUTDIR (default results), and\n"
+        "                  <Model>_rate_shift_lambda_tree.txt (-y format) when a clade passes PVALUE (default 0.05); one GPU, not with -b or --simulate\n"
         "  --gpus N: the scorer calls shard the families over devices 0..N-1 (one host thread per GPU, one RCCL all-reduce per call)\n"
         "lambda per family (the reference's -b): cafexp_hip -t TREE -i FAMILIES -b [-y LAMBDA_TREE] [-e ERRMODEL] [-p [L]] [-z] [-s SEED] [-I MAXITER]\n"
         "                  [--workspace BYTES] [-o OUTDIR]   writes OUTDIR (default results)/Base_lambda_per_family.txt, one line per family\n"
@@ -178,6 +182,7 @@ int main(int argc, char** argv) {
     std::string family_mu;                                       // --family-mu (with -b): rates, or "estimate"
     bool do_standard_errors = false;                             // --standard-errors
     bool do_events = false;                                      // --expected-events
+    bool do_rate_shift = false;                                  // --rate-shift-scan
     unsigned seed = 0;
     bool have_seed = false;
     for (int i = 1; i < argc; ++i) {
@@ -197,6 +202,7 @@ int main(int argc, char** argv) {
         else if (a == "--family-mu") family_mu = next();
         else if (a == "--standard-errors") do_standard_errors = true;
         else if (a == "--expected-events") do_events = true;
+        else if (a == "--rate-shift-scan") do_rate_shift = true;
         else if (a == "-e") { use_err = true; err_path = optional(); }
         else if (a == "-p") { use_poisson = true; std::string v = optional(); poisson = v.empty() ? 0 : std::stod(v); }
         else if (a == "-f") rootdist_path = next();
@@ -234,6 +240,7 @@ int main(int argc, char** argv) {
         if (!family_mu.empty()) { std::fprintf(stderr, "cafexp_hip: --family-mu sets the death rates of -b: it is not supported without -b\n"); return 1; }
         if (do_standard_errors) { std::fprintf(stderr, "cafexp_hip: --standard-errors belongs to a fitted model: --simulate is not supported with it\n"); return 1; }
         if (do_events) { std::fprintf(stderr, "cafexp_hip: --expected-events belongs to a fitted model: --simulate is not supported with it\n"); return 1; }
+        if (do_rate_shift) { std::fprintf(stderr, "cafexp_hip: --rate-shift-scan belongs to a fitted model: --simulate is not supported with it\n"); return 1; }
         if (have_seed) randomizer_engine.seed(seed);
         return simulate_main(tree_path, fam_path, rootdist_path, lambda_tree_path, multi, err_path, use_err, fixed_lambda, fixed_alpha, k,
                              simulate_n, simulate_on_device, have_seed ? seed : randomizer_engine(), device, sim_workspace, out_dir, mu_list);
@@ -254,6 +261,12 @@ int main(int argc, char** argv) {
         const char* why = nullptr;
         if (gpus_given) why = "--standard-errors runs on one GPU: --gpus is not supported with it";
         else if (per_family) why = "--standard-errors needs one fitted model: -b is not supported with it";
+        if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
+    }
+    if (do_rate_shift) {
+        const char* why = nullptr;
+        if (gpus_given) why = "--rate-shift-scan runs on one GPU: --gpus is not supported with it";
+        else if (per_family) why = "--rate-shift-scan needs one fitted model: -b is not supported with it";
         if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
     }
     if (do_marginal) {
@@ -529,9 +542,11 @@ int main(int argc, char** argv) {
         // standard errors of what the search estimated, from the per-family scores of the searched objective at the optimum
         standard_errors se;
         std::vector<double> slopes;
+        // what the search estimated (both --standard-errors and --rate-shift-scan condition on the rest)
+        auto g = dynamic_cast<hip_gamma_model*>(mdl.get());
+        const bool lambda_searched = scorer && !d.p_lambda, alpha_searched = scorer && g && !(fixed_alpha > 0);
+        if ((do_standard_errors || do_rate_shift) && alpha_searched) slopes = multiplier_slopes(g->get_lambda_multipliers().size(), g->get_alpha());
         if (do_standard_errors) {
-            auto g = dynamic_cast<hip_gamma_model*>(mdl.get());
-            const bool lambda_searched = scorer && !d.p_lambda, alpha_searched = scorer && g && !(fixed_alpha > 0);
             const gradient_result gr = mdl->score_gradient(d.p_prior.get(), d.rootdist, CAFE_ROOT_MAX);
             const std::vector<double> lv = mdl->get_lambda()->values();
             const size_t nl = gr.n_lambdas, F = d.gene_families.size();
@@ -540,7 +555,7 @@ int main(int argc, char** argv) {
             auto rate_name = [&](const char* what, size_t i) { return nl == 1 ? std::string(what) : what + std::to_string(i + 1); };
             if (lambda_searched) for (size_t i = 0; i < nl; ++i) { names.push_back(rate_name("Lambda", i)); est.push_back(lv[i]); }
             if (estimate_mu) for (size_t i = 0; i < nl; ++i) { names.push_back(rate_name("Mu", i)); est.push_back(mdl->death_rates()[i]); }
-            if (alpha_searched) { names.push_back("Alpha"); est.push_back(g->get_alpha()); slopes = multiplier_slopes(gr.n_categories, g->get_alpha()); }
+            if (alpha_searched) { names.push_back("Alpha"); est.push_back(g->get_alpha()); }
             if (names.empty()) throw std::runtime_error("--standard-errors: no parameter was estimated (lambda, mu and alpha are all fixed)");
             const size_t P = names.size();
             std::vector<double> scores(F * P);
@@ -563,6 +578,35 @@ int main(int argc, char** argv) {
             const std::string dir = out_dir.empty() ? "results" : out_dir;
             if (::mkdir(dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("Failed to create directory " + dir);
             write_standard_errors(se, mdl->name(), dir, cond);
+        }
+        // score tests of a rate shift on every branch and clade, from the branch scores and their information at the optimum
+        rate_shift_scan scan;
+        double scan_s = 0;
+        bool scan_tree = false;
+        if (do_rate_shift) {
+            auto t0 = std::chrono::steady_clock::now();
+            cladevector order;
+            d.p_tree->apply_reverse_level_order([&order](const clade* c) { order.push_back(c); });
+            const branch_scores_result bs = mdl->branch_scores(d.p_prior.get(), d.rootdist, CAFE_ROOT_MAX, order);
+            std::vector<std::vector<double>> theta;
+            std::vector<std::string> names;
+            auto rate_name = [&](const char* what, size_t i) { return bs.n_lambdas == 1 ? std::string(what) : what + std::to_string(i + 1); };
+            auto unit = [&](size_t at) { std::vector<double> v(bs.P, 0.0); v[at] = 1.0; return v; };
+            if (lambda_searched) for (size_t i = 0; i < bs.n_lambdas; ++i) { names.push_back(rate_name("Lambda", i)); theta.push_back(unit(bs.global(i))); }
+            if (estimate_mu) for (size_t i = 0; i < bs.n_lambdas; ++i) { names.push_back(rate_name("Mu", i)); theta.push_back(unit(bs.global(bs.n_lambdas + i))); }
+            if (alpha_searched) {
+                std::vector<double> v(bs.P, 0.0);
+                for (size_t c = 0; c < bs.n_categories; ++c) v[bs.global(bs.n_lambdas * bs.n_par + c)] = slopes[c];
+                names.push_back("Alpha"); theta.push_back(v);
+            }
+            scan = compute_rate_shift_scan(bs, order, theta, names);
+            const std::string dir = out_dir.empty() ? "results" : out_dir;
+            if (::mkdir(dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("Failed to create directory " + dir);
+            write_rate_shift_scan(scan, mdl->name(), dir, order);
+            scan_tree = scan.best >= 0 && scan.rows[(size_t)scan.best].subtree.holm < test_pvalue;
+            if (scan_tree) write_rate_shift_lambda_tree(scan, d.p_tree.get(), mdl->name(), dir);
+            else std::fprintf(stderr, "cafexp_hip: --rate-shift-scan: no rate shift passed the threshold %g (Holm-adjusted clade p)\n", test_pvalue);
+            scan_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         }
         std::printf("{\"model\": \"%s\", ", mdl->name().c_str());
         print_num("neg_lnl", score);
@@ -620,6 +664,15 @@ int main(int argc, char** argv) {
             list("total_score", se.total_score); std::printf(", ");
             if (!slopes.empty()) { list("dmultiplier_dalpha", slopes); std::printf(", "); }
             std::printf("\"families\": %zu, \"left_out\": %zu}", se.families_used, se.families_left_out);
+        }
+        if (do_rate_shift) {
+            std::printf(", \"rate_shift_scan\": {\"seconds\": %.3f, \"families\": %zu, \"left_out\": %zu, \"profiled\": [", scan_s, scan.families_used, scan.families_failed);
+            for (size_t i = 0; i < scan.profiled.size(); ++i) std::printf("%s\"%s\"", i ? ", " : "", scan.profiled[i].c_str());
+            std::printf("], \"dmultiplier_dalpha\": [");
+            for (size_t i = 0; i < slopes.size(); ++i) std::printf("%s%.17g", i ? ", " : "", slopes[i]);
+            std::printf("], \"threshold\": %.17g, \"lambda_tree_written\": %s, ", test_pvalue, scan_tree ? "true" : "false");
+            print_num("smallest_clade_holm_p", scan.best >= 0 ? scan.rows[(size_t)scan.best].subtree.holm : NAN, false);
+            std::printf("}");
         }
         std::printf("}\n");
     } catch (const std::exception& e) {

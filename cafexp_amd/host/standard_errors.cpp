@@ -40,8 +40,8 @@ gradient_result hip_model_base::score_gradient(root_equilibrium_distribution* pr
 
 // The inverse of a symmetric positive definite matrix by Gauss-Jordan elimination with full pivoting on its correlation form
 // (rows and columns scaled by 1 / sqrt(diagonal)); false when a diagonal entry is not positive or a pivot falls below 1e-12
-// of the unit scale: singular or too ill-conditioned to report.
-static bool invert_information(const std::vector<double>& A, size_t n, std::vector<double>& inv) {
+// of the unit scale: singular or too ill-conditioned to report.  (rate_shift_scan.cpp inverts its T^T G T with it.)
+bool invert_information(const std::vector<double>& A, size_t n, std::vector<double>& inv) {
     std::vector<double> s(n);
     for (size_t i = 0; i < n; ++i) {
         if (!(A[i * n + i] > 0) || !std::isfinite(A[i * n + i])) return false;

@@ -437,6 +437,48 @@ int cafe_score_gradient(cafe_ctx* ctx, const cafe_params* params, int32_t root_r
  * both equal t / (1 + lambda t)^2, the derivative of the lambda = mu kernels' alpha.  Pure host code, no device needed. */
 int cafe_bd_rates_grad(double lambda, double mu, double t, double out[4]);
 
+/* Per-branch scores for a rate-shift scan: cafe_score_gradient's derivative kept per branch, and the information of those
+ * scores.  For every family f and non-root node v, with c_v a factor on BOTH rates of the branch above v (and on nothing
+ * else), rate[f][v] = d lnL_f / d log c_v at c = 1; since the matrix of a branch depends on it only through lambda t and mu t,
+ * that is also t_v d lnL_f / d t_v.  With death rates set, birth and death are the same for a factor on lambda alone and on mu
+ * alone, rate = birth + death; without them birth / death non-NULL is CAFE_ERR_STATE.  The model, the two passes, the root
+ * rules, the column batches and the error codes are cafe_score_gradient's; with the gamma model the categories mix as there:
+ * a branch's score is sum_k of the category's weight times (lambda_q m_k d/d(lambda_q m_k) + mu_q m_k d/d(mu_q m_k)) restricted
+ * to that branch.  The derivative is that of the smooth likelihood at the quantized keys; a zero-marked branch (cafe_bd_rates
+ * out[2]) gives exactly 0.  Sums: over the branches of lambda index q, rate (birth) adds up to lambdas[q] d_lambda[q], death to
+ * mus[q] d_mu[q]; over all branches rate adds up to sum_k multipliers[k] d_multiplier[k] -- to rounding.
+ * family_lnl, d_lambda, d_mu, d_multiplier and failed are bit for bit cafe_score_gradient's for the same arguments (one body).
+ * The score vector z_f has P = cafe_branch_scores_dim entries: without death rates `rate` of every non-root node in the
+ * problem's node order; with death rates `birth` of every non-root node, then `death` of every non-root node; then d_lambda
+ * [n_lambdas], d_mu [n_lambdas] while death rates are set, d_multiplier [K] under the gamma model.  total = sum_f z_f and
+ * gram = sum_f z_f z_f^T over the families that did not fail (n_used of them), formed on the device once, after the last
+ * column batch, from the scores of all distinct families weighted by their multiplicity (cafe_weighted_gram): neither depends
+ * on workspace_limit, and gram is exactly symmetric.  The panel of those scores -- P x (distinct families, padded to 128)
+ * doubles -- stays on the device beside one batch and is not counted against workspace_limit; CAFE_ERR_MEMORY when it does not
+ * fit.  A failed family (Z = 0 or not finite) has NaN doubles in its rows, failed = 1, and adds nothing to total / gram.  The
+ * root's entries of rate / birth / death are NaN.  Any pointer may be NULL; with gram, total, n_used NULL no Gram is formed, and
+ * with the [n_families][n_nodes] pointers NULL nothing of that size leaves the device.  cafe_debug_marginal_gemm reports this
+ * call's GEMM launches: the same as cafe_score_gradient's. */
+typedef struct cafe_branch_scores_out {
+    double*  rate;         /* [n_families][n_nodes] d lnL_f / d log c_v, c_v scaling BOTH rates of the branch above v; NaN at the root */
+    double*  birth;        /* [n_families][n_nodes] d / d log lambda_v; only while death rates are set (else CAFE_ERR_STATE) */
+    double*  death;        /* [n_families][n_nodes] d / d log mu_v;     likewise; rate = birth + death */
+    double*  family_lnl;   /* as cafe_gradient_out */
+    double*  d_lambda;
+    double*  d_mu;
+    double*  d_multiplier; /* as cafe_gradient_out, from the same pass */
+    int32_t* failed;
+    double*  total;        /* [P]    U = sum_f z_f over the families that did not fail */
+    double*  gram;         /* [P][P] sum_f z_f z_f^T, row-major, exactly symmetric */
+    int64_t* n_used;       /* families that entered total / gram */
+} cafe_branch_scores_out;
+int cafe_branch_scores(cafe_ctx* ctx, const cafe_params* params, int32_t root_rule, const cafe_branch_scores_out* out);
+/* P, the length of the score vector, for this context's death rates and params->model / n_categories */
+int cafe_branch_scores_dim(const cafe_ctx* ctx, const cafe_params* params, int32_t* P);
+/* measurement: the flops of the MFMAs of the Gram kernel of the last cafe_branch_scores (lower-triangle tiles only) and, when
+ * it ran with profiling on (cafe_set_profiling), the HIP-event time in milliseconds of its three launches (else 0) */
+int cafe_debug_gram(cafe_ctx* ctx, double* ms, double* flops);
+
 /* Expected gene gains and losses: the posterior expectation, given the leaf counts, of the number of births (gains) and of
  * deaths (losses) on the branch above every node -- the turnover that node sizes do not show (a branch on which a family gained
  * three genes and lost three has no net change).  The model is cafe_marginal_reconstruct's: the call's lambdas, categories,
@@ -532,6 +574,12 @@ int cafe_build_matrices(int32_t device, int32_t n, int32_t count, const double* 
 /* the same under separate birth and death rates (lambdas[i], mus[i], ts[i]): K1's two-rate instantiation (bd_matrix_lm.hip) */
 int cafe_build_matrices_lm(int32_t device, int32_t n, int32_t count, const double* lambdas, const double* mus, const double* ts,
                            int32_t layout, double* out);
+/* The weighted Gram matrix of cafe_branch_scores alone: gram[p][p] = S diag(w) S^T and total[p] = S w for S [p][n] row-major,
+ * host pointers (gram or total may be NULL).  One wave forms one 16 x 16 tile of the lower triangle over one slab of 2048
+ * columns on v_mfma_f64_16x16x4_f64; the slabs' partial tiles are added in slab order and the upper triangle is the mirror
+ * image, so gram is exactly symmetric and its bits depend on (p, n) alone.  A column of weight 0 adds exactly 0 whatever it
+ * holds. */
+int cafe_weighted_gram(int32_t device, int32_t p, int64_t n, const double* S, const double* w, double* gram, double* total);
 /* back-to-back v_mfma_f64_16x16x4_f64 issue-rate probe: returns achieved TFLOP/s on `device`. */
 int cafe_probe_fp64_mfma(int32_t device, double* tflops);
 
