@@ -68,6 +68,11 @@ class CafeEventsOut(C.Structure):
     _fields_ = [("gains", _f64p), ("losses", _f64p), ("log_evidence", _f64p), ("failed", _i32p)]
 
 
+class CafeLeafPredictiveOut(C.Structure):
+    _fields_ = [("mean", _f64p), ("sd", _f64p), ("p_below", _f64p), ("p_obs", _f64p), ("p_above", _f64p), ("log_evidence", _f64p),
+                ("failed", _i32p)]
+
+
 class CafeHistoryOut(C.Structure):
     _fields_ = [("sizes", _i32p), ("category", _i32p), ("n_increase", _i64p), ("n_decrease", _i64p), ("net_change", _i64p),
                 ("log_evidence", _f64p), ("failed", _i32p)]
@@ -110,6 +115,7 @@ EXPORTS = [
     "cafe_set_death_rates", "cafe_bd_rates", "cafe_build_matrices_lm", "cafe_score_per_family_lm", "cafe_simulate_lm",
     "cafe_score_gradient", "cafe_bd_rates_grad", "cafe_expected_events", "cafe_bd_rates_events",
     "cafe_branch_scores", "cafe_branch_scores_dim", "cafe_weighted_gram", "cafe_debug_gram",
+    "cafe_leaf_predictive",
 ]
 CAFE_COMM_ID_BYTES = 128
 
@@ -193,6 +199,8 @@ def load():
     L.cafe_expected_events.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.POINTER(CafeEventsOut)]
     L.cafe_bd_rates_events.restype = C.c_int
     L.cafe_bd_rates_events.argtypes = [C.c_double, C.c_double, C.c_double, _f64p]
+    L.cafe_leaf_predictive.restype = C.c_int
+    L.cafe_leaf_predictive.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.POINTER(CafeLeafPredictiveOut)]
     L.cafe_branch_scores.restype = C.c_int
     L.cafe_branch_scores.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.POINTER(CafeBranchScoresOut)]
     L.cafe_branch_scores_dim.restype = C.c_int
@@ -536,6 +544,22 @@ class Context:
         for name, t in CafeEventsOut._fields_:
             setattr(eo, name, _p(res[name], t))
         self._check(self._lib.cafe_expected_events(self._h, C.byref(cp), C.byref(eo)))
+        return res
+
+    def leaf_predictive(self, pr: Params, alpha: float = 1.0) -> dict:
+        """cafe_leaf_predictive: the leave-one-out predictive distribution of every leaf count -- species l's count given the
+        counts of every other species of the family, under marginal_reconstruct's model.  Returns numpy arrays: mean, sd,
+        p_below, p_obs, p_above [n_families][n_taxa] (columns as the problem's counts; NaN where the distribution has no
+        mass), log_evidence and failed [n_families].  p_below + p_obs and p_obs + p_above are the one-sided tail
+        probabilities of the observed count."""
+        cp, keep = self._params(pr, alpha)
+        F, nt = self.n_families, self.problem.n_taxa
+        res = {name: np.full((F, nt), np.nan) for name in ("mean", "sd", "p_below", "p_obs", "p_above")}
+        res.update({"log_evidence": np.empty(F), "failed": np.empty(F, dtype=np.int32)})
+        lo = CafeLeafPredictiveOut()
+        for name, t in CafeLeafPredictiveOut._fields_:
+            setattr(lo, name, _p(res[name], t))
+        self._check(self._lib.cafe_leaf_predictive(self._h, C.byref(cp), C.byref(lo)))
         return res
 
     def sample_histories(self, pr: Params, n_draws: int, seed: int, alpha: float = 1.0, sizes: bool = True) -> dict:

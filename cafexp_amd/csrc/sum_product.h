@@ -1,5 +1,5 @@
 // Internal: what cafe_marginal_reconstruct (marginal.hip), cafe_sample_histories (history.hip), cafe_score_gradient
-// (gradient.hip) and cafe_expected_events (events.hip) share.  The engine (sum_product.hip): the up pass of sum-products, F_v[i] = sum_j P_v[i][j] B_v[j], B_p[i] =
+// (gradient.hip), cafe_expected_events (events.hip) and cafe_leaf_predictive (predictive.hip) share.  The engine (sum_product.hip): the up pass of sum-products, F_v[i] = sum_j P_v[i][j] B_v[j], B_p[i] =
 // prod_{children} F_c[i], the leaves gathered with the error model's taps, its fp64 MFMA GEMM and product kernel, the down pass's
 // walk.  The frame, on top of cafe_call.h: argument checks, opening, constants, the test for a failed family, closing.
 #pragma once

@@ -13,6 +13,7 @@
 // forward to cafe_score (HIP kernels), and fail loudly when the library or a GPU is missing.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -287,6 +288,56 @@ struct events_result {
 void write_events_reports(const events_result& res, const std::string& model_identifier, const std::string& dir,
                           const std::vector<const clade*>& order, const std::vector<gene_family>& families);
 
+// cafe_leaf_predictive's outputs, [family][species] with the species in the order of `species` (NaN for a cell whose predictive
+// distribution has no mass; failed: [family], judged on the family's evidence)
+struct leaf_predictive_result {
+    std::vector<std::string> species;
+    std::vector<int> observed;                                       // [family][species]
+    std::vector<double> mean, sd, p_below, p_obs, p_above;
+    std::vector<int32_t> failed;
+    size_t n_species() const { return species.size(); }
+};
+// Holm's step-down adjustment of the p-values p (any order): adjusted[i] = max over the entries at or before i in ascending
+// order (ties in input order) of min(1, (n - rank) p)
+inline std::vector<double> holm_adjusted(const std::vector<double>& p) {
+    std::vector<size_t> idx(p.size());
+    for (size_t i = 0; i < idx.size(); ++i) idx[i] = i;
+    std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return p[a] < p[b]; });
+    std::vector<double> adj(p.size());
+    double run = 0;
+    for (size_t r = 0; r < idx.size(); ++r) {
+        run = std::max(run, std::min(1.0, (double)(idx.size() - r) * p[idx[r]]));
+        adj[idx[r]] = run;
+    }
+    return adj;
+}
+// One finite cell of the table as an outlier candidate: the one-sided tails p_low = p_below + p_obs and p_high = p_obs + p_above,
+// the two-sided p = min(1, 2 min(p_low, p_high)), its direction (low: p_low <= p_high) and, after leaf_outliers, Holm's adjustment
+// over all finite cells of the table
+struct leaf_cell {
+    size_t family = 0, species = 0;
+    double p_low = NAN, p_high = NAN, p = NAN, holm = NAN;
+    bool low = false;
+};
+// every finite cell, most extreme first (Holm-adjusted p, then p, then table order)
+std::vector<leaf_cell> leaf_outliers(const leaf_predictive_result& res);
+// Per species: the finite cells, the mean of (x - mean) / sd over the cells with sd > 0, the outliers (holm <= threshold) low and
+// high, and sum log p_obs over the cells with p_obs > 0
+struct species_fit {
+    size_t cells = 0, low = 0, high = 0;
+    double mean_z = NAN, log_p_obs = 0;
+};
+std::vector<species_fit> leaf_species_fit(const leaf_predictive_result& res, const std::vector<leaf_cell>& cells, double threshold);
+struct leaf_predictive_summary {
+    size_t failed_cells = 0, outliers = 0;
+    double log_pseudo_likelihood = 0;                                // sum log p_obs over the finite cells with p_obs > 0
+};
+// <Model>_leaf_predictive.tab (mean:sd:p_low:p_high per family and species, "-" for a cell without mass; family order of
+// <Model>_count.tab), <Model>_leaf_outliers.tab (the cells with holm <= threshold, most extreme first: family, species, observed,
+// mean, sd, direction, p, adjusted p) and <Model>_species_fit.tab (leaf_species_fit)
+leaf_predictive_summary write_leaf_predictive_reports(const leaf_predictive_result& res, double threshold, const std::string& model_identifier,
+                                                      const std::string& dir, const std::vector<gene_family>& families);
+
 // cafe_sample_histories' counts, [draw][index in the caller's node order] (failed: [family])
 struct history_result {
     size_t n_draws = 0, n_nodes = 0;
@@ -421,6 +472,9 @@ public:
     // Expected number of births and of deaths on the branch above every node given the leaf counts, under the same model
     // (cafe_expected_events); columns in `order`
     events_result expected_events(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<const clade*>& order);
+    // The leave-one-out predictive distribution of every leaf count under the same model (cafe_leaf_predictive): species in
+    // the order of the table's columns on the device (the leaves of the post-order)
+    leaf_predictive_result leaf_predictive(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist);
     // Whole ancestral histories drawn from the same posterior (cafe_sample_histories), counted per draw on the device:
     // how many families expanded / contracted on every branch and the net change, rows in `order`
     history_result sample_histories(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, int n_draws, uint64_t seed,

@@ -199,6 +199,37 @@ void write_events_reports(const events_result& res, const std::string& model_ide
     }
 }
 
+leaf_predictive_result hip_model_base::leaf_predictive(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist) {
+    std::vector<double> mult, probs;
+    double alpha = 0;
+    category_parameters(mult, probs, alpha);
+    const int K = mult.empty() ? 1 : (int)mult.size();
+    ensure_context(K);
+    std::vector<float> prior_f;
+    std::vector<double> err, lambdas;
+    gather_call_inputs(prior, rootdist, prior_f, err, lambdas);
+    cafe_params pr{};
+    pr.model = mult.empty() ? CAFE_MODEL_BASE : CAFE_MODEL_GAMMA;
+    pr.lambdas = lambdas.data(); pr.n_categories = K;
+    pr.multipliers = mult.empty() ? nullptr : mult.data();
+    pr.cat_probs = probs.empty() ? nullptr : probs.data();
+    pr.alpha = alpha; pr.prior = prior_f.data(); pr.error_model = err.empty() ? nullptr : err.data();
+    leaf_predictive_result res;
+    for (const clade* c : _order) if (c->is_leaf()) res.species.push_back(c->get_taxon_name());      // the columns of the context's counts
+    const size_t F = _p_gene_families->size(), T = res.species.size();
+    res.observed.resize(F * T);
+    for (size_t f = 0; f < F; ++f)
+        for (size_t t = 0; t < T; ++t) res.observed[f * T + t] = (*_p_gene_families)[f].get_species_size(res.species[t]);
+    for (std::vector<double>* v : {&res.mean, &res.sd, &res.p_below, &res.p_obs, &res.p_above}) v->assign(F * T, NAN);
+    res.failed.resize(F);
+    cafe_leaf_predictive_out out{};
+    out.mean = res.mean.data(); out.sd = res.sd.data(); out.p_below = res.p_below.data(); out.p_obs = res.p_obs.data();
+    out.p_above = res.p_above.data(); out.failed = res.failed.data();
+    if (cafe_leaf_predictive(_ctx, &pr, &out) != CAFE_OK)
+        throw std::runtime_error(std::string("cafe_leaf_predictive: ") + cafe_last_error(_ctx));
+    return res;
+}
+
 history_result hip_model_base::sample_histories(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, int n_draws, uint64_t seed,
                                                 const std::vector<const clade*>& order) {
     std::vector<double> mult, probs;

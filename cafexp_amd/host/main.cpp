@@ -43,6 +43,12 @@ static void usage() {
         "                  and their information; Rao score tests of a rate shift on every branch and in every clade (and, under death\n"
         "                  rates, of birth and death jointly), Holm-adjusted -> <Model>_rate_shift_scan.tab in -o OUTDIR (default results), and\n"
         "                  <Model>_rate_shift_lambda_tree.txt (-y format) when a clade passes PVALUE (default 0.05); one GPU, not with -b or --simulate\n"
+        "                  [--leaf-predictive [-P PVALUE]]   after the search: for every family and species the distribution of the species'\n"
+        "                  count predicted from the counts of all the other species under the fitted model -> in -o OUTDIR (default results)\n"
+        "                  <Model>_leaf_predictive.tab (mean:sd:p_low:p_high, the two one-sided tails of the observed count),\n"
+        "                  <Model>_leaf_outliers.tab (the cells whose two-sided p, Holm-adjusted over the table, is <= PVALUE, default 0.05) and\n"
+        "                  <Model>_species_fit.tab (per species: mean standardised residual, outliers low / high, sum log p_obs); one GPU, not\n"
+        "                  with -b or --simulate\n"
         "  --gpus N: the scorer calls shard the families over devices 0..N-1 (one host thread per GPU, one RCCL all-reduce per call)\n"
         "lambda per family (the reference's -b): cafexp_hip -t TREE -i FAMILIES -b [-y LAMBDA_TREE] [-e ERRMODEL] [-p [L]] [-z] [-s SEED] [-I MAXITER]\n"
         "                  [--workspace BYTES] [-o OUTDIR]   writes OUTDIR (default results)/Base_lambda_per_family.txt, one line per family\n"
@@ -183,6 +189,7 @@ int main(int argc, char** argv) {
     bool do_standard_errors = false;                             // --standard-errors
     bool do_events = false;                                      // --expected-events
     bool do_rate_shift = false;                                  // --rate-shift-scan
+    bool do_leaf_predictive = false;                             // --leaf-predictive
     unsigned seed = 0;
     bool have_seed = false;
     for (int i = 1; i < argc; ++i) {
@@ -203,6 +210,7 @@ int main(int argc, char** argv) {
         else if (a == "--standard-errors") do_standard_errors = true;
         else if (a == "--expected-events") do_events = true;
         else if (a == "--rate-shift-scan") do_rate_shift = true;
+        else if (a == "--leaf-predictive") do_leaf_predictive = true;
         else if (a == "-e") { use_err = true; err_path = optional(); }
         else if (a == "-p") { use_poisson = true; std::string v = optional(); poisson = v.empty() ? 0 : std::stod(v); }
         else if (a == "-f") rootdist_path = next();
@@ -241,6 +249,7 @@ int main(int argc, char** argv) {
         if (do_standard_errors) { std::fprintf(stderr, "cafexp_hip: --standard-errors belongs to a fitted model: --simulate is not supported with it\n"); return 1; }
         if (do_events) { std::fprintf(stderr, "cafexp_hip: --expected-events belongs to a fitted model: --simulate is not supported with it\n"); return 1; }
         if (do_rate_shift) { std::fprintf(stderr, "cafexp_hip: --rate-shift-scan belongs to a fitted model: --simulate is not supported with it\n"); return 1; }
+        if (do_leaf_predictive) { std::fprintf(stderr, "cafexp_hip: --leaf-predictive belongs to a fitted model: --simulate is not supported with it\n"); return 1; }
         if (have_seed) randomizer_engine.seed(seed);
         return simulate_main(tree_path, fam_path, rootdist_path, lambda_tree_path, multi, err_path, use_err, fixed_lambda, fixed_alpha, k,
                              simulate_n, simulate_on_device, have_seed ? seed : randomizer_engine(), device, sim_workspace, out_dir, mu_list);
@@ -280,6 +289,12 @@ int main(int argc, char** argv) {
         const char* why = nullptr;
         if (gpus_given) why = "--expected-events runs on one GPU: --gpus is not supported with it";
         else if (per_family) why = "--expected-events needs one fitted model: -b is not supported with it";
+        if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
+    }
+    if (do_leaf_predictive) {
+        const char* why = nullptr;
+        if (gpus_given) why = "--leaf-predictive runs on one GPU: --gpus is not supported with it";
+        else if (per_family) why = "--leaf-predictive needs one fitted model: -b is not supported with it";
         if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
     }
     if (do_histories) {
@@ -539,6 +554,17 @@ int main(int argc, char** argv) {
             events_failed = er.failed_count();
             if (!out_dir.empty()) write_events_reports(er, mdl->name(), out_dir, order, d.gene_families);
         }
+        // the leave-one-out predictive check of every leaf count under the same model: which cells of the table are surprising
+        double predictive_s = 0;
+        leaf_predictive_summary predictive;
+        if (do_leaf_predictive) {
+            auto t0 = std::chrono::steady_clock::now();
+            const leaf_predictive_result lp = mdl->leaf_predictive(d.p_prior.get(), d.rootdist);
+            const std::string dir = out_dir.empty() ? "results" : out_dir;
+            if (::mkdir(dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("Failed to create directory " + dir);
+            predictive = write_leaf_predictive_reports(lp, test_pvalue, mdl->name(), dir, d.gene_families);
+            predictive_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
         // standard errors of what the search estimated, from the per-family scores of the searched objective at the optimum
         standard_errors se;
         std::vector<double> slopes;
@@ -647,6 +673,11 @@ int main(int argc, char** argv) {
             std::printf(", \"histories\": {\"seconds\": %.3f, \"draws\": %d, \"failed\": %zu}", history_s, history_draws, history_failed);
         if (do_events)
             std::printf(", \"expected_events\": {\"seconds\": %.3f, \"failed\": %zu}", events_s, events_failed);
+        if (do_leaf_predictive) {
+            std::printf(", \"leaf_predictive\": {\"seconds\": %.3f, \"failed_cells\": %zu, \"outliers\": %zu, ", predictive_s, predictive.failed_cells, predictive.outliers);
+            print_num("log_pseudo_likelihood", predictive.log_pseudo_likelihood, false);
+            std::printf("}");
+        }
         if (do_standard_errors) {
             auto list = [](const char* key, const std::vector<double>& v) {
                 std::printf("\"%s\": [", key);

@@ -61,13 +61,10 @@ double quad(const std::vector<double>& G, size_t P, const std::vector<size_t>& x
 
 void holm_adjust(std::vector<score_test*>& tests) {
     std::vector<score_test*> t;
-    for (score_test* x : tests) if (x->testable) t.push_back(x);
-    std::stable_sort(t.begin(), t.end(), [](const score_test* a, const score_test* b) { return a->p < b->p; });
-    double run = 0;
-    for (size_t r = 0; r < t.size(); ++r) {
-        run = std::max(run, std::min(1.0, (double)(t.size() - r) * t[r]->p));
-        t[r]->holm = run;
-    }
+    std::vector<double> p;
+    for (score_test* x : tests) if (x->testable) { t.push_back(x); p.push_back(x->p); }
+    const std::vector<double> adj = holm_adjusted(p);
+    for (size_t i = 0; i < t.size(); ++i) t[i]->holm = adj[i];
 }
 
 }  // namespace

@@ -510,6 +510,36 @@ int cafe_expected_events(cafe_ctx* ctx, const cafe_params* params, const cafe_ev
  * |lambda - mu| t is small), so finite and accurate as mu -> lambda and at mu = lambda.  Pure host code, no device needed. */
 int cafe_bd_rates_events(double lambda, double mu, double t, double out[6]);
 
+/* Leave-one-out predictive check of every leaf count: the distribution of species l's count given the counts of every other
+ * species of the family, under cafe_marginal_reconstruct's model (the call's lambdas, categories, prior and error model, the
+ * context's death rates when set, the root weight of CAFE_ROOT_SUM).  With G_l the down pass's outside message on the parent's
+ * sizes (O_parent times the siblings' factors) and P_l the leaf's matrix,
+ *     O_l[c] = sum_i P_l[i][c] G_l[i], c = 0..M        u = sum_k p_k O_l^k
+ *     w[y] = u[y], or with an error model sum_t err[y][t] u[y - half + t] (taps outside [0, M] dropped)        W = sum_y w[y]
+ * so that w[x] at the observed count x is the family's evidence Z and nothing else in w depends on x.  One fp64 MFMA GEMM per
+ * leaf branch and category forms O_l for all columns; the sums over y follow in a second kernel.  Outputs
+ * (host pointers, any may be NULL), rows in the problem's family order, columns as `counts`:
+ *   mean, sd [n_families][n_taxa]: of w / W over 0..M; they do not depend on x, not even in the last bit;
+ *   p_below, p_obs, p_above: the mass of y < x, y = x and y > x, each summed on its own (a small tail keeps its relative
+ *     accuracy); p_below + p_obs and p_obs + p_above are the two one-sided tail probabilities of the observed count;
+ *   log_evidence, failed [n_families] as cafe_marginal_reconstruct, judged on Z.
+ * A cell whose W is zero or not finite has NaN in all five (the call still returns CAFE_OK); a family that failed because its
+ * observation is impossible may still have finite cells with p_obs = 0.  CAFE_ERR_ARGUMENT for invalid rates or a bad K;
+ * CAFE_ERR_STATE on a context with a communicator attached.  The columns are processed in batches that fit the problem's
+ * workspace_limit (0 = automatic); a value never depends on the batches, identical families get identical rows.
+ * cafe_family_results is not meaningful after this call; a later cafe_score is unaffected; cafe_debug_marginal_gemm reports this
+ * call's GEMM launches. */
+typedef struct cafe_leaf_predictive_out {
+    double*  mean;          /* [n_families][n_taxa], columns as `counts` */
+    double*  sd;
+    double*  p_below;
+    double*  p_obs;
+    double*  p_above;
+    double*  log_evidence;  /* [n_families] */
+    int32_t* failed;        /* [n_families] */
+} cafe_leaf_predictive_out;
+int cafe_leaf_predictive(cafe_ctx* ctx, const cafe_params* params, const cafe_leaf_predictive_out* out);
+
 /* Introspection for parity tests: the transition matrix the last call built for the branch above
  * `node` in category k (N x N row-major, N = max(M,R)+1: matrix_cache::get_matrix; for an interior
  * branch the columns c > M, which the prune never reads, are not materialised and come back 0), and the root
