@@ -73,6 +73,11 @@ class CafeLeafPredictiveOut(C.Structure):
                 ("failed", _i32p)]
 
 
+class CafeRootPosteriorOut(C.Structure):
+    _fields_ = [("total", _f64p), ("n_used", _i64p), ("mean", _f64p), ("mode", _i32p), ("category_posterior", _f64p),
+                ("log_evidence", _f64p), ("failed", _i32p)]
+
+
 class CafeHistoryOut(C.Structure):
     _fields_ = [("sizes", _i32p), ("category", _i32p), ("n_increase", _i64p), ("n_decrease", _i64p), ("net_change", _i64p),
                 ("log_evidence", _f64p), ("failed", _i32p)]
@@ -115,7 +120,7 @@ EXPORTS = [
     "cafe_set_death_rates", "cafe_bd_rates", "cafe_build_matrices_lm", "cafe_score_per_family_lm", "cafe_simulate_lm",
     "cafe_score_gradient", "cafe_bd_rates_grad", "cafe_expected_events", "cafe_bd_rates_events",
     "cafe_branch_scores", "cafe_branch_scores_dim", "cafe_weighted_gram", "cafe_debug_gram",
-    "cafe_leaf_predictive",
+    "cafe_leaf_predictive", "cafe_set_root_rule", "cafe_get_root_rule", "cafe_root_posterior",
 ]
 CAFE_COMM_ID_BYTES = 128
 
@@ -201,6 +206,12 @@ def load():
     L.cafe_bd_rates_events.argtypes = [C.c_double, C.c_double, C.c_double, _f64p]
     L.cafe_leaf_predictive.restype = C.c_int
     L.cafe_leaf_predictive.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.POINTER(CafeLeafPredictiveOut)]
+    L.cafe_set_root_rule.restype = C.c_int
+    L.cafe_set_root_rule.argtypes = [C.c_void_p, C.c_int32]
+    L.cafe_get_root_rule.restype = C.c_int
+    L.cafe_get_root_rule.argtypes = [C.c_void_p]
+    L.cafe_root_posterior.restype = C.c_int
+    L.cafe_root_posterior.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.POINTER(CafeRootPosteriorOut)]
     L.cafe_branch_scores.restype = C.c_int
     L.cafe_branch_scores.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.POINTER(CafeBranchScoresOut)]
     L.cafe_branch_scores_dim.restype = C.c_int
@@ -768,6 +779,36 @@ class Context:
         self._check(self._lib.cafe_set_death_rates(self._h, _p(mu, _f64p)))
         self._death_rates = True
 
+    def set_root_rule(self, rule):
+        """cafe_set_root_rule: "max" (the default, the reference's max_s(L_s prior_s)) or "sum" (the marginal likelihood
+        sum_s L_s prior_s) -- what score(), score_partial(), family_results() and score_per_family[_lm]() make of a family's
+        root vector from now on."""
+        self._check(self._lib.cafe_set_root_rule(self._h, int({"max": CAFE_ROOT_MAX, "sum": CAFE_ROOT_SUM}.get(rule, rule))))
+
+    def root_rule(self) -> str:
+        return "sum" if self._lib.cafe_get_root_rule(self._h) == CAFE_ROOT_SUM else "max"
+
+    def root_posterior(self, pr: Params, alpha: float = 1.0) -> dict:
+        """cafe_root_posterior: the posterior of every family's root size under the sum rule, on the scorer's own prune.
+        Returns total [R] (the sum over the families that did not fail of P(root size = j + 1 | data)), n_used (int), mean,
+        mode, log_evidence and failed [n_families] and, with the gamma model, category_posterior [n_families][K].
+        total / n_used is the EM update of the root distribution."""
+        cp, keep = self._params(pr, alpha)
+        F = self.n_families
+        res = {"total": np.empty(self.R), "mean": np.empty(F), "mode": np.empty(F, dtype=np.int32), "log_evidence": np.empty(F),
+               "failed": np.empty(F, dtype=np.int32)}
+        if pr.multipliers is not None:
+            res["category_posterior"] = np.empty((F, len(pr.multipliers)))
+        n_used = np.zeros(1, dtype=np.int64)
+        ro = CafeRootPosteriorOut()
+        for name, t in CafeRootPosteriorOut._fields_:
+            if name in res:
+                setattr(ro, name, _p(res[name], t))
+        ro.n_used = _p(n_used, _i64p)
+        self._check(self._lib.cafe_root_posterior(self._h, C.byref(cp), C.byref(ro)))
+        res["n_used"] = int(n_used[0])
+        return res
+
     def set_graphs(self, on: bool):
         """False: enqueue every call launch by launch instead of replaying its captured hipGraph."""
         self._check(self._lib.cafe_set_graphs(self._h, 1 if on else 0))
@@ -835,6 +876,11 @@ class Sharded:
             fo.family_likelihood = _p(res["family_likelihood"], _f64p)
         self._check(self._lib.cafe_sharded_family_results(self._h, C.byref(fo)))
         return res
+
+    def set_root_rule(self, rule):
+        """Context.set_root_rule on every shard (the C ABI has no sharded entry: the rule is a property of each shard's context)."""
+        for r in range(self.size):
+            self.shard(r).set_root_rule(rule)
 
     def shard(self, r: int) -> Context:
         h = self._lib.cafe_sharded_context(self._h, r)

@@ -1,6 +1,7 @@
 // Internal: the context behind the C ABI handle and what the translation units of the library share.  cafe_create.hip builds
 // it, cafe_score.hip is the scorer's call path, cafe_debug.hip reads it back; reconstruct.hip, marginal.hip, gradient.hip, history.hip,
-// pvalues.hip and family_lambda.hip are the calls beside the scorer (their common frame: cafe_call.h), cafe_sharded.hip the multi-GPU layer.
+// pvalues.hip and family_lambda.hip are the calls beside the scorer (their common frame: cafe_call.h), root_posterior.hip the one that
+// runs the scorer's own path with other kernels behind the root panel, cafe_sharded.hip the multi-GPU layer.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -80,6 +81,8 @@ struct DescSet {
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline int64_t round_up64(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
+struct RootPosteriorArgs;                    // root_sum.h
+
 }  // namespace cafe
 
 struct cafe_ctx {
@@ -150,6 +153,11 @@ struct cafe_ctx {
     std::vector<double> mus;                 // [n_lambdas] death rate per lambda index; empty: lambda = mu
     cafe::SlotParamLM* d_slots_lm = nullptr;
     cafe::SlotParamLM* h_slots_lm = nullptr;
+    // cafe_set_root_rule: what K4 (and the per-family root kernel) make of a root vector, CAFE_ROOT_MAX or CAFE_ROOT_SUM
+    int root_rule = CAFE_ROOT_MAX;
+    // cafe_root_posterior (root_posterior.hip) sets this for the one enqueue it makes: the call's two kernels then stand where
+    // K4 and the final sum do, on the stream path (no graph), and the gamma model's host rejection is not applied
+    const cafe::RootPosteriorArgs* root_posterior = nullptr;
     double* d_panels = nullptr;
     int64_t panel_stride = 0;               // doubles per panel
     int64_t panel_kstride = 0;              // doubles per category inside a panel
@@ -342,6 +350,8 @@ int score_per_family_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const i
 // ... each under its own (lambdas, mus): the same frame with the kernel's two-rate instantiation (family_lambda_lm.hip)
 int score_per_family_lm_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_t* family, const double* lambdas, const double* mus,
                              double* family_lnl);
+// the root posterior of every family on the scorer's own prune (root_posterior.hip)
+int root_posterior_impl(cafe_ctx* c, const cafe_params* pr, const cafe_root_posterior_out* out);
 // multi-GPU (cafe_sharded.hip)
 int comm_allreduce_pair(cafe_ctx* c, double* d_pair, hipStream_t s);
 void comm_release(cafe_ctx* c);

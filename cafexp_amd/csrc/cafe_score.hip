@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "cafe_call.h"
+#include "root_sum.h"
 
 using namespace cafe;
 
@@ -284,7 +285,7 @@ int prepare_descriptors(cafe_ctx* c, DescSet& ds, int K, int64_t cols, const std
 // The device work of one call, enqueued on `s` (or recorded into a graph being captured on `s`): parameter upload,
 // K1, the schedule (K2 / K3 launches), K4, the final sum into d_out.  Everything that changes between calls of the
 // same shape travels through the parameter block; kernel arguments depend only on (reduction, K, error model).
-int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool use_err, double* d_out, hipStream_t s, bool events, bool capturing) {
+int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool rootsum, bool use_err, double* d_out, hipStream_t s, bool events, bool capturing) {
     c->stats.gemm_flops = c->stats.gemm_bytes = c->stats.gemm_flops_per_family = c->stats.gemm_flops_dense = 0;
     c->stats.gemm_launches = 0;
     c->desc_last = &ds;
@@ -408,7 +409,9 @@ int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool 
         r.prior = c->d_prior; r.log_prior = c->d_logprior; r.cat_probs = c->d_catprobs;
         r.f0 = f0; r.nf = std::max<int64_t>(0, std::min<int64_t>(cols, c->F_uniq - f0));
         r.fam_out = c->d_fam_out; r.fam_lik = c->d_fam_lik; r.cat_out = c->d_cat_out; r.failed = c->d_failed;
-        HIP_TRY(c, launch_root_reduce(r, s));
+        if (c->root_posterior) HIP_TRY(c, launch_root_posterior(r, *c->root_posterior, s));     // cafe_root_posterior's two kernels
+        else if (rootsum) HIP_TRY(c, launch_root_reduce_sum(r, s));
+        else HIP_TRY(c, launch_root_reduce(r, s));
         c->last_chunk_f0 = f0;
         c->last_chunk_nf = r.nf;
         // (several chunks with extents: the lists depend on this chunk's panel extents -- none: extents need one chunk -- and
@@ -417,7 +420,8 @@ int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool 
     c->plan_launches_last = c->n_gemm_groups;
     // (the pair also goes straight into pinned host memory: cafe_score without a communicator reads it there after the
     // stream has drained, no device-to-host copy)
-    HIP_TRY(c, launch_final_sum(c->d_fam_out, c->d_weights, c->d_failed, c->F_uniq, c->d_scratch, c->n_scratch, d_out, c->h_result, s));
+    if (!c->root_posterior)
+        HIP_TRY(c, launch_final_sum(c->d_fam_out, c->d_weights, c->d_failed, c->F_uniq, c->d_scratch, c->n_scratch, d_out, c->h_result, s));
     if (events) { HIP_TRY(c, hipEventRecord(c->ev[3], s)); c->events_valid = true; }
     return CAFE_OK;
 }
@@ -430,6 +434,7 @@ int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bo
     if (!pr || !pr->lambdas || (!rootmax && !pr->prior)) { set_err(c, "cafe_score: lambdas and prior are required"); return CAFE_ERR_ARGUMENT; }
     const bool gamma = !rootmax && pr->model == CAFE_MODEL_GAMMA;
     const bool use_err = !rootmax && c->n_dev > 0;
+    const bool rootsum = !rootmax && c->root_rule == CAFE_ROOT_SUM;
     const int K = gamma ? pr->n_categories : 1;
     if (gamma && (K < 1 || K > c->Kmax || !pr->multipliers || !pr->cat_probs)) {
         set_err(c, "cafe_score: gamma model needs 1..%d categories with multipliers and cat_probs", c->Kmax);
@@ -448,7 +453,7 @@ int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bo
     c->model_last = rootmax ? CAFE_MODEL_BASE : pr->model;
     c->rootmax_last = rootmax;
 
-    c->last_rejected = rootmax ? !rates_valid(c, pr->lambdas) : rejected(c, pr, K);
+    c->last_rejected = rootmax || c->root_posterior ? !rates_valid(c, pr->lambdas) : rejected(c, pr, K);
     if (c->last_rejected) {
         double* hr = reinterpret_cast<double*>(c->h_stage);
         hr[0] = 0.0; hr[1] = 1.0;
@@ -476,13 +481,14 @@ int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bo
         if (use_err) std::memcpy(c->h_stage + ((char*)c->d_err - c->d_params), pr->error_model, sizeof(double) * (size_t)(c->M + 1) * c->n_dev);
     }
 
-    const bool graph_ok = c->use_graph && !c->profile && !c->d_stamps && c->force_mi == 0;
+    const bool graph_ok = c->use_graph && !c->profile && !c->d_stamps && c->force_mi == 0 && !c->root_posterior;
     if (!graph_ok) {
-        const int rc = record_call(c, c->desc, K, gamma, rootmax, use_err, d_out, s, c->profile != 0, false);
+        const int rc = record_call(c, c->desc, K, gamma, rootmax, rootsum, use_err, d_out, s, c->profile != 0, false);
         if (rc != CAFE_OK) return rc;
     } else {
-        // (a graph holds the K1 kernels of the mode it was captured in: one per mode)
-        const int key = (rootmax ? 2 : (gamma ? 1 : 0)) + 4 * K + (c->mus.empty() ? 0 : 4 * (kMaxCategories + 1));
+        // (a graph holds the K1 kernels of the mode and the K4 of the root rule it was captured in: one per mode and rule)
+        const int key = (rootmax ? 2 : (gamma ? 1 : 0)) + 4 * K + (c->mus.empty() ? 0 : 4 * (kMaxCategories + 1)) +
+                        (rootsum ? 8 * (kMaxCategories + 1) : 0);
         cafe_ctx::CallGraph& cg = c->graphs[key];
         auto drop = [&]() { hipFree(cg.desc.d_gemm_ops); hipFree(cg.desc.d_plan_desc); hipFree(cg.desc.d_plan); c->graphs.erase(key); };
         if (!cg.exec) {
@@ -499,7 +505,7 @@ int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bo
             }
             hipGraph_t graph = nullptr;
             HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            const int rc = record_call(c, cg.desc, K, gamma, rootmax, use_err, c->d_result, c->stream, false, true);
+            const int rc = record_call(c, cg.desc, K, gamma, rootmax, rootsum, use_err, c->d_result, c->stream, false, true);
             const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
             if (rc != CAFE_OK) { if (graph) (void)hipGraphDestroy(graph); drop(); return rc; }
             if (ee != hipSuccess || !graph) { drop(); set_err(c, "hipStreamEndCapture failed: %s", hipGetErrorString(ee)); return CAFE_ERR_DEVICE; }
@@ -674,6 +680,15 @@ int cafe_set_profiling(cafe_ctx* ctx, int on) {
 int cafe_set_death_rates(cafe_ctx* ctx, const double* mus) {
     return guarded(ctx, "cafe_set_death_rates", [&] { return set_death_rates_impl(ctx, mus); });
 }
+
+int cafe_set_root_rule(cafe_ctx* ctx, int32_t rule) {
+    if (!ctx) return CAFE_ERR_ARGUMENT;
+    if (rule != CAFE_ROOT_MAX && rule != CAFE_ROOT_SUM) { set_err(ctx, "cafe_set_root_rule: rule must be CAFE_ROOT_MAX or CAFE_ROOT_SUM"); return CAFE_ERR_ARGUMENT; }
+    ctx->root_rule = rule;
+    return CAFE_OK;
+}
+
+int cafe_get_root_rule(const cafe_ctx* ctx) { return ctx ? ctx->root_rule : CAFE_ROOT_MAX; }
 
 int cafe_bd_rates(double lambda, double mu, double t, double out[3]) {
     if (!out) return CAFE_ERR_ARGUMENT;

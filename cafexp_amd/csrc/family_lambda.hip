@@ -70,6 +70,39 @@ __global__ __launch_bounds__(64) void family_root_kernel(const FamRootArgs a) {
     if (lane == 0) a.out[b] = best;
 }
 
+// ... and under CAFE_ROOT_SUM (cafe_set_root_rule) lnL_f = log sum_j L_j prior_j as K4's sum rule evaluates it: m = max_j t_j,
+// t_j = log L_j + log prior_j, then m + log sum_j exp(t_j - m) -- a lane adds its rows j = lane, lane + 64, ... in ascending
+// order, the lanes are folded by a fixed tree.  All t_j = -inf: -inf; a NaN term: NaN.  A kernel of its own: the max rule's
+// code stays what it was.
+__global__ __launch_bounds__(64) void family_root_sum_kernel(const FamRootArgs a) {
+    const int lane = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const double* __restrict__ fac_b = a.factors + b * a.n_nodes * a.ld;
+    const double ninf = -__builtin_huge_val();
+    double m = ninf;
+    for (int j = lane; j < a.R; j += 64) {
+        double L = 1.0;
+        for (int k = 0; k < a.n_root_children; ++k) L *= fac_b[(int64_t)a.root_children[k] * a.ld + j + 1];
+        const double t = log(L) + a.log_prior[j];
+        if (t > m) m = t;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {                // (butterfly: every lane ends with the maximum)
+        const double o = __shfl_xor(m, d);
+        if (o > m) m = o;
+    }
+    double s = 0.0;
+    for (int j = lane; j < a.R; j += 64) {
+        double L = 1.0;
+        for (int k = 0; k < a.n_root_children; ++k) L *= fac_b[(int64_t)a.root_children[k] * a.ld + j + 1];
+        const double t = log(L) + a.log_prior[j];
+        s += t == ninf ? 0.0 : exp(t - m);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d);
+    if (lane == 0) a.out[b] = m + log(s);
+}
+
 inline size_t align_up(size_t v) { return (v + 255) / 256 * 256; }
 
 // The branch above node u under one family's lambdas
@@ -230,7 +263,8 @@ int per_family_frame(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_
             a.nodes = d_tables + o_level + level_off[lv];
             HIP_TRY(c, launch_family_lambda(a, c->N, nb, level_off[lv + 1] - level_off[lv], s));
         }
-        CAFE_LAUNCH(c, family_root_kernel, dim3((unsigned)nb), dim3(64), 0, s, ra);
+        if (c->root_rule == CAFE_ROOT_SUM) CAFE_LAUNCH(c, family_root_sum_kernel, dim3((unsigned)nb), dim3(64), 0, s, ra);
+        else CAFE_LAUNCH(c, family_root_kernel, dim3((unsigned)nb), dim3(64), 0, s, ra);
         HIP_TRY(c, hipMemcpyAsync(res.data(), base + o_out, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));            // the host tables of this batch go out of use
         for (int64_t b = 0; b < nb; ++b) family_lnl[active[b0 + b]] = res[b];

@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "cafe_kernels.h"
+#include "root_sum.h"
 
 namespace cafe {
 
@@ -487,6 +488,48 @@ hipError_t launch_root_reduce(const ReduceArgs& a, hipStream_t stream) {
     dim3 grid((unsigned)((a.nf + kRedFam - 1) / kRedFam)), block(256);
     (void)hipGetLastError();
     hipLaunchKernelGGL(root_reduce_kernel, grid, block, 0, stream, a);
+    return hipGetLastError();
+}
+
+// K4 under CAFE_ROOT_SUM (cafe_set_root_rule): the same shape and traffic, a sum where root_reduce_kernel takes a maximum --
+// a kernel of its own, so that the max rule's code is what it was.  Base model: log sum_j L_j prior_j as a log-sum-exp;
+// gamma model: p_k sum_j L_j prior_j per category in the linear domain (root_sum.h); `failed` as under the max rule.
+__global__ __launch_bounds__(256) void root_reduce_sum_kernel(const ReduceArgs a) {
+    __shared__ double sh[kSumFam * kSumSeg];
+    const int fam = threadIdx.x % kSumFam, seg = threadIdx.x / kSumFam;
+    const int64_t fl = (int64_t)blockIdx.x * kSumFam + fam;
+    const bool live = fl < a.nf;                            // (every thread reaches the barriers)
+    const int64_t f = a.f0 + fl;
+    if (a.model == 0) {
+        const double v = column_log_sum(a.root + fl, a.ld, a.R, a.log_prior, live, sh, fam, seg);
+        if (live && seg == 0) { a.fam_out[f] = v; a.failed[f] = 0; }
+        return;
+    }
+    double lik = 0.0;
+    int fail = 0;
+    for (int k = 0; k < a.K; ++k) {
+        double plain;
+        const double s = column_sum(a.root + (int64_t)k * a.panel_kstride + fl, a.ld, a.R, a.prior, live, sh, fam, seg, &plain);
+        if (live && seg == 0) {
+            if (plain == 0.0) fail = 1;                    // "saturation", gamma_core.cpp:152
+            const double cl = s * a.cat_probs[k];
+            a.cat_out[f * a.K + k] = cl;
+            lik += cl;
+        }
+    }
+    if (live && seg == 0) {
+        a.fam_lik[f] = lik;
+        a.fam_out[f] = log(lik);
+        a.failed[f] = fail;
+    }
+}
+
+hipError_t launch_root_reduce_sum(const ReduceArgs& a, hipStream_t stream) {
+    if (a.nf <= 0) return hipSuccess;
+    if (a.model != 0 && a.model != 1) return hipErrorInvalidValue;
+    dim3 grid((unsigned)((a.nf + kSumFam - 1) / kSumFam)), block(256);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(root_reduce_sum_kernel, grid, block, 0, stream, a);
     return hipGetLastError();
 }
 

@@ -197,6 +197,22 @@ public:
     void initialize(const root_distribution* rd) override;
     float compute(size_t val) const override { return val >= _pdf.size() ? 0 : (float)_pdf[val]; }
 };
+// A root distribution given as probabilities, one per root size 1, 2, ..: what --estimate-rootdist writes and --rootdist-probs
+// reads back (rootdist_arg / -f hold COUNTS, which uniform_distribution normalises in float arithmetic).  compute(j) is the
+// probability of size j + 1 rounded to the float the ABI takes; sizes past the table have probability 0.
+class file_probability_distribution : public root_equilibrium_distribution {
+    std::vector<double> _p;
+public:
+    file_probability_distribution() {}
+    explicit file_probability_distribution(const std::vector<double>& probabilities) : _p(probabilities) {}
+    void set(const std::vector<double>& probabilities) { _p = probabilities; }
+    const std::vector<double>& probabilities() const { return _p; }
+    void initialize(const root_distribution*) override {}
+    float compute(size_t val) const override { return val >= _p.size() ? 0 : (float)_p[val]; }
+};
+// "size<TAB>probability" lines, sizes 1, 2, .. in order without gaps ('#' lines skipped); throws on anything else
+std::vector<double> read_rootdist_probabilities(std::istream& in);
+void write_rootdist_probabilities(std::ostream& ost, const std::vector<double>& probabilities);     // 17 significant digits
 
 // ---------------------------------------------------------------- discrete gamma (src/gamma.cpp, PAML)
 double point_normal(double prob);
@@ -234,7 +250,12 @@ protected:
     event_monitor _monitor;
     // Separate birth and death rates: one mu per lambda (index order); empty = the reference's model, lambda = mu
     std::vector<double> _death_rates;
+    // What a scorer call makes of a family's root vector (cafe_set_root_rule): 0 = CAFE_ROOT_MAX, the reference's
+    // max_s(L_s prior_s); 1 = CAFE_ROOT_SUM, the marginal likelihood sum_s L_s prior_s.  Held like the death rates.
+    int _root_rule = 0;
 public:
+    void set_root_rule(int rule) { _root_rule = rule; }
+    int root_rule() const { return _root_rule; }
     void set_death_rates(const std::vector<double>& mus) { _death_rates = mus; }
     const std::vector<double>& death_rates() const { return _death_rates; }
     std::string death_rates_to_string() const;                       // formatted like lambda::to_string
@@ -274,6 +295,15 @@ struct marginal_result {
 // header row, family order and node naming of <Model>_count.tab
 void write_marginal_reports(const marginal_result& res, const std::string& model_identifier, const std::string& dir,
                             const std::vector<const clade*>& order, const std::vector<gene_family>& families);
+
+// cafe_root_posterior's outputs: total[j] = sum over the families that did not fail of P(root size = j + 1 | data) (n_used of
+// them; total / n_used is the EM update of the root distribution), category_posterior [family][K] under the gamma model
+struct root_posterior_result {
+    std::vector<double> total, mean, log_evidence, category_posterior;
+    std::vector<int32_t> mode, failed;
+    int64_t n_used = 0;
+    size_t n_categories = 0;                                         // 0: base model
+};
 
 // cafe_expected_events' outputs, [family][index in the caller's node order] (NaN at the root and for a failed family; failed: [family])
 struct events_result {
@@ -472,6 +502,9 @@ public:
     // Expected number of births and of deaths on the branch above every node given the leaf counts, under the same model
     // (cafe_expected_events); columns in `order`
     events_result expected_events(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<const clade*>& order);
+    // The posterior of every family's root size under the sum rule on the scorer's own prune, and its sum over the table
+    // (cafe_root_posterior), at the model's current parameters
+    root_posterior_result root_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist);
     // The leave-one-out predictive distribution of every leaf count under the same model (cafe_leaf_predictive): species in
     // the order of the table's columns on the device (the leaves of the post-order)
     leaf_predictive_result leaf_predictive(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist);
@@ -816,6 +849,7 @@ public:
     double tolx = 1e-6, tolf = 1e-6;            // OPTIMIZER_HIGH_PRECISION
     int similarity_window = 12;                 // OPTIMIZER_SIMILARITY_CUTOFF_SIZE, 0 = off
     double similarity_precision = 1e-3;         // OPTIMIZER_LOW_PRECISION
+    std::vector<double> start;                  // not empty: the search starts here (no draws), e.g. from an earlier optimum
     std::vector<double> get_initial_guesses(int& calls);          // <= 100 retries while +inf (optimizer.cpp:345)
     optimizer_result optimize();
 };

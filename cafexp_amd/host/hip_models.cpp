@@ -80,16 +80,18 @@ static std::vector<int32_t> flatten_counts(const clade* tree, const std::vector<
     return counts;
 }
 
-// the model's death rates on a context (none: lambda = mu)
-static void apply_death_rates(cafe_ctx* ctx, const std::vector<double>& mus, int n_lambdas) {
+// the model's death rates (none: lambda = mu) and its root rule on a context
+static void apply_death_rates(cafe_ctx* ctx, const std::vector<double>& mus, int n_lambdas, int root_rule) {
     if (!mus.empty() && (int)mus.size() != n_lambdas) throw std::runtime_error("hip model: one death rate per lambda is required");
     if (cafe_set_death_rates(ctx, mus.empty() ? nullptr : mus.data()) != CAFE_OK)
         throw std::runtime_error(std::string("cafe_set_death_rates: ") + cafe_last_error(ctx));
+    if (cafe_set_root_rule(ctx, root_rule) != CAFE_OK)
+        throw std::runtime_error(std::string("cafe_set_root_rule: ") + cafe_last_error(ctx));
 }
 
 void hip_model_base::ensure_context(int max_categories) {
     const int sig = _p_lambda->count() * 2 + (dynamic_cast<const multiple_lambda*>(_p_lambda) ? 1 : 0);
-    if (_ctx && max_categories <= _ctx_categories && sig == _ctx_lambda_sig) { apply_death_rates(_ctx, _death_rates, _p_lambda->count()); return; }
+    if (_ctx && max_categories <= _ctx_categories && sig == _ctx_lambda_sig) { apply_death_rates(_ctx, _death_rates, _p_lambda->count(), _root_rule); return; }
     _ctx_lambda_sig = sig;
     if (_ctx) { cafe_destroy(_ctx); _ctx = nullptr; }
     if (!_p_tree || !_p_gene_families || _p_gene_families->empty())
@@ -98,7 +100,7 @@ void hip_model_base::ensure_context(int max_categories) {
     _ctx = create_device_context(_p_lambda, _order, counts.data(), (int64_t)_p_gene_families->size(), _max_family_size, _max_root_family_size,
                                  max_categories, _p_error_model ? (int)_p_error_model->n_deviations() : 0, _device, _workspace_limit);
     _ctx_categories = max_categories;
-    apply_death_rates(_ctx, _death_rates, _p_lambda->count());
+    apply_death_rates(_ctx, _death_rates, _p_lambda->count(), _root_rule);
 }
 
 void hip_model_base::ensure_scorer(int max_categories) {
@@ -107,7 +109,7 @@ void hip_model_base::ensure_scorer(int max_categories) {
     if (_devices.size() <= 1 && std::getenv("CAFE_FORCE_SHARDED")) { if (_devices.empty()) _devices.push_back(_device); }
     else if (_devices.size() <= 1) { ensure_context(max_categories); return; }
     const int sig = _p_lambda->count() * 2 + (dynamic_cast<const multiple_lambda*>(_p_lambda) ? 1 : 0);
-    auto apply_to_shards = [this] { for (int32_t r = 0; r < cafe_sharded_size(_sharded); ++r) apply_death_rates(cafe_sharded_context(_sharded, r), _death_rates, _p_lambda->count()); };
+    auto apply_to_shards = [this] { for (int32_t r = 0; r < cafe_sharded_size(_sharded); ++r) apply_death_rates(cafe_sharded_context(_sharded, r), _death_rates, _p_lambda->count(), _root_rule); };
     if (_sharded && max_categories <= _sharded_categories && sig == _sharded_lambda_sig) { apply_to_shards(); return; }
     _sharded_lambda_sig = sig;
     if (_sharded) { cafe_sharded_destroy(_sharded); _sharded = nullptr; }
@@ -200,6 +202,34 @@ std::vector<double> hip_base_model::per_family_scores(root_equilibrium_distribut
         throw std::runtime_error(std::string("cafe_score_per_family: ") + cafe_last_error(_ctx));
     for (double& v : out) v = std::isnan(v) ? std::numeric_limits<double>::infinity() : -v;      // optimizer_scorer.cpp:30
     return out;
+}
+
+root_posterior_result hip_model_base::root_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist) {
+    std::vector<double> mult, probs;
+    double alpha = 0;
+    category_parameters(mult, probs, alpha);
+    const int K = mult.empty() ? 1 : (int)mult.size();
+    ensure_context(K);
+    std::vector<float> prior_f;
+    std::vector<double> err, lambdas;
+    gather_call_inputs(prior, rootdist, prior_f, err, lambdas);
+    cafe_params pr{};
+    pr.model = mult.empty() ? CAFE_MODEL_BASE : CAFE_MODEL_GAMMA;
+    pr.lambdas = lambdas.data(); pr.n_categories = K;
+    pr.multipliers = mult.empty() ? nullptr : mult.data();
+    pr.cat_probs = probs.empty() ? nullptr : probs.data();
+    pr.alpha = alpha; pr.prior = prior_f.data(); pr.error_model = err.empty() ? nullptr : err.data();
+    const size_t F = _p_gene_families->size();
+    root_posterior_result res;
+    res.n_categories = mult.empty() ? 0 : (size_t)K;
+    res.total.resize((size_t)_max_root_family_size); res.mean.resize(F); res.log_evidence.resize(F); res.mode.resize(F); res.failed.resize(F);
+    cafe_root_posterior_out out{};
+    out.total = res.total.data(); out.n_used = &res.n_used; out.mean = res.mean.data(); out.mode = res.mode.data();
+    out.log_evidence = res.log_evidence.data(); out.failed = res.failed.data();
+    if (!mult.empty()) { res.category_posterior.resize(F * K); out.category_posterior = res.category_posterior.data(); }
+    if (cafe_root_posterior(_ctx, &pr, &out) != CAFE_OK)
+        throw std::runtime_error(std::string("cafe_root_posterior: ") + cafe_last_error(_ctx));
+    return res;
 }
 
 void hip_base_model::write_family_likelihoods(std::ostream& ost) {

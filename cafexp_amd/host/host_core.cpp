@@ -340,6 +340,27 @@ void poisson_distribution::initialize(const root_distribution* rd) {
         _pdf[i] = std::exp((double)i * std::log(_lambda) - std::lgamma((double)i + 1) - _lambda);
 }
 
+std::vector<double> read_rootdist_probabilities(std::istream& in) {
+    std::vector<double> p;
+    std::string line;
+    while (std::getline(in, line)) {
+        if (line.empty() || line[0] == '#') continue;
+        std::istringstream ls(line);
+        long size = 0;
+        double prob = 0;
+        if (!(ls >> size >> prob) || size != (long)p.size() + 1 || !(prob >= 0) || !(prob <= 1))
+            throw std::runtime_error("Root distribution probabilities: expected \"size<TAB>probability\" with sizes 1, 2, .. in order, got '" + line + "'");
+        p.push_back(prob);
+    }
+    if (p.empty()) throw std::runtime_error("Root distribution probabilities: no entries");
+    return p;
+}
+
+void write_rootdist_probabilities(std::ostream& ost, const std::vector<double>& probabilities) {
+    ost << std::setprecision(17);
+    for (size_t j = 0; j < probabilities.size(); ++j) ost << j + 1 << '\t' << probabilities[j] << '\n';
+}
+
 // ------------------------------------------------------------------------------------------ models: shared bits
 std::ostream& operator<<(std::ostream& o, const family_info_stash& r) {
     o << r.family_id << "\t" << r.lambda_multiplier << "\t" << r.category_likelihood << "\t" << r.family_likelihood << "\t"
@@ -362,6 +383,7 @@ void event_monitor::summarize(std::ostream& ost) const {
 
 void model::write_vital_statistics(std::ostream& ost, double final_likelihood) {
     ost << "Model " << name() << " Final Likelihood (-lnL): " << final_likelihood << std::endl;
+    if (_root_rule != 0) ost << "Root rule: sum (-lnL is minus the log of the marginal likelihood, summed over the root size)" << std::endl;
     ost << "Lambda: " << _p_lambda->to_string() << std::endl;
     if (!_death_rates.empty()) ost << "Mu: " << death_rates_to_string() << std::endl;
     if (_p_error_model) ost << "Epsilon: " << _p_error_model->get_epsilons()[0] << std::endl;

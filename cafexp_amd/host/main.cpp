@@ -49,6 +49,17 @@ static void usage() {
         "                  <Model>_leaf_outliers.tab (the cells whose two-sided p, Holm-adjusted over the table, is <= PVALUE, default 0.05) and\n"
         "                  <Model>_species_fit.tab (per species: mean standardised residual, outliers low / high, sum log p_obs); one GPU, not\n"
         "                  with -b or --simulate\n"
+        "                  [--root-sum]   every search and every scorer call under the marginal likelihood sum_s L_s prior_s of a family instead\n"
+        "                  of the reference's max_s (cafe_set_root_rule): the objective the posterior reports condition on.  <Model>_results.txt\n"
+        "                  names the rule; --standard-errors and --rate-shift-scan then differentiate the sum; the gamma model also writes\n"
+        "                  Gamma_category_posterior.tab (per family the posterior probability of every rate category) in -o OUTDIR (default results)\n"
+        "                  [--estimate-rootdist [ROUNDS]]   implies --root-sum: the root size distribution estimated by EM, at most ROUNDS\n"
+        "                  (default 10) rounds behind the usual search under the starting prior (uniform, -p or -f).  A round sets\n"
+        "                  prior[s] = mean over the families of P(root = s | data) at the current optimum, rounded to float, and searches again\n"
+        "                  from that optimum; it stops when a round lowers -lnL by less than 1e-3 relative.  No smoothing: a size that no family\n"
+        "                  supports keeps probability 0.  Writes <Model>_root_distribution.txt (size<TAB>probability) and one line per round in\n"
+        "                  <Model>_results.txt to -o OUTDIR (default results); one GPU, not with -b\n"
+        "                  [--rootdist-probs FILE]   the root prior from such a file of probabilities (instead of -p / -f)\n"
         "  --gpus N: the scorer calls shard the families over devices 0..N-1 (one host thread per GPU, one RCCL all-reduce per call)\n"
         "lambda per family (the reference's -b): cafexp_hip -t TREE -i FAMILIES -b [-y LAMBDA_TREE] [-e ERRMODEL] [-p [L]] [-z] [-s SEED] [-I MAXITER]\n"
         "                  [--workspace BYTES] [-o OUTDIR]   writes OUTDIR (default results)/Base_lambda_per_family.txt, one line per family\n"
@@ -190,6 +201,10 @@ int main(int argc, char** argv) {
     bool do_events = false;                                      // --expected-events
     bool do_rate_shift = false;                                  // --rate-shift-scan
     bool do_leaf_predictive = false;                             // --leaf-predictive
+    bool root_sum = false;                                       // --root-sum: score under CAFE_ROOT_SUM
+    bool estimate_rootdist = false;                              // --estimate-rootdist [ROUNDS]
+    int rootdist_rounds = 10;
+    std::string rootdist_probs;                                  // --rootdist-probs FILE
     unsigned seed = 0;
     bool have_seed = false;
     for (int i = 1; i < argc; ++i) {
@@ -211,6 +226,9 @@ int main(int argc, char** argv) {
         else if (a == "--expected-events") do_events = true;
         else if (a == "--rate-shift-scan") do_rate_shift = true;
         else if (a == "--leaf-predictive") do_leaf_predictive = true;
+        else if (a == "--root-sum") root_sum = true;
+        else if (a == "--estimate-rootdist") { estimate_rootdist = root_sum = true; std::string v = optional(); if (!v.empty()) rootdist_rounds = std::stoi(v); }
+        else if (a == "--rootdist-probs") rootdist_probs = next();
         else if (a == "-e") { use_err = true; err_path = optional(); }
         else if (a == "-p") { use_poisson = true; std::string v = optional(); poisson = v.empty() ? 0 : std::stod(v); }
         else if (a == "-f") rootdist_path = next();
@@ -297,6 +315,13 @@ int main(int argc, char** argv) {
         else if (per_family) why = "--leaf-predictive needs one fitted model: -b is not supported with it";
         if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
     }
+    if (estimate_rootdist) {
+        const char* why = nullptr;
+        if (gpus_given) why = "--estimate-rootdist runs on one GPU: --gpus is not supported with it";
+        else if (per_family) why = "--estimate-rootdist needs one fitted model: -b is not supported with it";
+        else if (rootdist_rounds < 0) why = "--estimate-rootdist: ROUNDS must not be negative";
+        if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
+    }
     if (do_histories) {
         const char* why = nullptr;
         if (gpus_given) why = "--sample-histories runs on one GPU: --gpus is not supported with it";
@@ -356,7 +381,12 @@ int main(int argc, char** argv) {
             d.gene_families.erase(rem, d.gene_families.end());
         }
         if (limit >= 0 && (size_t)limit < d.gene_families.size()) d.gene_families.resize(limit);
-        if (use_poisson && poisson > 0) d.p_prior.reset(new poisson_distribution(poisson));
+        if (!rootdist_probs.empty()) {
+            std::ifstream f(rootdist_probs);
+            if (!f.is_open()) throw std::runtime_error("Failed to open file '" + rootdist_probs + "'");
+            d.p_prior.reset(new file_probability_distribution(read_rootdist_probabilities(f)));
+        }
+        else if (use_poisson && poisson > 0) d.p_prior.reset(new poisson_distribution(poisson));
         else if (use_poisson) d.p_prior.reset(new poisson_distribution(&d.gene_families));     // fitted to the leaf sizes (root_equilibrium_distribution.cpp:34)
         else d.p_prior.reset(new uniform_distribution());
 
@@ -378,6 +408,18 @@ int main(int argc, char** argv) {
             mdl.reset(new hip_base_model(start_lambda, d.p_tree.get(), &d.gene_families, d.max_family_size, d.max_root_family_size, em));
         }
         mdl->set_device(device);
+        mdl->set_root_rule(root_sum ? CAFE_ROOT_SUM : CAFE_ROOT_MAX);
+        file_probability_distribution* em_prior = nullptr;
+        if (estimate_rootdist) {                                 // the starting prior as the floats a call reads, held where the rounds can replace it
+            root_distribution rd;
+            if (!d.rootdist.empty()) rd.vectorize(d.rootdist);
+            else rd.vectorize_uniform(d.max_root_family_size);
+            d.p_prior->initialize(&rd);
+            std::vector<double> p((size_t)d.max_root_family_size);
+            for (size_t j = 0; j < p.size(); ++j) p[j] = d.p_prior->compute(j);
+            em_prior = new file_probability_distribution(p);
+            d.p_prior.reset(em_prior);
+        }
         if (!mu_list.empty()) {                                  // fixed death rates: one per lambda of the -y tree (one without)
             const std::vector<double> mus = parse_rates(mu_list);
             size_t n_lambdas = 1;
@@ -447,6 +489,45 @@ int main(int argc, char** argv) {
             search_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             scorer->finalize(opt.values.data());
         }
+        // EM rounds on the root distribution: the E step is one cafe_root_posterior call at the optimum, the M step total / n_used
+        struct em_round { double neg_lnl; std::string rates; };
+        std::vector<em_round> em_rounds;
+        if (estimate_rootdist) {
+            auto rates_now = [&] {
+                std::string r = "Lambda: " + mdl->get_lambda()->to_string();
+                if (!mdl->death_rates().empty()) r += " Mu: " + mdl->death_rates_to_string();
+                if (auto gm = dynamic_cast<hip_gamma_model*>(mdl.get())) { std::ostringstream o; o.precision(14); o << " Alpha: " << gm->get_alpha(); r += o.str(); }
+                return r;
+            };
+            double prev = scorer ? opt.score : mdl->infer_family_likelihoods(d.p_prior.get(), d.rootdist, mdl->get_lambda());
+            em_rounds.push_back({prev, rates_now()});
+            for (int round = 1; round <= rootdist_rounds; ++round) {
+                const root_posterior_result rp = mdl->root_posterior(d.p_prior.get(), d.rootdist);
+                if (rp.n_used < 1) throw std::runtime_error("--estimate-rootdist: every family failed (zero likelihood) at the current optimum");
+                std::vector<double> p(rp.total.size());
+                for (size_t j = 0; j < p.size(); ++j) p[j] = (double)(float)(rp.total[j] / (double)rp.n_used);      // the float the ABI takes
+                em_prior->set(p);
+                double cur;
+                if (scorer) {
+                    optimizer o(scorer.get());
+                    o.max_iterations = max_iter;
+                    o.start = opt.values;
+                    auto t0 = std::chrono::steady_clock::now();
+                    optimizer_result again = o.optimize();
+                    search_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+                    scorer->finalize(again.values.data());
+                    opt.values = again.values; opt.score = again.score;
+                    opt.num_iterations += again.num_iterations; opt.num_scorer_calls += again.num_scorer_calls;
+                    cur = again.score;
+                } else {
+                    cur = mdl->infer_family_likelihoods(d.p_prior.get(), d.rootdist, mdl->get_lambda());
+                }
+                em_rounds.push_back({cur, rates_now()});
+                const bool settled = prev - cur < optimizer(nullptr).similarity_precision * std::fabs(prev);
+                prev = cur;
+                if (settled) break;
+            }
+        }
         double score = 0, best = 1e300;
         for (int r = 0; r < reps; ++r) {                         // compute (execute.cpp:42)
             auto t0 = std::chrono::steady_clock::now();
@@ -458,9 +539,16 @@ int main(int argc, char** argv) {
             f.precision(17);
             mdl->write_family_likelihoods(f);
         }
+        if (estimate_rootdist) {                                 // its files, the results file's rounds among them, default to results/
+            if (out_dir.empty()) out_dir = "results";
+            if (::mkdir(out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("Failed to create directory " + out_dir);
+        }
         if (!out_dir.empty()) {                                  // the two files of estimator::compute (execute.cpp:49-54)
             std::ofstream rf(out_dir + "/" + mdl->name() + "_results.txt");
             mdl->write_vital_statistics(rf, score);
+            rf.precision(17);
+            for (size_t r = 0; r < em_rounds.size(); ++r)
+                rf << "Root distribution round " << r << ": -lnL " << em_rounds[r].neg_lnl << " " << em_rounds[r].rates << std::endl;
             std::ofstream lf(out_dir + "/" + mdl->name() + "_family_likelihoods.txt");
             mdl->write_family_likelihoods(lf);
             if (use_err) {                                       // write_error_model_if_specified (execute.cpp:24-40)
@@ -472,6 +560,28 @@ int main(int argc, char** argv) {
                     write_error_model_file(ef, none);
                 }
             }
+        }
+        if (estimate_rootdist) {
+            std::ofstream f(out_dir + "/" + mdl->name() + "_root_distribution.txt");
+            write_rootdist_probabilities(f, em_prior->probabilities());
+            if (!f) throw std::runtime_error("Failed to write " + out_dir + "/" + mdl->name() + "_root_distribution.txt");
+        }
+        // the posterior probability of every rate category per family, under the rule that was searched
+        if (root_sum && dynamic_cast<hip_gamma_model*>(mdl.get())) {
+            const root_posterior_result rp = mdl->root_posterior(d.p_prior.get(), d.rootdist);
+            const std::string dir = out_dir.empty() ? "results" : out_dir;
+            if (::mkdir(dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("Failed to create directory " + dir);
+            std::ofstream f(dir + "/" + mdl->name() + "_category_posterior.tab");
+            f.precision(17);
+            f << "#FamilyID";
+            for (double m : dynamic_cast<hip_gamma_model*>(mdl.get())->get_lambda_multipliers()) f << '\t' << m;
+            f << '\n';
+            for (size_t i = 0; i < d.gene_families.size(); ++i) {
+                f << d.gene_families[i].id();
+                for (size_t c = 0; c < rp.n_categories; ++c) f << '\t' << rp.category_posterior[i * rp.n_categories + c];
+                f << '\n';
+            }
+            if (!f) throw std::runtime_error("Failed to write " + dir + "/" + mdl->name() + "_category_posterior.tab");
         }
         // compute_pvalues with the model's plain lambda (execute.cpp:153-161); 1000 simulations in the reference
         std::vector<double> pvalues;
@@ -573,7 +683,7 @@ int main(int argc, char** argv) {
         const bool lambda_searched = scorer && !d.p_lambda, alpha_searched = scorer && g && !(fixed_alpha > 0);
         if ((do_standard_errors || do_rate_shift) && alpha_searched) slopes = multiplier_slopes(g->get_lambda_multipliers().size(), g->get_alpha());
         if (do_standard_errors) {
-            const gradient_result gr = mdl->score_gradient(d.p_prior.get(), d.rootdist, CAFE_ROOT_MAX);
+            const gradient_result gr = mdl->score_gradient(d.p_prior.get(), d.rootdist, root_sum ? CAFE_ROOT_SUM : CAFE_ROOT_MAX);
             const std::vector<double> lv = mdl->get_lambda()->values();
             const size_t nl = gr.n_lambdas, F = d.gene_families.size();
             std::vector<std::string> names;
@@ -613,7 +723,7 @@ int main(int argc, char** argv) {
             auto t0 = std::chrono::steady_clock::now();
             cladevector order;
             d.p_tree->apply_reverse_level_order([&order](const clade* c) { order.push_back(c); });
-            const branch_scores_result bs = mdl->branch_scores(d.p_prior.get(), d.rootdist, CAFE_ROOT_MAX, order);
+            const branch_scores_result bs = mdl->branch_scores(d.p_prior.get(), d.rootdist, root_sum ? CAFE_ROOT_SUM : CAFE_ROOT_MAX, order);
             std::vector<std::vector<double>> theta;
             std::vector<std::string> names;
             auto rate_name = [&](const char* what, size_t i) { return bs.n_lambdas == 1 ? std::string(what) : what + std::to_string(i + 1); };
@@ -636,6 +746,7 @@ int main(int argc, char** argv) {
         }
         std::printf("{\"model\": \"%s\", ", mdl->name().c_str());
         print_num("neg_lnl", score);
+        if (root_sum) std::printf("\"root_rule\": \"sum\", ");
         std::printf("\"n_families\": %zu, \"max_family_size\": %d, \"max_root_family_size\": %d, \"seconds_per_call\": %.6f, ",
                     d.gene_families.size(), d.max_family_size, d.max_root_family_size, best);
         std::printf("\"lambda\": [");
@@ -659,6 +770,14 @@ int main(int argc, char** argv) {
             std::printf(", \"search\": {\"iterations\": %d, \"scorer_calls\": %d, \"seconds\": %.3f, ", opt.num_iterations, opt.num_scorer_calls, search_s);
             print_num("score", opt.score, false);
             std::printf("}");
+        }
+        if (estimate_rootdist) {
+            std::printf(", \"rootdist\": {\"rounds\": [");
+            for (size_t r = 0; r < em_rounds.size(); ++r) {
+                if (std::isfinite(em_rounds[r].neg_lnl)) std::printf("%s%.17g", r ? ", " : "", em_rounds[r].neg_lnl);
+                else std::printf("%s\"inf\"", r ? ", " : "");
+            }
+            std::printf("], \"max_rounds\": %d}", rootdist_rounds);
         }
         if (pvalue_sims > 0) {
             size_t sig = 0;

@@ -12,6 +12,7 @@
 namespace cafe {
 
 std::vector<double> optimizer::get_initial_guesses(int& calls) {
+    if (!start.empty()) return start;                             // (the search scores it as its first trial)
     std::vector<double> initial = _scorer->initial_guesses();
     double first = _scorer->calculate_score(initial.data());
     ++calls;

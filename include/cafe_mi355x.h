@@ -540,6 +540,57 @@ typedef struct cafe_leaf_predictive_out {
 } cafe_leaf_predictive_out;
 int cafe_leaf_predictive(cafe_ctx* ctx, const cafe_params* params, const cafe_leaf_predictive_out* out);
 
+/* Root rule of a context: what the scorer makes of a family's root vector L_j (j = 0..R-1 for root size j + 1).  A property of
+ * the context, like the death rates: every later scoring call reads it.  CAFE_ROOT_MAX (the default) is the reference's rule,
+ * max_j(L_j prior_j).  Under CAFE_ROOT_SUM a family's value is the marginal likelihood every posterior call conditions on:
+ *   base model   family_lnl = log sum_j L_j prior_j, evaluated as m + log sum_j exp(t_j - m) with t_j = log L_j + log prior_j
+ *                (the host's log of the float prior, as the max rule reads it) and m = max_j t_j: finite where the plain product
+ *                underflows; all t_j = -inf gives -inf (the call's -lnL is then +inf); a NaN term gives NaN;
+ *   gamma model  category_likelihood[f][k] = p_k sum_j L_j prior_j in the linear domain, family_likelihood their sum over k,
+ *                family_lnl its log; failed[f] keeps the reference's rule (a category whose sum_j L_j is exactly 0).
+ * The sum over j runs in a fixed order (16 interleaved row segments, combined in segment order): a value depends on the
+ * family's column and R only, never on column chunks, graphs or the stream.  Honoured by cafe_score, cafe_score_partial /
+ * cafe_finish_partial, cafe_family_results, cafe_score_per_family and cafe_score_per_family_lm; sharded use needs no entry of
+ * its own: call the setter on every cafe_sharded_context(s, r).  It combines with death rates, error models, several lambdas
+ * and several column chunks.  Not affected: cafe_root_max, cafe_pvalues, cafe_reconstruct, cafe_branch_probabilities (the
+ * reference's own statistics) and every posterior call (each takes a root_rule or is defined on the sum).  With CAFE_ROOT_MAX
+ * -- never set, or set back -- every result of every entry is bit for bit what it is without this setter.  Any other value:
+ * CAFE_ERR_ARGUMENT, the rule stays. */
+int cafe_set_root_rule(cafe_ctx* ctx, int32_t rule);
+int cafe_get_root_rule(const cafe_ctx* ctx);      /* CAFE_ROOT_MAX or CAFE_ROOT_SUM; CAFE_ROOT_MAX for a NULL context */
+
+/* Root posterior on the scorer's own prune: P(root size = j + 1 | data_f) for every family, summarised per family and summed
+ * over the table -- the E step of a maximum-likelihood update of the root distribution, prior_new[j] = total[j] / n_used.  The
+ * call runs the scorer's path (K1, the schedule with subtree sharing and zero extents, K2 / K3), not the sum-product engine,
+ * and per column chunk two kernels stand where K4 does: one per column (Z, log Z, mean, mode, category posteriors and the
+ * column's scale w_f / Z_f, w_f its multiplicity), one per root row (the weighted row sum of the panel).  The weights are
+ * always the sum rule's, whatever cafe_set_root_rule says: with the gamma model
+ * P(root = j + 1 | data) = sum_k p_k prior_j L^k_j / Z, Z = sum_k p_k sum_j prior_j L^k_j.  Outputs (host pointers, any may be
+ * NULL), rows in the problem's family order:
+ *   total[R] = sum over the families that did not fail of P(root size = j + 1 | data_f), every family of the table counted
+ *     (identical families as often as they occur); n_used the number of those families, so sum_j total[j] = n_used to rounding.
+ *     Per root row the 128-column tiles are folded in tile order, each tile summed by a fixed tree: total does not depend on
+ *     workspace_limit, not even in the last bit;
+ *   mean[n_families], mode[n_families] (first arg max, as a size 1..R) of the family's root posterior;
+ *   category_posterior[n_families][K] = p_k Z_k / Z, gamma model only (CAFE_ERR_ARGUMENT otherwise);
+ *   log_evidence[n_families] = log Z (base model: the log-sum-exp of cafe_set_root_rule, the bits cafe_score returns per
+ *     family under CAFE_ROOT_SUM; gamma model likewise);
+ *   failed[n_families] = 1 where Z is 0 or not finite: that family's doubles are NaN, its mode -1, and it adds nothing to total
+ *     (the call still returns CAFE_OK).
+ * Reads model, lambdas, n_categories, multipliers, cat_probs, prior and error_model of params; the context's death rates
+ * apply.  CAFE_ERR_ARGUMENT for invalid rates or a bad K; CAFE_ERR_STATE on a context with a communicator attached.
+ * cafe_family_results is not meaningful after this call; a later cafe_score is unaffected. */
+typedef struct cafe_root_posterior_out {
+    double*  total;              /* [R] */
+    int64_t* n_used;             /* families that entered total */
+    double*  mean;               /* [n_families] posterior mean root size */
+    int32_t* mode;               /* [n_families] first arg max, as a size (1..R) */
+    double*  category_posterior; /* [n_families][K]; gamma model only */
+    double*  log_evidence;       /* [n_families] */
+    int32_t* failed;             /* [n_families] */
+} cafe_root_posterior_out;
+int cafe_root_posterior(cafe_ctx* ctx, const cafe_params* params, const cafe_root_posterior_out* out);
+
 /* Introspection for parity tests: the transition matrix the last call built for the branch above
  * `node` in category k (N x N row-major, N = max(M,R)+1: matrix_cache::get_matrix; for an interior
  * branch the columns c > M, which the prune never reads, are not materialised and come back 0), and the root
