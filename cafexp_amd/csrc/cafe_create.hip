@@ -46,7 +46,7 @@ namespace {
 
 // Environment switches read at cafe_create, all diagnostics: none of them changes a result bit.  Those of the call path go
 // into the context; those of cafe_create itself come back.
-struct Switches { bool no_groups, no_kskip, no_leaf_t, gemm_stamps, dump_schedule; double lt_min; int kb; };
+struct Switches { bool no_groups, no_kskip, no_leaf_t, no_cherry_swap, gemm_stamps, dump_schedule; double lt_min, inherit_all, inherit_big; int kb; };
 
 Switches read_switches(cafe_ctx* c) {
     Switches sw{};
@@ -54,7 +54,12 @@ Switches read_switches(cafe_ctx* c) {
     sw.no_groups = std::getenv("CAFE_NO_GROUPS");            // one op per launch from the slot pool instead of level-batched launches
     sw.no_kskip = std::getenv("CAFE_NO_KSKIP");              // no matrix or panel extents: every K tile of every launch
     sw.no_leaf_t = std::getenv("CAFE_NO_LEAF_T");            // no transposed leaf matrices for the assemble passes
+    sw.no_cherry_swap = std::getenv("CAFE_NO_CHERRY_SWAP");  // a cherry on one matrix keeps counts (a, b) and (b, a) in columns of their own
     sw.lt_min = (e = std::getenv("CAFE_LEAF_T_MIN")) ? atof(e) : 6.0;   // a leaf branch gets one when its passes write >= lt_min N columns
+    // column-space thresholds of the subtree de-duplication (plan_patterns, step 2): "all,big"
+    sw.inherit_all = 0.15; sw.inherit_big = 0.12;
+    double th[2];
+    if ((e = std::getenv("CAFE_INHERIT")) && std::sscanf(e, "%lf,%lf", &th[0], &th[1]) == 2 && th[0] >= 0 && th[1] >= 0) { sw.inherit_all = th[0]; sw.inherit_big = th[1]; }
     sw.kb = (e = std::getenv("CAFE_KB")) ? (std::atoi(e) == 16 ? 16 : std::atoi(e) == 12 ? 12 : 8) : 0;   // depth of K2's K tiles: 8, 12 or 16
     sw.gemm_stamps = std::getenv("CAFE_GEMM_STAMPS");        // per-workgroup block timeline of a K2 launch (cafe_debug_stamps)
     sw.dump_schedule = std::getenv("CAFE_DUMP_SCHEDULE");    // the launch list with its column counts, on stderr
@@ -417,7 +422,7 @@ int create_impl(cafe_ctx* c, const cafe_problem* p) {
 
     // subtree-level de-duplication tables (the schedule depends on them)
     const bool dedup = !device_counts && !(p->flags & CAFE_FLAG_NO_SUBTREE_DEDUP);
-    if (dedup) plan_patterns(c, p, uniq);
+    if (dedup) plan_patterns(c, p, uniq, !sw.no_cherry_swap, sw.inherit_all, sw.inherit_big);
     if ((rc = upload_families(c, p, uniq)) != CAFE_OK) return rc;
     plan_pools(c, sw.kb);
     // Extents (K2 skips the K tiles outside a matrix's non-zero band).  Small matrices (mammals: N = 141, 9 K tiles): a row

@@ -299,7 +299,7 @@ inline int64_t panel_cols(bool dedup, const cafe_ctx* c, int v, int64_t cols) { 
 inline int64_t panel_cols(const cafe_ctx* c, int v, int64_t cols) { return panel_cols(c->subtree_dedup, c, v, cols); }
 
 // Host planner of cafe_create (cafe_schedule.hip): no HIP call, no environment; in the order cafe_create runs them
-void plan_patterns(cafe_ctx* c, const cafe_problem* p, const std::vector<int64_t>& uniq);
+void plan_patterns(cafe_ctx* c, const cafe_problem* p, const std::vector<int64_t>& uniq, bool cherry_swap, double inherit_all, double inherit_big);
 // commits the chosen schedule (ops, panels, chunk width, subtree_dedup, grouped); returns the arena's size in doubles
 size_t plan_schedule(cafe_ctx* c, bool dedup, bool try_grouped, size_t budget, int64_t desc_cols);
 std::vector<int> plan_extent_levels(cafe_ctx* c, bool matrix_extents);

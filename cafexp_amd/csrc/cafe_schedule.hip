@@ -10,9 +10,6 @@ namespace cafe {
 
 namespace {
 
-// Column-space thresholds of the subtree de-duplication (see plan_patterns)
-constexpr double kInheritAll = 0.15, kInheritBig = 0.12;
-
 // Sethi-Ullman style need: panels live while evaluating node v (leaves need none).
 int panel_need(const cafe_ctx* c, int v, std::vector<int>& need) {
     std::vector<int> kid;
@@ -218,7 +215,15 @@ Schedule slot_schedule(const cafe_ctx* c, bool dedup, const std::vector<int>& ne
 // column of each child for every column of its parent, and the leaf children's counts per parent column.  Columns are
 // numbered by first occurrence in (distinct-)family order, so the root's columns are the distinct families themselves
 // and a child with as many patterns as its parent has them in the same order (an identity map: no combine pass).
-void plan_patterns(cafe_ctx* c, const cafe_problem* p, const std::vector<int64_t>& uniq) {
+//
+// cherry_swap: a node whose only children are two leaves on the same matrix (equal quantized branch length and lambda index --
+// what plan_pools makes one pair of; mu goes by the lambda index) keys its patterns on the UNORDERED pair of counts.  Its
+// column for counts (a, b) is P[s][a] * P[s][b] -- each factor formed from its leaf's count alone (one matrix column, or the
+// error-model taps in tap order), the panel value their product in store mode (leaf_gather_fast_kernel, leaf_gather_kernel:
+// v = 1.0 * fa * fb) -- and an IEEE product does not depend on the order of its factors, so (b, a) has the same bits and
+// shares the column.  The representative keeps its counts in leaf order; parents see the merged pid and shrink by
+// themselves.  A node with any further child is not covered: (F * fa) * fb and (F * fb) * fa may differ in the last bit.
+void plan_patterns(cafe_ctx* c, const cafe_problem* p, const std::vector<int64_t>& uniq, bool cherry_swap, double inherit_all, double inherit_big) {
     const int n = c->n_nodes, T = c->n_taxa;
     const int64_t F = c->F_uniq;
     c->pat_cols.assign(n, 0);
@@ -247,10 +252,13 @@ void plan_patterns(cafe_ctx* c, const cafe_problem* p, const std::vector<int64_t
         seen.reserve((size_t)F * 2);
         std::vector<int64_t> first;                      // raw pattern (first-occurrence number) -> first family
         std::vector<int32_t> key(kw);
+        const bool symmetric = cherry_swap && inner.empty() && leaves.size() == 2 && c->lam_idx[leaves[0]] == c->lam_idx[leaves[1]] &&
+                               quantize_time(c->blen[leaves[0]]) == quantize_time(c->blen[leaves[1]]);
         for (int64_t f = 0; f < F; ++f) {
             size_t k = 0;
             for (int u : inner) key[k++] = pid[u][f];
             for (int u : leaves) key[k++] = p->counts[uniq[f] * T + c->leaf_taxon[u]];
+            if (symmetric && key[0] > key[1]) std::swap(key[0], key[1]);
             std::string ks(reinterpret_cast<const char*>(key.data()), sizeof(int32_t) * kw);
             auto it = seen.find(ks);
             if (it == seen.end()) {
@@ -292,6 +300,7 @@ void plan_patterns(cafe_ctx* c, const cafe_problem* p, const std::vector<int64_t
     // ---- 2. column space of every interior node, parents first: its own patterns, or its parent's columns, which makes
     // the edge direct (the GEMM's epilogue writes the parent's panel).  A GEMM column costs about 0.12 us, a column of an
     // assemble pass 0.024 us (one factor + leaf) to 0.036 us (two factors) at the bench shape, so:
+    // (inherit_all = 0.15, inherit_big = 0.12 unless CAFE_INHERIT sweeps them)
     //  * all interior children inherit when together they add < 15 % GEMM columns (store / multiply epilogues, one leaf
     //    sibling fused);
     //  * of two interior children (no leaf sibling) the larger one inherits alone when it adds < 12 % (an assemble pass
@@ -306,11 +315,11 @@ void plan_patterns(cafe_ctx* c, const cafe_problem* p, const std::vector<int64_t
         const double Uv = (double)rep[space[v]].size();
         double extra = 0;
         for (int u : inner) extra += 1.0 - (double)rep[u].size() / Uv;
-        const bool inherit = !inner.empty() && n_leaves <= 1 && extra < kInheritAll;
+        const bool inherit = !inner.empty() && n_leaves <= 1 && extra < inherit_all;
         for (int u : inner) space[u] = inherit ? space[v] : u;
         if (!inherit && inner.size() == 2 && n_leaves == 0) {
             const int big = rep[inner[0]].size() >= rep[inner[1]].size() ? inner[0] : inner[1];
-            if (1.0 - (double)rep[big].size() / Uv < kInheritBig) space[big] = space[v];
+            if (1.0 - (double)rep[big].size() / Uv < inherit_big) space[big] = space[v];
         }
     }
     // ---- 3. tables (cafe_create uploads them)
