@@ -115,7 +115,7 @@ EXPORTS = [
     "cafe_comm_unique_id", "cafe_comm_attach", "cafe_comm_detach", "cafe_shard_plan", "cafe_shard_plan_scaled", "cafe_create_sharded",
     "cafe_sharded_destroy", "cafe_sharded_last_error", "cafe_sharded_score", "cafe_sharded_family_results",
     "cafe_sharded_size", "cafe_sharded_context", "cafe_set_graphs", "cafe_executed_flops", "cafe_debug_tile_range_flops", "cafe_get_extents", "cafe_debug_launch_flops", "cafe_debug_launch_ms", "cafe_debug_plan_check",
-    "cafe_debug_fail_next", "cafe_debug_column_extents", "cafe_debug_leaf_transposes", "cafe_simulate",
+    "cafe_debug_fail_next", "cafe_debug_column_extents", "cafe_debug_panel_bounds", "cafe_debug_k_ranges", "cafe_issued_flops", "cafe_debug_leaf_transposes", "cafe_simulate",
     "cafe_score_per_family", "cafe_marginal_reconstruct", "cafe_debug_marginal_gemm", "cafe_sample_histories", "cafe_debug_history_batches",
     "cafe_set_death_rates", "cafe_bd_rates", "cafe_build_matrices_lm", "cafe_score_per_family_lm", "cafe_simulate_lm",
     "cafe_score_gradient", "cafe_bd_rates_grad", "cafe_expected_events", "cafe_bd_rates_events",
@@ -711,6 +711,30 @@ class Context:
         self._check(self._lib.cafe_debug_column_extents(self._h, node, category, _p(out, _i32p), out.size, C.byref(n)))
         return out[:n.value]
 
+    def panel_bounds(self, node: int, category: int = 0) -> np.ndarray:
+        """Magnitude bounds [tiles][row steps] of an interior non-root node's panel in the last call: an upper bound of log2 of
+        every computed entry of rows 4 r .. 4 r + 3 of a 128-column tile, -inf where all are zero (cafe_debug_panel_bounds)."""
+        f = self._lib.cafe_debug_panel_bounds
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _f64p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        nt, nr = C.c_int32(), C.c_int32()
+        self._check(f(self._h, node, category, None, 0, C.byref(nt), C.byref(nr)))
+        out = np.zeros((nt.value, nr.value), dtype=np.float64)
+        self._check(f(self._h, node, category, _p(out, _f64p), out.size, C.byref(nt), C.byref(nr)))
+        return out
+
+    def k_ranges(self, node: int, category: int = 0) -> np.ndarray:
+        """K ranges [tiles][16-row blocks][2] (first / last k-step, 4 deep; first > last: none) of the K2 op of the branch above
+        an interior non-root node in the last call (cafe_debug_k_ranges)."""
+        f = self._lib.cafe_debug_k_ranges
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _i32p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        nt, nb = C.c_int32(), C.c_int32()
+        self._check(f(self._h, node, category, None, 0, C.byref(nt), C.byref(nb)))
+        out = np.zeros((nt.value, nb.value, 2), dtype=np.int32)
+        self._check(f(self._h, node, category, _p(out, _i32p), out.size, C.byref(nt), C.byref(nb)))
+        return out
+
     def leaf_transposes(self):
         """(leaf branches with a transposed copy of their matrix for the assemble passes, whether the last call used them)."""
         self._lib.cafe_debug_leaf_transposes.restype = C.c_int
@@ -739,6 +763,15 @@ class Context:
         """Flops the K2 launches of the last call really ran (K tiles outside matrix extent x panel extent are skipped)."""
         v = C.c_double()
         self._check(self._lib.cafe_executed_flops(self._h, C.byref(v)))
+        return v.value
+
+    def issued_flops(self) -> float:
+        """Flops of the MFMAs the K2 launches of the last call issued: executed_flops() less the k-steps whose products
+        underflow below the smallest denormal (cafe_issued_flops)."""
+        self._lib.cafe_issued_flops.restype = C.c_int
+        self._lib.cafe_issued_flops.argtypes = [C.c_void_p, _f64p]
+        v = C.c_double()
+        self._check(self._lib.cafe_issued_flops(self._h, C.byref(v)))
         return v.value
 
     def tile_range_flops(self) -> float:

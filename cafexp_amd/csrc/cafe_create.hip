@@ -26,8 +26,8 @@ void free_device(cafe_ctx* c) {
     comm_release(c);
     for (auto& g : c->graphs) if (g.second.exec) hipGraphExecDestroy(g.second.exec);
     hipFree(c->d_counts); hipFree(c->d_weights); hipFree(c->pool.base); hipFree(c->kpool.base); hipFree(c->kpool.ext); hipFree(c->pool.ext); hipFree(c->d_params); hipFree(c->d_panels);
-    hipFree(c->d_ext_nodes); hipFree(c->d_fam_out); hipFree(c->d_fam_lik); hipFree(c->d_cat_out); hipFree(c->d_failed);
-    for (auto* ptrs : {&c->d_colext, &c->d_tileext, &c->d_edge_map, &c->d_leaf_cnt}) for (auto ptr : *ptrs) hipFree(ptr);
+    hipFree(c->d_ext_nodes); hipFree(c->d_mag_a16); hipFree(c->d_mag_t4); hipFree(c->d_mag_lt); hipFree(c->d_jr); hipFree(c->d_fam_out); hipFree(c->d_fam_lik); hipFree(c->d_cat_out); hipFree(c->d_failed);
+    for (auto* ptrs : {&c->d_colext, &c->d_tileext, &c->d_bound, &c->d_edge_map, &c->d_leaf_cnt}) for (auto ptr : *ptrs) hipFree(ptr);
     hipFree(c->d_scratch); hipFree(c->d_result); hipFree(c->d_stamps);
     for (void* h : {(void*)c->h_stage, (void*)c->h_result, (void*)c->h_ext, (void*)c->h_gemm_stage, (void*)c->h_plan_desc}) if (h) hipHostFree(h);
     auto free_desc = [](DescSet& d) { hipFree(d.d_gemm_ops); hipFree(d.d_plan_desc); hipFree(d.d_plan); d = DescSet(); };
@@ -46,13 +46,14 @@ namespace {
 
 // Environment switches read at cafe_create, all diagnostics: none of them changes a result bit.  Those of the call path go
 // into the context; those of cafe_create itself come back.
-struct Switches { bool no_groups, no_kskip, no_leaf_t, no_cherry_swap, gemm_stamps, dump_schedule; double lt_min, inherit_all, inherit_big; int kb; };
+struct Switches { bool no_groups, no_kskip, no_magskip, no_leaf_t, no_cherry_swap, gemm_stamps, dump_schedule; double lt_min, inherit_all, inherit_big; int kb; };
 
 Switches read_switches(cafe_ctx* c) {
     Switches sw{};
     const char* e;
     sw.no_groups = std::getenv("CAFE_NO_GROUPS");            // one op per launch from the slot pool instead of level-batched launches
     sw.no_kskip = std::getenv("CAFE_NO_KSKIP");              // no matrix or panel extents: every K tile of every launch
+    sw.no_magskip = std::getenv("CAFE_NO_MAGSKIP");          // K ranges from the exact-zero extents alone, no magnitude bounds
     sw.no_leaf_t = std::getenv("CAFE_NO_LEAF_T");            // no transposed leaf matrices for the assemble passes
     sw.no_cherry_swap = std::getenv("CAFE_NO_CHERRY_SWAP");  // a cherry on one matrix keeps counts (a, b) and (b, a) in columns of their own
     sw.lt_min = (e = std::getenv("CAFE_LEAF_T_MIN")) ? atof(e) : 6.0;   // a leaf branch gets one when its passes write >= lt_min N columns
@@ -310,7 +311,7 @@ int alloc_resident(cafe_ctx* c, bool kskip, bool gemm_stamps) {
 int cnt_row(const cafe_ctx* c, int leaf) { return c->subtree_dedup ? c->leaf_rank[leaf] : c->leaf_taxon[leaf]; }
 
 // The arena of the likelihood panels, and the zero extents of the planned nodes' panels with their descriptors
-int alloc_panels(cafe_ctx* c, size_t panel_doubles, const std::vector<int>& ext_order) {
+int alloc_panels(cafe_ctx* c, size_t panel_doubles, const std::vector<int>& ext_order, bool magskip) {
     // (+64 KB: the assemble pass reads whole 64-row tiles of a transposed factor, up to a tile past its last column)
     const size_t panel_bytes = panel_doubles * sizeof(double) + 65536;
     if (hipMalloc(&c->d_panels, panel_bytes) != hipSuccess) { set_err(c, "cafe_create: cannot allocate %.2f GB of likelihood panels", panel_bytes / 1e9); return CAFE_ERR_MEMORY; }
@@ -323,10 +324,24 @@ int alloc_panels(cafe_ctx* c, size_t panel_doubles, const std::vector<int>& ext_
         HIP_TRY(c, hipMalloc(&c->d_colext[v], sizeof(int32_t) * 2 * (size_t)c->Kmax * cols));
         HIP_TRY(c, hipMalloc(&c->d_tileext[v], sizeof(int32_t) * 2 * (size_t)c->Kmax * (cols / kBN)));
     }
+    // magnitude tables and panel bounds (extents.hip).  They come after the panels and are an optimisation: where they do
+    // not fit, the call keeps the exact extents.
+    c->d_bound.assign(c->n_nodes, nullptr);
+    c->n_ksteps = (c->M + 1 + 3) / 4; c->n_rsteps = (c->N + 3) / 4;
+    if (c->panel_extents && magskip) {
+        bool ok = hipMalloc(&c->d_mag_a16, sizeof(int32_t) * (size_t)c->max_kslots * c->n_ksteps * c->kpool.ext_blocks) == hipSuccess &&
+                  hipMalloc(&c->d_mag_t4, sizeof(int32_t) * (size_t)c->max_kslots * c->n_ksteps * c->n_rsteps) == hipSuccess &&
+                  hipMalloc(&c->d_mag_lt, sizeof(int32_t) * (size_t)std::max(1, c->max_slots) * (c->M + 1) * c->n_rsteps) == hipSuccess;
+        for (int v : ext_order)
+            ok = ok && hipMalloc(&c->d_bound[v], sizeof(int32_t) * (size_t)c->Kmax * (panel_cols(c, v, c->Fp) / kBN) * c->n_rsteps) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+        c->magskip = ok;
+    }
     if (c->panel_extents) {
         std::vector<ExtNode> nodes;
         for (int v : ext_order) {
             ExtNode nd{};
+            nd.bound = c->magskip ? c->d_bound[v] : nullptr;
             nd.cols = (int32_t)panel_cols(c, v, c->Fp);
             nd.colext = c->d_colext[v]; nd.tileext = c->d_tileext[v];
             nd.cnt = c->subtree_dedup ? c->d_leaf_cnt[v] : c->d_counts; nd.cnt_ld = nd.cols;
@@ -335,6 +350,7 @@ int alloc_panels(cafe_ctx* c, size_t panel_doubles, const std::vector<int>& ext_
                 nd.inner_pair[nd.n_inner] = c->pair_of[u];
                 nd.inner_cols[nd.n_inner] = (int32_t)panel_cols(c, u, c->Fp);
                 nd.inner_map[nd.n_inner] = c->subtree_dedup ? c->d_edge_map[u] : nullptr;    // (nullptr for an identity edge)
+                nd.inner_bound[nd.n_inner] = c->magskip ? c->d_bound[u] : nullptr;
                 nd.inner_colext[nd.n_inner++] = c->d_colext[u];
             }
             nodes.push_back(nd);
@@ -347,6 +363,15 @@ int alloc_panels(cafe_ctx* c, size_t panel_doubles, const std::vector<int>& ext_
 // Static descriptors (n_row_tiles of a K2 op follows the tile height, chosen per call) and the per-call launch state
 int build_descriptors(cafe_ctx* c, const std::vector<int>& lt_of_pair) {
     c->h_gemm_ops.assign(std::max(1, c->n_gemm_ops), GemmOp{}); c->h_gather_ops.assign(std::max(1, c->n_gather_ops), GatherArgs{});
+    // joint K ranges of the K2 ops (whenever the matrices publish extents): per op [category][column tiles or 1][blocks + pad]
+    const size_t jr_row = (size_t)c->kpool.ext_blocks + kRangePad;
+    if (c->kpool.ext) {
+        size_t words = 0;
+        for (const Op& op : c->ops)
+            if (op.type == 1) words += (size_t)c->Kmax * (c->panel_extents ? panel_cols(c, op.child, c->Fp) / kBN : 1) * jr_row;
+        HIP_TRY(c, hipMalloc(&c->d_jr, sizeof(int32_t) * std::max<size_t>(1, words)));
+    }
+    size_t jr_used = 0;
     const int64_t lt_kstride = (int64_t)(c->M + 1) * c->factor_ld;
     for (const Op& op : c->ops) {
         const int32_t* cnt_base = c->subtree_dedup ? c->d_leaf_cnt[op.parent] : c->d_counts;
@@ -373,6 +398,13 @@ int build_descriptors(cafe_ctx* c, const std::vector<int>& lt_of_pair) {
                 g.gath_ld = c->factor_ld; g.gath_map = c->d_edge_map[op.gath_child];
             }
             g.bext = c->panel_extents ? c->d_tileext[op.child] : nullptr;
+            if (c->d_jr) {
+                g.jr = c->d_jr + jr_used;
+                g.jr_nct = c->panel_extents ? g.n_col_tiles : 1; g.jr_ct_mask = c->panel_extents ? -1 : 0;
+                jr_used += (size_t)c->Kmax * g.jr_nct * jr_row;
+                c->jr_max_tiles = std::max(c->jr_max_tiles, (int)g.jr_nct);
+                g.bbound = c->magskip ? c->d_bound[op.child] : nullptr;
+            }
         } else {
             GatherArgs& g = c->h_gather_ops[op.desc];
             g.n_leaf = op.n_leaf;
@@ -439,7 +471,7 @@ int create_impl(cafe_ctx* c, const cafe_problem* p) {
     const size_t panel_doubles = plan_schedule(c, dedup, !sw.no_groups, budget, desc_cols);
     if (c->chunk_cols < kBN) { set_err(c, "cafe_create: %zu bytes of workspace cannot hold %d panels of one 128-family tile", budget, c->n_panels); return CAFE_ERR_MEMORY; }
     const std::vector<int> ext_order = plan_extent_levels(c, kskip);
-    if ((rc = alloc_panels(c, panel_doubles, ext_order)) != CAFE_OK) return rc;
+    if ((rc = alloc_panels(c, panel_doubles, ext_order, !sw.no_magskip)) != CAFE_OK) return rc;
 
     // transposed leaf copies, if they fit what is free after the panels
     std::vector<int> lt_of_pair;

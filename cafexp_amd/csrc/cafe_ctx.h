@@ -229,6 +229,14 @@ struct cafe_ctx {
     std::vector<int32_t*> d_colext, d_tileext;            // [n_nodes] (interior non-root nodes only)
     struct ExtLevel { int first, count, max_col_tiles; };
     std::vector<ExtLevel> ext_levels;
+    // K steps whose products underflow (extents.hip, "Magnitudes"): the magnitude tables of a call's matrices, the bounds of
+    // every planned node's panel, and -- whenever the matrices publish extents -- the joint K ranges of every K2 op
+    bool magskip = false;                                 // panel_extents, no CAFE_NO_MAGSKIP, tables allocated
+    bool magskip_last = false;                            // the last call used them (not with an error model: exact extents)
+    int32_t *d_mag_a16 = nullptr, *d_mag_t4 = nullptr, *d_mag_lt = nullptr;
+    std::vector<int32_t*> d_bound;                        // [n_nodes] (interior non-root nodes only)
+    int32_t* d_jr = nullptr;                              // the ops' range tables, one allocation
+    int n_ksteps = 0, n_rsteps = 0, jr_max_tiles = 0;
 
     // K2's row-tile height per launch is chosen from the non-zero extents of the PREVIOUS call's matrices (K1 publishes
     // them on the device; a copy lands in h_ext while the call's K2 launches run): the parameters of consecutive scorer
@@ -323,7 +331,7 @@ inline void quantized_rates(const cafe_ctx* c, const double* lambdas, int i, dou
 int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bool rootmax = false);
 void collect_stats(cafe_ctx* c);                          // the profiling events of the last call into c->stats
 // cafe_debug.hip: flops the K2 launches of the last call executed, from the extents it published (< 0: read-back failed)
-double count_executed_flops(cafe_ctx* c, std::vector<double>* per_launch = nullptr, bool per_block = true);
+double count_executed_flops(cafe_ctx* c, std::vector<double>* per_launch = nullptr, bool per_block = true, bool exact = false);
 // One slot per distinct quantized (lambda * multiplier, t) and layout (matrix_cache.h:42-61), parameters uploaded on
 // `s`, K1 launched: afterwards slot_of[node * Kmax + k] names the matrix of every branch and category.
 int prepare_matrices(cafe_ctx* c, const double* lambdas, const double* multipliers, int K, hipStream_t s);

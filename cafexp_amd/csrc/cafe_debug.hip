@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "cafe_call.h"
@@ -11,71 +12,96 @@ using namespace cafe;
 
 namespace cafe {
 
-// Flops the K2 launches of the last (profiled) call EXECUTED: a (row tile, column tile) pair runs only the K tiles inside
-// matrix extent x panel extent, so read the extents this call published and count, per launch, what its tiles ran.  Reads
-// the extents back (a few synchronous copies, milliseconds of host work): for measurement, once, not per call.
-// per_block: count a row block only over the k-steps (4 deep) inside its own extent and the panel's (what the kernel issues,
-// prune_gemm.hip block_ranges); false: every block over its tile's whole K range (the count of rounds 2 and 3a, kept for
-// comparison).  Both count the valid k and rows only (a ragged last k-step counts its k <= M, a ragged last block its rows).
-double count_executed_flops(cafe_ctx* c, std::vector<double>* per_launch, bool per_block) {
+// The joint K ranges of a K2 op as the last call's range_kernel left them: [K][g.jr_nct][ext_blocks + kRangePad] (empty: none)
+static bool read_ranges(cafe_ctx* c, const GemmOp& g, int K, std::vector<int32_t>& out) {
+    out.clear();
+    if (!g.jr) return true;
+    out.resize((size_t)K * g.jr_nct * (c->kpool.ext_blocks + kRangePad));
+    return hipMemcpy(out.data(), g.jr, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+// The same table from the exact-zero extents alone (range_kernel without magnitude tables, on the host): what the ranges
+// are under CAFE_NO_MAGSKIP=1, whatever the last call used.  aext: the k-major pool's extents, read back by the caller.
+static bool exact_ranges(cafe_ctx* c, const GemmOp& g, int K, const std::vector<int32_t>& aext, std::vector<int32_t>& out) {
+    out.clear();
+    if (!g.jr) return true;
+    const int nb = c->kpool.ext_blocks, row = nb + kRangePad;
+    out.assign((size_t)K * g.jr_nct * row, 1);             // lo 1, hi 0: none
+    std::vector<int32_t> bext;
+    if (g.bext) {
+        bext.resize((size_t)2 * K * g.jr_nct);
+        if (hipMemcpy(bext.data(), g.bext, bext.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return false;
+    }
+    for (int k = 0; k < K; ++k)
+        for (int ct = 0; ct < g.jr_nct; ++ct) {
+            int plo = 0, phi = c->M;
+            if (g.bext) {
+                const int32_t* be = bext.data() + ((size_t)k * g.jr_nct + ct) * 2;
+                plo = be[0]; phi = std::min(be[1], phi);
+                if (be[1] < be[0]) { plo = 0; phi = 0; }    // an empty panel extent: row 0 (extents.hip)
+            }
+            for (int b = 0; b < nb; ++b) {
+                const int32_t* e = aext.data() + ((size_t)g.slot[k] * nb + b) * 2;
+                const int lo = std::max(e[0], plo), hi = std::min(e[1], phi);
+                if (hi >= lo) out[((size_t)k * g.jr_nct + ct) * row + b] = (lo / 4) | ((hi / 4) << 16);
+            }
+        }
+    return true;
+}
+
+// Flops the K2 launches of the last (profiled) call EXECUTED: a row block of a (row tile, column tile) pair issues MFMAs only
+// in the k-steps of its joint range (GemmOp::jr: matrix extent x panel extent, less the k-steps whose products underflow), so
+// read the ranges this call published and count, per launch, what its tiles ran.  A few synchronous copies, milliseconds of
+// host work: for measurement, once, not per call.
+// per_block: what the kernel issues (prune_gemm.hip block_ranges); false: every block over its tile's whole K range (the hull
+// of its blocks' ranges in whole K tiles -- the count of rounds 2 and 3a, kept for comparison).  Both count the valid k and rows only
+// (a ragged last k-step counts its k <= M, a ragged last block its rows).
+// exact: count over the ranges the exact-zero extents alone give (exact_ranges) -- the products that have no exact zero in
+// them, whether or not the call issued them all.
+double count_executed_flops(cafe_ctx* c, std::vector<double>* per_launch, bool per_block, bool exact) {
     if (c->gemm_launches_info.empty()) return c->stats.gemm_flops;
     const int kBK = c->kb;
-    const int nb = c->kpool.ext_blocks;
-    std::vector<int32_t> ext;
-    if (c->kpool.ext) {
-        ext.resize((size_t)2 * c->max_kslots * nb);
-        if (hipMemcpy(ext.data(), c->kpool.ext, ext.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1.0;
-    }
+    const int jr_row = c->kpool.ext_blocks + kRangePad;
     double executed = 0;
-    std::vector<int32_t> bext;
+    std::vector<int32_t> jr, aext;
+    if (exact && c->kpool.ext) {
+        aext.resize((size_t)2 * c->max_kslots * c->kpool.ext_blocks);
+        if (hipMemcpy(aext.data(), c->kpool.ext, aext.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1.0;
+    }
     for (const auto& L : c->gemm_launches_info) {
         const double before = executed;
         const int mi = L.mi, bm = 16 * mi;
         for (int oi : c->groups[L.group].ops) {
             const Op& op = c->ops[oi];
+            const GemmOp& g = c->h_gemm_ops[op.desc];
             const int rows = op.to_root ? c->R : c->M;
             const int64_t cols = panel_cols(c, op.child, L.cols);
             const int n_ct = (int)(cols / kBN);
-            const bool have_b = c->kpool.ext && c->panel_extents && c->d_tileext[op.child];
-            if (have_b) {
-                bext.resize((size_t)2 * L.K * n_ct);
-                if (hipMemcpy(bext.data(), c->d_tileext[op.child], bext.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1.0;
-            }
-            for (int k = 0; k < L.K; ++k) {
-                const int32_t* e = c->kpool.ext ? ext.data() + (size_t)c->slot_of[(size_t)op.child * c->Kmax + k] * nb * 2 : nullptr;
-                for (int row0 = 0; row0 < rows; row0 += bm) {
-                    int alo = 0, ahi = c->M;
-                    if (e) {
-                        alo = 0x7fffffff; ahi = -1;
-                        for (int b = row0 / 16; b < row0 / 16 + mi && b < nb; ++b) { alo = std::min(alo, e[2 * b]); ahi = std::max(ahi, e[2 * b + 1]); }
-                    }
-                    for (int ct = 0; ct < (have_b ? n_ct : 1); ++ct) {
-                        int lo = alo, hi = ahi, plo = 0, phi = c->M;
-                        if (have_b) {
-                            plo = bext[((size_t)k * n_ct + ct) * 2]; phi = std::min(c->M, bext[((size_t)k * n_ct + ct) * 2 + 1]);
-                            lo = std::max(lo, plo); hi = std::min(hi, phi);
-                            if (bext[((size_t)k * n_ct + ct) * 2 + 1] < plo) { plo = 0; phi = 0; }      // an empty panel extent: row 0 (extents.hip)
-                        }
-                        if (hi < lo) { lo = 0; hi = 0; }
-                        hi = std::min(hi, c->M);
-                        // the tile runs K tiles lo/kb .. hi/kb; its row block b issues MFMAs only in the k-steps that meet ITS OWN
-                        // extent cut by the panel's (prune_gemm.hip, block_ranges); the last k-step of the matrix is ragged
-                        const int t_lo = lo / kBK, t_hi = hi / kBK;
+            if (!(exact ? exact_ranges(c, g, L.K, aext, jr) : read_ranges(c, g, L.K, jr))) return -1.0;
+            const bool per_tile = g.jr && g.jr_ct_mask;      // the ranges differ between column tiles
+            for (int k = 0; k < L.K; ++k)
+                for (int row0 = 0; row0 < rows; row0 += bm)
+                    for (int ct = 0; ct < (per_tile ? n_ct : 1); ++ct) {
+                        const double width = per_tile ? (double)kBN : (double)cols;
+                        const int32_t* e = g.jr ? jr.data() + ((size_t)k * g.jr_nct + ct) * jr_row : nullptr;
+                        int slo = 0x7fff, shi = -1;
+                        for (int b = row0 / 16; e && b < row0 / 16 + mi; ++b)
+                            if ((e[b] >> 16) >= (e[b] & 0xFFFF)) { slo = std::min(slo, e[b] & 0xFFFF); shi = std::max(shi, e[b] >> 16); }
+                        if (!e) { slo = 0; shi = c->M / 4; }
+                        if (shi < slo) { slo = 0; shi = 0; }     // an all-zero tile runs one K tile
+                        const int t_lo = slo * 4 / kBK, t_hi = std::min(shi * 4 + 3, c->M) / kBK;
                         for (int b = row0 / 16; b < row0 / 16 + mi && b * 16 < rows; ++b) {
                             int kk;
                             if (e && per_block) {
-                                if (b >= nb) continue;
-                                const int s_lo = std::max(e[2 * b], plo), s_hi = std::min(e[2 * b + 1], phi);
-                                if (s_hi < s_lo) continue;
-                                kk = std::min((s_hi / 4 - s_lo / 4 + 1) * 4, c->M + 1 - s_lo / 4 * 4);
+                                const int l = e[b] & 0xFFFF, h = e[b] >> 16;
+                                if (h < l) continue;
+                                kk = std::min((h - l + 1) * 4, c->M + 1 - l * 4);
                             } else {
                                 kk = std::min((t_hi - t_lo + 1) * kBK, c->M + 1 - t_lo * kBK);
                             }
-                            executed += 2.0 * std::min(16, rows - b * 16) * (double)kk * (have_b ? (double)kBN : (double)cols);
+                            executed += 2.0 * std::min(16, rows - b * 16) * (double)kk * width;
                         }
                     }
-                }
-            }
         }
         if (per_launch) per_launch->push_back(executed - before);
     }
@@ -153,6 +179,51 @@ int cafe_debug_column_extents(cafe_ctx* ctx, int32_t node, int32_t category, int
     return CAFE_OK;
 }
 
+// Upper bounds of a node's panel (node_bound_kernel): out[tile * row_steps + r] = bound of log2 of every computed entry of
+// rows 4 r .. 4 r + 3 in 128-column tile `tile` of `category`; -inf where all of them are exactly zero.
+int cafe_debug_panel_bounds(cafe_ctx* ctx, int32_t node, int32_t category, double* out, size_t out_len, int32_t* n_tiles, int32_t* row_steps) {
+    if (!ctx) return CAFE_ERR_ARGUMENT;
+    if (!ctx->have_results || ctx->last_rejected) { set_err(ctx, "cafe_debug_panel_bounds: no completed call"); return CAFE_ERR_STATE; }
+    if (node < 0 || node >= ctx->n_nodes || category < 0 || category >= ctx->K_last) { set_err(ctx, "cafe_debug_panel_bounds: node/category out of range"); return CAFE_ERR_ARGUMENT; }
+    if (!ctx->magskip_last || !ctx->d_bound[node]) { set_err(ctx, "cafe_debug_panel_bounds: the last call kept no bounds for this node"); return CAFE_ERR_STATE; }
+    const int nt = (int)(panel_cols(ctx, node, ctx->Fp) / kBN), nr = ctx->n_rsteps;
+    if (n_tiles) *n_tiles = nt;
+    if (row_steps) *row_steps = nr;
+    if (!out) return CAFE_OK;
+    if (out_len < (size_t)nt * nr) { set_err(ctx, "cafe_debug_panel_bounds: out too small"); return CAFE_ERR_ARGUMENT; }
+    if (const int rc = wait_last_call(ctx)) return rc;
+    std::vector<int32_t> q((size_t)nt * nr);
+    HIP_TRY(ctx, hipMemcpy(q.data(), ctx->d_bound[node] + (size_t)category * nt * nr, q.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < q.size(); ++i) out[i] = q[i] == kMagNone ? -HUGE_VAL : (double)q[i] / kMagUnit;
+    return CAFE_OK;
+}
+
+// The joint K ranges of the K2 op that multiplies the matrix of the branch above `node` (an interior non-root node):
+// out[(tile * blocks + b) * 2 + {0, 1}] = first / last k-step (4 deep) of 16-row block b against column tile `tile` of the
+// node's panel, first > last: none.  *n_tiles = 1 where the panels have no extents (one range per block).
+int cafe_debug_k_ranges(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* out, size_t out_len, int32_t* n_tiles, int32_t* n_blocks) {
+    if (!ctx) return CAFE_ERR_ARGUMENT;
+    if (!ctx->have_results || ctx->last_rejected) { set_err(ctx, "cafe_debug_k_ranges: no completed call"); return CAFE_ERR_STATE; }
+    if (category < 0 || category >= ctx->K_last) { set_err(ctx, "cafe_debug_k_ranges: category out of range"); return CAFE_ERR_ARGUMENT; }
+    const GemmOp* g = nullptr;
+    for (const Op& op : ctx->ops) if (op.type == 1 && op.child == node) g = &ctx->h_gemm_ops[op.desc];
+    if (!g || !g->jr) { set_err(ctx, "cafe_debug_k_ranges: no K2 op with ranges for this node"); return CAFE_ERR_STATE; }
+    const int nb = ctx->kpool.ext_blocks;
+    if (n_tiles) *n_tiles = g->jr_nct;
+    if (n_blocks) *n_blocks = nb;
+    if (!out) return CAFE_OK;
+    if (out_len < (size_t)2 * g->jr_nct * nb) { set_err(ctx, "cafe_debug_k_ranges: out too small"); return CAFE_ERR_ARGUMENT; }
+    if (const int rc = wait_last_call(ctx)) return rc;
+    std::vector<int32_t> jr;
+    if (!read_ranges(ctx, *g, ctx->K_last, jr)) { set_err(ctx, "cafe_debug_k_ranges: reading the ranges back failed"); return CAFE_ERR_DEVICE; }
+    for (int t = 0; t < g->jr_nct; ++t)
+        for (int b = 0; b < nb; ++b) {
+            const int32_t v = jr[((size_t)category * g->jr_nct + t) * (nb + kRangePad) + b];
+            out[((size_t)t * nb + b) * 2] = v & 0xFFFF; out[((size_t)t * nb + b) * 2 + 1] = v >> 16;
+        }
+    return CAFE_OK;
+}
+
 int cafe_debug_tile_range_flops(cafe_ctx* ctx, double* flops) {
     if (!ctx || !flops) return CAFE_ERR_ARGUMENT;
     if (!ctx->have_results || ctx->gemm_launches_info.empty()) { set_err(ctx, "cafe_debug_tile_range_flops: no completed call that was enqueued launch by launch"); return CAFE_ERR_STATE; }
@@ -168,8 +239,19 @@ int cafe_executed_flops(cafe_ctx* ctx, double* flops) {
     if (!ctx->have_results) { set_err(ctx, "cafe_executed_flops: no completed call"); return CAFE_ERR_STATE; }
     if (const int rc = wait_last_call(ctx)) return rc;
     if (ctx->gemm_launches_info.empty()) { set_err(ctx, "cafe_executed_flops: the last call was not enqueued launch by launch (a graph replay keeps no launch list)"); return CAFE_ERR_STATE; }
-    const double v = count_executed_flops(ctx);
+    const double v = count_executed_flops(ctx, nullptr, true, true);
     if (v < 0) { set_err(ctx, "cafe_executed_flops: reading the extents back failed"); return CAFE_ERR_DEVICE; }
+    *flops = v;
+    return CAFE_OK;
+}
+
+int cafe_issued_flops(cafe_ctx* ctx, double* flops) {
+    if (!ctx || !flops) return CAFE_ERR_ARGUMENT;
+    if (!ctx->have_results) { set_err(ctx, "cafe_issued_flops: no completed call"); return CAFE_ERR_STATE; }
+    if (const int rc = wait_last_call(ctx)) return rc;
+    if (ctx->gemm_launches_info.empty()) { set_err(ctx, "cafe_issued_flops: the last call was not enqueued launch by launch (a graph replay keeps no launch list)"); return CAFE_ERR_STATE; }
+    const double v = count_executed_flops(ctx);
+    if (v < 0) { set_err(ctx, "cafe_issued_flops: reading the ranges back failed"); return CAFE_ERR_DEVICE; }
     *flops = v;
     return CAFE_OK;
 }
@@ -184,12 +266,7 @@ int cafe_debug_plan_check(cafe_ctx* ctx, int32_t* n_planned, double* worst_load)
     const DescSet* ds = ctx->desc_last;
     if (!ds || ctx->plan_launches_last == 0 || ds->plan_desc_sent.empty()) return CAFE_OK;
     if (const int rc = wait_last_call(ctx)) return rc;
-    const int nb = ctx->kpool.ext_blocks;
-    std::vector<int32_t> aext, bext;
-    if (ctx->kpool.ext) {
-        aext.resize((size_t)2 * ctx->max_kslots * nb);
-        HIP_TRY(ctx, hipMemcpy(aext.data(), ctx->kpool.ext, aext.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
+    const int jr_row = ctx->kpool.ext_blocks + kRangePad;
     std::vector<int2> plan;
     double worst = 1.0;
     for (const PlanLaunch& L : ds->plan_desc_sent) {
@@ -197,9 +274,10 @@ int cafe_debug_plan_check(cafe_ctx* ctx, int32_t* n_planned, double* worst_load)
         plan.resize((size_t)8 * nlb * L.rounds);
         HIP_TRY(ctx, hipMemcpy(plan.data(), L.plan, plan.size() * sizeof(int2), hipMemcpyDeviceToHost));
         const GemmOp* ops = ds->gemm_ops_sent.data() + (L.ops - ds->d_gemm_ops);
-        std::vector<std::vector<int32_t>> op_bext(L.n_ops);
+        std::vector<std::vector<int32_t>> op_bext(L.n_ops), op_jr(L.n_ops);
         for (int o = 0; o < L.n_ops; ++o) {
             const int nct = L.uniform_ld > 0 ? L.uniform_ld / kBN : ops[o].n_col_tiles;
+            if (ctx->kpool.ext && !read_ranges(ctx, ops[o], L.n_categories, op_jr[o])) { set_err(ctx, "cafe_debug_plan_check: reading the ranges back failed"); return CAFE_ERR_DEVICE; }
             if (ops[o].bext && ctx->kpool.ext) {
                 op_bext[o].resize((size_t)2 * L.n_categories * nct);
                 HIP_TRY(ctx, hipMemcpy(op_bext[o].data(), ops[o].bext, op_bext[o].size() * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -226,15 +304,16 @@ int cafe_debug_plan_check(cafe_ctx* ctx, int32_t* n_planned, double* worst_load)
                     const int ct = pair % nct, cat = pair / nct, b0 = row_tile * L.mi;
                     int lo = 0, hi = L.k_valid - 1, zlo = 0;
                     if (ctx->kpool.ext) {
-                        const int32_t* a = aext.data() + ((size_t)ops[o].slot[cat] * nb + b0) * 2;
-                        lo = 0x7fffffff; hi = -1;
-                        for (int b = 0; b < L.mi && b0 + b < nb; ++b) { lo = std::min(lo, a[2 * b]); hi = std::max(hi, a[2 * b + 1]); }
+                        const int32_t* a = op_jr[o].data() + ((size_t)cat * ops[o].jr_nct + (ct & ops[o].jr_ct_mask)) * jr_row + b0;
+                        int slo = 0x7fff, shi = -1;
+                        for (int b = 0; b < L.mi; ++b)
+                            if ((a[b] >> 16) >= (a[b] & 0xFFFF)) { slo = std::min(slo, a[b] & 0xFFFF); shi = std::max(shi, a[b] >> 16); }
+                        lo = slo * 4; hi = shi * 4 + 3;
                         if (!op_bext[o].empty()) {
                             const int32_t* be = op_bext[o].data() + ((size_t)cat * nct + ct) * 2;
-                            lo = std::max(lo, be[0]); hi = std::min(hi, be[1]);
                             if (be[1] >= be[0]) zlo = be[0];
                         }
-                        if (hi < lo) { lo = zlo; hi = zlo; }
+                        if (shi < slo) { lo = zlo; hi = zlo; }
                         hi = std::min(hi, L.k_valid - 1);
                     }
                     if ((e.y >> 16) != lo / L.kb || (e.y & 0xFFFF) != hi / L.kb - lo / L.kb + 1) goto bad;
@@ -249,7 +328,7 @@ int cafe_debug_plan_check(cafe_ctx* ctx, int32_t* n_planned, double* worst_load)
         if (n_planned) *n_planned += 1;
         continue;
     bad:
-        set_err(ctx, "cafe_debug_plan_check: the tile lists of a launch do not match its extents");
+        set_err(ctx, "cafe_debug_plan_check: the tile lists of a launch do not match its K ranges");
         return CAFE_ERR_STATE;
     }
     if (worst_load) *worst_load = worst;

@@ -172,7 +172,17 @@ struct GemmOp {
     // per (category, column tile) of the CHILD panel: rows outside [bext[..][0], bext[..][1]] are exactly zero (extents.hip);
     // nullptr: unknown
     const int32_t* bext;
+    // Joint K ranges (range_kernel, extents.hip; nullptr: no extents, every k-step): per (category, column tile, 16-row block
+    // of the matrix) the first and last k-step (4 deep) this op's MFMAs need, lo | hi << 16, lo > hi: none --
+    // jr[((category * jr_nct + (column tile & jr_ct_mask)) * (ext_blocks + kRangePad)) + block].  jr_nct = 1 and jr_ct_mask = 0
+    // where the panels have no extents (the ranges are then the matrix's own).  The planner takes a tile's K tiles from the
+    // hull of its blocks' ranges; K2 reads its MI ranges from here.
+    const int32_t* jr;
+    int32_t jr_nct, jr_ct_mask;
+    // upper bounds of the child panel's magnitudes (node_bound_kernel): [category][column tile][row steps], or nullptr
+    const int32_t* bbound;
 };
+constexpr int kRangePad = 8;        // blocks a row tile may overhang the matrix's last one (MI - 1): entries past it say "none"
 
 struct GemmArgs {
     MatrixPool pool;                // k-major pool
@@ -293,6 +303,10 @@ struct ExtNode {
     const int32_t* inner_colext[kMaxExtChildren];   // the child's per-column extents [category][its columns][2]
     int32_t* colext;                         // [category][cols][2]: rows outside [lo, hi] of a column are exactly zero
     int32_t* tileext;                        // [category][cols / 128][2]: hull over a 128-column tile (K2's B operand)
+    // magnitude bounds (node_bound_kernel): [category][cols / 128][row steps] per 128-column tile and step of 4 panel rows,
+    // an upper bound of log2 of every COMPUTED entry, in 1/256 (kMagNone: all exactly zero); the interior children's likewise
+    int32_t* bound;
+    const int32_t* inner_bound[kMaxExtChildren];
 };
 struct ExtArgs {
     const ExtNode* nodes;
@@ -304,8 +318,45 @@ struct ExtArgs {
     int32_t M;
     const double* err;                       // error model or nullptr
     int32_t n_dev;
+    // magnitude tables of this call's matrices (MagArgs), nullptr: no bounds
+    const int32_t* t4;
+    const int32_t* lt;
+    int32_t n_rsteps, n_ksteps;
 };
 hipError_t launch_node_extents(const ExtArgs& a, int max_col_tiles, int n_categories, hipStream_t stream);
+
+// Magnitudes (extents.hip).  A product P[s][k] L[k][f] of two non-zero factors below half the smallest denormal moves no
+// accumulator either: the tables below bound log2 of the matrix entries, node_bound_kernel propagates bounds of the panels
+// up the tree, and range_kernel cuts a block's K range to the k-steps where (matrix bound + panel bound) >= kSkipBelow.
+// All bounds are upper bounds of log2 in units of 1/256, rounded up.
+constexpr int32_t kMagUnit = 256;
+constexpr int32_t kMagNone = -(1 << 28);             // every entry exactly zero (two of them still add without overflow)
+constexpr int32_t kMagFloor = -1050 * kMagUnit;      // a panel bound inside the exact extent is never below this: a sum of up to
+                                                     // 2048 products, each rounded up in the denormal range, stays under 2^-1063
+constexpr int32_t kMagSlack = 16;                    // added per tree level: (1 + 2^-53)^n of the roundings, the denormal round-ups
+constexpr int32_t kSkipBelow = -1100 * kMagUnit;     // 2^-1100 * 4 products of an MFMA < 2^-1075: rounds away against 0 or >= 2^-1074
+constexpr int kMaxSteps = 512;                       // k-steps / row steps of the largest matrix order (2048 / 4)
+struct MagArgs {
+    MatrixPool kpool, lpool;
+    int32_t n_kslots, n_lslots;      // slots of this call
+    int32_t n_ksteps;                // ceil((M + 1) / 4): steps of 4 child sizes (K2's k-steps)
+    int32_t n_rsteps;                // ceil(N / 4): steps of 4 parent sizes 4r .. 4r + 3 (panel rows)
+    int32_t M;
+    int32_t* a16;                    // [k-major slot][k-step][ext_blocks]: largest entry of (16 parent sizes of a block) x (4 child sizes)
+    int32_t* t4;                     // [k-major slot][k-step][row step]: largest over the step's parent sizes of sum_c P[s][c], c in the k-step
+    int32_t* lt;                     // [row-major slot][count x <= M][row step]: largest P[s][x] over the step's sizes
+};
+hipError_t launch_magnitude_tables(const MagArgs& a, hipStream_t stream);
+hipError_t launch_node_bounds(const ExtArgs& a, int max_col_tiles, int n_categories, hipStream_t stream);
+struct RangeArgs {
+    const GemmOp* ops;
+    int32_t n_ops;
+    const int32_t* aext;             // MatrixPool::ext of the k-major pool
+    int32_t ext_blocks;
+    const int32_t* a16;              // MagArgs::a16, or nullptr: exact-zero extents only
+    int32_t n_ksteps, n_rsteps, k_valid;
+};
+hipError_t launch_joint_ranges(const RangeArgs& a, int max_col_tiles, int n_categories, hipStream_t stream);
 
 struct ReduceArgs {
     const double* root;             // root panel [category][i][family]

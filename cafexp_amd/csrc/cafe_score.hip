@@ -317,8 +317,19 @@ int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool 
         c->h_ext_valid = true;
         c->h_ext_K = K;
     }
+    const bool mag = c->magskip && !use_err; // (an error model's taps would need bounds of their own: exact extents then)
+    c->magskip_last = mag;
+    if (mag) {                               // magnitude tables of this call's matrices: one pass over the two pools
+        MagArgs ma{};
+        ma.kpool = c->kpool; ma.lpool = c->pool;
+        ma.n_kslots = c->n_kslots_last; ma.n_lslots = c->n_slots_last;
+        ma.n_ksteps = c->n_ksteps; ma.n_rsteps = c->n_rsteps; ma.M = c->M;
+        ma.a16 = c->d_mag_a16; ma.t4 = c->d_mag_t4; ma.lt = c->d_mag_lt;
+        HIP_TRY(c, launch_magnitude_tables(ma, s));
+    }
     if (c->panel_extents) {                  // zero extents of every node's panel for this call's matrices (extents.hip)
         ExtArgs ea{};
+        ea.t4 = mag ? c->d_mag_t4 : nullptr; ea.lt = c->d_mag_lt; ea.n_rsteps = c->n_rsteps; ea.n_ksteps = c->n_ksteps;
         ea.nodes = c->d_ext_nodes;
         ea.leaf_ext = c->pool.ext; ea.leaf_ext_blocks = c->pool.ext_blocks; ea.n_pairs_leaf = c->n_pairs[0];
         ea.kext = c->kpool.ext; ea.kext_blocks = c->kpool.ext_blocks; ea.n_pairs_inner = c->n_pairs[1];
@@ -327,7 +338,16 @@ int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool 
         for (const auto& L : c->ext_levels) {
             ea.first = L.first; ea.count = L.count;
             HIP_TRY(c, launch_node_extents(ea, L.max_col_tiles, K, s));
+            HIP_TRY(c, launch_node_bounds(ea, L.max_col_tiles, K, s));
         }
+    }
+    if (c->d_jr) {                           // the K ranges of every K2 op, for the planner and for K2
+        RangeArgs ra{};
+        ra.ops = ds.d_gemm_ops; ra.n_ops = (int)c->h_gemm_ops.size();
+        ra.aext = c->kpool.ext; ra.ext_blocks = c->kpool.ext_blocks;
+        ra.a16 = mag ? c->d_mag_a16 : nullptr;
+        ra.n_ksteps = c->n_ksteps; ra.n_rsteps = c->n_rsteps; ra.k_valid = c->M + 1;
+        HIP_TRY(c, launch_joint_ranges(ra, std::max(1, c->jr_max_tiles), K, s));
     }
 
     const bool leaf_t = c->d_lt && !use_err;

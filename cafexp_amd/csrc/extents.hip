@@ -75,6 +75,248 @@ hipError_t launch_node_extents(const ExtArgs& a, int max_col_tiles, int n_catego
     return hipGetLastError();
 }
 
+// ---- Magnitudes: K steps whose products underflow below the smallest denormal.
+// The extents above leave out a product only when one factor is exactly zero.  A product of two non-zero factors below
+// 2^-1075 has no effect either: all operands are non-negative, an accumulator that is 0 stays 0 and one that is not is at
+// least 2^-1074 and does not move under round-to-nearest, whether the MFMA fuses its four products, chains them or rounds
+// each one.  Three steps, all per call: (1) tables of the largest entries of this call's matrices, one pass over the pools;
+// (2) upper bounds of the panels, propagated with the intervals, level by level; (3) per (op, category, column tile,
+// 16-row block) the k-steps that can still matter, cut out of the exact interval.
+
+// upper bound of log2(v) in 1/256, v >= 0
+__device__ inline int32_t mag_of(double v) {
+    if (!(v > 0.0)) return kMagNone;
+    int e;
+    const double m = frexp(v, &e);                         // v = m 2^e, m in [0.5, 1)
+    return e * kMagUnit + (int32_t)ceilf(log2f((float)m) * (float)kMagUnit) + 1;
+}
+
+// one workgroup per (k-step, k-major slot): the four matrix rows c = 4 ks .. 4 ks + 3 over all parent sizes
+__global__ __launch_bounds__(256) void mag_kmajor_kernel(const MagArgs a) {
+    __shared__ double s_max[2048], s_sum[2048];
+    const int ks = blockIdx.x, slot = blockIdx.y, tid = threadIdx.x;
+    const int ncol = min(a.kpool.n - 1, 2048);             // parent sizes 1 .. n - 1 are columns 0 .. n - 2
+    const double* P = a.kpool.base + (int64_t)slot * a.kpool.stride + (int64_t)ks * 4 * a.kpool.ld;
+    for (int j = tid; j < ncol; j += 256) {
+        double mx = 0.0, sm = 0.0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const double v = ks * 4 + c < a.kpool.k_valid ? P[(int64_t)c * a.kpool.ld + j] : 0.0;
+            mx = fmax(mx, v); sm += v;
+        }
+        s_max[j] = mx; s_sum[j] = sm;
+    }
+    __syncthreads();
+    const int nb = a.kpool.ext_blocks;
+    for (int b = tid; b < nb; b += 256) {
+        double mx = 0.0;
+        for (int j = 16 * b; j < 16 * b + 16 && j < ncol; ++j) mx = fmax(mx, s_max[j]);
+        a.a16[((int64_t)slot * a.n_ksteps + ks) * nb + b] = mag_of(mx);
+    }
+    for (int r = tid; r < a.n_rsteps; r += 256) {
+        double mx = (r == 0 && ks == 0) ? 1.0 : 0.0;       // parent size 0: P[0][c] = delta(c, 0)
+        for (int s = max(4 * r, 1); s < 4 * r + 4 && s - 1 < ncol; ++s) mx = fmax(mx, s_sum[s - 1]);
+        a.t4[((int64_t)slot * a.n_ksteps + ks) * a.n_rsteps + r] = mag_of(mx);
+    }
+}
+
+// one workgroup per (row step, row-major slot): rows s = 4 r .. 4 r + 3 over the counts x <= M
+__global__ __launch_bounds__(256) void mag_leaf_kernel(const MagArgs a) {
+    const int r = blockIdx.x, slot = blockIdx.y;
+    const double* P = a.lpool.base + (int64_t)slot * a.lpool.stride;
+    for (int x = threadIdx.x; x <= a.M && x < a.lpool.n; x += 256) {
+        double mx = (r == 0 && x == 0) ? 1.0 : 0.0;
+        for (int s = 4 * r; s < 4 * r + 4 && s < a.lpool.n; ++s) mx = fmax(mx, P[(int64_t)s * a.lpool.ld + x]);
+        a.lt[((int64_t)slot * (a.M + 1) + x) * a.n_rsteps + r] = mag_of(mx);
+    }
+}
+
+hipError_t launch_magnitude_tables(const MagArgs& a, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (a.n_kslots > 0) hipLaunchKernelGGL(mag_kmajor_kernel, dim3(a.n_ksteps, a.n_kslots), dim3(256), 0, stream, a);
+    if (a.n_lslots > 0) hipLaunchKernelGGL(mag_leaf_kernel, dim3(a.n_rsteps, a.n_lslots), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+// Upper bounds of a node's panel per (category, 128-column tile, step of 4 rows), after the node's extents (it reads the
+// tile's hull) and its children's bounds.  They must dominate the COMPUTED values, not the exact ones:
+//   leaf factor      max of the leaf's table over the counts that occur in the tile;
+//   interior factor  log2 sum_ks 2^(t4[ks][r] + child bound[ks]), the child bound taken over the child tiles that the tile's
+//                    columns map to: sum_c P[s][c] L[c][f] <= sum_ks (sum_{c in ks} P[s][c]) max_{c in ks} L[c][f];
+//   node             the sum over its factors + kMagSlack, never below kMagFloor inside the exact extent: what the roundings
+//                    of the sums and products add is a factor (1 + 2^-53)^n and, in the denormal range, at most 2^-1075 per
+//                    operation -- under 2^-1063 in all, which a bound of at least 2^-1050 swallows within the slack.
+// The loops over counts, child tiles and k-steps read tables far larger than the caches: each batches kBoundBatch independent
+// loads in front of the arithmetic (one after the other they cost a memory round trip per item: 7.3 ms per bench call).
+constexpr int kBoundThreads = 256, kBoundBatch = 16;
+__global__ __launch_bounds__(kBoundThreads) void node_bound_kernel(const ExtArgs a) {
+    const ExtNode& nd = a.nodes[a.first + blockIdx.z];
+    if (blockIdx.x * kBN >= nd.cols) return;
+    const int k = blockIdx.y, ct = blockIdx.x, tid = threadIdx.x, col = ct * kBN + (tid & (kBN - 1));
+    const int nr = a.n_rsteps, nk = a.n_ksteps, nct = nd.cols / kBN;
+    __shared__ int32_t s_acc[kMaxSteps], s_cb[kMaxSteps];
+    __shared__ int s_list[kBN];                            // the distinct counts / child tiles of the tile's columns
+    __shared__ unsigned s_bits[kMaxSteps / 8];             // counts 0 .. 2047
+    __shared__ int s_n, s_klo, s_khi;
+    for (int r = tid; r < nr; r += kBoundThreads) s_acc[r] = 0;
+    for (int l = 0; l < nd.n_leaf; ++l) {
+        __syncthreads();
+        if (tid < kMaxSteps / 8) s_bits[tid] = 0;
+        if (tid == 0) s_n = 0;
+        __syncthreads();
+        if (tid < kBN) {
+            const int x = nd.cnt[(int64_t)nd.leaf_row[l] * nd.cnt_ld + col];
+            if (!(atomicOr(&s_bits[x >> 5], 1u << (x & 31)) & (1u << (x & 31)))) s_list[atomicAdd(&s_n, 1)] = x;    // the first to set it
+        }
+        __syncthreads();
+        const int n = s_n;
+        const int32_t* lt = a.lt + (int64_t)(k * a.n_pairs_leaf + nd.leaf_pair[l]) * (a.M + 1) * nr;
+        for (int r = tid; r < nr; r += kBoundThreads) {
+            int32_t m = kMagNone;
+            for (int i0 = 0; i0 < n; i0 += kBoundBatch) {
+                int32_t v[kBoundBatch];
+#pragma unroll
+                for (int i = 0; i < kBoundBatch; ++i) v[i] = lt[(int64_t)s_list[min(i0 + i, n - 1)] * nr + r];
+#pragma unroll
+                for (int i = 0; i < kBoundBatch; ++i) m = max(m, v[i]);
+            }
+            s_acc[r] = (m == kMagNone || s_acc[r] == kMagNone) ? kMagNone : s_acc[r] + m;
+        }
+    }
+    for (int j = 0; j < nd.n_inner; ++j) {
+        __syncthreads();
+        if (tid < kMaxSteps / 8) s_bits[tid] = 0;
+        if (tid == 0) { s_n = 0; s_klo = nk; s_khi = -1; }
+        __syncthreads();
+        if (tid < kBN) {
+            const int t = (nd.inner_map[j] ? nd.inner_map[j][col] : col) / kBN;
+            // (tiles past the bitmap enter the list once per column: that costs loads and changes no maximum)
+            if (t >= kMaxSteps * 4 || !(atomicOr(&s_bits[t >> 5], 1u << (t & 31)) & (1u << (t & 31)))) s_list[atomicAdd(&s_n, 1)] = t;
+        }
+        __syncthreads();
+        const int n = s_n;
+        const int32_t* cb = nd.inner_bound[j] + (int64_t)k * (nd.inner_cols[j] / kBN) * nr;
+        for (int ks = tid; ks < nk; ks += kBoundThreads) {
+            int32_t m = kMagNone;
+            for (int i0 = 0; i0 < n; i0 += kBoundBatch) {
+                int32_t v[kBoundBatch];
+#pragma unroll
+                for (int i = 0; i < kBoundBatch; ++i) v[i] = cb[(int64_t)s_list[min(i0 + i, n - 1)] * nr + ks];
+#pragma unroll
+                for (int i = 0; i < kBoundBatch; ++i) m = max(m, v[i]);
+            }
+            s_cb[ks] = m;
+            if (m != kMagNone) { atomicMin(&s_klo, ks); atomicMax(&s_khi, ks); }
+        }
+        __syncthreads();
+        const int slot = k * a.n_pairs_inner + nd.inner_pair[j];
+        const int32_t* t4 = a.t4 + (int64_t)slot * nk * nr;
+        const int32_t* e = a.kext + (int64_t)slot * a.kext_blocks * 2;
+        for (int r = tid; r < nr; r += kBoundThreads) {
+            // the k-steps inside the child's support and inside the non-zero extents of the matrix blocks that hold the parent
+            // sizes 4 r .. 4 r + 3 (block b: sizes 16 b + 1 .. 16 b + 16; size 0 only reaches child size 0)
+            int klo = nk, khi = -1;
+            for (int b = max(4 * r - 1, 0) / 16; b <= (4 * r + 2) / 16 && b < a.kext_blocks; ++b)
+                if (e[2 * b + 1] >= e[2 * b]) { klo = min(klo, e[2 * b] / 4); khi = max(khi, e[2 * b + 1] / 4); }
+            if (r == 0) klo = 0, khi = max(khi, 0);
+            klo = max(klo, s_klo); khi = min(min(khi, s_khi), nk - 1);
+            int32_t top = kMagNone;                         // running maximum and sum_i 2^(v_i - top)
+            float sum = 0.f;
+            for (int k0 = klo; k0 <= khi; k0 += kBoundBatch) {
+                int32_t tv[kBoundBatch];
+#pragma unroll
+                for (int i = 0; i < kBoundBatch; ++i) tv[i] = t4[(int64_t)min(k0 + i, khi) * nr + r];
+#pragma unroll
+                for (int i = 0; i < kBoundBatch; ++i) {
+                    const int32_t cv = s_cb[min(k0 + i, khi)];
+                    if (k0 + i > khi || tv[i] == kMagNone || cv == kMagNone) continue;
+                    const int32_t v = tv[i] + cv;
+                    if (v > top) { sum = sum * exp2f((float)(top - v) * (1.f / kMagUnit)) + 1.f; top = v; }
+                    else sum += exp2f((float)(v - top) * (1.f / kMagUnit));
+                }
+            }
+            const int32_t f = top == kMagNone ? kMagNone : top + (int32_t)ceilf(log2f(sum) * (float)kMagUnit) + 1;
+            s_acc[r] = (f == kMagNone || s_acc[r] == kMagNone) ? kMagNone : s_acc[r] + f;
+        }
+    }
+    __syncthreads();
+    const int32_t* te = nd.tileext + ((int64_t)k * nct + ct) * 2;
+    const int lo = te[0], hi = te[1];
+    int32_t* out = nd.bound + ((int64_t)k * nct + ct) * nr;
+    for (int r = tid; r < nr; r += kBoundThreads)
+        out[r] = (hi >= lo && 4 * r + 3 >= lo && 4 * r <= hi) ? max(s_acc[r], kMagFloor) + kMagSlack : kMagNone;
+}
+
+hipError_t launch_node_bounds(const ExtArgs& a, int max_col_tiles, int n_categories, hipStream_t stream) {
+    if (a.count <= 0 || !a.t4) return hipSuccess;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(node_bound_kernel, dim3(max_col_tiles, n_categories, a.count), dim3(kBoundThreads), 0, stream, a);
+    return hipGetLastError();
+}
+
+// Joint K ranges (GemmOp::jr): lane = 16-row block of the op's matrix.  The exact interval is the block's matrix extent cut
+// by the panel's (an empty panel extent: row 0, so that the panel receives its zeros); with magnitude tables the interval
+// shrinks from both ends while (largest entry of the block in the k-step) x (bound of the panel's rows of the k-step) lies
+// below 2^-1100.  The ranges only ever shrink: no MFMA reads a panel row the assemble pass left unwritten.
+__global__ __launch_bounds__(256) void range_kernel(const RangeArgs a) {
+    const GemmOp& o = a.ops[blockIdx.z];
+    if (!o.jr || (int)blockIdx.x >= o.jr_nct) return;
+    const int ct = blockIdx.x, cat = blockIdx.y, b = threadIdx.x, nb = a.ext_blocks;
+    const bool mag = a.a16 && o.bbound;
+    __shared__ int32_t s_b[kMaxSteps];                      // the panel's bound per k-step
+    if (mag) {
+        const int32_t* B = o.bbound + ((int64_t)cat * o.jr_nct + ct) * a.n_rsteps;
+        for (int i = b; i < a.n_ksteps; i += 256) s_b[i] = B[i];
+        __syncthreads();
+    }
+    if (b >= nb + kRangePad) return;
+    int slo = 1, shi = 0;
+    if (b < nb) {
+        const int slot = o.slot[cat];
+        const int32_t* e = a.aext + ((int64_t)slot * nb + b) * 2;
+        int plo = 0, phi = a.k_valid - 1;
+        if (o.bext) {
+            const int32_t* be = o.bext + ((int64_t)cat * o.jr_nct + ct) * 2;
+            plo = be[0]; phi = min(be[1], phi);
+            if (be[1] < be[0]) { plo = 0; phi = 0; }
+        }
+        const int lo = max(e[0], plo), hi = min(e[1], phi);
+        if (hi >= lo) {
+            slo = lo / 4; shi = hi / 4;
+            if (mag) {
+                // four k-steps per look from either end (independent loads); a step counts when it may reach 2^-1100
+                const int32_t* A = a.a16 + (int64_t)slot * a.n_ksteps * nb + b;
+                const int first = slo, last = shi;
+                for (bool found = false; !found && slo <= last; ) {
+                    int32_t v[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) v[i] = A[(int64_t)min(slo + i, last) * nb];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (!found) { if (slo <= last && v[i] + s_b[slo] >= kSkipBelow) found = true; else ++slo; }
+                }
+                for (bool found = false; !found && shi >= slo; ) {
+                    int32_t v[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) v[i] = A[(int64_t)max(shi - i, first) * nb];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (!found) { if (shi >= slo && v[i] + s_b[shi] >= kSkipBelow) found = true; else --shi; }
+                }
+                if (slo > shi) { slo = 1; shi = 0; }
+            }
+        }
+    }
+    const_cast<int32_t*>(o.jr)[((int64_t)cat * o.jr_nct + ct) * (nb + kRangePad) + b] = slo | (shi << 16);
+}
+
+hipError_t launch_joint_ranges(const RangeArgs& a, int max_col_tiles, int n_categories, hipStream_t stream) {
+    if (a.n_ops <= 0 || !a.aext) return hipSuccess;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(range_kernel, dim3(max_col_tiles, n_categories, a.n_ops), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
 constexpr int kPlanTail = 2;
 // Tile lists of the K2 launches of a call (PlanLaunch, cafe_kernels.h): one wave per (XCD, launch), lane = workgroup.
 // Cost of a tile = its K tiles + PlanLaunch::fixed.  With the full grid (64 workgroups per XCD) workgroups j and j + 32 share
@@ -105,19 +347,20 @@ __device__ inline int2 plan_tile_entry(const PlanLaunch& L, const int* s_first, 
     const int ct = pair % nct, cat = pair / nct;
     int lo = 0, hi = L.k_valid - 1, zlo = 0;
     if (L.aext) {
-        const int b0 = row_tile * L.mi;
-        const int32_t* e = L.aext + ((int64_t)o.slot[cat] * L.ext_blocks + b0) * 2;
-        lo = 0x7fffffff; hi = -1;
-        for (int b = 0; b < L.mi; ++b)
-            if (b0 + b < L.ext_blocks) { lo = min(lo, e[2 * b]); hi = max(hi, e[2 * b + 1]); }
+        // the hull of the row blocks' joint ranges (range_kernel; entries past the matrix's last block say "none")
+        const int32_t* e = o.jr + ((int64_t)cat * o.jr_nct + (ct & o.jr_ct_mask)) * (L.ext_blocks + kRangePad) + row_tile * L.mi;
+        int slo = 0x7fff, shi = -1;
+        for (int b = 0; b < L.mi; ++b) {
+            const int l = e[b] & 0xFFFF, h = e[b] >> 16;
+            if (h >= l) { slo = min(slo, l); shi = max(shi, h); }
+        }
+        lo = slo * 4; hi = shi * 4 + 3;
         if (o.bext) {
             // (rows of B outside its tile extent may never have been written: the assemble pass leaves them out, leaf_reduce.hip)
             const int32_t* be = o.bext + ((int64_t)cat * nct + ct) * 2;
-            lo = max(lo, be[0]);
-            hi = min(hi, be[1]);
             if (be[1] >= be[0]) zlo = be[0];
         }
-        if (hi < lo) { lo = zlo; hi = zlo; }               // an all-zero tile still runs one K tile: the panel must receive its zeros
+        if (shi < slo) { lo = zlo; hi = zlo; }             // an all-zero tile still runs one K tile: the panel must receive its zeros
         hi = min(hi, L.k_valid - 1);
     }
     return make_int2((op << 24) | tl, ((lo / L.kb) << 16) | (hi / L.kb - lo / L.kb + 1));

@@ -227,36 +227,28 @@ __global__ __launch_bounds__(256, prune_gemm_wg_per_cu(MI, KB)) void prune_gemm_
     };
 
     // Which of the tile's MI row blocks take part in k-step ks (4 deep, counted from the first one of the tile's range): block i
-    // only where k lies inside ITS OWN matrix extent and inside the panel's extent (the tile's range is the hull of those, in
-    // whole K tiles).  The band of a transition matrix moves down by 16 rows per block, so the first k-steps of a range meet
-    // only the upper blocks and the last ones only the lower blocks -- a tenth of the MFMAs of a config-4 call multiply a zero
-    // block of A; leaving them out changes no accumulator bit.  The same rule at every depth of a K tile, so the MFMAs issued
-    // do not depend on it; and no MFMA reads a panel row outside the panel's extent rounded to k-steps -- rows the assemble pass
-    // may have left unwritten (it writes the extent rounded to 16 rows, which 12-deep K tiles overhang).  All scalar.
+    // only inside ITS OWN joint range (GemmOp::jr, extents.hip: the block's matrix extent cut by the panel's, and by the k-steps
+    // whose products all lie below 2^-1100; the tile's range is the hull of those, in whole K tiles).  The band of a
+    // transition matrix moves down by 16 rows per block, so the first k-steps of a range meet only the upper blocks and the
+    // last ones only the lower blocks; leaving the others out changes no accumulator bit.  The same rule at every depth of a K
+    // tile, so the MFMAs issued do not depend on it; and no MFMA reads a panel row outside the panel's extent rounded to
+    // k-steps -- rows the assemble pass may have left unwritten (it writes the extent rounded to 16 rows, which 12-deep K
+    // tiles overhang).  All scalar: MI consecutive words of the table.
     typedef const __attribute__((address_space(4))) int32_t* ext_cptr_t;
     struct Blocks { int lo[MI], hi[MI]; };                  // k-steps relative to the tile's first one; lo > hi: never
     auto block_ranges = [&](const Tile& x) -> Blocks {
         Blocks b;
-        if (!a.pool.ext) {
+        if (!x.o->jr) {
 #pragma unroll
             for (int i = 0; i < MI; ++i) { b.lo[i] = 0; b.hi[i] = 0x7fff; }
             return b;
         }
-        int plo = 0, phi = a.k_valid - 1;
-        if (x.o->bext) {                                    // the panel's extent, as the planner read it (empty: row 0, extents.hip)
-            const ext_cptr_t be = (ext_cptr_t)(unsigned long long)(x.o->bext + ((int64_t)x.cat * (x.ldb / kBN) + x.col0 / kBN) * 2);
-            plo = be[0];
-            phi = min(be[1], phi);
-            if (be[1] < be[0]) { plo = 0; phi = 0; }
-        }
-        const ext_cptr_t e = (ext_cptr_t)(unsigned long long)(a.pool.ext + ((int64_t)x.o->slot[x.cat] * a.pool.ext_blocks + x.row_tile * MI) * 2);
+        const ext_cptr_t e = (ext_cptr_t)(unsigned long long)(x.o->jr + ((int64_t)x.cat * x.o->jr_nct + ((x.col0 / kBN) & x.o->jr_ct_mask)) * (a.pool.ext_blocks + kRangePad) + x.row_tile * MI);
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
-            int lo = 1, hi = 0;
-            if (x.row_tile * MI + i < a.pool.ext_blocks) { lo = max(e[2 * i], plo); hi = min(e[2 * i + 1], phi); }
-            const bool some = hi >= lo;
-            b.lo[i] = some ? lo / 4 - x.kt0 * NS : 1;
-            b.hi[i] = some ? hi / 4 - x.kt0 * NS : 0;
+            const int v = e[i];
+            b.lo[i] = (v & 0xFFFF) - x.kt0 * NS;
+            b.hi[i] = (v >> 16) - x.kt0 * NS;
         }
         return b;
     };

@@ -608,6 +608,16 @@ int cafe_get_extents(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* mat
 /* diagnostic: the per-COLUMN zero extents of an interior non-root node's panel in the last call, out[columns][2] (rows outside
  * [lo, hi] of a column are exactly zero; lo > hi: the whole column); *n_cols receives the panel's (padded) column count */
 int cafe_debug_column_extents(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* out, size_t out_len, int64_t* n_cols);
+/* diagnostic: the magnitude bounds of an interior non-root node's panel in the last call (extents.hip, node_bound_kernel):
+ * out[tile * *row_steps + r] is an upper bound of log2 of every COMPUTED entry of panel rows 4 r .. 4 r + 3 in 128-column tile
+ * `tile`, -inf where they are all exactly zero, never below -1060 otherwise.  out == NULL: the two sizes only.  CAFE_ERR_STATE
+ * when the last call kept none (CAFE_NO_MAGSKIP, CAFE_NO_KSKIP, matrix order below 256, an error model). */
+int cafe_debug_panel_bounds(cafe_ctx* ctx, int32_t node, int32_t category, double* out, size_t out_len, int32_t* n_tiles, int32_t* row_steps);
+/* diagnostic: the K ranges of the K2 op that multiplies the matrix of the branch above `node` (interior, not the root) in the
+ * last call: out[(tile * *n_blocks + b) * 2 + {0, 1}] = first / last k-step (4 deep) that 16-row block b of the matrix runs
+ * against column tile `tile` of the node's panel (first > last: none).  The block's non-zero extent cut by the panel's and,
+ * unless CAFE_NO_MAGSKIP is set, by the k-steps whose products all lie below 2^-1100.  out == NULL: the two sizes only. */
+int cafe_debug_k_ranges(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* out, size_t out_len, int32_t* n_tiles, int32_t* n_blocks);
 /* diagnostic: leaf branches whose matrix the context keeps a transposed copy of (leaf_reduce.hip, leaf_transpose_kernel: a
  * leaf that meets an interior sibling's factor in an assemble pass), and whether the last call used the copies (it does not
  * when it carries an error model) */
@@ -618,6 +628,13 @@ int cafe_get_stats(const cafe_ctx* ctx, cafe_stats* stats);
  * only the ones inside its own extent -- the products left out all have an exact zero in them.  Reads the extents back and counts on the host (milliseconds): measurement only.  Needs a call that
  * was enqueued launch by launch (no graph replay). */
 int cafe_executed_flops(cafe_ctx* ctx, double* flops);
+/* Flops of the MFMAs the K2 launches of the last call ISSUED.  cafe_executed_flops counts the products that have no exact
+ * zero in them -- what the kernel issues under CAFE_NO_MAGSKIP=1.  By default a row block's K range is shorter still by the
+ * k-steps at its ends whose products all lie below half the smallest denormal (cafe_debug_k_ranges): the same result bits,
+ * fewer MFMAs, and this is their count (<= cafe_executed_flops, equal under CAFE_NO_MAGSKIP=1 or with an error model).  Over
+ * a launch's time it is the rate of the matrix pipe; cafe_executed_flops over the same time is the rate at which the
+ * non-zero products are dealt with, which may exceed the pipe's peak.  Same conditions as cafe_executed_flops. */
+int cafe_issued_flops(cafe_ctx* ctx, double* flops);
 /* diagnostic: the same count with every 16-row block of a tile taken over the tile's WHOLE K range (the hull of its blocks'
  * ranges) -- what the kernel issued until each block got its own range (prune_gemm.hip, block_ranges), and what rounds 2 and
  * 3a quoted their roofline fractions on; >= cafe_executed_flops */
