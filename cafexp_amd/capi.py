@@ -120,9 +120,11 @@ EXPORTS = [
     "cafe_set_death_rates", "cafe_bd_rates", "cafe_build_matrices_lm", "cafe_score_per_family_lm", "cafe_simulate_lm",
     "cafe_score_gradient", "cafe_bd_rates_grad", "cafe_expected_events", "cafe_bd_rates_events",
     "cafe_branch_scores", "cafe_branch_scores_dim", "cafe_weighted_gram", "cafe_debug_gram",
-    "cafe_leaf_predictive", "cafe_set_root_rule", "cafe_get_root_rule", "cafe_root_posterior",
+    "cafe_leaf_predictive", "cafe_set_root_rule", "cafe_get_root_rule", "cafe_root_posterior", "cafe_debug_magnitude_tables", "cafe_debug_level_tiles",
 ]
 CAFE_COMM_ID_BYTES = 128
+MAG_NONE = -(1 << 28)           # a magnitude-table entry whose items are all exactly zero (cafe_kernels.h, kMagNone)
+MAG_UNIT = 256                  # table units per power of two
 
 _lib = None
 
@@ -721,6 +723,28 @@ class Context:
         self._check(f(self._h, node, category, None, 0, C.byref(nt), C.byref(nr)))
         out = np.zeros((nt.value, nr.value), dtype=np.float64)
         self._check(f(self._h, node, category, _p(out, _f64p), out.size, C.byref(nt), C.byref(nr)))
+        return out
+
+    def set_level_tiles(self, tiles: int) -> None:
+        """Column tiles per workgroup of the per-level interval / bound kernel in the following calls: 1, 2 or 4, 0 = chosen per
+        level (cafe_debug_level_tiles).  Diagnostic: nothing the library returns depends on it."""
+        self._lib.cafe_debug_level_tiles.restype = C.c_int
+        self._lib.cafe_debug_level_tiles.argtypes = [C.c_void_p, C.c_int]
+        self._check(self._lib.cafe_debug_level_tiles(self._h, tiles))
+
+    def magnitude_tables(self, which: str, node: int, category: int = 0) -> np.ndarray:
+        """One magnitude table of the matrix of the branch above `node` in the last call, as the device wrote it (int32, units
+        of 1/256 of log2, MAG_NONE where everything the entry stands for is zero): "a16" [k-steps][16-row blocks] and "t4"
+        [k-steps][row steps] of an interior branch, "lt" [counts 0 .. M][row steps] of a leaf branch
+        (cafe_debug_magnitude_tables)."""
+        f = self._lib.cafe_debug_magnitude_tables
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _i32p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32]
+        w = {"a16": 0, "t4": 1, "lt": 2}[which]
+        n0, n1 = C.c_int32(), C.c_int32()
+        self._check(f(self._h, w, -1, None, 0, C.byref(n0), C.byref(n1), node, category))
+        out = np.zeros((n0.value, n1.value), dtype=np.int32)
+        self._check(f(self._h, w, -1, _p(out, _i32p), out.size, C.byref(n0), C.byref(n1), node, category))
         return out
 
     def k_ranges(self, node: int, category: int = 0) -> np.ndarray:

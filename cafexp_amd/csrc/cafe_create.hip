@@ -150,7 +150,7 @@ int load_problem(cafe_ctx* c, const cafe_problem* p, std::vector<int64_t>& uniq)
     c->F_uniq = (int64_t)uniq.size();
     c->Fp = round_up64(c->F_uniq, kBN);
     // Columns in order of the families' largest count: a likelihood column is exactly zero far from the observed sizes
-    // (node_extent_kernel), K2 skips the all-zero rows of a 128-column tile of its B operand, and a tile of families of
+    // (node_level_kernel), K2 skips the all-zero rows of a 128-column tile of its B operand, and a tile of families of
     // similar size has many of them.  Internal order only: ref_of maps every family of the table to its column.
     if (!device_counts) {
         std::vector<int32_t> key(c->F_uniq);

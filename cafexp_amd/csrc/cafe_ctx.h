@@ -261,6 +261,7 @@ struct cafe_ctx {
     std::vector<GemmLaunch> gemm_launches_info;
     bool stats_flops_stale = false;           // gemm_flops still holds the dense count of the last profiled call
     int profile = 0;
+    int force_level_tiles = 0;               // diagnostic: column tiles per workgroup of node_level_kernel (0 = chosen per level)
     int force_mi = 0;                        // diagnostic: K2 row-tile height for every launch (0 = chosen per launch)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     std::vector<hipEvent_t> gemm_ev;

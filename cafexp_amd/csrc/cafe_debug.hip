@@ -130,6 +130,12 @@ int cafe_debug_force_tile(cafe_ctx* ctx, int mi) {
     return CAFE_OK;
 }
 
+int cafe_debug_level_tiles(cafe_ctx* ctx, int tiles) {
+    if (!ctx || (tiles != 0 && tiles != 1 && tiles != 2 && tiles != 4)) return CAFE_ERR_ARGUMENT;
+    ctx->force_level_tiles = tiles;
+    return CAFE_OK;
+}
+
 int cafe_get_extents(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* matrix_ext, size_t matrix_ext_len,
                      int32_t* panel_ext, size_t panel_ext_len, int32_t* n_tiles) {
     if (!ctx) return CAFE_ERR_ARGUMENT;
@@ -179,7 +185,7 @@ int cafe_debug_column_extents(cafe_ctx* ctx, int32_t node, int32_t category, int
     return CAFE_OK;
 }
 
-// Upper bounds of a node's panel (node_bound_kernel): out[tile * row_steps + r] = bound of log2 of every computed entry of
+// Upper bounds of a node's panel (node_level_kernel): out[tile * row_steps + r] = bound of log2 of every computed entry of
 // rows 4 r .. 4 r + 3 in 128-column tile `tile` of `category`; -inf where all of them are exactly zero.
 int cafe_debug_panel_bounds(cafe_ctx* ctx, int32_t node, int32_t category, double* out, size_t out_len, int32_t* n_tiles, int32_t* row_steps) {
     if (!ctx) return CAFE_ERR_ARGUMENT;
@@ -195,6 +201,39 @@ int cafe_debug_panel_bounds(cafe_ctx* ctx, int32_t node, int32_t category, doubl
     std::vector<int32_t> q((size_t)nt * nr);
     HIP_TRY(ctx, hipMemcpy(q.data(), ctx->d_bound[node] + (size_t)category * nt * nr, q.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < q.size(); ++i) out[i] = q[i] == kMagNone ? -HUGE_VAL : (double)q[i] / kMagUnit;
+    return CAFE_OK;
+}
+
+// The magnitude tables of the last call's matrices (mag_tables_kernel), one slot's, as the kernel wrote them (units of 1/256,
+// kMagNone where every entry is zero): which 0 = a16 [k-steps][16-row blocks], 1 = t4 [k-steps][row steps] (k-major slots),
+// 2 = lt [counts 0 .. M][row steps] (row-major slots).  slot < 0: the slot of the branch above `node` in `category`.
+int cafe_debug_magnitude_tables(cafe_ctx* ctx, int32_t which, int32_t slot, int32_t* out, size_t out_len, int32_t* n0, int32_t* n1,
+                                int32_t node, int32_t category) {
+    if (!ctx) return CAFE_ERR_ARGUMENT;
+    if (!ctx->have_results || ctx->last_rejected) { set_err(ctx, "cafe_debug_magnitude_tables: no completed call"); return CAFE_ERR_STATE; }
+    if (which < 0 || which > 2) { set_err(ctx, "cafe_debug_magnitude_tables: which must be 0 (a16), 1 (t4) or 2 (lt)"); return CAFE_ERR_ARGUMENT; }
+    if (!ctx->magskip_last || !ctx->d_mag_a16 || !ctx->d_mag_t4 || !ctx->d_mag_lt) {
+        set_err(ctx, "cafe_debug_magnitude_tables: the last call kept no tables");
+        return CAFE_ERR_STATE;
+    }
+    const bool leaf_table = which == 2;
+    if (slot < 0) {
+        if (node < 0 || node >= ctx->n_nodes || node == ctx->root || category < 0 || category >= ctx->K_last ||
+            (ctx->leaf_taxon[node] >= 0) != leaf_table) {
+            set_err(ctx, "cafe_debug_magnitude_tables: node/category out of range for this table");
+            return CAFE_ERR_ARGUMENT;
+        }
+        slot = ctx->slot_of[(size_t)node * ctx->Kmax + category];
+    }
+    if (slot < 0 || slot >= (leaf_table ? ctx->n_slots_last : ctx->n_kslots_last)) { set_err(ctx, "cafe_debug_magnitude_tables: slot out of range"); return CAFE_ERR_ARGUMENT; }
+    const int d0 = leaf_table ? ctx->M + 1 : ctx->n_ksteps, d1 = which == 0 ? ctx->kpool.ext_blocks : ctx->n_rsteps;
+    if (n0) *n0 = d0;
+    if (n1) *n1 = d1;
+    if (!out) return CAFE_OK;
+    if (out_len < (size_t)d0 * d1) { set_err(ctx, "cafe_debug_magnitude_tables: out too small"); return CAFE_ERR_ARGUMENT; }
+    if (const int rc = wait_last_call(ctx)) return rc;
+    const int32_t* src = which == 0 ? ctx->d_mag_a16 : which == 1 ? ctx->d_mag_t4 : ctx->d_mag_lt;
+    HIP_TRY(ctx, hipMemcpy(out, src + (size_t)slot * d0 * d1, sizeof(int32_t) * (size_t)d0 * d1, hipMemcpyDeviceToHost));
     return CAFE_OK;
 }
 

@@ -179,7 +179,7 @@ struct GemmOp {
     // hull of its blocks' ranges; K2 reads its MI ranges from here.
     const int32_t* jr;
     int32_t jr_nct, jr_ct_mask;
-    // upper bounds of the child panel's magnitudes (node_bound_kernel): [category][column tile][row steps], or nullptr
+    // upper bounds of the child panel's magnitudes (node_level_kernel): [category][column tile][row steps], or nullptr
     const int32_t* bbound;
 };
 constexpr int kRangePad = 8;        // blocks a row tile may overhang the matrix's last one (MI - 1): entries past it say "none"
@@ -303,7 +303,7 @@ struct ExtNode {
     const int32_t* inner_colext[kMaxExtChildren];   // the child's per-column extents [category][its columns][2]
     int32_t* colext;                         // [category][cols][2]: rows outside [lo, hi] of a column are exactly zero
     int32_t* tileext;                        // [category][cols / 128][2]: hull over a 128-column tile (K2's B operand)
-    // magnitude bounds (node_bound_kernel): [category][cols / 128][row steps] per 128-column tile and step of 4 panel rows,
+    // magnitude bounds (node_level_kernel): [category][cols / 128][row steps] per 128-column tile and step of 4 panel rows,
     // an upper bound of log2 of every COMPUTED entry, in 1/256 (kMagNone: all exactly zero); the interior children's likewise
     int32_t* bound;
     const int32_t* inner_bound[kMaxExtChildren];
@@ -322,11 +322,14 @@ struct ExtArgs {
     const int32_t* t4;
     const int32_t* lt;
     int32_t n_rsteps, n_ksteps;
+    int32_t n_cu;                            // compute units of the device: sizes the tiles a workgroup owns
+    int32_t level_tiles;                     // diagnostic (cafe_debug_level_tiles): column tiles per workgroup, 0 = chosen per level
 };
-hipError_t launch_node_extents(const ExtArgs& a, int max_col_tiles, int n_categories, hipStream_t stream);
+// one launch per tree level: the intervals of the level's nodes and, with magnitude tables, the bounds of their panels
+hipError_t launch_node_level(const ExtArgs& a, int max_col_tiles, int n_categories, hipStream_t stream);
 
 // Magnitudes (extents.hip).  A product P[s][k] L[k][f] of two non-zero factors below half the smallest denormal moves no
-// accumulator either: the tables below bound log2 of the matrix entries, node_bound_kernel propagates bounds of the panels
+// accumulator either: the tables below bound log2 of the matrix entries, node_level_kernel propagates bounds of the panels
 // up the tree, and range_kernel cuts a block's K range to the k-steps where (matrix bound + panel bound) >= kSkipBelow.
 // All bounds are upper bounds of log2 in units of 1/256, rounded up.
 constexpr int32_t kMagUnit = 256;
@@ -347,7 +350,6 @@ struct MagArgs {
     int32_t* lt;                     // [row-major slot][count x <= M][row step]: largest P[s][x] over the step's sizes
 };
 hipError_t launch_magnitude_tables(const MagArgs& a, hipStream_t stream);
-hipError_t launch_node_bounds(const ExtArgs& a, int max_col_tiles, int n_categories, hipStream_t stream);
 struct RangeArgs {
     const GemmOp* ops;
     int32_t n_ops;

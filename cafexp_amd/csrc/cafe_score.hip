@@ -331,14 +331,14 @@ int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool 
         ExtArgs ea{};
         ea.t4 = mag ? c->d_mag_t4 : nullptr; ea.lt = c->d_mag_lt; ea.n_rsteps = c->n_rsteps; ea.n_ksteps = c->n_ksteps;
         ea.nodes = c->d_ext_nodes;
+        ea.n_cu = c->n_cu; ea.level_tiles = c->force_level_tiles;
         ea.leaf_ext = c->pool.ext; ea.leaf_ext_blocks = c->pool.ext_blocks; ea.n_pairs_leaf = c->n_pairs[0];
         ea.kext = c->kpool.ext; ea.kext_blocks = c->kpool.ext_blocks; ea.n_pairs_inner = c->n_pairs[1];
         ea.M = c->M;
         ea.err = use_err ? c->d_err : nullptr; ea.n_dev = use_err ? c->n_dev : 0;
         for (const auto& L : c->ext_levels) {
             ea.first = L.first; ea.count = L.count;
-            HIP_TRY(c, launch_node_extents(ea, L.max_col_tiles, K, s));
-            HIP_TRY(c, launch_node_bounds(ea, L.max_col_tiles, K, s));
+            HIP_TRY(c, launch_node_level(ea, L.max_col_tiles, K, s));
         }
     }
     if (c->d_jr) {                           // the K ranges of every K2 op, for the planner and for K2
@@ -501,7 +501,7 @@ int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bo
         if (use_err) std::memcpy(c->h_stage + ((char*)c->d_err - c->d_params), pr->error_model, sizeof(double) * (size_t)(c->M + 1) * c->n_dev);
     }
 
-    const bool graph_ok = c->use_graph && !c->profile && !c->d_stamps && c->force_mi == 0 && !c->root_posterior;
+    const bool graph_ok = c->use_graph && !c->profile && !c->d_stamps && c->force_mi == 0 && c->force_level_tiles == 0 && !c->root_posterior;
     if (!graph_ok) {
         const int rc = record_call(c, c->desc, K, gamma, rootmax, rootsum, use_err, d_out, s, c->profile != 0, false);
         if (rc != CAFE_OK) return rc;

@@ -16,11 +16,15 @@
 
 namespace cafe {
 
-__global__ __launch_bounds__(kBN) void node_extent_kernel(const ExtArgs a) {
-    const ExtNode& nd = a.nodes[a.first + blockIdx.z];
-    const int col = blockIdx.x * kBN + threadIdx.x;
-    if (blockIdx.x * kBN >= nd.cols) return;               // (levels are launched as wide as their widest node)
-    const int k = blockIdx.y;
+// the interval of one panel column (node_level_kernel below runs it per column and reduces a tile's hull).  kext: the extents
+// of the interior children's matrices, staged in LDS by the caller -- every column walks all their blocks, and from global
+// memory each step of that walk is a dependent load.  mono[j]: first and last child size of child j's matrix do not decrease
+// from block to block (a band: the caller checks it) -- the blocks that meet a child interval are then the run between
+// the first block whose last size reaches the interval and the last block whose first size does, found by two binary
+// searches instead of the walk; the same blocks, so the same interval.  Any other matrix takes the walk.
+constexpr int kMaxExtBlocks = 128;                         // blocks of 16 parent sizes of the largest matrix order (2048)
+__device__ inline int2 column_interval(const ExtArgs& a, const ExtNode& nd, int k, int col, const int32_t (*kext)[2 * kMaxExtBlocks],
+                                       const int* mono) {
     int lo = 0, hi = a.M;
     const int half = a.n_dev > 0 ? (a.n_dev - 1) / 2 : 0;
     for (int l = 0; l < nd.n_leaf; ++l) {
@@ -46,33 +50,24 @@ __global__ __launch_bounds__(kBN) void node_extent_kernel(const ExtArgs a) {
         if (chi >= clo) {
             // parent sizes s = 16 b + 1 .. 16 b + 16 (panel rows s) of block b have non-zero matrix entries for the child
             // sizes [e[2b], e[2b+1]]; size 0 only reaches child size 0 (P[0][c] = delta(c, 0))
-            const int32_t* e = a.kext + (int64_t)(k * a.n_pairs_inner + nd.inner_pair[j]) * a.kext_blocks * 2;
-            for (int b = 0; b < a.kext_blocks; ++b)
-                if (e[2 * b + 1] >= clo && e[2 * b] <= chi) { flo = min(flo, 16 * b + 1); fhi = max(fhi, 16 * b + 16); }
+            const int32_t* e = kext[j];
+            if (mono[j]) {
+                int b1 = 0, n1 = a.kext_blocks;            // first block with e[2b+1] >= clo (kext_blocks: none)
+                while (n1 > 0) { const int h = n1 >> 1; if (e[2 * (b1 + h) + 1] < clo) { b1 += h + 1; n1 -= h + 1; } else n1 = h; }
+                int b2 = 0, n2 = a.kext_blocks;            // first block with e[2b] > chi; the one before it is the last that starts inside
+                while (n2 > 0) { const int h = n2 >> 1; if (e[2 * (b2 + h)] <= chi) { b2 += h + 1; n2 -= h + 1; } else n2 = h; }
+                if (b1 < b2) { flo = 16 * b1 + 1; fhi = 16 * (b2 - 1) + 16; }
+            } else {
+                for (int b = 0; b < a.kext_blocks; ++b)
+                    if (e[2 * b + 1] >= clo && e[2 * b] <= chi) { flo = min(flo, 16 * b + 1); fhi = max(fhi, 16 * b + 16); }
+            }
             if (clo == 0) { flo = 0; fhi = max(fhi, 0); }
             fhi = min(fhi, a.M);
         }
         lo = max(lo, flo); hi = min(hi, fhi);
     }
     if (hi < lo) { lo = 0x7fffffff; hi = -1; }
-    int32_t* out = nd.colext + ((int64_t)k * nd.cols + col) * 2;
-    out[0] = lo; out[1] = hi;
-    // hull over the 128 columns of the tile
-    __shared__ int s_lo[2], s_hi[2];
-    for (int off = 32; off > 0; off >>= 1) { lo = min(lo, __shfl_down(lo, off)); hi = max(hi, __shfl_down(hi, off)); }
-    if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int32_t* t = nd.tileext + ((int64_t)k * (nd.cols / kBN) + blockIdx.x) * 2;
-        t[0] = min(s_lo[0], s_lo[1]); t[1] = max(s_hi[0], s_hi[1]);
-    }
-}
-
-hipError_t launch_node_extents(const ExtArgs& a, int max_col_tiles, int n_categories, hipStream_t stream) {
-    if (a.count <= 0) return hipSuccess;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(node_extent_kernel, dim3(max_col_tiles, n_categories, a.count), dim3(kBN), 0, stream, a);
-    return hipGetLastError();
+    return make_int2(lo, hi);
 }
 
 // ---- Magnitudes: K steps whose products underflow below the smallest denormal.
@@ -91,11 +86,54 @@ __device__ inline int32_t mag_of(double v) {
     return e * kMagUnit + (int32_t)ceilf(log2f((float)m) * (float)kMagUnit) + 1;
 }
 
-// one workgroup per (k-step, k-major slot): the four matrix rows c = 4 ks .. 4 ks + 3 over all parent sizes
-__global__ __launch_bounds__(256) void mag_kmajor_kernel(const MagArgs a) {
-    __shared__ double s_max[2048], s_sum[2048];
-    const int ks = blockIdx.x, slot = blockIdx.y, tid = threadIdx.x;
+// Both tables in one launch, the block index decides the role (block-uniform):
+//   leaf role     one workgroup per (32 row steps, 64 counts x, row-major slot): rows s = 4 r .. 4 r + 3 over the counts x <= M.
+//                 The table is [slot][x][r] -- its reader walks r -- while the matrix is read along x: the workgroup turns its
+//                 64 x 32 tile through LDS and stores 32 consecutive r per count (128-byte runs; one r per workgroup meant a
+//                 4-byte store per line);
+//   k-major role  one workgroup per (k-step, k-major slot): the four matrix rows c = 4 ks .. 4 ks + 3 over all parent sizes.
+// The leaf workgroups come first in the grid; the k-major ones follow and stream the larger pool behind them.
+constexpr int kLeafR = 32, kLeafX = 64, kLeafLd = kLeafR + 1;
+__global__ __launch_bounds__(256) void mag_tables_kernel(const MagArgs a, int leaf_blocks, int leaf_rb, int leaf_xb) {
+    extern __shared__ double s_dyn[];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x < leaf_blocks) {
+        int32_t* s_t = reinterpret_cast<int32_t*>(s_dyn);  // [kLeafX][kLeafLd]
+        int id = blockIdx.x;
+        const int rb = id % leaf_rb; id /= leaf_rb;
+        const int xb = id % leaf_xb, slot = id / leaf_xb;
+        const double* P = a.lpool.base + (int64_t)slot * a.lpool.stride;
+        const int xl = tid & (kLeafX - 1), x = xb * kLeafX + xl, w = tid / kLeafX;
+        const bool x_in = x <= a.M && x < a.lpool.n;
+        // all 32 loads of a lane first (rows past the matrix and counts past M: the entry at (0, 0) in their place, not used)
+        double v[kLeafR / 4][4];
+#pragma unroll
+        for (int i = 0; i < kLeafR / 4; ++i)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int s = 4 * (rb * kLeafR + w + 4 * i) + q;
+                v[i][q] = P[x_in && s < a.lpool.n ? (int64_t)s * a.lpool.ld + x : 0];
+            }
+#pragma unroll
+        for (int i = 0; i < kLeafR / 4; ++i) {
+            const int rl = w + 4 * i, r = rb * kLeafR + rl;
+            double mx = (r == 0 && x == 0) ? 1.0 : 0.0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (x_in && 4 * r + q < a.lpool.n) mx = fmax(mx, v[i][q]);
+            s_t[xl * kLeafLd + rl] = mag_of(mx);
+        }
+        __syncthreads();
+        for (int i = tid; i < kLeafX * kLeafR; i += 256) {
+            const int ox = i / kLeafR, rl = i % kLeafR, xx = xb * kLeafX + ox, r = rb * kLeafR + rl;
+            if (xx <= a.M && xx < a.lpool.n && r < a.n_rsteps) a.lt[((int64_t)slot * (a.M + 1) + xx) * a.n_rsteps + r] = s_t[ox * kLeafLd + rl];
+        }
+        return;
+    }
+    const int kid = blockIdx.x - leaf_blocks, ks = kid % a.n_ksteps, slot = kid / a.n_ksteps;
     const int ncol = min(a.kpool.n - 1, 2048);             // parent sizes 1 .. n - 1 are columns 0 .. n - 2
+    double* s_max = s_dyn;
+    double* s_sum = s_dyn + ncol;
     const double* P = a.kpool.base + (int64_t)slot * a.kpool.stride + (int64_t)ks * 4 * a.kpool.ld;
     for (int j = tid; j < ncol; j += 256) {
         double mx = 0.0, sm = 0.0;
@@ -120,21 +158,15 @@ __global__ __launch_bounds__(256) void mag_kmajor_kernel(const MagArgs a) {
     }
 }
 
-// one workgroup per (row step, row-major slot): rows s = 4 r .. 4 r + 3 over the counts x <= M
-__global__ __launch_bounds__(256) void mag_leaf_kernel(const MagArgs a) {
-    const int r = blockIdx.x, slot = blockIdx.y;
-    const double* P = a.lpool.base + (int64_t)slot * a.lpool.stride;
-    for (int x = threadIdx.x; x <= a.M && x < a.lpool.n; x += 256) {
-        double mx = (r == 0 && x == 0) ? 1.0 : 0.0;
-        for (int s = 4 * r; s < 4 * r + 4 && s < a.lpool.n; ++s) mx = fmax(mx, P[(int64_t)s * a.lpool.ld + x]);
-        a.lt[((int64_t)slot * (a.M + 1) + x) * a.n_rsteps + r] = mag_of(mx);
-    }
-}
-
 hipError_t launch_magnitude_tables(const MagArgs& a, hipStream_t stream) {
+    const int leaf_rb = (a.n_rsteps + kLeafR - 1) / kLeafR, leaf_xb = (a.M + 1 + kLeafX - 1) / kLeafX;
+    const int leaf_blocks = a.n_lslots > 0 ? leaf_rb * leaf_xb * a.n_lslots : 0;
+    const int k_blocks = a.n_kslots > 0 ? a.n_ksteps * a.n_kslots : 0;
+    if (leaf_blocks + k_blocks <= 0) return hipSuccess;
+    const int ncol = std::min(a.kpool.n - 1, 2048);
+    const size_t lds = std::max(sizeof(double) * 2 * (size_t)std::max(ncol, 0), sizeof(int32_t) * kLeafX * kLeafLd);
     (void)hipGetLastError();
-    if (a.n_kslots > 0) hipLaunchKernelGGL(mag_kmajor_kernel, dim3(a.n_ksteps, a.n_kslots), dim3(256), 0, stream, a);
-    if (a.n_lslots > 0) hipLaunchKernelGGL(mag_leaf_kernel, dim3(a.n_rsteps, a.n_lslots), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(mag_tables_kernel, dim3(leaf_blocks + k_blocks), dim3(256), lds, stream, a, leaf_blocks, leaf_rb, leaf_xb);
     return hipGetLastError();
 }
 
@@ -146,111 +178,266 @@ hipError_t launch_magnitude_tables(const MagArgs& a, hipStream_t stream) {
 //   node             the sum over its factors + kMagSlack, never below kMagFloor inside the exact extent: what the roundings
 //                    of the sums and products add is a factor (1 + 2^-53)^n and, in the denormal range, at most 2^-1075 per
 //                    operation -- under 2^-1063 in all, which a bound of at least 2^-1050 swallows within the slack.
-// The loops over counts, child tiles and k-steps read tables far larger than the caches: each batches kBoundBatch independent
-// loads in front of the arithmetic (one after the other they cost a memory round trip per item: 7.3 ms per bench call).
-constexpr int kBoundThreads = 256, kBoundBatch = 16;
-__global__ __launch_bounds__(kBoundThreads) void node_bound_kernel(const ExtArgs a) {
+// The interior factor's sum runs in float, spread over kLevelPhases waves (wave w: the k-steps ks = w mod kLevelPhases of a
+// row's range, ascending in batches of kBoundBatch, as a running maximum `top` and S = sum 2^((v - top) / 256), rescaled
+// once per batch) and combined in the fixed order w = 0, 1, ...: deterministic, no float atomics.  Every term is at most 1,
+// so against the exact sum S carries a relative error of at most (terms + rescales + combines) x (2^-24 of the addition or
+// multiplication + 2^-22 of the exponential) -- with up to 512 k-steps, counting a term and a rescale for each, under
+// 1030 x 1.25 x 2^-22 < 2^-11.6.  The sum is therefore scaled by (1 + 2^-11) before its logarithm is taken (in float: the factor
+// leaves 1.8e-4 of the sum, 0.067 of a unit, over; log2f of a sum of at most 512 is off by under 2e-6 and the product with
+// 256 by under 2e-4 of a unit) and rounded up to the unit: the factor's bound dominates the exact log2 sum
+// with no further unit added (the factor costs 0.18 of a unit; a unit per partial sum would cost one each, and the serial
+// float sum this replaces added one after its ceiling: the bounds come out a unit tighter per interior factor, not looser).
+// The loops over counts, child tiles and k-steps read tables far larger than the caches: each batches independent loads in
+// front of the arithmetic (kListBatch per list, kBoundBatch per wave and round of k-steps; one after the other they cost a
+// memory round trip per item: 7.3 ms per bench call).  A round is kLevelPhases x kBoundBatch = 16 k-steps: the rows' ranges
+// at the bench order are short, and every k-step of a round is computed whether the range holds it or not (rounds of 64:
+// 4.06 ms per bench call for the kernel, of 32: 3.5, of 16: 3.2).
+//
+// One launch per tree level: a workgroup owns up to kLevelTiles consecutive column tiles of one (node, category).  It first
+// runs the intervals of its columns (column_interval) and reduces each tile's hull, which stays in LDS; without magnitude
+// tables (ExtArgs::t4 null) it ends there.  Then the bounds, for the row steps inside the hulls only (outside they say
+// kMagNone): every t4 entry a lane loads serves all the workgroup's tiles, which differ only in their child-tile maxima.
+// A workgroup reads what earlier levels wrote and what it wrote itself, never another workgroup's output of its own level.
+constexpr int kLevelThreads = 256, kLevelTiles = 4, kLevelPhases = kLevelThreads / 64, kBoundBatch = 4, kListBatch = 16;
+static_assert(kLevelPhases == kLevelTiles && kLevelTiles == 4 && kLevelThreads == 2 * kBN,
+              "the combine step maps wave -> tile, s_cb holds the tiles of a k-step as an int4, the intervals run two tiles per pass");
+__global__ __launch_bounds__(kLevelThreads, 4) void node_level_kernel(const ExtArgs a, const int tiles_per_block) {
     const ExtNode& nd = a.nodes[a.first + blockIdx.z];
-    if (blockIdx.x * kBN >= nd.cols) return;
-    const int k = blockIdx.y, ct = blockIdx.x, tid = threadIdx.x, col = ct * kBN + (tid & (kBN - 1));
-    const int nr = a.n_rsteps, nk = a.n_ksteps, nct = nd.cols / kBN;
-    __shared__ int32_t s_acc[kMaxSteps], s_cb[kMaxSteps];
-    __shared__ int s_list[kBN];                            // the distinct counts / child tiles of the tile's columns
-    __shared__ unsigned s_bits[kMaxSteps / 8];             // counts 0 .. 2047
-    __shared__ int s_n, s_klo, s_khi;
-    for (int r = tid; r < nr; r += kBoundThreads) s_acc[r] = 0;
+    const int nct = nd.cols / kBN, ct0 = blockIdx.x * tiles_per_block;
+    if (ct0 >= nct) return;                                // (levels are launched as wide as their widest node; block-uniform)
+    const int nt = min(tiles_per_block, nct - ct0);        // <= kLevelTiles
+    const int k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nr = a.n_rsteps, nk = a.n_ksteps;
+    __shared__ int32_t s_acc[kLevelTiles][kMaxSteps];
+    __shared__ int4 s_cb[kMaxSteps];                        // the child's bound per k-step, the workgroup's four tiles side by side
+    __shared__ int s_list[kLevelTiles][kBN];               // the distinct counts / child tiles of a tile's columns
+    __shared__ unsigned s_bits[kLevelTiles][kMaxSteps / 8];    // counts 0 .. 2047
+    __shared__ int s_n[kLevelTiles], s_klo[kLevelTiles], s_khi[kLevelTiles];
+    __shared__ int s_wlo[2 * kLevelTiles], s_whi[2 * kLevelTiles], s_lo[kLevelTiles], s_hi[kLevelTiles], s_rlo[kLevelTiles], s_rhi[kLevelTiles];
+    __shared__ int32_t s_ptop[kLevelPhases][kLevelTiles][64];
+    __shared__ float s_psum[kLevelPhases][kLevelTiles][64];
+    __shared__ int32_t s_kext[kMaxExtChildren][2 * kMaxExtBlocks];     // the interior children's matrix extents (this category)
+    __shared__ int s_mono[kMaxExtChildren];                // the child's matrix extents do not decrease from block to block
+    if (tid < kMaxExtChildren) s_mono[tid] = 1;
+    __syncthreads();
+    for (int j = 0; j < nd.n_inner; ++j)
+        for (int i = tid; i < 2 * a.kext_blocks; i += kLevelThreads) {
+            const int32_t* g = a.kext + (int64_t)(k * a.n_pairs_inner + nd.inner_pair[j]) * a.kext_blocks * 2;
+            s_kext[j][i] = g[i];
+            if (i >= 2 && g[i] < g[i - 2]) s_mono[j] = 0;   // (first sizes are the even entries, last sizes the odd ones)
+        }
+    __syncthreads();
+
+    // ---- intervals: 128 threads per tile, two tiles at a time (a wave lies inside one tile)
+    // (both passes' intervals before either's stores: the chains of dependent loads of the two then run side by side)
+    int2 iv[kLevelTiles * kBN / kLevelThreads];
+#pragma unroll
+    for (int p = 0; p < kLevelTiles * kBN / kLevelThreads; ++p)
+        if (tid + p * kLevelThreads < nt * kBN) iv[p] = column_interval(a, nd, k, ct0 * kBN + tid + p * kLevelThreads, s_kext, s_mono);
+#pragma unroll
+    for (int p = 0; p < kLevelTiles * kBN / kLevelThreads; ++p) {
+        const int i = tid + p * kLevelThreads;
+        if (i >= nt * kBN) continue;                       // (whole waves: a wave lies inside one tile)
+        int lo = iv[p].x, hi = iv[p].y;
+        int32_t* out = nd.colext + ((int64_t)k * nd.cols + ct0 * kBN + i) * 2;
+        out[0] = lo; out[1] = hi;
+        for (int off = 32; off > 0; off >>= 1) { lo = min(lo, __shfl_down(lo, off)); hi = max(hi, __shfl_down(hi, off)); }
+        if (lane == 0) { s_wlo[i >> 6] = lo; s_whi[i >> 6] = hi; }
+    }
+    __syncthreads();
+    if (tid < nt) {                                        // hull over the 128 columns of a tile
+        const int lo = min(s_wlo[2 * tid], s_wlo[2 * tid + 1]), hi = max(s_whi[2 * tid], s_whi[2 * tid + 1]);
+        int32_t* t = nd.tileext + ((int64_t)k * nct + ct0 + tid) * 2;
+        t[0] = lo; t[1] = hi;
+        s_lo[tid] = lo; s_hi[tid] = hi;
+        s_rlo[tid] = hi >= lo ? lo / 4 : nr; s_rhi[tid] = hi >= lo ? min(hi / 4, nr - 1) : -1;
+    }
+    if (!a.t4) return;                                     // (a kernel argument: uniform)
+    __syncthreads();
+    // the row steps inside a hull: all of a tile's, and of the workgroup's tiles together
+    int rlo = nr, rhi = -1;
+    for (int c = 0; c < nt; ++c) { rlo = min(rlo, s_rlo[c]); rhi = max(rhi, s_rhi[c]); }
+    for (int i = tid; i < kLevelTiles * kMaxSteps; i += kLevelThreads) (&s_acc[0][0])[i] = 0;
+
+    // ---- leaf factors: the largest table entry over the distinct counts of the tile's columns
     for (int l = 0; l < nd.n_leaf; ++l) {
         __syncthreads();
-        if (tid < kMaxSteps / 8) s_bits[tid] = 0;
-        if (tid == 0) s_n = 0;
+        for (int i = tid; i < kLevelTiles * (kMaxSteps / 8); i += kLevelThreads) (&s_bits[0][0])[i] = 0;
+        if (tid < kLevelTiles) s_n[tid] = 0;
         __syncthreads();
-        if (tid < kBN) {
-            const int x = nd.cnt[(int64_t)nd.leaf_row[l] * nd.cnt_ld + col];
-            if (!(atomicOr(&s_bits[x >> 5], 1u << (x & 31)) & (1u << (x & 31)))) s_list[atomicAdd(&s_n, 1)] = x;    // the first to set it
+        for (int i = tid; i < nt * kBN; i += kLevelThreads) {
+            const int c = i / kBN;
+            const int x = nd.cnt[(int64_t)nd.leaf_row[l] * nd.cnt_ld + ct0 * kBN + i];
+            if (!(atomicOr(&s_bits[c][x >> 5], 1u << (x & 31)) & (1u << (x & 31)))) s_list[c][atomicAdd(&s_n[c], 1)] = x;    // the first to set it
         }
         __syncthreads();
-        const int n = s_n;
         const int32_t* lt = a.lt + (int64_t)(k * a.n_pairs_leaf + nd.leaf_pair[l]) * (a.M + 1) * nr;
-        for (int r = tid; r < nr; r += kBoundThreads) {
+        const int span = rhi - rlo + 1;
+        for (int i = tid; i < nt * span; i += kLevelThreads) {
+            const int c = i / span, r = rlo + i % span;
+            if (r < s_rlo[c] || r > s_rhi[c]) continue;
+            const int n = s_n[c];
             int32_t m = kMagNone;
-            for (int i0 = 0; i0 < n; i0 += kBoundBatch) {
-                int32_t v[kBoundBatch];
+            for (int i0 = 0; i0 < n; i0 += kListBatch) {
+                int32_t v[kListBatch];
 #pragma unroll
-                for (int i = 0; i < kBoundBatch; ++i) v[i] = lt[(int64_t)s_list[min(i0 + i, n - 1)] * nr + r];
+                for (int q = 0; q < kListBatch; ++q) v[q] = lt[(int64_t)s_list[c][min(i0 + q, n - 1)] * nr + r];
 #pragma unroll
-                for (int i = 0; i < kBoundBatch; ++i) m = max(m, v[i]);
+                for (int q = 0; q < kListBatch; ++q) m = max(m, v[q]);
             }
-            s_acc[r] = (m == kMagNone || s_acc[r] == kMagNone) ? kMagNone : s_acc[r] + m;
+            s_acc[c][r] = (m == kMagNone || s_acc[c][r] == kMagNone) ? kMagNone : s_acc[c][r] + m;
         }
     }
+
+    // ---- interior factors
     for (int j = 0; j < nd.n_inner; ++j) {
         __syncthreads();
-        if (tid < kMaxSteps / 8) s_bits[tid] = 0;
-        if (tid == 0) { s_n = 0; s_klo = nk; s_khi = -1; }
+        for (int i = tid; i < kLevelTiles * (kMaxSteps / 8); i += kLevelThreads) (&s_bits[0][0])[i] = 0;
+        if (tid < kLevelTiles) { s_n[tid] = 0; s_klo[tid] = nk; s_khi[tid] = -1; }
         __syncthreads();
-        if (tid < kBN) {
+        for (int i = tid; i < nt * kBN; i += kLevelThreads) {
+            const int c = i / kBN, col = ct0 * kBN + i;
             const int t = (nd.inner_map[j] ? nd.inner_map[j][col] : col) / kBN;
             // (tiles past the bitmap enter the list once per column: that costs loads and changes no maximum)
-            if (t >= kMaxSteps * 4 || !(atomicOr(&s_bits[t >> 5], 1u << (t & 31)) & (1u << (t & 31)))) s_list[atomicAdd(&s_n, 1)] = t;
+            if (t >= kMaxSteps * 4 || !(atomicOr(&s_bits[c][t >> 5], 1u << (t & 31)) & (1u << (t & 31)))) s_list[c][atomicAdd(&s_n[c], 1)] = t;
         }
         __syncthreads();
-        const int n = s_n;
-        const int32_t* cb = nd.inner_bound[j] + (int64_t)k * (nd.inner_cols[j] / kBN) * nr;
-        for (int ks = tid; ks < nk; ks += kBoundThreads) {
-            int32_t m = kMagNone;
-            for (int i0 = 0; i0 < n; i0 += kBoundBatch) {
-                int32_t v[kBoundBatch];
-#pragma unroll
-                for (int i = 0; i < kBoundBatch; ++i) v[i] = cb[(int64_t)s_list[min(i0 + i, n - 1)] * nr + ks];
-#pragma unroll
-                for (int i = 0; i < kBoundBatch; ++i) m = max(m, v[i]);
-            }
-            s_cb[ks] = m;
-            if (m != kMagNone) { atomicMin(&s_klo, ks); atomicMax(&s_khi, ks); }
-        }
-        __syncthreads();
+        // the child's bound per k-step: the maximum over the child tiles the tile's columns map to -- for the k-steps that the
+        // matrix blocks of the hulls' rows reach (the union of the rows' ranges below); the others are not looked at
         const int slot = k * a.n_pairs_inner + nd.inner_pair[j];
+        const int32_t* e = s_kext[j];
+        int kmin = nk, kmax = -1;
+        if (rhi >= rlo) {
+            for (int b = max(4 * rlo - 1, 0) / 16; b <= (4 * rhi + 2) / 16 && b < a.kext_blocks; ++b)
+                if (e[2 * b + 1] >= e[2 * b]) { kmin = min(kmin, e[2 * b] / 4); kmax = max(kmax, e[2 * b + 1] / 4); }
+            if (rlo == 0) kmin = 0, kmax = max(kmax, 0);
+            kmax = min(kmax, nk - 1);
+        }
+        const int kspan = max(kmax - kmin + 1, 0);
+        for (int i = tid; i < nt * nk; i += kLevelThreads)
+            if (i % nk < kmin || i % nk > kmax) (&s_cb[i % nk].x)[i / nk] = kMagNone;
+        const int32_t* cb = nd.inner_bound[j] + (int64_t)k * (nd.inner_cols[j] / kBN) * nr;
+        for (int i = tid; i < nt * kspan; i += kLevelThreads) {
+            const int c = i / kspan, ks = kmin + i % kspan, n = s_n[c];
+            int32_t m = kMagNone;
+            for (int i0 = 0; i0 < n; i0 += kListBatch) {
+                int32_t v[kListBatch];
+#pragma unroll
+                for (int q = 0; q < kListBatch; ++q) v[q] = cb[(int64_t)s_list[c][min(i0 + q, n - 1)] * nr + ks];
+#pragma unroll
+                for (int q = 0; q < kListBatch; ++q) m = max(m, v[q]);
+            }
+            (&s_cb[ks].x)[c] = m;
+            if (m != kMagNone) { atomicMin(&s_klo[c], ks); atomicMax(&s_khi[c], ks); }
+        }
+        __syncthreads();
+        int cklo = nk, ckhi = -1;                          // the k-steps where some tile's child bound says anything
+#pragma unroll
+        for (int c = 0; c < kLevelTiles; ++c)
+            if (c < nt) { cklo = min(cklo, s_klo[c]); ckhi = max(ckhi, s_khi[c]); }
         const int32_t* t4 = a.t4 + (int64_t)slot * nk * nr;
-        const int32_t* e = a.kext + (int64_t)slot * a.kext_blocks * 2;
-        for (int r = tid; r < nr; r += kBoundThreads) {
-            // the k-steps inside the child's support and inside the non-zero extents of the matrix blocks that hold the parent
-            // sizes 4 r .. 4 r + 3 (block b: sizes 16 b + 1 .. 16 b + 16; size 0 only reaches child size 0)
-            int klo = nk, khi = -1;
-            for (int b = max(4 * r - 1, 0) / 16; b <= (4 * r + 2) / 16 && b < a.kext_blocks; ++b)
-                if (e[2 * b + 1] >= e[2 * b]) { klo = min(klo, e[2 * b] / 4); khi = max(khi, e[2 * b + 1] / 4); }
-            if (r == 0) klo = 0, khi = max(khi, 0);
-            klo = max(klo, s_klo); khi = min(min(khi, s_khi), nk - 1);
-            int32_t top = kMagNone;                         // running maximum and sum_i 2^(v_i - top)
-            float sum = 0.f;
-            for (int k0 = klo; k0 <= khi; k0 += kBoundBatch) {
-                int32_t tv[kBoundBatch];
+        // 64 row steps at a time, lane = row step; wave w sums the k-steps = w mod kLevelPhases of the row's range
+        for (int r0 = rlo; r0 <= rhi; r0 += 64) {
+            const int r = r0 + lane;
+            int32_t top[kLevelTiles];
+            float sum[kLevelTiles];                        // (a sum means nothing while its top says "none": see the rounds below)
 #pragma unroll
-                for (int i = 0; i < kBoundBatch; ++i) tv[i] = t4[(int64_t)min(k0 + i, khi) * nr + r];
+            for (int c = 0; c < kLevelTiles; ++c) { top[c] = kMagNone; sum[c] = 0.f; }
+            if (r <= rhi) {
+                // the k-steps inside the child's support and inside the non-zero extents of the matrix blocks that hold the parent
+                // sizes 4 r .. 4 r + 3 (block b: sizes 16 b + 1 .. 16 b + 16; size 0 only reaches child size 0)
+                int klo = nk, khi = -1;
+                for (int b = max(4 * r - 1, 0) / 16; b <= (4 * r + 2) / 16 && b < a.kext_blocks; ++b)
+                    if (e[2 * b + 1] >= e[2 * b]) { klo = min(klo, e[2 * b] / 4); khi = max(khi, e[2 * b + 1] / 4); }
+                if (r == 0) klo = 0, khi = max(khi, 0);
+                klo = max(klo, cklo); khi = min(min(khi, ckhi), nk - 1);
+                // (rounds of kLevelPhases x kBoundBatch k-steps on an absolute grid, not from klo: klo and khi depend on which
+                // tiles share the workgroup, and so would the batches and the roundings of a tile's sum; on the grid a tile's
+                // sum meets the same terms in the same batches whatever its neighbours are -- the steps a wider range adds say
+                // "none" for it and add exact zeros -- so its bound has the same bits for any number of tiles per workgroup)
+                for (int k0 = klo / (kLevelPhases * kBoundBatch) * (kLevelPhases * kBoundBatch) + wave; k0 <= khi; k0 += kLevelPhases * kBoundBatch) {
+                    int32_t tv[kBoundBatch];
 #pragma unroll
-                for (int i = 0; i < kBoundBatch; ++i) {
-                    const int32_t cv = s_cb[min(k0 + i, khi)];
-                    if (k0 + i > khi || tv[i] == kMagNone || cv == kMagNone) continue;
-                    const int32_t v = tv[i] + cv;
-                    if (v > top) { sum = sum * exp2f((float)(top - v) * (1.f / kMagUnit)) + 1.f; top = v; }
-                    else sum += exp2f((float)(v - top) * (1.f / kMagUnit));
+                    for (int q = 0; q < kBoundBatch; ++q) tv[q] = t4[(int64_t)min(max(k0 + kLevelPhases * q, klo), khi) * nr + r];
+                    // a batch at a time: the new maxima first, then one rescale of each sum and one term per k-step and tile, no
+                    // branch per term (a term that says "none" is 2^(-2^20) = 0 against any maximum; v_exp_f32 itself: a term
+                    // below 2^-126 of the largest counts as 0, 512 of them are far inside the factor above)
+                    // (while a tile has met no term at all its maximum says "none" too and the sum collects ones: the first real
+                    // maximum rescales them by 2^(-2^20) = 0, and the combine step leaves out a partial sum whose maximum is "none")
+                    int32_t m[kLevelTiles];
+#pragma unroll
+                    for (int c = 0; c < kLevelTiles; ++c) m[c] = top[c];
+#pragma unroll
+                    for (int q = 0; q < kBoundBatch; ++q) {
+                        const int ks = k0 + kLevelPhases * q;
+                        const int4 cv4 = s_cb[min(max(ks, klo), khi)];
+                        const int32_t cv[kLevelTiles] = {cv4.x, cv4.y, cv4.z, cv4.w};
+                        if (ks < klo || ks > khi) tv[q] = kMagNone;
+#pragma unroll
+                        for (int c = 0; c < kLevelTiles; ++c)
+                            if (c < nt && tv[q] != kMagNone && cv[c] != kMagNone) m[c] = max(m[c], tv[q] + cv[c]);
+                    }
+#pragma unroll
+                    for (int c = 0; c < kLevelTiles; ++c) {
+                        sum[c] *= __builtin_amdgcn_exp2f((float)(top[c] - m[c]) * (1.f / kMagUnit));
+                        top[c] = m[c];
+                    }
+#pragma unroll
+                    for (int q = 0; q < kBoundBatch; ++q) {
+                        const int4 cv4 = s_cb[min(max(k0 + kLevelPhases * q, klo), khi)];
+                        const int32_t cv[kLevelTiles] = {cv4.x, cv4.y, cv4.z, cv4.w};
+#pragma unroll
+                        for (int c = 0; c < kLevelTiles; ++c) {
+                            if (c >= nt) continue;
+                            const int32_t v = (tv[q] != kMagNone && cv[c] != kMagNone) ? tv[q] + cv[c] : kMagNone;
+                            sum[c] += __builtin_amdgcn_exp2f((float)(v - m[c]) * (1.f / kMagUnit));
+                        }
+                    }
                 }
             }
-            const int32_t f = top == kMagNone ? kMagNone : top + (int32_t)ceilf(log2f(sum) * (float)kMagUnit) + 1;
-            s_acc[r] = (f == kMagNone || s_acc[r] == kMagNone) ? kMagNone : s_acc[r] + f;
+#pragma unroll
+            for (int c = 0; c < kLevelTiles; ++c) { s_ptop[wave][c][lane] = top[c]; s_psum[wave][c][lane] = sum[c]; }
+            __syncthreads();
+            {   // thread -> (tile, row step of the chunk): the partial sums in the order of the waves
+                const int c = wave, rr = r0 + lane;
+                if (c < nt && rr >= s_rlo[c] && rr <= s_rhi[c]) {
+                    int32_t T = kMagNone;
+#pragma unroll
+                    for (int w = 0; w < kLevelPhases; ++w) T = max(T, s_ptop[w][c][lane]);
+                    int32_t f = kMagNone;
+                    if (T != kMagNone) {
+                        float S = 0.f;
+#pragma unroll
+                        for (int w = 0; w < kLevelPhases; ++w)
+                            if (s_ptop[w][c][lane] != kMagNone) S += s_psum[w][c][lane] * exp2f((float)(s_ptop[w][c][lane] - T) * (1.f / kMagUnit));
+                        f = T + (int32_t)ceilf(log2f(S * (1.f + 0x1p-11f)) * (float)kMagUnit);
+                    }
+                    s_acc[c][rr] = (f == kMagNone || s_acc[c][rr] == kMagNone) ? kMagNone : s_acc[c][rr] + f;
+                }
+            }
+            __syncthreads();
         }
     }
     __syncthreads();
-    const int32_t* te = nd.tileext + ((int64_t)k * nct + ct) * 2;
-    const int lo = te[0], hi = te[1];
-    int32_t* out = nd.bound + ((int64_t)k * nct + ct) * nr;
-    for (int r = tid; r < nr; r += kBoundThreads)
-        out[r] = (hi >= lo && 4 * r + 3 >= lo && 4 * r <= hi) ? max(s_acc[r], kMagFloor) + kMagSlack : kMagNone;
+    for (int i = tid; i < nt * nr; i += kLevelThreads) {
+        const int c = i / nr, r = i % nr, lo = s_lo[c], hi = s_hi[c];
+        nd.bound[((int64_t)k * nct + ct0 + c) * nr + r] =
+            (hi >= lo && 4 * r + 3 >= lo && 4 * r <= hi) ? max(s_acc[c][r], kMagFloor) + kMagSlack : kMagNone;
+    }
 }
 
-hipError_t launch_node_bounds(const ExtArgs& a, int max_col_tiles, int n_categories, hipStream_t stream) {
-    if (a.count <= 0 || !a.t4) return hipSuccess;
+// Tiles a workgroup owns (ExtArgs::level_tiles, or 0: chosen here): four where that still leaves the level's grid ten
+// workgroups per CU's worth of tiles, two from five (five are resident per CU; with fewer tiles one workgroup each keeps
+// more CUs busy).  A tile's bound does not depend on the choice (node_level_kernel: the grid of its rounds is absolute).
+hipError_t launch_node_level(const ExtArgs& a, int max_col_tiles, int n_categories, hipStream_t stream) {
+    if (a.count <= 0) return hipSuccess;
+    const int64_t tiles = (int64_t)max_col_tiles * n_categories * a.count, cus = std::max(1, a.n_cu);
+    int per_block = !a.t4 ? 2 : tiles >= 10 * cus ? kLevelTiles : tiles >= 5 * cus ? 2 : 1;
+    if (a.level_tiles == 1 || a.level_tiles == 2 || a.level_tiles == kLevelTiles) per_block = a.level_tiles;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(node_bound_kernel, dim3(max_col_tiles, n_categories, a.count), dim3(kBoundThreads), 0, stream, a);
+    hipLaunchKernelGGL(node_level_kernel, dim3((max_col_tiles + per_block - 1) / per_block, n_categories, a.count), dim3(kLevelThreads), 0,
+                       stream, a, per_block);
     return hipGetLastError();
 }
 
@@ -258,62 +445,72 @@ hipError_t launch_node_bounds(const ExtArgs& a, int max_col_tiles, int n_categor
 // by the panel's (an empty panel extent: row 0, so that the panel receives its zeros); with magnitude tables the interval
 // shrinks from both ends while (largest entry of the block in the k-step) x (bound of the panel's rows of the k-step) lies
 // below 2^-1100.  The ranges only ever shrink: no MFMA reads a panel row the assemble pass left unwritten.
-__global__ __launch_bounds__(256) void range_kernel(const RangeArgs a) {
+// One wave per (op, category, column tile), four column tiles per workgroup: the lanes of a wave are the matrix's blocks
+// (ext_blocks + kRangePad <= 136: up to three per lane), and a lane looks from both ends of its interval at once,
+// kRangeBatch k-steps from either end per look (independent loads).  The first and the last k-step that count do not depend
+// on how many are looked at together.
+constexpr int kRangeWaves = 4, kRangeBatch = 8;
+__global__ __launch_bounds__(64 * kRangeWaves) void range_kernel(const RangeArgs a) {
     const GemmOp& o = a.ops[blockIdx.z];
-    if (!o.jr || (int)blockIdx.x >= o.jr_nct) return;
-    const int ct = blockIdx.x, cat = blockIdx.y, b = threadIdx.x, nb = a.ext_blocks;
-    const bool mag = a.a16 && o.bbound;
-    __shared__ int32_t s_b[kMaxSteps];                      // the panel's bound per k-step
+    if (!o.jr || (int)blockIdx.x * kRangeWaves >= o.jr_nct) return;     // (block-uniform)
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ct = blockIdx.x * kRangeWaves + wave, cat = blockIdx.y, nb = a.ext_blocks;
+    const bool live = ct < o.jr_nct, mag = a.a16 && o.bbound;
+    __shared__ int32_t s_ball[kRangeWaves][kMaxSteps];      // the panel's bound per k-step
+    const int32_t* s_b = s_ball[wave];
     if (mag) {
-        const int32_t* B = o.bbound + ((int64_t)cat * o.jr_nct + ct) * a.n_rsteps;
-        for (int i = b; i < a.n_ksteps; i += 256) s_b[i] = B[i];
+        if (live) {
+            const int32_t* B = o.bbound + ((int64_t)cat * o.jr_nct + ct) * a.n_rsteps;
+            for (int i = lane; i < a.n_ksteps; i += 64) s_ball[wave][i] = B[i];
+        }
         __syncthreads();
     }
-    if (b >= nb + kRangePad) return;
-    int slo = 1, shi = 0;
-    if (b < nb) {
-        const int slot = o.slot[cat];
-        const int32_t* e = a.aext + ((int64_t)slot * nb + b) * 2;
-        int plo = 0, phi = a.k_valid - 1;
-        if (o.bext) {
-            const int32_t* be = o.bext + ((int64_t)cat * o.jr_nct + ct) * 2;
-            plo = be[0]; phi = min(be[1], phi);
-            if (be[1] < be[0]) { plo = 0; phi = 0; }
-        }
-        const int lo = max(e[0], plo), hi = min(e[1], phi);
-        if (hi >= lo) {
-            slo = lo / 4; shi = hi / 4;
-            if (mag) {
-                // four k-steps per look from either end (independent loads); a step counts when it may reach 2^-1100
-                const int32_t* A = a.a16 + (int64_t)slot * a.n_ksteps * nb + b;
-                const int first = slo, last = shi;
-                for (bool found = false; !found && slo <= last; ) {
-                    int32_t v[4];
+    if (!live) return;
+    const int slot = o.slot[cat];
+    int plo = 0, phi = a.k_valid - 1;
+    if (o.bext) {
+        const int32_t* be = o.bext + ((int64_t)cat * o.jr_nct + ct) * 2;
+        plo = be[0]; phi = min(be[1], phi);
+        if (be[1] < be[0]) { plo = 0; phi = 0; }
+    }
+    for (int b = lane; b < nb + kRangePad; b += 64) {
+        int slo = 1, shi = 0;
+        if (b < nb) {
+            const int32_t* e = a.aext + ((int64_t)slot * nb + b) * 2;
+            const int lo = max(e[0], plo), hi = min(e[1], phi);
+            if (hi >= lo) {
+                slo = lo / 4; shi = hi / 4;
+                if (mag) {
+                    // a step counts when it may reach 2^-1100
+                    const int32_t* A = a.a16 + (int64_t)slot * a.n_ksteps * nb + b;
+                    const int first = slo, last = shi;
+                    bool ffound = false, lfound = false;
+                    while ((!ffound && slo <= last) || (!lfound && shi >= first)) {
+                        int32_t vf[kRangeBatch], vl[kRangeBatch];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] = A[(int64_t)min(slo + i, last) * nb];
+                        for (int i = 0; i < kRangeBatch; ++i) {
+                            vf[i] = A[(int64_t)min(slo + i, last) * nb];
+                            vl[i] = A[(int64_t)max(shi - i, first) * nb];
+                        }
 #pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (!found) { if (slo <= last && v[i] + s_b[slo] >= kSkipBelow) found = true; else ++slo; }
+                        for (int i = 0; i < kRangeBatch; ++i) {
+                            if (!ffound) { if (slo <= last && vf[i] + s_b[slo] >= kSkipBelow) ffound = true; else if (slo <= last) ++slo; }
+                            if (!lfound) { if (shi >= first && vl[i] + s_b[shi] >= kSkipBelow) lfound = true; else if (shi >= first) --shi; }
+                        }
+                    }
+                    if (!ffound || !lfound || slo > shi) { slo = 1; shi = 0; }
                 }
-                for (bool found = false; !found && shi >= slo; ) {
-                    int32_t v[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] = A[(int64_t)max(shi - i, first) * nb];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (!found) { if (shi >= slo && v[i] + s_b[shi] >= kSkipBelow) found = true; else --shi; }
-                }
-                if (slo > shi) { slo = 1; shi = 0; }
             }
         }
+        const_cast<int32_t*>(o.jr)[((int64_t)cat * o.jr_nct + ct) * (nb + kRangePad) + b] = slo | (shi << 16);
     }
-    const_cast<int32_t*>(o.jr)[((int64_t)cat * o.jr_nct + ct) * (nb + kRangePad) + b] = slo | (shi << 16);
 }
 
 hipError_t launch_joint_ranges(const RangeArgs& a, int max_col_tiles, int n_categories, hipStream_t stream) {
     if (a.n_ops <= 0 || !a.aext) return hipSuccess;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(range_kernel, dim3(max_col_tiles, n_categories, a.n_ops), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(range_kernel, dim3((max_col_tiles + kRangeWaves - 1) / kRangeWaves, n_categories, a.n_ops), dim3(64 * kRangeWaves), 0,
+                       stream, a);
     return hipGetLastError();
 }
 
@@ -327,9 +524,11 @@ constexpr int kPlanTail = 2;
 // evenly -- the one dispatched first wins the arbitration (with three per CU and equal lists they finish at 2 672 / 3 200 /
 // 3 503 us of a 3 563 us launch: tools/k2_tile_costs.py) -- so the planner charges the favoured ones less and they take more
 // of the work.  Full grids only (local indices j, j + 32, ... share a CU).
-__device__ inline int plan_weight(const PlanLaunch& L, int nlb, int w) {
+__device__ inline int plan_weight(const PlanLaunch& L, const int* bias3, int nlb, int w) {
     if (nlb == 64 && L.bias) return w < 32 ? 100 - L.bias : 100 + L.bias;
-    if (nlb == 96 || nlb == 128) return L.bias3[w >> 5];
+    // (bias3: PlanLaunch::bias3 staged in LDS -- indexing the member of the kernel's register copy of L would put the whole copy
+    // into scratch memory)
+    if (nlb == 96 || nlb == 128) return bias3[w >> 5];
     return 100;
 }
 
@@ -378,7 +577,8 @@ __global__ __launch_bounds__(kPlanLanes) void tile_plan_kernel(const PlanLaunch*
     const PlanLaunch L = launches[blockIdx.y];
     const int xcd = blockIdx.x, lane = threadIdx.x;         // lane = workgroup of the XCD (< blocks_per_xcd <= kPlanLanes)
     const int nlb = L.blocks_per_xcd;
-    __shared__ int s_first[kMaxGroupOps + 1];
+    __shared__ int s_first[kMaxGroupOps + 1], s_bias3[4];
+    if (lane < 4) s_bias3[lane] = launches[blockIdx.y].bias3[lane];
     if (lane == 0) {
         int acc = 0;
         for (int o = 0; o < L.n_ops; ++o) {
@@ -426,7 +626,7 @@ __global__ __launch_bounds__(kPlanLanes) void tile_plan_kernel(const PlanLaunch*
         if (valid) {
             const int w = s_who[crank];
             L.plan[((int64_t)xcd * nlb + w) * L.rounds + r] = en;
-            s_load[w] += cst * plan_weight(L, nlb, w);
+            s_load[w] += cst * plan_weight(L, s_bias3, nlb, w);
         }
         __syncthreads();
     }
@@ -455,7 +655,7 @@ __global__ __launch_bounds__(kPlanLanes) void tile_plan_kernel(const PlanLaunch*
     unsigned load[2] = {(unsigned)s_load[wg[0]], (unsigned)s_load[wg[1]]};
     int wt[2];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) wt[h] = plan_weight(L, nlb, wg[h]);
+    for (int h = 0; h < 2; ++h) wt[h] = plan_weight(L, s_bias3, nlb, wg[h]);
     for (int q = 0; q < n_tail; ++q) {
         const int item = t_by_rank[q];
         unsigned key = 0xFFFFFFFFu;

@@ -608,11 +608,25 @@ int cafe_get_extents(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* mat
 /* diagnostic: the per-COLUMN zero extents of an interior non-root node's panel in the last call, out[columns][2] (rows outside
  * [lo, hi] of a column are exactly zero; lo > hi: the whole column); *n_cols receives the panel's (padded) column count */
 int cafe_debug_column_extents(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* out, size_t out_len, int64_t* n_cols);
-/* diagnostic: the magnitude bounds of an interior non-root node's panel in the last call (extents.hip, node_bound_kernel):
+/* diagnostic: the magnitude bounds of an interior non-root node's panel in the last call (extents.hip, node_level_kernel):
  * out[tile * *row_steps + r] is an upper bound of log2 of every COMPUTED entry of panel rows 4 r .. 4 r + 3 in 128-column tile
  * `tile`, -inf where they are all exactly zero, never below -1060 otherwise.  out == NULL: the two sizes only.  CAFE_ERR_STATE
  * when the last call kept none (CAFE_NO_MAGSKIP, CAFE_NO_KSKIP, matrix order below 256, an error model). */
 int cafe_debug_panel_bounds(cafe_ctx* ctx, int32_t node, int32_t category, double* out, size_t out_len, int32_t* n_tiles, int32_t* row_steps);
+/* diagnostic: one slot of the magnitude tables of the last call's matrices (extents.hip, mag_tables_kernel), as written: upper
+ * bounds of log2 in units of 1/256, -(1 << 28) where every entry the item stands for is exactly zero.
+ *   which 0: a16, out[ks * *n1 + b]  the largest P[s][c], s in 16 b + 1 .. 16 b + 16, c in 4 ks .. 4 ks + 3   (interior branch)
+ *   which 1: t4,  out[ks * *n1 + r]  the largest sum of P[s][c] over those four c, s in 4 r .. 4 r + 3         (interior branch)
+ *   which 2: lt,  out[x * *n1 + r]   the largest P[s][x], s in 4 r .. 4 r + 3, x = 0 .. M                      (leaf branch)
+ * slot >= 0 names the matrix by its slot in the k-major (which 0, 1) or row-major (which 2) pool; slot < 0: the matrix of the
+ * branch above `node` in `category`.  out == NULL: the two sizes only.  Never called on the scorer path.  The state errors are
+ * those of cafe_debug_panel_bounds. */
+int cafe_debug_magnitude_tables(cafe_ctx* ctx, int32_t which, int32_t slot, int32_t* out, size_t out_len, int32_t* n0, int32_t* n1,
+                                int32_t node, int32_t category);
+/* diagnostic: column tiles a workgroup of the per-level interval / bound kernel owns in the following calls (1, 2 or 4;
+ * 0 = chosen per level from the level's size, the default).  No result, bound or range depends on it; calls made while
+ * it is set are enqueued launch by launch (no graph replay). */
+int cafe_debug_level_tiles(cafe_ctx* ctx, int tiles);
 /* diagnostic: the K ranges of the K2 op that multiplies the matrix of the branch above `node` (interior, not the root) in the
  * last call: out[(tile * *n_blocks + b) * 2 + {0, 1}] = first / last k-step (4 deep) that 16-row block b of the matrix runs
  * against column tile `tile` of the node's panel (first > last: none).  The block's non-zero extent cut by the panel's and,

@@ -31,6 +31,7 @@ print("launch  ~cols  mi  executed/all  ms      TF/s(executed)")
 for i in order:
     print("%4d %7.0f  %d   %.3f       %.4f  %.1f" % (i, cols[i], mi[i], ex[i] / al[i], ms[i], ex[i] / ms[i] / 1e9 if ms[i] > 0 else 0))
 print("total: %.2f ms, %.1f TF/s over executed flops, executed share %.3f" % (ms.sum(), ex.sum() / ms.sum() / 1e9, ex.sum() / al.sum()))
+print("issued flop: %.0f in %d launches, %.6e per launch" % (ex.sum(), len(ex), ex.sum() / max(1, len(ex))))
 for lo, hi in ((0, 1024), (1024, 8192), (8192, 32768), (32768, 1 << 30)):
     m = (cols >= lo) & (cols < hi)
     if m.any():
