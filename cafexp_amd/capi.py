@@ -20,6 +20,8 @@ LIB_PATH = os.path.join(_HERE, "libcafe_mi355x.so")
 CAFE_MAX_CATEGORIES = 32
 CAFE_FLAG_NO_DEDUP = 1
 CAFE_FLAG_NO_SUBTREE_DEDUP = 2
+CAFE_FLAG_MISSING_COUNTS = 4     # counts may hold CAFE_COUNT_MISSING (Problem.missing_counts sets it)
+CAFE_COUNT_MISSING = -1
 CAFE_MODEL_BASE, CAFE_MODEL_GAMMA = 0, 1
 CAFE_ROOT_MAX, CAFE_ROOT_SUM = 0, 1
 
@@ -295,7 +297,7 @@ def _c_problem(pb: Problem, keep: list, max_categories: int = 1, device: int = 0
     cp.max_categories = max_categories
     cp.n_deviations = pb.n_deviations
     cp.device = device
-    cp.flags = flags
+    cp.flags = flags | (CAFE_FLAG_MISSING_COUNTS if getattr(pb, "missing_counts", False) else 0)
     cp.workspace_limit = workspace_limit
     return cp
 

@@ -273,7 +273,7 @@ int branch_scores_impl(cafe_ctx* c, const cafe_params* pr, int32_t root_rule, co
 extern "C" {
 
 int cafe_branch_scores(cafe_ctx* ctx, const cafe_params* params, int32_t root_rule, const cafe_branch_scores_out* out) {
-    return cafe::guarded(ctx, "cafe_branch_scores", [&] { return cafe::branch_scores_impl(ctx, params, root_rule, out); });
+    return cafe::guarded_observed(ctx, "cafe_branch_scores", [&] { return cafe::branch_scores_impl(ctx, params, root_rule, out); });
 }
 
 int cafe_branch_scores_dim(const cafe_ctx* ctx, const cafe_params* params, int32_t* P) {

@@ -17,6 +17,16 @@ int guarded(cafe_ctx* c, const char* entry, Fn&& fn) {
     catch (const std::exception& e) { set_err(c, "%s: %s", entry, e.what()); return CAFE_ERR_MEMORY; }
 }
 
+// The shell of an entry whose kernels index by the observed count and have no instantiation for CAFE_COUNT_MISSING: a context
+// whose table has missing cells is refused here, before the entry touches the device -- such a kernel must never see a -1.
+// The context stays as it was.
+template <class Fn>
+int guarded_observed(cafe_ctx* c, const char* entry, Fn&& fn) {
+    if (!c) return CAFE_ERR_ARGUMENT;
+    if (c->has_missing) { set_err(c, "%s: the table has missing cells (CAFE_COUNT_MISSING); this call is not available for such a context", entry); return CAFE_ERR_STATE; }
+    return guarded(c, entry, fn);
+}
+
 // One kernel launch of an *_impl: a stale error of the thread is cleared first, so that what is reported belongs to this launch
 #define CAFE_LAUNCH(c, kernel, grid, block, shmem, stream, ...)                  \
     do {                                                                         \

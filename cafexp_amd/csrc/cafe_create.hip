@@ -120,11 +120,14 @@ int load_problem(cafe_ctx* c, const cafe_problem* p, std::vector<int64_t>& uniq)
     c->F_all = p->n_families;
     c->workspace_limit = p->workspace_limit;
     const int T = c->n_taxa;
-    for (int64_t i = 0; !device_counts && i < c->F_all * T; ++i)
+    const bool may_miss = !device_counts && (p->flags & CAFE_FLAG_MISSING_COUNTS);
+    for (int64_t i = 0; !device_counts && i < c->F_all * T; ++i) {
+        if (may_miss && p->counts[i] == CAFE_COUNT_MISSING) { c->has_missing = true; continue; }
         if (p->counts[i] < 0 || p->counts[i] > c->M) {
             set_err(c, "cafe_create: family %lld has a count outside [0, %d]", (long long)(i / T), c->M);
             return CAFE_ERR_ARGUMENT;
         }
+    }
     c->ref_of.resize(c->F_all);
     if ((p->flags & CAFE_FLAG_NO_DEDUP) || device_counts) {
         uniq.resize(c->F_all);

@@ -96,6 +96,10 @@ struct cafe_ctx {
     int64_t F_all = 0, F_uniq = 0, Fp = 0;
     std::vector<int64_t> ref_of;            // family -> unique column
     std::vector<double> weights;
+    // CAFE_FLAG_MISSING_COUNTS and at least one CAFE_COUNT_MISSING in the table: the schedule keeps leaves out of K2's epilogues
+    // and off the transposed-leaf assemble, K3 and the extent pass run their MISSING instantiations (cafe_kernels.h:
+    // count_is_missing), and the calls that have no such instantiation refuse the context (guarded_observed, cafe_call.h)
+    bool has_missing = false;
 
     // schedule
     std::vector<cafe::Op> ops;

@@ -18,6 +18,16 @@ namespace cafe {
 constexpr int kMaxCategories = 32;   // CAFE_MAX_CATEGORIES
 constexpr int kMaxLeafPerOp = 4;     // leaf children folded by one gather launch / one GEMM epilogue
 
+// Missing cells (CAFE_COUNT_MISSING, include/cafe_mi355x.h): THE rule, for every kernel that turns a leaf count into a factor.
+// A missing leaf's factor is exactly 1.0 for every parent size -- no matrix column, no error-model taps.  A reader keeps its
+// addresses in bounds with count_index (column 0 stands in for the load whose value is then dropped) and takes its factor
+// through leaf_factor_or_one; a product with 1.0 leaves every bit of the other factors as it is, so the value is that of the
+// tree without the leaf.  Only the MISSING instantiations of the readers call these: contexts without a missing cell run the
+// code they ran before.
+__host__ __device__ inline bool count_is_missing(int x) { return x < 0; }
+__host__ __device__ inline int count_index(int x) { return x < 0 ? 0 : x; }
+__host__ __device__ inline double leaf_factor_or_one(int x, double fac) { return x < 0 ? 1.0 : fac; }
+
 // GEMM tiling (fp64 MFMA 16x16x4): block tile (16*MI) x 128, K step 16, 4 waves side by side in N
 constexpr int kBN = 128;
 constexpr int kBK = 16;          // largest depth of a K tile (panel / matrix row counts are rounded to it); a context runs K2 with 16-deep
@@ -326,7 +336,9 @@ struct ExtArgs {
     int32_t level_tiles;                     // diagnostic (cafe_debug_level_tiles): column tiles per workgroup, 0 = chosen per level
 };
 // one launch per tree level: the intervals of the level's nodes and, with magnitude tables, the bounds of their panels
-hipError_t launch_node_level(const ExtArgs& a, int max_col_tiles, int n_categories, hipStream_t stream);
+// missing: the counts may hold CAFE_COUNT_MISSING (the kernel's MISSING instantiation: such a leaf narrows no interval and
+// bounds its factor by the magnitude of 1.0)
+hipError_t launch_node_level(const ExtArgs& a, int max_col_tiles, int n_categories, hipStream_t stream, bool missing = false);
 
 // Magnitudes (extents.hip).  A product P[s][k] L[k][f] of two non-zero factors below half the smallest denormal moves no
 // accumulator either: the tables below bound log2 of the matrix entries, node_level_kernel propagates bounds of the panels
@@ -418,8 +430,9 @@ struct GatherGroup {
     int32_t leaf_t;                 // this call filled the transposed leaf matrices (GatherArgs::lt): no error model, copies made
 };
 // One launch for a group of K3 ops of one variant (same n_leaf, n_src, mode; the error model is the call's): d_ops device
-// array, h_ops the same on the host (grid extents)
-hipError_t launch_leaf_gather_group(const GatherGroup& g, const GatherArgs* h_ops, hipStream_t stream);
+// array, h_ops the same on the host (grid extents).  missing: the counts may hold CAFE_COUNT_MISSING -- the MISSING
+// instantiations of the three kernels; the transposed leaf copies are not read then (the planner makes none)
+hipError_t launch_leaf_gather_group(const GatherGroup& g, const GatherArgs* h_ops, hipStream_t stream, bool missing = false);
 hipError_t launch_root_reduce(const ReduceArgs& a, hipStream_t stream);
 // sum_f w_f * fam_out[f] and the number of failed families -> out[0], out[1] (and out_host[0..1] when not null: pinned host memory)
 hipError_t launch_final_sum(const double* fam_out, const double* weights, const int32_t* failed, int64_t n,

@@ -45,7 +45,9 @@ int emit_node(const cafe_ctx* c, bool dedup, int v, const std::vector<int>& need
     // P . L over ITS columns in a scratch panel, which a combine pass spreads over the parent's columns.
     auto is_direct = [&](int u) { return !dedup || c->edge_identity[u]; };
     const bool first_direct = !inner.empty() && is_direct(inner[0]);
-    size_t fused = (!first_direct || leaves.empty() || (c->n_dev != 0 && c->n_dev != 3)) ? 0 : 1;
+    // (a table with missing cells: K2's leaf epilogues turn the count into a buffer offset and know no missing count -- the leaf
+    // goes to a K3 pass instead, whose MISSING instantiation does)
+    size_t fused = (!first_direct || leaves.empty() || (c->n_dev != 0 && c->n_dev != 3) || c->has_missing) ? 0 : 1;
     std::vector<std::pair<int, int>> factors;             // (child, scratch panel) waiting to be assembled
     auto new_op = [&](int type, int dst_panel, int mode) { Op o{}; o.type = type; o.parent = v; o.to_root = (v == c->root); o.dst_panel = dst_panel; o.mode = mode; return o; };
     if (inner.size() == 2 && leaves.empty() && is_direct(inner[0]) != is_direct(inner[1])) {
@@ -284,6 +286,7 @@ void plan_patterns(cafe_ctx* c, const cafe_problem* p, const std::vector<int64_t
         for (size_t i = 0; i < U; ++i)
             for (int t : under) {
                 const int32_t x = p->counts[uniq[first[i]] * T + t];
+                if (count_is_missing(x)) continue;        // (a missing cell moves neither end of a column's non-zero rows)
                 big[i] = std::max(big[i], x);
                 small[i] = std::min(small[i], x);
             }
@@ -411,6 +414,7 @@ std::vector<int> plan_extent_levels(cafe_ctx* c, bool matrix_extents) {
 // the copy of every leaf pair (-1: none); returns the bytes of the copies (0: none).
 size_t plan_leaf_transposes(cafe_ctx* c, double lt_min, size_t free_bytes, std::vector<int>& lt_of_pair) {
     lt_of_pair.assign(std::max(1, c->n_pairs[0]), -1);
+    if (c->has_missing) return 0;            // the copies are indexed by count: a table with missing cells gathers its leaves (leaf_reduce.hip)
     std::vector<int64_t> served(lt_of_pair.size(), 0);
     auto eligible = [](const Op& op) { return op.type == 0 && op.n_src >= 1 && op.n_src <= 2 && op.n_leaf >= 1 && op.n_leaf <= 2; };
     for (const Op& op : c->ops)

@@ -338,7 +338,7 @@ int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool 
         ea.err = use_err ? c->d_err : nullptr; ea.n_dev = use_err ? c->n_dev : 0;
         for (const auto& L : c->ext_levels) {
             ea.first = L.first; ea.count = L.count;
-            HIP_TRY(c, launch_node_level(ea, L.max_col_tiles, K, s));
+            HIP_TRY(c, launch_node_level(ea, L.max_col_tiles, K, s, c->has_missing));
         }
     }
     if (c->d_jr) {                           // the K ranges of every K2 op, for the planner and for K2
@@ -391,7 +391,7 @@ int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool 
                 gg.uniform_ld = uniform_ld;
                 gg.f0 = c->subtree_dedup ? 0 : f0;
                 gg.leaf_t = leaf_t ? 1 : 0;
-                HIP_TRY(c, launch_leaf_gather_group(gg, c->h_gather_ops.data() + g.first_desc, s));
+                HIP_TRY(c, launch_leaf_gather_group(gg, c->h_gather_ops.data() + g.first_desc, s, c->has_missing));
                 continue;
             }
             GemmArgs a{};

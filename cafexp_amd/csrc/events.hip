@@ -287,7 +287,7 @@ int expected_events_impl(cafe_ctx* c, const cafe_params* pr, const cafe_events_o
 extern "C" {
 
 int cafe_expected_events(cafe_ctx* ctx, const cafe_params* params, const cafe_events_out* out) {
-    return cafe::guarded(ctx, "cafe_expected_events", [&] { return cafe::expected_events_impl(ctx, params, out); });
+    return cafe::guarded_observed(ctx, "cafe_expected_events", [&] { return cafe::expected_events_impl(ctx, params, out); });
 }
 
 int cafe_bd_rates_events(double lambda, double mu, double t, double out[6]) {

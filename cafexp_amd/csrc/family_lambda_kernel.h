@@ -47,6 +47,10 @@ __global__ __launch_bounds__(64) void family_lambda_kernel(const FamLamArgs<Slot
     const int tx = a.taxon[u];
     if (tx >= 0) {                                     // probability.cpp:179-199
         const int x = a.counts[(int64_t)tx * a.counts_ld + a.col[b]];
+        if (count_is_missing(x)) {                     // a missing cell: the factor is exactly 1.0 for every parent size (cafe_kernels.h),
+            for (int r = lane; r < n_rows; r += 64) out[r] = leaf_factor_or_one(x, 0.0);       // no row of the recurrence is run
+            return;                                    // (block-uniform: the block is one (family, branch))
+        }
         if (a.err) {
             const int lo = x - (a.n_dev - 1) / 2;      // taps outside [0, M] are dropped
 #pragma unroll

@@ -453,7 +453,7 @@ int gradient_walk(cafe_ctx* c, const char* entry, const cafe_params* pr, int32_t
 extern "C" {
 
 int cafe_score_gradient(cafe_ctx* ctx, const cafe_params* params, int32_t root_rule, const cafe_gradient_out* out) {
-    return cafe::guarded(ctx, "cafe_score_gradient", [&] { return cafe::gradient_walk(ctx, "cafe_score_gradient", params, root_rule, out, nullptr); });
+    return cafe::guarded_observed(ctx, "cafe_score_gradient", [&] { return cafe::gradient_walk(ctx, "cafe_score_gradient", params, root_rule, out, nullptr); });
 }
 
 int cafe_bd_rates_grad(double lambda, double mu, double t, double out[4]) {

@@ -416,7 +416,7 @@ int history_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_draws, uint64_t s
 extern "C" {
 
 int cafe_sample_histories(cafe_ctx* ctx, const cafe_params* params, int32_t n_draws, uint64_t seed, const cafe_history_out* out) {
-    return cafe::guarded(ctx, "cafe_sample_histories", [&] { return cafe::history_impl(ctx, params, n_draws, seed, out); });
+    return cafe::guarded_observed(ctx, "cafe_sample_histories", [&] { return cafe::history_impl(ctx, params, n_draws, seed, out); });
 }
 
 int cafe_debug_history_batches(cafe_ctx* ctx, int32_t* column_batches, int32_t* draw_passes) {

@@ -27,6 +27,10 @@ typedef const __attribute__((address_space(4))) GatherArgs* gop_cptr_t;
     const gop_cptr_t a = (gop_cptr_t)(unsigned long long)g.ops + op_index;              \
     const int ld = g.uniform_ld > 0 ? g.uniform_ld : a->ld
 
+// MISSING (every kernel of this file that reads a count): a count may be CAFE_COUNT_MISSING -- count_index keeps the loads in
+// bounds, leaf_factor_or_one puts exactly 1.0 where the factor would stand (cafe_kernels.h).  MISSING = false compiles to the
+// code without these lines.
+template <bool MISSING>
 __global__ __launch_bounds__(256) void leaf_gather_kernel(const GatherGroup g) {
     CAFE_GATHER_OP();
     const int f = blockIdx.x * 256 + threadIdx.x;           // column inside the chunk (ld is a multiple of 128)
@@ -62,16 +66,18 @@ __global__ __launch_bounds__(256) void leaf_gather_kernel(const GatherGroup g) {
             for (int l = 0; l < kMaxLeafPerOp; ++l) {
                 if (l < n_leaf) {
                     double fac;
+                    const int xl = MISSING ? count_index(x[l]) : x[l];
                     if (g.err == nullptr) {
-                        fac = P[l][srow + x[l]];
+                        fac = P[l][srow + xl];
                     } else {
                         fac = 0.0;
                         for (int i = 0; i < g.n_dev; ++i) {
-                            const int c = x[l] - half + i;
+                            const int c = xl - half + i;
                             if (c < 0 || c > g.max_family_size) continue;
-                            fac += P[l][srow + c] * g.err[(int64_t)x[l] * g.n_dev + i];
+                            fac += P[l][srow + c] * g.err[(int64_t)xl * g.n_dev + i];
                         }
                     }
+                    if (MISSING) fac = leaf_factor_or_one(x[l], fac);
                     v *= fac;
                 }
             }
@@ -89,7 +95,7 @@ __global__ __launch_bounds__(256) void leaf_gather_kernel(const GatherGroup g) {
 // clamped column instead of a branch: fac = sum_i err[x][i] * P[s][x - half + i] in the reference's tap order
 // (probability.cpp:187-196 builds the leaf vector, matrix_cache.cpp:28 multiplies it).
 constexpr int kFastRows = 8;
-template <int NLEAF, int NDEV, bool MUL, int NSRC>
+template <int NLEAF, int NDEV, bool MUL, int NSRC, bool MISSING = false>
 __global__ __launch_bounds__(256) void leaf_gather_fast_kernel(const GatherGroup g) {
     CAFE_GATHER_OP();
     const int f = (blockIdx.x * 256 + threadIdx.x) * 2;
@@ -115,6 +121,7 @@ __global__ __launch_bounds__(256) void leaf_gather_fast_kernel(const GatherGroup
     constexpr int NL = NLEAF > 0 ? NLEAF : 1;               // (zero-length arrays are not allowed)
     unsigned o0[NL][NDEV], o1[NL][NDEV];
     double w0[NL][NDEV], w1[NL][NDEV];
+    int xm0[MISSING ? NL : 1], xm1[MISSING ? NL : 1];      // MISSING: the two columns' counts as read (either, both or neither missing)
     const double* P[NL];
     const double* S[NSRC > 0 ? NSRC : 1];                   // factor panels, row r0 of this category
     unsigned m0[NSRC > 0 ? NSRC : 1], m1[NSRC > 0 ? NSRC : 1];
@@ -131,7 +138,8 @@ __global__ __launch_bounds__(256) void leaf_gather_fast_kernel(const GatherGroup
 #pragma unroll
     for (int l = 0; l < NLEAF; ++l) {
         const int32_t* cnt = a->counts + (int64_t)a->taxon[l] * a->counts_ld + g.f0 + f;
-        const int x0 = cnt[0], x1 = cnt[1];
+        int x0 = cnt[0], x1 = cnt[1];
+        if (MISSING) { xm0[l] = x0; xm1[l] = x1; x0 = count_index(x0); x1 = count_index(x1); }
 #pragma unroll
         for (int i = 0; i < NDEV; ++i) {
             const int c0 = x0 - half + i, c1 = x1 - half + i;
@@ -153,8 +161,13 @@ __global__ __launch_bounds__(256) void leaf_gather_fast_kernel(const GatherGroup
             for (int l = 0; l < NLEAF; ++l) {
                 const double* row = P[l] + (unsigned)rr * ldp;
                 if (NDEV == 1) {
-                    x *= row[o0[l][0]];
-                    y *= row[o1[l][0]];
+                    if (MISSING) {
+                        x *= leaf_factor_or_one(xm0[l], row[o0[l][0]]);
+                        y *= leaf_factor_or_one(xm1[l], row[o1[l][0]]);
+                    } else {
+                        x *= row[o0[l][0]];
+                        y *= row[o1[l][0]];
+                    }
                 } else {
                     double fx = 0.0, fy = 0.0;
 #pragma unroll
@@ -162,6 +175,7 @@ __global__ __launch_bounds__(256) void leaf_gather_fast_kernel(const GatherGroup
                         fx += row[o0[l][i]] * w0[l][i];
                         fy += row[o1[l][i]] * w1[l][i];
                     }
+                    if (MISSING) { fx = leaf_factor_or_one(xm0[l], fx); fy = leaf_factor_or_one(xm1[l], fy); }
                     x *= fx;
                     y *= fy;
                 }
@@ -189,14 +203,15 @@ __global__ __launch_bounds__(256) void leaf_gather_fast_kernel(const GatherGroup
         }
 }
 
-template <int NLEAF, int NDEV, int NSRC>
+template <int NLEAF, int NDEV, int NSRC, bool MISSING>
 static void launch_fast3(const GatherGroup& g, int mode, dim3 grid, hipStream_t stream) {
-    if (mode) hipLaunchKernelGGL((leaf_gather_fast_kernel<NLEAF, NDEV, true, NSRC>), grid, dim3(256), 0, stream, g);
-    else hipLaunchKernelGGL((leaf_gather_fast_kernel<NLEAF, NDEV, false, NSRC>), grid, dim3(256), 0, stream, g);
+    if (mode) hipLaunchKernelGGL((leaf_gather_fast_kernel<NLEAF, NDEV, true, NSRC, MISSING>), grid, dim3(256), 0, stream, g);
+    else hipLaunchKernelGGL((leaf_gather_fast_kernel<NLEAF, NDEV, false, NSRC, MISSING>), grid, dim3(256), 0, stream, g);
 }
 template <int NLEAF, int NDEV>
-static void launch_fast(const GatherGroup& g, int mode, dim3 grid, hipStream_t stream) {
-    launch_fast3<NLEAF, NDEV, 0>(g, mode, grid, stream);
+static void launch_fast(const GatherGroup& g, int mode, bool missing, dim3 grid, hipStream_t stream) {
+    if (missing) launch_fast3<NLEAF, NDEV, 0, true>(g, mode, grid, stream);
+    else launch_fast3<NLEAF, NDEV, 0, false>(g, mode, grid, stream);
 }
 
 // Assemble pass: the parent's panel from the TRANSPOSED factor panels of its de-duplicated interior children (and its
@@ -211,7 +226,9 @@ constexpr int kAsmS = kAsmT + 1;            // LDS row stride (doubles): column-
 // LEAFT: the leaf children come as transposed copies of their matrices (GatherArgs::lt, no error model): they are
 // multiplied in phase A like further factors -- the same products in the same order as the gather of phase B, so the panel
 // has the same bits either way.
-template <int NSRC, int NLEAF, int NDEV, bool MUL, bool LEAFT = false>
+// MISSING: only without LEAFT -- a context with missing cells gets no transposed leaf copies (plan_leaf_transposes), its leaves
+// are gathered in phase B.
+template <int NSRC, int NLEAF, int NDEV, bool MUL, bool LEAFT = false, bool MISSING = false>
 __global__ __launch_bounds__(256) void assemble_t_kernel(const GatherGroup g) {
     __shared__ double tile[kAsmT * kAsmS];
     CAFE_GATHER_OP();
@@ -265,12 +282,15 @@ __global__ __launch_bounds__(256) void assemble_t_kernel(const GatherGroup g) {
     constexpr int NG = LEAFT ? 0 : NLEAF;                   // leaves still to gather on the way out
     constexpr int NL = NG > 0 ? NG : 1;
     constexpr int half = (NDEV - 1) / 2;
+    static_assert(!(MISSING && LEAFT), "the transposed leaf copies are indexed by count: not with missing cells");
     unsigned o[NL][NDEV];
     double wgt[NL][NDEV];
+    int xm[MISSING ? NL : 1];
     const double* P[NL];
 #pragma unroll
     for (int l = 0; l < NG; ++l) {
-        const int x = a->counts[(int64_t)a->taxon[l] * a->counts_ld + g.f0 + f];
+        int x = a->counts[(int64_t)a->taxon[l] * a->counts_ld + g.f0 + f];
+        if (MISSING) { xm[l] = x; x = count_index(x); }
 #pragma unroll
         for (int i = 0; i < NDEV; ++i) {
             const int c = x - half + i;
@@ -292,12 +312,12 @@ __global__ __launch_bounds__(256) void assemble_t_kernel(const GatherGroup g) {
             for (int l = 0; l < NG; ++l) {
                 const double* row = P[l] + (int64_t)(r + row_off) * g.pool.ld;
                 if (NDEV == 1) {
-                    v *= row[o[l][0]];
+                    v *= MISSING ? leaf_factor_or_one(xm[l], row[o[l][0]]) : row[o[l][0]];
                 } else {
                     double fx = 0.0;
 #pragma unroll
                     for (int i = 0; i < NDEV; ++i) fx += row[o[l][i]] * wgt[l][i];
-                    v *= fx;
+                    v *= MISSING ? leaf_factor_or_one(xm[l], fx) : fx;
                 }
             }
             if (MUL) v *= dst[(int64_t)r * ld];
@@ -306,10 +326,17 @@ __global__ __launch_bounds__(256) void assemble_t_kernel(const GatherGroup g) {
     }
 }
 
-template <int NSRC, int NLEAF, int NDEV, bool LEAFT = false>
+template <int NSRC, int NLEAF, int NDEV, bool LEAFT = false, bool MISSING = false>
 static void launch_asm3(const GatherGroup& g, int mode, dim3 grid, hipStream_t stream) {
-    if (mode) hipLaunchKernelGGL((assemble_t_kernel<NSRC, NLEAF, NDEV, true, LEAFT>), grid, dim3(256), 0, stream, g);
-    else hipLaunchKernelGGL((assemble_t_kernel<NSRC, NLEAF, NDEV, false, LEAFT>), grid, dim3(256), 0, stream, g);
+    if (mode) hipLaunchKernelGGL((assemble_t_kernel<NSRC, NLEAF, NDEV, true, LEAFT, MISSING>), grid, dim3(256), 0, stream, g);
+    else hipLaunchKernelGGL((assemble_t_kernel<NSRC, NLEAF, NDEV, false, LEAFT, MISSING>), grid, dim3(256), 0, stream, g);
+}
+// the passes of a context with missing cells: its leaves (if any) gathered on the way out, never from transposed copies
+template <int NSRC>
+static void launch_asm_missing(const GatherGroup& g, int n_leaf, int mode, int ndev, dim3 grid, hipStream_t stream) {
+    if (n_leaf == 0) launch_asm3<NSRC, 0, 1>(g, mode, grid, stream);               // (no count is read)
+    else if (n_leaf == 1) { if (ndev == 1) launch_asm3<NSRC, 1, 1, false, true>(g, mode, grid, stream); else launch_asm3<NSRC, 1, 3, false, true>(g, mode, grid, stream); }
+    else { if (ndev == 1) launch_asm3<NSRC, 2, 1, false, true>(g, mode, grid, stream); else launch_asm3<NSRC, 2, 3, false, true>(g, mode, grid, stream); }
 }
 template <int NSRC>
 static void launch_asm(const GatherGroup& g, int n_leaf, int mode, int ndev, bool leaf_t, dim3 grid, hipStream_t stream) {
@@ -360,7 +387,7 @@ hipError_t launch_leaf_transpose(const LeafTArgs& a, int n_pairs, int n_categori
 
 // h_ops: the group's descriptors on the host (grid extents and the variant: every op of a group has the same n_leaf, n_src
 // and mode -- the schedule groups by them)
-hipError_t launch_leaf_gather_group(const GatherGroup& g, const GatherArgs* h_ops, hipStream_t stream) {
+hipError_t launch_leaf_gather_group(const GatherGroup& g, const GatherArgs* h_ops, hipStream_t stream, bool missing) {
     (void)hipGetLastError();
     if (g.n_ops < 1 || !g.ops || !h_ops) return hipErrorInvalidValue;
     const int n_leaf = h_ops[0].n_leaf, n_src = h_ops[0].n_src, mode = h_ops[0].mode;
@@ -377,6 +404,11 @@ hipError_t launch_leaf_gather_group(const GatherGroup& g, const GatherArgs* h_op
     const int ndev = g.err == nullptr ? 1 : g.n_dev;
     if ((ndev == 1 || ndev == 3) && n_leaf <= 2 && n_src >= 1 && n_src <= 2) {
         dim3 grid(max_ld / kAsmT, (max_rows_store + 15 + max_row_off + kAsmT - 1) / kAsmT, z);
+        if (missing) {
+            if (n_src == 1) launch_asm_missing<1>(g, n_leaf, mode, ndev, grid, stream);
+            else launch_asm_missing<2>(g, n_leaf, mode, ndev, grid, stream);
+            return hipGetLastError();
+        }
         bool leaf_t = n_leaf > 0 && g.leaf_t;              // every leaf of every op has its transposed copy, and this call filled them
         for (int i = 0; i < g.n_ops && leaf_t; ++i)
             for (int l = 0; l < n_leaf; ++l) leaf_t = leaf_t && h_ops[i].lt[l] != nullptr;
@@ -386,12 +418,13 @@ hipError_t launch_leaf_gather_group(const GatherGroup& g, const GatherArgs* h_op
     }
     if ((ndev == 1 || ndev == 3) && n_leaf <= 2 && n_src == 0) {
         dim3 grid((max_ld / 2 + 255) / 256, (max_rows_store + kFastRows - 1) / kFastRows, z);
-        if (n_leaf == 1) { if (ndev == 1) launch_fast<1, 1>(g, mode, grid, stream); else launch_fast<1, 3>(g, mode, grid, stream); }
-        else { if (ndev == 1) launch_fast<2, 1>(g, mode, grid, stream); else launch_fast<2, 3>(g, mode, grid, stream); }
+        if (n_leaf == 1) { if (ndev == 1) launch_fast<1, 1>(g, mode, missing, grid, stream); else launch_fast<1, 3>(g, mode, missing, grid, stream); }
+        else { if (ndev == 1) launch_fast<2, 1>(g, mode, missing, grid, stream); else launch_fast<2, 3>(g, mode, missing, grid, stream); }
         return hipGetLastError();
     }
     dim3 grid((max_ld + 255) / 256, (max_rows_store + kGatherRows - 1) / kGatherRows, z), block(256);
-    hipLaunchKernelGGL(leaf_gather_kernel, grid, block, 0, stream, g);
+    if (missing) hipLaunchKernelGGL(leaf_gather_kernel<true>, grid, block, 0, stream, g);
+    else hipLaunchKernelGGL(leaf_gather_kernel<false>, grid, block, 0, stream, g);
     return hipGetLastError();
 }
 

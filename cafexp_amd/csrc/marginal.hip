@@ -292,7 +292,7 @@ int marginal_impl(cafe_ctx* c, const cafe_params* pr, double level, const cafe_m
 extern "C" {
 
 int cafe_marginal_reconstruct(cafe_ctx* ctx, const cafe_params* params, double level, const cafe_marginal_out* out) {
-    return cafe::guarded(ctx, "cafe_marginal_reconstruct", [&] { return cafe::marginal_impl(ctx, params, level, out); });
+    return cafe::guarded_observed(ctx, "cafe_marginal_reconstruct", [&] { return cafe::marginal_impl(ctx, params, level, out); });
 }
 
 int cafe_debug_marginal_gemm(cafe_ctx* ctx, double* ms, double* flops) {

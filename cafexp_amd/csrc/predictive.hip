@@ -113,7 +113,9 @@ __global__ __launch_bounds__(256) void predictive_gemm_kernel(const PredictiveGe
 // ---------------------------------------------------------------------------------------------------------------- sums
 // One thread per column walks y = 0..M over the GEMM's panel U, forms w[y] from its taps on the fly and adds
 // p_k {sum_{y < x} w, w[x], sum_{y > x} w, sum w, sum y w, sum y^2 w} into the six sums of the (leaf, column): acc[j][f], j-th row
-// `stride` doubles on.  The first category stores, the others add.
+// `stride` doubles on.  The first category stores, the others add.  A missing cell (x = CAFE_COUNT_MISSING) indexes nothing
+// here: every y lies above it, the three totals t0, t1, t2 are what they are for any x, and its w[x] slot carries NaN, by
+// which predictive_finish_kernel knows the cell and turns its tails into NaN.
 constexpr int kSums = 6;
 __global__ __launch_bounds__(256) void predictive_sums_kernel(const double* __restrict__ U, int M, int64_t ld, const int32_t* __restrict__ cnt,
                                                               const double* __restrict__ err, int n_dev, double pk, int first,
@@ -142,6 +144,7 @@ __global__ __launch_bounds__(256) void predictive_sums_kernel(const double* __re
         t1 += (double)y * w;
         t2 += (double)(y * y) * w;
     }
+    if (count_is_missing(x)) obs = __builtin_nan("");      // no observation: the mark predictive_finish_kernel reads (a NaN w[x] comes with a NaN t0)
     const double s[kSums] = {below, obs, above, t0, t1, t2};
 #pragma unroll
     for (int j = 0; j < kSums; ++j) {
@@ -151,15 +154,18 @@ __global__ __launch_bounds__(256) void predictive_sums_kernel(const double* __re
 }
 
 // Per column (blockIdx.x) and leaf (blockIdx.y): the five outputs over the first five of the leaf's six sums, in the order
-// mean, sd, p_below, p_obs, p_above; NaN in all five where W or the total is zero or not finite
+// mean, sd, p_below, p_obs, p_above; NaN in all five where W or the total is zero or not finite.  A missing cell (w[x] NaN beside
+// a total that is not: predictive_sums_kernel) has no observation: its three tail outputs are NaN, its mean and sd -- which read
+// t0, t1, t2 only -- are the model's prediction of the count from the family's other species.
 __global__ __launch_bounds__(256) void predictive_finish_kernel(double* __restrict__ acc, int64_t ld, int64_t stride) {
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (f >= ld) return;
     double* a = acc + (int64_t)blockIdx.y * kSums * stride + f;
     const double below = a[0], obs = a[stride], above = a[2 * stride], t0 = a[3 * stride], t1 = a[4 * stride], t2 = a[5 * stride];
-    const double W = below + obs + above;
     const double nan = __builtin_nan("");
-    const bool bad = evidence_failed(W) || evidence_failed(t0);
+    const bool missing = obs != obs && t0 == t0;
+    const double W = below + obs + above;
+    const bool bad = (!missing && evidence_failed(W)) || evidence_failed(t0);
     const double mean = t1 / t0;
     const double var = fmax(t2 / t0 - mean * mean, 0.0);
     a[0] = bad ? nan : mean;
@@ -208,7 +214,6 @@ int leaf_predictive_impl(cafe_ctx* c, const cafe_params* pr, const cafe_leaf_pre
     double* d_Z = d_acc + (int64_t)kSums * nL * cols;
     double* d_lnl = d_Z + cols;
     if (const int rc = upload_constants(c, pr, &pc)) return rc;
-
     std::vector<double> h_acc((size_t)kSums * nL * cols), h_Z(cols), h_lnl(cols);
     double* const dst[5] = {out->mean, out->sd, out->p_below, out->p_obs, out->p_above};
 

@@ -213,5 +213,5 @@ int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t see
 }  // namespace cafe
 
 extern "C" int cafe_pvalues(cafe_ctx* ctx, const cafe_params* params, int32_t n_simulations, uint64_t seed, double* pvalues) {
-    return cafe::guarded(ctx, "cafe_pvalues", [&] { return cafe::pvalues_impl(ctx, params, n_simulations, seed, pvalues); });
+    return cafe::guarded_observed(ctx, "cafe_pvalues", [&] { return cafe::pvalues_impl(ctx, params, n_simulations, seed, pvalues); });
 }

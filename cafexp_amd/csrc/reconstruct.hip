@@ -400,9 +400,9 @@ int branch_probabilities_impl(cafe_ctx* c, const cafe_params* pr, const int32_t*
 }  // namespace cafe
 
 extern "C" int cafe_reconstruct(cafe_ctx* ctx, const cafe_params* params, const float* root_prior, int32_t* states) {
-    return cafe::guarded(ctx, "cafe_reconstruct", [&] { return cafe::reconstruct_impl(ctx, params, root_prior, states); });
+    return cafe::guarded_observed(ctx, "cafe_reconstruct", [&] { return cafe::reconstruct_impl(ctx, params, root_prior, states); });
 }
 
 extern "C" int cafe_branch_probabilities(cafe_ctx* ctx, const cafe_params* params, const int32_t* sizes, double* out) {
-    return cafe::guarded(ctx, "cafe_branch_probabilities", [&] { return cafe::branch_probabilities_impl(ctx, params, sizes, out); });
+    return cafe::guarded_observed(ctx, "cafe_branch_probabilities", [&] { return cafe::branch_probabilities_impl(ctx, params, sizes, out); });
 }

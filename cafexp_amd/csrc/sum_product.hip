@@ -118,8 +118,10 @@ __global__ __launch_bounds__(256) void marginal_gemm_kernel(const GemmParams a) 
 }
 
 // The scorer's leaf factor (leaf_reduce.hip): P[i][x], or with an error model sum_t err[x][t] P[i][x - half + t], taps
-// outside [0, M] dropped, in the scorer's tap order.
+// outside [0, M] dropped, in the scorer's tap order.  A missing cell's factor is exactly 1.0 (cafe_kernels.h); the posterior
+// calls built on this unit refuse a context that has one (guarded_observed, cafe_call.h), all but the leave-one-out check.
 __device__ inline double leaf_factor(const double* __restrict__ P, int ldp, int i, int x, const double* __restrict__ err, int n_dev, int M) {
+    if (count_is_missing(x)) return leaf_factor_or_one(x, 0.0);
     const double* row = P + (int64_t)i * ldp;
     if (err == nullptr) return row[x];
     const int half = (n_dev - 1) / 2;

@@ -77,6 +77,7 @@ private:
 clade* parse_newick(const std::string& text, bool parse_to_lambdas = false);
 
 // ---------------------------------------------------------------- families (src/gene_family.{h,cpp})
+constexpr int kCountMissing = -1;            // CAFE_COUNT_MISSING: the cell's count is unknown and is summed out (include/cafe_mi355x.h)
 class gene_family {
 public:
     void set_id(const std::string& id) { _id = id; }
@@ -84,7 +85,10 @@ public:
     std::string id() const { return _id; }
     void set_species_size(const std::string& species, int count);
     int get_species_size(const std::string& species) const;          // throws when absent (gene_family.cpp:36)
-    int get_max_size() const;
+    int get_max_size() const;                                        // over the observed cells (0 when none is)
+    // a cell whose count is unknown (kCountMissing: `--missing`, `--mask-cells`); false for a species the family does not have
+    bool is_missing(const std::string& species) const;
+    size_t n_missing() const;
     std::vector<std::string> get_species() const;
     bool species_size_match(const gene_family& o) const { return _sizes == o._sizes; }
     bool exists_at_root(const clade* tree) const;                    // gene_family.cpp:60
@@ -367,6 +371,14 @@ struct leaf_predictive_summary {
 // mean, sd, direction, p, adjusted p) and <Model>_species_fit.tab (leaf_species_fit)
 leaf_predictive_summary write_leaf_predictive_reports(const leaf_predictive_result& res, double threshold, const std::string& model_identifier,
                                                       const std::string& dir, const std::vector<gene_family>& families);
+// One imputed cell: the model's prediction of a missing count from the family's observed species.  lo / hi: the central 95 %
+// interval of the normal distribution with the predictive mean and sd, rounded outwards to whole genes and cut at 0 (the C ABI
+// returns the two moments of the predictive distribution, not its quantiles)
+struct imputed_cell { size_t family, species; double mean, sd; long lo, hi; };
+std::vector<imputed_cell> imputed_cells(const leaf_predictive_result& res);
+// <Model>_imputed_counts.tab: family, species, mean, sd, lo, hi -- one line per missing cell (observed < 0), table order.  Returns the lines
+size_t write_imputed_counts(const leaf_predictive_result& res, const std::string& model_identifier, const std::string& dir,
+                            const std::vector<gene_family>& families);
 
 // cafe_sample_histories' counts, [draw][index in the caller's node order] (failed: [family])
 struct history_result {
@@ -750,7 +762,17 @@ struct user_data {
     std::vector<gene_family> gene_families;
     std::map<int, int> rootdist;
 };
-void read_gene_families(std::istream& in, const clade* tree, std::vector<gene_family>& out);    // io.cpp:134
+// missing_tokens (or nullptr: none): a cell spelled like one of them, blanks around it ignored, becomes kCountMissing; every
+// other cell goes through atoi as in the reference (io.cpp:134), where "NA" reads as 0
+void read_gene_families(std::istream& in, const clade* tree, std::vector<gene_family>& out, const std::set<std::string>* missing_tokens = nullptr);
+// "NA,?,-" -> {"NA", "?", "-"} (empty entries dropped)
+std::set<std::string> parse_missing_tokens(const std::string& list);
+// Lines `family<TAB>species[<TAB>anything]` (a line that starts with '#' and empty lines are skipped; the first two columns of
+// <Model>_leaf_outliers.tab are such a file): every family with that id gets kCountMissing for that species.  Throws on an id
+// or a species the table does not have.  Returns the number of cells newly marked.
+size_t mask_cells(std::istream& in, std::vector<gene_family>& fams);
+struct missing_summary { size_t cells = 0, families = 0; };
+missing_summary count_missing(const std::vector<gene_family>& fams);
 void read_error_model_file(std::istream& in, error_model* em);                                  // io.cpp:226
 void write_error_model_file(std::ostream& ost, const error_model& em);                          // io.cpp:275
 void read_rootdist(std::istream& in, std::map<int, int>& out);                                  // user_data.cpp:103

@@ -57,6 +57,8 @@ static void create_device_objects(const lambda* lam, const std::vector<const cla
     pb.n_lambdas = lam->count(); pb.single_lambda = ml ? 0 : 1; pb.max_categories = max_categories;
     pb.n_deviations = n_deviations;
     pb.device = device; pb.flags = 0; pb.workspace_limit = workspace_limit;
+    // a table with unknown cells (kCountMissing, only ever from --missing / --mask-cells): the library sums them out
+    for (int64_t i = 0; counts && i < n_families * T; ++i) if (counts[i] == kCountMissing) { pb.flags |= CAFE_FLAG_MISSING_COUNTS; break; }
     char err[512];
     if (devices && !devices->empty() && out_sharded) {
         std::vector<int32_t> dev(devices->begin(), devices->end());

@@ -216,9 +216,20 @@ int gene_family::get_species_size(const std::string& species) const {
 }
 
 int gene_family::get_max_size() const {
-    int m = 0;
+    int m = 0;                                   // (a missing cell, kCountMissing < 0, never raises it)
     for (const auto& kv : _sizes) m = std::max(m, kv.second);
     return m;
+}
+
+bool gene_family::is_missing(const std::string& species) const {
+    auto it = _sizes.find(lower(species));
+    return it != _sizes.end() && it->second == kCountMissing;
+}
+
+size_t gene_family::n_missing() const {
+    size_t n = 0;
+    for (const auto& kv : _sizes) n += kv.second == kCountMissing;
+    return n;
 }
 
 std::vector<std::string> gene_family::get_species() const {
@@ -420,7 +431,51 @@ std::vector<std::string> split(const std::string& s, char delim) {
 }
 }  // namespace
 
-void read_gene_families(std::istream& in, const clade* tree, std::vector<gene_family>& out) {
+static std::string trimmed(const std::string& s) {
+    size_t a = 0, b = s.size();
+    while (a < b && std::isspace((unsigned char)s[a])) ++a;
+    while (b > a && std::isspace((unsigned char)s[b - 1])) --b;
+    return s.substr(a, b - a);
+}
+
+std::set<std::string> parse_missing_tokens(const std::string& list) {
+    std::set<std::string> out;
+    for (const std::string& t : split(list, ',')) if (!trimmed(t).empty()) out.insert(trimmed(t));
+    return out;
+}
+
+size_t mask_cells(std::istream& in, std::vector<gene_family>& fams) {
+    std::multimap<std::string, size_t> by_id;
+    for (size_t i = 0; i < fams.size(); ++i) by_id.emplace(fams[i].id(), i);
+    std::string line;
+    size_t marked = 0;
+    while (std::getline(in, line)) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        const std::vector<std::string> tk = split(line, '\t');
+        if (tk.size() < 2) throw std::runtime_error("--mask-cells: expected family<TAB>species, got '" + line + "'");
+        const auto range = by_id.equal_range(tk[0]);
+        if (range.first == range.second) throw std::runtime_error("--mask-cells: family " + tk[0] + " is not in the table");
+        for (auto it = range.first; it != range.second; ++it) {
+            gene_family& f = fams[it->second];
+            const int was = f.get_species_size(trimmed(tk[1]));          // throws for a species the table does not have
+            if (was != kCountMissing) { f.set_species_size(trimmed(tk[1]), kCountMissing); ++marked; }
+        }
+    }
+    return marked;
+}
+
+missing_summary count_missing(const std::vector<gene_family>& fams) {
+    missing_summary s;
+    for (const gene_family& f : fams) { const size_t n = f.n_missing(); s.cells += n; s.families += n > 0; }
+    return s;
+}
+
+void read_gene_families(std::istream& in, const clade* tree, std::vector<gene_family>& out, const std::set<std::string>* missing_tokens) {
+    auto cell = [&](const std::string& s) {
+        if (missing_tokens && !missing_tokens->empty() && missing_tokens->count(trimmed(s))) return kCountMissing;
+        return std::atoi(s.c_str());
+    };
     // CAFE format: one header line "Desc<TAB>Family ID<TAB>species...", then one family per line.
     // CAFExp format: "#species" header lines, counts in tree order, id last (io.cpp:134-215).
     std::string line;
@@ -452,12 +507,12 @@ void read_gene_families(std::istream& in, const clade* tree, std::vector<gene_fa
             for (size_t i = 0; i < tk.size(); ++i) {
                 if (i == 0) fam.set_desc(tk[i]);
                 else if (i == 1) fam.set_id(tk[i]);
-                else if (i < columns.size()) fam.set_species_size(columns[i], std::atoi(tk[i].c_str()));
+                else if (i < columns.size()) fam.set_species_size(columns[i], cell(tk[i]));
             }
         } else {
             for (size_t i = 0; i < tk.size(); ++i) {
                 auto it = leaf_of_index.find(i);
-                if (it != leaf_of_index.end()) fam.set_species_size(it->second, std::atoi(tk[i].c_str()));
+                if (it != leaf_of_index.end()) fam.set_species_size(it->second, cell(tk[i]));
                 else if (i + 1 == tk.size()) fam.set_id(tk[i]);
             }
         }

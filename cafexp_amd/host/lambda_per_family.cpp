@@ -31,6 +31,7 @@ void initialization_failure_advice(std::ostream& ost, const std::vector<gene_fam
         bool first = true;
         for (const std::string& sp : gf.get_species()) {
             const int c = gf.get_species_size(sp);
+            if (c == kCountMissing) continue;
             lo = first ? c : std::min(lo, c);
             hi = first ? c : std::max(hi, c);
             first = false;

@@ -62,6 +62,11 @@ leaf_predictive_summary write_leaf_predictive_reports(const leaf_predictive_resu
         table << families[f].id();
         for (size_t t = 0; t < T; ++t) {
             const size_t at = f * T + t;
+            if (res.observed[at] == kCountMissing && std::isfinite(res.mean[at])) {      // no observation: the prediction alone
+                std::snprintf(buf, sizeof buf, "\t%.6g:%.6g:NA:NA", res.mean[at], res.sd[at]);
+                table << buf;
+                continue;
+            }
             if (!std::isfinite(res.p_obs[at])) { table << "\t-"; ++sum.failed_cells; continue; }
             std::snprintf(buf, sizeof buf, "\t%.6g:%.6g:%.6g:%.6g", res.mean[at], res.sd[at], res.p_below[at] + res.p_obs[at], res.p_obs[at] + res.p_above[at]);
             table << buf;
@@ -88,6 +93,36 @@ leaf_predictive_summary write_leaf_predictive_reports(const leaf_predictive_resu
         sum.log_pseudo_likelihood += fit[t].log_p_obs;
     }
     return sum;
+}
+
+std::vector<imputed_cell> imputed_cells(const leaf_predictive_result& res) {
+    const size_t T = res.n_species();
+    std::vector<imputed_cell> out;
+    for (size_t at = 0; at < res.observed.size(); ++at) {
+        if (res.observed[at] != kCountMissing) continue;
+        imputed_cell c{at / T, at % T, res.mean[at], res.sd[at], 0, 0};
+        if (std::isfinite(c.mean) && std::isfinite(c.sd)) {
+            c.lo = std::max(0L, (long)std::floor(c.mean - 1.959963984540054 * c.sd));
+            c.hi = std::max(c.lo, (long)std::ceil(c.mean + 1.959963984540054 * c.sd));
+        }
+        out.push_back(c);
+    }
+    return out;
+}
+
+size_t write_imputed_counts(const leaf_predictive_result& res, const std::string& model_identifier, const std::string& dir,
+                            const std::vector<gene_family>& families) {
+    std::ofstream f((dir.empty() ? std::string("results") : dir) + "/" + model_identifier + "_imputed_counts.tab");
+    f << "#FamilyID\tSpecies\tMean\tSD\tLo95\tHi95\t(the count of a missing cell predicted from the family's observed species; Lo95 - Hi95: the central 95 % "
+         "interval of the normal distribution with that mean and sd, in whole genes)" << std::endl;
+    char buf[160];
+    const std::vector<imputed_cell> cells = imputed_cells(res);
+    for (const imputed_cell& c : cells) {
+        if (std::isfinite(c.mean) && std::isfinite(c.sd)) std::snprintf(buf, sizeof buf, "\t%.6g\t%.6g\t%ld\t%ld", c.mean, c.sd, c.lo, c.hi);
+        else std::snprintf(buf, sizeof buf, "\t-\t-\t-\t-");
+        f << families[c.family].id() << "\t" << res.species[c.species] << buf << std::endl;
+    }
+    return cells.size();
 }
 
 }  // namespace cafe

@@ -43,6 +43,12 @@ static void usage() {
         "                  and their information; Rao score tests of a rate shift on every branch and in every clade (and, under death\n"
         "                  rates, of birth and death jointly), Holm-adjusted -> <Model>_rate_shift_scan.tab in -o OUTDIR (default results), and\n"
         "                  <Model>_rate_shift_lambda_tree.txt (-y format) when a clade passes PVALUE (default 0.05); one GPU, not with -b or --simulate\n"
+        "                  [--missing TOKENS] [--mask-cells FILE]   cells whose count is unknown: spelled like one of the comma list TOKENS\n"
+        "                  (e.g. NA,?,-), or named by a line family<TAB>species of FILE (the first two columns of <Model>_leaf_outliers.tab\n"
+        "                  are such a file).  They are summed out of the likelihood (the family on the tree without that species); M and R\n"
+        "                  come from the observed cells; with --leaf-predictive also <Model>_imputed_counts.tab (family, species, mean,\n"
+        "                  sd, 95 %% interval of the predicted count).  Works with -b and --gpus; not with --pvalues, --reconstruct[-marginal],\n"
+        "                  --sample-histories, --standard-errors, --expected-events, --rate-shift-scan\n"
         "                  [--leaf-predictive [-P PVALUE]]   after the search: for every family and species the distribution of the species'\n"
         "                  count predicted from the counts of all the other species under the fitted model -> in -o OUTDIR (default results)\n"
         "                  <Model>_leaf_predictive.tab (mean:sd:p_low:p_high, the two one-sided tails of the observed count),\n"
@@ -201,6 +207,7 @@ int main(int argc, char** argv) {
     bool do_events = false;                                      // --expected-events
     bool do_rate_shift = false;                                  // --rate-shift-scan
     bool do_leaf_predictive = false;                             // --leaf-predictive
+    std::string missing_list, mask_path;                         // --missing TOKENS, --mask-cells FILE: cells whose count is unknown
     bool root_sum = false;                                       // --root-sum: score under CAFE_ROOT_SUM
     bool estimate_rootdist = false;                              // --estimate-rootdist [ROUNDS]
     int rootdist_rounds = 10;
@@ -226,6 +233,8 @@ int main(int argc, char** argv) {
         else if (a == "--expected-events") do_events = true;
         else if (a == "--rate-shift-scan") do_rate_shift = true;
         else if (a == "--leaf-predictive") do_leaf_predictive = true;
+        else if (a == "--missing") missing_list = next();
+        else if (a == "--mask-cells") mask_path = next();
         else if (a == "--root-sum") root_sum = true;
         else if (a == "--estimate-rootdist") { estimate_rootdist = root_sum = true; std::string v = optional(); if (!v.empty()) rootdist_rounds = std::stoi(v); }
         else if (a == "--rootdist-probs") rootdist_probs = next();
@@ -273,6 +282,18 @@ int main(int argc, char** argv) {
                              simulate_n, simulate_on_device, have_seed ? seed : randomizer_engine(), device, sim_workspace, out_dir, mu_list);
     }
     if (tree_path.empty() || fam_path.empty()) { usage(); return 2; }
+    if (!missing_list.empty() || !mask_path.empty()) {           // unknown cells are summed out by the scorer, -b and --leaf-predictive only
+        const char* why = nullptr;
+        if (!missing_list.empty() && parse_missing_tokens(missing_list).empty()) why = "--missing: TOKENS must name at least one spelling, e.g. NA,?,-";
+        else if (pvalue_sims > 0) why = "--pvalues simulates complete families: it is not supported on a table with missing cells (--missing / --mask-cells)";
+        else if (do_reconstruct) why = "--reconstruct reads every leaf count: it is not supported on a table with missing cells (--missing / --mask-cells)";
+        else if (do_marginal) why = "--reconstruct-marginal is not ported to missing cells: it is not supported with --missing / --mask-cells";
+        else if (do_histories) why = "--sample-histories is not ported to missing cells: it is not supported with --missing / --mask-cells";
+        else if (do_standard_errors) why = "--standard-errors is not ported to missing cells: it is not supported with --missing / --mask-cells";
+        else if (do_events) why = "--expected-events is not ported to missing cells: it is not supported with --missing / --mask-cells";
+        else if (do_rate_shift) why = "--rate-shift-scan is not ported to missing cells: it is not supported with --missing / --mask-cells";
+        if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
+    }
     if (estimate_mu || !mu_list.empty()) {
         const char* why = nullptr;
         if (estimate_mu && !mu_list.empty()) why = "--mu fixes the death rates and --estimate-mu searches them: give one of the two";
@@ -349,7 +370,13 @@ int main(int argc, char** argv) {
         {
             std::ifstream f(fam_path);
             if (!f.is_open()) throw std::runtime_error(fam_path + ": Failed to open. Exiting...");
-            read_gene_families(f, d.p_tree.get(), d.gene_families);
+            const std::set<std::string> tokens = parse_missing_tokens(missing_list);
+            read_gene_families(f, d.p_tree.get(), d.gene_families, missing_list.empty() ? nullptr : &tokens);
+        }
+        if (!mask_path.empty()) {
+            std::ifstream f(mask_path);
+            if (!f.is_open()) throw std::runtime_error("Failed to open " + mask_path + ". Exiting...");
+            mask_cells(f, d.gene_families);
         }
         compute_max_sizes(d.gene_families, d.max_family_size, d.max_root_family_size);
         if (force_m > 0) { d.max_family_size = force_m; d.max_root_family_size = force_r; }
@@ -546,6 +573,8 @@ int main(int argc, char** argv) {
         if (!out_dir.empty()) {                                  // the two files of estimator::compute (execute.cpp:49-54)
             std::ofstream rf(out_dir + "/" + mdl->name() + "_results.txt");
             mdl->write_vital_statistics(rf, score);
+            const missing_summary ms = count_missing(d.gene_families);
+            if (ms.cells > 0) rf << "Missing cells: " << ms.cells << " in " << ms.families << " families (summed out)" << std::endl;
             rf.precision(17);
             for (size_t r = 0; r < em_rounds.size(); ++r)
                 rf << "Root distribution round " << r << ": -lnL " << em_rounds[r].neg_lnl << " " << em_rounds[r].rates << std::endl;
@@ -673,6 +702,7 @@ int main(int argc, char** argv) {
             const std::string dir = out_dir.empty() ? "results" : out_dir;
             if (::mkdir(dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("Failed to create directory " + dir);
             predictive = write_leaf_predictive_reports(lp, test_pvalue, mdl->name(), dir, d.gene_families);
+            if (count_missing(d.gene_families).cells > 0) write_imputed_counts(lp, mdl->name(), dir, d.gene_families);
             predictive_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         }
         // standard errors of what the search estimated, from the per-family scores of the searched objective at the optimum

@@ -26,8 +26,10 @@ import numpy as np
 __all__ = [
     "Node", "parse_newick", "Problem", "Params", "read_family_table", "max_sizes", "exists_at_root",
     "read_error_model", "default_error_model", "error_model_table", "prior_uniform", "prior_poisson",
-    "prior_rootdist", "build_problem", "shard_families",
+    "prior_rootdist", "build_problem", "shard_families", "COUNT_MISSING",
 ]
+
+COUNT_MISSING = -1      # CAFE_COUNT_MISSING: the cell's count is unknown (include/cafe_mi355x.h)
 
 _TOKEN = re.compile(r"\(|\)|[^\s\(\)\:\;\,]+|\:[+-]?[0-9]*\.?[0-9]+(?:[eE][+-]?[0-9]+)?|\,|\;")
 
@@ -132,6 +134,7 @@ class Problem:
     n_lambdas: int = 1
     single_lambda: bool = True
     n_deviations: int = 0
+    missing_counts: bool = False  # CAFE_FLAG_MISSING_COUNTS: counts may hold COUNT_MISSING
     taxa: List[str] = field(default_factory=list)
     family_ids: List[str] = field(default_factory=list)
     node_names: List[str] = field(default_factory=list)
@@ -167,9 +170,12 @@ class Params:
         return self.multipliers is not None
 
 
-def read_family_table(text: str) -> Tuple[List[str], List[str], np.ndarray]:
+def read_family_table(text: str, missing_tokens: Sequence[str] = ()) -> Tuple[List[str], List[str], np.ndarray]:
     """CAFE-format table (io.cpp:164-176, :189-197): header `Desc<TAB>Family ID<TAB>sp...`, then rows.
-    Returns (species names, family ids, counts[F, S])."""
+    Returns (species names, family ids, counts[F, S]).  A cell spelled like one of `missing_tokens` (e.g. "NA", "?", "-";
+    surrounding blanks ignored) becomes COUNT_MISSING; with none given (the default) every cell goes through atoi as in the
+    reference, where such a cell reads as 0."""
+    missing = {t.strip() for t in missing_tokens if t.strip() != ""}
     lines = [ln.rstrip("\r") for ln in text.split("\n")]
     lines = [ln for ln in lines if ln != ""]
     if not lines:
@@ -181,7 +187,7 @@ def read_family_table(text: str) -> Tuple[List[str], List[str], np.ndarray]:
     for ln in lines[1:]:
         tk = ln.split("\t")
         ids.append(tk[1] if len(tk) > 1 else "")
-        vals = [_atoi(x) for x in tk[2:2 + len(species)]]
+        vals = [COUNT_MISSING if x.strip() in missing else _atoi(x) for x in tk[2:2 + len(species)]]
         vals += [0] * (len(species) - len(vals))
         rows.append(vals)
     if not rows:
@@ -195,15 +201,16 @@ def _atoi(s: str) -> int:
 
 
 def max_sizes(counts: np.ndarray) -> Tuple[int, int]:
-    """(M, R) from the largest observed count (user_data.cpp:45-46)."""
-    mx = int(counts.max()) if counts.size else 0
+    """(M, R) from the largest observed count (user_data.cpp:45-46); missing cells (COUNT_MISSING) are no observation."""
+    mx = max(int(counts.max()), 0) if counts.size else 0
     r = max(30, int(round(mx * 1.25)))          # std::rint: ties to even, like Python's round()
     m = mx + max(50, mx // 5)
     return m, r
 
 
 def exists_at_root(root: Node, col_of_leaf: Dict[int, int], counts: np.ndarray) -> np.ndarray:
-    """Boolean mask [F]: every child subtree of the root holds a leaf with count > 0 (gene_family.cpp:60-89)."""
+    """Boolean mask [F]: every child subtree of the root holds a leaf with count > 0 (gene_family.cpp:60-89).  A missing
+    cell (COUNT_MISSING) counts as absent."""
     ok = np.ones(counts.shape[0], dtype=bool)
     for child in root.children:
         cols = [col_of_leaf[id(l)] for l in child.leaves()]
@@ -300,10 +307,16 @@ def prior_rootdist(R: int, rootdist: Dict[int, int]) -> np.ndarray:
 def build_problem(tree: Node, species: Sequence[str], family_ids: Sequence[str], counts: np.ndarray,
                   lambda_tree: Optional[Node] = None, root_filter: bool = True,
                   max_family_size: Optional[int] = None, max_root_family_size: Optional[int] = None,
-                  n_deviations: int = 0) -> Problem:
+                  n_deviations: int = 0, missing_tokens: Sequence[str] = ()) -> Problem:
     """Flatten (tree, table) into a Problem.  M and R come from the unfiltered table, then families that
     do not exist at the root are dropped -- the order the reference uses (user_data.cpp:118 then
-    cafexp.cpp:189)."""
+    cafexp.cpp:189).  `counts` may be the table's text instead of an array: it is then read with read_family_table(counts,
+    missing_tokens) and `species` / `family_ids` may be None.  For an ARRAY the tokens spell nothing: a non-empty
+    missing_tokens is then only the switch that says "cells equal to COUNT_MISSING in this array are meant" -- they set
+    Problem.missing_counts (and with it CAFE_FLAG_MISSING_COUNTS); without it a negative cell is left for cafe_create to reject,
+    as before.  M, R and the root filter look at the observed cells only."""
+    if isinstance(counts, str):
+        species, family_ids, counts = read_family_table(counts, missing_tokens)
     nodes = tree.postorder()
     index = {id(n): i for i, n in enumerate(nodes)}
     lower = {s.lower(): j for j, s in enumerate(species)}     # species lookup is case-insensitive (gene_family.h:10-25)
@@ -343,7 +356,7 @@ def build_problem(tree: Node, species: Sequence[str], family_ids: Sequence[str],
         single = False
     return Problem(parent=parent, branch_length=length, lambda_index=lam_idx, leaf_taxon=leaf_taxon, counts=cnt,
                    max_family_size=m, max_root_family_size=r, n_lambdas=n_lambdas, single_lambda=single,
-                   n_deviations=n_deviations, taxa=taxa, family_ids=ids, node_names=[n.key() for n in nodes])
+                   n_deviations=n_deviations, missing_counts=bool(len(tuple(missing_tokens)) and (cnt == COUNT_MISSING).any()), taxa=taxa, family_ids=ids, node_names=[n.key() for n in nodes])
 
 
 def shard_families(n_families: int, world_size: int, rank: int) -> Tuple[int, int]:

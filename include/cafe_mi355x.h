@@ -81,6 +81,24 @@ typedef struct cafe_problem {
 #define CAFE_FLAG_NO_SUBTREE_DEDUP 2 /* one panel column per family at every node, instead of one per distinct pattern of
                                         leaf counts under the node (the same sharing as build_reference_list, applied per
                                         subtree; values are identical either way) */
+/* Missing cells.  With CAFE_FLAG_MISSING_COUNTS set, a cell of `counts` may hold CAFE_COUNT_MISSING: the species' count for that
+ * family is unknown and is summed out.  A missing leaf's factor is EXACTLY 1.0 for every parent size, in every category, with or
+ * without an error model (no taps are applied to it): sum_c P[s][c] = 1 over all c >= 0 in the untruncated process, so this is
+ * the likelihood of the family on the tree with that leaf removed.  It is NOT the truncated row sum sum_{c <= M} P[s][c].  A
+ * family whose cells are all missing is allowed; its value is what the prune then gives (every leaf factor 1).  Any other
+ * negative count, and every negative count without the flag, is CAFE_ERR_ARGUMENT.  M and R stay the caller's inputs (compute
+ * them from the observed cells).  Identical families still share a column -- the missing pattern is part of a family's
+ * identity -- and a context created with the flag whose table has no missing cell behaves exactly as one created without it
+ * (the same kernels, the same bits).
+ * Contexts whose table has a missing cell are accepted by cafe_score, cafe_score_partial, cafe_family_results, cafe_root_max,
+ * cafe_root_posterior, cafe_score_per_family(_lm), cafe_leaf_predictive, cafe_shard_plan(_scaled) and cafe_sharded_*.
+ * cafe_leaf_predictive returns for a missing cell the predictive mean and sd of the count given the family's observed species;
+ * its p_below, p_obs and p_above are NaN there (nothing was observed), and log_evidence is over the observed cells.
+ * cafe_pvalues, cafe_reconstruct, cafe_branch_probabilities, cafe_marginal_reconstruct, cafe_sample_histories,
+ * cafe_score_gradient, cafe_branch_scores and cafe_expected_events return CAFE_ERR_STATE ("... the table has missing cells")
+ * before anything is enqueued; the context stays usable. */
+#define CAFE_FLAG_MISSING_COUNTS 4
+#define CAFE_COUNT_MISSING (-1)
 
 enum { CAFE_MODEL_BASE = 0, CAFE_MODEL_GAMMA = 1 };
 
