@@ -35,22 +35,48 @@ int guarded_observed(cafe_ctx* c, const char* entry, Fn&& fn) {
         HIP_TRY(c, hipGetLastError());                                           \
     } while (0)
 
+// Every call that builds matrices opens here: nothing of the call before it is readable any more, and what this one leaves
+// becomes readable when it sets its final state (LastCall, cafe_ctx.h)
+inline void open_call(cafe_ctx* c, int K, hipStream_t s) {
+    c->last.state = LastCall::kNone;
+    c->last.stream = s;
+    c->last.K = K;
+}
+
 // Opens a call that needs this call's transition matrices and nothing else of the scorer: on the context's own stream
 // (-> *stream), the previous call's results dropped, the matrices of K categories built (prepare_matrices).  Argument
 // checks come before it, in the caller.
 inline int begin_matrix_call(cafe_ctx* c, const double* lambdas, const double* multipliers, int K, hipStream_t* stream) {
     HIP_TRY(c, hipSetDevice(c->device));
     *stream = c->stream;
-    c->have_results = false;
-    c->last_stream = c->stream;
-    c->K_last = K;
+    open_call(c, K, c->stream);
     return prepare_matrices(c, lambdas, multipliers, K, c->stream);
+}
+
+// A call failed behind an enqueue: whatever it left in flight is drained (best effort; not when the communicator it began with
+// was aborted on the way -- a peer is gone, and what waits for it on the stream may never end), the pinned stage is free again,
+// and nothing of the call can be read back.  Every failure return behind an enqueue comes through here.
+inline void fail_after_enqueue(cafe_ctx* c, hipStream_t s) {
+    const bool aborted = c->last.had_comm && !c->comm;
+    if (c->device_ready && !aborted && hipSetDevice(c->device) == hipSuccess) (void)hipStreamSynchronize(s);
+    c->upload_pending = false;
+    c->last.state = LastCall::kNone;
+}
+
+// The gate of the read-backs: what the last call must have left -- its matrices and launches (kScored or kMatricesOnly), or a
+// scorer's per-family results (kScored alone; the reference leaves `results` empty / stale on a rejected call,
+// gamma_core.cpp:173-179).  CAFE_ERR_STATE otherwise.
+enum LastNeed { kCompletedCall, kScorerResults };
+inline int require_last(cafe_ctx* c, const char* entry, LastNeed what = kCompletedCall) {
+    if (c->last.state == LastCall::kScored || (what == kCompletedCall && c->last.state == LastCall::kMatricesOnly)) return CAFE_OK;
+    set_err(c, "%s: %s", entry, what == kCompletedCall ? "no completed call" : "the last call was rejected (+inf) or no call was made");
+    return CAFE_ERR_STATE;
 }
 
 // What the last call enqueued has finished (read-backs and diagnostics)
 inline int wait_last_call(cafe_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->last_stream));
+    HIP_TRY(c, hipStreamSynchronize(c->last.stream));
     return CAFE_OK;
 }
 

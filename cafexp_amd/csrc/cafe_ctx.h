@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/cafe_mi355x.h"
@@ -83,6 +84,39 @@ inline int64_t round_up64(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 struct RootPosteriorArgs;                    // root_sum.h
 
+// What kind of scorer call this is, built once at the top of enqueue (cafe_score.hip): kernel arguments, the launches behind the
+// root panel and the captured graph a call replays follow from it and from nothing else
+struct CallMode {
+    enum Reduction { kBase = 0, kGamma = 1, kRootMax = 2 } reduction = kBase;       // the values of ReduceArgs::model
+    enum Tail { kMax, kSum, kPosterior } tail = kMax;    // K4 under either root rule, or cafe_root_posterior's two kernels on `posterior`
+    const RootPosteriorArgs* posterior = nullptr;
+    int K = 1;
+    bool use_err = false, two_rate = false;  // error model; death rates set (K1's two-rate instantiation)
+    struct GraphKey {                        // what a captured graph is captured for (cafe_ctx::graphs)
+        int reduction, K; bool two_rate, root_sum;
+        bool operator<(const GraphKey& o) const { return std::tie(reduction, K, two_rate, root_sum) < std::tie(o.reduction, o.K, o.two_rate, o.root_sum); }
+    };
+    GraphKey graph_key() const { return {(int)reduction, K, two_rate, tail == kSum}; }
+};
+
+// What the last call left behind.  A call opens by setting state = kNone (open_call, cafe_call.h) and closes by setting its final
+// state; the read-backs ask require_last.  The shape below the state is written as a call fixes it and stays until a later call
+// writes it again: a call that builds matrices only leaves the launch shape of the scorer call before it in place.
+struct LastCall {
+    enum State {
+        kNone,                               // nothing to read: fresh context, failed call, a matrix call not yet closed, cafe_score_per_family
+        kRejected,                           // the host rejected the parameters (+inf): nothing was built
+        kScored,                             // a scorer call: everything is readable
+        kMatricesOnly                        // root maximum, a closed posterior call, cafe_root_posterior: all but cafe_family_results
+    } state = kNone;
+    int K = 0, model = -1, n_slots = 0, n_kslots = 0;
+    int64_t chunk_f0 = 0, chunk_nf = 0;      // the column chunk resident in the panels
+    bool magskip = false, leaf_t = false, had_comm = false;   // magnitude tables / transposed leaf matrices used; a communicator attached as it began
+    int plan_launches = 0;                   // K2 launches of the last recorded call
+    const DescSet* desc = nullptr;           // its descriptors (diagnostics)
+    hipStream_t stream = nullptr;            // the stream it was enqueued on
+};
+
 }  // namespace cafe
 
 struct cafe_ctx {
@@ -115,7 +149,6 @@ struct cafe_ctx {
     double* d_lt = nullptr;
     int32_t* d_lt_pairs = nullptr;
     std::vector<int32_t> lt_pairs;           // pair index in the row-major pool
-    bool lt_used_last = false;
     cafe::GemmOp* h_gemm_stage = nullptr;    // pinned
     cafe::DescSet desc;                      // stream path
     bool panels_dirty = false;               // the last call returned NaN: stale NaNs may sit in padding rows; cleared before the next call
@@ -132,7 +165,6 @@ struct cafe_ctx {
     // device state
     bool device_ready = false;
     hipStream_t stream = nullptr;
-    hipStream_t last_stream = nullptr;       // stream the last call was enqueued on
     int32_t* d_counts = nullptr;
     double* d_weights = nullptr;
     cafe::MatrixPool pool{nullptr, 0, 0, 0, 0, 0, 0};     // row-major matrices of leaf branches (K3)
@@ -159,9 +191,6 @@ struct cafe_ctx {
     cafe::SlotParamLM* h_slots_lm = nullptr;
     // cafe_set_root_rule: what K4 (and the per-family root kernel) make of a root vector, CAFE_ROOT_MAX or CAFE_ROOT_SUM
     int root_rule = CAFE_ROOT_MAX;
-    // cafe_root_posterior (root_posterior.hip) sets this for the one enqueue it makes: the call's two kernels then stand where
-    // K4 and the final sum do, on the stream path (no graph), and the gamma model's host rejection is not applied
-    const cafe::RootPosteriorArgs* root_posterior = nullptr;
     double* d_panels = nullptr;
     int64_t panel_stride = 0;               // doubles per panel
     int64_t panel_kstride = 0;              // doubles per category inside a panel
@@ -203,25 +232,21 @@ struct cafe_ctx {
     int history_batches = 0, history_passes = 0;            // cafe_sample_histories: column batches, draw passes per batch of the last call
     int debug_fail_in = 0;                  // cafe_debug_fail_next: the n-th next enqueue fails behind its K1 launch
 
-    // last call
     std::vector<int> slot_of;               // [node*Kmax + k]
-    int K_last = 0, model_last = -1;
-    bool last_rejected = false, have_results = false, rootmax_last = false;
-    int n_slots_last = 0, n_kslots_last = 0;
-    int64_t last_chunk_f0 = 0, last_chunk_nf = 0;
+    cafe::LastCall last;                    // what the last call left behind
 
     // launch
     int n_cu = 0;                            // compute units of the device (K2's persistent grid)
     long stamps_launch = -1;                 // CAFE_GEMM_STAMPS_LAUNCH, read once at cafe_create
-    // A call's enqueue sequence is fixed per (reduction, K): upload, K1, the schedule, K4.  It can be captured once in a
-    // hipGraph and replayed (one launch call instead of ~40 to ~300).  Off by default: on ROCm 7.2 the replay measured no
+    // A call's enqueue sequence is fixed per (reduction, K, rate model, root rule): upload, K1, the schedule, K4.  It can be captured
+    // once in a hipGraph and replayed (one launch call instead of ~40 to ~300).  Off by default: on ROCm 7.2 the replay measured no
     // faster than the stream enqueue at the mammals size (base 0.47 vs 0.48 ms) and slower with K = 4 (0.62 vs 0.41 ms).
     struct CallGraph {
         hipGraphExec_t exec = nullptr;
         cafe_stats stats{};                  // the work counters of the captured sequence
         cafe::DescSet desc;                  // its own descriptors and tile lists (frozen at capture)
     };
-    std::map<int, CallGraph> graphs;
+    std::map<cafe::CallMode::GraphKey, CallGraph> graphs;
     int use_graph = 0;
 
     // zero extents of the likelihood panels (extents.hip): one descriptor per interior non-root node, grouped in levels of
@@ -236,7 +261,6 @@ struct cafe_ctx {
     // K steps whose products underflow (extents.hip, "Magnitudes"): the magnitude tables of a call's matrices, the bounds of
     // every planned node's panel, and -- whenever the matrices publish extents -- the joint K ranges of every K2 op
     bool magskip = false;                                 // panel_extents, no CAFE_NO_MAGSKIP, tables allocated
-    bool magskip_last = false;                            // the last call used them (not with an error model: exact extents)
     int32_t *d_mag_a16 = nullptr, *d_mag_t4 = nullptr, *d_mag_lt = nullptr;
     std::vector<int32_t*> d_bound;                        // [n_nodes] (interior non-root nodes only)
     int32_t* d_jr = nullptr;                              // the ops' range tables, one allocation
@@ -248,7 +272,6 @@ struct cafe_ctx {
     int32_t* h_ext = nullptr;                // pinned [max_kslots][ext_blocks][2]
     // tile lists of the K2 launches (tile_plan_kernel): one descriptor per launch, rebuilt per call (the tile heights may
     // change), uploaded when it differs from the last upload
-    int plan_launches_last = 0;              // K2 launches of the last recorded call
     int plan_bias = 8;                       // percent by which the first-dispatched workgroup of a CU outruns the other (measured; CAFE_PLAN_BIAS)
     int plan_bias3[3] = {80, 100, 125};      // three workgroups per CU: cost of a K tile for the first / second / third dispatched (CAFE_PLAN_BIAS3=a,b,c)
     int plan_bias4[4] = {62, 88, 112, 160};  // four (CAFE_PLAN_BIAS4=a,b,c,d)
@@ -256,14 +279,12 @@ struct cafe_ctx {
     int plan_fixed = 8;                      // cost of an output tile beyond its K loop, in 8-deep K tiles (fitted: DESIGN.md; CAFE_PLAN_FIXED)
     size_t plan_entries = 0;
     cafe::PlanLaunch* h_plan_desc = nullptr;        // pinned
-    const cafe::DescSet* desc_last = nullptr;       // descriptors of the last recorded call (diagnostics)
     bool h_ext_valid = false;
     int h_ext_K = 0;                         // categories of the call the copy belongs to
 
     // measurement
     struct GemmLaunch { int group; int K; int mi; int64_t cols; };   // what count_executed_flops needs (cols: the chunk's, several chunks only)
     std::vector<GemmLaunch> gemm_launches_info;
-    bool stats_flops_stale = false;           // gemm_flops still holds the dense count of the last profiled call
     int profile = 0;
     int force_level_tiles = 0;               // diagnostic: column tiles per workgroup of node_level_kernel (0 = chosen per level)
     int force_mi = 0;                        // diagnostic: K2 row-tile height for every launch (0 = chosen per launch)
@@ -332,8 +353,9 @@ inline void quantized_rates(const cafe_ctx* c, const double* lambdas, int i, dou
     *lq = quantize_lambda(lambdas[i] * mult);
     *mq = c->mus.empty() ? *lq : quantize_lambda(c->mus[i] * mult);
 }
-// one scorer call enqueued on `s`, {sum lnL, rejects} -> d_out; rootmax: max_j L_root[j] per family instead (-> d_fam_out)
-int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bool rootmax = false);
+// one scorer call enqueued on `s`, {sum lnL, rejects} -> d_out; rootmax: max_j L_root[j] per family instead (-> d_fam_out); posterior:
+// cafe_root_posterior's two kernels where K4 and the final sum stand, on the stream path (no graph), without the gamma model's host rejection
+int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bool rootmax = false, const RootPosteriorArgs* posterior = nullptr);
 void collect_stats(cafe_ctx* c);                          // the profiling events of the last call into c->stats
 // cafe_debug.hip: flops the K2 launches of the last call executed, from the extents it published (< 0: read-back failed)
 double count_executed_flops(cafe_ctx* c, std::vector<double>* per_launch = nullptr, bool per_block = true, bool exact = false);

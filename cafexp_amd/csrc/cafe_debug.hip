@@ -49,6 +49,15 @@ static bool exact_ranges(cafe_ctx* c, const GemmOp& g, int K, const std::vector<
     return true;
 }
 
+// K range of a row tile = hull of its blocks' joint ranges.  e: the `mi` 16-row blocks of the tile in a row of a range table, each
+// first | last << 16 in 4-deep k-steps, first > last: none.  false (and an empty hull, *slo > *shi): no block has a range.
+static bool tile_k_hull(const int32_t* e, int mi, int* slo, int* shi) {
+    *slo = 0x7fff; *shi = -1;
+    for (int b = 0; b < mi; ++b)
+        if ((e[b] >> 16) >= (e[b] & 0xFFFF)) { *slo = std::min(*slo, e[b] & 0xFFFF); *shi = std::max(*shi, e[b] >> 16); }
+    return *shi >= *slo;
+}
+
 // Flops the K2 launches of the last (profiled) call EXECUTED: a row block of a (row tile, column tile) pair issues MFMAs only
 // in the k-steps of its joint range (GemmOp::jr: matrix extent x panel extent, less the k-steps whose products underflow), so
 // read the ranges this call published and count, per launch, what its tiles ran.  A few synchronous copies, milliseconds of
@@ -84,11 +93,8 @@ double count_executed_flops(cafe_ctx* c, std::vector<double>* per_launch, bool p
                     for (int ct = 0; ct < (per_tile ? n_ct : 1); ++ct) {
                         const double width = per_tile ? (double)kBN : (double)cols;
                         const int32_t* e = g.jr ? jr.data() + ((size_t)k * g.jr_nct + ct) * jr_row : nullptr;
-                        int slo = 0x7fff, shi = -1;
-                        for (int b = row0 / 16; e && b < row0 / 16 + mi; ++b)
-                            if ((e[b] >> 16) >= (e[b] & 0xFFFF)) { slo = std::min(slo, e[b] & 0xFFFF); shi = std::max(shi, e[b] >> 16); }
-                        if (!e) { slo = 0; shi = c->M / 4; }
-                        if (shi < slo) { slo = 0; shi = 0; }     // an all-zero tile runs one K tile
+                        int slo = 0, shi = c->M / 4;             // no ranges: every k-step
+                        if (e && !tile_k_hull(e + row0 / 16, mi, &slo, &shi)) { slo = 0; shi = 0; }     // an all-zero tile runs one K tile
                         const int t_lo = slo * 4 / kBK, t_hi = std::min(shi * 4 + 3, c->M) / kBK;
                         for (int b = row0 / 16; b < row0 / 16 + mi && b * 16 < rows; ++b) {
                             int kk;
@@ -139,8 +145,8 @@ int cafe_debug_level_tiles(cafe_ctx* ctx, int tiles) {
 int cafe_get_extents(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* matrix_ext, size_t matrix_ext_len,
                      int32_t* panel_ext, size_t panel_ext_len, int32_t* n_tiles) {
     if (!ctx) return CAFE_ERR_ARGUMENT;
-    if (!ctx->have_results || ctx->last_rejected) { set_err(ctx, "cafe_get_extents: no completed call"); return CAFE_ERR_STATE; }
-    if (node < 0 || node >= ctx->n_nodes || node == ctx->root || category < 0 || category >= ctx->K_last) {
+    if (const int rc = require_last(ctx, "cafe_get_extents")) return rc;
+    if (node < 0 || node >= ctx->n_nodes || node == ctx->root || category < 0 || category >= ctx->last.K) {
         set_err(ctx, "cafe_get_extents: node/category out of range");
         return CAFE_ERR_ARGUMENT;
     }
@@ -166,14 +172,14 @@ int cafe_get_extents(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* mat
 int cafe_debug_leaf_transposes(cafe_ctx* ctx, int32_t* n_branches, int32_t* used_by_last_call) {
     if (!ctx) return CAFE_ERR_ARGUMENT;
     if (n_branches) *n_branches = ctx->d_lt ? (int32_t)ctx->lt_pairs.size() : 0;
-    if (used_by_last_call) *used_by_last_call = ctx->lt_used_last ? 1 : 0;
+    if (used_by_last_call) *used_by_last_call = ctx->last.leaf_t ? 1 : 0;
     return CAFE_OK;
 }
 
 int cafe_debug_column_extents(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* out, size_t out_len, int64_t* n_cols) {
     if (!ctx || !out) return CAFE_ERR_ARGUMENT;
-    if (!ctx->have_results || ctx->last_rejected) { set_err(ctx, "cafe_debug_column_extents: no completed call"); return CAFE_ERR_STATE; }
-    if (node < 0 || node >= ctx->n_nodes || category < 0 || category >= ctx->K_last || !ctx->panel_extents || !ctx->d_colext[node]) {
+    if (const int rc = require_last(ctx, "cafe_debug_column_extents")) return rc;
+    if (node < 0 || node >= ctx->n_nodes || category < 0 || category >= ctx->last.K || !ctx->panel_extents || !ctx->d_colext[node]) {
         set_err(ctx, "cafe_debug_column_extents: no extents for this node");
         return CAFE_ERR_ARGUMENT;
     }
@@ -189,9 +195,9 @@ int cafe_debug_column_extents(cafe_ctx* ctx, int32_t node, int32_t category, int
 // rows 4 r .. 4 r + 3 in 128-column tile `tile` of `category`; -inf where all of them are exactly zero.
 int cafe_debug_panel_bounds(cafe_ctx* ctx, int32_t node, int32_t category, double* out, size_t out_len, int32_t* n_tiles, int32_t* row_steps) {
     if (!ctx) return CAFE_ERR_ARGUMENT;
-    if (!ctx->have_results || ctx->last_rejected) { set_err(ctx, "cafe_debug_panel_bounds: no completed call"); return CAFE_ERR_STATE; }
-    if (node < 0 || node >= ctx->n_nodes || category < 0 || category >= ctx->K_last) { set_err(ctx, "cafe_debug_panel_bounds: node/category out of range"); return CAFE_ERR_ARGUMENT; }
-    if (!ctx->magskip_last || !ctx->d_bound[node]) { set_err(ctx, "cafe_debug_panel_bounds: the last call kept no bounds for this node"); return CAFE_ERR_STATE; }
+    if (const int rc = require_last(ctx, "cafe_debug_panel_bounds")) return rc;
+    if (node < 0 || node >= ctx->n_nodes || category < 0 || category >= ctx->last.K) { set_err(ctx, "cafe_debug_panel_bounds: node/category out of range"); return CAFE_ERR_ARGUMENT; }
+    if (!ctx->last.magskip || !ctx->d_bound[node]) { set_err(ctx, "cafe_debug_panel_bounds: the last call kept no bounds for this node"); return CAFE_ERR_STATE; }
     const int nt = (int)(panel_cols(ctx, node, ctx->Fp) / kBN), nr = ctx->n_rsteps;
     if (n_tiles) *n_tiles = nt;
     if (row_steps) *row_steps = nr;
@@ -210,22 +216,22 @@ int cafe_debug_panel_bounds(cafe_ctx* ctx, int32_t node, int32_t category, doubl
 int cafe_debug_magnitude_tables(cafe_ctx* ctx, int32_t which, int32_t slot, int32_t* out, size_t out_len, int32_t* n0, int32_t* n1,
                                 int32_t node, int32_t category) {
     if (!ctx) return CAFE_ERR_ARGUMENT;
-    if (!ctx->have_results || ctx->last_rejected) { set_err(ctx, "cafe_debug_magnitude_tables: no completed call"); return CAFE_ERR_STATE; }
+    if (const int rc = require_last(ctx, "cafe_debug_magnitude_tables")) return rc;
     if (which < 0 || which > 2) { set_err(ctx, "cafe_debug_magnitude_tables: which must be 0 (a16), 1 (t4) or 2 (lt)"); return CAFE_ERR_ARGUMENT; }
-    if (!ctx->magskip_last || !ctx->d_mag_a16 || !ctx->d_mag_t4 || !ctx->d_mag_lt) {
+    if (!ctx->last.magskip || !ctx->d_mag_a16 || !ctx->d_mag_t4 || !ctx->d_mag_lt) {
         set_err(ctx, "cafe_debug_magnitude_tables: the last call kept no tables");
         return CAFE_ERR_STATE;
     }
     const bool leaf_table = which == 2;
     if (slot < 0) {
-        if (node < 0 || node >= ctx->n_nodes || node == ctx->root || category < 0 || category >= ctx->K_last ||
+        if (node < 0 || node >= ctx->n_nodes || node == ctx->root || category < 0 || category >= ctx->last.K ||
             (ctx->leaf_taxon[node] >= 0) != leaf_table) {
             set_err(ctx, "cafe_debug_magnitude_tables: node/category out of range for this table");
             return CAFE_ERR_ARGUMENT;
         }
         slot = ctx->slot_of[(size_t)node * ctx->Kmax + category];
     }
-    if (slot < 0 || slot >= (leaf_table ? ctx->n_slots_last : ctx->n_kslots_last)) { set_err(ctx, "cafe_debug_magnitude_tables: slot out of range"); return CAFE_ERR_ARGUMENT; }
+    if (slot < 0 || slot >= (leaf_table ? ctx->last.n_slots : ctx->last.n_kslots)) { set_err(ctx, "cafe_debug_magnitude_tables: slot out of range"); return CAFE_ERR_ARGUMENT; }
     const int d0 = leaf_table ? ctx->M + 1 : ctx->n_ksteps, d1 = which == 0 ? ctx->kpool.ext_blocks : ctx->n_rsteps;
     if (n0) *n0 = d0;
     if (n1) *n1 = d1;
@@ -242,8 +248,8 @@ int cafe_debug_magnitude_tables(cafe_ctx* ctx, int32_t which, int32_t slot, int3
 // node's panel, first > last: none.  *n_tiles = 1 where the panels have no extents (one range per block).
 int cafe_debug_k_ranges(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* out, size_t out_len, int32_t* n_tiles, int32_t* n_blocks) {
     if (!ctx) return CAFE_ERR_ARGUMENT;
-    if (!ctx->have_results || ctx->last_rejected) { set_err(ctx, "cafe_debug_k_ranges: no completed call"); return CAFE_ERR_STATE; }
-    if (category < 0 || category >= ctx->K_last) { set_err(ctx, "cafe_debug_k_ranges: category out of range"); return CAFE_ERR_ARGUMENT; }
+    if (const int rc = require_last(ctx, "cafe_debug_k_ranges")) return rc;
+    if (category < 0 || category >= ctx->last.K) { set_err(ctx, "cafe_debug_k_ranges: category out of range"); return CAFE_ERR_ARGUMENT; }
     const GemmOp* g = nullptr;
     for (const Op& op : ctx->ops) if (op.type == 1 && op.child == node) g = &ctx->h_gemm_ops[op.desc];
     if (!g || !g->jr) { set_err(ctx, "cafe_debug_k_ranges: no K2 op with ranges for this node"); return CAFE_ERR_STATE; }
@@ -254,7 +260,7 @@ int cafe_debug_k_ranges(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* 
     if (out_len < (size_t)2 * g->jr_nct * nb) { set_err(ctx, "cafe_debug_k_ranges: out too small"); return CAFE_ERR_ARGUMENT; }
     if (const int rc = wait_last_call(ctx)) return rc;
     std::vector<int32_t> jr;
-    if (!read_ranges(ctx, *g, ctx->K_last, jr)) { set_err(ctx, "cafe_debug_k_ranges: reading the ranges back failed"); return CAFE_ERR_DEVICE; }
+    if (!read_ranges(ctx, *g, ctx->last.K, jr)) { set_err(ctx, "cafe_debug_k_ranges: reading the ranges back failed"); return CAFE_ERR_DEVICE; }
     for (int t = 0; t < g->jr_nct; ++t)
         for (int b = 0; b < nb; ++b) {
             const int32_t v = jr[((size_t)category * g->jr_nct + t) * (nb + kRangePad) + b];
@@ -263,37 +269,24 @@ int cafe_debug_k_ranges(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* 
     return CAFE_OK;
 }
 
-int cafe_debug_tile_range_flops(cafe_ctx* ctx, double* flops) {
-    if (!ctx || !flops) return CAFE_ERR_ARGUMENT;
-    if (!ctx->have_results || ctx->gemm_launches_info.empty()) { set_err(ctx, "cafe_debug_tile_range_flops: no completed call that was enqueued launch by launch"); return CAFE_ERR_STATE; }
-    if (const int rc = wait_last_call(ctx)) return rc;
-    const double v = count_executed_flops(ctx, nullptr, false);
-    if (v < 0) { set_err(ctx, "cafe_debug_tile_range_flops: reading the extents back failed"); return CAFE_ERR_DEVICE; }
-    *flops = v;
-    return CAFE_OK;
+// The gate of the read-backs that count over the last call's launch list: a completed call, enqueued launch by launch, finished
+static int require_launch_list(cafe_ctx* ctx, const char* entry) {
+    if (const int rc = require_last(ctx, entry)) return rc;
+    if (ctx->gemm_launches_info.empty()) { set_err(ctx, "%s: the last call was not enqueued launch by launch (a graph replay keeps no launch list)", entry); return CAFE_ERR_STATE; }
+    return wait_last_call(ctx);
 }
 
-int cafe_executed_flops(cafe_ctx* ctx, double* flops) {
+static int counted_flops(cafe_ctx* ctx, const char* entry, bool per_block, bool exact, double* flops) {
     if (!ctx || !flops) return CAFE_ERR_ARGUMENT;
-    if (!ctx->have_results) { set_err(ctx, "cafe_executed_flops: no completed call"); return CAFE_ERR_STATE; }
-    if (const int rc = wait_last_call(ctx)) return rc;
-    if (ctx->gemm_launches_info.empty()) { set_err(ctx, "cafe_executed_flops: the last call was not enqueued launch by launch (a graph replay keeps no launch list)"); return CAFE_ERR_STATE; }
-    const double v = count_executed_flops(ctx, nullptr, true, true);
-    if (v < 0) { set_err(ctx, "cafe_executed_flops: reading the extents back failed"); return CAFE_ERR_DEVICE; }
+    if (const int rc = require_launch_list(ctx, entry)) return rc;
+    const double v = count_executed_flops(ctx, nullptr, per_block, exact);
+    if (v < 0) { set_err(ctx, "%s: reading the ranges back failed", entry); return CAFE_ERR_DEVICE; }
     *flops = v;
     return CAFE_OK;
 }
-
-int cafe_issued_flops(cafe_ctx* ctx, double* flops) {
-    if (!ctx || !flops) return CAFE_ERR_ARGUMENT;
-    if (!ctx->have_results) { set_err(ctx, "cafe_issued_flops: no completed call"); return CAFE_ERR_STATE; }
-    if (const int rc = wait_last_call(ctx)) return rc;
-    if (ctx->gemm_launches_info.empty()) { set_err(ctx, "cafe_issued_flops: the last call was not enqueued launch by launch (a graph replay keeps no launch list)"); return CAFE_ERR_STATE; }
-    const double v = count_executed_flops(ctx);
-    if (v < 0) { set_err(ctx, "cafe_issued_flops: reading the ranges back failed"); return CAFE_ERR_DEVICE; }
-    *flops = v;
-    return CAFE_OK;
-}
+int cafe_debug_tile_range_flops(cafe_ctx* ctx, double* flops) { return counted_flops(ctx, "cafe_debug_tile_range_flops", false, false, flops); }
+int cafe_executed_flops(cafe_ctx* ctx, double* flops) { return counted_flops(ctx, "cafe_executed_flops", true, true, flops); }
+int cafe_issued_flops(cafe_ctx* ctx, double* flops) { return counted_flops(ctx, "cafe_issued_flops", true, false, flops); }
 
 // diagnostic / test: read the tile lists of the last call back and check them against the extents -- every tile of every
 // op of every launch exactly once, with the K range the extents give, nothing behind the end of a list.
@@ -302,8 +295,8 @@ int cafe_debug_plan_check(cafe_ctx* ctx, int32_t* n_planned, double* worst_load)
     if (!ctx) return CAFE_ERR_ARGUMENT;
     if (n_planned) *n_planned = 0;
     if (worst_load) *worst_load = 1.0;
-    const DescSet* ds = ctx->desc_last;
-    if (!ds || ctx->plan_launches_last == 0 || ds->plan_desc_sent.empty()) return CAFE_OK;
+    const DescSet* ds = ctx->last.desc;
+    if (!ds || ctx->last.plan_launches == 0 || ds->plan_desc_sent.empty()) return CAFE_OK;
     if (const int rc = wait_last_call(ctx)) return rc;
     const int jr_row = ctx->kpool.ext_blocks + kRangePad;
     std::vector<int2> plan;
@@ -344,15 +337,14 @@ int cafe_debug_plan_check(cafe_ctx* ctx, int32_t* n_planned, double* worst_load)
                     int lo = 0, hi = L.k_valid - 1, zlo = 0;
                     if (ctx->kpool.ext) {
                         const int32_t* a = op_jr[o].data() + ((size_t)cat * ops[o].jr_nct + (ct & ops[o].jr_ct_mask)) * jr_row + b0;
-                        int slo = 0x7fff, shi = -1;
-                        for (int b = 0; b < L.mi; ++b)
-                            if ((a[b] >> 16) >= (a[b] & 0xFFFF)) { slo = std::min(slo, a[b] & 0xFFFF); shi = std::max(shi, a[b] >> 16); }
+                        int slo, shi;
+                        const bool any = tile_k_hull(a, L.mi, &slo, &shi);
                         lo = slo * 4; hi = shi * 4 + 3;
                         if (!op_bext[o].empty()) {
                             const int32_t* be = op_bext[o].data() + ((size_t)cat * nct + ct) * 2;
                             if (be[1] >= be[0]) zlo = be[0];
                         }
-                        if (shi < slo) { lo = zlo; hi = zlo; }
+                        if (!any) { lo = zlo; hi = zlo; }
                         hi = std::min(hi, L.k_valid - 1);
                     }
                     if ((e.y >> 16) != lo / L.kb || (e.y & 0xFFFF) != hi / L.kb - lo / L.kb + 1) goto bad;
@@ -386,8 +378,7 @@ int cafe_debug_launch_ms(cafe_ctx* ctx, double* ms, size_t n) {      // diagnost
 
 int cafe_debug_launch_flops(cafe_ctx* ctx, double* executed, double* all_k_tiles, int32_t* tile_height, size_t n) {
     if (!ctx || !executed) return CAFE_ERR_ARGUMENT;
-    if (!ctx->have_results || ctx->gemm_launches_info.empty()) { set_err(ctx, "cafe_debug_launch_flops: no call enqueued launch by launch"); return CAFE_ERR_STATE; }
-    if (const int rc = wait_last_call(ctx)) return rc;
+    if (const int rc = require_launch_list(ctx, "cafe_debug_launch_flops")) return rc;
     std::vector<double> v;
     if (count_executed_flops(ctx, &v) < 0) { set_err(ctx, "cafe_debug_launch_flops: reading the extents back failed"); return CAFE_ERR_DEVICE; }
     for (size_t i = 0; i < n && i < v.size(); ++i) {
@@ -402,13 +393,22 @@ int cafe_debug_launch_flops(cafe_ctx* ctx, double* executed, double* all_k_tiles
         }
         if (tile_height) tile_height[i] = L.mi;
     }
-    return (int)std::min(n, v.size()) >= 0 ? CAFE_OK : CAFE_OK;
+    return CAFE_OK;
+}
+
+// A matrix of order n out of its k-major slot: Pt[c][s-1] = P[s][c] for s >= 1; row 0 of P is e_0, implicit in the layout, and the
+// columns c > M are never materialised (the prune never reads them): reported as 0
+static void unpack_kmajor(const double* t, const MatrixPool& p, size_t n, double* out) {
+    std::fill(out, out + n * n, 0.0);
+    out[0] = 1.0;
+    for (size_t s = 1; s < n; ++s)
+        for (size_t c = 0; c < n && c < (size_t)p.rows; ++c) out[s * n + c] = t[c * (size_t)p.ld + (s - 1)];
 }
 
 int cafe_get_matrix(cafe_ctx* ctx, int32_t node, int32_t category, double* out, size_t out_len) {
     if (!ctx || !out) return CAFE_ERR_ARGUMENT;
-    if (!ctx->have_results) { set_err(ctx, "cafe_get_matrix: no completed call"); return CAFE_ERR_STATE; }
-    if (node < 0 || node >= ctx->n_nodes || node == ctx->root || category < 0 || category >= ctx->K_last) {
+    if (const int rc = require_last(ctx, "cafe_get_matrix")) return rc;
+    if (node < 0 || node >= ctx->n_nodes || node == ctx->root || category < 0 || category >= ctx->last.K) {
         set_err(ctx, "cafe_get_matrix: node/category out of range");
         return CAFE_ERR_ARGUMENT;
     }
@@ -421,34 +421,28 @@ int cafe_get_matrix(cafe_ctx* ctx, int32_t node, int32_t category, double* out, 
                                  (size_t)ctx->pool.ld * sizeof(double), n * sizeof(double), n, hipMemcpyDeviceToHost));
         return CAFE_OK;
     }
-    // interior branch: stored k-major, Pt[c][s-1] = P[s][c] for c <= M, s >= 1; row 0 of P is e_0 and the
-    // columns c > M are never materialised (the prune never reads them): reported as 0
-    const size_t ldt = (size_t)ctx->kpool.ld, rows = (size_t)ctx->kpool.rows;
-    std::vector<double> tmp(rows * ldt);
+    std::vector<double> tmp((size_t)ctx->kpool.rows * ctx->kpool.ld);       // interior branch: stored k-major
     HIP_TRY(ctx, hipMemcpy(tmp.data(), ctx->kpool.base + (int64_t)slot * ctx->kpool.stride, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
-    std::fill(out, out + n * n, 0.0);
-    out[0] = 1.0;
-    for (size_t s2 = 1; s2 < n; ++s2)
-        for (size_t c2 = 0; c2 < n && c2 < rows; ++c2) out[s2 * n + c2] = tmp[c2 * ldt + (s2 - 1)];
+    unpack_kmajor(tmp.data(), ctx->kpool, n, out);
     return CAFE_OK;
 }
 
 int cafe_get_root_likelihoods(cafe_ctx* ctx, int64_t family, int32_t category, double* out, size_t out_len) {
     if (!ctx || !out) return CAFE_ERR_ARGUMENT;
-    if (!ctx->have_results || ctx->last_rejected) { set_err(ctx, "cafe_get_root_likelihoods: no completed call"); return CAFE_ERR_STATE; }
-    if (family < 0 || family >= ctx->F_all || category < 0 || category >= ctx->K_last || out_len < (size_t)ctx->R) {
+    if (const int rc = require_last(ctx, "cafe_get_root_likelihoods")) return rc;
+    if (family < 0 || family >= ctx->F_all || category < 0 || category >= ctx->last.K || out_len < (size_t)ctx->R) {
         set_err(ctx, "cafe_get_root_likelihoods: argument out of range");
         return CAFE_ERR_ARGUMENT;
     }
     const int64_t u = ctx->ref_of[family];
-    if (u < ctx->last_chunk_f0 || u >= ctx->last_chunk_f0 + ctx->last_chunk_nf) {
+    if (u < ctx->last.chunk_f0 || u >= ctx->last.chunk_f0 + ctx->last.chunk_nf) {
         set_err(ctx, "cafe_get_root_likelihoods: family is not in the last resident chunk");
         return CAFE_ERR_STATE;
     }
     if (const int rc = wait_last_call(ctx)) return rc;
-    const int64_t cols = std::min<int64_t>(ctx->chunk_cols, ctx->Fp - ctx->last_chunk_f0);
+    const int64_t cols = std::min<int64_t>(ctx->chunk_cols, ctx->Fp - ctx->last.chunk_f0);
     const cafe::Panel& RP = ctx->panels[ctx->root_panel];
-    const double* src = ctx->d_panels + RP.offset + (int64_t)category * RP.kstride + (u - ctx->last_chunk_f0);
+    const double* src = ctx->d_panels + RP.offset + (int64_t)category * RP.kstride + (u - ctx->last.chunk_f0);
     HIP_TRY(ctx, hipMemcpy2D(out, sizeof(double), src, (size_t)cols * sizeof(double), sizeof(double), (size_t)ctx->R, hipMemcpyDeviceToHost));
     return CAFE_OK;
 }
@@ -496,10 +490,7 @@ static int build_matrices(int32_t device, int32_t n, int32_t count, const double
                 rc = CAFE_ERR_DEVICE;
                 break;
             }
-            std::fill(o, o + (size_t)n * n, 0.0);
-            o[0] = 1.0;                                    // P's row 0 = e_0 is implicit in the k-major layout
-            for (int s2 = 1; s2 < n; ++s2)
-                for (int c2 = 0; c2 < n; ++c2) o[(size_t)s2 * n + c2] = tmp[(size_t)c2 * pool.ld + (s2 - 1)];
+            unpack_kmajor(tmp.data(), pool, (size_t)n, o);
         }
     }
     (void)hipFree(pool.base);

@@ -80,27 +80,17 @@ void fill_slots(cafe_ctx* c, const double* lambdas, const double* multipliers, i
     SlotParam* h[2] = {reinterpret_cast<SlotParam*>(c->h_stage), reinterpret_cast<SlotParam*>(c->h_stage) + c->max_slots};
     for (int layout = 0; layout < 2; ++layout) {
         const int P = c->n_pairs[layout];
-        for (int k = 0; k < K; ++k) {
-            const double mult = multipliers ? multipliers[k] : 1.0;
+        for (int k = 0; k < K; ++k)
             for (int p = 0; p < P; ++p) {
-                h[layout][k * P + p] = slot_param(quantize_lambda(lambdas[c->pair_lam[layout][p]] * mult), c->pair_tq[layout][p]);
+                long lq, mq;
+                quantized_rates(c, lambdas, c->pair_lam[layout][p], multipliers ? multipliers[k] : 1.0, &lq, &mq);
+                h[layout][k * P + p] = slot_param(lq, c->pair_tq[layout][p]);
+                // death rates set: the two-rate kernel's parameters, same slots (the multiplier scales both rates)
+                if (!c->mus.empty()) c->h_slots_lm[(layout ? c->max_slots : 0) + k * P + p] = slot_param_lm(lq, mq, c->pair_tq[layout][p]);
             }
-        }
     }
-    if (!c->mus.empty()) {                   // death rates set: the two-rate kernel's parameters, same slots (the multiplier scales both rates)
-        SlotParamLM* hl[2] = {c->h_slots_lm, c->h_slots_lm + c->max_slots};
-        for (int layout = 0; layout < 2; ++layout) {
-            const int P = c->n_pairs[layout];
-            for (int k = 0; k < K; ++k)
-                for (int p = 0; p < P; ++p) {
-                    long lq, mq;
-                    quantized_rates(c, lambdas, c->pair_lam[layout][p], multipliers ? multipliers[k] : 1.0, &lq, &mq);
-                    hl[layout][k * P + p] = slot_param_lm(lq, mq, c->pair_tq[layout][p]);
-                }
-        }
-    }
-    c->n_slots_last = K * c->n_pairs[0];
-    c->n_kslots_last = K * c->n_pairs[1];
+    c->last.n_slots = K * c->n_pairs[0];
+    c->last.n_kslots = K * c->n_pairs[1];
     c->stats.n_matrices = (int64_t)K * c->n_distinct_pairs;
 }
 
@@ -113,10 +103,8 @@ int upload_lm_slots(cafe_ctx* c, hipStream_t s) {
     return CAFE_OK;
 }
 int launch_call_matrices(cafe_ctx* c, hipStream_t s) {
-    if (c->mus.empty())
-        HIP_TRY(c, launch_bd_matrix_build_both(c->pool, c->kpool, c->d_slots, c->d_slots + c->max_slots, c->n_slots_last, c->n_kslots_last, s));
-    else
-        HIP_TRY(c, launch_bd_matrix_build_both(c->pool, c->kpool, c->d_slots_lm, c->d_slots_lm + c->max_slots, c->n_slots_last, c->n_kslots_last, s));
+    if (c->mus.empty()) HIP_TRY(c, launch_bd_matrix_build_both(c->pool, c->kpool, c->d_slots, c->d_slots + c->max_slots, c->last.n_slots, c->last.n_kslots, s));
+    else HIP_TRY(c, launch_bd_matrix_build_both(c->pool, c->kpool, c->d_slots_lm, c->d_slots_lm + c->max_slots, c->last.n_slots, c->last.n_kslots, s));
     return CAFE_OK;
 }
 
@@ -135,10 +123,12 @@ int prepare_matrices(cafe_ctx* c, const double* lambdas, const double* multiplie
 
 namespace {
 
-// Host-only rejections; true => the call's value is +inf without touching the device.
-bool rejected(const cafe_ctx* c, const cafe_params* pr, int K) {
+// Host-only rejections; true => the call's value is +inf without touching the device.  (The gamma model's own apply to the
+// scorer's reduction, not to cafe_root_posterior's.)
+bool rejected(const cafe_ctx* c, const cafe_params* pr, const CallMode& m) {
     if (!rates_valid(c, pr->lambdas)) return true;                             // base_model.cpp:56 / gamma_core.cpp:125
-    if (pr->model != CAFE_MODEL_GAMMA) return false;
+    if (m.reduction != CallMode::kGamma || m.tail == CallMode::kPosterior) return false;
+    const int K = m.K;
     if (pr->alpha < 0) return true;                                            // gamma_core.cpp:128
     // gamma_core.cpp:131-139: longest branch x largest multiplier x largest lambda saturated?
     bool first = true;
@@ -257,24 +247,13 @@ int prepare_descriptors(cafe_ctx* c, DescSet& ds, int K, int64_t cols, const std
     const bool ops_same = ds.gemm_ops_sent.size() == n_ops && std::memcmp(ds.gemm_ops_sent.data(), ops.data(), sizeof(GemmOp) * n_ops) == 0;
     const bool plans_same = ds.plan_desc_sent.size() == plans.size() &&
                             (plans.empty() || std::memcmp(ds.plan_desc_sent.data(), plans.data(), sizeof(PlanLaunch) * plans.size()) == 0);
-    if (!ops_same) {
-        if (sync) {
-            HIP_TRY(c, hipMemcpy(ds.d_gemm_ops, ops.data(), sizeof(GemmOp) * n_ops, hipMemcpyHostToDevice));
-        } else {
-            std::memcpy(c->h_gemm_stage, ops.data(), sizeof(GemmOp) * n_ops);       // (the previous upload from here was waited for: ev_upload)
-            HIP_TRY(c, hipMemcpyAsync(ds.d_gemm_ops, c->h_gemm_stage, sizeof(GemmOp) * n_ops, hipMemcpyHostToDevice, s));
-        }
-        ds.gemm_ops_sent = ops;
-    }
-    if (!plans_same && !plans.empty()) {
-        if (sync) {
-            HIP_TRY(c, hipMemcpy(ds.d_plan_desc, plans.data(), sizeof(PlanLaunch) * plans.size(), hipMemcpyHostToDevice));
-        } else {
-            std::memcpy(c->h_plan_desc, plans.data(), sizeof(PlanLaunch) * plans.size());
-            HIP_TRY(c, hipMemcpyAsync(ds.d_plan_desc, c->h_plan_desc, sizeof(PlanLaunch) * plans.size(), hipMemcpyHostToDevice, s));
-        }
-        ds.plan_desc_sent = plans;
-    }
+    auto upload = [&](void* dst, void* stage, const void* src, size_t bytes) {
+        if (sync) return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
+        std::memcpy(stage, src, bytes);      // (the previous upload from this pinned stage was waited for: ev_upload)
+        return hipMemcpyAsync(dst, stage, bytes, hipMemcpyHostToDevice, s);
+    };
+    if (!ops_same) { HIP_TRY(c, upload(ds.d_gemm_ops, c->h_gemm_stage, ops.data(), sizeof(GemmOp) * n_ops)); ds.gemm_ops_sent = ops; }
+    if (!plans_same && !plans.empty()) { HIP_TRY(c, upload(ds.d_plan_desc, c->h_plan_desc, plans.data(), sizeof(PlanLaunch) * plans.size())); ds.plan_desc_sent = plans; }
     // with extents the lists follow this call's matrices: planned every call; without, only when something they depend on changed
     const bool static_ok = ds.plan_static_valid && ds.plan_static_K == K && ds.plan_static_cols == cols && ops_same && plans_same;
     *plan_needed = c->kpool.ext != nullptr || !static_ok;
@@ -282,23 +261,26 @@ int prepare_descriptors(cafe_ctx* c, DescSet& ds, int K, int64_t cols, const std
     return CAFE_OK;
 }
 
-// The device work of one call, enqueued on `s` (or recorded into a graph being captured on `s`): parameter upload,
-// K1, the schedule (K2 / K3 launches), K4, the final sum into d_out.  Everything that changes between calls of the
-// same shape travels through the parameter block; kernel arguments depend only on (reduction, K, error model).
-int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool rootsum, bool use_err, double* d_out, hipStream_t s, bool events, bool capturing) {
-    c->stats.gemm_flops = c->stats.gemm_bytes = c->stats.gemm_flops_per_family = c->stats.gemm_flops_dense = 0;
-    c->stats.gemm_launches = 0;
-    c->desc_last = &ds;
-    // ---- host: tile heights and descriptors (the previous call's extents are in h_ext: that call was waited for)
-    const bool have_ext = c->h_ext && c->h_ext_valid && c->h_ext_K == K;       // the previous call's extents (same shape)
-    std::vector<int32_t> prev_ext;
-    if (have_ext) prev_ext.assign(c->h_ext, c->h_ext + (size_t)2 * c->n_kslots_last * c->kpool.ext_blocks);
-    bool plan_needed = true;
-    const int64_t cols0 = std::min<int64_t>(c->chunk_cols, c->Fp);
-    if (!capturing) {                        // (a capture's descriptors were prepared and uploaded before it began)
-        const int rc = prepare_descriptors(c, ds, K, cols0, have_ext ? &prev_ext : nullptr, false, s, &plan_needed);
-        if (rc != CAFE_OK) return rc;
-    }
+// The extents the previous scorer call's matrices published, when it had the same K, for prepare_descriptors: copied into
+// `ext`, since h_ext is this call's to overwrite.  nullptr: none.
+const std::vector<int32_t>* previous_extents(const cafe_ctx* c, int K, std::vector<int32_t>& ext) {
+    if (!(c->h_ext && c->h_ext_valid && c->h_ext_K == K)) return nullptr;
+    ext.assign(c->h_ext, c->h_ext + (size_t)2 * K * c->n_pairs[1] * c->kpool.ext_blocks);      // (n_kslots of a call with K categories)
+    return &ext;
+}
+
+// The five work counters of a call's K2 launches: record_call counts them from zero, a graph replay copies its capture's
+void copy_work(cafe_stats& to, const cafe_stats& from) {
+    to.gemm_flops = from.gemm_flops; to.gemm_bytes = from.gemm_bytes; to.gemm_flops_per_family = from.gemm_flops_per_family;
+    to.gemm_flops_dense = from.gemm_flops_dense; to.gemm_launches = from.gemm_launches;
+}
+void reset_work(cafe_stats& st) { copy_work(st, cafe_stats{}); }
+
+// The three parts of a call's device work (record_call below).  In front of the prune: NaN clearing, parameter upload, K1, the
+// extent copy for the next call, magnitude tables, node levels, joint K ranges, leaf transposes.
+int enqueue_prepass(cafe_ctx* c, const DescSet& ds, const CallMode& m, hipStream_t s, bool events) {
+    const int K = m.K;
+    const bool use_err = m.use_err;
     if (c->panels_dirty) {                   // the last call returned NaN: no stale NaN may meet a zero of a padded K step
         HIP_TRY(c, hipMemsetAsync(c->d_panels, 0, (size_t)c->stats.panel_bytes, s));
         c->panels_dirty = false;
@@ -313,16 +295,15 @@ int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool 
         return CAFE_ERR_DEVICE;
     }
     if (c->h_ext) {                          // this call's extents for the next one; lands while the K2 launches run
-        HIP_TRY(c, hipMemcpyAsync(c->h_ext, c->kpool.ext, sizeof(int32_t) * 2 * (size_t)c->n_kslots_last * c->kpool.ext_blocks, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(c->h_ext, c->kpool.ext, sizeof(int32_t) * 2 * (size_t)c->last.n_kslots * c->kpool.ext_blocks, hipMemcpyDeviceToHost, s));
         c->h_ext_valid = true;
         c->h_ext_K = K;
     }
-    const bool mag = c->magskip && !use_err; // (an error model's taps would need bounds of their own: exact extents then)
-    c->magskip_last = mag;
+    const bool mag = c->last.magskip = c->magskip && !use_err;   // (an error model's taps would need bounds of their own: exact extents then)
     if (mag) {                               // magnitude tables of this call's matrices: one pass over the two pools
         MagArgs ma{};
         ma.kpool = c->kpool; ma.lpool = c->pool;
-        ma.n_kslots = c->n_kslots_last; ma.n_lslots = c->n_slots_last;
+        ma.n_kslots = c->last.n_kslots; ma.n_lslots = c->last.n_slots;
         ma.n_ksteps = c->n_ksteps; ma.n_rsteps = c->n_rsteps; ma.M = c->M;
         ma.a16 = c->d_mag_a16; ma.t4 = c->d_mag_t4; ma.lt = c->d_mag_lt;
         HIP_TRY(c, launch_magnitude_tables(ma, s));
@@ -350,98 +331,124 @@ int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool 
         HIP_TRY(c, launch_joint_ranges(ra, std::max(1, c->jr_max_tiles), K, s));
     }
 
-    const bool leaf_t = c->d_lt && !use_err;
-    c->lt_used_last = leaf_t;
-    if (leaf_t) {                            // transposed copies of the leaf matrices that meet a factor in an assemble pass
+    if ((c->last.leaf_t = c->d_lt && !use_err)) {   // transposed copies of the leaf matrices that meet a factor in an assemble pass
         LeafTArgs lt{};
         lt.pool = c->pool; lt.pairs = c->d_lt_pairs; lt.pool_pairs = c->n_pairs[0]; lt.n_list = (int)c->lt_pairs.size();
         lt.n_x = c->M + 1; lt.ld_t = c->factor_ld; lt.dst = c->d_lt;
         lt.kstride = (int64_t)(c->M + 1) * c->factor_ld; lt.pair_stride = lt.kstride * c->Kmax;
         HIP_TRY(c, launch_leaf_transpose(lt, lt.n_list, K, s));
     }
+    return CAFE_OK;
+}
+
+// The prune of one column chunk [f0, f0 + cols): the K3 / K2 launches of the schedule, in its order
+int enqueue_chunk(cafe_ctx* c, const DescSet& ds, const CallMode& m, int64_t f0, int64_t cols, hipStream_t s, bool events) {
+    const int K = m.K;
+    const bool use_err = m.use_err, leaf_t = c->last.leaf_t;
+    const int uniform_ld = (c->subtree_dedup || c->grouped) ? 0 : (int)cols;
+    int gi = 0;
+    for (size_t g_index = 0; g_index < c->groups.size(); ++g_index) {
+        const Group& g = c->groups[g_index];
+        if (g.type == 0) {
+            GatherGroup gg{};
+            gg.pool = c->pool;
+            gg.ops = c->d_gather_ops + g.first_desc; gg.n_ops = (int)g.ops.size(); gg.n_categories = K;
+            gg.max_family_size = c->M;
+            gg.err = use_err ? c->d_err : nullptr; gg.n_dev = use_err ? c->n_dev : 0;
+            gg.uniform_ld = uniform_ld;
+            gg.f0 = c->subtree_dedup ? 0 : f0;
+            gg.leaf_t = leaf_t ? 1 : 0;
+            HIP_TRY(c, launch_leaf_gather_group(gg, c->h_gather_ops.data() + g.first_desc, s, c->has_missing));
+            continue;
+        }
+        GemmArgs a{};
+        a.pool = c->kpool; a.lpool = c->pool;
+        a.ops = ds.d_gemm_ops + g.first_desc; a.n_ops = (int)g.ops.size();
+        a.k_valid = c->M + 1; a.kb = c->kb; a.mi = ds.group_mi[gi]; a.n_categories = K;
+        a.uniform_ld = uniform_ld;
+        a.f0 = c->subtree_dedup ? 0 : f0;
+        a.err = use_err ? c->d_err : nullptr; a.max_family_size = c->M;
+        a.stamps = (c->stamps_launch < 0 || c->stamps_launch == (long)c->stats.gemm_launches) ? c->d_stamps : nullptr;
+        a.plan = ds.d_plan + ds.group_plan_off[gi]; a.plan_rounds = ds.group_rounds[gi];
+        if (events && c->gemm_ev_used + 2 <= c->gemm_ev.size()) {       // start / stop events ride on the dispatch itself
+            HIP_TRY(c, launch_prune_gemm(a, g.variant, ds.group_blocks[gi], s, c->gemm_ev[c->gemm_ev_used], c->gemm_ev[c->gemm_ev_used + 1]));
+            c->gemm_ev_used += 2;
+        } else {
+            HIP_TRY(c, launch_prune_gemm(a, g.variant, ds.group_blocks[gi], s));
+        }
+        c->stats.gemm_launches += 1;
+        c->gemm_launches_info.push_back({(int)g_index, K, a.mi, cols});
+        for (int oi : g.ops) {
+            const Op& op = c->ops[oi];
+            const double gc = (double)panel_cols(c, op.child, cols);
+            const int rows = op.to_root ? c->R : c->M;
+            c->stats.gemm_flops_dense += 2.0 * rows * (c->M + 1) * gc * K;
+            c->stats.gemm_flops += 2.0 * rows * (c->M + 1) * gc * K;      // (cafe_executed_flops counts what the tiles really ran)
+            c->stats.gemm_flops_per_family += 2.0 * rows * (c->M + 1) * (double)cols * K;
+            c->stats.gemm_bytes += 8.0 * K * ((double)rows * (c->M + 1) + (double)(c->M + 1) * gc + (double)rows * gc);
+        }
+        ++gi;
+    }
+    return CAFE_OK;
+}
+
+// What stands behind a chunk's root panel: K4 under the call's root rule, or cafe_root_posterior's two kernels; behind the last
+// chunk (d_out given) the final sum, unless the tail is the posterior's.  (The pair also goes straight into pinned host memory:
+// cafe_score without a communicator reads it there after the stream has drained, no device-to-host copy.)
+int enqueue_root_tail(cafe_ctx* c, const CallMode& m, int64_t f0, int64_t cols, double* d_out, hipStream_t s) {
+    ReduceArgs r{};
+    r.root = c->d_panels + c->panels[c->root_panel].offset;
+    r.panel_kstride = c->panels[c->root_panel].kstride; r.ld = (int)cols; r.R = c->R; r.K = m.K; r.model = (int)m.reduction;
+    r.prior = c->d_prior; r.log_prior = c->d_logprior; r.cat_probs = c->d_catprobs;
+    r.f0 = f0; r.nf = std::max<int64_t>(0, std::min<int64_t>(cols, c->F_uniq - f0));
+    r.fam_out = c->d_fam_out; r.fam_lik = c->d_fam_lik; r.cat_out = c->d_cat_out; r.failed = c->d_failed;
+    if (m.tail == CallMode::kPosterior) HIP_TRY(c, launch_root_posterior(r, *m.posterior, s));
+    else if (m.tail == CallMode::kSum) HIP_TRY(c, launch_root_reduce_sum(r, s));
+    else HIP_TRY(c, launch_root_reduce(r, s));
+    c->last.chunk_f0 = f0; c->last.chunk_nf = r.nf;
+    if (d_out && m.tail != CallMode::kPosterior)
+        HIP_TRY(c, launch_final_sum(c->d_fam_out, c->d_weights, c->d_failed, c->F_uniq, c->d_scratch, c->n_scratch, d_out, c->h_result, s));
+    return CAFE_OK;
+}
+
+// The device work of one call, enqueued on `s` (or recorded into a graph being captured on `s`): parameter upload,
+// K1, the schedule (K2 / K3 launches), K4, the final sum into d_out.  Everything that changes between calls of the
+// same shape travels through the parameter block; kernel arguments depend only on the CallMode.
+int record_call(cafe_ctx* c, DescSet& ds, const CallMode& m, double* d_out, hipStream_t s, bool events, bool capturing) {
+    reset_work(c->stats);
+    c->last.desc = &ds;
+    // ---- host: tile heights and descriptors (the previous call's extents are in h_ext: that call was waited for)
+    std::vector<int32_t> prev_ext;
+    const std::vector<int32_t>* prev = previous_extents(c, m.K, prev_ext);
+    bool plan_needed = true;
+    int64_t planned_cols = std::min<int64_t>(c->chunk_cols, c->Fp);
+    if (!capturing) if (const int rc = prepare_descriptors(c, ds, m.K, planned_cols, prev, false, s, &plan_needed)) return rc;   // (a capture's: before it began)
+    if (const int rc = enqueue_prepass(c, ds, m, s, events)) return rc;
 
     // ---- prune, chunk by chunk (one chunk unless the workspace is limited)
     c->gemm_ev_used = 0;
     c->gemm_launches_info.clear();
-    int64_t planned_cols = cols0;
     for (int64_t f0 = 0; f0 < c->Fp; f0 += c->chunk_cols) {
         const int64_t cols = std::min<int64_t>(c->chunk_cols, c->Fp - f0);
-        const int uniform_ld = (c->subtree_dedup || c->grouped) ? 0 : (int)cols;
+        const bool last = f0 + c->chunk_cols >= c->Fp;
         if (cols != planned_cols) {          // the last chunk is narrower: its own descriptors and lists (same stream: in order)
             if (capturing) { set_err(c, "internal: a captured call cannot re-plan for a narrower last chunk"); return CAFE_ERR_STATE; }
             HIP_TRY(c, hipStreamSynchronize(s));             // the descriptors (and their pinned stage) are still in use by the chunks before
-            const int rc = prepare_descriptors(c, ds, K, cols, have_ext ? &prev_ext : nullptr, false, s, &plan_needed);
-            if (rc != CAFE_OK) return rc;
+            if (const int rc = prepare_descriptors(c, ds, m.K, cols, prev, false, s, &plan_needed)) return rc;
             plan_needed = true;
             planned_cols = cols;
             ds.plan_static_valid = false;
         }
+        // (several chunks with extents: the lists depend on this chunk's panel extents -- none: extents need one chunk -- and
+        // on the matrices, the same for every chunk: no re-plan)
         if (plan_needed && c->n_gemm_groups > 0)
             HIP_TRY(c, launch_tile_plan(ds.d_plan_desc, c->n_gemm_groups, *std::max_element(ds.group_rounds.begin(), ds.group_rounds.end()), s));
         plan_needed = false;
-        int gi = 0;
-        for (size_t g_index = 0; g_index < c->groups.size(); ++g_index) {
-            const Group& g = c->groups[g_index];
-            if (g.type == 0) {
-                GatherGroup gg{};
-                gg.pool = c->pool;
-                gg.ops = c->d_gather_ops + g.first_desc; gg.n_ops = (int)g.ops.size(); gg.n_categories = K;
-                gg.max_family_size = c->M;
-                gg.err = use_err ? c->d_err : nullptr; gg.n_dev = use_err ? c->n_dev : 0;
-                gg.uniform_ld = uniform_ld;
-                gg.f0 = c->subtree_dedup ? 0 : f0;
-                gg.leaf_t = leaf_t ? 1 : 0;
-                HIP_TRY(c, launch_leaf_gather_group(gg, c->h_gather_ops.data() + g.first_desc, s, c->has_missing));
-                continue;
-            }
-            GemmArgs a{};
-            a.pool = c->kpool; a.lpool = c->pool;
-            a.ops = ds.d_gemm_ops + g.first_desc; a.n_ops = (int)g.ops.size();
-            a.k_valid = c->M + 1; a.kb = c->kb; a.mi = ds.group_mi[gi]; a.n_categories = K;
-            a.uniform_ld = uniform_ld;
-            a.f0 = c->subtree_dedup ? 0 : f0;
-            a.err = use_err ? c->d_err : nullptr; a.max_family_size = c->M;
-            a.stamps = (c->stamps_launch < 0 || c->stamps_launch == (long)c->stats.gemm_launches) ? c->d_stamps : nullptr;
-            a.plan = ds.d_plan + ds.group_plan_off[gi]; a.plan_rounds = ds.group_rounds[gi];
-            if (events && c->gemm_ev_used + 2 <= c->gemm_ev.size()) {       // start / stop events ride on the dispatch itself
-                HIP_TRY(c, launch_prune_gemm(a, g.variant, ds.group_blocks[gi], s, c->gemm_ev[c->gemm_ev_used], c->gemm_ev[c->gemm_ev_used + 1]));
-                c->gemm_ev_used += 2;
-            } else {
-                HIP_TRY(c, launch_prune_gemm(a, g.variant, ds.group_blocks[gi], s));
-            }
-            c->stats.gemm_launches += 1;
-            c->gemm_launches_info.push_back({(int)g_index, K, a.mi, cols});
-            for (int oi : g.ops) {
-                const Op& op = c->ops[oi];
-                const double gc = (double)panel_cols(c, op.child, cols);
-                const int rows = op.to_root ? c->R : c->M;
-                c->stats.gemm_flops_dense += 2.0 * rows * (c->M + 1) * gc * K;
-                c->stats.gemm_flops += 2.0 * rows * (c->M + 1) * gc * K;      // (cafe_executed_flops counts what the tiles really ran)
-                c->stats.gemm_flops_per_family += 2.0 * rows * (c->M + 1) * (double)cols * K;
-                c->stats.gemm_bytes += 8.0 * K * ((double)rows * (c->M + 1) + (double)(c->M + 1) * gc + (double)rows * gc);
-            }
-            ++gi;
-        }
-        if (events && f0 + c->chunk_cols >= c->Fp) HIP_TRY(c, hipEventRecord(c->ev[2], s));
-        ReduceArgs r{};
-        r.root = c->d_panels + c->panels[c->root_panel].offset;
-        r.panel_kstride = c->panels[c->root_panel].kstride; r.ld = (int)cols; r.R = c->R; r.K = K; r.model = rootmax ? 2 : (gamma ? 1 : 0);
-        r.prior = c->d_prior; r.log_prior = c->d_logprior; r.cat_probs = c->d_catprobs;
-        r.f0 = f0; r.nf = std::max<int64_t>(0, std::min<int64_t>(cols, c->F_uniq - f0));
-        r.fam_out = c->d_fam_out; r.fam_lik = c->d_fam_lik; r.cat_out = c->d_cat_out; r.failed = c->d_failed;
-        if (c->root_posterior) HIP_TRY(c, launch_root_posterior(r, *c->root_posterior, s));     // cafe_root_posterior's two kernels
-        else if (rootsum) HIP_TRY(c, launch_root_reduce_sum(r, s));
-        else HIP_TRY(c, launch_root_reduce(r, s));
-        c->last_chunk_f0 = f0;
-        c->last_chunk_nf = r.nf;
-        // (several chunks with extents: the lists depend on this chunk's panel extents -- none: extents need one chunk -- and
-        // on the matrices, the same for every chunk: no re-plan)
+        if (const int rc = enqueue_chunk(c, ds, m, f0, cols, s, events)) return rc;
+        if (events && last) HIP_TRY(c, hipEventRecord(c->ev[2], s));
+        if (const int rc = enqueue_root_tail(c, m, f0, cols, last ? d_out : nullptr, s)) return rc;
     }
-    c->plan_launches_last = c->n_gemm_groups;
-    // (the pair also goes straight into pinned host memory: cafe_score without a communicator reads it there after the
-    // stream has drained, no device-to-host copy)
-    if (!c->root_posterior)
-        HIP_TRY(c, launch_final_sum(c->d_fam_out, c->d_weights, c->d_failed, c->F_uniq, c->d_scratch, c->n_scratch, d_out, c->h_result, s));
+    c->last.plan_launches = c->n_gemm_groups;
     if (events) { HIP_TRY(c, hipEventRecord(c->ev[3], s)); c->events_valid = true; }
     return CAFE_OK;
 }
@@ -450,12 +457,15 @@ int record_call(cafe_ctx* c, DescSet& ds, int K, bool gamma, bool rootmax, bool 
 
 // rootmax: the p-value path (probability.cpp:273-317, 391-444) prunes with the plain lambda, no error model and
 // no prior, and keeps max_j L_root[j] per family instead of the scorer's reduction.
-int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bool rootmax) {
+int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bool rootmax, const RootPosteriorArgs* posterior) {
+    c->last.had_comm = c->comm != nullptr;
     if (!pr || !pr->lambdas || (!rootmax && !pr->prior)) { set_err(c, "cafe_score: lambdas and prior are required"); return CAFE_ERR_ARGUMENT; }
-    const bool gamma = !rootmax && pr->model == CAFE_MODEL_GAMMA;
-    const bool use_err = !rootmax && c->n_dev > 0;
-    const bool rootsum = !rootmax && c->root_rule == CAFE_ROOT_SUM;
-    const int K = gamma ? pr->n_categories : 1;
+    CallMode m;
+    m.reduction = rootmax ? CallMode::kRootMax : pr->model == CAFE_MODEL_GAMMA ? CallMode::kGamma : CallMode::kBase;
+    m.tail = posterior ? CallMode::kPosterior : !rootmax && c->root_rule == CAFE_ROOT_SUM ? CallMode::kSum : CallMode::kMax;
+    m.posterior = posterior; m.use_err = !rootmax && c->n_dev > 0; m.two_rate = !c->mus.empty();
+    const bool gamma = m.reduction == CallMode::kGamma;
+    const int K = m.K = gamma ? pr->n_categories : 1;
     if (gamma && (K < 1 || K > c->Kmax || !pr->multipliers || !pr->cat_probs)) {
         set_err(c, "cafe_score: gamma model needs 1..%d categories with multipliers and cat_probs", c->Kmax);
         return CAFE_ERR_ARGUMENT;
@@ -465,67 +475,54 @@ int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bo
         return CAFE_ERR_ARGUMENT;
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    c->last_stream = s;
     if (const int rc = wait_for_stage(c)) return rc;
-    c->have_results = false;
+    open_call(c, K, s);
     c->events_valid = false;
-    c->K_last = K;
-    c->model_last = rootmax ? CAFE_MODEL_BASE : pr->model;
-    c->rootmax_last = rootmax;
+    c->last.model = rootmax ? CAFE_MODEL_BASE : pr->model;
 
-    c->last_rejected = rootmax || c->root_posterior ? !rates_valid(c, pr->lambdas) : rejected(c, pr, K);
-    if (c->last_rejected) {
+    if (rejected(c, pr, m)) {
         double* hr = reinterpret_cast<double*>(c->h_stage);
         hr[0] = 0.0; hr[1] = 1.0;
         HIP_TRY(c, hipMemcpyAsync(d_out, hr, 2 * sizeof(double), hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipEventRecord(c->ev_upload, s));
         c->upload_pending = true;
         c->stats.n_matrices = 0;
-        c->stats.gemm_flops = c->stats.gemm_bytes = c->stats.gemm_flops_per_family = 0;
-        c->stats.gemm_launches = 0;
+        reset_work(c->stats);
+        c->last.state = LastCall::kRejected;
         return CAFE_OK;
     }
 
     // ---- the call's parameters into the pinned mirror of the device block
     fill_slots(c, pr->lambdas, gamma ? pr->multipliers : nullptr, K);
-    {
-        double* h_prior = reinterpret_cast<double*>(c->h_stage + ((char*)c->d_prior - c->d_params));
-        double* h_logprior = reinterpret_cast<double*>(c->h_stage + ((char*)c->d_logprior - c->d_params));
-        double* h_cat = reinterpret_cast<double*>(c->h_stage + ((char*)c->d_catprobs - c->d_params));
-        for (int j = 0; j < c->R; ++j) {
-            const double eq = rootmax ? 1.0 : (double)pr->prior[j];    // compute() returns float (root_equilibrium_distribution.h:15)
-            h_prior[j] = eq;
-            h_logprior[j] = std::log(eq);
-        }
-        for (int k = 0; k < K; ++k) h_cat[k] = gamma ? pr->cat_probs[k] : 1.0;
-        if (use_err) std::memcpy(c->h_stage + ((char*)c->d_err - c->d_params), pr->error_model, sizeof(double) * (size_t)(c->M + 1) * c->n_dev);
+    double* h_prior = reinterpret_cast<double*>(c->h_stage + ((char*)c->d_prior - c->d_params));
+    double* h_logprior = reinterpret_cast<double*>(c->h_stage + ((char*)c->d_logprior - c->d_params));
+    double* h_cat = reinterpret_cast<double*>(c->h_stage + ((char*)c->d_catprobs - c->d_params));
+    for (int j = 0; j < c->R; ++j) {
+        const double eq = rootmax ? 1.0 : (double)pr->prior[j];    // compute() returns float (root_equilibrium_distribution.h:15)
+        h_prior[j] = eq;
+        h_logprior[j] = std::log(eq);
     }
+    for (int k = 0; k < K; ++k) h_cat[k] = gamma ? pr->cat_probs[k] : 1.0;
+    if (m.use_err) std::memcpy(c->h_stage + ((char*)c->d_err - c->d_params), pr->error_model, sizeof(double) * (size_t)(c->M + 1) * c->n_dev);
 
-    const bool graph_ok = c->use_graph && !c->profile && !c->d_stamps && c->force_mi == 0 && c->force_level_tiles == 0 && !c->root_posterior;
+    const bool graph_ok = c->use_graph && !c->profile && !c->d_stamps && c->force_mi == 0 && c->force_level_tiles == 0 && m.tail != CallMode::kPosterior;
     if (!graph_ok) {
-        const int rc = record_call(c, c->desc, K, gamma, rootmax, rootsum, use_err, d_out, s, c->profile != 0, false);
-        if (rc != CAFE_OK) return rc;
+        if (const int rc = record_call(c, c->desc, m, d_out, s, c->profile != 0, false)) return rc;
     } else {
-        // (a graph holds the K1 kernels of the mode and the K4 of the root rule it was captured in: one per mode and rule)
-        const int key = (rootmax ? 2 : (gamma ? 1 : 0)) + 4 * K + (c->mus.empty() ? 0 : 4 * (kMaxCategories + 1)) +
-                        (rootsum ? 8 * (kMaxCategories + 1) : 0);
+        const CallMode::GraphKey key = m.graph_key();
         cafe_ctx::CallGraph& cg = c->graphs[key];
         auto drop = [&]() { hipFree(cg.desc.d_gemm_ops); hipFree(cg.desc.d_plan_desc); hipFree(cg.desc.d_plan); c->graphs.erase(key); };
         if (!cg.exec) {
             // capture on the context's own stream (idle: calls are sequential), replay on the caller's.  The graph gets
             // descriptors and tile lists of its own, uploaded before the capture begins; its tile heights are frozen.
             if (c->stats.n_chunks > 1) { drop(); set_err(c, "cafe_set_graphs: a call in several column chunks cannot be captured"); return CAFE_ERR_STATE; }
-            {
-                const bool have_ext = c->h_ext && c->h_ext_valid && c->h_ext_K == K;
-                std::vector<int32_t> prev_ext;
-                if (have_ext) prev_ext.assign(c->h_ext, c->h_ext + (size_t)2 * c->n_kslots_last * c->kpool.ext_blocks);
-                bool plan_needed = true;
-                const int rp = prepare_descriptors(c, cg.desc, K, std::min<int64_t>(c->chunk_cols, c->Fp), have_ext ? &prev_ext : nullptr, true, c->stream, &plan_needed);
-                if (rp != CAFE_OK) { drop(); return rp; }
-            }
+            std::vector<int32_t> prev_ext;
+            bool plan_needed = true;
+            const int rp = prepare_descriptors(c, cg.desc, K, std::min<int64_t>(c->chunk_cols, c->Fp), previous_extents(c, K, prev_ext), true, c->stream, &plan_needed);
+            if (rp != CAFE_OK) { drop(); return rp; }
             hipGraph_t graph = nullptr;
             HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            const int rc = record_call(c, cg.desc, K, gamma, rootmax, rootsum, use_err, c->d_result, c->stream, false, true);
+            const int rc = record_call(c, cg.desc, m, c->d_result, c->stream, false, true);
             const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
             if (rc != CAFE_OK) { if (graph) (void)hipGraphDestroy(graph); drop(); return rc; }
             if (ee != hipSuccess || !graph) { drop(); set_err(c, "hipStreamEndCapture failed: %s", hipGetErrorString(ee)); return CAFE_ERR_DEVICE; }
@@ -534,19 +531,15 @@ int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bo
             if (ei != hipSuccess) { drop(); set_err(c, "hipGraphInstantiate failed: %s", hipGetErrorString(ei)); return CAFE_ERR_DEVICE; }
             cg.stats = c->stats;
         }
-        const int64_t n_mat = c->stats.n_matrices;
-        c->stats.gemm_flops = cg.stats.gemm_flops; c->stats.gemm_bytes = cg.stats.gemm_bytes;
-        c->stats.gemm_flops_per_family = cg.stats.gemm_flops_per_family; c->stats.gemm_launches = cg.stats.gemm_launches;
-        c->stats.gemm_flops_dense = cg.stats.gemm_flops_dense;
-        c->stats.n_matrices = n_mat;
-        c->last_chunk_f0 = (c->Fp - 1) / c->chunk_cols * c->chunk_cols;
-        c->last_chunk_nf = std::max<int64_t>(0, std::min<int64_t>(c->chunk_cols, c->F_uniq - c->last_chunk_f0));
+        copy_work(c->stats, cg.stats);
+        c->last.chunk_f0 = (c->Fp - 1) / c->chunk_cols * c->chunk_cols;
+        c->last.chunk_nf = std::max<int64_t>(0, std::min<int64_t>(c->chunk_cols, c->F_uniq - c->last.chunk_f0));
         HIP_TRY(c, hipGraphLaunch(cg.exec, s));
         if (d_out != c->d_result) HIP_TRY(c, hipMemcpyAsync(d_out, c->d_result, 2 * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
     HIP_TRY(c, hipEventRecord(c->ev_upload, s));
     c->upload_pending = true;
-    c->have_results = true;
+    c->last.state = rootmax || posterior ? LastCall::kMatricesOnly : LastCall::kScored;
     return CAFE_OK;
 }
 
@@ -582,14 +575,43 @@ int cafe_score_partial(cafe_ctx* ctx, const cafe_params* params, double* device_
     if (!ctx) return CAFE_ERR_ARGUMENT;
     if (!device_partial) { set_err(ctx, "cafe_score_partial: device_partial is NULL"); return CAFE_ERR_ARGUMENT; }
     const int rc = guarded(ctx, "cafe_score_partial", [&] { return enqueue(ctx, params, device_partial, (hipStream_t)hip_stream); });
+    if (rc == CAFE_OK) return rc;
     // the caller owns the collective: a failed shard leaves rejects = NaN in its pair (best effort), so that a reduction over
     // the shards reads NaN on every rank (cafe_finish_partial returns NaN) even if this return code goes unread
-    if (rc != CAFE_OK && ctx->h_poison && ctx->device_ready) {
-        (void)hipMemcpyAsync(device_partial, ctx->h_poison, 2 * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)hip_stream);
-        (void)hipStreamSynchronize((hipStream_t)hip_stream);        // whatever the failed call left in flight (its upload reads h_stage)
-        ctx->upload_pending = false;
-    }
+    if (ctx->h_poison && ctx->device_ready) (void)hipMemcpyAsync(device_partial, ctx->h_poison, 2 * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)hip_stream);
+    fail_after_enqueue(ctx, (hipStream_t)hip_stream);
     return rc;
+}
+
+// cafe_score behind a failed enqueue on a context with a communicator.  The call is collective: the other ranks are in the
+// all-reduce or on their way into it, whatever went wrong here (a HIP error, an allocation, an exception -- argument errors are
+// the same on every rank, but nothing relies on that).  Enter it with rejects = NaN: every rank then reads NaN and returns an
+// error.  If even that cannot be enqueued, abort the communicator; the others run into their deadline (comm_wait_stream).
+static void fail_together(cafe_ctx* ctx) {
+    const std::string first = ctx->err;
+    bool sent = hipSetDevice(ctx->device) == hipSuccess &&
+                hipMemcpyAsync(ctx->d_result, ctx->h_poison, 2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+                comm_allreduce_pair(ctx, ctx->d_result, ctx->stream) == CAFE_OK;
+    if (sent) sent = comm_wait_stream(ctx, ctx->stream) == CAFE_OK;
+    if (!sent) comm_abort(ctx);
+    set_err(ctx, "%s [rank %d of %d; the other ranks were %s]", first.c_str(), ctx->comm_rank, ctx->comm_world,
+            sent ? "told through the all-reduce" : "NOT told: communicator aborted");
+}
+
+// cafe_score behind its enqueue: {sum lnL, rejects}, summed over the communicator's ranks when there is one, in h_result
+static int read_score_pair(cafe_ctx* ctx) {
+    if (const int rc = comm_allreduce_pair(ctx, ctx->d_result, ctx->stream)) { comm_abort(ctx); return rc; }   // family shards on other GPUs: one RCCL all-reduce
+    // without a communicator K4's last kernel has already written the pair to h_result (a host-only rejection went
+    // through a copy into d_result instead)
+    if (ctx->comm || ctx->last.state == LastCall::kRejected)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_result, ctx->d_result, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (const int rc = comm_wait_stream(ctx, ctx->stream)) return rc;
+    ctx->upload_pending = false;
+    if (ctx->comm && std::isnan(ctx->h_result[1])) {                    // (rejects is a sum of family weights: never NaN by itself)
+        set_err(ctx, "cafe_score: another rank of the communicator failed its call (rank %d of %d read the poisoned pair)", ctx->comm_rank, ctx->comm_world);
+        return CAFE_ERR_DEVICE;
+    }
+    return CAFE_OK;
 }
 
 int cafe_score(cafe_ctx* ctx, const cafe_params* params, double* neg_lnl, const cafe_family_out* out) {
@@ -597,42 +619,9 @@ int cafe_score(cafe_ctx* ctx, const cafe_params* params, double* neg_lnl, const 
     if (!neg_lnl) { set_err(ctx, "cafe_score: neg_lnl is NULL"); return CAFE_ERR_ARGUMENT; }
     auto t0 = std::chrono::steady_clock::now();
     int rc = guarded(ctx, "cafe_score", [&] { return enqueue(ctx, params, ctx->d_result, ctx->stream); });
-    if (rc != CAFE_OK) {
-        if (!ctx->comm) {
-            if (ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);   // what the failed call left in flight
-            ctx->upload_pending = false;
-            return rc;
-        }
-        // The call is collective: the other ranks are in the all-reduce or on their way into it, whatever went wrong here
-        // (a HIP error, an allocation, an exception -- argument errors are the same on every rank, but nothing relies on
-        // that).  Enter it with rejects = NaN: every rank then reads NaN and returns an error.  If even that cannot be
-        // enqueued, abort the communicator; the others run into their deadline (comm_wait_stream).
-        const std::string first = ctx->err;
-        bool sent = hipSetDevice(ctx->device) == hipSuccess &&
-                    hipMemcpyAsync(ctx->d_result, ctx->h_poison, 2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
-                    comm_allreduce_pair(ctx, ctx->d_result, ctx->stream) == CAFE_OK;
-        if (sent) sent = comm_wait_stream(ctx, ctx->stream) == CAFE_OK;
-        if (!sent) comm_abort(ctx);
-        ctx->upload_pending = false;
-        ctx->have_results = false;
-        set_err(ctx, "%s [rank %d of %d; the other ranks were %s]", first.c_str(), ctx->comm_rank, ctx->comm_world,
-                sent ? "told through the all-reduce" : "NOT told: communicator aborted");
-        return rc;
-    }
-    rc = comm_allreduce_pair(ctx, ctx->d_result, ctx->stream);          // family shards on other GPUs: one RCCL all-reduce
-    if (rc != CAFE_OK) { comm_abort(ctx); return rc; }
-    // without a communicator K4's last kernel has already written the pair to h_result (a host-only rejection went
-    // through a copy into d_result instead)
-    if (ctx->comm || ctx->last_rejected)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_result, ctx->d_result, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    rc = comm_wait_stream(ctx, ctx->stream);
-    if (rc != CAFE_OK) return rc;
-    ctx->upload_pending = false;
-    if (ctx->comm && std::isnan(ctx->h_result[1])) {                    // (rejects is a sum of family weights: never NaN by itself)
-        ctx->have_results = false;
-        set_err(ctx, "cafe_score: another rank of the communicator failed its call (rank %d of %d read the poisoned pair)", ctx->comm_rank, ctx->comm_world);
-        return CAFE_ERR_DEVICE;
-    }
+    if (rc == CAFE_OK) rc = read_score_pair(ctx);
+    else if (ctx->comm) fail_together(ctx);
+    if (rc != CAFE_OK) { fail_after_enqueue(ctx, ctx->stream); return rc; }
     *neg_lnl = cafe_finish_partial(ctx->h_result);
     if (std::isnan(ctx->h_result[0])) ctx->panels_dirty = true;        // NaNs may now sit in the panels (see record_call)
     ctx->stats.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -643,20 +632,16 @@ int cafe_score(cafe_ctx* ctx, const cafe_params* params, double* neg_lnl, const 
 
 int cafe_family_results(cafe_ctx* ctx, const cafe_family_out* out) {
     if (!ctx || !out) return CAFE_ERR_ARGUMENT;
-    if (ctx->last_rejected || !ctx->have_results || ctx->rootmax_last) {
-        // the reference leaves `results` empty / stale on a rejected call (gamma_core.cpp:173-179)
-        set_err(ctx, "cafe_family_results: the last call was rejected (+inf) or no call was made");
-        return CAFE_ERR_STATE;
-    }
+    if (const int rc = require_last(ctx, "cafe_family_results", kScorerResults)) return rc;
     if (const int rc = wait_last_call(ctx)) return rc;
-    const int K = ctx->K_last;
+    const int K = ctx->last.K;
     std::vector<double> tmp((size_t)ctx->F_uniq * std::max(1, K));
     std::vector<int32_t> itmp;
     if (out->family_lnl) {
         HIP_TRY(ctx, hipMemcpy(tmp.data(), ctx->d_fam_out, sizeof(double) * ctx->F_uniq, hipMemcpyDeviceToHost));
         spread_unique(ctx, tmp.data(), out->family_lnl);
     }
-    if (ctx->model_last == CAFE_MODEL_GAMMA) {
+    if (ctx->last.model == CAFE_MODEL_GAMMA) {
         if (out->family_likelihood) {
             HIP_TRY(ctx, hipMemcpy(tmp.data(), ctx->d_fam_lik, sizeof(double) * ctx->F_uniq, hipMemcpyDeviceToHost));
             spread_unique(ctx, tmp.data(), out->family_likelihood);
@@ -677,11 +662,12 @@ int cafe_family_results(cafe_ctx* ctx, const cafe_family_out* out) {
 int cafe_root_max(cafe_ctx* ctx, const cafe_params* params, double* out) {
     if (!ctx) return CAFE_ERR_ARGUMENT;
     if (!out) { set_err(ctx, "cafe_root_max: out is NULL"); return CAFE_ERR_ARGUMENT; }
-    if (const int rc = guarded(ctx, "cafe_root_max", [&] { return enqueue(ctx, params, ctx->d_result, ctx->stream, true); })) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    int rc = guarded(ctx, "cafe_root_max", [&] { return enqueue(ctx, params, ctx->d_result, ctx->stream, true); });
+    if (rc == CAFE_OK) rc = wait_last_call(ctx);
+    if (rc != CAFE_OK) { fail_after_enqueue(ctx, ctx->stream); return rc; }
     ctx->upload_pending = false;
     collect_stats(ctx);
-    if (ctx->last_rejected) {            // an invalid lambda has no matrices: the reference would throw (matrix_cache.cpp:90)
+    if (ctx->last.state == LastCall::kRejected) {            // an invalid lambda has no matrices: the reference would throw (matrix_cache.cpp:90)
         set_err(ctx, "cafe_root_max: invalid lambda or death rate");
         return CAFE_ERR_ARGUMENT;
     }

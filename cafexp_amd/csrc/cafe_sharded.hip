@@ -498,7 +498,7 @@ int cafe_sharded_family_results(cafe_sharded* s, const cafe_family_out* out) {
     const int n = (int)s->ctx.size();
     std::vector<int> rc(n, CAFE_OK);
     int K = 1;
-    for (cafe_ctx* c : s->ctx) K = std::max(K, c->K_last);
+    for (cafe_ctx* c : s->ctx) K = std::max(K, c->last.K);
     s->run_all([&](int r) {
         const int64_t lo = s->bounds[r], nf = s->bounds[r + 1] - lo;
         std::vector<double> lnl, cat, lik;
@@ -511,7 +511,7 @@ int cafe_sharded_family_results(cafe_sharded* s, const cafe_family_out* out) {
         try { rc[r] = cafe_family_results(s->ctx[r], &o); }
         catch (const std::exception&) { rc[r] = CAFE_ERR_MEMORY; }
         if (rc[r] != CAFE_OK) return;
-        const bool gamma = s->ctx[r]->model_last == CAFE_MODEL_GAMMA;
+        const bool gamma = s->ctx[r]->last.model == CAFE_MODEL_GAMMA;
         for (int64_t i = 0; i < nf; ++i) {                   // shards write disjoint families
             const int64_t f = s->order[lo + i];
             if (out->family_lnl) out->family_lnl[f] = lnl[i];

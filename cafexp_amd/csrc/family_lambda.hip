@@ -174,7 +174,7 @@ int per_family_frame(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_
         else if (nan) family_lnl[i] = std::numeric_limits<double>::quiet_NaN();
         else active.push_back(i);
     }
-    c->have_results = false;                           // cafe_family_results is not meaningful after this call
+    c->last.state = LastCall::kNone;                   // cafe_family_results is not meaningful after this call
     if (active.empty()) return CAFE_OK;
     const int64_t na = (int64_t)active.size();
 

@@ -125,7 +125,7 @@ int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t see
     const int64_t Fs = (int64_t)R * n_sim;
 
     // ---- observed families: max_j L_root[j] (also builds this call's matrices for the plain lambdas)
-    { const int rc = enqueue_rootmax(c, pr->lambdas, s); if (rc != CAFE_OK) return rc; }
+    if (const int rc = enqueue_rootmax(c, pr->lambdas, s)) { fail_after_enqueue(c, s); return rc; }
 
     // ---- row-major matrix + CDF of EVERY branch (the scorer keeps interior branches k-major only)
     MatrixPool sp = row_major_pool(N);
@@ -191,7 +191,12 @@ int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t see
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
     CAFE_LAUNCH(c, simulate_kernel, dim3((unsigned)((Fs + 255) / 256)), dim3(256), 0, s, a);
     HIP_TRY(c, hipStreamSynchronize(s));                            // the child context runs on its own stream
-    { const int rc = enqueue_rootmax(child, pr->lambdas, child->stream); if (rc != CAFE_OK) { set_err(c, "cafe_pvalues: %s", child->err.c_str()); return rc; } }
+    if (const int rc = enqueue_rootmax(child, pr->lambdas, child->stream)) {
+        fail_after_enqueue(child, child->stream);
+        fail_after_enqueue(c, s);                                   // (the observed families' root maxima are not results of a failed call)
+        set_err(c, "cafe_pvalues: %s", child->err.c_str());
+        return rc;
+    }
     HIP_TRY(c, hipMemcpyAsync(d_cond.p, child->d_fam_out, sizeof(double) * Fs, hipMemcpyDeviceToDevice, child->stream));
     int P2 = 1;
     while (P2 < n_sim) P2 <<= 1;

@@ -156,19 +156,8 @@ int root_posterior_impl(cafe_ctx* c, const cafe_params* pr, const cafe_root_post
     HIP_TRY(c, hipMemsetAsync(ra.row_total, 0, sizeof(double) * (size_t)R, c->stream));
 
     // ---- one scorer call with the two kernels in K4's place
-    struct Hook {
-        cafe_ctx* c;
-        ~Hook() { c->root_posterior = nullptr; }
-    } hook{c};
-    c->root_posterior = &ra;
-    const int rc = enqueue(c, pr, c->d_result, c->stream);
-    if (rc != CAFE_OK) {
-        if (c->stream) (void)hipStreamSynchronize(c->stream);          // what the failed call left in flight
-        c->upload_pending = false;
-        c->have_results = false;
-        return rc;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (const int rc = enqueue(c, pr, c->d_result, c->stream, false, &ra)) { fail_after_enqueue(c, c->stream); return rc; }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));        // (a device error from here on: cafe_root_posterior below)
     close_posterior_call(c, nullptr);                   // the matrices stay readable; cafe_family_results is not meaningful
     collect_stats(c);
 
@@ -214,6 +203,6 @@ int root_posterior_impl(cafe_ctx* c, const cafe_params* pr, const cafe_root_post
 
 int cafe_root_posterior(cafe_ctx* ctx, const cafe_params* params, const cafe_root_posterior_out* out) {
     const int rc = cafe::guarded(ctx, "cafe_root_posterior", [&] { return cafe::root_posterior_impl(ctx, params, out); });
-    if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
+    if (rc == CAFE_ERR_DEVICE) cafe::fail_after_enqueue(ctx, ctx->stream);
     return rc;
 }

@@ -163,9 +163,7 @@ int upload_constants(cafe_ctx* c, const cafe_params* pr, PosteriorCall* pc);
 // The call succeeded: its matrices stay readable, scorer results are not meaningful; a timer's totals go to cafe_debug_marginal_gemm
 inline void close_posterior_call(cafe_ctx* c, const GemmTimer* timer) {
     c->upload_pending = false;
-    c->have_results = true;
-    c->rootmax_last = true;
-    c->last_rejected = false;
+    c->last.state = LastCall::kMatricesOnly;
     if (!timer) return;
     c->marginal_gemm_ms = timer->on ? timer->total_ms() : 0.0;
     c->marginal_gemm_flops = timer->flops;

@@ -224,7 +224,8 @@ int32_t cafe_sharded_size(const cafe_sharded* s);
 /* shard r's context (owned by s): statistics, introspection */
 cafe_ctx* cafe_sharded_context(cafe_sharded* s, int32_t r);
 
-/* Per-family results of the last call (valid after the stream was synchronised). */
+/* Per-family results of the last call (valid after the stream was synchronised).  CAFE_ERR_STATE when the last call was
+ * no scorer call, was rejected (+inf) or returned an error: a call reported as failed leaves nothing to read back. */
 int cafe_family_results(cafe_ctx* ctx, const cafe_family_out* out);
 
 /* P-value path.  For every family of the context: max_j L_root[j], the "observed max likelihood"
