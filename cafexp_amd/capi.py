@@ -75,6 +75,11 @@ class CafeLeafPredictiveOut(C.Structure):
                 ("failed", _i32p)]
 
 
+class CafeBranchChangeOut(C.Structure):
+    _fields_ = [("pmf", _f64p), ("below", _f64p), ("above", _f64p), ("mean", _f64p), ("mode", _i32p), ("lo", _i32p), ("hi", _i32p),
+                ("log_evidence", _f64p), ("failed", _i32p)]
+
+
 class CafeRootPosteriorOut(C.Structure):
     _fields_ = [("total", _f64p), ("n_used", _i64p), ("mean", _f64p), ("mode", _i32p), ("category_posterior", _f64p),
                 ("log_evidence", _f64p), ("failed", _i32p)]
@@ -123,7 +128,9 @@ EXPORTS = [
     "cafe_score_gradient", "cafe_bd_rates_grad", "cafe_expected_events", "cafe_bd_rates_events",
     "cafe_branch_scores", "cafe_branch_scores_dim", "cafe_weighted_gram", "cafe_debug_gram",
     "cafe_leaf_predictive", "cafe_set_root_rule", "cafe_get_root_rule", "cafe_root_posterior", "cafe_debug_magnitude_tables", "cafe_debug_level_tiles",
+    "cafe_branch_change", "cafe_debug_branch_change_band",
 ]
+CAFE_CHANGE_NONE = -(1 << 31)   # mode / lo / hi of cafe_branch_change at the root and in a failed family
 CAFE_COMM_ID_BYTES = 128
 MAG_NONE = -(1 << 28)           # a magnitude-table entry whose items are all exactly zero (cafe_kernels.h, kMagNone)
 MAG_UNIT = 256                  # table units per power of two
@@ -210,6 +217,10 @@ def load():
     L.cafe_bd_rates_events.argtypes = [C.c_double, C.c_double, C.c_double, _f64p]
     L.cafe_leaf_predictive.restype = C.c_int
     L.cafe_leaf_predictive.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.POINTER(CafeLeafPredictiveOut)]
+    L.cafe_branch_change.restype = C.c_int
+    L.cafe_branch_change.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.c_double, C.POINTER(CafeBranchChangeOut)]
+    L.cafe_debug_branch_change_band.restype = C.c_int
+    L.cafe_debug_branch_change_band.argtypes = [C.c_void_p, _f64p]
     L.cafe_set_root_rule.restype = C.c_int
     L.cafe_set_root_rule.argtypes = [C.c_void_p, C.c_int32]
     L.cafe_get_root_rule.restype = C.c_int
@@ -576,6 +587,33 @@ class Context:
             setattr(lo, name, _p(res[name], t))
         self._check(self._lib.cafe_leaf_predictive(self._h, C.byref(cp), C.byref(lo)))
         return res
+
+    def branch_change(self, pr: Params, max_change: int = 10, level: float = 0.95, pmf: bool = True, alpha: float = 1.0) -> dict:
+        """cafe_branch_change: the posterior of Delta = size(v) - size(parent(v)) on the branch above every node, under
+        marginal_reconstruct's model.  Returns numpy arrays: pmf [n_families][n_nodes][2 max_change + 1] over
+        -max_change..max_change (left out, and not allocated, with pmf=False), below and above (the mass beyond the band, each a
+        sum of its own), mean (exact over the whole range), mode, lo, hi [n_families][n_nodes] (lo = -max_change - 1 /
+        hi = max_change + 1: the interval's end lies in a tail), log_evidence and failed [n_families].  At the root and in a failed
+        family the doubles are NaN and the integers CAFE_CHANGE_NONE."""
+        cp, keep = self._params(pr, alpha)
+        F, n, D = self.n_families, self.n_nodes, int(max_change)
+        res = {"below": np.empty((F, n)), "above": np.empty((F, n)), "mean": np.empty((F, n)), "mode": np.empty((F, n), dtype=np.int32),
+               "lo": np.empty((F, n), dtype=np.int32), "hi": np.empty((F, n), dtype=np.int32), "log_evidence": np.empty(F),
+               "failed": np.empty(F, dtype=np.int32)}
+        if pmf:
+            res["pmf"] = np.empty((F, n, 2 * D + 1 if D >= 0 else 0))
+        co = CafeBranchChangeOut()
+        for name, t in CafeBranchChangeOut._fields_:
+            if name in res:
+                setattr(co, name, _p(res[name], t))
+        self._check(self._lib.cafe_branch_change(self._h, C.byref(cp), D, float(level), C.byref(co)))
+        return res
+
+    def branch_change_band_ms(self):
+        """summed HIP-event ms of the band kernel's launches of the last branch_change (0 unless profiling was on)"""
+        ms = C.c_double()
+        self._check(self._lib.cafe_debug_branch_change_band(self._h, C.byref(ms)))
+        return ms.value
 
     def sample_histories(self, pr: Params, n_draws: int, seed: int, alpha: float = 1.0, sizes: bool = True) -> dict:
         """cafe_sample_histories: n_draws ancestral histories of every family from the posterior of marginal_reconstruct's

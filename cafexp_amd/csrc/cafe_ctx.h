@@ -228,6 +228,7 @@ struct cafe_ctx {
     size_t pf_dev_bytes = 0;
     int64_t pf_max_batch = 0;                // CAFE_PER_FAMILY_BATCH: at most that many families per batch (diagnostic; 0 = what fits)
     double marginal_gemm_ms = 0, marginal_gemm_flops = 0;   // cafe_marginal_reconstruct: its GEMM launches (ms: while profiling)
+    double change_band_ms = 0;                              // cafe_branch_change: its band kernel's launches (while profiling)
     double gram_ms = 0.0, gram_flops = 0.0;  // the Gram kernels of the last cafe_branch_scores (ms: profiling on)
     int history_batches = 0, history_passes = 0;            // cafe_sample_histories: column batches, draw passes per batch of the last call
     int debug_fail_in = 0;                  // cafe_debug_fail_next: the n-th next enqueue fails behind its K1 launch

@@ -322,6 +322,35 @@ struct events_result {
 void write_events_reports(const events_result& res, const std::string& model_identifier, const std::string& dir,
                           const std::vector<const clade*>& order, const std::vector<gene_family>& families);
 
+// cafe_branch_change's summaries, [family][index in the caller's node order]: mean, mode and the equal-tailed interval at
+// `level` of Delta = size(node) - size(parent) on the branch above the node, and the posterior mass beyond the band of
+// +-max_change.  NaN / CAFE_CHANGE_NONE at the root and for a failed family; lo = -max_change - 1 / hi = max_change + 1: that end
+// of the interval lies beyond the band (failed: [family]).  names, root: [node], what the reports print and leave out.
+struct branch_change_result {
+    int max_change = 10;
+    double level = 0.95;
+    std::vector<std::string> names;
+    std::vector<char> root;
+    std::vector<double> mean, below, above;
+    std::vector<int32_t> mode, lo, hi, failed;
+    size_t n_nodes() const { return names.size(); }
+    size_t failed_count() const { size_t k = 0; for (int32_t f : failed) k += f != 0; return k; }
+};
+// One line of <Model>_branch_change_summary.tab: over the families that did not fail, the sum of the means, the families whose
+// interval lies wholly above 0 (lo > 0) and wholly below 0 (hi < 0), and the ones with an interval end beyond the band
+struct branch_change_row {
+    double mean_sum = 0;
+    size_t expanded = 0, contracted = 0, clipped = 0;
+};
+std::vector<branch_change_row> branch_change_rows(const branch_change_result& res);
+// "mean:mode:[lo,hi]:p_below_band:p_above_band" of one family and node ("-" at the root and for a failed family)
+std::string branch_change_cell(const branch_change_result& res, size_t family, size_t node);
+// <Model>_branch_change.tab (one branch_change_cell per family and node under a header row of the nodes' names) and
+// <Model>_branch_change_summary.tab (one branch_change_row per branch).  Returns the number of (family, branch) cells whose
+// interval is clipped by the band: raise max_change when it is not small
+size_t write_branch_change_reports(const branch_change_result& res, const std::string& model_identifier, const std::string& dir,
+                                   const std::vector<std::string>& family_ids);
+
 // cafe_leaf_predictive's outputs, [family][species] with the species in the order of `species` (NaN for a cell whose predictive
 // distribution has no mass; failed: [family], judged on the family's evidence)
 struct leaf_predictive_result {
@@ -514,6 +543,10 @@ public:
     // Expected number of births and of deaths on the branch above every node given the leaf counts, under the same model
     // (cafe_expected_events); columns in `order`
     events_result expected_events(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<const clade*>& order);
+    // The posterior of the size change on the branch above every node, in a band of +-max_change, summarised at `level`
+    // (cafe_branch_change; the band itself stays on the device side of the call); columns in `order`
+    branch_change_result branch_change(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, int max_change, double level,
+                                       const std::vector<const clade*>& order);
     // The posterior of every family's root size under the sum rule on the scorer's own prune, and its sum over the table
     // (cafe_root_posterior), at the model's current parameters
     root_posterior_result root_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist);

@@ -6,4 +6,8 @@
 
 namespace cafe {
 void hip_gamma_model::set_alpha(double) { std::abort(); }
+// branch_change_tests checks the reports' arithmetic on tables it writes down; the device call behind them has no CPU path either
+branch_change_result hip_model_base::branch_change(root_equilibrium_distribution*, const std::map<int, int>&, int, double, const std::vector<const clade*>&) {
+    std::abort();
+}
 }  // namespace cafe

@@ -199,6 +199,47 @@ void write_events_reports(const events_result& res, const std::string& model_ide
     }
 }
 
+branch_change_result hip_model_base::branch_change(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, int max_change, double level,
+                                                   const std::vector<const clade*>& order) {
+    std::vector<double> mult, probs;
+    double alpha = 0;
+    category_parameters(mult, probs, alpha);
+    const int K = mult.empty() ? 1 : (int)mult.size();
+    ensure_context(K);
+    std::vector<float> prior_f;
+    std::vector<double> err, lambdas;
+    gather_call_inputs(prior, rootdist, prior_f, err, lambdas);
+    cafe_params pr{};
+    pr.model = mult.empty() ? CAFE_MODEL_BASE : CAFE_MODEL_GAMMA;
+    pr.lambdas = lambdas.data(); pr.n_categories = K;
+    pr.multipliers = mult.empty() ? nullptr : mult.data();
+    pr.cat_probs = probs.empty() ? nullptr : probs.data();
+    pr.alpha = alpha; pr.prior = prior_f.data(); pr.error_model = err.empty() ? nullptr : err.data();
+    const size_t n = _order.size(), F = _p_gene_families->size(), m = order.size();
+    std::vector<double> mean(F * n), below(F * n), above(F * n);
+    std::vector<int32_t> mode(F * n), lo(F * n), hi(F * n);
+    branch_change_result res;
+    res.max_change = max_change; res.level = level;
+    res.failed.resize(F);
+    cafe_branch_change_out out{};                            // the band itself is not asked for: nothing of its size leaves the call
+    out.mean = mean.data(); out.below = below.data(); out.above = above.data(); out.mode = mode.data(); out.lo = lo.data(); out.hi = hi.data();
+    out.failed = res.failed.data();
+    if (cafe_branch_change(_ctx, &pr, max_change, level, &out) != CAFE_OK)
+        throw std::runtime_error(std::string("cafe_branch_change: ") + cafe_last_error(_ctx));
+    std::map<const clade*, size_t> pos;
+    for (size_t v = 0; v < n; ++v) pos[_order[v]] = v;
+    for (const clade* c : order) { res.names.push_back(clade_index_or_name(c, order)); res.root.push_back(c->is_root() ? 1 : 0); }
+    for (std::vector<double>* v : {&res.mean, &res.below, &res.above}) v->resize(F * m);
+    for (std::vector<int32_t>* v : {&res.mode, &res.lo, &res.hi}) v->resize(F * m);
+    for (size_t f = 0; f < F; ++f)
+        for (size_t i = 0; i < m; ++i) {
+            const size_t src = f * n + pos.at(order[i]), dst = f * m + i;
+            res.mean[dst] = mean[src]; res.below[dst] = below[src]; res.above[dst] = above[src];
+            res.mode[dst] = mode[src]; res.lo[dst] = lo[src]; res.hi[dst] = hi[src];
+        }
+    return res;
+}
+
 leaf_predictive_result hip_model_base::leaf_predictive(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist) {
     std::vector<double> mult, probs;
     double alpha = 0;

@@ -36,6 +36,12 @@ static void usage() {
         "                  [--expected-events]   after the search: the expected number of gene gains (births) and losses (deaths) on every\n"
         "                  branch of every family given its counts, under the fitted model; with -o: <Model>_expected_events.tab (gains:losses\n"
         "                  per family and node) and <Model>_branch_events.tab (per branch: gains, losses, net, turnover over the table); one GPU\n"
+        "                  [--branch-change [D] [-P PVALUE]]   after the search: for every family and branch the posterior of the change\n"
+        "                  size(node) - size(parent) under the fitted model, exact in a band of +-D (default 10) with the mass beyond it in two\n"
+        "                  tails -> in -o OUTDIR (default results) <Model>_branch_change.tab (mean:mode:[lo,hi]:p_below_band:p_above_band, the\n"
+        "                  equal-tailed interval at level 1 - PVALUE, default 0.95; lo = -D-1 / hi = D+1: beyond the band) and\n"
+        "                  <Model>_branch_change_summary.tab (per branch: summed mean change, families whose interval lies wholly above / wholly\n"
+        "                  below 0, families whose interval is clipped by the band: raise D); one GPU, not with -b, --simulate or missing cells\n"
         "                  [--standard-errors]   after the search: the per-family scores at the optimum, the standard error of every\n"
         "                  estimated lambda, mu (--estimate-mu) and alpha from their outer product, Wald 95 %% intervals, correlations and the\n"
         "                  total score -> <Model>_standard_errors.txt in -o OUTDIR (default results); one GPU, not with -b or --simulate\n"
@@ -48,7 +54,7 @@ static void usage() {
         "                  are such a file).  They are summed out of the likelihood (the family on the tree without that species); M and R\n"
         "                  come from the observed cells; with --leaf-predictive also <Model>_imputed_counts.tab (family, species, mean,\n"
         "                  sd, 95 %% interval of the predicted count).  Works with -b and --gpus; not with --pvalues, --reconstruct[-marginal],\n"
-        "                  --sample-histories, --standard-errors, --expected-events, --rate-shift-scan\n"
+        "                  --sample-histories, --standard-errors, --expected-events, --rate-shift-scan, --branch-change\n"
         "                  [--leaf-predictive [-P PVALUE]]   after the search: for every family and species the distribution of the species'\n"
         "                  count predicted from the counts of all the other species under the fitted model -> in -o OUTDIR (default results)\n"
         "                  <Model>_leaf_predictive.tab (mean:sd:p_low:p_high, the two one-sided tails of the observed count),\n"
@@ -207,6 +213,8 @@ int main(int argc, char** argv) {
     bool do_events = false;                                      // --expected-events
     bool do_rate_shift = false;                                  // --rate-shift-scan
     bool do_leaf_predictive = false;                             // --leaf-predictive
+    bool do_branch_change = false;                               // --branch-change [D]
+    int branch_change_band = 10;
     std::string missing_list, mask_path;                         // --missing TOKENS, --mask-cells FILE: cells whose count is unknown
     bool root_sum = false;                                       // --root-sum: score under CAFE_ROOT_SUM
     bool estimate_rootdist = false;                              // --estimate-rootdist [ROUNDS]
@@ -233,6 +241,7 @@ int main(int argc, char** argv) {
         else if (a == "--expected-events") do_events = true;
         else if (a == "--rate-shift-scan") do_rate_shift = true;
         else if (a == "--leaf-predictive") do_leaf_predictive = true;
+        else if (a == "--branch-change") { do_branch_change = true; std::string v = optional(); if (!v.empty()) branch_change_band = std::stoi(v); }
         else if (a == "--missing") missing_list = next();
         else if (a == "--mask-cells") mask_path = next();
         else if (a == "--root-sum") root_sum = true;
@@ -277,6 +286,7 @@ int main(int argc, char** argv) {
         if (do_events) { std::fprintf(stderr, "cafexp_hip: --expected-events belongs to a fitted model: --simulate is not supported with it\n"); return 1; }
         if (do_rate_shift) { std::fprintf(stderr, "cafexp_hip: --rate-shift-scan belongs to a fitted model: --simulate is not supported with it\n"); return 1; }
         if (do_leaf_predictive) { std::fprintf(stderr, "cafexp_hip: --leaf-predictive belongs to a fitted model: --simulate is not supported with it\n"); return 1; }
+        if (do_branch_change) { std::fprintf(stderr, "cafexp_hip: --branch-change belongs to a fitted model: --simulate is not supported with it\n"); return 1; }
         if (have_seed) randomizer_engine.seed(seed);
         return simulate_main(tree_path, fam_path, rootdist_path, lambda_tree_path, multi, err_path, use_err, fixed_lambda, fixed_alpha, k,
                              simulate_n, simulate_on_device, have_seed ? seed : randomizer_engine(), device, sim_workspace, out_dir, mu_list);
@@ -292,6 +302,7 @@ int main(int argc, char** argv) {
         else if (do_standard_errors) why = "--standard-errors is not ported to missing cells: it is not supported with --missing / --mask-cells";
         else if (do_events) why = "--expected-events is not ported to missing cells: it is not supported with --missing / --mask-cells";
         else if (do_rate_shift) why = "--rate-shift-scan is not ported to missing cells: it is not supported with --missing / --mask-cells";
+        else if (do_branch_change) why = "--branch-change is not ported to missing cells: it is not supported with --missing / --mask-cells";
         if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
     }
     if (estimate_mu || !mu_list.empty()) {
@@ -334,6 +345,14 @@ int main(int argc, char** argv) {
         const char* why = nullptr;
         if (gpus_given) why = "--leaf-predictive runs on one GPU: --gpus is not supported with it";
         else if (per_family) why = "--leaf-predictive needs one fitted model: -b is not supported with it";
+        if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
+    }
+    if (do_branch_change) {
+        const char* why = nullptr;
+        if (gpus_given) why = "--branch-change runs on one GPU: --gpus is not supported with it";
+        else if (per_family) why = "--branch-change needs one fitted model: -b is not supported with it";
+        else if (branch_change_band < 0) why = "--branch-change: D must not be negative";
+        else if (!(test_pvalue > 0 && test_pvalue < 1)) why = "--branch-change: PVALUE (-P) must lie in (0, 1)";
         if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
     }
     if (estimate_rootdist) {
@@ -705,6 +724,23 @@ int main(int argc, char** argv) {
             if (count_missing(d.gene_families).cells > 0) write_imputed_counts(lp, mdl->name(), dir, d.gene_families);
             predictive_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         }
+        // the posterior of every branch's size change under the same model: by how much, and how sure
+        double change_s = 0;
+        size_t change_failed = 0, change_clipped = 0;
+        if (do_branch_change) {
+            auto t0 = std::chrono::steady_clock::now();
+            cladevector order;
+            d.p_tree->apply_reverse_level_order([&order](const clade* c) { order.push_back(c); });
+            const int band = std::min(branch_change_band, std::max(d.max_family_size, d.max_root_family_size));      // no change is larger
+            const branch_change_result bc = mdl->branch_change(d.p_prior.get(), d.rootdist, band, 1.0 - test_pvalue, order);
+            const std::string dir = out_dir.empty() ? "results" : out_dir;
+            if (::mkdir(dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("Failed to create directory " + dir);
+            std::vector<std::string> ids;
+            for (const auto& gf : d.gene_families) ids.push_back(gf.id());
+            change_clipped = write_branch_change_reports(bc, mdl->name(), dir, ids);
+            change_failed = bc.failed_count();
+            change_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
         // standard errors of what the search estimated, from the per-family scores of the searched objective at the optimum
         standard_errors se;
         std::vector<double> slopes;
@@ -822,6 +858,9 @@ int main(int argc, char** argv) {
             std::printf(", \"histories\": {\"seconds\": %.3f, \"draws\": %d, \"failed\": %zu}", history_s, history_draws, history_failed);
         if (do_events)
             std::printf(", \"expected_events\": {\"seconds\": %.3f, \"failed\": %zu}", events_s, events_failed);
+        if (do_branch_change)
+            std::printf(", \"branch_change\": {\"seconds\": %.3f, \"max_change\": %d, \"level\": %.17g, \"failed\": %zu, \"clipped\": %zu}", change_s,
+                        std::min(branch_change_band, std::max(d.max_family_size, d.max_root_family_size)), 1.0 - test_pvalue, change_failed, change_clipped);
         if (do_leaf_predictive) {
             std::printf(", \"leaf_predictive\": {\"seconds\": %.3f, \"failed_cells\": %zu, \"outliers\": %zu, ", predictive_s, predictive.failed_cells, predictive.outliers);
             print_num("log_pseudo_likelihood", predictive.log_pseudo_likelihood, false);

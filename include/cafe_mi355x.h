@@ -95,7 +95,7 @@ typedef struct cafe_problem {
  * cafe_leaf_predictive returns for a missing cell the predictive mean and sd of the count given the family's observed species;
  * its p_below, p_obs and p_above are NaN there (nothing was observed), and log_evidence is over the observed cells.
  * cafe_pvalues, cafe_reconstruct, cafe_branch_probabilities, cafe_marginal_reconstruct, cafe_sample_histories,
- * cafe_score_gradient, cafe_branch_scores and cafe_expected_events return CAFE_ERR_STATE ("... the table has missing cells")
+ * cafe_score_gradient, cafe_branch_scores, cafe_expected_events and cafe_branch_change return CAFE_ERR_STATE ("... the table has missing cells")
  * before anything is enqueued; the context stays usable. */
 #define CAFE_FLAG_MISSING_COUNTS 4
 #define CAFE_COUNT_MISSING (-1)
@@ -558,6 +558,50 @@ typedef struct cafe_leaf_predictive_out {
     int32_t* failed;        /* [n_families] */
 } cafe_leaf_predictive_out;
 int cafe_leaf_predictive(cafe_ctx* ctx, const cafe_params* params, const cafe_leaf_predictive_out* out);
+
+/* Posterior of each branch's size change: for every family and non-root node v, the distribution of Delta = X_v - X_parent(v)
+ * given the leaf counts -- by how much the family changed on the branch, and how sure that is.  Parent and child are strongly
+ * correlated, so this cannot be formed from the two nodes' rows of cafe_marginal_reconstruct.  The model is that call's: the
+ * call's lambdas, categories, prior and error model, the context's death rates when set, the root weight of CAFE_ROOT_SUM.  With
+ * G_v the down pass's outside message on the parent's sizes, P_v the branch's matrix and B_v the up pass's message of v, per
+ * category k (i = 0..np, np = R under the root, else M; j = 0..M; P[0][j] = delta(j, 0)):
+ *     J_k[i][j] = G_v^k[i] P_v^k[i][j] B_v^k[j]
+ *     w[d]  = sum_k p_k sum_i J_k[i][i + d],  d = -max_change..max_change, terms with i + d outside 0..M absent
+ *     below = sum_k p_k sum_{j - i < -max_change} J_k[i][j]        above = sum_k p_k sum_{j - i > max_change} J_k[i][j]
+ * all divided by Z = sum_k p_k Z_k.  A leaf branch without an error model has j fixed at the observed x; with one, Delta is
+ * (true size c_t) - i with weights err[x][t] G[i] P[i][c_t], the taps in the scorer's order, taps outside 0..M dropped.  Each
+ * w[d] is summed in the order of i, then over the taps, then over k: it has the same bits whatever max_change, workspace_limit
+ * or column batch the call ran with.  The tails are sums of their own, never complements.  Outputs (host pointers, any may
+ * be NULL), in the problem's orders:
+ *   pmf [n_families][n_nodes][2 max_change + 1]: P(Delta = d | data), d ascending;
+ *   below, above [n_families][n_nodes]: P(Delta < -max_change | data), P(Delta > max_change | data);
+ *   mean [n_families][n_nodes] = E[X_v] - E[X_parent] from the two nodes' posteriors: exact over the whole range, not the band's;
+ *   mode: the first arg max over the band;  lo / hi: the equal-tailed interval at `level` in (0, 1) on the CDF over
+ *     (below, -max_change..max_change, above): lo = min{d : CDF(d) >= (1 - level) / 2}, hi = min{d : CDF(d) >= 1 - (1 - level) / 2};
+ *     lo = -max_change - 1 / hi = max_change + 1: the crossing lies in the lower / upper tail (raise max_change);
+ *   log_evidence, failed [n_families] as cafe_marginal_reconstruct.
+ * At the root, and at every node of a failed family (Z zero or not finite), the doubles are NaN and the integers
+ * CAFE_CHANGE_NONE (-1 is a valid change); the call still returns CAFE_OK.  CAFE_ERR_ARGUMENT for max_change outside
+ * 0..max(M, R), a level outside (0, 1), invalid rates or a bad K; CAFE_ERR_STATE on a context with a communicator attached or
+ * with missing cells.  The columns are processed in batches that fit the problem's workspace_limit (0 = automatic); identical
+ * families get identical rows.  cafe_family_results is not meaningful after this call; a later cafe_score is unaffected;
+ * cafe_debug_marginal_gemm reports this call's GEMM launches. */
+#define CAFE_CHANGE_NONE (-2147483647 - 1)
+typedef struct cafe_branch_change_out {
+    double*  pmf;           /* [n_families][n_nodes][2 max_change + 1] */
+    double*  below;         /* [n_families][n_nodes] */
+    double*  above;
+    double*  mean;
+    int32_t* mode;
+    int32_t* lo;
+    int32_t* hi;
+    double*  log_evidence;  /* [n_families] */
+    int32_t* failed;        /* [n_families] */
+} cafe_branch_change_out;
+int cafe_branch_change(cafe_ctx* ctx, const cafe_params* params, int32_t max_change, double level, const cafe_branch_change_out* out);
+/* measurement: the summed HIP-event time in milliseconds of the band kernel's launches of the last cafe_branch_change when it
+ * ran with profiling on (cafe_set_profiling), else 0 */
+int cafe_debug_branch_change_band(cafe_ctx* ctx, double* ms);
 
 /* Root rule of a context: what the scorer makes of a family's root vector L_j (j = 0..R-1 for root size j + 1).  A property of
  * the context, like the death rates: every later scoring call reads it.  CAFE_ROOT_MAX (the default) is the reference's rule,
