@@ -48,6 +48,13 @@ class CafeParams(C.Structure):
     ]
 
 
+class CafeBatchParams(C.Structure):
+    _fields_ = [
+        ("n_points", C.c_int32), ("model", C.c_int32), ("n_categories", C.c_int32), ("lambdas", _f64p), ("mus", _f64p),
+        ("multipliers", _f64p), ("cat_probs", _f64p), ("alpha", _f64p), ("prior", _f32p), ("error_model", _f64p),
+    ]
+
+
 class CafeFamilyOut(C.Structure):
     _fields_ = [("family_lnl", _f64p), ("category_likelihood", _f64p), ("family_likelihood", _f64p), ("failed", _i32p)]
 
@@ -128,7 +135,7 @@ EXPORTS = [
     "cafe_score_gradient", "cafe_bd_rates_grad", "cafe_expected_events", "cafe_bd_rates_events",
     "cafe_branch_scores", "cafe_branch_scores_dim", "cafe_weighted_gram", "cafe_debug_gram",
     "cafe_leaf_predictive", "cafe_set_root_rule", "cafe_get_root_rule", "cafe_root_posterior", "cafe_debug_magnitude_tables", "cafe_debug_level_tiles",
-    "cafe_branch_change", "cafe_debug_branch_change_band",
+    "cafe_branch_change", "cafe_debug_branch_change_band", "cafe_score_batch",
 ]
 CAFE_CHANGE_NONE = -(1 << 31)   # mode / lo / hi of cafe_branch_change at the root and in a failed family
 CAFE_COMM_ID_BYTES = 128
@@ -167,6 +174,8 @@ def load():
     L.cafe_last_error.argtypes = [C.c_void_p]
     L.cafe_score.restype = C.c_int
     L.cafe_score.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p, C.POINTER(CafeFamilyOut)]
+    L.cafe_score_batch.restype = C.c_int
+    L.cafe_score_batch.argtypes = [C.c_void_p, C.POINTER(CafeBatchParams), _f64p]
     L.cafe_score_partial.restype = C.c_int
     L.cafe_score_partial.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_void_p, C.c_void_p]
     L.cafe_finish_partial.restype = C.c_double
@@ -432,6 +441,47 @@ class Context:
         if not per_family:
             return out.value
         return out.value, self.family_results(len(pr.multipliers) if pr.multipliers is not None else 0)
+
+    def score_batch(self, points, alphas=None, mus=None) -> np.ndarray:
+        """cafe_score_batch: -lnL of several parameter vectors in one call, a float64 array with score()'s bits for each.
+        points: Params of one model (all base, or all gamma with the same number of categories); prior and error model are the
+        first point's, shared by the batch.  alphas: one per point (gamma; default 1.0).  mus: [len(points)][n_lambdas] death
+        rates per point (the context must have death rates set), None: the context's own."""
+        points = list(points)
+        G = len(points)
+        if G < 1:
+            raise ValueError("score_batch needs at least one point")
+        gamma = points[0].multipliers is not None
+        K = len(points[0].multipliers) if gamma else 1
+        for pr in points:
+            if (pr.multipliers is not None) != gamma or (gamma and len(pr.multipliers) != K):
+                raise ValueError("the points of a batch share one model and one number of categories")
+        bp = CafeBatchParams()
+        bp.n_points, bp.model, bp.n_categories = G, (CAFE_MODEL_GAMMA if gamma else CAFE_MODEL_BASE), K
+        lam = np.ascontiguousarray([np.atleast_1d(pr.lambdas) for pr in points], dtype=np.float64)
+        if lam.shape != (G, self.problem.n_lambdas):
+            raise ValueError("every point needs %d lambdas" % self.problem.n_lambdas)
+        bp.lambdas = _p(lam, _f64p)
+        mu = None
+        if mus is not None:
+            mu = np.ascontiguousarray(mus, dtype=np.float64).reshape(G, -1)
+            if mu.shape != lam.shape:
+                raise ValueError("mus must be [%d][%d]" % lam.shape)
+            bp.mus = _p(mu, _f64p)
+        if gamma:
+            mult = np.ascontiguousarray([pr.multipliers for pr in points], dtype=np.float64)
+            cat = np.ascontiguousarray([pr.cat_probs for pr in points], dtype=np.float64)
+            al = np.ascontiguousarray(np.ones(G) if alphas is None else alphas, dtype=np.float64)
+            if mult.shape != (G, K) or cat.shape != (G, K) or al.shape != (G,):
+                raise ValueError("multipliers and cat_probs must be [%d][%d], alphas [%d]" % (G, K, G))
+            bp.multipliers, bp.cat_probs, bp.alpha = _p(mult, _f64p), _p(cat, _f64p), _p(al, _f64p)
+        prior = np.ascontiguousarray(points[0].prior, dtype=np.float32)
+        bp.prior = _p(prior, _f32p)
+        err = np.ascontiguousarray(points[0].error_model, dtype=np.float64) if points[0].error_model is not None else None
+        bp.error_model = _p(err, _f64p)
+        out = np.empty(G)
+        self._check(self._lib.cafe_score_batch(self._h, C.byref(bp), _p(out, _f64p)))
+        return out
 
     def family_results(self, K: int = 0):
         F = self.n_families

@@ -69,7 +69,8 @@ inline void fail_after_enqueue(cafe_ctx* c, hipStream_t s) {
 enum LastNeed { kCompletedCall, kScorerResults };
 inline int require_last(cafe_ctx* c, const char* entry, LastNeed what = kCompletedCall) {
     if (c->last.state == LastCall::kScored || (what == kCompletedCall && c->last.state == LastCall::kMatricesOnly)) return CAFE_OK;
-    set_err(c, "%s: %s", entry, what == kCompletedCall ? "no completed call" : "the last call was rejected (+inf) or no call was made");
+    set_err(c, "%s: %s", entry, c->last.state == LastCall::kBatch ? "the last call was a batch (cafe_score_batch): nothing of it can be read back"
+                                : what == kCompletedCall ? "no completed call" : "the last call was rejected (+inf) or no call was made");
     return CAFE_ERR_STATE;
 }
 

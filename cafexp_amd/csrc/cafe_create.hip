@@ -34,6 +34,7 @@ void free_device(cafe_ctx* c) {
     free_desc(c->desc);
     for (auto& g : c->graphs) free_desc(g.second.desc);
     hipFree(c->d_slots_lm); if (c->h_slots_lm) hipHostFree(c->h_slots_lm);
+    hipFree(c->d_bfam_out); hipFree(c->d_bfailed); hipFree(c->d_bscratch); hipFree(c->d_bresult); if (c->h_bresult) hipHostFree(c->h_bresult);
     hipFree(c->d_gather_ops); hipFree(c->d_lt); hipFree(c->d_lt_pairs); hipFree(c->pf_dev);
     if (c->ev_upload) hipEventDestroy(c->ev_upload);
     for (auto& e : c->ev) if (e) hipEventDestroy(e);

@@ -84,6 +84,13 @@ inline int64_t round_up64(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 struct RootPosteriorArgs;                    // root_sum.h
 
+// The rates of one category of a call (fill_slots, cafe_score.hip): lambdas and mus are [n_lambdas], mus nullptr: mu = lambda
+struct CategoryRates {
+    const double* lambdas;
+    const double* mus;
+    double multiplier;
+};
+
 // What kind of scorer call this is, built once at the top of enqueue (cafe_score.hip): kernel arguments, the launches behind the
 // root panel and the captured graph a call replays follow from it and from nothing else
 struct CallMode {
@@ -91,12 +98,17 @@ struct CallMode {
     enum Tail { kMax, kSum, kPosterior } tail = kMax;    // K4 under either root rule, or cafe_root_posterior's two kernels on `posterior`
     const RootPosteriorArgs* posterior = nullptr;
     int K = 1;
+    // cafe_score_batch: `points` parameter vectors of K / points categories each ride through the prune as the K categories of
+    // this call; behind the root panel stand the batch's two kernels (root_reduce_batch.hip).  0: a single call.
+    int points = 0;
     bool use_err = false, two_rate = false;  // error model; death rates set (K1's two-rate instantiation)
     struct GraphKey {                        // what a captured graph is captured for (cafe_ctx::graphs)
-        int reduction, K; bool two_rate, root_sum;
-        bool operator<(const GraphKey& o) const { return std::tie(reduction, K, two_rate, root_sum) < std::tie(o.reduction, o.K, o.two_rate, o.root_sum); }
+        int reduction, K; bool two_rate, root_sum; int points;
+        bool operator<(const GraphKey& o) const {
+            return std::tie(reduction, K, two_rate, root_sum, points) < std::tie(o.reduction, o.K, o.two_rate, o.root_sum, o.points);
+        }
     };
-    GraphKey graph_key() const { return {(int)reduction, K, two_rate, tail == kSum}; }
+    GraphKey graph_key() const { return {(int)reduction, K, two_rate, tail == kSum, points}; }
 };
 
 // What the last call left behind.  A call opens by setting state = kNone (open_call, cafe_call.h) and closes by setting its final
@@ -107,7 +119,8 @@ struct LastCall {
         kNone,                               // nothing to read: fresh context, failed call, a matrix call not yet closed, cafe_score_per_family
         kRejected,                           // the host rejected the parameters (+inf): nothing was built
         kScored,                             // a scorer call: everything is readable
-        kMatricesOnly                        // root maximum, a closed posterior call, cafe_root_posterior: all but cafe_family_results
+        kMatricesOnly,                       // root maximum, a closed posterior call, cafe_root_posterior: all but cafe_family_results
+        kBatch                               // cafe_score_batch: the categories were several points' -- nothing a read-back could name
     } state = kNone;
     int K = 0, model = -1, n_slots = 0, n_kslots = 0;
     int64_t chunk_f0 = 0, chunk_nf = 0;      // the column chunk resident in the panels
@@ -204,6 +217,13 @@ struct cafe_ctx {
     double* d_scratch = nullptr;
     int n_scratch = 1024;
     double* d_result = nullptr;
+    // cafe_score_batch: per point (at most Kmax of them) a row of per-family values and flags, a scratch region with its ticket
+    // for the final sum and a pair {sum lnL, rejects}, on the device and in pinned host memory; allocated by the first batch call
+    double* d_bfam_out = nullptr;            // [Kmax][F_uniq]
+    int32_t* d_bfailed = nullptr;            // [Kmax][F_uniq]
+    double* d_bscratch = nullptr;            // [Kmax][2 * n_scratch + 1]
+    double* d_bresult = nullptr;             // [Kmax][2]
+    double* h_bresult = nullptr;             // pinned [Kmax][2]
     unsigned long long* d_stamps = nullptr;     // diagnostic block timeline of the LAST K2 launch (CAFE_GEMM_STAMPS=1)
     size_t stamps_words = 0;
     // pinned staging
@@ -348,12 +368,15 @@ void free_device(cafe_ctx* c);                            // releases what creat
 // cafe_score.hip
 bool lambdas_valid(const cafe_ctx* c, const double* lam);
 bool rates_valid(const cafe_ctx* c, const double* lam);  // lambdas_valid, and no death rate of the context (cafe_set_death_rates) negative
+bool rates_valid(const cafe_ctx* c, const double* lam, const double* mus);     // ... of `mus` ([n_lambdas], or nullptr: none)
 int set_death_rates_impl(cafe_ctx* c, const double* mus);     // cafe_set_death_rates: [n_lambdas] or nullptr (lambda = mu again)
 // the (lambda, mu) of lambda index i under multiplier `mult` as the matrix key quantizes them; mu = lambda without death rates
-inline void quantized_rates(const cafe_ctx* c, const double* lambdas, int i, double mult, long* lq, long* mq) {
+// (mus: [n_lambdas] death rates, nullptr: none)
+inline void quantized_rates(const double* lambdas, const double* mus, int i, double mult, long* lq, long* mq) {
     *lq = quantize_lambda(lambdas[i] * mult);
-    *mq = c->mus.empty() ? *lq : quantize_lambda(c->mus[i] * mult);
+    *mq = mus ? quantize_lambda(mus[i] * mult) : *lq;
 }
+inline const double* context_mus(const cafe_ctx* c) { return c->mus.empty() ? nullptr : c->mus.data(); }
 // one scorer call enqueued on `s`, {sum lnL, rejects} -> d_out; rootmax: max_j L_root[j] per family instead (-> d_fam_out); posterior:
 // cafe_root_posterior's two kernels where K4 and the final sum stand, on the stream path (no graph), without the gamma model's host rejection
 int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bool rootmax = false, const RootPosteriorArgs* posterior = nullptr);

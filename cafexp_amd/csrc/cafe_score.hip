@@ -22,7 +22,7 @@
 #include <vector>
 
 #include "cafe_call.h"
-#include "root_sum.h"
+#include "root_family.h"
 
 using namespace cafe;
 
@@ -44,11 +44,12 @@ bool lambdas_valid(const cafe_ctx* c, const double* lam) {
 }
 
 // ... and the death rates of the context, when it has any: no rate may be negative (one lambda: that lambda > 0 as above)
-bool rates_valid(const cafe_ctx* c, const double* lam) {
+bool rates_valid(const cafe_ctx* c, const double* lam, const double* mus) {
     if (!lambdas_valid(c, lam)) return false;
-    for (const double mu : c->mus) if (!(mu >= 0)) return false;
+    for (int i = 0; mus && i < c->n_lambdas; ++i) if (!(mus[i] >= 0)) return false;
     return true;
 }
+bool rates_valid(const cafe_ctx* c, const double* lam) { return rates_valid(c, lam, context_mus(c)); }
 
 int set_death_rates_impl(cafe_ctx* c, const double* mus) {
     if (!mus) { c->mus.clear(); return CAFE_OK; }
@@ -76,14 +77,17 @@ int wait_for_stage(cafe_ctx* c) {
 
 // Slot parameters of a call into the pinned stage: slot = k * n_pairs[layout] + pair, built from the de-quantized key
 // like matrix_cache.cpp:148-149 (lambda.h:39, :82-88 for lambda * multiplier).
-void fill_slots(cafe_ctx* c, const double* lambdas, const double* multipliers, int K) {
+// Every category brings its own rates: the K of a gamma call share one (lambdas, mus) and differ in the multiplier, the G * K of a
+// batch (cafe_score_batch) are K per parameter vector.  The two-rate parameters are written whenever the context has death
+// rates set (a category's mus then stand in for the context's).
+void fill_slots(cafe_ctx* c, const CategoryRates* cats, int K) {
     SlotParam* h[2] = {reinterpret_cast<SlotParam*>(c->h_stage), reinterpret_cast<SlotParam*>(c->h_stage) + c->max_slots};
     for (int layout = 0; layout < 2; ++layout) {
         const int P = c->n_pairs[layout];
         for (int k = 0; k < K; ++k)
             for (int p = 0; p < P; ++p) {
                 long lq, mq;
-                quantized_rates(c, lambdas, c->pair_lam[layout][p], multipliers ? multipliers[k] : 1.0, &lq, &mq);
+                quantized_rates(cats[k].lambdas, cats[k].mus, c->pair_lam[layout][p], cats[k].multiplier, &lq, &mq);
                 h[layout][k * P + p] = slot_param(lq, c->pair_tq[layout][p]);
                 // death rates set: the two-rate kernel's parameters, same slots (the multiplier scales both rates)
                 if (!c->mus.empty()) c->h_slots_lm[(layout ? c->max_slots : 0) + k * P + p] = slot_param_lm(lq, mq, c->pair_tq[layout][p]);
@@ -92,6 +96,12 @@ void fill_slots(cafe_ctx* c, const double* lambdas, const double* multipliers, i
     c->last.n_slots = K * c->n_pairs[0];
     c->last.n_kslots = K * c->n_pairs[1];
     c->stats.n_matrices = (int64_t)K * c->n_distinct_pairs;
+}
+// ... of one parameter vector under the context's own death rates
+void fill_slots(cafe_ctx* c, const double* lambdas, const double* multipliers, int K) {
+    std::vector<CategoryRates> cats(K);
+    for (int k = 0; k < K; ++k) cats[k] = {lambdas, context_mus(c), multipliers ? multipliers[k] : 1.0};
+    fill_slots(c, cats.data(), K);
 }
 
 // K1 of a call whose slot parameters fill_slots left in the pinned mirrors: the lambda = mu kernels, or with death rates set
@@ -125,11 +135,11 @@ namespace {
 
 // Host-only rejections; true => the call's value is +inf without touching the device.  (The gamma model's own apply to the
 // scorer's reduction, not to cafe_root_posterior's.)
-bool rejected(const cafe_ctx* c, const cafe_params* pr, const CallMode& m) {
-    if (!rates_valid(c, pr->lambdas)) return true;                             // base_model.cpp:56 / gamma_core.cpp:125
-    if (m.reduction != CallMode::kGamma || m.tail == CallMode::kPosterior) return false;
-    const int K = m.K;
-    if (pr->alpha < 0) return true;                                            // gamma_core.cpp:128
+// One parameter vector: lambdas, mus ([n_lambdas], or nullptr: none), and with gamma_rules the K multipliers and alpha.
+bool rejected(const cafe_ctx* c, const double* lambdas, const double* mus, bool gamma_rules, const double* multipliers, int K, double alpha) {
+    if (!rates_valid(c, lambdas, mus)) return true;                            // base_model.cpp:56 / gamma_core.cpp:125
+    if (!gamma_rules) return false;
+    if (alpha < 0) return true;                                                // gamma_core.cpp:128
     // gamma_core.cpp:131-139: longest branch x largest multiplier x largest lambda saturated?
     bool first = true;
     double longest = 0;
@@ -138,12 +148,15 @@ bool rejected(const cafe_ctx* c, const cafe_params* pr, const CallMode& m) {
         if (!(t > 0.0)) continue;
         if (first || t > longest) { longest = t; first = false; }
     }
-    double lm = *std::max_element(pr->multipliers, pr->multipliers + K);
-    double ll = *std::max_element(pr->lambdas, pr->lambdas + c->n_lambdas);
+    double lm = *std::max_element(multipliers, multipliers + K);
+    double ll = *std::max_element(lambdas, lambdas + c->n_lambdas);
     double lambda = lm * ll;
     // matrix_cache.cpp:115; with death rates: coeff = 1 - alpha - beta of that branch under the largest of either rate
-    const double mu = c->mus.empty() ? lambda : lm * *std::max_element(c->mus.begin(), c->mus.end());
+    const double mu = !mus ? lambda : lm * *std::max_element(mus, mus + c->n_lambdas);
     return bd_rates(lambda, mu, longest).coeff < 0;
+}
+bool rejected(const cafe_ctx* c, const cafe_params* pr, const CallMode& m) {
+    return rejected(c, pr->lambdas, context_mus(c), m.reduction == CallMode::kGamma && m.tail != CallMode::kPosterior, pr->multipliers, m.K, pr->alpha);
 }
 
 // Row-tile height of one K2 launch (a group of ops) from the (previous call's) non-zero extents of its matrices: a tile runs
@@ -396,6 +409,20 @@ int enqueue_chunk(cafe_ctx* c, const DescSet& ds, const CallMode& m, int64_t f0,
 // chunk (d_out given) the final sum, unless the tail is the posterior's.  (The pair also goes straight into pinned host memory:
 // cafe_score without a communicator reads it there after the stream has drained, no device-to-host copy.)
 int enqueue_root_tail(cafe_ctx* c, const CallMode& m, int64_t f0, int64_t cols, double* d_out, hipStream_t s) {
+    if (m.points > 0) {                      // a batch: one launch reduces every point's categories, one sums every point's families
+        ReduceBatchArgs b{};
+        b.root = c->d_panels + c->panels[c->root_panel].offset;
+        b.panel_kstride = c->panels[c->root_panel].kstride; b.ld = (int32_t)cols; b.R = c->R; b.K = m.K / m.points; b.G = m.points;
+        b.model = (int)m.reduction; b.root_sum = m.tail == CallMode::kSum;
+        b.prior = c->d_prior; b.log_prior = c->d_logprior; b.cat_probs = c->d_catprobs;
+        b.f0 = f0; b.nf = std::max<int64_t>(0, std::min<int64_t>(cols, c->F_uniq - f0)); b.F = c->F_uniq;
+        b.fam_out = c->d_bfam_out; b.failed = c->d_bfailed;
+        HIP_TRY(c, launch_root_reduce_batch(b, s));
+        c->last.chunk_f0 = f0; c->last.chunk_nf = b.nf;
+        if (d_out)
+            HIP_TRY(c, launch_final_sum_batch(c->d_bfam_out, c->d_weights, c->d_bfailed, c->F_uniq, m.points, c->d_bscratch, c->n_scratch, d_out, c->h_bresult, s));
+        return CAFE_OK;
+    }
     ReduceArgs r{};
     r.root = c->d_panels + c->panels[c->root_panel].offset;
     r.panel_kstride = c->panels[c->root_panel].kstride; r.ld = (int)cols; r.R = c->R; r.K = m.K; r.model = (int)m.reduction;
@@ -455,6 +482,8 @@ int record_call(cafe_ctx* c, DescSet& ds, const CallMode& m, double* d_out, hipS
 
 }  // namespace
 
+int launch_call(cafe_ctx* c, const CallMode& m, double* d_out, hipStream_t s);
+
 // rootmax: the p-value path (probability.cpp:273-317, 391-444) prunes with the plain lambda, no error model and
 // no prior, and keeps max_j L_root[j] per family instead of the scorer's reduction.
 int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bool rootmax, const RootPosteriorArgs* posterior) {
@@ -505,6 +534,16 @@ int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bo
     for (int k = 0; k < K; ++k) h_cat[k] = gamma ? pr->cat_probs[k] : 1.0;
     if (m.use_err) std::memcpy(c->h_stage + ((char*)c->d_err - c->d_params), pr->error_model, sizeof(double) * (size_t)(c->M + 1) * c->n_dev);
 
+    if (const int rc = launch_call(c, m, d_out, s)) return rc;
+    c->last.state = rootmax || posterior ? LastCall::kMatricesOnly : LastCall::kScored;
+    return CAFE_OK;
+}
+
+// The device work of a call whose parameters stand in the pinned mirror: enqueued on `s`, or -- cafe_set_graphs -- captured once
+// per graph key and replayed.  d_out: the pair of a single call, [points][2] of a batch.
+int launch_call(cafe_ctx* c, const CallMode& m, double* d_out, hipStream_t s) {
+    const int K = m.K;
+    double* const own_out = m.points > 0 ? c->d_bresult : c->d_result;          // where a captured graph leaves its result
     const bool graph_ok = c->use_graph && !c->profile && !c->d_stamps && c->force_mi == 0 && c->force_level_tiles == 0 && m.tail != CallMode::kPosterior;
     if (!graph_ok) {
         if (const int rc = record_call(c, c->desc, m, d_out, s, c->profile != 0, false)) return rc;
@@ -522,7 +561,7 @@ int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bo
             if (rp != CAFE_OK) { drop(); return rp; }
             hipGraph_t graph = nullptr;
             HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            const int rc = record_call(c, cg.desc, m, c->d_result, c->stream, false, true);
+            const int rc = record_call(c, cg.desc, m, own_out, c->stream, false, true);
             const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
             if (rc != CAFE_OK) { if (graph) (void)hipGraphDestroy(graph); drop(); return rc; }
             if (ee != hipSuccess || !graph) { drop(); set_err(c, "hipStreamEndCapture failed: %s", hipGetErrorString(ee)); return CAFE_ERR_DEVICE; }
@@ -535,11 +574,101 @@ int enqueue(cafe_ctx* c, const cafe_params* pr, double* d_out, hipStream_t s, bo
         c->last.chunk_f0 = (c->Fp - 1) / c->chunk_cols * c->chunk_cols;
         c->last.chunk_nf = std::max<int64_t>(0, std::min<int64_t>(c->chunk_cols, c->F_uniq - c->last.chunk_f0));
         HIP_TRY(c, hipGraphLaunch(cg.exec, s));
-        if (d_out != c->d_result) HIP_TRY(c, hipMemcpyAsync(d_out, c->d_result, 2 * sizeof(double), hipMemcpyDeviceToDevice, s));
+        if (d_out != own_out) HIP_TRY(c, hipMemcpyAsync(d_out, own_out, 2 * sizeof(double) * std::max(1, m.points), hipMemcpyDeviceToDevice, s));
     }
     HIP_TRY(c, hipEventRecord(c->ev_upload, s));
     c->upload_pending = true;
-    c->last.state = rootmax || posterior ? LastCall::kMatricesOnly : LastCall::kScored;
+    return CAFE_OK;
+}
+
+// cafe_score_batch's buffers, sized for as many points as the context has categories (a batch cannot hold more); each on its
+// own pointer: a call that failed half way allocates only what is still missing
+static int ensure_batch_buffers(cafe_ctx* c) {
+    const size_t G = (size_t)std::max(1, c->Kmax), F = (size_t)std::max<int64_t>(1, c->F_uniq), ns = (size_t)(2 * c->n_scratch + 1);
+    if (!c->d_bfam_out) HIP_TRY(c, hipMalloc(&c->d_bfam_out, sizeof(double) * G * F));
+    if (!c->d_bfailed) HIP_TRY(c, hipMalloc(&c->d_bfailed, sizeof(int32_t) * G * F));
+    if (!c->d_bscratch) {
+        HIP_TRY(c, hipMalloc(&c->d_bscratch, sizeof(double) * G * ns));
+        const hipError_t e = hipMemset(c->d_bscratch, 0, sizeof(double) * G * ns);     // the tickets start at zero
+        if (e != hipSuccess) { (void)hipFree(c->d_bscratch); c->d_bscratch = nullptr; HIP_TRY(c, e); }
+    }
+    if (!c->d_bresult) HIP_TRY(c, hipMalloc(&c->d_bresult, sizeof(double) * 2 * G));
+    if (!c->h_bresult) HIP_TRY(c, hipHostMalloc(&c->h_bresult, sizeof(double) * 2 * G, hipHostMallocDefault));
+    return CAFE_OK;
+}
+
+// cafe_score_batch up to its last launch.  live: the points the host did not reject, in batch order -- point live[i] rides as
+// the categories i K .. i K + K - 1 of one call and leaves its pair in h_bresult[2 i ..]; a rejected point costs nothing.
+int enqueue_batch(cafe_ctx* c, const cafe_batch_params* bp, std::vector<int>& live) {
+    hipStream_t s = c->stream;
+    c->last.had_comm = c->comm != nullptr;
+    if (!bp || !bp->lambdas || !bp->prior) { set_err(c, "cafe_score_batch: lambdas and prior are required"); return CAFE_ERR_ARGUMENT; }
+    if (bp->n_points < 1) { set_err(c, "cafe_score_batch: n_points must be at least 1"); return CAFE_ERR_ARGUMENT; }
+    if (bp->model != CAFE_MODEL_BASE && bp->model != CAFE_MODEL_GAMMA) { set_err(c, "cafe_score_batch: unknown model %d", bp->model); return CAFE_ERR_ARGUMENT; }
+    const bool gamma = bp->model == CAFE_MODEL_GAMMA;
+    const int G = bp->n_points, K = gamma ? bp->n_categories : 1, L = c->n_lambdas;
+    if (gamma && (K < 1 || !bp->multipliers || !bp->cat_probs || !bp->alpha)) {
+        set_err(c, "cafe_score_batch: gamma model needs at least one category with multipliers, cat_probs and alpha of every point");
+        return CAFE_ERR_ARGUMENT;
+    }
+    if ((int64_t)G * K > c->Kmax) {
+        set_err(c, "cafe_score_batch: %d points x %d categories exceed the context's max_categories = %d", G, K, c->Kmax);
+        return CAFE_ERR_ARGUMENT;
+    }
+    if ((c->n_dev > 0) != (bp->error_model != nullptr)) {
+        set_err(c, "cafe_score_batch: error model %s but the problem was created with n_deviations=%d", bp->error_model ? "given" : "missing", c->n_dev);
+        return CAFE_ERR_ARGUMENT;
+    }
+    if (c->comm) { set_err(c, "cafe_score_batch: not available on a context with a communicator attached"); return CAFE_ERR_STATE; }
+    if (bp->mus && c->mus.empty()) { set_err(c, "cafe_score_batch: mus given but the context has no death rates set (cafe_set_death_rates)"); return CAFE_ERR_STATE; }
+
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = wait_for_stage(c)) return rc;
+    open_call(c, 0, s);
+    c->events_valid = false;
+    c->last.model = bp->model;
+    auto mus_of = [&](int g) { return bp->mus ? bp->mus + (size_t)g * L : context_mus(c); };
+    live.clear();
+    for (int g = 0; g < G; ++g)
+        if (!rejected(c, bp->lambdas + (size_t)g * L, mus_of(g), gamma, gamma ? bp->multipliers + (size_t)g * K : nullptr, K, gamma ? bp->alpha[g] : 0.0))
+            live.push_back(g);
+    const int Gl = (int)live.size();
+    if (Gl == 0) {                           // nothing to build: every value is +inf
+        c->stats.n_matrices = 0;
+        reset_work(c->stats);
+        c->last.state = LastCall::kBatch;
+        return CAFE_OK;
+    }
+    if (const int rc = ensure_batch_buffers(c)) return rc;
+
+    CallMode m;
+    m.reduction = gamma ? CallMode::kGamma : CallMode::kBase;
+    m.tail = c->root_rule == CAFE_ROOT_SUM ? CallMode::kSum : CallMode::kMax;
+    m.use_err = c->n_dev > 0; m.two_rate = !c->mus.empty();
+    m.points = Gl; m.K = Gl * K;
+    c->last.K = m.K;
+
+    // ---- the call's parameters into the pinned mirror of the device block
+    std::vector<CategoryRates> cats((size_t)m.K);
+    double* h_prior = reinterpret_cast<double*>(c->h_stage + ((char*)c->d_prior - c->d_params));
+    double* h_logprior = reinterpret_cast<double*>(c->h_stage + ((char*)c->d_logprior - c->d_params));
+    double* h_cat = reinterpret_cast<double*>(c->h_stage + ((char*)c->d_catprobs - c->d_params));
+    for (int i = 0; i < Gl; ++i)
+        for (int k = 0; k < K; ++k) {
+            const int g = live[i];
+            cats[(size_t)i * K + k] = {bp->lambdas + (size_t)g * L, mus_of(g), gamma ? bp->multipliers[(size_t)g * K + k] : 1.0};
+            h_cat[(size_t)i * K + k] = gamma ? bp->cat_probs[(size_t)g * K + k] : 1.0;
+        }
+    fill_slots(c, cats.data(), m.K);
+    for (int j = 0; j < c->R; ++j) {
+        const double eq = (double)bp->prior[j];
+        h_prior[j] = eq;
+        h_logprior[j] = std::log(eq);
+    }
+    if (m.use_err) std::memcpy(c->h_stage + ((char*)c->d_err - c->d_params), bp->error_model, sizeof(double) * (size_t)(c->M + 1) * c->n_dev);
+
+    if (const int rc = launch_call(c, m, c->d_bresult, s)) return rc;
+    c->last.state = LastCall::kBatch;
     return CAFE_OK;
 }
 
@@ -627,6 +756,27 @@ int cafe_score(cafe_ctx* ctx, const cafe_params* params, double* neg_lnl, const 
     ctx->stats.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     collect_stats(ctx);
     if (out) return cafe_family_results(ctx, out);
+    return CAFE_OK;
+}
+
+int cafe_score_batch(cafe_ctx* ctx, const cafe_batch_params* params, double* neg_lnl) {
+    if (!ctx) return CAFE_ERR_ARGUMENT;
+    if (!neg_lnl) { set_err(ctx, "cafe_score_batch: neg_lnl is NULL"); return CAFE_ERR_ARGUMENT; }
+    auto t0 = std::chrono::steady_clock::now();
+    std::vector<int> live;
+    int rc = guarded(ctx, "cafe_score_batch", [&] { return enqueue_batch(ctx, params, live); });
+    // the batch's last kernel has written every live point's pair to h_bresult
+    if (rc == CAFE_OK && !live.empty()) rc = comm_wait_stream(ctx, ctx->stream);
+    if (rc != CAFE_OK) { fail_after_enqueue(ctx, ctx->stream); return rc; }
+    ctx->upload_pending = false;
+    for (int g = 0; g < params->n_points; ++g) neg_lnl[g] = std::numeric_limits<double>::infinity();
+    for (size_t i = 0; i < live.size(); ++i) {
+        const double* hp = ctx->h_bresult + 2 * i;
+        neg_lnl[live[i]] = cafe_finish_partial(hp);
+        if (std::isnan(hp[0])) ctx->panels_dirty = true;                // NaNs may now sit in the panels (see record_call)
+    }
+    ctx->stats.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    collect_stats(ctx);
     return CAFE_OK;
 }
 

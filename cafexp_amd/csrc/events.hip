@@ -149,7 +149,7 @@ BranchEvents branch_events(const cafe_ctx* c, const double* lambdas, int v, doub
     const int layout = c->leaf_taxon[v] >= 0 ? 0 : 1;
     const long tq = c->pair_tq[layout][c->pair_of[v]];
     long lq, mq;
-    quantized_rates(c, lambdas, c->lam_idx[v], mult, &lq, &mq);
+    quantized_rates(lambdas, context_mus(c), c->lam_idx[v], mult, &lq, &mq);
     BranchEvents r{};
     double alpha;
     if (c->mus.empty()) {

@@ -253,7 +253,7 @@ BranchRates branch_rates(const cafe_ctx* c, const double* lambdas, int v, double
     const int layout = c->leaf_taxon[v] >= 0 ? 0 : 1;
     const long tq = c->pair_tq[layout][c->pair_of[v]];
     long lq, mq;
-    quantized_rates(c, lambdas, c->lam_idx[v], mult, &lq, &mq);
+    quantized_rates(lambdas, context_mus(c), c->lam_idx[v], mult, &lq, &mq);
     BranchRates r{};
     const double l = double(lq) / 1000000000.0, m = double(mq) / 1000000000.0, t = double(tq) / 1000.0;
     if (c->mus.empty()) {

@@ -12,7 +12,7 @@
 #include <algorithm>
 
 #include "cafe_kernels.h"
-#include "root_sum.h"
+#include "root_family.h"
 
 namespace cafe {
 
@@ -430,30 +430,9 @@ hipError_t launch_leaf_gather_group(const GatherGroup& g, const GatherArgs* h_op
 
 // kRedFam families x kRedSeg row segments per workgroup: thread (family, segment) walks the rows j = segment,
 // segment + kRedSeg, ... of its family's root column (a wave instruction reads kRedFam consecutive families of 64 / kRedFam
-// rows: full 128-byte lines), the segments are then combined in LDS.  Maxima do not depend on the order they are combined
-// in; the category sum is only tested against zero (all terms are non-negative).  NaN follows the reference's scan
-// (std::max_element / the `>` scan of gamma_core.cpp:158): a NaN at j = 0 is returned, a NaN elsewhere never wins a
-// comparison.  (One thread per family, 750 x 8 dependent strided loads, took 2.5 ms whatever the number of families.)
-constexpr int kRedFam = 16, kRedSeg = 16;
-__device__ inline double combine_max(double* sh, int fam, int seg, double v) {
-    sh[seg * kRedFam + fam] = v;
-    __syncthreads();
-    double best = sh[fam];
-    if (seg == 0)
-        for (int s2 = 1; s2 < kRedSeg; ++s2) { const double p = sh[s2 * kRedFam + fam]; if (p > best) best = p; }
-    __syncthreads();
-    return best;
-}
-__device__ inline double combine_sum(double* sh, int fam, int seg, double v) {
-    sh[seg * kRedFam + fam] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (seg == 0)
-        for (int s2 = 0; s2 < kRedSeg; ++s2) t += sh[s2 * kRedFam + fam];
-    __syncthreads();
-    return t;
-}
-
+// rows: full 128-byte lines), the segments are then combined in LDS.  The per-family arithmetic is root_family.h's, shared
+// with the kernels of a batch.  (One thread per family, 750 x 8 dependent strided loads, took 2.5 ms whatever the number of
+// families.)
 __global__ __launch_bounds__(256) void root_reduce_kernel(const ReduceArgs a) {
     __shared__ double sh[kRedFam * kRedSeg];
     const int fam = threadIdx.x % kRedFam, seg = threadIdx.x / kRedFam;
@@ -476,39 +455,13 @@ __global__ __launch_bounds__(256) void root_reduce_kernel(const ReduceArgs a) {
         return;
     }
     if (a.model == 0) {
-        // lnL_f = max_j( log L_j + log prior_j ), first maximum like std::max_element (base_model.cpp:94-101)
-        const double* col = a.root + fl;
-        double best = ninf;
-        if (live)
-            for (int j = seg; j < a.R; j += kRedSeg) {
-                const double full = log(col[(int64_t)j * a.ld]) + a.log_prior[j];
-                if (j == 0 || full > best) best = full;
-            }
-        best = combine_max(sh, fam, seg, best);
+        const double best = family_base_max(a.root + fl, a.ld, a.R, a.log_prior, live, sh, fam, seg);
         if (live && seg == 0) { a.fam_out[f] = best; a.failed[f] = 0; }
         return;
     }
-    double lik = 0.0;
     int fail = 0;
-    for (int k = 0; k < a.K; ++k) {
-        const double* col = a.root + (int64_t)k * a.panel_kstride + fl;
-        double sum = 0.0, best = ninf;
-        if (live)
-            for (int j = seg; j < a.R; j += kRedSeg) {
-                const double L = col[(int64_t)j * a.ld];
-                sum += L;
-                const double full = L * a.prior[j];
-                if (j == 0 || full > best) best = full;
-            }
-        sum = combine_sum(sh, fam, seg, sum);
-        best = combine_max(sh, fam, seg, best);
-        if (live && seg == 0) {
-            if (sum == 0.0) fail = 1;                      // "saturation", gamma_core.cpp:152
-            const double cl = best * a.cat_probs[k];        // gamma_core.cpp:162
-            a.cat_out[f * a.K + k] = cl;
-            lik += cl;                                      // gamma_core.cpp:207
-        }
-    }
+    const double lik = family_gamma_max(a.root + fl, a.panel_kstride, a.ld, a.R, a.K, a.prior, a.cat_probs, live, sh, fam, seg,
+                                        live ? a.cat_out + f * a.K : nullptr, &fail);
     if (live && seg == 0) {
         a.fam_lik[f] = lik;
         a.fam_out[f] = log(lik);
@@ -538,18 +491,9 @@ __global__ __launch_bounds__(256) void root_reduce_sum_kernel(const ReduceArgs a
         if (live && seg == 0) { a.fam_out[f] = v; a.failed[f] = 0; }
         return;
     }
-    double lik = 0.0;
     int fail = 0;
-    for (int k = 0; k < a.K; ++k) {
-        double plain;
-        const double s = column_sum(a.root + (int64_t)k * a.panel_kstride + fl, a.ld, a.R, a.prior, live, sh, fam, seg, &plain);
-        if (live && seg == 0) {
-            if (plain == 0.0) fail = 1;                    // "saturation", gamma_core.cpp:152
-            const double cl = s * a.cat_probs[k];
-            a.cat_out[f * a.K + k] = cl;
-            lik += cl;
-        }
-    }
+    const double lik = family_gamma_sum(a.root + fl, a.panel_kstride, a.ld, a.R, a.K, a.prior, a.cat_probs, live, sh, fam, seg,
+                                        live ? a.cat_out + f * a.K : nullptr, &fail);
     if (live && seg == 0) {
         a.fam_lik[f] = lik;
         a.fam_out[f] = log(lik);
@@ -566,61 +510,19 @@ hipError_t launch_root_reduce_sum(const ReduceArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-// Deterministic two-stage sum: fixed block partials, then one block folds them in index order.
-__device__ inline double block_sum(double v, double* sh) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) sh[w] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
-    __syncthreads();
-    return t;
-}
-
-// ... and the block that finishes last folds the partials, in index order whichever block that is (one launch instead of two:
-// in the small-matrix regime a call is the sum of its kernels' latencies).  scratch: [2 * blocks] partials, then one
-// unsigned counter (zero between calls: the folding block resets it).
+// The final sum (root_family.h: final_sum_block): the block that finishes last folds the partials, in index order whichever
+// block that is (one launch instead of two: in the small-matrix regime a call is the sum of its kernels' latencies).
 // out2: optionally a second copy, in host memory the device can write (the scorer's return value without a copy engine hop)
 __global__ __launch_bounds__(256) void partial_sum_kernel(const double* __restrict__ fam_out, const double* __restrict__ w,
                                                           const int32_t* __restrict__ failed, int64_t n, double* scratch, double* out, double* out2) {
     __shared__ double sh[4];
     __shared__ bool last;
-    double s = 0.0, bad = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        s += w[i] * fam_out[i];
-        bad += failed[i] ? w[i] : 0.0;
-    }
-    const double ts = block_sum(s, sh);
-    const double tb = block_sum(bad, sh);
-    unsigned* counter = reinterpret_cast<unsigned*>(scratch + 2 * gridDim.x);
-    if (threadIdx.x == 0) {
-        scratch[2 * blockIdx.x] = ts;
-        scratch[2 * blockIdx.x + 1] = tb;
-        __threadfence();                                     // the partials are visible before the ticket is taken
-        last = atomicAdd(counter, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last || threadIdx.x != 0) return;
-    __threadfence();
-    double fs = 0.0, fb = 0.0;
-    const volatile double* sc = scratch;                     // (written by other blocks of this launch)
-    for (unsigned i = 0; i < gridDim.x; ++i) {
-        fs += sc[2 * i];
-        fb += sc[2 * i + 1];
-    }
-    out[0] = fs;
-    out[1] = fb;
-    if (out2) { out2[0] = fs; out2[1] = fb; }
-    *counter = 0u;
+    final_sum_block(fam_out, w, failed, n, scratch, out, out2, blockIdx.x, gridDim.x, sh, &last);
 }
 
 hipError_t launch_final_sum(const double* fam_out, const double* weights, const int32_t* failed, int64_t n,
                             double* scratch, int n_scratch, double* out, double* out_host, hipStream_t stream) {
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > n_scratch) blocks = n_scratch;
-    if (blocks < 1) blocks = 1;
+    const int blocks = final_sum_blocks(n, n_scratch);
     (void)hipGetLastError();
     hipLaunchKernelGGL(partial_sum_kernel, dim3(blocks), dim3(256), 0, stream, fam_out, weights, failed, n, scratch, out, out_host);
     return hipGetLastError();

@@ -140,7 +140,7 @@ int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t see
         h_leaf[v] = c->leaf_taxon[v];
         if (v == c->root) continue;
         long lq, mq;
-        quantized_rates(c, pr->lambdas, c->lam_idx[v], 1.0, &lq, &mq);
+        quantized_rates(pr->lambdas, context_mus(c), c->lam_idx[v], 1.0, &lq, &mq);
         const long tq = quantize_time(c->blen[v]);
         auto it = key_slot.find({tq, lq, mq});
         if (it == key_slot.end()) {

@@ -277,6 +277,17 @@ public:
     virtual reconstruction* reconstruct_ancestral_states(const std::vector<gene_family>& families, root_equilibrium_distribution* p_prior);
     const std::vector<family_info_stash>& get_results() const { return results; }
     const event_monitor& get_monitor() const { return _monitor; }
+    // a parameter vector the search consumed whose score was already known (optimizer::batch): counted as the call it replaces
+    void note_attempt() { _monitor.attempts++; }
+    // scores made ahead of the search are not attempts of its trajectory: the monitor is put back behind them
+    void restore_monitor(const event_monitor& m) { _monitor = m; }
+    // Several parameter vectors in one device call (cafe_score_batch).  batch_begin: true when the model can score n_points
+    // vectors at once -- the caller then sets each vector on the model through its own setters and calls batch_stage, which
+    // records the model's parameters of that moment as the next point, and batch_score returns every point's
+    // infer_family_likelihoods value (out[n_points]) without touching results or the monitor.  Default: cannot.
+    virtual bool batch_begin(int n_points) { (void)n_points; return false; }
+    virtual void batch_stage() {}
+    virtual void batch_score(root_equilibrium_distribution*, const std::map<int, int>&, double*) {}
     void initialize_lambda(const clade* lambda_tree);                // core.cpp:76
     const clade* tree() const { return _p_tree; }
 };
@@ -524,6 +535,11 @@ public:
     ~hip_model_base() override;
     void set_device(int d) { _device = d; }
     void set_workspace_limit(size_t bytes) { _workspace_limit = bytes; }     // cafe_problem::workspace_limit of the contexts made from now on
+    // G > 1: the contexts made from now on hold G times the model's categories, and batch_begin accepts up to G points
+    void set_search_batch(int points) { _search_batch = points < 1 ? 1 : points; }
+    bool batch_begin(int n_points) override;
+    void batch_stage() override;
+    void batch_score(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, double* out) override;
     void set_devices(const std::vector<int>& d) { _devices = d; if (!d.empty()) _device = d[0]; }
     // compute_pvalues with the Monte-Carlo simulation on the device too (cafe_pvalues): statistical agreement with the
     // reference's procedure, not draw for draw
@@ -560,6 +576,12 @@ public:
 protected:
     // gamma model: multipliers, category probabilities and alpha of the mixture; the base model leaves them empty
     virtual void category_parameters(std::vector<double>&, std::vector<double>&, double&) const {}
+    // what infer_family_likelihoods tests before it goes to the device: false is +inf (and a reject of the monitor)
+    virtual bool host_accepts() const { return _p_lambda->is_valid(); }
+    int _search_batch = 1;
+    // the points staged since batch_begin: flat [point][..]; accepted[point]: host_accepts at that moment
+    std::vector<double> _staged_lambdas, _staged_mus, _staged_multipliers, _staged_probs, _staged_alpha;
+    std::vector<char> _staged_accepted;
 public:
     // compute_viterbi_sum (gene_family_reconstructor.cpp:361) for every family x node of `order` under the model's
     // plain lambda: [family][order index], NaN where the reference returns an invalid branch_probability
@@ -595,6 +617,7 @@ public:
     double get_alpha() const { return _alpha; }
     std::vector<double> get_lambda_multipliers() const { return _lambda_multipliers; }
     bool can_infer() const;                                          // gamma_core.cpp:123
+    bool host_accepts() const override { return can_infer(); }
     void category_parameters(std::vector<double>& multipliers, std::vector<double>& probs, double& alpha) const override {
         multipliers = _lambda_multipliers; probs = _gamma_cat_probs; alpha = _alpha;
     }
@@ -700,6 +723,12 @@ public:
     virtual ~optimizer_scorer() {}
     virtual std::vector<double> initial_guesses() = 0;
     virtual double calculate_score(const double* values) = 0;
+    // The scores of n_points vectors of n_values each (values[point][value]) -> out[point].  The default scores them one by one;
+    // a scorer whose model can score several vectors in one device call (cafe_score_batch) may override it.  What it leaves in
+    // the model is unspecified: optimizer::optimize prepares the point it consumes again.
+    virtual void calculate_scores(const double* values, int n_points, int n_values, double* out) {
+        for (int i = 0; i < n_points; ++i) out[i] = calculate_score(values + (size_t)i * n_values);
+    }
 };
 // empirical Poisson prior: -lnL of the leaf sizes shifted by one (src/poisson.cpp:38-77)
 class poisson_scorer : public optimizer_scorer {
@@ -722,6 +751,13 @@ public:
     inference_optimizer_scorer(lambda* l, model* m, root_equilibrium_distribution* d, const std::map<int, int>& rootdist)
         : _p_lambda(l), _p_model(m), _p_distribution(d), _rootdist_map(rootdist) {}
     double calculate_score(const double* values) override;           // NaN -> +inf (optimizer_scorer.cpp:30)
+    // one device call where the model can (model::batch_begin) and this scorer's vector is all a point needs (batchable):
+    // every vector goes through prepare_calculation, the model stages itself; else the loop.  Either way the model's monitor is
+    // left as it was: what the search consumes is counted when it is consumed (consumed_cached, or calculate_score for a reject)
+    void calculate_scores(const double* values, int n_points, int n_values, double* out) override;
+    virtual bool batchable() const { return true; }
+    // optimizer::batch consumed a vector whose finite score it already had: prepare_calculation and report_precalculation ran
+    void consumed_cached() { _p_model->note_attempt(); }
     virtual void finalize(double* result) = 0;
     bool quiet = true;
 };
@@ -746,6 +782,7 @@ public:
     void prepare_calculation(const double* values) override;
     void report_precalculation() override;
     void finalize(double* results) override;
+    bool batchable() const override { return false; }                // one error table per point: a batch shares one
 };
 class gamma_optimizer : public inference_optimizer_scorer {
     hip_gamma_model* _p_gamma_model;
@@ -783,6 +820,7 @@ public:
     void prepare_calculation(const double* values) override { _inner->prepare_calculation(values); apply(values); }
     void report_precalculation() override;
     void finalize(double* results) override { _inner->finalize(results); apply(results); }
+    bool batchable() const override { return _inner->batchable(); }
 };
 
 // ---------------------------------------------------------------- inputs (src/io.cpp, src/user_data.cpp)
@@ -854,7 +892,9 @@ struct optimizer_result {
     std::vector<double> values;
     double score = 0;
     int num_iterations = 0;
-    int num_scorer_calls = 0;
+    int num_scorer_calls = 0;                    // points the search consumed (and the draws for a start)
+    int num_batches = 0;                         // optimizer::batch > 1: calculate_scores calls
+    int num_points_scored = 0;                   // ... and the points they and the re-scored rejects evaluated
 };
 // One Nelder-Mead search as a state machine (the moves and stop rules of optimizer::optimize, which drives one of these):
 // trial() is the point whose score is needed next, feed() takes it.  A caller with many independent searches can gather
@@ -877,6 +917,13 @@ public:
     double best_score() const { return _simplex[0].f; }
     int iterations() const { return _it; }
     int calls() const { return _calls; }
+    int shrinks() const { return _shrinks; }
+    // The points, other than trial(), whose score the search may ask for before it next sorts the simplex, in the order it
+    // would ask: in the first simplex the remaining vertices (built with the unwidened delta: a vertex that follows an infinite
+    // one is widened, and then is not the one listed here); before the reflected point's score the expansion, the outside and
+    // the inside contraction; in a shrink the remaining shrunk vertices; otherwise none.  Each is computed by the expression
+    // feed() uses, so that it has the bits of the later trial.
+    void lookahead(std::vector<std::vector<double>>& points) const;
 private:
     enum phase { INIT, REFLECT, EXPAND, CONTRACT_IN, CONTRACT_OUT, SHRINK, DONE };
     nm_settings _s;
@@ -888,7 +935,7 @@ private:
     static constexpr int kTrialReflected = -1, kTrialOther = -2;
     int _trial = 0;                              // the vertex whose point is the trial, or one of the two above
     phase _phase = INIT;
-    int _i = 0, _it = 0, _calls = 0;
+    int _i = 0, _it = 0, _calls = 0, _shrinks = 0;
     double _fr = 0;
     void begin_iteration();
     void end_iteration();
@@ -905,8 +952,19 @@ public:
     int similarity_window = 12;                 // OPTIMIZER_SIMILARITY_CUTOFF_SIZE, 0 = off
     double similarity_precision = 1e-3;         // OPTIMIZER_LOW_PRECISION
     std::vector<double> start;                  // not empty: the search starts here (no draws), e.g. from an earlier optimum
-    std::vector<double> get_initial_guesses(int& calls);          // <= 100 retries while +inf (optimizer.cpp:345)
-    optimizer_result optimize();
+    // > 1: the same search, but a point whose score is not known yet goes to the scorer together with the points the search may
+    // ask for next (nm_search::lookahead), at most `batch` in one calculate_scores call, and every score is kept for the rest of
+    // this optimize() call under the exact bits of its vector.  The trajectory, the result and what the scorer prints are the
+    // sequential search's; only the number of dependent scorer round trips falls (optimizer_result::num_batches).
+    int batch = 1;
+    typedef std::vector<std::pair<std::vector<double>, double>> scored_points;
+    // <= 100 retries while +inf (optimizer.cpp:345); drawn: every (draw, score) it made, in order
+    std::vector<double> get_initial_guesses(int& calls, scored_points* drawn = nullptr);
+    // fed (batch > 1 only): called with every (point, score) as the search is fed it
+    typedef std::function<void(const std::vector<double>&, double)> feed_observer;
+    optimizer_result optimize(const feed_observer& fed = nullptr);
+private:
+    optimizer_result optimize_batched(const feed_observer& fed);
 };
 
 // ---------------------------------------------------------------- lambda per family (-b; src/execute.cpp:104-128)

@@ -92,6 +92,7 @@ static void apply_death_rates(cafe_ctx* ctx, const std::vector<double>& mus, int
 }
 
 void hip_model_base::ensure_context(int max_categories) {
+    max_categories *= _search_batch;                            // room for a batch of that many points (set_search_batch)
     const int sig = _p_lambda->count() * 2 + (dynamic_cast<const multiple_lambda*>(_p_lambda) ? 1 : 0);
     if (_ctx && max_categories <= _ctx_categories && sig == _ctx_lambda_sig) { apply_death_rates(_ctx, _death_rates, _p_lambda->count(), _root_rule); return; }
     _ctx_lambda_sig = sig;
@@ -122,6 +123,59 @@ void hip_model_base::ensure_scorer(int max_categories) {
                           _p_error_model ? (int)_p_error_model->n_deviations() : 0, _device, &_devices, nullptr, &_sharded);
     _sharded_categories = max_categories;
     apply_to_shards();
+}
+
+// ---- several parameter vectors in one cafe_score_batch call (model::batch_begin): one device, at most _search_batch points
+bool hip_model_base::batch_begin(int n_points) {
+    if (n_points < 2 || n_points > _search_batch || _devices.size() > 1 || std::getenv("CAFE_FORCE_SHARDED")) return false;
+    _staged_lambdas.clear(); _staged_mus.clear(); _staged_multipliers.clear(); _staged_probs.clear(); _staged_alpha.clear();
+    _staged_accepted.clear();
+    return true;
+}
+void hip_model_base::batch_stage() {
+    std::vector<double> mult, probs;
+    double alpha = 0;
+    category_parameters(mult, probs, alpha);
+    const std::vector<double> lam = _p_lambda->values();
+    if (!_death_rates.empty() && _death_rates.size() != lam.size()) throw std::runtime_error("hip model: one death rate per lambda is required");
+    _staged_accepted.push_back(host_accepts() ? 1 : 0);
+    _staged_lambdas.insert(_staged_lambdas.end(), lam.begin(), lam.end());
+    _staged_mus.insert(_staged_mus.end(), _death_rates.begin(), _death_rates.end());
+    _staged_multipliers.insert(_staged_multipliers.end(), mult.begin(), mult.end());
+    _staged_probs.insert(_staged_probs.end(), probs.begin(), probs.end());
+    _staged_alpha.push_back(alpha);
+}
+void hip_model_base::batch_score(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, double* out) {
+    const size_t G = _staged_accepted.size(), L = (size_t)_p_lambda->count(), K = G ? _staged_multipliers.size() / G : 0;
+    const bool gamma = K > 0, two_rate = !_staged_mus.empty();
+    if (_staged_lambdas.size() != G * L || (two_rate && _staged_mus.size() != G * L) || _staged_multipliers.size() != G * K || _staged_probs.size() != G * K)
+        throw std::runtime_error("hip model: the staged points of a batch differ in shape");
+    // the points the model itself accepts, packed; the others are +inf as infer_family_likelihoods returns them
+    std::vector<double> lam, mus, mult, probs, alpha;
+    std::vector<size_t> sent;
+    for (size_t g = 0; g < G; ++g) {
+        out[g] = std::numeric_limits<double>::infinity();
+        if (!_staged_accepted[g]) continue;
+        sent.push_back(g);
+        lam.insert(lam.end(), _staged_lambdas.begin() + g * L, _staged_lambdas.begin() + (g + 1) * L);
+        if (two_rate) mus.insert(mus.end(), _staged_mus.begin() + g * L, _staged_mus.begin() + (g + 1) * L);
+        mult.insert(mult.end(), _staged_multipliers.begin() + g * K, _staged_multipliers.begin() + (g + 1) * K);
+        probs.insert(probs.end(), _staged_probs.begin() + g * K, _staged_probs.begin() + (g + 1) * K);
+        alpha.push_back(_staged_alpha[g]);
+    }
+    if (sent.empty()) return;
+    ensure_context(gamma ? (int)K : 1);                         // (the model's death rates of this moment set: the buffers two rates need exist)
+    std::vector<float> prior_f;
+    std::vector<double> err, unused;
+    gather_call_inputs(prior, rootdist, prior_f, err, unused);
+    cafe_batch_params bp{};
+    bp.n_points = (int32_t)sent.size(); bp.model = gamma ? CAFE_MODEL_GAMMA : CAFE_MODEL_BASE; bp.n_categories = gamma ? (int32_t)K : 1;
+    bp.lambdas = lam.data(); bp.mus = two_rate ? mus.data() : nullptr;
+    if (gamma) { bp.multipliers = mult.data(); bp.cat_probs = probs.data(); bp.alpha = alpha.data(); }
+    bp.prior = prior_f.data(); bp.error_model = err.empty() ? nullptr : err.data();
+    std::vector<double> got(sent.size());
+    if (cafe_score_batch(_ctx, &bp, got.data()) != CAFE_OK) throw std::runtime_error(std::string("cafe_score_batch: ") + cafe_last_error(_ctx));
+    for (size_t i = 0; i < sent.size(); ++i) out[sent[i]] = got[i];
 }
 
 int hip_model_base::score_call(const cafe_params* pr, double* score) {

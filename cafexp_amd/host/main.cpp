@@ -72,6 +72,10 @@ static void usage() {
         "                  supports keeps probability 0.  Writes <Model>_root_distribution.txt (size<TAB>probability) and one line per round in\n"
         "                  <Model>_results.txt to -o OUTDIR (default results); one GPU, not with -b\n"
         "                  [--rootdist-probs FILE]   the root prior from such a file of probabilities (instead of -p / -f)\n"
+        "  --search-batch G: look-ahead Nelder-Mead -- a point whose score is not known goes to the device with the points the search may ask\n"
+        "                  for next, G in one call (cafe_score_batch); same trajectory, files and result, fewer dependent calls.  2 <= G,\n"
+        "                  G x K <= 32; one GPU, not with -b or --simulate.  Pays at small matrix orders only (a batch of 4 costs 1.1 to 1.5\n"
+        "                  calls at order 141, 3.5 at order 751)\n"
         "  --gpus N: the scorer calls shard the families over devices 0..N-1 (one host thread per GPU, one RCCL all-reduce per call)\n"
         "lambda per family (the reference's -b): cafexp_hip -t TREE -i FAMILIES -b [-y LAMBDA_TREE] [-e ERRMODEL] [-p [L]] [-z] [-s SEED] [-I MAXITER]\n"
         "                  [--workspace BYTES] [-o OUTDIR]   writes OUTDIR (default results)/Base_lambda_per_family.txt, one line per family\n"
@@ -222,6 +226,8 @@ int main(int argc, char** argv) {
     std::string rootdist_probs;                                  // --rootdist-probs FILE
     unsigned seed = 0;
     bool have_seed = false;
+    int search_batch = 1;                                        // --search-batch G: look-ahead search, G points per device call
+    bool search_batch_given = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> std::string { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
@@ -276,7 +282,18 @@ int main(int argc, char** argv) {
         else if (a == "--simulate") { std::string v = optional(); simulate_n = v.empty() ? 0 : std::stoi(v); }
         else if (a == "--simulate-device") simulate_on_device = true;
         else if (a == "--workspace") sim_workspace = std::stoull(next());
+        else if (a == "--search-batch") { search_batch = std::stoi(next()); search_batch_given = true; }
         else { usage(); return 2; }
+    }
+    if (search_batch_given) {                                    // refused before anything is read or written
+        const char* why = nullptr;
+        const int K = (fixed_alpha > 0 || k > 1) ? std::max(1, k) : 1;
+        if (search_batch < 2) why = "--search-batch: G must be at least 2";
+        else if ((long)search_batch * K > 32) why = "--search-batch: G x K (the -k categories) must not exceed 32";
+        else if (n_gpus > 1) why = "--search-batch scores its points in one call on one GPU: --gpus N > 1 is not supported with it";
+        else if (per_family) why = "--search-batch drives the search of one fitted model: -b is not supported with it";
+        else if (simulate_n >= 0) why = "--search-batch drives a search: --simulate is not supported with it";
+        if (why) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
     }
     if (simulate_n >= 0) {
         if (tree_path.empty()) { usage(); return 2; }
@@ -454,6 +471,7 @@ int main(int argc, char** argv) {
             mdl.reset(new hip_base_model(start_lambda, d.p_tree.get(), &d.gene_families, d.max_family_size, d.max_root_family_size, em));
         }
         mdl->set_device(device);
+        mdl->set_search_batch(search_batch);                     // contexts with room for G x K categories
         mdl->set_root_rule(root_sum ? CAFE_ROOT_SUM : CAFE_ROOT_MAX);
         file_probability_distribution* em_prior = nullptr;
         if (estimate_rootdist) {                                 // the starting prior as the floats a call reads, held where the rounds can replace it
@@ -528,8 +546,11 @@ int main(int argc, char** argv) {
         double search_s = 0;
         if (scorer) {                                            // estimate_missing_variables (execute.cpp:78)
             if (!d.p_lambda) owned_lambda.reset(mdl->get_lambda());
+            if (search_batch > 1 && !scorer->batchable())
+                std::cout << "--search-batch: the error model is estimated (one error table per point): the look-ahead points are scored one call each" << std::endl;
             optimizer o(scorer.get());
             o.max_iterations = max_iter;
+            o.batch = search_batch;
             auto t0 = std::chrono::steady_clock::now();
             opt = o.optimize();
             search_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -557,6 +578,7 @@ int main(int argc, char** argv) {
                 if (scorer) {
                     optimizer o(scorer.get());
                     o.max_iterations = max_iter;
+                    o.batch = search_batch;
                     o.start = opt.values;
                     auto t0 = std::chrono::steady_clock::now();
                     optimizer_result again = o.optimize();
@@ -564,6 +586,7 @@ int main(int argc, char** argv) {
                     scorer->finalize(again.values.data());
                     opt.values = again.values; opt.score = again.score;
                     opt.num_iterations += again.num_iterations; opt.num_scorer_calls += again.num_scorer_calls;
+                    opt.num_batches += again.num_batches; opt.num_points_scored += again.num_points_scored;
                     cur = again.score;
                 } else {
                     cur = mdl->infer_family_likelihoods(d.p_prior.get(), d.rootdist, mdl->get_lambda());
@@ -834,6 +857,7 @@ int main(int argc, char** argv) {
         if (em) { std::printf(", "); print_num("epsilon", em->get_epsilons().back(), false); }
         if (scorer) {
             std::printf(", \"search\": {\"iterations\": %d, \"scorer_calls\": %d, \"seconds\": %.3f, ", opt.num_iterations, opt.num_scorer_calls, search_s);
+            if (search_batch > 1) std::printf("\"batches\": %d, \"points_scored\": %d, ", opt.num_batches, opt.num_points_scored);
             print_num("score", opt.score, false);
             std::printf("}");
         }

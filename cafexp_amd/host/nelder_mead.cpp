@@ -7,19 +7,23 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <deque>
+#include <map>
 
 namespace cafe {
 
-std::vector<double> optimizer::get_initial_guesses(int& calls) {
+std::vector<double> optimizer::get_initial_guesses(int& calls, scored_points* drawn) {
     if (!start.empty()) return start;                             // (the search scores it as its first trial)
     std::vector<double> initial = _scorer->initial_guesses();
     double first = _scorer->calculate_score(initial.data());
     ++calls;
+    if (drawn) drawn->push_back({initial, first});
     for (int i = 0; std::isinf(first) && i < 100; ++i) {          // NUM_OPTIMIZER_INITIALIZATION_ATTEMPTS
         initial = _scorer->initial_guesses();
         first = _scorer->calculate_score(initial.data());
         ++calls;
+        if (drawn) drawn->push_back({initial, first});
     }
     if (std::isinf(first)) throw std::runtime_error("Failed to initialize any reasonable values");
     return initial;
@@ -79,6 +83,7 @@ void nm_search::begin_iteration() {
 }
 
 void nm_search::start_shrink() {
+    ++_shrinks;
     _phase = SHRINK;
     _i = 1;
     for (int j = 0; j < _n; ++j) _simplex[1].x[j] = _simplex[0].x[j] + sigma * (_simplex[1].x[j] - _simplex[0].x[j]);
@@ -144,7 +149,110 @@ void nm_search::feed(double f) {
     }
 }
 
-optimizer_result optimizer::optimize() {
+void nm_search::lookahead(std::vector<std::vector<double>>& points) const {
+    points.clear();
+    const int n = _n;
+    std::vector<double> x(n);
+    switch (_phase) {
+    case INIT:
+        for (int i = _i + 1; i <= n; ++i) {
+            const int j = i - 1;
+            x = _x0;
+            x[j] = _x0[j] ? (1 + _s.delta) * _x0[j] : zero_delta;
+            points.push_back(x);
+        }
+        break;
+    case REFLECT: {
+        const vertex& worst = _simplex[n];
+        for (int j = 0; j < n; ++j) x[j] = _mean[j] + chi * (_xr[j] - _mean[j]);
+        points.push_back(x);
+        for (int j = 0; j < n; ++j) x[j] = _mean[j] + psi * (_xr[j] - _mean[j]);
+        points.push_back(x);
+        for (int j = 0; j < n; ++j) x[j] = _mean[j] + psi * (_mean[j] - worst.x[j]);
+        points.push_back(x);
+        break;
+    }
+    case SHRINK:
+        for (int i = _i + 1; i <= n; ++i) {
+            for (int j = 0; j < n; ++j) x[j] = _simplex[0].x[j] + sigma * (_simplex[i].x[j] - _simplex[0].x[j]);
+            points.push_back(x);
+        }
+        break;
+    default:
+        break;
+    }
+}
+
+namespace {
+typedef std::vector<uint64_t> point_key;                             // the exact bits of a parameter vector
+point_key key_of(const std::vector<double>& x) {
+    point_key k(x.size());
+    if (!x.empty()) std::memcpy(k.data(), x.data(), sizeof(double) * x.size());
+    return k;
+}
+}  // namespace
+
+// optimize() with batch > 1.  The score cache lives for this call only: what a vector scores depends on state the caller may
+// change between searches (the prior, between the rounds of a root-distribution estimate).
+optimizer_result optimizer::optimize_batched(const feed_observer& fed) {
+    optimizer_result res;
+    std::map<point_key, double> cache;
+    auto* inference = dynamic_cast<inference_optimizer_scorer*>(_scorer);
+    scored_points drawn;                     // the draws for a start seed the cache
+    const std::vector<double> x0 = get_initial_guesses(res.num_scorer_calls, &drawn);
+    res.num_points_scored += (int)drawn.size();
+    for (const auto& d : drawn) cache[key_of(d.first)] = d.second;
+    nm_settings s;
+    s.max_iterations = max_iterations; s.tolx = tolx; s.tolf = tolf;
+    s.similarity_window = similarity_window; s.similarity_precision = similarity_precision;
+    nm_search search(s, x0);
+    const int n = (int)x0.size();
+    std::vector<std::vector<double>> ahead;
+    std::vector<double> flat, scores;
+    while (!search.done()) {
+        const std::vector<double> x = search.trial();
+        auto hit = cache.find(key_of(x));
+        if (hit == cache.end()) {            // the trial and what may follow it, not yet scored, in the order the search would ask
+            search.lookahead(ahead);
+            std::vector<point_key> keys{key_of(x)};
+            flat.assign(x.begin(), x.end());
+            for (const auto& p : ahead) {
+                if ((int)keys.size() >= batch) break;
+                const point_key k = key_of(p);
+                if (cache.count(k) || std::find(keys.begin(), keys.end(), k) != keys.end()) continue;
+                keys.push_back(k);
+                flat.insert(flat.end(), p.begin(), p.end());
+            }
+            scores.assign(keys.size(), 0.0);
+            _scorer->calculate_scores(flat.data(), (int)keys.size(), n, scores.data());
+            ++res.num_batches;
+            res.num_points_scored += (int)keys.size();
+            for (size_t i = 0; i < keys.size(); ++i) cache[keys[i]] = scores[i];
+            hit = cache.find(keys[0]);
+        }
+        double f = hit->second;
+        if (std::isfinite(f)) {              // the model's state and the scorer's lines are the sequential search's
+            if (inference) {
+                inference->prepare_calculation(x.data());
+                if (!inference->quiet) inference->report_precalculation();
+                inference->consumed_cached();
+            }
+        } else {                             // a reject: scored the ordinary way, so that the model's monitor counts it as it did
+            f = _scorer->calculate_score(x.data());
+            ++res.num_points_scored;
+        }
+        if (fed) fed(x, f);
+        search.feed(f);
+    }
+    res.values = search.best();
+    res.score = search.best_score();
+    res.num_iterations = search.iterations();
+    res.num_scorer_calls += search.calls();
+    return res;
+}
+
+optimizer_result optimizer::optimize(const feed_observer& fed) {
+    if (batch > 1) return optimize_batched(fed);
     optimizer_result res;
     const std::vector<double> x0 = get_initial_guesses(res.num_scorer_calls);
     nm_settings s;

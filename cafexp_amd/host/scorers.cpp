@@ -18,6 +18,21 @@ double inference_optimizer_scorer::calculate_score(const double* values) {
     return score;
 }
 
+void inference_optimizer_scorer::calculate_scores(const double* values, int n_points, int n_values, double* out) {
+    if (!batchable() || !_p_model->batch_begin(n_points)) {
+        const event_monitor before = _p_model->get_monitor();
+        optimizer_scorer::calculate_scores(values, n_points, n_values, out);
+        _p_model->restore_monitor(before);
+        return;
+    }
+    for (int i = 0; i < n_points; ++i) {
+        prepare_calculation(values + (size_t)i * n_values);
+        _p_model->batch_stage();
+    }
+    _p_model->batch_score(_p_distribution, _rootdist_map, out);
+    for (int i = 0; i < n_points; ++i) if (std::isnan(out[i])) out[i] = std::numeric_limits<double>::infinity();      // as calculate_score
+}
+
 // 1/longest_branch times a normal draw centred so that lambda starts near 0.002 (optimizer_scorer.cpp:37-52)
 std::vector<double> lambda_optimizer::initial_guesses() {
     const double distmean = 0.002 / (1.0 / _longest_branch);

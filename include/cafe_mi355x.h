@@ -164,6 +164,37 @@ int       cafe_abi_version(void);
 /* One model::infer_family_likelihoods call: writes -lnL (or +inf / NaN, see conventions). */
 int cafe_score(cafe_ctx* ctx, const cafe_params* params, double* neg_lnl, const cafe_family_out* out);
 
+/* Several parameter vectors in one call: neg_lnl[g] has the bits cafe_score returns for point g's parameters on a context of
+ * the same problem under the same root rule (and, where mus is given, with cafe_set_death_rates(mus[g])), whatever else is in
+ * the batch and in whatever order.  The G points go through the matrix build and the prune as G * K categories of one call and
+ * part only behind the root panel, so a batch costs little more than one call wherever a call is bound by its launch
+ * latencies (small matrix orders), and about G calls where one call already fills the device.  A search that knows which
+ * points it may need next (Nelder-Mead: expansion and contractions beside the reflection, the first simplex, a shrink) saves
+ * dependent round trips with it.
+ *   - a point cafe_score would reject on the host (invalid rates, alpha < 0, a saturated longest branch -- by its own lambdas,
+ *     mus and multipliers) gets +inf and costs the others nothing; a batch of only such points launches no kernel.  A point
+ *     with a category whose root vector sums to zero gets +inf; NaN stays NaN.
+ *   - mus non-NULL on a context without death rates set is CAFE_ERR_STATE (cafe_set_death_rates allocates what two rates need);
+ *     the context's own death rates are never changed.
+ *   - G * K above the problem's max_categories is CAFE_ERR_ARGUMENT; a context with a communicator attached is CAFE_ERR_STATE
+ *     (there is no cafe_sharded form either).  Both are refused before anything is enqueued.  A refused or failed batch, like
+ *     a refused or failed cafe_score, leaves nothing of the call before it to read back (the last-call record is cleared).
+ *   - afterwards cafe_family_results and every other read-back of a last call return CAFE_ERR_STATE (the categories were
+ *     several points'); a following cafe_score is unaffected. */
+typedef struct cafe_batch_params {
+    int32_t n_points;                /* G >= 1 */
+    int32_t model;                   /* CAFE_MODEL_BASE | CAFE_MODEL_GAMMA, one for the batch */
+    int32_t n_categories;            /* K of every point (gamma); G*K <= the context's max_categories */
+    const double* lambdas;           /* [G][n_lambdas] */
+    const double* mus;               /* [G][n_lambdas], or NULL: every point under the context's death rates (or none) */
+    const double* multipliers;       /* [G][K]  gamma */
+    const double* cat_probs;         /* [G][K]  gamma */
+    const double* alpha;             /* [G]     gamma (can_infer's test only) */
+    const float*  prior;             /* [R], shared by the batch */
+    const double* error_model;       /* shared by the batch, or NULL (as cafe_params) */
+} cafe_batch_params;
+int cafe_score_batch(cafe_ctx* ctx, const cafe_batch_params* params, double* neg_lnl /* [G] */);
+
 /* The same work for a family shard, without the final host read-back: device_partial must point
  * to 2 doubles of DEVICE memory and receives {sum_f lnL_f, number of rejected/invalid families}
  * (+inf rejection that the host can decide alone is encoded as partial[1] = 1).  The kernels are
