@@ -22,6 +22,7 @@ CAFE_FLAG_NO_DEDUP = 1
 CAFE_FLAG_NO_SUBTREE_DEDUP = 2
 CAFE_FLAG_MISSING_COUNTS = 4     # counts may hold CAFE_COUNT_MISSING (Problem.missing_counts sets it)
 CAFE_COUNT_MISSING = -1
+CAFE_FAMILY_ABSENT = -1          # cafe_score_per_family_gain: the profile with every count 0, whether or not the table holds it
 CAFE_MODEL_BASE, CAFE_MODEL_GAMMA = 0, 1
 CAFE_ROOT_MAX, CAFE_ROOT_SUM = 0, 1
 
@@ -136,6 +137,7 @@ EXPORTS = [
     "cafe_branch_scores", "cafe_branch_scores_dim", "cafe_weighted_gram", "cafe_debug_gram",
     "cafe_leaf_predictive", "cafe_set_root_rule", "cafe_get_root_rule", "cafe_root_posterior", "cafe_debug_magnitude_tables", "cafe_debug_level_tiles",
     "cafe_branch_change", "cafe_debug_branch_change_band", "cafe_score_batch",
+    "cafe_score_per_family_gain", "cafe_bd_gain_row0",
 ]
 CAFE_CHANGE_NONE = -(1 << 31)   # mode / lo / hi of cafe_branch_change at the root and in a failed family
 CAFE_COMM_ID_BYTES = 128
@@ -214,6 +216,10 @@ def load():
     L.cafe_build_matrices_lm.argtypes = [C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, C.c_int32, _f64p]
     L.cafe_set_death_rates.restype = C.c_int
     L.cafe_set_death_rates.argtypes = [C.c_void_p, _f64p]
+    L.cafe_score_per_family_gain.restype = C.c_int
+    L.cafe_score_per_family_gain.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p, _f64p, C.c_double, _f64p]
+    L.cafe_bd_gain_row0.restype = C.c_int
+    L.cafe_bd_gain_row0.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _f64p, _f64p]
     L.cafe_bd_rates.restype = C.c_int
     L.cafe_bd_rates.argtypes = [C.c_double, C.c_double, C.c_double, _f64p]
     L.cafe_score_gradient.restype = C.c_int
@@ -523,6 +529,22 @@ class Context:
         out = np.empty(len(fam))
         self._check(self._lib.cafe_score_per_family_lm(self._h, C.byref(cp), len(fam), _p(fam, _i64p), _p(lam, _f64p), _p(mu, _f64p),
                                                        _p(out, _f64p)))
+        return out
+
+    def score_per_family_gain(self, pr: Params, family, lambdas, mus, nus, root_absent: float = 0.0) -> np.ndarray:
+        """cafe_score_per_family_gain: lnL of every listed family under ITS OWN birth, death and gain rates (lambdas, mus and
+        nus [n][n_lambdas]; 1-d arrays are one rate per family; mus None: mu = lambda), root sizes 0..R with mass root_absent
+        at 0.  family may hold CAFE_FAMILY_ABSENT, the all-zero profile.  Otherwise score_per_family_lm."""
+        fam = np.ascontiguousarray(family, dtype=np.int64).reshape(-1)
+        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(len(fam), -1)
+        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(len(fam), -1)
+        mu = None if mus is None else np.ascontiguousarray(mus, dtype=np.float64).reshape(len(fam), -1)
+        if lam.shape[1] != self.problem.n_lambdas or nu.shape != lam.shape or (mu is not None and mu.shape != lam.shape):
+            raise ValueError("lambdas, mus and nus must be [%d][%d]" % (len(fam), self.problem.n_lambdas))
+        cp, keep = self._params(pr)
+        out = np.empty(len(fam))
+        self._check(self._lib.cafe_score_per_family_gain(self._h, C.byref(cp), len(fam), _p(fam, _i64p), _p(lam, _f64p),
+                                                         None if mu is None else _p(mu, _f64p), _p(nu, _f64p), float(root_absent), _p(out, _f64p)))
         return out
 
     def marginal_reconstruct(self, pr: Params, level: float = 0.95, alpha: float = 1.0) -> dict:
@@ -1053,6 +1075,16 @@ def bd_rates(lam: float, mu: float, t: float):
     if rc:
         raise CafeError("cafe_bd_rates failed with code %d" % rc)
     return float(out[0]), float(out[1]), bool(out[2])
+
+
+def bd_gain_row0(lam: float, mu: float, nu: float, t: float, n: int):
+    """cafe_bd_gain_row0: (row 0 of the gain model's matrix for the quantized key, columns 0..n-1; r = nu / lambda).  Host
+    code: needs no GPU."""
+    out, r = np.empty(int(n)), np.empty(1)
+    rc = load().cafe_bd_gain_row0(float(lam), float(mu), float(nu), float(t), int(n), _p(out, _f64p), _p(r, _f64p))
+    if rc != 0:
+        raise CafeError("cafe_bd_gain_row0 failed with code %d" % rc)
+    return out, float(r[0])
 
 
 def bd_rates_grad(lam: float, mu: float, t: float):

@@ -1,6 +1,6 @@
 // The per-family branch kernel (family_lambda.hip has the reasoning), one body for both rate models: the kernel, its argument
-// block and its launcher are templates on the slot type.  family_lambda.hip instantiates SlotParam (cafe_score_per_family) and
-// holds the host frame of both entries; family_lambda_lm.hip instantiates SlotParamLM (cafe_score_per_family_lm).  The slot
+// block and its launcher are templates on the slot type.  family_lambda.hip instantiates SlotParam (cafe_score_per_family),
+// family_lambda_lm.hip SlotParamLM (cafe_score_per_family_lm); the host frame of the entries is family_frame.h's.  The slot
 // decides the row step's constants (bd_row.h) through slot_tail / slot_q and nothing else.  Only the ROW-MAJOR recurrence is
 // involved -- row 0 is e_0, the factor is sum_c P[s][c] v[c] of the process itself -- so the exchange identity of the k-major
 // build (bd_matrix.hip) plays no part here.

@@ -603,6 +603,12 @@ public:
     std::vector<double> per_family_scores(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist,
                                           const std::vector<int64_t>& family, const std::vector<double>& lambdas,
                                           const std::vector<double>* mus = nullptr);
+    // lnL (not negated; -inf and NaN as the call gives them) of the listed families under the gain model, each under its own
+    // (lambdas, mus, nus) laid out like lambdas: one cafe_score_per_family_gain call under the model's root rule.  family may
+    // hold kFamilyAbsent, the all-zero profile.
+    std::vector<double> per_family_gain_lnl(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist,
+                                            const std::vector<int64_t>& family, const std::vector<double>& lambdas,
+                                            const std::vector<double>& mus, const std::vector<double>& nus, double root_absent);
 };
 class hip_gamma_model : public hip_model_base {
     std::vector<double> _lambda_multipliers, _gamma_cat_probs;
@@ -994,5 +1000,68 @@ struct per_family_result {
 per_family_result estimate_lambda_per_family(hip_base_model& mdl, user_data& data, int max_iterations, const per_family_mu& family_mu = per_family_mu());
 // what the reference prints when no start has a finite score (execute.cpp:192-206)
 void initialization_failure_advice(std::ostream& ost, const std::vector<gene_family>& families);
+
+// ---------------------------------------------------------------- gene gain rate (--gain / --estimate-gain; gain_model.cpp)
+// One set of rates for the whole table under the birth-death process with a gain rate nu (cafe_score_per_family_gain), fitted to
+// the likelihood CONDITIONAL on a family having been seen in at least one species, under the sum rule.
+constexpr int64_t kFamilyAbsent = -1;           // CAFE_FAMILY_ABSENT
+struct gain_options {
+    bool estimate_nu = false;                    // --estimate-gain; else nu = fixed_nu (--gain NU)
+    double fixed_nu = 0;
+    double root_absent = 0;                      // --root-absent
+    bool conditional = true;                     // false: --gain-unconditional
+    bool estimate_mu = false;                    // --estimate-mu: mus searched, start mu = lambda
+    std::vector<double> fixed_lambdas, fixed_mus;       // -l / -m and --mu (empty: searched / mu = lambda)
+    int max_iterations = 300;
+};
+// every distinct family once (its first index in the table) with its multiplicity, then kFamilyAbsent with weight 0
+struct gain_table {
+    std::vector<int64_t> family;
+    std::vector<double> weight;
+    double n_families = 0;
+};
+gain_table gain_distinct_families(const std::vector<gene_family>& families);
+// The search vector: [lambdas (unless fixed)..., mus (if searched)..., nu (if with_nu)]
+struct gain_layout {
+    int L = 1;
+    bool lambdas_free = true, mus_free = false, nu_free = false;
+    std::vector<double> fixed_lambdas, fixed_mus;
+    double fixed_nu = 0;
+    int width() const { return (lambdas_free ? L : 0) + (mus_free ? L : 0) + (nu_free ? 1 : 0); }
+    // the rates of point x; false when a rate is out of range (lambda or mu negative, one lambda not positive, nu negative, NaN)
+    bool unpack(const double* x, std::vector<double>& lambdas, std::vector<double>& mus, double& nu) const;
+    std::vector<double> pack(const std::vector<double>& lambdas, const std::vector<double>& mus, double nu) const;
+};
+// -sum_f w_f lnL_f (+ F log(1 - exp(lnL_absent)) if conditional); lnl: one per entry of the table, the absent profile last.
+// +inf when a weighted family is impossible, a value is NaN, or (conditional) the model never shows a family (lnL_absent >= 0).
+double gain_objective(const std::vector<double>& lnl, const gain_table& table, bool conditional);
+// lnL of every entry of the table under shared (lambdas, mus, nu): the device call, or a mock
+typedef std::function<std::vector<double>(const std::vector<double>& lambdas, const std::vector<double>& mus, double nu)> gain_scorer;
+struct gain_fit {
+    std::vector<double> lambdas, mus;
+    double nu = 0, neg_lnl = 0, p_absent = 0;
+    std::vector<double> lnl;                     // per entry of the table at the optimum
+    std::vector<double> start;                   // the search vector the search began at (empty: nothing was searched)
+    int calls = 0;
+};
+struct gain_result {
+    gain_fit without, with;                      // the nu = 0 fit, and the fit it was extended to
+    double lr_statistic = 0;                     // 2 (neg_lnl(without) - neg_lnl(with))
+};
+// The nested search: first without nu (nothing to search: one evaluation), then with nu -- searched from nu = lambda / 10 or held
+// at fixed_nu -- from that optimum.  A gain fit that ends above the nu = 0 fit is replaced by it.  draw_lambdas: a start for the
+// lambdas of the first search.
+gain_result fit_gain_model(const gain_scorer& score, const gain_table& table, int n_lambdas, const gain_options& opt,
+                           const std::function<std::vector<double>()>& draw_lambdas);
+// Why the gain options cannot be combined with what else was asked for, or nullptr
+struct gain_request {
+    bool gain = false, estimate_gain = false, root_absent_given = false, unconditional = false;
+    double nu = 0, root_absent = 0;
+    bool gamma = false, per_family = false, gpus = false, simulate = false, pvalues = false, reconstruct = false, marginal = false, histories = false,
+         standard_errors = false, events = false, rate_shift = false, leaf_predictive = false, branch_change = false, rootdist_em = false,
+         search_batch = false, estimate_error = false;
+};
+const char* gain_refusal(const gain_request& r);
+void write_gain_results(std::ostream& ost, const gain_result& res, const gain_options& opt, const gain_table& table);
 
 }  // namespace cafe

@@ -260,6 +260,23 @@ std::vector<double> hip_base_model::per_family_scores(root_equilibrium_distribut
     return out;
 }
 
+std::vector<double> hip_base_model::per_family_gain_lnl(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist,
+                                                        const std::vector<int64_t>& family, const std::vector<double>& lambdas,
+                                                        const std::vector<double>& mus, const std::vector<double>& nus, double root_absent) {
+    ensure_context(1);
+    std::vector<float> prior_f;
+    std::vector<double> err, unused;
+    gather_call_inputs(prior, rootdist, prior_f, err, unused);
+    cafe_params pr{};
+    pr.model = CAFE_MODEL_BASE; pr.n_categories = 1; pr.prior = prior_f.data();
+    pr.error_model = err.empty() ? nullptr : err.data();
+    if (mus.size() != lambdas.size() || nus.size() != lambdas.size()) throw std::runtime_error("per_family_gain_lnl: one mu and one nu per lambda are required");
+    std::vector<double> out(family.size());
+    if (cafe_score_per_family_gain(_ctx, &pr, (int64_t)family.size(), family.data(), lambdas.data(), mus.data(), nus.data(), root_absent, out.data()) != CAFE_OK)
+        throw std::runtime_error(std::string("cafe_score_per_family_gain: ") + cafe_last_error(_ctx));
+    return out;
+}
+
 root_posterior_result hip_model_base::root_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist) {
     std::vector<double> mult, probs;
     double alpha = 0;

@@ -14,6 +14,8 @@
 #include <sstream>
 
 #include "cafe_host.h"
+
+#include <iomanip>
 #include "../../include/cafe_mi355x.h"
 
 using namespace cafe;
@@ -81,6 +83,14 @@ static void usage() {
         "                  [--workspace BYTES] [-o OUTDIR]   writes OUTDIR (default results)/Base_lambda_per_family.txt, one line per family\n"
         "                  [--family-mu M1[,M2,..] | --family-mu estimate]   separate death rates per family (only with -b): fixed at the given\n"
         "                  rates, one per lambda, or searched with each family's lambdas (start mu = lambda); also writes Base_mu_per_family.txt\n"
+        "gene gain rate: cafexp_hip -t TREE -i FAMILIES (--gain NU | --estimate-gain) [--root-absent P0] [--gain-unconditional] [-l LAMBDA | -m L1,L2,..]\n"
+        "                  [-y LAMBDA_TREE] [--mu M1,.. | --estimate-mu] [-e ERRMODEL] [-p [L]] [-f ROOTDIST] [--missing TOKENS] [--mask-cells FILE] [-z] [-o OUTDIR]\n"
+        "                  birth-death with immigration (n -> n+1 at rate n lambda + NU): a family absent in an ancestor can appear below it.  One set\n"
+        "                  of rates for the table, fitted under the sum rule to the likelihood conditional on a family being seen in at least one\n"
+        "                  species (--gain-unconditional: without that correction); the root is absent with probability P0 (default 0).  First the fit\n"
+        "                  without NU, then with it from that optimum.  Writes OUTDIR/Gain_results.txt and Gain_family_likelihoods.txt.  -z keeps the\n"
+        "                  families of one clade only, which this model is about.  Base model, one GPU; not with -k / -a, -b, --gpus, --simulate,\n"
+        "                  --pvalues, a reconstruction or posterior report, or --search-batch\n"
         "simulation (the reference's -s; -s here is the SEED): cafexp_hip -t TREE (-l LAMBDA | -m L1,L2,.. -y LAMBDA_TREE) --simulate [N]\n"
         "                  [-k K] [-a ALPHA] [-e ERRMODEL] [-f ROOTDIST] [-s SEED] [-o OUTDIR] [--simulate-device [--workspace BYTES]] [-d DEVICE]\n"
         "  writes OUTDIR (default results)/simulation.txt and simulation_truth.txt; N families (root sizes 0..99), or the\n"
@@ -226,6 +236,7 @@ int main(int argc, char** argv) {
     std::string rootdist_probs;                                  // --rootdist-probs FILE
     unsigned seed = 0;
     bool have_seed = false;
+    gain_request gain;                                           // --gain NU, --estimate-gain, --root-absent P0, --gain-unconditional
     int search_batch = 1;                                        // --search-batch G: look-ahead search, G points per device call
     bool search_batch_given = false;
     for (int i = 1; i < argc; ++i) {
@@ -283,8 +294,21 @@ int main(int argc, char** argv) {
         else if (a == "--simulate-device") simulate_on_device = true;
         else if (a == "--workspace") sim_workspace = std::stoull(next());
         else if (a == "--search-batch") { search_batch = std::stoi(next()); search_batch_given = true; }
+        else if (a == "--gain") { gain.gain = true; gain.nu = std::stod(next()); }
+        else if (a == "--estimate-gain") gain.estimate_gain = true;
+        else if (a == "--root-absent") { gain.root_absent_given = true; gain.root_absent = std::stod(next()); }
+        else if (a == "--gain-unconditional") gain.unconditional = true;
         else { usage(); return 2; }
     }
+    {                                                            // the gain model: refused before anything is read or written
+        gain.gamma = k > 1 || alpha_given; gain.per_family = per_family; gain.gpus = gpus_given; gain.simulate = simulate_n >= 0;
+        gain.pvalues = pvalue_sims > 0; gain.reconstruct = do_reconstruct; gain.marginal = do_marginal; gain.histories = do_histories;
+        gain.standard_errors = do_standard_errors; gain.events = do_events; gain.rate_shift = do_rate_shift; gain.leaf_predictive = do_leaf_predictive;
+        gain.branch_change = do_branch_change; gain.rootdist_em = estimate_rootdist; gain.search_batch = search_batch_given;
+        gain.estimate_error = use_err && err_path.empty();
+        if (const char* why = gain_refusal(gain)) { std::fprintf(stderr, "cafexp_hip: %s\n", why); return 1; }
+    }
+    const bool gain_run = gain.gain || gain.estimate_gain;
     if (search_batch_given) {                                    // refused before anything is read or written
         const char* why = nullptr;
         const int K = (fixed_alpha > 0 || k > 1) ? std::max(1, k) : 1;
@@ -494,6 +518,68 @@ int main(int argc, char** argv) {
             }
             if (mus.size() != n_lambdas) throw std::runtime_error("--mu needs one death rate per lambda (" + std::to_string(n_lambdas) + ")");
             mdl->set_death_rates(mus);
+        }
+        if (gain_run) {                                          // gain_model.cpp: the table's rates under a gene gain rate
+            hip_base_model* base = static_cast<hip_base_model*>(mdl.get());      // -k / -a were refused above
+            base->set_workspace_limit(sim_workspace);
+            base->set_root_rule(CAFE_ROOT_SUM);                  // the absent profile's value is a probability under the sum rule only
+            base->initialize_lambda(d.p_lambda_tree.get());
+            std::unique_ptr<lambda> shape(base->get_lambda());
+            const int L = shape->count();
+            gain_options go;
+            go.estimate_nu = gain.estimate_gain; go.fixed_nu = gain.nu; go.root_absent = gain.root_absent; go.conditional = !gain.unconditional;
+            go.estimate_mu = estimate_mu; go.max_iterations = max_iter;
+            if (fixed_lambda > 0) go.fixed_lambdas.assign(1, fixed_lambda);
+            if (!multi.empty()) go.fixed_lambdas = parse_rates(multi);
+            if (!mu_list.empty()) go.fixed_mus = parse_rates(mu_list);
+            const gain_table table = gain_distinct_families(d.gene_families);
+            const std::set<double> lengths = d.p_tree->get_branch_lengths();
+            lambda_optimizer starts(shape.get(), base, d.p_prior.get(), *std::max_element(lengths.begin(), lengths.end()), d.rootdist);
+            const gain_scorer score = [&](const std::vector<double>& lambdas, const std::vector<double>& mus, double nu) {
+                const size_t n = table.family.size();
+                std::vector<double> lam, mu, nus(n * L, nu);
+                for (size_t i = 0; i < n; ++i) { lam.insert(lam.end(), lambdas.begin(), lambdas.end()); mu.insert(mu.end(), mus.begin(), mus.end()); }
+                return base->per_family_gain_lnl(d.p_prior.get(), d.rootdist, table.family, lam, mu, nus, go.root_absent);
+            };
+            const auto t0 = std::chrono::steady_clock::now();
+            const gain_result res = fit_gain_model(score, table, L, go, [&] { return starts.initial_guesses(); });
+            const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            base->set_lambda(nullptr);                           // `shape` goes with this scope
+            if (out_dir.empty()) out_dir = "results";
+            if (::mkdir(out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("Failed to create directory " + out_dir);
+            {
+                std::ofstream f(out_dir + "/Gain_results.txt");
+                write_gain_results(f, res, go, table);
+                if (!f) throw std::runtime_error("Failed to write " + out_dir + "/Gain_results.txt");
+                std::map<std::string, size_t> entry_of;          // the table's distinct entry of every family, by its counts
+                std::ofstream g(out_dir + "/Gain_family_likelihoods.txt");
+                g << "#FamilyID\tLikelihood of Family (lnL)\n" << std::setprecision(17);
+                for (size_t i = 0, e = 0; i < d.gene_families.size(); ++i) {
+                    std::string key;
+                    for (const std::string& sp : d.gene_families[i].get_species()) key += sp + ':' + std::to_string(d.gene_families[i].get_species_size(sp)) + ',';
+                    const auto it = entry_of.emplace(key, e);
+                    if (it.second) ++e;
+                    g << d.gene_families[i].id() << '\t' << res.with.lnl[it.first->second] << "\n";
+                }
+                g << "(absent)\t" << res.with.lnl.back() << "\n";
+                if (!g) throw std::runtime_error("Failed to write " + out_dir + "/Gain_family_likelihoods.txt");
+            }
+            auto list = [](const char* name, const std::vector<double>& v) {
+                std::printf("\"%s\": [", name);
+                for (size_t i = 0; i < v.size(); ++i) std::printf("%s%.17g", i ? ", " : "", v[i]);
+                std::printf("], ");
+            };
+            std::printf("{\"model\": \"Gain\", \"root_rule\": \"sum\", \"conditional\": %s, \"families\": %zu, \"distinct_families\": %zu, ",
+                        go.conditional ? "true" : "false", d.gene_families.size(), table.family.size() - 1);
+            std::printf("\"neg_lnl\": %.17g, ", res.with.neg_lnl);
+            list("lambda", res.with.lambdas); list("mu", res.with.mus);
+            std::printf("\"nu\": %.17g, \"root_absent\": %.17g, \"p_absent\": %.17g, \"neg_lnl_without_gain\": %.17g, ", res.with.nu, go.root_absent, res.with.p_absent,
+                        res.without.neg_lnl);
+            list("lambda_without_gain", res.without.lambdas); list("mu_without_gain", res.without.mus);
+            list("start_without_gain", res.without.start); list("start", res.with.start);
+            std::printf("\"lr_statistic\": %.17g, \"calls\": %d, \"max_family_size\": %d, \"max_root_family_size\": %d, \"seconds\": %.3f}\n", res.lr_statistic,
+                        res.without.calls + res.with.calls, d.max_family_size, d.max_root_family_size, seconds);
+            return 0;
         }
         if (per_family) {                                        // estimator::estimate_lambda_per_family (execute.cpp:104-128, :136-141)
             hip_base_model* base = static_cast<hip_base_model*>(mdl.get());      // -k / -a were refused above

@@ -345,6 +345,29 @@ int cafe_score_per_family(cafe_ctx* ctx, const cafe_params* params, int64_t n, c
 int cafe_score_per_family_lm(cafe_ctx* ctx, const cafe_params* params, int64_t n, const int64_t* family,
                              const double* lambdas, const double* mus, double* family_lnl);
 
+/* The per-family path under a gene GAIN rate: n -> n+1 at rate n lambdas + nus, n -> n-1 at rate n mus (the linear birth-death
+ * process with immigration; size 0 is no longer absorbing, so a family absent in an ancestor can appear below it).  Entry i
+ * scores family[i] under (lambdas[i], mus[i], nus[i]), each [n_lambdas]; mus == NULL means mu = lambda.  The single-lineage law
+ * and its alpha and beta are cafe_bd_rates'; row s of a branch's matrix is row s-1 convolved with that law as before, and row 0
+ * is the law of the immigrants' descendants, cafe_bd_gain_row0.  The root's size runs over 0..R: size 0 has prior mass
+ * root_absent, size j >= 1 has (1 - root_absent) * prior[j-1], under the context's root rule (cafe_set_root_rule).
+ * family[i] == CAFE_FAMILY_ABSENT scores the profile with every species' count 0 under entry i's rates, whether or not the
+ * table holds such a family (with an error model: the taps of an observed 0) -- what a likelihood conditional on the family
+ * having been seen needs.  Everything else is cafe_score_per_family_lm's contract: base model only, CAFE_ERR_STATE with a
+ * communicator attached, the context's death rates are not read, an invalid entry gives -inf and a NaN lambda that passes the
+ * rule gives NaN, a rate * 1e9 beyond a long saturates the branch.  A nu that is negative or NaN, or root_absent outside
+ * [0, 1], is CAFE_ERR_ARGUMENT.  With nus all 0 and root_absent = 0 every value is bit for bit cafe_score_per_family_lm's
+ * (cafe_score_per_family's with mus == lambdas or NULL). */
+#define CAFE_FAMILY_ABSENT (-1)   /* the profile with every species' count 0, whether or not the table holds it */
+int cafe_score_per_family_gain(cafe_ctx* ctx, const cafe_params* params, int64_t n, const int64_t* family,
+                               const double* lambdas, const double* mus, const double* nus, double root_absent, double* family_lnl);
+/* Row 0 of the gain model's matrix for the key (lambda, mu, nu, t): the three rates quantized like a lambda, t like a branch
+ * length, alpha and beta cafe_bd_rates'.  out[k] = C(r+k-1, k) (1-beta)^r beta^k, k < n, r = nu / lambda (written to out_r[0]
+ * unless out_r is NULL; +inf for lambda = 0 < nu).  nu = 0 gives exactly e_0.  lambda = 0 < nu is the limit r -> inf, beta -> 0:
+ * the Poisson law with mean nu (1 - exp(-mu t)) / mu (nu t for mu = 0).  The kernel evaluates the same formula.  Pure host code,
+ * no device needed.  CAFE_ERR_ARGUMENT for a negative or NaN argument or a rate * 1e9 beyond a long. */
+int cafe_bd_gain_row0(double lambda, double mu, double nu, double t, int32_t n, double* out, double out_r[1]);
+
 /* Separate birth and death rates.  The reference fits the critical process lambda = mu only; with death rates set a context
  * scores the linear birth-death process with birth rate lambdas[i] and death rate mus[i] per lineage on the branches of
  * lambda index i.  mus[n_lambdas] is copied; NULL restores lambda = mu (and the kernels that run then).  While death rates
