@@ -137,7 +137,7 @@ EXPORTS = [
     "cafe_branch_scores", "cafe_branch_scores_dim", "cafe_weighted_gram", "cafe_debug_gram",
     "cafe_leaf_predictive", "cafe_set_root_rule", "cafe_get_root_rule", "cafe_root_posterior", "cafe_debug_magnitude_tables", "cafe_debug_level_tiles",
     "cafe_branch_change", "cafe_debug_branch_change_band", "cafe_score_batch",
-    "cafe_score_per_family_gain", "cafe_bd_gain_row0",
+    "cafe_score_per_family_gain", "cafe_bd_gain_row0", "cafe_debug_narrowed_extents",
 ]
 CAFE_CHANGE_NONE = -(1 << 31)   # mode / lo / hi of cafe_branch_change at the root and in a failed family
 CAFE_COMM_ID_BYTES = 128
@@ -870,6 +870,18 @@ class Context:
         out = np.zeros((nt.value, nb.value, 2), dtype=np.int32)
         self._check(f(self._h, node, category, _p(out, _i32p), out.size, C.byref(nt), C.byref(nb)))
         return out
+
+    def narrowed_extents(self, node: int, category: int = 0) -> np.ndarray:
+        """Narrowed hulls [tiles][2] of an interior non-root node's panel in the last call: the structural hull of each
+        128-column tile cut back over the rows the magnitude bounds prove to be computed zeros (first > last: the whole tile);
+        the structural hulls themselves under CAFE_NO_NARROW=1 or without bounds (cafe_debug_narrowed_extents)."""
+        f = self._lib.cafe_debug_narrowed_extents
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _i32p, C.c_size_t, C.POINTER(C.c_int32)]
+        out = np.zeros(((self.n_families + 256) // 128 + 2, 2), dtype=np.int32)
+        nt = C.c_int32()
+        self._check(f(self._h, node, category, _p(out, _i32p), out.size, C.byref(nt)))
+        return out[:nt.value]
 
     def leaf_transposes(self):
         """(leaf branches with a transposed copy of their matrix for the assemble passes, whether the last call used them)."""

@@ -27,7 +27,7 @@ void free_device(cafe_ctx* c) {
     for (auto& g : c->graphs) if (g.second.exec) hipGraphExecDestroy(g.second.exec);
     hipFree(c->d_counts); hipFree(c->d_weights); hipFree(c->pool.base); hipFree(c->kpool.base); hipFree(c->kpool.ext); hipFree(c->pool.ext); hipFree(c->d_params); hipFree(c->d_panels);
     hipFree(c->d_ext_nodes); hipFree(c->d_mag_a16); hipFree(c->d_mag_t4); hipFree(c->d_mag_lt); hipFree(c->d_jr); hipFree(c->d_fam_out); hipFree(c->d_fam_lik); hipFree(c->d_cat_out); hipFree(c->d_failed);
-    for (auto* ptrs : {&c->d_colext, &c->d_tileext, &c->d_bound, &c->d_edge_map, &c->d_leaf_cnt}) for (auto ptr : *ptrs) hipFree(ptr);
+    for (auto* ptrs : {&c->d_colext, &c->d_tileext, &c->d_narrow, &c->d_bound, &c->d_edge_map, &c->d_leaf_cnt}) for (auto ptr : *ptrs) hipFree(ptr);
     hipFree(c->d_scratch); hipFree(c->d_result); hipFree(c->d_stamps);
     for (void* h : {(void*)c->h_stage, (void*)c->h_result, (void*)c->h_ext, (void*)c->h_gemm_stage, (void*)c->h_plan_desc}) if (h) hipHostFree(h);
     auto free_desc = [](DescSet& d) { hipFree(d.d_gemm_ops); hipFree(d.d_plan_desc); hipFree(d.d_plan); d = DescSet(); };
@@ -68,6 +68,7 @@ Switches read_switches(cafe_ctx* c) {
     if ((e = std::getenv("CAFE_GEMM_STAMPS_LAUNCH"))) c->stamps_launch = std::atol(e);   // stamps of that K2 launch only
     if ((e = std::getenv("CAFE_PER_FAMILY_BATCH"))) c->pf_max_batch = std::max(0L, std::atol(e));   // cafe_score_per_family: families per batch
     c->no_asm_skip = std::getenv("CAFE_NO_ASM_SKIP") != nullptr;   // the assemble passes write every row
+    c->no_narrow = std::getenv("CAFE_NO_NARROW") != nullptr;       // the hulls stay structural: the magnitude bounds cut no row off them
     if ((e = std::getenv("CAFE_FORCE_TILE")) && std::atoi(e) >= 2 && std::atoi(e) <= 9) c->force_mi = std::atoi(e);   // like cafe_debug_force_tile
     if ((e = std::getenv("CAFE_PLAN_FIXED"))) c->plan_fixed = std::max(0, atoi(e));   // the tile planner's cost of a tile beyond its K loop
     if ((e = std::getenv("CAFE_PLAN_BIAS"))) c->plan_bias = std::min(50, std::max(0, atoi(e)));   // first-dispatched workgroup of a CU, percent
@@ -322,11 +323,12 @@ int alloc_panels(cafe_ctx* c, size_t panel_doubles, const std::vector<int>& ext_
     // rows beyond what the first writer of a panel covers must not hold NaN bit patterns
     HIP_TRY(c, hipMemset(c->d_panels, 0, panel_bytes));
     c->stats.panel_bytes = (int64_t)panel_bytes; c->stats.n_unique_families = c->F_uniq;
-    c->d_colext.assign(c->n_nodes, nullptr); c->d_tileext.assign(c->n_nodes, nullptr);
+    c->d_colext.assign(c->n_nodes, nullptr); c->d_tileext.assign(c->n_nodes, nullptr); c->d_narrow.assign(c->n_nodes, nullptr);
     for (int v : ext_order) {
         const int64_t cols = panel_cols(c, v, c->Fp);
         HIP_TRY(c, hipMalloc(&c->d_colext[v], sizeof(int32_t) * 2 * (size_t)c->Kmax * cols));
         HIP_TRY(c, hipMalloc(&c->d_tileext[v], sizeof(int32_t) * 2 * (size_t)c->Kmax * (cols / kBN)));
+        HIP_TRY(c, hipMalloc(&c->d_narrow[v], sizeof(int32_t) * 2 * (size_t)c->Kmax * (cols / kBN)));
     }
     // magnitude tables and panel bounds (extents.hip).  They come after the panels and are an optimisation: where they do
     // not fit, the call keeps the exact extents.
@@ -347,7 +349,7 @@ int alloc_panels(cafe_ctx* c, size_t panel_doubles, const std::vector<int>& ext_
             ExtNode nd{};
             nd.bound = c->magskip ? c->d_bound[v] : nullptr;
             nd.cols = (int32_t)panel_cols(c, v, c->Fp);
-            nd.colext = c->d_colext[v]; nd.tileext = c->d_tileext[v];
+            nd.colext = c->d_colext[v]; nd.tileext = c->d_tileext[v]; nd.narrow = c->d_narrow[v];
             nd.cnt = c->subtree_dedup ? c->d_leaf_cnt[v] : c->d_counts; nd.cnt_ld = nd.cols;
             for (int u : c->leaves[v]) { nd.leaf_pair[nd.n_leaf] = c->pair_of[u]; nd.leaf_row[nd.n_leaf++] = cnt_row(c, u); }
             for (int u : c->inner[v]) {
@@ -355,6 +357,7 @@ int alloc_panels(cafe_ctx* c, size_t panel_doubles, const std::vector<int>& ext_
                 nd.inner_cols[nd.n_inner] = (int32_t)panel_cols(c, u, c->Fp);
                 nd.inner_map[nd.n_inner] = c->subtree_dedup ? c->d_edge_map[u] : nullptr;    // (nullptr for an identity edge)
                 nd.inner_bound[nd.n_inner] = c->magskip ? c->d_bound[u] : nullptr;
+                nd.inner_narrow[nd.n_inner] = c->d_narrow[u];
                 nd.inner_colext[nd.n_inner++] = c->d_colext[u];
             }
             nodes.push_back(nd);
@@ -408,6 +411,7 @@ int build_descriptors(cafe_ctx* c, const std::vector<int>& lt_of_pair) {
                 jr_used += (size_t)c->Kmax * g.jr_nct * jr_row;
                 c->jr_max_tiles = std::max(c->jr_max_tiles, (int)g.jr_nct);
                 g.bbound = c->magskip ? c->d_bound[op.child] : nullptr;
+                g.bnarrow = c->magskip && c->panel_extents ? c->d_narrow[op.child] : nullptr;
             }
         } else {
             GatherArgs& g = c->h_gather_ops[op.desc];
@@ -426,7 +430,8 @@ int build_descriptors(cafe_ctx* c, const std::vector<int>& lt_of_pair) {
                 g.ld_src[j] = c->factor_ld; g.map[j] = c->d_edge_map[op.src_child[j]];
             }
             // (the root's vector is read whole by the reduction and has no extent record)
-            g.tileext = c->panel_extents && !op.to_root && !c->no_asm_skip ? c->d_tileext[op.parent] : nullptr;
+            // (the narrowed hull: it is the structural one in a call without magnitude tables, and no K range reaches outside it)
+            g.tileext = c->panel_extents && !op.to_root && !c->no_asm_skip ? c->d_narrow[op.parent] : nullptr;
             g.lt_kstride = lt_kstride;
             if (op.leaf_t)
                 for (int l = 0; l < op.n_leaf && l < kMaxLeafPerOp; ++l)

@@ -275,6 +275,8 @@ struct cafe_ctx {
     // and per-128-column-tile intervals outside which the panel is exactly zero
     bool panel_extents = false;
     bool no_asm_skip = false;                             // CAFE_NO_ASM_SKIP: the assemble pass writes every row (diagnostic)
+    bool no_narrow = false;                               // CAFE_NO_NARROW: the magnitude bounds cut no row off the hulls (A/B runs, tests)
+    std::vector<int32_t*> d_narrow;                       // [n_nodes] the narrowed hulls (ExtNode::narrow), beside d_tileext
     cafe::ExtNode* d_ext_nodes = nullptr;
     std::vector<int32_t*> d_colext, d_tileext;            // [n_nodes] (interior non-root nodes only)
     struct ExtLevel { int first, count, max_col_tiles; };

@@ -210,6 +210,22 @@ int cafe_debug_panel_bounds(cafe_ctx* ctx, int32_t node, int32_t category, doubl
     return CAFE_OK;
 }
 
+// The narrowed hulls of a node's panel (node_level_kernel, ExtNode::narrow): out[tile][2]
+int cafe_debug_narrowed_extents(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* out, size_t out_len, int32_t* n_tiles) {
+    if (!ctx || !out) return CAFE_ERR_ARGUMENT;
+    if (const int rc = require_last(ctx, "cafe_debug_narrowed_extents")) return rc;
+    if (node < 0 || node >= ctx->n_nodes || category < 0 || category >= ctx->last.K || !ctx->panel_extents || !ctx->d_narrow[node]) {
+        set_err(ctx, "cafe_debug_narrowed_extents: no extents for this node");
+        return CAFE_ERR_ARGUMENT;
+    }
+    const int nt = (int)(panel_cols(ctx, node, ctx->Fp) / kBN);
+    if (n_tiles) *n_tiles = nt;
+    if (out_len < (size_t)2 * nt) { set_err(ctx, "cafe_debug_narrowed_extents: out too small"); return CAFE_ERR_ARGUMENT; }
+    if (const int rc = wait_last_call(ctx)) return rc;
+    HIP_TRY(ctx, hipMemcpy(out, ctx->d_narrow[node] + (size_t)category * nt * 2, sizeof(int32_t) * 2 * nt, hipMemcpyDeviceToHost));
+    return CAFE_OK;
+}
+
 // The magnitude tables of the last call's matrices (mag_tables_kernel), one slot's, as the kernel wrote them (units of 1/256,
 // kMagNone where every entry is zero): which 0 = a16 [k-steps][16-row blocks], 1 = t4 [k-steps][row steps] (k-major slots),
 // 2 = lt [counts 0 .. M][row steps] (row-major slots).  slot < 0: the slot of the branch above `node` in `category`.

@@ -191,6 +191,9 @@ struct GemmOp {
     int32_t jr_nct, jr_ct_mask;
     // upper bounds of the child panel's magnitudes (node_level_kernel): [category][column tile][row steps], or nullptr
     const int32_t* bbound;
+    // the child panel's narrowed hulls (ExtNode::narrow), laid out like bext: where range_kernel starts to look when it has
+    // magnitude tables, and outside which it takes every bound as "all zero"; nullptr: none
+    const int32_t* bnarrow;
 };
 constexpr int kRangePad = 8;        // blocks a row tile may overhang the matrix's last one (MI - 1): entries past it say "none"
 
@@ -317,6 +320,11 @@ struct ExtNode {
     // an upper bound of log2 of every COMPUTED entry, in 1/256 (kMagNone: all exactly zero); the interior children's likewise
     int32_t* bound;
     const int32_t* inner_bound[kMaxExtChildren];
+    // [category][cols / 128][2]: the tile's hull cut back from both ends over the row steps that the magnitude bounds prove to
+    // hold computed zeros only (node_level_kernel).  Contiguous, inside tileext; equal to it without magnitude tables or
+    // with ExtArgs::narrow off.  The assemble passes write these rows only, and no K range reaches outside them.
+    int32_t* narrow;
+    const int32_t* inner_narrow[kMaxExtChildren];
 };
 struct ExtArgs {
     const ExtNode* nodes;
@@ -334,6 +342,7 @@ struct ExtArgs {
     int32_t n_rsteps, n_ksteps;
     int32_t n_cu;                            // compute units of the device: sizes the tiles a workgroup owns
     int32_t level_tiles;                     // diagnostic (cafe_debug_level_tiles): column tiles per workgroup, 0 = chosen per level
+    int32_t narrow;                          // cut the hulls back by the bounds (ExtNode::narrow); 0: CAFE_NO_NARROW, they stay structural
 };
 // one launch per tree level: the intervals of the level's nodes and, with magnitude tables, the bounds of their panels
 // missing: the counts may hold CAFE_COUNT_MISSING (the kernel's MISSING instantiation: such a leaf narrows no interval and
@@ -350,6 +359,11 @@ constexpr int32_t kMagFloor = -1050 * kMagUnit;      // a panel bound inside the
                                                      // 2048 products, each rounded up in the denormal range, stays under 2^-1063
 constexpr int32_t kMagSlack = 16;                    // added per tree level: (1 + 2^-53)^n of the roundings, the denormal round-ups
 constexpr int32_t kSkipBelow = -1100 * kMagUnit;     // 2^-1100 * 4 products of an MFMA < 2^-1075: rounds away against 0 or >= 2^-1074
+// Narrowed hulls.  A row step whose bound BEFORE the floor lies below kSkipBelow holds computed zeros only: a factor whose
+// log-sum is below it is a sum of products that all round to zero, in any order and any fusion (the argument of the k-step
+// skip), and a product of factors bounded below it rounds to zero.  node_level_kernel cuts such row steps off both ends of a
+// tile's hull into a second interval (ExtNode::narrow).  The bound table keeps its floor over the whole structural hull; its
+// readers -- the level above, range_kernel -- take the bound of a row step outside the narrowed interval as "all zero".
 constexpr int kMaxSteps = 512;                       // k-steps / row steps of the largest matrix order (2048 / 4)
 struct MagArgs {
     MatrixPool kpool, lpool;

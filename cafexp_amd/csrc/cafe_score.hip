@@ -325,7 +325,7 @@ int enqueue_prepass(cafe_ctx* c, const DescSet& ds, const CallMode& m, hipStream
         ExtArgs ea{};
         ea.t4 = mag ? c->d_mag_t4 : nullptr; ea.lt = c->d_mag_lt; ea.n_rsteps = c->n_rsteps; ea.n_ksteps = c->n_ksteps;
         ea.nodes = c->d_ext_nodes;
-        ea.n_cu = c->n_cu; ea.level_tiles = c->force_level_tiles;
+        ea.n_cu = c->n_cu; ea.level_tiles = c->force_level_tiles; ea.narrow = mag && !c->no_narrow;
         ea.leaf_ext = c->pool.ext; ea.leaf_ext_blocks = c->pool.ext_blocks; ea.n_pairs_leaf = c->n_pairs[0];
         ea.kext = c->kpool.ext; ea.kext_blocks = c->kpool.ext_blocks; ea.n_pairs_inner = c->n_pairs[1];
         ea.M = c->M;

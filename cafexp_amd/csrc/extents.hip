@@ -140,18 +140,26 @@ __global__ __launch_bounds__(64 * kRangeWaves) void range_kernel(const RangeArgs
     const bool live = ct < o.jr_nct, mag = a.a16 && o.bbound;
     __shared__ int32_t s_ball[kRangeWaves][kMaxSteps];      // the panel's bound per k-step
     const int32_t* s_b = s_ball[wave];
+    // with magnitude tables the panel's extent is its narrowed hull (ExtNode::narrow): the rows outside it are computed zeros,
+    // their bound counts as "none" whatever floor the table holds, and the assemble passes do not write them
+    const int32_t* pext = mag && o.bnarrow ? o.bnarrow : o.bext;
     if (mag) {
         if (live) {
             const int32_t* B = o.bbound + ((int64_t)cat * o.jr_nct + ct) * a.n_rsteps;
-            for (int i = lane; i < a.n_ksteps; i += 64) s_ball[wave][i] = B[i];
+            int nlo = 0, nhi = a.n_ksteps - 1;
+            if (o.bnarrow) {
+                const int32_t* be = o.bnarrow + ((int64_t)cat * o.jr_nct + ct) * 2;
+                nlo = be[1] >= be[0] ? be[0] / 4 : a.n_ksteps; nhi = be[1] >= be[0] ? be[1] / 4 : -1;
+            }
+            for (int i = lane; i < a.n_ksteps; i += 64) s_ball[wave][i] = (i >= nlo && i <= nhi) ? B[i] : kMagNone;
         }
         __syncthreads();
     }
     if (!live) return;
     const int slot = o.slot[cat];
     int plo = 0, phi = a.k_valid - 1;
-    if (o.bext) {
-        const int32_t* be = o.bext + ((int64_t)cat * o.jr_nct + ct) * 2;
+    if (pext) {
+        const int32_t* be = pext + ((int64_t)cat * o.jr_nct + ct) * 2;
         plo = be[0]; phi = min(be[1], phi);
         if (be[1] < be[0]) { plo = 0; phi = 0; }
     }
@@ -241,7 +249,11 @@ __device__ inline int2 plan_tile_entry(const PlanLaunch& L, const int* s_first, 
             const int32_t* be = o.bext + ((int64_t)cat * nct + ct) * 2;
             if (be[1] >= be[0]) zlo = be[0];
         }
-        if (shi < slo) { lo = zlo; hi = zlo; }             // an all-zero tile still runs one K tile: the panel must receive its zeros
+        // An all-zero tile still runs one K tile: the panel must receive its zeros.  zlo stays the STRUCTURAL first row, not
+        // the narrowed one: the K tile there is fetched and never multiplied (every block's mask is empty), so it may hold rows
+        // that a narrowed assemble pass left as an earlier call wrote them -- finite, the panels are cleared after a call that
+        // returned NaN -- and the entry stays what cafe_debug_plan_check and the tests of the lists recompute.
+        if (shi < slo) { lo = zlo; hi = zlo; }
         hi = min(hi, L.k_valid - 1);
     }
     return make_int2((op << 24) | tl, ((lo / L.kb) << 16) | (hi / L.kb - lo / L.kb + 1));

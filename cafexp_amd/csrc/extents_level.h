@@ -123,11 +123,18 @@ __global__ __launch_bounds__(kLevelThreads, 4) void node_level_kernel(const ExtA
     __shared__ unsigned s_bits[kLevelTiles][kMaxSteps / 8];    // counts 0 .. 2047
     __shared__ int s_n[kLevelTiles], s_klo[kLevelTiles], s_khi[kLevelTiles];
     __shared__ int s_wlo[2 * kLevelTiles], s_whi[2 * kLevelTiles], s_lo[kLevelTiles], s_hi[kLevelTiles], s_rlo[kLevelTiles], s_rhi[kLevelTiles];
-    __shared__ int32_t s_ptop[kLevelPhases][kLevelTiles][64];
+    // One buffer, two lives inside an interior child's turn: first the narrowed interval of each listed child tile, in k-steps
+    // (read while the child's bounds are gathered), then, from the barrier behind that gather on, the partial sums' maxima.
+    // Keeping them apart would put the workgroup over a fifth of a CU's LDS.
+    __shared__ union {
+        int32_t ptop[kLevelPhases][kLevelTiles][64];
+        struct { int lo[kLevelTiles][kBN], hi[kLevelTiles][kBN]; } child;
+    } s_u;
     __shared__ float s_psum[kLevelPhases][kLevelTiles][64];
     __shared__ int32_t s_kext[kMaxExtChildren][2 * kMaxExtBlocks];     // the interior children's matrix extents (this category)
     __shared__ int s_mono[kMaxExtChildren];                // the child's matrix extents do not decrease from block to block
     __shared__ int s_miss[MISSING ? kLevelTiles : 1];      // MISSING: some column of the tile has no count for the leaf at hand
+    __shared__ int s_nlo[kLevelTiles], s_nhi[kLevelTiles];  // first / last row step of a tile that is not proven zero
     if (tid < kMaxExtChildren) s_mono[tid] = 1;
     __syncthreads();
     for (int j = 0; j < nd.n_inner; ++j)
@@ -160,6 +167,10 @@ __global__ __launch_bounds__(kLevelThreads, 4) void node_level_kernel(const ExtA
         int32_t* t = nd.tileext + ((int64_t)k * nct + ct0 + tid) * 2;
         t[0] = lo; t[1] = hi;
         s_lo[tid] = lo; s_hi[tid] = hi;
+        if (!a.t4 || !a.narrow) {                           // no bounds to cut by: the narrowed interval is the hull
+            int32_t* n = nd.narrow + ((int64_t)k * nct + ct0 + tid) * 2;
+            n[0] = lo; n[1] = hi;
+        }
         s_rlo[tid] = hi >= lo ? lo / 4 : nr; s_rhi[tid] = hi >= lo ? min(hi / 4, nr - 1) : -1;
     }
     if (!a.t4) return;                                     // (a kernel argument: uniform)
@@ -213,6 +224,18 @@ __global__ __launch_bounds__(kLevelThreads, 4) void node_level_kernel(const ExtA
             if (t >= kMaxSteps * 4 || !(atomicOr(&s_bits[c][t >> 5], 1u << (t & 31)) & (1u << (t & 31)))) s_list[c][atomicAdd(&s_n[c], 1)] = t;
         }
         __syncthreads();
+        // (a child tile's rows outside its narrowed interval are computed zeros: their bound counts as "none" here, whatever
+        // floor the table holds -- what is cut at one level shortens the sums of the next)
+        if (a.narrow) {
+            const int32_t* cn = nd.inner_narrow[j] + (int64_t)k * (nd.inner_cols[j] / kBN) * 2;
+            for (int i = tid; i < nt * kBN; i += kLevelThreads) {
+                const int c = i / kBN, q = i % kBN;
+                if (q >= s_n[c]) continue;
+                const int lo = cn[2 * s_list[c][q]], hi = cn[2 * s_list[c][q] + 1];
+                s_u.child.lo[c][q] = hi >= lo ? lo / 4 : nk; s_u.child.hi[c][q] = hi >= lo ? hi / 4 : -1;
+            }
+            __syncthreads();
+        }
         // the child's bound per k-step: the maximum over the child tiles the tile's columns map to -- for the k-steps that the
         // matrix blocks of the hulls' rows reach (the union of the rows' ranges below); the others are not looked at
         const int slot = k * a.n_pairs_inner + nd.inner_pair[j];
@@ -235,6 +258,11 @@ __global__ __launch_bounds__(kLevelThreads, 4) void node_level_kernel(const ExtA
                 int32_t v[kListBatch];
 #pragma unroll
                 for (int q = 0; q < kListBatch; ++q) v[q] = cb[(int64_t)s_list[c][min(i0 + q, n - 1)] * nr + ks];
+                if (a.narrow) {
+#pragma unroll
+                    for (int q = 0; q < kListBatch; ++q)
+                        if (ks < s_u.child.lo[c][min(i0 + q, n - 1)] || ks > s_u.child.hi[c][min(i0 + q, n - 1)]) v[q] = kMagNone;
+                }
 #pragma unroll
                 for (int q = 0; q < kListBatch; ++q) m = max(m, v[q]);
             }
@@ -307,21 +335,24 @@ __global__ __launch_bounds__(kLevelThreads, 4) void node_level_kernel(const ExtA
                 }
             }
 #pragma unroll
-            for (int c = 0; c < kLevelTiles; ++c) { s_ptop[wave][c][lane] = top[c]; s_psum[wave][c][lane] = sum[c]; }
+            for (int c = 0; c < kLevelTiles; ++c) { s_u.ptop[wave][c][lane] = top[c]; s_psum[wave][c][lane] = sum[c]; }
             __syncthreads();
             {   // thread -> (tile, row step of the chunk): the partial sums in the order of the waves
                 const int c = wave, rr = r0 + lane;
                 if (c < nt && rr >= s_rlo[c] && rr <= s_rhi[c]) {
                     int32_t T = kMagNone;
 #pragma unroll
-                    for (int w = 0; w < kLevelPhases; ++w) T = max(T, s_ptop[w][c][lane]);
+                    for (int w = 0; w < kLevelPhases; ++w) T = max(T, s_u.ptop[w][c][lane]);
                     int32_t f = kMagNone;
                     if (T != kMagNone) {
                         float S = 0.f;
 #pragma unroll
                         for (int w = 0; w < kLevelPhases; ++w)
-                            if (s_ptop[w][c][lane] != kMagNone) S += s_psum[w][c][lane] * exp2f((float)(s_ptop[w][c][lane] - T) * (1.f / kMagUnit));
+                            if (s_u.ptop[w][c][lane] != kMagNone) S += s_psum[w][c][lane] * exp2f((float)(s_u.ptop[w][c][lane] - T) * (1.f / kMagUnit));
                         f = T + (int32_t)ceilf(log2f(S * (1.f + 0x1p-11f)) * (float)kMagUnit);
+                        // (a factor whose whole sum is below 2^-1100 is a computed zero, whatever its siblings hold: every
+                        // product that feeds it rounds to zero.  "None" makes the row step one that the narrowing may cut.)
+                        if (a.narrow && f < kSkipBelow) f = kMagNone;
                     }
                     s_acc[c][rr] = (f == kMagNone || s_acc[c][rr] == kMagNone) ? kMagNone : s_acc[c][rr] + f;
                 }
@@ -330,6 +361,30 @@ __global__ __launch_bounds__(kLevelThreads, 4) void node_level_kernel(const ExtA
         }
     }
     __syncthreads();
+    if (a.narrow) {
+        // ---- the narrowed interval: the hull cut back from both ends over the row steps whose bound, before the floor, lies
+        // below kSkipBelow (cafe_kernels.h: computed zeros only).  Row steps between two that count are never dropped.
+        // (K2 copies row 0 of a child's panel outside any K range.  A hull that holds row 0 keeps it: a column's interval
+        // reaches row 0 only where every leaf below is 0 or missing, that column's row 0 is exactly 1, and a bound that
+        // dominates it is far above the threshold.  A hull that does not hold row 0 had that row written by the assemble pass
+        // only while it began below row 16; cut back to row 16 or beyond, it now leaves row 0 as it was -- as every hull that
+        // begins there structurally always did.  What stands there is what an earlier call wrote, and without an error model a
+        // column's row 0 is the same in every call: 1 where every leaf below is 0 or missing, else exactly 0, whatever the
+        // rates.  An error model's taps make it non-zero only in a column with a count of 1, whose rows 1 .. 3 are then far
+        // above the threshold in a call without the model: row step 0 is kept and row 0 rewritten.)
+        if (tid < kLevelTiles) { s_nlo[tid] = nr; s_nhi[tid] = -1; }
+        __syncthreads();
+        for (int i = tid; i < nt * nr; i += kLevelThreads) {
+            const int c = i / nr, r = i % nr;
+            if (r >= s_rlo[c] && r <= s_rhi[c] && s_acc[c][r] + kMagSlack >= kSkipBelow) { atomicMin(&s_nlo[c], r); atomicMax(&s_nhi[c], r); }
+        }
+        __syncthreads();
+        if (tid < nt) {
+            const bool some = s_nhi[tid] >= s_nlo[tid];
+            int32_t* n = nd.narrow + ((int64_t)k * nct + ct0 + tid) * 2;
+            n[0] = some ? max(s_lo[tid], 4 * s_nlo[tid]) : 0x7fffffff; n[1] = some ? min(s_hi[tid], 4 * s_nhi[tid] + 3) : -1;
+        }
+    }
     for (int i = tid; i < nt * nr; i += kLevelThreads) {
         const int c = i / nr, r = i % nr, lo = s_lo[c], hi = s_hi[c];
         nd.bound[((int64_t)k * nct + ct0 + c) * nr + r] =

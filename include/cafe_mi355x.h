@@ -730,6 +730,12 @@ int cafe_debug_column_extents(cafe_ctx* ctx, int32_t node, int32_t category, int
  * `tile`, -inf where they are all exactly zero, never below -1060 otherwise.  out == NULL: the two sizes only.  CAFE_ERR_STATE
  * when the last call kept none (CAFE_NO_MAGSKIP, CAFE_NO_KSKIP, matrix order below 256, an error model). */
 int cafe_debug_panel_bounds(cafe_ctx* ctx, int32_t node, int32_t category, double* out, size_t out_len, int32_t* n_tiles, int32_t* row_steps);
+/* diagnostic: the narrowed hulls of an interior non-root node's panel in the last call, out[tile][2], laid out like
+ * cafe_get_extents' panel_ext: the structural hull of a 128-column tile cut back from both ends over the steps of 4 rows whose
+ * magnitude bound, before its floor, lies below 2^-1100 -- rows that hold computed zeros only, that the assemble passes do not
+ * write and that no K range reaches (lo > hi: the whole tile).  Equal to panel_ext where the last call kept no bounds (the
+ * state errors of cafe_debug_panel_bounds do not apply) and under CAFE_NO_NARROW=1.  *n_tiles receives the number of tiles. */
+int cafe_debug_narrowed_extents(cafe_ctx* ctx, int32_t node, int32_t category, int32_t* out, size_t out_len, int32_t* n_tiles);
 /* diagnostic: one slot of the magnitude tables of the last call's matrices (extents.hip, mag_tables_kernel), as written: upper
  * bounds of log2 in units of 1/256, -(1 << 28) where every entry the item stands for is exactly zero.
  *   which 0: a16, out[ks * *n1 + b]  the largest P[s][c], s in 16 b + 1 .. 16 b + 16, c in 4 ks .. 4 ks + 3   (interior branch)

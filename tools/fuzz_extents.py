@@ -1,6 +1,7 @@
 """Randomised cross-check of everything that decides WHICH work K2 / the assemble pass do (zero extents, planned tile lists,
 rows left out by the assemble pass, tile heights, grouped launches): random trees, tables, rates, categories, error models, several calls per
-context; every per-family value must have the bits of a context created with all of it switched off (CAFE_NO_KSKIP).
+context; every per-family value must have the bits of a context created with all of it switched off (CAFE_NO_KSKIP) or, in
+half the cases, with the narrowed hulls alone switched off (CAFE_NO_NARROW: the reference then skips by the structural hulls).
 Usage: fuzz_extents.py [cases] [seed]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -33,7 +34,7 @@ for case in range(n_cases):
             calls.append((P.Params(lambdas=lam, prior=P.prior_uniform(pb.max_root_family_size), multipliers=mult, cat_probs=probs, error_model=em), alpha))
         else:
             calls.append((P.Params(lambdas=lam, prior=P.prior_uniform(pb.max_root_family_size), error_model=em), 1.0))
-    for k in ("CAFE_NO_KSKIP", "CAFE_FORCE_TILE"):
+    for k in ("CAFE_NO_KSKIP", "CAFE_NO_NARROW", "CAFE_FORCE_TILE"):
         os.environ.pop(k, None)
     if rng.integers(0, 3) == 0:
         os.environ["CAFE_FORCE_TILE"] = str(int(rng.choice([2, 3, 4, 6, 7, 8])))
@@ -43,13 +44,14 @@ for case in range(n_cases):
     os.environ.pop("CAFE_FORCE_TILE", None)
     os.environ.pop("CAFE_LEAF_T_MIN", None)
     os.environ["CAFE_KB"] = "16" if os.environ["CAFE_KB"] == "8" else "8"
-    os.environ["CAFE_NO_KSKIP"] = "1"
+    ref_switch = "CAFE_NO_NARROW" if rng.integers(0, 2) == 0 else "CAFE_NO_KSKIP"
+    os.environ[ref_switch] = "1"
     if rng.integers(0, 2) == 0:
         os.environ["CAFE_NO_GROUPS"] = "1"                   # ... and one op per launch from the slot pool (the grouped schedule is the default)
     if rng.integers(0, 2) == 0:
         os.environ["CAFE_NO_LEAF_T"] = "1"                   # ... and assemble passes that gather their leaf from the row-major matrix
     plain = capi.Context(pb, max_categories=8)
-    os.environ.pop("CAFE_NO_KSKIP")
+    os.environ.pop(ref_switch)
     os.environ.pop("CAFE_NO_GROUPS", None)
     os.environ.pop("CAFE_NO_LEAF_T", None)
     os.environ.pop("CAFE_KB", None)
@@ -65,8 +67,8 @@ for case in range(n_cases):
         ok = ok and same
     n_planned = fast.plan_check()[0]
     st = fast.stats()
-    print("case %2d: taxa %2d families %5d N %d K %d lambdas %d error model %d: planned launches %d / %d, assemble passes %d -> %s"
-          % (case, n_taxa, n_fam, pb.matrix_size, K, pb.n_lambdas, n_dev, n_planned, st["gemm_launches"], st["n_assemble_passes"], "identical" if ok else "DIFFERENT"), flush=True)
+    print("case %2d: taxa %2d families %5d N %d K %d lambdas %d error model %d: planned launches %d / %d, assemble passes %d, reference %s -> %s"
+          % (case, n_taxa, n_fam, pb.matrix_size, K, pb.n_lambdas, n_dev, n_planned, st["gemm_launches"], st["n_assemble_passes"], ref_switch, "identical" if ok else "DIFFERENT"), flush=True)
     bad += not ok
 print("FAILED" if bad else "all identical")
 sys.exit(1 if bad else 0)
