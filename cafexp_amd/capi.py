@@ -98,6 +98,10 @@ class CafeHistoryOut(C.Structure):
                 ("log_evidence", _f64p), ("failed", _i32p)]
 
 
+class CafePvalueStages(C.Structure):
+    _fields_ = [("sizes", _i32p), ("counts", _i32p), ("cond_unsorted", _f64p), ("cond_sorted", _f64p), ("observed", _f64p)]
+
+
 class CafeStats(C.Structure):
     _fields_ = [
         ("ms_total", C.c_double), ("ms_matrices", C.c_double), ("ms_prune", C.c_double), ("ms_gemm", C.c_double),
@@ -138,6 +142,7 @@ EXPORTS = [
     "cafe_leaf_predictive", "cafe_set_root_rule", "cafe_get_root_rule", "cafe_root_posterior", "cafe_debug_magnitude_tables", "cafe_debug_level_tiles",
     "cafe_branch_change", "cafe_debug_branch_change_band", "cafe_score_batch",
     "cafe_score_per_family_gain", "cafe_bd_gain_row0", "cafe_debug_narrowed_extents",
+    "cafe_debug_pvalues_stages", "cafe_debug_sort_rows", "cafe_debug_tree_pvalue",
 ]
 CAFE_CHANGE_NONE = -(1 << 31)   # mode / lo / hi of cafe_branch_change at the root and in a failed family
 CAFE_COMM_ID_BYTES = 128
@@ -735,7 +740,9 @@ class Context:
         return out
 
     def pvalues(self, lambdas, n_simulations: int = 1000, seed: int = 1) -> np.ndarray:
-        """compute_pvalues with the simulation on the device (probability.cpp:418): statistical, not draw-for-draw."""
+        """compute_pvalues with the simulation on the device (probability.cpp:418): against the reference's own sample the
+        agreement is statistical, not draw-for-draw; the device's sample itself is a function of the seed that
+        tests/test_pvalues_replay.py replays draw for draw (tests/pvalues_ref.py) and checks stage by stage."""
         lam = np.ascontiguousarray(lambdas, dtype=np.float64)
         cp = CafeParams()
         cp.model = CAFE_MODEL_BASE
@@ -744,6 +751,29 @@ class Context:
         out = np.empty(self.n_families)
         self._check(self._lib.cafe_pvalues(self._h, C.byref(cp), n_simulations, seed, _p(out, _f64p)))
         return out
+
+    def pvalues_stages(self, lambdas, n_simulations: int = 1000, seed: int = 1) -> dict:
+        """One pvalues() call that also reads back what its stages left on the device (cafe_debug_pvalues_stages), Fs = R *
+        n_simulations: sizes int32 [n_nodes][Fs], counts int32 [n_taxa][Fs] (the simulated families' leaf counts as their
+        context reads them), cond_unsorted / cond_sorted [R][n_simulations] (their root maxima either side of the sort),
+        observed [n_families] (the root maxima of the listed families), pvalues [n_families]."""
+        f = self._lib.cafe_debug_pvalues_stages
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.c_uint64, C.POINTER(CafePvalueStages), _f64p]
+        lam = np.ascontiguousarray(lambdas, dtype=np.float64)
+        cp = CafeParams()
+        cp.model = CAFE_MODEL_BASE
+        cp.lambdas = _p(lam, _f64p)
+        cp.n_categories = 1
+        pb = self.problem
+        Fs = max(0, self.R * n_simulations)                  # (an invalid n_simulations is refused before anything is written)
+        res = {"sizes": np.full((self.n_nodes, Fs), -1, dtype=np.int32), "counts": np.full((pb.n_taxa, Fs), -1, dtype=np.int32),
+               "cond_unsorted": np.full((self.R, max(0, n_simulations)), np.nan), "cond_sorted": np.full((self.R, max(0, n_simulations)), np.nan),
+               "observed": np.full(self.n_families, np.nan), "pvalues": np.full(self.n_families, np.nan)}
+        st = CafePvalueStages(_p(res["sizes"], _i32p), _p(res["counts"], _i32p), _p(res["cond_unsorted"], _f64p),
+                              _p(res["cond_sorted"], _f64p), _p(res["observed"], _f64p))
+        self._check(f(self._h, C.byref(cp), n_simulations, seed, C.byref(st), _p(res["pvalues"], _f64p)))
+        return res
 
     def reconstruct(self, lambdas, root_prior, multipliers=None) -> np.ndarray:
         """Pupko joint reconstruction -> int32 [K][n_families][n_nodes] (gene_family_reconstructor.cpp:13-165).
@@ -1077,6 +1107,37 @@ def build_matrices(n: int, lambdas, ts, device: int = 0, layout: int = 0) -> np.
     rc = load().cafe_build_matrices(device, n, len(lam), _p(lam, _f64p), _p(t, _f64p), layout, _p(out, _f64p))
     if rc:
         raise CafeError("cafe_build_matrices failed with code %d" % rc)
+    return out
+
+
+def debug_sort_rows(values, device: int = 0) -> np.ndarray:
+    """cafe_debug_sort_rows: every row of values [rows][n] sorted ascending by cafe_pvalues' sort kernel, launched as it
+    launches it; returns a new array."""
+    L = load()
+    L.cafe_debug_sort_rows.restype = C.c_int
+    L.cafe_debug_sort_rows.argtypes = [C.c_int32, _f64p, C.c_int32, C.c_int32]
+    out = np.array(values, dtype=np.float64, order="C")
+    if out.ndim != 2:
+        raise ValueError("values must be [rows][n]")
+    rc = L.cafe_debug_sort_rows(device, _p(out, _f64p), out.shape[0], out.shape[1])
+    if rc:
+        raise CafeError("cafe_debug_sort_rows failed with code %d" % rc)
+    return out
+
+
+def debug_tree_pvalue(observed, cond, device: int = 0) -> np.ndarray:
+    """cafe_debug_tree_pvalue: cafe_pvalues' p-value kernel on observed [F] and cond [R][n] (rows sorted ascending)."""
+    L = load()
+    L.cafe_debug_tree_pvalue.restype = C.c_int
+    L.cafe_debug_tree_pvalue.argtypes = [C.c_int32, _f64p, C.c_int64, _f64p, C.c_int32, C.c_int32, _f64p]
+    obs = np.ascontiguousarray(observed, dtype=np.float64)
+    c = np.ascontiguousarray(cond, dtype=np.float64)
+    if obs.ndim != 1 or c.ndim != 2:
+        raise ValueError("observed must be [F] and cond [R][n]")
+    out = np.full(len(obs), np.nan)
+    rc = L.cafe_debug_tree_pvalue(device, _p(obs, _f64p), len(obs), _p(c, _f64p), c.shape[0], c.shape[1], _p(out, _f64p))
+    if rc:
+        raise CafeError("cafe_debug_tree_pvalue failed with code %d" % rc)
     return out
 
 

@@ -402,7 +402,8 @@ int history_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_draws, uint64_t s
 // Device-side p-values (pvalues.hip) and what it needs from cafe_create.hip and cafe_score.hip: a context over the same tree
 // whose family counts are written on the device, and the root-maximum prune of a context's families (-> d_fam_out, on stream s)
 constexpr int32_t kFlagDeviceCounts = 0x40000000;        // internal cafe_problem flag
-int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_simulations, uint64_t seed, double* pvalues);
+// (capture: cafe_debug_pvalues_stages' record of what the stages left, nullptr for cafe_pvalues -- no copy, no extra wait)
+int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_simulations, uint64_t seed, double* pvalues, const cafe_pvalue_stages* capture = nullptr);
 cafe_ctx* create_child_for_device_counts(const cafe_ctx* parent, int64_t n_families);
 void destroy_child(cafe_ctx* c);
 int enqueue_rootmax(cafe_ctx* c, const double* lambdas, hipStream_t s);

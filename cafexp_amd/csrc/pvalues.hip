@@ -113,9 +113,24 @@ __global__ __launch_bounds__(256) void tree_pvalue_kernel(const double* __restri
     out[f] = best;
 }
 
+// The two closing launches, one place for cafe_pvalues and the test hooks below
+hipError_t launch_sort_rows(double* d_rows, int rows, int n, hipStream_t s) {
+    int P2 = 1;
+    while (P2 < n) P2 <<= 1;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(sort_rows_kernel, dim3(rows), dim3(256), sizeof(double) * P2, s, d_rows, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_tree_pvalue(const double* d_observed, int64_t F, const double* d_cond, int R, int n, double* d_out, hipStream_t s) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(tree_pvalue_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, s, d_observed, F, d_cond, R, n, d_out);
+    return hipGetLastError();
+}
+
 }  // namespace
 
-int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t seed, double* pvalues) {
+int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t seed, double* pvalues, const cafe_pvalue_stages* cap) {
     if (!pr || !pr->lambdas || !pvalues) { set_err(c, "cafe_pvalues: lambdas and pvalues are required"); return CAFE_ERR_ARGUMENT; }
     if (n_sim < 1 || n_sim > 2048) { set_err(c, "cafe_pvalues: 1..2048 simulations per root size"); return CAFE_ERR_ARGUMENT; }
     if (!rates_valid(c, pr->lambdas)) { set_err(c, "cafe_pvalues: invalid lambda or death rate"); return CAFE_ERR_ARGUMENT; }
@@ -191,6 +206,9 @@ int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t see
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
     CAFE_LAUNCH(c, simulate_kernel, dim3((unsigned)((Fs + 255) / 256)), dim3(256), 0, s, a);
     HIP_TRY(c, hipStreamSynchronize(s));                            // the child context runs on its own stream
+    if (cap && cap->sizes) HIP_TRY(c, hipMemcpy(cap->sizes, d_sizes.p, sizeof(int32_t) * (size_t)n * Fs, hipMemcpyDeviceToHost));
+    if (cap && cap->counts)
+        HIP_TRY(c, hipMemcpy2D(cap->counts, sizeof(int32_t) * Fs, child->d_counts, sizeof(int32_t) * child->Fp, sizeof(int32_t) * Fs, c->n_taxa, hipMemcpyDeviceToHost));
     if (const int rc = enqueue_rootmax(child, pr->lambdas, child->stream)) {
         fail_after_enqueue(child, child->stream);
         fail_after_enqueue(c, s);                                   // (the observed families' root maxima are not results of a failed call)
@@ -198,25 +216,84 @@ int pvalues_impl(cafe_ctx* c, const cafe_params* pr, int32_t n_sim, uint64_t see
         return rc;
     }
     HIP_TRY(c, hipMemcpyAsync(d_cond.p, child->d_fam_out, sizeof(double) * Fs, hipMemcpyDeviceToDevice, child->stream));
-    int P2 = 1;
-    while (P2 < n_sim) P2 <<= 1;
-    CAFE_LAUNCH(c, sort_rows_kernel, dim3(R), dim3(256), sizeof(double) * P2, child->stream, static_cast<double*>(d_cond.p), n_sim);
+    if (cap && cap->cond_unsorted) {
+        HIP_TRY(c, hipStreamSynchronize(child->stream));
+        HIP_TRY(c, hipMemcpy(cap->cond_unsorted, d_cond.p, sizeof(double) * Fs, hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(c, launch_sort_rows(static_cast<double*>(d_cond.p), R, n_sim, child->stream));
     HIP_TRY(c, hipStreamSynchronize(child->stream));
     child->upload_pending = false;
+    if (cap && cap->cond_sorted) HIP_TRY(c, hipMemcpy(cap->cond_sorted, d_cond.p, sizeof(double) * Fs, hipMemcpyDeviceToHost));
 
     // ---- p-value of every (distinct) observed family, spread to the families that share a column
-    CAFE_LAUNCH(c, tree_pvalue_kernel, dim3((unsigned)((c->F_uniq + 255) / 256)), dim3(256), 0, s, c->d_fam_out, c->F_uniq, static_cast<const double*>(d_cond.p), R,
-                n_sim, static_cast<double*>(d_pv.p));
+    HIP_TRY(c, launch_tree_pvalue(c->d_fam_out, c->F_uniq, static_cast<const double*>(d_cond.p), R, n_sim, static_cast<double*>(d_pv.p), s));
     std::vector<double> tmp((size_t)c->F_uniq);
     HIP_TRY(c, hipMemcpyAsync(tmp.data(), d_pv.p, sizeof(double) * c->F_uniq, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     c->upload_pending = false;
     spread_unique(c, tmp.data(), pvalues);
+    if (cap && cap->observed) {
+        HIP_TRY(c, hipMemcpy(tmp.data(), c->d_fam_out, sizeof(double) * c->F_uniq, hipMemcpyDeviceToHost));
+        spread_unique(c, tmp.data(), cap->observed);
+    }
     return CAFE_OK;
+}
+
+// A test hook's frame: host arrays to the device, one launch on the null stream, the result back
+namespace {
+
+int on_device(int32_t device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CAFE_ERR_DEVICE;
+    return hipSetDevice(device) == hipSuccess ? CAFE_OK : CAFE_ERR_DEVICE;
+}
+
+}  // namespace
+
+int debug_sort_rows(int32_t device, double* values, int32_t rows, int32_t n) {
+    if (!values || rows < 1 || n < 1 || n > 2048) return CAFE_ERR_ARGUMENT;
+    if (const int rc = on_device(device)) return rc;
+    const size_t bytes = sizeof(double) * (size_t)rows * n;
+    DevBuf d;
+    if (hipMalloc(&d.p, bytes) != hipSuccess) { (void)hipGetLastError(); return CAFE_ERR_MEMORY; }
+    if (hipMemcpy(d.p, values, bytes, hipMemcpyHostToDevice) != hipSuccess) return CAFE_ERR_DEVICE;
+    if (launch_sort_rows(static_cast<double*>(d.p), rows, n, nullptr) != hipSuccess) return CAFE_ERR_DEVICE;
+    return hipMemcpy(values, d.p, bytes, hipMemcpyDeviceToHost) == hipSuccess ? CAFE_OK : CAFE_ERR_DEVICE;
+}
+
+int debug_tree_pvalue(int32_t device, const double* observed, int64_t F, const double* cond, int32_t R, int32_t n, double* pvalues) {
+    if (!observed || !cond || !pvalues || F < 1 || R < 1 || n < 1 || n > 2048) return CAFE_ERR_ARGUMENT;
+    if (const int rc = on_device(device)) return rc;
+    DevBuf d_obs, d_cond, d_pv;
+    if (hipMalloc(&d_obs.p, sizeof(double) * F) != hipSuccess || hipMalloc(&d_cond.p, sizeof(double) * (size_t)R * n) != hipSuccess ||
+        hipMalloc(&d_pv.p, sizeof(double) * F) != hipSuccess) {
+        (void)hipGetLastError();
+        return CAFE_ERR_MEMORY;
+    }
+    if (hipMemcpy(d_obs.p, observed, sizeof(double) * F, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_cond.p, cond, sizeof(double) * (size_t)R * n, hipMemcpyHostToDevice) != hipSuccess)
+        return CAFE_ERR_DEVICE;
+    if (launch_tree_pvalue(static_cast<const double*>(d_obs.p), F, static_cast<const double*>(d_cond.p), R, n, static_cast<double*>(d_pv.p), nullptr) != hipSuccess)
+        return CAFE_ERR_DEVICE;
+    return hipMemcpy(pvalues, d_pv.p, sizeof(double) * F, hipMemcpyDeviceToHost) == hipSuccess ? CAFE_OK : CAFE_ERR_DEVICE;
 }
 
 }  // namespace cafe
 
 extern "C" int cafe_pvalues(cafe_ctx* ctx, const cafe_params* params, int32_t n_simulations, uint64_t seed, double* pvalues) {
     return cafe::guarded_observed(ctx, "cafe_pvalues", [&] { return cafe::pvalues_impl(ctx, params, n_simulations, seed, pvalues); });
+}
+
+extern "C" int cafe_debug_pvalues_stages(cafe_ctx* ctx, const cafe_params* params, int32_t n_simulations, uint64_t seed,
+                                         const cafe_pvalue_stages* stages, double* pvalues) {
+    return cafe::guarded_observed(ctx, "cafe_debug_pvalues_stages", [&] { return cafe::pvalues_impl(ctx, params, n_simulations, seed, pvalues, stages); });
+}
+
+extern "C" int cafe_debug_sort_rows(int32_t device, double* values, int32_t rows, int32_t n) {
+    try { return cafe::debug_sort_rows(device, values, rows, n); } catch (const std::exception&) { return CAFE_ERR_MEMORY; }
+}
+
+extern "C" int cafe_debug_tree_pvalue(int32_t device, const double* observed, int64_t n_observed, const double* cond, int32_t n_root_sizes,
+                                      int32_t n, double* pvalues) {
+    try { return cafe::debug_tree_pvalue(device, observed, n_observed, cond, n_root_sizes, n, pvalues); } catch (const std::exception&) { return CAFE_ERR_MEMORY; }
 }

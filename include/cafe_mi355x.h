@@ -799,6 +799,25 @@ int cafe_debug_force_tile(cafe_ctx* ctx, int mi);
 int cafe_debug_fail_next(cafe_ctx* ctx, int n);
 /* diagnostic (CAFE_GEMM_STAMPS=1 at cafe_create): per-block placement + timeline words of the last K2 launch */
 int cafe_debug_stamps(cafe_ctx* ctx, unsigned long long* out, size_t words);
+/* test hook: one cafe_pvalues call -- the same arguments, the same launches, the same p-values, bit for bit -- that also copies
+ * what its stages left on the device into the caller's host arrays (any of them may be NULL), Fs = R * n_simulations, family
+ * f = s * n_simulations + i simulated from root size s:
+ *   sizes[n_nodes][Fs]        the simulated size of every node (simulate_kernel's scratch);
+ *   counts[n_taxa][Fs]        the leaf counts as the context of the simulated families reads them: its taxon-major table, read
+ *                             with its own leading dimension and cut to Fs columns;
+ *   cond_unsorted[R][n_simulations], cond_sorted[R][n_simulations]
+ *                             that context's root maxima before and after sort_rows_kernel;
+ *   observed[n_families]      the observed families' root maxima the p-value kernel read, spread to the listed families.
+ * The copies cost synchronous transfers and two waits that cafe_pvalues does not make: for tests, not for timing. */
+typedef struct cafe_pvalue_stages {
+    int32_t* sizes;
+    int32_t* counts;
+    double*  cond_unsorted;
+    double*  cond_sorted;
+    double*  observed;
+} cafe_pvalue_stages;
+int cafe_debug_pvalues_stages(cafe_ctx* ctx, const cafe_params* params, int32_t n_simulations, uint64_t seed,
+                              const cafe_pvalue_stages* stages, double* pvalues);
 
 /* Stand-alone kernels exposed for unit parity tests and the roofline probe. */
 /* builds `count` matrices of order n for (lambda[i], t[i]) pairs with matrix_cache_key quantization
@@ -809,6 +828,15 @@ int cafe_build_matrices(int32_t device, int32_t n, int32_t count, const double* 
 /* the same under separate birth and death rates (lambdas[i], mus[i], ts[i]): K1's two-rate instantiation (bd_matrix_lm.hip) */
 int cafe_build_matrices_lm(int32_t device, int32_t n, int32_t count, const double* lambdas, const double* mus, const double* ts,
                            int32_t layout, double* out);
+/* cafe_pvalues' two closing kernels alone, on host arrays, launched as cafe_pvalues launches them (pvalues.hip):
+ *   cafe_debug_sort_rows    sorts each of the `rows` rows of values[rows][n] ascending in place (sort_rows_kernel, one block
+ *                           per row, n = 1..2048);
+ *   cafe_debug_tree_pvalue  pvalues[f] = max over the n_root_sizes rows of cond[n_root_sizes][n] (each sorted ascending) of
+ *                           the number of entries <= observed[f], a count of n reported as n - 1, over n (tree_pvalue_kernel).
+ * CAFE_ERR_ARGUMENT for a NULL array or a size outside those ranges. */
+int cafe_debug_sort_rows(int32_t device, double* values, int32_t rows, int32_t n);
+int cafe_debug_tree_pvalue(int32_t device, const double* observed, int64_t n_observed, const double* cond, int32_t n_root_sizes,
+                           int32_t n, double* pvalues);
 /* The weighted Gram matrix of cafe_branch_scores alone: gram[p][p] = S diag(w) S^T and total[p] = S w for S [p][n] row-major,
  * host pointers (gram or total may be NULL).  One wave forms one 16 x 16 tile of the lower triangle over one slab of 2048
  * columns on v_mfma_f64_16x16x4_f64; the slabs' partial tiles are added in slab order and the upper triangle is the mirror

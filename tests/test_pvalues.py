@@ -5,7 +5,8 @@ CPU: the oracle's restatement (root maximum, pvalue, tree p-value) against the r
 written by tests/golden/make_golden.py pvalues).
 GPU: cafe_root_max against the oracle, and the cafexp_hip driver's compute_pvalues -- host draws that consume the
 engine like the reference, both prune batches on the GPU -- against the same golden p-values and conditional
-distributions.
+distributions; cafe_pvalues (device draws) against them statistically.  What cafe_pvalues computes from its own seed -- every
+draw, the sort, the upper bounds -- is replayed exactly in tests/test_pvalues_replay.py.
 """
 import json
 import os
@@ -164,8 +165,9 @@ def test_driver_pvalues_match_compiled_reference(gp, tmp_path, name):
 @pytest.mark.gpu
 def test_device_side_simulation_agrees_statistically(gp):
     """cafe_pvalues draws on the device (Philox keyed by the seed): a different sample of the same distribution as the
-    reference's, so agreement is statistical.  Seeds are fixed, so the numbers below are reproducible; the bounds leave
-    several standard errors of a 1000-sample tail estimate (sqrt(p(1-p)/n) <= 0.016)."""
+    reference's, so agreement with the reference is statistical.  Seeds are fixed, so the numbers below are reproducible; the bounds leave
+    several standard errors of a 1000-sample tail estimate (sqrt(p(1-p)/n) <= 0.016).  The device's own sample, its sort and its
+    p-value rule are pinned exactly, stage by stage, by tests/test_pvalues_replay.py."""
     from cafexp_amd import capi
     e = gp["mammals"]
     pb, pr = _problem(e)
