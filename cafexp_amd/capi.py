@@ -78,6 +78,10 @@ class CafeEventsOut(C.Structure):
     _fields_ = [("gains", _f64p), ("losses", _f64p), ("log_evidence", _f64p), ("failed", _i32p)]
 
 
+class CafeGainPosteriorOut(C.Structure):
+    _fields_ = [("lnl", _f64p), ("p_absent", _f64p), ("mean", _f64p), ("p_gain", _f64p), ("p_loss", _f64p), ("posterior", _f64p)]
+
+
 class CafeLeafPredictiveOut(C.Structure):
     _fields_ = [("mean", _f64p), ("sd", _f64p), ("p_below", _f64p), ("p_obs", _f64p), ("p_above", _f64p), ("log_evidence", _f64p),
                 ("failed", _i32p)]
@@ -141,7 +145,7 @@ EXPORTS = [
     "cafe_branch_scores", "cafe_branch_scores_dim", "cafe_weighted_gram", "cafe_debug_gram",
     "cafe_leaf_predictive", "cafe_set_root_rule", "cafe_get_root_rule", "cafe_root_posterior", "cafe_debug_magnitude_tables", "cafe_debug_level_tiles",
     "cafe_branch_change", "cafe_debug_branch_change_band", "cafe_score_batch",
-    "cafe_score_per_family_gain", "cafe_bd_gain_row0", "cafe_debug_narrowed_extents",
+    "cafe_score_per_family_gain", "cafe_bd_gain_row0", "cafe_debug_narrowed_extents", "cafe_gain_posterior",
     "cafe_debug_pvalues_stages", "cafe_debug_sort_rows", "cafe_debug_tree_pvalue",
 ]
 CAFE_CHANGE_NONE = -(1 << 31)   # mode / lo / hi of cafe_branch_change at the root and in a failed family
@@ -223,6 +227,9 @@ def load():
     L.cafe_set_death_rates.argtypes = [C.c_void_p, _f64p]
     L.cafe_score_per_family_gain.restype = C.c_int
     L.cafe_score_per_family_gain.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p, _f64p, C.c_double, _f64p]
+    L.cafe_gain_posterior.restype = C.c_int
+    L.cafe_gain_posterior.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p, _f64p, C.c_double,
+                                      C.POINTER(CafeGainPosteriorOut)]
     L.cafe_bd_gain_row0.restype = C.c_int
     L.cafe_bd_gain_row0.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _f64p, _f64p]
     L.cafe_bd_rates.restype = C.c_int
@@ -551,6 +558,30 @@ class Context:
         self._check(self._lib.cafe_score_per_family_gain(self._h, C.byref(cp), len(fam), _p(fam, _i64p), _p(lam, _f64p),
                                                          None if mu is None else _p(mu, _f64p), _p(nu, _f64p), float(root_absent), _p(out, _f64p)))
         return out
+
+    def gain_posterior(self, pr: Params, families, lambdas, mus, nus, root_absent: float = 0.0, want_posterior: bool = False) -> dict:
+        """cafe_gain_posterior: under the gain model, entry i = families[i] under its own (lambdas, mus, nus)[i] (the arguments
+        of score_per_family_gain), for every node: p_absent = P(size = 0 | counts), mean, p_gain = P(parent absent, node present
+        | counts), p_loss = P(parent present, node absent | counts) -- NaN at the root -- all [n][n_nodes], and lnl [n], the
+        sum-rule lnL whatever the context's root rule is.  want_posterior adds posterior [n][n_nodes][matrix_size]."""
+        fam = np.ascontiguousarray(families, dtype=np.int64).reshape(-1)
+        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(len(fam), -1)
+        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(len(fam), -1)
+        mu = None if mus is None else np.ascontiguousarray(mus, dtype=np.float64).reshape(len(fam), -1)
+        if lam.shape[1] != self.problem.n_lambdas or nu.shape != lam.shape or (mu is not None and mu.shape != lam.shape):
+            raise ValueError("lambdas, mus and nus must be [%d][%d]" % (len(fam), self.problem.n_lambdas))
+        cp, keep = self._params(pr)
+        n, nodes = len(fam), self.problem.n_nodes
+        res = {"lnl": np.empty(n), "p_absent": np.empty((n, nodes)), "mean": np.empty((n, nodes)), "p_gain": np.empty((n, nodes)),
+               "p_loss": np.empty((n, nodes))}
+        if want_posterior:
+            res["posterior"] = np.empty((n, nodes, self.problem.matrix_size))
+        out = CafeGainPosteriorOut()
+        for name, array in res.items():
+            setattr(out, name, _p(array, _f64p))
+        self._check(self._lib.cafe_gain_posterior(self._h, C.byref(cp), n, _p(fam, _i64p), _p(lam, _f64p), None if mu is None else _p(mu, _f64p),
+                                                  _p(nu, _f64p), float(root_absent), C.byref(out)))
+        return res
 
     def marginal_reconstruct(self, pr: Params, level: float = 0.95, alpha: float = 1.0) -> dict:
         """cafe_marginal_reconstruct: posterior size of every node under the scorer's model with pr's lambdas, categories,

@@ -8,6 +8,10 @@
 //   branches(a, n, batch, nodes, s)      one level of branches
 //   root(c, ra, batch, s)                the root kernel of the context's root rule
 // mus and nus are [n][n_lambdas] or null, as the entry defines them.
+//
+// An entry that goes on where the root kernel stops (family_gain_posterior.hip: the down pass) hands the frame a Tail: device
+// bytes of its own behind the factors -- counted into the batch size -- one call when the workspace stands, one behind the root
+// kernel of every batch, one behind the batch's synchronisation.  The score entries pass FamNoTail: no byte, no call.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -50,11 +54,20 @@ inline SlotParamLM branch_param_lm(const cafe_ctx* c, int u, const double* lam, 
 
 inline size_t family_align_up(size_t v) { return (v + 255) / 256 * 256; }
 
+struct FamNoTail {
+    size_t static_bytes(const cafe_ctx*) const { return 0; }
+    size_t family_bytes(const cafe_ctx*, int) const { return 0; }
+    template <class Slot>
+    int begin(cafe_ctx*, const FamLamArgs<Slot>&, const FamRootArgs&, char*, char*, int64_t, hipStream_t) { return CAFE_OK; }
+    int run(cafe_ctx*, int64_t, hipStream_t) { return CAFE_OK; }
+    void collect(const int64_t*, const double*, int64_t) {}
+};
+
 // The host frame of every entry: argument checks, what the host decides alone, levels and tables, the batches under the
 // workspace limit, one launch per level and the root kernel.
-template <class Kind>
-int per_family_frame(const Kind& kind, cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_t* family, const double* lambdas, const double* mus,
-                     const double* nus, double* family_lnl) {
+template <class Kind, class Tail>
+int per_family_frame(const Kind& kind, Tail& tail, cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_t* family, const double* lambdas,
+                     const double* mus, const double* nus, double* family_lnl) {
     using Slot = typename Kind::Slot;
     const char* const who = Kind::entry;
     if (!pr || !pr->prior) { set_err(c, "%s: params with a prior are required", who); return CAFE_ERR_ARGUMENT; }
@@ -121,15 +134,17 @@ int per_family_frame(const Kind& kind, cafe_ctx* c, const cafe_params* pr, int64
 
     // ---- the batch: as many listed families as the workspace holds
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t static_bytes = family_align_up(sizeof(int32_t) * tables.size()) + family_align_up(sizeof(double) * reals.size());
-    const size_t family_bytes = sizeof(double) * (size_t)nn * ld + sizeof(Slot) * (size_t)nn + sizeof(int64_t) + sizeof(double);
+    const size_t tail_static = family_align_up(tail.static_bytes(c)), tail_family = tail.family_bytes(c, ld), tail_pad = tail_static + tail_family ? 256 : 0;
+    const size_t static_bytes = family_align_up(sizeof(int32_t) * tables.size()) + family_align_up(sizeof(double) * reals.size()) + tail_static + tail_pad;
+    const size_t family_bytes = sizeof(double) * (size_t)nn * ld + sizeof(Slot) * (size_t)nn + sizeof(int64_t) + sizeof(double) + tail_family;
     size_t budget = 0;
     HIP_TRY(c, workspace_budget(c->workspace_limit, c->pf_dev_bytes, &budget));
     int64_t batch = std::max<int64_t>(1, std::min<int64_t>(na, budget > static_bytes + 1024 ? (int64_t)((budget - static_bytes - 1024) / family_bytes) : 1));
     if (c->pf_max_batch > 0) batch = std::min(batch, c->pf_max_batch);
     const size_t o_reals = family_align_up(sizeof(int32_t) * tables.size()), o_col = o_reals + family_align_up(sizeof(double) * reals.size()),
                  o_out = o_col + family_align_up(sizeof(int64_t) * batch), o_slots = o_out + family_align_up(sizeof(double) * batch),
-                 o_fac = o_slots + family_align_up(sizeof(Slot) * (size_t)batch * nn), need = o_fac + sizeof(double) * (size_t)batch * nn * ld;
+                 o_fac = o_slots + family_align_up(sizeof(Slot) * (size_t)batch * nn), fac_end = o_fac + sizeof(double) * (size_t)batch * nn * ld,
+                 o_tail = tail_pad ? family_align_up(fac_end) : fac_end, need = o_tail + tail_static + tail_family * (size_t)batch;
     if (need > c->pf_dev_bytes) {
         if (c->pf_dev) { HIP_TRY(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->pf_dev); c->pf_dev = nullptr; c->pf_dev_bytes = 0; }
         if (hipMalloc(&c->pf_dev, need) != hipSuccess) {
@@ -159,6 +174,7 @@ int per_family_frame(const Kind& kind, cafe_ctx* c, const cafe_params* pr, int64
     ra.root_children = d_tables + o_rootch; ra.n_root_children = (int32_t)root_children.size();
     ra.R = c->R; ra.ld = ld; ra.n_nodes = nn; ra.log_prior = d_reals; ra.factors = a.factors;
     ra.out = reinterpret_cast<double*>(base + o_out);
+    if (const int rc = tail.begin(c, a, ra, base + o_tail, base + o_tail + tail_static, batch, s)) return rc;
 
     std::vector<Slot> slots((size_t)batch * nn);
     std::vector<int64_t> col((size_t)batch);
@@ -178,11 +194,27 @@ int per_family_frame(const Kind& kind, cafe_ctx* c, const cafe_params* pr, int64
             HIP_TRY(c, Kind::branches(a, c->N, nb, level_off[lv + 1] - level_off[lv], s));
         }
         HIP_TRY(c, kind.root(c, ra, nb, s));
+        if (const int rc = tail.run(c, nb, s)) return rc;
         HIP_TRY(c, hipMemcpyAsync(res.data(), base + o_out, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));            // the host tables of this batch go out of use
         for (int64_t b = 0; b < nb; ++b) family_lnl[active[b0 + b]] = res[b];
+        tail.collect(active.data() + b0, res.data(), nb);
     }
     return CAFE_OK;
 }
+
+template <class Kind>
+int per_family_frame(const Kind& kind, cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_t* family, const double* lambdas, const double* mus,
+                     const double* nus, double* family_lnl) {
+    FamNoTail none;
+    return per_family_frame(kind, none, c, pr, n, family, lambdas, mus, nus, family_lnl);
+}
+
+// What family_gain.hip lends the entries that run its kernels (family_gain_posterior.hip): the checks of nus and root_absent, the
+// slot of a branch and the sum-rule root kernel whatever the context's root rule is.
+struct SlotParamGain;
+int gain_rates_check(cafe_ctx* c, const char* who, int64_t n, const double* nus, double root_absent);
+SlotParamGain gain_branch_slot(const cafe_ctx* c, int u, const double* lam, const double* mus, const double* nus);
+hipError_t gain_root_sum(const FamRootArgs& ra, double root_absent, int64_t nb, hipStream_t s);
 
 }  // namespace cafe

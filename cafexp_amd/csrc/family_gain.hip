@@ -84,6 +84,43 @@ __global__ __launch_bounds__(64) void family_gain_root_sum_kernel(const FamRootG
 
 bool beyond_long(double rate) { return !(rate * 1000000000 < 9.0e18); }
 
+hipError_t launch_root(bool sum_rule, const FamRootArgs& ra, double root_absent, int64_t nb, hipStream_t s) {
+    FamRootGainArgs ga{ra, std::log(root_absent), std::log1p(-root_absent)};
+    (void)hipGetLastError();
+    if (sum_rule) hipLaunchKernelGGL(family_gain_root_sum_kernel, dim3((unsigned)nb), dim3(64), 0, s, ga);
+    else hipLaunchKernelGGL(family_gain_root_kernel, dim3((unsigned)nb), dim3(64), 0, s, ga);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+int gain_rates_check(cafe_ctx* c, const char* who, int64_t n, const double* nus, double root_absent) {
+    if (!(root_absent >= 0 && root_absent <= 1)) { set_err(c, "%s: root_absent %g outside [0, 1]", who, root_absent); return CAFE_ERR_ARGUMENT; }
+    if (n > 0 && !nus) { set_err(c, "%s: nus are required", who); return CAFE_ERR_ARGUMENT; }
+    for (int64_t i = 0; i < n * c->n_lambdas; ++i)
+        if (!(nus[i] >= 0)) { set_err(c, "%s: gain rate %g of entry %lld is negative or NaN", who, nus[i], (long long)(i / c->n_lambdas)); return CAFE_ERR_ARGUMENT; }
+    return CAFE_OK;
+}
+SlotParamGain gain_branch_slot(const cafe_ctx* c, int u, const double* lam, const double* mus, const double* nus) {
+    const int i = c->lam_idx[u];
+    const double l = lam[i], m = mus ? mus[i] : l, nu = nus[i];
+    if (beyond_long(l) || beyond_long(m) || beyond_long(nu)) return slot_param_gain(0, 0, nu > 0 ? 1 : 0, 0, true);
+    return slot_param_gain(quantize_lambda(l), quantize_lambda(m), quantize_lambda(nu), quantize_time(c->blen[u]));
+}
+hipError_t launch_family_gain(const FamLamArgs<SlotParamGain>& a, int n, int64_t batch, int n_level_nodes, hipStream_t stream) {
+    if (batch <= 0 || n_level_nodes <= 0) return hipSuccess;
+    if (n > bd_matrix_max_order() || n > a.ld || batch > 0x7fffffff || n_level_nodes > 65535) return hipErrorInvalidValue;
+    dim3 grid((unsigned)batch, (unsigned)n_level_nodes), block(64);
+    return for_lane_width(n, [&](auto e) {
+        (void)hipGetLastError();
+        hipLaunchKernelGGL((family_gain_kernel<decltype(e)::value>), grid, block, 0, stream, a);
+        return hipGetLastError();
+    });
+}
+hipError_t gain_root_sum(const FamRootArgs& ra, double root_absent, int64_t nb, hipStream_t s) { return launch_root(true, ra, root_absent, nb, s); }
+
+namespace {
+
 struct GainRates {
     using Slot = SlotParamGain;
     static constexpr const char* entry = "cafe_score_per_family_gain";
@@ -92,29 +129,14 @@ struct GainRates {
     double root_absent;
 
     static bool rates_ok(int L, const double* mus, const double*) { return death_rates_ok(L, mus); }      // (nus: checked for the whole call)
-    static Slot slot(const cafe_ctx* c, int u, const double* lam, const double* mus, const double* nus) {
-        const int i = c->lam_idx[u];
-        const double l = lam[i], m = mus ? mus[i] : l, nu = nus[i];
-        if (beyond_long(l) || beyond_long(m) || beyond_long(nu)) return slot_param_gain(0, 0, nu > 0 ? 1 : 0, 0, true);
-        return slot_param_gain(quantize_lambda(l), quantize_lambda(m), quantize_lambda(nu), quantize_time(c->blen[u]));
-    }
+    static Slot slot(const cafe_ctx* c, int u, const double* lam, const double* mus, const double* nus) { return gain_branch_slot(c, u, lam, mus, nus); }
     static hipError_t branches(const FamLamArgs<Slot>& a, int n, int64_t nb, int nodes, hipStream_t s) { return launch_family_gain(a, n, nb, nodes, s); }
-    hipError_t root(const cafe_ctx* c, const FamRootArgs& ra, int64_t nb, hipStream_t s) const {
-        FamRootGainArgs ga{ra, std::log(root_absent), std::log1p(-root_absent)};
-        (void)hipGetLastError();
-        if (c->root_rule == CAFE_ROOT_SUM) hipLaunchKernelGGL(family_gain_root_sum_kernel, dim3((unsigned)nb), dim3(64), 0, s, ga);
-        else hipLaunchKernelGGL(family_gain_root_kernel, dim3((unsigned)nb), dim3(64), 0, s, ga);
-        return hipGetLastError();
-    }
+    hipError_t root(const cafe_ctx* c, const FamRootArgs& ra, int64_t nb, hipStream_t s) const { return launch_root(c->root_rule == CAFE_ROOT_SUM, ra, root_absent, nb, s); }
 };
 
 int score_per_family_gain_impl(cafe_ctx* c, const cafe_params* pr, int64_t n, const int64_t* family, const double* lambdas, const double* mus,
                                const double* nus, double root_absent, double* family_lnl) {
-    const char* const who = GainRates::entry;
-    if (!(root_absent >= 0 && root_absent <= 1)) { set_err(c, "%s: root_absent %g outside [0, 1]", who, root_absent); return CAFE_ERR_ARGUMENT; }
-    if (n > 0 && !nus) { set_err(c, "%s: nus are required", who); return CAFE_ERR_ARGUMENT; }
-    for (int64_t i = 0; i < n * c->n_lambdas; ++i)
-        if (!(nus[i] >= 0)) { set_err(c, "%s: gain rate %g of entry %lld is negative or NaN", who, nus[i], (long long)(i / c->n_lambdas)); return CAFE_ERR_ARGUMENT; }
+    if (const int rc = gain_rates_check(c, GainRates::entry, n, nus, root_absent)) return rc;
     return per_family_frame(GainRates{root_absent}, c, pr, n, family, lambdas, mus, nus, family_lnl);
 }
 

@@ -186,16 +186,8 @@ __global__ __launch_bounds__(64) void family_gain_kernel(const FamLamArgs<SlotPa
     }
 }
 
-// one level of branches for `batch` listed families: grid (batch, n_level_nodes), one wave each; n = matrix order
-inline hipError_t launch_family_gain(const FamLamArgs<SlotParamGain>& a, int n, int64_t batch, int n_level_nodes, hipStream_t stream) {
-    if (batch <= 0 || n_level_nodes <= 0) return hipSuccess;
-    if (n > bd_matrix_max_order() || n > a.ld || batch > 0x7fffffff || n_level_nodes > 65535) return hipErrorInvalidValue;
-    dim3 grid((unsigned)batch, (unsigned)n_level_nodes), block(64);
-    return for_lane_width(n, [&](auto e) {
-        (void)hipGetLastError();
-        hipLaunchKernelGGL((family_gain_kernel<decltype(e)::value>), grid, block, 0, stream, a);
-        return hipGetLastError();
-    });
-}
+// one level of branches for `batch` listed families: grid (batch, n_level_nodes), one wave each; n = matrix order.  Defined in
+// family_gain.hip, so that the kernels are instantiated in that translation unit and nowhere else.
+hipError_t launch_family_gain(const FamLamArgs<SlotParamGain>& a, int n, int64_t batch, int n_level_nodes, hipStream_t stream);
 
 }  // namespace cafe

@@ -609,6 +609,11 @@ public:
     std::vector<double> per_family_gain_lnl(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist,
                                             const std::vector<int64_t>& family, const std::vector<double>& lambdas,
                                             const std::vector<double>& mus, const std::vector<double>& nus, double root_absent);
+    // cafe_gain_posterior at the same arguments: posterior absence, origin and loss of every listed family at every node, columns
+    // in `order` (gain_origins.cpp has the reports)
+    struct gain_origins gain_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
+                                       const std::vector<double>& lambdas, const std::vector<double>& mus, const std::vector<double>& nus,
+                                       double root_absent, const std::vector<const clade*>& order);
 };
 class hip_gamma_model : public hip_model_base {
     std::vector<double> _lambda_multipliers, _gamma_cat_probs;
@@ -1055,7 +1060,7 @@ gain_result fit_gain_model(const gain_scorer& score, const gain_table& table, in
                            const std::function<std::vector<double>()>& draw_lambdas);
 // Why the gain options cannot be combined with what else was asked for, or nullptr
 struct gain_request {
-    bool gain = false, estimate_gain = false, root_absent_given = false, unconditional = false;
+    bool gain = false, estimate_gain = false, root_absent_given = false, unconditional = false, posterior = false;
     double nu = 0, root_absent = 0;
     bool gamma = false, per_family = false, gpus = false, simulate = false, pvalues = false, reconstruct = false, marginal = false, histories = false,
          standard_errors = false, events = false, rate_shift = false, leaf_predictive = false, branch_change = false, rootdist_em = false,
@@ -1063,5 +1068,28 @@ struct gain_request {
 };
 const char* gain_refusal(const gain_request& r);
 void write_gain_results(std::ostream& ost, const gain_result& res, const gain_options& opt, const gain_table& table);
+
+// ---------------------------------------------------------------- --gain-posterior (gain_origins.cpp): where a family originated and was lost
+// cafe_gain_posterior at the fitted rates over the entries of a gain_table (every distinct family once, the absent profile last)
+struct gain_origins {
+    size_t n_nodes = 0;                          // columns, in the reports' node order
+    std::vector<double> lnl;                     // [entries]; an entry without a finite lnl has failed and NaN everywhere else
+    std::vector<double> p_absent, mean, p_gain, p_loss;       // [entries][n_nodes]; p_gain and p_loss are NaN at the root
+};
+// Sums over the table's families: entry e counts weight[e] times (the absent profile: 0), a failed entry not at all
+struct gain_branch_origins {
+    std::vector<double> originated, lost, present;            // [n_nodes] sum p_gain, sum p_loss, sum (1 - p_absent); 0 / 0 / sum at the root
+    std::vector<double> likely_origin;           // [n_nodes] the number of families with p_gain > 0.5 on the branch above the node
+    double absent_at_root = 0;                   // sum p_absent of the root
+    double used = 0, failed = 0;                 // families summed, and families whose entry failed
+    double origin_somewhere = 0;                 // families with p_gain > 0.5 on some branch
+};
+gain_branch_origins gain_origin_totals(const gain_origins& o, const std::vector<double>& weight, size_t root);
+// Gain_origins.tab: a header row, then one line per family of the table -- for every node p_absent:mean, then for every branch
+// (every node but the root, same order) p_gain:p_loss.  entry_of[i]: the entry of family i.
+void write_gain_origins(std::ostream& ost, const gain_origins& o, const std::vector<std::string>& node_names, size_t root,
+                        const std::vector<std::string>& family_ids, const std::vector<size_t>& entry_of);
+// Gain_branch_origins.tab: one line per branch -- originated, lost, present, the families with p_gain > 0.5 -- and a root line
+void write_gain_branch_origins(std::ostream& ost, const gain_branch_origins& t, const std::vector<std::string>& node_names, size_t root);
 
 }  // namespace cafe

@@ -168,6 +168,7 @@ const char* gain_refusal(const gain_request& r) {
     if (!r.gain && !r.estimate_gain) {
         if (r.root_absent_given) return "--root-absent sets the root's mass at size 0 under the gain model: give --gain NU or --estimate-gain with it";
         if (r.unconditional) return "--gain-unconditional belongs to the gain model: give --gain NU or --estimate-gain with it";
+        if (r.posterior) return "--gain-posterior reports where families originated under the gain model: give --gain NU or --estimate-gain with it";
         return nullptr;
     }
     if (r.gain && r.estimate_gain) return "--gain fixes the gain rate and --estimate-gain searches it: give one of the two";

@@ -277,6 +277,37 @@ std::vector<double> hip_base_model::per_family_gain_lnl(root_equilibrium_distrib
     return out;
 }
 
+gain_origins hip_base_model::gain_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
+                                            const std::vector<double>& lambdas, const std::vector<double>& mus, const std::vector<double>& nus,
+                                            double root_absent, const std::vector<const clade*>& order) {
+    ensure_context(1);
+    std::vector<float> prior_f;
+    std::vector<double> err, unused;
+    gather_call_inputs(prior, rootdist, prior_f, err, unused);
+    cafe_params pr{};
+    pr.model = CAFE_MODEL_BASE; pr.n_categories = 1; pr.prior = prior_f.data();
+    pr.error_model = err.empty() ? nullptr : err.data();
+    if (mus.size() != lambdas.size() || nus.size() != lambdas.size()) throw std::runtime_error("gain_posterior: one mu and one nu per lambda are required");
+    const size_t n = _order.size(), F = family.size(), m = order.size();
+    std::vector<double> p_absent(F * n), mean(F * n), p_gain(F * n), p_loss(F * n);
+    gain_origins res;
+    res.n_nodes = m;
+    res.lnl.resize(F);
+    cafe_gain_posterior_out out{};
+    out.lnl = res.lnl.data(); out.p_absent = p_absent.data(); out.mean = mean.data(); out.p_gain = p_gain.data(); out.p_loss = p_loss.data();
+    if (cafe_gain_posterior(_ctx, &pr, (int64_t)F, family.data(), lambdas.data(), mus.data(), nus.data(), root_absent, &out) != CAFE_OK)
+        throw std::runtime_error(std::string("cafe_gain_posterior: ") + cafe_last_error(_ctx));
+    std::map<const clade*, size_t> pos;
+    for (size_t v = 0; v < n; ++v) pos[_order[v]] = v;
+    res.p_absent.resize(F * m); res.mean.resize(F * m); res.p_gain.resize(F * m); res.p_loss.resize(F * m);
+    for (size_t f = 0; f < F; ++f)
+        for (size_t i = 0; i < m; ++i) {
+            const size_t src = f * n + pos.at(order[i]), dst = f * m + i;
+            res.p_absent[dst] = p_absent[src]; res.mean[dst] = mean[src]; res.p_gain[dst] = p_gain[src]; res.p_loss[dst] = p_loss[src];
+        }
+    return res;
+}
+
 root_posterior_result hip_model_base::root_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist) {
     std::vector<double> mult, probs;
     double alpha = 0;

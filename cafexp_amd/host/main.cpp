@@ -83,7 +83,7 @@ static void usage() {
         "                  [--workspace BYTES] [-o OUTDIR]   writes OUTDIR (default results)/Base_lambda_per_family.txt, one line per family\n"
         "                  [--family-mu M1[,M2,..] | --family-mu estimate]   separate death rates per family (only with -b): fixed at the given\n"
         "                  rates, one per lambda, or searched with each family's lambdas (start mu = lambda); also writes Base_mu_per_family.txt\n"
-        "gene gain rate: cafexp_hip -t TREE -i FAMILIES (--gain NU | --estimate-gain) [--root-absent P0] [--gain-unconditional] [-l LAMBDA | -m L1,L2,..]\n"
+        "gene gain rate: cafexp_hip -t TREE -i FAMILIES (--gain NU | --estimate-gain) [--root-absent P0] [--gain-unconditional] [--gain-posterior] [-l LAMBDA | -m L1,L2,..]\n"
         "                  [-y LAMBDA_TREE] [--mu M1,.. | --estimate-mu] [-e ERRMODEL] [-p [L]] [-f ROOTDIST] [--missing TOKENS] [--mask-cells FILE] [-z] [-o OUTDIR]\n"
         "                  birth-death with immigration (n -> n+1 at rate n lambda + NU): a family absent in an ancestor can appear below it.  One set\n"
         "                  of rates for the table, fitted under the sum rule to the likelihood conditional on a family being seen in at least one\n"
@@ -91,6 +91,11 @@ static void usage() {
         "                  without NU, then with it from that optimum.  Writes OUTDIR/Gain_results.txt and Gain_family_likelihoods.txt.  -z keeps the\n"
         "                  families of one clade only, which this model is about.  Base model, one GPU; not with -k / -a, -b, --gpus, --simulate,\n"
         "                  --pvalues, a reconstruction or posterior report, or --search-batch\n"
+        "                  [--gain-posterior]   after the fit, at the fitted rates: for every family and node the posterior probability that the\n"
+        "                  family is absent there and its mean size, and for every branch that it originated (parent absent, node present) or was\n"
+        "                  lost (parent present, node absent) on it: OUTDIR/Gain_origins.tab (p_absent:mean per node, p_gain:p_loss per branch) and\n"
+        "                  Gain_branch_origins.tab (per branch: the expected numbers of families that originated, were lost, are present, and the\n"
+        "                  families with p_gain > 0.5)\n"
         "simulation (the reference's -s; -s here is the SEED): cafexp_hip -t TREE (-l LAMBDA | -m L1,L2,.. -y LAMBDA_TREE) --simulate [N]\n"
         "                  [-k K] [-a ALPHA] [-e ERRMODEL] [-f ROOTDIST] [-s SEED] [-o OUTDIR] [--simulate-device [--workspace BYTES]] [-d DEVICE]\n"
         "  writes OUTDIR (default results)/simulation.txt and simulation_truth.txt; N families (root sizes 0..99), or the\n"
@@ -298,6 +303,7 @@ int main(int argc, char** argv) {
         else if (a == "--estimate-gain") gain.estimate_gain = true;
         else if (a == "--root-absent") { gain.root_absent_given = true; gain.root_absent = std::stod(next()); }
         else if (a == "--gain-unconditional") gain.unconditional = true;
+        else if (a == "--gain-posterior") gain.posterior = true;
         else { usage(); return 2; }
     }
     {                                                            // the gain model: refused before anything is read or written
@@ -544,7 +550,6 @@ int main(int argc, char** argv) {
             const auto t0 = std::chrono::steady_clock::now();
             const gain_result res = fit_gain_model(score, table, L, go, [&] { return starts.initial_guesses(); });
             const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            base->set_lambda(nullptr);                           // `shape` goes with this scope
             if (out_dir.empty()) out_dir = "results";
             if (::mkdir(out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("Failed to create directory " + out_dir);
             {
@@ -564,6 +569,37 @@ int main(int argc, char** argv) {
                 g << "(absent)\t" << res.with.lnl.back() << "\n";
                 if (!g) throw std::runtime_error("Failed to write " + out_dir + "/Gain_family_likelihoods.txt");
             }
+            double posterior_s = 0;
+            gain_branch_origins origins;
+            if (gain.posterior) {                                // gain_origins.cpp: one call at the fitted rates over every distinct family
+                const auto p0 = std::chrono::steady_clock::now();
+                cladevector order;
+                d.p_tree->apply_reverse_level_order([&order](const clade* c) { order.push_back(c); });
+                const size_t n = table.family.size();
+                std::vector<double> lam, mu, nus(n * L, res.with.nu);
+                for (size_t i = 0; i < n; ++i) { lam.insert(lam.end(), res.with.lambdas.begin(), res.with.lambdas.end()); mu.insert(mu.end(), res.with.mus.begin(), res.with.mus.end()); }
+                const gain_origins go_res = base->gain_posterior(d.p_prior.get(), d.rootdist, table.family, lam, mu, nus, go.root_absent, order);
+                std::vector<std::string> names, ids;
+                size_t root = 0;
+                for (size_t v = 0; v < order.size(); ++v) { names.push_back(clade_index_or_name(order[v], order)); if (order[v]->is_root()) root = v; }
+                std::map<std::string, size_t> entry_by_counts;
+                std::vector<size_t> entry_of;
+                for (size_t i = 0, e = 0; i < d.gene_families.size(); ++i) {
+                    std::string key;
+                    for (const std::string& sp : d.gene_families[i].get_species()) key += sp + ':' + std::to_string(d.gene_families[i].get_species_size(sp)) + ',';
+                    const auto it = entry_by_counts.emplace(key, e);
+                    if (it.second) ++e;
+                    entry_of.push_back(it.first->second);
+                    ids.push_back(d.gene_families[i].id());
+                }
+                origins = gain_origin_totals(go_res, table.weight, root);
+                std::ofstream cells(out_dir + "/Gain_origins.tab"), totals(out_dir + "/Gain_branch_origins.tab");
+                write_gain_origins(cells, go_res, names, root, ids, entry_of);
+                write_gain_branch_origins(totals, origins, names, root);
+                if (!cells || !totals) throw std::runtime_error("Failed to write " + out_dir + "/Gain_origins.tab or Gain_branch_origins.tab");
+                posterior_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - p0).count();
+            }
+            base->set_lambda(nullptr);                           // `shape` goes with this scope
             auto list = [](const char* name, const std::vector<double>& v) {
                 std::printf("\"%s\": [", name);
                 for (size_t i = 0; i < v.size(); ++i) std::printf("%s%.17g", i ? ", " : "", v[i]);
@@ -577,6 +613,13 @@ int main(int argc, char** argv) {
                         res.without.neg_lnl);
             list("lambda_without_gain", res.without.lambdas); list("mu_without_gain", res.without.mus);
             list("start_without_gain", res.without.start); list("start", res.with.start);
+            if (gain.posterior) {
+                double originated = 0, lost = 0;
+                for (double v : origins.originated) originated += v;
+                for (double v : origins.lost) lost += v;
+                std::printf("\"gain_posterior_seconds\": %.3f, \"expected_origins\": %.12g, \"expected_losses\": %.12g, \"absent_at_root\": %.12g, "
+                            "\"families_with_a_likely_origin\": %.12g, ", posterior_s, originated, lost, origins.absent_at_root, origins.origin_somewhere);
+            }
             std::printf("\"lr_statistic\": %.17g, \"calls\": %d, \"max_family_size\": %d, \"max_root_family_size\": %d, \"seconds\": %.3f}\n", res.lr_statistic,
                         res.without.calls + res.with.calls, d.max_family_size, d.max_root_family_size, seconds);
             return 0;

@@ -368,6 +368,40 @@ int cafe_score_per_family_gain(cafe_ctx* ctx, const cafe_params* params, int64_t
  * no device needed.  CAFE_ERR_ARGUMENT for a negative or NaN argument or a rate * 1e9 beyond a long. */
 int cafe_bd_gain_row0(double lambda, double mu, double nu, double t, int32_t n, double* out, double out_r[1]);
 
+/* Posterior absence, origin and loss under the gain model: for entry i -- family[i] under (lambdas[i], mus[i], nus[i]), as in
+ * cafe_score_per_family_gain, whose arguments these are and whose checks apply (base model only; an error model, missing cells
+ * and CAFE_FAMILY_ABSENT are accepted; CAFE_ERR_STATE with a communicator attached; a negative or NaN nu, or root_absent
+ * outside [0, 1], is CAFE_ERR_ARGUMENT) -- and every node v of the tree,
+ *   p_absent   P(size(v) = 0 | counts)
+ *   mean       the posterior mean of size(v)
+ *   p_gain     P(size(parent(v)) = 0, size(v) >= 1 | counts): the family originated on the branch above v.  NaN at the root
+ *   p_loss     P(size(parent(v)) >= 1, size(v) = 0 | counts): the family was lost on that branch.  NaN at the root
+ *   posterior  the whole distribution of size(v), cafe_matrix_size values per node, 0 past the node's range; NULL: not wanted
+ *              (one batch of it is staged in host memory: ask for it on short family lists)
+ *   lnl        the family's lnL; NULL: not wanted
+ * Root sizes run over 0..R with mass root_absent at 0 and (1 - root_absent) * (double)prior[j-1] at j; the other nodes' sizes
+ * over 0..M.  A posterior is a ratio against the marginal likelihood, so the call uses the SUM rule always: it neither reads nor
+ * changes cafe_set_root_rule, and lnl is bit for bit cafe_score_per_family_gain's under CAFE_ROOT_SUM.  Every output is
+ * divided by the family's Z = exp(lnl).  p_gain and p_loss are computed as sums of their own, not as differences.
+ * A MISSING leaf has factor exactly 1.0 -- the row sums of the untruncated process -- and is normalised by the same Z: its
+ * p_absent and p_gain are those of the untruncated process (p_gain from 1 - P[0][0] of cafe_bd_gain_row0), its mean and
+ * posterior run over 0..M only, so its posterior sums to 1 less the mass the process puts past M.  Every other node's
+ * posterior sums to 1.
+ * An entry whose rates are invalid has lnl = -inf, one whose rates are NaN has lnl = NaN (cafe_score_per_family_gain's rule),
+ * and both have NaN in every other output; so has a family whose lnl from the device is not finite.  Arrays are indexed
+ * [entry][node] ([entry][node][size] for posterior) in the node order of cafe_problem.  A later cafe_score returns what it
+ * returned before the call. */
+typedef struct cafe_gain_posterior_out {
+    double* lnl;        /* [n]           sum-rule lnL of the family; may be NULL */
+    double* p_absent;   /* [n][n_nodes]  P(size(node) = 0 | counts) */
+    double* mean;       /* [n][n_nodes]  posterior mean size of the node */
+    double* p_gain;     /* [n][n_nodes]  P(size(parent) = 0, size(node) >= 1 | counts); NaN at the root */
+    double* p_loss;     /* [n][n_nodes]  P(size(parent) >= 1, size(node) = 0 | counts); NaN at the root */
+    double* posterior;  /* optional, NULL or [n][n_nodes][cafe_matrix_size]: the whole distribution, 0 past the node's range */
+} cafe_gain_posterior_out;
+int cafe_gain_posterior(cafe_ctx* ctx, const cafe_params* params, int64_t n, const int64_t* family, const double* lambdas,
+                        const double* mus, const double* nus, double root_absent, const cafe_gain_posterior_out* out);
+
 /* Separate birth and death rates.  The reference fits the critical process lambda = mu only; with death rates set a context
  * scores the linear birth-death process with birth rate lambdas[i] and death rate mus[i] per lineage on the branches of
  * lambda index i.  mus[n_lambdas] is copied; NULL restores lambda = mu (and the kernels that run then).  While death rates
