@@ -147,6 +147,7 @@ EXPORTS = [
     "cafe_branch_change", "cafe_debug_branch_change_band", "cafe_score_batch",
     "cafe_score_per_family_gain", "cafe_bd_gain_row0", "cafe_debug_narrowed_extents", "cafe_gain_posterior",
     "cafe_debug_pvalues_stages", "cafe_debug_sort_rows", "cafe_debug_tree_pvalue",
+    "cafe_score_gain", "cafe_debug_gain_dense",
 ]
 CAFE_CHANGE_NONE = -(1 << 31)   # mode / lo / hi of cafe_branch_change at the root and in a failed family
 CAFE_COMM_ID_BYTES = 128
@@ -227,6 +228,10 @@ def load():
     L.cafe_set_death_rates.argtypes = [C.c_void_p, _f64p]
     L.cafe_score_per_family_gain.restype = C.c_int
     L.cafe_score_per_family_gain.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p, _f64p, C.c_double, _f64p]
+    L.cafe_score_gain.restype = C.c_int
+    L.cafe_score_gain.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p, _f64p, _f64p, C.c_double, C.c_int64, _i64p, _f64p]
+    L.cafe_debug_gain_dense.restype = C.c_int
+    L.cafe_debug_gain_dense.argtypes = [C.c_void_p, _f64p, _f64p]
     L.cafe_gain_posterior.restype = C.c_int
     L.cafe_gain_posterior.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p, _f64p, C.c_double,
                                       C.POINTER(CafeGainPosteriorOut)]
@@ -558,6 +563,29 @@ class Context:
         self._check(self._lib.cafe_score_per_family_gain(self._h, C.byref(cp), len(fam), _p(fam, _i64p), _p(lam, _f64p),
                                                          None if mu is None else _p(mu, _f64p), _p(nu, _f64p), float(root_absent), _p(out, _f64p)))
         return out
+
+    def score_gain(self, pr: Params, family, lambdas, mus, nus, root_absent: float = 0.0) -> np.ndarray:
+        """cafe_score_gain: lnL of every listed family under ONE set of birth, death and gain rates (lambdas, mus and nus
+        [n_lambdas]; mus None: mu = lambda) on the dense prune: every matrix built once, the families pruned together with
+        fp64 MFMA GEMMs.  family and root_absent as in score_per_family_gain, whose values these are to rounding."""
+        fam = np.ascontiguousarray(family, dtype=np.int64).reshape(-1)
+        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(-1)
+        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(-1)
+        mu = None if mus is None else np.ascontiguousarray(mus, dtype=np.float64).reshape(-1)
+        if len(lam) != self.problem.n_lambdas or nu.shape != lam.shape or (mu is not None and mu.shape != lam.shape):
+            raise ValueError("lambdas, mus and nus must be [%d]" % self.problem.n_lambdas)
+        cp, keep = self._params(pr)
+        out = np.empty(len(fam))
+        self._check(self._lib.cafe_score_gain(self._h, C.byref(cp), _p(lam, _f64p), None if mu is None else _p(mu, _f64p), _p(nu, _f64p),
+                                              float(root_absent), len(fam), _p(fam, _i64p), _p(out, _f64p)))
+        return out
+
+    def gain_dense_profile(self):
+        """(HIP-event ms of the build, product, GEMM and root launches of the last score_gain -- 0 unless profiling was on --,
+        the flops its GEMM launches issued)"""
+        ms, flops = np.zeros(4), np.zeros(1)
+        self._check(self._lib.cafe_debug_gain_dense(self._h, _p(ms, _f64p), _p(flops, _f64p)))
+        return ms, float(flops[0])
 
     def gain_posterior(self, pr: Params, families, lambdas, mus, nus, root_absent: float = 0.0, want_posterior: bool = False) -> dict:
         """cafe_gain_posterior: under the gain model, entry i = families[i] under its own (lambdas, mus, nus)[i] (the arguments

@@ -609,6 +609,9 @@ public:
     std::vector<double> per_family_gain_lnl(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist,
                                             const std::vector<int64_t>& family, const std::vector<double>& lambdas,
                                             const std::vector<double>& mus, const std::vector<double>& nus, double root_absent);
+    // ... under ONE set of rates ([n_lambdas] each) on the dense prune: one cafe_score_gain call (--gain-dense)
+    std::vector<double> gain_lnl(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
+                                 const std::vector<double>& lambdas, const std::vector<double>& mus, double nu, double root_absent);
     // cafe_gain_posterior at the same arguments: posterior absence, origin and loss of every listed family at every node, columns
     // in `order` (gain_origins.cpp has the reports)
     struct gain_origins gain_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
@@ -1060,7 +1063,7 @@ gain_result fit_gain_model(const gain_scorer& score, const gain_table& table, in
                            const std::function<std::vector<double>()>& draw_lambdas);
 // Why the gain options cannot be combined with what else was asked for, or nullptr
 struct gain_request {
-    bool gain = false, estimate_gain = false, root_absent_given = false, unconditional = false, posterior = false;
+    bool gain = false, estimate_gain = false, root_absent_given = false, unconditional = false, posterior = false, dense = false;
     double nu = 0, root_absent = 0;
     bool gamma = false, per_family = false, gpus = false, simulate = false, pvalues = false, reconstruct = false, marginal = false, histories = false,
          standard_errors = false, events = false, rate_shift = false, leaf_predictive = false, branch_change = false, rootdist_em = false,

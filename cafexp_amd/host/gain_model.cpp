@@ -8,7 +8,8 @@
 // f over the DISTINCT families with their multiplicities w_f (sum F), lnL_absent the value of CAFE_FAMILY_ABSENT under the same
 // rates -- one device call per point lists every distinct family once and the absent profile last.  It is evaluated under the
 // SUM rule: only there is the absent profile's value a probability (the max rule's is the largest term of it), and the driver
-// sets that rule for a gain run.  --gain-unconditional drops the correction.
+// sets that rule for a gain run.  --gain-unconditional drops the correction.  --gain-dense scores every point, and the final table, by
+// cafe_score_gain instead: the same rates for every entry, each matrix built once, the families pruned together.
 //
 // The search is the Nelder-Mead of every other fit (optimizer / nm_search), over [lambdas..., mus (--estimate-mu)..., nu], nested
 // like -b --family-mu estimate: first the model without nu, then with nu from that optimum (start nu = lambda / 10, or nu held at
@@ -169,6 +170,7 @@ const char* gain_refusal(const gain_request& r) {
         if (r.root_absent_given) return "--root-absent sets the root's mass at size 0 under the gain model: give --gain NU or --estimate-gain with it";
         if (r.unconditional) return "--gain-unconditional belongs to the gain model: give --gain NU or --estimate-gain with it";
         if (r.posterior) return "--gain-posterior reports where families originated under the gain model: give --gain NU or --estimate-gain with it";
+        if (r.dense) return "--gain-dense scores the gain model's shared rates on the dense prune: give --gain NU or --estimate-gain with it";
         return nullptr;
     }
     if (r.gain && r.estimate_gain) return "--gain fixes the gain rate and --estimate-gain searches it: give one of the two";

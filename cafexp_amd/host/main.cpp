@@ -83,7 +83,7 @@ static void usage() {
         "                  [--workspace BYTES] [-o OUTDIR]   writes OUTDIR (default results)/Base_lambda_per_family.txt, one line per family\n"
         "                  [--family-mu M1[,M2,..] | --family-mu estimate]   separate death rates per family (only with -b): fixed at the given\n"
         "                  rates, one per lambda, or searched with each family's lambdas (start mu = lambda); also writes Base_mu_per_family.txt\n"
-        "gene gain rate: cafexp_hip -t TREE -i FAMILIES (--gain NU | --estimate-gain) [--root-absent P0] [--gain-unconditional] [--gain-posterior] [-l LAMBDA | -m L1,L2,..]\n"
+        "gene gain rate: cafexp_hip -t TREE -i FAMILIES (--gain NU | --estimate-gain) [--root-absent P0] [--gain-unconditional] [--gain-posterior] [--gain-dense] [-l LAMBDA | -m L1,L2,..]\n"
         "                  [-y LAMBDA_TREE] [--mu M1,.. | --estimate-mu] [-e ERRMODEL] [-p [L]] [-f ROOTDIST] [--missing TOKENS] [--mask-cells FILE] [-z] [-o OUTDIR]\n"
         "                  birth-death with immigration (n -> n+1 at rate n lambda + NU): a family absent in an ancestor can appear below it.  One set\n"
         "                  of rates for the table, fitted under the sum rule to the likelihood conditional on a family being seen in at least one\n"
@@ -91,6 +91,8 @@ static void usage() {
         "                  without NU, then with it from that optimum.  Writes OUTDIR/Gain_results.txt and Gain_family_likelihoods.txt.  -z keeps the\n"
         "                  families of one clade only, which this model is about.  Base model, one GPU; not with -k / -a, -b, --gpus, --simulate,\n"
         "                  --pvalues, a reconstruction or posterior report, or --search-batch\n"
+        "                  [--gain-dense]   score every point of the search, and the final table, by cafe_score_gain: each branch's matrix built\n"
+        "                  once per point and all distinct families pruned together by fp64 MFMA GEMMs; values agree with the default path to rounding\n"
         "                  [--gain-posterior]   after the fit, at the fitted rates: for every family and node the posterior probability that the\n"
         "                  family is absent there and its mean size, and for every branch that it originated (parent absent, node present) or was\n"
         "                  lost (parent present, node absent) on it: OUTDIR/Gain_origins.tab (p_absent:mean per node, p_gain:p_loss per branch) and\n"
@@ -304,6 +306,7 @@ int main(int argc, char** argv) {
         else if (a == "--root-absent") { gain.root_absent_given = true; gain.root_absent = std::stod(next()); }
         else if (a == "--gain-unconditional") gain.unconditional = true;
         else if (a == "--gain-posterior") gain.posterior = true;
+        else if (a == "--gain-dense") gain.dense = true;
         else { usage(); return 2; }
     }
     {                                                            // the gain model: refused before anything is read or written
@@ -542,6 +545,7 @@ int main(int argc, char** argv) {
             const std::set<double> lengths = d.p_tree->get_branch_lengths();
             lambda_optimizer starts(shape.get(), base, d.p_prior.get(), *std::max_element(lengths.begin(), lengths.end()), d.rootdist);
             const gain_scorer score = [&](const std::vector<double>& lambdas, const std::vector<double>& mus, double nu) {
+                if (gain.dense) return base->gain_lnl(d.p_prior.get(), d.rootdist, table.family, lambdas, mus, nu, go.root_absent);
                 const size_t n = table.family.size();
                 std::vector<double> lam, mu, nus(n * L, nu);
                 for (size_t i = 0; i < n; ++i) { lam.insert(lam.end(), lambdas.begin(), lambdas.end()); mu.insert(mu.end(), mus.begin(), mus.end()); }

@@ -361,6 +361,26 @@ int cafe_score_per_family_lm(cafe_ctx* ctx, const cafe_params* params, int64_t n
 #define CAFE_FAMILY_ABSENT (-1)   /* the profile with every species' count 0, whether or not the table holds it */
 int cafe_score_per_family_gain(cafe_ctx* ctx, const cafe_params* params, int64_t n, const int64_t* family,
                                const double* lambdas, const double* mus, const double* nus, double root_absent, double* family_lnl);
+/* The gain model under ONE set of rates for the whole list, on a dense prune (gain_dense.hip): lambdas, mus and nus are
+ * [n_lambdas] -- mus == NULL means mu = lambda -- and family_lnl[i] is the lnL of family[i] under them.  family[n] is
+ * cafe_score_per_family_gain's: duplicates are allowed, CAFE_FAMILY_ABSENT is the all-zero profile.  Where that entry runs the
+ * row recurrence of a branch once per (family, branch), this one builds every distinct matrix of the call once, k-major, and
+ * prunes the listed families together, one panel column per entry, level by level: a product kernel forms the panels of a
+ * level's nodes, an fp64 MFMA GEMM their factors F_v = P_v B_v, a root kernel the lnL.  The contract is that entry's: base
+ * model only; params->prior and params->error_model are read, missing cells are summed out and a missing leaf's factor is
+ * exactly 1.0; root sizes run over 0..R with mass root_absent at 0 and (1 - root_absent) * (double)prior[j-1] above, under the
+ * context's root rule; the context's death rates are not read; CAFE_ERR_STATE with a communicator attached; CAFE_ERR_ARGUMENT
+ * for a negative or NaN nu, root_absent outside [0, 1] and a family index below -1; an invalid rate set gives -inf in every
+ * entry, a NaN lambda that passes the rule NaN; a rate * 1e9 beyond a long saturates the branch (rows >= 1 zero, row 0 kept).
+ * A value depends on the family's counts and the rates only, never on its position in the list or on how the list was cut into
+ * batches (whole 128-column tiles under workspace_limit, at most CAFE_PER_FAMILY_BATCH entries).  Values agree with
+ * cafe_score_per_family_gain's to rounding, not bit for bit: a GEMM sums in another order.  cafe_family_results is not
+ * meaningful after this call; a later cafe_score returns what it returned before. */
+int cafe_score_gain(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus,
+                    double root_absent, int64_t n, const int64_t* family, double* family_lnl);
+/* The last cafe_score_gain: summed HIP-event ms of its build, product, GEMM and root launches (0 unless cafe_set_profiling was
+ * on) and the flops its GEMM launches issued. */
+int cafe_debug_gain_dense(cafe_ctx* ctx, double ms[4], double* flops);
 /* Row 0 of the gain model's matrix for the key (lambda, mu, nu, t): the three rates quantized like a lambda, t like a branch
  * length, alpha and beta cafe_bd_rates'.  out[k] = C(r+k-1, k) (1-beta)^r beta^k, k < n, r = nu / lambda (written to out_r[0]
  * unless out_r is NULL; +inf for lambda = 0 < nu).  nu = 0 gives exactly e_0.  lambda = 0 < nu is the limit r -> inf, beta -> 0:
