@@ -148,6 +148,7 @@ EXPORTS = [
     "cafe_score_per_family_gain", "cafe_bd_gain_row0", "cafe_debug_narrowed_extents", "cafe_gain_posterior",
     "cafe_debug_pvalues_stages", "cafe_debug_sort_rows", "cafe_debug_tree_pvalue",
     "cafe_score_gain", "cafe_debug_gain_dense",
+    "cafe_gain_posterior_dense", "cafe_debug_gain_dense_posterior",
 ]
 CAFE_CHANGE_NONE = -(1 << 31)   # mode / lo / hi of cafe_branch_change at the root and in a failed family
 CAFE_COMM_ID_BYTES = 128
@@ -235,6 +236,11 @@ def load():
     L.cafe_gain_posterior.restype = C.c_int
     L.cafe_gain_posterior.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p, _f64p, C.c_double,
                                       C.POINTER(CafeGainPosteriorOut)]
+    L.cafe_gain_posterior_dense.restype = C.c_int
+    L.cafe_gain_posterior_dense.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p, _f64p, _f64p, C.c_double, C.c_int64, _i64p,
+                                            C.POINTER(CafeGainPosteriorOut)]
+    L.cafe_debug_gain_dense_posterior.restype = C.c_int
+    L.cafe_debug_gain_dense_posterior.argtypes = [C.c_void_p, _f64p, _f64p]
     L.cafe_bd_gain_row0.restype = C.c_int
     L.cafe_bd_gain_row0.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _f64p, _f64p]
     L.cafe_bd_rates.restype = C.c_int
@@ -610,6 +616,36 @@ class Context:
         self._check(self._lib.cafe_gain_posterior(self._h, C.byref(cp), n, _p(fam, _i64p), _p(lam, _f64p), None if mu is None else _p(mu, _f64p),
                                                   _p(nu, _f64p), float(root_absent), C.byref(out)))
         return res
+
+    def gain_posterior_dense(self, pr: Params, families, lambdas, mus, nus, root_absent: float = 0.0, want_posterior: bool = False) -> dict:
+        """cafe_gain_posterior_dense: gain_posterior's dict for every listed family under ONE set of rates (lambdas, mus and nus
+        [n_lambdas]; mus None: mu = lambda), on score_gain's dense prune and a down pass of fp64 MFMA GEMMs over the transposed
+        matrices.  lnl is score_gain's under the sum rule bit for bit; the other values are gain_posterior's to rounding."""
+        fam = np.ascontiguousarray(families, dtype=np.int64).reshape(-1)
+        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(-1)
+        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(-1)
+        mu = None if mus is None else np.ascontiguousarray(mus, dtype=np.float64).reshape(-1)
+        if len(lam) != self.problem.n_lambdas or nu.shape != lam.shape or (mu is not None and mu.shape != lam.shape):
+            raise ValueError("lambdas, mus and nus must be [%d]" % self.problem.n_lambdas)
+        cp, keep = self._params(pr)
+        n, nodes = len(fam), self.problem.n_nodes
+        res = {"lnl": np.empty(n), "p_absent": np.empty((n, nodes)), "mean": np.empty((n, nodes)), "p_gain": np.empty((n, nodes)),
+               "p_loss": np.empty((n, nodes))}
+        if want_posterior:
+            res["posterior"] = np.empty((n, nodes, self.problem.matrix_size))
+        out = CafeGainPosteriorOut()
+        for name, array in res.items():
+            setattr(out, name, _p(array, _f64p))
+        self._check(self._lib.cafe_gain_posterior_dense(self._h, C.byref(cp), _p(lam, _f64p), None if mu is None else _p(mu, _f64p), _p(nu, _f64p),
+                                                        float(root_absent), n, _p(fam, _i64p), C.byref(out)))
+        return res
+
+    def gain_dense_posterior_profile(self):
+        """(HIP-event ms of the build, product, GEMM, root, weights, transposed GEMM, interior output and leaf output launches of
+        the last gain_posterior_dense -- 0 unless profiling was on --, the flops its two GEMMs issued)"""
+        ms, flops = np.zeros(8), np.zeros(1)
+        self._check(self._lib.cafe_debug_gain_dense_posterior(self._h, _p(ms, _f64p), _p(flops, _f64p)))
+        return ms, float(flops[0])
 
     def marginal_reconstruct(self, pr: Params, level: float = 0.95, alpha: float = 1.0) -> dict:
         """cafe_marginal_reconstruct: posterior size of every node under the scorer's model with pr's lambdas, categories,

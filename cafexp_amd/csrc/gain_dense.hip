@@ -15,6 +15,10 @@
 //
 // Plain fp64, no rescaling.  A column's value is computed by the same operations in the same order wherever the column
 // stands, so it depends on the family's counts and the rates only: not on its position, not on the batch cut.
+//
+// cafe_gain_posterior_dense: the same up pass with the sum rule forced, then the other half of the sum-product on the panels it
+// left -- by depth from the root a weights kernel, an MFMA GEMM over the matrices as stored (P^T), and the output kernels of
+// the interior nodes and of the leaves ("down" below).  Both entries run gain_dense_impl.
 #include <map>
 #include <utility>
 
@@ -106,19 +110,13 @@ struct GainProdArgs {
 
 constexpr int kGdProdRows = 16;
 
-// grid (column blocks of 256, row blocks of 16, nodes of the level); a thread owns one column and 16 sizes
-__global__ __launch_bounds__(256) void gain_dense_product_kernel(const GainProdArgs a) {
-    const GainProdOp op = a.ops[blockIdx.z];
-    const int i0 = blockIdx.y * kGdProdRows;
-    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i0 >= op.rows || f >= a.ncols) return;
-    const int n = min(kGdProdRows, op.rows - i0);
-    const int64_t col = a.col[f];
-    double v[kGdProdRows];
-#pragma unroll
-    for (int j = 0; j < kGdProdRows; ++j) v[j] = 1.0;
-    for (int k = 0; k < op.n_children; ++k) {
-        const GainChild ch = a.children[op.child0 + k];
+// v[j] *= the factor of every listed child at parent size i0 + j, children in list order: an interior child's F panel, a leaf's
+// gather from its matrix (taps ascending; a missing cell exactly 1.0; a count past M 0).  The product kernel's body, and the
+// sibling product of the down pass's weights.
+__device__ __forceinline__ void gain_dense_times_children(const GainProdArgs& a, int child0, int n_children, int i0, int n, int64_t f, int64_t col,
+                                                          double (&v)[kGdProdRows]) {
+    for (int k = 0; k < n_children; ++k) {
+        const GainChild ch = a.children[child0 + k];
         if (ch.taxon < 0) {
             const double* __restrict__ F = a.panels + ch.src + (int64_t)i0 * a.ld + f;
 #pragma unroll
@@ -153,6 +151,19 @@ __global__ __launch_bounds__(256) void gain_dense_product_kernel(const GainProdA
             for (int j = 0; j < kGdProdRows; ++j) v[j] *= fac[j];
         }
     }
+}
+
+// grid (column blocks of 256, row blocks of 16, nodes of the level); a thread owns one column and 16 sizes
+__global__ __launch_bounds__(256) void gain_dense_product_kernel(const GainProdArgs a) {
+    const GainProdOp op = a.ops[blockIdx.z];
+    const int i0 = blockIdx.y * kGdProdRows;
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i0 >= op.rows || f >= a.ncols) return;
+    const int n = min(kGdProdRows, op.rows - i0);
+    double v[kGdProdRows];
+#pragma unroll
+    for (int j = 0; j < kGdProdRows; ++j) v[j] = 1.0;
+    gain_dense_times_children(a, op.child0, op.n_children, i0, n, f, a.col[f], v);
     double* __restrict__ dst = a.panels + op.dst + (int64_t)i0 * a.ld + f;
 #pragma unroll
     for (int j = 0; j < kGdProdRows; ++j)
@@ -287,8 +298,297 @@ __global__ __launch_bounds__(256) void gain_dense_root_kernel(const GainRootArgs
     if (y == 0) a.out[f] = a.sum_rule ? m + log((red[0][x] + red[1][x]) + (red[2][x] + red[3][x])) : m;
 }
 
+// ------------------------------------------------------------------------------------------------------- down: weights
+// cafe_gain_posterior_dense goes on where the root kernel stops, by DEPTH from the root (a branch is ready when its parent's
+// outside vector is).  w_u[s][f] = outside_parent[s][f] * prod_{siblings v != u} factor_v[s][f], s < rows(u): what the rest of
+// the tree says of the parent's size s.  The root's outside vector is the mass.  The product kernel's layout and its factors.
+struct GainWeightOp {
+    int64_t dst;                     // w panel of the node (doubles from `panels`)
+    int64_t outside;                 // the parent's outside panel; -1: the parent is the root, its outside vector is `mass`
+    int32_t rows;                    // R + 1 under the root, M + 1 below
+    int32_t child0, n_children;      // the siblings, in child order
+    int32_t pad;
+};
+struct GainWeightArgs {
+    GainProdArgs p;                  // (its ops are not read)
+    const GainWeightOp* ops;
+    const double* mass;              // [R + 1] root_absent, (1 - root_absent) (double)(float)prior[j - 1]
+};
+
+// grid (column blocks of 256, row blocks of 16, nodes of the depth)
+__global__ __launch_bounds__(256) void gain_posterior_dense_weights_kernel(const GainWeightArgs a) {
+    const GainWeightOp op = a.ops[blockIdx.z];
+    const int i0 = blockIdx.y * kGdProdRows;
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i0 >= op.rows || f >= a.p.ncols) return;
+    const int n = min(kGdProdRows, op.rows - i0);
+    double v[kGdProdRows];
+#pragma unroll
+    for (int j = 0; j < kGdProdRows; ++j) v[j] = 0.0;
+    if (op.outside < 0) {
+#pragma unroll
+        for (int j = 0; j < kGdProdRows; ++j)
+            if (j < n) v[j] = a.mass[i0 + j];
+    } else {
+        const double* __restrict__ O = a.p.panels + op.outside + (int64_t)i0 * a.p.ld + f;
+#pragma unroll
+        for (int j = 0; j < kGdProdRows; ++j)
+            if (j < n) v[j] = O[(int64_t)j * a.p.ld];
+    }
+    gain_dense_times_children(a.p, op.child0, op.n_children, i0, n, f, a.p.col[f], v);
+    double* __restrict__ dst = a.p.panels + op.dst + (int64_t)i0 * a.p.ld + f;
+#pragma unroll
+    for (int j = 0; j < kGdProdRows; ++j)
+        if (j < n) dst[(int64_t)j * a.p.ld] = v[j];
+}
+
+// ----------------------------------------------------------------------------------------------- down: transposed GEMM
+// outside_u[c][f] = sum_{s < rows(u)} P_u[s][c] w_u[s][f], c = 0..M: A[c][s] = Pt[c * ldp + s] is the matrix AS STORED, the
+// contraction index contiguous.  The tile, the waves, the fragment maps, the two buffer pairs and the B staging are the up
+// GEMM's; the A staging is its own.  Thread t loads four consecutive k of row t >> 2 (two aligned double2: ldp is even, K steps
+// are multiples of 16), so four neighbouring lanes cover the 128 bytes of a row and a wave 16 rows.  The LDS tile stays
+// k-major for the fragment maps, so the store is the transposing step: lane (row, q = t & 3) writes As[4 q + e][row], e = 0..3.
+// With the plain k * 80 + row the four q of a half-wave would meet in the same banks (4 * 80 = 0 mod 32 doubles): the row
+// index is XORed with q << 3, which sends the 8 rows x 4 q of a half-wave to 32 different doubles.  The swizzle is constant over
+// the four k of a fragment step (k >> 2 = s4) and permutes rows inside aligned groups of 32, so a fragment read still finds
+// 16 consecutive doubles per k, and its two k of a half-wave 16 doubles apart (80 = 16 mod 32): neither side serialises.
+// The contraction length is the op's (R + 1 and M + 1 meet in one launch); every load is guarded, c <= M and s < rows(u).
+struct GainGemmTOp {
+    int64_t Pt, W, O;                // matrix (doubles from `mats`), w and outside panels (doubles from `panels`)
+    int32_t nk;                      // contraction over s = 0..nk-1
+    int32_t pad;
+};
+struct GainGemmTArgs {
+    const GainGemmTOp* ops;
+    const double* mats;
+    double* panels;
+    int64_t ld;
+    int32_t nr, ldp;                 // rows c = 0..nr-1 of the outside panel
+};
+
+// grid (column tiles, row tiles of M + 1, interior non-root nodes of the depth)
+__global__ __launch_bounds__(256) void gain_posterior_dense_gemm_t_kernel(const GainGemmTArgs a) {
+    __shared__ __attribute__((aligned(16))) double As[2][kGdKT * kGdLdA];
+    __shared__ __attribute__((aligned(16))) double Xs[2][kGdKT * kGdLdX];
+    const GainGemmTOp op = a.ops[blockIdx.z];
+    const int r0 = blockIdx.y * kGdMT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const int arow = tid >> 2, aq = tid & 3;           // A staging: row of the tile, quad of k
+    const int64_t c0 = (int64_t)blockIdx.x * kGdCols, ld = a.ld;
+    const int nr = a.nr, nk = op.nk, ldp = a.ldp;
+    const double* __restrict__ Pt = a.mats + op.Pt + (int64_t)(r0 + arow) * ldp;
+    const double* __restrict__ X = a.panels + op.W;
+    typedef double d4 __attribute__((ext_vector_type(4)));
+    d4 acc[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
+    double2 ra[2], rx[4];
+    auto load = [&](int k0) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int k = k0 + 4 * aq + 2 * h;                              // (even: k < nk <= ldp keeps k + 1 inside the row)
+            double2 v = make_double2(0.0, 0.0);
+            if (r0 + arow < nr && k < nk) {
+                v = *reinterpret_cast<const double2*>(Pt + k);
+                if (k + 1 >= nk) v.y = 0.0;
+            }
+            ra[h] = v;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = k0 + wave + 4 * u;
+            rx[u] = k < nk ? *reinterpret_cast<const double2*>(X + (int64_t)k * ld + c0 + 2 * lane) : make_double2(0.0, 0.0);
+        }
+    };
+    auto stage = [&](int buf) {
+        const int col = arow ^ (aq << 3);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            As[buf][(4 * aq + 2 * h) * kGdLdA + col] = ra[h].x;
+            As[buf][(4 * aq + 2 * h + 1) * kGdLdA + col] = ra[h].y;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) *reinterpret_cast<double2*>(&Xs[buf][(wave + 4 * u) * kGdLdX + 2 * lane]) = rx[u];
+    };
+    load(0);
+    stage(0);
+    __syncthreads();
+    int buf = 0;
+    for (int k0 = 0; k0 < nk; k0 += kGdKT, buf ^= 1) {
+        const bool more = k0 + kGdKT < nk;
+        if (more) load(k0 + kGdKT);
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            double af[4], bf[2];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) af[i] = As[buf][(4 * s4 + l4) * kGdLdA + ((16 * i + l15) ^ (s4 << 3))];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bf[j] = Xs[buf][(4 * s4 + l4) * kGdLdX + 32 * wave + 16 * j + l15];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[j], acc[i][j], 0, 0, 0);
+        }
+        if (more) stage(buf ^ 1);                      // the other pair: its readers passed the barrier of the step before
+        __syncthreads();
+    }
+    double* __restrict__ O = a.panels + op.O;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int r = r0 + 16 * i + l4 + 4 * q;
+                if (r < nr) O[(int64_t)r * ld + c0 + 32 * wave + 16 * j + l15] = acc[i][j][q];
+            }
+}
+
+// ------------------------------------------------------------------------------------------------------- down: outputs
+// Both output kernels: 64 columns per block, lanes along f, the sizes dealt to four waves and folded in a fixed order.
+// res is [4][n_nodes][ld]: p_absent, mean, p_gain, p_loss; posterior, when asked for, [n_nodes][N][ld].  Everything / Z.
+struct GainNodeOp {
+    int64_t outside, B, W, Pt;       // interior: outside (-1: the root, `mass`), B, w (-1 at the root) panels, the matrix; leaf: W, Pt
+    int32_t node;
+    int32_t n;                       // interior: the node's sizes 0..n-1 (R + 1 at the root, M + 1 below)
+    int32_t rows;                    // rows(u): the parent's sizes
+    int32_t taxon;                   // leaf: its row of `counts`
+};
+struct GainOutArgs {
+    const GainNodeOp* ops;
+    const double* mats;
+    const double* panels;
+    const double* mass;
+    const double* lnl;               // [ld] the root kernel's sum-rule lnL: Z = exp(lnl)
+    double* res;
+    double* posterior;               // or nullptr
+    const int64_t* col;
+    const int32_t* counts;
+    const double* err;
+    int64_t counts_ld, ld;
+    int32_t nn, N, M, ldp, n_dev, any_missing;
+};
+
+__device__ __forceinline__ double gain_dense_fold4(double (*red)[64], int x, int y, double v) {
+    red[y][x] = v;
+    __syncthreads();
+    const double s = (red[0][x] + red[1][x]) + (red[2][x] + red[3][x]);
+    __syncthreads();                                   // red is free again
+    return s;
+}
+
+// interior nodes, the root among them (its op has no w: p_gain and p_loss are NaN): posterior_u[c] = outside_u[c] B_u[c] / Z,
+// p_gain = w[0] sum_{c >= 1} P[0][c] B[c] / Z (row 0 is Pt[c * ldp], wave-uniform), p_loss = B[0] sum_{s >= 1} w[s] P[s][0] / Z
+// (column 0 is Pt[s]).  grid (cols / 64, interior nodes of the depth)
+__global__ __launch_bounds__(256) void gain_posterior_dense_interior_kernel(const GainOutArgs a) {
+    __shared__ double red[4][64];
+    const GainNodeOp op = a.ops[blockIdx.y];
+    const int x = threadIdx.x & 63, y = threadIdx.x >> 6;
+    const int64_t f = (int64_t)blockIdx.x * 64 + x, ld = a.ld;
+    const bool root = op.W < 0;
+    const double Z = exp(a.lnl[f]);
+    const double* __restrict__ B = a.panels + op.B + f;
+    const double* __restrict__ O = a.panels + (root ? op.B : op.outside) + f;
+    const double* __restrict__ W = a.panels + (root ? op.B : op.W) + f;
+    const double* __restrict__ Pt = a.mats + op.Pt;
+    double m = 0.0, g = 0.0, l = 0.0, p0 = 0.0;
+    for (int c = y; c < a.N; c += 4) {
+        double post = 0.0;
+        if (c < op.n) {
+            const double b = B[(int64_t)c * ld];
+            post = (root ? a.mass[c] : O[(int64_t)c * ld]) * b / Z;
+            m = fma((double)c, post, m);
+            if (!root && c >= 1) g = fma(Pt[(int64_t)c * a.ldp], b, g);
+        }
+        if (!root && c >= 1 && c < op.rows) l = fma(W[(int64_t)c * ld], Pt[c], l);
+        if (c == 0) p0 = post;
+        if (a.posterior) a.posterior[((int64_t)op.node * a.N + c) * ld + f] = post;
+    }
+    m = gain_dense_fold4(red, x, y, m);
+    g = gain_dense_fold4(red, x, y, g);
+    l = gain_dense_fold4(red, x, y, l);
+    if (y != 0) return;
+    const int64_t o = (int64_t)op.node * ld + f, k = (int64_t)a.nn * ld;
+    a.res[o] = p0;
+    a.res[o + k] = m;
+    a.res[o + 2 * k] = root ? __builtin_nan("") : W[0] * g / Z;
+    a.res[o + 3 * k] = root ? __builtin_nan("") : B[0] * l / Z;
+}
+
+// leaves, without a GEMM: L_u is non-zero at the taps of the observed count only, so outside_u is needed there only --
+// sum_s w[s] Pt[c * ldp + s], a dot along a contiguous matrix column, the product kernel's gather turned round.  The four
+// waves take a quarter of the parent's sizes each.  A MISSING leaf (L_u = 1 over 0..M; on a context created with missing cells)
+// gets the full mat-vec from its own thread group instead: wave y the sizes c = y, y + 4, .., each a whole dot.  Its p_gain is
+// w[0] (1 - P[0][0]) / Z.  A count past M made lnl -inf: nothing is read for it.  grid (cols / 64, leaves of the depth)
+__global__ __launch_bounds__(256) void gain_posterior_dense_leaf_kernel(const GainOutArgs a) {
+    __shared__ double red[4][64];
+    const GainNodeOp op = a.ops[blockIdx.y];
+    const int x = threadIdx.x & 63, y = threadIdx.x >> 6;
+    const int64_t f = (int64_t)blockIdx.x * 64 + x, ld = a.ld;
+    const double Z = exp(a.lnl[f]);
+    const int64_t col = a.col[f];
+    const int cnt = col >= 0 ? a.counts[(int64_t)op.taxon * a.counts_ld + col] : 0;
+    const bool missing = count_is_missing(cnt), in = !missing && cnt <= a.M;
+    const double* __restrict__ W = a.panels + op.W + f;
+    const double* __restrict__ Pt = a.mats + op.Pt;
+    const int chunk = (op.rows + 3) / 4, s_lo = y * chunk, s_hi = min(op.rows, s_lo + chunk);
+    double* __restrict__ po = a.posterior ? a.posterior + (int64_t)op.node * a.N * ld + f : nullptr;
+    if (po)
+        for (int c = y; c < a.N; c += 4) po[(int64_t)c * ld] = 0.0;
+    __syncthreads();                                   // the zeros stand before wave 0 writes the taps
+
+    const int n_taps = a.err ? a.n_dev : 1, lo = a.err ? cnt - (a.n_dev - 1) / 2 : cnt;
+    double p0 = 0.0, mean = 0.0, g = 0.0, L0 = missing ? 1.0 : 0.0;
+    for (int t = 0; t < n_taps; ++t) {                 // taps ascending; those outside [0, M] are dropped
+        const int c = lo + t;
+        const bool ok = in && c >= 0 && c <= a.M;
+        double part = 0.0;
+        if (ok) {
+            const double* __restrict__ pc = Pt + (int64_t)c * a.ldp;
+            for (int s = s_lo; s < s_hi; ++s) part = fma(W[(int64_t)s * ld], pc[s], part);
+        }
+        const double dot = gain_dense_fold4(red, x, y, part);
+        if (y == 0 && ok) {
+            const double wt = a.err ? a.err[(int64_t)cnt * a.n_dev + t] : 1.0;
+            const double post = dot * wt / Z;
+            if (c == 0) { p0 = post; L0 = wt; }
+            else g = fma(Pt[(int64_t)c * a.ldp], wt, g);
+            mean = fma((double)c, post, mean);
+            if (po) po[(int64_t)c * ld] = post;
+        }
+    }
+    double part = 0.0;                                 // sum_{s >= 1} w[s] P[s][0]
+    for (int s = max(s_lo, 1); s < s_hi; ++s) part = fma(W[(int64_t)s * ld], Pt[s], part);
+    const double loss = gain_dense_fold4(red, x, y, part);
+
+    if (a.any_missing) {                               // (kernel-uniform)
+        double mm = 0.0;
+        if (missing)
+            for (int c = y; c <= a.M; c += 4) {
+                const double* __restrict__ pc = Pt + (int64_t)c * a.ldp;
+                double dot = 0.0;
+                for (int s = 0; s < op.rows; ++s) dot = fma(W[(int64_t)s * ld], pc[s], dot);
+                const double post = dot / Z;
+                if (c == 0) p0 = post;
+                mm = fma((double)c, post, mm);
+                if (po) po[(int64_t)c * ld] = post;
+            }
+        mm = gain_dense_fold4(red, x, y, mm);
+        if (missing) { mean = mm; g = 1.0 - Pt[0]; }
+    }
+    if (y != 0) return;
+    const int64_t o = (int64_t)op.node * ld + f, k = (int64_t)a.nn * ld;
+    a.res[o] = p0;
+    a.res[o + k] = mean;
+    a.res[o + 2 * k] = W[0] * g / Z;
+    a.res[o + 3 * k] = L0 * loss / Z;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host
-enum { kGdBuild = 0, kGdProduct = 1, kGdGemm = 2, kGdRoot = 3 };
+enum { kGdBuild = 0, kGdProduct = 1, kGdGemm = 2, kGdRoot = 3, kGdWeights = 4, kGdGemmT = 5, kGdInterior = 6, kGdLeaf = 7, kGdKinds = 8 };
 
 // HIP events around the launches of a call, by kind (cafe_set_profiling)
 struct GainTimer {
@@ -302,7 +602,7 @@ struct GainTimer {
         ev.push_back({kind, e});
         (void)hipEventRecord(e, s);
     }
-    void collect(double ms[4]) const {
+    void collect(double* ms) const {                   // ms[kind] += its launches
         for (size_t i = 0; on && i + 1 < ev.size(); i += 2) {
             float t = 0.f;
             if (hipEventElapsedTime(&t, ev[i].second, ev[i + 1].second) == hipSuccess) ms[ev[i].first] += t;
@@ -318,9 +618,28 @@ size_t put(std::vector<char>& blob, const std::vector<T>& v) {
     return at;
 }
 
-int score_gain_impl(cafe_ctx* c, const cafe_params* pr, const double* lam, const double* mus, const double* nus, double root_absent, int64_t n,
-                    const int64_t* family, double* family_lnl) {
-    const char* const who = "cafe_score_gain";
+// The staging of one batch of the down pass's outputs and the way back to the caller's arrays
+struct GainDownHost {
+    const cafe_gain_posterior_out* out;
+    std::vector<double> res, posterior;                // [4][n_nodes][nb], [n_nodes][N][nb]
+
+    void collect(int64_t b0, int64_t nb, int nn, int N, const double* lnl) const {
+        double* const dst[4] = {out->p_absent, out->mean, out->p_gain, out->p_loss};
+        for (int64_t b = 0; b < nb; ++b) {
+            if (!std::isfinite(lnl[b])) continue;      // the entry keeps its NaN
+            for (int k = 0; k < 4; ++k)
+                for (int v = 0; v < nn; ++v) dst[k][(b0 + b) * nn + v] = res[((size_t)k * nn + v) * nb + b];
+            if (!out->posterior) continue;
+            double* po = out->posterior + (b0 + b) * nn * N;
+            for (int64_t i = 0; i < (int64_t)nn * N; ++i) po[i] = posterior[(size_t)i * nb + b];
+        }
+    }
+};
+
+// Both entries: the planning (keys, levels, op tables, workspace), the up pass launch for launch, and -- with `down`, the
+// posterior entry -- the sum rule forced at the root, the plan and the launches of the down pass behind the root kernel.
+int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const double* lam, const double* mus, const double* nus, double root_absent,
+                    int64_t n, const int64_t* family, double* family_lnl, GainDownHost* down) {
     if (!pr || !pr->prior) { set_err(c, "%s: params with a prior are required", who); return CAFE_ERR_ARGUMENT; }
     if (pr->model != CAFE_MODEL_BASE) { set_err(c, "%s: base model only", who); return CAFE_ERR_ARGUMENT; }
     if (c->comm) { set_err(c, "%s: not valid on a context with a communicator attached", who); return CAFE_ERR_STATE; }
@@ -341,8 +660,14 @@ int score_gain_impl(cafe_ctx* c, const cafe_params* pr, const double* lam, const
 
     // ---- what the host decides alone: an invalid rate set is -inf in every entry, a NaN lambda that passes the rule NaN
     c->last.state = LastCall::kNone;                   // cafe_family_results is not meaningful after this call
-    for (int k = 0; k < 4; ++k) c->gain_dense_ms[k] = 0.0;
-    c->gain_dense_flops = 0.0;
+    double ms[kGdKinds] = {0, 0, 0, 0, 0, 0, 0, 0}, flops = 0.0;
+    if (down) {
+        std::copy(ms, ms + kGdKinds, c->gain_dense_posterior_ms);
+        c->gain_dense_posterior_flops = 0.0;
+    } else {
+        std::copy(ms, ms + 4, c->gain_dense_ms);
+        c->gain_dense_flops = 0.0;
+    }
     {
         bool nan = false;
         for (int k = 0; k < L; ++k) nan = nan || std::isnan(lam[k]);
@@ -376,12 +701,36 @@ int score_gain_impl(cafe_ctx* c, const cafe_params* pr, const double* lam, const
     const int n_keys = (int)slots.size();
     const int64_t mat_stride = (int64_t)N * ldp;
 
+    // ---- the down pass: the nodes by depth (breadth first: parents in front of their children), an outside panel per interior
+    // non-root node behind the up pass's panels, the w panels of the widest depth behind those
+    std::vector<int> depth(nn, 0), by_depth{c->root}, depth_off{0}, oidx(nn, -1), widx(nn, -1);
+    int n_down = 0, n_depths = 0;
+    const bool want_posterior = down && down->out->posterior;
+    if (down) {
+        int n_out = 0, widest = 0;
+        for (size_t at = 0; at < by_depth.size(); ++at)
+            for (int ch : c->children[by_depth[at]]) { depth[ch] = depth[by_depth[at]] + 1; by_depth.push_back(ch); }
+        for (size_t at = 1; at <= by_depth.size(); ++at) {
+            if (at < by_depth.size() && depth[by_depth[at]] == depth[by_depth[at - 1]]) continue;
+            widest = std::max(widest, (int)at - depth_off.back());
+            depth_off.push_back((int)at);
+        }
+        n_depths = (int)depth_off.size() - 1;
+        for (int u : by_depth)
+            if (u != c->root && c->leaf_taxon[u] < 0) oidx[u] = n_pan + n_out++;
+        for (int d = 1; d < n_depths; ++d)
+            for (int k = depth_off[d]; k < depth_off[d + 1]; ++k) widx[by_depth[k]] = n_pan + n_out + (k - depth_off[d]);
+        n_down = n_out + widest;
+    }
+
     // ---- columns per batch: the matrices stand once, a batch adds its panels
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t fixed_bytes = sizeof(double) * (size_t)mat_stride * n_keys + ((size_t)64 << 10) + sizeof(GainChild) * (size_t)nn +
                                sizeof(GainProdOp) * (size_t)nn + sizeof(GainGemmOp) * (size_t)nn + sizeof(SlotParamGain) * (size_t)n_keys +
-                               sizeof(double) * ((size_t)R + 1 + (size_t)(M + 1) * c->n_dev);
-    const size_t column_bytes = sizeof(double) * (size_t)n_pan * N + sizeof(int64_t) + sizeof(double);
+                               sizeof(double) * ((size_t)R + 1 + (size_t)(M + 1) * c->n_dev) +
+                               (down ? (sizeof(GainChild) + sizeof(GainWeightOp) + sizeof(GainGemmTOp) + sizeof(GainNodeOp)) * (size_t)nn + sizeof(double) * ((size_t)R + 1) : 0);
+    const size_t column_bytes = sizeof(double) * (size_t)n_pan * N + sizeof(int64_t) + sizeof(double) +
+                                (down ? sizeof(double) * ((size_t)n_down * N + 4 * (size_t)nn + (want_posterior ? (size_t)nn * N : 0)) : 0);
     size_t budget = 0;
     HIP_TRY(c, workspace_budget(c->workspace_limit, c->pf_dev_bytes, &budget));
     int64_t entries = budget > fixed_bytes ? (int64_t)((budget - fixed_bytes) / column_bytes) / kGdCols * kGdCols : 0;
@@ -417,6 +766,48 @@ int score_gain_impl(cafe_ctx* c, const cafe_params* pr, const double* lam, const
         prod_off.push_back((int)prod_ops.size()); gemm_off.push_back((int)gemm_ops.size());
         prod_rows.push_back(pr_rows); gemm_rows.push_back(gm_rows);
     }
+    // the down pass's tables, depth by depth: the weights of every node, the transposed GEMM and the outputs of the interior ones
+    // (depth 0: the root's outputs alone), the outputs of the leaves
+    std::vector<GainWeightOp> weight_ops;
+    std::vector<GainGemmTOp> gemmt_ops;
+    std::vector<GainNodeOp> int_ops, leaf_ops;
+    std::vector<int> weight_off{0}, gemmt_off{0}, int_off{0}, leaf_off{0}, weight_rows;
+    for (int d = 0; d < n_depths; ++d) {
+        int w_rows = 0;
+        for (int k = depth_off[d]; k < depth_off[d + 1]; ++k) {
+            const int u = by_depth[k], p = c->parent[u];
+            if (u == c->root) {
+                int_ops.push_back({-1, bidx[u] * pan_stride, -1, 0, u, R + 1, 0, -1});
+                continue;
+            }
+            const int rows = (p == c->root ? R : M) + 1;
+            GainWeightOp wo{widx[u] * pan_stride, p == c->root ? -1 : oidx[p] * pan_stride, rows, (int32_t)children.size(), 0, 0};
+            for (int sib : c->children[p]) {
+                if (sib == u) continue;
+                const bool leaf = c->leaf_taxon[sib] >= 0;
+                children.push_back({leaf ? node_key[sib] * mat_stride : fidx[sib] * pan_stride, leaf ? c->leaf_taxon[sib] : -1, 0});
+            }
+            wo.n_children = (int32_t)children.size() - wo.child0;
+            weight_ops.push_back(wo);
+            w_rows = std::max(w_rows, rows);
+            if (c->leaf_taxon[u] >= 0) {
+                leaf_ops.push_back({-1, -1, widx[u] * pan_stride, node_key[u] * mat_stride, u, M + 1, rows, c->leaf_taxon[u]});
+                continue;
+            }
+            gemmt_ops.push_back({node_key[u] * mat_stride, widx[u] * pan_stride, oidx[u] * pan_stride, rows, 0});
+            int_ops.push_back({oidx[u] * pan_stride, bidx[u] * pan_stride, widx[u] * pan_stride, node_key[u] * mat_stride, u, M + 1, rows, -1});
+        }
+        weight_off.push_back((int)weight_ops.size()); gemmt_off.push_back((int)gemmt_ops.size());
+        int_off.push_back((int)int_ops.size()); leaf_off.push_back((int)leaf_ops.size());
+        weight_rows.push_back(w_rows);
+    }
+    std::vector<double> mass;                          // the root's outside vector, beside logmass
+    if (down) {
+        mass.resize((size_t)R + 1);
+        mass[0] = root_absent;
+        for (int j = 1; j <= R; ++j) mass[j] = (1.0 - root_absent) * (double)pr->prior[j - 1];
+    }
+
     std::vector<double> reals((size_t)R + 1 + (size_t)(M + 1) * c->n_dev);  // log mass of the root sizes, error model
     reals[0] = std::log(root_absent);
     for (int j = 0; j < R; ++j) reals[j + 1] = std::log1p(-root_absent) + std::log((double)pr->prior[j]);    // compute() returns float
@@ -424,10 +815,13 @@ int score_gain_impl(cafe_ctx* c, const cafe_params* pr, const double* lam, const
 
     std::vector<char> blob;
     const size_t o_children = put(blob, children), o_prod = put(blob, prod_ops), o_gemm = put(blob, gemm_ops), o_slots = put(blob, slots),
-                 o_reals = put(blob, reals);
+                 o_reals = put(blob, reals), o_weight = put(blob, weight_ops), o_gemmt = put(blob, gemmt_ops), o_int = put(blob, int_ops),
+                 o_leaf = put(blob, leaf_ops), o_mass = put(blob, mass);
     const size_t o_col = family_align_up(blob.size()), o_out = o_col + family_align_up(sizeof(int64_t) * ld),
                  o_mats = o_out + family_align_up(sizeof(double) * ld), o_pan = o_mats + family_align_up(sizeof(double) * (size_t)mat_stride * n_keys),
-                 need = o_pan + sizeof(double) * (size_t)pan_stride * n_pan;
+                 o_res = o_pan + sizeof(double) * (size_t)pan_stride * (n_pan + n_down),
+                 o_post = o_res + (down ? sizeof(double) * 4 * (size_t)nn * ld : 0),
+                 need = o_post + (want_posterior ? sizeof(double) * (size_t)nn * N * ld : 0);
     if (need > c->pf_dev_bytes) {
         if (c->pf_dev) { HIP_TRY(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->pf_dev); c->pf_dev = nullptr; c->pf_dev_bytes = 0; }
         if (hipMalloc(&c->pf_dev, need) != hipSuccess) {
@@ -459,7 +853,19 @@ int score_gain_impl(cafe_ctx* c, const cafe_params* pr, const double* lam, const
     pa.err = c->n_dev > 0 ? d_reals + R + 1 : nullptr;
     pa.n_dev = c->n_dev; pa.M = M; pa.ldp = ldp;
     GainGemmArgs ga{reinterpret_cast<const GainGemmOp*>(base + o_gemm), mats, panels, ld, M + 1, ldp};
-    GainRootArgs ra{panels + bidx[c->root] * pan_stride, d_reals, reinterpret_cast<double*>(base + o_out), ld, R, c->root_rule == CAFE_ROOT_SUM ? 1 : 0};
+    GainRootArgs ra{panels + bidx[c->root] * pan_stride, d_reals, reinterpret_cast<double*>(base + o_out), ld, R,
+                    down || c->root_rule == CAFE_ROOT_SUM ? 1 : 0};
+    GainWeightArgs wa{pa, reinterpret_cast<const GainWeightOp*>(base + o_weight), reinterpret_cast<const double*>(base + o_mass)};
+    GainGemmTArgs ta{reinterpret_cast<const GainGemmTOp*>(base + o_gemmt), mats, panels, ld, M + 1, ldp};
+    GainOutArgs oa{};
+    oa.mats = mats; oa.panels = panels; oa.mass = wa.mass; oa.lnl = ra.out;
+    oa.res = reinterpret_cast<double*>(base + o_res); oa.posterior = want_posterior ? reinterpret_cast<double*>(base + o_post) : nullptr;
+    oa.col = pa.col; oa.counts = pa.counts; oa.err = pa.err; oa.counts_ld = pa.counts_ld; oa.ld = ld;
+    oa.nn = nn; oa.N = N; oa.M = M; oa.ldp = ldp; oa.n_dev = c->n_dev; oa.any_missing = c->has_missing ? 1 : 0;
+    if (down) {
+        down->res.resize(4 * (size_t)nn * entries);
+        if (want_posterior) down->posterior.resize((size_t)nn * N * entries);
+    }
 
     std::vector<int64_t> col((size_t)ld);
     std::vector<double> res((size_t)ld);
@@ -484,16 +890,61 @@ int score_gain_impl(cafe_ctx* c, const cafe_params* pr, const double* lam, const
             CAFE_LAUNCH(c, gain_dense_gemm_kernel, dim3(tiles, (unsigned)((gemm_rows[lv] + kGdMT - 1) / kGdMT), (unsigned)ng), dim3(256), 0, s, g);
             timer.mark(kGdGemm, s);
             for (int k = gemm_off[lv]; k < gemm_off[lv + 1]; ++k)
-                c->gain_dense_flops += 2.0 * round_up(gemm_ops[k].nr, kGdMT) * (double)round_up(M + 1, kGdKT) * (double)cols;
+                flops += 2.0 * round_up(gemm_ops[k].nr, kGdMT) * (double)round_up(M + 1, kGdKT) * (double)cols;
         }
         timer.mark(kGdRoot, s);
         CAFE_LAUNCH(c, gain_dense_root_kernel, dim3((unsigned)(cols / 64)), dim3(256), 0, s, ra);
         timer.mark(kGdRoot, s);
         HIP_TRY(c, hipMemcpyAsync(res.data(), base + o_out, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
+        for (int d = 0; d < n_depths; ++d) {           // the down pass: every B and F panel of the batch is still in place
+            const int nw = weight_off[d + 1] - weight_off[d], nt = gemmt_off[d + 1] - gemmt_off[d], ni = int_off[d + 1] - int_off[d],
+                      nl = leaf_off[d + 1] - leaf_off[d];
+            if (nw > 0) {
+                GainWeightArgs w = wa;
+                w.ops += weight_off[d];
+                w.p.ncols = cols;
+                timer.mark(kGdWeights, s);
+                CAFE_LAUNCH(c, gain_posterior_dense_weights_kernel,
+                            dim3((unsigned)((cols + 255) / 256), (unsigned)((weight_rows[d] + kGdProdRows - 1) / kGdProdRows), (unsigned)nw), dim3(256), 0, s, w);
+                timer.mark(kGdWeights, s);
+            }
+            if (nt > 0) {
+                GainGemmTArgs t = ta;
+                t.ops += gemmt_off[d];
+                timer.mark(kGdGemmT, s);
+                CAFE_LAUNCH(c, gain_posterior_dense_gemm_t_kernel, dim3(tiles, (unsigned)((M + kGdMT) / kGdMT), (unsigned)nt), dim3(256), 0, s, t);
+                timer.mark(kGdGemmT, s);
+                for (int k = gemmt_off[d]; k < gemmt_off[d + 1]; ++k)
+                    flops += 2.0 * round_up(M + 1, kGdMT) * (double)round_up(gemmt_ops[k].nk, kGdKT) * (double)cols;
+            }
+            GainOutArgs o = oa;
+            if (ni > 0) {
+                o.ops = reinterpret_cast<const GainNodeOp*>(base + o_int) + int_off[d];
+                timer.mark(kGdInterior, s);
+                CAFE_LAUNCH(c, gain_posterior_dense_interior_kernel, dim3((unsigned)(cols / 64), (unsigned)ni), dim3(256), 0, s, o);
+                timer.mark(kGdInterior, s);
+            }
+            if (nl > 0) {
+                o.ops = reinterpret_cast<const GainNodeOp*>(base + o_leaf) + leaf_off[d];
+                timer.mark(kGdLeaf, s);
+                CAFE_LAUNCH(c, gain_posterior_dense_leaf_kernel, dim3((unsigned)(cols / 64), (unsigned)nl), dim3(256), 0, s, o);
+                timer.mark(kGdLeaf, s);
+            }
+        }
+        if (down) {                                    // [rows][ld] on the device, [rows][nb] on the host
+            HIP_TRY(c, hipMemcpy2DAsync(down->res.data(), sizeof(double) * nb, oa.res, sizeof(double) * ld, sizeof(double) * nb, 4 * (size_t)nn,
+                                        hipMemcpyDeviceToHost, s));
+            if (want_posterior)
+                HIP_TRY(c, hipMemcpy2DAsync(down->posterior.data(), sizeof(double) * nb, oa.posterior, sizeof(double) * ld, sizeof(double) * nb, (size_t)nn * N,
+                                            hipMemcpyDeviceToHost, s));
+        }
         HIP_TRY(c, hipStreamSynchronize(s));            // the host tables of this batch go out of use
         std::copy(res.begin(), res.begin() + nb, family_lnl + b0);
+        if (down) down->collect(b0, nb, nn, N, res.data());
     }
-    timer.collect(c->gain_dense_ms);
+    timer.collect(ms);
+    std::copy(ms, ms + (down ? (int)kGdKinds : 4), down ? c->gain_dense_posterior_ms : c->gain_dense_ms);
+    (down ? c->gain_dense_posterior_flops : c->gain_dense_flops) = flops;
     return CAFE_OK;
 }
 
@@ -502,7 +953,8 @@ int score_gain_impl(cafe_ctx* c, const cafe_params* pr, const double* lam, const
 
 int cafe_score_gain(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus, double root_absent, int64_t n,
                     const int64_t* family, double* family_lnl) {
-    const int rc = cafe::guarded(ctx, "cafe_score_gain", [&] { return cafe::score_gain_impl(ctx, params, lambdas, mus, nus, root_absent, n, family, family_lnl); });
+    const int rc = cafe::guarded(ctx, "cafe_score_gain",
+                                 [&] { return cafe::gain_dense_impl(ctx, "cafe_score_gain", params, lambdas, mus, nus, root_absent, n, family, family_lnl, nullptr); });
     if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
     return rc;
 }
@@ -511,5 +963,36 @@ int cafe_debug_gain_dense(cafe_ctx* ctx, double ms[4], double* flops) {
     if (!ctx) return CAFE_ERR_ARGUMENT;
     for (int k = 0; ms && k < 4; ++k) ms[k] = ctx->gain_dense_ms[k];
     if (flops) *flops = ctx->gain_dense_flops;
+    return CAFE_OK;
+}
+
+int cafe_gain_posterior_dense(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus, double root_absent,
+                              int64_t n, const int64_t* family, const cafe_gain_posterior_out* out) {
+    const char* const who = "cafe_gain_posterior_dense";
+    const int rc = cafe::guarded(ctx, who, [&] {
+        if (!out || (n > 0 && (!out->p_absent || !out->mean || !out->p_gain || !out->p_loss))) {
+            cafe::set_err(ctx, "%s: out with p_absent, mean, p_gain and p_loss is required", who);
+            return (int)CAFE_ERR_ARGUMENT;
+        }
+        std::vector<double> own_lnl;
+        double* lnl = out->lnl;
+        if (!lnl && n > 0) { own_lnl.resize((size_t)n); lnl = own_lnl.data(); }
+        if (n > 0) {                                   // what no finite lnl replaces
+            const size_t nodes = (size_t)n * ctx->n_nodes;
+            const double nan = std::numeric_limits<double>::quiet_NaN();
+            for (double* p : {out->p_absent, out->mean, out->p_gain, out->p_loss}) std::fill(p, p + nodes, nan);
+            if (out->posterior) std::fill(out->posterior, out->posterior + nodes * ctx->N, nan);
+        }
+        cafe::GainDownHost down{out, {}, {}};
+        return cafe::gain_dense_impl(ctx, who, params, lambdas, mus, nus, root_absent, n, family, lnl, &down);
+    });
+    if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
+    return rc;
+}
+
+int cafe_debug_gain_dense_posterior(cafe_ctx* ctx, double ms[8], double* flops) {
+    if (!ctx) return CAFE_ERR_ARGUMENT;
+    for (int k = 0; ms && k < 8; ++k) ms[k] = ctx->gain_dense_posterior_ms[k];
+    if (flops) *flops = ctx->gain_dense_posterior_flops;
     return CAFE_OK;
 }

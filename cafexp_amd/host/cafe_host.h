@@ -613,10 +613,11 @@ public:
     std::vector<double> gain_lnl(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
                                  const std::vector<double>& lambdas, const std::vector<double>& mus, double nu, double root_absent);
     // cafe_gain_posterior at the same arguments: posterior absence, origin and loss of every listed family at every node, columns
-    // in `order` (gain_origins.cpp has the reports)
+    // in `order` (gain_origins.cpp has the reports).  dense: ONE set of rates ([n_lambdas] each) for the whole list, one
+    // cafe_gain_posterior_dense call (--gain-dense)
     struct gain_origins gain_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
                                        const std::vector<double>& lambdas, const std::vector<double>& mus, const std::vector<double>& nus,
-                                       double root_absent, const std::vector<const clade*>& order);
+                                       double root_absent, const std::vector<const clade*>& order, bool dense = false);
 };
 class hip_gamma_model : public hip_model_base {
     std::vector<double> _lambda_multipliers, _gamma_cat_probs;

@@ -296,7 +296,7 @@ std::vector<double> hip_base_model::gain_lnl(root_equilibrium_distribution* prio
 
 gain_origins hip_base_model::gain_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
                                             const std::vector<double>& lambdas, const std::vector<double>& mus, const std::vector<double>& nus,
-                                            double root_absent, const std::vector<const clade*>& order) {
+                                            double root_absent, const std::vector<const clade*>& order, bool dense) {
     ensure_context(1);
     std::vector<float> prior_f;
     std::vector<double> err, unused;
@@ -312,7 +312,10 @@ gain_origins hip_base_model::gain_posterior(root_equilibrium_distribution* prior
     res.lnl.resize(F);
     cafe_gain_posterior_out out{};
     out.lnl = res.lnl.data(); out.p_absent = p_absent.data(); out.mean = mean.data(); out.p_gain = p_gain.data(); out.p_loss = p_loss.data();
-    if (cafe_gain_posterior(_ctx, &pr, (int64_t)F, family.data(), lambdas.data(), mus.data(), nus.data(), root_absent, &out) != CAFE_OK)
+    if (dense) {
+        if (cafe_gain_posterior_dense(_ctx, &pr, lambdas.data(), mus.data(), nus.data(), root_absent, (int64_t)F, family.data(), &out) != CAFE_OK)
+            throw std::runtime_error(std::string("cafe_gain_posterior_dense: ") + cafe_last_error(_ctx));
+    } else if (cafe_gain_posterior(_ctx, &pr, (int64_t)F, family.data(), lambdas.data(), mus.data(), nus.data(), root_absent, &out) != CAFE_OK)
         throw std::runtime_error(std::string("cafe_gain_posterior: ") + cafe_last_error(_ctx));
     std::map<const clade*, size_t> pos;
     for (size_t v = 0; v < n; ++v) pos[_order[v]] = v;

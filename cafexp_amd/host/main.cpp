@@ -92,7 +92,8 @@ static void usage() {
         "                  families of one clade only, which this model is about.  Base model, one GPU; not with -k / -a, -b, --gpus, --simulate,\n"
         "                  --pvalues, a reconstruction or posterior report, or --search-batch\n"
         "                  [--gain-dense]   score every point of the search, and the final table, by cafe_score_gain: each branch's matrix built\n"
-        "                  once per point and all distinct families pruned together by fp64 MFMA GEMMs; values agree with the default path to rounding\n"
+        "                  once per point and all distinct families pruned together by fp64 MFMA GEMMs; values agree with the default path to rounding;\n"
+        "                  with --gain-posterior the posterior runs on the same prune, by cafe_gain_posterior_dense\n"
         "                  [--gain-posterior]   after the fit, at the fitted rates: for every family and node the posterior probability that the\n"
         "                  family is absent there and its mean size, and for every branch that it originated (parent absent, node present) or was\n"
         "                  lost (parent present, node absent) on it: OUTDIR/Gain_origins.tab (p_absent:mean per node, p_gain:p_loss per branch) and\n"
@@ -580,9 +581,10 @@ int main(int argc, char** argv) {
                 cladevector order;
                 d.p_tree->apply_reverse_level_order([&order](const clade* c) { order.push_back(c); });
                 const size_t n = table.family.size();
-                std::vector<double> lam, mu, nus(n * L, res.with.nu);
-                for (size_t i = 0; i < n; ++i) { lam.insert(lam.end(), res.with.lambdas.begin(), res.with.lambdas.end()); mu.insert(mu.end(), res.with.mus.begin(), res.with.mus.end()); }
-                const gain_origins go_res = base->gain_posterior(d.p_prior.get(), d.rootdist, table.family, lam, mu, nus, go.root_absent, order);
+                const size_t sets = gain.dense ? 1 : n;           // --gain-dense: the fitted rate set once, cafe_gain_posterior_dense
+                std::vector<double> lam, mu, nus(sets * L, res.with.nu);
+                for (size_t i = 0; i < sets; ++i) { lam.insert(lam.end(), res.with.lambdas.begin(), res.with.lambdas.end()); mu.insert(mu.end(), res.with.mus.begin(), res.with.mus.end()); }
+                const gain_origins go_res = base->gain_posterior(d.p_prior.get(), d.rootdist, table.family, lam, mu, nus, go.root_absent, order, gain.dense);
                 std::vector<std::string> names, ids;
                 size_t root = 0;
                 for (size_t v = 0; v < order.size(); ++v) { names.push_back(clade_index_or_name(order[v], order)); if (order[v]->is_root()) root = v; }
@@ -621,6 +623,7 @@ int main(int argc, char** argv) {
                 double originated = 0, lost = 0;
                 for (double v : origins.originated) originated += v;
                 for (double v : origins.lost) lost += v;
+                std::printf("\"gain_posterior_path\": \"%s\", ", gain.dense ? "cafe_gain_posterior_dense" : "cafe_gain_posterior");
                 std::printf("\"gain_posterior_seconds\": %.3f, \"expected_origins\": %.12g, \"expected_losses\": %.12g, \"absent_at_root\": %.12g, "
                             "\"families_with_a_likely_origin\": %.12g, ", posterior_s, originated, lost, origins.absent_at_root, origins.origin_somewhere);
             }

@@ -421,6 +421,27 @@ typedef struct cafe_gain_posterior_out {
 } cafe_gain_posterior_out;
 int cafe_gain_posterior(cafe_ctx* ctx, const cafe_params* params, int64_t n, const int64_t* family, const double* lambdas,
                         const double* mus, const double* nus, double root_absent, const cafe_gain_posterior_out* out);
+/* cafe_gain_posterior under ONE set of rates for the whole list, on the dense prune of cafe_score_gain (gain_dense.hip).  The
+ * arguments are cafe_score_gain's -- lambdas, mus (NULL: mu = lambda) and nus are [n_lambdas], family[n] may repeat an index and
+ * may hold CAFE_FAMILY_ABSENT -- the outputs cafe_gain_posterior's, meaning for meaning.  The up pass is cafe_score_gain's launch
+ * for launch with the sum rule forced at the root (the context's root rule is neither read nor changed): lnl is bit for bit
+ * cafe_score_gain's under CAFE_ROOT_SUM.  Every B and F panel of a batch is still in the workspace when the root kernel ends, and
+ * the down pass runs on them by depth from the root: the weights w_u = outside_parent * prod siblings' factors of every node of
+ * a depth in one launch, outside_u = P_u^T w_u of its interior nodes by an fp64 MFMA GEMM over the matrices as they are stored,
+ * then the outputs -- of the interior nodes from outside_u and B_u, of the leaves from dot products at the taps of their counts
+ * (a missing leaf: the whole matrix-vector product).  Checks and host-decided values are cafe_score_gain's: base model only;
+ * CAFE_ERR_STATE with a communicator attached; CAFE_ERR_ARGUMENT for a negative or NaN nu, root_absent outside [0, 1] and a
+ * family index below -1; an invalid rate set gives lnl -inf and NaN in every other output, a NaN lambda that passes the rule NaN
+ * everywhere; a family whose lnl from the device is not finite has NaN in every other output.  An error model, missing cells and
+ * a saturated key (row 0 kept, zeros below) are accepted.  A value depends on the family's counts and the rates only, never on
+ * its position in the list or on the batch cut (whole 128-column tiles under workspace_limit, at most CAFE_PER_FAMILY_BATCH
+ * entries); values agree with cafe_gain_posterior's to rounding.  posterior is staged per batch: ask for it on short lists.
+ * cafe_family_results is not meaningful after this call; a later cafe_score returns what it returned before. */
+int cafe_gain_posterior_dense(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus,
+                              double root_absent, int64_t n, const int64_t* family, const cafe_gain_posterior_out* out);
+/* The last cafe_gain_posterior_dense: summed HIP-event ms of its build, product, GEMM, root, weights, transposed GEMM, interior
+ * output and leaf output launches (0 unless cafe_set_profiling was on) and the flops both GEMMs issued. */
+int cafe_debug_gain_dense_posterior(cafe_ctx* ctx, double ms[8], double* flops);
 
 /* Separate birth and death rates.  The reference fits the critical process lambda = mu only; with death rates set a context
  * scores the linear birth-death process with birth rate lambdas[i] and death rate mus[i] per lineage on the branches of
