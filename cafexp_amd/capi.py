@@ -148,7 +148,7 @@ EXPORTS = [
     "cafe_score_per_family_gain", "cafe_bd_gain_row0", "cafe_debug_narrowed_extents", "cafe_gain_posterior",
     "cafe_debug_pvalues_stages", "cafe_debug_sort_rows", "cafe_debug_tree_pvalue",
     "cafe_score_gain", "cafe_debug_gain_dense",
-    "cafe_gain_posterior_dense", "cafe_debug_gain_dense_posterior",
+    "cafe_gain_posterior_dense", "cafe_debug_gain_dense_posterior", "cafe_set_gain_scaling",
 ]
 CAFE_CHANGE_NONE = -(1 << 31)   # mode / lo / hi of cafe_branch_change at the root and in a failed family
 CAFE_COMM_ID_BYTES = 128
@@ -241,6 +241,8 @@ def load():
                                             C.POINTER(CafeGainPosteriorOut)]
     L.cafe_debug_gain_dense_posterior.restype = C.c_int
     L.cafe_debug_gain_dense_posterior.argtypes = [C.c_void_p, _f64p, _f64p]
+    L.cafe_set_gain_scaling.restype = C.c_int
+    L.cafe_set_gain_scaling.argtypes = [C.c_void_p, C.c_int]
     L.cafe_bd_gain_row0.restype = C.c_int
     L.cafe_bd_gain_row0.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _f64p, _f64p]
     L.cafe_bd_rates.restype = C.c_int
@@ -646,6 +648,12 @@ class Context:
         ms, flops = np.zeros(8), np.zeros(1)
         self._check(self._lib.cafe_debug_gain_dense_posterior(self._h, _p(ms, _f64p), _p(flops, _f64p)))
         return ms, float(flops[0])
+
+    def set_gain_scaling(self, on: bool):
+        """cafe_set_gain_scaling: score_gain and gain_posterior_dense hold every likelihood panel as mantissas and one binary
+        exponent per (node, column), so a family whose likelihood lies below fp64's range gets its lnl and posteriors where the
+        plain path (the default) answers -inf and NaN.  Matrix entries stay plain fp64."""
+        self._check(self._lib.cafe_set_gain_scaling(self._h, int(bool(on))))
 
     def marginal_reconstruct(self, pr: Params, level: float = 0.95, alpha: float = 1.0) -> dict:
         """cafe_marginal_reconstruct: posterior size of every node under the scorer's model with pr's lambdas, categories,

@@ -249,6 +249,7 @@ struct cafe_ctx {
     int64_t pf_max_batch = 0;                // CAFE_PER_FAMILY_BATCH: at most that many families per batch (diagnostic; 0 = what fits)
     double marginal_gemm_ms = 0, marginal_gemm_flops = 0;   // cafe_marginal_reconstruct: its GEMM launches (ms: while profiling)
     double gain_dense_ms[4] = {0, 0, 0, 0}, gain_dense_flops = 0;   // cafe_score_gain: build / product / GEMM / root launches (ms: while profiling), GEMM flops issued
+    int gain_scaling = 0;            // cafe_set_gain_scaling: cafe_score_gain and cafe_gain_posterior_dense hold their panels as mantissas and exponents
     double gain_dense_posterior_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0}, gain_dense_posterior_flops = 0;   // cafe_gain_posterior_dense: those four, then weights / transposed GEMM / interior / leaf outputs; both GEMMs' flops
     double change_band_ms = 0;                              // cafe_branch_change: its band kernel's launches (while profiling)
     double gram_ms = 0.0, gram_flops = 0.0;  // the Gram kernels of the last cafe_branch_scores (ms: profiling on)

@@ -13,8 +13,14 @@
 //            64 x 128 x 16 tiles, A and B staged through two LDS buffers, every load guarded by the order
 //   root     lnL_f from mass[j] B_root[j][f], j = 0..R, in logarithms, the maximum or the sum by the context's root rule
 //
-// Plain fp64, no rescaling.  A column's value is computed by the same operations in the same order wherever the column
-// stands, so it depends on the family's counts and the rates only: not on its position, not on the batch cut.
+// Plain fp64, no rescaling, by default.  A column's value is computed by the same operations in the same order wherever the
+// column stands, so it depends on the family's counts and the rates only: not on its position, not on the batch cut.
+//
+// cafe_set_gain_scaling switches both entries to the SCALED mode ("scaled" below): every panel is held as mantissas and one
+// int32 binary exponent per (node, column), B~_v[s][f] = B_v[s][f] 2^-E_v[f], E chosen so that the column's largest entry has
+// binary exponent 0.  A power of two per column commutes with the GEMMs exactly, so both GEMM kernels run as they are and their
+// outputs carry their inputs' exponents; the product, weights, root and output kernels have scaled twins.  Matrix entries stay
+// plain fp64.
 //
 // cafe_gain_posterior_dense: the same up pass with the sum rule forced, then the other half of the sum-product on the panels it
 // left -- by depth from the root a weights kernel, an MFMA GEMM over the matrices as stored (P^T), and the output kernels of
@@ -94,7 +100,7 @@ struct GainProdOp {
     int64_t dst;                     // B panel of the node
     int32_t rows;                    // sizes 0..rows-1
     int32_t child0, n_children;      // children[child0 .. child0 + n_children)
-    int32_t pad;
+    int32_t carry;                   // scaled: the F panel (an index) that the GEMM makes of this one and that carries its exponents, -1 at the root
 };
 struct GainProdArgs {
     const GainProdOp* ops;
@@ -110,18 +116,40 @@ struct GainProdArgs {
 
 constexpr int kGdProdRows = 16;
 
+// v *= f.  Track (the scaled kernels): the element is the pair (v, k) standing for v 2^(-512 k).  A non-zero factor below 2^-512
+// is lifted by 2^512 before the multiplication and a non-zero product below 2^-512 after it, each counted in k, so a many-way
+// product of factors each above 2^-1024 stays within 2^-1024 of the normal range while its exponent is still unknown.  Each is
+// lifted ONCE: a product of two values just above 2^-512 can land in [2^-1024, 2^-1022) and lose up to two bits before its lift,
+// and a factor below 2^-1024 (a denormal matrix entry, or a mantissa that far under its column's largest) stays below 2^-512
+// after its lift, so the product under it can lose more.  Both need values more than 150 decimal orders under their column's
+// largest or a denormal matrix entry.  The lifts are powers of two: where nothing was going to underflow the mantissa is the
+// untracked product's.
+constexpr double kGdTiny = 0x1p-512, kGdLift = 0x1p+512;
+template <bool Track>
+__device__ __forceinline__ void gain_dense_mul(double& v, int& k, double f) {
+    if constexpr (Track) {
+        if (f > 0.0 && f < kGdTiny) { f *= kGdLift; ++k; }
+        v *= f;
+        if (v > 0.0 && v < kGdTiny) { v *= kGdLift; ++k; }
+    } else {
+        v *= f;
+    }
+}
+
 // v[j] *= the factor of every listed child at parent size i0 + j, children in list order: an interior child's F panel, a leaf's
 // gather from its matrix (taps ascending; a missing cell exactly 1.0; a count past M 0).  The product kernel's body, and the
-// sibling product of the down pass's weights.
+// sibling product of the down pass's weights.  Track: gain_dense_mul's lifts are counted in k[j]; an interior child's panel is then
+// its mantissas, and the caller adds the child's column exponent.
+template <bool Track = false>
 __device__ __forceinline__ void gain_dense_times_children(const GainProdArgs& a, int child0, int n_children, int i0, int n, int64_t f, int64_t col,
-                                                          double (&v)[kGdProdRows]) {
-    for (int k = 0; k < n_children; ++k) {
-        const GainChild ch = a.children[child0 + k];
+                                                          double (&v)[kGdProdRows], int (&k)[kGdProdRows]) {
+    for (int ci = 0; ci < n_children; ++ci) {
+        const GainChild ch = a.children[child0 + ci];
         if (ch.taxon < 0) {
             const double* __restrict__ F = a.panels + ch.src + (int64_t)i0 * a.ld + f;
 #pragma unroll
             for (int j = 0; j < kGdProdRows; ++j)
-                if (j < n) v[j] *= F[(int64_t)j * a.ld];
+                if (j < n) gain_dense_mul<Track>(v[j], k[j], F[(int64_t)j * a.ld]);
             continue;
         }
         const int x = col >= 0 ? a.counts[(int64_t)ch.taxon * a.counts_ld + col] : 0;
@@ -132,7 +160,7 @@ __device__ __forceinline__ void gain_dense_times_children(const GainProdArgs& a,
             const double* __restrict__ pc = P + (int64_t)(in ? x : 0) * a.ldp;
 #pragma unroll
             for (int j = 0; j < kGdProdRows; ++j)
-                if (j < n) v[j] *= in ? pc[j] : 0.0;
+                if (j < n) gain_dense_mul<Track>(v[j], k[j], in ? pc[j] : 0.0);
         } else {
             const int lo = x - (a.n_dev - 1) / 2;      // taps outside [0, M] are dropped
             double fac[kGdProdRows];
@@ -148,7 +176,7 @@ __device__ __forceinline__ void gain_dense_times_children(const GainProdArgs& a,
                     if (j < n) fac[j] = fma(pc[j], w, fac[j]);
             }
 #pragma unroll
-            for (int j = 0; j < kGdProdRows; ++j) v[j] *= fac[j];
+            for (int j = 0; j < kGdProdRows; ++j) gain_dense_mul<Track>(v[j], k[j], fac[j]);
         }
     }
 }
@@ -161,9 +189,10 @@ __global__ __launch_bounds__(256) void gain_dense_product_kernel(const GainProdA
     if (i0 >= op.rows || f >= a.ncols) return;
     const int n = min(kGdProdRows, op.rows - i0);
     double v[kGdProdRows];
+    int lifts[kGdProdRows];                            // (not read: the untracked product)
 #pragma unroll
     for (int j = 0; j < kGdProdRows; ++j) v[j] = 1.0;
-    gain_dense_times_children(a, op.child0, op.n_children, i0, n, f, a.col[f], v);
+    gain_dense_times_children(a, op.child0, op.n_children, i0, n, f, a.col[f], v, lifts);
     double* __restrict__ dst = a.panels + op.dst + (int64_t)i0 * a.ld + f;
 #pragma unroll
     for (int j = 0; j < kGdProdRows; ++j)
@@ -271,9 +300,11 @@ struct GainRootArgs {
     int32_t R, sum_rule;
 };
 
-// 64 columns per block, the sizes dealt to four waves: t_j = log B[j][f] + logmass[j], then the maximum, or m + log sum exp(t - m)
-__global__ __launch_bounds__(256) void gain_dense_root_kernel(const GainRootArgs a) {
-    __shared__ double red[4][64];
+// 64 columns per block, the sizes dealt to four waves: t_j = log B[j][f] + logmass[j], then the maximum, or m + log sum exp(t - m).
+// Scaled: B is the root's mantissas, so that value is the log of the scaled evidence Z~ -- kept in zt for the down pass -- and
+// lnL = log Z~ + E_root ln 2 (-inf for a zero column, whose exponent is 0).
+template <bool Scaled>
+__device__ __forceinline__ void gain_dense_root(const GainRootArgs& a, double (*red)[64], const int32_t* exps, double* zt) {
     const int x = threadIdx.x & 63, y = threadIdx.x >> 6;
     const int64_t f = (int64_t)blockIdx.x * 64 + x;    // (ld is a multiple of 128)
     const double ninf = -__builtin_huge_val();
@@ -295,7 +326,25 @@ __global__ __launch_bounds__(256) void gain_dense_root_kernel(const GainRootArgs
         }
     red[y][x] = s;
     __syncthreads();
-    if (y == 0) a.out[f] = a.sum_rule ? m + log((red[0][x] + red[1][x]) + (red[2][x] + red[3][x])) : m;
+    if (y != 0) return;
+    const double z = a.sum_rule ? m + log((red[0][x] + red[1][x]) + (red[2][x] + red[3][x])) : m;
+    if constexpr (Scaled) {
+        zt[f] = z;
+        a.out[f] = z + (double)exps[f] * 0.693147180559945309417;
+    } else {
+        a.out[f] = z;
+    }
+}
+
+__global__ __launch_bounds__(256) void gain_dense_root_kernel(const GainRootArgs a) {
+    __shared__ double red[4][64];
+    gain_dense_root<false>(a, red, nullptr, nullptr);
+}
+
+// exps: the exponents of the root's panel
+__global__ __launch_bounds__(256) void gain_scaled_root_kernel(const GainRootArgs a, const int32_t* exps, double* zt) {
+    __shared__ double red[4][64];
+    gain_dense_root<true>(a, red, exps, zt);
 }
 
 // ------------------------------------------------------------------------------------------------------- down: weights
@@ -307,7 +356,7 @@ struct GainWeightOp {
     int64_t outside;                 // the parent's outside panel; -1: the parent is the root, its outside vector is `mass`
     int32_t rows;                    // R + 1 under the root, M + 1 below
     int32_t child0, n_children;      // the siblings, in child order
-    int32_t pad;
+    int32_t carry;                   // scaled: the node's outside panel (an index), which carries w's exponents; -1 for a leaf
 };
 struct GainWeightArgs {
     GainProdArgs p;                  // (its ops are not read)
@@ -323,6 +372,7 @@ __global__ __launch_bounds__(256) void gain_posterior_dense_weights_kernel(const
     if (i0 >= op.rows || f >= a.p.ncols) return;
     const int n = min(kGdProdRows, op.rows - i0);
     double v[kGdProdRows];
+    int lifts[kGdProdRows];                            // (not read: the untracked product)
 #pragma unroll
     for (int j = 0; j < kGdProdRows; ++j) v[j] = 0.0;
     if (op.outside < 0) {
@@ -335,11 +385,98 @@ __global__ __launch_bounds__(256) void gain_posterior_dense_weights_kernel(const
         for (int j = 0; j < kGdProdRows; ++j)
             if (j < n) v[j] = O[(int64_t)j * a.p.ld];
     }
-    gain_dense_times_children(a.p, op.child0, op.n_children, i0, n, f, a.p.col[f], v);
+    gain_dense_times_children(a.p, op.child0, op.n_children, i0, n, f, a.p.col[f], v, lifts);
     double* __restrict__ dst = a.p.panels + op.dst + (int64_t)i0 * a.p.ld + f;
 #pragma unroll
     for (int j = 0; j < kGdProdRows; ++j)
         if (j < n) dst[(int64_t)j * a.p.ld] = v[j];
+}
+
+// --------------------------------------------------------------------------------------- scaled: product and weights
+// The scaled twins of the product and the weights kernel.  The plain kernels give a thread 16 sizes of a column and their
+// blocks along y never meet, so no column maximum exists there.  Here a workgroup owns 64 columns over ALL sizes of the node:
+// lanes along f (a panel row is read and written 512 contiguous bytes at a time), the 16-size chunks dealt to the four waves --
+// wave y takes the chunks y, y + 4, .. -- as the root kernel deals sizes.
+//   pass 1  forms every element as (mantissa, lifts) with gain_dense_times_children<true> and keeps only the largest binary
+//           exponent of the column, folded across the four waves through LDS
+//   pass 2  forms the elements again (the inputs now come from L2) and stores them shifted by that exponent: the panel is
+//           written once and no unscaled panel ever reaches memory
+// The column's exponent is the sum of the exponents its factors carry (the interior children's; under the weights also the
+// parent's outside vector's) plus the shift.  An all-zero column and a column holding a NaN or an infinity get exponent 0; the
+// latter is stored as it is, unscaled.  Everything a column sees is its own: no value depends on the column's neighbours.
+struct GainScaleArgs {
+    int32_t* exps;                   // [panels][ld]: the exponents of the panel at `off` doubles from `panels` are exps + off / N
+    int32_t N;
+};
+
+constexpr int kGdNoExp = INT32_MIN, kGdBadExp = INT32_MAX;    // an all-zero column; one holding a NaN or an infinity
+
+// grid (column tiles of 64, nodes).  init(i0, n, v): the elements before the children are multiplied in, as mantissas of the
+// exponent e0.
+template <class Init>
+__device__ __forceinline__ void gain_scaled_node(const GainProdArgs& a, const GainScaleArgs& sc, int (*red)[64], int child0, int n_children, int rows,
+                                                 int64_t dst, int carry, int e0, Init init) {
+    const int x = threadIdx.x & 63, y = threadIdx.x >> 6;
+    const int64_t f = (int64_t)blockIdx.x * 64 + x, col = a.col[f];
+    int ecol = e0;
+    for (int ci = 0; ci < n_children; ++ci) {
+        const GainChild ch = a.children[child0 + ci];
+        if (ch.taxon < 0) ecol += sc.exps[ch.src / sc.N + f];
+    }
+    double v[kGdProdRows];
+    int k[kGdProdRows];
+    auto form = [&](int i0, int n) {
+        init(i0, n, v);
+#pragma unroll
+        for (int j = 0; j < kGdProdRows; ++j) k[j] = 0;
+        gain_dense_times_children<true>(a, child0, n_children, i0, n, f, col, v, k);
+    };
+    int best = kGdNoExp;
+    for (int i0 = y * kGdProdRows; i0 < rows; i0 += 4 * kGdProdRows) {
+        const int n = min(kGdProdRows, rows - i0);
+        form(i0, n);
+#pragma unroll
+        for (int j = 0; j < kGdProdRows; ++j)
+            if (j < n && v[j] != 0.0) best = max(best, isfinite(v[j]) ? ilogb(v[j]) - 512 * k[j] : kGdBadExp);
+    }
+    red[y][x] = best;
+    __syncthreads();
+    best = max(max(red[0][x], red[1][x]), max(red[2][x], red[3][x]));
+    const int shift = (best == kGdNoExp || best == kGdBadExp) ? -ecol : best;
+    for (int i0 = y * kGdProdRows; i0 < rows; i0 += 4 * kGdProdRows) {
+        const int n = min(kGdProdRows, rows - i0);
+        form(i0, n);
+        double* __restrict__ out = a.panels + dst + (int64_t)i0 * a.ld + f;
+#pragma unroll
+        for (int j = 0; j < kGdProdRows; ++j)
+            if (j < n) out[(int64_t)j * a.ld] = ldexp(v[j], -512 * k[j] - shift);
+    }
+    if (y != 0) return;
+    sc.exps[dst / sc.N + f] = ecol + shift;
+    if (carry >= 0) sc.exps[(int64_t)carry * a.ld + f] = ecol + shift;
+}
+
+__global__ __launch_bounds__(256) void gain_scaled_product_kernel(const GainProdArgs a, const GainScaleArgs sc) {
+    __shared__ int red[4][64];
+    const GainProdOp op = a.ops[blockIdx.y];
+    gain_scaled_node(a, sc, red, op.child0, op.n_children, op.rows, op.dst, op.carry, 0, [](int, int, double (&v)[kGdProdRows]) {
+#pragma unroll
+        for (int j = 0; j < kGdProdRows; ++j) v[j] = 1.0;
+    });
+}
+
+// under the root the outside vector is the plain mass, exponent 0
+__global__ __launch_bounds__(256) void gain_scaled_weights_kernel(const GainWeightArgs a, const GainScaleArgs sc) {
+    __shared__ int red[4][64];
+    const GainWeightOp op = a.ops[blockIdx.y];
+    const int64_t f = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
+    const int e0 = op.outside < 0 ? 0 : sc.exps[op.outside / sc.N + f];
+    gain_scaled_node(a.p, sc, red, op.child0, op.n_children, op.rows, op.dst, op.carry, e0, [&](int i0, int n, double (&v)[kGdProdRows]) {
+        const double* __restrict__ O = op.outside < 0 ? a.mass + i0 : a.p.panels + op.outside + (int64_t)i0 * a.p.ld + f;
+        const int64_t step = op.outside < 0 ? 1 : a.p.ld;
+#pragma unroll
+        for (int j = 0; j < kGdProdRows; ++j) v[j] = j < n ? O[j * step] : 0.0;
+    });
 }
 
 // ----------------------------------------------------------------------------------------------- down: transposed GEMM
@@ -462,7 +599,7 @@ struct GainOutArgs {
     const double* mats;
     const double* panels;
     const double* mass;
-    const double* lnl;               // [ld] the root kernel's sum-rule lnL: Z = exp(lnl)
+    const double* lnl;               // [ld] the root kernel's sum-rule lnL: Z = exp(lnl); scaled: its log Z~
     double* res;
     double* posterior;               // or nullptr
     const int64_t* col;
@@ -470,6 +607,7 @@ struct GainOutArgs {
     const double* err;
     int64_t counts_ld, ld;
     int32_t nn, N, M, ldp, n_dev, any_missing;
+    int64_t root_B;                  // the root's panel (doubles from `panels`): scaled, where E_root stands
 };
 
 __device__ __forceinline__ double gain_dense_fold4(double (*red)[64], int x, int y, double v) {
@@ -480,16 +618,31 @@ __device__ __forceinline__ double gain_dense_fold4(double (*red)[64], int x, int
     return s;
 }
 
+// Scaled: the operands are mantissas and Z is Z~, so a ratio is short of its value by 2^d, d = E_w(u) + E_u - E_root for every
+// output of the node (outside_u carries w_u's exponent; a leaf's own vector is its taps, exponent 0; at the root d = 0).  The
+// ratio is formed first and shifted by ldexp after: nothing goes through exp(lnl).  The ratio is a product of two mantissas, so
+// where d is large and positive -- the outside vector and the node's own vector peak at sizes hundreds of binary orders apart --
+// it can pass through the denormal range, or to 0 below 2^-1074, before the shift brings it back: such an entry is short of
+// bits though its value is representable.  Shifting one operand first would keep it; no input of the tests reaches this.
+template <bool Scaled>
+__device__ __forceinline__ double gain_dense_shifted(double ratio, int d) {
+    if constexpr (Scaled) return ldexp(ratio, d);
+    return ratio;
+}
+
 // interior nodes, the root among them (its op has no w: p_gain and p_loss are NaN): posterior_u[c] = outside_u[c] B_u[c] / Z,
 // p_gain = w[0] sum_{c >= 1} P[0][c] B[c] / Z (row 0 is Pt[c * ldp], wave-uniform), p_loss = B[0] sum_{s >= 1} w[s] P[s][0] / Z
 // (column 0 is Pt[s]).  grid (cols / 64, interior nodes of the depth)
-__global__ __launch_bounds__(256) void gain_posterior_dense_interior_kernel(const GainOutArgs a) {
-    __shared__ double red[4][64];
+template <bool Scaled>
+__device__ __forceinline__ void gain_posterior_dense_interior(const GainOutArgs& a, double (*red)[64], const int32_t* exps) {
     const GainNodeOp op = a.ops[blockIdx.y];
     const int x = threadIdx.x & 63, y = threadIdx.x >> 6;
     const int64_t f = (int64_t)blockIdx.x * 64 + x, ld = a.ld;
     const bool root = op.W < 0;
     const double Z = exp(a.lnl[f]);
+    int d = 0;
+    if constexpr (Scaled)
+        if (!root) d = exps[op.W / a.N + f] + exps[op.B / a.N + f] - exps[a.root_B / a.N + f];
     const double* __restrict__ B = a.panels + op.B + f;
     const double* __restrict__ O = a.panels + (root ? op.B : op.outside) + f;
     const double* __restrict__ W = a.panels + (root ? op.B : op.W) + f;
@@ -499,7 +652,7 @@ __global__ __launch_bounds__(256) void gain_posterior_dense_interior_kernel(cons
         double post = 0.0;
         if (c < op.n) {
             const double b = B[(int64_t)c * ld];
-            post = (root ? a.mass[c] : O[(int64_t)c * ld]) * b / Z;
+            post = gain_dense_shifted<Scaled>((root ? a.mass[c] : O[(int64_t)c * ld]) * b / Z, d);
             m = fma((double)c, post, m);
             if (!root && c >= 1) g = fma(Pt[(int64_t)c * a.ldp], b, g);
         }
@@ -514,8 +667,18 @@ __global__ __launch_bounds__(256) void gain_posterior_dense_interior_kernel(cons
     const int64_t o = (int64_t)op.node * ld + f, k = (int64_t)a.nn * ld;
     a.res[o] = p0;
     a.res[o + k] = m;
-    a.res[o + 2 * k] = root ? __builtin_nan("") : W[0] * g / Z;
-    a.res[o + 3 * k] = root ? __builtin_nan("") : B[0] * l / Z;
+    a.res[o + 2 * k] = root ? __builtin_nan("") : gain_dense_shifted<Scaled>(W[0] * g / Z, d);
+    a.res[o + 3 * k] = root ? __builtin_nan("") : gain_dense_shifted<Scaled>(B[0] * l / Z, d);
+}
+
+__global__ __launch_bounds__(256) void gain_posterior_dense_interior_kernel(const GainOutArgs a) {
+    __shared__ double red[4][64];
+    gain_posterior_dense_interior<false>(a, red, nullptr);
+}
+
+__global__ __launch_bounds__(256) void gain_scaled_interior_kernel(const GainOutArgs a, const int32_t* exps) {
+    __shared__ double red[4][64];
+    gain_posterior_dense_interior<true>(a, red, exps);
 }
 
 // leaves, without a GEMM: L_u is non-zero at the taps of the observed count only, so outside_u is needed there only --
@@ -523,12 +686,14 @@ __global__ __launch_bounds__(256) void gain_posterior_dense_interior_kernel(cons
 // waves take a quarter of the parent's sizes each.  A MISSING leaf (L_u = 1 over 0..M; on a context created with missing cells)
 // gets the full mat-vec from its own thread group instead: wave y the sizes c = y, y + 4, .., each a whole dot.  Its p_gain is
 // w[0] (1 - P[0][0]) / Z.  A count past M made lnl -inf: nothing is read for it.  grid (cols / 64, leaves of the depth)
-__global__ __launch_bounds__(256) void gain_posterior_dense_leaf_kernel(const GainOutArgs a) {
-    __shared__ double red[4][64];
+template <bool Scaled>
+__device__ __forceinline__ void gain_posterior_dense_leaf(const GainOutArgs& a, double (*red)[64], const int32_t* exps) {
     const GainNodeOp op = a.ops[blockIdx.y];
     const int x = threadIdx.x & 63, y = threadIdx.x >> 6;
     const int64_t f = (int64_t)blockIdx.x * 64 + x, ld = a.ld;
     const double Z = exp(a.lnl[f]);
+    int d = 0;
+    if constexpr (Scaled) d = exps[op.W / a.N + f] - exps[a.root_B / a.N + f];
     const int64_t col = a.col[f];
     const int cnt = col >= 0 ? a.counts[(int64_t)op.taxon * a.counts_ld + col] : 0;
     const bool missing = count_is_missing(cnt), in = !missing && cnt <= a.M;
@@ -553,7 +718,7 @@ __global__ __launch_bounds__(256) void gain_posterior_dense_leaf_kernel(const Ga
         const double dot = gain_dense_fold4(red, x, y, part);
         if (y == 0 && ok) {
             const double wt = a.err ? a.err[(int64_t)cnt * a.n_dev + t] : 1.0;
-            const double post = dot * wt / Z;
+            const double post = gain_dense_shifted<Scaled>(dot * wt / Z, d);
             if (c == 0) { p0 = post; L0 = wt; }
             else g = fma(Pt[(int64_t)c * a.ldp], wt, g);
             mean = fma((double)c, post, mean);
@@ -571,7 +736,7 @@ __global__ __launch_bounds__(256) void gain_posterior_dense_leaf_kernel(const Ga
                 const double* __restrict__ pc = Pt + (int64_t)c * a.ldp;
                 double dot = 0.0;
                 for (int s = 0; s < op.rows; ++s) dot = fma(W[(int64_t)s * ld], pc[s], dot);
-                const double post = dot / Z;
+                const double post = gain_dense_shifted<Scaled>(dot / Z, d);
                 if (c == 0) p0 = post;
                 mm = fma((double)c, post, mm);
                 if (po) po[(int64_t)c * ld] = post;
@@ -583,8 +748,18 @@ __global__ __launch_bounds__(256) void gain_posterior_dense_leaf_kernel(const Ga
     const int64_t o = (int64_t)op.node * ld + f, k = (int64_t)a.nn * ld;
     a.res[o] = p0;
     a.res[o + k] = mean;
-    a.res[o + 2 * k] = W[0] * g / Z;
-    a.res[o + 3 * k] = L0 * loss / Z;
+    a.res[o + 2 * k] = gain_dense_shifted<Scaled>(W[0] * g / Z, d);
+    a.res[o + 3 * k] = gain_dense_shifted<Scaled>(L0 * loss / Z, d);
+}
+
+__global__ __launch_bounds__(256) void gain_posterior_dense_leaf_kernel(const GainOutArgs a) {
+    __shared__ double red[4][64];
+    gain_posterior_dense_leaf<false>(a, red, nullptr);
+}
+
+__global__ __launch_bounds__(256) void gain_scaled_leaf_kernel(const GainOutArgs a, const int32_t* exps) {
+    __shared__ double red[4][64];
+    gain_posterior_dense_leaf<true>(a, red, exps);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
@@ -657,6 +832,7 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
     if (const int rc = gain_rates_check(c, who, 1, nus, root_absent)) return rc;
     if (n == 0) return CAFE_OK;
     const int nn = c->n_nodes, L = c->n_lambdas, N = c->N, M = c->M, R = c->R, ldp = round_up(N, 2);
+    const bool scaled = c->gain_scaling != 0;          // cafe_set_gain_scaling: the scaled twins of every kernel but the build and the GEMMs
 
     // ---- what the host decides alone: an invalid rate set is -inf in every entry, a NaN lambda that passes the rule NaN
     c->last.state = LastCall::kNone;                   // cafe_family_results is not meaningful after this call
@@ -730,7 +906,8 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
                                sizeof(double) * ((size_t)R + 1 + (size_t)(M + 1) * c->n_dev) +
                                (down ? (sizeof(GainChild) + sizeof(GainWeightOp) + sizeof(GainGemmTOp) + sizeof(GainNodeOp)) * (size_t)nn + sizeof(double) * ((size_t)R + 1) : 0);
     const size_t column_bytes = sizeof(double) * (size_t)n_pan * N + sizeof(int64_t) + sizeof(double) +
-                                (down ? sizeof(double) * ((size_t)n_down * N + 4 * (size_t)nn + (want_posterior ? (size_t)nn * N : 0)) : 0);
+                                (down ? sizeof(double) * ((size_t)n_down * N + 4 * (size_t)nn + (want_posterior ? (size_t)nn * N : 0)) : 0) +
+                                (scaled ? sizeof(int32_t) * (size_t)(n_pan + n_down) + sizeof(double) : 0);     // the exponents, log Z~
     size_t budget = 0;
     HIP_TRY(c, workspace_budget(c->workspace_limit, c->pf_dev_bytes, &budget));
     int64_t entries = budget > fixed_bytes ? (int64_t)((budget - fixed_bytes) / column_bytes) / kGdCols * kGdCols : 0;
@@ -756,6 +933,7 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
                 children.push_back({leaf ? node_key[ch] * mat_stride : fidx[ch] * pan_stride, leaf ? c->leaf_taxon[ch] : -1, 0});
             }
             po.n_children = (int32_t)children.size() - po.child0;
+            po.carry = fidx[u];
             prod_ops.push_back(po);
             pr_rows = std::max(pr_rows, po.rows);
             if (u == c->root) continue;
@@ -781,7 +959,7 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
                 continue;
             }
             const int rows = (p == c->root ? R : M) + 1;
-            GainWeightOp wo{widx[u] * pan_stride, p == c->root ? -1 : oidx[p] * pan_stride, rows, (int32_t)children.size(), 0, 0};
+            GainWeightOp wo{widx[u] * pan_stride, p == c->root ? -1 : oidx[p] * pan_stride, rows, (int32_t)children.size(), 0, oidx[u]};
             for (int sib : c->children[p]) {
                 if (sib == u) continue;
                 const bool leaf = c->leaf_taxon[sib] >= 0;
@@ -821,7 +999,9 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
                  o_mats = o_out + family_align_up(sizeof(double) * ld), o_pan = o_mats + family_align_up(sizeof(double) * (size_t)mat_stride * n_keys),
                  o_res = o_pan + sizeof(double) * (size_t)pan_stride * (n_pan + n_down),
                  o_post = o_res + (down ? sizeof(double) * 4 * (size_t)nn * ld : 0),
-                 need = o_post + (want_posterior ? sizeof(double) * (size_t)nn * N * ld : 0);
+                 o_exps = o_post + (want_posterior ? sizeof(double) * (size_t)nn * N * ld : 0),
+                 o_zt = o_exps + (scaled ? family_align_up(sizeof(int32_t) * (size_t)(n_pan + n_down) * ld) : 0),
+                 need = o_zt + (scaled ? sizeof(double) * ld : 0);
     if (need > c->pf_dev_bytes) {
         if (c->pf_dev) { HIP_TRY(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->pf_dev); c->pf_dev = nullptr; c->pf_dev_bytes = 0; }
         if (hipMalloc(&c->pf_dev, need) != hipSuccess) {
@@ -862,6 +1042,11 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
     oa.res = reinterpret_cast<double*>(base + o_res); oa.posterior = want_posterior ? reinterpret_cast<double*>(base + o_post) : nullptr;
     oa.col = pa.col; oa.counts = pa.counts; oa.err = pa.err; oa.counts_ld = pa.counts_ld; oa.ld = ld;
     oa.nn = nn; oa.N = N; oa.M = M; oa.ldp = ldp; oa.n_dev = c->n_dev; oa.any_missing = c->has_missing ? 1 : 0;
+    oa.root_B = bidx[c->root] * pan_stride;
+    const GainScaleArgs sa{reinterpret_cast<int32_t*>(base + o_exps), N};
+    const int32_t* root_exps = sa.exps + bidx[c->root] * ld;
+    double* zt = reinterpret_cast<double*>(base + o_zt);
+    if (scaled) oa.lnl = zt;                           // the outputs divide by Z~ = exp(log Z~)
     if (down) {
         down->res.resize(4 * (size_t)nn * entries);
         if (want_posterior) down->posterior.resize((size_t)nn * N * entries);
@@ -880,8 +1065,11 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
             p.ops += prod_off[lv];
             p.ncols = cols;
             timer.mark(kGdProduct, s);
-            CAFE_LAUNCH(c, gain_dense_product_kernel, dim3((unsigned)((cols + 255) / 256), (unsigned)((prod_rows[lv] + kGdProdRows - 1) / kGdProdRows), (unsigned)np),
-                        dim3(256), 0, s, p);
+            if (scaled)
+                CAFE_LAUNCH(c, gain_scaled_product_kernel, dim3((unsigned)(cols / 64), (unsigned)np), dim3(256), 0, s, p, sa);
+            else
+                CAFE_LAUNCH(c, gain_dense_product_kernel, dim3((unsigned)((cols + 255) / 256), (unsigned)((prod_rows[lv] + kGdProdRows - 1) / kGdProdRows), (unsigned)np),
+                            dim3(256), 0, s, p);
             timer.mark(kGdProduct, s);
             if (ng == 0) continue;
             GainGemmArgs g = ga;
@@ -893,7 +1081,10 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
                 flops += 2.0 * round_up(gemm_ops[k].nr, kGdMT) * (double)round_up(M + 1, kGdKT) * (double)cols;
         }
         timer.mark(kGdRoot, s);
-        CAFE_LAUNCH(c, gain_dense_root_kernel, dim3((unsigned)(cols / 64)), dim3(256), 0, s, ra);
+        if (scaled)
+            CAFE_LAUNCH(c, gain_scaled_root_kernel, dim3((unsigned)(cols / 64)), dim3(256), 0, s, ra, root_exps, zt);
+        else
+            CAFE_LAUNCH(c, gain_dense_root_kernel, dim3((unsigned)(cols / 64)), dim3(256), 0, s, ra);
         timer.mark(kGdRoot, s);
         HIP_TRY(c, hipMemcpyAsync(res.data(), base + o_out, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
         for (int d = 0; d < n_depths; ++d) {           // the down pass: every B and F panel of the batch is still in place
@@ -904,8 +1095,11 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
                 w.ops += weight_off[d];
                 w.p.ncols = cols;
                 timer.mark(kGdWeights, s);
-                CAFE_LAUNCH(c, gain_posterior_dense_weights_kernel,
-                            dim3((unsigned)((cols + 255) / 256), (unsigned)((weight_rows[d] + kGdProdRows - 1) / kGdProdRows), (unsigned)nw), dim3(256), 0, s, w);
+                if (scaled)
+                    CAFE_LAUNCH(c, gain_scaled_weights_kernel, dim3((unsigned)(cols / 64), (unsigned)nw), dim3(256), 0, s, w, sa);
+                else
+                    CAFE_LAUNCH(c, gain_posterior_dense_weights_kernel,
+                                dim3((unsigned)((cols + 255) / 256), (unsigned)((weight_rows[d] + kGdProdRows - 1) / kGdProdRows), (unsigned)nw), dim3(256), 0, s, w);
                 timer.mark(kGdWeights, s);
             }
             if (nt > 0) {
@@ -921,13 +1115,19 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
             if (ni > 0) {
                 o.ops = reinterpret_cast<const GainNodeOp*>(base + o_int) + int_off[d];
                 timer.mark(kGdInterior, s);
-                CAFE_LAUNCH(c, gain_posterior_dense_interior_kernel, dim3((unsigned)(cols / 64), (unsigned)ni), dim3(256), 0, s, o);
+                if (scaled)
+                    CAFE_LAUNCH(c, gain_scaled_interior_kernel, dim3((unsigned)(cols / 64), (unsigned)ni), dim3(256), 0, s, o, (const int32_t*)sa.exps);
+                else
+                    CAFE_LAUNCH(c, gain_posterior_dense_interior_kernel, dim3((unsigned)(cols / 64), (unsigned)ni), dim3(256), 0, s, o);
                 timer.mark(kGdInterior, s);
             }
             if (nl > 0) {
                 o.ops = reinterpret_cast<const GainNodeOp*>(base + o_leaf) + leaf_off[d];
                 timer.mark(kGdLeaf, s);
-                CAFE_LAUNCH(c, gain_posterior_dense_leaf_kernel, dim3((unsigned)(cols / 64), (unsigned)nl), dim3(256), 0, s, o);
+                if (scaled)
+                    CAFE_LAUNCH(c, gain_scaled_leaf_kernel, dim3((unsigned)(cols / 64), (unsigned)nl), dim3(256), 0, s, o, (const int32_t*)sa.exps);
+                else
+                    CAFE_LAUNCH(c, gain_posterior_dense_leaf_kernel, dim3((unsigned)(cols / 64), (unsigned)nl), dim3(256), 0, s, o);
                 timer.mark(kGdLeaf, s);
             }
         }
@@ -957,6 +1157,12 @@ int cafe_score_gain(cafe_ctx* ctx, const cafe_params* params, const double* lamb
                                  [&] { return cafe::gain_dense_impl(ctx, "cafe_score_gain", params, lambdas, mus, nus, root_absent, n, family, family_lnl, nullptr); });
     if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
     return rc;
+}
+
+int cafe_set_gain_scaling(cafe_ctx* ctx, int on) {
+    if (!ctx) return CAFE_ERR_ARGUMENT;
+    ctx->gain_scaling = on != 0;
+    return CAFE_OK;
 }
 
 int cafe_debug_gain_dense(cafe_ctx* ctx, double ms[4], double* flops) {

@@ -609,6 +609,9 @@ public:
     std::vector<double> per_family_gain_lnl(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist,
                                             const std::vector<int64_t>& family, const std::vector<double>& lambdas,
                                             const std::vector<double>& mus, const std::vector<double>& nus, double root_absent);
+    // --gain-scaled: both dense calls below run in the scaled mode (cafe_set_gain_scaling), which survives likelihoods below
+    // fp64's range; set on the context at each of the two calls
+    void set_gain_scaling(bool on) { _gain_scaled = on; }
     // ... under ONE set of rates ([n_lambdas] each) on the dense prune: one cafe_score_gain call (--gain-dense)
     std::vector<double> gain_lnl(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
                                  const std::vector<double>& lambdas, const std::vector<double>& mus, double nu, double root_absent);
@@ -618,6 +621,8 @@ public:
     struct gain_origins gain_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
                                        const std::vector<double>& lambdas, const std::vector<double>& mus, const std::vector<double>& nus,
                                        double root_absent, const std::vector<const clade*>& order, bool dense = false);
+private:
+    bool _gain_scaled = false;
 };
 class hip_gamma_model : public hip_model_base {
     std::vector<double> _lambda_multipliers, _gamma_cat_probs;
@@ -1064,7 +1069,7 @@ gain_result fit_gain_model(const gain_scorer& score, const gain_table& table, in
                            const std::function<std::vector<double>()>& draw_lambdas);
 // Why the gain options cannot be combined with what else was asked for, or nullptr
 struct gain_request {
-    bool gain = false, estimate_gain = false, root_absent_given = false, unconditional = false, posterior = false, dense = false;
+    bool gain = false, estimate_gain = false, root_absent_given = false, unconditional = false, posterior = false, dense = false, scaled = false;
     double nu = 0, root_absent = 0;
     bool gamma = false, per_family = false, gpus = false, simulate = false, pvalues = false, reconstruct = false, marginal = false, histories = false,
          standard_errors = false, events = false, rate_shift = false, leaf_predictive = false, branch_change = false, rootdist_em = false,

@@ -9,7 +9,9 @@
 // rates -- one device call per point lists every distinct family once and the absent profile last.  It is evaluated under the
 // SUM rule: only there is the absent profile's value a probability (the max rule's is the largest term of it), and the driver
 // sets that rule for a gain run.  --gain-unconditional drops the correction.  --gain-dense scores every point, and the final table, by
-// cafe_score_gain instead: the same rates for every entry, each matrix built once, the families pruned together.
+// cafe_score_gain instead: the same rates for every entry, each matrix built once, the families pruned together; --gain-scaled
+// with it holds the dense panels as mantissas and binary exponents (cafe_set_gain_scaling), for tables whose families'
+// likelihoods lie below fp64's range and would otherwise make -lnL inf.
 //
 // The search is the Nelder-Mead of every other fit (optimizer / nm_search), over [lambdas..., mus (--estimate-mu)..., nu], nested
 // like -b --family-mu estimate: first the model without nu, then with nu from that optimum (start nu = lambda / 10, or nu held at
@@ -166,6 +168,7 @@ gain_result fit_gain_model(const gain_scorer& score, const gain_table& table, in
 }
 
 const char* gain_refusal(const gain_request& r) {
+    if (r.scaled && !r.dense) return "--gain-scaled is the scaled mode of the dense prune: give --gain-dense with it";
     if (!r.gain && !r.estimate_gain) {
         if (r.root_absent_given) return "--root-absent sets the root's mass at size 0 under the gain model: give --gain NU or --estimate-gain with it";
         if (r.unconditional) return "--gain-unconditional belongs to the gain model: give --gain NU or --estimate-gain with it";

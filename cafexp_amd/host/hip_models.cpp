@@ -289,6 +289,7 @@ std::vector<double> hip_base_model::gain_lnl(root_equilibrium_distribution* prio
     if (mus.size() != lambdas.size()) throw std::runtime_error("gain_lnl: one mu per lambda is required");
     const std::vector<double> nus(lambdas.size(), nu);
     std::vector<double> out(family.size());
+    cafe_set_gain_scaling(_ctx, _gain_scaled ? 1 : 0);
     if (cafe_score_gain(_ctx, &pr, lambdas.data(), mus.data(), nus.data(), root_absent, (int64_t)family.size(), family.data(), out.data()) != CAFE_OK)
         throw std::runtime_error(std::string("cafe_score_gain: ") + cafe_last_error(_ctx));
     return out;
@@ -313,6 +314,7 @@ gain_origins hip_base_model::gain_posterior(root_equilibrium_distribution* prior
     cafe_gain_posterior_out out{};
     out.lnl = res.lnl.data(); out.p_absent = p_absent.data(); out.mean = mean.data(); out.p_gain = p_gain.data(); out.p_loss = p_loss.data();
     if (dense) {
+        cafe_set_gain_scaling(_ctx, _gain_scaled ? 1 : 0);
         if (cafe_gain_posterior_dense(_ctx, &pr, lambdas.data(), mus.data(), nus.data(), root_absent, (int64_t)F, family.data(), &out) != CAFE_OK)
             throw std::runtime_error(std::string("cafe_gain_posterior_dense: ") + cafe_last_error(_ctx));
     } else if (cafe_gain_posterior(_ctx, &pr, (int64_t)F, family.data(), lambdas.data(), mus.data(), nus.data(), root_absent, &out) != CAFE_OK)

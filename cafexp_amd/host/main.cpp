@@ -83,7 +83,7 @@ static void usage() {
         "                  [--workspace BYTES] [-o OUTDIR]   writes OUTDIR (default results)/Base_lambda_per_family.txt, one line per family\n"
         "                  [--family-mu M1[,M2,..] | --family-mu estimate]   separate death rates per family (only with -b): fixed at the given\n"
         "                  rates, one per lambda, or searched with each family's lambdas (start mu = lambda); also writes Base_mu_per_family.txt\n"
-        "gene gain rate: cafexp_hip -t TREE -i FAMILIES (--gain NU | --estimate-gain) [--root-absent P0] [--gain-unconditional] [--gain-posterior] [--gain-dense] [-l LAMBDA | -m L1,L2,..]\n"
+        "gene gain rate: cafexp_hip -t TREE -i FAMILIES (--gain NU | --estimate-gain) [--root-absent P0] [--gain-unconditional] [--gain-posterior] [--gain-dense [--gain-scaled]] [-l LAMBDA | -m L1,L2,..]\n"
         "                  [-y LAMBDA_TREE] [--mu M1,.. | --estimate-mu] [-e ERRMODEL] [-p [L]] [-f ROOTDIST] [--missing TOKENS] [--mask-cells FILE] [-z] [-o OUTDIR]\n"
         "                  birth-death with immigration (n -> n+1 at rate n lambda + NU): a family absent in an ancestor can appear below it.  One set\n"
         "                  of rates for the table, fitted under the sum rule to the likelihood conditional on a family being seen in at least one\n"
@@ -94,6 +94,9 @@ static void usage() {
         "                  [--gain-dense]   score every point of the search, and the final table, by cafe_score_gain: each branch's matrix built\n"
         "                  once per point and all distinct families pruned together by fp64 MFMA GEMMs; values agree with the default path to rounding;\n"
         "                  with --gain-posterior the posterior runs on the same prune, by cafe_gain_posterior_dense\n"
+        "                  [--gain-scaled]   only with --gain-dense: the dense prune holds its panels as mantissas and one binary exponent per\n"
+        "                  (node, family), so families whose likelihood lies below fp64's range (trees of a few dozen taxa with counts that disagree\n"
+        "                  across clades) keep a finite -lnL and their posteriors; applies to the search and to --gain-posterior\n"
         "                  [--gain-posterior]   after the fit, at the fitted rates: for every family and node the posterior probability that the\n"
         "                  family is absent there and its mean size, and for every branch that it originated (parent absent, node present) or was\n"
         "                  lost (parent present, node absent) on it: OUTDIR/Gain_origins.tab (p_absent:mean per node, p_gain:p_loss per branch) and\n"
@@ -308,6 +311,7 @@ int main(int argc, char** argv) {
         else if (a == "--gain-unconditional") gain.unconditional = true;
         else if (a == "--gain-posterior") gain.posterior = true;
         else if (a == "--gain-dense") gain.dense = true;
+        else if (a == "--gain-scaled") gain.scaled = true;
         else { usage(); return 2; }
     }
     {                                                            // the gain model: refused before anything is read or written
@@ -533,6 +537,7 @@ int main(int argc, char** argv) {
             hip_base_model* base = static_cast<hip_base_model*>(mdl.get());      // -k / -a were refused above
             base->set_workspace_limit(sim_workspace);
             base->set_root_rule(CAFE_ROOT_SUM);                  // the absent profile's value is a probability under the sum rule only
+            base->set_gain_scaling(gain.scaled);                 // the search and --gain-posterior, through the two dense calls
             base->initialize_lambda(d.p_lambda_tree.get());
             std::unique_ptr<lambda> shape(base->get_lambda());
             const int L = shape->count();
@@ -613,6 +618,7 @@ int main(int argc, char** argv) {
             };
             std::printf("{\"model\": \"Gain\", \"root_rule\": \"sum\", \"conditional\": %s, \"families\": %zu, \"distinct_families\": %zu, ",
                         go.conditional ? "true" : "false", d.gene_families.size(), table.family.size() - 1);
+            if (gain.dense) std::printf("\"gain_dense_mode\": \"%s\", ", gain.scaled ? "scaled" : "plain");
             std::printf("\"neg_lnl\": %.17g, ", res.with.neg_lnl);
             list("lambda", res.with.lambdas); list("mu", res.with.mus);
             std::printf("\"nu\": %.17g, \"root_absent\": %.17g, \"p_absent\": %.17g, \"neg_lnl_without_gain\": %.17g, ", res.with.nu, go.root_absent, res.with.p_absent,

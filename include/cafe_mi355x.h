@@ -374,12 +374,14 @@ int cafe_score_per_family_gain(cafe_ctx* ctx, const cafe_params* params, int64_t
  * entry, a NaN lambda that passes the rule NaN; a rate * 1e9 beyond a long saturates the branch (rows >= 1 zero, row 0 kept).
  * A value depends on the family's counts and the rates only, never on its position in the list or on how the list was cut into
  * batches (whole 128-column tiles under workspace_limit, at most CAFE_PER_FAMILY_BATCH entries).  Values agree with
- * cafe_score_per_family_gain's to rounding, not bit for bit: a GEMM sums in another order.  cafe_family_results is not
- * meaningful after this call; a later cafe_score returns what it returned before. */
+ * cafe_score_per_family_gain's to rounding, not bit for bit: a GEMM sums in another order.  Plain fp64 without rescaling by
+ * default: a family whose likelihood lies below fp64's range gives -inf; cafe_set_gain_scaling (below) is the mode that
+ * survives it.  cafe_family_results is not meaningful after this call; a later cafe_score returns what it returned before. */
 int cafe_score_gain(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus,
                     double root_absent, int64_t n, const int64_t* family, double* family_lnl);
 /* The last cafe_score_gain: summed HIP-event ms of its build, product, GEMM and root launches (0 unless cafe_set_profiling was
- * on) and the flops its GEMM launches issued. */
+ * on) and the flops its GEMM launches issued.  In the scaled mode (cafe_set_gain_scaling) the product and root figures are
+ * those of the scaled kernels. */
 int cafe_debug_gain_dense(cafe_ctx* ctx, double ms[4], double* flops);
 /* Row 0 of the gain model's matrix for the key (lambda, mu, nu, t): the three rates quantized like a lambda, t like a branch
  * length, alpha and beta cafe_bd_rates'.  out[k] = C(r+k-1, k) (1-beta)^r beta^k, k < n, r = nu / lambda (written to out_r[0]
@@ -440,8 +442,26 @@ int cafe_gain_posterior(cafe_ctx* ctx, const cafe_params* params, int64_t n, con
 int cafe_gain_posterior_dense(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus,
                               double root_absent, int64_t n, const int64_t* family, const cafe_gain_posterior_out* out);
 /* The last cafe_gain_posterior_dense: summed HIP-event ms of its build, product, GEMM, root, weights, transposed GEMM, interior
- * output and leaf output launches (0 unless cafe_set_profiling was on) and the flops both GEMMs issued. */
+ * output and leaf output launches (0 unless cafe_set_profiling was on) and the flops both GEMMs issued.  In the scaled mode the
+ * product, root, weights and output figures are those of the scaled kernels; the build and both GEMMs are the same launches. */
 int cafe_debug_gain_dense_posterior(cafe_ctx* ctx, double ms[8], double* flops);
+/* The scaled mode of cafe_score_gain and cafe_gain_posterior_dense (no other entry reads it); on != 0 switches it on, the
+ * default is off.  A family's likelihood is a product over the whole tree and leaves fp64's range on trees of a few dozen taxa
+ * whose counts disagree across clades: the plain path then answers lnl = -inf (NaN in every posterior output).  In the scaled
+ * mode every likelihood panel is held as mantissas and one int32 binary exponent per (node, column), chosen so that the
+ * column's largest entry over the node's sizes has binary exponent 0 (an all-zero column and a column holding a NaN: exponent 0,
+ * stored as it is).  The product and the weights are formed by kernels that own a column over all the node's sizes and track
+ * every element as (double, int) while the children are multiplied in, so a many-way product does not underflow half way;
+ * both GEMMs run unchanged on the mantissas -- a power of two per column commutes with them -- and their outputs carry their
+ * inputs' exponents.  lnl is the root's scaled log-sum (or maximum, by the root rule) plus E_root ln 2; every posterior output
+ * is a ratio of scaled operands against the scaled evidence, shifted by the exponent difference with ldexp, never through
+ * exp(lnl).  Matrix entries themselves stay plain fp64: an entry below fp64's range is 0 in either mode.  Where nothing leaves
+ * the normal range every mantissa is the plain path's bit for bit, and values agree to rounding (lnl adds E_root ln 2 in
+ * floating point).  What one exponent per column cannot hold: an entry more than 1074 binary orders under the largest of its
+ * column is 0, so a posterior output built from such an entry comes out 0 even where its own value is representable (a root
+ * size whose panel entry lies that far under size 0's while root_absent = 0 gives size 0 no mass).  Checks, host-decided values, the batch cut and the independence of a value from its place in the list are
+ * those of the two entries; the workspace holds 4 more bytes per panel and column.  CAFE_ERR_ARGUMENT for a NULL ctx. */
+int cafe_set_gain_scaling(cafe_ctx* ctx, int on);
 
 /* Separate birth and death rates.  The reference fits the critical process lambda = mu only; with death rates set a context
  * scores the linear birth-death process with birth rate lambdas[i] and death rate mus[i] per lineage on the branches of

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """cafe_score_gain (the dense prune, gain_dense.hip) next to cafe_score_per_family_gain with the same rates tiled.
 
-    python tools/gain_dense_time.py [OUT.json]     (on a machine with the GPU)
+    python tools/gain_dense_time.py [--scaled] [OUT.json]     (on a machine with the GPU; --scaled: cafe_set_gain_scaling on)
 
 One process.  The two lists DESIGN section 8 quotes for the gain entry: the distinct families of the mammals table (order 141,
 7 repetitions) and 3000 families of the bench table (100 taxa, order 751, 3 repetitions), ONE rate set for the list, mu = lambda,
@@ -21,6 +21,7 @@ sys.path.insert(0, ROOT)
 from cafexp_amd import capi, problem as P, synth  # noqa: E402
 
 DATA = os.path.join(ROOT, "tests", "golden", "data")
+SCALED = "--scaled" in sys.argv[1:]
 
 
 def read(name):
@@ -36,6 +37,8 @@ def alternated(name, pb, fam, lam, nu_over_lam, reps):
     times = {"cafe_score_per_family_gain": [], "cafe_score_gain": []}
     try:
         ctx.set_root_rule("sum")
+        if SCALED:
+            ctx.set_gain_scaling(True)
         calls = {"cafe_score_per_family_gain": lambda: ctx.score_per_family_gain(pr, fam, *tiled, 0.1),
                  "cafe_score_gain": lambda: ctx.score_gain(pr, fam, [lam], [lam], [nu], 0.1)}
         a, b = calls["cafe_score_per_family_gain"](), calls["cafe_score_gain"]()
@@ -62,7 +65,7 @@ def alternated(name, pb, fam, lam, nu_over_lam, reps):
                          repetitions=reps, median_ms=float(np.median(t)), min_ms=min(t), max_ms=max(t)))
         print(json.dumps(rows[-1]), flush=True)
     med = np.median(np.array(split), axis=0)
-    rows.append(dict(table=name, nu_over_lambda=nu_over_lam, ratio_of_medians=rows[0]["median_ms"] / rows[1]["median_ms"], finite=int(both.sum()), finite_in_one_only=mismatched,
+    rows.append(dict(table=name, scaled=SCALED, nu_over_lambda=nu_over_lam, ratio_of_medians=rows[0]["median_ms"] / rows[1]["median_ms"], finite=int(both.sum()), finite_in_one_only=mismatched,
                      largest_relative_difference=rel, build_ms=med[0], product_ms=med[1], gemm_ms=med[2], root_ms=med[3], gemm_flops_issued=med[4],
                      gemm_tflops=med[4] / (med[2] * 1e-3) / 1e12 if med[2] > 0 else None))
     print(json.dumps(rows[-1]), flush=True)
@@ -78,8 +81,9 @@ def main():
     for ratio in (0.0, 0.3):
         rows += alternated("mammal_gene_families.txt, distinct families", mammals, distinct, 0.005, ratio, 7)
         rows += alternated("bench table (100 taxa, order 751)", bench, np.arange(bench.n_families), 0.002, ratio, 3)
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
+    out = [a for a in sys.argv[1:] if a != "--scaled"]
+    if out:
+        with open(out[0], "w") as f:
             json.dump({"rows": rows}, f, indent=1)
             f.write("\n")
 
