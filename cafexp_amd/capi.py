@@ -82,6 +82,10 @@ class CafeGainPosteriorOut(C.Structure):
     _fields_ = [("lnl", _f64p), ("p_absent", _f64p), ("mean", _f64p), ("p_gain", _f64p), ("p_loss", _f64p), ("posterior", _f64p)]
 
 
+class CafeGainLeafPredictiveOut(C.Structure):
+    _fields_ = [("lnl", _f64p), ("mean", _f64p), ("sd", _f64p), ("p_below", _f64p), ("p_obs", _f64p), ("p_above", _f64p)]
+
+
 class CafeLeafPredictiveOut(C.Structure):
     _fields_ = [("mean", _f64p), ("sd", _f64p), ("p_below", _f64p), ("p_obs", _f64p), ("p_above", _f64p), ("log_evidence", _f64p),
                 ("failed", _i32p)]
@@ -148,7 +152,7 @@ EXPORTS = [
     "cafe_score_per_family_gain", "cafe_bd_gain_row0", "cafe_debug_narrowed_extents", "cafe_gain_posterior",
     "cafe_debug_pvalues_stages", "cafe_debug_sort_rows", "cafe_debug_tree_pvalue",
     "cafe_score_gain", "cafe_debug_gain_dense",
-    "cafe_gain_posterior_dense", "cafe_debug_gain_dense_posterior", "cafe_set_gain_scaling",
+    "cafe_gain_posterior_dense", "cafe_debug_gain_dense_posterior", "cafe_set_gain_scaling", "cafe_gain_leaf_predictive", "cafe_debug_gain_predictive",
 ]
 CAFE_CHANGE_NONE = -(1 << 31)   # mode / lo / hi of cafe_branch_change at the root and in a failed family
 CAFE_COMM_ID_BYTES = 128
@@ -241,6 +245,11 @@ def load():
                                             C.POINTER(CafeGainPosteriorOut)]
     L.cafe_debug_gain_dense_posterior.restype = C.c_int
     L.cafe_debug_gain_dense_posterior.argtypes = [C.c_void_p, _f64p, _f64p]
+    L.cafe_gain_leaf_predictive.restype = C.c_int
+    L.cafe_gain_leaf_predictive.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p, _f64p, _f64p, C.c_double, C.c_int64, _i64p,
+                                            C.POINTER(CafeGainLeafPredictiveOut)]
+    L.cafe_debug_gain_predictive.restype = C.c_int
+    L.cafe_debug_gain_predictive.argtypes = [C.c_void_p, _f64p, _f64p]
     L.cafe_set_gain_scaling.restype = C.c_int
     L.cafe_set_gain_scaling.argtypes = [C.c_void_p, C.c_int]
     L.cafe_bd_gain_row0.restype = C.c_int
@@ -647,6 +656,35 @@ class Context:
         the last gain_posterior_dense -- 0 unless profiling was on --, the flops its two GEMMs issued)"""
         ms, flops = np.zeros(8), np.zeros(1)
         self._check(self._lib.cafe_debug_gain_dense_posterior(self._h, _p(ms, _f64p), _p(flops, _f64p)))
+        return ms, float(flops[0])
+
+    def gain_leaf_predictive(self, pr: Params, families, lambdas, mus, nus, root_absent: float = 0.0) -> dict:
+        """cafe_gain_leaf_predictive: under the gain model with ONE set of rates (score_gain's arguments), for every listed family
+        and taxon the distribution of the taxon's count given the counts of every other species: mean, sd, p_below, p_obs and
+        p_above [n][n_taxa] (columns as the problem's counts; the p's are the mass below, at and above the observed count, NaN
+        for a missing cell) and lnl [n], score_gain's under the sum rule bit for bit."""
+        fam = np.ascontiguousarray(families, dtype=np.int64).reshape(-1)
+        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(-1)
+        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(-1)
+        mu = None if mus is None else np.ascontiguousarray(mus, dtype=np.float64).reshape(-1)
+        if len(lam) != self.problem.n_lambdas or nu.shape != lam.shape or (mu is not None and mu.shape != lam.shape):
+            raise ValueError("lambdas, mus and nus must be [%d]" % self.problem.n_lambdas)
+        cp, keep = self._params(pr)
+        n, taxa = len(fam), self.problem.n_taxa
+        res = {"lnl": np.empty(n)}
+        res.update({key: np.empty((n, taxa)) for key in ("mean", "sd", "p_below", "p_obs", "p_above")})
+        out = CafeGainLeafPredictiveOut()
+        for name, array in res.items():
+            setattr(out, name, _p(array, _f64p))
+        self._check(self._lib.cafe_gain_leaf_predictive(self._h, C.byref(cp), _p(lam, _f64p), None if mu is None else _p(mu, _f64p), _p(nu, _f64p),
+                                                        float(root_absent), n, _p(fam, _i64p), C.byref(out)))
+        return res
+
+    def gain_predictive_profile(self):
+        """(HIP-event ms of the build, product, GEMM, root, weights, transposed GEMM and fused leaf launches of the last
+        gain_leaf_predictive -- 0 unless profiling was on --, the flops its three MFMA kernels issued)"""
+        ms, flops = np.zeros(7), np.zeros(1)
+        self._check(self._lib.cafe_debug_gain_predictive(self._h, _p(ms, _f64p), _p(flops, _f64p)))
         return ms, float(flops[0])
 
     def set_gain_scaling(self, on: bool):

@@ -503,25 +503,19 @@ struct GainGemmTArgs {
     int32_t nr, ldp;                 // rows c = 0..nr-1 of the outside panel
 };
 
-// grid (column tiles, row tiles of M + 1, interior non-root nodes of the depth)
-__global__ __launch_bounds__(256) void gain_posterior_dense_gemm_t_kernel(const GainGemmTArgs a) {
-    __shared__ __attribute__((aligned(16))) double As[2][kGdKT * kGdLdA];
-    __shared__ __attribute__((aligned(16))) double Xs[2][kGdKT * kGdLdX];
-    const GainGemmTOp op = a.ops[blockIdx.z];
-    const int r0 = blockIdx.y * kGdMT;
+// One 64 x 128 tile of that product: acc = A[r0 .. r0 + 63][0 .. nk) X[0 .. nk)[c0 .. c0 + 127], the K loop of both kernels that
+// contract over a matrix as stored.  Ends behind a barrier: the buffers are free for the caller's next tile.
+typedef double gd4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void gain_dense_tile_t(double (*As)[kGdKT * kGdLdA], double (*Xs)[kGdKT * kGdLdX], const double* __restrict__ mat,
+                                                  const double* __restrict__ X, int r0, int nr, int nk, int ldp, int64_t ld, int64_t c0, gd4 (&acc)[4][2]) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     const int arow = tid >> 2, aq = tid & 3;           // A staging: row of the tile, quad of k
-    const int64_t c0 = (int64_t)blockIdx.x * kGdCols, ld = a.ld;
-    const int nr = a.nr, nk = op.nk, ldp = a.ldp;
-    const double* __restrict__ Pt = a.mats + op.Pt + (int64_t)(r0 + arow) * ldp;
-    const double* __restrict__ X = a.panels + op.W;
-    typedef double d4 __attribute__((ext_vector_type(4)));
-    d4 acc[4][2];
+    const double* __restrict__ Pt = mat + (int64_t)(r0 + arow) * ldp;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
+        for (int j = 0; j < 2; ++j) acc[i][j] = (gd4){0.0, 0.0, 0.0, 0.0};
     double2 ra[2], rx[4];
     auto load = [&](int k0) {
 #pragma unroll
@@ -572,6 +566,18 @@ __global__ __launch_bounds__(256) void gain_posterior_dense_gemm_t_kernel(const 
         if (more) stage(buf ^ 1);                      // the other pair: its readers passed the barrier of the step before
         __syncthreads();
     }
+}
+
+// grid (column tiles, row tiles of M + 1, interior non-root nodes of the depth)
+__global__ __launch_bounds__(256) void gain_posterior_dense_gemm_t_kernel(const GainGemmTArgs a) {
+    __shared__ __attribute__((aligned(16))) double As[2][kGdKT * kGdLdA];
+    __shared__ __attribute__((aligned(16))) double Xs[2][kGdKT * kGdLdX];
+    const GainGemmTOp op = a.ops[blockIdx.z];
+    const int r0 = blockIdx.y * kGdMT, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l15 = lane & 15, l4 = lane >> 4, nr = a.nr;
+    const int64_t c0 = (int64_t)blockIdx.x * kGdCols, ld = a.ld;
+    gd4 acc[4][2];
+    gain_dense_tile_t(As, Xs, a.mats + op.Pt, a.panels + op.W, r0, nr, op.nk, a.ldp, ld, c0, acc);
     double* __restrict__ O = a.panels + op.O;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -762,8 +768,121 @@ __global__ __launch_bounds__(256) void gain_scaled_leaf_kernel(const GainOutArgs
     gain_posterior_dense_leaf<true>(a, red, exps);
 }
 
+// -------------------------------------------------------------------------------------- down: leave-one-out predictive
+// cafe_gain_leaf_predictive wants, for a leaf l, the whole of O_l = P_l^T w_l -- what the rest of the tree says of EVERY count the
+// leaf might have shown -- but only six sums of each of its columns, so the transposed GEMM's tile runs with an epilogue that
+// reduces the accumulators over c instead of storing them: no O panel ever reaches memory.  A workgroup owns (leaf, column tile)
+// and walks the row tiles of 0..M in ascending order, re-reading its w tile (from L2) for each; the six sums of a column stay in
+// the registers of the lanes that hold it.  An observed value y sees the true size c = y - half + t with weight err[y][t] (no
+// error model: y = c, weight 1), so element O[c][f] goes, for the taps t ascending with 0 <= y <= M, as e = err[y][t] O[c][f] into
+//   W += e, S1 += (y - x) e, S2 += (y - x)^2 e, and below, obs or above by y < x, y = x, y > x
+// about the pivot x, the column's observed count (0 for a missing cell): a cell that sits where the model expects it keeps its
+// variance.  A lane adds its 16 rows of a tile in ascending order; the four 16-lane groups that share a column meet at the end
+// by two cross-lane exchanges, (g0 + g1) + (g2 + g3).  No atomics, and nothing of a column depends on its neighbours, its tile
+// or the batch.  Every output is a ratio inside one column of one w panel: in the scaled mode the column's power of two
+// cancels exactly and the kernel runs on the mantissas as it is.  res is [5][n_taxa][ld]: mean, sd, p_below, p_obs, p_above.
+struct GainPredOp {
+    int64_t Pt, W;                   // the leaf's matrix (doubles from `mats`), its w panel (doubles from `panels`)
+    int32_t nk;                      // rows(l): the parent's sizes, the contraction
+    int32_t taxon;                   // the leaf's row of `counts` and of res
+};
+struct GainPredArgs {
+    const GainPredOp* ops;
+    const double* mats;
+    const double* panels;
+    double* res;
+    const int64_t* col;
+    const int32_t* counts;
+    const double* err;               // [(M+1)][n_dev] or nullptr
+    int64_t counts_ld, ld;
+    int32_t nr, ldp, n_dev, n_taxa;  // nr = M + 1
+};
+
+// grid (column tiles, leaves of the depth)
+__global__ __launch_bounds__(256) void gain_predictive_dense_leaf_kernel(const GainPredArgs a) {
+    __shared__ __attribute__((aligned(16))) double As[2][kGdKT * kGdLdA];
+    __shared__ __attribute__((aligned(16))) double Xs[2][kGdKT * kGdLdX];
+    const GainPredOp op = a.ops[blockIdx.y];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, l4 = lane >> 4;
+    const int64_t c0 = (int64_t)blockIdx.x * kGdCols, ld = a.ld;
+    const int nr = a.nr;
+    int x[2];
+    bool missing[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int64_t col = a.col[c0 + 32 * wave + 16 * j + l15];
+        const int cnt = col >= 0 ? a.counts[(int64_t)op.taxon * a.counts_ld + col] : 0;
+        missing[j] = count_is_missing(cnt);
+        x[j] = missing[j] ? 0 : cnt;
+    }
+    double sum[2][6];                                  // W, S1, S2, below, obs, above of the lane's two columns
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) sum[j][k] = 0.0;
+    auto add = [&](int j, int y, double e) {           // the observed value y with mass e, about the pivot x[j]
+        const double dy = (double)(y - x[j]);
+        sum[j][0] += e;
+        sum[j][1] = fma(dy, e, sum[j][1]);
+        sum[j][2] = fma(dy * dy, e, sum[j][2]);
+        sum[j][3] += y < x[j] ? e : 0.0;
+        sum[j][4] += y == x[j] ? e : 0.0;
+        sum[j][5] += y > x[j] ? e : 0.0;
+    };
+    for (int r0 = 0; r0 < nr; r0 += kGdMT) {
+        gd4 acc[4][2];
+        gain_dense_tile_t(As, Xs, a.mats + op.Pt, a.panels + op.W, r0, nr, op.nk, a.ldp, ld, c0, acc);
+        if (a.err == nullptr) {                        // (kernel-uniform) no error model: y = c, weight 1 -- no tap loop, no load
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int c = r0 + 16 * i + l4 + 4 * q;
+                    if (c >= nr) continue;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) add(j, c, acc[i][j][q]);
+                }
+            continue;
+        }
+        const int half = (a.n_dev - 1) / 2;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = r0 + 16 * i + l4 + 4 * q;
+                if (c >= nr) continue;
+                for (int t = 0; t < a.n_dev; ++t) {
+                    const int y = c + half - t;
+                    if (y < 0 || y >= nr) continue;
+                    const double wt = a.err[(int64_t)y * a.n_dev + t];
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) add(j, y, wt * acc[i][j][q]);
+                }
+            }
+    }
+    const double nan = __builtin_nan("");
+    const int64_t plane = (int64_t)a.n_taxa * ld;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            sum[j][k] += __shfl_xor(sum[j][k], 16);
+            sum[j][k] += __shfl_xor(sum[j][k], 32);
+        }
+        if (l4 != 0) continue;
+        const double W = sum[j][0], m1 = sum[j][1] / W;
+        const bool ok = W > 0.0 && isfinite(W);        // a predictive distribution without mass: NaN in all five
+        double* __restrict__ out = a.res + (int64_t)op.taxon * ld + c0 + 32 * wave + 16 * j + l15;
+        out[0] = ok ? (double)x[j] + m1 : nan;
+        out[plane] = ok ? sqrt(fmax(sum[j][2] / W - m1 * m1, 0.0)) : nan;
+        out[2 * plane] = ok && !missing[j] ? sum[j][3] / W : nan;
+        out[3 * plane] = ok && !missing[j] ? sum[j][4] / W : nan;
+        out[4 * plane] = ok && !missing[j] ? sum[j][5] / W : nan;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host
-enum { kGdBuild = 0, kGdProduct = 1, kGdGemm = 2, kGdRoot = 3, kGdWeights = 4, kGdGemmT = 5, kGdInterior = 6, kGdLeaf = 7, kGdKinds = 8 };
+enum { kGdBuild = 0, kGdProduct = 1, kGdGemm = 2, kGdRoot = 3, kGdWeights = 4, kGdGemmT = 5, kGdInterior = 6, kGdLeaf = 7, kGdPredict = 8, kGdKinds = 9 };
 
 // HIP events around the launches of a call, by kind (cafe_set_profiling)
 struct GainTimer {
@@ -811,10 +930,27 @@ struct GainDownHost {
     }
 };
 
-// Both entries: the planning (keys, levels, op tables, workspace), the up pass launch for launch, and -- with `down`, the
-// posterior entry -- the sum rule forced at the root, the plan and the launches of the down pass behind the root kernel.
+// The same for cafe_gain_leaf_predictive: five numbers per (entry, taxon)
+struct GainPredictHost {
+    const cafe_gain_leaf_predictive_out* out;
+    std::vector<double> res;                           // [5][n_taxa][nb]
+
+    void collect(int64_t b0, int64_t nb, int T, const double* lnl) const {
+        double* const dst[5] = {out->mean, out->sd, out->p_below, out->p_obs, out->p_above};
+        for (int64_t b = 0; b < nb; ++b) {
+            if (!std::isfinite(lnl[b])) continue;      // the entry keeps its NaN
+            for (int k = 0; k < 5; ++k)
+                for (int t = 0; dst[k] && t < T; ++t) dst[k][(b0 + b) * T + t] = res[((size_t)k * T + t) * nb + b];
+        }
+    }
+};
+
+// All three entries: the planning (keys, levels, op tables, workspace), the up pass launch for launch, and -- with `down`, the
+// posterior entry, or `pred`, the predictive one -- the sum rule forced at the root, the plan and the launches of the down pass
+// behind the root kernel.  Both walk the depths with the weights kernel and the transposed GEMM of the interior nodes; `down` adds
+// the output kernels of every node, `pred` the fused kernel of the depth's leaves.
 int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const double* lam, const double* mus, const double* nus, double root_absent,
-                    int64_t n, const int64_t* family, double* family_lnl, GainDownHost* down) {
+                    int64_t n, const int64_t* family, double* family_lnl, GainDownHost* down, GainPredictHost* pred = nullptr) {
     if (!pr || !pr->prior) { set_err(c, "%s: params with a prior are required", who); return CAFE_ERR_ARGUMENT; }
     if (pr->model != CAFE_MODEL_BASE) { set_err(c, "%s: base model only", who); return CAFE_ERR_ARGUMENT; }
     if (c->comm) { set_err(c, "%s: not valid on a context with a communicator attached", who); return CAFE_ERR_STATE; }
@@ -836,10 +972,15 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
 
     // ---- what the host decides alone: an invalid rate set is -inf in every entry, a NaN lambda that passes the rule NaN
     c->last.state = LastCall::kNone;                   // cafe_family_results is not meaningful after this call
-    double ms[kGdKinds] = {0, 0, 0, 0, 0, 0, 0, 0}, flops = 0.0;
+    const bool walk = down || pred;                    // the down pass is planned and run
+    const int T = c->n_taxa;
+    double ms[kGdKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, flops = 0.0;
     if (down) {
-        std::copy(ms, ms + kGdKinds, c->gain_dense_posterior_ms);
+        std::copy(ms, ms + 8, c->gain_dense_posterior_ms);
         c->gain_dense_posterior_flops = 0.0;
+    } else if (pred) {
+        std::copy(ms, ms + 7, c->gain_predictive_ms);
+        c->gain_predictive_flops = 0.0;
     } else {
         std::copy(ms, ms + 4, c->gain_dense_ms);
         c->gain_dense_flops = 0.0;
@@ -882,7 +1023,7 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
     std::vector<int> depth(nn, 0), by_depth{c->root}, depth_off{0}, oidx(nn, -1), widx(nn, -1);
     int n_down = 0, n_depths = 0;
     const bool want_posterior = down && down->out->posterior;
-    if (down) {
+    if (walk) {
         int n_out = 0, widest = 0;
         for (size_t at = 0; at < by_depth.size(); ++at)
             for (int ch : c->children[by_depth[at]]) { depth[ch] = depth[by_depth[at]] + 1; by_depth.push_back(ch); }
@@ -904,9 +1045,9 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
     const size_t fixed_bytes = sizeof(double) * (size_t)mat_stride * n_keys + ((size_t)64 << 10) + sizeof(GainChild) * (size_t)nn +
                                sizeof(GainProdOp) * (size_t)nn + sizeof(GainGemmOp) * (size_t)nn + sizeof(SlotParamGain) * (size_t)n_keys +
                                sizeof(double) * ((size_t)R + 1 + (size_t)(M + 1) * c->n_dev) +
-                               (down ? (sizeof(GainChild) + sizeof(GainWeightOp) + sizeof(GainGemmTOp) + sizeof(GainNodeOp)) * (size_t)nn + sizeof(double) * ((size_t)R + 1) : 0);
+                               (walk ? (sizeof(GainChild) + sizeof(GainWeightOp) + sizeof(GainGemmTOp) + sizeof(GainNodeOp) + sizeof(GainPredOp)) * (size_t)nn + sizeof(double) * ((size_t)R + 1) : 0);
     const size_t column_bytes = sizeof(double) * (size_t)n_pan * N + sizeof(int64_t) + sizeof(double) +
-                                (down ? sizeof(double) * ((size_t)n_down * N + 4 * (size_t)nn + (want_posterior ? (size_t)nn * N : 0)) : 0) +
+                                (walk ? sizeof(double) * ((size_t)n_down * N + (pred ? 5 * (size_t)T : 4 * (size_t)nn) + (want_posterior ? (size_t)nn * N : 0)) : 0) +
                                 (scaled ? sizeof(int32_t) * (size_t)(n_pan + n_down) + sizeof(double) : 0);     // the exponents, log Z~
     size_t budget = 0;
     HIP_TRY(c, workspace_budget(c->workspace_limit, c->pf_dev_bytes, &budget));
@@ -949,6 +1090,7 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
     std::vector<GainWeightOp> weight_ops;
     std::vector<GainGemmTOp> gemmt_ops;
     std::vector<GainNodeOp> int_ops, leaf_ops;
+    std::vector<GainPredOp> pred_ops;                  // (a leaf has an entry in both leaf tables: leaf_off serves both)
     std::vector<int> weight_off{0}, gemmt_off{0}, int_off{0}, leaf_off{0}, weight_rows;
     for (int d = 0; d < n_depths; ++d) {
         int w_rows = 0;
@@ -970,6 +1112,7 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
             w_rows = std::max(w_rows, rows);
             if (c->leaf_taxon[u] >= 0) {
                 leaf_ops.push_back({-1, -1, widx[u] * pan_stride, node_key[u] * mat_stride, u, M + 1, rows, c->leaf_taxon[u]});
+                pred_ops.push_back({node_key[u] * mat_stride, widx[u] * pan_stride, rows, c->leaf_taxon[u]});
                 continue;
             }
             gemmt_ops.push_back({node_key[u] * mat_stride, widx[u] * pan_stride, oidx[u] * pan_stride, rows, 0});
@@ -980,7 +1123,7 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
         weight_rows.push_back(w_rows);
     }
     std::vector<double> mass;                          // the root's outside vector, beside logmass
-    if (down) {
+    if (walk) {
         mass.resize((size_t)R + 1);
         mass[0] = root_absent;
         for (int j = 1; j <= R; ++j) mass[j] = (1.0 - root_absent) * (double)pr->prior[j - 1];
@@ -994,11 +1137,11 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
     std::vector<char> blob;
     const size_t o_children = put(blob, children), o_prod = put(blob, prod_ops), o_gemm = put(blob, gemm_ops), o_slots = put(blob, slots),
                  o_reals = put(blob, reals), o_weight = put(blob, weight_ops), o_gemmt = put(blob, gemmt_ops), o_int = put(blob, int_ops),
-                 o_leaf = put(blob, leaf_ops), o_mass = put(blob, mass);
+                 o_leaf = put(blob, leaf_ops), o_pred = put(blob, pred_ops), o_mass = put(blob, mass);
     const size_t o_col = family_align_up(blob.size()), o_out = o_col + family_align_up(sizeof(int64_t) * ld),
                  o_mats = o_out + family_align_up(sizeof(double) * ld), o_pan = o_mats + family_align_up(sizeof(double) * (size_t)mat_stride * n_keys),
                  o_res = o_pan + sizeof(double) * (size_t)pan_stride * (n_pan + n_down),
-                 o_post = o_res + (down ? sizeof(double) * 4 * (size_t)nn * ld : 0),
+                 o_post = o_res + sizeof(double) * (down ? 4 * (size_t)nn : pred ? 5 * (size_t)T : 0) * ld,
                  o_exps = o_post + (want_posterior ? sizeof(double) * (size_t)nn * N * ld : 0),
                  o_zt = o_exps + (scaled ? family_align_up(sizeof(int32_t) * (size_t)(n_pan + n_down) * ld) : 0),
                  need = o_zt + (scaled ? sizeof(double) * ld : 0);
@@ -1034,7 +1177,7 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
     pa.n_dev = c->n_dev; pa.M = M; pa.ldp = ldp;
     GainGemmArgs ga{reinterpret_cast<const GainGemmOp*>(base + o_gemm), mats, panels, ld, M + 1, ldp};
     GainRootArgs ra{panels + bidx[c->root] * pan_stride, d_reals, reinterpret_cast<double*>(base + o_out), ld, R,
-                    down || c->root_rule == CAFE_ROOT_SUM ? 1 : 0};
+                    walk || c->root_rule == CAFE_ROOT_SUM ? 1 : 0};
     GainWeightArgs wa{pa, reinterpret_cast<const GainWeightOp*>(base + o_weight), reinterpret_cast<const double*>(base + o_mass)};
     GainGemmTArgs ta{reinterpret_cast<const GainGemmTOp*>(base + o_gemmt), mats, panels, ld, M + 1, ldp};
     GainOutArgs oa{};
@@ -1043,6 +1186,7 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
     oa.col = pa.col; oa.counts = pa.counts; oa.err = pa.err; oa.counts_ld = pa.counts_ld; oa.ld = ld;
     oa.nn = nn; oa.N = N; oa.M = M; oa.ldp = ldp; oa.n_dev = c->n_dev; oa.any_missing = c->has_missing ? 1 : 0;
     oa.root_B = bidx[c->root] * pan_stride;
+    GainPredArgs qa{reinterpret_cast<const GainPredOp*>(base + o_pred), mats, panels, oa.res, pa.col, pa.counts, pa.err, pa.counts_ld, ld, M + 1, ldp, c->n_dev, T};
     const GainScaleArgs sa{reinterpret_cast<int32_t*>(base + o_exps), N};
     const int32_t* root_exps = sa.exps + bidx[c->root] * ld;
     double* zt = reinterpret_cast<double*>(base + o_zt);
@@ -1051,6 +1195,7 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
         down->res.resize(4 * (size_t)nn * entries);
         if (want_posterior) down->posterior.resize((size_t)nn * N * entries);
     }
+    if (pred) pred->res.resize(5 * (size_t)T * entries);
 
     std::vector<int64_t> col((size_t)ld);
     std::vector<double> res((size_t)ld);
@@ -1111,6 +1256,17 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
                 for (int k = gemmt_off[d]; k < gemmt_off[d + 1]; ++k)
                     flops += 2.0 * round_up(M + 1, kGdMT) * (double)round_up(gemmt_ops[k].nk, kGdKT) * (double)cols;
             }
+            if (pred) {                                // the leaves' six sums straight from the MFMA accumulators; no other output
+                if (nl == 0) continue;
+                GainPredArgs q = qa;
+                q.ops += leaf_off[d];
+                timer.mark(kGdPredict, s);
+                CAFE_LAUNCH(c, gain_predictive_dense_leaf_kernel, dim3(tiles, (unsigned)nl), dim3(256), 0, s, q);
+                timer.mark(kGdPredict, s);
+                for (int k = leaf_off[d]; k < leaf_off[d + 1]; ++k)
+                    flops += 2.0 * round_up(M + 1, kGdMT) * (double)round_up(pred_ops[k].nk, kGdKT) * (double)cols;
+                continue;
+            }
             GainOutArgs o = oa;
             if (ni > 0) {
                 o.ops = reinterpret_cast<const GainNodeOp*>(base + o_int) + int_off[d];
@@ -1138,12 +1294,22 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
                 HIP_TRY(c, hipMemcpy2DAsync(down->posterior.data(), sizeof(double) * nb, oa.posterior, sizeof(double) * ld, sizeof(double) * nb, (size_t)nn * N,
                                             hipMemcpyDeviceToHost, s));
         }
+        if (pred)
+            HIP_TRY(c, hipMemcpy2DAsync(pred->res.data(), sizeof(double) * nb, oa.res, sizeof(double) * ld, sizeof(double) * nb, 5 * (size_t)T,
+                                        hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));            // the host tables of this batch go out of use
         std::copy(res.begin(), res.begin() + nb, family_lnl + b0);
         if (down) down->collect(b0, nb, nn, N, res.data());
+        if (pred) pred->collect(b0, nb, T, res.data());
     }
     timer.collect(ms);
-    std::copy(ms, ms + (down ? (int)kGdKinds : 4), down ? c->gain_dense_posterior_ms : c->gain_dense_ms);
+    if (pred) {
+        ms[6] = ms[kGdPredict];                        // build, product, GEMM, root, weights, transposed GEMM, fused leaf
+        std::copy(ms, ms + 7, c->gain_predictive_ms);
+        c->gain_predictive_flops = flops;
+        return CAFE_OK;
+    }
+    std::copy(ms, ms + (down ? 8 : 4), down ? c->gain_dense_posterior_ms : c->gain_dense_ms);
     (down ? c->gain_dense_posterior_flops : c->gain_dense_flops) = flops;
     return CAFE_OK;
 }
@@ -1200,5 +1366,29 @@ int cafe_debug_gain_dense_posterior(cafe_ctx* ctx, double ms[8], double* flops) 
     if (!ctx) return CAFE_ERR_ARGUMENT;
     for (int k = 0; ms && k < 8; ++k) ms[k] = ctx->gain_dense_posterior_ms[k];
     if (flops) *flops = ctx->gain_dense_posterior_flops;
+    return CAFE_OK;
+}
+
+int cafe_gain_leaf_predictive(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus, double root_absent,
+                              int64_t n, const int64_t* family, const cafe_gain_leaf_predictive_out* out) {
+    const char* const who = "cafe_gain_leaf_predictive";
+    const int rc = cafe::guarded(ctx, who, [&] {
+        if (!out) { cafe::set_err(ctx, "%s: out is required", who); return (int)CAFE_ERR_ARGUMENT; }
+        std::vector<double> own_lnl;
+        double* lnl = out->lnl;
+        if (!lnl && n > 0) { own_lnl.resize((size_t)n); lnl = own_lnl.data(); }
+        for (double* p : {out->mean, out->sd, out->p_below, out->p_obs, out->p_above})      // what no finite lnl replaces
+            if (p && n > 0) std::fill(p, p + (size_t)n * ctx->n_taxa, std::numeric_limits<double>::quiet_NaN());
+        cafe::GainPredictHost pred{out, {}};
+        return cafe::gain_dense_impl(ctx, who, params, lambdas, mus, nus, root_absent, n, family, lnl, nullptr, &pred);
+    });
+    if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
+    return rc;
+}
+
+int cafe_debug_gain_predictive(cafe_ctx* ctx, double ms[7], double* flops) {
+    if (!ctx) return CAFE_ERR_ARGUMENT;
+    for (int k = 0; ms && k < 7; ++k) ms[k] = ctx->gain_predictive_ms[k];
+    if (flops) *flops = ctx->gain_predictive_flops;
     return CAFE_OK;
 }

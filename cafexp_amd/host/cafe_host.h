@@ -621,6 +621,12 @@ public:
     struct gain_origins gain_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
                                        const std::vector<double>& lambdas, const std::vector<double>& mus, const std::vector<double>& nus,
                                        double root_absent, const std::vector<const clade*>& order, bool dense = false);
+    // cafe_gain_leaf_predictive at ONE set of rates over the listed entries (--gain-dense --leaf-predictive): the leave-one-out
+    // predictive distribution of every leaf count under the gain model, laid out for write_leaf_predictive_reports -- one row per
+    // family of the model's table, family i taking the row of entry entry_of[i] (the list holds every distinct family once)
+    leaf_predictive_result gain_leaf_predictive(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
+                                                const std::vector<size_t>& entry_of, const std::vector<double>& lambdas, const std::vector<double>& mus,
+                                                double nu, double root_absent);
 private:
     bool _gain_scaled = false;
 };
@@ -1032,6 +1038,7 @@ struct gain_options {
 struct gain_table {
     std::vector<int64_t> family;
     std::vector<double> weight;
+    std::vector<size_t> entry_of;                                    // [families of the table] the entry that holds the family's counts
     double n_families = 0;
 };
 gain_table gain_distinct_families(const std::vector<gene_family>& families);

@@ -11,7 +11,8 @@
 // sets that rule for a gain run.  --gain-unconditional drops the correction.  --gain-dense scores every point, and the final table, by
 // cafe_score_gain instead: the same rates for every entry, each matrix built once, the families pruned together; --gain-scaled
 // with it holds the dense panels as mantissas and binary exponents (cafe_set_gain_scaling), for tables whose families'
-// likelihoods lie below fp64's range and would otherwise make -lnL inf.
+// likelihoods lie below fp64's range and would otherwise make -lnL inf.  --leaf-predictive with --gain-dense: after the fit,
+// cafe_gain_leaf_predictive at the fitted rates over the distinct families, and leaf_predictive.cpp's reports under the name Gain.
 //
 // The search is the Nelder-Mead of every other fit (optimizer / nm_search), over [lambdas..., mus (--estimate-mu)..., nu], nested
 // like -b --family-mu estimate: first the model without nu, then with nu from that optimum (start nu = lambda / 10, or nu held at
@@ -36,6 +37,7 @@ gain_table gain_distinct_families(const std::vector<gene_family>& fams) {
         const auto it = seen.emplace(key, t.family.size());
         if (it.second) { t.family.push_back((int64_t)f); t.weight.push_back(0.0); }
         t.weight[it.first->second] += 1.0;
+        t.entry_of.push_back(it.first->second);
     }
     t.n_families = (double)fams.size();
     t.family.push_back(kFamilyAbsent);
@@ -185,7 +187,7 @@ const char* gain_refusal(const gain_request& r) {
     if (r.simulate) return "the simulator has no gain rate: --simulate is not supported with --gain / --estimate-gain";
     if (r.pvalues) return "--pvalues simulates without a gain rate: it is not supported with --gain / --estimate-gain";
     if (r.reconstruct || r.marginal || r.histories) return "the reconstructions are not ported to the gain model: --reconstruct, --reconstruct-marginal and --sample-histories are not supported with --gain / --estimate-gain";
-    if (r.standard_errors || r.events || r.rate_shift || r.leaf_predictive || r.branch_change || r.rootdist_em)
+    if (r.standard_errors || r.events || r.rate_shift || (r.leaf_predictive && !r.dense) || r.branch_change || r.rootdist_em)      // (the dense path has its own leave-one-out call)
         return "the posterior reports are not ported to the gain model: --standard-errors, --expected-events, --rate-shift-scan, --leaf-predictive, --branch-change and --estimate-rootdist are not supported with --gain / --estimate-gain";
     if (r.search_batch) return "the gain search scores one point per call: --search-batch is not supported with --gain / --estimate-gain";
     if (r.estimate_error) return "the gain model needs an error model file: -e without FILE (estimating epsilon) is not supported with --gain / --estimate-gain";

@@ -330,6 +330,45 @@ gain_origins hip_base_model::gain_posterior(root_equilibrium_distribution* prior
     return res;
 }
 
+leaf_predictive_result hip_base_model::gain_leaf_predictive(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist,
+                                                            const std::vector<int64_t>& family, const std::vector<size_t>& entry_of,
+                                                            const std::vector<double>& lambdas, const std::vector<double>& mus, double nu, double root_absent) {
+    ensure_context(1);
+    std::vector<float> prior_f;
+    std::vector<double> err, unused;
+    gather_call_inputs(prior, rootdist, prior_f, err, unused);
+    cafe_params pr{};
+    pr.model = CAFE_MODEL_BASE; pr.n_categories = 1; pr.prior = prior_f.data();
+    pr.error_model = err.empty() ? nullptr : err.data();
+    if (mus.size() != lambdas.size()) throw std::runtime_error("gain_leaf_predictive: one mu per lambda is required");
+    const std::vector<double> nus(lambdas.size(), nu);
+    leaf_predictive_result res;
+    for (const clade* c : _order) if (c->is_leaf()) res.species.push_back(c->get_taxon_name());      // the columns of the context's counts
+    const size_t F = _p_gene_families->size(), T = res.species.size(), n = family.size();
+    if (entry_of.size() != F) throw std::runtime_error("gain_leaf_predictive: one entry per family of the table is required");
+    std::vector<double> lnl(n), cells[5];
+    for (auto& v : cells) v.resize(n * T);
+    cafe_gain_leaf_predictive_out out{};
+    out.lnl = lnl.data(); out.mean = cells[0].data(); out.sd = cells[1].data(); out.p_below = cells[2].data(); out.p_obs = cells[3].data();
+    out.p_above = cells[4].data();
+    cafe_set_gain_scaling(_ctx, _gain_scaled ? 1 : 0);
+    if (cafe_gain_leaf_predictive(_ctx, &pr, lambdas.data(), mus.data(), nus.data(), root_absent, (int64_t)n, family.data(), &out) != CAFE_OK)
+        throw std::runtime_error(std::string("cafe_gain_leaf_predictive: ") + cafe_last_error(_ctx));
+    res.observed.resize(F * T);
+    res.failed.resize(F);
+    std::vector<double>* const dst[5] = {&res.mean, &res.sd, &res.p_below, &res.p_obs, &res.p_above};
+    for (std::vector<double>* v : dst) v->resize(F * T);
+    for (size_t f = 0; f < F; ++f) {
+        const size_t e = entry_of.at(f);
+        res.failed[f] = std::isfinite(lnl.at(e)) ? 0 : 1;
+        for (size_t t = 0; t < T; ++t) {
+            res.observed[f * T + t] = (*_p_gene_families)[f].get_species_size(res.species[t]);
+            for (int k = 0; k < 5; ++k) (*dst[k])[f * T + t] = cells[k][e * T + t];
+        }
+    }
+    return res;
+}
+
 root_posterior_result hip_model_base::root_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist) {
     std::vector<double> mult, probs;
     double alpha = 0;

@@ -90,10 +90,14 @@ static void usage() {
         "                  species (--gain-unconditional: without that correction); the root is absent with probability P0 (default 0).  First the fit\n"
         "                  without NU, then with it from that optimum.  Writes OUTDIR/Gain_results.txt and Gain_family_likelihoods.txt.  -z keeps the\n"
         "                  families of one clade only, which this model is about.  Base model, one GPU; not with -k / -a, -b, --gpus, --simulate,\n"
-        "                  --pvalues, a reconstruction or posterior report, or --search-batch\n"
+        "                  --pvalues, a reconstruction or posterior report (but --leaf-predictive with --gain-dense, below), or --search-batch\n"
         "                  [--gain-dense]   score every point of the search, and the final table, by cafe_score_gain: each branch's matrix built\n"
         "                  once per point and all distinct families pruned together by fp64 MFMA GEMMs; values agree with the default path to rounding;\n"
         "                  with --gain-posterior the posterior runs on the same prune, by cafe_gain_posterior_dense\n"
+        "                  [--leaf-predictive [-P PVALUE]]   only with --gain-dense (also with --gain-scaled and missing cells): after the fit, at the\n"
+        "                  fitted rates, the leave-one-out distribution of every species' count under the gain model, by cafe_gain_leaf_predictive ->\n"
+        "                  OUTDIR/Gain_leaf_predictive.tab, Gain_leaf_outliers.tab, Gain_species_fit.tab (the reports of --leaf-predictive above; its\n"
+        "                  sum log p_obs is comparable with the fit without NU) and, when cells are missing, Gain_imputed_counts.tab\n"
         "                  [--gain-scaled]   only with --gain-dense: the dense prune holds its panels as mantissas and one binary exponent per\n"
         "                  (node, family), so families whose likelihood lies below fp64's range (trees of a few dozen taxa with counts that disagree\n"
         "                  across clades) keep a finite -lnL and their posteriors; applies to the search and to --gain-posterior\n"
@@ -566,16 +570,9 @@ int main(int argc, char** argv) {
                 std::ofstream f(out_dir + "/Gain_results.txt");
                 write_gain_results(f, res, go, table);
                 if (!f) throw std::runtime_error("Failed to write " + out_dir + "/Gain_results.txt");
-                std::map<std::string, size_t> entry_of;          // the table's distinct entry of every family, by its counts
                 std::ofstream g(out_dir + "/Gain_family_likelihoods.txt");
                 g << "#FamilyID\tLikelihood of Family (lnL)\n" << std::setprecision(17);
-                for (size_t i = 0, e = 0; i < d.gene_families.size(); ++i) {
-                    std::string key;
-                    for (const std::string& sp : d.gene_families[i].get_species()) key += sp + ':' + std::to_string(d.gene_families[i].get_species_size(sp)) + ',';
-                    const auto it = entry_of.emplace(key, e);
-                    if (it.second) ++e;
-                    g << d.gene_families[i].id() << '\t' << res.with.lnl[it.first->second] << "\n";
-                }
+                for (size_t i = 0; i < d.gene_families.size(); ++i) g << d.gene_families[i].id() << '\t' << res.with.lnl[table.entry_of[i]] << "\n";
                 g << "(absent)\t" << res.with.lnl.back() << "\n";
                 if (!g) throw std::runtime_error("Failed to write " + out_dir + "/Gain_family_likelihoods.txt");
             }
@@ -593,22 +590,23 @@ int main(int argc, char** argv) {
                 std::vector<std::string> names, ids;
                 size_t root = 0;
                 for (size_t v = 0; v < order.size(); ++v) { names.push_back(clade_index_or_name(order[v], order)); if (order[v]->is_root()) root = v; }
-                std::map<std::string, size_t> entry_by_counts;
-                std::vector<size_t> entry_of;
-                for (size_t i = 0, e = 0; i < d.gene_families.size(); ++i) {
-                    std::string key;
-                    for (const std::string& sp : d.gene_families[i].get_species()) key += sp + ':' + std::to_string(d.gene_families[i].get_species_size(sp)) + ',';
-                    const auto it = entry_by_counts.emplace(key, e);
-                    if (it.second) ++e;
-                    entry_of.push_back(it.first->second);
-                    ids.push_back(d.gene_families[i].id());
-                }
+                for (const gene_family& fam : d.gene_families) ids.push_back(fam.id());
                 origins = gain_origin_totals(go_res, table.weight, root);
                 std::ofstream cells(out_dir + "/Gain_origins.tab"), totals(out_dir + "/Gain_branch_origins.tab");
-                write_gain_origins(cells, go_res, names, root, ids, entry_of);
+                write_gain_origins(cells, go_res, names, root, ids, table.entry_of);
                 write_gain_branch_origins(totals, origins, names, root);
                 if (!cells || !totals) throw std::runtime_error("Failed to write " + out_dir + "/Gain_origins.tab or Gain_branch_origins.tab");
                 posterior_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - p0).count();
+            }
+            double predictive_s = 0;
+            leaf_predictive_summary predictive;
+            if (do_leaf_predictive) {                            // (with --gain-dense only) the leave-one-out check at the fitted rates
+                const auto p0 = std::chrono::steady_clock::now();
+                const leaf_predictive_result lp = base->gain_leaf_predictive(d.p_prior.get(), d.rootdist, table.family, table.entry_of, res.with.lambdas,
+                                                                             res.with.mus, res.with.nu, go.root_absent);
+                predictive = write_leaf_predictive_reports(lp, test_pvalue, "Gain", out_dir, d.gene_families);
+                if (count_missing(d.gene_families).cells > 0) write_imputed_counts(lp, "Gain", out_dir, d.gene_families);
+                predictive_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - p0).count();
             }
             base->set_lambda(nullptr);                           // `shape` goes with this scope
             auto list = [](const char* name, const std::vector<double>& v) {
@@ -632,6 +630,11 @@ int main(int argc, char** argv) {
                 std::printf("\"gain_posterior_path\": \"%s\", ", gain.dense ? "cafe_gain_posterior_dense" : "cafe_gain_posterior");
                 std::printf("\"gain_posterior_seconds\": %.3f, \"expected_origins\": %.12g, \"expected_losses\": %.12g, \"absent_at_root\": %.12g, "
                             "\"families_with_a_likely_origin\": %.12g, ", posterior_s, originated, lost, origins.absent_at_root, origins.origin_somewhere);
+            }
+            if (do_leaf_predictive) {
+                std::printf("\"leaf_predictive\": {\"seconds\": %.3f, \"failed_cells\": %zu, \"outliers\": %zu, ", predictive_s, predictive.failed_cells, predictive.outliers);
+                print_num("log_pseudo_likelihood", predictive.log_pseudo_likelihood, false);
+                std::printf("}, ");
             }
             std::printf("\"lr_statistic\": %.17g, \"calls\": %d, \"max_family_size\": %d, \"max_root_family_size\": %d, \"seconds\": %.3f}\n", res.lr_statistic,
                         res.without.calls + res.with.calls, d.max_family_size, d.max_root_family_size, seconds);

@@ -445,7 +445,45 @@ int cafe_gain_posterior_dense(cafe_ctx* ctx, const cafe_params* params, const do
  * output and leaf output launches (0 unless cafe_set_profiling was on) and the flops both GEMMs issued.  In the scaled mode the
  * product, root, weights and output figures are those of the scaled kernels; the build and both GEMMs are the same launches. */
 int cafe_debug_gain_dense_posterior(cafe_ctx* ctx, double ms[8], double* flops);
-/* The scaled mode of cafe_score_gain and cafe_gain_posterior_dense (no other entry reads it); on != 0 switches it on, the
+/* The leave-one-out predictive check of every leaf count under the gain model, on the dense prune: for entry i of the list and
+ * every taxon l, the distribution of the count species l would show given the counts of every OTHER species of the family,
+ *   p(y) = w_l[y] / W,   w_l[y] = the sum-rule evidence of the family with l's count replaced by y,   W = sum_{y = 0..M} w_l[y],
+ * reduced about the observed count x (0 for a missing cell) to
+ *   mean     x + sum (y - x) p(y)
+ *   sd       sqrt(max(sum (y - x)^2 p(y) - (sum (y - x) p(y))^2, 0)): the moments are taken about x, so a cell that sits where the
+ *            model expects it does not lose its variance to cancellation
+ *   p_below, p_obs, p_above   the mass at y < x, y = x, y > x, each a sum of its own
+ * cafe_leaf_predictive's five numbers, for the one model here in which a 0 in the table is informative.  With an error model y
+ * is the OBSERVED value: true size c is seen as y = c + half - t with weight err[y][t], the taps of the scorer.  The arguments,
+ * the checks and the host-decided values are cafe_score_gain's: one rate set [n_lambdas] for the whole list (mus NULL: mu =
+ * lambda), family[n] may repeat an index and may hold CAFE_FAMILY_ABSENT (x = 0 everywhere); base model only; CAFE_ERR_STATE with
+ * a communicator attached; CAFE_ERR_ARGUMENT for a negative or NaN nu, root_absent outside [0, 1] and a family index below -1;
+ * an invalid rate set gives lnl -inf and NaN in every other output, a NaN lambda NaN everywhere, and a family whose lnl from the
+ * device is not finite NaN in every other output.  An error model, missing cells and a saturated key are accepted.  A cell whose
+ * W is zero or not finite has NaN in all five; a MISSING cell has its mean and sd -- the imputation -- and NaN in the three p's.
+ * The up pass is cafe_score_gain's launch for launch with the sum rule forced (the context's root rule is neither read nor
+ * changed): lnl is bit for bit cafe_score_gain's under CAFE_ROOT_SUM.  Then, by depth from the root, the weights kernel and the
+ * transposed GEMM of cafe_gain_posterior_dense for the interior nodes, and for the depth's leaves a fused kernel: the same fp64
+ * MFMA tile forms O_l = P_l^T w_l, 64 sizes x 128 columns at a time, and reduces it to six sums per column in registers -- O_l is
+ * never stored (gain_dense.hip).  Nothing goes through exp(lnl), and every output is a ratio inside one column of one panel, so
+ * under cafe_set_gain_scaling the column's power of two cancels exactly: the call then runs the scaled product, root and weights
+ * kernels and the same fused kernel on the mantissas, and a family whose plain lnl is -inf has its five numbers.  A value depends
+ * on the family's counts and the rates only, never on its place in the list or on the batch cut.  Any pointer of out may be
+ * NULL.  cafe_family_results is not meaningful after this call; a later cafe_score returns what it returned before. */
+typedef struct cafe_gain_leaf_predictive_out {
+    double* lnl;        /* [n]          sum-rule lnL of the family */
+    double* mean;       /* [n][n_taxa]  predictive mean of the taxon's count, columns as `counts` */
+    double* sd;         /* [n][n_taxa]  predictive standard deviation */
+    double* p_below;    /* [n][n_taxa]  P(y < observed | the other species); NaN for a missing cell */
+    double* p_obs;      /* [n][n_taxa]  P(y = observed | the other species); NaN for a missing cell */
+    double* p_above;    /* [n][n_taxa]  P(y > observed | the other species); NaN for a missing cell */
+} cafe_gain_leaf_predictive_out;
+int cafe_gain_leaf_predictive(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus,
+                              double root_absent, int64_t n, const int64_t* family, const cafe_gain_leaf_predictive_out* out);
+/* The last cafe_gain_leaf_predictive: summed HIP-event ms of its build, product, GEMM, root, weights, transposed GEMM and fused
+ * leaf launches (0 unless cafe_set_profiling was on) and the flops its three MFMA kernels issued. */
+int cafe_debug_gain_predictive(cafe_ctx* ctx, double ms[7], double* flops);
+/* The scaled mode of cafe_score_gain, cafe_gain_posterior_dense and cafe_gain_leaf_predictive (no other entry reads it); on != 0 switches it on, the
  * default is off.  A family's likelihood is a product over the whole tree and leaves fp64's range on trees of a few dozen taxa
  * whose counts disagree across clades: the plain path then answers lnl = -inf (NaN in every posterior output).  In the scaled
  * mode every likelihood panel is held as mantissas and one int32 binary exponent per (node, column), chosen so that the
