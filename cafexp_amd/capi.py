@@ -65,6 +65,11 @@ class CafeMarginalOut(C.Structure):
                 ("log_evidence", _f64p), ("failed", _i32p)]
 
 
+class CafeGainMarginalOut(C.Structure):
+    _fields_ = [("lnl", _f64p), ("mean", _f64p), ("mode", _i32p), ("lo", _i32p), ("hi", _i32p), ("p_increase", _f64p), ("p_decrease", _f64p),
+                ("p_same", _f64p)]
+
+
 class CafeGradientOut(C.Structure):
     _fields_ = [("family_lnl", _f64p), ("d_lambda", _f64p), ("d_mu", _f64p), ("d_multiplier", _f64p), ("failed", _i32p)]
 
@@ -153,6 +158,7 @@ EXPORTS = [
     "cafe_debug_pvalues_stages", "cafe_debug_sort_rows", "cafe_debug_tree_pvalue",
     "cafe_score_gain", "cafe_debug_gain_dense",
     "cafe_gain_posterior_dense", "cafe_debug_gain_dense_posterior", "cafe_set_gain_scaling", "cafe_gain_leaf_predictive", "cafe_debug_gain_predictive",
+    "cafe_gain_marginal_dense", "cafe_debug_gain_marginal",
 ]
 CAFE_CHANGE_NONE = -(1 << 31)   # mode / lo / hi of cafe_branch_change at the root and in a failed family
 CAFE_COMM_ID_BYTES = 128
@@ -250,6 +256,11 @@ def load():
                                             C.POINTER(CafeGainLeafPredictiveOut)]
     L.cafe_debug_gain_predictive.restype = C.c_int
     L.cafe_debug_gain_predictive.argtypes = [C.c_void_p, _f64p, _f64p]
+    L.cafe_gain_marginal_dense.restype = C.c_int
+    L.cafe_gain_marginal_dense.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p, _f64p, _f64p, C.c_double, C.c_double, C.c_int64, _i64p,
+                                           C.POINTER(CafeGainMarginalOut)]
+    L.cafe_debug_gain_marginal.restype = C.c_int
+    L.cafe_debug_gain_marginal.argtypes = [C.c_void_p, _f64p, _f64p]
     L.cafe_set_gain_scaling.restype = C.c_int
     L.cafe_set_gain_scaling.argtypes = [C.c_void_p, C.c_int]
     L.cafe_bd_gain_row0.restype = C.c_int
@@ -685,6 +696,37 @@ class Context:
         gain_leaf_predictive -- 0 unless profiling was on --, the flops its three MFMA kernels issued)"""
         ms, flops = np.zeros(7), np.zeros(1)
         self._check(self._lib.cafe_debug_gain_predictive(self._h, _p(ms, _f64p), _p(flops, _f64p)))
+        return ms, float(flops[0])
+
+    def gain_marginal_dense(self, pr: Params, families, lambdas, mus, nus, root_absent: float = 0.0, level: float = 0.95) -> dict:
+        """cafe_gain_marginal_dense: under the gain model with ONE set of rates (score_gain's arguments), for every listed family
+        and node the posterior size as mean, mode (first arg max) and the equal-tailed interval lo..hi at `level`, and for the
+        branch above the node p_increase, p_decrease and p_same = P(size(node) >, <, = size(parent) | counts), NaN at the root;
+        all [n][n_nodes] (mode, lo, hi int32), and lnl [n], score_gain's under the sum rule bit for bit."""
+        fam = np.ascontiguousarray(families, dtype=np.int64).reshape(-1)
+        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(-1)
+        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(-1)
+        mu = None if mus is None else np.ascontiguousarray(mus, dtype=np.float64).reshape(-1)
+        if len(lam) != self.problem.n_lambdas or nu.shape != lam.shape or (mu is not None and mu.shape != lam.shape):
+            raise ValueError("lambdas, mus and nus must be [%d]" % self.problem.n_lambdas)
+        cp, keep = self._params(pr)
+        n, nodes = len(fam), self.problem.n_nodes
+        res = {"lnl": np.empty(n)}
+        res.update({key: np.empty((n, nodes)) for key in ("mean", "p_increase", "p_decrease", "p_same")})
+        res.update({key: np.empty((n, nodes), dtype=np.int32) for key in ("mode", "lo", "hi")})
+        out = CafeGainMarginalOut()
+        for name, array in res.items():
+            setattr(out, name, _p(array, _i32p if array.dtype == np.int32 else _f64p))
+        self._check(self._lib.cafe_gain_marginal_dense(self._h, C.byref(cp), _p(lam, _f64p), None if mu is None else _p(mu, _f64p), _p(nu, _f64p),
+                                                       float(root_absent), float(level), n, _p(fam, _i64p), C.byref(out)))
+        return res
+
+    def gain_marginal_profile(self):
+        """(HIP-event ms of the build, product, GEMM, root, weights, split GEMM, interior summary and leaf summary launches of the
+        last gain_marginal_dense and their total -- 0 unless profiling was on --, the flops its MFMA kernels issued, the masked
+        repeats of the split included)"""
+        ms, flops = np.zeros(9), np.zeros(1)
+        self._check(self._lib.cafe_debug_gain_marginal(self._h, _p(ms, _f64p), _p(flops, _f64p)))
         return ms, float(flops[0])
 
     def set_gain_scaling(self, on: bool):

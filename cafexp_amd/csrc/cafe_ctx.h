@@ -252,6 +252,7 @@ struct cafe_ctx {
     int gain_scaling = 0;            // cafe_set_gain_scaling: cafe_score_gain and cafe_gain_posterior_dense hold their panels as mantissas and exponents
     double gain_dense_posterior_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0}, gain_dense_posterior_flops = 0;   // cafe_gain_posterior_dense: those four, then weights / transposed GEMM / interior / leaf outputs; both GEMMs' flops
     double gain_predictive_ms[7] = {0, 0, 0, 0, 0, 0, 0}, gain_predictive_flops = 0;   // cafe_gain_leaf_predictive: build / product / GEMM / root / weights / transposed GEMM / fused leaf launches; the three MFMA kernels' flops
+    double gain_marginal_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, gain_marginal_flops = 0;   // cafe_gain_marginal_dense: build / product / GEMM / root / weights / split GEMM / interior / leaf summaries / their total; the MFMAs issued
     double change_band_ms = 0;                              // cafe_branch_change: its band kernel's launches (while profiling)
     double gram_ms = 0.0, gram_flops = 0.0;  // the Gram kernels of the last cafe_branch_scores (ms: profiling on)
     int history_batches = 0, history_passes = 0;            // cafe_sample_histories: column batches, draw passes per batch of the last call

@@ -881,6 +881,9 @@ __global__ __launch_bounds__(256) void gain_predictive_dense_leaf_kernel(const G
     }
 }
 
+// ------------------------------------------------------------------------------------- down: sizes, intervals, change
+#include "gain_marginal_kernel.h"
+
 // ---------------------------------------------------------------------------------------------------------------- host
 enum { kGdBuild = 0, kGdProduct = 1, kGdGemm = 2, kGdRoot = 3, kGdWeights = 4, kGdGemmT = 5, kGdInterior = 6, kGdLeaf = 7, kGdPredict = 8, kGdKinds = 9 };
 
@@ -945,12 +948,33 @@ struct GainPredictHost {
     }
 };
 
-// All three entries: the planning (keys, levels, op tables, workspace), the up pass launch for launch, and -- with `down`, the
+// The same for cafe_gain_marginal_dense: four doubles and three integers per (entry, node)
+struct GainMarginalHost {
+    const cafe_gain_marginal_out* out;
+    double level;
+    std::vector<double> res;                           // [4][n_nodes][nb]: mean, p_increase, p_decrease, p_same
+    std::vector<int32_t> ires;                         // [3][n_nodes][nb]: mode, lo, hi
+
+    void collect(int64_t b0, int64_t nb, int nn, const double* lnl) const {
+        double* const dst[4] = {out->mean, out->p_increase, out->p_decrease, out->p_same};
+        int32_t* const idst[3] = {out->mode, out->lo, out->hi};
+        for (int64_t b = 0; b < nb; ++b) {
+            if (!std::isfinite(lnl[b])) continue;      // the entry keeps its NaN and -1
+            for (int v = 0; v < nn; ++v) {
+                for (int k = 0; k < 4; ++k) dst[k][(b0 + b) * nn + v] = res[((size_t)k * nn + v) * nb + b];
+                for (int k = 0; k < 3; ++k) idst[k][(b0 + b) * nn + v] = ires[((size_t)k * nn + v) * nb + b];
+            }
+        }
+    }
+};
+
+// All four entries: the planning (keys, levels, op tables, workspace), the up pass launch for launch, and -- with `down`, the
 // posterior entry, or `pred`, the predictive one -- the sum rule forced at the root, the plan and the launches of the down pass
 // behind the root kernel.  Both walk the depths with the weights kernel and the transposed GEMM of the interior nodes; `down` adds
-// the output kernels of every node, `pred` the fused kernel of the depth's leaves.
+// the output kernels of every node, `pred` the fused kernel of the depth's leaves.  `marg`, the marginal entry, walks them with the
+// weights kernel, the SPLIT transposed GEMM in the other one's place, and the summary kernels of every node.
 int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const double* lam, const double* mus, const double* nus, double root_absent,
-                    int64_t n, const int64_t* family, double* family_lnl, GainDownHost* down, GainPredictHost* pred = nullptr) {
+                    int64_t n, const int64_t* family, double* family_lnl, GainDownHost* down, GainPredictHost* pred = nullptr, GainMarginalHost* marg = nullptr) {
     if (!pr || !pr->prior) { set_err(c, "%s: params with a prior are required", who); return CAFE_ERR_ARGUMENT; }
     if (pr->model != CAFE_MODEL_BASE) { set_err(c, "%s: base model only", who); return CAFE_ERR_ARGUMENT; }
     if (c->comm) { set_err(c, "%s: not valid on a context with a communicator attached", who); return CAFE_ERR_STATE; }
@@ -972,7 +996,7 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
 
     // ---- what the host decides alone: an invalid rate set is -inf in every entry, a NaN lambda that passes the rule NaN
     c->last.state = LastCall::kNone;                   // cafe_family_results is not meaningful after this call
-    const bool walk = down || pred;                    // the down pass is planned and run
+    const bool walk = down || pred || marg;            // the down pass is planned and run
     const int T = c->n_taxa;
     double ms[kGdKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, flops = 0.0;
     if (down) {
@@ -981,6 +1005,9 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
     } else if (pred) {
         std::copy(ms, ms + 7, c->gain_predictive_ms);
         c->gain_predictive_flops = 0.0;
+    } else if (marg) {
+        std::copy(ms, ms + 9, c->gain_marginal_ms);
+        c->gain_marginal_flops = 0.0;
     } else {
         std::copy(ms, ms + 4, c->gain_dense_ms);
         c->gain_dense_flops = 0.0;
@@ -1041,13 +1068,15 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
     }
 
     // ---- columns per batch: the matrices stand once, a batch adds its panels
+    const int split_tiles = (M + kGdMT) / kGdMT;       // row tiles of the split GEMM: its partials are [n_nodes][tiles][3][ld]
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t fixed_bytes = sizeof(double) * (size_t)mat_stride * n_keys + ((size_t)64 << 10) + sizeof(GainChild) * (size_t)nn +
                                sizeof(GainProdOp) * (size_t)nn + sizeof(GainGemmOp) * (size_t)nn + sizeof(SlotParamGain) * (size_t)n_keys +
                                sizeof(double) * ((size_t)R + 1 + (size_t)(M + 1) * c->n_dev) +
-                               (walk ? (sizeof(GainChild) + sizeof(GainWeightOp) + sizeof(GainGemmTOp) + sizeof(GainNodeOp) + sizeof(GainPredOp)) * (size_t)nn + sizeof(double) * ((size_t)R + 1) : 0);
+                               (walk ? (sizeof(GainChild) + sizeof(GainWeightOp) + sizeof(GainGemmTOp) + sizeof(GainNodeOp) + sizeof(GainPredOp) + sizeof(GainSplitOp)) * (size_t)nn + sizeof(double) * ((size_t)R + 1) : 0);
     const size_t column_bytes = sizeof(double) * (size_t)n_pan * N + sizeof(int64_t) + sizeof(double) +
                                 (walk ? sizeof(double) * ((size_t)n_down * N + (pred ? 5 * (size_t)T : 4 * (size_t)nn) + (want_posterior ? (size_t)nn * N : 0)) : 0) +
+                                (marg ? (sizeof(double) * 3 * (size_t)split_tiles + sizeof(int32_t) * 3) * (size_t)nn : 0) +     // the split's partials, the integers
                                 (scaled ? sizeof(int32_t) * (size_t)(n_pan + n_down) + sizeof(double) : 0);     // the exponents, log Z~
     size_t budget = 0;
     HIP_TRY(c, workspace_budget(c->workspace_limit, c->pf_dev_bytes, &budget));
@@ -1091,6 +1120,7 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
     std::vector<GainGemmTOp> gemmt_ops;
     std::vector<GainNodeOp> int_ops, leaf_ops;
     std::vector<GainPredOp> pred_ops;                  // (a leaf has an entry in both leaf tables: leaf_off serves both)
+    std::vector<GainSplitOp> split_ops;                // (beside gemmt_ops entry for entry: gemmt_off serves both)
     std::vector<int> weight_off{0}, gemmt_off{0}, int_off{0}, leaf_off{0}, weight_rows;
     for (int d = 0; d < n_depths; ++d) {
         int w_rows = 0;
@@ -1116,6 +1146,7 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
                 continue;
             }
             gemmt_ops.push_back({node_key[u] * mat_stride, widx[u] * pan_stride, oidx[u] * pan_stride, rows, 0});
+            split_ops.push_back({node_key[u] * mat_stride, widx[u] * pan_stride, oidx[u] * pan_stride, bidx[u] * pan_stride, rows, u});
             int_ops.push_back({oidx[u] * pan_stride, bidx[u] * pan_stride, widx[u] * pan_stride, node_key[u] * mat_stride, u, M + 1, rows, -1});
         }
         weight_off.push_back((int)weight_ops.size()); gemmt_off.push_back((int)gemmt_ops.size());
@@ -1137,12 +1168,14 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
     std::vector<char> blob;
     const size_t o_children = put(blob, children), o_prod = put(blob, prod_ops), o_gemm = put(blob, gemm_ops), o_slots = put(blob, slots),
                  o_reals = put(blob, reals), o_weight = put(blob, weight_ops), o_gemmt = put(blob, gemmt_ops), o_int = put(blob, int_ops),
-                 o_leaf = put(blob, leaf_ops), o_pred = put(blob, pred_ops), o_mass = put(blob, mass);
+                 o_leaf = put(blob, leaf_ops), o_pred = put(blob, pred_ops), o_split = put(blob, split_ops), o_mass = put(blob, mass);
     const size_t o_col = family_align_up(blob.size()), o_out = o_col + family_align_up(sizeof(int64_t) * ld),
                  o_mats = o_out + family_align_up(sizeof(double) * ld), o_pan = o_mats + family_align_up(sizeof(double) * (size_t)mat_stride * n_keys),
                  o_res = o_pan + sizeof(double) * (size_t)pan_stride * (n_pan + n_down),
-                 o_post = o_res + sizeof(double) * (down ? 4 * (size_t)nn : pred ? 5 * (size_t)T : 0) * ld,
-                 o_exps = o_post + (want_posterior ? sizeof(double) * (size_t)nn * N * ld : 0),
+                 o_post = o_res + sizeof(double) * (down || marg ? 4 * (size_t)nn : pred ? 5 * (size_t)T : 0) * ld,
+                 o_parts = o_post + (want_posterior ? sizeof(double) * (size_t)nn * N * ld : 0),
+                 o_ires = o_parts + (marg ? sizeof(double) * 3 * (size_t)split_tiles * nn * ld : 0),
+                 o_exps = o_ires + (marg ? family_align_up(sizeof(int32_t) * 3 * (size_t)nn * ld) : 0),
                  o_zt = o_exps + (scaled ? family_align_up(sizeof(int32_t) * (size_t)(n_pan + n_down) * ld) : 0),
                  need = o_zt + (scaled ? sizeof(double) * ld : 0);
     if (need > c->pf_dev_bytes) {
@@ -1196,6 +1229,12 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
         if (want_posterior) down->posterior.resize((size_t)nn * N * entries);
     }
     if (pred) pred->res.resize(5 * (size_t)T * entries);
+    GainSplitArgs xa{reinterpret_cast<const GainSplitOp*>(base + o_split), mats, panels, reinterpret_cast<double*>(base + o_parts), ld, M + 1, ldp};
+    GainSummaryArgs ya{oa, xa.parts, reinterpret_cast<int32_t*>(base + o_ires), marg ? marg->level : 0.0, split_tiles};
+    if (marg) {
+        marg->res.resize(4 * (size_t)nn * entries);
+        marg->ires.resize(3 * (size_t)nn * entries);
+    }
 
     std::vector<int64_t> col((size_t)ld);
     std::vector<double> res((size_t)ld);
@@ -1247,7 +1286,18 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
                                 dim3((unsigned)((cols + 255) / 256), (unsigned)((weight_rows[d] + kGdProdRows - 1) / kGdProdRows), (unsigned)nw), dim3(256), 0, s, w);
                 timer.mark(kGdWeights, s);
             }
-            if (nt > 0) {
+            if (nt > 0 && marg) {                      // the split GEMM: the outside panels and the three sums of every branch
+                GainSplitArgs x = xa;
+                x.ops += gemmt_off[d];
+                timer.mark(kGdGemmT, s);
+                CAFE_LAUNCH(c, gain_marginal_dense_split_kernel, dim3(tiles, (unsigned)split_tiles, (unsigned)nt), dim3(256), 0, s, x);
+                timer.mark(kGdGemmT, s);
+                for (int k = gemmt_off[d]; k < gemmt_off[d + 1]; ++k)
+                    for (int r0 = 0; r0 <= M; r0 += kGdMT) {               // the K tiles both phases issue, the masked repeats among them
+                        const int k_end = round_up(split_ops[k].nk, kGdKT);
+                        flops += 2.0 * kGdMT * (double)(gain_marginal_phase1_end(r0, split_ops[k].nk) + std::max(0, k_end - r0)) * (double)cols;
+                    }
+            } else if (nt > 0) {
                 GainGemmTArgs t = ta;
                 t.ops += gemmt_off[d];
                 timer.mark(kGdGemmT, s);
@@ -1265,6 +1315,28 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
                 timer.mark(kGdPredict, s);
                 for (int k = leaf_off[d]; k < leaf_off[d + 1]; ++k)
                     flops += 2.0 * round_up(M + 1, kGdMT) * (double)round_up(pred_ops[k].nk, kGdKT) * (double)cols;
+                continue;
+            }
+            if (marg) {                                // the summaries: nothing of a posterior is stored
+                GainSummaryArgs y = ya;
+                if (ni > 0) {
+                    y.o.ops = reinterpret_cast<const GainNodeOp*>(base + o_int) + int_off[d];
+                    timer.mark(kGdInterior, s);
+                    if (scaled)
+                        CAFE_LAUNCH(c, gain_marginal_scaled_interior_kernel, dim3((unsigned)(cols / 64), (unsigned)ni), dim3(256), 0, s, y, (const int32_t*)sa.exps);
+                    else
+                        CAFE_LAUNCH(c, gain_marginal_dense_interior_kernel, dim3((unsigned)(cols / 64), (unsigned)ni), dim3(256), 0, s, y);
+                    timer.mark(kGdInterior, s);
+                }
+                if (nl > 0) {
+                    y.o.ops = reinterpret_cast<const GainNodeOp*>(base + o_leaf) + leaf_off[d];
+                    timer.mark(kGdLeaf, s);
+                    if (scaled)
+                        CAFE_LAUNCH(c, gain_marginal_scaled_leaf_kernel, dim3((unsigned)(cols / 64), (unsigned)nl), dim3(256), 0, s, y, (const int32_t*)sa.exps);
+                    else
+                        CAFE_LAUNCH(c, gain_marginal_dense_leaf_kernel, dim3((unsigned)(cols / 64), (unsigned)nl), dim3(256), 0, s, y);
+                    timer.mark(kGdLeaf, s);
+                }
                 continue;
             }
             GainOutArgs o = oa;
@@ -1297,16 +1369,30 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
         if (pred)
             HIP_TRY(c, hipMemcpy2DAsync(pred->res.data(), sizeof(double) * nb, oa.res, sizeof(double) * ld, sizeof(double) * nb, 5 * (size_t)T,
                                         hipMemcpyDeviceToHost, s));
+        if (marg) {
+            HIP_TRY(c, hipMemcpy2DAsync(marg->res.data(), sizeof(double) * nb, oa.res, sizeof(double) * ld, sizeof(double) * nb, 4 * (size_t)nn,
+                                        hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpy2DAsync(marg->ires.data(), sizeof(int32_t) * nb, ya.ires, sizeof(int32_t) * ld, sizeof(int32_t) * nb, 3 * (size_t)nn,
+                                        hipMemcpyDeviceToHost, s));
+        }
         HIP_TRY(c, hipStreamSynchronize(s));            // the host tables of this batch go out of use
         std::copy(res.begin(), res.begin() + nb, family_lnl + b0);
         if (down) down->collect(b0, nb, nn, N, res.data());
         if (pred) pred->collect(b0, nb, T, res.data());
+        if (marg) marg->collect(b0, nb, nn, res.data());
     }
     timer.collect(ms);
     if (pred) {
         ms[6] = ms[kGdPredict];                        // build, product, GEMM, root, weights, transposed GEMM, fused leaf
         std::copy(ms, ms + 7, c->gain_predictive_ms);
         c->gain_predictive_flops = flops;
+        return CAFE_OK;
+    }
+    if (marg) {                                        // the posterior entry's eight, the split GEMM sixth; then their total
+        ms[8] = 0.0;
+        for (int k = 0; k < 8; ++k) ms[8] += ms[k];
+        std::copy(ms, ms + 9, c->gain_marginal_ms);
+        c->gain_marginal_flops = flops;
         return CAFE_OK;
     }
     std::copy(ms, ms + (down ? 8 : 4), down ? c->gain_dense_posterior_ms : c->gain_dense_ms);
@@ -1390,5 +1476,36 @@ int cafe_debug_gain_predictive(cafe_ctx* ctx, double ms[7], double* flops) {
     if (!ctx) return CAFE_ERR_ARGUMENT;
     for (int k = 0; ms && k < 7; ++k) ms[k] = ctx->gain_predictive_ms[k];
     if (flops) *flops = ctx->gain_predictive_flops;
+    return CAFE_OK;
+}
+
+int cafe_gain_marginal_dense(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus, double root_absent,
+                             double level, int64_t n, const int64_t* family, const cafe_gain_marginal_out* out) {
+    const char* const who = "cafe_gain_marginal_dense";
+    const int rc = cafe::guarded_observed(ctx, who, [&] {       // the leaf summary has no instantiation for a missing cell
+        if (!out || (n > 0 && (!out->mean || !out->mode || !out->lo || !out->hi || !out->p_increase || !out->p_decrease || !out->p_same))) {
+            cafe::set_err(ctx, "%s: out with mean, mode, lo, hi, p_increase, p_decrease and p_same is required", who);
+            return (int)CAFE_ERR_ARGUMENT;
+        }
+        if (!(level > 0.0 && level < 1.0)) { cafe::set_err(ctx, "%s: level must lie in (0, 1)", who); return (int)CAFE_ERR_ARGUMENT; }
+        std::vector<double> own_lnl;
+        double* lnl = out->lnl;
+        if (!lnl && n > 0) { own_lnl.resize((size_t)n); lnl = own_lnl.data(); }
+        if (n > 0) {                                   // what no finite lnl replaces
+            const size_t nodes = (size_t)n * ctx->n_nodes;
+            for (double* p : {out->mean, out->p_increase, out->p_decrease, out->p_same}) std::fill(p, p + nodes, std::numeric_limits<double>::quiet_NaN());
+            for (int32_t* p : {out->mode, out->lo, out->hi}) std::fill(p, p + nodes, -1);
+        }
+        cafe::GainMarginalHost marg{out, level, {}, {}};
+        return cafe::gain_dense_impl(ctx, who, params, lambdas, mus, nus, root_absent, n, family, lnl, nullptr, nullptr, &marg);
+    });
+    if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
+    return rc;
+}
+
+int cafe_debug_gain_marginal(cafe_ctx* ctx, double ms[9], double* flops) {
+    if (!ctx) return CAFE_ERR_ARGUMENT;
+    for (int k = 0; ms && k < 9; ++k) ms[k] = ctx->gain_marginal_ms[k];
+    if (flops) *flops = ctx->gain_marginal_flops;
     return CAFE_OK;
 }

@@ -627,6 +627,12 @@ public:
     leaf_predictive_result gain_leaf_predictive(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
                                                 const std::vector<size_t>& entry_of, const std::vector<double>& lambdas, const std::vector<double>& mus,
                                                 double nu, double root_absent);
+    // cafe_gain_marginal_dense at ONE set of rates over the listed entries (--gain-dense --reconstruct-marginal): posterior size of
+    // every node and the probability that the family grew or shrank on every branch under the gain model, laid out for
+    // write_marginal_reports -- one row per family of the model's table (entry_of as above), nodes in the caller's order
+    marginal_result gain_marginal(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
+                                  const std::vector<size_t>& entry_of, const std::vector<double>& lambdas, const std::vector<double>& mus, double nu,
+                                  double root_absent, double level, const std::vector<const clade*>& order);
 private:
     bool _gain_scaled = false;
 };

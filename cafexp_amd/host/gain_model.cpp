@@ -13,6 +13,8 @@
 // with it holds the dense panels as mantissas and binary exponents (cafe_set_gain_scaling), for tables whose families'
 // likelihoods lie below fp64's range and would otherwise make -lnL inf.  --leaf-predictive with --gain-dense: after the fit,
 // cafe_gain_leaf_predictive at the fitted rates over the distinct families, and leaf_predictive.cpp's reports under the name Gain.
+// --reconstruct-marginal [LEVEL] with --gain-dense: likewise cafe_gain_marginal_dense, and the base model's marginal reports
+// (Gain_posterior_sizes.tab, Gain_posterior_change.tab).
 //
 // The search is the Nelder-Mead of every other fit (optimizer / nm_search), over [lambdas..., mus (--estimate-mu)..., nu], nested
 // like -b --family-mu estimate: first the model without nu, then with nu from that optimum (start nu = lambda / 10, or nu held at
@@ -186,7 +188,7 @@ const char* gain_refusal(const gain_request& r) {
     if (r.gpus) return "the gain model runs on one GPU: --gpus is not supported with --gain / --estimate-gain";
     if (r.simulate) return "the simulator has no gain rate: --simulate is not supported with --gain / --estimate-gain";
     if (r.pvalues) return "--pvalues simulates without a gain rate: it is not supported with --gain / --estimate-gain";
-    if (r.reconstruct || r.marginal || r.histories) return "the reconstructions are not ported to the gain model: --reconstruct, --reconstruct-marginal and --sample-histories are not supported with --gain / --estimate-gain";
+    if (r.reconstruct || (r.marginal && !r.dense) || r.histories) return "the reconstructions are not ported to the gain model: --reconstruct, --reconstruct-marginal and --sample-histories are not supported with --gain / --estimate-gain";
     if (r.standard_errors || r.events || r.rate_shift || (r.leaf_predictive && !r.dense) || r.branch_change || r.rootdist_em)      // (the dense path has its own leave-one-out call)
         return "the posterior reports are not ported to the gain model: --standard-errors, --expected-events, --rate-shift-scan, --leaf-predictive, --branch-change and --estimate-rootdist are not supported with --gain / --estimate-gain";
     if (r.search_batch) return "the gain search scores one point per call: --search-batch is not supported with --gain / --estimate-gain";

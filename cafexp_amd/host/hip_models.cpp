@@ -369,6 +369,48 @@ leaf_predictive_result hip_base_model::gain_leaf_predictive(root_equilibrium_dis
     return res;
 }
 
+marginal_result hip_base_model::gain_marginal(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
+                                              const std::vector<size_t>& entry_of, const std::vector<double>& lambdas, const std::vector<double>& mus,
+                                              double nu, double root_absent, double level, const std::vector<const clade*>& order) {
+    ensure_context(1);
+    std::vector<float> prior_f;
+    std::vector<double> err, unused;
+    gather_call_inputs(prior, rootdist, prior_f, err, unused);
+    cafe_params pr{};
+    pr.model = CAFE_MODEL_BASE; pr.n_categories = 1; pr.prior = prior_f.data();
+    pr.error_model = err.empty() ? nullptr : err.data();
+    if (mus.size() != lambdas.size()) throw std::runtime_error("gain_marginal: one mu per lambda is required");
+    const std::vector<double> nus(lambdas.size(), nu);
+    const size_t F = _p_gene_families->size(), nn = _order.size(), n = family.size(), m = order.size();
+    if (entry_of.size() != F) throw std::runtime_error("gain_marginal: one entry per family of the table is required");
+    std::vector<double> lnl(n), mean(n * nn), pi(n * nn), pd(n * nn), ps(n * nn);
+    std::vector<int32_t> mode(n * nn), lo(n * nn), hi(n * nn);
+    cafe_gain_marginal_out out{};
+    out.lnl = lnl.data(); out.mean = mean.data(); out.mode = mode.data(); out.lo = lo.data(); out.hi = hi.data();
+    out.p_increase = pi.data(); out.p_decrease = pd.data(); out.p_same = ps.data();
+    cafe_set_gain_scaling(_ctx, _gain_scaled ? 1 : 0);
+    if (cafe_gain_marginal_dense(_ctx, &pr, lambdas.data(), mus.data(), nus.data(), root_absent, level, (int64_t)n, family.data(), &out) != CAFE_OK)
+        throw std::runtime_error(std::string("cafe_gain_marginal_dense: ") + cafe_last_error(_ctx));
+    marginal_result res;
+    res.level = level; res.n_nodes = m;
+    res.log_evidence.resize(F); res.failed.resize(F);
+    res.mean.resize(F * m); res.p_increase.resize(F * m); res.p_decrease.resize(F * m);
+    res.mode.resize(F * m); res.lo.resize(F * m); res.hi.resize(F * m);
+    std::map<const clade*, size_t> pos;
+    for (size_t v = 0; v < nn; ++v) pos[_order[v]] = v;
+    for (size_t f = 0; f < F; ++f) {
+        const size_t e = entry_of.at(f);
+        res.log_evidence[f] = lnl.at(e);
+        res.failed[f] = std::isfinite(lnl[e]) ? 0 : 1;
+        for (size_t i = 0; i < m; ++i) {
+            const size_t src = e * nn + pos.at(order[i]), dst = f * m + i;
+            res.mean[dst] = mean[src]; res.mode[dst] = mode[src]; res.lo[dst] = lo[src]; res.hi[dst] = hi[src];
+            res.p_increase[dst] = pi[src]; res.p_decrease[dst] = pd[src];
+        }
+    }
+    return res;
+}
+
 root_posterior_result hip_model_base::root_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist) {
     std::vector<double> mult, probs;
     double alpha = 0;

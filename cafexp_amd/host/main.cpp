@@ -90,7 +90,7 @@ static void usage() {
         "                  species (--gain-unconditional: without that correction); the root is absent with probability P0 (default 0).  First the fit\n"
         "                  without NU, then with it from that optimum.  Writes OUTDIR/Gain_results.txt and Gain_family_likelihoods.txt.  -z keeps the\n"
         "                  families of one clade only, which this model is about.  Base model, one GPU; not with -k / -a, -b, --gpus, --simulate,\n"
-        "                  --pvalues, a reconstruction or posterior report (but --leaf-predictive with --gain-dense, below), or --search-batch\n"
+        "                  --pvalues, a reconstruction or posterior report (but --leaf-predictive and --reconstruct-marginal with --gain-dense, below), or --search-batch\n"
         "                  [--gain-dense]   score every point of the search, and the final table, by cafe_score_gain: each branch's matrix built\n"
         "                  once per point and all distinct families pruned together by fp64 MFMA GEMMs; values agree with the default path to rounding;\n"
         "                  with --gain-posterior the posterior runs on the same prune, by cafe_gain_posterior_dense\n"
@@ -98,6 +98,10 @@ static void usage() {
         "                  fitted rates, the leave-one-out distribution of every species' count under the gain model, by cafe_gain_leaf_predictive ->\n"
         "                  OUTDIR/Gain_leaf_predictive.tab, Gain_leaf_outliers.tab, Gain_species_fit.tab (the reports of --leaf-predictive above; its\n"
         "                  sum log p_obs is comparable with the fit without NU) and, when cells are missing, Gain_imputed_counts.tab\n"
+        "                  [--reconstruct-marginal [LEVEL]]   only with --gain-dense (also with --gain-scaled; not with missing cells): after the fit,\n"
+        "                  at the fitted rates, posterior size of every node (mean, mode, equal-tailed interval) and the probability that the family\n"
+        "                  shrank or grew on every branch under the gain model, by cafe_gain_marginal_dense -> OUTDIR/Gain_posterior_sizes.tab,\n"
+        "                  Gain_posterior_change.tab (the formats of --reconstruct-marginal above)\n"
         "                  [--gain-scaled]   only with --gain-dense: the dense prune holds its panels as mantissas and one binary exponent per\n"
         "                  (node, family), so families whose likelihood lies below fp64's range (trees of a few dozen taxa with counts that disagree\n"
         "                  across clades) keep a finite -lnL and their posteriors; applies to the search and to --gain-posterior\n"
@@ -356,6 +360,7 @@ int main(int argc, char** argv) {
         if (!missing_list.empty() && parse_missing_tokens(missing_list).empty()) why = "--missing: TOKENS must name at least one spelling, e.g. NA,?,-";
         else if (pvalue_sims > 0) why = "--pvalues simulates complete families: it is not supported on a table with missing cells (--missing / --mask-cells)";
         else if (do_reconstruct) why = "--reconstruct reads every leaf count: it is not supported on a table with missing cells (--missing / --mask-cells)";
+        else if (do_marginal && gain_run) why = "the gain model's --reconstruct-marginal summarises every leaf at its observed count: it is not supported with --missing / --mask-cells";
         else if (do_marginal) why = "--reconstruct-marginal is not ported to missing cells: it is not supported with --missing / --mask-cells";
         else if (do_histories) why = "--sample-histories is not ported to missing cells: it is not supported with --missing / --mask-cells";
         else if (do_standard_errors) why = "--standard-errors is not ported to missing cells: it is not supported with --missing / --mask-cells";
@@ -608,6 +613,18 @@ int main(int argc, char** argv) {
                 if (count_missing(d.gene_families).cells > 0) write_imputed_counts(lp, "Gain", out_dir, d.gene_families);
                 predictive_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - p0).count();
             }
+            double gain_marginal_s = 0;
+            size_t gain_marginal_failed = 0;
+            if (do_marginal) {                                   // (with --gain-dense only) posterior sizes and change at the fitted rates
+                const auto p0 = std::chrono::steady_clock::now();
+                cladevector order;
+                d.p_tree->apply_reverse_level_order([&order](const clade* c) { order.push_back(c); });
+                const marginal_result mr = base->gain_marginal(d.p_prior.get(), d.rootdist, table.family, table.entry_of, res.with.lambdas, res.with.mus,
+                                                               res.with.nu, go.root_absent, marginal_level, order);
+                gain_marginal_failed = mr.failed_count();
+                write_marginal_reports(mr, "Gain", out_dir, order, d.gene_families);
+                gain_marginal_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - p0).count();
+            }
             base->set_lambda(nullptr);                           // `shape` goes with this scope
             auto list = [](const char* name, const std::vector<double>& v) {
                 std::printf("\"%s\": [", name);
@@ -636,6 +653,8 @@ int main(int argc, char** argv) {
                 print_num("log_pseudo_likelihood", predictive.log_pseudo_likelihood, false);
                 std::printf("}, ");
             }
+            if (do_marginal)
+                std::printf("\"marginal\": {\"seconds\": %.3f, \"level\": %.17g, \"failed\": %zu}, ", gain_marginal_s, marginal_level, gain_marginal_failed);
             std::printf("\"lr_statistic\": %.17g, \"calls\": %d, \"max_family_size\": %d, \"max_root_family_size\": %d, \"seconds\": %.3f}\n", res.lr_statistic,
                         res.without.calls + res.with.calls, d.max_family_size, d.max_root_family_size, seconds);
             return 0;

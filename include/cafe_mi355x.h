@@ -483,6 +483,48 @@ int cafe_gain_leaf_predictive(cafe_ctx* ctx, const cafe_params* params, const do
 /* The last cafe_gain_leaf_predictive: summed HIP-event ms of its build, product, GEMM, root, weights, transposed GEMM and fused
  * leaf launches (0 unless cafe_set_profiling was on) and the flops its three MFMA kernels issued. */
 int cafe_debug_gain_predictive(cafe_ctx* ctx, double ms[7], double* flops);
+/* The report of a fit under the gain model, on the dense prune: for entry i of the list and every node v the posterior of
+ * size(v) given the family's counts -- the distribution cafe_gain_posterior_dense's `posterior` holds, over sizes 0..R at the root
+ * and 0..M below it -- summarised on the device and never stored, and for the branch above v its joint with the parent's size
+ * split at the diagonal:
+ *   mean        the posterior mean of size(v), cafe_gain_posterior_dense's
+ *   mode        the first arg max
+ *   lo, hi      the equal-tailed interval on the discrete CDF at `level` in (0, 1), cafe_marginal_reconstruct's rule:
+ *               lo = min{j : CDF(j) >= (1 - level) / 2}, hi = min{j : CDF(j) >= 1 - (1 - level) / 2}.  The CDF is the running
+ *               sum of the posterior values, each already divided by Z; its total is taken as 1 and is NOT renormalised by the
+ *               node's own sum, and a threshold the running sum never reaches gives the node's last size (marginal.hip)
+ *   p_increase, p_decrease, p_same   P(size(v) > , < , = size(parent(v)) | counts); NaN at the root.  Each is a sum of its own
+ *               non-negative terms w[s] P[s][c] B[c] / Z over c > s, c < s, c = s, never a difference
+ *   lnl         the family's sum-rule lnL; NULL: not wanted
+ * A leaf's row is its observed count, or with an error model the posterior over the model's taps.  The arguments, the checks, the
+ * host-decided values (-inf / NaN entries) and the batching are cafe_gain_posterior_dense's; in addition CAFE_ERR_ARGUMENT for a
+ * level outside (0, 1), and CAFE_ERR_STATE for a context created with missing cells (as cafe_marginal_reconstruct).  An entry
+ * whose lnl is not finite keeps NaN in its doubles and -1 in its integers.  The up pass is cafe_score_gain's launch for launch
+ * with the sum rule forced: lnl is bit for bit that entry's under CAFE_ROOT_SUM.  The down pass goes by depth from the root: the
+ * weights kernel of cafe_gain_posterior_dense; in the transposed GEMM's place a SPLIT one (gain_marginal_kernel.h) that runs the
+ * contraction over the parent's sizes s in two phases, s < c and s > c, masks the four K tiles that straddle the diagonal on the
+ * staging registers, takes the diagonal element by element, and leaves the outside panel and, per 64-row tile, the three sums of
+ * every column; then summary kernels that fold those sums in ascending tile order and walk outside x B twice for mean, mode and
+ * the CDF crossings.  No atomics: a value depends on the family's counts and the rates only, never on its place in the list or on
+ * the batch cut.  The outside panel sums in another order than cafe_gain_posterior_dense's, so `mean` agrees with that call's to
+ * rounding.  Under cafe_set_gain_scaling the split GEMM runs unchanged on the mantissas and every output is a ratio against Z~
+ * shifted with ldexp.  cafe_family_results is not meaningful after this call; a later cafe_score returns what it returned before. */
+typedef struct cafe_gain_marginal_out {
+    double*  lnl;         /* [n]           as cafe_gain_posterior_dense (may be NULL) */
+    double*  mean;        /* [n][n_nodes]  */
+    int32_t* mode;        /* [n][n_nodes]  first arg max */
+    int32_t* lo;          /* [n][n_nodes]  */
+    int32_t* hi;          /* [n][n_nodes]  */
+    double*  p_increase;  /* [n][n_nodes]  P(size(v) > size(parent(v)) | counts); NaN at the root */
+    double*  p_decrease;  /* [n][n_nodes]  P(size(v) < size(parent(v)) | counts); NaN at the root */
+    double*  p_same;      /* [n][n_nodes]  P(size(v) = size(parent(v)) | counts); NaN at the root */
+} cafe_gain_marginal_out;
+int cafe_gain_marginal_dense(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus,
+                             double root_absent, double level, int64_t n, const int64_t* family, const cafe_gain_marginal_out* out);
+/* The last cafe_gain_marginal_dense: summed HIP-event ms of its build, product, GEMM, root, weights, split GEMM, interior summary
+ * and leaf summary launches and, ninth, the total of those eight (0 unless cafe_set_profiling was on), and the flops of the MFMAs
+ * its GEMM kernels issued, the masked repeats of the split included. */
+int cafe_debug_gain_marginal(cafe_ctx* ctx, double ms[9], double* flops);
 /* The scaled mode of cafe_score_gain, cafe_gain_posterior_dense and cafe_gain_leaf_predictive (no other entry reads it); on != 0 switches it on, the
  * default is off.  A family's likelihood is a product over the whole tree and leaves fp64's range on trees of a few dozen taxa
  * whose counts disagree across clades: the plain path then answers lnl = -inf (NaN in every posterior output).  In the scaled
