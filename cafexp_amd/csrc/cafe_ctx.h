@@ -130,6 +130,16 @@ struct LastCall {
     hipStream_t stream = nullptr;            // the stream it was enqueued on
 };
 
+// The gain dense path (gain_dense.hip): its four entries are four modes of one call, and its launches fall into nine kinds --
+// build, product, GEMM, root (every mode), weights, transposed or split GEMM, interior and leaf outputs or summaries (the down
+// pass), the fused leaf kernel (the predictive mode).  A mode's last call leaves one record: HIP-event ms by kind (while
+// profiling) and the flops its MFMA kernels issued.  The cafe_debug_gain_* entries publish it in their own slot layouts.
+enum GainMode { kGainScore = 0, kGainPosterior = 1, kGainPredictive = 2, kGainMarginal = 3, kGainModes = 4 };
+enum { kGdBuild = 0, kGdProduct = 1, kGdGemm = 2, kGdRoot = 3, kGdWeights = 4, kGdGemmT = 5, kGdInterior = 6, kGdLeaf = 7, kGdPredict = 8, kGdKinds = 9 };
+struct GainProfile {
+    double ms[kGdKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, flops = 0;
+};
+
 }  // namespace cafe
 
 struct cafe_ctx {
@@ -248,11 +258,8 @@ struct cafe_ctx {
     size_t pf_dev_bytes = 0;
     int64_t pf_max_batch = 0;                // CAFE_PER_FAMILY_BATCH: at most that many families per batch (diagnostic; 0 = what fits)
     double marginal_gemm_ms = 0, marginal_gemm_flops = 0;   // cafe_marginal_reconstruct: its GEMM launches (ms: while profiling)
-    double gain_dense_ms[4] = {0, 0, 0, 0}, gain_dense_flops = 0;   // cafe_score_gain: build / product / GEMM / root launches (ms: while profiling), GEMM flops issued
     int gain_scaling = 0;            // cafe_set_gain_scaling: cafe_score_gain and cafe_gain_posterior_dense hold their panels as mantissas and exponents
-    double gain_dense_posterior_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0}, gain_dense_posterior_flops = 0;   // cafe_gain_posterior_dense: those four, then weights / transposed GEMM / interior / leaf outputs; both GEMMs' flops
-    double gain_predictive_ms[7] = {0, 0, 0, 0, 0, 0, 0}, gain_predictive_flops = 0;   // cafe_gain_leaf_predictive: build / product / GEMM / root / weights / transposed GEMM / fused leaf launches; the three MFMA kernels' flops
-    double gain_marginal_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, gain_marginal_flops = 0;   // cafe_gain_marginal_dense: build / product / GEMM / root / weights / split GEMM / interior / leaf summaries / their total; the MFMAs issued
+    cafe::GainProfile gain_profile[cafe::kGainModes];      // the last call of each mode of the gain dense path
     double change_band_ms = 0;                              // cafe_branch_change: its band kernel's launches (while profiling)
     double gram_ms = 0.0, gram_flops = 0.0;  // the Gram kernels of the last cafe_branch_scores (ms: profiling on)
     int history_batches = 0, history_passes = 0;            // cafe_sample_histories: column batches, draw passes per batch of the last call

@@ -24,7 +24,16 @@
 //
 // cafe_gain_posterior_dense: the same up pass with the sum rule forced, then the other half of the sum-product on the panels it
 // left -- by depth from the root a weights kernel, an MFMA GEMM over the matrices as stored (P^T), and the output kernels of
-// the interior nodes and of the leaves ("down" below).  Both entries run gain_dense_impl.
+// the interior nodes and of the leaves ("down" below).  cafe_gain_leaf_predictive and cafe_gain_marginal_dense walk the same
+// depths with other kernels behind the weights: the fused leaf kernel, the split GEMM and the summaries.
+//
+// How the file hangs together.  Every MFMA kernel -- the up GEMM, the transposed GEMM, the fused predictive kernel, the split GEMM --
+// runs the ONE tile loop gain_dense_tile, told at compile time how the matrix holds A and which side of the diagonal to keep.
+// Every kernel of the down pass behind the weights reads the ONE op GainNodeOp.  On the host the four entries are four modes
+// (GainMode) of gain_dense_run behind one shell, gain_dense_entry: the checks and what the host decides alone, then GainPlan
+// (keys, levels, depths, panel indices and the op tables -- host data only), GainLayout (the batch width the context's budget
+// allows and the workspace's offsets) and gain_dense_batches (the launches).  A mode's outputs leave through one GainSink, which
+// describes them as planes, and its launches are timed into one GainProfile of the context (cafe_ctx.h).
 #include <map>
 #include <utility>
 
@@ -181,22 +190,30 @@ __device__ __forceinline__ void gain_dense_times_children(const GainProdArgs& a,
     }
 }
 
-// grid (column blocks of 256, row blocks of 16, nodes of the level); a thread owns one column and 16 sizes
-__global__ __launch_bounds__(256) void gain_dense_product_kernel(const GainProdArgs a) {
-    const GainProdOp op = a.ops[blockIdx.z];
+// grid (column blocks of 256, row blocks of 16, nodes); a thread owns one column and 16 sizes.  The body of the plain product
+// and weights kernels.  init(i0, n, f, v): the elements before the children are multiplied in.
+template <class Init>
+__device__ __forceinline__ void gain_dense_node(const GainProdArgs& a, int child0, int n_children, int rows, int64_t dst, Init init) {
     const int i0 = blockIdx.y * kGdProdRows;
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i0 >= op.rows || f >= a.ncols) return;
-    const int n = min(kGdProdRows, op.rows - i0);
+    if (i0 >= rows || f >= a.ncols) return;
+    const int n = min(kGdProdRows, rows - i0);
     double v[kGdProdRows];
     int lifts[kGdProdRows];                            // (not read: the untracked product)
-#pragma unroll
-    for (int j = 0; j < kGdProdRows; ++j) v[j] = 1.0;
-    gain_dense_times_children(a, op.child0, op.n_children, i0, n, f, a.col[f], v, lifts);
-    double* __restrict__ dst = a.panels + op.dst + (int64_t)i0 * a.ld + f;
+    init(i0, n, f, v);
+    gain_dense_times_children(a, child0, n_children, i0, n, f, a.col[f], v, lifts);
+    double* __restrict__ out = a.panels + dst + (int64_t)i0 * a.ld + f;
 #pragma unroll
     for (int j = 0; j < kGdProdRows; ++j)
-        if (j < n) dst[(int64_t)j * a.ld] = v[j];
+        if (j < n) out[(int64_t)j * a.ld] = v[j];
+}
+
+__global__ __launch_bounds__(256) void gain_dense_product_kernel(const GainProdArgs a) {
+    const GainProdOp op = a.ops[blockIdx.z];
+    gain_dense_node(a, op.child0, op.n_children, op.rows, op.dst, [](int, int, int64_t, double (&v)[kGdProdRows]) {
+#pragma unroll
+        for (int j = 0; j < kGdProdRows; ++j) v[j] = 1.0;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------- GEMM
@@ -221,54 +238,85 @@ struct GainGemmArgs {
     int32_t nk, ldp;                 // contraction over c = 0..nk-1
 };
 
-// grid (column tiles, row tiles of the tallest op, interior non-root nodes of the level)
-__global__ __launch_bounds__(256) void gain_dense_gemm_kernel(const GainGemmArgs a) {
-    __shared__ __attribute__((aligned(16))) double As[2][kGdKT * kGdLdA];
-    __shared__ __attribute__((aligned(16))) double Xs[2][kGdKT * kGdLdX];
-    const GainGemmOp op = a.ops[blockIdx.z];
-    const int r0 = blockIdx.y * kGdMT;
-    if (r0 >= op.nr) return;                           // (block-uniform, ahead of every barrier)
+// The tile of every MFMA kernel of this file: acc = A[r0 .. r0 + 63][kb .. ke) X[kb .. ke)[c0 .. c0 + 127] over the K tiles [kb, ke)
+// (kb a multiple of 16; the contraction itself is 0..nk-1 and every load is guarded by it and by nr).  acc is zeroed here and the
+// function ends behind a barrier: the buffers are free for the caller's next tile.  With an empty range acc is zero.
+//   AForm  how `mat` holds A.  kGdAColumn: A[r][k] = mat[k * ldp + r], the 64 consecutive sizes of a k are one load of a wave and
+//          one LDS row -- the up GEMM.  kGdAStored: A[r][k] = mat[r * ldp + k], the matrix AS STORED with the contraction index
+//          contiguous -- the down pass; its staging is described at the transposed GEMM below.
+//   Side   0: the whole range.  +1 keeps k < r, -1 keeps k > r (kGdAStored only), inside the straddling tiles r0 <= k0 < r0 + 64
+//          only -- every other tile of the range lies wholly on the kept side and is staged as it is.  The comparison is made
+//          once, on the staging registers, as the tile is loaded, never in the MFMA loop.
+enum { kGdAColumn = 0, kGdAStored = 1 };
+typedef double gd4 __attribute__((ext_vector_type(4)));
+template <int AForm, int Side>
+__device__ __forceinline__ void gain_dense_tile(double (*As)[kGdKT * kGdLdA], double (*Xs)[kGdKT * kGdLdX], const double* __restrict__ mat,
+                                                const double* __restrict__ X, int r0, int nr, int kb, int ke, int nk, int ldp, int64_t ld, int64_t c0,
+                                                gd4 (&acc)[4][2]) {
+    static_assert(Side == 0 || AForm == kGdAStored, "the diagonal mask is the stored form's");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
-    const int64_t c0 = (int64_t)blockIdx.x * kGdCols, ld = a.ld;
-    const int nr = op.nr, nk = a.nk, ldp = a.ldp;
-    const double* __restrict__ Pt = a.mats + op.Pt;
-    const double* __restrict__ X = a.panels + op.B;
-    typedef double d4 __attribute__((ext_vector_type(4)));
-    d4 acc[4][2];
+    const int arow = tid >> 2, aq = tid & 3;           // kGdAStored: row of the tile, quad of k
+    const int c = r0 + arow;                           // its row's size
+    const double* __restrict__ Pt = AForm == kGdAStored ? mat + (int64_t)c * ldp : mat;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
+        for (int j = 0; j < 2; ++j) acc[i][j] = (gd4){0.0, 0.0, 0.0, 0.0};
+    if (kb >= ke) return;                              // (block-uniform)
     double ra[4];
     double2 rx[4];
     auto load = [&](int k0) {
+        if constexpr (AForm == kGdAColumn) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int r = r0 + lane, k = k0 + wave + 4 * u;
+                ra[u] = (r < nr && k < nk) ? Pt[(int64_t)k * ldp + r] : 0.0;
+            }
+        } else {
+            const bool straddle = Side != 0 && k0 >= r0 && k0 < r0 + kGdMT; // (block-uniform)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int k = k0 + 4 * aq + 2 * h;                          // (even: k < nk <= ldp keeps k + 1 inside the row)
+                double2 v = make_double2(0.0, 0.0);
+                if (c < nr && k < nk) {
+                    v = *reinterpret_cast<const double2*>(Pt + k);
+                    if (k + 1 >= nk) v.y = 0.0;
+                    if (straddle) {                                         // the split
+                        if (Side > 0 ? !(k < c) : !(k > c)) v.x = 0.0;
+                        if (Side > 0 ? !(k + 1 < c) : !(k + 1 > c)) v.y = 0.0;
+                    }
+                }
+                ra[2 * h] = v.x;
+                ra[2 * h + 1] = v.y;
+            }
+        }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int r = r0 + lane, k = k0 + wave + 4 * u;                 // A[r][k] = Pt[k][r]: 64 consecutive sizes per k
-            ra[u] = (r < nr && k < nk) ? Pt[(int64_t)k * ldp + r] : 0.0;
+            const int k = k0 + wave + 4 * u;
             rx[u] = k < nk ? *reinterpret_cast<const double2*>(X + (int64_t)k * ld + c0 + 2 * lane) : make_double2(0.0, 0.0);
         }
     };
     auto stage = [&](int buf) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            As[buf][(wave + 4 * u) * kGdLdA + lane] = ra[u];
+            if constexpr (AForm == kGdAColumn) As[buf][(wave + 4 * u) * kGdLdA + lane] = ra[u];
+            else As[buf][(4 * aq + u) * kGdLdA + (arow ^ (aq << 3))] = ra[u];
             *reinterpret_cast<double2*>(&Xs[buf][(wave + 4 * u) * kGdLdX + 2 * lane]) = rx[u];
         }
     };
-    load(0);
+    load(kb);
     stage(0);
     __syncthreads();
     int buf = 0;
-    for (int k0 = 0; k0 < nk; k0 += kGdKT, buf ^= 1) {
-        const bool more = k0 + kGdKT < nk;
+    for (int k0 = kb; k0 < ke; k0 += kGdKT, buf ^= 1) {
+        const bool more = k0 + kGdKT < ke;
         if (more) load(k0 + kGdKT);
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) {
             double af[4], bf[2];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = As[buf][(4 * s4 + l4) * kGdLdA + 16 * i + l15];
+            for (int i = 0; i < 4; ++i) af[i] = As[buf][(4 * s4 + l4) * kGdLdA + ((16 * i + l15) ^ (AForm == kGdAStored ? s4 << 3 : 0))];
 #pragma unroll
             for (int j = 0; j < 2; ++j) bf[j] = Xs[buf][(4 * s4 + l4) * kGdLdX + 32 * wave + 16 * j + l15];
 #pragma unroll
@@ -279,7 +327,11 @@ __global__ __launch_bounds__(256) void gain_dense_gemm_kernel(const GainGemmArgs
         if (more) stage(buf ^ 1);                      // the other pair: its readers passed the barrier of the step before
         __syncthreads();
     }
-    double* __restrict__ F = a.panels + op.F;
+}
+
+// acc[i][j][q] is row r0 + 16 i + (lane >> 4) + 4 q, column c0 + 32 wave + 16 j + (lane & 15): the rows below nr go to `out`
+__device__ __forceinline__ void gain_dense_tile_store(double* __restrict__ out, int r0, int nr, int64_t ld, int64_t c0, const gd4 (&acc)[4][2]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, l4 = lane >> 4;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -287,8 +339,21 @@ __global__ __launch_bounds__(256) void gain_dense_gemm_kernel(const GainGemmArgs
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int r = r0 + 16 * i + l4 + 4 * q;
-                if (r < nr) F[(int64_t)r * ld + c0 + 32 * wave + 16 * j + l15] = acc[i][j][q];
+                if (r < nr) out[(int64_t)r * ld + c0 + 32 * wave + 16 * j + l15] = acc[i][j][q];
             }
+}
+
+// grid (column tiles, row tiles of the tallest op, interior non-root nodes of the level)
+__global__ __launch_bounds__(256) void gain_dense_gemm_kernel(const GainGemmArgs a) {
+    __shared__ __attribute__((aligned(16))) double As[2][kGdKT * kGdLdA];
+    __shared__ __attribute__((aligned(16))) double Xs[2][kGdKT * kGdLdX];
+    const GainGemmOp op = a.ops[blockIdx.z];
+    const int r0 = blockIdx.y * kGdMT;
+    if (r0 >= op.nr) return;                           // (block-uniform, ahead of every barrier)
+    const int64_t c0 = (int64_t)blockIdx.x * kGdCols;
+    gd4 acc[4][2];
+    gain_dense_tile<kGdAColumn, 0>(As, Xs, a.mats + op.Pt, a.panels + op.B, r0, op.nr, 0, a.nk, a.nk, a.ldp, a.ld, c0, acc);
+    gain_dense_tile_store(a.panels + op.F, r0, op.nr, a.ld, c0, acc);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- root
@@ -367,29 +432,20 @@ struct GainWeightArgs {
 // grid (column blocks of 256, row blocks of 16, nodes of the depth)
 __global__ __launch_bounds__(256) void gain_posterior_dense_weights_kernel(const GainWeightArgs a) {
     const GainWeightOp op = a.ops[blockIdx.z];
-    const int i0 = blockIdx.y * kGdProdRows;
-    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i0 >= op.rows || f >= a.p.ncols) return;
-    const int n = min(kGdProdRows, op.rows - i0);
-    double v[kGdProdRows];
-    int lifts[kGdProdRows];                            // (not read: the untracked product)
+    gain_dense_node(a.p, op.child0, op.n_children, op.rows, op.dst, [&](int i0, int n, int64_t f, double (&v)[kGdProdRows]) {
 #pragma unroll
-    for (int j = 0; j < kGdProdRows; ++j) v[j] = 0.0;
-    if (op.outside < 0) {
+        for (int j = 0; j < kGdProdRows; ++j) v[j] = 0.0;
+        if (op.outside < 0) {
 #pragma unroll
-        for (int j = 0; j < kGdProdRows; ++j)
-            if (j < n) v[j] = a.mass[i0 + j];
-    } else {
-        const double* __restrict__ O = a.p.panels + op.outside + (int64_t)i0 * a.p.ld + f;
+            for (int j = 0; j < kGdProdRows; ++j)
+                if (j < n) v[j] = a.mass[i0 + j];
+        } else {
+            const double* __restrict__ O = a.p.panels + op.outside + (int64_t)i0 * a.p.ld + f;
 #pragma unroll
-        for (int j = 0; j < kGdProdRows; ++j)
-            if (j < n) v[j] = O[(int64_t)j * a.p.ld];
-    }
-    gain_dense_times_children(a.p, op.child0, op.n_children, i0, n, f, a.p.col[f], v, lifts);
-    double* __restrict__ dst = a.p.panels + op.dst + (int64_t)i0 * a.p.ld + f;
-#pragma unroll
-    for (int j = 0; j < kGdProdRows; ++j)
-        if (j < n) dst[(int64_t)j * a.p.ld] = v[j];
+            for (int j = 0; j < kGdProdRows; ++j)
+                if (j < n) v[j] = O[(int64_t)j * a.p.ld];
+        }
+    });
 }
 
 // --------------------------------------------------------------------------------------- scaled: product and weights
@@ -490,116 +546,40 @@ __global__ __launch_bounds__(256) void gain_scaled_weights_kernel(const GainWeig
 // the four k of a fragment step (k >> 2 = s4) and permutes rows inside aligned groups of 32, so a fragment read still finds
 // 16 consecutive doubles per k, and its two k of a half-wave 16 doubles apart (80 = 16 mod 32): neither side serialises.
 // The contraction length is the op's (R + 1 and M + 1 meet in one launch); every load is guarded, c <= M and s < rows(u).
-struct GainGemmTOp {
-    int64_t Pt, W, O;                // matrix (doubles from `mats`), w and outside panels (doubles from `panels`)
-    int32_t nk;                      // contraction over s = 0..nk-1
-    int32_t pad;
+//
+// GainNodeOp is the ONE op of the down pass behind the weights: per depth a table of the interior nodes (the root alone at depth
+// 0, which no GEMM reads) and one of the leaves.  The transposed GEMM, the split GEMM and the interior outputs and summaries read
+// the first, the leaf outputs and summaries and the fused predictive kernel the second.
+struct GainNodeOp {
+    int64_t outside, B, W, Pt;       // interior: outside (-1: the root, `mass`), B, w (-1 at the root) panels, the matrix; leaf: W, Pt
+    int32_t node;
+    int32_t n;                       // interior: the node's sizes 0..n-1 (R + 1 at the root, M + 1 below)
+    int32_t rows;                    // rows(u): the parent's sizes, the contraction of the node's GEMM
+    int32_t taxon;                   // leaf: its row of `counts`
 };
 struct GainGemmTArgs {
-    const GainGemmTOp* ops;
+    const GainNodeOp* ops;
     const double* mats;
     double* panels;
     int64_t ld;
     int32_t nr, ldp;                 // rows c = 0..nr-1 of the outside panel
 };
 
-// One 64 x 128 tile of that product: acc = A[r0 .. r0 + 63][0 .. nk) X[0 .. nk)[c0 .. c0 + 127], the K loop of both kernels that
-// contract over a matrix as stored.  Ends behind a barrier: the buffers are free for the caller's next tile.
-typedef double gd4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void gain_dense_tile_t(double (*As)[kGdKT * kGdLdA], double (*Xs)[kGdKT * kGdLdX], const double* __restrict__ mat,
-                                                  const double* __restrict__ X, int r0, int nr, int nk, int ldp, int64_t ld, int64_t c0, gd4 (&acc)[4][2]) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l15 = lane & 15, l4 = lane >> 4;
-    const int arow = tid >> 2, aq = tid & 3;           // A staging: row of the tile, quad of k
-    const double* __restrict__ Pt = mat + (int64_t)(r0 + arow) * ldp;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (gd4){0.0, 0.0, 0.0, 0.0};
-    double2 ra[2], rx[4];
-    auto load = [&](int k0) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int k = k0 + 4 * aq + 2 * h;                              // (even: k < nk <= ldp keeps k + 1 inside the row)
-            double2 v = make_double2(0.0, 0.0);
-            if (r0 + arow < nr && k < nk) {
-                v = *reinterpret_cast<const double2*>(Pt + k);
-                if (k + 1 >= nk) v.y = 0.0;
-            }
-            ra[h] = v;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = k0 + wave + 4 * u;
-            rx[u] = k < nk ? *reinterpret_cast<const double2*>(X + (int64_t)k * ld + c0 + 2 * lane) : make_double2(0.0, 0.0);
-        }
-    };
-    auto stage = [&](int buf) {
-        const int col = arow ^ (aq << 3);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            As[buf][(4 * aq + 2 * h) * kGdLdA + col] = ra[h].x;
-            As[buf][(4 * aq + 2 * h + 1) * kGdLdA + col] = ra[h].y;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) *reinterpret_cast<double2*>(&Xs[buf][(wave + 4 * u) * kGdLdX + 2 * lane]) = rx[u];
-    };
-    load(0);
-    stage(0);
-    __syncthreads();
-    int buf = 0;
-    for (int k0 = 0; k0 < nk; k0 += kGdKT, buf ^= 1) {
-        const bool more = k0 + kGdKT < nk;
-        if (more) load(k0 + kGdKT);
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            double af[4], bf[2];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = As[buf][(4 * s4 + l4) * kGdLdA + ((16 * i + l15) ^ (s4 << 3))];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bf[j] = Xs[buf][(4 * s4 + l4) * kGdLdX + 32 * wave + 16 * j + l15];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[j], acc[i][j], 0, 0, 0);
-        }
-        if (more) stage(buf ^ 1);                      // the other pair: its readers passed the barrier of the step before
-        __syncthreads();
-    }
-}
-
 // grid (column tiles, row tiles of M + 1, interior non-root nodes of the depth)
 __global__ __launch_bounds__(256) void gain_posterior_dense_gemm_t_kernel(const GainGemmTArgs a) {
     __shared__ __attribute__((aligned(16))) double As[2][kGdKT * kGdLdA];
     __shared__ __attribute__((aligned(16))) double Xs[2][kGdKT * kGdLdX];
-    const GainGemmTOp op = a.ops[blockIdx.z];
-    const int r0 = blockIdx.y * kGdMT, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int l15 = lane & 15, l4 = lane >> 4, nr = a.nr;
-    const int64_t c0 = (int64_t)blockIdx.x * kGdCols, ld = a.ld;
+    const GainNodeOp op = a.ops[blockIdx.z];
+    const int r0 = blockIdx.y * kGdMT;
+    const int64_t c0 = (int64_t)blockIdx.x * kGdCols;
     gd4 acc[4][2];
-    gain_dense_tile_t(As, Xs, a.mats + op.Pt, a.panels + op.W, r0, nr, op.nk, a.ldp, ld, c0, acc);
-    double* __restrict__ O = a.panels + op.O;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int r = r0 + 16 * i + l4 + 4 * q;
-                if (r < nr) O[(int64_t)r * ld + c0 + 32 * wave + 16 * j + l15] = acc[i][j][q];
-            }
+    gain_dense_tile<kGdAStored, 0>(As, Xs, a.mats + op.Pt, a.panels + op.W, r0, a.nr, 0, op.rows, op.rows, a.ldp, a.ld, c0, acc);
+    gain_dense_tile_store(a.panels + op.outside, r0, a.nr, a.ld, c0, acc);
 }
 
 // ------------------------------------------------------------------------------------------------------- down: outputs
 // Both output kernels: 64 columns per block, lanes along f, the sizes dealt to four waves and folded in a fixed order.
 // res is [4][n_nodes][ld]: p_absent, mean, p_gain, p_loss; posterior, when asked for, [n_nodes][N][ld].  Everything / Z.
-struct GainNodeOp {
-    int64_t outside, B, W, Pt;       // interior: outside (-1: the root, `mass`), B, w (-1 at the root) panels, the matrix; leaf: W, Pt
-    int32_t node;
-    int32_t n;                       // interior: the node's sizes 0..n-1 (R + 1 at the root, M + 1 below)
-    int32_t rows;                    // rows(u): the parent's sizes
-    int32_t taxon;                   // leaf: its row of `counts`
-};
 struct GainOutArgs {
     const GainNodeOp* ops;
     const double* mats;
@@ -781,13 +761,8 @@ __global__ __launch_bounds__(256) void gain_scaled_leaf_kernel(const GainOutArgs
 // by two cross-lane exchanges, (g0 + g1) + (g2 + g3).  No atomics, and nothing of a column depends on its neighbours, its tile
 // or the batch.  Every output is a ratio inside one column of one w panel: in the scaled mode the column's power of two
 // cancels exactly and the kernel runs on the mantissas as it is.  res is [5][n_taxa][ld]: mean, sd, p_below, p_obs, p_above.
-struct GainPredOp {
-    int64_t Pt, W;                   // the leaf's matrix (doubles from `mats`), its w panel (doubles from `panels`)
-    int32_t nk;                      // rows(l): the parent's sizes, the contraction
-    int32_t taxon;                   // the leaf's row of `counts` and of res
-};
 struct GainPredArgs {
-    const GainPredOp* ops;
+    const GainNodeOp* ops;           // the depth's leaves: Pt, W, rows (the contraction) and taxon, the leaf's row of `counts` and of res
     const double* mats;
     const double* panels;
     double* res;
@@ -802,7 +777,7 @@ struct GainPredArgs {
 __global__ __launch_bounds__(256) void gain_predictive_dense_leaf_kernel(const GainPredArgs a) {
     __shared__ __attribute__((aligned(16))) double As[2][kGdKT * kGdLdA];
     __shared__ __attribute__((aligned(16))) double Xs[2][kGdKT * kGdLdX];
-    const GainPredOp op = a.ops[blockIdx.y];
+    const GainNodeOp op = a.ops[blockIdx.y];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, l4 = lane >> 4;
     const int64_t c0 = (int64_t)blockIdx.x * kGdCols, ld = a.ld;
     const int nr = a.nr;
@@ -831,7 +806,7 @@ __global__ __launch_bounds__(256) void gain_predictive_dense_leaf_kernel(const G
     };
     for (int r0 = 0; r0 < nr; r0 += kGdMT) {
         gd4 acc[4][2];
-        gain_dense_tile_t(As, Xs, a.mats + op.Pt, a.panels + op.W, r0, nr, op.nk, a.ldp, ld, c0, acc);
+        gain_dense_tile<kGdAStored, 0>(As, Xs, a.mats + op.Pt, a.panels + op.W, r0, nr, 0, op.rows, op.rows, a.ldp, ld, c0, acc);
         if (a.err == nullptr) {                        // (kernel-uniform) no error model: y = c, weight 1 -- no tap loop, no load
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -885,8 +860,6 @@ __global__ __launch_bounds__(256) void gain_predictive_dense_leaf_kernel(const G
 #include "gain_marginal_kernel.h"
 
 // ---------------------------------------------------------------------------------------------------------------- host
-enum { kGdBuild = 0, kGdProduct = 1, kGdGemm = 2, kGdRoot = 3, kGdWeights = 4, kGdGemmT = 5, kGdInterior = 6, kGdLeaf = 7, kGdPredict = 8, kGdKinds = 9 };
-
 // HIP events around the launches of a call, by kind (cafe_set_profiling)
 struct GainTimer {
     bool on = false;
@@ -915,142 +888,162 @@ size_t put(std::vector<char>& blob, const std::vector<T>& v) {
     return at;
 }
 
-// The staging of one batch of the down pass's outputs and the way back to the caller's arrays
-struct GainDownHost {
-    const cafe_gain_posterior_out* out;
-    std::vector<double> res, posterior;                // [4][n_nodes][nb], [n_nodes][N][nb]
+// A plain kernel or, in the scaled mode, its twin, which takes the plain kernel's argument and then its own
+template <class A, class... X>
+void launch_either(bool scaled, void (*plain)(A), dim3 plain_grid, void (*twin)(A, X...), dim3 twin_grid, hipStream_t s, const A& a, X... x) {
+    if (scaled) hipLaunchKernelGGL(twin, twin_grid, dim3(256), 0, s, a, x...);
+    else hipLaunchKernelGGL(plain, plain_grid, dim3(256), 0, s, a);
+}
+// CAFE_LAUNCH around it, its failure text included; args: launch_either's, in parentheses
+#define GAIN_LAUNCH_EITHER(c, args)              \
+    do {                                         \
+        (void)hipGetLastError();                 \
+        launch_either args;                      \
+        HIP_TRY(c, hipGetLastError());           \
+    } while (0)
 
-    void collect(int64_t b0, int64_t nb, int nn, int N, const double* lnl) const {
-        double* const dst[4] = {out->p_absent, out->mean, out->p_gain, out->p_loss};
-        for (int64_t b = 0; b < nb; ++b) {
-            if (!std::isfinite(lnl[b])) continue;      // the entry keeps its NaN
-            for (int k = 0; k < 4; ++k)
-                for (int v = 0; v < nn; ++v) dst[k][(b0 + b) * nn + v] = res[((size_t)k * nn + v) * nb + b];
-            if (!out->posterior) continue;
-            double* po = out->posterior + (b0 + b) * nn * N;
-            for (int64_t i = 0; i < (int64_t)nn * N; ++i) po[i] = posterior[(size_t)i * nb + b];
-        }
-    }
+// What the four entries are asked in common
+struct GainCall {
+    const cafe_params* pr;
+    const double *lam, *mus, *nus;
+    double root_absent;
+    int64_t n;
+    const int64_t* family;
+    double level = 0.0;                                // the marginal entry's interval
 };
 
-// The same for cafe_gain_leaf_predictive: five numbers per (entry, taxon)
-struct GainPredictHost {
-    const cafe_gain_leaf_predictive_out* out;
-    std::vector<double> res;                           // [5][n_taxa][nb]
+// Where a call's answers go.  The mode says which down pass runs (kGainScore: none); the planes say what it leaves: every
+// output but lnl is a plane [n][rows] of the caller's, rows = n_nodes or, in the predictive mode, n_taxa, in the order in which
+// the mode's kernels write them ([planes][rows][ld] on the device).  A batch comes back by one 2-D copy per kind of plane into
+// the staging below and is scattered from there.
+struct GainSink {
+    GainMode mode = kGainScore;
+    double* lnl = nullptr;                             // [n]
+    std::vector<double*> dst;                          // a null plane is computed and not delivered (the predictive entry)
+    std::vector<int32_t*> idst;
+    int rows = 0;
+    double* posterior = nullptr;                       // optional block [n][rows][N] (the posterior entry)
+    std::vector<double> res, post;                     // [planes][rows][nb], [rows][N][nb]
+    std::vector<int32_t> ires;
 
-    void collect(int64_t b0, int64_t nb, int T, const double* lnl) const {
-        double* const dst[5] = {out->mean, out->sd, out->p_below, out->p_obs, out->p_above};
-        for (int64_t b = 0; b < nb; ++b) {
-            if (!std::isfinite(lnl[b])) continue;      // the entry keeps its NaN
-            for (int k = 0; k < 5; ++k)
-                for (int t = 0; dst[k] && t < T; ++t) dst[k][(b0 + b) * T + t] = res[((size_t)k * T + t) * nb + b];
-        }
+    void resize(int64_t entries, int N) {
+        res.resize(dst.size() * (size_t)rows * entries);
+        ires.resize(idst.size() * (size_t)rows * entries);
+        if (posterior) post.resize((size_t)rows * N * entries);
     }
-};
-
-// The same for cafe_gain_marginal_dense: four doubles and three integers per (entry, node)
-struct GainMarginalHost {
-    const cafe_gain_marginal_out* out;
-    double level;
-    std::vector<double> res;                           // [4][n_nodes][nb]: mean, p_increase, p_decrease, p_same
-    std::vector<int32_t> ires;                         // [3][n_nodes][nb]: mode, lo, hi
-
-    void collect(int64_t b0, int64_t nb, int nn, const double* lnl) const {
-        double* const dst[4] = {out->mean, out->p_increase, out->p_decrease, out->p_same};
-        int32_t* const idst[3] = {out->mode, out->lo, out->hi};
+    hipError_t copy_back(const double* d_res, const int32_t* d_ires, const double* d_post, int64_t ld, int64_t nb, int N, hipStream_t s) {
+        hipError_t e = hipSuccess;                     // [..][ld] on the device, [..][nb] on the host
+        if (!dst.empty())
+            e = hipMemcpy2DAsync(res.data(), sizeof(double) * nb, d_res, sizeof(double) * ld, sizeof(double) * nb, dst.size() * (size_t)rows, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && !idst.empty())
+            e = hipMemcpy2DAsync(ires.data(), sizeof(int32_t) * nb, d_ires, sizeof(int32_t) * ld, sizeof(int32_t) * nb, idst.size() * (size_t)rows, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && posterior)
+            e = hipMemcpy2DAsync(post.data(), sizeof(double) * nb, d_post, sizeof(double) * ld, sizeof(double) * nb, (size_t)rows * N, hipMemcpyDeviceToHost, s);
+        return e;
+    }
+    // lnl: the batch's.  An entry whose lnl is not finite keeps what its caller filled in: NaN, and -1 in the integers.
+    void collect(int64_t b0, int64_t nb, int N, const double* lnl) const {
+        const int nr = rows;                           // (locals: the scatter is the hot loop of a call on a short tree)
         for (int64_t b = 0; b < nb; ++b) {
-            if (!std::isfinite(lnl[b])) continue;      // the entry keeps its NaN and -1
-            for (int v = 0; v < nn; ++v) {
-                for (int k = 0; k < 4; ++k) dst[k][(b0 + b) * nn + v] = res[((size_t)k * nn + v) * nb + b];
-                for (int k = 0; k < 3; ++k) idst[k][(b0 + b) * nn + v] = ires[((size_t)k * nn + v) * nb + b];
+            if (!std::isfinite(lnl[b])) continue;
+            for (size_t k = 0; k < dst.size(); ++k) {
+                double* const to = dst[k];
+                if (!to) continue;
+                const double* const from = res.data() + k * nr * nb + b;
+                for (int v = 0; v < nr; ++v) to[(b0 + b) * nr + v] = from[(size_t)v * nb];
             }
+            for (size_t k = 0; k < idst.size(); ++k) {
+                int32_t* const to = idst[k];
+                const int32_t* const from = ires.data() + k * nr * nb + b;
+                for (int v = 0; v < nr; ++v) to[(b0 + b) * nr + v] = from[(size_t)v * nb];
+            }
+            if (!posterior) continue;
+            double* po = posterior + (b0 + b) * nr * N;
+            for (int64_t i = 0; i < (int64_t)nr * N; ++i) po[i] = post[(size_t)i * nb + b];
         }
     }
 };
 
-// All four entries: the planning (keys, levels, op tables, workspace), the up pass launch for launch, and -- with `down`, the
-// posterior entry, or `pred`, the predictive one -- the sum rule forced at the root, the plan and the launches of the down pass
-// behind the root kernel.  Both walk the depths with the weights kernel and the transposed GEMM of the interior nodes; `down` adds
-// the output kernels of every node, `pred` the fused kernel of the depth's leaves.  `marg`, the marginal entry, walks them with the
-// weights kernel, the SPLIT transposed GEMM in the other one's place, and the summary kernels of every node.
-int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const double* lam, const double* mus, const double* nus, double root_absent,
-                    int64_t n, const int64_t* family, double* family_lnl, GainDownHost* down, GainPredictHost* pred = nullptr, GainMarginalHost* marg = nullptr) {
+// ---- the checks every mode makes of its arguments and of the context
+int gain_dense_check(cafe_ctx* c, const char* who, const GainCall& q, const double* family_lnl) {
+    const cafe_params* pr = q.pr;
     if (!pr || !pr->prior) { set_err(c, "%s: params with a prior are required", who); return CAFE_ERR_ARGUMENT; }
     if (pr->model != CAFE_MODEL_BASE) { set_err(c, "%s: base model only", who); return CAFE_ERR_ARGUMENT; }
     if (c->comm) { set_err(c, "%s: not valid on a context with a communicator attached", who); return CAFE_ERR_STATE; }
-    if (n < 0 || !lam || (n > 0 && (!family || !family_lnl))) { set_err(c, "%s: lambdas, family and family_lnl are required", who); return CAFE_ERR_ARGUMENT; }
+    if (q.n < 0 || !q.lam || (q.n > 0 && (!q.family || !family_lnl))) { set_err(c, "%s: lambdas, family and family_lnl are required", who); return CAFE_ERR_ARGUMENT; }
     if ((c->n_dev > 0) != (pr->error_model != nullptr)) {
         set_err(c, "%s: error model %s but the problem was created with n_deviations=%d", who, pr->error_model ? "given" : "missing", c->n_dev);
         return CAFE_ERR_ARGUMENT;
     }
     if (!c->device_ready || !c->d_counts) { set_err(c, "%s: the context holds no family table", who); return CAFE_ERR_STATE; }
-    for (int64_t i = 0; i < n; ++i)
-        if (family[i] < -1 || family[i] >= c->F_all) {
-            set_err(c, "%s: family index %lld outside -1..%lld", who, (long long)family[i], (long long)c->F_all - 1);
+    for (int64_t i = 0; i < q.n; ++i)
+        if (q.family[i] < -1 || q.family[i] >= c->F_all) {
+            set_err(c, "%s: family index %lld outside -1..%lld", who, (long long)q.family[i], (long long)c->F_all - 1);
             return CAFE_ERR_ARGUMENT;
         }
-    if (const int rc = gain_rates_check(c, who, 1, nus, root_absent)) return rc;
-    if (n == 0) return CAFE_OK;
-    const int nn = c->n_nodes, L = c->n_lambdas, N = c->N, M = c->M, R = c->R, ldp = round_up(N, 2);
-    const bool scaled = c->gain_scaling != 0;          // cafe_set_gain_scaling: the scaled twins of every kernel but the build and the GEMMs
+    return gain_rates_check(c, who, 1, q.nus, q.root_absent);
+}
 
-    // ---- what the host decides alone: an invalid rate set is -inf in every entry, a NaN lambda that passes the rule NaN
-    c->last.state = LastCall::kNone;                   // cafe_family_results is not meaningful after this call
-    const bool walk = down || pred || marg;            // the down pass is planned and run
-    const int T = c->n_taxa;
-    double ms[kGdKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, flops = 0.0;
-    if (down) {
-        std::copy(ms, ms + 8, c->gain_dense_posterior_ms);
-        c->gain_dense_posterior_flops = 0.0;
-    } else if (pred) {
-        std::copy(ms, ms + 7, c->gain_predictive_ms);
-        c->gain_predictive_flops = 0.0;
-    } else if (marg) {
-        std::copy(ms, ms + 9, c->gain_marginal_ms);
-        c->gain_marginal_flops = 0.0;
-    } else {
-        std::copy(ms, ms + 4, c->gain_dense_ms);
-        c->gain_dense_flops = 0.0;
-    }
-    {
-        bool nan = false;
-        for (int k = 0; k < L; ++k) nan = nan || std::isnan(lam[k]);
-        const bool valid = lambdas_valid(c, lam) && death_rates_ok(L, mus);
-        if (!valid || nan) {
-            std::fill(family_lnl, family_lnl + n, valid ? std::numeric_limits<double>::quiet_NaN() : -std::numeric_limits<double>::infinity());
-            return CAFE_OK;
-        }
-    }
+// ---- what the host decides alone: an invalid rate set is -inf in every entry, a NaN lambda that passes the rule NaN
+bool gain_dense_host_answer(cafe_ctx* c, const GainCall& q, double* family_lnl) {
+    bool nan = false;
+    for (int k = 0; k < c->n_lambdas; ++k) nan = nan || std::isnan(q.lam[k]);
+    const bool valid = lambdas_valid(c, q.lam) && death_rates_ok(c->n_lambdas, q.mus);
+    if (valid && !nan) return false;
+    std::fill(family_lnl, family_lnl + q.n, valid ? std::numeric_limits<double>::quiet_NaN() : -std::numeric_limits<double>::infinity());
+    return true;
+}
 
-    // ---- keys, levels and the op tables.  A node's height: 0 when its children are leaves, else 1 + its tallest interior child's;
-    // a level's product reads the F panels of the levels below it, its GEMMs read the level's own B panels
-    std::map<std::pair<int, long>, int> key_of;
+// ---- the plan: everything a call fixes from the tree, the rates and the mode before the device is asked anything.  index()
+// numbers the matrices and panels, which sizes the workspace; tables() then writes the op tables for the panel stride that the
+// workspace allows.
+struct GainPlan {
+    // keys: one matrix per distinct (lambda index, quantized t)
     std::vector<SlotParamGain> slots;
-    std::vector<int> node_key(nn, -1), height(nn, -1), bidx(nn, -1), fidx(nn, -1);
+    std::vector<int> node_key;
+    // the up pass.  A node's height: 0 when its children are leaves, else 1 + its tallest interior child's; a level's product
+    // reads the F panels of the levels below it, its GEMMs read the level's own B panels
+    std::vector<int> height, bidx, fidx;
     int n_pan = 0, n_levels = 0;
-    for (int u = 0; u < nn; ++u) {
-        if (u != c->root) {
-            const auto it = key_of.emplace(std::make_pair(c->lam_idx[u], quantize_time(c->blen[u])), (int)slots.size());
-            if (it.second) slots.push_back(gain_branch_slot(c, u, lam, mus, nus));
-            node_key[u] = it.first->second;
-        }
-        if (c->leaf_taxon[u] >= 0) continue;
-        height[u] = 0;
-        for (int ch : c->children[u]) height[u] = std::max(height[u], height[ch] + 1);
-        n_levels = std::max(n_levels, height[u] + 1);
-        bidx[u] = n_pan++;
-        if (u != c->root) fidx[u] = n_pan++;
-    }
-    if (c->leaf_taxon[c->root] >= 0 || height[c->root] != n_levels - 1) { set_err(c, "%s: the root is not the tallest node of the tree", who); return CAFE_ERR_STATE; }
-    const int n_keys = (int)slots.size();
-    const int64_t mat_stride = (int64_t)N * ldp;
-
-    // ---- the down pass: the nodes by depth (breadth first: parents in front of their children), an outside panel per interior
-    // non-root node behind the up pass's panels, the w panels of the widest depth behind those
-    std::vector<int> depth(nn, 0), by_depth{c->root}, depth_off{0}, oidx(nn, -1), widx(nn, -1);
+    // the down pass (with `walk`): the nodes by depth (breadth first: parents in front of their children), an outside panel per
+    // interior non-root node behind the up pass's panels, the w panels of the widest depth behind those
+    std::vector<int> by_depth, depth_off{0}, oidx, widx;
     int n_down = 0, n_depths = 0;
-    const bool want_posterior = down && down->out->posterior;
-    if (walk) {
+    // the tables: per level its products and GEMMs and the tallest of each; per depth the weights of every node, the interior
+    // nodes (at depth 0 the root alone) and the leaves
+    std::vector<GainChild> children;
+    std::vector<GainProdOp> prod_ops;
+    std::vector<GainGemmOp> gemm_ops;
+    std::vector<GainWeightOp> weight_ops;
+    std::vector<GainNodeOp> int_ops, leaf_ops;
+    std::vector<int> prod_off{0}, gemm_off{0}, prod_rows, gemm_rows, weight_off{0}, int_off{0}, leaf_off{0}, weight_rows;
+    std::vector<double> reals;                         // log mass of the root sizes, then the error model
+    std::vector<double> mass;                          // the root's outside vector (with `walk`)
+
+    int n_keys() const { return (int)slots.size(); }
+
+    int index(cafe_ctx* c, const char* who, const GainCall& q, bool walk) {
+        const int nn = c->n_nodes;
+        std::map<std::pair<int, long>, int> key_of;
+        node_key.assign(nn, -1); height.assign(nn, -1); bidx.assign(nn, -1); fidx.assign(nn, -1);
+        for (int u = 0; u < nn; ++u) {
+            if (u != c->root) {
+                const auto it = key_of.emplace(std::make_pair(c->lam_idx[u], quantize_time(c->blen[u])), (int)slots.size());
+                if (it.second) slots.push_back(gain_branch_slot(c, u, q.lam, q.mus, q.nus));
+                node_key[u] = it.first->second;
+            }
+            if (c->leaf_taxon[u] >= 0) continue;
+            height[u] = 0;
+            for (int ch : c->children[u]) height[u] = std::max(height[u], height[ch] + 1);
+            n_levels = std::max(n_levels, height[u] + 1);
+            bidx[u] = n_pan++;
+            if (u != c->root) fidx[u] = n_pan++;
+        }
+        if (c->leaf_taxon[c->root] >= 0 || height[c->root] != n_levels - 1) { set_err(c, "%s: the root is not the tallest node of the tree", who); return CAFE_ERR_STATE; }
+        oidx.assign(nn, -1); widx.assign(nn, -1);
+        by_depth.assign(1, c->root);
+        if (!walk) return CAFE_OK;
+        std::vector<int> depth(nn, 0);
         int n_out = 0, widest = 0;
         for (size_t at = 0; at < by_depth.size(); ++at)
             for (int ch : c->children[by_depth[at]]) { depth[ch] = depth[by_depth[at]] + 1; by_depth.push_back(ch); }
@@ -1065,338 +1058,360 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
         for (int d = 1; d < n_depths; ++d)
             for (int k = depth_off[d]; k < depth_off[d + 1]; ++k) widx[by_depth[k]] = n_pan + n_out + (k - depth_off[d]);
         n_down = n_out + widest;
+        return CAFE_OK;
     }
 
-    // ---- columns per batch: the matrices stand once, a batch adds its panels
-    const int split_tiles = (M + kGdMT) / kGdMT;       // row tiles of the split GEMM: its partials are [n_nodes][tiles][3][ld]
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t fixed_bytes = sizeof(double) * (size_t)mat_stride * n_keys + ((size_t)64 << 10) + sizeof(GainChild) * (size_t)nn +
+    void tables(const cafe_ctx* c, const GainCall& q, bool walk, int64_t mat_stride, int64_t pan_stride) {
+        const int nn = c->n_nodes, M = c->M, R = c->R;
+        auto factor = [&](int v) {                     // the factor of node v in a product over its parent's sizes
+            const bool leaf = c->leaf_taxon[v] >= 0;
+            return GainChild{leaf ? node_key[v] * mat_stride : fidx[v] * pan_stride, leaf ? c->leaf_taxon[v] : -1, 0};
+        };
+        for (int lv = 0; lv < n_levels; ++lv) {
+            int pr_rows = 0, gm_rows = 0;
+            for (int u = 0; u < nn; ++u) {
+                if (height[u] != lv) continue;
+                GainProdOp po{};
+                po.dst = bidx[u] * pan_stride;
+                po.rows = (u == c->root ? R : M) + 1;
+                po.child0 = (int32_t)children.size();
+                for (int ch : c->children[u]) children.push_back(factor(ch));
+                po.n_children = (int32_t)children.size() - po.child0;
+                po.carry = fidx[u];
+                prod_ops.push_back(po);
+                pr_rows = std::max(pr_rows, po.rows);
+                if (u == c->root) continue;
+                const int nr = (c->parent[u] == c->root ? R : M) + 1;
+                gemm_ops.push_back({node_key[u] * mat_stride, bidx[u] * pan_stride, fidx[u] * pan_stride, nr, 0});
+                gm_rows = std::max(gm_rows, nr);
+            }
+            prod_off.push_back((int)prod_ops.size()); gemm_off.push_back((int)gemm_ops.size());
+            prod_rows.push_back(pr_rows); gemm_rows.push_back(gm_rows);
+        }
+        for (int d = 0; d < n_depths; ++d) {
+            int w_rows = 0;
+            for (int k = depth_off[d]; k < depth_off[d + 1]; ++k) {
+                const int u = by_depth[k], p = c->parent[u];
+                if (u == c->root) {
+                    int_ops.push_back({-1, bidx[u] * pan_stride, -1, 0, u, R + 1, 0, -1});
+                    continue;
+                }
+                const int rows = (p == c->root ? R : M) + 1;
+                GainWeightOp wo{widx[u] * pan_stride, p == c->root ? -1 : oidx[p] * pan_stride, rows, (int32_t)children.size(), 0, oidx[u]};
+                for (int sib : c->children[p])
+                    if (sib != u) children.push_back(factor(sib));
+                wo.n_children = (int32_t)children.size() - wo.child0;
+                weight_ops.push_back(wo);
+                w_rows = std::max(w_rows, rows);
+                if (c->leaf_taxon[u] >= 0)
+                    leaf_ops.push_back({-1, -1, widx[u] * pan_stride, node_key[u] * mat_stride, u, M + 1, rows, c->leaf_taxon[u]});
+                else
+                    int_ops.push_back({oidx[u] * pan_stride, bidx[u] * pan_stride, widx[u] * pan_stride, node_key[u] * mat_stride, u, M + 1, rows, -1});
+            }
+            weight_off.push_back((int)weight_ops.size());
+            int_off.push_back((int)int_ops.size()); leaf_off.push_back((int)leaf_ops.size());
+            weight_rows.push_back(w_rows);
+        }
+        reals.resize((size_t)R + 1 + (size_t)(M + 1) * c->n_dev);
+        reals[0] = std::log(q.root_absent);
+        for (int j = 0; j < R; ++j) reals[j + 1] = std::log1p(-q.root_absent) + std::log((double)q.pr->prior[j]);    // compute() returns float
+        if (c->n_dev > 0) std::memcpy(reals.data() + R + 1, q.pr->error_model, sizeof(double) * (size_t)(M + 1) * c->n_dev);
+        if (!walk) return;
+        mass.resize((size_t)R + 1);
+        mass[0] = q.root_absent;
+        for (int j = 1; j <= R; ++j) mass[j] = (1.0 - q.root_absent) * (double)q.pr->prior[j - 1];
+    }
+};
+
+// ---- the workspace: the tables in one blob at its front, then the batch's columns and lnl, the matrices (they stand once), the
+// panels, and what the mode's down pass leaves.  Offsets are bytes from the workspace's base.  The columns, the matrices and the
+// panels start on 4 KB: where they stand must not depend on the size of the tables in front of them -- at 256-byte steps the
+// memory-bound kernels measured up to 5 % apart (leaf outputs, order 751) between two blob sizes 19 KB apart.  The 64 KB of
+// slack in the budget's fixed part covers the three gaps.
+constexpr size_t kGdRegion = 4096;
+inline size_t gain_region_up(size_t v) { return (v + kGdRegion - 1) / kGdRegion * kGdRegion; }
+struct GainLayout {
+    int64_t entries = 0, ld = 0, mat_stride = 0, pan_stride = 0;   // entries per batch; columns of a panel; doubles per matrix and per panel
+    int split_tiles = 0;                               // row tiles of the split GEMM: its partials are [n_nodes][tiles][3][ld]
+    std::vector<char> blob;
+    size_t o_children = 0, o_prod = 0, o_gemm = 0, o_slots = 0, o_reals = 0, o_weight = 0, o_int = 0, o_leaf = 0, o_mass = 0;
+    size_t o_col = 0, o_out = 0, o_mats = 0, o_pan = 0, o_res = 0, o_post = 0, o_parts = 0, o_ires = 0, o_exps = 0, o_zt = 0, need = 0;
+
+    void batch(const cafe_ctx* c, const GainCall& q, const GainSink& sink, bool scaled, const GainPlan& plan, size_t budget);
+    void place(const cafe_ctx* c, const GainSink& sink, bool scaled, const GainPlan& plan);
+};
+
+// Columns per batch under `budget` bytes, from the plan's index alone: the matrices stand once, a batch adds its panels
+void GainLayout::batch(const cafe_ctx* c, const GainCall& q, const GainSink& sink, bool scaled, const GainPlan& plan, size_t budget) {
+    GainLayout& w = *this;
+    const int nn = c->n_nodes, N = c->N, M = c->M, R = c->R, n_keys = plan.n_keys(), n_pan = plan.n_pan, n_down = plan.n_down;
+    const bool walk = sink.mode != kGainScore, marg = sink.mode == kGainMarginal;
+    const size_t planes = sink.dst.size() * (size_t)sink.rows, iplanes = sink.idst.size() * (size_t)sink.rows;
+    w.mat_stride = (int64_t)N * round_up(N, 2);
+    w.split_tiles = (M + kGdMT) / kGdMT;
+    const size_t fixed_bytes = sizeof(double) * (size_t)w.mat_stride * n_keys + ((size_t)64 << 10) + sizeof(GainChild) * (size_t)nn +
                                sizeof(GainProdOp) * (size_t)nn + sizeof(GainGemmOp) * (size_t)nn + sizeof(SlotParamGain) * (size_t)n_keys +
                                sizeof(double) * ((size_t)R + 1 + (size_t)(M + 1) * c->n_dev) +
-                               (walk ? (sizeof(GainChild) + sizeof(GainWeightOp) + sizeof(GainGemmTOp) + sizeof(GainNodeOp) + sizeof(GainPredOp) + sizeof(GainSplitOp)) * (size_t)nn + sizeof(double) * ((size_t)R + 1) : 0);
+                               (walk ? (sizeof(GainChild) + sizeof(GainWeightOp) + sizeof(GainNodeOp)) * (size_t)nn + sizeof(double) * ((size_t)R + 1) : 0);
     const size_t column_bytes = sizeof(double) * (size_t)n_pan * N + sizeof(int64_t) + sizeof(double) +
-                                (walk ? sizeof(double) * ((size_t)n_down * N + (pred ? 5 * (size_t)T : 4 * (size_t)nn) + (want_posterior ? (size_t)nn * N : 0)) : 0) +
-                                (marg ? (sizeof(double) * 3 * (size_t)split_tiles + sizeof(int32_t) * 3) * (size_t)nn : 0) +     // the split's partials, the integers
+                                sizeof(double) * ((size_t)n_down * N + planes + (sink.posterior ? (size_t)nn * N : 0)) + sizeof(int32_t) * iplanes +
+                                (marg ? sizeof(double) * 3 * (size_t)w.split_tiles * nn : 0) +                     // the split's partials
                                 (scaled ? sizeof(int32_t) * (size_t)(n_pan + n_down) + sizeof(double) : 0);     // the exponents, log Z~
-    size_t budget = 0;
-    HIP_TRY(c, workspace_budget(c->workspace_limit, c->pf_dev_bytes, &budget));
     int64_t entries = budget > fixed_bytes ? (int64_t)((budget - fixed_bytes) / column_bytes) / kGdCols * kGdCols : 0;
-    entries = std::max<int64_t>(kGdCols, std::min<int64_t>(entries, round_up64(n, kGdCols)));
+    entries = std::max<int64_t>(kGdCols, std::min<int64_t>(entries, round_up64(q.n, kGdCols)));
     if (c->pf_max_batch > 0) entries = std::min(entries, c->pf_max_batch);
-    const int64_t ld = round_up64(entries, kGdCols);
-    const int64_t pan_stride = (int64_t)N * ld;
+    w.entries = entries;
+    w.ld = round_up64(entries, kGdCols);
+    w.pan_stride = (int64_t)N * w.ld;
+}
 
-    std::vector<GainChild> children;
-    std::vector<GainProdOp> prod_ops;
-    std::vector<GainGemmOp> gemm_ops;
-    std::vector<int> prod_off{0}, gemm_off{0}, prod_rows, gemm_rows;       // per level: its ops, its tallest op
-    for (int lv = 0; lv < n_levels; ++lv) {
-        int pr_rows = 0, gm_rows = 0;
-        for (int u = 0; u < nn; ++u) {
-            if (height[u] != lv) continue;
-            GainProdOp po{};
-            po.dst = bidx[u] * pan_stride;
-            po.rows = (u == c->root ? R : M) + 1;
-            po.child0 = (int32_t)children.size();
-            for (int ch : c->children[u]) {
-                const bool leaf = c->leaf_taxon[ch] >= 0;
-                children.push_back({leaf ? node_key[ch] * mat_stride : fidx[ch] * pan_stride, leaf ? c->leaf_taxon[ch] : -1, 0});
-            }
-            po.n_children = (int32_t)children.size() - po.child0;
-            po.carry = fidx[u];
-            prod_ops.push_back(po);
-            pr_rows = std::max(pr_rows, po.rows);
-            if (u == c->root) continue;
-            const int nr = (c->parent[u] == c->root ? R : M) + 1;
-            gemm_ops.push_back({node_key[u] * mat_stride, bidx[u] * pan_stride, fidx[u] * pan_stride, nr, 0});
-            gm_rows = std::max(gm_rows, nr);
-        }
-        prod_off.push_back((int)prod_ops.size()); gemm_off.push_back((int)gemm_ops.size());
-        prod_rows.push_back(pr_rows); gemm_rows.push_back(gm_rows);
-    }
-    // the down pass's tables, depth by depth: the weights of every node, the transposed GEMM and the outputs of the interior ones
-    // (depth 0: the root's outputs alone), the outputs of the leaves
-    std::vector<GainWeightOp> weight_ops;
-    std::vector<GainGemmTOp> gemmt_ops;
-    std::vector<GainNodeOp> int_ops, leaf_ops;
-    std::vector<GainPredOp> pred_ops;                  // (a leaf has an entry in both leaf tables: leaf_off serves both)
-    std::vector<GainSplitOp> split_ops;                // (beside gemmt_ops entry for entry: gemmt_off serves both)
-    std::vector<int> weight_off{0}, gemmt_off{0}, int_off{0}, leaf_off{0}, weight_rows;
-    for (int d = 0; d < n_depths; ++d) {
-        int w_rows = 0;
-        for (int k = depth_off[d]; k < depth_off[d + 1]; ++k) {
-            const int u = by_depth[k], p = c->parent[u];
-            if (u == c->root) {
-                int_ops.push_back({-1, bidx[u] * pan_stride, -1, 0, u, R + 1, 0, -1});
-                continue;
-            }
-            const int rows = (p == c->root ? R : M) + 1;
-            GainWeightOp wo{widx[u] * pan_stride, p == c->root ? -1 : oidx[p] * pan_stride, rows, (int32_t)children.size(), 0, oidx[u]};
-            for (int sib : c->children[p]) {
-                if (sib == u) continue;
-                const bool leaf = c->leaf_taxon[sib] >= 0;
-                children.push_back({leaf ? node_key[sib] * mat_stride : fidx[sib] * pan_stride, leaf ? c->leaf_taxon[sib] : -1, 0});
-            }
-            wo.n_children = (int32_t)children.size() - wo.child0;
-            weight_ops.push_back(wo);
-            w_rows = std::max(w_rows, rows);
-            if (c->leaf_taxon[u] >= 0) {
-                leaf_ops.push_back({-1, -1, widx[u] * pan_stride, node_key[u] * mat_stride, u, M + 1, rows, c->leaf_taxon[u]});
-                pred_ops.push_back({node_key[u] * mat_stride, widx[u] * pan_stride, rows, c->leaf_taxon[u]});
-                continue;
-            }
-            gemmt_ops.push_back({node_key[u] * mat_stride, widx[u] * pan_stride, oidx[u] * pan_stride, rows, 0});
-            split_ops.push_back({node_key[u] * mat_stride, widx[u] * pan_stride, oidx[u] * pan_stride, bidx[u] * pan_stride, rows, u});
-            int_ops.push_back({oidx[u] * pan_stride, bidx[u] * pan_stride, widx[u] * pan_stride, node_key[u] * mat_stride, u, M + 1, rows, -1});
-        }
-        weight_off.push_back((int)weight_ops.size()); gemmt_off.push_back((int)gemmt_ops.size());
-        int_off.push_back((int)int_ops.size()); leaf_off.push_back((int)leaf_ops.size());
-        weight_rows.push_back(w_rows);
-    }
-    std::vector<double> mass;                          // the root's outside vector, beside logmass
-    if (walk) {
-        mass.resize((size_t)R + 1);
-        mass[0] = root_absent;
-        for (int j = 1; j <= R; ++j) mass[j] = (1.0 - root_absent) * (double)pr->prior[j - 1];
-    }
+// The plan's tables in the blob and the offsets behind it
+void GainLayout::place(const cafe_ctx* c, const GainSink& sink, bool scaled, const GainPlan& plan) {
+    GainLayout& w = *this;
+    const int nn = c->n_nodes, N = c->N, n_keys = plan.n_keys(), n_pan = plan.n_pan, n_down = plan.n_down;
+    const bool marg = sink.mode == kGainMarginal;
+    const size_t planes = sink.dst.size() * (size_t)sink.rows, iplanes = sink.idst.size() * (size_t)sink.rows;
+    const int64_t ld = w.ld;
+    w.o_children = put(w.blob, plan.children); w.o_prod = put(w.blob, plan.prod_ops); w.o_gemm = put(w.blob, plan.gemm_ops);
+    w.o_slots = put(w.blob, plan.slots); w.o_reals = put(w.blob, plan.reals); w.o_weight = put(w.blob, plan.weight_ops);
+    w.o_int = put(w.blob, plan.int_ops); w.o_leaf = put(w.blob, plan.leaf_ops); w.o_mass = put(w.blob, plan.mass);
+    w.o_col = gain_region_up(w.blob.size());
+    w.o_out = w.o_col + family_align_up(sizeof(int64_t) * ld);
+    w.o_mats = gain_region_up(w.o_out + sizeof(double) * ld);
+    w.o_pan = gain_region_up(w.o_mats + sizeof(double) * (size_t)w.mat_stride * n_keys);
+    w.o_res = w.o_pan + sizeof(double) * (size_t)w.pan_stride * (n_pan + n_down);
+    w.o_post = w.o_res + sizeof(double) * planes * ld;
+    w.o_parts = w.o_post + (sink.posterior ? sizeof(double) * (size_t)nn * N * ld : 0);
+    w.o_ires = w.o_parts + (marg ? sizeof(double) * 3 * (size_t)w.split_tiles * nn * ld : 0);
+    w.o_exps = w.o_ires + (iplanes ? family_align_up(sizeof(int32_t) * iplanes * ld) : 0);
+    w.o_zt = w.o_exps + (scaled ? family_align_up(sizeof(int32_t) * (size_t)(n_pan + n_down) * ld) : 0);
+    w.need = w.o_zt + (scaled ? sizeof(double) * ld : 0);
+}
 
-    std::vector<double> reals((size_t)R + 1 + (size_t)(M + 1) * c->n_dev);  // log mass of the root sizes, error model
-    reals[0] = std::log(root_absent);
-    for (int j = 0; j < R; ++j) reals[j + 1] = std::log1p(-root_absent) + std::log((double)pr->prior[j]);    // compute() returns float
-    if (c->n_dev > 0) std::memcpy(reals.data() + R + 1, pr->error_model, sizeof(double) * (size_t)(M + 1) * c->n_dev);
-
-    std::vector<char> blob;
-    const size_t o_children = put(blob, children), o_prod = put(blob, prod_ops), o_gemm = put(blob, gemm_ops), o_slots = put(blob, slots),
-                 o_reals = put(blob, reals), o_weight = put(blob, weight_ops), o_gemmt = put(blob, gemmt_ops), o_int = put(blob, int_ops),
-                 o_leaf = put(blob, leaf_ops), o_pred = put(blob, pred_ops), o_split = put(blob, split_ops), o_mass = put(blob, mass);
-    const size_t o_col = family_align_up(blob.size()), o_out = o_col + family_align_up(sizeof(int64_t) * ld),
-                 o_mats = o_out + family_align_up(sizeof(double) * ld), o_pan = o_mats + family_align_up(sizeof(double) * (size_t)mat_stride * n_keys),
-                 o_res = o_pan + sizeof(double) * (size_t)pan_stride * (n_pan + n_down),
-                 o_post = o_res + sizeof(double) * (down || marg ? 4 * (size_t)nn : pred ? 5 * (size_t)T : 0) * ld,
-                 o_parts = o_post + (want_posterior ? sizeof(double) * (size_t)nn * N * ld : 0),
-                 o_ires = o_parts + (marg ? sizeof(double) * 3 * (size_t)split_tiles * nn * ld : 0),
-                 o_exps = o_ires + (marg ? family_align_up(sizeof(int32_t) * 3 * (size_t)nn * ld) : 0),
-                 o_zt = o_exps + (scaled ? family_align_up(sizeof(int32_t) * (size_t)(n_pan + n_down) * ld) : 0),
-                 need = o_zt + (scaled ? sizeof(double) * ld : 0);
-    if (need > c->pf_dev_bytes) {
-        if (c->pf_dev) { HIP_TRY(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->pf_dev); c->pf_dev = nullptr; c->pf_dev_bytes = 0; }
-        if (hipMalloc(&c->pf_dev, need) != hipSuccess) {
-            (void)hipGetLastError();
-            c->pf_dev = nullptr;
-            set_err(c, "%s: cannot allocate a workspace of %zu bytes (%d matrices of order %d, %lld columns per batch)", who, need, n_keys, N, (long long)ld);
-            return CAFE_ERR_MEMORY;
-        }
-        c->pf_dev_bytes = need;
+// The context's workspace, kept between calls, grown to the layout's need
+int gain_dense_workspace(cafe_ctx* c, const char* who, const GainLayout& w, int n_keys) {
+    if (w.need <= c->pf_dev_bytes) return CAFE_OK;
+    if (c->pf_dev) { HIP_TRY(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->pf_dev); c->pf_dev = nullptr; c->pf_dev_bytes = 0; }
+    if (hipMalloc(&c->pf_dev, w.need) != hipSuccess) {
+        (void)hipGetLastError();
+        c->pf_dev = nullptr;
+        set_err(c, "%s: cannot allocate a workspace of %zu bytes (%d matrices of order %d, %lld columns per batch)", who, w.need, n_keys, c->N, (long long)w.ld);
+        return CAFE_ERR_MEMORY;
     }
+    c->pf_dev_bytes = w.need;
+    return CAFE_OK;
+}
+
+// ---- the launches, batch by batch: the up pass level by level and the root kernel, then -- kGainScore apart -- by depth the
+// weights of every node, the transposed GEMM of the interior ones (the marginal mode: the SPLIT GEMM in its place) and what the
+// mode wants of the depth: the output kernels of every node (posterior), their summary kernels (marginal), or the fused kernel of
+// the leaves alone (predictive).  prof: the launches' ms by kind and the MFMA flops issued.
+int gain_dense_batches(cafe_ctx* c, const GainCall& q, const GainPlan& plan, const GainLayout& w, bool scaled, GainSink& sink, GainProfile& prof) {
+    const int nn = c->n_nodes, N = c->N, M = c->M, R = c->R, ldp = round_up(N, 2);
+    const int64_t ld = w.ld, n = q.n;
+    const GainMode mode = sink.mode;
     char* base = static_cast<char*>(c->pf_dev);
     hipStream_t s = c->stream;
-    HIP_TRY(c, hipMemcpyAsync(base, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(base, w.blob.data(), w.blob.size(), hipMemcpyHostToDevice, s));
     GainTimer timer;
     timer.on = c->profile != 0;
 
-    double* mats = reinterpret_cast<double*>(base + o_mats);
-    double* panels = reinterpret_cast<double*>(base + o_pan);
-    const double* d_reals = reinterpret_cast<const double*>(base + o_reals);
-    GainBuildArgs ba{reinterpret_cast<const SlotParamGain*>(base + o_slots), mats, N, ldp, mat_stride};
+    double* mats = reinterpret_cast<double*>(base + w.o_mats);
+    double* panels = reinterpret_cast<double*>(base + w.o_pan);
+    const double* d_reals = reinterpret_cast<const double*>(base + w.o_reals);
+    const GainNodeOp* int_ops = reinterpret_cast<const GainNodeOp*>(base + w.o_int);
+    const GainNodeOp* leaf_ops = reinterpret_cast<const GainNodeOp*>(base + w.o_leaf);
+    GainBuildArgs ba{reinterpret_cast<const SlotParamGain*>(base + w.o_slots), mats, N, ldp, w.mat_stride};
     timer.mark(kGdBuild, s);
-    HIP_TRY(c, launch_build(ba, n_keys, s));
+    HIP_TRY(c, launch_build(ba, plan.n_keys(), s));
     timer.mark(kGdBuild, s);
 
     GainProdArgs pa{};
-    pa.ops = reinterpret_cast<const GainProdOp*>(base + o_prod); pa.children = reinterpret_cast<const GainChild*>(base + o_children);
-    pa.panels = panels; pa.mats = mats; pa.col = reinterpret_cast<const int64_t*>(base + o_col);
+    pa.ops = reinterpret_cast<const GainProdOp*>(base + w.o_prod); pa.children = reinterpret_cast<const GainChild*>(base + w.o_children);
+    pa.panels = panels; pa.mats = mats; pa.col = reinterpret_cast<const int64_t*>(base + w.o_col);
     pa.counts = c->d_counts; pa.counts_ld = c->Fp; pa.ld = ld;
     pa.err = c->n_dev > 0 ? d_reals + R + 1 : nullptr;
     pa.n_dev = c->n_dev; pa.M = M; pa.ldp = ldp;
-    GainGemmArgs ga{reinterpret_cast<const GainGemmOp*>(base + o_gemm), mats, panels, ld, M + 1, ldp};
-    GainRootArgs ra{panels + bidx[c->root] * pan_stride, d_reals, reinterpret_cast<double*>(base + o_out), ld, R,
-                    walk || c->root_rule == CAFE_ROOT_SUM ? 1 : 0};
-    GainWeightArgs wa{pa, reinterpret_cast<const GainWeightOp*>(base + o_weight), reinterpret_cast<const double*>(base + o_mass)};
-    GainGemmTArgs ta{reinterpret_cast<const GainGemmTOp*>(base + o_gemmt), mats, panels, ld, M + 1, ldp};
+    GainGemmArgs ga{reinterpret_cast<const GainGemmOp*>(base + w.o_gemm), mats, panels, ld, M + 1, ldp};
+    GainRootArgs ra{panels + plan.bidx[c->root] * w.pan_stride, d_reals, reinterpret_cast<double*>(base + w.o_out), ld, R,
+                    mode != kGainScore || c->root_rule == CAFE_ROOT_SUM ? 1 : 0};      // every down pass forces the sum rule
+    GainWeightArgs wa{pa, reinterpret_cast<const GainWeightOp*>(base + w.o_weight), reinterpret_cast<const double*>(base + w.o_mass)};
+    GainGemmTArgs ta{int_ops, mats, panels, ld, M + 1, ldp};
     GainOutArgs oa{};
     oa.mats = mats; oa.panels = panels; oa.mass = wa.mass; oa.lnl = ra.out;
-    oa.res = reinterpret_cast<double*>(base + o_res); oa.posterior = want_posterior ? reinterpret_cast<double*>(base + o_post) : nullptr;
+    oa.res = reinterpret_cast<double*>(base + w.o_res); oa.posterior = sink.posterior ? reinterpret_cast<double*>(base + w.o_post) : nullptr;
     oa.col = pa.col; oa.counts = pa.counts; oa.err = pa.err; oa.counts_ld = pa.counts_ld; oa.ld = ld;
     oa.nn = nn; oa.N = N; oa.M = M; oa.ldp = ldp; oa.n_dev = c->n_dev; oa.any_missing = c->has_missing ? 1 : 0;
-    oa.root_B = bidx[c->root] * pan_stride;
-    GainPredArgs qa{reinterpret_cast<const GainPredOp*>(base + o_pred), mats, panels, oa.res, pa.col, pa.counts, pa.err, pa.counts_ld, ld, M + 1, ldp, c->n_dev, T};
-    const GainScaleArgs sa{reinterpret_cast<int32_t*>(base + o_exps), N};
-    const int32_t* root_exps = sa.exps + bidx[c->root] * ld;
-    double* zt = reinterpret_cast<double*>(base + o_zt);
+    oa.root_B = plan.bidx[c->root] * w.pan_stride;
+    GainPredArgs qa{leaf_ops, mats, panels, oa.res, pa.col, pa.counts, pa.err, pa.counts_ld, ld, M + 1, ldp, c->n_dev, c->n_taxa};
+    const GainScaleArgs sa{reinterpret_cast<int32_t*>(base + w.o_exps), N};
+    const int32_t* exps = sa.exps;
+    const int32_t* root_exps = exps + plan.bidx[c->root] * ld;
+    double* zt = reinterpret_cast<double*>(base + w.o_zt);
     if (scaled) oa.lnl = zt;                           // the outputs divide by Z~ = exp(log Z~)
-    if (down) {
-        down->res.resize(4 * (size_t)nn * entries);
-        if (want_posterior) down->posterior.resize((size_t)nn * N * entries);
-    }
-    if (pred) pred->res.resize(5 * (size_t)T * entries);
-    GainSplitArgs xa{reinterpret_cast<const GainSplitOp*>(base + o_split), mats, panels, reinterpret_cast<double*>(base + o_parts), ld, M + 1, ldp};
-    GainSummaryArgs ya{oa, xa.parts, reinterpret_cast<int32_t*>(base + o_ires), marg ? marg->level : 0.0, split_tiles};
-    if (marg) {
-        marg->res.resize(4 * (size_t)nn * entries);
-        marg->ires.resize(3 * (size_t)nn * entries);
-    }
+    GainSplitArgs xa{int_ops, mats, panels, reinterpret_cast<double*>(base + w.o_parts), ld, M + 1, ldp};
+    GainSummaryArgs ya{oa, xa.parts, reinterpret_cast<int32_t*>(base + w.o_ires), q.level, w.split_tiles};
+    sink.resize(w.entries, N);
 
+    const double k_rows = round_up(M + 1, kGdMT);      // the rows a down-pass MFMA kernel issues for a node
+    double flops = 0.0;
     std::vector<int64_t> col((size_t)ld);
     std::vector<double> res((size_t)ld);
-    for (int64_t b0 = 0; b0 < n; b0 += entries) {
-        const int64_t nb = std::min(entries, n - b0), cols = round_up64(nb, kGdCols);
-        for (int64_t b = 0; b < cols; ++b) col[b] = (b < nb && family[b0 + b] >= 0) ? c->ref_of[family[b0 + b]] : -1;    // (padding: the absent profile)
-        HIP_TRY(c, hipMemcpyAsync(base + o_col, col.data(), sizeof(int64_t) * cols, hipMemcpyHostToDevice, s));
-        const unsigned tiles = (unsigned)(cols / kGdCols);
-        for (int lv = 0; lv < n_levels; ++lv) {
-            const int np = prod_off[lv + 1] - prod_off[lv], ng = gemm_off[lv + 1] - gemm_off[lv];
+    for (int64_t b0 = 0; b0 < n; b0 += w.entries) {
+        const int64_t nb = std::min(w.entries, n - b0), cols = round_up64(nb, kGdCols);
+        for (int64_t b = 0; b < cols; ++b) col[b] = (b < nb && q.family[b0 + b] >= 0) ? c->ref_of[q.family[b0 + b]] : -1;    // (padding: the absent profile)
+        HIP_TRY(c, hipMemcpyAsync(base + w.o_col, col.data(), sizeof(int64_t) * cols, hipMemcpyHostToDevice, s));
+        const unsigned tiles = (unsigned)(cols / kGdCols), blocks64 = (unsigned)(cols / 64), blocks256 = (unsigned)((cols + 255) / 256);
+        for (int lv = 0; lv < plan.n_levels; ++lv) {
+            const int np = plan.prod_off[lv + 1] - plan.prod_off[lv], ng = plan.gemm_off[lv + 1] - plan.gemm_off[lv];
             GainProdArgs p = pa;
-            p.ops += prod_off[lv];
+            p.ops += plan.prod_off[lv];
             p.ncols = cols;
             timer.mark(kGdProduct, s);
-            if (scaled)
-                CAFE_LAUNCH(c, gain_scaled_product_kernel, dim3((unsigned)(cols / 64), (unsigned)np), dim3(256), 0, s, p, sa);
-            else
-                CAFE_LAUNCH(c, gain_dense_product_kernel, dim3((unsigned)((cols + 255) / 256), (unsigned)((prod_rows[lv] + kGdProdRows - 1) / kGdProdRows), (unsigned)np),
-                            dim3(256), 0, s, p);
+            GAIN_LAUNCH_EITHER(c, (scaled, gain_dense_product_kernel, dim3(blocks256, (unsigned)((plan.prod_rows[lv] + kGdProdRows - 1) / kGdProdRows), (unsigned)np),
+                                     gain_scaled_product_kernel, dim3(blocks64, (unsigned)np), s, p, sa));
             timer.mark(kGdProduct, s);
             if (ng == 0) continue;
             GainGemmArgs g = ga;
-            g.ops += gemm_off[lv];
+            g.ops += plan.gemm_off[lv];
             timer.mark(kGdGemm, s);
-            CAFE_LAUNCH(c, gain_dense_gemm_kernel, dim3(tiles, (unsigned)((gemm_rows[lv] + kGdMT - 1) / kGdMT), (unsigned)ng), dim3(256), 0, s, g);
+            CAFE_LAUNCH(c, gain_dense_gemm_kernel, dim3(tiles, (unsigned)((plan.gemm_rows[lv] + kGdMT - 1) / kGdMT), (unsigned)ng), dim3(256), 0, s, g);
             timer.mark(kGdGemm, s);
-            for (int k = gemm_off[lv]; k < gemm_off[lv + 1]; ++k)
-                flops += 2.0 * round_up(gemm_ops[k].nr, kGdMT) * (double)round_up(M + 1, kGdKT) * (double)cols;
+            for (int k = plan.gemm_off[lv]; k < plan.gemm_off[lv + 1]; ++k)
+                flops += 2.0 * round_up(plan.gemm_ops[k].nr, kGdMT) * (double)round_up(M + 1, kGdKT) * (double)cols;
         }
         timer.mark(kGdRoot, s);
-        if (scaled)
-            CAFE_LAUNCH(c, gain_scaled_root_kernel, dim3((unsigned)(cols / 64)), dim3(256), 0, s, ra, root_exps, zt);
-        else
-            CAFE_LAUNCH(c, gain_dense_root_kernel, dim3((unsigned)(cols / 64)), dim3(256), 0, s, ra);
+        GAIN_LAUNCH_EITHER(c, (scaled, gain_dense_root_kernel, dim3(blocks64), gain_scaled_root_kernel, dim3(blocks64), s, ra, root_exps, zt));
         timer.mark(kGdRoot, s);
-        HIP_TRY(c, hipMemcpyAsync(res.data(), base + o_out, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
-        for (int d = 0; d < n_depths; ++d) {           // the down pass: every B and F panel of the batch is still in place
-            const int nw = weight_off[d + 1] - weight_off[d], nt = gemmt_off[d + 1] - gemmt_off[d], ni = int_off[d + 1] - int_off[d],
-                      nl = leaf_off[d + 1] - leaf_off[d];
+        HIP_TRY(c, hipMemcpyAsync(res.data(), base + w.o_out, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
+        for (int d = 0; d < plan.n_depths; ++d) {      // the down pass: every B and F panel of the batch is still in place
+            const int nw = plan.weight_off[d + 1] - plan.weight_off[d], ni = plan.int_off[d + 1] - plan.int_off[d],
+                      nl = plan.leaf_off[d + 1] - plan.leaf_off[d], nt = d > 0 ? ni : 0;      // (depth 0 is the root: outputs, no GEMM)
+            const GainNodeOp* const h_int = plan.int_ops.data() + plan.int_off[d];
+            const GainNodeOp* const h_leaf = plan.leaf_ops.data() + plan.leaf_off[d];
             if (nw > 0) {
-                GainWeightArgs w = wa;
-                w.ops += weight_off[d];
-                w.p.ncols = cols;
+                GainWeightArgs wt = wa;
+                wt.ops += plan.weight_off[d];
+                wt.p.ncols = cols;
                 timer.mark(kGdWeights, s);
-                if (scaled)
-                    CAFE_LAUNCH(c, gain_scaled_weights_kernel, dim3((unsigned)(cols / 64), (unsigned)nw), dim3(256), 0, s, w, sa);
-                else
-                    CAFE_LAUNCH(c, gain_posterior_dense_weights_kernel,
-                                dim3((unsigned)((cols + 255) / 256), (unsigned)((weight_rows[d] + kGdProdRows - 1) / kGdProdRows), (unsigned)nw), dim3(256), 0, s, w);
+                GAIN_LAUNCH_EITHER(c, (scaled, gain_posterior_dense_weights_kernel,
+                                         dim3(blocks256, (unsigned)((plan.weight_rows[d] + kGdProdRows - 1) / kGdProdRows), (unsigned)nw),
+                                         gain_scaled_weights_kernel, dim3(blocks64, (unsigned)nw), s, wt, sa));
                 timer.mark(kGdWeights, s);
             }
-            if (nt > 0 && marg) {                      // the split GEMM: the outside panels and the three sums of every branch
+            if (nt > 0 && mode == kGainMarginal) {     // the split GEMM: the outside panels and the three sums of every branch
                 GainSplitArgs x = xa;
-                x.ops += gemmt_off[d];
+                x.ops += plan.int_off[d];
                 timer.mark(kGdGemmT, s);
-                CAFE_LAUNCH(c, gain_marginal_dense_split_kernel, dim3(tiles, (unsigned)split_tiles, (unsigned)nt), dim3(256), 0, s, x);
+                CAFE_LAUNCH(c, gain_marginal_dense_split_kernel, dim3(tiles, (unsigned)w.split_tiles, (unsigned)nt), dim3(256), 0, s, x);
                 timer.mark(kGdGemmT, s);
-                for (int k = gemmt_off[d]; k < gemmt_off[d + 1]; ++k)
+                for (int k = 0; k < nt; ++k)
                     for (int r0 = 0; r0 <= M; r0 += kGdMT) {               // the K tiles both phases issue, the masked repeats among them
-                        const int k_end = round_up(split_ops[k].nk, kGdKT);
-                        flops += 2.0 * kGdMT * (double)(gain_marginal_phase1_end(r0, split_ops[k].nk) + std::max(0, k_end - r0)) * (double)cols;
+                        const int k_end = round_up(h_int[k].rows, kGdKT);
+                        flops += 2.0 * kGdMT * (double)(gain_marginal_phase1_end(r0, h_int[k].rows) + std::max(0, k_end - r0)) * (double)cols;
                     }
             } else if (nt > 0) {
                 GainGemmTArgs t = ta;
-                t.ops += gemmt_off[d];
+                t.ops += plan.int_off[d];
                 timer.mark(kGdGemmT, s);
                 CAFE_LAUNCH(c, gain_posterior_dense_gemm_t_kernel, dim3(tiles, (unsigned)((M + kGdMT) / kGdMT), (unsigned)nt), dim3(256), 0, s, t);
                 timer.mark(kGdGemmT, s);
-                for (int k = gemmt_off[d]; k < gemmt_off[d + 1]; ++k)
-                    flops += 2.0 * round_up(M + 1, kGdMT) * (double)round_up(gemmt_ops[k].nk, kGdKT) * (double)cols;
+                for (int k = 0; k < nt; ++k) flops += 2.0 * k_rows * (double)round_up(h_int[k].rows, kGdKT) * (double)cols;
             }
-            if (pred) {                                // the leaves' six sums straight from the MFMA accumulators; no other output
+            if (mode == kGainPredictive) {             // the leaves' six sums straight from the MFMA accumulators; no other output
                 if (nl == 0) continue;
-                GainPredArgs q = qa;
-                q.ops += leaf_off[d];
+                GainPredArgs pq = qa;
+                pq.ops += plan.leaf_off[d];
                 timer.mark(kGdPredict, s);
-                CAFE_LAUNCH(c, gain_predictive_dense_leaf_kernel, dim3(tiles, (unsigned)nl), dim3(256), 0, s, q);
+                CAFE_LAUNCH(c, gain_predictive_dense_leaf_kernel, dim3(tiles, (unsigned)nl), dim3(256), 0, s, pq);
                 timer.mark(kGdPredict, s);
-                for (int k = leaf_off[d]; k < leaf_off[d + 1]; ++k)
-                    flops += 2.0 * round_up(M + 1, kGdMT) * (double)round_up(pred_ops[k].nk, kGdKT) * (double)cols;
+                for (int k = 0; k < nl; ++k) flops += 2.0 * k_rows * (double)round_up(h_leaf[k].rows, kGdKT) * (double)cols;
                 continue;
             }
-            if (marg) {                                // the summaries: nothing of a posterior is stored
-                GainSummaryArgs y = ya;
-                if (ni > 0) {
-                    y.o.ops = reinterpret_cast<const GainNodeOp*>(base + o_int) + int_off[d];
-                    timer.mark(kGdInterior, s);
-                    if (scaled)
-                        CAFE_LAUNCH(c, gain_marginal_scaled_interior_kernel, dim3((unsigned)(cols / 64), (unsigned)ni), dim3(256), 0, s, y, (const int32_t*)sa.exps);
-                    else
-                        CAFE_LAUNCH(c, gain_marginal_dense_interior_kernel, dim3((unsigned)(cols / 64), (unsigned)ni), dim3(256), 0, s, y);
-                    timer.mark(kGdInterior, s);
-                }
-                if (nl > 0) {
-                    y.o.ops = reinterpret_cast<const GainNodeOp*>(base + o_leaf) + leaf_off[d];
-                    timer.mark(kGdLeaf, s);
-                    if (scaled)
-                        CAFE_LAUNCH(c, gain_marginal_scaled_leaf_kernel, dim3((unsigned)(cols / 64), (unsigned)nl), dim3(256), 0, s, y, (const int32_t*)sa.exps);
-                    else
-                        CAFE_LAUNCH(c, gain_marginal_dense_leaf_kernel, dim3((unsigned)(cols / 64), (unsigned)nl), dim3(256), 0, s, y);
-                    timer.mark(kGdLeaf, s);
-                }
-                continue;
-            }
-            GainOutArgs o = oa;
+            // the outputs of every node of the depth; the marginal mode's summaries store nothing of a posterior
+            GainSummaryArgs y = ya;
+            GainOutArgs& o = y.o;
             if (ni > 0) {
-                o.ops = reinterpret_cast<const GainNodeOp*>(base + o_int) + int_off[d];
+                o.ops = int_ops + plan.int_off[d];
                 timer.mark(kGdInterior, s);
-                if (scaled)
-                    CAFE_LAUNCH(c, gain_scaled_interior_kernel, dim3((unsigned)(cols / 64), (unsigned)ni), dim3(256), 0, s, o, (const int32_t*)sa.exps);
+                if (mode == kGainMarginal)
+                    GAIN_LAUNCH_EITHER(c, (scaled, gain_marginal_dense_interior_kernel, dim3(blocks64, (unsigned)ni), gain_marginal_scaled_interior_kernel,
+                                             dim3(blocks64, (unsigned)ni), s, y, exps));
                 else
-                    CAFE_LAUNCH(c, gain_posterior_dense_interior_kernel, dim3((unsigned)(cols / 64), (unsigned)ni), dim3(256), 0, s, o);
+                    GAIN_LAUNCH_EITHER(c, (scaled, gain_posterior_dense_interior_kernel, dim3(blocks64, (unsigned)ni), gain_scaled_interior_kernel,
+                                             dim3(blocks64, (unsigned)ni), s, o, exps));
                 timer.mark(kGdInterior, s);
             }
             if (nl > 0) {
-                o.ops = reinterpret_cast<const GainNodeOp*>(base + o_leaf) + leaf_off[d];
+                o.ops = leaf_ops + plan.leaf_off[d];
                 timer.mark(kGdLeaf, s);
-                if (scaled)
-                    CAFE_LAUNCH(c, gain_scaled_leaf_kernel, dim3((unsigned)(cols / 64), (unsigned)nl), dim3(256), 0, s, o, (const int32_t*)sa.exps);
+                if (mode == kGainMarginal)
+                    GAIN_LAUNCH_EITHER(c, (scaled, gain_marginal_dense_leaf_kernel, dim3(blocks64, (unsigned)nl), gain_marginal_scaled_leaf_kernel,
+                                             dim3(blocks64, (unsigned)nl), s, y, exps));
                 else
-                    CAFE_LAUNCH(c, gain_posterior_dense_leaf_kernel, dim3((unsigned)(cols / 64), (unsigned)nl), dim3(256), 0, s, o);
+                    GAIN_LAUNCH_EITHER(c, (scaled, gain_posterior_dense_leaf_kernel, dim3(blocks64, (unsigned)nl), gain_scaled_leaf_kernel,
+                                             dim3(blocks64, (unsigned)nl), s, o, exps));
                 timer.mark(kGdLeaf, s);
             }
         }
-        if (down) {                                    // [rows][ld] on the device, [rows][nb] on the host
-            HIP_TRY(c, hipMemcpy2DAsync(down->res.data(), sizeof(double) * nb, oa.res, sizeof(double) * ld, sizeof(double) * nb, 4 * (size_t)nn,
-                                        hipMemcpyDeviceToHost, s));
-            if (want_posterior)
-                HIP_TRY(c, hipMemcpy2DAsync(down->posterior.data(), sizeof(double) * nb, oa.posterior, sizeof(double) * ld, sizeof(double) * nb, (size_t)nn * N,
-                                            hipMemcpyDeviceToHost, s));
-        }
-        if (pred)
-            HIP_TRY(c, hipMemcpy2DAsync(pred->res.data(), sizeof(double) * nb, oa.res, sizeof(double) * ld, sizeof(double) * nb, 5 * (size_t)T,
-                                        hipMemcpyDeviceToHost, s));
-        if (marg) {
-            HIP_TRY(c, hipMemcpy2DAsync(marg->res.data(), sizeof(double) * nb, oa.res, sizeof(double) * ld, sizeof(double) * nb, 4 * (size_t)nn,
-                                        hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipMemcpy2DAsync(marg->ires.data(), sizeof(int32_t) * nb, ya.ires, sizeof(int32_t) * ld, sizeof(int32_t) * nb, 3 * (size_t)nn,
-                                        hipMemcpyDeviceToHost, s));
-        }
+        HIP_TRY(c, sink.copy_back(oa.res, ya.ires, oa.posterior, ld, nb, N, s));
         HIP_TRY(c, hipStreamSynchronize(s));            // the host tables of this batch go out of use
-        std::copy(res.begin(), res.begin() + nb, family_lnl + b0);
-        if (down) down->collect(b0, nb, nn, N, res.data());
-        if (pred) pred->collect(b0, nb, T, res.data());
-        if (marg) marg->collect(b0, nb, nn, res.data());
+        std::copy(res.begin(), res.begin() + nb, sink.lnl + b0);
+        sink.collect(b0, nb, N, res.data());
     }
-    timer.collect(ms);
-    if (pred) {
-        ms[6] = ms[kGdPredict];                        // build, product, GEMM, root, weights, transposed GEMM, fused leaf
-        std::copy(ms, ms + 7, c->gain_predictive_ms);
-        c->gain_predictive_flops = flops;
-        return CAFE_OK;
-    }
-    if (marg) {                                        // the posterior entry's eight, the split GEMM sixth; then their total
-        ms[8] = 0.0;
-        for (int k = 0; k < 8; ++k) ms[8] += ms[k];
-        std::copy(ms, ms + 9, c->gain_marginal_ms);
-        c->gain_marginal_flops = flops;
-        return CAFE_OK;
-    }
-    std::copy(ms, ms + (down ? 8 : 4), down ? c->gain_dense_posterior_ms : c->gain_dense_ms);
-    (down ? c->gain_dense_posterior_flops : c->gain_dense_flops) = flops;
+    timer.collect(prof.ms);
+    prof.flops = flops;
+    return CAFE_OK;
+}
+
+// All four entries behind their shells.  The mode's record is zeroed on entry, ahead of the host-decided answers, and written
+// when the call has run to its end; the other modes' records are not touched.
+int gain_dense_run(cafe_ctx* c, const char* who, const GainCall& q, GainSink& sink) {
+    if (const int rc = gain_dense_check(c, who, q, sink.lnl)) return rc;
+    if (q.n == 0) return CAFE_OK;
+    const bool scaled = c->gain_scaling != 0;          // cafe_set_gain_scaling: the scaled twins of every kernel but the build and the GEMMs
+    c->last.state = LastCall::kNone;                   // cafe_family_results is not meaningful after this call
+    c->gain_profile[sink.mode] = GainProfile{};
+    if (gain_dense_host_answer(c, q, sink.lnl)) return CAFE_OK;
+    GainPlan plan;
+    if (const int rc = plan.index(c, who, q, sink.mode != kGainScore)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    size_t budget = 0;
+    HIP_TRY(c, workspace_budget(c->workspace_limit, c->pf_dev_bytes, &budget));
+    GainLayout layout;
+    layout.batch(c, q, sink, scaled, plan, budget);
+    plan.tables(c, q, sink.mode != kGainScore, layout.mat_stride, layout.pan_stride);
+    layout.place(c, sink, scaled, plan);
+    if (const int rc = gain_dense_workspace(c, who, layout, plan.n_keys())) return rc;
+    GainProfile prof;
+    if (const int rc = gain_dense_batches(c, q, plan, layout, scaled, sink, prof)) return rc;
+    c->gain_profile[sink.mode] = prof;
+    return CAFE_OK;
+}
+
+// The shell of the four entries.  prepare(sink): the entry's own argument check, the fill of its outputs with what no finite lnl
+// replaces, and the sink's planes.  An entry whose lnl is one output among others may leave it out: a stand-in takes it.
+template <class Prepare>
+int gain_dense_entry(cafe_ctx* ctx, const char* who, GainMode mode, const GainCall& q, Prepare prepare) {
+    auto body = [&] {
+        GainSink sink;
+        sink.mode = mode;
+        if (const int rc = prepare(sink)) return rc;
+        std::vector<double> own_lnl;
+        if (!sink.lnl && q.n > 0 && mode != kGainScore) { own_lnl.resize((size_t)q.n); sink.lnl = own_lnl.data(); }
+        return gain_dense_run(ctx, who, q, sink);
+    };
+    // the marginal mode's leaf summary has no instantiation for a missing cell
+    const int rc = mode == kGainMarginal ? guarded_observed(ctx, who, body) : guarded(ctx, who, body);
+    if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
+    return rc;
+}
+
+// A mode's record as its debug entry publishes it: the first `kinds` kinds
+int gain_profile_read(cafe_ctx* ctx, GainMode mode, int kinds, double* ms, double* flops) {
+    if (!ctx) return CAFE_ERR_ARGUMENT;
+    for (int k = 0; ms && k < kinds; ++k) ms[k] = ctx->gain_profile[mode].ms[k];
+    if (flops) *flops = ctx->gain_profile[mode].flops;
     return CAFE_OK;
 }
 
@@ -1405,10 +1420,10 @@ int gain_dense_impl(cafe_ctx* c, const char* who, const cafe_params* pr, const d
 
 int cafe_score_gain(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus, double root_absent, int64_t n,
                     const int64_t* family, double* family_lnl) {
-    const int rc = cafe::guarded(ctx, "cafe_score_gain",
-                                 [&] { return cafe::gain_dense_impl(ctx, "cafe_score_gain", params, lambdas, mus, nus, root_absent, n, family, family_lnl, nullptr); });
-    if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
-    return rc;
+    return cafe::gain_dense_entry(ctx, "cafe_score_gain", cafe::kGainScore, {params, lambdas, mus, nus, root_absent, n, family}, [&](cafe::GainSink& sink) {
+        sink.lnl = family_lnl;
+        return (int)CAFE_OK;
+    });
 }
 
 int cafe_set_gain_scaling(cafe_ctx* ctx, int on) {
@@ -1417,95 +1432,79 @@ int cafe_set_gain_scaling(cafe_ctx* ctx, int on) {
     return CAFE_OK;
 }
 
-int cafe_debug_gain_dense(cafe_ctx* ctx, double ms[4], double* flops) {
-    if (!ctx) return CAFE_ERR_ARGUMENT;
-    for (int k = 0; ms && k < 4; ++k) ms[k] = ctx->gain_dense_ms[k];
-    if (flops) *flops = ctx->gain_dense_flops;
-    return CAFE_OK;
-}
+int cafe_debug_gain_dense(cafe_ctx* ctx, double ms[4], double* flops) { return cafe::gain_profile_read(ctx, cafe::kGainScore, 4, ms, flops); }
 
 int cafe_gain_posterior_dense(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus, double root_absent,
                               int64_t n, const int64_t* family, const cafe_gain_posterior_out* out) {
     const char* const who = "cafe_gain_posterior_dense";
-    const int rc = cafe::guarded(ctx, who, [&] {
+    return cafe::gain_dense_entry(ctx, who, cafe::kGainPosterior, {params, lambdas, mus, nus, root_absent, n, family}, [&](cafe::GainSink& sink) {
         if (!out || (n > 0 && (!out->p_absent || !out->mean || !out->p_gain || !out->p_loss))) {
             cafe::set_err(ctx, "%s: out with p_absent, mean, p_gain and p_loss is required", who);
             return (int)CAFE_ERR_ARGUMENT;
         }
-        std::vector<double> own_lnl;
-        double* lnl = out->lnl;
-        if (!lnl && n > 0) { own_lnl.resize((size_t)n); lnl = own_lnl.data(); }
-        if (n > 0) {                                   // what no finite lnl replaces
+        sink.lnl = out->lnl;
+        sink.dst = {out->p_absent, out->mean, out->p_gain, out->p_loss};
+        sink.rows = ctx->n_nodes;
+        sink.posterior = out->posterior;
+        if (n > 0) {
             const size_t nodes = (size_t)n * ctx->n_nodes;
-            const double nan = std::numeric_limits<double>::quiet_NaN();
-            for (double* p : {out->p_absent, out->mean, out->p_gain, out->p_loss}) std::fill(p, p + nodes, nan);
-            if (out->posterior) std::fill(out->posterior, out->posterior + nodes * ctx->N, nan);
+            for (double* p : sink.dst) std::fill(p, p + nodes, std::numeric_limits<double>::quiet_NaN());
+            if (out->posterior) std::fill(out->posterior, out->posterior + nodes * ctx->N, std::numeric_limits<double>::quiet_NaN());
         }
-        cafe::GainDownHost down{out, {}, {}};
-        return cafe::gain_dense_impl(ctx, who, params, lambdas, mus, nus, root_absent, n, family, lnl, &down);
+        return (int)CAFE_OK;
     });
-    if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
-    return rc;
 }
 
-int cafe_debug_gain_dense_posterior(cafe_ctx* ctx, double ms[8], double* flops) {
-    if (!ctx) return CAFE_ERR_ARGUMENT;
-    for (int k = 0; ms && k < 8; ++k) ms[k] = ctx->gain_dense_posterior_ms[k];
-    if (flops) *flops = ctx->gain_dense_posterior_flops;
-    return CAFE_OK;
-}
+int cafe_debug_gain_dense_posterior(cafe_ctx* ctx, double ms[8], double* flops) { return cafe::gain_profile_read(ctx, cafe::kGainPosterior, 8, ms, flops); }
 
 int cafe_gain_leaf_predictive(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus, double root_absent,
                               int64_t n, const int64_t* family, const cafe_gain_leaf_predictive_out* out) {
     const char* const who = "cafe_gain_leaf_predictive";
-    const int rc = cafe::guarded(ctx, who, [&] {
+    return cafe::gain_dense_entry(ctx, who, cafe::kGainPredictive, {params, lambdas, mus, nus, root_absent, n, family}, [&](cafe::GainSink& sink) {
         if (!out) { cafe::set_err(ctx, "%s: out is required", who); return (int)CAFE_ERR_ARGUMENT; }
-        std::vector<double> own_lnl;
-        double* lnl = out->lnl;
-        if (!lnl && n > 0) { own_lnl.resize((size_t)n); lnl = own_lnl.data(); }
-        for (double* p : {out->mean, out->sd, out->p_below, out->p_obs, out->p_above})      // what no finite lnl replaces
+        sink.lnl = out->lnl;
+        sink.dst = {out->mean, out->sd, out->p_below, out->p_obs, out->p_above};
+        sink.rows = ctx->n_taxa;
+        for (double* p : sink.dst)
             if (p && n > 0) std::fill(p, p + (size_t)n * ctx->n_taxa, std::numeric_limits<double>::quiet_NaN());
-        cafe::GainPredictHost pred{out, {}};
-        return cafe::gain_dense_impl(ctx, who, params, lambdas, mus, nus, root_absent, n, family, lnl, nullptr, &pred);
+        return (int)CAFE_OK;
     });
-    if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
-    return rc;
 }
 
+// build, product, GEMM, root, weights, transposed GEMM, and the fused leaf kernel in the seventh slot
 int cafe_debug_gain_predictive(cafe_ctx* ctx, double ms[7], double* flops) {
-    if (!ctx) return CAFE_ERR_ARGUMENT;
-    for (int k = 0; ms && k < 7; ++k) ms[k] = ctx->gain_predictive_ms[k];
-    if (flops) *flops = ctx->gain_predictive_flops;
-    return CAFE_OK;
+    const int rc = cafe::gain_profile_read(ctx, cafe::kGainPredictive, 6, ms, flops);
+    if (rc == CAFE_OK && ms) ms[6] = ctx->gain_profile[cafe::kGainPredictive].ms[cafe::kGdPredict];
+    return rc;
 }
 
 int cafe_gain_marginal_dense(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus, double root_absent,
                              double level, int64_t n, const int64_t* family, const cafe_gain_marginal_out* out) {
     const char* const who = "cafe_gain_marginal_dense";
-    const int rc = cafe::guarded_observed(ctx, who, [&] {       // the leaf summary has no instantiation for a missing cell
+    return cafe::gain_dense_entry(ctx, who, cafe::kGainMarginal, {params, lambdas, mus, nus, root_absent, n, family, level}, [&](cafe::GainSink& sink) {
         if (!out || (n > 0 && (!out->mean || !out->mode || !out->lo || !out->hi || !out->p_increase || !out->p_decrease || !out->p_same))) {
             cafe::set_err(ctx, "%s: out with mean, mode, lo, hi, p_increase, p_decrease and p_same is required", who);
             return (int)CAFE_ERR_ARGUMENT;
         }
         if (!(level > 0.0 && level < 1.0)) { cafe::set_err(ctx, "%s: level must lie in (0, 1)", who); return (int)CAFE_ERR_ARGUMENT; }
-        std::vector<double> own_lnl;
-        double* lnl = out->lnl;
-        if (!lnl && n > 0) { own_lnl.resize((size_t)n); lnl = own_lnl.data(); }
-        if (n > 0) {                                   // what no finite lnl replaces
+        sink.lnl = out->lnl;
+        sink.dst = {out->mean, out->p_increase, out->p_decrease, out->p_same};
+        sink.idst = {out->mode, out->lo, out->hi};
+        sink.rows = ctx->n_nodes;
+        if (n > 0) {
             const size_t nodes = (size_t)n * ctx->n_nodes;
-            for (double* p : {out->mean, out->p_increase, out->p_decrease, out->p_same}) std::fill(p, p + nodes, std::numeric_limits<double>::quiet_NaN());
-            for (int32_t* p : {out->mode, out->lo, out->hi}) std::fill(p, p + nodes, -1);
+            for (double* p : sink.dst) std::fill(p, p + nodes, std::numeric_limits<double>::quiet_NaN());
+            for (int32_t* p : sink.idst) std::fill(p, p + nodes, -1);
         }
-        cafe::GainMarginalHost marg{out, level, {}, {}};
-        return cafe::gain_dense_impl(ctx, who, params, lambdas, mus, nus, root_absent, n, family, lnl, nullptr, nullptr, &marg);
+        return (int)CAFE_OK;
     });
-    if (rc == CAFE_ERR_DEVICE && ctx->device_ready && ctx->stream) (void)hipStreamSynchronize(ctx->stream);     // what the failed call left in flight
-    return rc;
 }
 
+// the posterior entry's eight, the split GEMM sixth; then their total
 int cafe_debug_gain_marginal(cafe_ctx* ctx, double ms[9], double* flops) {
-    if (!ctx) return CAFE_ERR_ARGUMENT;
-    for (int k = 0; ms && k < 9; ++k) ms[k] = ctx->gain_marginal_ms[k];
-    if (flops) *flops = ctx->gain_marginal_flops;
-    return CAFE_OK;
+    const int rc = cafe::gain_profile_read(ctx, cafe::kGainMarginal, 8, ms, flops);
+    if (rc != CAFE_OK || !ms) return rc;
+    ms[8] = 0.0;
+    for (int k = 0; k < 8; ++k) ms[8] += ms[k];
+    return rc;
 }

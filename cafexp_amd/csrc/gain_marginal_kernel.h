@@ -11,7 +11,7 @@
 //
 //   split     gain_marginal_dense_split_kernel, in place of the transposed GEMM: grid (column tiles of 128, row tiles of 64
 //             sizes c, interior non-root nodes of the depth).  One accumulator set, two phases over the 64 x 128 x 16 tile, the
-//             two LDS buffer pairs, v_mfma_f64_16x16x4 and the XOR-swizzled transposing A staging of gain_dense_tile_t:
+//             two LDS buffer pairs, v_mfma_f64_16x16x4 and the XOR-swizzled transposing A staging of gain_dense_tile:
 //               phase 1  s in [0, min(nk, r0 + 64)) with s < c: the K tiles below r0 whole, the four K tiles r0 .. r0 + 63 with
 //                        the A element zeroed where s >= c -- the comparison is made once, on the staging registers ra[], as
 //                        the tile is loaded, never in the MFMA loop.  Epilogue: inc[col] = sum_c B[c] acc[c], and the tile is
@@ -35,93 +35,14 @@
 // ldexp by the exponents of w, B and the root, as gain_posterior_dense_interior does.
 #pragma once
 
-struct GainSplitOp {
-    int64_t Pt, W, O, B;             // matrix (doubles from `mats`), w, outside and B panels (doubles from `panels`)
-    int32_t nk;                      // contraction over s = 0..nk-1: the parent's sizes
-    int32_t node;                    // its partials stand at parts + node * tiles * 3 * ld
-};
 struct GainSplitArgs {
-    const GainSplitOp* ops;
+    const GainNodeOp* ops;           // the depth's interior nodes: the contraction is op.rows, the partials stand at parts + op.node * tiles * 3 * ld
     const double* mats;
     double* panels;
     double* parts;                   // [n_nodes][row tiles][3][ld]: increase, decrease, same
     int64_t ld;
     int32_t nr, ldp;                 // rows c = 0..nr-1 of the outside panel
 };
-
-// The K loop of gain_dense_tile_t over the K tiles [kb, ke) (multiples of 16) with one side of the diagonal kept: Side = +1
-// keeps s < c, Side = -1 keeps s > c, inside the straddling tiles r0 <= k0 < r0 + 64 only -- every other tile of the range lies
-// wholly on the kept side and is staged as it is.  Ends behind a barrier; with an empty range acc is zero.
-template <int Side>
-__device__ __forceinline__ void gain_marginal_tile_side(double (*As)[kGdKT * kGdLdA], double (*Xs)[kGdKT * kGdLdX], const double* __restrict__ mat,
-                                                        const double* __restrict__ X, int r0, int nr, int kb, int ke, int nk, int ldp, int64_t ld,
-                                                        int64_t c0, gd4 (&acc)[4][2]) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l15 = lane & 15, l4 = lane >> 4;
-    const int arow = tid >> 2, aq = tid & 3;           // A staging: row of the tile, quad of k
-    const int c = r0 + arow;                           // the staged row's size
-    const double* __restrict__ Pt = mat + (int64_t)c * ldp;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (gd4){0.0, 0.0, 0.0, 0.0};
-    if (kb >= ke) return;                              // (block-uniform)
-    double2 ra[2], rx[4];
-    auto load = [&](int k0) {
-        const bool straddle = k0 >= r0 && k0 < r0 + kGdMT;                  // (block-uniform)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int k = k0 + 4 * aq + 2 * h;                              // (even: k < nk <= ldp keeps k + 1 inside the row)
-            double2 v = make_double2(0.0, 0.0);
-            if (c < nr && k < nk) {
-                v = *reinterpret_cast<const double2*>(Pt + k);
-                if (k + 1 >= nk) v.y = 0.0;
-                if (straddle) {                                             // the split: on the staging registers, once
-                    if (Side > 0 ? !(k < c) : !(k > c)) v.x = 0.0;
-                    if (Side > 0 ? !(k + 1 < c) : !(k + 1 > c)) v.y = 0.0;
-                }
-            }
-            ra[h] = v;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = k0 + wave + 4 * u;
-            rx[u] = k < nk ? *reinterpret_cast<const double2*>(X + (int64_t)k * ld + c0 + 2 * lane) : make_double2(0.0, 0.0);
-        }
-    };
-    auto stage = [&](int buf) {
-        const int col = arow ^ (aq << 3);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            As[buf][(4 * aq + 2 * h) * kGdLdA + col] = ra[h].x;
-            As[buf][(4 * aq + 2 * h + 1) * kGdLdA + col] = ra[h].y;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) *reinterpret_cast<double2*>(&Xs[buf][(wave + 4 * u) * kGdLdX + 2 * lane]) = rx[u];
-    };
-    load(kb);
-    stage(0);
-    __syncthreads();
-    int buf = 0;
-    for (int k0 = kb; k0 < ke; k0 += kGdKT, buf ^= 1) {
-        const bool more = k0 + kGdKT < ke;
-        if (more) load(k0 + kGdKT);
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            double af[4], bf[2];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = As[buf][(4 * s4 + l4) * kGdLdA + ((16 * i + l15) ^ (s4 << 3))];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bf[j] = Xs[buf][(4 * s4 + l4) * kGdLdX + 32 * wave + 16 * j + l15];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[j], acc[i][j], 0, 0, 0);
-        }
-        if (more) stage(buf ^ 1);                      // the other pair: its readers passed the barrier of the step before
-        __syncthreads();
-    }
-}
 
 // where phase 1 of row tile r0 ends: behind its straddling K tiles, or with the contraction (the host counts the flops by it)
 __host__ __device__ inline int gain_marginal_phase1_end(int r0, int nk) {
@@ -133,19 +54,19 @@ __host__ __device__ inline int gain_marginal_phase1_end(int r0, int nk) {
 __global__ __launch_bounds__(256) void gain_marginal_dense_split_kernel(const GainSplitArgs a) {
     __shared__ __attribute__((aligned(16))) double As[2][kGdKT * kGdLdA];
     __shared__ __attribute__((aligned(16))) double Xs[2][kGdKT * kGdLdX];
-    const GainSplitOp op = a.ops[blockIdx.z];
+    const GainNodeOp op = a.ops[blockIdx.z];
     const int r0 = blockIdx.y * kGdMT, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int l15 = lane & 15, l4 = lane >> 4, nr = a.nr, nk = op.nk;
+    const int l15 = lane & 15, l4 = lane >> 4, nr = a.nr, nk = op.rows;
     const int64_t c0 = (int64_t)blockIdx.x * kGdCols, ld = a.ld;
     const int k_end = (nk + kGdKT - 1) / kGdKT * kGdKT;
     const double* __restrict__ mat = a.mats + op.Pt;
     const double* __restrict__ W = a.panels + op.W + c0 + 32 * wave + l15;
     const double* __restrict__ B = a.panels + op.B + c0 + 32 * wave + l15;
-    double* __restrict__ O = a.panels + op.O + c0 + 32 * wave + l15;
+    double* __restrict__ O = a.panels + op.outside + c0 + 32 * wave + l15;
     gd4 acc[4][2];
     double inc[2] = {0.0, 0.0}, dec[2] = {0.0, 0.0}, same[2] = {0.0, 0.0};
 
-    gain_marginal_tile_side<+1>(As, Xs, mat, a.panels + op.W, r0, nr, 0, gain_marginal_phase1_end(r0, nk), nk, a.ldp, ld, c0, acc);
+    gain_dense_tile<kGdAStored, +1>(As, Xs, mat, a.panels + op.W, r0, nr, 0, gain_marginal_phase1_end(r0, nk), nk, a.ldp, ld, c0, acc);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -159,7 +80,7 @@ __global__ __launch_bounds__(256) void gain_marginal_dense_split_kernel(const Ga
             }
         }
 
-    gain_marginal_tile_side<-1>(As, Xs, mat, a.panels + op.W, r0, nr, r0, k_end, nk, a.ldp, ld, c0, acc);
+    gain_dense_tile<kGdAStored, -1>(As, Xs, mat, a.panels + op.W, r0, nr, r0, k_end, nk, a.ldp, ld, c0, acc);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
