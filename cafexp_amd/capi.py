@@ -70,6 +70,11 @@ class CafeGainMarginalOut(C.Structure):
                 ("p_same", _f64p)]
 
 
+class CafeGainGradientOut(C.Structure):
+    _fields_ = [("lnl", _f64p), ("d_lambda", _f64p), ("d_mu", _f64p), ("d_nu", _f64p), ("d_alpha", _f64p), ("d_beta", _f64p),
+                ("d_r", _f64p)]
+
+
 class CafeGradientOut(C.Structure):
     _fields_ = [("family_lnl", _f64p), ("d_lambda", _f64p), ("d_mu", _f64p), ("d_multiplier", _f64p), ("failed", _i32p)]
 
@@ -158,7 +163,7 @@ EXPORTS = [
     "cafe_debug_pvalues_stages", "cafe_debug_sort_rows", "cafe_debug_tree_pvalue",
     "cafe_score_gain", "cafe_debug_gain_dense",
     "cafe_gain_posterior_dense", "cafe_debug_gain_dense_posterior", "cafe_set_gain_scaling", "cafe_gain_leaf_predictive", "cafe_debug_gain_predictive",
-    "cafe_gain_marginal_dense", "cafe_debug_gain_marginal",
+    "cafe_gain_marginal_dense", "cafe_debug_gain_marginal", "cafe_gain_score_gradient", "cafe_debug_gain_gradient",
 ]
 CAFE_CHANGE_NONE = -(1 << 31)   # mode / lo / hi of cafe_branch_change at the root and in a failed family
 CAFE_COMM_ID_BYTES = 128
@@ -261,6 +266,11 @@ def load():
                                            C.POINTER(CafeGainMarginalOut)]
     L.cafe_debug_gain_marginal.restype = C.c_int
     L.cafe_debug_gain_marginal.argtypes = [C.c_void_p, _f64p, _f64p]
+    L.cafe_gain_score_gradient.restype = C.c_int
+    L.cafe_gain_score_gradient.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p, _f64p, _f64p, C.c_double, C.c_int64, _i64p,
+                                           C.POINTER(CafeGainGradientOut)]
+    L.cafe_debug_gain_gradient.restype = C.c_int
+    L.cafe_debug_gain_gradient.argtypes = [C.c_void_p, _f64p, _f64p]
     L.cafe_set_gain_scaling.restype = C.c_int
     L.cafe_set_gain_scaling.argtypes = [C.c_void_p, C.c_int]
     L.cafe_bd_gain_row0.restype = C.c_int
@@ -727,6 +737,38 @@ class Context:
         repeats of the split included)"""
         ms, flops = np.zeros(9), np.zeros(1)
         self._check(self._lib.cafe_debug_gain_marginal(self._h, _p(ms, _f64p), _p(flops, _f64p)))
+        return ms, float(flops[0])
+
+    def gain_score_gradient(self, pr: Params, families, lambdas, mus, nus, root_absent: float = 0.0) -> dict:
+        """cafe_gain_score_gradient: under the gain model with ONE set of rates (score_gain's arguments), for every listed family
+        the derivative of its sum-rule lnL in the rates -- d_lambda, d_nu and, when mus is given, d_mu [n][n_lambdas] (mus None:
+        d_lambda is taken along mu = lambda) -- and per branch in alpha, beta and r = nu / lambda: d_alpha, d_beta, d_r
+        [n][n_nodes], NaN at the root; lnl [n] is score_gain's under the sum rule bit for bit.  Plain fp64 whatever
+        set_gain_scaling says."""
+        fam = np.ascontiguousarray(families, dtype=np.int64).reshape(-1)
+        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(-1)
+        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(-1)
+        mu = None if mus is None else np.ascontiguousarray(mus, dtype=np.float64).reshape(-1)
+        if len(lam) != self.problem.n_lambdas or nu.shape != lam.shape or (mu is not None and mu.shape != lam.shape):
+            raise ValueError("lambdas, mus and nus must be [%d]" % self.problem.n_lambdas)
+        cp, keep = self._params(pr)
+        n, nodes = len(fam), self.problem.n_nodes
+        res = {"lnl": np.empty(n)}
+        res.update({key: np.empty((n, len(lam))) for key in ("d_lambda", "d_nu") + (() if mu is None else ("d_mu",))})
+        res.update({key: np.empty((n, nodes)) for key in ("d_alpha", "d_beta", "d_r")})
+        out = CafeGainGradientOut()
+        for name, array in res.items():
+            setattr(out, name, _p(array, _f64p))
+        self._check(self._lib.cafe_gain_score_gradient(self._h, C.byref(cp), _p(lam, _f64p), None if mu is None else _p(mu, _f64p), _p(nu, _f64p),
+                                                       float(root_absent), n, _p(fam, _i64p), C.byref(out)))
+        return res
+
+    def gain_gradient_profile(self):
+        """(HIP-event ms of the build, product, GEMM, root, weights, transposed GEMM, interior score, leaf score, second outside
+        GEMM, Toeplitz GEMM and leaf filter launches of the last gain_score_gradient and their total -- 0 unless profiling was
+        on --, the flops its MFMA kernels issued)"""
+        ms, flops = np.zeros(12), np.zeros(1)
+        self._check(self._lib.cafe_debug_gain_gradient(self._h, _p(ms, _f64p), _p(flops, _f64p)))
         return ms, float(flops[0])
 
     def set_gain_scaling(self, on: bool):

@@ -130,14 +130,16 @@ struct LastCall {
     hipStream_t stream = nullptr;            // the stream it was enqueued on
 };
 
-// The gain dense path (gain_dense.hip): its four entries are four modes of one call, and its launches fall into nine kinds --
-// build, product, GEMM, root (every mode), weights, transposed or split GEMM, interior and leaf outputs or summaries (the down
-// pass), the fused leaf kernel (the predictive mode).  A mode's last call leaves one record: HIP-event ms by kind (while
-// profiling) and the flops its MFMA kernels issued.  The cafe_debug_gain_* entries publish it in their own slot layouts.
-enum GainMode { kGainScore = 0, kGainPosterior = 1, kGainPredictive = 2, kGainMarginal = 3, kGainModes = 4 };
-enum { kGdBuild = 0, kGdProduct = 1, kGdGemm = 2, kGdRoot = 3, kGdWeights = 4, kGdGemmT = 5, kGdInterior = 6, kGdLeaf = 7, kGdPredict = 8, kGdKinds = 9 };
+// The gain dense path (gain_dense.hip): its five entries are five modes of one call, and its launches fall into twelve kinds --
+// build, product, GEMM, root (every mode), weights, transposed or split GEMM, interior and leaf outputs, summaries or scores (the
+// down pass), the fused leaf kernel (the predictive mode), and the gradient mode's second outside GEMM, Toeplitz GEMM and leaf
+// filters.  A mode's last call leaves one record: HIP-event ms by kind (while profiling) and the flops its MFMA kernels issued.
+// The cafe_debug_gain_* entries publish it in their own slot layouts.
+enum GainMode { kGainScore = 0, kGainPosterior = 1, kGainPredictive = 2, kGainMarginal = 3, kGainGradient = 4, kGainModes = 5 };
+enum { kGdBuild = 0, kGdProduct = 1, kGdGemm = 2, kGdRoot = 3, kGdWeights = 4, kGdGemmT = 5, kGdInterior = 6, kGdLeaf = 7, kGdPredict = 8,
+       kGdOutside2 = 9, kGdToeplitz = 10, kGdFilter = 11, kGdKinds = 12 };
 struct GainProfile {
-    double ms[kGdKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, flops = 0;
+    double ms[kGdKinds] = {}, flops = 0;
 };
 
 }  // namespace cafe

@@ -25,7 +25,8 @@
 // cafe_gain_posterior_dense: the same up pass with the sum rule forced, then the other half of the sum-product on the panels it
 // left -- by depth from the root a weights kernel, an MFMA GEMM over the matrices as stored (P^T), and the output kernels of
 // the interior nodes and of the leaves ("down" below).  cafe_gain_leaf_predictive and cafe_gain_marginal_dense walk the same
-// depths with other kernels behind the weights: the fused leaf kernel, the split GEMM and the summaries.
+// depths with other kernels behind the weights: the fused leaf kernel, the split GEMM and the summaries.  cafe_gain_score_gradient
+// keeps the transposed GEMM and adds a second outside panel, a Toeplitz GEMM and the score kernels (gain_gradient_kernel.h).
 //
 // How the file hangs together.  Every MFMA kernel -- the up GEMM, the transposed GEMM, the fused predictive kernel, the split GEMM --
 // runs the ONE tile loop gain_dense_tile, told at compile time how the matrix holds A and which side of the diagonal to keep.
@@ -247,9 +248,13 @@ struct GainGemmArgs {
 //   Side   0: the whole range.  +1 keeps k < r, -1 keeps k > r (kGdAStored only), inside the straddling tiles r0 <= k0 < r0 + 64
 //          only -- every other tile of the range lies wholly on the kept side and is staged as it is.  The comparison is made
 //          once, on the staging registers, as the tile is loaded, never in the MFMA loop.
-enum { kGdAColumn = 0, kGdAStored = 1 };
+//          kGdAToeplitz: A[r][k] = mat[k - r] for k > r, else 0 -- a strictly upper triangular Toeplitz matrix that is never
+//          stored: `mat` is its one generating row and the tile is made on the staging registers, in the stored form's
+//          arrangement (gain_gradient_kernel.h).
+//   Shift  the right-hand side is X'[k] = (k + 1) X[k + 1] in place of X[k]; nk counts the rows of X' (one fewer than X has).
+enum { kGdAColumn = 0, kGdAStored = 1, kGdAToeplitz = 2 };
 typedef double gd4 __attribute__((ext_vector_type(4)));
-template <int AForm, int Side>
+template <int AForm, int Side, bool Shift = false>
 __device__ __forceinline__ void gain_dense_tile(double (*As)[kGdKT * kGdLdA], double (*Xs)[kGdKT * kGdLdX], const double* __restrict__ mat,
                                                 const double* __restrict__ X, int r0, int nr, int kb, int ke, int nk, int ldp, int64_t ld, int64_t c0,
                                                 gd4 (&acc)[4][2]) {
@@ -273,6 +278,12 @@ __device__ __forceinline__ void gain_dense_tile(double (*As)[kGdKT * kGdLdA], do
                 const int r = r0 + lane, k = k0 + wave + 4 * u;
                 ra[u] = (r < nr && k < nk) ? Pt[(int64_t)k * ldp + r] : 0.0;
             }
+        } else if constexpr (AForm == kGdAToeplitz) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int k = k0 + 4 * aq + u;
+                ra[u] = (c < nr && k > c && k < nk) ? Pt[k - c] : 0.0;
+            }
         } else {
             const bool straddle = Side != 0 && k0 >= r0 && k0 < r0 + kGdMT; // (block-uniform)
 #pragma unroll
@@ -294,7 +305,8 @@ __device__ __forceinline__ void gain_dense_tile(double (*As)[kGdKT * kGdLdA], do
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int k = k0 + wave + 4 * u;
-            rx[u] = k < nk ? *reinterpret_cast<const double2*>(X + (int64_t)k * ld + c0 + 2 * lane) : make_double2(0.0, 0.0);
+            rx[u] = k < nk ? *reinterpret_cast<const double2*>(X + (int64_t)(k + (Shift ? 1 : 0)) * ld + c0 + 2 * lane) : make_double2(0.0, 0.0);
+            if constexpr (Shift) { rx[u].x *= (double)(k + 1); rx[u].y *= (double)(k + 1); }
         }
     };
     auto stage = [&](int buf) {
@@ -316,7 +328,7 @@ __device__ __forceinline__ void gain_dense_tile(double (*As)[kGdKT * kGdLdA], do
         for (int s4 = 0; s4 < 4; ++s4) {
             double af[4], bf[2];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = As[buf][(4 * s4 + l4) * kGdLdA + ((16 * i + l15) ^ (AForm == kGdAStored ? s4 << 3 : 0))];
+            for (int i = 0; i < 4; ++i) af[i] = As[buf][(4 * s4 + l4) * kGdLdA + ((16 * i + l15) ^ (AForm != kGdAColumn ? s4 << 3 : 0))];
 #pragma unroll
             for (int j = 0; j < 2; ++j) bf[j] = Xs[buf][(4 * s4 + l4) * kGdLdX + 32 * wave + 16 * j + l15];
 #pragma unroll
@@ -859,6 +871,9 @@ __global__ __launch_bounds__(256) void gain_predictive_dense_leaf_kernel(const G
 // ------------------------------------------------------------------------------------- down: sizes, intervals, change
 #include "gain_marginal_kernel.h"
 
+// ----------------------------------------------------------------------------- down: score vectors in alpha, beta, r
+#include "gain_gradient_kernel.h"
+
 // ---------------------------------------------------------------------------------------------------------------- host
 // HIP events around the launches of a call, by kind (cafe_set_profiling)
 struct GainTimer {
@@ -1019,10 +1034,15 @@ struct GainPlan {
     std::vector<int> prod_off{0}, gemm_off{0}, prod_rows, gemm_rows, weight_off{0}, int_off{0}, leaf_off{0}, weight_rows;
     std::vector<double> reals;                         // log mass of the root sizes, then the error model
     std::vector<double> mass;                          // the root's outside vector (with `walk`)
+    // the gradient mode: the keys that leaves have (three derivative matrices each), a key's place among them, the table
+    // L[j] = beta^j / j of every key in rows of ldl doubles, and the first of the second outside panels (one per node of the widest depth)
+    std::vector<int32_t> leaf_keys, dmat_of;
+    std::vector<double> ltab;
+    int ldl = 0, o2idx = 0;
 
     int n_keys() const { return (int)slots.size(); }
 
-    int index(cafe_ctx* c, const char* who, const GainCall& q, bool walk) {
+    int index(cafe_ctx* c, const char* who, const GainCall& q, bool walk, bool grad = false) {
         const int nn = c->n_nodes;
         std::map<std::pair<int, long>, int> key_of;
         node_key.assign(nn, -1); height.assign(nn, -1); bidx.assign(nn, -1); fidx.assign(nn, -1);
@@ -1058,6 +1078,24 @@ struct GainPlan {
         for (int d = 1; d < n_depths; ++d)
             for (int k = depth_off[d]; k < depth_off[d + 1]; ++k) widx[by_depth[k]] = n_pan + n_out + (k - depth_off[d]);
         n_down = n_out + widest;
+        if (!grad) return CAFE_OK;
+        o2idx = n_pan + n_down;
+        n_down += widest;
+        dmat_of.assign(slots.size(), -1);
+        for (int u = 0; u < nn; ++u)
+            if (u != c->root && c->leaf_taxon[u] >= 0 && dmat_of[node_key[u]] < 0) {
+                dmat_of[node_key[u]] = (int32_t)leaf_keys.size();
+                leaf_keys.push_back(node_key[u]);
+            }
+        ldl = round_up(c->N, 16) + 16;
+        ltab.assign(slots.size() * (size_t)ldl, 0.0);
+        for (size_t k = 0; k < slots.size(); ++k) {
+            double bj = 1.0;
+            for (int j = 1; j <= c->M; ++j) {
+                bj *= slots[k].beta;
+                ltab[k * ldl + j] = bj / j;
+            }
+        }
         return CAFE_OK;
     }
 
@@ -1136,6 +1174,7 @@ struct GainLayout {
     std::vector<char> blob;
     size_t o_children = 0, o_prod = 0, o_gemm = 0, o_slots = 0, o_reals = 0, o_weight = 0, o_int = 0, o_leaf = 0, o_mass = 0;
     size_t o_col = 0, o_out = 0, o_mats = 0, o_pan = 0, o_res = 0, o_post = 0, o_parts = 0, o_ires = 0, o_exps = 0, o_zt = 0, need = 0;
+    size_t o_ltab = 0, o_leaf_keys = 0, o_dmat_of = 0, o_dmats = 0;    // the gradient mode's tables and derivative matrices
 
     void batch(const cafe_ctx* c, const GainCall& q, const GainSink& sink, bool scaled, const GainPlan& plan, size_t budget);
     void place(const cafe_ctx* c, const GainSink& sink, bool scaled, const GainPlan& plan);
@@ -1145,17 +1184,19 @@ struct GainLayout {
 void GainLayout::batch(const cafe_ctx* c, const GainCall& q, const GainSink& sink, bool scaled, const GainPlan& plan, size_t budget) {
     GainLayout& w = *this;
     const int nn = c->n_nodes, N = c->N, M = c->M, R = c->R, n_keys = plan.n_keys(), n_pan = plan.n_pan, n_down = plan.n_down;
-    const bool walk = sink.mode != kGainScore, marg = sink.mode == kGainMarginal;
+    const bool walk = sink.mode != kGainScore, marg = sink.mode == kGainMarginal, grad = sink.mode == kGainGradient;
     const size_t planes = sink.dst.size() * (size_t)sink.rows, iplanes = sink.idst.size() * (size_t)sink.rows;
     w.mat_stride = (int64_t)N * round_up(N, 2);
     w.split_tiles = (M + kGdMT) / kGdMT;
     const size_t fixed_bytes = sizeof(double) * (size_t)w.mat_stride * n_keys + ((size_t)64 << 10) + sizeof(GainChild) * (size_t)nn +
                                sizeof(GainProdOp) * (size_t)nn + sizeof(GainGemmOp) * (size_t)nn + sizeof(SlotParamGain) * (size_t)n_keys +
                                sizeof(double) * ((size_t)R + 1 + (size_t)(M + 1) * c->n_dev) +
-                               (walk ? (sizeof(GainChild) + sizeof(GainWeightOp) + sizeof(GainNodeOp)) * (size_t)nn + sizeof(double) * ((size_t)R + 1) : 0);
+                               (walk ? (sizeof(GainChild) + sizeof(GainWeightOp) + sizeof(GainNodeOp)) * (size_t)nn + sizeof(double) * ((size_t)R + 1) : 0) +
+                               (grad ? sizeof(double) * (3 * (size_t)w.mat_stride * plan.leaf_keys.size() + plan.ltab.size()) + 2 * sizeof(int32_t) * (size_t)n_keys + kGdRegion : 0);
     const size_t column_bytes = sizeof(double) * (size_t)n_pan * N + sizeof(int64_t) + sizeof(double) +
                                 sizeof(double) * ((size_t)n_down * N + planes + (sink.posterior ? (size_t)nn * N : 0)) + sizeof(int32_t) * iplanes +
                                 (marg ? sizeof(double) * 3 * (size_t)w.split_tiles * nn : 0) +                     // the split's partials
+                                (grad ? sizeof(double) * (size_t)w.split_tiles * nn : 0) +                         // the Toeplitz GEMM's
                                 (scaled ? sizeof(int32_t) * (size_t)(n_pan + n_down) + sizeof(double) : 0);     // the exponents, log Z~
     int64_t entries = budget > fixed_bytes ? (int64_t)((budget - fixed_bytes) / column_bytes) / kGdCols * kGdCols : 0;
     entries = std::max<int64_t>(kGdCols, std::min<int64_t>(entries, round_up64(q.n, kGdCols)));
@@ -1169,20 +1210,22 @@ void GainLayout::batch(const cafe_ctx* c, const GainCall& q, const GainSink& sin
 void GainLayout::place(const cafe_ctx* c, const GainSink& sink, bool scaled, const GainPlan& plan) {
     GainLayout& w = *this;
     const int nn = c->n_nodes, N = c->N, n_keys = plan.n_keys(), n_pan = plan.n_pan, n_down = plan.n_down;
-    const bool marg = sink.mode == kGainMarginal;
+    const bool marg = sink.mode == kGainMarginal, grad = sink.mode == kGainGradient;
     const size_t planes = sink.dst.size() * (size_t)sink.rows, iplanes = sink.idst.size() * (size_t)sink.rows;
     const int64_t ld = w.ld;
     w.o_children = put(w.blob, plan.children); w.o_prod = put(w.blob, plan.prod_ops); w.o_gemm = put(w.blob, plan.gemm_ops);
     w.o_slots = put(w.blob, plan.slots); w.o_reals = put(w.blob, plan.reals); w.o_weight = put(w.blob, plan.weight_ops);
     w.o_int = put(w.blob, plan.int_ops); w.o_leaf = put(w.blob, plan.leaf_ops); w.o_mass = put(w.blob, plan.mass);
+    w.o_ltab = put(w.blob, plan.ltab); w.o_leaf_keys = put(w.blob, plan.leaf_keys); w.o_dmat_of = put(w.blob, plan.dmat_of);
     w.o_col = gain_region_up(w.blob.size());
     w.o_out = w.o_col + family_align_up(sizeof(int64_t) * ld);
     w.o_mats = gain_region_up(w.o_out + sizeof(double) * ld);
-    w.o_pan = gain_region_up(w.o_mats + sizeof(double) * (size_t)w.mat_stride * n_keys);
+    w.o_dmats = gain_region_up(w.o_mats + sizeof(double) * (size_t)w.mat_stride * n_keys);
+    w.o_pan = gain_region_up(w.o_dmats + sizeof(double) * 3 * (size_t)w.mat_stride * plan.leaf_keys.size());
     w.o_res = w.o_pan + sizeof(double) * (size_t)w.pan_stride * (n_pan + n_down);
     w.o_post = w.o_res + sizeof(double) * planes * ld;
     w.o_parts = w.o_post + (sink.posterior ? sizeof(double) * (size_t)nn * N * ld : 0);
-    w.o_ires = w.o_parts + (marg ? sizeof(double) * 3 * (size_t)w.split_tiles * nn * ld : 0);
+    w.o_ires = w.o_parts + sizeof(double) * (marg ? 3 : grad ? 1 : 0) * (size_t)w.split_tiles * nn * ld;
     w.o_exps = w.o_ires + (iplanes ? family_align_up(sizeof(int32_t) * iplanes * ld) : 0);
     w.o_zt = w.o_exps + (scaled ? family_align_up(sizeof(int32_t) * (size_t)(n_pan + n_down) * ld) : 0);
     w.need = w.o_zt + (scaled ? sizeof(double) * ld : 0);
@@ -1251,6 +1294,20 @@ int gain_dense_batches(cafe_ctx* c, const GainCall& q, const GainPlan& plan, con
     if (scaled) oa.lnl = zt;                           // the outputs divide by Z~ = exp(log Z~)
     GainSplitArgs xa{int_ops, mats, panels, reinterpret_cast<double*>(base + w.o_parts), ld, M + 1, ldp};
     GainSummaryArgs ya{oa, xa.parts, reinterpret_cast<int32_t*>(base + w.o_ires), q.level, w.split_tiles};
+    GainGradArgs da{};
+    da.slots = ba.slots; da.mats = mats; da.panels = panels; da.ltab = reinterpret_cast<const double*>(base + w.o_ltab); da.parts = xa.parts;
+    da.dmats = reinterpret_cast<double*>(base + w.o_dmats); da.leaf_keys = reinterpret_cast<const int32_t*>(base + w.o_leaf_keys);
+    da.dmat_of = reinterpret_cast<const int32_t*>(base + w.o_dmat_of); da.lnl = ra.out; da.res = oa.res;
+    da.col = pa.col; da.counts = pa.counts; da.err = pa.err; da.counts_ld = pa.counts_ld; da.ld = ld;
+    da.mat_stride = w.mat_stride; da.pan_stride = w.pan_stride; da.o2 = plan.o2idx * w.pan_stride;
+    da.nn = nn; da.N = N; da.M = M; da.ldp = ldp; da.ldl = plan.ldl; da.n_dev = c->n_dev; da.tiles = w.split_tiles;
+    if (mode == kGainGradient && !plan.leaf_keys.empty()) {      // the derivative matrices of the leaf keys stand once, like the matrices
+        const unsigned nk = (unsigned)plan.leaf_keys.size(), sb = (unsigned)((N + 63) / 64);
+        timer.mark(kGdFilter, s);
+        CAFE_LAUNCH(c, gain_gradient_filter_kernel, dim3(sb, nk), dim3(64), 0, s, da);
+        CAFE_LAUNCH(c, gain_gradient_lambda_kernel, dim3(sb, (unsigned)((M + kGgChunk) / kGgChunk), nk), dim3(64), 0, s, da);
+        timer.mark(kGdFilter, s);
+    }
     sink.resize(w.entries, N);
 
     const double k_rows = round_up(M + 1, kGdMT);      // the rows a down-pass MFMA kernel issues for a node
@@ -1318,6 +1375,36 @@ int gain_dense_batches(cafe_ctx* c, const GainCall& q, const GainPlan& plan, con
                 timer.mark(kGdGemmT, s);
                 for (int k = 0; k < nt; ++k) flops += 2.0 * k_rows * (double)round_up(h_int[k].rows, kGdKT) * (double)cols;
             }
+            if (mode == kGainGradient) {               // the second outside panels and the Toeplitz sums, then the three scores of every branch
+                GainGradArgs g = da;
+                g.ncols = cols;
+                g.ops = int_ops + plan.int_off[d];
+                if (nt > 0) {
+                    const dim3 grid(tiles, (unsigned)w.split_tiles, (unsigned)nt);
+                    timer.mark(kGdOutside2, s);
+                    CAFE_LAUNCH(c, gain_gradient_outside2_kernel, grid, dim3(256), 0, s, g);
+                    timer.mark(kGdOutside2, s);
+                    timer.mark(kGdToeplitz, s);
+                    CAFE_LAUNCH(c, gain_gradient_toeplitz_kernel, grid, dim3(256), 0, s, g);
+                    timer.mark(kGdToeplitz, s);
+                    for (int k = 0; k < nt; ++k) {
+                        flops += 2.0 * k_rows * (double)round_up(h_int[k].rows - 1, kGdKT) * (double)cols;
+                        for (int r0 = 0; r0 <= M; r0 += kGdMT) flops += 2.0 * kGdMT * (double)(round_up(M + 1, kGdKT) - r0) * (double)cols;
+                    }
+                }
+                if (ni > 0) {
+                    timer.mark(kGdInterior, s);
+                    CAFE_LAUNCH(c, gain_gradient_interior_kernel, dim3(blocks256, (unsigned)ni), dim3(256), 0, s, g);
+                    timer.mark(kGdInterior, s);
+                }
+                if (nl > 0) {
+                    g.ops = leaf_ops + plan.leaf_off[d];
+                    timer.mark(kGdLeaf, s);
+                    CAFE_LAUNCH(c, gain_gradient_leaf_kernel, dim3(blocks64, (unsigned)nl), dim3(256), 0, s, g);
+                    timer.mark(kGdLeaf, s);
+                }
+                continue;
+            }
             if (mode == kGainPredictive) {             // the leaves' six sums straight from the MFMA accumulators; no other output
                 if (nl == 0) continue;
                 GainPredArgs pq = qa;
@@ -1369,12 +1456,13 @@ int gain_dense_batches(cafe_ctx* c, const GainCall& q, const GainPlan& plan, con
 int gain_dense_run(cafe_ctx* c, const char* who, const GainCall& q, GainSink& sink) {
     if (const int rc = gain_dense_check(c, who, q, sink.lnl)) return rc;
     if (q.n == 0) return CAFE_OK;
-    const bool scaled = c->gain_scaling != 0;          // cafe_set_gain_scaling: the scaled twins of every kernel but the build and the GEMMs
+    const bool grad = sink.mode == kGainGradient;
+    const bool scaled = c->gain_scaling != 0 && !grad; // cafe_set_gain_scaling: the scaled twins of every kernel but the build and the GEMMs; the gradient mode has none
     c->last.state = LastCall::kNone;                   // cafe_family_results is not meaningful after this call
     c->gain_profile[sink.mode] = GainProfile{};
     if (gain_dense_host_answer(c, q, sink.lnl)) return CAFE_OK;
     GainPlan plan;
-    if (const int rc = plan.index(c, who, q, sink.mode != kGainScore)) return rc;
+    if (const int rc = plan.index(c, who, q, sink.mode != kGainScore, grad)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     size_t budget = 0;
     HIP_TRY(c, workspace_budget(c->workspace_limit, c->pf_dev_bytes, &budget));
@@ -1415,8 +1503,95 @@ int gain_profile_read(cafe_ctx* ctx, GainMode mode, int kinds, double* ms, doubl
     return CAFE_OK;
 }
 
+// The chain rule of cafe_gain_score_gradient, per node in node order: the branch scores in (alpha, beta, r) of an entry -- raw
+// [3][n][n_nodes] -- to the scores in the rates at the quantized key.  mus == nullptr: one free rate along mu = lambda.  A
+// saturated key adds exactly 0 (and its three raw scores are delivered as 0); a rate index whose quantized lambda is 0 has NaN.
+void gain_gradient_chain(const cafe_ctx* c, const GainCall& q, const std::vector<double>& lnl, std::vector<double>& raw, const cafe_gain_gradient_out* out) {
+    const int nn = c->n_nodes, nl = c->n_lambdas;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const size_t plane = (size_t)q.n * nn;
+    bool any = false;
+    for (int64_t i = 0; i < q.n; ++i) any = any || std::isfinite(lnl[i]);
+    struct Coef { double al, am, bl, bm, rl, rn; int kind; };   // kind 0: saturated, 1: live, 2: lambda_q = 0
+    std::vector<Coef> coef(nn, Coef{0, 0, 0, 0, 0, 0, 0});
+    std::vector<char> poisson(nl, 0);
+    for (int u = 0; any && u < nn; ++u) {
+        if (u == c->root) continue;
+        const int k = c->lam_idx[u];
+        if (gain_branch_slot(c, u, q.lam, q.mus, q.nus).zero) continue;
+        const long lq = quantize_lambda(q.lam[k]), mq = q.mus ? quantize_lambda(q.mus[k]) : lq;
+        if (lq == 0) { coef[u].kind = 2; continue; }
+        const double l = double(lq) / 1000000000.0, m = double(mq) / 1000000000.0, nu = double(quantize_lambda(q.nus[k])) / 1000000000.0;
+        double g[4];
+        bd_rates_grad(l, m, double(quantize_time(c->blen[u])) / 1000.0, g);
+        coef[u] = Coef{g[0], g[1], g[2], g[3], -nu / (l * l), 1.0 / l, 1};
+    }
+    for (int k = 0; any && k < nl; ++k) poisson[k] = poisson[k] || quantize_lambda(q.lam[k]) == 0;
+    for (int64_t i = 0; i < q.n; ++i) {
+        if (out->lnl) out->lnl[i] = lnl[i];
+        const bool ok = std::isfinite(lnl[i]);
+        double* const ra = raw.data() + i * nn, *const rb = ra + plane, *const rr = rb + plane;
+        if (!ok) for (double* r : {ra, rb, rr}) std::fill(r, r + nn, nan);
+        for (int k = 0; k < nl; ++k) {
+            double dl = 0.0, dm = 0.0, dn = 0.0;
+            for (int u = 0; ok && u < nn; ++u) {
+                if (u == c->root || c->lam_idx[u] != k) continue;
+                const Coef& e = coef[u];
+                if (e.kind != 1) { ra[u] = rb[u] = rr[u] = e.kind == 0 ? 0.0 : nan; continue; }
+                if (q.mus) {
+                    dl += (ra[u] * e.al + rb[u] * e.bl) + rr[u] * e.rl;
+                    dm += ra[u] * e.am + rb[u] * e.bm;
+                } else {
+                    dl += (ra[u] * (e.al + e.am) + rb[u] * (e.bl + e.bm)) + rr[u] * e.rl;
+                }
+                dn += rr[u] * e.rn;
+            }
+            const bool bad = !ok || poisson[k];
+            if (out->d_lambda) out->d_lambda[i * nl + k] = bad ? nan : dl;
+            if (out->d_mu && q.mus) out->d_mu[i * nl + k] = bad ? nan : dm;
+            if (out->d_nu) out->d_nu[i * nl + k] = bad ? nan : dn;
+        }
+        double* const to[3] = {out->d_alpha, out->d_beta, out->d_r};
+        const double* const from[3] = {ra, rb, rr};
+        for (int p = 0; p < 3; ++p)
+            if (to[p]) std::copy(from[p], from[p] + nn, to[p] + i * nn);
+    }
+}
+
 }  // namespace
 }  // namespace cafe
+
+int cafe_gain_score_gradient(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus, double root_absent,
+                             int64_t n, const int64_t* family, const cafe_gain_gradient_out* out) {
+    const char* const who = "cafe_gain_score_gradient";
+    const cafe::GainCall q{params, lambdas, mus, nus, root_absent, n, family};
+    std::vector<double> raw, lnl;
+    const int rc = cafe::gain_dense_entry(ctx, who, cafe::kGainGradient, q, [&](cafe::GainSink& sink) {
+        if (!out) { cafe::set_err(ctx, "%s: out is required", who); return (int)CAFE_ERR_ARGUMENT; }
+        const size_t entries = n > 0 ? (size_t)n : 0, plane = entries * ctx->n_nodes;
+        raw.assign(3 * plane, std::numeric_limits<double>::quiet_NaN());
+        lnl.assign(entries, std::numeric_limits<double>::quiet_NaN());
+        sink.lnl = lnl.data();
+        sink.dst = {raw.data(), raw.data() + plane, raw.data() + 2 * plane};
+        sink.rows = ctx->n_nodes;
+        return (int)CAFE_OK;
+    });
+    if (rc != CAFE_OK || n <= 0) return rc;
+    return cafe::guarded(ctx, who, [&] { cafe::gain_gradient_chain(ctx, q, lnl, raw, out); return (int)CAFE_OK; });
+}
+
+// the posterior entry's eight (interior and leaf: the score kernels), the second outside GEMM, the Toeplitz GEMM, the leaf filters;
+// then their total
+int cafe_debug_gain_gradient(cafe_ctx* ctx, double ms[12], double* flops) {
+    const int rc = cafe::gain_profile_read(ctx, cafe::kGainGradient, 8, ms, flops);
+    if (rc != CAFE_OK || !ms) return rc;
+    ms[8] = ctx->gain_profile[cafe::kGainGradient].ms[cafe::kGdOutside2];
+    ms[9] = ctx->gain_profile[cafe::kGainGradient].ms[cafe::kGdToeplitz];
+    ms[10] = ctx->gain_profile[cafe::kGainGradient].ms[cafe::kGdFilter];
+    ms[11] = 0.0;
+    for (int k = 0; k < 11; ++k) ms[11] += ms[k];
+    return rc;
+}
 
 int cafe_score_gain(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus, double root_absent, int64_t n,
                     const int64_t* family, double* family_lnl) {

@@ -438,6 +438,7 @@ void write_history_reports(const history_result& res, double level, const std::s
 struct gradient_result {
     size_t n_lambdas = 0, n_categories = 0;                          // n_categories: 0 for the base model
     std::vector<double> family_lnl, d_lambda, d_mu, d_multiplier;    // [family], [family][lambda] (d_mu: with death rates), [family][category]
+    std::vector<double> d_nu;                                        // [family][lambda]: the gain model's call alone (gain_score_gradient)
     std::vector<int32_t> failed;
 };
 // Standard errors from per-family scores (standard_errors.cpp): information = sum_f s_f s_f^T over the families with finite
@@ -633,6 +634,10 @@ public:
     marginal_result gain_marginal(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
                                   const std::vector<size_t>& entry_of, const std::vector<double>& lambdas, const std::vector<double>& mus, double nu,
                                   double root_absent, double level, const std::vector<const clade*>& order);
+    // cafe_gain_score_gradient at ONE set of rates over the listed entries (--gain-dense --standard-errors): family_lnl [n] and
+    // d_lambda, d_mu, d_nu [n][n_lambdas] of the listed entries.  mu_tied: mu = lambda is one free rate (mus is not passed)
+    gradient_result gain_score_gradient(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
+                                        const std::vector<double>& lambdas, const std::vector<double>& mus, double nu, double root_absent, bool mu_tied);
 private:
     bool _gain_scaled = false;
 };

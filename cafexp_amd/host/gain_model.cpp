@@ -14,7 +14,9 @@
 // likelihoods lie below fp64's range and would otherwise make -lnL inf.  --leaf-predictive with --gain-dense: after the fit,
 // cafe_gain_leaf_predictive at the fitted rates over the distinct families, and leaf_predictive.cpp's reports under the name Gain.
 // --reconstruct-marginal [LEVEL] with --gain-dense: likewise cafe_gain_marginal_dense, and the base model's marginal reports
-// (Gain_posterior_sizes.tab, Gain_posterior_change.tab).
+// (Gain_posterior_sizes.tab, Gain_posterior_change.tab).  --standard-errors with --gain-dense: cafe_gain_score_gradient at the
+// fitted rates over the distinct families and the absent profile; a family's score of the conditional likelihood is
+// s_f + (p / (1 - p)) s_absent, p = exp(lnL_absent), and standard_errors.cpp makes Gain_standard_errors.txt of them.
 //
 // The search is the Nelder-Mead of every other fit (optimizer / nm_search), over [lambdas..., mus (--estimate-mu)..., nu], nested
 // like -b --family-mu estimate: first the model without nu, then with nu from that optimum (start nu = lambda / 10, or nu held at
@@ -189,7 +191,7 @@ const char* gain_refusal(const gain_request& r) {
     if (r.simulate) return "the simulator has no gain rate: --simulate is not supported with --gain / --estimate-gain";
     if (r.pvalues) return "--pvalues simulates without a gain rate: it is not supported with --gain / --estimate-gain";
     if (r.reconstruct || (r.marginal && !r.dense) || r.histories) return "the reconstructions are not ported to the gain model: --reconstruct, --reconstruct-marginal and --sample-histories are not supported with --gain / --estimate-gain";
-    if (r.standard_errors || r.events || r.rate_shift || (r.leaf_predictive && !r.dense) || r.branch_change || r.rootdist_em)      // (the dense path has its own leave-one-out call)
+    if ((r.standard_errors && !r.dense) || r.events || r.rate_shift || (r.leaf_predictive && !r.dense) || r.branch_change || r.rootdist_em)      // (the dense path has its own leave-one-out call)
         return "the posterior reports are not ported to the gain model: --standard-errors, --expected-events, --rate-shift-scan, --leaf-predictive, --branch-change and --estimate-rootdist are not supported with --gain / --estimate-gain";
     if (r.search_batch) return "the gain search scores one point per call: --search-batch is not supported with --gain / --estimate-gain";
     if (r.estimate_error) return "the gain model needs an error model file: -e without FILE (estimating epsilon) is not supported with --gain / --estimate-gain";

@@ -295,6 +295,29 @@ std::vector<double> hip_base_model::gain_lnl(root_equilibrium_distribution* prio
     return out;
 }
 
+gradient_result hip_base_model::gain_score_gradient(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
+                                                    const std::vector<double>& lambdas, const std::vector<double>& mus, double nu, double root_absent, bool mu_tied) {
+    ensure_context(1);
+    std::vector<float> prior_f;
+    std::vector<double> err, unused;
+    gather_call_inputs(prior, rootdist, prior_f, err, unused);
+    cafe_params pr{};
+    pr.model = CAFE_MODEL_BASE; pr.n_categories = 1; pr.prior = prior_f.data();
+    pr.error_model = err.empty() ? nullptr : err.data();
+    if (mus.size() != lambdas.size()) throw std::runtime_error("gain_score_gradient: one mu per lambda is required");
+    const std::vector<double> nus(lambdas.size(), nu);
+    const size_t n = family.size(), nl = lambdas.size();
+    gradient_result g;
+    g.n_lambdas = nl;
+    g.family_lnl.resize(n); g.d_lambda.resize(n * nl); g.d_nu.resize(n * nl);
+    if (!mu_tied) g.d_mu.resize(n * nl);
+    cafe_gain_gradient_out out{};
+    out.lnl = g.family_lnl.data(); out.d_lambda = g.d_lambda.data(); out.d_nu = g.d_nu.data(); out.d_mu = mu_tied ? nullptr : g.d_mu.data();
+    if (cafe_gain_score_gradient(_ctx, &pr, lambdas.data(), mu_tied ? nullptr : mus.data(), nus.data(), root_absent, (int64_t)n, family.data(), &out) != CAFE_OK)
+        throw std::runtime_error(std::string("cafe_gain_score_gradient: ") + cafe_last_error(_ctx));
+    return g;
+}
+
 gain_origins hip_base_model::gain_posterior(root_equilibrium_distribution* prior, const std::map<int, int>& rootdist, const std::vector<int64_t>& family,
                                             const std::vector<double>& lambdas, const std::vector<double>& mus, const std::vector<double>& nus,
                                             double root_absent, const std::vector<const clade*>& order, bool dense) {

@@ -102,6 +102,8 @@ static void usage() {
         "                  at the fitted rates, posterior size of every node (mean, mode, equal-tailed interval) and the probability that the family\n"
         "                  shrank or grew on every branch under the gain model, by cafe_gain_marginal_dense -> OUTDIR/Gain_posterior_sizes.tab,\n"
         "                  Gain_posterior_change.tab (the formats of --reconstruct-marginal above)\n"
+        "                  [--standard-errors]   only with --gain-dense: standard errors of the searched lambda, mu and nu from the per-family scores\n"
+        "                  of the (conditional) likelihood at the fitted rates, by cafe_gain_score_gradient -> OUTDIR/Gain_standard_errors.txt\n"
         "                  [--gain-scaled]   only with --gain-dense: the dense prune holds its panels as mantissas and one binary exponent per\n"
         "                  (node, family), so families whose likelihood lies below fp64's range (trees of a few dozen taxa with counts that disagree\n"
         "                  across clades) keep a finite -lnL and their posteriors; applies to the search and to --gain-posterior\n"
@@ -625,6 +627,42 @@ int main(int argc, char** argv) {
                 write_marginal_reports(mr, "Gain", out_dir, order, d.gene_families);
                 gain_marginal_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - p0).count();
             }
+            standard_errors gain_se;
+            if (do_standard_errors) {                            // (with --gain-dense only) the scores of the searched objective at the fitted rates
+                const bool lambda_searched = go.fixed_lambdas.empty(), mu_tied = !estimate_mu && go.fixed_mus.empty();
+                const gradient_result gr = base->gain_score_gradient(d.p_prior.get(), d.rootdist, table.family, res.with.lambdas, res.with.mus, res.with.nu,
+                                                                     go.root_absent, mu_tied);
+                const size_t nl = (size_t)L, F = d.gene_families.size(), absent = table.family.size() - 1;
+                std::vector<std::string> names;
+                std::vector<double> est;
+                auto rate_name = [&](const char* what, size_t i) { return nl == 1 ? std::string(what) : what + std::to_string(i + 1); };
+                if (lambda_searched) for (size_t i = 0; i < nl; ++i) { names.push_back(rate_name("Lambda", i)); est.push_back(res.with.lambdas[i]); }
+                if (estimate_mu) for (size_t i = 0; i < nl; ++i) { names.push_back(rate_name("Mu", i)); est.push_back(res.with.mus[i]); }
+                if (go.estimate_nu) { names.push_back("Nu"); est.push_back(res.with.nu); }
+                if (names.empty()) throw std::runtime_error("--standard-errors: no parameter was estimated (lambda, mu and nu are all fixed)");
+                const size_t P = names.size();
+                auto score_of = [&](size_t entry) {              // the entry's score in the searched parameters; one nu for every rate index
+                    std::vector<double> s;
+                    if (lambda_searched) for (size_t i = 0; i < nl; ++i) s.push_back(gr.d_lambda[entry * nl + i]);
+                    if (estimate_mu) for (size_t i = 0; i < nl; ++i) s.push_back(gr.d_mu[entry * nl + i]);
+                    if (go.estimate_nu) { double t = 0; for (size_t i = 0; i < nl; ++i) t += gr.d_nu[entry * nl + i]; s.push_back(t); }
+                    return s;
+                };
+                const std::vector<double> s_abs = score_of(absent);
+                const double p = std::exp(gr.family_lnl[absent]), odds = go.conditional ? p / (1 - p) : 0.0;
+                std::vector<double> scores(F * P);
+                for (size_t f = 0; f < F; ++f) {
+                    const std::vector<double> s = score_of(table.entry_of[f]);
+                    for (size_t k = 0; k < P; ++k) scores[f * P + k] = go.conditional ? s[k] + odds * s_abs[k] : s[k];
+                }
+                gain_se = compute_standard_errors(names, est, scores, F);
+                if (!gain_se.ok) std::fprintf(stderr, "cafexp_hip: warning: the information matrix of the scores is singular or ill-conditioned: no standard errors\n");
+                std::string cond = go.conditional ? "the family being seen in at least one species, root_absent as given" : "root_absent as given";
+                if (!lambda_searched) cond += ", the fixed lambda";
+                if (!estimate_mu) cond += mu_tied ? ", mu = lambda" : ", the fixed mu";
+                if (!go.estimate_nu) cond += ", the fixed nu";
+                write_standard_errors(gain_se, "Gain", out_dir, cond);
+            }
             base->set_lambda(nullptr);                           // `shape` goes with this scope
             auto list = [](const char* name, const std::vector<double>& v) {
                 std::printf("\"%s\": [", name);
@@ -655,6 +693,21 @@ int main(int argc, char** argv) {
             }
             if (do_marginal)
                 std::printf("\"marginal\": {\"seconds\": %.3f, \"level\": %.17g, \"failed\": %zu}, ", gain_marginal_s, marginal_level, gain_marginal_failed);
+            if (do_standard_errors) {
+                auto nums = [](const char* key, const std::vector<double>& v) {
+                    std::printf("\"%s\": [", key);
+                    for (size_t i = 0; i < v.size(); ++i) {
+                        if (std::isfinite(v[i])) std::printf("%s%.17g", i ? ", " : "", v[i]);
+                        else std::printf("%s\"nan\"", i ? ", " : "");
+                    }
+                    std::printf("], ");
+                };
+                std::printf("\"standard_errors\": {\"parameters\": [");
+                for (size_t i = 0; i < gain_se.names.size(); ++i) std::printf("%s\"%s\"", i ? ", " : "", gain_se.names[i].c_str());
+                std::printf("], ");
+                nums("estimate", gain_se.estimate); nums("se", gain_se.se); nums("total_score", gain_se.total_score);
+                std::printf("\"families\": %zu, \"left_out\": %zu}, ", gain_se.families_used, gain_se.families_left_out);
+            }
             std::printf("\"lr_statistic\": %.17g, \"calls\": %d, \"max_family_size\": %d, \"max_root_family_size\": %d, \"seconds\": %.3f}\n", res.lr_statistic,
                         res.without.calls + res.with.calls, d.max_family_size, d.max_root_family_size, seconds);
             return 0;

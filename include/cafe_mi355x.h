@@ -525,6 +525,42 @@ int cafe_gain_marginal_dense(cafe_ctx* ctx, const cafe_params* params, const dou
  * and leaf summary launches and, ninth, the total of those eight (0 unless cafe_set_profiling was on), and the flops of the MFMAs
  * its GEMM kernels issued, the masked repeats of the split included. */
 int cafe_debug_gain_marginal(cafe_ctx* ctx, double ms[9], double* flops);
+/* Score vectors of the gain model, on the dense prune: for entry i of the list the derivative of its sum-rule lnL in the rates
+ * lambda, mu and nu of every rate index -- what standard errors of a gain fit and a score test of nu = 0 are made of -- and, per
+ * branch, in the branch's own three parameters alpha, beta (cafe_bd_rates) and r = nu / lambda.  Row s of a branch's matrix has the
+ * generating function ((1-beta)/(1-beta z))^r ((alpha + (1-alpha-beta) z)/(1-beta z))^s, and with the causal filters H: y[j] = x[j]
+ * + beta y[j-1], S the shift, D = I - S and (Lambda x)[j] = sum_{k>=1} (beta^k / k) x[j-k] along a row
+ *   dP[s]/dalpha = s H D P[s-1],   dP[s]/dbeta = -s (1-alpha) H H S D P[s-1] - (r/(1-beta)) H D P[s],   dP[s]/dr = ln(1-beta) P[s] + Lambda P[s]
+ * on the matrix cut at M as it stands (every operator is lower triangular); the last is valid at r = 0, where it is the score for
+ * the test of nu = 0.  The arguments, the checks, the host-decided values (-inf / NaN entries), the batching, CAFE_FAMILY_ABSENT, an
+ * error model and missing cells are cafe_gain_posterior_dense's; the sum rule is forced and lnl is bit for bit cafe_score_gain's
+ * under CAFE_ROOT_SUM.  The down pass is that call's weights kernel and transposed GEMM by depth, and behind them
+ * (gain_gradient_kernel.h): a second transposed GEMM for O'[c] = sum_{s>=1} s w[s] P[s-1][c]; an fp64 MFMA GEMM over the strictly
+ * upper triangular Toeplitz matrix of beta^j / j, generated on the staging registers from one table per key and reduced against the
+ * outside panel in its epilogue, from the diagonal K tile on; one thread per column running the anti-causal scans H^T B and H^T H^T B
+ * and their dots; and for the leaves three derivative matrices per distinct leaf key (counted against the workspace limit) gathered
+ * at the taps of the observed count.  No atomics: a value depends on the family's counts and the rates only, never on its place in
+ * the list or on the batch cut.  The chain rule is the host's, per node in node order, with cafe_bd_rates_grad's partials at the
+ * quantized key, dr/dlambda = -nu / lambda^2 and dr/dnu = 1 / lambda; mus NULL: one free rate along mu = lambda, in d_lambda.  A
+ * saturated key adds exactly 0; a MISSING leaf's factor is exactly 1.0 and its branch adds exactly 0; a rate index whose quantized
+ * lambda is 0 (the Poisson limit: r is not finite) has NaN in its three scores; a family whose lnl is not finite has NaN scores.
+ * The call runs the plain fp64 kernels whatever cafe_set_gain_scaling says.  Every pointer of out may be NULL.
+ * cafe_family_results is not meaningful after this call; a later cafe_score returns what it returned before. */
+typedef struct cafe_gain_gradient_out {
+    double* lnl;        /* [n]             sum-rule lnL of the family */
+    double* d_lambda;   /* [n][n_lambdas]  d lnL / d lambda_q (mus NULL: along mu = lambda) */
+    double* d_mu;       /* [n][n_lambdas]  d lnL / d mu_q; written only when mus is given */
+    double* d_nu;       /* [n][n_lambdas]  d lnL / d nu_q */
+    double* d_alpha;    /* [n][n_nodes]    (dZ / d alpha of the branch above the node) / Z; NaN at the root */
+    double* d_beta;     /* [n][n_nodes]    likewise in beta */
+    double* d_r;        /* [n][n_nodes]    likewise in r */
+} cafe_gain_gradient_out;
+int cafe_gain_score_gradient(cafe_ctx* ctx, const cafe_params* params, const double* lambdas, const double* mus, const double* nus,
+                             double root_absent, int64_t n, const int64_t* family, const cafe_gain_gradient_out* out);
+/* The last cafe_gain_score_gradient: summed HIP-event ms of its build, product, GEMM, root, weights, transposed GEMM, interior score,
+ * leaf score, second outside GEMM, Toeplitz GEMM and leaf filter launches and, twelfth, their total (0 unless cafe_set_profiling
+ * was on), and the flops its MFMA kernels issued. */
+int cafe_debug_gain_gradient(cafe_ctx* ctx, double ms[12], double* flops);
 /* The scaled mode of cafe_score_gain, cafe_gain_posterior_dense and cafe_gain_leaf_predictive (no other entry reads it); on != 0 switches it on, the
  * default is off.  A family's likelihood is a product over the whole tree and leaves fp64's range on trees of a few dozen taxa
  * whose counts disagree across clades: the plain path then answers lnl = -inf (NaN in every posterior output).  In the scaled
