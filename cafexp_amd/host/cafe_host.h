@@ -32,7 +32,6 @@ struct cafe_ctx;
 struct cafe_sharded;
 struct cafe_params;
 struct cafe_family_out;
-struct cafe_sharded;
 
 namespace cafe {
 
@@ -1118,5 +1117,76 @@ void write_gain_origins(std::ostream& ost, const gain_origins& o, const std::vec
                         const std::vector<std::string>& family_ids, const std::vector<size_t>& entry_of);
 // Gain_branch_origins.tab: one line per branch -- originated, lost, present, the families with p_gain > 0.5 -- and a root line
 void write_gain_branch_origins(std::ostream& ost, const gain_branch_origins& t, const std::vector<std::string>& node_names, size_t root);
+
+// ---------------------------------------------------------------- the driver's command line (driver_options.cpp; no HIP library)
+struct driver_options {
+    std::string tree_path, fam_path, lambda_tree_path, multi, err_path, rootdist_path, family_out, out_dir;
+    std::string pvalues_out, pvalues_cond;
+    int simulate_n = -1;                         // -1: estimation; >= 0: simulation (0 = no count given)
+    bool simulate_on_device = false;
+    size_t sim_workspace = 0;
+    int pvalue_sims = 0, force_m = -1, force_r = -1;
+    bool do_reconstruct = false, pvalues_on_device = false;
+    bool do_marginal = false;                    // --reconstruct-marginal [LEVEL]
+    double marginal_level = 0.95;
+    int history_draws = 0;                       // --sample-histories N
+    bool do_histories = false, have_history_seed = false;
+    uint64_t history_seed = 1;                   // --sample-seed S; else -s; else this
+    double test_pvalue = 0.05;                   // input_parameters::pvalue default (io.h)
+    long limit = -1;
+    double fixed_lambda = 0, fixed_alpha = -1, poisson = 0;
+    int k = 1, device = 0, max_iter = 300, reps = 1, n_gpus = 1;
+    bool use_err = false, use_poisson = false, keep_all = false;
+    bool per_family = false, gpus_given = false, alpha_given = false;      // -b: one lambda (vector) per family
+    std::string mu_list;                         // --mu: fixed death rates, one per lambda
+    bool estimate_mu = false;                    // --estimate-mu: death rates searched with the lambdas
+    std::string family_mu;                       // --family-mu (with -b): rates, or "estimate"
+    bool do_standard_errors = false, do_events = false, do_rate_shift = false, do_leaf_predictive = false;
+    bool do_branch_change = false;               // --branch-change [D]
+    int branch_change_band = 10;
+    std::string missing_list, mask_path;         // --missing TOKENS, --mask-cells FILE: cells whose count is unknown
+    bool root_sum = false;                       // --root-sum: score under CAFE_ROOT_SUM
+    bool estimate_rootdist = false;              // --estimate-rootdist [ROUNDS]
+    int rootdist_rounds = 10;
+    std::string rootdist_probs;                  // --rootdist-probs FILE
+    unsigned seed = 0;
+    bool have_seed = false;
+    bool gain = false, estimate_gain = false, root_absent_given = false, gain_unconditional = false, gain_posterior = false,
+         gain_dense = false, gain_scaled = false;              // --gain NU, --estimate-gain, --root-absent P0, --gain-*
+    double gain_nu = 0, root_absent = 0;
+    int search_batch = 1;                        // --search-batch G: look-ahead search, G points per device call
+    bool search_batch_given = false;
+    bool gain_run() const { return gain || estimate_gain; }
+    bool gamma() const { return fixed_alpha > 0 || k > 1; }  // build_models (core.cpp:26)
+};
+// argv into o; false at an unknown option or an option without its value (the caller prints the usage and exits with 2)
+bool parse_options(int argc, char** argv, driver_options& o);
+gain_request gain_request_of(const driver_options& o);
+// Why the run is refused, before any file is read or the device touched: the first reason in the documented order, nullptr when
+// there is none, or driver_usage_exit (compare the pointer) where the driver prints its usage and exits with 2 instead
+extern const char* const driver_usage_exit;
+const char* driver_refusal(const driver_options& o);
+// What follows an accepted command line: --sample-seed falls back to -s, -b clears -l / -m (warning on stderr), -s seeds randomizer_engine
+void normalise_options(driver_options& o);
+// "V1,V2,.." -> rates
+std::vector<double> parse_rates(const std::string& list);
+
+// ---------------------------------------------------------------- the driver's modes (driver.cpp; needs the HIP library)
+// Tree, [families, mask,] error model, lambda tree, lambdas, rootdist, opened in that order; with the families also the root
+// filter, --limit and the prior.  Throws what the driver prints.
+void load_inputs(const driver_options& o, bool with_families, user_data& d);
+// build_models (core.cpp:16-50): gamma iff -a > 0 or -k > 1, the default error model for -e without a file, and what the
+// options set on the model before any call (device, search batch, root rule, the prior --estimate-rootdist replaces, --mu)
+struct driver_model {
+    std::unique_ptr<error_model> default_em;
+    error_model* em = nullptr;
+    std::unique_ptr<hip_model_base> mdl;
+    file_probability_distribution* em_prior = nullptr;       // owned by user_data::p_prior
+};
+void build_model(const driver_options& o, user_data& d, driver_model& m);
+int run_simulation(const driver_options& o);                 // loads its own inputs, behind the simulator's checks; prints its own failure
+void run_gain_model(const driver_options& o, user_data& d, driver_model& m);
+void run_lambda_per_family(const driver_options& o, user_data& d, driver_model& m);
+void run_fitted_model(const driver_options& o, user_data& d, driver_model& m);
 
 }  // namespace cafe

@@ -281,7 +281,139 @@ static void test_poisson_scorer() {                           // test.cpp:2270-2
     CLOSE(fitted.poisson_lambda(), (0 + 1 + 2 + 3) / 4.0, 1e-3);
 }
 
+// ---------------------------------------------------------------- the driver's command line (driver_options.cpp)
+static driver_options parsed(std::vector<std::string> words, bool* ok = nullptr) {
+    words.insert(words.begin(), "cafexp_hip");
+    std::vector<char*> argv;
+    for (std::string& w : words) argv.push_back(&w[0]);
+    driver_options o;
+    const bool good = parse_options((int)argv.size(), argv.data(), o);
+    if (ok) *ok = good;
+    return o;
+}
+static driver_options estimation(std::vector<std::string> more) {        // "-t x -i y" and the rest
+    more.insert(more.begin(), {"-t", "x", "-i", "y"});
+    return parsed(more);
+}
+static bool refused(const driver_options& o, const std::string& why) {
+    const char* got = driver_refusal(o);
+    if (got && got != driver_usage_exit && why == got) return true;
+    std::printf("  refusal: got \"%s\", expected \"%s\"\n", got ? got : "(none)", why.c_str());
+    return false;
+}
+
+static void test_parse_options() {
+    bool ok = false;
+    driver_options o = parsed({"-t", "T", "-i", "F", "--estimate-rootdist", "-e", "--sizes", "40,30", "-s", "7", "--branch-change", "-P", "0.1"}, &ok);
+    CHECK(ok && o.tree_path == "T" && o.fam_path == "F");
+    CHECK(o.estimate_rootdist && o.root_sum && o.rootdist_rounds == 10);         // --estimate-rootdist implies --root-sum
+    CHECK(o.use_err && o.err_path.empty());                                      // -e without FILE: epsilon is estimated
+    CHECK(o.force_m == 40 && o.force_r == 30 && o.have_seed && o.seed == 7);
+    CHECK(o.do_branch_change && o.branch_change_band == 10 && o.test_pvalue == 0.1);      // -P is not read as D
+    o = parsed({"--estimate-rootdist", "3", "-e", "E", "--branch-change", "4", "--simulate", "--reconstruct-marginal", "0.5"}, &ok);
+    CHECK(ok && o.rootdist_rounds == 3 && o.err_path == "E" && o.branch_change_band == 4 && o.simulate_n == 0 && o.marginal_level == 0.5);
+    const driver_options defaults;
+    CHECK(defaults.simulate_n == -1 && defaults.k == 1 && defaults.max_iter == 300 && defaults.n_gpus == 1 && defaults.reps == 1 && defaults.limit == -1);
+    CHECK(defaults.fixed_alpha == -1 && defaults.marginal_level == 0.95 && defaults.test_pvalue == 0.05 && defaults.history_seed == 1 && defaults.search_batch == 1);
+    parsed({"-t", "T", "--no-such-option"}, &ok);
+    CHECK(!ok);                                                                  // the usage exit: an unknown option ...
+    parsed({"-t", "T", "-i"}, &ok);
+    CHECK(!ok);                                                                  // ... and an option without its value
+    parsed({"--sizes"}, &ok);
+    CHECK(!ok);
+    CHECK(driver_refusal(parsed({"-i", "y"})) == driver_usage_exit && driver_refusal(parsed({"-t", "x"})) == driver_usage_exit);
+    CHECK(driver_refusal(parsed({"--simulate", "-i", "y", "--standard-errors"})) == driver_usage_exit);      // before the --simulate refusals
+    CHECK(driver_refusal(estimation({})) == nullptr && driver_refusal(parsed({"-t", "x", "--simulate", "5"})) == nullptr);
+}
+
+static void test_driver_refusals() {
+    struct row { const char* flag; std::vector<std::string> args; bool simulate_refuses; };
+    const std::vector<row> reports = {
+        {"--standard-errors", {"--standard-errors"}, true}, {"--rate-shift-scan", {"--rate-shift-scan"}, true},
+        {"--reconstruct-marginal", {"--reconstruct-marginal"}, false}, {"--expected-events", {"--expected-events"}, true},
+        {"--leaf-predictive", {"--leaf-predictive"}, true}, {"--branch-change", {"--branch-change"}, true},
+        {"--estimate-rootdist", {"--estimate-rootdist"}, false}, {"--sample-histories", {"--sample-histories", "5"}, false},
+    };
+    for (const row& r : reports) {
+        std::vector<std::string> a = r.args;
+        a.insert(a.end(), {"--gpus", "2"});
+        CHECK(refused(estimation(a), std::string(r.flag) + " runs on one GPU: --gpus is not supported with it"));
+        a = r.args; a.push_back("-b");
+        CHECK(refused(estimation(a), std::string(r.flag) + " needs one fitted model: -b is not supported with it"));
+        a = r.args; a.insert(a.end(), {"-t", "x", "--simulate", "10", "-l", "0.01"});
+        if (r.simulate_refuses) CHECK(refused(parsed(a), std::string(r.flag) + " belongs to a fitted model: --simulate is not supported with it"));
+        else CHECK(driver_refusal(parsed(a)) == nullptr);        // marginal, rootdist and histories are ignored by --simulate
+        CHECK(driver_refusal(estimation(r.args)) == nullptr);
+    }
+    // the range checks
+    CHECK(refused(estimation({"--reconstruct-marginal", "1"}), "--reconstruct-marginal: LEVEL must lie in (0, 1)"));
+    CHECK(refused(estimation({"--reconstruct-marginal", "0"}), "--reconstruct-marginal: LEVEL must lie in (0, 1)"));
+    driver_options o = estimation({"--branch-change"});
+    o.branch_change_band = -1;                                   // (a negative D cannot be typed: it reads as an option)
+    CHECK(refused(o, "--branch-change: D must not be negative"));
+    CHECK(refused(estimation({"--branch-change", "3", "-P", "1"}), "--branch-change: PVALUE (-P) must lie in (0, 1)"));
+    CHECK(refused(estimation({"--branch-change", "-P", "0"}), "--branch-change: PVALUE (-P) must lie in (0, 1)"));
+    o = estimation({"--estimate-rootdist"});
+    o.rootdist_rounds = -1;
+    CHECK(refused(o, "--estimate-rootdist: ROUNDS must not be negative"));
+    CHECK(driver_refusal(estimation({"--estimate-rootdist", "0"})) == nullptr);
+    CHECK(refused(estimation({"--sample-histories", "0"}), "--sample-histories: N must lie in 1..65536"));
+    CHECK(refused(estimation({"--sample-histories", "65537"}), "--sample-histories: N must lie in 1..65536"));
+    CHECK(driver_refusal(estimation({"--sample-histories", "65536"})) == nullptr);
+    CHECK(refused(estimation({"--sample-histories", "5", "--reconstruct-marginal", "2"}), "--reconstruct-marginal: LEVEL must lie in (0, 1)"));
+    o = estimation({"--sample-histories", "5"});
+    o.marginal_level = 2;                                        // (LEVEL without --reconstruct-marginal: only the histories read it)
+    CHECK(refused(o, "--sample-histories: LEVEL must lie in (0, 1)"));
+    CHECK(driver_refusal(estimation({"--leaf-predictive", "-P", "7"})) == nullptr);       // -P is range-checked by --branch-change only
+    // the order: of two conflicts the earlier block's text
+    CHECK(refused(estimation({"--expected-events", "--gpus", "2", "--standard-errors", "-b"}), "--standard-errors runs on one GPU: --gpus is not supported with it"));
+    CHECK(refused(estimation({"--expected-events", "--standard-errors", "-b"}), "--standard-errors needs one fitted model: -b is not supported with it"));
+    CHECK(refused(estimation({"-b", "--mu", "0.1", "--search-batch", "1"}), "--search-batch: G must be at least 2"));
+    CHECK(refused(estimation({"-b", "--mu", "0.1"}), "-b runs the lambda = mu kernel: --mu / --estimate-mu are not supported with it"));
+    CHECK(refused(estimation({"--search-batch", "1", "--standard-errors", "-b", "--gain-scaled"}), "--gain-scaled is the scaled mode of the dense prune: give --gain-dense with it"));
+    CHECK(refused(estimation({"--gain", "0.1", "-b", "--mu", "0.1"}), "the gain model shares its rates over the table: -b is not supported with --gain / --estimate-gain"));
+    CHECK(refused(parsed({"--gain", "0.1", "--simulate"}), "the simulator has no gain rate: --simulate is not supported with --gain / --estimate-gain"));      // (before the usage exit)
+    CHECK(refused(estimation({"--sample-histories", "0", "--branch-change", "--gpus", "2"}), "--branch-change runs on one GPU: --gpus is not supported with it"));
+    CHECK(refused(estimation({"-b", "-k", "2", "--family-mu", "0.1", "--estimate-rootdist"}), "--estimate-rootdist needs one fitted model: -b is not supported with it"));
+    CHECK(refused(estimation({"--missing", "NA", "--reconstruct", "--mu", "0.1", "--estimate-mu"}),
+                  "--reconstruct reads every leaf count: it is not supported on a table with missing cells (--missing / --mask-cells)"));
+    // --simulate tries the reports in its own order, behind its own two refusals
+    CHECK(refused(parsed({"-t", "x", "--simulate", "--rate-shift-scan", "--expected-events"}), "--expected-events belongs to a fitted model: --simulate is not supported with it"));
+    CHECK(refused(parsed({"-t", "x", "--simulate", "--branch-change", "--leaf-predictive"}), "--leaf-predictive belongs to a fitted model: --simulate is not supported with it"));
+    CHECK(refused(parsed({"-t", "x", "--simulate", "--standard-errors", "--estimate-mu"}), "--simulate draws under given rates: --estimate-mu is not supported with it (give --mu)"));
+    CHECK(refused(parsed({"-t", "x", "--simulate", "--standard-errors", "--family-mu", "0.1"}), "--family-mu sets the death rates of -b: it is not supported without -b"));
+    CHECK(refused(parsed({"-t", "x", "--simulate", "--search-batch", "4"}), "--search-batch drives a search: --simulate is not supported with it"));
+    CHECK(driver_refusal(parsed({"-t", "x", "--simulate", "-b", "--gpus", "2", "--missing", ",", "--mu", "0.1"})) == nullptr);       // none of the estimation's blocks is tried
+    // the other blocks
+    CHECK(refused(estimation({"--search-batch", "17", "-k", "2"}), "--search-batch: G x K (the -k categories) must not exceed 32"));
+    CHECK(refused(estimation({"--search-batch", "4", "--gpus", "2"}), "--search-batch scores its points in one call on one GPU: --gpus N > 1 is not supported with it"));
+    CHECK(refused(estimation({"--search-batch", "4", "-b"}), "--search-batch drives the search of one fitted model: -b is not supported with it"));
+    CHECK(refused(estimation({"--missing", ","}), "--missing: TOKENS must name at least one spelling, e.g. NA,?,-"));
+    CHECK(refused(estimation({"--mask-cells", "m", "--gain", "0.1", "--gain-dense", "--reconstruct-marginal"}),
+                  "the gain model's --reconstruct-marginal summarises every leaf at its observed count: it is not supported with --missing / --mask-cells"));
+    CHECK(refused(estimation({"--mu", "0.1", "--estimate-mu"}), "--mu fixes the death rates and --estimate-mu searches them: give one of the two"));
+    CHECK(refused(estimation({"--estimate-mu", "-l", "0.1"}), "--estimate-mu searches lambda and mu together: -l / -m are not supported with it"));
+    CHECK(refused(estimation({"--family-mu", "estimate"}), "--family-mu sets the death rates of -b: it is not supported without -b"));
+    CHECK(refused(estimation({"-b", "-a", "1"}), "-b estimates one lambda per family under the base model; -k > 1 and -a are not supported with it"));
+    CHECK(refused(estimation({"-b", "-e"}), "-b with -e needs an error model file: estimating epsilon per family is not supported"));
+    CHECK(refused(estimation({"-b", "--gpus", "1"}), "-b runs on one GPU: --gpus is not supported with it"));
+    CHECK(driver_refusal(estimation({"-b", "-e", "E", "--family-mu", "0.1", "--missing", "NA"})) == nullptr);
+    // what follows an accepted command line
+    o = estimation({"-s", "11", "--sample-histories", "5", "-b", "-l", "0.1"});
+    const gain_request g = gain_request_of(o);
+    CHECK(g.per_family && g.histories && !g.gain && !g.gpus && !g.simulate && !g.estimate_error);
+    normalise_options(o);                                        // (warns on stderr that -l is ignored)
+    CHECK(o.history_seed == 11 && o.fixed_lambda == 0 && o.multi.empty());
+    std::mt19937 same(11);
+    CHECK(randomizer_engine() == same());                        // -s seeded the engine
+    o = estimation({"-s", "11", "--sample-histories", "5", "--sample-seed", "3"});
+    normalise_options(o);
+    CHECK(o.history_seed == 3);
+}
+
 int main() {
+    test_parse_options();
+    test_driver_refusals();
     test_poisson_scorer();
     test_reconstruction_reports();
     test_pvalue();
