@@ -144,27 +144,109 @@ class CafeSimProblem(C.Structure):
     ]
 
 
-EXPORTS = [
-    "cafe_abi_version", "cafe_create", "cafe_destroy", "cafe_last_error", "cafe_score", "cafe_score_partial",
-    "cafe_finish_partial", "cafe_family_results", "cafe_get_matrix", "cafe_get_root_likelihoods", "cafe_get_stats",
-    "cafe_matrix_size", "cafe_build_matrices", "cafe_probe_fp64_mfma", "cafe_set_profiling", "cafe_debug_stamps",
-    "cafe_root_max", "cafe_reconstruct", "cafe_branch_probabilities", "cafe_pvalues", "cafe_debug_force_tile",
-    "cafe_comm_unique_id", "cafe_comm_attach", "cafe_comm_detach", "cafe_shard_plan", "cafe_shard_plan_scaled", "cafe_create_sharded",
-    "cafe_sharded_destroy", "cafe_sharded_last_error", "cafe_sharded_score", "cafe_sharded_family_results",
-    "cafe_sharded_size", "cafe_sharded_context", "cafe_set_graphs", "cafe_executed_flops", "cafe_debug_tile_range_flops", "cafe_get_extents", "cafe_debug_launch_flops", "cafe_debug_launch_ms", "cafe_debug_plan_check",
-    "cafe_debug_fail_next", "cafe_debug_column_extents", "cafe_debug_panel_bounds", "cafe_debug_k_ranges", "cafe_issued_flops", "cafe_debug_leaf_transposes", "cafe_simulate",
-    "cafe_score_per_family", "cafe_marginal_reconstruct", "cafe_debug_marginal_gemm", "cafe_sample_histories", "cafe_debug_history_batches",
-    "cafe_set_death_rates", "cafe_bd_rates", "cafe_build_matrices_lm", "cafe_score_per_family_lm", "cafe_simulate_lm",
-    "cafe_score_gradient", "cafe_bd_rates_grad", "cafe_expected_events", "cafe_bd_rates_events",
-    "cafe_branch_scores", "cafe_branch_scores_dim", "cafe_weighted_gram", "cafe_debug_gram",
-    "cafe_leaf_predictive", "cafe_set_root_rule", "cafe_get_root_rule", "cafe_root_posterior", "cafe_debug_magnitude_tables", "cafe_debug_level_tiles",
-    "cafe_branch_change", "cafe_debug_branch_change_band", "cafe_score_batch",
-    "cafe_score_per_family_gain", "cafe_bd_gain_row0", "cafe_debug_narrowed_extents", "cafe_gain_posterior",
-    "cafe_debug_pvalues_stages", "cafe_debug_sort_rows", "cafe_debug_tree_pvalue",
-    "cafe_score_gain", "cafe_debug_gain_dense",
-    "cafe_gain_posterior_dense", "cafe_debug_gain_dense_posterior", "cafe_set_gain_scaling", "cafe_gain_leaf_predictive", "cafe_debug_gain_predictive",
-    "cafe_gain_marginal_dense", "cafe_debug_gain_marginal", "cafe_gain_score_gradient", "cafe_debug_gain_gradient",
-]
+# Every entry point of include/cafe_mi355x.h, in the header's order: name -> (restype, argtypes).  load() applies the table and
+# tests/test_capi_signatures.py holds every row to the header's prototype.  _ctx is an opaque handle (cafe_ctx*, cafe_sharded*).
+_ctx, _str, _int, _size = C.c_void_p, C.c_char_p, C.c_int, C.c_size_t
+_i32, _i64, _u64, _f64 = C.c_int32, C.c_int64, C.c_uint64, C.c_double
+_problem, _sim, _params = C.POINTER(CafeProblem), C.POINTER(CafeSimProblem), C.POINTER(CafeParams)
+_family_out = C.POINTER(CafeFamilyOut)
+_profile = (_int, [_ctx, _f64p, _f64p])                                            # (ctx, ms[kinds], flops)
+_shared_rates = [_ctx, _params, _f64p, _f64p, _f64p, _f64, _i64, _i64p]            # (ctx, params, lambdas, mus, nus, root_absent, n, family)
+_SIGNATURES = {
+    "cafe_create": (_ctx, [_problem, _str, _size]),
+    "cafe_destroy": (None, [_ctx]),
+    "cafe_last_error": (_str, [_ctx]),
+    "cafe_abi_version": (_int, []),
+    "cafe_score": (_int, [_ctx, _params, _f64p, _family_out]),
+    "cafe_score_batch": (_int, [_ctx, C.POINTER(CafeBatchParams), _f64p]),
+    "cafe_score_partial": (_int, [_ctx, _params, C.c_void_p, C.c_void_p]),         # device_partial is a device address, never a host array
+    "cafe_finish_partial": (_f64, [_f64p]),
+    "cafe_comm_unique_id": (_int, [_str]),
+    "cafe_comm_attach": (_int, [_ctx, _str, _i32, _i32]),
+    "cafe_comm_detach": (_int, [_ctx]),
+    "cafe_shard_plan": (_int, [_problem, _i32, _i64p, _i64p]),
+    "cafe_shard_plan_scaled": (_int, [_problem, _i32, _f64p, _i64p, _i64p]),
+    "cafe_create_sharded": (_ctx, [_problem, _i32p, _i32, _str, _size]),
+    "cafe_sharded_destroy": (None, [_ctx]),
+    "cafe_sharded_last_error": (_str, [_ctx]),
+    "cafe_sharded_score": (_int, [_ctx, _params, _f64p, _family_out]),
+    "cafe_sharded_family_results": (_int, [_ctx, _family_out]),
+    "cafe_sharded_size": (_i32, [_ctx]),
+    "cafe_sharded_context": (_ctx, [_ctx, _i32]),
+    "cafe_family_results": (_int, [_ctx, _family_out]),
+    "cafe_root_max": (_int, [_ctx, _params, _f64p]),
+    "cafe_pvalues": (_int, [_ctx, _params, _i32, _u64, _f64p]),
+    "cafe_simulate": (_int, [_sim, _u64, _i32p, _i32p, _str, _size]),
+    "cafe_simulate_lm": (_int, [_sim, _f64p, _u64, _i32p, _i32p, _str, _size]),
+    "cafe_score_per_family": (_int, [_ctx, _params, _i64, _i64p, _f64p, _f64p]),
+    "cafe_score_per_family_lm": (_int, [_ctx, _params, _i64, _i64p, _f64p, _f64p, _f64p]),
+    "cafe_score_per_family_gain": (_int, [_ctx, _params, _i64, _i64p, _f64p, _f64p, _f64p, _f64, _f64p]),
+    "cafe_score_gain": (_int, _shared_rates + [_f64p]),
+    "cafe_debug_gain_dense": _profile,
+    "cafe_bd_gain_row0": (_int, [_f64, _f64, _f64, _f64, _i32, _f64p, _f64p]),
+    "cafe_gain_posterior": (_int, [_ctx, _params, _i64, _i64p, _f64p, _f64p, _f64p, _f64, C.POINTER(CafeGainPosteriorOut)]),
+    "cafe_gain_posterior_dense": (_int, _shared_rates + [C.POINTER(CafeGainPosteriorOut)]),
+    "cafe_debug_gain_dense_posterior": _profile,
+    "cafe_gain_leaf_predictive": (_int, _shared_rates + [C.POINTER(CafeGainLeafPredictiveOut)]),
+    "cafe_debug_gain_predictive": _profile,
+    "cafe_gain_marginal_dense": (_int, _shared_rates[:6] + [_f64] + _shared_rates[6:] + [C.POINTER(CafeGainMarginalOut)]),   # level after root_absent
+    "cafe_debug_gain_marginal": _profile,
+    "cafe_gain_score_gradient": (_int, _shared_rates + [C.POINTER(CafeGainGradientOut)]),
+    "cafe_debug_gain_gradient": _profile,
+    "cafe_set_gain_scaling": (_int, [_ctx, _int]),
+    "cafe_set_death_rates": (_int, [_ctx, _f64p]),
+    "cafe_bd_rates": (_int, [_f64, _f64, _f64, _f64p]),
+    "cafe_reconstruct": (_int, [_ctx, _params, _f32p, _i32p]),
+    "cafe_branch_probabilities": (_int, [_ctx, _params, _i32p, _f64p]),
+    "cafe_marginal_reconstruct": (_int, [_ctx, _params, _f64, C.POINTER(CafeMarginalOut)]),
+    "cafe_debug_marginal_gemm": (_int, [_ctx, _f64p, _f64p]),
+    "cafe_sample_histories": (_int, [_ctx, _params, _i32, _u64, C.POINTER(CafeHistoryOut)]),
+    "cafe_debug_history_batches": (_int, [_ctx, _i32p, _i32p]),
+    "cafe_score_gradient": (_int, [_ctx, _params, _i32, C.POINTER(CafeGradientOut)]),
+    "cafe_bd_rates_grad": (_int, [_f64, _f64, _f64, _f64p]),
+    "cafe_branch_scores": (_int, [_ctx, _params, _i32, C.POINTER(CafeBranchScoresOut)]),
+    "cafe_branch_scores_dim": (_int, [_ctx, _params, _i32p]),
+    "cafe_debug_gram": (_int, [_ctx, _f64p, _f64p]),
+    "cafe_expected_events": (_int, [_ctx, _params, C.POINTER(CafeEventsOut)]),
+    "cafe_bd_rates_events": (_int, [_f64, _f64, _f64, _f64p]),
+    "cafe_leaf_predictive": (_int, [_ctx, _params, C.POINTER(CafeLeafPredictiveOut)]),
+    "cafe_branch_change": (_int, [_ctx, _params, _i32, _f64, C.POINTER(CafeBranchChangeOut)]),
+    "cafe_debug_branch_change_band": (_int, [_ctx, _f64p]),
+    "cafe_set_root_rule": (_int, [_ctx, _i32]),
+    "cafe_get_root_rule": (_int, [_ctx]),
+    "cafe_root_posterior": (_int, [_ctx, _params, C.POINTER(CafeRootPosteriorOut)]),
+    "cafe_get_matrix": (_int, [_ctx, _i32, _i32, _f64p, _size]),
+    "cafe_get_root_likelihoods": (_int, [_ctx, _i64, _i32, _f64p, _size]),
+    "cafe_get_extents": (_int, [_ctx, _i32, _i32, _i32p, _size, _i32p, _size, _i32p]),
+    "cafe_debug_column_extents": (_int, [_ctx, _i32, _i32, _i32p, _size, _i64p]),
+    "cafe_debug_panel_bounds": (_int, [_ctx, _i32, _i32, _f64p, _size, _i32p, _i32p]),
+    "cafe_debug_narrowed_extents": (_int, [_ctx, _i32, _i32, _i32p, _size, _i32p]),
+    "cafe_debug_magnitude_tables": (_int, [_ctx, _i32, _i32, _i32p, _size, _i32p, _i32p, _i32, _i32]),
+    "cafe_debug_level_tiles": (_int, [_ctx, _int]),
+    "cafe_debug_k_ranges": (_int, [_ctx, _i32, _i32, _i32p, _size, _i32p, _i32p]),
+    "cafe_debug_leaf_transposes": (_int, [_ctx, _i32p, _i32p]),
+    "cafe_get_stats": (_int, [_ctx, C.POINTER(CafeStats)]),
+    "cafe_executed_flops": (_int, [_ctx, _f64p]),
+    "cafe_issued_flops": (_int, [_ctx, _f64p]),
+    "cafe_debug_tile_range_flops": (_int, [_ctx, _f64p]),
+    "cafe_debug_launch_flops": (_int, [_ctx, _f64p, _f64p, _i32p, _size]),
+    "cafe_debug_launch_ms": (_int, [_ctx, _f64p, _size]),
+    "cafe_debug_plan_check": (_int, [_ctx, _i32p, _f64p]),
+    "cafe_matrix_size": (_int, [_ctx]),
+    "cafe_set_profiling": (_int, [_ctx, _int]),
+    "cafe_set_graphs": (_int, [_ctx, _int]),
+    "cafe_debug_force_tile": (_int, [_ctx, _int]),
+    "cafe_debug_fail_next": (_int, [_ctx, _int]),
+    "cafe_debug_stamps": (_int, [_ctx, C.POINTER(_u64), _size]),
+    "cafe_debug_pvalues_stages": (_int, [_ctx, _params, _i32, _u64, C.POINTER(CafePvalueStages), _f64p]),
+    "cafe_build_matrices": (_int, [_i32, _i32, _i32, _f64p, _f64p, _i32, _f64p]),
+    "cafe_build_matrices_lm": (_int, [_i32, _i32, _i32, _f64p, _f64p, _f64p, _i32, _f64p]),
+    "cafe_debug_sort_rows": (_int, [_i32, _f64p, _i32, _i32]),
+    "cafe_debug_tree_pvalue": (_int, [_i32, _f64p, _i64, _f64p, _i32, _i32, _f64p]),
+    "cafe_weighted_gram": (_int, [_i32, _i32, _i64, _f64p, _f64p, _f64p, _f64p]),
+    "cafe_probe_fp64_mfma": (_int, [_i32, _f64p]),
+}
+EXPORTS = list(_SIGNATURES)
 CAFE_CHANGE_NONE = -(1 << 31)   # mode / lo / hi of cafe_branch_change at the root and in a failed family
 CAFE_COMM_ID_BYTES = 128
 MAG_NONE = -(1 << 28)           # a magnitude-table entry whose items are all exactly zero (cafe_kernels.h, kMagNone)
@@ -193,162 +275,9 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise CafeError("%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950)" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    L.cafe_abi_version.restype = C.c_int
-    L.cafe_create.restype = C.c_void_p
-    L.cafe_create.argtypes = [C.POINTER(CafeProblem), C.c_char_p, C.c_size_t]
-    L.cafe_destroy.argtypes = [C.c_void_p]
-    L.cafe_destroy.restype = None
-    L.cafe_last_error.restype = C.c_char_p
-    L.cafe_last_error.argtypes = [C.c_void_p]
-    L.cafe_score.restype = C.c_int
-    L.cafe_score.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p, C.POINTER(CafeFamilyOut)]
-    L.cafe_score_batch.restype = C.c_int
-    L.cafe_score_batch.argtypes = [C.c_void_p, C.POINTER(CafeBatchParams), _f64p]
-    L.cafe_score_partial.restype = C.c_int
-    L.cafe_score_partial.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_void_p, C.c_void_p]
-    L.cafe_finish_partial.restype = C.c_double
-    L.cafe_finish_partial.argtypes = [_f64p]
-    L.cafe_family_results.restype = C.c_int
-    L.cafe_family_results.argtypes = [C.c_void_p, C.POINTER(CafeFamilyOut)]
-    L.cafe_get_matrix.restype = C.c_int
-    L.cafe_get_matrix.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _f64p, C.c_size_t]
-    L.cafe_get_root_likelihoods.restype = C.c_int
-    L.cafe_get_root_likelihoods.argtypes = [C.c_void_p, C.c_int64, C.c_int32, _f64p, C.c_size_t]
-    L.cafe_root_max.restype = C.c_int
-    L.cafe_root_max.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p]
-    L.cafe_score_per_family.restype = C.c_int
-    L.cafe_score_per_family.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p]
-    L.cafe_score_per_family_lm.restype = C.c_int
-    L.cafe_score_per_family_lm.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p, _f64p]
-    L.cafe_marginal_reconstruct.restype = C.c_int
-    L.cafe_marginal_reconstruct.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_double, C.POINTER(CafeMarginalOut)]
-    L.cafe_sample_histories.restype = C.c_int
-    L.cafe_sample_histories.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.c_uint64, C.POINTER(CafeHistoryOut)]
-    L.cafe_debug_marginal_gemm.restype = C.c_int
-    L.cafe_debug_marginal_gemm.argtypes = [C.c_void_p, _f64p, _f64p]
-    L.cafe_pvalues.restype = C.c_int
-    L.cafe_pvalues.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.c_uint64, _f64p]
-    L.cafe_reconstruct.restype = C.c_int
-    L.cafe_reconstruct.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f32p, _i32p]
-    L.cafe_branch_probabilities.restype = C.c_int
-    L.cafe_branch_probabilities.argtypes = [C.c_void_p, C.POINTER(CafeParams), _i32p, _f64p]
-    L.cafe_get_stats.restype = C.c_int
-    L.cafe_get_stats.argtypes = [C.c_void_p, C.POINTER(CafeStats)]
-    L.cafe_matrix_size.restype = C.c_int
-    L.cafe_matrix_size.argtypes = [C.c_void_p]
-    L.cafe_build_matrices.restype = C.c_int
-    L.cafe_build_matrices.argtypes = [C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, C.c_int32, _f64p]
-    L.cafe_build_matrices_lm.restype = C.c_int
-    L.cafe_build_matrices_lm.argtypes = [C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, C.c_int32, _f64p]
-    L.cafe_set_death_rates.restype = C.c_int
-    L.cafe_set_death_rates.argtypes = [C.c_void_p, _f64p]
-    L.cafe_score_per_family_gain.restype = C.c_int
-    L.cafe_score_per_family_gain.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p, _f64p, C.c_double, _f64p]
-    L.cafe_score_gain.restype = C.c_int
-    L.cafe_score_gain.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p, _f64p, _f64p, C.c_double, C.c_int64, _i64p, _f64p]
-    L.cafe_debug_gain_dense.restype = C.c_int
-    L.cafe_debug_gain_dense.argtypes = [C.c_void_p, _f64p, _f64p]
-    L.cafe_gain_posterior.restype = C.c_int
-    L.cafe_gain_posterior.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int64, _i64p, _f64p, _f64p, _f64p, C.c_double,
-                                      C.POINTER(CafeGainPosteriorOut)]
-    L.cafe_gain_posterior_dense.restype = C.c_int
-    L.cafe_gain_posterior_dense.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p, _f64p, _f64p, C.c_double, C.c_int64, _i64p,
-                                            C.POINTER(CafeGainPosteriorOut)]
-    L.cafe_debug_gain_dense_posterior.restype = C.c_int
-    L.cafe_debug_gain_dense_posterior.argtypes = [C.c_void_p, _f64p, _f64p]
-    L.cafe_gain_leaf_predictive.restype = C.c_int
-    L.cafe_gain_leaf_predictive.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p, _f64p, _f64p, C.c_double, C.c_int64, _i64p,
-                                            C.POINTER(CafeGainLeafPredictiveOut)]
-    L.cafe_debug_gain_predictive.restype = C.c_int
-    L.cafe_debug_gain_predictive.argtypes = [C.c_void_p, _f64p, _f64p]
-    L.cafe_gain_marginal_dense.restype = C.c_int
-    L.cafe_gain_marginal_dense.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p, _f64p, _f64p, C.c_double, C.c_double, C.c_int64, _i64p,
-                                           C.POINTER(CafeGainMarginalOut)]
-    L.cafe_debug_gain_marginal.restype = C.c_int
-    L.cafe_debug_gain_marginal.argtypes = [C.c_void_p, _f64p, _f64p]
-    L.cafe_gain_score_gradient.restype = C.c_int
-    L.cafe_gain_score_gradient.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p, _f64p, _f64p, C.c_double, C.c_int64, _i64p,
-                                           C.POINTER(CafeGainGradientOut)]
-    L.cafe_debug_gain_gradient.restype = C.c_int
-    L.cafe_debug_gain_gradient.argtypes = [C.c_void_p, _f64p, _f64p]
-    L.cafe_set_gain_scaling.restype = C.c_int
-    L.cafe_set_gain_scaling.argtypes = [C.c_void_p, C.c_int]
-    L.cafe_bd_gain_row0.restype = C.c_int
-    L.cafe_bd_gain_row0.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _f64p, _f64p]
-    L.cafe_bd_rates.restype = C.c_int
-    L.cafe_bd_rates.argtypes = [C.c_double, C.c_double, C.c_double, _f64p]
-    L.cafe_score_gradient.restype = C.c_int
-    L.cafe_score_gradient.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.POINTER(CafeGradientOut)]
-    L.cafe_bd_rates_grad.restype = C.c_int
-    L.cafe_bd_rates_grad.argtypes = [C.c_double, C.c_double, C.c_double, _f64p]
-    L.cafe_expected_events.restype = C.c_int
-    L.cafe_expected_events.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.POINTER(CafeEventsOut)]
-    L.cafe_bd_rates_events.restype = C.c_int
-    L.cafe_bd_rates_events.argtypes = [C.c_double, C.c_double, C.c_double, _f64p]
-    L.cafe_leaf_predictive.restype = C.c_int
-    L.cafe_leaf_predictive.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.POINTER(CafeLeafPredictiveOut)]
-    L.cafe_branch_change.restype = C.c_int
-    L.cafe_branch_change.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.c_double, C.POINTER(CafeBranchChangeOut)]
-    L.cafe_debug_branch_change_band.restype = C.c_int
-    L.cafe_debug_branch_change_band.argtypes = [C.c_void_p, _f64p]
-    L.cafe_set_root_rule.restype = C.c_int
-    L.cafe_set_root_rule.argtypes = [C.c_void_p, C.c_int32]
-    L.cafe_get_root_rule.restype = C.c_int
-    L.cafe_get_root_rule.argtypes = [C.c_void_p]
-    L.cafe_root_posterior.restype = C.c_int
-    L.cafe_root_posterior.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.POINTER(CafeRootPosteriorOut)]
-    L.cafe_branch_scores.restype = C.c_int
-    L.cafe_branch_scores.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.POINTER(CafeBranchScoresOut)]
-    L.cafe_branch_scores_dim.restype = C.c_int
-    L.cafe_branch_scores_dim.argtypes = [C.c_void_p, C.POINTER(CafeParams), _i32p]
-    L.cafe_debug_gram.restype = C.c_int
-    L.cafe_debug_gram.argtypes = [C.c_void_p, _f64p, _f64p]
-    L.cafe_weighted_gram.restype = C.c_int
-    L.cafe_weighted_gram.argtypes = [C.c_int32, C.c_int32, C.c_int64, _f64p, _f64p, _f64p, _f64p]
-    L.cafe_probe_fp64_mfma.restype = C.c_int
-    L.cafe_probe_fp64_mfma.argtypes = [C.c_int32, _f64p]
-    L.cafe_debug_stamps.restype = C.c_int
-    L.cafe_debug_stamps.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t]
-    L.cafe_debug_force_tile.restype = C.c_int
-    L.cafe_debug_force_tile.argtypes = [C.c_void_p, C.c_int]
-    L.cafe_set_profiling.restype = C.c_int
-    L.cafe_set_profiling.argtypes = [C.c_void_p, C.c_int]
-    L.cafe_set_graphs.restype = C.c_int
-    L.cafe_set_graphs.argtypes = [C.c_void_p, C.c_int]
-    L.cafe_get_extents.restype = C.c_int
-    L.cafe_get_extents.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _i32p, C.c_size_t, _i32p, C.c_size_t, _i32p]
-    L.cafe_debug_launch_flops.restype = C.c_int
-    L.cafe_debug_launch_flops.argtypes = [C.c_void_p, _f64p, _f64p, _i32p, C.c_size_t]
-    L.cafe_executed_flops.restype = C.c_int
-    L.cafe_executed_flops.argtypes = [C.c_void_p, _f64p]
-    L.cafe_comm_unique_id.restype = C.c_int
-    L.cafe_comm_unique_id.argtypes = [C.c_char_p]
-    L.cafe_comm_attach.restype = C.c_int
-    L.cafe_comm_attach.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32]
-    L.cafe_comm_detach.restype = C.c_int
-    L.cafe_comm_detach.argtypes = [C.c_void_p]
-    L.cafe_shard_plan.restype = C.c_int
-    L.cafe_shard_plan.argtypes = [C.POINTER(CafeProblem), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.cafe_create_sharded.restype = C.c_void_p
-    L.cafe_create_sharded.argtypes = [C.POINTER(CafeProblem), _i32p, C.c_int32, C.c_char_p, C.c_size_t]
-    L.cafe_sharded_destroy.restype = None
-    L.cafe_sharded_destroy.argtypes = [C.c_void_p]
-    L.cafe_sharded_last_error.restype = C.c_char_p
-    L.cafe_sharded_last_error.argtypes = [C.c_void_p]
-    L.cafe_sharded_score.restype = C.c_int
-    L.cafe_sharded_score.argtypes = [C.c_void_p, C.POINTER(CafeParams), _f64p, C.POINTER(CafeFamilyOut)]
-    L.cafe_sharded_family_results.restype = C.c_int
-    L.cafe_sharded_family_results.argtypes = [C.c_void_p, C.POINTER(CafeFamilyOut)]
-    L.cafe_sharded_size.restype = C.c_int32
-    L.cafe_sharded_size.argtypes = [C.c_void_p]
-    L.cafe_sharded_context.restype = C.c_void_p
-    L.cafe_sharded_context.argtypes = [C.c_void_p, C.c_int32]
-    L.cafe_debug_fail_next.restype = C.c_int
-    L.cafe_debug_fail_next.argtypes = [C.c_void_p, C.c_int]
-    L.cafe_simulate.restype = C.c_int
-    L.cafe_simulate.argtypes = [C.POINTER(CafeSimProblem), C.c_uint64, _i32p, _i32p, C.c_char_p, C.c_size_t]
-    L.cafe_simulate_lm.restype = C.c_int
-    L.cafe_simulate_lm.argtypes = [C.POINTER(CafeSimProblem), _f64p, C.c_uint64, _i32p, _i32p, C.c_char_p, C.c_size_t]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -357,11 +286,57 @@ def _p(a, t):
     return a.ctypes.data_as(t) if a is not None else None
 
 
-def _c_problem(pb: Problem, keep: list, max_categories: int = 1, device: int = 0, flags: int = 0, workspace_limit: int = 0) -> CafeProblem:
+def _keeper(keep: list):
+    """k(a, dtype): `a` as a contiguous array of that dtype, held in `keep` for as long as a C struct points at it"""
     def k(a, dt):
         a = np.ascontiguousarray(a, dtype=dt)
         keep.append(a)
         return a
+    return k
+
+
+def _out(cls, res: dict):
+    """An out struct of class `cls` whose every field named in `res` points at that array; the other fields stay null, which
+    the library reads as "not asked for".  A key that is no field, or an array of another dtype than the field's, is refused."""
+    types = dict(cls._fields_)
+    out = cls()
+    for name, array in res.items():
+        if name not in types:
+            raise CafeError("%s has no field %r" % (cls.__name__, name))
+        if array.dtype != np.dtype(types[name]._type_):
+            raise CafeError("%s.%s takes %s, not %s" % (cls.__name__, name, np.dtype(types[name]._type_), array.dtype))
+        setattr(out, name, _p(array, types[name]))
+    return out
+
+
+def _base_params(lambdas):
+    """(cafe_params of the base model with these lambdas and nothing else, the array it points at)"""
+    lam = np.ascontiguousarray(lambdas, dtype=np.float64)
+    cp = CafeParams()
+    cp.model = CAFE_MODEL_BASE
+    cp.lambdas = _p(lam, _f64p)
+    cp.n_categories = 1
+    return cp, lam
+
+
+def _family_results(F: int, K: int):
+    """(the dict of family_results, the cafe_family_out that points into it)"""
+    res = {"family_lnl": np.empty(F), "failed": np.empty(F, dtype=np.int32)}
+    if K > 0:
+        res["category_likelihood"] = np.empty((F, K))
+        res["family_likelihood"] = np.empty(F)
+    return res, _out(CafeFamilyOut, res)
+
+
+def _call(name: str, *args):
+    """A library function that takes no context: its return code raises."""
+    rc = getattr(load(), name)(*args)
+    if rc:
+        raise CafeError("%s failed with code %d" % (name, rc))
+
+
+def _c_problem(pb: Problem, keep: list, max_categories: int = 1, device: int = 0, flags: int = 0, workspace_limit: int = 0) -> CafeProblem:
+    k = _keeper(keep)
     cp = CafeProblem()
     cp.n_nodes = pb.n_nodes
     cp.parent = _p(k(pb.parent, np.int32), _i32p)
@@ -385,11 +360,7 @@ def _c_problem(pb: Problem, keep: list, max_categories: int = 1, device: int = 0
 
 def _c_params(pr: Params, alpha: float = 1.0):
     keep = []
-
-    def k(a, dt):
-        a = np.ascontiguousarray(a, dtype=dt)
-        keep.append(a)
-        return a
+    k = _keeper(keep)
     cp = CafeParams()
     cp.model = CAFE_MODEL_GAMMA if pr.multipliers is not None else CAFE_MODEL_BASE
     cp.lambdas = _p(k(pr.lambdas, np.float64), _f64p)
@@ -415,13 +386,11 @@ def shard_plan(pb: Problem, n_shards: int, max_categories: int = 1, family_scale
     bounds = np.empty(n_shards + 1, dtype=np.int64)
     L = load()
     if family_scale is None:
-        rc = L.cafe_shard_plan(C.byref(cp), n_shards, order.ctypes.data_as(C.POINTER(C.c_int64)), bounds.ctypes.data_as(C.POINTER(C.c_int64)))
+        rc = L.cafe_shard_plan(C.byref(cp), n_shards, _p(order, _i64p), _p(bounds, _i64p))
     else:
         fs = np.ascontiguousarray(family_scale, dtype=np.float64)
         assert fs.shape == (pb.n_families,)
-        L.cafe_shard_plan_scaled.restype = C.c_int
-        L.cafe_shard_plan_scaled.argtypes = [C.POINTER(CafeProblem), C.c_int32, _f64p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        rc = L.cafe_shard_plan_scaled(C.byref(cp), n_shards, _p(fs, _f64p), order.ctypes.data_as(C.POINTER(C.c_int64)), bounds.ctypes.data_as(C.POINTER(C.c_int64)))
+        rc = L.cafe_shard_plan_scaled(C.byref(cp), n_shards, _p(fs, _f64p), _p(order, _i64p), _p(bounds, _i64p))
     if rc:
         raise CafeError("cafe_shard_plan failed with code %d" % rc)
     return [order[bounds[r]:bounds[r + 1]].copy() for r in range(n_shards)]
@@ -442,9 +411,7 @@ def rebalanced_plan(pb: Problem, plan, times, max_categories: int = 1, scale=Non
 
 def comm_unique_id() -> bytes:
     buf = C.create_string_buffer(CAFE_COMM_ID_BYTES)
-    rc = load().cafe_comm_unique_id(buf)
-    if rc:
-        raise CafeError("cafe_comm_unique_id failed with code %d" % rc)
+    _call("cafe_comm_unique_id", buf)
     return buf.raw
 
 
@@ -485,6 +452,54 @@ class Context:
 
     def _params(self, pr: Params, alpha: float = 1.0):
         return _c_params(pr, alpha)
+
+    def _rate_frame(self, family, lambdas, mus=None, nus=None, shared: bool = False, rates: int = 3):
+        """Contiguous (family int64 [n], lambdas, mus, nus) of a call that takes `rates` rates beside the params -- 1: lambdas, 2:
+        and mus, 3: and nus, where mus None stays None (mu = lambda); a rate the call does not take is None.  Every rate is
+        [n][n_lambdas], one row per listed family (a 1-d array is one rate per family), or with `shared` [n_lambdas] for all."""
+        fam = np.ascontiguousarray(family, dtype=np.int64).reshape(-1)
+        shape = (-1,) if shared else (len(fam), -1)
+        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(shape)
+        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(shape) if rates == 3 else None
+        mu = np.ascontiguousarray(mus, dtype=np.float64).reshape(shape) if rates == 2 or mus is not None else None
+        nl = self.problem.n_lambdas
+        if lam.shape[-1] != nl or (nu is not None and nu.shape != lam.shape) or (mu is not None and mu.shape != lam.shape):
+            what = ("lambdas", "lambdas and mus", "lambdas, mus and nus")[rates - 1]
+            raise ValueError("%s must be %s" % (what, "[%d]" % nl if shared else "[%d][%d]" % (len(fam), nl)))
+        return fam, lam, mu, nu
+
+    def _scalars(self, name: str, *lead):
+        """What the getter `name(ctx, lead..., T* a, U* b ...)` writes through its scalar pointers, as a list; T, U are the
+        signature table's."""
+        f = getattr(self._lib, name)
+        vals = [t._type_() for t in _SIGNATURES[name][1][1 + len(lead):]]
+        self._check(f(self._h, *lead, *[C.byref(v) for v in vals]))
+        return [v.value for v in vals]
+
+    def _sized(self, name: str, lead, tail=(), last=()):
+        """The array [n0][n1] + last of the reader `name(ctx, lead..., T* out, size_t out_len, int32_t* n0, int32_t* n1, tail...)`,
+        which is asked twice: with a null buffer for n0 and n1, then with a buffer of that size."""
+        f = getattr(self._lib, name)
+        ptr = _SIGNATURES[name][1][1 + len(lead)]
+        n0, n1 = C.c_int32(), C.c_int32()
+        self._check(f(self._h, *lead, None, 0, C.byref(n0), C.byref(n1), *tail))
+        out = np.zeros((n0.value, n1.value) + last, dtype=np.dtype(ptr._type_))
+        self._check(f(self._h, *lead, _p(out, ptr), out.size, C.byref(n0), C.byref(n1), *tail))
+        return out
+
+    def _gain_profile(self, name: str, kinds: int):
+        """(ms of each of the `kinds` launch kinds, flops) of the last call of one dense gain entry point"""
+        ms, flops = np.zeros(kinds), np.zeros(1)
+        self._check(getattr(self._lib, name)(self._h, _p(ms, _f64p), _p(flops, _f64p)))
+        return ms, float(flops[0])
+
+    def _gain_posterior_res(self, n: int, want_posterior: bool) -> dict:
+        nodes = self.problem.n_nodes
+        res = {"lnl": np.empty(n), "p_absent": np.empty((n, nodes)), "mean": np.empty((n, nodes)), "p_gain": np.empty((n, nodes)),
+               "p_loss": np.empty((n, nodes))}
+        if want_posterior:
+            res["posterior"] = np.empty((n, nodes, self.problem.matrix_size))
+        return res
 
     def comm_attach(self, comm_id: bytes, world_size: int, rank: int):
         """Join the RCCL communicator of the ranks holding the other family shards: from now on score() all-reduces
@@ -545,16 +560,7 @@ class Context:
         return out
 
     def family_results(self, K: int = 0):
-        F = self.n_families
-        fo = CafeFamilyOut()
-        res = {"family_lnl": np.empty(F), "failed": np.empty(F, dtype=np.int32)}
-        fo.family_lnl = _p(res["family_lnl"], _f64p)
-        fo.failed = _p(res["failed"], _i32p)
-        if K > 0:
-            res["category_likelihood"] = np.empty((F, K))
-            res["family_likelihood"] = np.empty(F)
-            fo.category_likelihood = _p(res["category_likelihood"], _f64p)
-            fo.family_likelihood = _p(res["family_likelihood"], _f64p)
+        res, fo = _family_results(self.n_families, K)
         self._check(self._lib.cafe_family_results(self._h, C.byref(fo)))
         return res
 
@@ -562,10 +568,7 @@ class Context:
         """cafe_score_per_family: lnL of every listed family under ITS OWN lambdas (lambdas[n][n_lambdas]; a 1-d array is
         one lambda per family).  -inf where score() would return +inf for that vector.  pr gives the prior and the error
         model; pr.lambdas is not read.  Base model only."""
-        fam = np.ascontiguousarray(family, dtype=np.int64).reshape(-1)
-        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(len(fam), -1)
-        if lam.shape[1] != self.problem.n_lambdas:
-            raise ValueError("lambdas must be [%d][%d]" % (len(fam), self.problem.n_lambdas))
+        fam, lam, _, _ = self._rate_frame(family, lambdas, rates=1)
         cp, keep = self._params(pr)
         out = np.empty(len(fam))
         self._check(self._lib.cafe_score_per_family(self._h, C.byref(cp), len(fam), _p(fam, _i64p), _p(lam, _f64p), _p(out, _f64p)))
@@ -575,11 +578,7 @@ class Context:
         """cafe_score_per_family_lm: lnL of every listed family under ITS OWN birth and death rates (lambdas and mus
         [n][n_lambdas]; 1-d arrays are one rate per family).  The context's death rates are not read.  Otherwise
         score_per_family."""
-        fam = np.ascontiguousarray(family, dtype=np.int64).reshape(-1)
-        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(len(fam), -1)
-        mu = np.ascontiguousarray(mus, dtype=np.float64).reshape(len(fam), -1)
-        if lam.shape[1] != self.problem.n_lambdas or mu.shape != lam.shape:
-            raise ValueError("lambdas and mus must be [%d][%d]" % (len(fam), self.problem.n_lambdas))
+        fam, lam, mu, _ = self._rate_frame(family, lambdas, mus, rates=2)
         cp, keep = self._params(pr)
         out = np.empty(len(fam))
         self._check(self._lib.cafe_score_per_family_lm(self._h, C.byref(cp), len(fam), _p(fam, _i64p), _p(lam, _f64p), _p(mu, _f64p),
@@ -590,154 +589,100 @@ class Context:
         """cafe_score_per_family_gain: lnL of every listed family under ITS OWN birth, death and gain rates (lambdas, mus and
         nus [n][n_lambdas]; 1-d arrays are one rate per family; mus None: mu = lambda), root sizes 0..R with mass root_absent
         at 0.  family may hold CAFE_FAMILY_ABSENT, the all-zero profile.  Otherwise score_per_family_lm."""
-        fam = np.ascontiguousarray(family, dtype=np.int64).reshape(-1)
-        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(len(fam), -1)
-        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(len(fam), -1)
-        mu = None if mus is None else np.ascontiguousarray(mus, dtype=np.float64).reshape(len(fam), -1)
-        if lam.shape[1] != self.problem.n_lambdas or nu.shape != lam.shape or (mu is not None and mu.shape != lam.shape):
-            raise ValueError("lambdas, mus and nus must be [%d][%d]" % (len(fam), self.problem.n_lambdas))
+        fam, lam, mu, nu = self._rate_frame(family, lambdas, mus, nus)
         cp, keep = self._params(pr)
         out = np.empty(len(fam))
-        self._check(self._lib.cafe_score_per_family_gain(self._h, C.byref(cp), len(fam), _p(fam, _i64p), _p(lam, _f64p),
-                                                         None if mu is None else _p(mu, _f64p), _p(nu, _f64p), float(root_absent), _p(out, _f64p)))
+        self._check(self._lib.cafe_score_per_family_gain(self._h, C.byref(cp), len(fam), _p(fam, _i64p), _p(lam, _f64p), _p(mu, _f64p),
+                                                         _p(nu, _f64p), float(root_absent), _p(out, _f64p)))
         return out
 
     def score_gain(self, pr: Params, family, lambdas, mus, nus, root_absent: float = 0.0) -> np.ndarray:
         """cafe_score_gain: lnL of every listed family under ONE set of birth, death and gain rates (lambdas, mus and nus
         [n_lambdas]; mus None: mu = lambda) on the dense prune: every matrix built once, the families pruned together with
         fp64 MFMA GEMMs.  family and root_absent as in score_per_family_gain, whose values these are to rounding."""
-        fam = np.ascontiguousarray(family, dtype=np.int64).reshape(-1)
-        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(-1)
-        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(-1)
-        mu = None if mus is None else np.ascontiguousarray(mus, dtype=np.float64).reshape(-1)
-        if len(lam) != self.problem.n_lambdas or nu.shape != lam.shape or (mu is not None and mu.shape != lam.shape):
-            raise ValueError("lambdas, mus and nus must be [%d]" % self.problem.n_lambdas)
+        fam, lam, mu, nu = self._rate_frame(family, lambdas, mus, nus, shared=True)
         cp, keep = self._params(pr)
         out = np.empty(len(fam))
-        self._check(self._lib.cafe_score_gain(self._h, C.byref(cp), _p(lam, _f64p), None if mu is None else _p(mu, _f64p), _p(nu, _f64p),
-                                              float(root_absent), len(fam), _p(fam, _i64p), _p(out, _f64p)))
+        self._check(self._lib.cafe_score_gain(self._h, C.byref(cp), _p(lam, _f64p), _p(mu, _f64p), _p(nu, _f64p), float(root_absent),
+                                              len(fam), _p(fam, _i64p), _p(out, _f64p)))
         return out
 
     def gain_dense_profile(self):
         """(HIP-event ms of the build, product, GEMM and root launches of the last score_gain -- 0 unless profiling was on --,
         the flops its GEMM launches issued)"""
-        ms, flops = np.zeros(4), np.zeros(1)
-        self._check(self._lib.cafe_debug_gain_dense(self._h, _p(ms, _f64p), _p(flops, _f64p)))
-        return ms, float(flops[0])
+        return self._gain_profile("cafe_debug_gain_dense", 4)
 
     def gain_posterior(self, pr: Params, families, lambdas, mus, nus, root_absent: float = 0.0, want_posterior: bool = False) -> dict:
         """cafe_gain_posterior: under the gain model, entry i = families[i] under its own (lambdas, mus, nus)[i] (the arguments
         of score_per_family_gain), for every node: p_absent = P(size = 0 | counts), mean, p_gain = P(parent absent, node present
         | counts), p_loss = P(parent present, node absent | counts) -- NaN at the root -- all [n][n_nodes], and lnl [n], the
         sum-rule lnL whatever the context's root rule is.  want_posterior adds posterior [n][n_nodes][matrix_size]."""
-        fam = np.ascontiguousarray(families, dtype=np.int64).reshape(-1)
-        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(len(fam), -1)
-        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(len(fam), -1)
-        mu = None if mus is None else np.ascontiguousarray(mus, dtype=np.float64).reshape(len(fam), -1)
-        if lam.shape[1] != self.problem.n_lambdas or nu.shape != lam.shape or (mu is not None and mu.shape != lam.shape):
-            raise ValueError("lambdas, mus and nus must be [%d][%d]" % (len(fam), self.problem.n_lambdas))
+        fam, lam, mu, nu = self._rate_frame(families, lambdas, mus, nus)
         cp, keep = self._params(pr)
-        n, nodes = len(fam), self.problem.n_nodes
-        res = {"lnl": np.empty(n), "p_absent": np.empty((n, nodes)), "mean": np.empty((n, nodes)), "p_gain": np.empty((n, nodes)),
-               "p_loss": np.empty((n, nodes))}
-        if want_posterior:
-            res["posterior"] = np.empty((n, nodes, self.problem.matrix_size))
-        out = CafeGainPosteriorOut()
-        for name, array in res.items():
-            setattr(out, name, _p(array, _f64p))
-        self._check(self._lib.cafe_gain_posterior(self._h, C.byref(cp), n, _p(fam, _i64p), _p(lam, _f64p), None if mu is None else _p(mu, _f64p),
-                                                  _p(nu, _f64p), float(root_absent), C.byref(out)))
+        res = self._gain_posterior_res(len(fam), want_posterior)
+        out = _out(CafeGainPosteriorOut, res)
+        self._check(self._lib.cafe_gain_posterior(self._h, C.byref(cp), len(fam), _p(fam, _i64p), _p(lam, _f64p), _p(mu, _f64p), _p(nu, _f64p),
+                                                  float(root_absent), C.byref(out)))
         return res
 
     def gain_posterior_dense(self, pr: Params, families, lambdas, mus, nus, root_absent: float = 0.0, want_posterior: bool = False) -> dict:
         """cafe_gain_posterior_dense: gain_posterior's dict for every listed family under ONE set of rates (lambdas, mus and nus
         [n_lambdas]; mus None: mu = lambda), on score_gain's dense prune and a down pass of fp64 MFMA GEMMs over the transposed
         matrices.  lnl is score_gain's under the sum rule bit for bit; the other values are gain_posterior's to rounding."""
-        fam = np.ascontiguousarray(families, dtype=np.int64).reshape(-1)
-        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(-1)
-        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(-1)
-        mu = None if mus is None else np.ascontiguousarray(mus, dtype=np.float64).reshape(-1)
-        if len(lam) != self.problem.n_lambdas or nu.shape != lam.shape or (mu is not None and mu.shape != lam.shape):
-            raise ValueError("lambdas, mus and nus must be [%d]" % self.problem.n_lambdas)
+        fam, lam, mu, nu = self._rate_frame(families, lambdas, mus, nus, shared=True)
         cp, keep = self._params(pr)
-        n, nodes = len(fam), self.problem.n_nodes
-        res = {"lnl": np.empty(n), "p_absent": np.empty((n, nodes)), "mean": np.empty((n, nodes)), "p_gain": np.empty((n, nodes)),
-               "p_loss": np.empty((n, nodes))}
-        if want_posterior:
-            res["posterior"] = np.empty((n, nodes, self.problem.matrix_size))
-        out = CafeGainPosteriorOut()
-        for name, array in res.items():
-            setattr(out, name, _p(array, _f64p))
-        self._check(self._lib.cafe_gain_posterior_dense(self._h, C.byref(cp), _p(lam, _f64p), None if mu is None else _p(mu, _f64p), _p(nu, _f64p),
-                                                        float(root_absent), n, _p(fam, _i64p), C.byref(out)))
+        res = self._gain_posterior_res(len(fam), want_posterior)
+        out = _out(CafeGainPosteriorOut, res)
+        self._check(self._lib.cafe_gain_posterior_dense(self._h, C.byref(cp), _p(lam, _f64p), _p(mu, _f64p), _p(nu, _f64p), float(root_absent),
+                                                        len(fam), _p(fam, _i64p), C.byref(out)))
         return res
 
     def gain_dense_posterior_profile(self):
         """(HIP-event ms of the build, product, GEMM, root, weights, transposed GEMM, interior output and leaf output launches of
         the last gain_posterior_dense -- 0 unless profiling was on --, the flops its two GEMMs issued)"""
-        ms, flops = np.zeros(8), np.zeros(1)
-        self._check(self._lib.cafe_debug_gain_dense_posterior(self._h, _p(ms, _f64p), _p(flops, _f64p)))
-        return ms, float(flops[0])
+        return self._gain_profile("cafe_debug_gain_dense_posterior", 8)
 
     def gain_leaf_predictive(self, pr: Params, families, lambdas, mus, nus, root_absent: float = 0.0) -> dict:
         """cafe_gain_leaf_predictive: under the gain model with ONE set of rates (score_gain's arguments), for every listed family
         and taxon the distribution of the taxon's count given the counts of every other species: mean, sd, p_below, p_obs and
         p_above [n][n_taxa] (columns as the problem's counts; the p's are the mass below, at and above the observed count, NaN
         for a missing cell) and lnl [n], score_gain's under the sum rule bit for bit."""
-        fam = np.ascontiguousarray(families, dtype=np.int64).reshape(-1)
-        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(-1)
-        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(-1)
-        mu = None if mus is None else np.ascontiguousarray(mus, dtype=np.float64).reshape(-1)
-        if len(lam) != self.problem.n_lambdas or nu.shape != lam.shape or (mu is not None and mu.shape != lam.shape):
-            raise ValueError("lambdas, mus and nus must be [%d]" % self.problem.n_lambdas)
+        fam, lam, mu, nu = self._rate_frame(families, lambdas, mus, nus, shared=True)
         cp, keep = self._params(pr)
         n, taxa = len(fam), self.problem.n_taxa
         res = {"lnl": np.empty(n)}
         res.update({key: np.empty((n, taxa)) for key in ("mean", "sd", "p_below", "p_obs", "p_above")})
-        out = CafeGainLeafPredictiveOut()
-        for name, array in res.items():
-            setattr(out, name, _p(array, _f64p))
-        self._check(self._lib.cafe_gain_leaf_predictive(self._h, C.byref(cp), _p(lam, _f64p), None if mu is None else _p(mu, _f64p), _p(nu, _f64p),
-                                                        float(root_absent), n, _p(fam, _i64p), C.byref(out)))
+        out = _out(CafeGainLeafPredictiveOut, res)
+        self._check(self._lib.cafe_gain_leaf_predictive(self._h, C.byref(cp), _p(lam, _f64p), _p(mu, _f64p), _p(nu, _f64p), float(root_absent),
+                                                        n, _p(fam, _i64p), C.byref(out)))
         return res
 
     def gain_predictive_profile(self):
         """(HIP-event ms of the build, product, GEMM, root, weights, transposed GEMM and fused leaf launches of the last
         gain_leaf_predictive -- 0 unless profiling was on --, the flops its three MFMA kernels issued)"""
-        ms, flops = np.zeros(7), np.zeros(1)
-        self._check(self._lib.cafe_debug_gain_predictive(self._h, _p(ms, _f64p), _p(flops, _f64p)))
-        return ms, float(flops[0])
+        return self._gain_profile("cafe_debug_gain_predictive", 7)
 
     def gain_marginal_dense(self, pr: Params, families, lambdas, mus, nus, root_absent: float = 0.0, level: float = 0.95) -> dict:
         """cafe_gain_marginal_dense: under the gain model with ONE set of rates (score_gain's arguments), for every listed family
         and node the posterior size as mean, mode (first arg max) and the equal-tailed interval lo..hi at `level`, and for the
         branch above the node p_increase, p_decrease and p_same = P(size(node) >, <, = size(parent) | counts), NaN at the root;
         all [n][n_nodes] (mode, lo, hi int32), and lnl [n], score_gain's under the sum rule bit for bit."""
-        fam = np.ascontiguousarray(families, dtype=np.int64).reshape(-1)
-        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(-1)
-        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(-1)
-        mu = None if mus is None else np.ascontiguousarray(mus, dtype=np.float64).reshape(-1)
-        if len(lam) != self.problem.n_lambdas or nu.shape != lam.shape or (mu is not None and mu.shape != lam.shape):
-            raise ValueError("lambdas, mus and nus must be [%d]" % self.problem.n_lambdas)
+        fam, lam, mu, nu = self._rate_frame(families, lambdas, mus, nus, shared=True)
         cp, keep = self._params(pr)
         n, nodes = len(fam), self.problem.n_nodes
         res = {"lnl": np.empty(n)}
         res.update({key: np.empty((n, nodes)) for key in ("mean", "p_increase", "p_decrease", "p_same")})
         res.update({key: np.empty((n, nodes), dtype=np.int32) for key in ("mode", "lo", "hi")})
-        out = CafeGainMarginalOut()
-        for name, array in res.items():
-            setattr(out, name, _p(array, _i32p if array.dtype == np.int32 else _f64p))
-        self._check(self._lib.cafe_gain_marginal_dense(self._h, C.byref(cp), _p(lam, _f64p), None if mu is None else _p(mu, _f64p), _p(nu, _f64p),
-                                                       float(root_absent), float(level), n, _p(fam, _i64p), C.byref(out)))
+        out = _out(CafeGainMarginalOut, res)
+        self._check(self._lib.cafe_gain_marginal_dense(self._h, C.byref(cp), _p(lam, _f64p), _p(mu, _f64p), _p(nu, _f64p), float(root_absent),
+                                                       float(level), n, _p(fam, _i64p), C.byref(out)))
         return res
 
     def gain_marginal_profile(self):
         """(HIP-event ms of the build, product, GEMM, root, weights, split GEMM, interior summary and leaf summary launches of the
         last gain_marginal_dense and their total -- 0 unless profiling was on --, the flops its MFMA kernels issued, the masked
         repeats of the split included)"""
-        ms, flops = np.zeros(9), np.zeros(1)
-        self._check(self._lib.cafe_debug_gain_marginal(self._h, _p(ms, _f64p), _p(flops, _f64p)))
-        return ms, float(flops[0])
+        return self._gain_profile("cafe_debug_gain_marginal", 9)
 
     def gain_score_gradient(self, pr: Params, families, lambdas, mus, nus, root_absent: float = 0.0) -> dict:
         """cafe_gain_score_gradient: under the gain model with ONE set of rates (score_gain's arguments), for every listed family
@@ -745,31 +690,22 @@ class Context:
         d_lambda is taken along mu = lambda) -- and per branch in alpha, beta and r = nu / lambda: d_alpha, d_beta, d_r
         [n][n_nodes], NaN at the root; lnl [n] is score_gain's under the sum rule bit for bit.  Plain fp64 whatever
         set_gain_scaling says."""
-        fam = np.ascontiguousarray(families, dtype=np.int64).reshape(-1)
-        lam = np.ascontiguousarray(lambdas, dtype=np.float64).reshape(-1)
-        nu = np.ascontiguousarray(nus, dtype=np.float64).reshape(-1)
-        mu = None if mus is None else np.ascontiguousarray(mus, dtype=np.float64).reshape(-1)
-        if len(lam) != self.problem.n_lambdas or nu.shape != lam.shape or (mu is not None and mu.shape != lam.shape):
-            raise ValueError("lambdas, mus and nus must be [%d]" % self.problem.n_lambdas)
+        fam, lam, mu, nu = self._rate_frame(families, lambdas, mus, nus, shared=True)
         cp, keep = self._params(pr)
         n, nodes = len(fam), self.problem.n_nodes
         res = {"lnl": np.empty(n)}
         res.update({key: np.empty((n, len(lam))) for key in ("d_lambda", "d_nu") + (() if mu is None else ("d_mu",))})
         res.update({key: np.empty((n, nodes)) for key in ("d_alpha", "d_beta", "d_r")})
-        out = CafeGainGradientOut()
-        for name, array in res.items():
-            setattr(out, name, _p(array, _f64p))
-        self._check(self._lib.cafe_gain_score_gradient(self._h, C.byref(cp), _p(lam, _f64p), None if mu is None else _p(mu, _f64p), _p(nu, _f64p),
-                                                       float(root_absent), n, _p(fam, _i64p), C.byref(out)))
+        out = _out(CafeGainGradientOut, res)
+        self._check(self._lib.cafe_gain_score_gradient(self._h, C.byref(cp), _p(lam, _f64p), _p(mu, _f64p), _p(nu, _f64p), float(root_absent),
+                                                       n, _p(fam, _i64p), C.byref(out)))
         return res
 
     def gain_gradient_profile(self):
         """(HIP-event ms of the build, product, GEMM, root, weights, transposed GEMM, interior score, leaf score, second outside
         GEMM, Toeplitz GEMM and leaf filter launches of the last gain_score_gradient and their total -- 0 unless profiling was
         on --, the flops its MFMA kernels issued)"""
-        ms, flops = np.zeros(12), np.zeros(1)
-        self._check(self._lib.cafe_debug_gain_gradient(self._h, _p(ms, _f64p), _p(flops, _f64p)))
-        return ms, float(flops[0])
+        return self._gain_profile("cafe_debug_gain_gradient", 12)
 
     def set_gain_scaling(self, on: bool):
         """cafe_set_gain_scaling: score_gain and gain_posterior_dense hold every likelihood panel as mantissas and one binary
@@ -786,9 +722,7 @@ class Context:
         res = {"mean": np.empty((F, n)), "mode": np.empty((F, n), dtype=np.int32), "lo": np.empty((F, n), dtype=np.int32),
                "hi": np.empty((F, n), dtype=np.int32), "p_increase": np.empty((F, n)), "p_decrease": np.empty((F, n)),
                "log_evidence": np.empty(F), "failed": np.empty(F, dtype=np.int32)}
-        mo = CafeMarginalOut()
-        for name, _ in CafeMarginalOut._fields_:
-            setattr(mo, name, _p(res[name], _i32p if res[name].dtype == np.int32 else _f64p))
+        mo = _out(CafeMarginalOut, res)
         self._check(self._lib.cafe_marginal_reconstruct(self._h, C.byref(cp), float(level), C.byref(mo)))
         return res
 
@@ -806,19 +740,14 @@ class Context:
             res["d_mu"] = np.empty((F, nl))
         if pr.multipliers is not None:
             res["d_multiplier"] = np.empty((F, len(pr.multipliers)))
-        go = CafeGradientOut()
-        for name, t in CafeGradientOut._fields_:
-            if name in res:
-                setattr(go, name, _p(res[name], t))
+        go = _out(CafeGradientOut, res)
         self._check(self._lib.cafe_score_gradient(self._h, C.byref(cp), int(rule), C.byref(go)))
         return res
 
     def branch_scores_dim(self, pr: Params) -> int:
         """cafe_branch_scores_dim: the length P of the score vector for pr's model and this context's death rates."""
         cp, keep = self._params(pr)
-        out = C.c_int32()
-        self._check(self._lib.cafe_branch_scores_dim(self._h, C.byref(cp), C.byref(out)))
-        return out.value
+        return self._scalars("cafe_branch_scores_dim", C.byref(cp))[0]
 
     def branch_scores(self, pr: Params, root_rule="max", alpha: float = 1.0, death_rates: Optional[bool] = None, per_family: bool = True,
                       gram: bool = True) -> dict:
@@ -840,26 +769,18 @@ class Context:
             res["rate"] = np.empty((F, n))
             if two:
                 res["birth"], res["death"] = np.empty((F, n)), np.empty((F, n))
-        n_used = np.zeros(1, dtype=np.int64)
         if gram:
             P = self.branch_scores_dim(pr)
-            res["total"], res["gram"] = np.empty(P), np.empty((P, P))
-        bo = CafeBranchScoresOut()
-        for name, t in CafeBranchScoresOut._fields_:
-            if name in res:
-                setattr(bo, name, _p(res[name], t))
-        if gram:
-            bo.n_used = _p(n_used, _i64p)
+            res["total"], res["gram"], res["n_used"] = np.empty(P), np.empty((P, P)), np.zeros(1, dtype=np.int64)
+        bo = _out(CafeBranchScoresOut, res)
         self._check(self._lib.cafe_branch_scores(self._h, C.byref(cp), int(rule), C.byref(bo)))
         if gram:
-            res["n_used"] = int(n_used[0])
+            res["n_used"] = int(res["n_used"][0])            # (the library writes one int64; the dict returns it as an int)
         return res
 
     def gram_stats(self):
         """(HIP-event ms of the Gram launches of the last branch_scores -- 0 unless profiling was on --, the flops of their MFMAs)"""
-        ms, fl = C.c_double(), C.c_double()
-        self._check(self._lib.cafe_debug_gram(self._h, C.byref(ms), C.byref(fl)))
-        return ms.value, fl.value
+        return tuple(self._scalars("cafe_debug_gram"))
 
     def expected_events(self, pr: Params, alpha: float = 1.0) -> dict:
         """cafe_expected_events: the expected number of births (gains) and of deaths (losses) on the branch above every node
@@ -868,9 +789,7 @@ class Context:
         cp, keep = self._params(pr, alpha)
         F, n = self.n_families, self.n_nodes
         res = {"gains": np.empty((F, n)), "losses": np.empty((F, n)), "log_evidence": np.empty(F), "failed": np.empty(F, dtype=np.int32)}
-        eo = CafeEventsOut()
-        for name, t in CafeEventsOut._fields_:
-            setattr(eo, name, _p(res[name], t))
+        eo = _out(CafeEventsOut, res)
         self._check(self._lib.cafe_expected_events(self._h, C.byref(cp), C.byref(eo)))
         return res
 
@@ -884,9 +803,7 @@ class Context:
         F, nt = self.n_families, self.problem.n_taxa
         res = {name: np.full((F, nt), np.nan) for name in ("mean", "sd", "p_below", "p_obs", "p_above")}
         res.update({"log_evidence": np.empty(F), "failed": np.empty(F, dtype=np.int32)})
-        lo = CafeLeafPredictiveOut()
-        for name, t in CafeLeafPredictiveOut._fields_:
-            setattr(lo, name, _p(res[name], t))
+        lo = _out(CafeLeafPredictiveOut, res)
         self._check(self._lib.cafe_leaf_predictive(self._h, C.byref(cp), C.byref(lo)))
         return res
 
@@ -904,18 +821,13 @@ class Context:
                "failed": np.empty(F, dtype=np.int32)}
         if pmf:
             res["pmf"] = np.empty((F, n, 2 * D + 1 if D >= 0 else 0))
-        co = CafeBranchChangeOut()
-        for name, t in CafeBranchChangeOut._fields_:
-            if name in res:
-                setattr(co, name, _p(res[name], t))
+        co = _out(CafeBranchChangeOut, res)
         self._check(self._lib.cafe_branch_change(self._h, C.byref(cp), D, float(level), C.byref(co)))
         return res
 
     def branch_change_band_ms(self):
         """summed HIP-event ms of the band kernel's launches of the last branch_change (0 unless profiling was on)"""
-        ms = C.c_double()
-        self._check(self._lib.cafe_debug_branch_change_band(self._h, C.byref(ms)))
-        return ms.value
+        return self._scalars("cafe_debug_branch_change_band")[0]
 
     def sample_histories(self, pr: Params, n_draws: int, seed: int, alpha: float = 1.0, sizes: bool = True) -> dict:
         """cafe_sample_histories: n_draws ancestral histories of every family from the posterior of marginal_reconstruct's
@@ -932,34 +844,21 @@ class Context:
                "log_evidence": np.empty(F), "failed": np.empty(F, dtype=np.int32)}
         if sizes:
             res["sizes"] = np.empty((rows, F, n), dtype=np.int32)
-        ho = CafeHistoryOut()
-        for name, t in CafeHistoryOut._fields_:
-            if name in res:
-                setattr(ho, name, _p(res[name], t))
+        ho = _out(CafeHistoryOut, res)
         self._check(self._lib.cafe_sample_histories(self._h, C.byref(cp), D, int(seed), C.byref(ho)))
         return res
 
     def history_batches(self):
         """(column batches, draw passes per batch) of the last sample_histories under the workspace budget"""
-        self._lib.cafe_debug_history_batches.restype = C.c_int
-        self._lib.cafe_debug_history_batches.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        nb, npass = C.c_int32(), C.c_int32()
-        self._check(self._lib.cafe_debug_history_batches(self._h, C.byref(nb), C.byref(npass)))
-        return nb.value, npass.value
+        return tuple(self._scalars("cafe_debug_history_batches"))
 
     def marginal_gemm_stats(self):
         """(summed HIP-event ms of the GEMM launches of the last marginal_reconstruct -- 0 unless profiling was on --, their flops)"""
-        ms, fl = C.c_double(), C.c_double()
-        self._check(self._lib.cafe_debug_marginal_gemm(self._h, C.byref(ms), C.byref(fl)))
-        return ms.value, fl.value
+        return tuple(self._scalars("cafe_debug_marginal_gemm"))
 
     def root_max(self, lambdas) -> np.ndarray:
         """max_j L_root[j] per family under the plain lambdas (p-value path, probability.cpp:313, :399)."""
-        lam = np.ascontiguousarray(lambdas, dtype=np.float64)
-        cp = CafeParams()
-        cp.model = CAFE_MODEL_BASE
-        cp.lambdas = _p(lam, _f64p)
-        cp.n_categories = 1
+        cp, lam = _base_params(lambdas)
         out = np.empty(self.n_families)
         self._check(self._lib.cafe_root_max(self._h, C.byref(cp), _p(out, _f64p)))
         return out
@@ -968,11 +867,7 @@ class Context:
         """compute_pvalues with the simulation on the device (probability.cpp:418): against the reference's own sample the
         agreement is statistical, not draw-for-draw; the device's sample itself is a function of the seed that
         tests/test_pvalues_replay.py replays draw for draw (tests/pvalues_ref.py) and checks stage by stage."""
-        lam = np.ascontiguousarray(lambdas, dtype=np.float64)
-        cp = CafeParams()
-        cp.model = CAFE_MODEL_BASE
-        cp.lambdas = _p(lam, _f64p)
-        cp.n_categories = 1
+        cp, lam = _base_params(lambdas)
         out = np.empty(self.n_families)
         self._check(self._lib.cafe_pvalues(self._h, C.byref(cp), n_simulations, seed, _p(out, _f64p)))
         return out
@@ -982,56 +877,36 @@ class Context:
         n_simulations: sizes int32 [n_nodes][Fs], counts int32 [n_taxa][Fs] (the simulated families' leaf counts as their
         context reads them), cond_unsorted / cond_sorted [R][n_simulations] (their root maxima either side of the sort),
         observed [n_families] (the root maxima of the listed families), pvalues [n_families]."""
-        f = self._lib.cafe_debug_pvalues_stages
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.POINTER(CafeParams), C.c_int32, C.c_uint64, C.POINTER(CafePvalueStages), _f64p]
-        lam = np.ascontiguousarray(lambdas, dtype=np.float64)
-        cp = CafeParams()
-        cp.model = CAFE_MODEL_BASE
-        cp.lambdas = _p(lam, _f64p)
-        cp.n_categories = 1
+        cp, lam = _base_params(lambdas)
         pb = self.problem
         Fs = max(0, self.R * n_simulations)                  # (an invalid n_simulations is refused before anything is written)
         res = {"sizes": np.full((self.n_nodes, Fs), -1, dtype=np.int32), "counts": np.full((pb.n_taxa, Fs), -1, dtype=np.int32),
                "cond_unsorted": np.full((self.R, max(0, n_simulations)), np.nan), "cond_sorted": np.full((self.R, max(0, n_simulations)), np.nan),
-               "observed": np.full(self.n_families, np.nan), "pvalues": np.full(self.n_families, np.nan)}
-        st = CafePvalueStages(_p(res["sizes"], _i32p), _p(res["counts"], _i32p), _p(res["cond_unsorted"], _f64p),
-                              _p(res["cond_sorted"], _f64p), _p(res["observed"], _f64p))
-        self._check(f(self._h, C.byref(cp), n_simulations, seed, C.byref(st), _p(res["pvalues"], _f64p)))
+               "observed": np.full(self.n_families, np.nan)}
+        st = _out(CafePvalueStages, res)
+        res["pvalues"] = np.full(self.n_families, np.nan)
+        self._check(self._lib.cafe_debug_pvalues_stages(self._h, C.byref(cp), n_simulations, seed, C.byref(st), _p(res["pvalues"], _f64p)))
         return res
 
     def reconstruct(self, lambdas, root_prior, multipliers=None) -> np.ndarray:
         """Pupko joint reconstruction -> int32 [K][n_families][n_nodes] (gene_family_reconstructor.cpp:13-165).
         root_prior[j] = compute(j), j = 0..min(M, R)."""
-        lam = np.ascontiguousarray(lambdas, dtype=np.float64)
+        cp, lam = _base_params(lambdas)
         rp = np.ascontiguousarray(root_prior, dtype=np.float32)
         if len(rp) < min(self.M, self.R) + 1:
             raise CafeError("root_prior needs min(M, R) + 1 entries")
-        cp = CafeParams()
-        cp.lambdas = _p(lam, _f64p)
-        K = 1
-        mult = None
         if multipliers is not None:
             mult = np.ascontiguousarray(multipliers, dtype=np.float64)
-            K = len(mult)
-            cp.model = CAFE_MODEL_GAMMA
-            cp.multipliers = _p(mult, _f64p)
-        else:
-            cp.model = CAFE_MODEL_BASE
-        cp.n_categories = K
-        out = np.empty((K, self.n_families, self.n_nodes), dtype=np.int32)
+            cp.model, cp.n_categories, cp.multipliers = CAFE_MODEL_GAMMA, len(mult), _p(mult, _f64p)
+        out = np.empty((cp.n_categories, self.n_families, self.n_nodes), dtype=np.int32)
         self._check(self._lib.cafe_reconstruct(self._h, C.byref(cp), _p(rp, _f32p), _p(out, _i32p)))
         return out
 
     def branch_probabilities(self, lambdas, sizes) -> np.ndarray:
         """compute_viterbi_sum for every (family, node); NaN = invalid (gene_family_reconstructor.cpp:361-400)."""
-        lam = np.ascontiguousarray(lambdas, dtype=np.float64)
+        cp, lam = _base_params(lambdas)
         sz = np.ascontiguousarray(sizes, dtype=np.int32)
         assert sz.shape == (self.n_families, self.n_nodes)
-        cp = CafeParams()
-        cp.model = CAFE_MODEL_BASE
-        cp.lambdas = _p(lam, _f64p)
-        cp.n_categories = 1
         out = np.empty((self.n_families, self.n_nodes))
         self._check(self._lib.cafe_branch_probabilities(self._h, C.byref(cp), _p(sz, _i32p), _p(out, _f64p)))
         return out
@@ -1073,8 +948,6 @@ class Context:
 
     def column_extents(self, node: int, category: int = 0) -> np.ndarray:
         """Per-column zero extents [columns][2] of an interior non-root node's panel in the last call (diagnostic)."""
-        self._lib.cafe_debug_column_extents.restype = C.c_int
-        self._lib.cafe_debug_column_extents.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _i32p, C.c_size_t, C.POINTER(C.c_int64)]
         out = np.zeros((self.n_families + 256, 2), dtype=np.int32)
         n = C.c_int64()
         self._check(self._lib.cafe_debug_column_extents(self._h, node, category, _p(out, _i32p), out.size, C.byref(n)))
@@ -1083,20 +956,11 @@ class Context:
     def panel_bounds(self, node: int, category: int = 0) -> np.ndarray:
         """Magnitude bounds [tiles][row steps] of an interior non-root node's panel in the last call: an upper bound of log2 of
         every computed entry of rows 4 r .. 4 r + 3 of a 128-column tile, -inf where all are zero (cafe_debug_panel_bounds)."""
-        f = self._lib.cafe_debug_panel_bounds
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _f64p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        nt, nr = C.c_int32(), C.c_int32()
-        self._check(f(self._h, node, category, None, 0, C.byref(nt), C.byref(nr)))
-        out = np.zeros((nt.value, nr.value), dtype=np.float64)
-        self._check(f(self._h, node, category, _p(out, _f64p), out.size, C.byref(nt), C.byref(nr)))
-        return out
+        return self._sized("cafe_debug_panel_bounds", (node, category))
 
     def set_level_tiles(self, tiles: int) -> None:
         """Column tiles per workgroup of the per-level interval / bound kernel in the following calls: 1, 2 or 4, 0 = chosen per
         level (cafe_debug_level_tiles).  Diagnostic: nothing the library returns depends on it."""
-        self._lib.cafe_debug_level_tiles.restype = C.c_int
-        self._lib.cafe_debug_level_tiles.argtypes = [C.c_void_p, C.c_int]
         self._check(self._lib.cafe_debug_level_tiles(self._h, tiles))
 
     def magnitude_tables(self, which: str, node: int, category: int = 0) -> np.ndarray:
@@ -1104,47 +968,26 @@ class Context:
         of 1/256 of log2, MAG_NONE where everything the entry stands for is zero): "a16" [k-steps][16-row blocks] and "t4"
         [k-steps][row steps] of an interior branch, "lt" [counts 0 .. M][row steps] of a leaf branch
         (cafe_debug_magnitude_tables)."""
-        f = self._lib.cafe_debug_magnitude_tables
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _i32p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32]
-        w = {"a16": 0, "t4": 1, "lt": 2}[which]
-        n0, n1 = C.c_int32(), C.c_int32()
-        self._check(f(self._h, w, -1, None, 0, C.byref(n0), C.byref(n1), node, category))
-        out = np.zeros((n0.value, n1.value), dtype=np.int32)
-        self._check(f(self._h, w, -1, _p(out, _i32p), out.size, C.byref(n0), C.byref(n1), node, category))
-        return out
+        return self._sized("cafe_debug_magnitude_tables", ({"a16": 0, "t4": 1, "lt": 2}[which], -1), tail=(node, category))
 
     def k_ranges(self, node: int, category: int = 0) -> np.ndarray:
         """K ranges [tiles][16-row blocks][2] (first / last k-step, 4 deep; first > last: none) of the K2 op of the branch above
         an interior non-root node in the last call (cafe_debug_k_ranges)."""
-        f = self._lib.cafe_debug_k_ranges
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _i32p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        nt, nb = C.c_int32(), C.c_int32()
-        self._check(f(self._h, node, category, None, 0, C.byref(nt), C.byref(nb)))
-        out = np.zeros((nt.value, nb.value, 2), dtype=np.int32)
-        self._check(f(self._h, node, category, _p(out, _i32p), out.size, C.byref(nt), C.byref(nb)))
-        return out
+        return self._sized("cafe_debug_k_ranges", (node, category), last=(2,))
 
     def narrowed_extents(self, node: int, category: int = 0) -> np.ndarray:
         """Narrowed hulls [tiles][2] of an interior non-root node's panel in the last call: the structural hull of each
         128-column tile cut back over the rows the magnitude bounds prove to be computed zeros (first > last: the whole tile);
         the structural hulls themselves under CAFE_NO_NARROW=1 or without bounds (cafe_debug_narrowed_extents)."""
-        f = self._lib.cafe_debug_narrowed_extents
-        f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _i32p, C.c_size_t, C.POINTER(C.c_int32)]
         out = np.zeros(((self.n_families + 256) // 128 + 2, 2), dtype=np.int32)
         nt = C.c_int32()
-        self._check(f(self._h, node, category, _p(out, _i32p), out.size, C.byref(nt)))
+        self._check(self._lib.cafe_debug_narrowed_extents(self._h, node, category, _p(out, _i32p), out.size, C.byref(nt)))
         return out[:nt.value]
 
     def leaf_transposes(self):
         """(leaf branches with a transposed copy of their matrix for the assemble passes, whether the last call used them)."""
-        self._lib.cafe_debug_leaf_transposes.restype = C.c_int
-        self._lib.cafe_debug_leaf_transposes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        n, used = C.c_int32(), C.c_int32()
-        self._check(self._lib.cafe_debug_leaf_transposes(self._h, C.byref(n), C.byref(used)))
-        return n.value, bool(used.value)
+        n, used = self._scalars("cafe_debug_leaf_transposes")
+        return n, bool(used)
 
     def launch_flops(self):
         """Per K2 launch of the last call: (executed flops, flops over all K tiles, tile height in 16-row blocks)."""
@@ -1156,34 +999,20 @@ class Context:
     def plan_check(self):
         """(launches of the last call that ran from planned tile lists, worst modelled workgroup load / mean); raises when a
         list does not cover its launch's tiles exactly once with the K ranges the extents give."""
-        n, w = C.c_int32(), C.c_double()
-        self._lib.cafe_debug_plan_check.restype = C.c_int
-        self._lib.cafe_debug_plan_check.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
-        self._check(self._lib.cafe_debug_plan_check(self._h, C.byref(n), C.byref(w)))
-        return n.value, w.value
+        return tuple(self._scalars("cafe_debug_plan_check"))
 
     def executed_flops(self) -> float:
         """Flops the K2 launches of the last call really ran (K tiles outside matrix extent x panel extent are skipped)."""
-        v = C.c_double()
-        self._check(self._lib.cafe_executed_flops(self._h, C.byref(v)))
-        return v.value
+        return self._scalars("cafe_executed_flops")[0]
 
     def issued_flops(self) -> float:
         """Flops of the MFMAs the K2 launches of the last call issued: executed_flops() less the k-steps whose products
         underflow below the smallest denormal (cafe_issued_flops)."""
-        self._lib.cafe_issued_flops.restype = C.c_int
-        self._lib.cafe_issued_flops.argtypes = [C.c_void_p, _f64p]
-        v = C.c_double()
-        self._check(self._lib.cafe_issued_flops(self._h, C.byref(v)))
-        return v.value
+        return self._scalars("cafe_issued_flops")[0]
 
     def tile_range_flops(self) -> float:
         """The same with every row block of a tile counted over the tile's whole K range (cafe_debug_tile_range_flops)."""
-        self._lib.cafe_debug_tile_range_flops.restype = C.c_int
-        self._lib.cafe_debug_tile_range_flops.argtypes = [C.c_void_p, _f64p]
-        v = C.c_double()
-        self._check(self._lib.cafe_debug_tile_range_flops(self._h, C.byref(v)))
-        return v.value
+        return self._scalars("cafe_debug_tile_range_flops")[0]
 
     def debug_stamps(self, words: int) -> np.ndarray:
         out = np.zeros(words, dtype=np.uint64)
@@ -1235,14 +1064,10 @@ class Context:
                "failed": np.empty(F, dtype=np.int32)}
         if pr.multipliers is not None:
             res["category_posterior"] = np.empty((F, len(pr.multipliers)))
-        n_used = np.zeros(1, dtype=np.int64)
-        ro = CafeRootPosteriorOut()
-        for name, t in CafeRootPosteriorOut._fields_:
-            if name in res:
-                setattr(ro, name, _p(res[name], t))
-        ro.n_used = _p(n_used, _i64p)
+        res["n_used"] = np.zeros(1, dtype=np.int64)
+        ro = _out(CafeRootPosteriorOut, res)
         self._check(self._lib.cafe_root_posterior(self._h, C.byref(cp), C.byref(ro)))
-        res["n_used"] = int(n_used[0])
+        res["n_used"] = int(res["n_used"][0])                # (as in branch_scores)
         return res
 
     def set_graphs(self, on: bool):
@@ -1300,16 +1125,7 @@ class Sharded:
         return out.value, self.family_results(len(pr.multipliers) if pr.multipliers is not None else 0)
 
     def family_results(self, K: int = 0):
-        F = self.n_families
-        fo = CafeFamilyOut()
-        res = {"family_lnl": np.empty(F), "failed": np.empty(F, dtype=np.int32)}
-        fo.family_lnl = _p(res["family_lnl"], _f64p)
-        fo.failed = _p(res["failed"], _i32p)
-        if K > 0:
-            res["category_likelihood"] = np.empty((F, K))
-            res["family_likelihood"] = np.empty(F)
-            fo.category_likelihood = _p(res["category_likelihood"], _f64p)
-            fo.family_likelihood = _p(res["family_likelihood"], _f64p)
+        res, fo = _family_results(self.n_families, K)
         self._check(self._lib.cafe_sharded_family_results(self._h, C.byref(fo)))
         return res
 
@@ -1329,49 +1145,35 @@ def build_matrices(n: int, lambdas, ts, device: int = 0, layout: int = 0) -> np.
     lam = np.ascontiguousarray(lambdas, dtype=np.float64)
     t = np.ascontiguousarray(ts, dtype=np.float64)
     out = np.empty((len(lam), n, n))
-    rc = load().cafe_build_matrices(device, n, len(lam), _p(lam, _f64p), _p(t, _f64p), layout, _p(out, _f64p))
-    if rc:
-        raise CafeError("cafe_build_matrices failed with code %d" % rc)
+    _call("cafe_build_matrices", device, n, len(lam), _p(lam, _f64p), _p(t, _f64p), layout, _p(out, _f64p))
     return out
 
 
 def debug_sort_rows(values, device: int = 0) -> np.ndarray:
     """cafe_debug_sort_rows: every row of values [rows][n] sorted ascending by cafe_pvalues' sort kernel, launched as it
     launches it; returns a new array."""
-    L = load()
-    L.cafe_debug_sort_rows.restype = C.c_int
-    L.cafe_debug_sort_rows.argtypes = [C.c_int32, _f64p, C.c_int32, C.c_int32]
     out = np.array(values, dtype=np.float64, order="C")
     if out.ndim != 2:
         raise ValueError("values must be [rows][n]")
-    rc = L.cafe_debug_sort_rows(device, _p(out, _f64p), out.shape[0], out.shape[1])
-    if rc:
-        raise CafeError("cafe_debug_sort_rows failed with code %d" % rc)
+    _call("cafe_debug_sort_rows", device, _p(out, _f64p), out.shape[0], out.shape[1])
     return out
 
 
 def debug_tree_pvalue(observed, cond, device: int = 0) -> np.ndarray:
     """cafe_debug_tree_pvalue: cafe_pvalues' p-value kernel on observed [F] and cond [R][n] (rows sorted ascending)."""
-    L = load()
-    L.cafe_debug_tree_pvalue.restype = C.c_int
-    L.cafe_debug_tree_pvalue.argtypes = [C.c_int32, _f64p, C.c_int64, _f64p, C.c_int32, C.c_int32, _f64p]
     obs = np.ascontiguousarray(observed, dtype=np.float64)
     c = np.ascontiguousarray(cond, dtype=np.float64)
     if obs.ndim != 1 or c.ndim != 2:
         raise ValueError("observed must be [F] and cond [R][n]")
     out = np.full(len(obs), np.nan)
-    rc = L.cafe_debug_tree_pvalue(device, _p(obs, _f64p), len(obs), _p(c, _f64p), c.shape[0], c.shape[1], _p(out, _f64p))
-    if rc:
-        raise CafeError("cafe_debug_tree_pvalue failed with code %d" % rc)
+    _call("cafe_debug_tree_pvalue", device, _p(obs, _f64p), len(obs), _p(c, _f64p), c.shape[0], c.shape[1], _p(out, _f64p))
     return out
 
 
 def bd_rates(lam: float, mu: float, t: float):
     """cafe_bd_rates: (alpha, beta, zero) of the quantized key (lambda, mu, t).  Host code: needs no GPU."""
     out = np.empty(3)
-    rc = load().cafe_bd_rates(float(lam), float(mu), float(t), _p(out, _f64p))
-    if rc:
-        raise CafeError("cafe_bd_rates failed with code %d" % rc)
+    _call("cafe_bd_rates", float(lam), float(mu), float(t), _p(out, _f64p))
     return float(out[0]), float(out[1]), bool(out[2])
 
 
@@ -1379,9 +1181,7 @@ def bd_gain_row0(lam: float, mu: float, nu: float, t: float, n: int):
     """cafe_bd_gain_row0: (row 0 of the gain model's matrix for the quantized key, columns 0..n-1; r = nu / lambda).  Host
     code: needs no GPU."""
     out, r = np.empty(int(n)), np.empty(1)
-    rc = load().cafe_bd_gain_row0(float(lam), float(mu), float(nu), float(t), int(n), _p(out, _f64p), _p(r, _f64p))
-    if rc != 0:
-        raise CafeError("cafe_bd_gain_row0 failed with code %d" % rc)
+    _call("cafe_bd_gain_row0", float(lam), float(mu), float(nu), float(t), int(n), _p(out, _f64p), _p(r, _f64p))
     return out, float(r[0])
 
 
@@ -1389,9 +1189,7 @@ def bd_rates_grad(lam: float, mu: float, t: float):
     """cafe_bd_rates_grad: (d alpha / d lambda, d alpha / d mu, d beta / d lambda, d beta / d mu) at the quantized key
     (lambda, mu, t).  Host code: needs no GPU."""
     out = np.empty(4)
-    rc = load().cafe_bd_rates_grad(float(lam), float(mu), float(t), _p(out, _f64p))
-    if rc:
-        raise CafeError("cafe_bd_rates_grad failed with code %d" % rc)
+    _call("cafe_bd_rates_grad", float(lam), float(mu), float(t), _p(out, _f64p))
     return tuple(float(x) for x in out)
 
 
@@ -1403,9 +1201,7 @@ def weighted_gram(S, w, device: int = 0):
     if w.shape != (n,):
         raise ValueError("w must have one entry per column of S")
     gram, total = np.empty((p, p)), np.empty(p)
-    rc = load().cafe_weighted_gram(int(device), p, n, _p(S, _f64p), _p(w, _f64p), _p(gram, _f64p), _p(total, _f64p))
-    if rc != 0:
-        raise CafeError("cafe_weighted_gram failed with code %d" % rc)
+    _call("cafe_weighted_gram", int(device), p, n, _p(S, _f64p), _p(w, _f64p), _p(gram, _f64p), _p(total, _f64p))
     return gram, total
 
 
@@ -1413,9 +1209,7 @@ def bd_rates_events(lam: float, mu: float, t: float):
     """cafe_bd_rates_events: (da, db, dc) of the births tag, then (da, db, dc) of the deaths tag, at the quantized key
     (lambda, mu, t).  Host code: needs no GPU."""
     out = np.empty(6)
-    rc = load().cafe_bd_rates_events(float(lam), float(mu), float(t), _p(out, _f64p))
-    if rc:
-        raise CafeError("cafe_bd_rates_events failed with code %d" % rc)
+    _call("cafe_bd_rates_events", float(lam), float(mu), float(t), _p(out, _f64p))
     return tuple(float(x) for x in out)
 
 
@@ -1427,9 +1221,7 @@ def build_matrices_lm(n: int, lambdas, mus, ts, device: int = 0, layout: int = 0
     if not (lam.shape == mu.shape == t.shape):
         raise ValueError("lambdas, mus and ts must have the same length")
     out = np.empty((len(lam), n, n))
-    rc = load().cafe_build_matrices_lm(device, n, len(lam), _p(lam, _f64p), _p(mu, _f64p), _p(t, _f64p), layout, _p(out, _f64p))
-    if rc:
-        raise CafeError("cafe_build_matrices_lm failed with code %d" % rc)
+    _call("cafe_build_matrices_lm", device, n, len(lam), _p(lam, _f64p), _p(mu, _f64p), _p(t, _f64p), layout, _p(out, _f64p))
     return out
 
 
@@ -1438,11 +1230,7 @@ def _simulate(call, pb: Problem, lambdas, max_family_size: int, root_size, seed:
     """What simulate and simulate_lm share: the cafe_sim_problem block and the outputs.  call(problem, seed, leaf, nodes, err,
     errlen) is the C entry, with whatever else it takes already bound."""
     keep = []
-
-    def k(a, dt):
-        a = np.ascontiguousarray(a, dtype=dt)
-        keep.append(a)
-        return a
+    k = _keeper(keep)
     lam = k(np.atleast_1d(lambdas), np.float64)
     roots = k(root_size, np.int32).reshape(-1)
     F = len(roots)
@@ -1508,7 +1296,5 @@ def simulate_lm(pb: Problem, lambdas, mus, max_family_size: int, root_size, seed
 
 def probe_fp64_mfma(device: int = 0) -> float:
     v = C.c_double()
-    rc = load().cafe_probe_fp64_mfma(device, C.byref(v))
-    if rc:
-        raise CafeError("cafe_probe_fp64_mfma failed with code %d" % rc)
+    _call("cafe_probe_fp64_mfma", device, C.byref(v))
     return v.value

@@ -21,10 +21,7 @@ for _ in range(3):
 ex, al, mi = ctx.launch_flops()
 st = ctx.stats()
 ms = np.zeros(len(ex))
-lib = capi.load()
-lib.cafe_debug_launch_ms.restype = C.c_int
-lib.cafe_debug_launch_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_size_t]
-lib.cafe_debug_launch_ms(ctx._h, ms.ctypes.data_as(C.POINTER(C.c_double)), len(ms))
+ctx._lib.cafe_debug_launch_ms(ctx._h, ms.ctypes.data_as(C.POINTER(C.c_double)), len(ms))
 cols = al / (2.0 * 720 * 721 * 8)
 order = np.argsort(cols)
 print("launch  ~cols  mi  executed/all  ms      TF/s(executed)")
